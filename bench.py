@@ -31,8 +31,13 @@ final trajectory in the end-to-end leg.  `python bench.py --gpus N` on its own
 starts those N ranks itself (a child process tree, before this process touches
 the GPU); a world size that is not --gpus is an error, never an N = 1 line.
 
-The timed region of K steps is repeated (at least 5 regions, at least ~0.6 s of
-GPU work in total): `value` is the median region, min / max are beside it.
+The headline is one timed region of exactly K steps (`ms_per_step` = that
+region / K); the other legs repeat their regions (at least 5, at least ~0.6 s
+of GPU work in total) and report the median, min / max beside it.
+
+  --dump-outputs DIR   after the timed steps, write what the headline step
+               computed in its last step (the match lists a caller of
+               viso_batch_get_matches receives) as DIR/*.npy, float32
 """
 import argparse
 import concurrent.futures
@@ -233,6 +238,33 @@ def cpu_baseline(seq, st, tm, budget_s):
                                     f"single threaded), {t_all:.1f} s", "nproc": len(os.sched_getaffinity(0))}}
 
 
+DUMP_BYTES_MAX = 64 << 20
+MATCH_KINDS = ("stereo", "temporal_left", "temporal_right")   # viso_batch_get_matches `which` 0, 1, 2
+
+
+def dump_matcher_outputs(out_dir, batch, nf, rank, world):
+    """The matcher step's results as its caller receives them: for each kind and frame t the (i1, i2, dist) triples of
+    viso_batch_get_matches (temporal kinds from t = 1).  Written per kind as <kind>_matches.npy [M, 4] float32 rows
+    (t, i1, i2, dist) in frame order, plus <kind>_counts.npy, one count per frame of frames.npy (every value is an
+    integer below 2^24: exact in float32).  Above 64 MB in all, frames.npy is a fixed seeded sample of the frames."""
+    lists = {k: [batch.matches(w, t) if (w == 0 or t >= 1) else np.zeros((0, 3), np.int32) for t in range(nf)]
+             for w, k in enumerate(MATCH_KINDS)}
+    total = sum(4 * (4 * len(m) + 1) for ls in lists.values() for m in ls)
+    frames = np.arange(nf)
+    if total > DUMP_BYTES_MAX:
+        keep = max(1, int(nf * DUMP_BYTES_MAX / total))
+        frames = np.sort(np.random.default_rng(12345).choice(nf, keep, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    prefix = f"rank{rank}_" if world > 1 else ""
+    np.save(os.path.join(out_dir, f"{prefix}frames.npy"), frames.astype(np.float32))
+    for k, ls in lists.items():
+        rows = [np.concatenate([np.full((len(ls[t]), 1), t, np.int64), ls[t].astype(np.int64)], 1) for t in frames]
+        m = np.concatenate(rows, 0) if rows else np.zeros((0, 4), np.int64)
+        assert m.size == 0 or int(np.abs(m).max()) < (1 << 24)
+        np.save(os.path.join(out_dir, f"{prefix}{k}_matches.npy"), m.astype(np.float32))
+        np.save(os.path.join(out_dir, f"{prefix}{k}_counts.npy"), np.array([len(ls[t]) for t in frames], np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -271,11 +303,15 @@ def main():
     ap.add_argument("--drop-in-frames", type=int, default=256, help="frame pairs of the per-call drop-in leg")
     ap.add_argument("--ab-variants", default="", help="matcher variants timed by --ab (default: all of the build)")
     ap.add_argument("--ab", action="store_true", help="also time the other matcher variants, interleaved, same process")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the match lists of the headline leg's last timed step to DIR/*.npy (float32, <= 64 MB)")
     args = ap.parse_args()
 
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` on its own: start the N ranks as a child process tree.  Nothing in this process
         # has touched the GPU (torch is not imported yet), and it is a child, not an exec.
@@ -437,8 +473,11 @@ def main():
     sync_all()
     for _, b in lanes:
         b.kernel_timing(True)
-    dts_m = timed_regions(lambda b: b.run_matcher(), args.steps, 0)
-    dt = float(np.median(dts_m))
+    # exactly --steps timed steps: one region, not repeated (the other legs below repeat theirs)
+    dts_m = [timed(lambda b: b.run_matcher(), args.steps, 0)]
+    dt = dts_m[0]
+    if args.dump_outputs:
+        dump_matcher_outputs(args.dump_outputs, lanes[(args.steps - 1) % n_streams][1], nf, rank, world)
     kern_ms_sum, kern_n = 0.0, 0
     for _, b in lanes:
         ms, n = b.kernel_ms()
@@ -883,8 +922,8 @@ def main():
             "value": fps, "unit": "frames/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
             "value_spread": fps_spread,
-            "timing": f"the {args.steps}-step region (barrier + synchronize on both sides, max over ranks) repeated "
-                      f"{fps_spread['regions']} times after the warm-up; value / ms_per_step = the median region",
+            "timing": f"one region of exactly {args.steps} steps after the warm-up (barrier + synchronize on both sides, "
+                      "max over ranks); value / ms_per_step = that region",
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "u16", "data": "synthetic",
             "config": {"workload": workload_name(args),

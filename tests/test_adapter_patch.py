@@ -1,30 +1,23 @@
-"""adapters/libviso_hip.patch must apply to the reference tree, leave it untouched when VISO_USE_HIP is not defined, and
+"""adapters/libviso_hip.patch must fit the reference tree, leave it untouched when VISO_USE_HIP is not defined, and
 with the macro swap exactly the hot-path functions for adapters/viso_hip_adapter.inc.  The reference
-itself cannot be compiled in this image (no OpenCV / Boost), so this is a source-level check: `git apply --check` on a
-scratch copy, then the two preprocessor views of the patched files.  Skipped where /root/reference does not exist (the
-GPU box)."""
+itself cannot be compiled here (no OpenCV / Boost), so this is a source-level check of the two preprocessor views of the
+patched files.  The reference is not part of this repository: its src/viso.cpp and src/viso.h are stood in for by
+tests/golden/reference_layout.json (made by tests/golden/make_reference_layout.py from a checkout of the reference),
+which gives their line counts, the lines of their conditional directives and the lines of the definitions and call
+sites named below.  The patch is applied to a placeholder file of that shape, one numbered placeholder per reference
+line, so that every surviving reference line can be told by its number."""
+import json
 import os
 import re
-import shutil
-import subprocess
-import sys
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
 PATCH = os.path.join(ROOT, "adapters", "libviso_hip.patch")
 ADAPTER = os.path.join(ROOT, "adapters", "viso_hip_adapter.inc")
+LAYOUT = os.path.join(ROOT, "tests", "golden", "reference_layout.json")
 
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "src")), reason="reference tree not present")
-
-REPLACED = {   # function -> first line of its definition in the reference's viso.cpp
-    "tr2mat": r"^tr2mat\(vector<double> tr,Mat& Tr\)",
-    "match_circle": r"^match_circle\(const Matches& match_lr, const Matches& match_lr_prev,",
-    "match_desc": r"^match_desc\(const KeyPoints& kp1, const KeyPoints& kp2,",
-    "ransac_minimize_reproj": r"^ransac_minimize_reproj\(const Mat& X, /\* 3d points \*/",
-    "minimize_reproj": r"^minimize_reproj\(const Mat& X, const Mat& observe, vector<double>& tr,",
-}
+REPLACED = ("tr2mat", "match_circle", "match_desc", "ransac_minimize_reproj", "minimize_reproj")   # anchors def_<name>
 
 
 def view(text, defined):
@@ -49,58 +42,132 @@ def view(text, defined):
     return "".join(out)
 
 
+def parse_patch(text):
+    """{file: [(old_start, old_count, new_start, new_count, [hunk lines])]} of a unified diff."""
+    files, hunks, lines = {}, None, text.splitlines()
+    i = 0
+    while i < len(lines):
+        ln = lines[i]
+        if ln.startswith("--- a/"):
+            assert lines[i + 1].startswith("+++ b/")
+            hunks = files.setdefault(lines[i + 1][len("+++ b/"):], [])
+            i += 2
+            continue
+        m = re.match(r"@@ -(\d+)(?:,(\d+))? \+(\d+)(?:,(\d+))? @@", ln)
+        if m:
+            hunks.append((int(m[1]), int(m[2] or 1), int(m[3]), int(m[4] or 1), []))
+        else:
+            hunks[-1][4].append(ln)
+        i += 1
+    return files
+
+
+def _kind(line):
+    s = line.strip()
+    return "if" if re.match(r"#\s*if", s) else "endif" if re.match(r"#\s*endif", s) else None
+
+
+def placeholder_file(info):
+    """One line per reference line: its conditional directives keep their kind, every line carries its number."""
+    ifs, endifs = set(info["if"]), set(info["endif"])
+    return [("#if " if n in ifs else "#endif " if n in endifs else "") + f"/*@ref {n}*/"
+            for n in range(1, info["lines"] + 1)]
+
+
+def apply_hunks(old, hunks):
+    """The patched file.  The hunks' positions must agree with the reference's length, and every context line must
+    fall on a reference line of the same kind (directive or not)."""
+    new, pos = [], 0
+    for a, b, c, d, body in hunks:
+        start = a - 1 if b else a
+        assert pos <= start <= len(old)
+        new += old[pos:start]
+        pos = start
+        assert len(new) == (c - 1 if d else c)
+        for ln in body:
+            tag, txt = (ln[:1] or " "), ln[1:]
+            assert tag in " +", "the patch removes no reference line"
+            if tag == " ":
+                assert pos < len(old) and _kind(txt) == _kind(old[pos]), (a, ln)
+                new.append(old[pos])
+                pos += 1
+            else:
+                new.append(txt)
+        assert pos == start + b and len(new) == (c - 1 if d else c) + d
+    return new + old[pos:]
+
+
 @pytest.fixture(scope="module")
-def patched(tmp_path_factory):
-    dst = str(tmp_path_factory.mktemp("ref") / "libviso")
-    shutil.copytree(REF, dst)
-    r = subprocess.run(["git", "apply", "--check", PATCH], cwd=dst, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    r = subprocess.run(["git", "apply", PATCH], cwd=dst, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return dst
+def layout():
+    with open(LAYOUT) as f:
+        lay = json.load(f)
+    assert not any(info["mentions_VISO_USE_HIP"] for info in lay["files"].values())
+    return lay
 
 
-def _read(root, rel):
-    return open(os.path.join(root, rel), encoding="utf-8", errors="surrogateescape").read()
+@pytest.fixture(scope="module")
+def patched(layout):
+    """{file: (reference placeholder lines, patched lines)} for src/viso.cpp and src/viso.h."""
+    files = parse_patch(open(PATCH).read())
+    out = {}
+    for rel, info in layout["files"].items():
+        old = placeholder_file(info)
+        out[rel] = (old, apply_hunks(old, files[rel]))
+    return out
 
 
-def test_patch_is_what_the_generator_writes():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "make_adapter_patch.py"), REF], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    assert r.stdout == open(PATCH).read()
+def _text(lines):
+    return "".join(ln + "\n" for ln in lines)
+
+
+def _ref_positions(lines):
+    """reference line number -> index in `lines`, for the reference lines that survived."""
+    out = {}
+    for i, ln in enumerate(lines):
+        m = re.search(r"/\*@ref (\d+)\*/", ln)
+        if m:
+            out[int(m[1])] = i
+    return out
 
 
 def test_without_the_macro_the_tree_is_the_reference(patched):
     for rel in ("src/viso.cpp", "src/viso.h"):
-        assert view(_read(patched, rel), defined=False) == _read(REF, rel), rel
-    # every other source file is untouched
-    for rel in ("src/kitti.cpp", "src/mvg.cpp", "src/mvg.h", "src/estimation.cpp", "src/estimation.h", "src/misc.h", "test/test.cpp"):
-        assert _read(patched, rel) == _read(REF, rel), rel
+        old, new = patched[rel]
+        assert view(_text(new), defined=False) == _text(old), rel
+    # every other source file is untouched (src/CMakeLists.txt only gains the VISO_USE_HIP option)
+    assert sorted(parse_patch(open(PATCH).read())) == ["src/CMakeLists.txt", "src/viso.cpp", "src/viso.h"]
 
 
-def test_with_the_macro_the_hot_path_comes_from_the_adapter(patched):
-    cpp = view(_read(patched, "src/viso.cpp"), defined=True)
-    lines = cpp.splitlines()
-    for name, rx in REPLACED.items():
-        assert not [ln for ln in lines if re.match(rx, ln)], f"the reference's {name} is still compiled"
+def test_with_the_macro_the_hot_path_comes_from_the_adapter(layout, patched):
+    anchor = {k: v["lines"] for k, v in layout["anchors"].items()}
+    assert all(v["file"] == "src/viso.cpp" for v in layout["anchors"].values())
+    lines = view(_text(patched["src/viso.cpp"][1]), defined=True).splitlines()
+    kept = _ref_positions(lines)
+    for name in REPLACED:
+        assert len(anchor["def_" + name]) == 1, name
+        assert not [n for n in anchor["def_" + name] if n in kept], f"the reference's {name} is still compiled"
     # collect_matches: the (.., Mat &x) overload is gone, the other two stay
-    cm = [i for i, ln in enumerate(lines) if ln.startswith("collect_matches(const KeyPoints& kp1, const KeyPoints &kp2,")]
-    assert len(cm) == 2 and not any("Mat &x)" in lines[i + 1] for i in cm)
+    cm, cm_x = anchor["def_collect_matches"], anchor["def_collect_matches_x"]
+    assert len(cm) == 3 and len(cm_x) == 1 and cm_x[0] in cm
+    assert cm_x[0] not in kept and all(n in kept for n in cm if n != cm_x[0])
     # the adapter: once, behind both triangulate_rectified templates (an explicit specialisation needs its primary
     # template), in front of sequence_odometry (its first use), where MatchParams and kp2mat are visible
     inc = [i for i, ln in enumerate(lines) if ln.strip() == '#include "viso_hip_adapter.inc"']
     assert len(inc) == 1
-    pos = lambda rx: [i for i, ln in enumerate(lines) if re.match(rx, ln)]
-    assert max(pos(r"^triangulate_rectified\(const Mat& x,")) < inc[0] < pos(r"^sequence_odometry\(const Mat& P1")[0]
-    assert pos(r"^struct MatchParams")[0] < inc[0] and pos(r"^kp2mat\(const KeyPoints& kp\)")[0] < inc[0]
+    pos = lambda name: [kept[n] for n in anchor[name]]
+    assert len(anchor["def_triangulate_rectified"]) == 2
+    assert max(pos("def_triangulate_rectified")) < inc[0] < pos("def_sequence_odometry")[0]
+    assert pos("def_struct_MatchParams")[0] < inc[0] and pos("def_kp2mat")[0] < inc[0]
     # the call sites are the reference's own, unchanged (5-argument match_desc needs the adapter's default argument)
-    assert sum("match_desc(kp1,kp1_prev,d1,d1_prev,match11);" in ln for ln in lines) == 1
+    assert len(anchor["call_match_desc_match11"]) == 1 and anchor["call_match_desc_match11"][0] in kept
+    assert not any("match_desc(kp1,kp1_prev,d1,d1_prev,match11);" in ln for ln in lines)   # no added call site
     # RANSAC stream key = the frame's FILE NUMBER (what viso_kitti / kitti_shard key on), read off the generator
     assert sum("param.frame_index = images.index() - 1;" in ln for ln in lines) == 1
-    h = view(_read(patched, "src/viso.h"), defined=True)
+    h = view(_text(patched["src/viso.h"][1]), defined=True)
     assert "unsigned long long ransac_seed = 0, frame_index = 0;" in h
     assert "int index() const { return m_index; }" in h
-    assert "VISO_USE_HIP" in _read(patched, "src/CMakeLists.txt")
+    cmake = parse_patch(open(PATCH).read())["src/CMakeLists.txt"]
+    assert any("VISO_USE_HIP" in ln for h_ in cmake for ln in h_[4] if ln.startswith("+"))
 
 
 def test_adapter_defines_each_replacement_once():

@@ -1,4 +1,7 @@
-"""adapters/viso_hip_adapter.inc through a C++ front end.
+#!/usr/bin/env python3
+"""adapters/viso_hip_adapter.inc through a C++ front end, against a checkout of the reference:
+
+    python tools/check_adapter_compiles.py <checkout of alexkreimer/libviso>
 
 The adapter is compiled by a libviso maintainer INSIDE the reference's src/viso.cpp, against OpenCV
 and Boost — neither exists in this image, so until now no compiler had ever seen it.  Here the translation unit is
@@ -8,19 +11,19 @@ templates (patched src/viso.cpp) — are CUT FROM THE PATCHED REFERENCE AT TEST 
 names they and the adapter use come from tests/adapter_stub/cv_boost_stub.hpp (a type stub, nothing is executed), then
 `#include "viso_hip_adapter.inc"` exactly as the patch places it, then callers with the reference's call-site argument
 types (src/viso.cpp:1240,1264,1275,1282,1245-1247,1313,1316).  `g++ -std=c++11 -fsyntax-only -Wall -Werror`.
-This is a type check of the adapter, not an oracle.  Skipped where /root/reference does not exist (the GPU box)."""
+This is a type check of the adapter, not an oracle.  It needs the reference's text, which is not part of this
+repository, so it is a maintainer's tool rather than a test (tests/test_adapter_patch.py checks the patch itself from
+tests/golden/reference_layout.json)."""
 import os
 import re
+import pathlib
 import shutil
 import subprocess
-
-import pytest
+import sys
+import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
 PATCH = os.path.join(ROOT, "adapters", "libviso_hip.patch")
-
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "src")), reason="reference tree not present")
 
 
 def _block(lines, start_rx, end_rx, start_from=0):
@@ -50,7 +53,7 @@ static void use_everything(const Mat& P_F) {
 '''
 
 
-def test_adapter_type_checks_in_the_patched_reference(tmp_path):
+def check(REF, tmp_path):
     dst = str(tmp_path / "libviso")
     shutil.copytree(REF, dst)
     r = subprocess.run(["git", "apply", PATCH], cwd=dst, capture_output=True, text=True)
@@ -91,3 +94,11 @@ def test_adapter_type_checks_in_the_patched_reference(tmp_path):
     cmd2 = cmd2[:-1] + [str(bad_dir), str(src)]   # the "-I" that pointed at adapters/ now takes the broken copy's directory
     r = subprocess.run(cmd2, capture_output=True, text=True)
     assert r.returncode != 0 and "viso_tr2mat" in r.stderr
+
+
+if __name__ == "__main__":
+    if len(sys.argv) != 2 or not os.path.isdir(os.path.join(sys.argv[1], "src")):
+        raise SystemExit(__doc__)
+    with tempfile.TemporaryDirectory() as tmp:
+        check(sys.argv[1], pathlib.Path(tmp))
+    print("adapter type-checks in the patched reference; a broken call inside it does not")
