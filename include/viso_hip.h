@@ -404,6 +404,44 @@ int viso_batch_kernel_ms(viso_batch* b, double* matcher_ms_avg, int* n_launches)
 int viso_batch_stamp(viso_batch* b, int which);
 int viso_batch_stamp_ms(viso_batch* b, double ms[2]);
 
+/* ------------------------------------------------ sub-pixel stereo refinement (opt-in; NOT in the reference)
+ *
+ * Every stereo correspondence of the reference is an integer pixel pair (Harris keypoints are Point2f(int,int),
+ * src/viso.cpp:967), and collect_matches / triangulate_rectified turn that integer disparity straight into depth
+ * (:501-514, :1137-1162).  With this on, the right-image point of every stereo match is refined to sub-pixel precision
+ * by a parabola through the descriptor-window SADs at the match and its two neighbours.  Definition, for a stereo row
+ * (i1, i2, dist) of frame t as viso_batch_get_matches(b, 0, t, ...) returns it:
+ *   p = (cvRound(kp1[i1].x), cvRound(kp1[i1].y)), q = (cvRound(kp2[i2].x), cvRound(kp2[i2].y))   (rounding half to even,
+ *       as MyFeatureExtractor, src/viso.cpp:1013);
+ *   W_L(p) = the left descriptor window, W_R(x, y) = the right image's window at (x, y): exactly viso_extract_descriptors
+ *       (Sobel-x with BORDER_REFLECT_101, 11x11, each pixel zeroed where y<=0 | y>=rows | x<=0 | x>=cols) at that point;
+ *   Sx(d) = SAD(W_L(p), W_R(q.x+d, q.y)), Sy(d) = SAD(W_L(p), W_R(q.x, q.y+d)), d in {-1, 0, +1}: int32, exact
+ *       (Sx(0) = Sy(0) = the row's dist);
+ *   off(S-, S0, S+) = (double)(S- - S+) / (2.0 * (double)(S- + S+ - 2*S0)) when S0 <= S-, S0 <= S+ and S- + S+ - 2*S0 > 0,
+ *       else 0 (so |off| <= 1/2); IEEE double, no contraction;
+ *   uR' = (float)((double)q.x + off(Sx)); vR' = (float)((double)q.y + off(Sy)) in mode 2, (float)q.y in mode 1.
+ * The left point is not changed.  Modes: 0 = off (the default), 1 = horizontal only (disparity), 2 = horizontal and vertical.
+ *
+ * In a batch (image-in runs only), subpixel_refine_kernel refines every frame's final stereo list once per run, and the circle
+ * join takes the right-image observation of x_c (rows 2-3) from frame t's refined point of the joined stereo row and
+ * triangulates Xp_c with frame t-1's refined uR.  Match lists, the circle join's rows and the RANSAC stream key (seed,
+ * first_frame + t) are those of mode 0; poses are not comparable with the reference's.  Mode 0 runs exactly the kernels
+ * and arithmetic of the reference path. */
+
+/* mode 0, 1 or 2 for the batch's next runs.  viso_batch_run_images (matcher_only included) then refines; viso_batch_run /
+ * viso_batch_run_matcher (descriptor-in frames: no images to refine on) return VISO_ERR_ARG while mode != 0, and the batch
+ * stays usable. */
+int viso_batch_set_subpixel(viso_batch* b, int mode);
+/* The refined points of frame t's stereo rows from the last run: uv [n][2] float (uR', vR'), in the order of
+ * viso_batch_get_matches(b, 0, t, ...); *out_n = n.  VISO_ERR_ARG when the last run refined nothing (mode 0, or a
+ * descriptor-in run).  Synchronises like the other getters. */
+int viso_batch_get_subpixel(viso_batch* b, int t, float* uv, int* out_n);
+/* The same refinement for host pointers on the default context (single calls, tests): imgL / imgR rows x cols uint8,
+ * kp1 n1 x 2, kp2 n2 x 2 float (x,y), match n x 3 int32 (i1, i2, dist) with 0 <= i1 < n1, 0 <= i2 < n2; mode 1 or 2.
+ * out_uv: n x 2 float (uR', vR') per row of match. */
+int viso_refine_stereo_subpixel(const uint8_t* imgL, const uint8_t* imgR, int rows, int cols, const float* kp1, int n1,
+                                const float* kp2, int n2, const int32_t* match, int n, int mode, float* out_uv);
+
 #ifdef __cplusplus
 }
 #endif

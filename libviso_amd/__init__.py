@@ -16,7 +16,7 @@ import weakref
 
 import numpy as np
 
-from .abi import (DESC_LEN, MatchParams, Param, declare_common, f32p, f64p, i32p, i64p, intp, ptr)
+from .abi import (DESC_LEN, MatchParams, Param, declare_common, declare_subpixel, f32p, f64p, i32p, i64p, intp, ptr)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("VISO_HIP_SO") or os.path.join(_HERE, "libviso_hip.so")   # VISO_HIP_SO: another build of the library (A/B runs)
@@ -112,6 +112,8 @@ def load():
     L.viso_batch_run_images.argtypes = [C.c_void_p, C.c_int]
     L.viso_batch_detect.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double]
     L.viso_batch_get_keypoints.argtypes = [C.c_void_p, C.c_int, C.c_int, f32p, intp]
+    if hasattr(L, "viso_batch_set_subpixel"):   # (absent from older builds of the library: VISO_HIP_SO A/B runs)
+        declare_subpixel(L)
     L.viso_harris_response.argtypes = [C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_double, f32p]
     L.viso_detect_harris_binned.argtypes = [C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                             C.c_double, f32p, f32p, intp]
@@ -374,6 +376,26 @@ def extract_descriptors(img, kp, radius=5):
     return d
 
 
+def refine_stereo_subpixel(imgL, imgR, kp1, kp2, match, mode=1):
+    """viso_refine_stereo_subpixel: the opt-in sub-pixel refinement of stereo matches (not in the reference;
+    include/viso_hip.h).  match: (n, 3) int32 rows (i1, i2, dist) into kp1 / kp2; mode 1 (horizontal) or 2 (both axes).
+    Returns (n, 2) float32 refined right-image points (uR', vR')."""
+    L = load()
+    imgL = np.ascontiguousarray(imgL, dtype=np.uint8)
+    imgR = np.ascontiguousarray(imgR, dtype=np.uint8)
+    if imgL.shape != imgR.shape or imgL.ndim != 2:
+        raise ValueError("refine_stereo_subpixel: the two images must be 2-D and of one size")
+    kp1, kp2 = _f32(kp1).reshape(-1, 2), _f32(kp2).reshape(-1, 2)
+    match = _i32(match).reshape(-1, 3)
+    out = np.empty((max(len(match), 1), 2), np.float32)
+    r = L.viso_refine_stereo_subpixel(ptr(imgL, C.c_uint8), ptr(imgR, C.c_uint8), imgL.shape[0], imgL.shape[1],
+                                      ptr(kp1, C.c_float), len(kp1), ptr(kp2, C.c_float), len(kp2),
+                                      ptr(match, C.c_int32), len(match), int(mode), ptr(out, C.c_float))
+    if r != 1:
+        _err("viso_refine_stereo_subpixel", r)
+    return out[:len(match)].copy()
+
+
 HARRIS_K = float(np.float32(0.04))   # the reference's intended default (float k = .04, src/viso.cpp:915)
 
 
@@ -516,6 +538,17 @@ class Batch:
 
     def run_images(self, matcher_only=False):
         self._chk("viso_batch_run_images", self.L.viso_batch_run_images(self.h, int(matcher_only)))
+
+    def set_subpixel(self, mode):
+        """viso_batch_set_subpixel: 0 = off (default), 1 = refine the stereo matches' uR, 2 = uR and vR (image-in runs only)."""
+        self._chk("viso_batch_set_subpixel", self.L.viso_batch_set_subpixel(self.h, int(mode)))
+
+    def subpixel(self, t):
+        """(n, 2) float32 refined (uR', vR') of frame t's stereo rows from the last run, in the order of matches(0, t)."""
+        out = np.empty((self.cap, 2), np.float32)
+        n = C.c_int(0)
+        self._chk("viso_batch_get_subpixel", self.L.viso_batch_get_subpixel(self.h, t, ptr(out, C.c_float), C.byref(n)))
+        return out[:n.value].copy()
 
     def set_params(self, stereo, temporal, param, seed=0, first_frame=0):
         self._chk("viso_batch_set_params", self.L.viso_batch_set_params(

@@ -125,3 +125,12 @@ def declare_common(lib, prefix):
     fn("F_from_P", None, [f64p, f64p, f64p])
     fn("extract_descriptors", C.c_int, [u8p, C.c_int, C.c_int, f32p, C.c_int, C.c_int, f32p])
     return MP, PP
+
+
+def declare_subpixel(lib):
+    """Prototypes of the opt-in sub-pixel stereo refinement (include/viso_hip.h; libviso_hip.so only)."""
+    u8p = C.POINTER(C.c_uint8)
+    lib.viso_batch_set_subpixel.argtypes = [C.c_void_p, C.c_int]
+    lib.viso_batch_get_subpixel.argtypes = [C.c_void_p, C.c_int, f32p, intp]
+    lib.viso_refine_stereo_subpixel.argtypes = [u8p, u8p, C.c_int, C.c_int, f32p, C.c_int, f32p, C.c_int, i32p, C.c_int,
+                                                C.c_int, f32p]

@@ -9,6 +9,7 @@
 //   res     [3][nf][cap] int2            per query (target | -1, SAD)
 //   sorted  [3][nf][cap][3] int          match lists in (dist,i1) order; pos = inverse
 //   x_c [nf][4][cap], Xp_c [nf][3][cap]   double, SoA rows like cv::Mat(4,M): the solver's inputs, written by the circle join
+//   uv  [nf][cap] float2                 refined right-image points per stereo row (viso_batch_set_subpixel != 0 only)
 // `which` = 0 stereo L->R of frame t, 1 temporal left (t vs t-1), 2 temporal right.
 #include "common.h"
 
@@ -34,6 +35,9 @@ struct viso_batch {
     int* tile_flag; int tiles;   // [3][nf][tiles] per-64-query-tile scratch of the stereo kernels
     int2* res; int* sorted; int* pos; int* m_cnt; int* ovf_cnt; unsigned long long* scored; size_t zeroed_bytes;
     double *x_c, *Xp_c;          // the solver's inputs: gathered + triangulated by the circle join
+    // opt-in sub-pixel refinement of the stereo observations (subpixel.hip): the mode asked for, the buffer (allocated on the first
+    // request), and the mode the last run refined with (0: the last run produced no refined points)
+    int subpix = 0; float2* uv = nullptr; int uv_mode = 0;
     JoinItem* join; SolverItem* sitems;
     int *circ, *pcl, *mc;
     double* tr_h; int *ok_h, *cnt_h, *hq; char* rot;   // hq: list of undecided hypotheses (launch_ransac)
@@ -138,7 +142,7 @@ int viso_batch_free(viso_batch* b, bool keep_shell) {
     void* ptrs[] = {b->h_part, b->h_resp, b->h_tmp_kp, b->h_tmp_resp, b->h_cnt, b->images, b->skp, b->sidx, b->rank, b->bstart, b->xinfo, b->views,
                     b->kp, b->desc, b->n, b->packed, b->packed8, b->r8cnt, b->sums, b->zero, b->probs, b->res, b->sorted,
                     b->pos, b->m_cnt, b->scored, b->x_c, b->Xp_c, b->join,
-                    b->sitems, b->circ, b->pcl, b->mc, b->tr /* + ok, n_inl */, b->inl, b->tr_h, b->ok_h, b->cnt_h, b->hq, b->samp_h, b->rot, b->tile_flag, b->qord, b->ovf_q};
+                    b->sitems, b->circ, b->pcl, b->mc, b->uv, b->tr /* + ok, n_inl */, b->inl, b->tr_h, b->ok_h, b->cnt_h, b->hq, b->samp_h, b->rot, b->tile_flag, b->qord, b->ovf_q};
     for (void* p : ptrs) if (p) note(hipFree(p));
     if (keep_shell) { b->ctx = nullptr; b->events.clear(); b->desc_family.clear(); b->desc_family.shrink_to_fit(); }
     else delete b;
@@ -205,6 +209,7 @@ static int build_items(viso_batch* b) {
             j.kp1 = img_kp(t, 0); j.kp2 = img_kp(t, 1); j.kp1p = img_kp(t - 1, 0); j.kp2p = img_kp(t - 1, 1);
             j.circ = b->circ + (size_t)t * cap * 4; j.pcl = b->pcl + (size_t)t * cap * 2; j.mc = b->mc + t;
             j.x_c = b->x_c + (size_t)t * 4 * cap; j.Xp_c = b->Xp_c + (size_t)t * 3 * cap; j.ldc = cap;
+            j.uv = b->uv ? b->uv + (size_t)t * cap : nullptr; j.uvp = b->uv ? b->uv + (size_t)(t - 1) * cap : nullptr;
         }
         HIP_TRY(hipMemcpy(b->join, J.data(), sizeof(JoinItem) * J.size(), hipMemcpyHostToDevice));
     }
@@ -503,6 +508,11 @@ static int run_matcher_impl(viso_batch* b, bool from_images) {
         viso_set_error("viso_batch_run_images: no images uploaded (or descriptor length is not 121)");
         return VISO_ERR_ARG;
     }
+    if (!from_images && b->subpix) {
+        viso_set_error("viso_batch_run: sub-pixel refinement (viso_batch_set_subpixel %d) needs the images: use viso_batch_run_images, "
+                       "or set mode 0 for descriptor-in runs", b->subpix);
+        return VISO_ERR_ARG;
+    }
     if (!from_images) {   // f32 rows and int16 rows share one device buffer: a run over frames of both families would
                           // reinterpret one of them (garbage matches, no error) -- refuse it
         bool f32 = false, i16 = false;
@@ -564,6 +574,14 @@ static int run_matcher_impl(viso_batch* b, bool from_images) {
     }
     if ((r = launch_match_timed(s, b->probs, b->n_probs, b->cap, b->dlen, b->mp, b->bad_any, e0, e1, 1, b->ctx->matcher_variant, b->ovf_q, b->ovf_cnt, r8s, from_images ? 0 : 1)) < 0) return r;
     if ((r = launch_sort(s, b->probs, b->n_probs, b->cap)) < 0) return r;
+    b->uv_mode = 0;
+    if (from_images && b->subpix) {   // the stereo lists are final: refine their right-image points (which = 0 lists come first)
+        const size_t per = (size_t)b->img_rows * b->img_cols;
+        if ((r = launch_subpixel(s, b->images, 2 * per, per, b->img_rows, b->img_cols, b->kp, 2 * (size_t)b->cap, b->cap, b->sorted,
+                                 3 * (size_t)b->cap, b->m_cnt, b->nf, b->subpix, b->uv, b->packed, 2 * (size_t)b->cap * VISO_ROW, b->rank,
+                                 2 * (size_t)b->cap)) < 0) return r;
+        b->uv_mode = b->subpix;
+    }
     if (b->stamps) HIP_TRY(hipEventRecord(b->ev_stamp[2], s));   // re-recorded behind the solver by run_rest
     return VISO_OK;
 }
@@ -598,6 +616,7 @@ extern "C" int viso_batch_stamp_ms(viso_batch* b, double ms[2]) {
 extern "C" int viso_batch_run_matcher(viso_batch* b) { return run_matcher_impl(b, false); }
 
 static int run_rest(viso_batch* b);
+static bool slot_ok(viso_batch* b, int which, int t);
 
 extern "C" int viso_batch_run(viso_batch* b) {
     int r = run_matcher_impl(b, false);
@@ -700,6 +719,34 @@ extern "C" int viso_batch_get_keypoints(viso_batch* b, int t, int side, float* k
     return VISO_OK;
 }
 
+// Opt-in sub-pixel refinement of the stereo observations (not in the reference; subpixel.hip).  The buffer of the refined points
+// is allocated on the first request, and the join items are rebuilt to point at it (after the batch's work in flight).
+extern "C" int viso_batch_set_subpixel(viso_batch* b, int mode) {
+    if (dead(b) || mode < 0 || mode > 2) { viso_set_error("viso_batch_set_subpixel: bad argument (mode 0, 1 or 2)"); return VISO_ERR_ARG; }
+    int r;
+    if ((r = enter(b)) < 0) return r;
+    if (mode && !b->uv) {
+        if ((r = batch_sync(b)) < 0) return r;
+        if ((r = dalloc(&b->uv, (size_t)b->nf * b->cap)) < 0) return r;
+        if ((r = build_items(b)) < 0) return r;
+    }
+    b->subpix = mode;
+    return VISO_OK;
+}
+
+// The refined (uR', vR') of frame t's stereo rows, in the order of viso_batch_get_matches(b, 0, t).
+extern "C" int viso_batch_get_subpixel(viso_batch* b, int t, float* uv, int* out_n) {
+    if (!slot_ok(b, 0, t) || !out_n) { viso_set_error("viso_batch_get_subpixel: bad argument"); return VISO_ERR_ARG; }
+    { const int rs_ = batch_sync(b); if (rs_ < 0) return rs_; }
+    if (!b->uv_mode) { viso_set_error("viso_batch_get_subpixel: the last run refined nothing (mode 0, or not viso_batch_run_images)"); return VISO_ERR_ARG; }
+    int m = 0;
+    HIP_TRY(hipMemcpy(&m, b->m_cnt + t, sizeof(int), hipMemcpyDeviceToHost));
+    if (m > b->cap) m = b->cap;
+    if (m > 0 && uv) HIP_TRY(hipMemcpy(uv, b->uv + (size_t)t * b->cap, sizeof(float2) * (size_t)m, hipMemcpyDeviceToHost));
+    *out_n = m;
+    return VISO_OK;
+}
+
 static int run_rest(viso_batch* b) {
     int r;
     if ((r = enter(b)) < 0) return r;
@@ -708,7 +755,7 @@ static int run_rest(viso_batch* b) {
     // the circle join rewrites what the previous run's RANSAC reads (x_c, Xp_c, mc)
     if (ss != s && b->ransac_pending) HIP_TRY(hipStreamWaitEvent(s, b->ev_ransac, 0));
     if (b->nf > 1) {
-        if ((r = launch_circle_join(s, b->join, b->nf - 1, b->sp)) < 0) return r;         // :1245-1247 (the rows it joins), :1282, 1292-1305
+        if ((r = launch_circle_join(s, b->join, b->nf - 1, b->sp, b->uv_mode != 0)) < 0) return r;   // :1245-1247 (the rows it joins), :1282, 1292-1305
         if (ss != s) {
             HIP_TRY(hipEventRecord(b->ev_join, s));
             HIP_TRY(hipStreamWaitEvent(ss, b->ev_join, 0));

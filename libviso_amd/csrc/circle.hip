@@ -191,8 +191,12 @@ int launch_circle_table(hipStream_t s, const CircleArgs& a, int* tab, int tabn) 
 // collect_matches of the joined stereo match of frame t (:501-514), Xp_c column = triangulate_rectified<double> of the
 // joined stereo match of frame t-1 (:1137-1162, no clamp) — the same expressions, evaluated only for the rows the
 // solver will read, so the batch path needs no collect / triangulate launch of its own.
+// circle_join_subpixel_kernel (viso_batch_set_subpixel != 0): the right-image observation of x_c (rows 2-3) is the refined point of the joined stereo
+// row of frame t, uv[pcl[0]], and Xp_c is triangulated with the refined uR of frame t-1's row, uvp[pcl[1]]; the left points and
+// everything else as without it.
 #define CIRC_NCH 8   // chunks of CIRC_THREADS stereo matches whose lookups are in flight together
-__global__ __launch_bounds__(CIRC_THREADS) void circle_join_kernel(const JoinItem* items, int n_items, SolverParamsDev sp) {
+template <bool SUBPIX>
+__device__ __forceinline__ void circle_join_body(const JoinItem* items, int n_items, const SolverParamsDev& sp) {
     __shared__ int s_tot[CIRC_NCH][CIRC_THREADS / 64];
     if ((int)blockIdx.x >= n_items) return;
     const JoinItem J = items[blockIdx.x];
@@ -258,10 +262,10 @@ __global__ __launch_bounds__(CIRC_THREADS) void circle_join_kernel(const JoinIte
                 J.circ[4 * oc + 0] = ileft[c]; J.circ[4 * oc + 1] = iright[c];
                 J.circ[4 * oc + 2] = ileft_prev[c]; J.circ[4 * oc + 3] = iright_prev[c];
                 J.pcl[2 * oc + 0] = r; J.pcl[2 * oc + 1] = k[c];
-                const float2 a1 = J.kp1[ileft[c]], a2 = J.kp2[iright[c]];
+                const float2 a1 = J.kp1[ileft[c]], a2 = SUBPIX ? J.uv[r] : J.kp2[iright[c]];
                 J.x_c[0 * J.ldc + oc] = (double)a1.x; J.x_c[1 * J.ldc + oc] = (double)a1.y;
                 J.x_c[2 * J.ldc + oc] = (double)a2.x; J.x_c[3 * J.ldc + oc] = (double)a2.y;
-                const float2 p1 = J.kp1p[ileft_prev[c]], p2 = J.kp2p[iright_prev[c]];
+                const float2 p1 = J.kp1p[ileft_prev[c]], p2 = SUBPIX ? J.uvp[k[c]] : J.kp2p[iright_prev[c]];
                 const double uL = p1.x, vL = p1.y, uR = p2.x;
                 const double d = uL - uR;                       // src/viso.cpp:1148-1151, no clamp
                 J.Xp_c[0 * J.ldc + oc] = sp.base * (uL - sp.cu) / d;
@@ -272,10 +276,17 @@ __global__ __launch_bounds__(CIRC_THREADS) void circle_join_kernel(const JoinIte
     }
     if (threadIdx.x == 0) *J.mc = running;
 }
+__global__ __launch_bounds__(CIRC_THREADS) void circle_join_kernel(const JoinItem* items, int n_items, SolverParamsDev sp) {
+    circle_join_body<false>(items, n_items, sp);
+}
+__global__ __launch_bounds__(CIRC_THREADS) void circle_join_subpixel_kernel(const JoinItem* items, int n_items, SolverParamsDev sp) {
+    circle_join_body<true>(items, n_items, sp);
+}
 
-int launch_circle_join(hipStream_t s, const JoinItem* items_dev, int n_items, const SolverParamsDev& sp) {
+int launch_circle_join(hipStream_t s, const JoinItem* items_dev, int n_items, const SolverParamsDev& sp, bool subpixel) {
     if (n_items <= 0) return VISO_OK;
-    hipLaunchKernelGGL(circle_join_kernel, dim3(n_items), dim3(CIRC_THREADS), 0, s, items_dev, n_items, sp);
+    if (subpixel) hipLaunchKernelGGL(circle_join_subpixel_kernel, dim3(n_items), dim3(CIRC_THREADS), 0, s, items_dev, n_items, sp);
+    else hipLaunchKernelGGL(circle_join_kernel, dim3(n_items), dim3(CIRC_THREADS), 0, s, items_dev, n_items, sp);
     HIP_TRY(hipGetLastError());
     return VISO_OK;
 }

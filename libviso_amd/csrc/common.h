@@ -395,6 +395,8 @@ struct JoinItem {
                                              // computed in the join itself (src/viso.cpp:501-514, 1137-1162, 1292-1305)
     int* circ; int* pcl; int* mc;            // outputs
     double* x_c; double* Xp_c; int ldc;      // 4 x ldc, 3 x ldc
+    const float2* uv; const float2* uvp;     // refined right-image points of frame t / t-1 per stereo row (viso_batch_set_subpixel;
+                                             // read by circle_join_subpixel_kernel only)
 };
 
 struct TriItem {
@@ -411,7 +413,7 @@ int launch_ransac(hipStream_t s, const SolverItem* items_dev, int n_items, int i
                   unsigned long long seed, const SolverParamsDev& sp, int* queue, int split, int max_points,
                   const RefitMirror* mir = nullptr, const OutArgs* ride = nullptr, int ride_blocks = 0);
 size_t viso_rot_bytes(int iters);   // bytes of SolverItem::rot
-int launch_circle_join(hipStream_t s, const JoinItem* items_dev, int n_items, const SolverParamsDev& sp);
+int launch_circle_join(hipStream_t s, const JoinItem* items_dev, int n_items, const SolverParamsDev& sp, bool subpixel = false);
 int launch_collect_triangulate(hipStream_t s, const TriItem* items_dev, int n_items,
                                const SolverParamsDev& sp, int cap);
 struct BatchMatchArgs {          // kernarg of match_batch_kernel / match_union_kernel (tiles of 64 queries)
@@ -434,6 +436,10 @@ int launch_match_stereo(hipStream_t s, const BatchMatchArgs& a64, int cap_max);
 // match_frame.hip: the stereo and the temporal problems of a handful of problems (one frame) in ONE launch
 int launch_match_frame(hipStream_t s, const BatchMatchArgs& at, const BatchMatchArgs& as64, long long blocks_t, int cap_max);
 #define VISO_FRAME_MAX_BLOCKS 256   // temporal grids up to this size (8 problem slots of 2000 keypoints) take the one-launch kernel
+// subpixel.hip: the opt-in sub-pixel refinement of frames' stereo lists (viso_batch_set_subpixel); uv [n_frames][cap]
+int launch_subpixel(hipStream_t s, const uint8_t* images, size_t img_stride, size_t r_off, int rows, int cols, const float2* kp,
+                    size_t kp_stride, int cap, const int* lists, size_t list_stride, const int* m_cnt, int n_frames, int mode, float2* uv,
+                    const uint16_t* lrows, size_t lrows_stride, const int* lrank, size_t lrank_stride);   // lrows == null: W_L from the image
 int launch_extract_pack(hipStream_t s, const ImageView* imgs_dev, int n_img, int cap, const uint8_t* images,
                         int rows, int cols, int extras, int r8s, int* r8cnt);
 int launch_harris_response(hipStream_t s, const uint8_t* images, int n_img, int rows, int cols, double k, float* resp);

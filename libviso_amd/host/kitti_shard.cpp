@@ -51,13 +51,14 @@ int kitti_count_frames(const std::string& seq_base, int begin, int end) {
 
 std::vector<FrameRecord> kitti_run_range(const std::string& seq_base, const Matd& P1, const Matd& P2, int begin,
                                          int first, int last, int device, int chunk, uint64_t ransac_seed,
-                                         int decode_threads, OdometryStats* stats) {
+                                         int decode_threads, OdometryStats* stats, int subpixel) {
     std::vector<FrameRecord> rec;
     if (last <= first) return rec;
     const std::string ext = kitti_image_ext(seq_base, begin);
     StereoImageGenerator images({seq_base + "/image_0/%06d" + ext, seq_base + "/image_1/%06d" + ext},
                                 begin + first, begin + last);
-    OdometryResult res = sequence_odometry(P1, P2, images, chunk, ransac_seed, (uint64_t)(begin + first), device, decode_threads);
+    OdometryResult res = sequence_odometry(P1, P2, images, chunk, ransac_seed, (uint64_t)(begin + first), device, decode_threads,
+                                           subpixel);
     if (stats) *stats = res.stats;
     // res.ok / res.tr / res.n_inliers: one entry per frame read, entry 0 = this range's first frame (no pose)
     for (size_t t = 1; t < res.ok.size(); ++t) {
@@ -138,6 +139,7 @@ void mkdirs(const std::string& path) {
 static thread_local std::string g_host_err;
 static thread_local viso::OdometryStats g_last_stats;
 static thread_local int g_decode_threads = 0;
+static thread_local int g_subpixel = 0;
 
 extern "C" const char* viso_host_last_error(void) { return g_host_err.c_str(); }
 namespace viso { void set_host_error(const std::string& s) { g_host_err = s; } }   // for the other C entry points (drop_in.cpp)
@@ -162,7 +164,7 @@ extern "C" int viso_kitti_run_range(const char* seq_base, int begin, int first, 
         }
         g_last_stats = viso::OdometryStats();
         std::vector<viso::FrameRecord> rec = viso::kitti_run_range(seq_base, P1, P2, begin, first, last, device, chunk, ransac_seed,
-                                                                   g_decode_threads, &g_last_stats);
+                                                                   g_decode_threads, &g_last_stats, g_subpixel);
         for (size_t i = 0; i < rec.size(); ++i) {
             for (int j = 0; j < 6; ++j) rec8[i * 8 + (size_t)j] = rec[i].tr[j];
             rec8[i * 8 + 6] = rec[i].ok;
@@ -184,6 +186,12 @@ extern "C" void viso_kitti_last_stats(double out[9]) {
 }
 
 extern "C" void viso_kitti_set_decode_threads(int n) { g_decode_threads = n > 0 ? n : 0; }
+
+extern "C" int viso_kitti_set_subpixel(int mode) {
+    if (mode < 0 || mode > 2) { g_host_err = "viso_kitti_set_subpixel: mode must be 0, 1 or 2"; return VISO_ERR_ARG; }
+    g_subpixel = mode;
+    return VISO_OK;
+}
 
 extern "C" int viso_kitti_write_poses(const char* file_name, const double* rec8, int n, int* n_poses) {
     return viso_kitti_write_poses2(file_name, rec8, n, 0, n_poses);

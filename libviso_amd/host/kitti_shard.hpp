@@ -44,9 +44,10 @@ int kitti_count_frames(const std::string& seq_base, int begin, int end);
 // rec[i] = record of the pair ending at frame first + 1 + i.  Fewer than last - first records come back when an
 // image in the range cannot be decoded (the reference's generator stops there, src/viso.h:94-96).
 // stats (may be null): where the range's wall time went (decode / upload / GPU), see OdometryStats.
+// subpixel: the opt-in sub-pixel stereo refinement of sequence_odometry (0 = off, the reference's arithmetic).
 std::vector<FrameRecord> kitti_run_range(const std::string& seq_base, const Matd& P1, const Matd& P2, int begin,
                                          int first, int last, int device, int chunk = 64, uint64_t ransac_seed = 0,
-                                         int decode_threads = 0, OdometryStats* stats = nullptr);
+                                         int decode_threads = 0, OdometryStats* stats = nullptr, int subpixel = 0);
 
 // poses[0] = I, then pose <- pose * inv(tr2mat(tr)) per solved record (src/viso.cpp:1189-1190, 1315-1321): the list
 // [I, P1, ..., Pn] the reference's code reads as.
@@ -80,6 +81,9 @@ int viso_kitti_run_range(const char* seq_base, int begin, int first, int last, i
 void viso_kitti_last_stats(double out[9]);
 // worker threads the next viso_kitti_run_range calls of this thread decode with (0 = default)
 void viso_kitti_set_decode_threads(int n);
+// sub-pixel stereo refinement mode (viso_batch_set_subpixel: 0 = off, 1, 2) of the next viso_kitti_run_range calls of this
+// thread; returns VISO_ERR_ARG for another value
+int viso_kitti_set_subpixel(int mode);
 // chain n records and write the KITTI pose file (directories are created); *n_poses = lines written
 int viso_kitti_write_poses(const char* file_name, const double* rec8, int n, int* n_poses);
 // the same with the pose list the reference writes ([P1..Pn, Pn], see chain_records) when reference_pose_list != 0

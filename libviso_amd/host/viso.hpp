@@ -258,8 +258,11 @@ private:
 // decode_threads: worker threads that decode a chunk's images while the GPU works on the previous chunk
 // (0 = $VISO_DECODE_THREADS, else min(16, hardware threads)).  The frames are consumed in order and the sequence ends
 // at the first pair that cannot be decoded, exactly like the reference's generator (src/viso.h:94-96).
+// subpixel: the opt-in sub-pixel refinement of the stereo observations (viso_batch_set_subpixel; NOT in the reference, poses
+// not comparable with its output): 0 = off, 1 = uR, 2 = uR and vR.  A chunk's halo frame is refined again like any other
+// frame, so every chunking and partition gives the same records.
 OdometryResult sequence_odometry(const Matd& P1, const Matd& P2, StereoImageGenerator& images,
                                  int chunk = 64, uint64_t ransac_seed = 0, uint64_t first_frame_index = 0,
-                                 int device = 0, int decode_threads = 0);
+                                 int device = 0, int decode_threads = 0, int subpixel = 0);
 
 }  // namespace viso

@@ -724,7 +724,7 @@ int cpu_budget() {
 // asynchronous uploads from the slot's pinned buffer), the worker threads decode chunk c + 1 straight into the other
 // slot's pinned buffer.  The halo frame is copied from the previous slot's buffer, not decoded twice.
 OdometryResult sequence_odometry(const Matd& P1, const Matd& P2, StereoImageGenerator& images, int chunk,
-                                 uint64_t ransac_seed, uint64_t first_frame_index, int device, int decode_threads) {
+                                 uint64_t ransac_seed, uint64_t first_frame_index, int device, int decode_threads, int subpixel) {
     using clock = std::chrono::steady_clock;
     auto since = [](clock::time_point t0) { return std::chrono::duration<double>(clock::now() - t0).count(); };
     const auto t_start = clock::now();
@@ -811,6 +811,7 @@ OdometryResult sequence_odometry(const Matd& P1, const Matd& P2, StereoImageGene
         viso_batch* b = pipe.acquire(nf, MAX_FEATURE_NUM, VISO_DESC_LEN, global0);
         int r = viso_batch_upload_images(b, 0, 0, nullptr, rows, cols, nullptr, nullptr);          // device buffers for this geometry
         if (r >= 0) r = viso_batch_set_params(b, &st, &tm, &vp, ransac_seed, first_frame_index + (uint64_t)global0);
+        if (r >= 0) r = viso_batch_set_subpixel(b, subpixel);
         if (r >= 0) r = viso_batch_stamp(b, 0);
         if (r >= 0) r = viso_batch_upload_images_async(b, 0, nf, pin, rows, cols, nullptr, nullptr);
         if (r >= 0) r = viso_batch_stamp(b, 1);

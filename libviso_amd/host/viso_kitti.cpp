@@ -17,6 +17,8 @@
 //   --decode-threads n  PNG decoding threads per rank (default: min(64, usable host threads / ranks): decoding bounds the run; usable = hardware, affinity, cgroup quota)
 //   --reference-pose-list   write the list the reference's code actually produces, [P1, ..., Pn, Pn] (src/viso.cpp:1317-1321
 //                       overwrites poses.back() before pushing the clone), instead of [I, P1, ..., Pn]
+//   --subpixel m        opt-in sub-pixel stereo refinement (viso_batch_set_subpixel): 0 = off (default: the reference's
+//                       arithmetic), 1 = uR, 2 = uR and vR.  Not in the reference: such poses are not comparable with its output
 // Every rank reports where its wall time went: decode (PNG inflate on the worker threads; the calling thread's wait for
 // it is the runner's critical path), upload and GPU seconds from time stamps on the device.
 // libviso_amd/kitti_shard.py is the same runner with the gather as an RCCL all-gather (torch.distributed).
@@ -41,7 +43,7 @@ struct Args {
     const char* result_sha = nullptr;
     std::string seq_name;
     int begin = 0, end = INT_MAX;
-    int gpus = 0, rank = -1, world = 0, gather = 0, device = -1, chunk = 64, decode_threads = 0;
+    int gpus = 0, rank = -1, world = 0, gather = 0, device = -1, chunk = 64, decode_threads = 0, subpixel = 0;
     bool same_device = false, reference_pose_list = false;
     unsigned long long seed = 0;
 };
@@ -58,6 +60,7 @@ bool parse(int argc, char** argv, Args& a) {
         else if (s == "--device") { if (!val(a.device)) return false; }
         else if (s == "--chunk") { if (!val(a.chunk)) return false; }
         else if (s == "--decode-threads") { if (!val(a.decode_threads)) return false; }
+        else if (s == "--subpixel") { if (!val(a.subpixel) || a.subpixel < 0 || a.subpixel > 2) return false; }
         else if (s == "--reference-pose-list") a.reference_pose_list = true;
         else if (s == "--seed") { if (i + 1 >= argc) return false; a.seed = std::strtoull(argv[++i], nullptr, 10); }
         else if (s == "--same-device") a.same_device = true;
@@ -98,7 +101,7 @@ int main(int argc, char** argv) {
     Args a;
     if (!parse(argc, argv, a)) {
         std::printf("usage: demo result_sha seq_name begin end [--gpus W | --rank r --world W | --gather W] "
-                    "[--device d] [--same-device] [--chunk n] [--seed s] [--decode-threads n] [--reference-pose-list]\n");   // :81-85
+                    "[--device d] [--same-device] [--chunk n] [--seed s] [--decode-threads n] [--reference-pose-list] [--subpixel 0|1|2]\n");   // :81-85
         return 1;
     }
     const char* home = std::getenv("KITTI_HOME");                                              // :96
@@ -174,7 +177,7 @@ int main(int argc, char** argv) {
             const int device = a.device >= 0 ? a.device : a.rank;
             viso::OdometryStats stats;
             std::vector<viso::FrameRecord> rec = viso::kitti_run_range(seq_base, P1, P2, a.begin, range.first, range.second,
-                                                                       device, a.chunk, a.seed, a.decode_threads, &stats);
+                                                                       device, a.chunk, a.seed, a.decode_threads, &stats, a.subpixel);
             viso::mkdirs(result_dir + "/shards");
             const std::string f = rank_file(result_dir, a.seq_name, a.rank, a.world);
             if (!viso::write_records(f, range.first, range.second, rec)) { std::fprintf(stderr, "cannot write %s\n", f.c_str()); return 3; }
@@ -187,7 +190,7 @@ int main(int argc, char** argv) {
         const std::string ext = viso::kitti_image_ext(seq_base, a.begin);
         viso::StereoImageGenerator images({seq_base + "/image_0/%06d" + ext, seq_base + "/image_1/%06d" + ext}, a.begin, a.end);
         viso::OdometryResult res = viso::sequence_odometry(P1, P2, images, a.chunk, a.seed, (uint64_t)a.begin,
-                                                           a.device >= 0 ? a.device : 0, a.decode_threads);      // :111
+                                                           a.device >= 0 ? a.device : 0, a.decode_threads, a.subpixel);   // :111
         viso::mkdirs(result_dir + "/data");                                                    // :112-113
         if (a.reference_pose_list && res.poses.size() > 1) {                                   // [P1, ..., Pn, Pn], see kitti_shard.hpp
             res.poses.erase(res.poses.begin());

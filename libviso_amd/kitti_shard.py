@@ -65,6 +65,7 @@ def load_host():
     L.viso_kitti_last_stats.restype = None
     L.viso_kitti_set_decode_threads.argtypes = [C.c_int]
     L.viso_kitti_set_decode_threads.restype = None
+    L.viso_kitti_set_subpixel.argtypes = [C.c_int]
     L.viso_host_last_error.restype = C.c_char_p
     return L
 
@@ -220,6 +221,9 @@ def main(argv=None):
     ap.add_argument("--decode-threads", type=int, default=0, help="PNG decoding threads per rank (0: min(64, cpus / ranks))")
     ap.add_argument("--reference-pose-list", action="store_true",
                     help="write the list the reference's code actually produces, [P1..Pn, Pn] (src/viso.cpp:1317-1321)")
+    ap.add_argument("--subpixel", type=int, default=0, choices=(0, 1, 2),
+                    help="opt-in sub-pixel stereo refinement: 0 = off (the reference's arithmetic), 1 = uR, 2 = uR and vR; "
+                         "not in the reference, poses are not comparable with its output")
     args = ap.parse_args(argv)
     home = os.environ.get("KITTI_HOME")
     if not home:
@@ -262,6 +266,9 @@ def main(argv=None):
     L = load_host()
     threads = args.decode_threads or int(os.environ.get("VISO_DECODE_THREADS", "0")) or max(1, min(64, cpu_budget() // world))
     L.viso_kitti_set_decode_threads(threads)
+    if L.viso_kitti_set_subpixel(args.subpixel) != 1:
+        print(f"kitti_shard: {L.viso_host_last_error().decode()}", file=sys.stderr)
+        return 2
 
     def die(code, what):
         # a failure that the peers cannot learn about through the collective: leave WITHOUT joining one (no barrier,

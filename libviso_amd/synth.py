@@ -245,3 +245,90 @@ def make_image_sequence(seed, n_frames, n_kp=2000, width=1241, height=376, outli
     param = Param.default(base=base, f=f, cu=cu, cv=cv)
     return dict(images=images, kp=kp, n=n, tr_gt=tr_gt, param=param, F=F, P1=KITTI_P1, P2=KITTI_P2,
                 width=width, height=height)
+
+
+def make_subpixel_image_sequence(seed, n_frames, n_kp=1500, width=1241, height=376, outlier_frac=0.2,
+                                 noise_sigma=1.0, cap=None, zmin=4.0, zmax=60.0, n_blobs=6):
+    """Image-in scene with fractional disparities, for the opt-in sub-pixel stereo refinement
+    (viso_batch_set_subpixel).  make_image_sequence paints every world point's patch at its ROUNDED projection, so
+    there is no fractional disparity to recover; here every world point owns a continuous texture -- `n_blobs`
+    Gaussian blobs (offsets within 5 px, sigma 1.2..2.5 px, signed amplitudes) -- rendered at its exact fractional
+    projection in each view and sampled at the pixel centres.  Keypoints sit at the rounded projections, as a Harris
+    detector would give them (Point2f(int,int), src/viso.cpp:967).  Same dict as make_image_sequence (tr_gt[t] maps
+    points of frame t-1 into frame t) plus xy_true [n_frames][2][cap][2] float64: the exact projection behind every
+    keypoint (NaN for outliers).  A random stream of its own: the other generators are untouched."""
+    rng = np.random.default_rng(seed)
+    cap = cap or n_kp
+    f, cu, cv, base = KITTI_F, KITTI_CU, KITTI_CV, KITTI_BASE
+    n_in = int(round(n_kp * (1.0 - outlier_frac)))
+    R = 8                                                   # render radius: blob offset 5 + 2.5 sigma
+    images = np.zeros((n_frames, 2, height, width), np.uint8)
+    kp = np.zeros((n_frames, 2, cap, 2), np.float32)
+    n = np.zeros((n_frames, 2), np.int32)
+    tr_gt = np.zeros((n_frames, 6))
+    xy_true = np.full((n_frames, 2, cap, 2), np.nan)
+
+    def new_textures(k):   # [k][n_blobs][4]: dx, dy, sigma, amplitude
+        tx = np.empty((k, n_blobs, 4))
+        tx[..., 0:2] = rng.uniform(-5.0, 5.0, (k, n_blobs, 2))
+        tx[..., 2] = rng.uniform(1.2, 2.5, (k, n_blobs))
+        tx[..., 3] = rng.uniform(40.0, 90.0, (k, n_blobs)) * rng.choice([-1.0, 1.0], (k, n_blobs))
+        return tx
+
+    P = _new_points(rng, n_in, width, height, zmin, zmax, f, cu, cv)
+    T = new_textures(n_in)
+    g = np.arange(-R, R + 1, dtype=np.float64)
+    for t in range(n_frames):
+        if t > 0:
+            tr = np.concatenate([rng.uniform(-0.02, 0.02, 3), rng.uniform(-0.05, 0.05, 2),
+                                 -rng.uniform(0.5, 1.5, 1)])
+            tr_gt[t] = tr
+            Rm, tt = rot_from_tr(tr)
+            P = P @ Rm.T + tt
+            u = f * P[:, 0] / P[:, 2] + cu
+            v = f * P[:, 1] / P[:, 2] + cv
+            keep = (P[:, 2] > 2.0) & (u >= 0) & (u <= width - 1) & (v >= 0) & (v <= height - 1)
+            P, T = P[keep], T[keep]
+            k_new = n_in - len(P)
+            if k_new > 0:
+                P = np.concatenate([P, _new_points(rng, k_new, width, height, zmin, zmax, f, cu, cv)])
+                T = np.concatenate([T, new_textures(k_new)])
+        uLf = f * P[:, 0] / P[:, 2] + cu
+        vLf = f * P[:, 1] / P[:, 2] + cv
+        uRf = f * (P[:, 0] - base) / P[:, 2] + cu
+        vL = np.rint(vLf).astype(int)
+        for side in (0, 1):
+            uf = uLf if side == 0 else uRf
+            ui = np.rint(uf).astype(int)
+            vis = np.ones(len(P), bool) if side == 0 else ((ui >= 0) & (ui <= width - 1))
+            img = np.full((height + 2 * R, width + 2 * R), 128.0)   # padded: renders near the border need no clipping
+            for j in np.nonzero(vis)[0]:
+                x0, y0 = ui[j], vL[j]
+                gx = (x0 + g) - uf[j]                        # pixel centres relative to the exact projection
+                gy = (y0 + g) - vLf[j]
+                b = T[j]
+                ex = np.exp(-(gx[None, :] - b[:, 0, None]) ** 2 / (2.0 * b[:, 2, None] ** 2))   # [n_blobs][2R+1]
+                ey = np.exp(-(gy[None, :] - b[:, 1, None]) ** 2 / (2.0 * b[:, 2, None] ** 2))
+                img[y0:y0 + 2 * R + 1, x0:x0 + 2 * R + 1] += np.einsum("b,by,bx->yx", b[:, 3], ey, ex)
+            img = img[R:R + height, R:R + width] + rng.normal(0.0, noise_sigma, (height, width))
+            images[t, side] = np.clip(np.rint(img), 0, 255).astype(np.uint8)
+            idx = np.nonzero(vis)[0][:n_kp]
+            k_real = len(idx)
+            k_out = n_kp - k_real
+            xy = np.empty((n_kp, 2), np.float32)
+            xy[:k_real, 0] = ui[idx]
+            xy[:k_real, 1] = vL[idx]
+            xy[k_real:, 0] = rng.integers(0, width, k_out)
+            xy[k_real:, 1] = rng.integers(0, height, k_out)
+            xt = np.full((n_kp, 2), np.nan)
+            xt[:k_real, 0] = uf[idx]
+            xt[:k_real, 1] = vLf[idx]
+            perm = rng.permutation(n_kp)
+            kp[t, side, :n_kp] = xy[perm]
+            xy_true[t, side, :n_kp] = xt[perm]
+            n[t, side] = n_kp
+    from . import hostmath
+    F = hostmath.F_from_P(KITTI_P1, KITTI_P2)
+    param = Param.default(base=base, f=f, cu=cu, cv=cv)
+    return dict(images=images, kp=kp, n=n, tr_gt=tr_gt, xy_true=xy_true, param=param, F=F, P1=KITTI_P1, P2=KITTI_P2,
+                width=width, height=height)
