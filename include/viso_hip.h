@@ -442,6 +442,59 @@ int viso_batch_get_subpixel(viso_batch* b, int t, float* uv, int* out_n);
 int viso_refine_stereo_subpixel(const uint8_t* imgL, const uint8_t* imgR, int rows, int cols, const float* kp1, int n1,
                                 const float* kp2, int n2, const int32_t* match, int n, int mode, float* out_uv);
 
+/* ------------------------------------------------ rectification of raw camera images (opt-in; NOT in the reference)
+ *
+ * Every stage assumes undistorted, rectified pairs (triangulate_rectified, src/viso.cpp:1137-1162; the Sampson gate around
+ * F_from_P(P1, P2)); KITTI odometry ships them, other rigs and KITTI raw's unrectified drives do not.  With this on, the batch's
+ * image uploads take RAW images and a HIP kernel (rectify_remap_kernel) undistorts and rectifies them into the image buffer the
+ * detector, the extractor, the matchers and the sub-pixel refinement read; none of those changes.
+ *
+ * Map of one camera: mapx, mapy [out_rows][out_cols] float, the raw-image position output pixel (x, y) samples (pixel centres at
+ * integer coordinates, the convention of the extractor and Harris).  viso_rectify_map builds it with the plumb-bob model in the
+ * form of OpenCV's initUndistortRectifyMap, in double: K 3x3 (K[0][1] must be 0), D = (k1, k2, p1, p2, k3), R 3x3 the
+ * rectifying rotation, P 3x4 of which only the left 3x3 P33 is used:
+ *   iR = inverse(P33 R); (x', y', w) = iR (x, y, 1); x' /= w; y' /= w; r2 = x'^2 + y'^2; kr = 1 + k1 r2 + k2 r2^2 + k3 r2^3;
+ *   xd = x' kr + 2 p1 x' y' + p2 (r2 + 2 x'^2); yd = y' kr + p1 (r2 + 2 y'^2) + 2 p2 x' y';
+ *   mapx = (float)(K00 xd + K02); mapy = (float)(K11 yd + K12).
+ * (Held to a tolerance, not to bit equality; K = P33, D = 0, R = I gives mapx = x, mapy = y exactly.)
+ * Quantisation (host, when a map is installed): X = lrintf(mapx * 32) (ties to even), ix = X >> 5 (floor), fx = X & 31, the
+ * same for y; an entry that is not finite or has |map| >= 32768 is OUTSIDE: its output is the border value and it loads nothing.
+ * Remap (device, integer, exact), with tap(a, b) = raw[iy+b][ix+a] when 0 <= ix+a < raw_cols and 0 <= iy+b < raw_rows, else border:
+ *   out = ((32-fx)(32-fy) tap(0,0) + fx(32-fy) tap(1,0) + (32-fx) fy tap(0,1) + fx fy tap(1,1) + 512) >> 10   (<= 255).
+ * Bilinear at 1/32 pixel like OpenCV's INTER_LINEAR, whose 15-bit weight tables can differ from this by one LSB: the result is
+ * not claimed equal to OpenCV's remap.
+ *
+ * In a batch one launch rectifies all frames of an upload: each workgroup keeps its output tile's map entries in registers and
+ * loops over a chunk of 32 of the upload's frames, so a caller that uploads one frame at a time re-reads the maps (8 B per
+ * output pixel and camera) for every frame; upload several frames per call where possible.  Outside entries and taps beyond the raw image are
+ * resolved on the host before any address is formed: no map makes the kernel read out of bounds. */
+
+/* The map of one camera (host only, no device; see above).  K 9, D 5, R 9, P 12 doubles, row-major; mapx, mapy
+ * out_rows x out_cols.  VISO_ERR_ARG: sizes <= 0, a null pointer, K[0][1] != 0, or P33 R singular. */
+int viso_rectify_map(const double K[9], const double D[5], const double R[9], const double P[12], int out_rows, int out_cols,
+                     float* mapx, float* mapy);
+/* Install (all four maps non-NULL, each out_rows x out_cols) or remove (all four NULL) rectification for the batch's NEXT image
+ * uploads; synchronises like the other synchronous setters.  While it is on:
+ *   - viso_batch_upload_images(_async) take raw images [nf][2][raw_rows][raw_cols]; a rows / cols other than the raw geometry
+ *     returns VISO_ERR_ARG and the batch stays usable;
+ *   - an upload copies into a raw staging buffer of the batch and enqueues the remap on the context's stream (the stream rule
+ *     and the async host-buffer rule of the uploads hold unchanged);
+ *   - keypoints passed with an upload are in rectified coordinates; viso_batch_detect and the runs see out_rows x out_cols images.
+ * Descriptor-in uploads and runs are unaffected; with rectification never installed every call launches what it launched
+ * before.  VISO_ERR_ARG: sizes <= 0, border outside 0..255, some but not all maps NULL. */
+int viso_batch_set_rectify(viso_batch* b, int raw_rows, int raw_cols, int out_rows, int out_cols, const float* mapxL,
+                           const float* mapyL, const float* mapxR, const float* mapyR, int border);
+/* The batch's device image of frame t, side (0 left, 1 right): img_rows x img_cols bytes, rectified when rectification was on at
+ * its upload.  Synchronises like the other getters. */
+int viso_batch_get_image(viso_batch* b, int t, int side, uint8_t* out);
+/* The geometry of those images (img_rows x img_cols, what viso_batch_get_image copies): the last image upload's, or the
+ * output geometry of viso_batch_set_rectify; 0 x 0 before either. */
+int viso_batch_get_image_geometry(viso_batch* b, int* rows, int* cols);
+/* Host pointers, default context, the batch's kernel: n raw images raw_rows x raw_cols of ONE camera -> n rectified images
+ * out_rows x out_cols (out).  Same argument rules as viso_batch_set_rectify. */
+int viso_rectify_images(const uint8_t* raw, int n, int raw_rows, int raw_cols, const float* mapx, const float* mapy, int out_rows,
+                        int out_cols, int border, uint8_t* out);
+
 #ifdef __cplusplus
 }
 #endif

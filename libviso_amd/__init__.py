@@ -16,7 +16,7 @@ import weakref
 
 import numpy as np
 
-from .abi import (DESC_LEN, MatchParams, Param, declare_common, declare_subpixel, f32p, f64p, i32p, i64p, intp, ptr)
+from .abi import (DESC_LEN, MatchParams, Param, declare_common, declare_rectify, declare_subpixel, f32p, f64p, i32p, i64p, intp, ptr)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("VISO_HIP_SO") or os.path.join(_HERE, "libviso_hip.so")   # VISO_HIP_SO: another build of the library (A/B runs)
@@ -114,6 +114,8 @@ def load():
     L.viso_batch_get_keypoints.argtypes = [C.c_void_p, C.c_int, C.c_int, f32p, intp]
     if hasattr(L, "viso_batch_set_subpixel"):   # (absent from older builds of the library: VISO_HIP_SO A/B runs)
         declare_subpixel(L)
+    if hasattr(L, "viso_batch_set_rectify"):
+        declare_rectify(L)
     L.viso_harris_response.argtypes = [C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_double, f32p]
     L.viso_detect_harris_binned.argtypes = [C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                             C.c_double, f32p, f32p, intp]
@@ -396,6 +398,50 @@ def refine_stereo_subpixel(imgL, imgR, kp1, kp2, match, mode=1):
     return out[:len(match)].copy()
 
 
+def rectify_map(K, D, R, P, out_shape):
+    """viso_rectify_map: the map of one camera (opt-in rectification, not in the reference; include/viso_hip.h), on the host.
+    K 3x3 (K[0][1] == 0), D (k1, k2, p1, p2, k3), R 3x3 rectifying rotation, P 3x4 rectified projection; out_shape (rows, cols).
+    Returns (mapx, mapy), float32 arrays of out_shape: the raw-image position every output pixel samples."""
+    L = load()
+    K, D, R, P = (_f64(np.asarray(a, np.float64).reshape(-1)) for a in (K, D, R, P))
+    if (K.size, D.size, R.size, P.size) != (9, 5, 9, 12):
+        raise ValueError("rectify_map: K 3x3, D 5, R 3x3, P 3x4")
+    rows, cols = (int(v) for v in out_shape)
+    mapx = np.empty((max(rows, 1), max(cols, 1)), np.float32)
+    mapy = np.empty_like(mapx)
+    r = L.viso_rectify_map(ptr(K, C.c_double), ptr(D, C.c_double), ptr(R, C.c_double), ptr(P, C.c_double), rows, cols,
+                           ptr(mapx, C.c_float), ptr(mapy, C.c_float))
+    if r != 1:
+        _err("viso_rectify_map", r)
+    return mapx, mapy
+
+
+def _map_pair(mapx, mapy, out_shape):
+    mapx, mapy = _f32(mapx), _f32(mapy)
+    if mapx.shape != tuple(out_shape) or mapy.shape != tuple(out_shape):
+        raise ValueError(f"maps must have the output shape {tuple(out_shape)}")
+    return mapx, mapy
+
+
+def rectify_images(raw, mapx, mapy, out_shape, border=0):
+    """viso_rectify_images: raw uint8 images (n, raw_rows, raw_cols) or one (raw_rows, raw_cols) of ONE camera -> rectified images
+    of out_shape, on the device (the batch's kernel; the remap rule of include/viso_hip.h)."""
+    L = load()
+    raw = np.ascontiguousarray(raw, dtype=np.uint8)
+    single = raw.ndim == 2
+    if single:
+        raw = raw[None]
+    n, rr, rc = raw.shape
+    rows, cols = (int(v) for v in out_shape)
+    mapx, mapy = _map_pair(mapx, mapy, (rows, cols))
+    out = np.empty((max(n, 1), rows, cols), np.uint8)
+    r = L.viso_rectify_images(ptr(raw, C.c_uint8), n, rr, rc, ptr(mapx, C.c_float), ptr(mapy, C.c_float), rows, cols, int(border),
+                              ptr(out, C.c_uint8))
+    if r != 1:
+        _err("viso_rectify_images", r)
+    return out[0].copy() if single else out[:n].copy()
+
+
 HARRIS_K = float(np.float32(0.04))   # the reference's intended default (float k = .04, src/viso.cpp:915)
 
 
@@ -549,6 +595,37 @@ class Batch:
         n = C.c_int(0)
         self._chk("viso_batch_get_subpixel", self.L.viso_batch_get_subpixel(self.h, t, ptr(out, C.c_float), C.byref(n)))
         return out[:n.value].copy()
+
+    def set_rectify(self, raw_shape, out_shape=None, left=None, right=None, border=0):
+        """viso_batch_set_rectify: from the next image upload on, uploads take raw images of raw_shape (rows, cols) and the device
+        rectifies them to out_shape with the maps left = (mapx, mapy) and right = (mapx, mapy) (rectify_map).  set_rectify(None)
+        turns it off."""
+        if raw_shape is None:
+            self._chk("viso_batch_set_rectify", self.L.viso_batch_set_rectify(self.h, 0, 0, 0, 0, None, None, None, None, 0))
+            return
+        if left is None or right is None or out_shape is None:
+            raise ValueError("set_rectify: out_shape and both maps are needed (or raw_shape=None to turn it off)")
+        rows, cols = (int(v) for v in out_shape)
+        lx, ly = _map_pair(left[0], left[1], (rows, cols))
+        rx, ry = _map_pair(right[0], right[1], (rows, cols))
+        rr, rc = (int(v) for v in raw_shape)
+        self._chk("viso_batch_set_rectify", self.L.viso_batch_set_rectify(
+            self.h, rr, rc, rows, cols, ptr(lx, C.c_float), ptr(ly, C.c_float), ptr(rx, C.c_float), ptr(ry, C.c_float), int(border)))
+
+    def image_shape(self):
+        """(rows, cols) of the device images (viso_batch_get_image_geometry); (0, 0) before any image upload."""
+        r, c = C.c_int(0), C.c_int(0)
+        self._chk("viso_batch_get_image_geometry", self.L.viso_batch_get_image_geometry(self.h, C.byref(r), C.byref(c)))
+        return r.value, c.value
+
+    def image(self, t, side):
+        """The device image of frame t, side (uint8, rectified when rectification was on at its upload)."""
+        shape = self.image_shape()   # the library's geometry, not a copy of it here: the buffer always fits what is copied
+        if shape == (0, 0):
+            raise VisoError("Batch.image: no images uploaded")
+        out = np.empty(shape, np.uint8)
+        self._chk("viso_batch_get_image", self.L.viso_batch_get_image(self.h, int(t), int(side), ptr(out, C.c_uint8)))
+        return out
 
     def set_params(self, stereo, temporal, param, seed=0, first_frame=0):
         self._chk("viso_batch_set_params", self.L.viso_batch_set_params(

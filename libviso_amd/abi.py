@@ -134,3 +134,13 @@ def declare_subpixel(lib):
     lib.viso_batch_get_subpixel.argtypes = [C.c_void_p, C.c_int, f32p, intp]
     lib.viso_refine_stereo_subpixel.argtypes = [u8p, u8p, C.c_int, C.c_int, f32p, C.c_int, f32p, C.c_int, i32p, C.c_int,
                                                 C.c_int, f32p]
+
+
+def declare_rectify(lib):
+    """Prototypes of the opt-in rectification of raw images (include/viso_hip.h; libviso_hip.so only)."""
+    u8p = C.POINTER(C.c_uint8)
+    lib.viso_rectify_map.argtypes = [f64p, f64p, f64p, f64p, C.c_int, C.c_int, f32p, f32p]
+    lib.viso_batch_set_rectify.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, f32p, f32p, f32p, f32p, C.c_int]
+    lib.viso_batch_get_image.argtypes = [C.c_void_p, C.c_int, C.c_int, u8p]
+    lib.viso_batch_get_image_geometry.argtypes = [C.c_void_p, intp, intp]
+    lib.viso_rectify_images.argtypes = [u8p, C.c_int, C.c_int, C.c_int, f32p, f32p, C.c_int, C.c_int, C.c_int, u8p]

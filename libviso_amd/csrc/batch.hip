@@ -10,6 +10,7 @@
 //   sorted  [3][nf][cap][3] int          match lists in (dist,i1) order; pos = inverse
 //   x_c [nf][4][cap], Xp_c [nf][3][cap]   double, SoA rows like cv::Mat(4,M): the solver's inputs, written by the circle join
 //   uv  [nf][cap] float2                 refined right-image points per stereo row (viso_batch_set_subpixel != 0 only)
+//   raw [nf][2][raw_rows][raw_cols] u8   staged raw images the remap reads into `images` (viso_batch_set_rectify only)
 // `which` = 0 stereo L->R of frame t, 1 temporal left (t vs t-1), 2 temporal right.
 #include "common.h"
 
@@ -38,6 +39,9 @@ struct viso_batch {
     // opt-in sub-pixel refinement of the stereo observations (subpixel.hip): the mode asked for, the buffer (allocated on the first
     // request), and the mode the last run refined with (0: the last run produced no refined points)
     int subpix = 0; float2* uv = nullptr; int uv_mode = 0;
+    // opt-in rectification of raw images (rectify.hip): on while rmap != null; the quantised maps [2][img_rows * img_cols], the
+    // raw staging buffer, its geometry and the border value
+    RectEntry* rmap = nullptr; uint8_t* raw = nullptr; int raw_rows = 0, raw_cols = 0, rborder = 0; size_t raw_bytes = 0;
     JoinItem* join; SolverItem* sitems;
     int *circ, *pcl, *mc;
     double* tr_h; int *ok_h, *cnt_h, *hq; char* rot;   // hq: list of undecided hypotheses (launch_ransac)
@@ -142,7 +146,7 @@ int viso_batch_free(viso_batch* b, bool keep_shell) {
     void* ptrs[] = {b->h_part, b->h_resp, b->h_tmp_kp, b->h_tmp_resp, b->h_cnt, b->images, b->skp, b->sidx, b->rank, b->bstart, b->xinfo, b->views,
                     b->kp, b->desc, b->n, b->packed, b->packed8, b->r8cnt, b->sums, b->zero, b->probs, b->res, b->sorted,
                     b->pos, b->m_cnt, b->scored, b->x_c, b->Xp_c, b->join,
-                    b->sitems, b->circ, b->pcl, b->mc, b->uv, b->tr /* + ok, n_inl */, b->inl, b->tr_h, b->ok_h, b->cnt_h, b->hq, b->samp_h, b->rot, b->tile_flag, b->qord, b->ovf_q};
+                    b->sitems, b->circ, b->pcl, b->mc, b->uv, b->rmap, b->raw, b->tr /* + ok, n_inl */, b->inl, b->tr_h, b->ok_h, b->cnt_h, b->hq, b->samp_h, b->rot, b->tile_flag, b->qord, b->ovf_q};
     for (void* p : ptrs) if (p) note(hipFree(p));
     if (keep_shell) { b->ctx = nullptr; b->events.clear(); b->desc_family.clear(); b->desc_family.shrink_to_fit(); }
     else delete b;
@@ -420,13 +424,43 @@ extern "C" int viso_batch_upload_i16_async(viso_batch* b, int f0, int nf, const 
     return upload_i16_impl(b, f0, nf, kp, desc16, n, false, "viso_batch_upload_i16_async");
 }
 
+// The image buffer for rows x cols images (the caller has synchronised the batch's stream).  The Harris response image of
+// viso_batch_detect is sized by the geometry it first met: it goes with the old buffer.
+static int ensure_images(viso_batch* b, int rows, int cols) {
+    if (b->images && (rows != b->img_rows || cols != b->img_cols)) {
+        HIP_TRY(hipFree(b->images));
+        b->images = nullptr;
+        if (b->h_resp) HIP_TRY(hipFree(b->h_resp));
+        b->h_resp = nullptr;
+    }
+    if (!b->images) {
+        HIP_TRY(hipMalloc((void**)&b->images, (size_t)rows * cols * 2 * (size_t)b->nf));
+        b->img_rows = rows; b->img_cols = cols;
+    }
+    return VISO_OK;
+}
+
+// Rectification on: raw images of frames f0 .. f0+nf-1 -> the staging buffer -> rectify_remap_kernel -> the image buffer, all on s.
+// One launch per upload: the maps are read once per upload, not once per frame.
+static int upload_raw(viso_batch* b, int f0, int nf, const uint8_t* images, hipStream_t s) {
+    const size_t rper = (size_t)b->raw_rows * b->raw_cols, oper = (size_t)b->img_rows * b->img_cols;
+    HIP_TRY(hipMemcpyAsync(b->raw + (size_t)f0 * 2 * rper, images, rper * 2 * (size_t)nf, hipMemcpyHostToDevice, s));
+    return launch_rectify(s, b->raw + (size_t)f0 * 2 * rper, 2 * rper, rper, b->raw_cols, b->images + (size_t)f0 * 2 * oper, 2 * oper,
+                          oper, b->rmap, b->img_rows, b->img_cols, nf, 2, b->rborder);
+}
+
 extern "C" int viso_batch_upload_images_async(viso_batch* b, int f0, int nf, const uint8_t* images, int rows, int cols,
                                               const float* kp, const int32_t* n) {
     if (dead(b) || f0 < 0 || nf < 0 || f0 + nf > b->nf || rows <= 0 || cols <= 0 || (nf && !images) || ((kp == nullptr) != (n == nullptr))) {
         viso_set_error("viso_batch_upload_images_async: bad argument");
         return VISO_ERR_ARG;
     }
-    if (!b->images || rows != b->img_rows || cols != b->img_cols) {
+    if (b->rmap && (rows != b->raw_rows || cols != b->raw_cols)) {
+        viso_set_error("viso_batch_upload_images_async: rectification is on: the images must be raw, %d x %d (got %d x %d)", b->raw_rows,
+                       b->raw_cols, rows, cols);
+        return VISO_ERR_ARG;
+    }
+    if (!b->rmap && (!b->images || rows != b->img_rows || cols != b->img_cols)) {
         viso_set_error("viso_batch_upload_images_async: image buffers not allocated for %d x %d (call viso_batch_upload_images once first)", rows, cols);
         return VISO_ERR_ARG;
     }
@@ -437,7 +471,11 @@ extern "C" int viso_batch_upload_images_async(viso_batch* b, int f0, int nf, con
     if ((r = enter(b)) < 0) return r;
     hipStream_t s = b->ctx->stream;
     const size_t per = (size_t)rows * cols, c = (size_t)b->cap;
-    HIP_TRY(hipMemcpyAsync(b->images + (size_t)f0 * 2 * per, images, per * 2 * (size_t)nf, hipMemcpyHostToDevice, s));
+    if (b->rmap) {
+        if ((r = upload_raw(b, f0, nf, images, s)) < 0) return r;
+    } else {
+        HIP_TRY(hipMemcpyAsync(b->images + (size_t)f0 * 2 * per, images, per * 2 * (size_t)nf, hipMemcpyHostToDevice, s));
+    }
     if (kp) {
         HIP_TRY(hipMemcpyAsync(b->kp + (size_t)f0 * 2 * c, kp, sizeof(float2) * (size_t)nf * 2 * c, hipMemcpyHostToDevice, s));
         return stage_n_async(b, f0, nf, n, s);
@@ -638,20 +676,29 @@ extern "C" int viso_batch_upload_images(viso_batch* b, int f0, int nf, const uin
     }
     for (int i = 0; n && i < 2 * nf; ++i)
         if (n[i] < 0 || n[i] > b->cap) { viso_set_error("viso_batch_upload_images: n[%d]=%d exceeds cap %d", i, n[i], b->cap); return VISO_ERR_ARG; }
+    if (b->rmap && (rows != b->raw_rows || cols != b->raw_cols)) {
+        viso_set_error("viso_batch_upload_images: rectification is on: the images must be raw, %d x %d (got %d x %d)", b->raw_rows,
+                       b->raw_cols, rows, cols);
+        return VISO_ERR_ARG;
+    }
     int r0;
     if ((r0 = enter(b)) < 0) return r0;
-    HIP_TRY(hipStreamSynchronize(b->ctx->stream));   // a run in flight may still read what the (null-stream) copies below rewrite
-    if (b->images && (rows != b->img_rows || cols != b->img_cols)) {
-        HIP_TRY(hipFree(b->images));
-        b->images = nullptr;
-    }
-    const size_t per = (size_t)rows * cols;
-    if (!b->images) {
-        HIP_TRY(hipMalloc((void**)&b->images, per * 2 * (size_t)b->nf));
-        b->img_rows = rows; b->img_cols = cols;
-    }
-    if (nf == 0) return VISO_OK;
     const size_t c = (size_t)b->cap;
+    if (b->rmap) {   // raw images: staged and rectified on the batch's stream, behind the run in flight
+        if (nf == 0) return VISO_OK;
+        hipStream_t s = b->ctx->stream;
+        if ((r0 = upload_raw(b, f0, nf, images, s)) < 0) return r0;
+        if (kp) {
+            HIP_TRY(hipMemcpyAsync(b->kp + (size_t)f0 * 2 * c, kp, sizeof(float2) * (size_t)nf * 2 * c, hipMemcpyHostToDevice, s));
+            HIP_TRY(hipMemcpyAsync(b->n + (size_t)f0 * 2, n, sizeof(int) * (size_t)nf * 2, hipMemcpyHostToDevice, s));
+        }
+        HIP_TRY(hipStreamSynchronize(s));
+        return VISO_OK;
+    }
+    HIP_TRY(hipStreamSynchronize(b->ctx->stream));   // a run in flight may still read what the (null-stream) copies below rewrite
+    if ((r0 = ensure_images(b, rows, cols)) < 0) return r0;
+    const size_t per = (size_t)rows * cols;
+    if (nf == 0) return VISO_OK;
     HIP_TRY(hipMemcpy(b->images + (size_t)f0 * 2 * per, images, per * 2 * (size_t)nf, hipMemcpyHostToDevice));
     if (kp) {   // keypoints may instead come from viso_batch_detect
         HIP_TRY(hipMemcpy(b->kp + (size_t)f0 * 2 * c, kp, sizeof(float2) * (size_t)nf * 2 * c, hipMemcpyHostToDevice));
@@ -744,6 +791,68 @@ extern "C" int viso_batch_get_subpixel(viso_batch* b, int t, float* uv, int* out
     if (m > b->cap) m = b->cap;
     if (m > 0 && uv) HIP_TRY(hipMemcpy(uv, b->uv + (size_t)t * b->cap, sizeof(float2) * (size_t)m, hipMemcpyDeviceToHost));
     *out_n = m;
+    return VISO_OK;
+}
+
+// Opt-in rectification of raw images (not in the reference; rectify.hip).  Synchronous like the other setters: the batch's work
+// in flight finishes first, then the maps are quantised on the host and the buffers (re)allocated.
+extern "C" int viso_batch_set_rectify(viso_batch* b, int raw_rows, int raw_cols, int out_rows, int out_cols, const float* mapxL,
+                                      const float* mapyL, const float* mapxR, const float* mapyR, int border) {
+    const int given = (mapxL != nullptr) + (mapyL != nullptr) + (mapxR != nullptr) + (mapyR != nullptr);
+    if (dead(b) || (given != 0 && given != 4) ||
+        (given == 4 && (!rect_geometry_ok(raw_rows, raw_cols, out_rows, out_cols) || border < 0 || border > 255))) {
+        viso_set_error("viso_batch_set_rectify: bad argument (sizes > 0, border 0..255, all four maps or none)");
+        return VISO_ERR_ARG;
+    }
+    int r;
+    if ((r = enter(b)) < 0) return r;
+    if ((r = batch_sync(b)) < 0) return r;
+    if (b->rmap) HIP_TRY(hipFree(b->rmap));
+    b->rmap = nullptr;
+    if (given == 0) {   // off: the staging buffer goes too; the image buffer stays (the next upload decides its geometry)
+        if (b->raw) HIP_TRY(hipFree(b->raw));
+        b->raw = nullptr; b->raw_bytes = 0; b->raw_rows = b->raw_cols = 0;
+        return VISO_OK;
+    }
+    const size_t oper = (size_t)out_rows * out_cols, rbytes = (size_t)raw_rows * raw_cols * 2 * (size_t)b->nf;
+    std::vector<RectEntry> q(2 * oper);
+    rect_quantise(mapxL, mapyL, oper, raw_rows, raw_cols, q.data());
+    rect_quantise(mapxR, mapyR, oper, raw_rows, raw_cols, q.data() + oper);
+    if ((r = ensure_images(b, out_rows, out_cols)) < 0) return r;
+    if (b->raw && b->raw_bytes != rbytes) {
+        HIP_TRY(hipFree(b->raw));
+        b->raw = nullptr; b->raw_bytes = 0;
+    }
+    if (!b->raw) {
+        HIP_TRY(hipMalloc((void**)&b->raw, rbytes));
+        b->raw_bytes = rbytes;
+    }
+    RectEntry* m = nullptr;
+    if ((r = dalloc(&m, 2 * oper)) < 0) return r;
+    if (hipMemcpy(m, q.data(), sizeof(RectEntry) * 2 * oper, hipMemcpyHostToDevice) != hipSuccess) {
+        hipFree(m);
+        viso_set_error("viso_batch_set_rectify: copying the maps failed");
+        return VISO_ERR_HIP;
+    }
+    b->rmap = m; b->raw_rows = raw_rows; b->raw_cols = raw_cols; b->rborder = border;
+    return VISO_OK;
+}
+
+// The geometry of the batch's device images (what viso_batch_get_image copies): 0 x 0 before the first image upload.
+extern "C" int viso_batch_get_image_geometry(viso_batch* b, int* rows, int* cols) {
+    if (dead(b) || !rows || !cols) { viso_set_error("viso_batch_get_image_geometry: bad argument"); return VISO_ERR_ARG; }
+    *rows = b->images ? b->img_rows : 0;
+    *cols = b->images ? b->img_cols : 0;
+    return VISO_OK;
+}
+
+// The device image of frame t, side (what the run reads: rectified when rectification was on at its upload).
+extern "C" int viso_batch_get_image(viso_batch* b, int t, int side, uint8_t* out) {
+    if (dead(b) || t < 0 || t >= b->nf || side < 0 || side > 1 || !out) { viso_set_error("viso_batch_get_image: bad argument"); return VISO_ERR_ARG; }
+    if (!b->images) { viso_set_error("viso_batch_get_image: no images uploaded"); return VISO_ERR_ARG; }
+    { const int rs_ = batch_sync(b); if (rs_ < 0) return rs_; }
+    const size_t per = (size_t)b->img_rows * b->img_cols;
+    HIP_TRY(hipMemcpy(out, b->images + ((size_t)t * 2 + side) * per, per, hipMemcpyDeviceToHost));
     return VISO_OK;
 }
 

@@ -440,6 +440,14 @@ int launch_match_frame(hipStream_t s, const BatchMatchArgs& at, const BatchMatch
 int launch_subpixel(hipStream_t s, const uint8_t* images, size_t img_stride, size_t r_off, int rows, int cols, const float2* kp,
                     size_t kp_stride, int cap, const int* lists, size_t list_stride, const int* m_cnt, int n_frames, int mode, float2* uv,
                     const uint16_t* lrows, size_t lrows_stride, const int* lrank, size_t lrank_stride);   // lrows == null: W_L from the image
+// rectify.hip: the opt-in rectification of raw images (viso_batch_set_rectify).  One entry per output pixel, quantised on the host:
+// off = byte offset of tap (0,0) in the raw image; meta = fx | fy << 5 | inside bits of taps (0,0) (1,0) (0,1) (1,1) << 10..13
+struct RectEntry { int off; unsigned meta; };
+void rect_quantise(const float* mapx, const float* mapy, size_t n, int raw_rows, int raw_cols, RectEntry* out);
+bool rect_geometry_ok(int raw_rows, int raw_cols, int out_rows, int out_cols);
+// image (f, side) of raw / out at f * fs + side * ss; map [sides][out_rows * out_cols]; frames 0 .. n_frames-1 of the pointers
+int launch_rectify(hipStream_t s, const uint8_t* raw, size_t raw_fs, size_t raw_ss, int raw_cols, uint8_t* out, size_t out_fs,
+                   size_t out_ss, const RectEntry* map, int out_rows, int out_cols, int n_frames, int sides, int border);
 int launch_extract_pack(hipStream_t s, const ImageView* imgs_dev, int n_img, int cap, const uint8_t* images,
                         int rows, int cols, int extras, int r8s, int* r8cnt);
 int launch_harris_response(hipStream_t s, const uint8_t* images, int n_img, int rows, int cols, double k, float* resp);

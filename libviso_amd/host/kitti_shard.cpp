@@ -51,14 +51,14 @@ int kitti_count_frames(const std::string& seq_base, int begin, int end) {
 
 std::vector<FrameRecord> kitti_run_range(const std::string& seq_base, const Matd& P1, const Matd& P2, int begin,
                                          int first, int last, int device, int chunk, uint64_t ransac_seed,
-                                         int decode_threads, OdometryStats* stats, int subpixel) {
+                                         int decode_threads, OdometryStats* stats, int subpixel, const StereoRectification* rect) {
     std::vector<FrameRecord> rec;
     if (last <= first) return rec;
     const std::string ext = kitti_image_ext(seq_base, begin);
     StereoImageGenerator images({seq_base + "/image_0/%06d" + ext, seq_base + "/image_1/%06d" + ext},
                                 begin + first, begin + last);
     OdometryResult res = sequence_odometry(P1, P2, images, chunk, ransac_seed, (uint64_t)(begin + first), device, decode_threads,
-                                           subpixel);
+                                           subpixel, rect);
     if (stats) *stats = res.stats;
     // res.ok / res.tr / res.n_inliers: one entry per frame read, entry 0 = this range's first frame (no pose)
     for (size_t t = 1; t < res.ok.size(); ++t) {
@@ -140,6 +140,10 @@ static thread_local std::string g_host_err;
 static thread_local viso::OdometryStats g_last_stats;
 static thread_local int g_decode_threads = 0;
 static thread_local int g_subpixel = 0;
+// viso_kitti_set_rectify: the calibration read from its calib_cam_to_cam.txt (g_rect_on), used in place of calib.txt
+static thread_local bool g_rect_on = false;
+static thread_local viso::StereoRectification g_rect;
+static thread_local viso::Matd g_rect_P1, g_rect_P2;
 
 extern "C" const char* viso_host_last_error(void) { return g_host_err.c_str(); }
 namespace viso { void set_host_error(const std::string& s) { g_host_err = s; } }   // for the other C entry points (drop_in.cpp)
@@ -158,13 +162,16 @@ extern "C" int viso_kitti_run_range(const char* seq_base, int begin, int first, 
     *n_done = 0;
     try {
         viso::Matd P1, P2;
-        if (!viso::loadCalib(std::string(seq_base) + "/calib.txt", P1, P2)) {
+        if (g_rect_on) {
+            P1 = g_rect_P1; P2 = g_rect_P2;
+        } else if (!viso::loadCalib(std::string(seq_base) + "/calib.txt", P1, P2)) {
             g_host_err = std::string("cannot read ") + seq_base + "/calib.txt";
             return VISO_ERR_ARG;
         }
         g_last_stats = viso::OdometryStats();
         std::vector<viso::FrameRecord> rec = viso::kitti_run_range(seq_base, P1, P2, begin, first, last, device, chunk, ransac_seed,
-                                                                   g_decode_threads, &g_last_stats, g_subpixel);
+                                                                   g_decode_threads, &g_last_stats, g_subpixel,
+                                                                   g_rect_on ? &g_rect : nullptr);
         for (size_t i = 0; i < rec.size(); ++i) {
             for (int j = 0; j < 6; ++j) rec8[i * 8 + (size_t)j] = rec[i].tr[j];
             rec8[i * 8 + 6] = rec[i].ok;
@@ -190,6 +197,36 @@ extern "C" void viso_kitti_set_decode_threads(int n) { g_decode_threads = n > 0 
 extern "C" int viso_kitti_set_subpixel(int mode) {
     if (mode < 0 || mode > 2) { g_host_err = "viso_kitti_set_subpixel: mode must be 0, 1 or 2"; return VISO_ERR_ARG; }
     g_subpixel = mode;
+    return VISO_OK;
+}
+
+extern "C" int viso_kitti_load_cam_to_cam(const char* file_name, double K[18], double D[10], double R[18], double P[24], int geometry[4]) {
+    if (!file_name || !K || !D || !R || !P || !geometry) { g_host_err = "viso_kitti_load_cam_to_cam: bad argument"; return VISO_ERR_ARG; }
+    viso::StereoRectification r;
+    viso::Matd P1, P2;
+    if (!viso::loadCalibCamToCam(file_name, r, P1, P2)) {
+        g_host_err = std::string("cannot read a KITTI raw calib_cam_to_cam file (S, K, D, R_rect, P_rect, S_rect of cameras 00 and 01) from ") +
+                     file_name;
+        return VISO_ERR_ARG;
+    }
+    for (int c = 0; c < 2; ++c) {
+        for (int i = 0; i < 9; ++i) { K[9 * c + i] = r.K[c].data[(size_t)i]; R[9 * c + i] = r.R[c].data[(size_t)i]; }
+        for (int i = 0; i < 5; ++i) D[5 * c + i] = r.D[c].data[(size_t)i];
+        for (int i = 0; i < 12; ++i) P[12 * c + i] = r.P[c].data[(size_t)i];
+    }
+    geometry[0] = r.raw_rows; geometry[1] = r.raw_cols; geometry[2] = r.out_rows; geometry[3] = r.out_cols;
+    return VISO_OK;
+}
+
+extern "C" int viso_kitti_set_rectify(const char* cam_to_cam_file) {
+    if (!cam_to_cam_file || !*cam_to_cam_file) { g_rect_on = false; return VISO_OK; }
+    viso::StereoRectification r;
+    viso::Matd P1, P2;
+    if (!viso::loadCalibCamToCam(cam_to_cam_file, r, P1, P2)) {
+        g_host_err = std::string("viso_kitti_set_rectify: cannot read a KITTI raw calib_cam_to_cam file from ") + cam_to_cam_file;
+        return VISO_ERR_ARG;
+    }
+    g_rect = r; g_rect_P1 = P1; g_rect_P2 = P2; g_rect_on = true;
     return VISO_OK;
 }
 

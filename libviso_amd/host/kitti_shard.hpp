@@ -45,9 +45,11 @@ int kitti_count_frames(const std::string& seq_base, int begin, int end);
 // image in the range cannot be decoded (the reference's generator stops there, src/viso.h:94-96).
 // stats (may be null): where the range's wall time went (decode / upload / GPU), see OdometryStats.
 // subpixel: the opt-in sub-pixel stereo refinement of sequence_odometry (0 = off, the reference's arithmetic).
+// rect: the opt-in rectification of raw images of sequence_odometry (null = the images are rectified already).
 std::vector<FrameRecord> kitti_run_range(const std::string& seq_base, const Matd& P1, const Matd& P2, int begin,
                                          int first, int last, int device, int chunk = 64, uint64_t ransac_seed = 0,
-                                         int decode_threads = 0, OdometryStats* stats = nullptr, int subpixel = 0);
+                                         int decode_threads = 0, OdometryStats* stats = nullptr, int subpixel = 0,
+                                         const StereoRectification* rect = nullptr);
 
 // poses[0] = I, then pose <- pose * inv(tr2mat(tr)) per solved record (src/viso.cpp:1189-1190, 1315-1321): the list
 // [I, P1, ..., Pn] the reference's code reads as.
@@ -84,6 +86,13 @@ void viso_kitti_set_decode_threads(int n);
 // sub-pixel stereo refinement mode (viso_batch_set_subpixel: 0 = off, 1, 2) of the next viso_kitti_run_range calls of this
 // thread; returns VISO_ERR_ARG for another value
 int viso_kitti_set_subpixel(int mode);
+// KITTI raw calib_cam_to_cam.txt (viso::loadCalibCamToCam): K [2][9], D [2][5], R [2][9] (R_rect), P [2][12] (P_rect),
+// geometry = raw_rows, raw_cols, out_rows, out_cols.  Camera 0 = left (*_00), 1 = right (*_01).  No device needed.
+int viso_kitti_load_cam_to_cam(const char* file_name, double K[18], double D[10], double R[18], double P[24], int geometry[4]);
+// the next viso_kitti_run_range calls of this thread read RAW images and rectify them on the device with the calibration of
+// this calib_cam_to_cam.txt, whose P_rect_00 / P_rect_01 replace the sequence's calib.txt; null or "" = off.  VISO_ERR_ARG
+// when the file cannot be read.
+int viso_kitti_set_rectify(const char* cam_to_cam_file);
 // chain n records and write the KITTI pose file (directories are created); *n_poses = lines written
 int viso_kitti_write_poses(const char* file_name, const double* rec8, int n, int* n_poses);
 // the same with the pose list the reference writes ([P1..Pn, Pn], see chain_records) when reference_pose_list != 0

@@ -252,6 +252,16 @@ private:
     int m_index, m_end;
 };
 
+// Opt-in rectification of raw camera images (viso_batch_set_rectify; NOT in the reference, which reads rectified pairs):
+// per camera (0 = left, 1 = right) the plumb-bob calibration of viso_rectify_map -- K 3x3 (K(0,1) = 0), D 1x5 (k1, k2, p1, p2,
+// k3), R 3x3 the rectifying rotation, P 3x4 the rectified projection -- the raw and the rectified geometry, and the value of
+// output pixels whose taps fall outside the raw image.
+struct StereoRectification {
+    Matd K[2], D[2], R[2], P[2];
+    int raw_rows = 0, raw_cols = 0, out_rows = 0, out_cols = 0;
+    int border = 0;
+};
+
 // sequence_odometry(P1, P2, images, dbg_dir), src/viso.h:138-139 / src/viso.cpp:1167-1330, without the
 // debug dumps: detection (MAX_FEATURE_NUM 1200, radius 5, :1171-1174), description, matching and the
 // solver all run on the device, `chunk` frames per batch.
@@ -261,8 +271,12 @@ private:
 // subpixel: the opt-in sub-pixel refinement of the stereo observations (viso_batch_set_subpixel; NOT in the reference, poses
 // not comparable with its output): 0 = off, 1 = uR, 2 = uR and vR.  A chunk's halo frame is refined again like any other
 // frame, so every chunking and partition gives the same records.
+// rect (may be null): the images are RAW, rect->raw_rows x raw_cols, and each batch rectifies them on the device to
+// rect->out_rows x out_cols (viso_batch_set_rectify) before detection; P1 / P2 are the rectified projections (P_rect).  A chunk's
+// halo frame is rectified again like any other frame.
 OdometryResult sequence_odometry(const Matd& P1, const Matd& P2, StereoImageGenerator& images,
                                  int chunk = 64, uint64_t ransac_seed = 0, uint64_t first_frame_index = 0,
-                                 int device = 0, int decode_threads = 0, int subpixel = 0);
+                                 int device = 0, int decode_threads = 0, int subpixel = 0,
+                                 const StereoRectification* rect = nullptr);
 
 }  // namespace viso

@@ -300,6 +300,7 @@ struct ChunkPipeline {
         int global0 = 0;                    // global frame index of the chunk's first frame (its halo)
         bool busy = false;
         bool stamped = false;               // the chunk in flight carries time stamps (viso_batch_stamp)
+        bool rectify = false;               // the batch has the sequence's rectification maps installed
         uint8_t* pin = nullptr;             // pinned staging buffer of the image-driven path: [frames][2][rows][cols]
         size_t pin_bytes = 0;
         explicit Slot(int device) : ctx(device) {}
@@ -331,7 +332,7 @@ struct ChunkPipeline {
             if (s.b) viso_batch_destroy(s.b);
             s.b = viso_batch_create(s.ctx.c, nf, cap, dlen);
             if (!s.b) throw std::runtime_error(std::string("viso_batch_create: ") + viso_last_error());
-            s.nf = nf; s.cap = cap; s.dlen = dlen;
+            s.nf = nf; s.cap = cap; s.dlen = dlen; s.rectify = false;
         }
         s.global0 = global0;
         return s.b;
@@ -724,7 +725,8 @@ int cpu_budget() {
 // asynchronous uploads from the slot's pinned buffer), the worker threads decode chunk c + 1 straight into the other
 // slot's pinned buffer.  The halo frame is copied from the previous slot's buffer, not decoded twice.
 OdometryResult sequence_odometry(const Matd& P1, const Matd& P2, StereoImageGenerator& images, int chunk,
-                                 uint64_t ransac_seed, uint64_t first_frame_index, int device, int decode_threads, int subpixel) {
+                                 uint64_t ransac_seed, uint64_t first_frame_index, int device, int decode_threads, int subpixel,
+                                 const StereoRectification* rect) {
     using clock = std::chrono::steady_clock;
     auto since = [](clock::time_point t0) { return std::chrono::duration<double>(clock::now() - t0).count(); };
     const auto t_start = clock::now();
@@ -753,6 +755,23 @@ OdometryResult sequence_odometry(const Matd& P1, const Matd& P2, StereoImageGene
     }
     const int rows = first_l.rows, cols = first_l.cols;
     if (first_r.rows != rows || first_r.cols != cols) throw std::invalid_argument("sequence_odometry: image size changes inside a sequence");
+    // rectification: the maps of both cameras, built once on the host (viso_rectify_map); the decoded frames are raw
+    std::vector<float> maps[4];
+    if (rect) {
+        if (rows != rect->raw_rows || cols != rect->raw_cols)
+            throw std::invalid_argument("sequence_odometry: the images are " + std::to_string(cols) + " x " + std::to_string(rows) +
+                                        ", the rectification expects raw images of " + std::to_string(rect->raw_cols) + " x " +
+                                        std::to_string(rect->raw_rows));
+        const size_t oper = (size_t)rect->out_rows * (rect->out_cols > 0 ? rect->out_cols : 0);
+        for (int c = 0; c < 2; ++c) {
+            const Matd &K = rect->K[c], &D = rect->D[c], &R = rect->R[c], &P = rect->P[c];
+            if (K.data.size() != 9 || D.data.size() != 5 || R.data.size() != 9 || P.data.size() != 12)
+                throw std::invalid_argument("sequence_odometry: rectification needs K 3x3, D 1x5, R 3x3 and P 3x4 per camera");
+            maps[2 * c].resize(oper ? oper : 1); maps[2 * c + 1].resize(oper ? oper : 1);
+            hip_check(viso_rectify_map(K.data.data(), D.data.data(), R.data.data(), P.data.data(), rect->out_rows, rect->out_cols,
+                                       maps[2 * c].data(), maps[2 * c + 1].data()), "sequence_odometry (viso_rectify_map)");
+        }
+    }
     const size_t per = (size_t)rows * cols;
     const int first_index = images.index();
     images.seek(first_index + 1);
@@ -809,7 +828,13 @@ OdometryResult sequence_odometry(const Matd& P1, const Matd& P2, StereoImageGene
         if (nf == 1 && global0 > 0) break;
         const auto t1 = clock::now();
         viso_batch* b = pipe.acquire(nf, MAX_FEATURE_NUM, VISO_DESC_LEN, global0);
-        int r = viso_batch_upload_images(b, 0, 0, nullptr, rows, cols, nullptr, nullptr);          // device buffers for this geometry
+        int r = VISO_OK;
+        if (rect && !s.rectify) {   // once per batch: the same maps for every chunk
+            r = viso_batch_set_rectify(b, rect->raw_rows, rect->raw_cols, rect->out_rows, rect->out_cols, maps[0].data(), maps[1].data(),
+                                       maps[2].data(), maps[3].data(), rect->border);
+            s.rectify = r >= 0;
+        }
+        if (r >= 0) r = viso_batch_upload_images(b, 0, 0, nullptr, rows, cols, nullptr, nullptr);   // device buffers for this geometry
         if (r >= 0) r = viso_batch_set_params(b, &st, &tm, &vp, ransac_seed, first_frame_index + (uint64_t)global0);
         if (r >= 0) r = viso_batch_set_subpixel(b, subpixel);
         if (r >= 0) r = viso_batch_stamp(b, 0);

@@ -19,6 +19,9 @@
 //                       overwrites poses.back() before pushing the clone), instead of [I, P1, ..., Pn]
 //   --subpixel m        opt-in sub-pixel stereo refinement (viso_batch_set_subpixel): 0 = off (default: the reference's
 //                       arithmetic), 1 = uR, 2 = uR and vR.  Not in the reference: such poses are not comparable with its output
+//   --rectify file      opt-in: the images are RAW (KITTI raw's unrectified drives, other rigs) and are undistorted and rectified
+//                       on the device (viso_batch_set_rectify) with KITTI raw's calib_cam_to_cam.txt `file`, which is used in
+//                       place of calib.txt (P_rect_00 / P_rect_01).  Not in the reference
 // Every rank reports where its wall time went: decode (PNG inflate on the worker threads; the calling thread's wait for
 // it is the runner's critical path), upload and GPU seconds from time stamps on the device.
 // libviso_amd/kitti_shard.py is the same runner with the gather as an RCCL all-gather (torch.distributed).
@@ -46,6 +49,7 @@ struct Args {
     int gpus = 0, rank = -1, world = 0, gather = 0, device = -1, chunk = 64, decode_threads = 0, subpixel = 0;
     bool same_device = false, reference_pose_list = false;
     unsigned long long seed = 0;
+    std::string rectify;   // calib_cam_to_cam.txt of --rectify ("" = off)
 };
 
 bool parse(int argc, char** argv, Args& a) {
@@ -62,6 +66,7 @@ bool parse(int argc, char** argv, Args& a) {
         else if (s == "--decode-threads") { if (!val(a.decode_threads)) return false; }
         else if (s == "--subpixel") { if (!val(a.subpixel) || a.subpixel < 0 || a.subpixel > 2) return false; }
         else if (s == "--reference-pose-list") a.reference_pose_list = true;
+        else if (s == "--rectify") { if (i + 1 >= argc || !*argv[i + 1]) return false; a.rectify = argv[++i]; }
         else if (s == "--seed") { if (i + 1 >= argc) return false; a.seed = std::strtoull(argv[++i], nullptr, 10); }
         else if (s == "--same-device") a.same_device = true;
         else if (s.rfind("--", 0) == 0) return false;
@@ -101,7 +106,7 @@ int main(int argc, char** argv) {
     Args a;
     if (!parse(argc, argv, a)) {
         std::printf("usage: demo result_sha seq_name begin end [--gpus W | --rank r --world W | --gather W] "
-                    "[--device d] [--same-device] [--chunk n] [--seed s] [--decode-threads n] [--reference-pose-list] [--subpixel 0|1|2]\n");   // :81-85
+                    "[--device d] [--same-device] [--chunk n] [--seed s] [--decode-threads n] [--reference-pose-list] [--subpixel 0|1|2] [--rectify calib_cam_to_cam.txt]\n");   // :81-85
         return 1;
     }
     const char* home = std::getenv("KITTI_HOME");                                              // :96
@@ -110,7 +115,16 @@ int main(int argc, char** argv) {
     const std::string result_dir = std::string(home) + "/results/" + a.seq_name + "/" + a.result_sha;   // :100
     const std::string out = result_dir + "/data/" + a.seq_name + ".txt";                       // :114
     viso::Matd P1, P2;
-    if (!viso::loadCalib(seq_base + "/calib.txt", P1, P2)) { std::fprintf(stderr, "cannot read %s/calib.txt\n", seq_base.c_str()); return 2; }
+    viso::StereoRectification rect;
+    const viso::StereoRectification* rectp = nullptr;
+    if (!a.rectify.empty()) {
+        if (!viso::loadCalibCamToCam(a.rectify, rect, P1, P2)) {
+            std::fprintf(stderr, "cannot read a KITTI raw calib_cam_to_cam file (S, K, D, R_rect, P_rect, S_rect of cameras 00 and 01) from %s\n",
+                         a.rectify.c_str());
+            return 2;
+        }
+        rectp = &rect;
+    } else if (!viso::loadCalib(seq_base + "/calib.txt", P1, P2)) { std::fprintf(stderr, "cannot read %s/calib.txt\n", seq_base.c_str()); return 2; }
     const int n_frames = viso::kitti_count_frames(seq_base, a.begin, a.end);
 
     // ---- --gpus W: fork the ranks BEFORE this process touches the GPU (the parent never does: nothing above makes a
@@ -177,7 +191,7 @@ int main(int argc, char** argv) {
             const int device = a.device >= 0 ? a.device : a.rank;
             viso::OdometryStats stats;
             std::vector<viso::FrameRecord> rec = viso::kitti_run_range(seq_base, P1, P2, a.begin, range.first, range.second,
-                                                                       device, a.chunk, a.seed, a.decode_threads, &stats, a.subpixel);
+                                                                       device, a.chunk, a.seed, a.decode_threads, &stats, a.subpixel, rectp);
             viso::mkdirs(result_dir + "/shards");
             const std::string f = rank_file(result_dir, a.seq_name, a.rank, a.world);
             if (!viso::write_records(f, range.first, range.second, rec)) { std::fprintf(stderr, "cannot write %s\n", f.c_str()); return 3; }
@@ -190,7 +204,7 @@ int main(int argc, char** argv) {
         const std::string ext = viso::kitti_image_ext(seq_base, a.begin);
         viso::StereoImageGenerator images({seq_base + "/image_0/%06d" + ext, seq_base + "/image_1/%06d" + ext}, a.begin, a.end);
         viso::OdometryResult res = viso::sequence_odometry(P1, P2, images, a.chunk, a.seed, (uint64_t)a.begin,
-                                                           a.device >= 0 ? a.device : 0, a.decode_threads, a.subpixel);   // :111
+                                                           a.device >= 0 ? a.device : 0, a.decode_threads, a.subpixel, rectp);   // :111
         viso::mkdirs(result_dir + "/data");                                                    // :112-113
         if (a.reference_pose_list && res.poses.size() > 1) {                                   // [P1, ..., Pn, Pn], see kitti_shard.hpp
             res.poses.erase(res.poses.begin());

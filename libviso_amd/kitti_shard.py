@@ -66,8 +66,24 @@ def load_host():
     L.viso_kitti_set_decode_threads.argtypes = [C.c_int]
     L.viso_kitti_set_decode_threads.restype = None
     L.viso_kitti_set_subpixel.argtypes = [C.c_int]
+    L.viso_kitti_set_rectify.argtypes = [C.c_char_p]
+    L.viso_kitti_load_cam_to_cam.argtypes = [C.c_char_p] + [C.POINTER(C.c_double)] * 4 + [C.POINTER(C.c_int)]
     L.viso_host_last_error.restype = C.c_char_p
     return L
+
+
+def load_cam_to_cam(file_name):
+    """KITTI raw calib_cam_to_cam.txt through the C++ parser (viso_kitti_load_cam_to_cam, no device): a dict in the form of
+    synth.raw_stereo_calib -- K, D, R (R_rect), P (P_rect): lists of two (camera 00 = left, 01 = right), raw_shape, out_shape."""
+    import numpy as np
+    L = load_host()
+    K, D, R, P = np.zeros(18), np.zeros(10), np.zeros(18), np.zeros(24)
+    geo = (C.c_int * 4)()
+    dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))   # noqa: E731
+    if L.viso_kitti_load_cam_to_cam(os.fsencode(file_name), dp(K), dp(D), dp(R), dp(P), geo) != 1:
+        raise ValueError(L.viso_host_last_error().decode())
+    return dict(K=[K[:9].reshape(3, 3), K[9:].reshape(3, 3)], D=[D[:5], D[5:]], R=[R[:9].reshape(3, 3), R[9:].reshape(3, 3)],
+                P=[P[:12].reshape(3, 4), P[12:].reshape(3, 4)], raw_shape=(geo[0], geo[1]), out_shape=(geo[2], geo[3]))
 
 
 def cpu_budget():
@@ -224,6 +240,9 @@ def main(argv=None):
     ap.add_argument("--subpixel", type=int, default=0, choices=(0, 1, 2),
                     help="opt-in sub-pixel stereo refinement: 0 = off (the reference's arithmetic), 1 = uR, 2 = uR and vR; "
                          "not in the reference, poses are not comparable with its output")
+    ap.add_argument("--rectify", default=None, metavar="CALIB_CAM_TO_CAM",
+                    help="opt-in: the images are raw; undistort and rectify them on the device with this KITTI raw "
+                         "calib_cam_to_cam.txt, used in place of calib.txt (not in the reference)")
     args = ap.parse_args(argv)
     home = os.environ.get("KITTI_HOME")
     if not home:
@@ -267,6 +286,9 @@ def main(argv=None):
     threads = args.decode_threads or int(os.environ.get("VISO_DECODE_THREADS", "0")) or max(1, min(64, cpu_budget() // world))
     L.viso_kitti_set_decode_threads(threads)
     if L.viso_kitti_set_subpixel(args.subpixel) != 1:
+        print(f"kitti_shard: {L.viso_host_last_error().decode()}", file=sys.stderr)
+        return 2
+    if args.rectify is not None and L.viso_kitti_set_rectify(os.fsencode(os.path.abspath(args.rectify))) != 1:
         print(f"kitti_shard: {L.viso_host_last_error().decode()}", file=sys.stderr)
         return 2
 

@@ -332,3 +332,90 @@ def make_subpixel_image_sequence(seed, n_frames, n_kp=1500, width=1241, height=3
     param = Param.default(base=base, f=f, cu=cu, cv=cv)
     return dict(images=images, kp=kp, n=n, tr_gt=tr_gt, xy_true=xy_true, param=param, F=F, P1=KITTI_P1, P2=KITTI_P2,
                 width=width, height=height)
+
+
+def _distort_normalized(x, y, D):
+    """The plumb-bob model (include/viso_hip.h, viso_rectify_map): undistorted normalized (x, y) -> distorted (xd, yd)."""
+    k1, k2, p1, p2, k3 = D
+    r2 = x * x + y * y
+    kr = 1.0 + k1 * r2 + k2 * r2 * r2 + k3 * r2 * r2 * r2
+    return (x * kr + 2.0 * p1 * x * y + p2 * (r2 + 2.0 * x * x),
+            y * kr + p1 * (r2 + 2.0 * y * y) + 2.0 * p2 * x * y)
+
+
+def _rotation(rx, ry, rz):
+    return rot_from_tr(np.array([rx, ry, rz, 0.0, 0.0, 0.0]))[0]
+
+
+def raw_stereo_calib(seed=0, raw_shape=(512, 1392), out_shape=(376, 1241), P1=KITTI_P1, P2=KITTI_P2, margin=3.0):
+    """A KITTI-raw-like stereo calibration for the opt-in rectification (viso_batch_set_rectify): per camera K (fx ~ fy),
+    D = (k1, k2, p1, p2, k3) with strong barrel distortion (k1 ~ -0.37, k2 ~ 0.2, small p1 / p2 / k3), a rectifying rotation R of
+    about 0.5 degrees, and P = P1 / P2 (KITTI_P1 / KITTI_P2 by default, so the synthetic scenes' geometry holds).  fx, fy, cx, cy
+    are chosen so that the raw image (raw_shape rows, cols) covers the rectified view (out_shape) with `margin` pixels to spare.
+    Returns dict(K, D, R, P: lists of two, raw_shape, out_shape)."""
+    rng = np.random.default_rng(seed)
+    out_rows, out_cols = out_shape
+    raw_rows, raw_cols = raw_shape
+    K, D, R = [], [], []
+    for P in (P1, P2):
+        d = np.array([rng.uniform(-0.38, -0.36), rng.uniform(0.19, 0.21), rng.uniform(-1e-3, 1e-3), rng.uniform(-1e-3, 1e-3),
+                      rng.uniform(-0.03, -0.01)])
+        r = _rotation(*np.deg2rad(rng.uniform(-0.5, 0.5, 3)))
+        # the rectified view's border -> raw normalized coordinates: its extent sets the raw intrinsics
+        e = np.concatenate([np.stack([np.arange(out_cols), np.zeros(out_cols)], 1), np.stack([np.arange(out_cols), np.full(out_cols, out_rows - 1)], 1),
+                            np.stack([np.zeros(out_rows), np.arange(out_rows)], 1), np.stack([np.full(out_rows, out_cols - 1), np.arange(out_rows)], 1)])
+        ray = np.linalg.inv(P[:, :3] @ r) @ np.stack([e[:, 0], e[:, 1], np.ones(len(e))])
+        xd, yd = _distort_normalized(ray[0] / ray[2], ray[1] / ray[2], d)
+        f = min((raw_cols - 1 - 2 * margin) / (xd.max() - xd.min()), (raw_rows - 1 - 2 * margin) / (yd.max() - yd.min()))
+        fx, fy = f, f * rng.uniform(0.995, 1.005)
+        cx = (raw_cols - 1) / 2.0 - fx * (xd.max() + xd.min()) / 2.0
+        cy = (raw_rows - 1) / 2.0 - fy * (yd.max() + yd.min()) / 2.0
+        K.append(np.array([[fx, 0.0, cx], [0.0, fy, cy], [0.0, 0.0, 1.0]]))
+        D.append(d)
+        R.append(r)
+    return dict(K=K, D=D, R=R, P=[np.asarray(P1, np.float64), np.asarray(P2, np.float64)], raw_shape=tuple(raw_shape),
+                out_shape=tuple(out_shape))
+
+
+def raw_to_rectified(calib, side, iters=20):
+    """For every raw pixel of camera `side`, the rectified-image position it shows: undistort iteratively (fixed point, like
+    OpenCV's undistortPoints), rotate by R, project with P33.  Returns (u, v) float64 arrays of raw_shape."""
+    raw_rows, raw_cols = calib["raw_shape"]
+    K, d, r, P = calib["K"][side], calib["D"][side], calib["R"][side], calib["P"][side]
+    Y, X = np.mgrid[0:raw_rows, 0:raw_cols].astype(np.float64)
+    xd, yd = (X - K[0, 2]) / K[0, 0], (Y - K[1, 2]) / K[1, 1]
+    x, y = xd.copy(), yd.copy()
+    k1, k2, p1, p2, k3 = d
+    for _ in range(iters):
+        r2 = x * x + y * y
+        kr = 1.0 + k1 * r2 + k2 * r2 * r2 + k3 * r2 * r2 * r2
+        x = (xd - (2.0 * p1 * x * y + p2 * (r2 + 2.0 * x * x))) / kr
+        y = (yd - (p1 * (r2 + 2.0 * y * y) + 2.0 * p2 * x * y)) / kr
+    p = P[:, :3] @ r @ np.stack([x.ravel(), y.ravel(), np.ones(x.size)])
+    return (p[0] / p[2]).reshape(X.shape), (p[1] / p[2]).reshape(X.shape)
+
+
+def distort_image_sequence(seq, calib, seed=0, fill_sigma=6.0):
+    """Raw images of a rectified synthetic sequence (make_image_sequence / make_subpixel_image_sequence): for every raw pixel,
+    the rectified position it shows (raw_to_rectified) is sampled bilinearly in float64 from the rectified image; raw pixels that
+    see nothing of it get background noise N(128, fill_sigma) from a random stream of its own (seed).  Returns a copy of seq
+    with images [nf][2][raw_rows][raw_cols] uint8, the rectified ones as images_rect, and calib."""
+    rng = np.random.default_rng(seed)
+    rect = seq["images"]
+    nf, _, rows, cols = rect.shape
+    assert (rows, cols) == tuple(calib["out_shape"])
+    raw_rows, raw_cols = calib["raw_shape"]
+    raw = np.empty((nf, 2, raw_rows, raw_cols), np.uint8)
+    for side in (0, 1):
+        u, v = raw_to_rectified(calib, side)
+        inside = (u >= 0) & (u <= cols - 1) & (v >= 0) & (v <= rows - 1)
+        uc, vc = np.clip(u, 0, cols - 1), np.clip(v, 0, rows - 1)
+        x0 = np.minimum(np.floor(uc).astype(int), cols - 2); y0 = np.minimum(np.floor(vc).astype(int), rows - 2)
+        ax, ay = uc - x0, vc - y0
+        for t in range(nf):
+            img = rect[t, side].astype(np.float64)
+            s = ((1 - ax) * (1 - ay) * img[y0, x0] + ax * (1 - ay) * img[y0, x0 + 1] + (1 - ax) * ay * img[y0 + 1, x0] +
+                 ax * ay * img[y0 + 1, x0 + 1])
+            s = np.where(inside, s, rng.normal(128.0, fill_sigma, s.shape))
+            raw[t, side] = np.clip(np.rint(s), 0, 255).astype(np.uint8)
+    return dict(seq, images=raw, images_rect=rect, calib=calib)
