@@ -495,6 +495,64 @@ int viso_batch_get_image_geometry(viso_batch* b, int* rows, int* cols);
 int viso_rectify_images(const uint8_t* raw, int n, int raw_rows, int raw_cols, const float* mapx, const float* mapy, int out_rows,
                         int out_cols, int border, uint8_t* out);
 
+/* ------------------------------------------------ motion covariance (opt-in; NOT in the reference)
+ *
+ * For one frame: L = the final inlier list (ascending point indices, what viso_batch_get_pose returns), n = |L|; tr the frame's
+ * final motion; (f, cu, cv, b) from viso_param; j = 0..n-1 the position in L, k = L[j] the point; X = (X, Y, Z) the
+ * previous-frame point k, Xc = R(tr) X + t (Xc, Yc, Zc).
+ *   J_j   4x6  d pred_k / d tr at tr: compute_J (src/viso.cpp:1401-1497) without the weight;
+ *   r_j   4    obs[:,k] - pred_k (unweighted);
+ *   w_j        1 / (|obs[0][j] - cu| / |cu| + 0.05): the estimator's weight of the j-th entry -- column j, not k (Q6);
+ *   T_k   3x3  dX / d(uL, vL, uR) of the previous frame's triangulation (src/viso.cpp:1137-1162), d = f b / Z, columns
+ *              (b/d - X/d, -Y/d, -Z/d), (0, b/d, 0), (X/d, Y/d, Z/d)  (vR is not used by triangulation);
+ *   Jx_j  4x3  d pred / d X = Pc R, Pc rows uL (f/Zc, 0, -f Xc/Zc^2), vL (0, f/Zc, -f Yc/Zc^2),
+ *              uR (f/Zc, 0, -f (Xc-b)/Zc^2), vR = the vL row;
+ *   M_j = Jx_j T_k  4x3.
+ * Under iid pixel noise sigma^2 on every keypoint coordinate of both frames:
+ *   A = sum w_j^2 J_j'J_j,  B = sum w_j^4 J_j' (I4 + M_j M_j') J_j,  cov = sigma^2 A^-1 B A^-1  (the weighted estimator's sandwich;
+ *   parameter order of tr: rx, ry, rz in rad, tx, ty, tz in units of base);
+ *   g = sum w_j^2 J_j' r_j,  delta = A^-1 g (the step to the weighted least-squares optimum the reported tr may stop short of:
+ *   the reference's convergence test fabs(p > thresh), :1610, leaves a large negative step unapplied),
+ *   gap = g' B^-1 g / sigma^2 (= delta' cov^-1 delta; 0 when sigma^2 = 0).  tr itself is never changed.
+ * sigma^2: mode 1 estimates it, sigma2 = sum |r_j|^2 / (sum (4 + |M_j|_F^2) - 6); mode 2 takes sigma_px^2 from the caller
+ * (finite and > 0, else VISO_ERR_ARG); mode 0 is off (the default: every run launches what it launched before).
+ * status 1 valid; 0 no pose (frame 0, or ok == 0); -1 n < 6; -2 A or B not positive definite (a Cholesky pivot that is not
+ * > 1e-12 x the original diagonal entry).  When status != 1, cov, delta, sigma2 and gap are zeros.
+ * One HIP kernel (motion_cov_kernel) serves every path; its summation order depends on n only (fixed DPP and LDS trees, no
+ * atomics), so the batch at any chunking and the direct call give byte-identical records for the same inputs. */
+typedef struct viso_motion_cov {
+    double cov[36];     /* 6 x 6 row-major, symmetric */
+    double delta[6];
+    double sigma2;
+    double gap;
+    int32_t status;
+    int32_t n;          /* |L| */
+} viso_motion_cov;
+
+/* mode 0 (off), 1 (estimated sigma) or 2 (sigma = sigma_px) for the batch's next runs: viso_batch_run and viso_batch_run_images
+ * (not matcher_only) then launch motion_cov_kernel on the RANSAC stream behind the refit.  VISO_ERR_ARG: another mode, or mode 2
+ * with a sigma_px that is not finite and > 0. */
+int viso_batch_set_covariance(viso_batch* b, int mode, double sigma_px);
+/* The record of frame t / of all n_frames frames (frame 0: status 0) from the last run.  VISO_ERR_ARG when the last run computed
+ * none (mode 0, or matcher_only); the batch stays usable.  Synchronise like the other getters. */
+int viso_batch_get_covariance(viso_batch* b, int t, viso_motion_cov* out);
+int viso_batch_get_covariances(viso_batch* b, viso_motion_cov* out /* [n_frames] */);
+/* Frame t's solver inputs from the last run: X3xcap [3][cap] the previous-frame points, obs4xcap [4][cap] (uL, vL, uR, vR), rows of
+ * cap doubles of which the first *m columns are set (either pointer may be NULL).  Synchronises like the other getters. */
+int viso_batch_get_points(viso_batch* b, int t, double* X3xcap, double* obs4xcap, int* m);
+/* Host pointers, default context, the batch's kernel: X 3 x m, obs 4 x m (row-major), tr 6, inl n_inl indices in [0, m) with
+ * n_inl <= m; mode 1 or 2.  The pose counts as solved (ok = 1). */
+int viso_pose_covariance(const double* X, const double* obs, int m, const double tr[6], const int32_t* inl, int n_inl,
+                         const viso_param* param, int mode, double sigma_px, viso_motion_cov* out);
+/* Host only (no device).  Propagates the records along hostmath.chain_poses' list: entry 0 is the identity (zero covariance);
+ * every frame t with ok[t] != 0 appends P_k = P_{k-1} inv(T_k), T_k = tr2mat(tr[t]).  With the right perturbation P = P^ Exp(xi),
+ * xi = (phi, rho), rotation first:
+ *   S_k = Ad(T_k) S_{k-1} Ad(T_k)' + G_k cov_t G_k',  Ad(T) = [[R, 0], [t^ R, R]],  G_k = d Log(T_k inv(T(tr))) / d tr at tr[t].
+ * An entry is valid until the first chained frame whose status != 1 and invalid (zeros) from there on.  tr n x 6, ok n, cov n;
+ * pose_cov36 and valid hold n + 1 entries; *n_out = the number of entries written. */
+int viso_chain_covariances(const double* tr, const int32_t* ok, const viso_motion_cov* cov, int n, double* pose_cov36,
+                           int32_t* valid, int* n_out);
+
 #ifdef __cplusplus
 }
 #endif

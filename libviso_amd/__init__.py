@@ -16,7 +16,8 @@ import weakref
 
 import numpy as np
 
-from .abi import (DESC_LEN, MatchParams, Param, declare_common, declare_rectify, declare_subpixel, f32p, f64p, i32p, i64p, intp, ptr)
+from .abi import (DESC_LEN, MOTION_COV_DTYPE, MatchParams, Param, declare_common, declare_covariance, declare_rectify, declare_subpixel,
+                  f32p, f64p, i32p, i64p, intp, ptr)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("VISO_HIP_SO") or os.path.join(_HERE, "libviso_hip.so")   # VISO_HIP_SO: another build of the library (A/B runs)
@@ -116,6 +117,8 @@ def load():
         declare_subpixel(L)
     if hasattr(L, "viso_batch_set_rectify"):
         declare_rectify(L)
+    if hasattr(L, "viso_batch_set_covariance"):
+        declare_covariance(L)
     L.viso_harris_response.argtypes = [C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_double, f32p]
     L.viso_detect_harris_binned.argtypes = [C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                             C.c_double, f32p, f32p, intp]
@@ -445,6 +448,40 @@ def rectify_images(raw, mapx, mapy, out_shape, border=0):
 HARRIS_K = float(np.float32(0.04))   # the reference's intended default (float k = .04, src/viso.cpp:915)
 
 
+def pose_covariance(X, obs, tr, inliers, param, mode=1, sigma=None):
+    """viso_pose_covariance: the motion covariance record (a 0-d MOTION_COV_DTYPE array) of one frame's solve -- X 3 x m, obs 4 x m,
+    tr 6, inliers the final inlier list; mode 1 estimates sigma^2, mode 2 takes sigma (pixels)."""
+    L = load()
+    X, obs, tr, inl = _f64(X), _f64(obs), _f64(tr), _i32(inliers)
+    if X.ndim != 2 or X.shape[0] != 3 or obs.shape != (4, X.shape[1]) or tr.shape != (6,):
+        raise ValueError(f"pose_covariance: X must be (3, m), obs (4, m) and tr (6,); got {X.shape}, {obs.shape}, {tr.shape}")
+    m = X.shape[1]
+    out = np.zeros((), MOTION_COV_DTYPE)
+    r = L.viso_pose_covariance(ptr(X, C.c_double), ptr(obs, C.c_double), m, ptr(tr, C.c_double), ptr(inl, C.c_int32), len(inl),
+                               C.byref(param), int(mode), float(sigma) if sigma is not None else 0.0, out.ctypes.data)
+    if r != 1:
+        _err("viso_pose_covariance", r)
+    return out
+
+
+def chain_covariances(tr, ok, covs):
+    """viso_chain_covariances (host only): (pose_cov [k][6][6], valid [k]) along hostmath.chain_poses' list, k = 1 + sum(ok != 0)."""
+    L = load()
+    tr, ok = _f64(np.reshape(tr, (-1, 6))), _i32(ok)
+    covs = np.ascontiguousarray(covs, MOTION_COV_DTYPE)
+    n = len(tr)
+    if len(ok) != n or len(covs) != n:
+        raise ValueError("chain_covariances: tr, ok and covs need one entry per frame")
+    out = np.zeros((n + 1, 6, 6))
+    valid = np.zeros(n + 1, np.int32)
+    k = C.c_int(0)
+    r = L.viso_chain_covariances(ptr(tr, C.c_double), ptr(ok, C.c_int32), covs.ctypes.data, n, ptr(out, C.c_double),
+                                 ptr(valid, C.c_int32), C.byref(k))
+    if r != 1:
+        _err("viso_chain_covariances", r)
+    return out[:k.value].copy(), valid[:k.value].copy()
+
+
 def harris_response(img, k=HARRIS_K):
     """cv::cornerHarris(img, R, 3, 5, k, BORDER_DEFAULT) restated (reference src/viso.cpp:930)."""
     L = load()
@@ -626,6 +663,33 @@ class Batch:
         out = np.empty(shape, np.uint8)
         self._chk("viso_batch_get_image", self.L.viso_batch_get_image(self.h, int(t), int(side), ptr(out, C.c_uint8)))
         return out
+
+    def set_covariance(self, mode, sigma=None):
+        """viso_batch_set_covariance: 0 = off (default), 1 = per-frame motion covariance with sigma^2 estimated, 2 = with the given
+        sigma (pixels), for the next runs (run, and run_images unless matcher_only)."""
+        self._chk("viso_batch_set_covariance",
+                  self.L.viso_batch_set_covariance(self.h, int(mode), float(sigma) if sigma is not None else 0.0))
+
+    def covariance(self, t):
+        """The motion covariance record of frame t from the last run (a 0-d MOTION_COV_DTYPE array)."""
+        out = np.zeros((), MOTION_COV_DTYPE)
+        self._chk("viso_batch_get_covariance", self.L.viso_batch_get_covariance(self.h, int(t), out.ctypes.data))
+        return out
+
+    def covariances(self):
+        """The records of all frames from the last run: structured array [n_frames] of MOTION_COV_DTYPE (frame 0: status 0)."""
+        out = np.zeros(self.nf, MOTION_COV_DTYPE)
+        self._chk("viso_batch_get_covariances", self.L.viso_batch_get_covariances(self.h, out.ctypes.data))
+        return out
+
+    def points(self, t):
+        """(X [3][m], obs [4][m]) float64: frame t's solver inputs from the last run (previous-frame points, (uL, vL, uR, vR))."""
+        X = np.zeros((3, self.cap))
+        obs = np.zeros((4, self.cap))
+        m = C.c_int(0)
+        self._chk("viso_batch_get_points",
+                  self.L.viso_batch_get_points(self.h, int(t), ptr(X, C.c_double), ptr(obs, C.c_double), C.byref(m)))
+        return X[:, :m.value].copy(), obs[:, :m.value].copy()
 
     def set_params(self, stereo, temporal, param, seed=0, first_frame=0):
         self._chk("viso_batch_set_params", self.L.viso_batch_set_params(

@@ -144,3 +144,32 @@ def declare_rectify(lib):
     lib.viso_batch_get_image.argtypes = [C.c_void_p, C.c_int, C.c_int, u8p]
     lib.viso_batch_get_image_geometry.argtypes = [C.c_void_p, intp, intp]
     lib.viso_rectify_images.argtypes = [u8p, C.c_int, C.c_int, C.c_int, f32p, f32p, C.c_int, C.c_int, C.c_int, u8p]
+
+
+class MotionCov(C.Structure):
+    """struct viso_motion_cov (include/viso_hip.h, "motion covariance")."""
+    _fields_ = [
+        ("cov", C.c_double * 36),
+        ("delta", C.c_double * 6),
+        ("sigma2", C.c_double),
+        ("gap", C.c_double),
+        ("status", C.c_int32),
+        ("n", C.c_int32),
+    ]
+
+
+# the same layout as a numpy structured dtype (Batch.covariances, pose_covariance)
+MOTION_COV_DTYPE = np.dtype([("cov", np.float64, (6, 6)), ("delta", np.float64, 6), ("sigma2", np.float64), ("gap", np.float64),
+                             ("status", np.int32), ("n", np.int32)])
+assert MOTION_COV_DTYPE.itemsize == C.sizeof(MotionCov) == 360
+
+
+def declare_covariance(lib):
+    """Prototypes of the opt-in motion covariance (include/viso_hip.h; libviso_hip.so only)."""
+    vp = C.c_void_p
+    lib.viso_batch_set_covariance.argtypes = [vp, C.c_int, C.c_double]
+    lib.viso_batch_get_covariance.argtypes = [vp, C.c_int, vp]
+    lib.viso_batch_get_covariances.argtypes = [vp, vp]
+    lib.viso_batch_get_points.argtypes = [vp, C.c_int, f64p, f64p, intp]
+    lib.viso_pose_covariance.argtypes = [f64p, f64p, C.c_int, f64p, i32p, C.c_int, C.POINTER(Param), C.c_int, C.c_double, vp]
+    lib.viso_chain_covariances.argtypes = [f64p, i32p, vp, C.c_int, f64p, i32p, intp]

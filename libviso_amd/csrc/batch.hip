@@ -42,6 +42,9 @@ struct viso_batch {
     // opt-in rectification of raw images (rectify.hip): on while rmap != null; the quantised maps [2][img_rows * img_cols], the
     // raw staging buffer, its geometry and the border value
     RectEntry* rmap = nullptr; uint8_t* raw = nullptr; int raw_rows = 0, raw_cols = 0, rborder = 0; size_t raw_bytes = 0;
+    // opt-in motion covariance (covariance.hip): the mode and sigma asked for, the records [nf] (allocated on the first request,
+    // frame 0 stays zero: status 0), and the mode the last run computed them with (0: the last run computed none)
+    int cov_mode = 0; double cov_sigma = 0.0; viso_motion_cov* cov = nullptr; int cov_last = 0;
     JoinItem* join; SolverItem* sitems;
     int *circ, *pcl, *mc;
     double* tr_h; int *ok_h, *cnt_h, *hq; char* rot;   // hq: list of undecided hypotheses (launch_ransac)
@@ -146,7 +149,7 @@ int viso_batch_free(viso_batch* b, bool keep_shell) {
     void* ptrs[] = {b->h_part, b->h_resp, b->h_tmp_kp, b->h_tmp_resp, b->h_cnt, b->images, b->skp, b->sidx, b->rank, b->bstart, b->xinfo, b->views,
                     b->kp, b->desc, b->n, b->packed, b->packed8, b->r8cnt, b->sums, b->zero, b->probs, b->res, b->sorted,
                     b->pos, b->m_cnt, b->scored, b->x_c, b->Xp_c, b->join,
-                    b->sitems, b->circ, b->pcl, b->mc, b->uv, b->rmap, b->raw, b->tr /* + ok, n_inl */, b->inl, b->tr_h, b->ok_h, b->cnt_h, b->hq, b->samp_h, b->rot, b->tile_flag, b->qord, b->ovf_q};
+                    b->sitems, b->circ, b->pcl, b->mc, b->uv, b->cov, b->rmap, b->raw, b->tr /* + ok, n_inl */, b->inl, b->tr_h, b->ok_h, b->cnt_h, b->hq, b->samp_h, b->rot, b->tile_flag, b->qord, b->ovf_q};
     for (void* p : ptrs) if (p) note(hipFree(p));
     if (keep_shell) { b->ctx = nullptr; b->events.clear(); b->desc_family.clear(); b->desc_family.shrink_to_fit(); }
     else delete b;
@@ -541,6 +544,7 @@ extern "C" int viso_batch_kernel_timing(viso_batch* b, int enable) {
 }
 
 static int run_matcher_impl(viso_batch* b, bool from_images) {
+    if (!dead(b)) b->cov_last = 0;   // the records of an earlier run are not this run's
     if (dead(b) || !b->params_set) { viso_set_error("viso_batch_run: parameters not set"); return VISO_ERR_ARG; }
     if (from_images && (!b->images || b->dlen != VISO_DESC_LEN)) {
         viso_set_error("viso_batch_run_images: no images uploaded (or descriptor length is not 121)");
@@ -794,6 +798,61 @@ extern "C" int viso_batch_get_subpixel(viso_batch* b, int t, float* uv, int* out
     return VISO_OK;
 }
 
+// Opt-in motion covariance (not in the reference; covariance.hip).  The records are allocated (zeroed) on the first request.
+extern "C" int viso_batch_set_covariance(viso_batch* b, int mode, double sigma_px) {
+    if (dead(b) || (mode != 0 && !motion_cov_args_ok(mode, sigma_px))) {
+        viso_set_error("viso_batch_set_covariance: bad argument (mode 0, 1, or 2 with a finite sigma_px > 0)");
+        return VISO_ERR_ARG;
+    }
+    int r;
+    if ((r = enter(b)) < 0) return r;
+    if (mode && !b->cov) {
+        if ((r = batch_sync(b)) < 0) return r;
+        if ((r = dalloc(&b->cov, (size_t)b->nf)) < 0) return r;
+        HIP_TRY(hipMemset(b->cov, 0, sizeof(viso_motion_cov) * (size_t)b->nf));
+    }
+    b->cov_mode = mode;
+    b->cov_sigma = mode == 2 ? sigma_px : 0.0;
+    return VISO_OK;
+}
+
+static int cov_ready(viso_batch* b, const char* where) {
+    const int rs_ = batch_sync(b);
+    if (rs_ < 0) return rs_;
+    if (!b->cov_last) { viso_set_error("%s: the last run computed no covariance (mode 0, or matcher_only)", where); return VISO_ERR_ARG; }
+    return VISO_OK;
+}
+
+extern "C" int viso_batch_get_covariance(viso_batch* b, int t, viso_motion_cov* out) {
+    if (!slot_ok(b, 0, t) || !out) { viso_set_error("viso_batch_get_covariance: bad argument"); return VISO_ERR_ARG; }
+    int r;
+    if ((r = cov_ready(b, "viso_batch_get_covariance")) < 0) return r;
+    HIP_TRY(hipMemcpy(out, b->cov + t, sizeof(viso_motion_cov), hipMemcpyDeviceToHost));
+    return VISO_OK;
+}
+
+extern "C" int viso_batch_get_covariances(viso_batch* b, viso_motion_cov* out) {
+    if (dead(b) || !out) { viso_set_error("viso_batch_get_covariances: bad argument"); return VISO_ERR_ARG; }
+    int r;
+    if ((r = cov_ready(b, "viso_batch_get_covariances")) < 0) return r;
+    HIP_TRY(hipMemcpy(out, b->cov, sizeof(viso_motion_cov) * (size_t)b->nf, hipMemcpyDeviceToHost));
+    return VISO_OK;
+}
+
+// Frame t's solver inputs (what the circle join wrote for the last run): Xp_c and x_c rows of cap doubles.
+extern "C" int viso_batch_get_points(viso_batch* b, int t, double* X3xcap, double* obs4xcap, int* m) {
+    if (!slot_ok(b, 0, t) || !m) { viso_set_error("viso_batch_get_points: bad argument"); return VISO_ERR_ARG; }
+    { const int rs_ = batch_sync(b); if (rs_ < 0) return rs_; }
+    int mm = 0;
+    HIP_TRY(hipMemcpy(&mm, b->mc + t, sizeof(int), hipMemcpyDeviceToHost));
+    mm = mm < 0 ? 0 : mm > b->cap ? b->cap : mm;
+    const size_t c = (size_t)b->cap;
+    if (X3xcap) HIP_TRY(hipMemcpy(X3xcap, b->Xp_c + (size_t)t * 3 * c, sizeof(double) * 3 * c, hipMemcpyDeviceToHost));
+    if (obs4xcap) HIP_TRY(hipMemcpy(obs4xcap, b->x_c + (size_t)t * 4 * c, sizeof(double) * 4 * c, hipMemcpyDeviceToHost));
+    *m = mm;
+    return VISO_OK;
+}
+
 // Opt-in rectification of raw images (not in the reference; rectify.hip).  Synchronous like the other setters: the batch's work
 // in flight finishes first, then the maps are quantised on the host and the buffers (re)allocated.
 extern "C" int viso_batch_set_rectify(viso_batch* b, int raw_rows, int raw_cols, int out_rows, int out_cols, const float* mapxL,
@@ -876,7 +935,10 @@ static int run_rest(viso_batch* b) {
         // the run's poses, flags and inlier counts into the pinned mirror (the kernel writes over PCIe; viso_batch_get_poses
         // waits for the streams and reads host memory)
         if ((r = plain_blit(ss, b->tr, b->pose_pin, b->pose_bytes / 4)) < 0) return r;
+        // opt-in: the motion covariance from what the refit left (tr, ok, the final inlier list), frames 1 .. nf-1
+        if (b->cov_mode && (r = launch_motion_cov(ss, b->sitems, b->nf - 1, b->sp, b->cov_mode, b->cov_sigma, b->cov + 1)) < 0) return r;
     }
+    b->cov_last = b->cov_mode;
     if (ss != s) {
         HIP_TRY(hipEventRecord(b->ev_ransac, ss));
         b->ransac_pending = true;

@@ -448,6 +448,11 @@ bool rect_geometry_ok(int raw_rows, int raw_cols, int out_rows, int out_cols);
 // image (f, side) of raw / out at f * fs + side * ss; map [sides][out_rows * out_cols]; frames 0 .. n_frames-1 of the pointers
 int launch_rectify(hipStream_t s, const uint8_t* raw, size_t raw_fs, size_t raw_ss, int raw_cols, uint8_t* out, size_t out_fs,
                    size_t out_ss, const RectEntry* map, int out_rows, int out_cols, int n_frames, int sides, int border);
+// covariance.hip: the opt-in motion covariance (viso_batch_set_covariance); one record per item, out[item], read from the item's
+// X, obs, m_ptr, ld, tr, ok, n_inl, inl (what ransac_refit_kernel left)
+int launch_motion_cov(hipStream_t s, const SolverItem* items_dev, int n_items, const SolverParamsDev& sp, int mode, double sigma,
+                      viso_motion_cov* out);
+bool motion_cov_args_ok(int mode, double sigma_px);   // mode 1, or mode 2 with a finite sigma_px > 0
 int launch_extract_pack(hipStream_t s, const ImageView* imgs_dev, int n_img, int cap, const uint8_t* images,
                         int rows, int cols, int extras, int r8s, int* r8cnt);
 int launch_harris_response(hipStream_t s, const uint8_t* images, int n_img, int rows, int cols, double k, float* resp);

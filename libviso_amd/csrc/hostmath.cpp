@@ -107,3 +107,68 @@ extern "C" void viso_ransac_samples(uint64_t seed, uint64_t frame, int iters, in
         out[3 * h] = s3[0]; out[3 * h + 1] = s3[1]; out[3 * h + 2] = s3[2];
     }
 }
+
+// Propagation of the per-frame motion covariances along hostmath.chain_poses' list (include/viso_hip.h, "motion covariance";
+// DESIGN.md 5.8).  Right perturbation P = P^ Exp(xi), xi = (phi, rho): P_k = P_{k-1} inv(T_k) gives
+// S_k = Ad(T_k) S_{k-1} Ad(T_k)' + G_k cov_k G_k'.  G_k = d Log(T_k inv(T(tr))) / d tr at tr_k: with dR = [w]x R (w_rx = e_x,
+// w_ry = Rx e_y, w_rz = Rx Ry e_z, the columns of W), T_k inv(T(tr)) = [I - [w]x | -dt - [t]x w] to first order, so
+// G = [[-W, 0], [-[t]x W, -I]].
+static void mat6_mul(const double* a, const double* b, double* out, bool bt) {   // out = a b (bt: a b')
+    for (int i = 0; i < 6; ++i)
+        for (int j = 0; j < 6; ++j) {
+            double s = 0;
+            for (int k = 0; k < 6; ++k) s += a[6 * i + k] * (bt ? b[6 * j + k] : b[6 * k + j]);
+            out[6 * i + j] = s;
+        }
+}
+
+extern "C" int viso_chain_covariances(const double* tr, const int32_t* ok, const viso_motion_cov* cov, int n, double* pose_cov36,
+                                      int32_t* valid, int* n_out) {
+    if (n < 0 || !pose_cov36 || !valid || !n_out || (n > 0 && (!tr || !ok || !cov))) {
+        viso_set_error("viso_chain_covariances: bad argument");
+        return VISO_ERR_ARG;
+    }
+    double S[36] = {0}, Ad[36], G[36], tmp[36], a[36], c[36];
+    memset(pose_cov36, 0, sizeof(double) * 36);
+    valid[0] = 1;
+    bool live = true;
+    int k = 0;
+    for (int t = 0; t < n; ++t) {
+        if (!ok[t]) continue;
+        ++k;
+        live = live && cov[t].status == 1;
+        double* out = pose_cov36 + 36 * (size_t)k;
+        valid[k] = live ? 1 : 0;
+        if (!live) { memset(out, 0, sizeof(double) * 36); continue; }
+        double T[16];
+        viso_tr2mat(tr + 6 * (size_t)t, T);
+        const double R[3][3] = {{T[0], T[1], T[2]}, {T[4], T[5], T[6]}, {T[8], T[9], T[10]}};
+        const double tv[3] = {T[3], T[7], T[11]};
+        const double tx[3][3] = {{0, -tv[2], tv[1]}, {tv[2], 0, -tv[0]}, {-tv[1], tv[0], 0}};
+        const double sx = sin(tr[6 * t]), cx = cos(tr[6 * t]), sy = sin(tr[6 * t + 1]), cy = cos(tr[6 * t + 1]);
+        const double W[3][3] = {{1, 0, sy}, {0, cx, -sx * cy}, {0, sx, cx * cy}};   // columns w_rx, w_ry, w_rz
+        memset(Ad, 0, sizeof(Ad));
+        memset(G, 0, sizeof(G));
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) {
+                double tR = 0, tW = 0;
+                for (int l = 0; l < 3; ++l) { tR += tx[i][l] * R[l][j]; tW += tx[i][l] * W[l][j]; }
+                Ad[6 * i + j] = R[i][j];
+                Ad[6 * (i + 3) + j + 3] = R[i][j];
+                Ad[6 * (i + 3) + j] = tR;
+                G[6 * i + j] = -W[i][j];
+                G[6 * (i + 3) + j] = -tW;
+                G[6 * (i + 3) + j + 3] = i == j ? -1.0 : 0.0;
+            }
+        mat6_mul(Ad, S, tmp, false);
+        mat6_mul(tmp, Ad, a, true);
+        mat6_mul(G, cov[t].cov, tmp, false);
+        mat6_mul(tmp, G, c, true);
+        for (int i = 0; i < 36; ++i) S[i] = a[i] + c[i];
+        for (int i = 0; i < 6; ++i)   // exactly symmetric
+            for (int j = 0; j < i; ++j) S[6 * i + j] = S[6 * j + i] = 0.5 * (S[6 * i + j] + S[6 * j + i]);
+        memcpy(out, S, sizeof(S));
+    }
+    *n_out = k + 1;
+    return VISO_OK;
+}

@@ -557,25 +557,6 @@ __device__ __forceinline__ double uni(double v) {
     return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
 }
 
-// Sum of a double over the wave, valid in lane 63: row_shr 1, 2, 4, 8 inside the rows of 16 lanes (lanes without a source
-// add 0), then row_bcast:15 into rows 1 and 3 and row_bcast:31 into rows 2 and 3 (gfx9 reduction idiom; the halves of the
-// double move as two 32-bit DPP moves).
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double dpp_f64(double v) {
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, ROW_MASK, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, ROW_MASK, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double wave_sum_to_lane63(double v) {
-    v += dpp_f64<0x111, 0xf>(v);   // row_shr:1
-    v += dpp_f64<0x112, 0xf>(v);   // row_shr:2
-    v += dpp_f64<0x114, 0xf>(v);   // row_shr:4
-    v += dpp_f64<0x118, 0xf>(v);   // row_shr:8  -> lane 15 of every row = the row's sum
-    v += dpp_f64<0x142, 0xa>(v);   // row_bcast:15 into rows 1 and 3
-    v += dpp_f64<0x143, 0xc>(v);   // row_bcast:31 into rows 2 and 3 -> lane 63 = the wave's sum
-    return v;
-}
-
 #ifdef VISO_DEBUG_VARIANTS   // timing aid (tools/experiments/refit_phases.py): 100 MHz time stamps of the refit's phases, item 0
 __device__ unsigned long long viso_dbg_clk[16];
 extern "C" int viso_debug_refit_clocks(unsigned long long* out16) {

@@ -3,6 +3,7 @@
 #include "kitti_shard.hpp"
 
 #include <climits>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <sys/stat.h>
@@ -51,14 +52,16 @@ int kitti_count_frames(const std::string& seq_base, int begin, int end) {
 
 std::vector<FrameRecord> kitti_run_range(const std::string& seq_base, const Matd& P1, const Matd& P2, int begin,
                                          int first, int last, int device, int chunk, uint64_t ransac_seed,
-                                         int decode_threads, OdometryStats* stats, int subpixel, const StereoRectification* rect) {
+                                         int decode_threads, OdometryStats* stats, int subpixel, const StereoRectification* rect,
+                                         int cov_mode, double cov_sigma, std::vector<viso_motion_cov>* cov) {
     std::vector<FrameRecord> rec;
+    if (cov) cov->clear();
     if (last <= first) return rec;
     const std::string ext = kitti_image_ext(seq_base, begin);
     StereoImageGenerator images({seq_base + "/image_0/%06d" + ext, seq_base + "/image_1/%06d" + ext},
                                 begin + first, begin + last);
     OdometryResult res = sequence_odometry(P1, P2, images, chunk, ransac_seed, (uint64_t)(begin + first), device, decode_threads,
-                                           subpixel, rect);
+                                           subpixel, rect, cov ? cov_mode : 0, cov_sigma);
     if (stats) *stats = res.stats;
     // res.ok / res.tr / res.n_inliers: one entry per frame read, entry 0 = this range's first frame (no pose)
     for (size_t t = 1; t < res.ok.size(); ++t) {
@@ -69,8 +72,63 @@ std::vector<FrameRecord> kitti_run_range(const std::string& seq_base, const Matd
         r.frame = begin + first + (int)t;
         r.reserved = 0;
         rec.push_back(r);
+        if (cov && t < res.cov.size()) cov->push_back(res.cov[t]);
     }
     return rec;
+}
+
+bool write_covariance_file(const std::string& file_name, const viso_motion_cov* rec, size_t n) {
+    const std::string tmp = file_name + ".tmp";
+    FILE* fp = std::fopen(tmp.c_str(), "w");
+    if (!fp) return false;
+    bool ok = true;
+    for (size_t i = 0; i < n && ok; ++i) {
+        const viso_motion_cov& c = rec[i];
+        ok = std::fprintf(fp, "%d %d %.17g %.17g", (int)c.status, (int)c.n, c.sigma2, c.gap) > 0;
+        for (int p = 0; p < 6 && ok; ++p)
+            for (int q = p; q < 6 && ok; ++q) ok = std::fprintf(fp, " %.17g", c.cov[6 * p + q]) > 0;
+        ok = ok && std::fputc('\n', fp) != EOF;
+    }
+    ok = (std::fclose(fp) == 0) && ok;
+    return ok && std::rename(tmp.c_str(), file_name.c_str()) == 0;
+}
+
+static const int32_t COV_MAGIC = 0x56534B43;   // "VSKC"
+
+bool write_cov_records(const std::string& file_name, int first, int last, const std::vector<viso_motion_cov>& rec) {
+    const std::string tmp = file_name + ".tmp";
+    FILE* fp = std::fopen(tmp.c_str(), "wb");
+    if (!fp) return false;
+    const int32_t hdr[4] = {COV_MAGIC, first, last, (int32_t)rec.size()};
+    bool ok = std::fwrite(hdr, sizeof hdr, 1, fp) == 1;
+    if (ok && !rec.empty()) ok = std::fwrite(rec.data(), sizeof(viso_motion_cov), rec.size(), fp) == rec.size();
+    ok = (std::fclose(fp) == 0) && ok;
+    return ok && std::rename(tmp.c_str(), file_name.c_str()) == 0;
+}
+
+bool read_cov_records(const std::string& file_name, int& first, int& last, std::vector<viso_motion_cov>& rec) {
+    FILE* fp = std::fopen(file_name.c_str(), "rb");
+    if (!fp) return false;
+    int32_t hdr[4];
+    bool ok = std::fread(hdr, sizeof hdr, 1, fp) == 1 && hdr[0] == COV_MAGIC && hdr[3] >= 0 && hdr[2] >= hdr[1] &&
+              hdr[3] <= hdr[2] - hdr[1];
+    if (ok) {
+        first = hdr[1]; last = hdr[2];
+        rec.resize((size_t)hdr[3]);
+        if (hdr[3]) ok = std::fread(rec.data(), sizeof(viso_motion_cov), rec.size(), fp) == rec.size();
+    }
+    std::fclose(fp);
+    return ok;
+}
+
+std::vector<viso_motion_cov> stitch_cov_records(const std::vector<std::vector<viso_motion_cov>>& parts,
+                                                const std::vector<std::pair<int, int>>& ranges) {
+    std::vector<viso_motion_cov> all;   // the same cut as stitch_records
+    for (size_t r = 0; r < parts.size() && r < ranges.size(); ++r) {
+        all.insert(all.end(), parts[r].begin(), parts[r].end());
+        if ((int)parts[r].size() < ranges[r].second - ranges[r].first) break;
+    }
+    return all;
 }
 
 std::vector<Matd> chain_records(const FrameRecord* rec, int n, bool reference_pose_list) {
@@ -144,6 +202,10 @@ static thread_local int g_subpixel = 0;
 static thread_local bool g_rect_on = false;
 static thread_local viso::StereoRectification g_rect;
 static thread_local viso::Matd g_rect_P1, g_rect_P2;
+// viso_kitti_set_covariance, and the records of the last viso_kitti_run_range
+static thread_local int g_cov_mode = 0;
+static thread_local double g_cov_sigma = 0.0;
+static thread_local std::vector<viso_motion_cov> g_last_cov;
 
 extern "C" const char* viso_host_last_error(void) { return g_host_err.c_str(); }
 namespace viso { void set_host_error(const std::string& s) { g_host_err = s; } }   // for the other C entry points (drop_in.cpp)
@@ -169,9 +231,11 @@ extern "C" int viso_kitti_run_range(const char* seq_base, int begin, int first, 
             return VISO_ERR_ARG;
         }
         g_last_stats = viso::OdometryStats();
+        g_last_cov.clear();
         std::vector<viso::FrameRecord> rec = viso::kitti_run_range(seq_base, P1, P2, begin, first, last, device, chunk, ransac_seed,
                                                                    g_decode_threads, &g_last_stats, g_subpixel,
-                                                                   g_rect_on ? &g_rect : nullptr);
+                                                                   g_rect_on ? &g_rect : nullptr, g_cov_mode, g_cov_sigma,
+                                                                   g_cov_mode ? &g_last_cov : nullptr);
         for (size_t i = 0; i < rec.size(); ++i) {
             for (int j = 0; j < 6; ++j) rec8[i * 8 + (size_t)j] = rec[i].tr[j];
             rec8[i * 8 + 6] = rec[i].ok;
@@ -197,6 +261,33 @@ extern "C" void viso_kitti_set_decode_threads(int n) { g_decode_threads = n > 0 
 extern "C" int viso_kitti_set_subpixel(int mode) {
     if (mode < 0 || mode > 2) { g_host_err = "viso_kitti_set_subpixel: mode must be 0, 1 or 2"; return VISO_ERR_ARG; }
     g_subpixel = mode;
+    return VISO_OK;
+}
+
+extern "C" int viso_kitti_set_covariance(int mode, double sigma_px) {
+    if (mode != 0 && mode != 1 && !(mode == 2 && std::isfinite(sigma_px) && sigma_px > 0.0)) {
+        g_host_err = "viso_kitti_set_covariance: mode 0, 1, or 2 with a finite sigma_px > 0";
+        return VISO_ERR_ARG;
+    }
+    g_cov_mode = mode;
+    g_cov_sigma = mode == 2 ? sigma_px : 0.0;
+    return VISO_OK;
+}
+
+extern "C" int viso_kitti_last_covariances(viso_motion_cov* out, int cap, int* n) {
+    if (!n || cap < 0 || (cap > 0 && !out)) { g_host_err = "viso_kitti_last_covariances: bad argument"; return VISO_ERR_ARG; }
+    const size_t k = g_last_cov.size() < (size_t)cap ? g_last_cov.size() : (size_t)cap;
+    if (k) std::memcpy(out, g_last_cov.data(), sizeof(viso_motion_cov) * k);
+    *n = (int)g_last_cov.size();
+    return VISO_OK;
+}
+
+extern "C" int viso_kitti_write_covariances(const char* file_name, const viso_motion_cov* rec, int n) {
+    if (!file_name || n < 0 || (n > 0 && !rec)) { g_host_err = "viso_kitti_write_covariances: bad argument"; return VISO_ERR_ARG; }
+    const std::string f(file_name);
+    const size_t slash = f.rfind('/');
+    if (slash != std::string::npos && slash > 0) viso::mkdirs(f.substr(0, slash));
+    if (!viso::write_covariance_file(f, rec, (size_t)n)) { g_host_err = "cannot write " + f; return VISO_ERR_ARG; }
     return VISO_OK;
 }
 

@@ -49,7 +49,18 @@ int kitti_count_frames(const std::string& seq_base, int begin, int end);
 std::vector<FrameRecord> kitti_run_range(const std::string& seq_base, const Matd& P1, const Matd& P2, int begin,
                                          int first, int last, int device, int chunk = 64, uint64_t ransac_seed = 0,
                                          int decode_threads = 0, OdometryStats* stats = nullptr, int subpixel = 0,
-                                         const StereoRectification* rect = nullptr);
+                                         const StereoRectification* rect = nullptr, int cov_mode = 0, double cov_sigma = 0.0,
+                                         std::vector<viso_motion_cov>* cov = nullptr);
+// cov_mode / cov_sigma / cov: the opt-in motion covariance of sequence_odometry; *cov gets one record per FrameRecord.
+
+// The covariance file of the runners' --covariance option: one line per frame pair, "status n sigma2 gap" and the 21
+// upper-triangle entries of cov (row by row), every value %.17g.  Written under a temporary name and renamed.
+bool write_covariance_file(const std::string& file_name, const viso_motion_cov* rec, size_t n);
+// rank files of the covariance records (binary, next to the FrameRecord rank files), and the stitch of their parts
+bool write_cov_records(const std::string& file_name, int first, int last, const std::vector<viso_motion_cov>& rec);
+bool read_cov_records(const std::string& file_name, int& first, int& last, std::vector<viso_motion_cov>& rec);
+std::vector<viso_motion_cov> stitch_cov_records(const std::vector<std::vector<viso_motion_cov>>& parts,
+                                                const std::vector<std::pair<int, int>>& ranges);
 
 // poses[0] = I, then pose <- pose * inv(tr2mat(tr)) per solved record (src/viso.cpp:1189-1190, 1315-1321): the list
 // [I, P1, ..., Pn] the reference's code reads as.
@@ -93,6 +104,13 @@ int viso_kitti_load_cam_to_cam(const char* file_name, double K[18], double D[10]
 // this calib_cam_to_cam.txt, whose P_rect_00 / P_rect_01 replace the sequence's calib.txt; null or "" = off.  VISO_ERR_ARG
 // when the file cannot be read.
 int viso_kitti_set_rectify(const char* cam_to_cam_file);
+// the motion covariance (viso_batch_set_covariance) of the next viso_kitti_run_range calls of this thread: mode 0 (off), 1, or 2
+// with sigma_px; VISO_ERR_ARG for anything else
+int viso_kitti_set_covariance(int mode, double sigma_px);
+// the records of this thread's last viso_kitti_run_range (one per record it returned): *n = their number, copied up to cap
+int viso_kitti_last_covariances(viso_motion_cov* out, int cap, int* n);
+// the covariance file of --covariance (viso::write_covariance_file)
+int viso_kitti_write_covariances(const char* file_name, const viso_motion_cov* rec, int n);
 // chain n records and write the KITTI pose file (directories are created); *n_poses = lines written
 int viso_kitti_write_poses(const char* file_name, const double* rec8, int n, int* n_poses);
 // the same with the pose list the reference writes ([P1..Pn, Pn], see chain_records) when reference_pose_list != 0

@@ -146,6 +146,7 @@ struct OdometryResult {
     std::vector<int> frame_of_pose; // frame index of poses[i] (0 for the identity) — the reference drops failed frames silently (:1287,:1323)
     std::vector<int> ok, n_inliers; // per frame
     std::vector<std::array<double, 6>> tr;
+    std::vector<viso_motion_cov> cov; // per frame like ok (entry 0: status 0) when the image-driven run was asked for them (cov_mode)
     OdometryStats stats;
 };
 
@@ -274,9 +275,12 @@ struct StereoRectification {
 // rect (may be null): the images are RAW, rect->raw_rows x raw_cols, and each batch rectifies them on the device to
 // rect->out_rows x out_cols (viso_batch_set_rectify) before detection; P1 / P2 are the rectified projections (P_rect).  A chunk's
 // halo frame is rectified again like any other frame.
+// cov_mode (opt-in, viso_batch_set_covariance; NOT in the reference): 1 = sigma^2 estimated, 2 = sigma = cov_sigma pixels; fills
+// OdometryResult::cov with one viso_motion_cov per frame.  A chunk's halo frame is recomputed like any other frame, so every
+// chunking and partition gives byte-identical records.
 OdometryResult sequence_odometry(const Matd& P1, const Matd& P2, StereoImageGenerator& images,
                                  int chunk = 64, uint64_t ransac_seed = 0, uint64_t first_frame_index = 0,
                                  int device = 0, int decode_threads = 0, int subpixel = 0,
-                                 const StereoRectification* rect = nullptr);
+                                 const StereoRectification* rect = nullptr, int cov_mode = 0, double cov_sigma = 0.0);
 
 }  // namespace viso

@@ -320,6 +320,7 @@ struct ChunkPipeline {
     int next = 0;
     OdometryResult& out;
     double pose[16];
+    int cov_mode = 0;                       // the image-driven run's viso_batch_set_covariance mode: drain collects the records
     ChunkPipeline(OdometryResult& o, int device) : slot{Slot(device), Slot(device)}, out(o) {
         std::memcpy(pose, out.poses[0].ptr(), sizeof(pose));
     }
@@ -346,6 +347,8 @@ struct ChunkPipeline {
         std::vector<int32_t> ok((size_t)nf), ninl((size_t)nf);
         const auto t0 = std::chrono::steady_clock::now();
         hip_check(viso_batch_get_poses(s.b, tr.data(), ok.data(), ninl.data()), "sequence_odometry");
+        std::vector<viso_motion_cov> cov(cov_mode ? (size_t)nf : 0);
+        if (cov_mode) hip_check(viso_batch_get_covariances(s.b, cov.data()), "sequence_odometry (viso_batch_get_covariances)");
         out.stats.drain_wait_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         if (s.stamped) {
             double ms[2] = {0, 0};
@@ -358,6 +361,11 @@ struct ChunkPipeline {
         for (int t = (s.global0 == 0 ? 0 : 1); t < nf; ++t) {
             out.ok.push_back(t == 0 ? 0 : ok[(size_t)t]);
             out.n_inliers.push_back(t == 0 ? 0 : ninl[(size_t)t]);
+            if (cov_mode) {
+                viso_motion_cov c{};   // frame 0 of the sequence: no pose, status 0
+                if (t > 0) c = cov[(size_t)t];
+                out.cov.push_back(c);
+            }
             std::array<double, 6> a{};
             if (t > 0) for (int j = 0; j < 6; ++j) a[(size_t)j] = tr[(size_t)t * 6 + j];
             out.tr.push_back(a);
@@ -726,7 +734,7 @@ int cpu_budget() {
 // slot's pinned buffer.  The halo frame is copied from the previous slot's buffer, not decoded twice.
 OdometryResult sequence_odometry(const Matd& P1, const Matd& P2, StereoImageGenerator& images, int chunk,
                                  uint64_t ransac_seed, uint64_t first_frame_index, int device, int decode_threads, int subpixel,
-                                 const StereoRectification* rect) {
+                                 const StereoRectification* rect, int cov_mode, double cov_sigma) {
     using clock = std::chrono::steady_clock;
     auto since = [](clock::time_point t0) { return std::chrono::duration<double>(clock::now() - t0).count(); };
     const auto t_start = clock::now();
@@ -778,6 +786,7 @@ OdometryResult sequence_odometry(const Matd& P1, const Matd& P2, StereoImageGene
     DecodePool pool(decode_threads > 0 ? decode_threads : default_decode_threads());
     out.stats.decode_threads = pool.size();
     ChunkPipeline pipe(out, device);
+    pipe.cov_mode = cov_mode;
     int global0 = 0;                 // frame (relative to first_index) of the current chunk's halo
     int frames_read = 1;
     bool eos = false;
@@ -837,6 +846,7 @@ OdometryResult sequence_odometry(const Matd& P1, const Matd& P2, StereoImageGene
         if (r >= 0) r = viso_batch_upload_images(b, 0, 0, nullptr, rows, cols, nullptr, nullptr);   // device buffers for this geometry
         if (r >= 0) r = viso_batch_set_params(b, &st, &tm, &vp, ransac_seed, first_frame_index + (uint64_t)global0);
         if (r >= 0) r = viso_batch_set_subpixel(b, subpixel);
+        if (r >= 0 && cov_mode) r = viso_batch_set_covariance(b, cov_mode, cov_sigma);
         if (r >= 0) r = viso_batch_stamp(b, 0);
         if (r >= 0) r = viso_batch_upload_images_async(b, 0, nf, pin, rows, cols, nullptr, nullptr);
         if (r >= 0) r = viso_batch_stamp(b, 1);

@@ -22,10 +22,16 @@
 //   --rectify file      opt-in: the images are RAW (KITTI raw's unrectified drives, other rigs) and are undistorted and rectified
 //                       on the device (viso_batch_set_rectify) with KITTI raw's calib_cam_to_cam.txt `file`, which is used in
 //                       place of calib.txt (P_rect_00 / P_rect_01).  Not in the reference
+//   --covariance file   opt-in: also write the per-frame motion covariance (viso_batch_set_covariance, mode 1: sigma
+//                       estimated) to `file`, one line per frame pair: status n sigma2 gap and the 21 upper-triangle entries
+//                       (%.17g); byte-identical for every chunk size, W and partition.  Pose files are unchanged.  Not in the
+//                       reference
+//   --covariance-sigma s  with --covariance: mode 2, sigma = s pixels
 // Every rank reports where its wall time went: decode (PNG inflate on the worker threads; the calling thread's wait for
 // it is the runner's critical path), upload and GPU seconds from time stamps on the device.
 // libviso_amd/kitti_shard.py is the same runner with the gather as an RCCL all-gather (torch.distributed).
 #include <climits>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -50,6 +56,8 @@ struct Args {
     bool same_device = false, reference_pose_list = false;
     unsigned long long seed = 0;
     std::string rectify;   // calib_cam_to_cam.txt of --rectify ("" = off)
+    std::string covariance;   // --covariance file ("" = off)
+    double cov_sigma = 0.0;   // --covariance-sigma (0: mode 1)
 };
 
 bool parse(int argc, char** argv, Args& a) {
@@ -67,6 +75,13 @@ bool parse(int argc, char** argv, Args& a) {
         else if (s == "--subpixel") { if (!val(a.subpixel) || a.subpixel < 0 || a.subpixel > 2) return false; }
         else if (s == "--reference-pose-list") a.reference_pose_list = true;
         else if (s == "--rectify") { if (i + 1 >= argc || !*argv[i + 1]) return false; a.rectify = argv[++i]; }
+        else if (s == "--covariance") { if (i + 1 >= argc || !*argv[i + 1]) return false; a.covariance = argv[++i]; }
+        else if (s == "--covariance-sigma") {
+            if (i + 1 >= argc) return false;
+            char* e = nullptr;
+            a.cov_sigma = std::strtod(argv[++i], &e);
+            if (!e || *e || !std::isfinite(a.cov_sigma) || a.cov_sigma <= 0.0) return false;
+        }
         else if (s == "--seed") { if (i + 1 >= argc) return false; a.seed = std::strtoull(argv[++i], nullptr, 10); }
         else if (s == "--same-device") a.same_device = true;
         else if (s.rfind("--", 0) == 0) return false;
@@ -82,7 +97,18 @@ bool parse(int argc, char** argv, Args& a) {
     if (pos < 2) return false;
     if ((a.rank >= 0) != (a.world > 0)) return false;
     if (a.rank >= a.world && a.world > 0) return false;
+    if (a.cov_sigma > 0.0 && a.covariance.empty()) return false;   // --covariance-sigma belongs to --covariance
     return true;
+}
+
+int cov_mode(const Args& a) { return a.covariance.empty() ? 0 : a.cov_sigma > 0.0 ? 2 : 1; }
+
+bool write_covariances(const std::string& file, const std::vector<viso_motion_cov>& rec) {
+    const size_t slash = file.rfind('/');
+    if (slash != std::string::npos && slash > 0) viso::mkdirs(file.substr(0, slash));
+    if (viso::write_covariance_file(file, rec.data(), rec.size())) return true;
+    std::fprintf(stderr, "cannot write %s\n", file.c_str());
+    return false;
 }
 
 std::string rank_file(const std::string& result_dir, const std::string& seq, int r, int w) {
@@ -106,7 +132,8 @@ int main(int argc, char** argv) {
     Args a;
     if (!parse(argc, argv, a)) {
         std::printf("usage: demo result_sha seq_name begin end [--gpus W | --rank r --world W | --gather W] "
-                    "[--device d] [--same-device] [--chunk n] [--seed s] [--decode-threads n] [--reference-pose-list] [--subpixel 0|1|2] [--rectify calib_cam_to_cam.txt]\n");   // :81-85
+                    "[--device d] [--same-device] [--chunk n] [--seed s] [--decode-threads n] [--reference-pose-list] [--subpixel 0|1|2] [--rectify calib_cam_to_cam.txt] "
+                    "[--covariance file [--covariance-sigma s]]\n");   // :81-85
         return 1;
     }
     const char* home = std::getenv("KITTI_HOME");                                              // :96
@@ -175,6 +202,20 @@ int main(int argc, char** argv) {
                 }
             }
             const std::vector<viso::FrameRecord> all = viso::stitch_records(parts, ranges);
+            if (!a.covariance.empty()) {   // the ranks' covariance records, stitched the same way
+                std::vector<std::vector<viso_motion_cov>> cparts((size_t)a.gather);
+                for (int r = 0; r < a.gather; ++r) {
+                    int first = 0, last = 0;
+                    const std::string f = rank_file(result_dir, a.seq_name, r, a.gather) + ".cov";
+                    if (!viso::read_cov_records(f, first, last, cparts[(size_t)r]) || first != ranges[(size_t)r].first ||
+                        last != ranges[(size_t)r].second || cparts[(size_t)r].size() != parts[(size_t)r].size()) {
+                        std::fprintf(stderr, "cannot read %s (or it does not match the rank's records)\n", f.c_str());
+                        return 3;
+                    }
+                }
+                const std::vector<viso_motion_cov> call = viso::stitch_cov_records(cparts, ranges);
+                if (!write_covariances(a.covariance, call)) return 3;
+            }
             const std::vector<viso::Matd> poses = viso::chain_records(all.data(), (int)all.size(), a.reference_pose_list);
             viso::mkdirs(result_dir + "/data");
             if (!viso::savePoses(out, poses)) { std::fprintf(stderr, "cannot write %s\n", out.c_str()); return 3; }
@@ -190,10 +231,16 @@ int main(int argc, char** argv) {
             const auto range = viso::partition(n_frames, a.world)[(size_t)a.rank];
             const int device = a.device >= 0 ? a.device : a.rank;
             viso::OdometryStats stats;
+            std::vector<viso_motion_cov> cov;
             std::vector<viso::FrameRecord> rec = viso::kitti_run_range(seq_base, P1, P2, a.begin, range.first, range.second,
-                                                                       device, a.chunk, a.seed, a.decode_threads, &stats, a.subpixel, rectp);
+                                                                       device, a.chunk, a.seed, a.decode_threads, &stats, a.subpixel, rectp,
+                                                                       cov_mode(a), a.cov_sigma, a.covariance.empty() ? nullptr : &cov);
             viso::mkdirs(result_dir + "/shards");
             const std::string f = rank_file(result_dir, a.seq_name, a.rank, a.world);
+            if (!a.covariance.empty() && !viso::write_cov_records(f + ".cov", range.first, range.second, cov)) {
+                std::fprintf(stderr, "cannot write %s.cov\n", f.c_str());
+                return 3;
+            }
             if (!viso::write_records(f, range.first, range.second, rec)) { std::fprintf(stderr, "cannot write %s\n", f.c_str()); return 3; }
             std::printf("rank %d/%d device %d frames %d..%d pairs %zu -> %s\n", a.rank, a.world, device, a.begin + range.first,
                         a.begin + range.second, rec.size(), f.c_str());
@@ -204,7 +251,12 @@ int main(int argc, char** argv) {
         const std::string ext = viso::kitti_image_ext(seq_base, a.begin);
         viso::StereoImageGenerator images({seq_base + "/image_0/%06d" + ext, seq_base + "/image_1/%06d" + ext}, a.begin, a.end);
         viso::OdometryResult res = viso::sequence_odometry(P1, P2, images, a.chunk, a.seed, (uint64_t)a.begin,
-                                                           a.device >= 0 ? a.device : 0, a.decode_threads, a.subpixel, rectp);   // :111
+                                                           a.device >= 0 ? a.device : 0, a.decode_threads, a.subpixel, rectp,
+                                                           cov_mode(a), a.cov_sigma);   // :111
+        if (!a.covariance.empty()) {   // one line per frame pair: the records of frames 1 .. (entry 0 is the first frame)
+            const std::vector<viso_motion_cov> pairs(res.cov.size() > 1 ? res.cov.begin() + 1 : res.cov.end(), res.cov.end());
+            if (!write_covariances(a.covariance, pairs)) return 3;
+        }
         viso::mkdirs(result_dir + "/data");                                                    // :112-113
         if (a.reference_pose_list && res.poses.size() > 1) {                                   // [P1, ..., Pn, Pn], see kitti_shard.hpp
             res.poses.erase(res.poses.begin());

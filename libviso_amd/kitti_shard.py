@@ -36,9 +36,12 @@ import time
 
 import numpy as np
 
+from .abi import MOTION_COV_DTYPE
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 HOST_SO = os.path.join(_HERE, "libviso_host.so")
 REC = 8   # doubles per record: tr[6], ok, n_inl
+COV = 45  # doubles of a viso_motion_cov (360 bytes), appended to every record with --covariance (the wider rank record)
 
 
 def partition(n_frames, world):
@@ -67,6 +70,9 @@ def load_host():
     L.viso_kitti_set_decode_threads.restype = None
     L.viso_kitti_set_subpixel.argtypes = [C.c_int]
     L.viso_kitti_set_rectify.argtypes = [C.c_char_p]
+    L.viso_kitti_set_covariance.argtypes = [C.c_int, C.c_double]
+    L.viso_kitti_last_covariances.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    L.viso_kitti_write_covariances.argtypes = [C.c_char_p, C.c_void_p, C.c_int]
     L.viso_kitti_load_cam_to_cam.argtypes = [C.c_char_p] + [C.POINTER(C.c_double)] * 4 + [C.POINTER(C.c_int)]
     L.viso_host_last_error.restype = C.c_char_p
     return L
@@ -113,8 +119,9 @@ def last_stats(L):
     return dict(zip(STAT_NAMES, [float(x) for x in v]))
 
 
-def hip_engine(L, device, chunk=64, seed=0):
-    """engine(seq_base, begin, first, last) -> rec [(n_done), 8]: the range on the HIP pipeline."""
+def hip_engine(L, device, chunk=64, seed=0, covariance=False):
+    """engine(seq_base, begin, first, last) -> rec [(n_done), 8]: the range on the HIP pipeline.  covariance: each record is
+    followed by the frame's viso_motion_cov as COV doubles (viso_kitti_set_covariance must be on)."""
     def run(seq_base, begin, first, last):
         rec = np.zeros((max(last - first, 1), REC), np.float64)
         n_done = C.c_int(0)
@@ -122,7 +129,14 @@ def hip_engine(L, device, chunk=64, seed=0):
                                    rec.ctypes.data_as(C.POINTER(C.c_double)), C.byref(n_done))
         if r != 1:
             raise RuntimeError(f"viso_kitti_run_range failed with {r}: {L.viso_host_last_error().decode()}")
-        return rec[:n_done.value]
+        n = n_done.value
+        if not covariance:
+            return rec[:n]
+        cov = np.zeros(max(n, 1), MOTION_COV_DTYPE)
+        k = C.c_int(0)
+        if L.viso_kitti_last_covariances(cov.ctypes.data, len(cov), C.byref(k)) != 1 or k.value != n:
+            raise RuntimeError(f"viso_kitti_last_covariances: {k.value} records for {n} frame pairs")
+        return np.concatenate([rec[:n], cov[:n].view(np.float64).reshape(n, COV)], 1)
     return run
 
 
@@ -133,12 +147,12 @@ def count_frames(L, seq_base, begin, end):
     return n
 
 
-def gather_records(rec, n_pairs, first, rank, world, dist=None, device="cpu", failed=False):
+def gather_records(rec, n_pairs, first, rank, world, dist=None, device="cpu", failed=False, width=REC):
     """The one exchange step.  Every rank contributes a fixed-size block [n_pairs + 1, 8]: its records at the rows of
     its pairs, and in the last row how many it solved (a rank comes back short when an image of its range cannot be
     decoded) and a status word (1 = this rank's range failed: the block carries no records).  Returns the blocks of
     all ranks, rank order.  With dist=None and world == 1 nothing is exchanged."""
-    block = np.zeros((n_pairs + 1, REC), np.float64)
+    block = np.zeros((n_pairs + 1, width), np.float64)
     if not failed:
         block[first:first + len(rec)] = rec
         block[n_pairs, 0] = len(rec)
@@ -158,7 +172,7 @@ class RankFailed(RuntimeError):
     """Raised on EVERY rank, after the all-gather, when some rank's range failed."""
 
 
-def stitch(blocks, n_frames):
+def stitch(blocks, n_frames, width=REC):
     """Blocks of all ranks -> the records of the sequence in frame order, cut where a rank came back short
     (viso::stitch_records)."""
     world = len(blocks)
@@ -169,7 +183,7 @@ def stitch(blocks, n_frames):
         rows.append(blocks[r][a:a + done])
         if done < b - a:
             break
-    return np.concatenate(rows, 0) if rows else np.zeros((0, REC))
+    return np.concatenate(rows, 0) if rows else np.zeros((0, width))
 
 
 def write_poses(L, file_name, rec, reference_pose_list=False):
@@ -185,32 +199,38 @@ def write_poses(L, file_name, rec, reference_pose_list=False):
 
 
 def run_rank(home, result_sha, seq_name, begin, end, rank, world, L, engine, dist=None, coll_device="cpu",
-             reference_pose_list=False):
+             reference_pose_list=False, covariance=None):
     """One rank's whole job; returns (n_frames, records of the sequence, pose file or None).  `engine` is what
     turns a frame range into records (hip_engine here; the CPU tests inject the oracle).  An engine that raises does
     not keep this rank out of the collective: its block carries the failure, and every rank raises RankFailed behind
-    the all-gather."""
+    the all-gather.  covariance: the file of --covariance; the engine then returns records of REC + COV doubles (one
+    all-gather of the wider records), and rank 0 writes the file (viso_kitti_write_covariances)."""
     seq_base = os.path.join(home, "sequences", seq_name)
     n_frames = count_frames(L, seq_base, begin, end)      # may raise: BEFORE any collective, see main()
     n_pairs = max(0, n_frames - 1)
     first, last = partition(n_frames, world)[rank]
-    rec, err = np.zeros((0, REC)), None
+    width = REC + (COV if covariance else 0)
+    rec, err = np.zeros((0, width)), None
     try:
         if last > first:
             rec = engine(seq_base, begin, first, last)
     except Exception as e:                                # noqa: BLE001  reported through the collective
         err = e
         print(f"kitti_shard: rank {rank} failed on frames {begin + first}..{begin + last}: {e}", file=sys.stderr, flush=True)
-    blocks = gather_records(rec, n_pairs, first, rank, world, dist, coll_device, failed=err is not None)
+    blocks = gather_records(rec, n_pairs, first, rank, world, dist, coll_device, failed=err is not None, width=width)
     bad = [r for r, b in enumerate(blocks) if b[n_pairs, 1] != 0]
     if bad:
         raise RankFailed(f"rank(s) {bad} failed; no pose file written") from err
-    full = stitch(blocks, n_frames)
+    full = stitch(blocks, n_frames, width)
     out = None
     if rank == 0:
         out = os.path.join(home, "results", seq_name, result_sha, "data", seq_name + ".txt")   # src/kitti.cpp:100,112-114
-        write_poses(L, out, full, reference_pose_list)
-    return n_frames, full, out
+        write_poses(L, out, np.ascontiguousarray(full[:, :REC]), reference_pose_list)
+        if covariance:
+            cov = np.ascontiguousarray(full[:, REC:]).view(MOTION_COV_DTYPE).reshape(-1)
+            if L.viso_kitti_write_covariances(os.fsencode(covariance), cov.ctypes.data, len(cov)) != 1:
+                raise RuntimeError(L.viso_host_last_error().decode())
+    return n_frames, full[:, :REC], out
 
 
 def _free_port():
@@ -243,7 +263,14 @@ def main(argv=None):
     ap.add_argument("--rectify", default=None, metavar="CALIB_CAM_TO_CAM",
                     help="opt-in: the images are raw; undistort and rectify them on the device with this KITTI raw "
                          "calib_cam_to_cam.txt, used in place of calib.txt (not in the reference)")
+    ap.add_argument("--covariance", default=None, metavar="FILE",
+                    help="opt-in: also write the per-frame motion covariance (sigma estimated) to FILE, one line per frame pair "
+                         "(status n sigma2 gap + 21 upper-triangle entries); not in the reference")
+    ap.add_argument("--covariance-sigma", type=float, default=None, metavar="S",
+                    help="with --covariance: take sigma = S pixels instead of estimating it")
     args = ap.parse_args(argv)
+    if args.covariance_sigma is not None and args.covariance is None:
+        ap.error("--covariance-sigma needs --covariance")
     home = os.environ.get("KITTI_HOME")
     if not home:
         print("KITTI_HOME is not set", file=sys.stderr)
@@ -292,6 +319,12 @@ def main(argv=None):
         print(f"kitti_shard: {L.viso_host_last_error().decode()}", file=sys.stderr)
         return 2
 
+    if args.covariance is not None:
+        mode = 1 if args.covariance_sigma is None else 2
+        if L.viso_kitti_set_covariance(mode, float(args.covariance_sigma or 0.0)) != 1:
+            print(f"kitti_shard: {L.viso_host_last_error().decode()}", file=sys.stderr)
+            return 2
+
     def die(code, what):
         # a failure that the peers cannot learn about through the collective: leave WITHOUT joining one (no barrier,
         # no destroy_process_group: the peers may be inside the all-gather); torchrun sees the exit code and stops them
@@ -301,8 +334,9 @@ def main(argv=None):
 
     try:
         n_frames, full, out = run_rank(home, args.result_sha, args.seq_name, args.begin, args.end, rank, world, L,
-                                       hip_engine(L, device, args.chunk, args.seed), dist, coll_device,
-                                       args.reference_pose_list)
+                                       hip_engine(L, device, args.chunk, args.seed, args.covariance is not None), dist,
+                                       coll_device, args.reference_pose_list,
+                                       os.path.abspath(args.covariance) if args.covariance is not None else None)
     except RankFailed as e:                                # every rank is here, behind the same all-gather
         print(f"kitti_shard: rank {rank}: {e}", file=sys.stderr, flush=True)
         if dist is not None:

@@ -61,11 +61,14 @@ def _new_desc(rng, k):
 
 def make_sequence(seed, n_frames, n_kp=2000, width=1241, height=376, outlier_frac=0.2,
                   noise_sigma=6.0, dup_frac=0.0, cap=None, ragged=False,
-                  zmin=4.0, zmax=60.0, cluster_frac=0.0, n_blobs=14):
+                  zmin=4.0, zmax=60.0, cluster_frac=0.0, n_blobs=14, kp_sigma=None):
     """Returns dict(kp, desc, n, tr_gt, param, F, P1, P2, width, height).
 
     tr_gt[t] maps 3-D points of frame t-1 (left camera) into frame t, the
-    convention of compute_J (reference src/viso.cpp:1441-1443)."""
+    convention of compute_J (reference src/viso.cpp:1441-1443).
+    kp_sigma: None -> keypoints are the projections rounded to the pixel grid;
+    else the continuous projections plus N(0, kp_sigma^2) on every coordinate
+    (make_noisy_sequence)."""
     rng = np.random.default_rng(seed)
     cap = cap or n_kp
     f, cu, cv, base = KITTI_F, KITTI_CU, KITTI_CV, KITTI_BASE
@@ -95,24 +98,32 @@ def make_sequence(seed, n_frames, n_kp=2000, width=1241, height=376, outlier_fra
             if k_new > 0:
                 P = np.concatenate([P, _new_points(rng, k_new, width, height, zmin, zmax, f, cu, cv, blobs, cluster_frac)])
                 D = np.concatenate([D, _new_desc(rng, k_new)])
-        uL = np.rint(f * P[:, 0] / P[:, 2] + cu)
-        vL = np.rint(f * P[:, 1] / P[:, 2] + cv)
-        uR = np.rint(f * (P[:, 0] - base) / P[:, 2] + cu)
+        if kp_sigma is None:
+            uL = np.rint(f * P[:, 0] / P[:, 2] + cu)
+            vL = np.rint(f * P[:, 1] / P[:, 2] + cv)
+            uR = np.rint(f * (P[:, 0] - base) / P[:, 2] + cu)
+            vR = vL
+        else:
+            e = rng.normal(0.0, kp_sigma, (4, len(P)))
+            uL = f * P[:, 0] / P[:, 2] + cu + e[0]
+            vL = f * P[:, 1] / P[:, 2] + cv + e[1]
+            uR = f * (P[:, 0] - base) / P[:, 2] + cu + e[2]
+            vR = f * P[:, 1] / P[:, 2] + cv + e[3]
         for side in (0, 1):
             n_img = n_kp if not ragged else int(n_kp - rng.integers(0, max(1, n_kp // 5)))
             n_img = min(n_img, cap)
             if side == 0:
                 vis = np.ones(len(P), bool)
-                uu = uL
+                uu, vv = uL, vL
             else:
                 vis = (uR >= 0) & (uR <= width - 1)
-                uu = uR
+                uu, vv = uR, vR
             idx = np.nonzero(vis)[0][:n_img]
             k_real = len(idx)
             k_out = n_img - k_real
             xy = np.empty((n_img, 2), np.float32)
             xy[:k_real, 0] = uu[idx]
-            xy[:k_real, 1] = vL[idx]
+            xy[:k_real, 1] = vv[idx]
             xy[k_real:, 0] = rng.integers(0, width, k_out)
             xy[k_real:, 1] = rng.integers(0, height, k_out)
             dd = np.empty((n_img, DESC_LEN), np.int16)
@@ -135,6 +146,13 @@ def make_sequence(seed, n_frames, n_kp=2000, width=1241, height=376, outlier_fra
     param = Param.default(base=base, f=f, cu=cu, cv=cv)
     return dict(kp=kp, desc=desc, n=n, tr_gt=tr_gt, param=param, F=F, P1=KITTI_P1, P2=KITTI_P2,
                 width=width, height=height)
+
+
+def make_noisy_sequence(seed, n_frames, sigma, **kw):
+    """make_sequence with float keypoints: the continuous projections of the scene plus N(0, sigma^2) on every coordinate of both
+    images (uL, vL, uR, vR), descriptors planted as in make_sequence.  The observation model of the motion covariance
+    (include/viso_hip.h): iid pixel noise in both frames.  sigma <= 0.5 keeps the stereo Sampson gate (threshold 1.0) passing."""
+    return make_sequence(seed, n_frames, kp_sigma=float(sigma), **kw)
 
 
 def make_images(seed, rows=96, cols=128):
