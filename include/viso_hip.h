@@ -553,6 +553,62 @@ int viso_pose_covariance(const double* X, const double* obs, int m, const double
 int viso_chain_covariances(const double* tr, const int32_t* ok, const viso_motion_cov* cov, int n, double* pose_cov36,
                            int32_t* valid, int* n_out);
 
+/* ------------------------------------------------ motion refinement (opt-in; NOT in the reference)
+ *
+ * A two-frame stereo bundle adjustment: the maximum-likelihood motion and structure under iid pixel noise in both frames.  For one
+ * frame with a solved pose (ok = 1): L = the final inlier list, tr the final motion, (f, cu, cv, b) from viso_param.
+ *   L'  the entries k of L whose input X[:,k] is finite with Z > 0, in L's order; n = |L'| (fixed: no inlier is re-selected).
+ *   Unknowns tr (6, tr2mat's convention) and X_k (3) for k in L', starting at the frame's tr and the input X.
+ *   z0_k = (f X/Z + cu, f Y/Z + cv, f (X-b)/Z + cu) of the input X_k: the previous frame's observations, triangulate_rectified
+ *          inverted (sub-pixel disparities are honoured; vR of the previous frame is not used, as in the covariance);
+ *   r0_k = z0_k - pi0(X_k) (pi0 the same three expressions), r1_k = obs[:,k] - pred(tr, X_k) (4 rows, compute_J's prediction);
+ *   C = sum |r0|^2 + sum |r1|^2, unweighted (the reference's w_j and its Q6 column play no part).
+ *   J_k 4x6 compute_J without the weight; Jx_k = Pc R 4x3 (the covariance's); P0_k 3x3 rows (f/Z, 0, -fX/Z^2),
+ *   (0, f/Z, -fY/Z^2), (f/Z, 0, -f(X-b)/Z^2).
+ *   Hcc = sum J'J, Hcp_k = J_k'Jx_k, Hpp_k = Jx_k'Jx_k + P0_k'P0_k, gc = sum J'r1, gp_k = Jx_k'r1_k + P0_k'r0_k;
+ *   S = Hcc - sum Hcp_k Hpp_k^-1 Hcp_k', s = gc - sum Hcp_k Hpp_k^-1 gp_k; S dtr = s, dX_k = Hpp_k^-1 (gp_k - Hcp_k' dtr).
+ * Levenberg-Marquardt: the diagonals of Hcc and of every Hpp_k are multiplied by (1 + lambda), lambda_0 = 1e-4.  A candidate with a
+ * strictly lower C is accepted (lambda = max(lambda / 10, 1e-12)), otherwise lambda *= 10.  Stop after 8 consecutive rejections,
+ * after 20 accepted steps, after an accepted step with C_old - C_new <= 1e-12 C_old, or when C == 0.
+ * At the final state, undamped: cov = sigma^2 S^-1 (the motion's marginal covariance), gap = s'S^-1 s / sigma^2 (~ 0 at
+ * convergence; 0 when sigma^2 = 0).  sigma^2: mode 1 C / (4n - 6), mode 2 sigma_px^2 (finite and > 0, else VISO_ERR_ARG);
+ * mode 0 is off (the default: every run launches what it launched before).
+ * status 1 valid; 0 no pose (frame 0, or ok == 0); -1 n < 6; -2 a Cholesky pivot of S, of an Hpp_k (damped while iterating) or of
+ * a point's I - M M' (M = Jx~ l^-T; positive definite in exact arithmetic) is not > 1e-12 x its diagonal entry; -3 a non-finite value appeared (C at the start, the sums of S and s, the final record; a
+ * candidate whose C is not finite is rejected).  When status != 1, tr is the input tr, n is |L'| and every other field is zero:
+ * a consumer can always chain rec.tr where ok.  The batch's tr, ok, inliers and covariance records are never changed.
+ * One HIP kernel (motion_refine_kernel) serves every path; its summation order depends on n only (fixed DPP and LDS trees, no
+ * atomics), so the batch at any chunking and the direct call give byte-identical records for the same inputs. */
+typedef struct viso_motion_refine {
+    double tr[6];
+    double cov[36];     /* 6 x 6 row-major, symmetric */
+    double sigma2;
+    double cost0;       /* C at the start */
+    double cost;        /* C at the end */
+    double gap;
+    int32_t iters;      /* accepted steps */
+    int32_t status;
+    int32_t n;          /* |L'| */
+    int32_t _pad;
+} viso_motion_refine;
+
+/* mode 0 (off), 1 (estimated sigma) or 2 (sigma = sigma_px) for the batch's next runs: viso_batch_run and viso_batch_run_images
+ * (not matcher_only) then launch motion_refine_kernel on the RANSAC stream behind the refit (and behind the covariance when on).
+ * VISO_ERR_ARG: another mode, or mode 2 with a sigma_px that is not finite and > 0. */
+int viso_batch_set_refine(viso_batch* b, int mode, double sigma_px);
+/* The record of frame t / of all n_frames frames (frame 0: status 0) from the last run.  VISO_ERR_ARG when the last run computed
+ * none (mode 0, or matcher_only); the batch stays usable.  Synchronise like the other getters. */
+int viso_batch_get_refine(viso_batch* b, int t, viso_motion_refine* out);
+int viso_batch_get_refines(viso_batch* b, viso_motion_refine* out /* [n_frames] */);
+/* Frame t's refined points from the last run, in L' order: idx [cap] the point indices k, X3xcap [3][cap] rows of cap doubles, the
+ * first *n columns set (*n = 0 when the record's status != 1; either pointer may be NULL).  VISO_ERR_ARG as viso_batch_get_refine. */
+int viso_batch_get_refined_points(viso_batch* b, int t, int32_t* idx, double* X3xcap, int* n);
+/* Host pointers, default context, the batch's kernel: X 3 x m, obs 4 x m (row-major), tr 6, inl n_inl indices in [0, m) with
+ * n_inl <= m; mode 1 or 2.  The pose counts as solved (ok = 1).  Xout (may be NULL): 3 rows of n_inl doubles, the first out->n
+ * columns the refined points in L' order when status is 1. */
+int viso_pose_refine(const double* X, const double* obs, int m, const double tr[6], const int32_t* inl, int n_inl,
+                     const viso_param* param, int mode, double sigma_px, viso_motion_refine* out, double* Xout);
+
 #ifdef __cplusplus
 }
 #endif

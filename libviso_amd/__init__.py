@@ -16,8 +16,8 @@ import weakref
 
 import numpy as np
 
-from .abi import (DESC_LEN, MOTION_COV_DTYPE, MatchParams, Param, declare_common, declare_covariance, declare_rectify, declare_subpixel,
-                  f32p, f64p, i32p, i64p, intp, ptr)
+from .abi import (DESC_LEN, MOTION_COV_DTYPE, MOTION_REFINE_DTYPE, MatchParams, Param, declare_common, declare_covariance, declare_refine,
+                  declare_rectify, declare_subpixel, f32p, f64p, i32p, i64p, intp, ptr)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("VISO_HIP_SO") or os.path.join(_HERE, "libviso_hip.so")   # VISO_HIP_SO: another build of the library (A/B runs)
@@ -119,6 +119,8 @@ def load():
         declare_rectify(L)
     if hasattr(L, "viso_batch_set_covariance"):
         declare_covariance(L)
+    if hasattr(L, "viso_batch_set_refine"):
+        declare_refine(L)
     L.viso_harris_response.argtypes = [C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_double, f32p]
     L.viso_detect_harris_binned.argtypes = [C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                             C.c_double, f32p, f32p, intp]
@@ -464,6 +466,36 @@ def pose_covariance(X, obs, tr, inliers, param, mode=1, sigma=None):
     return out
 
 
+def pose_refine(X, obs, tr, inliers, param, mode=1, sigma=None):
+    """viso_pose_refine: the two-frame bundle adjustment of one frame's solve -- X 3 x m, obs 4 x m, tr 6, inliers the final inlier
+    list; mode 1 estimates sigma^2, mode 2 takes sigma (pixels).  Returns (record, points): a 0-d MOTION_REFINE_DTYPE array and
+    the refined points (3, n) in the order of the used inliers (empty unless status is 1)."""
+    L = load()
+    X, obs, tr, inl = _f64(X), _f64(obs), _f64(tr), _i32(inliers)
+    if X.ndim != 2 or X.shape[0] != 3 or obs.shape != (4, X.shape[1]) or tr.shape != (6,):
+        raise ValueError(f"pose_refine: X must be (3, m), obs (4, m) and tr (6,); got {X.shape}, {obs.shape}, {tr.shape}")
+    m = X.shape[1]
+    out = np.zeros((), MOTION_REFINE_DTYPE)
+    pts = np.zeros((3, max(len(inl), 1)))
+    r = L.viso_pose_refine(ptr(X, C.c_double), ptr(obs, C.c_double), m, ptr(tr, C.c_double), ptr(inl, C.c_int32), len(inl),
+                           C.byref(param), int(mode), float(sigma) if sigma is not None else 0.0, out.ctypes.data,
+                           ptr(pts, C.c_double))
+    if r != 1:
+        _err("viso_pose_refine", r)
+    k = int(out["n"]) if int(out["status"]) == 1 else 0
+    return out, pts[:, :k].copy()
+
+
+def refines_as_covariances(recs):
+    """Refine records packed as MOTION_COV_DTYPE (cov, sigma2, gap, status, n; delta zero), so that
+    chain_covariances(recs["tr"], ok, refines_as_covariances(recs)) propagates the refined trajectory's uncertainty."""
+    recs = np.asarray(recs, MOTION_REFINE_DTYPE)
+    out = np.zeros(recs.shape, MOTION_COV_DTYPE)
+    for k in ("cov", "sigma2", "gap", "status", "n"):
+        out[k] = recs[k]
+    return out
+
+
 def chain_covariances(tr, ok, covs):
     """viso_chain_covariances (host only): (pose_cov [k][6][6], valid [k]) along hostmath.chain_poses' list, k = 1 + sum(ok != 0)."""
     L = load()
@@ -681,6 +713,34 @@ class Batch:
         out = np.zeros(self.nf, MOTION_COV_DTYPE)
         self._chk("viso_batch_get_covariances", self.L.viso_batch_get_covariances(self.h, out.ctypes.data))
         return out
+
+    def set_refine(self, mode, sigma=None):
+        """viso_batch_set_refine: 0 = off (default), 1 = two-frame bundle adjustment of every solved frame with sigma^2 estimated,
+        2 = with the given sigma (pixels), for the next runs (run, and run_images unless matcher_only)."""
+        self._chk("viso_batch_set_refine",
+                  self.L.viso_batch_set_refine(self.h, int(mode), float(sigma) if sigma is not None else 0.0))
+
+    def refine(self, t):
+        """The refinement record of frame t from the last run (a 0-d MOTION_REFINE_DTYPE array)."""
+        out = np.zeros((), MOTION_REFINE_DTYPE)
+        self._chk("viso_batch_get_refine", self.L.viso_batch_get_refine(self.h, int(t), out.ctypes.data))
+        return out
+
+    def refines(self):
+        """The records of all frames from the last run: structured array [n_frames] of MOTION_REFINE_DTYPE (frame 0: status 0)."""
+        out = np.zeros(self.nf, MOTION_REFINE_DTYPE)
+        self._chk("viso_batch_get_refines", self.L.viso_batch_get_refines(self.h, out.ctypes.data))
+        return out
+
+    def refined_points(self, t):
+        """(idx [n] int32, X [3][n] float64): frame t's used inliers and their refined points from the last run (empty unless the
+        record's status is 1)."""
+        idx = np.zeros(self.cap, np.int32)
+        X = np.zeros((3, self.cap))
+        n = C.c_int(0)
+        self._chk("viso_batch_get_refined_points", self.L.viso_batch_get_refined_points(
+            self.h, int(t), ptr(idx, C.c_int32), ptr(X, C.c_double), C.byref(n)))
+        return idx[:n.value].copy(), X[:, :n.value].copy()
 
     def points(self, t):
         """(X [3][m], obs [4][m]) float64: frame t's solver inputs from the last run (previous-frame points, (uL, vL, uR, vR))."""

@@ -173,3 +173,20 @@ def declare_covariance(lib):
     lib.viso_batch_get_points.argtypes = [vp, C.c_int, f64p, f64p, intp]
     lib.viso_pose_covariance.argtypes = [f64p, f64p, C.c_int, f64p, i32p, C.c_int, C.POINTER(Param), C.c_int, C.c_double, vp]
     lib.viso_chain_covariances.argtypes = [f64p, i32p, vp, C.c_int, f64p, i32p, intp]
+
+
+# struct viso_motion_refine (include/viso_hip.h, "motion refinement") as a numpy structured dtype (Batch.refines, pose_refine)
+MOTION_REFINE_DTYPE = np.dtype([("tr", np.float64, 6), ("cov", np.float64, (6, 6)), ("sigma2", np.float64), ("cost0", np.float64),
+                                ("cost", np.float64), ("gap", np.float64), ("iters", np.int32), ("status", np.int32),
+                                ("n", np.int32), ("_pad", np.int32)])
+assert MOTION_REFINE_DTYPE.itemsize == 384
+
+
+def declare_refine(lib):
+    """Prototypes of the opt-in motion refinement (include/viso_hip.h; libviso_hip.so only)."""
+    vp = C.c_void_p
+    lib.viso_batch_set_refine.argtypes = [vp, C.c_int, C.c_double]
+    lib.viso_batch_get_refine.argtypes = [vp, C.c_int, vp]
+    lib.viso_batch_get_refines.argtypes = [vp, vp]
+    lib.viso_batch_get_refined_points.argtypes = [vp, C.c_int, i32p, f64p, intp]
+    lib.viso_pose_refine.argtypes = [f64p, f64p, C.c_int, f64p, i32p, C.c_int, C.POINTER(Param), C.c_int, C.c_double, vp, f64p]

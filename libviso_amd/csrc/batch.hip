@@ -45,6 +45,10 @@ struct viso_batch {
     // opt-in motion covariance (covariance.hip): the mode and sigma asked for, the records [nf] (allocated on the first request,
     // frame 0 stays zero: status 0), and the mode the last run computed them with (0: the last run computed none)
     int cov_mode = 0; double cov_sigma = 0.0; viso_motion_cov* cov = nullptr; int cov_last = 0;
+    // opt-in motion refinement (refine.hip): the mode and sigma asked for, the records [nf] and the working buffers (points
+    // [nf][2][3][cap], L' [nf][cap]; allocated on the first request, frame 0 stays zero), and the mode the last run computed them with
+    int ref_mode = 0; double ref_sigma = 0.0; viso_motion_refine* ref = nullptr; double* ref_pts = nullptr; int* ref_idx = nullptr;
+    int ref_last = 0;
     JoinItem* join; SolverItem* sitems;
     int *circ, *pcl, *mc;
     double* tr_h; int *ok_h, *cnt_h, *hq; char* rot;   // hq: list of undecided hypotheses (launch_ransac)
@@ -149,7 +153,7 @@ int viso_batch_free(viso_batch* b, bool keep_shell) {
     void* ptrs[] = {b->h_part, b->h_resp, b->h_tmp_kp, b->h_tmp_resp, b->h_cnt, b->images, b->skp, b->sidx, b->rank, b->bstart, b->xinfo, b->views,
                     b->kp, b->desc, b->n, b->packed, b->packed8, b->r8cnt, b->sums, b->zero, b->probs, b->res, b->sorted,
                     b->pos, b->m_cnt, b->scored, b->x_c, b->Xp_c, b->join,
-                    b->sitems, b->circ, b->pcl, b->mc, b->uv, b->cov, b->rmap, b->raw, b->tr /* + ok, n_inl */, b->inl, b->tr_h, b->ok_h, b->cnt_h, b->hq, b->samp_h, b->rot, b->tile_flag, b->qord, b->ovf_q};
+                    b->sitems, b->circ, b->pcl, b->mc, b->uv, b->cov, b->ref, b->ref_pts, b->ref_idx, b->rmap, b->raw, b->tr /* + ok, n_inl */, b->inl, b->tr_h, b->ok_h, b->cnt_h, b->hq, b->samp_h, b->rot, b->tile_flag, b->qord, b->ovf_q};
     for (void* p : ptrs) if (p) note(hipFree(p));
     if (keep_shell) { b->ctx = nullptr; b->events.clear(); b->desc_family.clear(); b->desc_family.shrink_to_fit(); }
     else delete b;
@@ -544,7 +548,7 @@ extern "C" int viso_batch_kernel_timing(viso_batch* b, int enable) {
 }
 
 static int run_matcher_impl(viso_batch* b, bool from_images) {
-    if (!dead(b)) b->cov_last = 0;   // the records of an earlier run are not this run's
+    if (!dead(b)) b->cov_last = b->ref_last = 0;   // the records of an earlier run are not this run's
     if (dead(b) || !b->params_set) { viso_set_error("viso_batch_run: parameters not set"); return VISO_ERR_ARG; }
     if (from_images && (!b->images || b->dlen != VISO_DESC_LEN)) {
         viso_set_error("viso_batch_run_images: no images uploaded (or descriptor length is not 121)");
@@ -853,6 +857,73 @@ extern "C" int viso_batch_get_points(viso_batch* b, int t, double* X3xcap, doubl
     return VISO_OK;
 }
 
+// Opt-in motion refinement (not in the reference; refine.hip).  The records and working buffers are allocated (zeroed) on the
+// first request.
+extern "C" int viso_batch_set_refine(viso_batch* b, int mode, double sigma_px) {
+    if (dead(b) || (mode != 0 && !motion_refine_args_ok(mode, sigma_px))) {
+        viso_set_error("viso_batch_set_refine: bad argument (mode 0, 1, or 2 with a finite sigma_px > 0)");
+        return VISO_ERR_ARG;
+    }
+    int r;
+    if ((r = enter(b)) < 0) return r;
+    if (mode && !b->ref) {
+        if ((r = batch_sync(b)) < 0) return r;
+        const size_t nf = (size_t)b->nf, c = (size_t)b->cap;
+        if ((r = dalloc(&b->ref, nf)) < 0 || (r = dalloc(&b->ref_pts, nf * 6 * c)) < 0 || (r = dalloc(&b->ref_idx, nf * c)) < 0) {
+            for (void* p : {(void*)b->ref, (void*)b->ref_pts, (void*)b->ref_idx}) if (p) (void)hipFree(p);
+            b->ref = nullptr; b->ref_pts = nullptr; b->ref_idx = nullptr;
+            return r;
+        }
+        HIP_TRY(hipMemset(b->ref, 0, sizeof(viso_motion_refine) * nf));
+        HIP_TRY(hipMemset(b->ref_pts, 0, sizeof(double) * nf * 6 * c));
+        HIP_TRY(hipMemset(b->ref_idx, 0, sizeof(int) * nf * c));
+    }
+    b->ref_mode = mode;
+    b->ref_sigma = mode == 2 ? sigma_px : 0.0;
+    return VISO_OK;
+}
+
+static int ref_ready(viso_batch* b, const char* where) {
+    const int rs_ = batch_sync(b);
+    if (rs_ < 0) return rs_;
+    if (!b->ref_last) { viso_set_error("%s: the last run computed no refinement (mode 0, or matcher_only)", where); return VISO_ERR_ARG; }
+    return VISO_OK;
+}
+
+extern "C" int viso_batch_get_refine(viso_batch* b, int t, viso_motion_refine* out) {
+    if (!slot_ok(b, 0, t) || !out) { viso_set_error("viso_batch_get_refine: bad argument"); return VISO_ERR_ARG; }
+    int r;
+    if ((r = ref_ready(b, "viso_batch_get_refine")) < 0) return r;
+    HIP_TRY(hipMemcpy(out, b->ref + t, sizeof(viso_motion_refine), hipMemcpyDeviceToHost));
+    return VISO_OK;
+}
+
+extern "C" int viso_batch_get_refines(viso_batch* b, viso_motion_refine* out) {
+    if (dead(b) || !out) { viso_set_error("viso_batch_get_refines: bad argument"); return VISO_ERR_ARG; }
+    int r;
+    if ((r = ref_ready(b, "viso_batch_get_refines")) < 0) return r;
+    HIP_TRY(hipMemcpy(out, b->ref, sizeof(viso_motion_refine) * (size_t)b->nf, hipMemcpyDeviceToHost));
+    return VISO_OK;
+}
+
+// Frame t's refined points (the kernel leaves the final state in half 0 of the frame's point buffer) and L'.
+extern "C" int viso_batch_get_refined_points(viso_batch* b, int t, int32_t* idx, double* X3xcap, int* n) {
+    if (!slot_ok(b, 0, t) || !n) { viso_set_error("viso_batch_get_refined_points: bad argument"); return VISO_ERR_ARG; }
+    int r;
+    if ((r = ref_ready(b, "viso_batch_get_refined_points")) < 0) return r;
+    viso_motion_refine rec;
+    HIP_TRY(hipMemcpy(&rec, b->ref + t, sizeof(rec), hipMemcpyDeviceToHost));
+    const int nn = rec.status == 1 ? (rec.n < 0 ? 0 : rec.n > b->cap ? b->cap : rec.n) : 0;
+    const size_t c = (size_t)b->cap;
+    if (idx && nn) HIP_TRY(hipMemcpy(idx, b->ref_idx + (size_t)t * c, sizeof(int) * (size_t)nn, hipMemcpyDeviceToHost));
+    if (X3xcap && nn)
+        for (int row = 0; row < 3; ++row)
+            HIP_TRY(hipMemcpy(X3xcap + (size_t)row * c, b->ref_pts + ((size_t)t * 6 + (size_t)row) * c, sizeof(double) * (size_t)nn,
+                              hipMemcpyDeviceToHost));
+    *n = nn;
+    return VISO_OK;
+}
+
 // Opt-in rectification of raw images (not in the reference; rectify.hip).  Synchronous like the other setters: the batch's work
 // in flight finishes first, then the maps are quantised on the host and the buffers (re)allocated.
 extern "C" int viso_batch_set_rectify(viso_batch* b, int raw_rows, int raw_cols, int out_rows, int out_cols, const float* mapxL,
@@ -937,8 +1008,13 @@ static int run_rest(viso_batch* b) {
         if ((r = plain_blit(ss, b->tr, b->pose_pin, b->pose_bytes / 4)) < 0) return r;
         // opt-in: the motion covariance from what the refit left (tr, ok, the final inlier list), frames 1 .. nf-1
         if (b->cov_mode && (r = launch_motion_cov(ss, b->sitems, b->nf - 1, b->sp, b->cov_mode, b->cov_sigma, b->cov + 1)) < 0) return r;
+        // opt-in: the two-frame bundle adjustment from the same inputs (it changes none of them)
+        const size_t c = (size_t)b->cap;
+        if (b->ref_mode && (r = launch_motion_refine(ss, b->sitems, b->nf - 1, b->sp, b->ref_mode, b->ref_sigma, b->ref_pts + 6 * c,
+                                                     b->ref_idx + c, c, b->ref + 1)) < 0) return r;
     }
     b->cov_last = b->cov_mode;
+    b->ref_last = b->ref_mode;
     if (ss != s) {
         HIP_TRY(hipEventRecord(b->ev_ransac, ss));
         b->ransac_pending = true;

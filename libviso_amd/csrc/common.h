@@ -453,6 +453,11 @@ int launch_rectify(hipStream_t s, const uint8_t* raw, size_t raw_fs, size_t raw_
 int launch_motion_cov(hipStream_t s, const SolverItem* items_dev, int n_items, const SolverParamsDev& sp, int mode, double sigma,
                       viso_motion_cov* out);
 bool motion_cov_args_ok(int mode, double sigma_px);   // mode 1, or mode 2 with a finite sigma_px > 0
+// refine.hip: the opt-in two-frame bundle adjustment (viso_batch_set_refine); one record per item, out[item], from the item's X,
+// obs, m_ptr, ld, tr, ok, n_inl, inl; pts [n_items][2][3][stride] and idx [n_items][stride] its working buffers (stride >= ld)
+int launch_motion_refine(hipStream_t s, const SolverItem* items_dev, int n_items, const SolverParamsDev& sp, int mode, double sigma,
+                         double* pts, int* idx, size_t stride, viso_motion_refine* out);
+bool motion_refine_args_ok(int mode, double sigma_px);   // mode 1, or mode 2 with a finite sigma_px > 0
 int launch_extract_pack(hipStream_t s, const ImageView* imgs_dev, int n_img, int cap, const uint8_t* images,
                         int rows, int cols, int extras, int r8s, int* r8cnt);
 int launch_harris_response(hipStream_t s, const uint8_t* images, int n_img, int rows, int cols, double k, float* resp);
