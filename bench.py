@@ -4,7 +4,9 @@
 A "step" is one pass of the hot path over one batch of synthetic frames that is
 already resident in HBM: by default BASELINE.json configs[1] (1241x376,
 ~2k features/frame, SAD matcher only = pack + 3 match_desc per frame incl. the
-final sort).  The same JSON line also carries
+final sort).  A plain run measures that headline and nothing else: it sets up,
+warms up, times the K steps, writes --dump-outputs and prints the JSON line.
+With --full the same line also carries (null in a plain run)
 
   resident_i16 the same matcher step with the descriptors resident as int16 rows
                (the step without the f32 -> u16 + u8 repack of the CV_32F boundary)
@@ -20,14 +22,17 @@ final sort).  The same JSON line also carries
                from a single-stream pass measured live with HIP events
   cpu_baseline the CPU oracle on the host cores: per stage, matcher-only and
                end to end on one thread, and frames-parallel on all cores
+  matcher_ab   with --ab: the other matcher variants, interleaved, one stream
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--frames B] [--kp N]
+The --no-* options leave single legs out of a --full run.
+
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--frames B] [--kp N] [--full]
 
 N > 1 is launched by the driver as
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 one rank per GPU; frames shard across ranks (each rank owns its own
 subsequence: weak scaling), no data-path collective; RCCL only gathers the
-final trajectory in the end-to-end leg.  `python bench.py --gpus N` on its own
+final trajectory in the end-to-end leg (--full).  `python bench.py --gpus N` on its own
 starts those N ranks itself (a child process tree, before this process touches
 the GPU); a world size that is not --gpus is an error, never an N = 1 line.
 
@@ -238,6 +243,133 @@ def cpu_baseline(seq, st, tm, budget_s):
                                     f"single threaded), {t_all:.1f} s", "nproc": len(os.sched_getaffinity(0))}}
 
 
+def roofline_figures(args, seq, batch, ctx, dt, n_streams, kern_ms, kern_n1, step_ms_single, kern_ms_region):
+    """The `roofline` object of a --full line: the dominant kernel's time from the single-stream pass before the
+    headline against the ceilings that can bound it (committed counter files), and what the step does to HBM."""
+    import libviso_amd
+    scored, m_out = batch.counters()
+    n_overflow = batch.overflow_count()
+    balg_stereo, balg_temporal = b_alg_bytes(seq["n"], scored, m_out)
+    bmin32_s, bmin32_t = b_min_bytes(seq["n"], m_out, elem=4)
+    bmin16_s, bmin16_t = b_min_bytes(seq["n"], m_out, elem=2)
+    kname = libviso_amd.matcher_kernel_name(ctx)
+    pairs = int(scored[1:].sum())              # the timed kernel takes the temporal problems (2 of 3 calls, ~97 % of the pairs)
+    t_k = kern_ms * 1e-3
+    default_workload = (args.frames, args.kp, args.width, args.height, args.clustered) == (512, 2000, 1241, 376, 0.0)
+    pmc = load_pmc(kname, default_workload)
+    ceilings = {}
+    # (iv) the arithmetic this path exists for.  u16 kernels: one v_sad_u16 wave-instruction (64 lanes x 2 elements) scores
+    # 128 elements = one (query, candidate) pair.  match_union8_kernel ranks every pair on the rows' 8-bit planes: one
+    # v_sad_u8 / v_sad_hi_u8 wave-instruction (64 lanes x 4 elements) scores TWO pairs, and only the two best candidates
+    # of a query are scored again on the u16 rows.  All of them are half-rate opcodes (one per 4 cycles per SIMD)
+    u8_kernel = kname == "match_union8_kernel"
+    bmin_k = b_min_bytes_union8(seq["n"], m_out) if u8_kernel else bmin16_t
+    sad_peak = N_SIMD * CLK_GHZ * 1e9 / VALU_CYCLES_SAD * (2 if u8_kernel else 1)
+    valu_peak = N_SIMD * CLK_GHZ * 1e9 / VALU_CYCLES_FULL
+    ceilings["sad_valu"] = {"achieved": pairs / t_k, "peak": sad_peak, "unit": "scored pairs/s",
+                            "frac": pairs / t_k / sad_peak,
+                            "what": ("useful v_sad_u8 issue: scored pairs (device counter) x HALF a wave-instruction each (a pair is 128 byte "
+                                     "elements, an instruction does 256); the two exact v_sad_u16 scorings per query are not counted as useful"
+                                     if u8_kernel else
+                                     "useful v_sad_u16 issue: scored pairs (device counter) x 1 wave-instruction each")
+                                    + "; a half-rate opcode: 4 cycles per wave-instruction per SIMD (tools/valu_rate.hip measures 4.56), 1024 SIMDs at 2.4 GHz"}
+    valu_busy = None
+    if pmc["hbm_bytes"] is not None:
+        a = pmc["hbm_bytes"] / t_k / 1e9
+        ceilings["hbm"] = {"achieved": a, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": a / HBM_PEAK_GBS,
+                           "what": "PMC bytes per launch (FETCH_SIZE x2 + WRITE_SIZE) / live single-stream kernel time"}
+    if pmc["sq"] is not None:
+        sq = pmc["sq"]
+        if "SQ_INSTS_VALU" in sq:
+            a = sq["SQ_INSTS_VALU"] / t_k
+            ceilings["valu_issue"] = {"achieved": a, "peak": valu_peak, "unit": "VALU wave-instructions/s", "frac": a / valu_peak,
+                                      "what": "SQ_INSTS_VALU / kernel time against the NOMINAL issue rate (every opcode at the full rate: "
+                                              "one wave64 instruction per 2 cycles per SIMD, 1024 SIMDs, 2.4 GHz). ~90 % of the kernel's "
+                                              "instructions are half-rate opcodes (v_sad_u8 / v_sad_u16, DPP adds, selects, v_med3/v_min): see valu_busy"}
+            if "SQ_ACTIVE_INST_VALU" in sq and "GRBM_GUI_ACTIVE" in sq:
+                cyc = sq["GRBM_GUI_ACTIVE"] / 8.0            # rocprofv3 sums the 8 XCDs: shader cycles of one launch
+                valu_busy = {"rocprof_VALUBusy": sq["SQ_ACTIVE_INST_VALU"] / 256.0 / cyc,
+                             "cycles_per_valu_instruction_per_simd": cyc * N_SIMD / sq["SQ_INSTS_VALU"],
+                             "note": "rocprofv3's VALUBusy formula (SQ_ACTIVE_INST_VALU / CU_NUM / GRBM_GUI_ACTIVE per XCD; the counter books "
+                                     "one quad-cycle per instruction): the share of the launch's cycles in which the vector ALUs execute. "
+                                     "cycles_per_valu_instruction_per_simd is the issue interval this launch sustained: 4 is what a loop of "
+                                     "half-rate opcodes can reach (tools/valu_rate.hip measures 4.2-4.7 for them, 2.4-2.7 for the full-rate "
+                                     "ones): what is left to gain is fewer or cheaper instructions, not a higher issue rate"}
+        if "TCP_TCC_READ_REQ_sum" in sq:
+            l2b = sq["TCP_TCC_READ_REQ_sum"] * L2_REQ_BYTES
+            peak = L2_GATHER_PEAK_GBS if kname in GATHER_KERNELS else L2_STREAM_PEAK_GBS
+            a = l2b / t_k / 1e9
+            ceilings["l2"] = {"achieved": a, "peak": peak, "unit": "GB/s", "frac": a / peak,
+                              "what": "TCP_TCC_READ_REQ_sum x 128 B (row gathers served by the XCD L2) against the guide's "
+                                      + ("indexed-row gather rate" if kname in GATHER_KERNELS else "aggregate L2 rate")}
+    # The unit that is FULL names the bound: rocprofv3's VALUBusy >= 0.90 means the vector ALUs hardly ever idle, whatever the
+    # nominal-peak fractions say (they differ by a few hundredths and flip with the choice of a peak: 18.8 TB/s is the
+    # guide's best case for another row shape, this kernel's own gather pattern measured 15-17 TB/s).  Otherwise the
+    # highest fraction.
+    if valu_busy is not None and valu_busy["rocprof_VALUBusy"] >= 0.90 and "valu_issue" in ceilings:
+        bound = "valu_issue"
+    else:
+        bound = max(ceilings, key=lambda k: ceilings[k]["frac"])
+    top = ceilings[bound]
+    if "l2" in ceilings and kname in GATHER_KERNELS:
+        a = ceilings["l2"]["achieved"]
+        ceilings["l2"]["peak_range_measured_for_this_block_shape"] = list(L2_GATHER_MEASURED_GBS)
+        ceilings["l2"]["frac_range_against_measured_peak"] = [a / L2_GATHER_MEASURED_GBS[1], a / L2_GATHER_MEASURED_GBS[0]]
+    # what the whole matcher STEP does to HBM: PMC bytes of every kernel of the step / ms_per_step / 8 TB/s, and the two
+    # kernels that are HBM kernels (pack: a format conversion stream; stereo: few pairs per row) on their own
+    step_hbm = None
+    if pmc["hbm_all"]:
+        tot = float(sum(pmc["hbm_all"].values()))
+        step_s = dt / args.steps
+        step_hbm = {"bytes_per_step": tot, "GB/s": tot / step_s / 1e9, "frac_of_8TBs": tot / step_s / 1e9 / HBM_PEAK_GBS,
+                    "ms_per_step": step_s * 1e3,
+                    "note": "sum over the step's kernels of PMC (FETCH_SIZE x2 + WRITE_SIZE) bytes per launch, one-stream counter passes, "
+                            "divided by the measured step time of this run (3 batches in flight)"}
+        kms = {}
+        p1 = os.path.join(ROOT, "profiles", f"{PROFILE_ROUND}_kernel_stats_1stream.csv")
+        if os.path.exists(p1):
+            import csv
+            for r in csv.DictReader(open(p1)):
+                kms[r["Name"]] = float(r["AverageNs"]) * 1e-6
+        per = {}
+        for kn, b in pmc["hbm_all"].items():
+            ms = next((v for k, v in kms.items() if k.split("(")[0] == kn.split("(")[0]), None)
+            if ms and b > 50e6:
+                per[kn.split("(")[0]] = {"ms_alone": ms, "hbm_bytes": b, "GB/s": b / ms / 1e6, "frac_of_8TBs": b / ms / 1e6 / HBM_PEAK_GBS}
+        step_hbm["kernels"] = per
+        step_hbm["kernels_note"] = f"ms_alone: profiles/{PROFILE_ROUND}_kernel_stats_1stream.csv (one batch in flight)"
+    roofline = {
+        "bound": bound, "achieved": top["achieved"], "peak": top["peak"], "unit": top["unit"], "frac": top["frac"],
+        "traffic": pmc["hbm_bytes"], "traffic_source": "; ".join(pmc["src"]) or None,
+        "pmc_dropped": pmc["dropped"] or None, "kernel_source_sha256": kernel_source_sha(),
+        "kernel": kname, "kernel_ms": kern_ms, "kernel_launches": kern_n1,
+        "kernel_ms_source": f"HIP events on the kernel's stream, {kern_n1} launches, ONE batch in flight (step alone: {step_ms_single:.3f} ms)",
+        "kernel_ms_in_timed_region_overlapped": kern_ms_region,
+        "kernel_ms_in_timed_region_note": f"{n_streams} batches in flight share the CUs: not a per-step cost, may exceed ms_per_step",
+        "ceilings": ceilings,
+        "valu_busy": valu_busy,
+        "bound_rule": "valu_issue when rocprofv3's VALUBusy >= 0.90 (the unit that is full), else the highest nominal-peak fraction",
+        "step_hbm": step_hbm,
+        "scored_pairs_per_launch": pairs,
+        "overflow_queries_per_step": n_overflow,
+        "overflow_note": "queries of one step (all three calls) handed to match_overflow_kernel: K cap, exact SAD tie, LDS list overflow",
+        "rows8_note": ("the pack kernels also write the rows' 8-bit planes (128 B per keypoint) for this kernel: inside the timed step" if u8_kernel else None),
+        "effective_bandwidth": {"algorithmic_bytes_per_launch": balg_temporal, "GB/s": balg_temporal / t_k / 1e9,
+                                "note": "SURVEY 8(d) B_alg (every scored pair counted as a fresh 484-B f32 row) / kernel time: an "
+                                        "effective figure served by L2/LDS, not comparable with the HBM peak"},
+        "compulsory_bytes": {"per_launch_f32_boundary": bmin32_t, "per_launch_u16_rows": bmin16_t,
+                             "per_launch_this_kernel": bmin_k,
+                             "per_launch_this_kernel_what": ("match_union8_kernel: planes + keypoints of both images, every query's u16 row, the u16 rows of the two "
+                                                             "exactly scored candidates per query (at most every target row once), result rows" if u8_kernel
+                                                             else "the u16 rows + keypoints of both images, result rows"),
+                             "traffic_over_compulsory": (pmc["hbm_bytes"] / bmin_k) if pmc["hbm_bytes"] else None,
+                             "per_step_all_calls_f32_boundary": bmin32_s + bmin32_t,
+                             "hbm_frac_if_only_compulsory": bmin_k / t_k / 1e9 / HBM_PEAK_GBS},
+        "algorithmic_bytes_per_step_all_calls": balg_stereo + balg_temporal,
+    }
+    return roofline
+
+
 DUMP_BYTES_MAX = 64 << 20
 MATCH_KINDS = ("stereo", "temporal_left", "temporal_right")   # viso_batch_get_matches `which` 0, 1, 2
 
@@ -270,6 +402,9 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=6)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline (roofline, resident_i16, end_to_end, drop_in_per_call, streaming, "
+                         "end_to_end_from_images, cpu_baseline; --ab); a plain run measures the headline alone")
     ap.add_argument("--frames", type=int, default=512, help="frame pairs per batch (per GPU)")
     ap.add_argument("--kp", type=int, default=2000, help="keypoints per image")
     ap.add_argument("--width", type=int, default=1241)
@@ -312,6 +447,8 @@ def main():
         raise SystemExit("bench.py: --gpus must be >= 1")
     if args.steps < 1:
         raise SystemExit("bench.py: --steps must be >= 1")
+    if args.ab and not args.full:
+        raise SystemExit("bench.py: --ab is a leg of the --full run")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` on its own: start the N ranks as a child process tree.  Nothing in this process
         # has touched the GPU (torch is not imported yet), and it is a child, not an exec.
@@ -452,6 +589,8 @@ def main():
     # committed `--streams 1` profile (profiles/*_kernel_stats_1stream.csv), behind a warm-up long enough for the clocks
     # to leave their idle state (the first ~30 launches of a fresh process read ~7 % longer); after the repeated
     # multi-stream regions below the card sits at its sustained clock and the same kernel reads 5-10 % longer again.
+    # A plain run makes this pass too (~0.1 s) without reporting it: it is the warm-up the headline has always been
+    # measured behind, and without it the first steps of a fresh process would run at idle clocks.
     n_single = max(8, min(40, args.steps))
     for _ in range(max(40, args.warmup)):       # ~50 ms of work first: a fresh process starts at idle clocks
         batch.run_matcher()
@@ -493,7 +632,7 @@ def main():
     # the f32 headline pays 0.3 ms of every 1.0 ms step for the f32 -> u16 + u8 repack of the reference's CV_32F rows: the
     # boundary's cost, not the matcher's; this is the matcher step without it
     res_i16 = None
-    if not args.no_i16:
+    if args.full and not args.no_i16:
         d16 = np.ascontiguousarray(seq["desc"].astype(np.int16))
         b16 = []
         for c, _ in lanes[:n_streams]:
@@ -512,126 +651,9 @@ def main():
             b.close()
         del d16
 
-    scored, m_out = batch.counters()
-    n_overflow = batch.overflow_count()
-    balg_stereo, balg_temporal = b_alg_bytes(seq["n"], scored, m_out)
-    bmin32_s, bmin32_t = b_min_bytes(seq["n"], m_out, elem=4)
-    bmin16_s, bmin16_t = b_min_bytes(seq["n"], m_out, elem=2)
-    kname = libviso_amd.matcher_kernel_name(ctx)
-    pairs = int(scored[1:].sum())              # the timed kernel takes the temporal problems (2 of 3 calls, ~97 % of the pairs)
-    t_k = kern_ms * 1e-3
-    default_workload = (args.frames, args.kp, args.width, args.height, args.clustered) == (512, 2000, 1241, 376, 0.0)
-    pmc = load_pmc(kname, default_workload)
-    ceilings = {}
-    # (iv) the arithmetic this path exists for.  u16 kernels: one v_sad_u16 wave-instruction (64 lanes x 2 elements) scores
-    # 128 elements = one (query, candidate) pair.  match_union8_kernel ranks every pair on the rows' 8-bit planes: one
-    # v_sad_u8 / v_sad_hi_u8 wave-instruction (64 lanes x 4 elements) scores TWO pairs, and only the two best candidates
-    # of a query are scored again on the u16 rows.  All of them are half-rate opcodes (one per 4 cycles per SIMD)
-    u8_kernel = kname == "match_union8_kernel"
-    bmin_k = b_min_bytes_union8(seq["n"], m_out) if u8_kernel else bmin16_t
-    sad_peak = N_SIMD * CLK_GHZ * 1e9 / VALU_CYCLES_SAD * (2 if u8_kernel else 1)
-    valu_peak = N_SIMD * CLK_GHZ * 1e9 / VALU_CYCLES_FULL
-    ceilings["sad_valu"] = {"achieved": pairs / t_k, "peak": sad_peak, "unit": "scored pairs/s",
-                            "frac": pairs / t_k / sad_peak,
-                            "what": ("useful v_sad_u8 issue: scored pairs (device counter) x HALF a wave-instruction each (a pair is 128 byte "
-                                     "elements, an instruction does 256); the two exact v_sad_u16 scorings per query are not counted as useful"
-                                     if u8_kernel else
-                                     "useful v_sad_u16 issue: scored pairs (device counter) x 1 wave-instruction each")
-                                    + "; a half-rate opcode: 4 cycles per wave-instruction per SIMD (tools/valu_rate.hip measures 4.56), 1024 SIMDs at 2.4 GHz"}
-    valu_busy = None
-    if pmc["hbm_bytes"] is not None:
-        a = pmc["hbm_bytes"] / t_k / 1e9
-        ceilings["hbm"] = {"achieved": a, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": a / HBM_PEAK_GBS,
-                           "what": "PMC bytes per launch (FETCH_SIZE x2 + WRITE_SIZE) / live single-stream kernel time"}
-    if pmc["sq"] is not None:
-        sq = pmc["sq"]
-        if "SQ_INSTS_VALU" in sq:
-            a = sq["SQ_INSTS_VALU"] / t_k
-            ceilings["valu_issue"] = {"achieved": a, "peak": valu_peak, "unit": "VALU wave-instructions/s", "frac": a / valu_peak,
-                                      "what": "SQ_INSTS_VALU / kernel time against the NOMINAL issue rate (every opcode at the full rate: "
-                                              "one wave64 instruction per 2 cycles per SIMD, 1024 SIMDs, 2.4 GHz). ~90 % of the kernel's "
-                                              "instructions are half-rate opcodes (v_sad_u8 / v_sad_u16, DPP adds, selects, v_med3/v_min): see valu_busy"}
-            if "SQ_ACTIVE_INST_VALU" in sq and "GRBM_GUI_ACTIVE" in sq:
-                cyc = sq["GRBM_GUI_ACTIVE"] / 8.0            # rocprofv3 sums the 8 XCDs: shader cycles of one launch
-                valu_busy = {"rocprof_VALUBusy": sq["SQ_ACTIVE_INST_VALU"] / 256.0 / cyc,
-                             "cycles_per_valu_instruction_per_simd": cyc * N_SIMD / sq["SQ_INSTS_VALU"],
-                             "note": "rocprofv3's VALUBusy formula (SQ_ACTIVE_INST_VALU / CU_NUM / GRBM_GUI_ACTIVE per XCD; the counter books "
-                                     "one quad-cycle per instruction): the share of the launch's cycles in which the vector ALUs execute. "
-                                     "cycles_per_valu_instruction_per_simd is the issue interval this launch sustained: 4 is what a loop of "
-                                     "half-rate opcodes can reach (tools/valu_rate.hip measures 4.2-4.7 for them, 2.4-2.7 for the full-rate "
-                                     "ones): what is left to gain is fewer or cheaper instructions, not a higher issue rate"}
-        if "TCP_TCC_READ_REQ_sum" in sq:
-            l2b = sq["TCP_TCC_READ_REQ_sum"] * L2_REQ_BYTES
-            peak = L2_GATHER_PEAK_GBS if kname in GATHER_KERNELS else L2_STREAM_PEAK_GBS
-            a = l2b / t_k / 1e9
-            ceilings["l2"] = {"achieved": a, "peak": peak, "unit": "GB/s", "frac": a / peak,
-                              "what": "TCP_TCC_READ_REQ_sum x 128 B (row gathers served by the XCD L2) against the guide's "
-                                      + ("indexed-row gather rate" if kname in GATHER_KERNELS else "aggregate L2 rate")}
-    # The unit that is FULL names the bound: rocprofv3's VALUBusy >= 0.90 means the vector ALUs hardly ever idle, whatever the
-    # nominal-peak fractions say (they differ by a few hundredths and flip with the choice of a peak: 18.8 TB/s is the
-    # guide's best case for another row shape, this kernel's own gather pattern measured 15-17 TB/s).  Otherwise the
-    # highest fraction.
-    if valu_busy is not None and valu_busy["rocprof_VALUBusy"] >= 0.90 and "valu_issue" in ceilings:
-        bound = "valu_issue"
-    else:
-        bound = max(ceilings, key=lambda k: ceilings[k]["frac"])
-    top = ceilings[bound]
-    if "l2" in ceilings and kname in GATHER_KERNELS:
-        a = ceilings["l2"]["achieved"]
-        ceilings["l2"]["peak_range_measured_for_this_block_shape"] = list(L2_GATHER_MEASURED_GBS)
-        ceilings["l2"]["frac_range_against_measured_peak"] = [a / L2_GATHER_MEASURED_GBS[1], a / L2_GATHER_MEASURED_GBS[0]]
-    # what the whole matcher STEP does to HBM: PMC bytes of every kernel of the step / ms_per_step / 8 TB/s, and the two
-    # kernels that are HBM kernels (pack: a format conversion stream; stereo: few pairs per row) on their own
-    step_hbm = None
-    if pmc["hbm_all"]:
-        tot = float(sum(pmc["hbm_all"].values()))
-        step_s = dt / args.steps
-        step_hbm = {"bytes_per_step": tot, "GB/s": tot / step_s / 1e9, "frac_of_8TBs": tot / step_s / 1e9 / HBM_PEAK_GBS,
-                    "ms_per_step": step_s * 1e3,
-                    "note": "sum over the step's kernels of PMC (FETCH_SIZE x2 + WRITE_SIZE) bytes per launch, one-stream counter passes, "
-                            "divided by the measured step time of this run (3 batches in flight)"}
-        kms = {}
-        p1 = os.path.join(ROOT, "profiles", f"{PROFILE_ROUND}_kernel_stats_1stream.csv")
-        if os.path.exists(p1):
-            import csv
-            for r in csv.DictReader(open(p1)):
-                kms[r["Name"]] = float(r["AverageNs"]) * 1e-6
-        per = {}
-        for kn, b in pmc["hbm_all"].items():
-            ms = next((v for k, v in kms.items() if k.split("(")[0] == kn.split("(")[0]), None)
-            if ms and b > 50e6:
-                per[kn.split("(")[0]] = {"ms_alone": ms, "hbm_bytes": b, "GB/s": b / ms / 1e6, "frac_of_8TBs": b / ms / 1e6 / HBM_PEAK_GBS}
-        step_hbm["kernels"] = per
-        step_hbm["kernels_note"] = f"ms_alone: profiles/{PROFILE_ROUND}_kernel_stats_1stream.csv (one batch in flight)"
-    roofline = {
-        "bound": bound, "achieved": top["achieved"], "peak": top["peak"], "unit": top["unit"], "frac": top["frac"],
-        "traffic": pmc["hbm_bytes"], "traffic_source": "; ".join(pmc["src"]) or None,
-        "pmc_dropped": pmc["dropped"] or None, "kernel_source_sha256": kernel_source_sha(),
-        "kernel": kname, "kernel_ms": kern_ms, "kernel_launches": kern_n1,
-        "kernel_ms_source": f"HIP events on the kernel's stream, {kern_n1} launches, ONE batch in flight (step alone: {step_ms_single:.3f} ms)",
-        "kernel_ms_in_timed_region_overlapped": kern_ms_region,
-        "kernel_ms_in_timed_region_note": f"{n_streams} batches in flight share the CUs: not a per-step cost, may exceed ms_per_step",
-        "ceilings": ceilings,
-        "valu_busy": valu_busy,
-        "bound_rule": "valu_issue when rocprofv3's VALUBusy >= 0.90 (the unit that is full), else the highest nominal-peak fraction",
-        "step_hbm": step_hbm,
-        "scored_pairs_per_launch": pairs,
-        "overflow_queries_per_step": n_overflow,
-        "overflow_note": "queries of one step (all three calls) handed to match_overflow_kernel: K cap, exact SAD tie, LDS list overflow",
-        "rows8_note": ("the pack kernels also write the rows' 8-bit planes (128 B per keypoint) for this kernel: inside the timed step" if u8_kernel else None),
-        "effective_bandwidth": {"algorithmic_bytes_per_launch": balg_temporal, "GB/s": balg_temporal / t_k / 1e9,
-                                "note": "SURVEY 8(d) B_alg (every scored pair counted as a fresh 484-B f32 row) / kernel time: an "
-                                        "effective figure served by L2/LDS, not comparable with the HBM peak"},
-        "compulsory_bytes": {"per_launch_f32_boundary": bmin32_t, "per_launch_u16_rows": bmin16_t,
-                             "per_launch_this_kernel": bmin_k,
-                             "per_launch_this_kernel_what": ("match_union8_kernel: planes + keypoints of both images, every query's u16 row, the u16 rows of the two "
-                                                             "exactly scored candidates per query (at most every target row once), result rows" if u8_kernel
-                                                             else "the u16 rows + keypoints of both images, result rows"),
-                             "traffic_over_compulsory": (pmc["hbm_bytes"] / bmin_k) if pmc["hbm_bytes"] else None,
-                             "per_step_all_calls_f32_boundary": bmin32_s + bmin32_t,
-                             "hbm_frac_if_only_compulsory": bmin_k / t_k / 1e9 / HBM_PEAK_GBS},
-        "algorithmic_bytes_per_step_all_calls": balg_stereo + balg_temporal,
-    }
+    roofline = None
+    if args.full:
+        roofline = roofline_figures(args, seq, batch, ctx, dt, n_streams, kern_ms, kern_n1, step_ms_single, kern_ms_region)
 
     ab = None
     if args.ab:   # interleaved rounds in ONE process (cdna guide rule 24)
@@ -661,7 +683,7 @@ def main():
     # ---- configs[2]: end to end (matcher + circle + RANSAC/GN) ---------------
     e2e = None
     collective = None
-    if not args.no_e2e:
+    if args.full and not args.no_e2e:
         # the end-to-end leg has its own number of batches in flight: every batch brings a RANSAC stream, and the chain of
         # latency-bound solver kernels of one step overlaps more of the other steps' matcher work with five than with three
         # (three is the matcher-only optimum); the extra batches exist for this leg only
@@ -709,7 +731,7 @@ def main():
     # copyTo carry-over of :1208-1222 -- what an unchanged kitti.cpp gets from adapters/libviso_hip.patch).  One frame at a
     # time, synchronous: a latency figure per GPU, not a throughput one.
     drop = None
-    if not args.no_e2e and not args.no_drop_in:
+    if args.full and not args.no_e2e and not args.no_drop_in:
         from libviso_amd import drop_in
         nd = min(nf, args.drop_in_frames + 1)
         dk, dd, dn = seq["kp"][:nd], seq["desc"][:nd], seq["n"][:nd]
@@ -775,7 +797,7 @@ def main():
     streaming = None
     iseq = None
     nfi = min(nf, max(2, args.image_frames + 1))
-    if not args.no_streaming:
+    if args.full and not args.no_streaming:
         hosts = []
         for rev in (False, True):
             pk = libviso_amd.PinnedArray(seq["kp"].shape, np.float32)
@@ -865,7 +887,7 @@ def main():
 
     # ---- resident image-in pipeline: uint8 images + keypoints already in HBM ---------
     e2e_img = None
-    if not args.no_images:
+    if args.full and not args.no_images:
         if iseq is None:
             t_syn = time.perf_counter()
             iseq = synth.make_image_sequence(2000 + rank, nfi, n_kp=args.kp, width=args.width, height=args.height)
@@ -913,7 +935,7 @@ def main():
 
     # ---- CPU baseline: the oracle on bounded samples of the same workload (rank 0, N = 1 only) ----
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         cpu = cpu_baseline(seq, st, tm, args.cpu_seconds)
 
     if rank == 0:
@@ -925,6 +947,7 @@ def main():
             "timing": f"one region of exactly {args.steps} steps after the warm-up (barrier + synchronize on both sides, "
                       "max over ranks); value / ms_per_step = that region",
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "full": bool(args.full),
             "dtype": "u16", "data": "synthetic",
             "config": {"workload": workload_name(args),
                        "frames_per_step_per_gpu": args.frames,

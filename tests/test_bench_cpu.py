@@ -58,3 +58,9 @@ def test_counters_of_other_sources_are_dropped(tmp_path, monkeypatch):
         else:
             assert out["hbm_bytes"] is None and out["sq"] is None and len(out["dropped"]) == 2
     assert bench.load_pmc("match_union_kernel", False)["hbm_bytes"] is None
+
+
+def test_ab_belongs_to_the_full_run():
+    """--ab is one of the legs beyond the headline: a plain run refuses it before it touches the GPU."""
+    r = _run(["--gpus", "1", "--steps", "1", "--warmup", "0", "--ab"], {})
+    assert r.returncode != 0 and "--full" in r.stderr and not _json_lines(r.stdout)

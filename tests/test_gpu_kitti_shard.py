@@ -177,7 +177,7 @@ def test_bench_gpus_2_starts_its_own_ranks_and_reports_them():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(VISO_BENCH_SAME_DEVICE="1", PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--frames", "24",
-                        "--kp", "600", "--steps", "3", "--warmup", "1", "--min-region-seconds", "0", "--no-cpu",
+                        "--kp", "600", "--steps", "3", "--warmup", "1", "--min-region-seconds", "0", "--full", "--no-cpu",
                         "--no-streaming", "--no-images"], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln]
@@ -196,9 +196,32 @@ def test_bench_force_collective_goes_through_rccl():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
     env.update(PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""), HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--force-collective", "--frames", "24", "--kp", "600", "--steps", "3",
-                        "--warmup", "1", "--min-region-seconds", "0", "--no-cpu", "--no-streaming", "--no-images"],
+                        "--warmup", "1", "--min-region-seconds", "0", "--full", "--no-cpu", "--no-streaming", "--no-images"],
                        capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln][0])
     assert d["n_gpus"] == 1 and d["collective"]["backend"] == "rccl" and d["collective"]["ranks"] == 1
     assert d["collective"]["gathered_records"] == 24 and d["end_to_end"]["poses_ok"] > 0
+
+
+def test_bench_plain_run_is_the_headline_alone(tmp_path):
+    """Without --full the bench measures its headline and nothing else: the line carries value / ms_per_step for exactly
+    --steps steps, every other leg is null, and --dump-outputs still writes the headline step's match lists."""
+    import json
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    env.update(PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
+    out = str(tmp_path / "dump")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--frames", "24", "--kp", "600",
+                        "--steps", "3", "--warmup", "1", "--dump-outputs", out],
+                       capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["full"] is False and d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0
+    assert d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"] == "u16"
+    for leg in ("roofline", "cpu_baseline", "resident_i16", "end_to_end", "drop_in_per_call", "collective", "streaming",
+                "end_to_end_from_images", "matcher_ab"):
+        assert d[leg] is None, leg
+    counts = np.load(os.path.join(out, "temporal_left_counts.npy"))
+    assert counts.shape == (25,) and counts[1:].min() > 0

@@ -1,5 +1,7 @@
 # kernel trace of the end-to-end leg (3 batches in flight) -> timeline summary of its second half
-cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-rocprofv3 --kernel-trace --stats -d gpurun_out/e2etrace -o s --output-format csv -- python3 bench.py --no-cpu --no-streaming --steps 40 > gpurun_out/e2etrace_bench.json 2>gpurun_out/e2etrace.err
-python3 tools/trace_overlap.py gpurun_out/e2etrace/s_kernel_trace.csv 0.75 0.98
-head -20 gpurun_out/e2etrace/s_kernel_stats.csv
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
+export OUT=$(realpath -m "${OUT:-$ROOT/out}") && mkdir -p $OUT   # results folder (default: out/ in the repository)
+cd /tmp && export TMPDIR=/tmp && cd $ROOT
+rocprofv3 --kernel-trace --stats -d $OUT/e2etrace -o s --output-format csv -- python3 bench.py --full --no-cpu --no-streaming --steps 40 > $OUT/e2etrace_bench.json 2>$OUT/e2etrace.err
+python3 tools/trace_overlap.py $OUT/e2etrace/s_kernel_trace.csv 0.75 0.98
+head -20 $OUT/e2etrace/s_kernel_stats.csv
