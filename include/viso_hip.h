@@ -609,6 +609,75 @@ int viso_batch_get_refined_points(viso_batch* b, int t, int32_t* idx, double* X3
 int viso_pose_refine(const double* X, const double* obs, int m, const double tr[6], const int32_t* inl, int n_inl,
                      const viso_param* param, int mode, double sigma_px, viso_motion_refine* out, double* Xout);
 
+/* ------------------------------------------------ window refinement (opt-in; NOT in the reference)
+ *
+ * A causal (fixed-lag) sliding-window stereo bundle adjustment over feature tracks.  Per frame j >= 1 of the batch:
+ * circ[j] rows (cur-left, cur-right, prev-left, prev-right), x_c[j] (4 x m) and Xp_c[j] (3 x m) (column i belongs to row i), ok_j,
+ * tr_j, the final inlier list L_j and L'_j (the motion refinement's set: the entries of L_j whose Xp_c column is finite with Z > 0,
+ * in L_j's order).
+ *   Window: K in 2..5.  A frame j >= 1 is a break when ok_j = 0 or |L'_j| < 6.  For frame t: status 0 when t = 0 or ok_t = 0, -1
+ *   when |L'_t| < 6 (in these cases the window is not formed); otherwise the anchor is a = max(t - K + 1, 0, the largest break
+ *   j < t), the window is frames a..t, len = t - a + 1 >= 2.  It never reaches before the batch's frame 0: a chunked sequence gives
+ *   the unchunked records when each chunk begins K - 1 frames early (the halo).
+ *   Links: a row r of L'_j, a + 1 < j <= t, with prev-left p links to the row r' of L'_{j-1} with cur-left p when r is the only row
+ *   of L'_j with prev-left p and r' the only row of L'_{j-1} with cur-left p (no forks).  Frame a's own rows are never used.
+ *   Tracks: the maximal chains r_{s+1} in L'_{s+1}, ..., r_e in L'_e of linked rows, a <= s < e <= t; every row of every L'_j,
+ *   a < j <= t, is in exactly one.  Order: s ascending, then L'_{s+1}'s order.  Observations: frame s gives z0 = pi0 of
+ *   Xp_c[s+1][:, r_{s+1}] (the motion refinement's three rows), every frame j in (s, e] gives x_c[j][:, r_j] (four rows).
+ *   Unknowns: tr_{a+1..t} (tr2mat's convention, starting at the batch's tr) and one point X per track in frame a's coordinates,
+ *   starting at Xp_c[s+1][:, r_{s+1}] mapped by the inverse of the starting T_s; T_j = M(tr_j) ... M(tr_{a+1}), T_a = I.
+ *   Predictions: pi0(T_s X) for frame s, compute_J's prediction of T_j X for j > s.  C = the sum of the squared unweighted residuals.
+ *   n_points = the number of tracks, n_rows = sum over the tracks of 3 + 4 (e - s).
+ * Levenberg-Marquardt as the motion refinement's (lambda_0 = 1e-4, x (1 + lambda) on the diagonals of the 6 (len - 1) square camera
+ * block and of every point's Hpp, the same accept, reject and stop rules); the camera block is solved through its Schur complement
+ * S, s.  Per-point guards (status -2 when a pivot is not > 1e-12 x its diagonal entry): the Cholesky factor l of the damped Hpp;
+ * for a track with s = a, I - M'M with M = Jx~ l^-T over its camera-dependent rows (the nonzero spectrum of the motion
+ * refinement's I - M M'; a track with s > a has no camera-free rows, its I - M M' is only semi-definite at lambda = 0 and is not
+ * tested).  At the final state, undamped: cov = sigma^2 x the tr_t block of S^-1, gap = s'S^-1 s / sigma^2 over the whole camera
+ * block.  sigma^2: mode 1 C / (n_rows - 3 n_points - 6 (len - 1)) (status -1 when that denominator is <= 0, in either mode), mode 2
+ * sigma_px^2.  status 1 valid, 0, -1, -2 (a pivot of S or of a point's block), -3 (non-finite: C at the start, the sums of S and s,
+ * the final record).  When status != 1: tr is tr_t, tr_win the input tr_{a+1..t}, len / n_points / n_rows are set (all three 0
+ * when the window is not formed), every other field is zero.
+ * Identity: at len = 2 the definition is the motion refinement's, so a K = 2 record's tr, cov, sigma2, cost0, cost, gap, iters and
+ * status agree with viso_motion_refine's to the bounds of two summation orders.  The batch's tr, ok, inliers, covariance and
+ * motion refinement records are never changed.  Two HIP kernels serve every path (window_links_kernel, window_refine_kernel); the
+ * summation order depends on the window's inputs only (fixed DPP and LDS trees, no float atomics), so the batch at any chunking
+ * with a K - 1 halo and the direct call give byte-identical records. */
+typedef struct viso_window_record {
+    double tr[6];        /* the refined tr_t */
+    double cov[36];      /* 6 x 6 row-major, symmetric */
+    double tr_win[4][6]; /* the refined tr_{a+1..t}, oldest first, zeros beyond len - 1 */
+    double sigma2;
+    double cost0;
+    double cost;
+    double gap;
+    int32_t iters;       /* accepted steps */
+    int32_t status;
+    int32_t len;
+    int32_t n_points;
+    int32_t n_rows;
+    int32_t _pad;
+} viso_window_record;
+
+/* K = 0 (off, the default: every run launches what it launched before) or K in 2..5 with mode 1 (estimated sigma) or 2 (sigma =
+ * sigma_px, finite and > 0) for the batch's next runs (viso_batch_run, viso_batch_run_images unless matcher_only): they launch the
+ * window kernels on the RANSAC stream behind the refit (and the covariance and motion refinement when on).  The working buffers
+ * are allocated (zeroed) on the first request with K > 0, and again when a larger K is asked for.  VISO_ERR_ARG: another K, a bad
+ * mode or sigma_px, a dead handle; the batch stays usable. */
+int viso_batch_set_window_refine(viso_batch* b, int K, int mode, double sigma_px);
+/* The record of frame t / of all n_frames frames from the last run (frame 0: status 0).  VISO_ERR_ARG when the last run computed
+ * none (K = 0, or matcher_only); the batch stays usable.  Synchronise like the other getters. */
+int viso_batch_get_window_refine(viso_batch* b, int t, viso_window_record* out);
+int viso_batch_get_window_refines(viso_batch* b, viso_window_record* out /* [n_frames] */);
+/* The direct call (host pointers, default context, the batch's kernels): the record of the last frame of a window of len frames
+ * (2..5) with K = len.  Frame 0's rows are never used, so only frames 1..len-1 are passed, concatenated: m[len-1] rows each; X the
+ * 3 x m_j blocks (row-major, block after block), obs the 4 x m_j blocks, left (cur-left, prev-left) per row (keypoint indices in
+ * [0, 2^20)), tr [len-1][6], inl the lists (n_inl[len-1] indices in [0, m_j) each).  Every frame counts as ok = 1; the break rule
+ * still applies.  mode 1 or 2 as viso_batch_set_window_refine. */
+int viso_window_refine(int len, const int* m, const double* X, const double* obs, const int32_t* left, const double* tr,
+                       const int32_t* inl, const int* n_inl, const viso_param* param, int mode, double sigma_px,
+                       viso_window_record* out);
+
 #ifdef __cplusplus
 }
 #endif

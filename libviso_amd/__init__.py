@@ -16,8 +16,9 @@ import weakref
 
 import numpy as np
 
-from .abi import (DESC_LEN, MOTION_COV_DTYPE, MOTION_REFINE_DTYPE, MatchParams, Param, declare_common, declare_covariance, declare_refine,
-                  declare_rectify, declare_subpixel, f32p, f64p, i32p, i64p, intp, ptr)
+from .abi import (DESC_LEN, MOTION_COV_DTYPE, MOTION_REFINE_DTYPE, WINDOW_RECORD_DTYPE, MatchParams, Param, declare_common,
+                  declare_covariance, declare_refine, declare_rectify, declare_subpixel, declare_window, f32p, f64p, i32p, i64p, intp,
+                  ptr)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("VISO_HIP_SO") or os.path.join(_HERE, "libviso_hip.so")   # VISO_HIP_SO: another build of the library (A/B runs)
@@ -121,6 +122,8 @@ def load():
         declare_covariance(L)
     if hasattr(L, "viso_batch_set_refine"):
         declare_refine(L)
+    if hasattr(L, "viso_batch_set_window_refine"):
+        declare_window(L)
     L.viso_harris_response.argtypes = [C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_double, f32p]
     L.viso_detect_harris_binned.argtypes = [C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                             C.c_double, f32p, f32p, intp]
@@ -496,6 +499,45 @@ def refines_as_covariances(recs):
     return out
 
 
+def window_refine(frames, param, mode=1, sigma=None):
+    """viso_window_refine: the sliding-window bundle adjustment's record of the last frame of a window of len = len(frames) + 1
+    frames (2..5), K = len.  frames: the window's frames 1..len-1, oldest first, each a tuple (X 3 x m, obs 4 x m, left m x 2 of
+    (cur-left, prev-left) keypoint indices, tr 6, inliers); frame 0's rows are never used.  mode 1 estimates sigma^2, mode 2 takes
+    sigma (pixels).  Returns a 0-d WINDOW_RECORD_DTYPE array."""
+    L = load()
+    Xs, Os, Ls, Ts, Is, ms, ns = [], [], [], [], [], [], []
+    for X, obs, left, tr, inl in frames:
+        X, obs, tr, inl = _f64(X), _f64(obs), _f64(tr), _i32(inl)
+        left = np.ascontiguousarray(np.asarray(left, np.int32).reshape(-1, 2))
+        if X.ndim != 2 or X.shape[0] != 3 or obs.shape != (4, X.shape[1]) or tr.shape != (6,) or left.shape[0] != X.shape[1]:
+            raise ValueError(f"window_refine: X must be (3, m), obs (4, m), left (m, 2) and tr (6,); got {X.shape}, {obs.shape}, "
+                             f"{left.shape}, {tr.shape}")
+        Xs.append(X.ravel()); Os.append(obs.ravel()); Ls.append(left.ravel()); Ts.append(tr); Is.append(inl)
+        ms.append(X.shape[1]); ns.append(len(inl))
+    cat = lambda a, dt: np.ascontiguousarray(np.concatenate(a) if a else np.zeros(0), dt)   # noqa: E731
+    X, obs, left, inl = cat(Xs, np.float64), cat(Os, np.float64), cat(Ls, np.int32), cat(Is, np.int32)
+    tr = np.ascontiguousarray(np.array(Ts, np.float64).reshape(-1, 6))
+    m, n = np.ascontiguousarray(ms, np.intc), np.ascontiguousarray(ns, np.intc)
+    out = np.zeros((), WINDOW_RECORD_DTYPE)
+    r = L.viso_window_refine(len(frames) + 1, ptr(m, C.c_int), ptr(X, C.c_double), ptr(obs, C.c_double), ptr(left, C.c_int32),
+                             ptr(tr, C.c_double), ptr(inl, C.c_int32), ptr(n, C.c_int), C.byref(param), int(mode),
+                             float(sigma) if sigma is not None else 0.0, out.ctypes.data)
+    if r != 1:
+        _err("viso_window_refine", r)
+    return out
+
+
+def window_refines_as_covariances(recs):
+    """Window records packed as MOTION_COV_DTYPE (cov, sigma2, gap, status; n = n_points; delta zero), so that
+    chain_covariances(recs["tr"], ok, window_refines_as_covariances(recs)) propagates the refined trajectory's uncertainty."""
+    recs = np.asarray(recs, WINDOW_RECORD_DTYPE)
+    out = np.zeros(recs.shape, MOTION_COV_DTYPE)
+    for k in ("cov", "sigma2", "gap", "status"):
+        out[k] = recs[k]
+    out["n"] = recs["n_points"]
+    return out
+
+
 def chain_covariances(tr, ok, covs):
     """viso_chain_covariances (host only): (pose_cov [k][6][6], valid [k]) along hostmath.chain_poses' list, k = 1 + sum(ok != 0)."""
     L = load()
@@ -741,6 +783,25 @@ class Batch:
         self._chk("viso_batch_get_refined_points", self.L.viso_batch_get_refined_points(
             self.h, int(t), ptr(idx, C.c_int32), ptr(X, C.c_double), C.byref(n)))
         return idx[:n.value].copy(), X[:, :n.value].copy()
+
+    def set_window_refine(self, K, mode=1, sigma=None):
+        """viso_batch_set_window_refine: K = 0 off (default), K in 2..5 the sliding-window bundle adjustment of every solved frame
+        over the window of frames t-K+1..t (mode 1: sigma^2 estimated, mode 2: the given sigma in pixels), for the next runs (run,
+        and run_images unless matcher_only)."""
+        self._chk("viso_batch_set_window_refine", self.L.viso_batch_set_window_refine(
+            self.h, int(K), int(mode), float(sigma) if sigma is not None else 0.0))
+
+    def window_refine(self, t):
+        """The window record of frame t from the last run (a 0-d WINDOW_RECORD_DTYPE array)."""
+        out = np.zeros((), WINDOW_RECORD_DTYPE)
+        self._chk("viso_batch_get_window_refine", self.L.viso_batch_get_window_refine(self.h, int(t), out.ctypes.data))
+        return out
+
+    def window_refines(self):
+        """The window records of all frames from the last run: structured array [n_frames] of WINDOW_RECORD_DTYPE (frame 0: status 0)."""
+        out = np.zeros(self.nf, WINDOW_RECORD_DTYPE)
+        self._chk("viso_batch_get_window_refines", self.L.viso_batch_get_window_refines(self.h, out.ctypes.data))
+        return out
 
     def points(self, t):
         """(X [3][m], obs [4][m]) float64: frame t's solver inputs from the last run (previous-frame points, (uL, vL, uR, vR))."""

@@ -190,3 +190,20 @@ def declare_refine(lib):
     lib.viso_batch_get_refines.argtypes = [vp, vp]
     lib.viso_batch_get_refined_points.argtypes = [vp, C.c_int, i32p, f64p, intp]
     lib.viso_pose_refine.argtypes = [f64p, f64p, C.c_int, f64p, i32p, C.c_int, C.POINTER(Param), C.c_int, C.c_double, vp, f64p]
+
+
+# struct viso_window_record (include/viso_hip.h, "window refinement") as a numpy structured dtype (Batch.window_refines, window_refine)
+WINDOW_RECORD_DTYPE = np.dtype([("tr", np.float64, 6), ("cov", np.float64, (6, 6)), ("tr_win", np.float64, (4, 6)),
+                                ("sigma2", np.float64), ("cost0", np.float64), ("cost", np.float64), ("gap", np.float64),
+                                ("iters", np.int32), ("status", np.int32), ("len", np.int32), ("n_points", np.int32),
+                                ("n_rows", np.int32), ("_pad", np.int32)])
+assert WINDOW_RECORD_DTYPE.itemsize == 584
+
+
+def declare_window(lib):
+    """Prototypes of the opt-in window refinement (include/viso_hip.h; libviso_hip.so only)."""
+    vp = C.c_void_p
+    lib.viso_batch_set_window_refine.argtypes = [vp, C.c_int, C.c_int, C.c_double]
+    lib.viso_batch_get_window_refine.argtypes = [vp, C.c_int, vp]
+    lib.viso_batch_get_window_refines.argtypes = [vp, vp]
+    lib.viso_window_refine.argtypes = [C.c_int, intp, f64p, f64p, i32p, f64p, i32p, intp, C.POINTER(Param), C.c_int, C.c_double, vp]

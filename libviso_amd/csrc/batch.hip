@@ -49,6 +49,11 @@ struct viso_batch {
     // [nf][2][3][cap], L' [nf][cap]; allocated on the first request, frame 0 stays zero), and the mode the last run computed them with
     int ref_mode = 0; double ref_sigma = 0.0; viso_motion_refine* ref = nullptr; double* ref_pts = nullptr; int* ref_idx = nullptr;
     int ref_last = 0;
+    // opt-in window refinement (window.hip): K (0 off), mode and sigma asked for, the records [nf] and the working buffers (L' [nf][cap],
+    // |L'| [nf], tables [nf][2][cap], tracks [nf][5][(K-1) cap], points [nf][2][3][(K-1) cap]; allocated on the first request with
+    // K > 0, for the largest K asked for so far: win_kalloc), and the K the last run computed them with (0: none)
+    int win_K = 0, win_mode = 0, win_kalloc = 0, win_last = 0; double win_sigma = 0.0; viso_window_record* win = nullptr;
+    int *win_lp = nullptr, *win_nlp = nullptr, *win_tab = nullptr, *win_trk = nullptr; double* win_pts = nullptr;
     JoinItem* join; SolverItem* sitems;
     int *circ, *pcl, *mc;
     double* tr_h; int *ok_h, *cnt_h, *hq; char* rot;   // hq: list of undecided hypotheses (launch_ransac)
@@ -153,7 +158,7 @@ int viso_batch_free(viso_batch* b, bool keep_shell) {
     void* ptrs[] = {b->h_part, b->h_resp, b->h_tmp_kp, b->h_tmp_resp, b->h_cnt, b->images, b->skp, b->sidx, b->rank, b->bstart, b->xinfo, b->views,
                     b->kp, b->desc, b->n, b->packed, b->packed8, b->r8cnt, b->sums, b->zero, b->probs, b->res, b->sorted,
                     b->pos, b->m_cnt, b->scored, b->x_c, b->Xp_c, b->join,
-                    b->sitems, b->circ, b->pcl, b->mc, b->uv, b->cov, b->ref, b->ref_pts, b->ref_idx, b->rmap, b->raw, b->tr /* + ok, n_inl */, b->inl, b->tr_h, b->ok_h, b->cnt_h, b->hq, b->samp_h, b->rot, b->tile_flag, b->qord, b->ovf_q};
+                    b->sitems, b->circ, b->pcl, b->mc, b->uv, b->cov, b->ref, b->ref_pts, b->ref_idx, b->win, b->win_lp, b->win_nlp, b->win_tab, b->win_trk, b->win_pts, b->rmap, b->raw, b->tr /* + ok, n_inl */, b->inl, b->tr_h, b->ok_h, b->cnt_h, b->hq, b->samp_h, b->rot, b->tile_flag, b->qord, b->ovf_q};
     for (void* p : ptrs) if (p) note(hipFree(p));
     if (keep_shell) { b->ctx = nullptr; b->events.clear(); b->desc_family.clear(); b->desc_family.shrink_to_fit(); }
     else delete b;
@@ -548,7 +553,7 @@ extern "C" int viso_batch_kernel_timing(viso_batch* b, int enable) {
 }
 
 static int run_matcher_impl(viso_batch* b, bool from_images) {
-    if (!dead(b)) b->cov_last = b->ref_last = 0;   // the records of an earlier run are not this run's
+    if (!dead(b)) b->cov_last = b->ref_last = b->win_last = 0;   // the records of an earlier run are not this run's
     if (dead(b) || !b->params_set) { viso_set_error("viso_batch_run: parameters not set"); return VISO_ERR_ARG; }
     if (from_images && (!b->images || b->dlen != VISO_DESC_LEN)) {
         viso_set_error("viso_batch_run_images: no images uploaded (or descriptor length is not 121)");
@@ -924,6 +929,66 @@ extern "C" int viso_batch_get_refined_points(viso_batch* b, int t, int32_t* idx,
     return VISO_OK;
 }
 
+// Opt-in window refinement (not in the reference; window.hip).  The records and working buffers are allocated (zeroed) on the first
+// request with K > 0 and again for a larger K: the track and point buffers are sized (K - 1) cap per frame.
+extern "C" int viso_batch_set_window_refine(viso_batch* b, int K, int mode, double sigma_px) {
+    if (dead(b) || (K != 0 && !window_refine_args_ok(K, mode, sigma_px))) {
+        viso_set_error("viso_batch_set_window_refine: bad argument (K 0, or K in 2..5 with mode 1, or mode 2 with a finite sigma_px > 0)");
+        return VISO_ERR_ARG;
+    }
+    int r;
+    if ((r = enter(b)) < 0) return r;
+    if (K > b->win_kalloc) {
+        if ((r = batch_sync(b)) < 0) return r;
+        void* old[] = {b->win, b->win_lp, b->win_nlp, b->win_tab, b->win_trk, b->win_pts};
+        for (void* p : old) if (p) (void)hipFree(p);
+        b->win = nullptr; b->win_lp = b->win_nlp = b->win_tab = b->win_trk = nullptr; b->win_pts = nullptr; b->win_kalloc = 0;
+        const size_t nf = (size_t)b->nf, c = (size_t)b->cap, T = (size_t)(K - 1) * c;
+        if ((r = dalloc(&b->win, nf)) < 0 || (r = dalloc(&b->win_lp, nf * c)) < 0 || (r = dalloc(&b->win_nlp, nf)) < 0 ||
+            (r = dalloc(&b->win_tab, nf * 2 * c)) < 0 || (r = dalloc(&b->win_trk, nf * 5 * T)) < 0 ||
+            (r = dalloc(&b->win_pts, nf * 6 * T)) < 0) {
+            void* got[] = {b->win, b->win_lp, b->win_nlp, b->win_tab, b->win_trk, b->win_pts};
+            for (void* p : got) if (p) (void)hipFree(p);
+            b->win = nullptr; b->win_lp = b->win_nlp = b->win_tab = b->win_trk = nullptr; b->win_pts = nullptr;
+            return r;
+        }
+        HIP_TRY(hipMemset(b->win, 0, sizeof(viso_window_record) * nf));
+        HIP_TRY(hipMemset(b->win_lp, 0, sizeof(int) * nf * c));
+        HIP_TRY(hipMemset(b->win_nlp, 0, sizeof(int) * nf));
+        HIP_TRY(hipMemset(b->win_tab, 0, sizeof(int) * nf * 2 * c));
+        HIP_TRY(hipMemset(b->win_trk, 0, sizeof(int) * nf * 5 * T));
+        HIP_TRY(hipMemset(b->win_pts, 0, sizeof(double) * nf * 6 * T));
+        b->win_kalloc = K;
+    }
+    b->win_K = K;
+    b->win_mode = K ? mode : 0;
+    b->win_sigma = K && mode == 2 ? sigma_px : 0.0;
+    return VISO_OK;
+}
+
+static int win_ready(viso_batch* b, const char* where) {
+    const int rs_ = batch_sync(b);
+    if (rs_ < 0) return rs_;
+    if (!b->win_last) { viso_set_error("%s: the last run computed no window refinement (K = 0, or matcher_only)", where); return VISO_ERR_ARG; }
+    return VISO_OK;
+}
+
+extern "C" int viso_batch_get_window_refine(viso_batch* b, int t, viso_window_record* out) {
+    if (!slot_ok(b, 0, t) || !out) { viso_set_error("viso_batch_get_window_refine: bad argument"); return VISO_ERR_ARG; }
+    int r;
+    if ((r = win_ready(b, "viso_batch_get_window_refine")) < 0) return r;
+    HIP_TRY(hipMemcpy(out, b->win + t, sizeof(viso_window_record), hipMemcpyDeviceToHost));
+    return VISO_OK;
+}
+
+extern "C" int viso_batch_get_window_refines(viso_batch* b, viso_window_record* out) {
+    if (dead(b) || !out) { viso_set_error("viso_batch_get_window_refines: bad argument"); return VISO_ERR_ARG; }
+    int r;
+    if ((r = win_ready(b, "viso_batch_get_window_refines")) < 0) return r;
+    HIP_TRY(hipMemcpy(out, b->win, sizeof(viso_window_record) * (size_t)b->nf, hipMemcpyDeviceToHost));
+    return VISO_OK;
+}
+
 // Opt-in rectification of raw images (not in the reference; rectify.hip).  Synchronous like the other setters: the batch's work
 // in flight finishes first, then the maps are quantised on the host and the buffers (re)allocated.
 extern "C" int viso_batch_set_rectify(viso_batch* b, int raw_rows, int raw_cols, int out_rows, int out_cols, const float* mapxL,
@@ -1012,9 +1077,21 @@ static int run_rest(viso_batch* b) {
         const size_t c = (size_t)b->cap;
         if (b->ref_mode && (r = launch_motion_refine(ss, b->sitems, b->nf - 1, b->sp, b->ref_mode, b->ref_sigma, b->ref_pts + 6 * c,
                                                      b->ref_idx + c, c, b->ref + 1)) < 0) return r;
+        // opt-in: the sliding-window bundle adjustment over every frame's final inliers (it changes none of the inputs)
+        if (b->win_K) {
+            WinData d;
+            d.X = b->Xp_c; d.obs = b->x_c; d.left = b->circ; d.left_fs = 4 * c; d.lstride = 4; d.lprev = 2;
+            d.tr = b->tr; d.ok = b->ok; d.n_inl = b->n_inl; d.inl = b->inl; d.m = b->mc; d.ld = b->cap; d.tab = b->cap;
+            WinWork w;
+            w.Lp = b->win_lp; w.nLp = b->win_nlp; w.tabs = b->win_tab; w.maxT = (size_t)(b->win_K - 1) * c;
+            w.trk = b->win_trk; w.pts = b->win_pts;
+            if ((r = launch_window_links(ss, d, w, 1, b->nf - 1)) < 0) return r;
+            if ((r = launch_window_refine(ss, d, w, b->sp, b->win_K, b->win_mode, b->win_sigma, 1, b->nf - 1, b->win + 1)) < 0) return r;
+        }
     }
     b->cov_last = b->cov_mode;
     b->ref_last = b->ref_mode;
+    b->win_last = b->win_K;
     if (ss != s) {
         HIP_TRY(hipEventRecord(b->ev_ransac, ss));
         b->ransac_pending = true;

@@ -458,6 +458,25 @@ bool motion_cov_args_ok(int mode, double sigma_px);   // mode 1, or mode 2 with 
 int launch_motion_refine(hipStream_t s, const SolverItem* items_dev, int n_items, const SolverParamsDev& sp, int mode, double sigma,
                          double* pts, int* idx, size_t stride, viso_motion_refine* out);
 bool motion_refine_args_ok(int mode, double sigma_px);   // mode 1, or mode 2 with a finite sigma_px > 0
+// window.hip: the opt-in sliding-window bundle adjustment (viso_batch_set_window_refine).  WinData: the per-frame inputs, frame F's
+// X at X + F * 3 * ld, obs at obs + F * 4 * ld, inl at inl + F * ld, the cur-left / prev-left of row r at left + F * left_fs +
+// r * lstride (+ 0 / + lprev); keypoint indices in [0, tab) can link.  WinWork: the working buffers (window.hip's header).
+struct WinData {
+    const double* X; const double* obs; const int* left; size_t left_fs; int lstride, lprev;
+    const double* tr; const int* ok; const int* n_inl; const int* inl; const int* m;
+    int ld, tab;
+};
+struct WinWork {
+    int* Lp; int* nLp;   // [nf][ld] L' of every frame, [nf] its length
+    int* tabs;           // [nf][2][tab] the unique row by cur-left | by prev-left (-1 none, -2 more than one)
+    int* trk;            // [n_items][5][maxT] the tracks of each window
+    double* pts;         // [n_items][2][3][maxT] their points (current | candidate)
+    size_t maxT;         // (K - 1) ld
+};
+int launch_window_links(hipStream_t s, const WinData& d, const WinWork& w, int j0, int n);
+int launch_window_refine(hipStream_t s, const WinData& d, const WinWork& w, const SolverParamsDev& sp, int K, int mode, double sigma,
+                         int t0, int n, viso_window_record* out);
+bool window_refine_args_ok(int K, int mode, double sigma_px);   // K in 2..5 and motion_refine_args_ok
 int launch_extract_pack(hipStream_t s, const ImageView* imgs_dev, int n_img, int cap, const uint8_t* images,
                         int rows, int cols, int extras, int r8s, int* r8cnt);
 int launch_harris_response(hipStream_t s, const uint8_t* images, int n_img, int rows, int cols, double k, float* resp);
