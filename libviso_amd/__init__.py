@@ -148,6 +148,11 @@ def _i32(a):
     return np.ascontiguousarray(a, dtype=np.int32)
 
 
+def _sigma(sigma):
+    """The sigma_px argument of the estimators: 0.0 when not given (mode 1 ignores it)."""
+    return float(sigma) if sigma is not None else 0.0
+
+
 
 
 def matcher_variants():
@@ -453,17 +458,22 @@ def rectify_images(raw, mapx, mapy, out_shape, border=0):
 HARRIS_K = float(np.float32(0.04))   # the reference's intended default (float k = .04, src/viso.cpp:915)
 
 
+def _pose_inputs(where, X, obs, tr, inliers):
+    """The direct calls' inputs as contiguous arrays (X 3 x m, obs 4 x m, tr 6 float64; the inlier list int32), and m."""
+    X, obs, tr, inl = _f64(X), _f64(obs), _f64(tr), _i32(inliers)
+    if X.ndim != 2 or X.shape[0] != 3 or obs.shape != (4, X.shape[1]) or tr.shape != (6,):
+        raise ValueError(f"{where}: X must be (3, m), obs (4, m) and tr (6,); got {X.shape}, {obs.shape}, {tr.shape}")
+    return X, obs, tr, inl, X.shape[1]
+
+
 def pose_covariance(X, obs, tr, inliers, param, mode=1, sigma=None):
     """viso_pose_covariance: the motion covariance record (a 0-d MOTION_COV_DTYPE array) of one frame's solve -- X 3 x m, obs 4 x m,
     tr 6, inliers the final inlier list; mode 1 estimates sigma^2, mode 2 takes sigma (pixels)."""
     L = load()
-    X, obs, tr, inl = _f64(X), _f64(obs), _f64(tr), _i32(inliers)
-    if X.ndim != 2 or X.shape[0] != 3 or obs.shape != (4, X.shape[1]) or tr.shape != (6,):
-        raise ValueError(f"pose_covariance: X must be (3, m), obs (4, m) and tr (6,); got {X.shape}, {obs.shape}, {tr.shape}")
-    m = X.shape[1]
+    X, obs, tr, inl, m = _pose_inputs("pose_covariance", X, obs, tr, inliers)
     out = np.zeros((), MOTION_COV_DTYPE)
     r = L.viso_pose_covariance(ptr(X, C.c_double), ptr(obs, C.c_double), m, ptr(tr, C.c_double), ptr(inl, C.c_int32), len(inl),
-                               C.byref(param), int(mode), float(sigma) if sigma is not None else 0.0, out.ctypes.data)
+                               C.byref(param), int(mode), _sigma(sigma), out.ctypes.data)
     if r != 1:
         _err("viso_pose_covariance", r)
     return out
@@ -474,15 +484,11 @@ def pose_refine(X, obs, tr, inliers, param, mode=1, sigma=None):
     list; mode 1 estimates sigma^2, mode 2 takes sigma (pixels).  Returns (record, points): a 0-d MOTION_REFINE_DTYPE array and
     the refined points (3, n) in the order of the used inliers (empty unless status is 1)."""
     L = load()
-    X, obs, tr, inl = _f64(X), _f64(obs), _f64(tr), _i32(inliers)
-    if X.ndim != 2 or X.shape[0] != 3 or obs.shape != (4, X.shape[1]) or tr.shape != (6,):
-        raise ValueError(f"pose_refine: X must be (3, m), obs (4, m) and tr (6,); got {X.shape}, {obs.shape}, {tr.shape}")
-    m = X.shape[1]
+    X, obs, tr, inl, m = _pose_inputs("pose_refine", X, obs, tr, inliers)
     out = np.zeros((), MOTION_REFINE_DTYPE)
     pts = np.zeros((3, max(len(inl), 1)))
     r = L.viso_pose_refine(ptr(X, C.c_double), ptr(obs, C.c_double), m, ptr(tr, C.c_double), ptr(inl, C.c_int32), len(inl),
-                           C.byref(param), int(mode), float(sigma) if sigma is not None else 0.0, out.ctypes.data,
-                           ptr(pts, C.c_double))
+                           C.byref(param), int(mode), _sigma(sigma), out.ctypes.data, ptr(pts, C.c_double))
     if r != 1:
         _err("viso_pose_refine", r)
     k = int(out["n"]) if int(out["status"]) == 1 else 0
@@ -520,8 +526,8 @@ def window_refine(frames, param, mode=1, sigma=None):
     m, n = np.ascontiguousarray(ms, np.intc), np.ascontiguousarray(ns, np.intc)
     out = np.zeros((), WINDOW_RECORD_DTYPE)
     r = L.viso_window_refine(len(frames) + 1, ptr(m, C.c_int), ptr(X, C.c_double), ptr(obs, C.c_double), ptr(left, C.c_int32),
-                             ptr(tr, C.c_double), ptr(inl, C.c_int32), ptr(n, C.c_int), C.byref(param), int(mode),
-                             float(sigma) if sigma is not None else 0.0, out.ctypes.data)
+                             ptr(tr, C.c_double), ptr(inl, C.c_int32), ptr(n, C.c_int), C.byref(param), int(mode), _sigma(sigma),
+                             out.ctypes.data)
     if r != 1:
         _err("viso_window_refine", r)
     return out
@@ -738,41 +744,42 @@ class Batch:
         self._chk("viso_batch_get_image", self.L.viso_batch_get_image(self.h, int(t), int(side), ptr(out, C.c_uint8)))
         return out
 
+    def _records(self, name, dtype, t=None):
+        """viso_batch_get_<name>(t): frame t's record of the last run (a 0-d array of dtype), or with t None viso_batch_get_<name>s:
+        the records of all frames (structured array [n_frames], frame 0: status 0)."""
+        if t is None:
+            out = np.zeros(self.nf, dtype)
+            self._chk(f"viso_batch_get_{name}s", getattr(self.L, f"viso_batch_get_{name}s")(self.h, out.ctypes.data))
+        else:
+            out = np.zeros((), dtype)
+            self._chk(f"viso_batch_get_{name}", getattr(self.L, f"viso_batch_get_{name}")(self.h, int(t), out.ctypes.data))
+        return out
+
     def set_covariance(self, mode, sigma=None):
         """viso_batch_set_covariance: 0 = off (default), 1 = per-frame motion covariance with sigma^2 estimated, 2 = with the given
         sigma (pixels), for the next runs (run, and run_images unless matcher_only)."""
-        self._chk("viso_batch_set_covariance",
-                  self.L.viso_batch_set_covariance(self.h, int(mode), float(sigma) if sigma is not None else 0.0))
+        self._chk("viso_batch_set_covariance", self.L.viso_batch_set_covariance(self.h, int(mode), _sigma(sigma)))
 
     def covariance(self, t):
         """The motion covariance record of frame t from the last run (a 0-d MOTION_COV_DTYPE array)."""
-        out = np.zeros((), MOTION_COV_DTYPE)
-        self._chk("viso_batch_get_covariance", self.L.viso_batch_get_covariance(self.h, int(t), out.ctypes.data))
-        return out
+        return self._records("covariance", MOTION_COV_DTYPE, t)
 
     def covariances(self):
         """The records of all frames from the last run: structured array [n_frames] of MOTION_COV_DTYPE (frame 0: status 0)."""
-        out = np.zeros(self.nf, MOTION_COV_DTYPE)
-        self._chk("viso_batch_get_covariances", self.L.viso_batch_get_covariances(self.h, out.ctypes.data))
-        return out
+        return self._records("covariance", MOTION_COV_DTYPE)
 
     def set_refine(self, mode, sigma=None):
         """viso_batch_set_refine: 0 = off (default), 1 = two-frame bundle adjustment of every solved frame with sigma^2 estimated,
         2 = with the given sigma (pixels), for the next runs (run, and run_images unless matcher_only)."""
-        self._chk("viso_batch_set_refine",
-                  self.L.viso_batch_set_refine(self.h, int(mode), float(sigma) if sigma is not None else 0.0))
+        self._chk("viso_batch_set_refine", self.L.viso_batch_set_refine(self.h, int(mode), _sigma(sigma)))
 
     def refine(self, t):
         """The refinement record of frame t from the last run (a 0-d MOTION_REFINE_DTYPE array)."""
-        out = np.zeros((), MOTION_REFINE_DTYPE)
-        self._chk("viso_batch_get_refine", self.L.viso_batch_get_refine(self.h, int(t), out.ctypes.data))
-        return out
+        return self._records("refine", MOTION_REFINE_DTYPE, t)
 
     def refines(self):
         """The records of all frames from the last run: structured array [n_frames] of MOTION_REFINE_DTYPE (frame 0: status 0)."""
-        out = np.zeros(self.nf, MOTION_REFINE_DTYPE)
-        self._chk("viso_batch_get_refines", self.L.viso_batch_get_refines(self.h, out.ctypes.data))
-        return out
+        return self._records("refine", MOTION_REFINE_DTYPE)
 
     def refined_points(self, t):
         """(idx [n] int32, X [3][n] float64): frame t's used inliers and their refined points from the last run (empty unless the
@@ -788,20 +795,15 @@ class Batch:
         """viso_batch_set_window_refine: K = 0 off (default), K in 2..5 the sliding-window bundle adjustment of every solved frame
         over the window of frames t-K+1..t (mode 1: sigma^2 estimated, mode 2: the given sigma in pixels), for the next runs (run,
         and run_images unless matcher_only)."""
-        self._chk("viso_batch_set_window_refine", self.L.viso_batch_set_window_refine(
-            self.h, int(K), int(mode), float(sigma) if sigma is not None else 0.0))
+        self._chk("viso_batch_set_window_refine", self.L.viso_batch_set_window_refine(self.h, int(K), int(mode), _sigma(sigma)))
 
     def window_refine(self, t):
         """The window record of frame t from the last run (a 0-d WINDOW_RECORD_DTYPE array)."""
-        out = np.zeros((), WINDOW_RECORD_DTYPE)
-        self._chk("viso_batch_get_window_refine", self.L.viso_batch_get_window_refine(self.h, int(t), out.ctypes.data))
-        return out
+        return self._records("window_refine", WINDOW_RECORD_DTYPE, t)
 
     def window_refines(self):
         """The window records of all frames from the last run: structured array [n_frames] of WINDOW_RECORD_DTYPE (frame 0: status 0)."""
-        out = np.zeros(self.nf, WINDOW_RECORD_DTYPE)
-        self._chk("viso_batch_get_window_refines", self.L.viso_batch_get_window_refines(self.h, out.ctypes.data))
-        return out
+        return self._records("window_refine", WINDOW_RECORD_DTYPE)
 
     def points(self, t):
         """(X [3][m], obs [4][m]) float64: frame t's solver inputs from the last run (previous-frame points, (uL, vL, uR, vR))."""

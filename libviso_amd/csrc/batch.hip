@@ -15,6 +15,7 @@
 #include "common.h"
 
 #include <string.h>
+#include <initializer_list>
 #include <vector>
 
 #define VISO_NPIN_SLOTS 4
@@ -110,6 +111,28 @@ template <class T>
 static int dalloc(T** p, size_t count) {
     *p = nullptr;
     HIP_TRY(hipMalloc((void**)p, sizeof(T) * (count ? count : 1)));
+    return VISO_OK;
+}
+
+// One buffer of dalloc_zeroed: the pointer to set and its element count.
+struct DBuf {
+    void** p; size_t bytes;
+    template <class T> DBuf(T** q, size_t count) : p(reinterpret_cast<void**>(q)), bytes(sizeof(T) * (count ? count : 1)) {}
+};
+
+// Allocates every buffer of the list and zeroes it.  When an allocation fails, the buffers already allocated are freed and every
+// pointer of the list is left null.
+static int dalloc_zeroed(std::initializer_list<DBuf> bufs) {
+    int r = VISO_OK;
+    for (const DBuf& d : bufs) *d.p = nullptr;
+    for (const DBuf& d : bufs)
+        if ((r = dalloc(reinterpret_cast<char**>(d.p), d.bytes)) < 0) break;
+    if (r < 0) {
+        for (const DBuf& d : bufs) if (*d.p) (void)hipFree(*d.p);
+        for (const DBuf& d : bufs) *d.p = nullptr;
+        return r;
+    }
+    for (const DBuf& d : bufs) HIP_TRY(hipMemset(*d.p, 0, d.bytes));
     return VISO_OK;
 }
 
@@ -809,7 +832,7 @@ extern "C" int viso_batch_get_subpixel(viso_batch* b, int t, float* uv, int* out
 
 // Opt-in motion covariance (not in the reference; covariance.hip).  The records are allocated (zeroed) on the first request.
 extern "C" int viso_batch_set_covariance(viso_batch* b, int mode, double sigma_px) {
-    if (dead(b) || (mode != 0 && !motion_cov_args_ok(mode, sigma_px))) {
+    if (dead(b) || (mode != 0 && !motion_args_ok(mode, sigma_px))) {
         viso_set_error("viso_batch_set_covariance: bad argument (mode 0, 1, or 2 with a finite sigma_px > 0)");
         return VISO_ERR_ARG;
     }
@@ -825,27 +848,36 @@ extern "C" int viso_batch_set_covariance(viso_batch* b, int mode, double sigma_p
     return VISO_OK;
 }
 
-static int cov_ready(viso_batch* b, const char* where) {
+// An opt-in estimator's records of the last run (the flag `last` of viso_batch): after the batch's work in flight, an error naming
+// `where` when that run computed none.
+static int records_ready(viso_batch* b, int last, const char* where, const char* none) {
     const int rs_ = batch_sync(b);
     if (rs_ < 0) return rs_;
-    if (!b->cov_last) { viso_set_error("%s: the last run computed no covariance (mode 0, or matcher_only)", where); return VISO_ERR_ARG; }
+    if (!last) { viso_set_error("%s: the last run computed no %s", where, none); return VISO_ERR_ARG; }
+    return VISO_OK;
+}
+#define COV_NONE "covariance (mode 0, or matcher_only)"
+#define REF_NONE "refinement (mode 0, or matcher_only)"
+#define WIN_NONE "window refinement (K = 0, or matcher_only)"
+
+// The body of the record getters: frame t's record, or (all) the records of every frame, of the estimator whose records and flag
+// are the members recs, last.
+template <class Rec>
+static int get_records(viso_batch* b, bool all, int t, Rec* out, Rec* viso_batch::*recs, int viso_batch::*last, const char* where,
+                       const char* none) {
+    if ((all ? dead(b) : !slot_ok(b, 0, t)) || !out) { viso_set_error("%s: bad argument", where); return VISO_ERR_ARG; }
+    int r;
+    if ((r = records_ready(b, b->*last, where, none)) < 0) return r;
+    HIP_TRY(hipMemcpy(out, b->*recs + (all ? 0 : t), sizeof(Rec) * (all ? (size_t)b->nf : 1), hipMemcpyDeviceToHost));
     return VISO_OK;
 }
 
 extern "C" int viso_batch_get_covariance(viso_batch* b, int t, viso_motion_cov* out) {
-    if (!slot_ok(b, 0, t) || !out) { viso_set_error("viso_batch_get_covariance: bad argument"); return VISO_ERR_ARG; }
-    int r;
-    if ((r = cov_ready(b, "viso_batch_get_covariance")) < 0) return r;
-    HIP_TRY(hipMemcpy(out, b->cov + t, sizeof(viso_motion_cov), hipMemcpyDeviceToHost));
-    return VISO_OK;
+    return get_records(b, false, t, out, &viso_batch::cov, &viso_batch::cov_last, "viso_batch_get_covariance", COV_NONE);
 }
 
 extern "C" int viso_batch_get_covariances(viso_batch* b, viso_motion_cov* out) {
-    if (dead(b) || !out) { viso_set_error("viso_batch_get_covariances: bad argument"); return VISO_ERR_ARG; }
-    int r;
-    if ((r = cov_ready(b, "viso_batch_get_covariances")) < 0) return r;
-    HIP_TRY(hipMemcpy(out, b->cov, sizeof(viso_motion_cov) * (size_t)b->nf, hipMemcpyDeviceToHost));
-    return VISO_OK;
+    return get_records(b, true, 0, out, &viso_batch::cov, &viso_batch::cov_last, "viso_batch_get_covariances", COV_NONE);
 }
 
 // Frame t's solver inputs (what the circle join wrote for the last run): Xp_c and x_c rows of cap doubles.
@@ -865,7 +897,7 @@ extern "C" int viso_batch_get_points(viso_batch* b, int t, double* X3xcap, doubl
 // Opt-in motion refinement (not in the reference; refine.hip).  The records and working buffers are allocated (zeroed) on the
 // first request.
 extern "C" int viso_batch_set_refine(viso_batch* b, int mode, double sigma_px) {
-    if (dead(b) || (mode != 0 && !motion_refine_args_ok(mode, sigma_px))) {
+    if (dead(b) || (mode != 0 && !motion_args_ok(mode, sigma_px))) {
         viso_set_error("viso_batch_set_refine: bad argument (mode 0, 1, or 2 with a finite sigma_px > 0)");
         return VISO_ERR_ARG;
     }
@@ -874,48 +906,26 @@ extern "C" int viso_batch_set_refine(viso_batch* b, int mode, double sigma_px) {
     if (mode && !b->ref) {
         if ((r = batch_sync(b)) < 0) return r;
         const size_t nf = (size_t)b->nf, c = (size_t)b->cap;
-        if ((r = dalloc(&b->ref, nf)) < 0 || (r = dalloc(&b->ref_pts, nf * 6 * c)) < 0 || (r = dalloc(&b->ref_idx, nf * c)) < 0) {
-            for (void* p : {(void*)b->ref, (void*)b->ref_pts, (void*)b->ref_idx}) if (p) (void)hipFree(p);
-            b->ref = nullptr; b->ref_pts = nullptr; b->ref_idx = nullptr;
-            return r;
-        }
-        HIP_TRY(hipMemset(b->ref, 0, sizeof(viso_motion_refine) * nf));
-        HIP_TRY(hipMemset(b->ref_pts, 0, sizeof(double) * nf * 6 * c));
-        HIP_TRY(hipMemset(b->ref_idx, 0, sizeof(int) * nf * c));
+        if ((r = dalloc_zeroed({{&b->ref, nf}, {&b->ref_pts, nf * 6 * c}, {&b->ref_idx, nf * c}})) < 0) return r;
     }
     b->ref_mode = mode;
     b->ref_sigma = mode == 2 ? sigma_px : 0.0;
     return VISO_OK;
 }
 
-static int ref_ready(viso_batch* b, const char* where) {
-    const int rs_ = batch_sync(b);
-    if (rs_ < 0) return rs_;
-    if (!b->ref_last) { viso_set_error("%s: the last run computed no refinement (mode 0, or matcher_only)", where); return VISO_ERR_ARG; }
-    return VISO_OK;
-}
-
 extern "C" int viso_batch_get_refine(viso_batch* b, int t, viso_motion_refine* out) {
-    if (!slot_ok(b, 0, t) || !out) { viso_set_error("viso_batch_get_refine: bad argument"); return VISO_ERR_ARG; }
-    int r;
-    if ((r = ref_ready(b, "viso_batch_get_refine")) < 0) return r;
-    HIP_TRY(hipMemcpy(out, b->ref + t, sizeof(viso_motion_refine), hipMemcpyDeviceToHost));
-    return VISO_OK;
+    return get_records(b, false, t, out, &viso_batch::ref, &viso_batch::ref_last, "viso_batch_get_refine", REF_NONE);
 }
 
 extern "C" int viso_batch_get_refines(viso_batch* b, viso_motion_refine* out) {
-    if (dead(b) || !out) { viso_set_error("viso_batch_get_refines: bad argument"); return VISO_ERR_ARG; }
-    int r;
-    if ((r = ref_ready(b, "viso_batch_get_refines")) < 0) return r;
-    HIP_TRY(hipMemcpy(out, b->ref, sizeof(viso_motion_refine) * (size_t)b->nf, hipMemcpyDeviceToHost));
-    return VISO_OK;
+    return get_records(b, true, 0, out, &viso_batch::ref, &viso_batch::ref_last, "viso_batch_get_refines", REF_NONE);
 }
 
 // Frame t's refined points (the kernel leaves the final state in half 0 of the frame's point buffer) and L'.
 extern "C" int viso_batch_get_refined_points(viso_batch* b, int t, int32_t* idx, double* X3xcap, int* n) {
     if (!slot_ok(b, 0, t) || !n) { viso_set_error("viso_batch_get_refined_points: bad argument"); return VISO_ERR_ARG; }
     int r;
-    if ((r = ref_ready(b, "viso_batch_get_refined_points")) < 0) return r;
+    if ((r = records_ready(b, b->ref_last, "viso_batch_get_refined_points", REF_NONE)) < 0) return r;
     viso_motion_refine rec;
     HIP_TRY(hipMemcpy(&rec, b->ref + t, sizeof(rec), hipMemcpyDeviceToHost));
     const int nn = rec.status == 1 ? (rec.n < 0 ? 0 : rec.n > b->cap ? b->cap : rec.n) : 0;
@@ -944,20 +954,9 @@ extern "C" int viso_batch_set_window_refine(viso_batch* b, int K, int mode, doub
         for (void* p : old) if (p) (void)hipFree(p);
         b->win = nullptr; b->win_lp = b->win_nlp = b->win_tab = b->win_trk = nullptr; b->win_pts = nullptr; b->win_kalloc = 0;
         const size_t nf = (size_t)b->nf, c = (size_t)b->cap, T = (size_t)(K - 1) * c;
-        if ((r = dalloc(&b->win, nf)) < 0 || (r = dalloc(&b->win_lp, nf * c)) < 0 || (r = dalloc(&b->win_nlp, nf)) < 0 ||
-            (r = dalloc(&b->win_tab, nf * 2 * c)) < 0 || (r = dalloc(&b->win_trk, nf * 5 * T)) < 0 ||
-            (r = dalloc(&b->win_pts, nf * 6 * T)) < 0) {
-            void* got[] = {b->win, b->win_lp, b->win_nlp, b->win_tab, b->win_trk, b->win_pts};
-            for (void* p : got) if (p) (void)hipFree(p);
-            b->win = nullptr; b->win_lp = b->win_nlp = b->win_tab = b->win_trk = nullptr; b->win_pts = nullptr;
+        if ((r = dalloc_zeroed({{&b->win, nf}, {&b->win_lp, nf * c}, {&b->win_nlp, nf}, {&b->win_tab, nf * 2 * c},
+                                {&b->win_trk, nf * 5 * T}, {&b->win_pts, nf * 6 * T}})) < 0)
             return r;
-        }
-        HIP_TRY(hipMemset(b->win, 0, sizeof(viso_window_record) * nf));
-        HIP_TRY(hipMemset(b->win_lp, 0, sizeof(int) * nf * c));
-        HIP_TRY(hipMemset(b->win_nlp, 0, sizeof(int) * nf));
-        HIP_TRY(hipMemset(b->win_tab, 0, sizeof(int) * nf * 2 * c));
-        HIP_TRY(hipMemset(b->win_trk, 0, sizeof(int) * nf * 5 * T));
-        HIP_TRY(hipMemset(b->win_pts, 0, sizeof(double) * nf * 6 * T));
         b->win_kalloc = K;
     }
     b->win_K = K;
@@ -966,27 +965,12 @@ extern "C" int viso_batch_set_window_refine(viso_batch* b, int K, int mode, doub
     return VISO_OK;
 }
 
-static int win_ready(viso_batch* b, const char* where) {
-    const int rs_ = batch_sync(b);
-    if (rs_ < 0) return rs_;
-    if (!b->win_last) { viso_set_error("%s: the last run computed no window refinement (K = 0, or matcher_only)", where); return VISO_ERR_ARG; }
-    return VISO_OK;
-}
-
 extern "C" int viso_batch_get_window_refine(viso_batch* b, int t, viso_window_record* out) {
-    if (!slot_ok(b, 0, t) || !out) { viso_set_error("viso_batch_get_window_refine: bad argument"); return VISO_ERR_ARG; }
-    int r;
-    if ((r = win_ready(b, "viso_batch_get_window_refine")) < 0) return r;
-    HIP_TRY(hipMemcpy(out, b->win + t, sizeof(viso_window_record), hipMemcpyDeviceToHost));
-    return VISO_OK;
+    return get_records(b, false, t, out, &viso_batch::win, &viso_batch::win_last, "viso_batch_get_window_refine", WIN_NONE);
 }
 
 extern "C" int viso_batch_get_window_refines(viso_batch* b, viso_window_record* out) {
-    if (dead(b) || !out) { viso_set_error("viso_batch_get_window_refines: bad argument"); return VISO_ERR_ARG; }
-    int r;
-    if ((r = win_ready(b, "viso_batch_get_window_refines")) < 0) return r;
-    HIP_TRY(hipMemcpy(out, b->win, sizeof(viso_window_record) * (size_t)b->nf, hipMemcpyDeviceToHost));
-    return VISO_OK;
+    return get_records(b, true, 0, out, &viso_batch::win, &viso_batch::win_last, "viso_batch_get_window_refines", WIN_NONE);
 }
 
 // Opt-in rectification of raw images (not in the reference; rectify.hip).  Synchronous like the other setters: the batch's work

@@ -145,6 +145,7 @@ struct PlainProf {
     int fn; hipStream_t s; bool on; int marks; double t0, tw, wait;
 };
 int ctx_scratch(viso_ctx* c, int slot, size_t bytes, void** out, bool zero_new = false);   // zero_new: a block that is (re)allocated starts zeroed
+static inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }   // offsets of the pieces of a scratch block
 int ctx_pinned(viso_ctx* c, int which, size_t bytes, char** out);
 void plain_cache_free(viso_ctx* c);   // plain.hip; from viso_ctx_destroy
 // plain.hip: a call of the reference's loop that the frame's stereo call has already answered (1 = served, 0 = go to the device)
@@ -452,12 +453,25 @@ int launch_rectify(hipStream_t s, const uint8_t* raw, size_t raw_fs, size_t raw_
 // X, obs, m_ptr, ld, tr, ok, n_inl, inl (what ransac_refit_kernel left)
 int launch_motion_cov(hipStream_t s, const SolverItem* items_dev, int n_items, const SolverParamsDev& sp, int mode, double sigma,
                       viso_motion_cov* out);
-bool motion_cov_args_ok(int mode, double sigma_px);   // mode 1, or mode 2 with a finite sigma_px > 0
+bool motion_args_ok(int mode, double sigma_px);   // the estimators' mode 1, or mode 2 with a finite sigma_px > 0
+// The direct calls viso_pose_covariance / viso_pose_refine (inside a PlainLock): checks the arguments (the error names `where`),
+// then stages one SolverItem on the default context's stream -- X, obs, inl, tr, the words ok, n_inl, m, the item, then
+// rec_bytes for the record and extra_bytes for the caller's own buffers, in scratch slot 0.
+struct PoseCall {
+    hipStream_t s;
+    SolverParamsDev sp;
+    size_t ld;                 // max(m, 1): the item's row length
+    const SolverItem* item;    // device
+    char* rec;                 // device, rec_bytes
+    char* extra;               // device, extra_bytes (256-byte aligned)
+};
+int pose_call_stage(const char* where, const double* X, const double* obs, int m, const double* tr, const int32_t* inl, int n_inl,
+                    const viso_param* param, int mode, double sigma_px, const void* out, size_t rec_bytes, size_t extra_bytes,
+                    PoseCall* pc);
 // refine.hip: the opt-in two-frame bundle adjustment (viso_batch_set_refine); one record per item, out[item], from the item's X,
 // obs, m_ptr, ld, tr, ok, n_inl, inl; pts [n_items][2][3][stride] and idx [n_items][stride] its working buffers (stride >= ld)
 int launch_motion_refine(hipStream_t s, const SolverItem* items_dev, int n_items, const SolverParamsDev& sp, int mode, double sigma,
                          double* pts, int* idx, size_t stride, viso_motion_refine* out);
-bool motion_refine_args_ok(int mode, double sigma_px);   // mode 1, or mode 2 with a finite sigma_px > 0
 // window.hip: the opt-in sliding-window bundle adjustment (viso_batch_set_window_refine).  WinData: the per-frame inputs, frame F's
 // X at X + F * 3 * ld, obs at obs + F * 4 * ld, inl at inl + F * ld, the cur-left / prev-left of row r at left + F * left_fs +
 // r * lstride (+ 0 / + lprev); keypoint indices in [0, tab) can link.  WinWork: the working buffers (window.hip's header).
@@ -476,7 +490,7 @@ struct WinWork {
 int launch_window_links(hipStream_t s, const WinData& d, const WinWork& w, int j0, int n);
 int launch_window_refine(hipStream_t s, const WinData& d, const WinWork& w, const SolverParamsDev& sp, int K, int mode, double sigma,
                          int t0, int n, viso_window_record* out);
-bool window_refine_args_ok(int K, int mode, double sigma_px);   // K in 2..5 and motion_refine_args_ok
+bool window_refine_args_ok(int K, int mode, double sigma_px);   // K in 2..5 and motion_args_ok
 int launch_extract_pack(hipStream_t s, const ImageView* imgs_dev, int n_img, int cap, const uint8_t* images,
                         int rows, int cols, int extras, int r8s, int* r8cnt);
 int launch_harris_response(hipStream_t s, const uint8_t* images, int n_img, int rows, int cols, double k, float* resp);

@@ -1,9 +1,10 @@
 // covariance.hip — the opt-in per-frame motion covariance (include/viso_hip.h, "motion covariance").  Not in the
 // reference.  One workgroup per frame: every lane strides over the final inlier list and keeps the 21 + 21 + 6 + 2 sums
 // (A = sum w^2 J'J, B = sum w^4 J'(I + M M')J, g = sum w^2 J'r, sum |r|^2, sum |M|_F^2) in fp64 registers; the sums go through the
-// DPP wave reduction of solver_dev.h and a fixed-order sum over the waves in LDS, and one lane does the 6 x 6 Cholesky work
+// workgroup sum of solver_dev.h (block_sum: DPP rows, then the waves in a fixed order in LDS), and one lane does the 6 x 6 Cholesky work
 // (A^-1 B A^-1, delta = A^-1 g, g'B^-1 g).  The summation tree depends on n only: the batch at any chunking and the direct call
-// give byte-identical records for the same inputs.  No scratch memory (check with -Rpass-analysis=kernel-resource-usage).
+// give byte-identical records for the same inputs.  No scratch memory (check with -Rpass-analysis=kernel-resource-usage).  The
+// direct call's staging (pose_call_stage) and the estimators' argument rule (motion_args_ok) are here; viso_pose_refine uses both.
 #include "solver_dev.h"
 
 #include <math.h>
@@ -93,8 +94,6 @@ __device__ __forceinline__ void cov_point(const RotDev& R, const SolverParamsDev
     S[49] += Mu[0] * Mu[0] + Mu[1] * Mu[1] + Mu[2] * Mu[2] + Mr[0] * Mr[0] + Mr[1] * Mr[1] + Mr[2] * Mr[2] +
              2.0 * (Mv[0] * Mv[0] + Mv[1] * Mv[1] + Mv[2] * Mv[2]);
 }
-
-__device__ __forceinline__ int up6(int p, int q) { return p * 6 - p * (p - 1) / 2 + (q - p); }   // p <= q
 
 // In-place Cholesky of a symmetric 6 x 6 (lower triangle of the result in L); false when a pivot is not > 1e-12 x the original
 // diagonal entry (NaN included).  Every index is static: the matrix stays in registers.
@@ -223,7 +222,6 @@ __device__ __forceinline__ void cov_zero(viso_motion_cov* o, int status, int n) 
 __global__ __launch_bounds__(COV_THREADS) void motion_cov_kernel(CovArgs a) {
     __shared__ double red[COV_WAVES * COV_NS];
     __shared__ double tot[COV_NS];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int item = blockIdx.x;
     if (item >= a.n_items) return;
     const SolverItem S = a.items[item];
@@ -242,25 +240,8 @@ __global__ __launch_bounds__(COV_THREADS) void motion_cov_kernel(CovArgs a) {
 #pragma unroll
     for (int k = 0; k < COV_NS; ++k) acc[k] = 0.0;
     for (int j = threadIdx.x; j < n; j += COV_THREADS) cov_point(R, a.sp, S.X, S.obs, S.ld, S.inl[j], j, acc);
-#pragma unroll
-    for (int k = 0; k < COV_NS; ++k) {
-        const double v = wave_sum_to_lane63(acc[k]);
-        if (lane == 63) red[wave * COV_NS + k] = v;
-        if ((k & 3) == 3) __builtin_amdgcn_sched_barrier(0);   // four chains in flight, not 50: registers
-    }
-    __syncthreads();
-    if (threadIdx.x < COV_NS) {
-        double s = red[threadIdx.x];
-#pragma unroll
-        for (int w = 1; w < COV_WAVES; ++w) s += red[w * COV_NS + threadIdx.x];   // fixed order over the waves
-        tot[threadIdx.x] = s;
-    }
-    __syncthreads();
+    block_sum<COV_NS, COV_WAVES>(acc, red, tot);
     if (threadIdx.x == 0) cov_finish(tot, n, a.mode, a.sigma2, o);
-}
-
-bool motion_cov_args_ok(int mode, double sigma_px) {
-    return mode == 1 || (mode == 2 && isfinite(sigma_px) && sigma_px > 0.0);
 }
 
 int launch_motion_cov(hipStream_t s, const SolverItem* items_dev, int n_items, const SolverParamsDev& sp, int mode, double sigma,
@@ -273,28 +254,30 @@ int launch_motion_cov(hipStream_t s, const SolverItem* items_dev, int n_items, c
     return VISO_OK;
 }
 
-// ---- the direct call: host pointers, default context ----------------------------------------------------------------------
-static size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
+bool motion_args_ok(int mode, double sigma_px) {
+    return mode == 1 || (mode == 2 && isfinite(sigma_px) && sigma_px > 0.0);
+}
 
-extern "C" int viso_pose_covariance(const double* X, const double* obs, int m, const double tr[6], const int32_t* inl, int n_inl,
-                                    const viso_param* param, int mode, double sigma_px, viso_motion_cov* out) {
+// ---- the direct calls: host pointers, default context ---------------------------------------------------------------------
+int pose_call_stage(const char* where, const double* X, const double* obs, int m, const double* tr, const int32_t* inl, int n_inl,
+                    const viso_param* param, int mode, double sigma_px, const void* out, size_t rec_bytes, size_t extra_bytes,
+                    PoseCall* pc) {
     bool ok = m >= 0 && n_inl >= 0 && n_inl <= m && tr && param && out && (m == 0 || (X && obs)) && (n_inl == 0 || inl) &&
-              motion_cov_args_ok(mode, sigma_px);
+              motion_args_ok(mode, sigma_px);
     for (int j = 0; ok && j < n_inl; ++j) ok = inl[j] >= 0 && inl[j] < m;
     if (!ok) {
-        viso_set_error("viso_pose_covariance: bad argument (m >= 0, 0 <= n_inl <= m, indices in [0, m), mode 1 or mode 2 with a "
-                       "finite sigma_px > 0)");
+        viso_set_error("%s: bad argument (m >= 0, 0 <= n_inl <= m, indices in [0, m), mode 1 or mode 2 with a finite sigma_px > 0)",
+                       where);
         return VISO_ERR_ARG;
     }
-    PlainLock lk;
     viso_ctx* c = viso_default_ctx();
     if (!c) return VISO_ERR_HIP;
     HIP_TRY(hipSetDevice(c->device));
     const size_t ld = (size_t)(m > 0 ? m : 1);
-    // one block: X [3][ld] | obs [4][ld] | inl [ld] | tr [6] | ok, n_inl, m | the item | the record
+    // one block: X [3][ld] | obs [4][ld] | inl [ld] | tr [6] | ok, n_inl, m | the item | the record | the caller's extra
     const size_t oX = 0, oO = al256(oX + sizeof(double) * 3 * ld), oI = al256(oO + sizeof(double) * 4 * ld),
                  oT = al256(oI + sizeof(int) * ld), oW = al256(oT + sizeof(double) * 6), oS = al256(oW + sizeof(int) * 4),
-                 oR = al256(oS + sizeof(SolverItem)), bytes = al256(oR + sizeof(viso_motion_cov));
+                 oR = al256(oS + sizeof(SolverItem)), oE = al256(oR + rec_bytes), bytes = al256(oE + extra_bytes);
     char* d;
     int r;
     if ((r = ctx_scratch(c, 0, bytes, (void**)&d)) < 0) return r;
@@ -314,11 +297,25 @@ extern "C" int viso_pose_covariance(const double* X, const double* obs, int m, c
     HIP_TRY(hipMemcpyAsync(d + oT, tr, sizeof(double) * 6, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(words, hw, sizeof(hw), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d + oS, &it, sizeof(it), hipMemcpyHostToDevice, s));
-    SolverParamsDev sp;
-    fill_solver_params(&sp, param);
-    if ((r = launch_motion_cov(s, reinterpret_cast<const SolverItem*>(d + oS), 1, sp, mode, sigma_px,
-                               reinterpret_cast<viso_motion_cov*>(d + oR))) < 0) return r;
-    HIP_TRY(hipMemcpyAsync(out, d + oR, sizeof(viso_motion_cov), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    pc->s = s;
+    fill_solver_params(&pc->sp, param);
+    pc->ld = ld;
+    pc->item = reinterpret_cast<const SolverItem*>(d + oS);
+    pc->rec = d + oR;
+    pc->extra = d + oE;
+    return VISO_OK;
+}
+
+extern "C" int viso_pose_covariance(const double* X, const double* obs, int m, const double tr[6], const int32_t* inl, int n_inl,
+                                    const viso_param* param, int mode, double sigma_px, viso_motion_cov* out) {
+    PlainLock lk;
+    PoseCall pc;
+    int r;
+    if ((r = pose_call_stage("viso_pose_covariance", X, obs, m, tr, inl, n_inl, param, mode, sigma_px, out, sizeof(viso_motion_cov), 0,
+                             &pc)) < 0)
+        return r;
+    if ((r = launch_motion_cov(pc.s, pc.item, 1, pc.sp, mode, sigma_px, reinterpret_cast<viso_motion_cov*>(pc.rec))) < 0) return r;
+    HIP_TRY(hipMemcpyAsync(out, pc.rec, sizeof(viso_motion_cov), hipMemcpyDeviceToHost, pc.s));
+    HIP_TRY(hipStreamSynchronize(pc.s));
     return VISO_OK;
 }

@@ -284,7 +284,6 @@ int PlainStage::flush(hipStream_t s) {
     return plain_blit(s, h, d, off / 4);
 }
 
-static size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 static size_t aux_bytes(size_t n) {   // skp 8n + sidx 4n + rank 4n | bstart + xinfo | qord | sums | rows8, 16-B aligned pieces
     return ((16 * n + 15) / 16) * 16 + ((4 * (VISO_NB + 1) + 32 + 15) / 16) * 16 + ((n + 63) / 64) * 64 + ((8 * n + 15) / 16) * 16 + VISO_ROW8 * n;
 }

@@ -9,8 +9,9 @@
 //   - every lane factors the damped 6 x 6 S itself (the same instructions on the same LDS words: no broadcast, no divergence,
 //     ~60 live registers, where motion_cov_kernel's serial lane-0 work held 256);
 //   - pass B recomputes the point blocks, forms dX and writes it into the other half, and sums the candidate's cost.
-// The summation tree (DPP rows of solver_dev.h, then the waves in a fixed order in LDS) depends on n only: the batch at any
-// chunking and the direct call give byte-identical records.  No scratch memory (-Rpass-analysis=kernel-resource-usage).
+// The summation tree (block_sum of solver_dev.h: DPP rows, then the waves in a fixed order in LDS) depends on n only: the batch at any
+// chunking and the direct call give byte-identical records.  No scratch memory (-Rpass-analysis=kernel-resource-usage).  The
+// rotation (RotLite), the LM schedule (LM_*) and the covariance write-out (write_cov6) are solver_dev.h's, shared with window.hip.
 #include "solver_dev.h"
 
 #include <math.h>
@@ -19,12 +20,6 @@
 #define RF_THREADS 256
 #define RF_WAVES (RF_THREADS / 64)
 #define RF_NS 27   // S upper triangle [0, 21) | s [21, 27)
-
-#define RF_LAMBDA0 1e-4
-#define RF_LAMBDA_MIN 1e-12
-#define RF_MAX_ACCEPT 20
-#define RF_MAX_REJECT 8
-#define RF_REL_TOL 1e-12
 
 struct RefineArgs {
     const SolverItem* items;
@@ -37,27 +32,6 @@ struct RefineArgs {
     size_t stride;     // elements per item of pts / 6 and of idx (>= every item's ld)
     viso_motion_refine* out;   // [n_items]
 };
-
-// The motion's rotation and translation, and the columns w_i of dR/dr_i = [w_i]x R (R = Rx Ry Rz, tr2mat's order):
-// w_0 = (1, 0, 0), w_1 = (0, cx, sx), w_2 = (sy, -sx cy, cx cy).  17 doubles where RotDev's derivative table holds 33: the
-// Jacobian columns are w_i x (R P), the same values to rounding.
-struct RotLite {
-    double r00, r01, r02, r10, r11, r12, r20, r21, r22, tx, ty, tz;
-    double sx, cx, sy, w21, w22;
-};
-__device__ __forceinline__ void rf_rot(const double (&tr)[6], RotLite& R) {
-    double sx, cx, sy, cy, sz, cz;
-    sincos(tr[0], &sx, &cx);
-    sincos(tr[1], &sy, &cy);
-    sincos(tr[2], &sz, &cz);
-    R.r00 = +cy * cz;                R.r01 = -cy * sz;                R.r02 = +sy;
-    R.r10 = +sx * sy * cz + cx * sz; R.r11 = -sx * sy * sz + cx * cz; R.r12 = -sx * cy;
-    R.r20 = -cx * sy * cz + sx * sz; R.r21 = +cx * sy * sz + sx * cz; R.r22 = +cx * cy;
-    R.tx = tr[3]; R.ty = tr[4]; R.tz = tr[5];
-    R.sx = sx; R.cx = cx; R.sy = sy; R.w21 = -sx * cy; R.w22 = cx * cy;
-}
-
-__device__ __forceinline__ int rf_up6(int p, int q) { return p * 6 - p * (p - 1) / 2 + (q - p); }   // p <= q
 
 // One point at the state (R, P) with damping lam.  The four current-frame rows enter as three, the shared v row scaled by sqrt 2
 // (J~, Jx~; r~_v = (r_vL + r_vR) / sqrt 2), so that J'J = J~'J~, Hcp = J~'Jx~ and J'r1 = J~'r~.  With l the Cholesky factor of
@@ -233,33 +207,13 @@ __device__ __forceinline__ void rf_obs(const SolverItem& S, const SolverParamsDe
     for (int r = 0; r < 4; ++r) z1[r] = S.obs[r * ld + k];
 }
 
-// Workgroup sum of NS per-lane values (DPP rows, then the waves in a fixed order); every thread returns with tot[] valid.
-template <int NS>
-__device__ __forceinline__ void rf_reduce(double (&acc)[NS], double* red, double* tot) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-    for (int k = 0; k < NS; ++k) {
-        const double v = wave_sum_to_lane63(acc[k]);
-        if (lane == 63) red[wave * NS + k] = v;
-        if ((k & 3) == 3) __builtin_amdgcn_sched_barrier(0);   // four chains in flight, not 35: registers
-    }
-    __syncthreads();
-    if (threadIdx.x < NS) {
-        double s = red[threadIdx.x];
-#pragma unroll
-        for (int w = 1; w < RF_WAVES; ++w) s += red[w * NS + threadIdx.x];
-        tot[threadIdx.x] = s;
-    }
-    __syncthreads();
-}
-
 // Cholesky of the symmetric 6 x 6 whose upper triangle is u[21] (plus lam x dg on the diagonal) into the packed lower factor
 // L[21] (row i at i (i + 1) / 2) and the reciprocals of its diagonal; false when a pivot is not > 1e-12 x its diagonal entry.
 __device__ __forceinline__ bool rf_chol6(const double* u, const double* dg, double lam, double (&L)[21], double (&id)[6]) {
     bool good = true;
 #pragma unroll
     for (int j = 0; j < 6; ++j) {
-        const double a = u[rf_up6(j, j)] + lam * dg[j];
+        const double a = u[up6(j, j)] + lam * dg[j];
         double s = a;
 #pragma unroll
         for (int k = 0; k < j; ++k) s -= L[j * (j + 1) / 2 + k] * L[j * (j + 1) / 2 + k];
@@ -268,7 +222,7 @@ __device__ __forceinline__ bool rf_chol6(const double* u, const double* dg, doub
         id[j] = 1.0 / L[j * (j + 1) / 2 + j];
 #pragma unroll
         for (int i = j + 1; i < 6; ++i) {
-            double t = u[rf_up6(j, i)];
+            double t = u[up6(j, i)];
 #pragma unroll
             for (int k = 0; k < j; ++k) t -= L[i * (i + 1) / 2 + k] * L[j * (j + 1) / 2 + k];
             L[i * (i + 1) / 2 + j] = t * id[j];
@@ -370,17 +324,17 @@ __global__ __launch_bounds__(RF_THREADS) void motion_refine_kernel(RefineArgs a)
 #pragma unroll
     for (int p = 0; p < 6; ++p) tr[p] = tr_in[p];
     int cur = 0, acc_steps = 0, rej = 0, status = 1;
-    double lam = RF_LAMBDA0, C = 0.0, C0 = 0.0;
+    double lam = LM_LAMBDA0, C = 0.0, C0 = 0.0;
     {   // the starting cost
         RotLite R;
-        rf_rot(tr, R);
+        rot_lite(tr, R);
         double accC[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
         for (int j = tid; j < n; j += RF_THREADS) {
             double z0[3], z1[4];
             rf_obs(S, sp, idx[j], z0, z1);
             rf_cost_diag(R, sp, z0, z1, P0[j], P0[a.stride + j], P0[2 * a.stride + j], accC);
         }
-        rf_reduce<7>(accC, red, tot);
+        block_sum<7, RF_WAVES>(accC, red, tot);
         C = C0 = tot[0];
         if (tid < 6) dg[tid] = tot[1 + tid];
     }
@@ -390,7 +344,7 @@ __global__ __launch_bounds__(RF_THREADS) void motion_refine_kernel(RefineArgs a)
         // pass A: the reduced system at the current state with damping lam
         {
             RotLite R;
-            rf_rot(tr, R);
+            rot_lite(tr, R);
             const double* Pc = P0 + (size_t)cur * 3 * a.stride;
             double acc[RF_NS];
 #pragma unroll
@@ -402,7 +356,7 @@ __global__ __launch_bounds__(RF_THREADS) void motion_refine_kernel(RefineArgs a)
                 rf_obs(S, sp, idx[j], z0, z1);
                 if (!rf_point<false>(R, sp, z0, z1, Pc[j], Pc[a.stride + j], Pc[2 * a.stride + j], lam, acc, zero6, dX)) bad = 1;
             }
-            rf_reduce<RF_NS>(acc, red, tot);
+            block_sum<RF_NS, RF_WAVES>(acc, red, tot);
         }
         if (bad) { status = -2; break; }
         bool fin = true;
@@ -428,8 +382,8 @@ __global__ __launch_bounds__(RF_THREADS) void motion_refine_kernel(RefineArgs a)
         for (int p = 0; p < 6; ++p) trn[p] = tr[p] + dtr[p];
         {
             RotLite R, Rn;
-            rf_rot(tr, R);
-            rf_rot(trn, Rn);
+            rot_lite(tr, R);
+            rot_lite(trn, Rn);
             const double* Pc = P0 + (size_t)cur * 3 * a.stride;
             double* Pn = P0 + (size_t)(1 - cur) * 3 * a.stride;
             double accC[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, dummy[RF_NS];
@@ -443,14 +397,14 @@ __global__ __launch_bounds__(RF_THREADS) void motion_refine_kernel(RefineArgs a)
                 Pn[j] = nx; Pn[a.stride + j] = ny; Pn[2 * a.stride + j] = nz;
                 rf_cost_diag(Rn, sp, z0, z1, nx, ny, nz, accC);
             }
-            rf_reduce<7>(accC, red, tot);
+            block_sum<7, RF_WAVES>(accC, red, tot);
         }
         const double Cn = tot[0];
         if (Cn < C) {
             ++acc_steps;
             rej = 0;
-            lam = fmax(lam / 10.0, RF_LAMBDA_MIN);
-            const bool stop = C - Cn <= RF_REL_TOL * C || Cn == 0.0 || acc_steps == RF_MAX_ACCEPT;
+            lam = fmax(lam / 10.0, LM_LAMBDA_MIN);
+            const bool stop = C - Cn <= LM_REL_TOL * C || Cn == 0.0 || acc_steps == LM_MAX_ACCEPT;
 #pragma unroll
             for (int p = 0; p < 6; ++p) tr[p] = trn[p];
             cur = 1 - cur;
@@ -460,7 +414,7 @@ __global__ __launch_bounds__(RF_THREADS) void motion_refine_kernel(RefineArgs a)
             if (stop) break;
         } else {
             lam *= 10.0;
-            if (++rej == RF_MAX_REJECT) break;
+            if (++rej == LM_MAX_REJECT) break;
         }
     }
     if (status == 1) {
@@ -468,7 +422,7 @@ __global__ __launch_bounds__(RF_THREADS) void motion_refine_kernel(RefineArgs a)
         __syncthreads();
         {
             RotLite R;
-            rf_rot(tr, R);
+            rot_lite(tr, R);
             const double* Pc = P0 + (size_t)cur * 3 * a.stride;
             double acc[RF_NS];
 #pragma unroll
@@ -480,7 +434,7 @@ __global__ __launch_bounds__(RF_THREADS) void motion_refine_kernel(RefineArgs a)
                 rf_obs(S, sp, idx[j], z0, z1);
                 if (!rf_point<false>(R, sp, z0, z1, Pc[j], Pc[a.stride + j], Pc[2 * a.stride + j], 0.0, acc, zero6, dX)) bad = 1;
             }
-            rf_reduce<RF_NS>(acc, red, tot);
+            block_sum<RF_NS, RF_WAVES>(acc, red, tot);
         }
         bool fin = true;
 #pragma unroll
@@ -517,16 +471,7 @@ __global__ __launch_bounds__(RF_THREADS) void motion_refine_kernel(RefineArgs a)
             for (int e = 0; e < 36; ++e) fin2 = fin2 && isfinite(Li[e]);
             if (!fin2) status = -3;
             if (status == 1) {
-                if (tid < 21) {
-                    int p = 0, q = tid;
-                    while (q >= 6 - p) { q -= 6 - p; ++p; }
-                    q += p;
-                    double v = 0.0;
-                    for (int k = q; k < 6; ++k) v += Li[k * 6 + p] * Li[k * 6 + q];   // L^-1 is lower: rows k >= max(p, q)
-                    v *= sigma2;
-                    o->cov[p * 6 + q] = v;
-                    o->cov[q * 6 + p] = v;
-                }
+                write_cov6(Li, sigma2, o->cov);
                 if (tid < 6) o->tr[tid] = tr[tid];
                 if (tid == 0) {
                     o->sigma2 = sigma2; o->cost0 = C0; o->cost = C; o->gap = gap;
@@ -546,10 +491,6 @@ __global__ __launch_bounds__(RF_THREADS) void motion_refine_kernel(RefineArgs a)
     rf_zero(o, tr_in, status, n);
 }
 
-bool motion_refine_args_ok(int mode, double sigma_px) {
-    return mode == 1 || (mode == 2 && isfinite(sigma_px) && sigma_px > 0.0);
-}
-
 int launch_motion_refine(hipStream_t s, const SolverItem* items_dev, int n_items, const SolverParamsDev& sp, int mode, double sigma,
                          double* pts, int* idx, size_t stride, viso_motion_refine* out) {
     if (n_items <= 0) return VISO_OK;
@@ -561,59 +502,26 @@ int launch_motion_refine(hipStream_t s, const SolverItem* items_dev, int n_items
     return VISO_OK;
 }
 
-// ---- the direct call: host pointers, default context ----------------------------------------------------------------------
-static size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
-
+// ---- the direct call: host pointers, default context (pose_call_stage, covariance.hip) --------------------------------------
 extern "C" int viso_pose_refine(const double* X, const double* obs, int m, const double tr[6], const int32_t* inl, int n_inl,
                                 const viso_param* param, int mode, double sigma_px, viso_motion_refine* out, double* Xout) {
-    bool ok = m >= 0 && n_inl >= 0 && n_inl <= m && tr && param && out && (m == 0 || (X && obs)) && (n_inl == 0 || inl) &&
-              motion_refine_args_ok(mode, sigma_px);
-    for (int j = 0; ok && j < n_inl; ++j) ok = inl[j] >= 0 && inl[j] < m;
-    if (!ok) {
-        viso_set_error("viso_pose_refine: bad argument (m >= 0, 0 <= n_inl <= m, indices in [0, m), mode 1 or mode 2 with a "
-                       "finite sigma_px > 0)");
-        return VISO_ERR_ARG;
-    }
     PlainLock lk;
-    viso_ctx* c = viso_default_ctx();
-    if (!c) return VISO_ERR_HIP;
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t ld = (size_t)(m > 0 ? m : 1);
-    // one block: X [3][ld] | obs [4][ld] | inl [ld] | tr [6] | ok, n_inl, m | the item | the record | points [2][3][ld] | L' [ld]
-    const size_t oX = 0, oO = al256(oX + sizeof(double) * 3 * ld), oI = al256(oO + sizeof(double) * 4 * ld),
-                 oT = al256(oI + sizeof(int) * ld), oW = al256(oT + sizeof(double) * 6), oS = al256(oW + sizeof(int) * 4),
-                 oR = al256(oS + sizeof(SolverItem)), oP = al256(oR + sizeof(viso_motion_refine)),
-                 oL = al256(oP + sizeof(double) * 6 * ld), bytes = al256(oL + sizeof(int) * ld);
-    char* d;
+    PoseCall pc;
     int r;
-    if ((r = ctx_scratch(c, 0, bytes, (void**)&d)) < 0) return r;
-    SolverItem it;
-    memset(&it, 0, sizeof(it));
-    it.X = reinterpret_cast<double*>(d + oX); it.obs = reinterpret_cast<double*>(d + oO); it.ld = (int)ld;
-    it.inl = reinterpret_cast<int*>(d + oI); it.tr = reinterpret_cast<double*>(d + oT);
-    int* words = reinterpret_cast<int*>(d + oW);
-    it.ok = words; it.n_inl = words + 1; it.m_ptr = words + 2;
-    const int hw[4] = {1, n_inl, m, 0};
-    hipStream_t s = c->stream;
-    if (m > 0) {
-        HIP_TRY(hipMemcpyAsync(d + oX, X, sizeof(double) * 3 * (size_t)m, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d + oO, obs, sizeof(double) * 4 * (size_t)m, hipMemcpyHostToDevice, s));
-    }
-    if (n_inl > 0) HIP_TRY(hipMemcpyAsync(d + oI, inl, sizeof(int) * (size_t)n_inl, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + oT, tr, sizeof(double) * 6, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(words, hw, sizeof(hw), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + oS, &it, sizeof(it), hipMemcpyHostToDevice, s));
-    SolverParamsDev sp;
-    fill_solver_params(&sp, param);
-    if ((r = launch_motion_refine(s, reinterpret_cast<const SolverItem*>(d + oS), 1, sp, mode, sigma_px,
-                                  reinterpret_cast<double*>(d + oP), reinterpret_cast<int*>(d + oL), ld,
-                                  reinterpret_cast<viso_motion_refine*>(d + oR))) < 0) return r;
-    HIP_TRY(hipMemcpyAsync(out, d + oR, sizeof(viso_motion_refine), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    // extra: points [2][3][ld] | L' [ld]
+    const size_t ld = (size_t)(m > 0 ? m : 1), oL = al256(sizeof(double) * 6 * ld);
+    if ((r = pose_call_stage("viso_pose_refine", X, obs, m, tr, inl, n_inl, param, mode, sigma_px, out, sizeof(viso_motion_refine),
+                             oL + sizeof(int) * ld, &pc)) < 0)
+        return r;
+    if ((r = launch_motion_refine(pc.s, pc.item, 1, pc.sp, mode, sigma_px, reinterpret_cast<double*>(pc.extra),
+                                  reinterpret_cast<int*>(pc.extra + oL), ld, reinterpret_cast<viso_motion_refine*>(pc.rec))) < 0)
+        return r;
+    HIP_TRY(hipMemcpyAsync(out, pc.rec, sizeof(viso_motion_refine), hipMemcpyDeviceToHost, pc.s));
+    HIP_TRY(hipStreamSynchronize(pc.s));
     if (Xout) {   // the refined points, L' order: rows of n_inl doubles, the first out->n columns set when status is 1
         if (out->status == 1 && out->n > 0)
             for (int row = 0; row < 3; ++row)
-                HIP_TRY(hipMemcpy(Xout + (size_t)row * (size_t)n_inl, d + oP + sizeof(double) * (size_t)row * ld,
+                HIP_TRY(hipMemcpy(Xout + (size_t)row * (size_t)n_inl, pc.extra + sizeof(double) * (size_t)row * ld,
                                   sizeof(double) * (size_t)out->n, hipMemcpyDeviceToHost));
     }
     return VISO_OK;

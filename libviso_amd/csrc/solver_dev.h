@@ -316,6 +316,76 @@ __device__ __forceinline__ double wave_sum_to_lane63(double v) {
     return v;
 }
 
+// ---- shared by the fp64 motion estimators: covariance.hip, refine.hip, window.hip ---------------------------------------
+// Workgroup sum of NS per-lane values (DPP rows, then the WAVES waves in a fixed order in LDS: red [WAVES][NS], tot [NS]); every
+// thread returns with tot[] valid.  The summation tree depends on the workgroup's size only.
+template <int NS, int WAVES>
+__device__ __forceinline__ void block_sum(double (&acc)[NS], double* red, double* tot) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+        const double v = wave_sum_to_lane63(acc[k]);
+        if (lane == 63) red[wave * NS + k] = v;
+        if ((k & 3) == 3) __builtin_amdgcn_sched_barrier(0);   // four chains in flight, not NS: registers
+    }
+    __syncthreads();
+    if (threadIdx.x < NS) {
+        double s = red[threadIdx.x];
+#pragma unroll
+        for (int w = 1; w < WAVES; ++w) s += red[w * NS + threadIdx.x];   // fixed order over the waves
+        tot[threadIdx.x] = s;
+    }
+    __syncthreads();
+}
+
+// Index of (p, q), p <= q, in the upper triangle of a 6 x 6 stored row by row (21 entries).
+__device__ __forceinline__ int up6(int p, int q) { return p * 6 - p * (p - 1) / 2 + (q - p); }
+
+// The motion's rotation and translation, and the columns w_i of dR/dr_i = [w_i]x R (R = Rx Ry Rz, tr2mat's order):
+// w_0 = (1, 0, 0), w_1 = (0, cx, sx), w_2 = (sy, -sx cy, cx cy).  17 doubles where RotDev's derivative table holds 33: the
+// Jacobian columns are w_i x (R P), the same values to rounding.
+struct RotLite {
+    double r00, r01, r02, r10, r11, r12, r20, r21, r22, tx, ty, tz;
+    double sx, cx, sy, w21, w22;
+};
+__device__ __forceinline__ void rot_lite(const double* tr, RotLite& R) {
+    double sx, cx, sy, cy, sz, cz;
+    sincos(tr[0], &sx, &cx);
+    sincos(tr[1], &sy, &cy);
+    sincos(tr[2], &sz, &cz);
+    R.r00 = +cy * cz;                R.r01 = -cy * sz;                R.r02 = +sy;
+    R.r10 = +sx * sy * cz + cx * sz; R.r11 = -sx * sy * sz + cx * cz; R.r12 = -sx * cy;
+    R.r20 = -cx * sy * cz + sx * sz; R.r21 = +cx * sy * sz + sx * cz; R.r22 = +cx * cy;
+    R.tx = tr[3]; R.ty = tr[4]; R.tz = tr[5];
+    R.sx = sx; R.cx = cx; R.sy = sy; R.w21 = -sx * cy; R.w22 = cx * cy;
+}
+
+// The Levenberg-Marquardt schedule of the bundle adjustments (refine.hip, window.hip): lambda starts at LM_LAMBDA0; an accepted
+// step (a lower cost) divides it by 10, not below LM_LAMBDA_MIN, and ends the loop when it gained no more than LM_REL_TOL of the
+// cost, reached a zero cost or was the LM_MAX_ACCEPT-th; a rejected step multiplies it by 10, and the LM_MAX_REJECT-th rejection in
+// a row ends the loop.  The update stays written out in each loop: as a shared function it moved the kernels' instructions.
+#define LM_LAMBDA0 1e-4
+#define LM_LAMBDA_MIN 1e-12
+#define LM_MAX_ACCEPT 20
+#define LM_MAX_REJECT 8
+#define LM_REL_TOL 1e-12
+
+// cov = sigma2 L^-T L^-1 (6 x 6, row-major) from the columns of the lower-triangular L^-1 (Li[i * 6 + c]): threads 0..20 one
+// entry of the upper triangle each, written to both halves.
+__device__ __forceinline__ void write_cov6(const double* Li, double sigma2, double* cov) {
+    const int tid = threadIdx.x;
+    if (tid < 21) {
+        int p = 0, q = tid;
+        while (q >= 6 - p) { q -= 6 - p; ++p; }
+        q += p;
+        double v = 0.0;
+        for (int k = q; k < 6; ++k) v += Li[k * 6 + p] * Li[k * 6 + q];   // L^-1 is lower: rows k >= max(p, q)
+        v *= sigma2;
+        cov[p * 6 + q] = v;
+        cov[q * 6 + p] = v;
+    }
+}
+
 // ---- the sample triples: randomsample(3, N, .), src/viso.cpp:87-107 ----------------------------------------------------
 // The reference returns a uniformly distributed 3-subset of 0..N-1, ascending, from a per-call random_device (Q9): which
 // generator drives it is this build's definition.  Since round 6: the first three outputs of a splitmix64 stream keyed

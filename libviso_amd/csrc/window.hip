@@ -9,7 +9,9 @@
 //     and the track's share of s), then the threads sum 3 x 3 tiles of S (with diag Hcc) and of s over the chunk in track order,
 //     each tile in a fixed number of interleaved partials (wn_pass_a); the damped S is factored in LDS column by column.
 // The order of every sum depends on the window's inputs only: the batch at any chunking and the direct call give byte-identical
-// records.  fp64 throughout; no scratch memory (-Rpass-analysis=kernel-resource-usage, tests/test_window_cpu.py).
+// records.  fp64 throughout; no scratch memory (-Rpass-analysis=kernel-resource-usage, tests/test_window_cpu.py).  The motions'
+// rotations (RotLite: w_0 = (1, 0, 0), w_1 = (0, cx, sx), w_2 = (sy, w21, w22)), the LM schedule (LM_*) and the covariance write-out
+// (write_cov6) are solver_dev.h's, shared with refine.hip.
 #include "solver_dev.h"
 
 #include <math.h>
@@ -25,12 +27,6 @@
 #define WN_EMAX (WN_NCMAX * (WN_NCMAX + 1) / 2 + 2 * WN_NCMAX)   // S upper | s | diag Hcc
 #define WN_SS 24                 // row stride of the LDS camera matrix
 
-#define WN_LAMBDA0 1e-4
-#define WN_LAMBDA_MIN 1e-12
-#define WN_MAX_ACCEPT 20
-#define WN_MAX_REJECT 8
-#define WN_REL_TOL 1e-12
-
 struct WinArgs {
     WinData d;
     WinWork w;
@@ -39,24 +35,6 @@ struct WinArgs {
     double sigma2;
     viso_window_record* out;   // [n_items]
 };
-
-// One motion: R, t and the columns w_i of dR/dr_i = [w_i]x R (refine.hip's RotLite): w_0 = (1, 0, 0), w_1 = (0, cx, sx),
-// w_2 = (sy, w21, w22).
-struct WnRot {
-    double r00, r01, r02, r10, r11, r12, r20, r21, r22, tx, ty, tz;
-    double sx, cx, sy, w21, w22;
-};
-__device__ __forceinline__ void wn_rot(const double* tr, WnRot& R) {
-    double sx, cx, sy, cy, sz, cz;
-    sincos(tr[0], &sx, &cx);
-    sincos(tr[1], &sy, &cy);
-    sincos(tr[2], &sz, &cz);
-    R.r00 = +cy * cz;                R.r01 = -cy * sz;                R.r02 = +sy;
-    R.r10 = +sx * sy * cz + cx * sz; R.r11 = -sx * sy * sz + cx * cz; R.r12 = -sx * cy;
-    R.r20 = -cx * sy * cz + sx * sz; R.r21 = +cx * sy * sz + sx * cz; R.r22 = +cx * cy;
-    R.tx = tr[3]; R.ty = tr[4]; R.tz = tr[5];
-    R.sx = sx; R.cx = cx; R.sy = sy; R.w21 = -sx * cy; R.w22 = cx * cy;
-}
 
 __device__ __forceinline__ int wn_slot_size(int len) { return (3 * (len - 1) + 4) * (6 * (len - 1)) + 30; }
 __device__ __forceinline__ int wn_chunk(int len) { const int c = WN_SLOTS / wn_slot_size(len); return c < WN_CHMAX ? c : WN_CHMAX; }
@@ -147,7 +125,7 @@ __device__ __forceinline__ void wn_z0(const WinData& d, const SolverParamsDev& s
 
 // The track's share of the cost with the motions rl[0 .. len-2] (frame offset i + 1) and the point (px, py, pz).
 // trk: the item's track table [5][T] (s | e << 4, then the rows r_{s+1} .. r_e).
-__device__ __forceinline__ double wn_cost(const WinArgs& a, const int* trk, size_t T, const WnRot* rl, int anc, int k, double px, double py, double pz) {
+__device__ __forceinline__ double wn_cost(const WinArgs& a, const int* trk, size_t T, const RotLite* rl, int anc, int k, double px, double py, double pz) {
     const SolverParamsDev& sp = a.sp;
     const int se = trk[k];
     const int so = se & 15, eo = se >> 4;
@@ -155,7 +133,7 @@ __device__ __forceinline__ double wn_cost(const WinArgs& a, const int* trk, size
     double Y0 = px, Y1 = py, Y2 = pz, c = 0.0;
     for (int j = 0; j <= eo; ++j) {
         if (j > 0) {
-            const WnRot& R = rl[j - 1];
+            const RotLite& R = rl[j - 1];
             const double q0 = R.r00 * Y0 + R.r01 * Y1 + R.r02 * Y2, q1 = R.r10 * Y0 + R.r11 * Y1 + R.r12 * Y2;
             const double q2 = R.r20 * Y0 + R.r21 * Y1 + R.r22 * Y2;
             Y0 = q0 + R.tx; Y1 = q1 + R.ty; Y2 = q2 + R.tz;
@@ -182,7 +160,7 @@ __device__ __forceinline__ double wn_cost(const WinArgs& a, const int* trk, size
 // three (merged) residuals.  Jx = Pj A[j][0] enters Hpp, gp (and hx when the rows depend on the cameras); the camera rows
 // Pj A[j][i] D_i (i <= j; D_i = [w_k x q_i | I]) go to U's rows `row`.., and Hcp' and the track's share of s are accumulated in Wt, g.
 __device__ __forceinline__ void wn_group(const double (&Pj)[3][3], const double (&r)[3], int j, bool camdep, int nc, const double* Am,
-                                         const WnRot* rl, const double* Qv, double* U, double* Wt, double* g, int& row,
+                                         const RotLite* rl, const double* Qv, double* U, double* Wt, double* g, int& row,
                                          double (&h)[6], double (&gp)[3], double (&hx)[6]) {
     const double* A0 = Am + 9 * wn_tri(j);
     double Jx[3][3];
@@ -213,7 +191,7 @@ __device__ __forceinline__ void wn_group(const double (&Pj)[3][3], const double 
             for (int a = 0; a < 3; ++a)
 #pragma unroll
                 for (int c = 0; c < 3; ++c) M3[a][c] = Pj[a][0] * Ai[c] + Pj[a][1] * Ai[3 + c] + Pj[a][2] * Ai[6 + c];
-            const WnRot& R = rl[i - 1];
+            const RotLite& R = rl[i - 1];
             const double q0 = Qv[3 * i], q1 = Qv[3 * i + 1], q2 = Qv[3 * i + 2];
             // w_k x q: w_0 = (1, 0, 0), w_1 = (0, cx, sx), w_2 = (sy, w21, w22)
             const double d0[3] = {0.0, -q2, q1};
@@ -250,7 +228,7 @@ __device__ __forceinline__ void wn_group(const double (&Pj)[3][3], const double 
 // of s) and *nU; STEP: also dX = l^-T (y - W~ dtr).  Returns false when a pivot of Hpp_d or (s = a) of I - M'M fails the test.
 template <bool STEP>
 __device__ __forceinline__ bool wn_point(const WinArgs& a, const int* trk, size_t T, int anc, int nc, int k, double px, double py, double pz,
-                         const WnRot* rl, const double* Am, double lam, double* slot, int* nU, const double* dtr, double (&dX)[3]) {
+                         const RotLite* rl, const double* Am, double lam, double* slot, int* nU, const double* dtr, double (&dX)[3]) {
     const SolverParamsDev& sp = a.sp;
     const double f = sp.f, b = sp.base, RT2 = 1.4142135623730951;
     const int ld = a.d.ld;
@@ -265,7 +243,7 @@ __device__ __forceinline__ bool wn_point(const WinArgs& a, const int* trk, size_
     for (int c = 0; c < 4 * nc; ++c) Wt[c] = 0.0;   // Wt and g
     Yv[0] = px; Yv[1] = py; Yv[2] = pz;
     for (int j = 1; j <= eo; ++j) {
-        const WnRot& R = rl[j - 1];
+        const RotLite& R = rl[j - 1];
         const double y0 = Yv[3 * j - 3], y1 = Yv[3 * j - 2], y2 = Yv[3 * j - 1];
         const double q0 = R.r00 * y0 + R.r01 * y1 + R.r02 * y2, q1 = R.r10 * y0 + R.r11 * y1 + R.r12 * y2;
         const double q2 = R.r20 * y0 + R.r21 * y1 + R.r22 * y2;
@@ -364,10 +342,10 @@ __device__ __forceinline__ double wn_reduce(double v, double* red) {
 }
 
 // Motions and chain products of a state: rl[i] for the cameras 1..len-1 (thread i - 1) and A[j][i] = R_j ... R_{i+1} (thread 0).
-__device__ __forceinline__ void wn_state(const double* trv, int len, WnRot* rl, double* Am) {
+__device__ __forceinline__ void wn_state(const double* trv, int len, RotLite* rl, double* Am) {
     const int tid = threadIdx.x;
     __syncthreads();
-    if (tid < len - 1) wn_rot(trv + 6 * tid, rl[tid]);
+    if (tid < len - 1) rot_lite(trv + 6 * tid, rl[tid]);
     __syncthreads();
     if (Am && tid == 0) {
         for (int j = 0; j < len; ++j) {
@@ -376,7 +354,7 @@ __device__ __forceinline__ void wn_state(const double* trv, int len, WnRot* rl, 
             for (int e = 0; e < 9; ++e) Ajj[e] = (e % 4 == 0) ? 1.0 : 0.0;
             for (int i = j - 1; i >= 0; --i) {   // A[j][i] = A[j][i+1] R_{i+1}
                 const double* P = Am + 9 * (wn_tri(j) + i + 1);
-                const WnRot& R = rl[i];
+                const RotLite& R = rl[i];
                 const double Rm[9] = {R.r00, R.r01, R.r02, R.r10, R.r11, R.r12, R.r20, R.r21, R.r22};
                 double* O = Am + 9 * (wn_tri(j) + i);
 #pragma unroll
@@ -402,7 +380,7 @@ __device__ __forceinline__ void wn_zero(viso_window_record* o, const double* tr_
 // U-only diagonal on the diagonal blocks) or a 3-vector of s; each tile's sum over the chunk's tracks is split into PP interleaved
 // partials (track kk of the chunk to partial kk % PP), one thread each, and the partials are added in order at the end.  Nine or
 // three independent accumulators per thread and one load of six U words per row: the chains are short and overlap.
-__device__ __forceinline__ bool wn_pass_a(const WinArgs& a, const int* trk, size_t T, const double* P, int anc, int len, int np, const WnRot* rl,
+__device__ __forceinline__ bool wn_pass_a(const WinArgs& a, const int* trk, size_t T, const double* P, int anc, int len, int np, const RotLite* rl,
                           const double* Am, double lam, double* slots, int* nUr, double* ent, int* bad) {
     const int tid = threadIdx.x;
     const int nc = 6 * (len - 1), nS = nc * (nc + 1) / 2, nb = nc / 3;
@@ -552,7 +530,7 @@ __global__ __launch_bounds__(WN_THREADS) void window_refine_kernel(WinArgs a) {
     __shared__ double Sm[WN_NCMAX * WN_SS];
     __shared__ double dgd[WN_NCMAX], Lid[WN_NCMAX], dtr[WN_NCMAX], trc[WN_NCMAX], trn[WN_NCMAX], trin[WN_NCMAX], tv[WN_NCMAX];
     __shared__ double Am[9 * 15];
-    __shared__ WnRot rl[2][WN_KMAX - 1];
+    __shared__ RotLite rl[2][WN_KMAX - 1];
     __shared__ double red[WN_WAVES];
     __shared__ double Li[36];
     __shared__ int wcnt[WN_WAVES];
@@ -626,7 +604,7 @@ __global__ __launch_bounds__(WN_THREADS) void window_refine_kernel(WinArgs a) {
         const double* X = d.X + (size_t)(anc + so + 1) * 3 * d.ld;
         double y0 = X[r], y1 = X[d.ld + r], y2 = X[2 * d.ld + r];
         for (int i = so; i >= 1; --i) {
-            const WnRot& R = rl[0][i - 1];
+            const RotLite& R = rl[0][i - 1];
             const double e0 = y0 - R.tx, e1 = y1 - R.ty, e2 = y2 - R.tz;
             y0 = R.r00 * e0 + R.r10 * e1 + R.r20 * e2;
             y1 = R.r01 * e0 + R.r11 * e1 + R.r21 * e2;
@@ -637,7 +615,7 @@ __global__ __launch_bounds__(WN_THREADS) void window_refine_kernel(WinArgs a) {
     __threadfence_block();
     __syncthreads();
     int cur = 0, acc_steps = 0, rej = 0, status = 1;
-    double lam = WN_LAMBDA0, C, C0;
+    double lam = LM_LAMBDA0, C, C0;
     {
         double c = 0.0;
         for (int k = tid; k < np; k += WN_THREADS) c += wn_cost(a, trk, T, rl[0], anc, k, P0[k], P0[T + k], P0[2 * T + k]);
@@ -689,8 +667,8 @@ __global__ __launch_bounds__(WN_THREADS) void window_refine_kernel(WinArgs a) {
         if (Cn < C) {
             ++acc_steps;
             rej = 0;
-            lam = fmax(lam / 10.0, WN_LAMBDA_MIN);
-            const bool stop = C - Cn <= WN_REL_TOL * C || Cn == 0.0 || acc_steps == WN_MAX_ACCEPT;
+            lam = fmax(lam / 10.0, LM_LAMBDA_MIN);
+            const bool stop = C - Cn <= LM_REL_TOL * C || Cn == 0.0 || acc_steps == LM_MAX_ACCEPT;
             __syncthreads();
             if (tid < nc) trc[tid] = trn[tid];
             cur = 1 - cur;
@@ -699,7 +677,7 @@ __global__ __launch_bounds__(WN_THREADS) void window_refine_kernel(WinArgs a) {
             if (stop) break;
         } else {
             lam *= 10.0;
-            if (++rej == WN_MAX_REJECT) break;
+            if (++rej == LM_MAX_REJECT) break;
         }
     }
     if (status == 1) {   // the final state without damping
@@ -740,16 +718,7 @@ __global__ __launch_bounds__(WN_THREADS) void window_refine_kernel(WinArgs a) {
             for (int e = 0; e < 36; ++e) fin = fin && isfinite(Li[e]);
             if (!fin) status = -3;
             if (status == 1) {
-                if (tid < 21) {
-                    int p = 0, q = tid;
-                    while (q >= 6 - p) { q -= 6 - p; ++p; }
-                    q += p;
-                    double v = 0.0;
-                    for (int k = q; k < 6; ++k) v += Li[k * 6 + p] * Li[k * 6 + q];
-                    v *= sigma2;
-                    o->cov[p * 6 + q] = v;
-                    o->cov[q * 6 + p] = v;
-                }
+                write_cov6(Li, sigma2, o->cov);
                 if (tid < 6) o->tr[tid] = trc[o6 + tid];
                 if (tid < 24) o->tr_win[tid / 6][tid % 6] = tid < nc ? trc[tid] : 0.0;
                 if (tid == 0) {
@@ -765,7 +734,7 @@ __global__ __launch_bounds__(WN_THREADS) void window_refine_kernel(WinArgs a) {
 }
 
 bool window_refine_args_ok(int K, int mode, double sigma_px) {
-    return K >= 2 && K <= WN_KMAX && motion_refine_args_ok(mode, sigma_px);
+    return K >= 2 && K <= WN_KMAX && motion_args_ok(mode, sigma_px);
 }
 
 int launch_window_links(hipStream_t s, const WinData& d, const WinWork& w, int j0, int n) {
@@ -787,12 +756,11 @@ int launch_window_refine(hipStream_t s, const WinData& d, const WinWork& w, cons
 }
 
 // ---- the direct call: host pointers, default context ----------------------------------------------------------------------
-static size_t wal256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 extern "C" int viso_window_refine(int len, const int* m, const double* X, const double* obs, const int32_t* left, const double* tr,
                                   const int32_t* inl, const int* n_inl, const viso_param* param, int mode, double sigma_px,
                                   viso_window_record* out) {
-    bool ok = len >= 2 && len <= WN_KMAX && m && tr && n_inl && param && out && motion_refine_args_ok(mode, sigma_px);
+    bool ok = len >= 2 && len <= WN_KMAX && m && tr && n_inl && param && out && motion_args_ok(mode, sigma_px);
     size_t rows = 0, ninl = 0;
     int ld = 1, tab = 1;
     for (int j = 0; ok && j < len - 1; ++j) {
@@ -825,11 +793,11 @@ extern "C" int viso_window_refine(int len, const int* m, const double* X, const 
     const size_t nf = (size_t)len, L = (size_t)ld, maxT = (size_t)(len - 1) * L;
     // one block: X [nf][3][ld] | obs [nf][4][ld] | left [nf][ld][2] | inl [nf][ld] | tr [nf][6] | ok, n_inl, m [nf] each | L' [nf][ld]
     // | nL' [nf] | tables [nf][2][tab] | tracks [5][maxT] | points [2][3][maxT] | the record
-    const size_t oX = 0, oO = wal256(oX + sizeof(double) * 3 * nf * L), oLe = wal256(oO + sizeof(double) * 4 * nf * L),
-                 oI = wal256(oLe + sizeof(int) * 2 * nf * L), oT = wal256(oI + sizeof(int) * nf * L), oW = wal256(oT + sizeof(double) * 6 * nf),
-                 oLp = wal256(oW + sizeof(int) * 3 * nf), oN = wal256(oLp + sizeof(int) * nf * L), oTb = wal256(oN + sizeof(int) * nf),
-                 oK = wal256(oTb + sizeof(int) * 2 * nf * (size_t)tab), oP = wal256(oK + sizeof(int) * 5 * maxT),
-                 oR = wal256(oP + sizeof(double) * 6 * maxT), bytes = wal256(oR + sizeof(viso_window_record));
+    const size_t oX = 0, oO = al256(oX + sizeof(double) * 3 * nf * L), oLe = al256(oO + sizeof(double) * 4 * nf * L),
+                 oI = al256(oLe + sizeof(int) * 2 * nf * L), oT = al256(oI + sizeof(int) * nf * L), oW = al256(oT + sizeof(double) * 6 * nf),
+                 oLp = al256(oW + sizeof(int) * 3 * nf), oN = al256(oLp + sizeof(int) * nf * L), oTb = al256(oN + sizeof(int) * nf),
+                 oK = al256(oTb + sizeof(int) * 2 * nf * (size_t)tab), oP = al256(oK + sizeof(int) * 5 * maxT),
+                 oR = al256(oP + sizeof(double) * 6 * maxT), bytes = al256(oR + sizeof(viso_window_record));
     char* dv;
     int r;
     if ((r = ctx_scratch(c, 0, bytes, (void**)&dv)) < 0) return r;

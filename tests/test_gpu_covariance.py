@@ -9,6 +9,7 @@ from libviso_amd import synth
 from libviso_amd.abi import MatchParams, Param
 
 import covariance_ref as CR
+from estimator_util import seq_batch
 
 pytestmark = pytest.mark.gpu
 
@@ -73,19 +74,6 @@ def test_direct_call_degenerate_cases(viso):
             _check(got, want, (i, mode))
 
 
-def _seq_run(ctx, seq, mode, sigma=None, seed=3, first=0, frames=None, run=True):
-    sl = slice(None) if frames is None else frames
-    kp, desc, n = (np.ascontiguousarray(seq[k][sl]) for k in ("kp", "desc", "n"))
-    nf, cap = kp.shape[0], kp.shape[2]
-    b = libviso_amd.Batch(ctx, nf, cap)
-    b.upload(kp, desc, n)
-    b.set_params(MatchParams.stereo(seq["F"]), MatchParams.temporal(), seq["param"], seed=seed, first_frame=first)
-    b.set_covariance(mode, sigma)
-    if run:
-        b.run()
-    return b
-
-
 def _check_batch_frames(b, param, mode, sigma=None):
     recs = b.covariances()
     n_valid = 0
@@ -111,7 +99,7 @@ def seq33():
 def test_batch_path_against_restatement_and_direct_call(viso, seq33):
     ctx = libviso_amd.Context(0)
     for mode, sigma in ((1, None), (2, 0.4)):
-        b = _seq_run(ctx, seq33, mode, sigma)
+        b = seq_batch(ctx, seq33, cov=(mode, sigma))
         assert _check_batch_frames(b, seq33["param"], mode, sigma) >= 30
         b.close()
     ctx.close()
@@ -141,8 +129,8 @@ def test_image_in_batch_path(viso, subpixel):
 
 def test_mode0_and_mode1_runs_are_otherwise_identical(viso, seq33):
     ctx = libviso_amd.Context(0)
-    b0 = _seq_run(ctx, seq33, 0)
-    b1 = _seq_run(ctx, seq33, 1)
+    b0 = seq_batch(ctx, seq33, cov=(0,))
+    b1 = seq_batch(ctx, seq33, cov=(1,))
     for a, c in zip(b0.poses(), b1.poses()):
         assert a.tobytes() == c.tobytes()
     for t in range(b0.nf):
@@ -172,9 +160,9 @@ def test_mode0_and_mode1_runs_are_otherwise_identical(viso, seq33):
 def test_chunked_batches_give_byte_equal_records(viso):
     seq = synth.make_sequence(7, 64, n_kp=1200)
     ctx = libviso_amd.Context(0)
-    whole = _seq_run(ctx, seq, 1).covariances()
-    a = _seq_run(ctx, seq, 1, frames=slice(0, 32)).covariances()
-    c = _seq_run(ctx, seq, 1, first=31, frames=slice(31, 64)).covariances()   # frame 31 is the second chunk's halo
+    whole = seq_batch(ctx, seq, cov=(1,)).covariances()
+    a = seq_batch(ctx, seq, cov=(1,), frames=slice(0, 32)).covariances()
+    c = seq_batch(ctx, seq, cov=(1,), first=31, frames=slice(31, 64)).covariances()   # frame 31 is the second chunk's halo
     assert a[1:].tobytes() == whole[1:32].tobytes()
     assert c[0]["status"] == 0
     assert c[1:].tobytes() == whole[32:].tobytes()
@@ -188,7 +176,7 @@ def test_consistency_on_a_noisy_sequence(viso):
     ctx = libviso_amd.Context(0)
     out = {}
     for mode, s in ((2, sigma), (1, None)):
-        b = _seq_run(ctx, seq, mode, s)
+        b = seq_batch(ctx, seq, cov=(mode, s))
         recs = b.covariances()
         tr, ok, _n = b.poses()
         good = np.nonzero(recs["status"] == 1)[0]

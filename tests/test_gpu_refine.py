@@ -10,17 +10,11 @@ from libviso_amd.abi import MatchParams
 
 import covariance_ref as CR
 import refine_ref as RR
+from estimator_util import ambiguous, seq_batch
 
 pytestmark = pytest.mark.gpu
 
 ZERO_FIELDS = ("cov", "sigma2", "cost0", "cost", "gap", "iters")
-
-
-def _ambiguous(want):
-    """True when one of the restatement's decisions compared costs that differ by less than 1e-11 relative -- the accept test
-    (C_new < C) and the stop test (C - C_new <= 1e-12 C) near their thresholds: there the device, whose sums run in another order,
-    may take the other branch (one accepted step more or less, of a size at rounding level)."""
-    return any(abs(d) < 1e-11 for d in want["trace"])
 
 
 def _check(got, want, what):
@@ -32,7 +26,7 @@ def _check(got, want, what):
         for k in ZERO_FIELDS:
             assert not np.any(got[k]), (what, k)
         return
-    if _ambiguous(want):
+    if ambiguous(want):
         assert abs(int(got["iters"]) - want["iters"]) <= 1, (what, int(got["iters"]), want["iters"])
     else:
         assert int(got["iters"]) == want["iters"], (what, int(got["iters"]), want["iters"])
@@ -41,8 +35,8 @@ def _check(got, want, what):
     # orders free to end up to ~1e-4 apart when they took different branches, far less when they did not
     white = float(np.sqrt(d @ np.linalg.solve(want["cov"] / max(want["sigma2"], 1e-300), d) / max(want["sigma2"], 1e-300)))
     if want["n"] >= 40:
-        assert white <= (1e-4 if _ambiguous(want) else 1e-5), (what, white, d)
-    if not _ambiguous(want):
+        assert white <= (1e-4 if ambiguous(want) else 1e-5), (what, white, d)
+    if not ambiguous(want):
         assert np.abs(d).max() <= (1e-8 if want["n"] >= 40 else 1e-7), (what, np.abs(d).max())
     else:
         assert np.abs(d).max() <= 1e-6, (what, np.abs(d).max())   # one rounding-size step apart, any n
@@ -68,9 +62,9 @@ def test_direct_call_against_the_restatement(viso):
             want = RR.refine(X, obs, tr, inl, param, mode, sigma)
             assert want["status"] == 1, m
             _check(got, want, (m, mode))
-            n_amb += _ambiguous(want)
+            n_amb += ambiguous(want)
             assert pts.shape == (3, want["n"])
-            if not _ambiguous(want):
+            if not ambiguous(want):
                 assert np.abs(pts - want["points"]).max() <= 1e-7 * max(1.0, np.abs(want["points"]).max()), m
             again, pts2 = libviso_amd.pose_refine(X, obs, tr, inl, param, mode=mode, sigma=sigma)
             assert got.tobytes() == again.tobytes() and pts.tobytes() == pts2.tobytes()
@@ -102,20 +96,7 @@ def test_direct_call_degenerate_inputs(viso):
             assert want["status"] == status, (i, want["status"])
             _check(got, want, (i, mode))
             if status == 1:
-                assert np.abs(pts - want["points"]).max() <= 1e-6 * np.abs(want["points"]).max() or _ambiguous(want)
-
-
-def _seq_run(ctx, seq, mode, sigma=None, seed=3, first=0, frames=None, cov=0):
-    sl = slice(None) if frames is None else frames
-    kp, desc, n = (np.ascontiguousarray(seq[k][sl]) for k in ("kp", "desc", "n"))
-    nf, cap = kp.shape[0], kp.shape[2]
-    b = libviso_amd.Batch(ctx, nf, cap)
-    b.upload(kp, desc, n)
-    b.set_params(MatchParams.stereo(seq["F"]), MatchParams.temporal(), seq["param"], seed=seed, first_frame=first)
-    b.set_covariance(cov)
-    b.set_refine(mode, sigma)
-    b.run()
-    return b
+                assert np.abs(pts - want["points"]).max() <= 1e-6 * np.abs(want["points"]).max() or ambiguous(want)
 
 
 def _check_batch_frames(b, param, mode, sigma=None):
@@ -149,7 +130,7 @@ def seq33():
 def test_batch_path_against_restatement_and_direct_call(viso, seq33):
     ctx = libviso_amd.Context(0)
     for mode, sigma in ((1, None), (2, 0.4)):
-        b = _seq_run(ctx, seq33, mode, sigma)
+        b = seq_batch(ctx, seq33, refine=(mode, sigma))
         assert _check_batch_frames(b, seq33["param"], mode, sigma) >= 30
         b.close()
     ctx.close()
@@ -181,8 +162,8 @@ def test_image_in_batch_path(viso, subpixel):
 
 def test_refine_on_and_off_leave_everything_else_identical(viso, seq33):
     ctx = libviso_amd.Context(0)
-    b0 = _seq_run(ctx, seq33, 0, cov=1)
-    b1 = _seq_run(ctx, seq33, 1, cov=1)
+    b0 = seq_batch(ctx, seq33, cov=(1,), refine=(0,))
+    b1 = seq_batch(ctx, seq33, cov=(1,), refine=(1,))
     for a, c in zip(b0.poses(), b1.poses()):
         assert a.tobytes() == c.tobytes()
     for t in range(b0.nf):
@@ -208,10 +189,10 @@ def test_refine_on_and_off_leave_everything_else_identical(viso, seq33):
 def test_chunked_batches_give_byte_equal_records(viso):
     seq = synth.make_sequence(7, 64, n_kp=1200)
     ctx = libviso_amd.Context(0)
-    bw = _seq_run(ctx, seq, 1)
+    bw = seq_batch(ctx, seq, refine=(1,))
     whole = bw.refines()
-    ba = _seq_run(ctx, seq, 1, frames=slice(0, 32))
-    bc = _seq_run(ctx, seq, 1, first=31, frames=slice(31, 64))   # frame 31 is the second chunk's halo
+    ba = seq_batch(ctx, seq, refine=(1,), frames=slice(0, 32))
+    bc = seq_batch(ctx, seq, refine=(1,), first=31, frames=slice(31, 64))   # frame 31 is the second chunk's halo
     a, c = ba.refines(), bc.refines()
     assert a[1:].tobytes() == whole[1:32].tobytes()
     assert c[0]["status"] == 0
@@ -229,7 +210,7 @@ def test_accuracy_and_consistency_on_a_noisy_sequence(viso):
     seq = synth.make_noisy_sequence(17, 257, sigma)
     gt = seq["tr_gt"]
     ctx = libviso_amd.Context(0)
-    b = _seq_run(ctx, seq, 2, sigma)
+    b = seq_batch(ctx, seq, refine=(2, sigma))
     recs = b.refines()
     tr, ok, _n = b.poses()
     good = np.nonzero(recs["status"] == 1)[0]

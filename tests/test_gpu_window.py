@@ -11,15 +11,11 @@ from libviso_amd.abi import MatchParams
 
 import covariance_ref as CR
 import window_ref as WR
+from estimator_util import ambiguous, seq_batch
 
 pytestmark = pytest.mark.gpu
 
 ZERO_FIELDS = ("cov", "sigma2", "cost0", "cost", "gap", "iters")
-
-
-def _ambiguous(want):
-    """A decision of the restatement at rounding level (see test_gpu_refine._ambiguous)."""
-    return any(abs(d) < 1e-11 for d in want["trace"])
 
 
 def _check(got, want, what):
@@ -33,7 +29,7 @@ def _check(got, want, what):
         for k in ZERO_FIELDS:
             assert not np.any(got[k]), (what, k)
         return
-    amb = _ambiguous(want)
+    amb = ambiguous(want)
     assert abs(int(got["iters"]) - want["iters"]) <= (1 if amb else 0), (what, int(got["iters"]), want["iters"])
     d = np.asarray(got["tr"]) - want["tr"]
     white = float(np.sqrt(d @ np.linalg.solve(want["cov"], d)))
@@ -49,20 +45,6 @@ def _check(got, want, what):
     assert float(got["gap"]) <= 1e-6 and want["gap"] <= 1e-6, (what, float(got["gap"]), want["gap"])
 
 
-def _seq_run(ctx, seq, K, mode=1, sigma=None, seed=3, first=0, frames=None, cov=0, refine=0):
-    sl = slice(None) if frames is None else frames
-    kp, desc, n = (np.ascontiguousarray(seq[k][sl]) for k in ("kp", "desc", "n"))
-    nf, cap = kp.shape[0], kp.shape[2]
-    b = libviso_amd.Batch(ctx, nf, cap)
-    b.upload(kp, desc, n)
-    b.set_params(MatchParams.stereo(seq["F"]), MatchParams.temporal(), seq["param"], seed=seed, first_frame=first)
-    b.set_covariance(cov)
-    b.set_refine(refine)
-    b.set_window_refine(K, mode, sigma)
-    b.run()
-    return b
-
-
 @pytest.fixture(scope="module")
 def noisy40():
     return synth.make_noisy_sequence(23, 40, 0.3, n_kp=1200)
@@ -71,7 +53,7 @@ def noisy40():
 @pytest.mark.parametrize("K", [2, 3, 4, 5])
 def test_batch_against_the_restatement(viso, noisy40, K):
     ctx = libviso_amd.Context(0)
-    b = _seq_run(ctx, noisy40, K)
+    b = seq_batch(ctx, noisy40, window=(K,))
     recs = b.window_refines()
     frames = WR.frames_from_batch(b)
     n_valid, lens = 0, []
@@ -87,7 +69,7 @@ def test_batch_against_the_restatement(viso, noisy40, K):
 
 def test_k2_records_agree_with_the_motion_refinement(viso, noisy40):
     ctx = libviso_amd.Context(0)
-    b = _seq_run(ctx, noisy40, 2, refine=1)
+    b = seq_batch(ctx, noisy40, refine=(1,), window=(2,))
     w, r = b.window_refines(), b.refines()
     good = 0
     for t in range(1, b.nf):
@@ -109,7 +91,7 @@ def test_k2_records_agree_with_the_motion_refinement(viso, noisy40):
 @pytest.mark.parametrize("K", [3, 5])
 def test_direct_call_is_byte_identical_to_the_batch(viso, noisy40, K):
     ctx = libviso_amd.Context(0)
-    b = _seq_run(ctx, noisy40, K, mode=2, sigma=0.3)
+    b = seq_batch(ctx, noisy40, window=(K, 2, 0.3))
     recs = b.window_refines()
     n = 0
     for t in range(1, b.nf):
@@ -132,10 +114,10 @@ def test_direct_call_is_byte_identical_to_the_batch(viso, noisy40, K):
 def test_chunked_batches_give_byte_equal_records(viso, noisy40):
     K = 4
     ctx = libviso_amd.Context(0)
-    whole = _seq_run(ctx, noisy40, K).window_refines()
+    whole = seq_batch(ctx, noisy40, window=(K,)).window_refines()
     c0 = 20
-    ba = _seq_run(ctx, noisy40, K, frames=slice(0, c0))
-    bc = _seq_run(ctx, noisy40, K, first=c0 - (K - 1), frames=slice(c0 - (K - 1), 40))   # a K - 1 frame halo
+    ba = seq_batch(ctx, noisy40, window=(K,), frames=slice(0, c0))
+    bc = seq_batch(ctx, noisy40, window=(K,), first=c0 - (K - 1), frames=slice(c0 - (K - 1), 40))   # a K - 1 frame halo
     a, c = ba.window_refines(), bc.window_refines()
     assert a[1:].tobytes() == whole[1:c0].tobytes()
     assert c[K - 1:].tobytes() == whole[c0:].tobytes()
@@ -145,8 +127,8 @@ def test_chunked_batches_give_byte_equal_records(viso, noisy40):
 
 def test_window_on_and_off_leave_everything_else_identical(viso, noisy40):
     ctx = libviso_amd.Context(0)
-    b0 = _seq_run(ctx, noisy40, 0, cov=1, refine=1)
-    b1 = _seq_run(ctx, noisy40, 5, cov=1, refine=1)
+    b0 = seq_batch(ctx, noisy40, cov=(1,), refine=(1,))
+    b1 = seq_batch(ctx, noisy40, cov=(1,), refine=(1,), window=(5,))
     for x, y in zip(b0.poses(), b1.poses()):
         assert x.tobytes() == y.tobytes()
     for t in range(b0.nf):
@@ -202,7 +184,7 @@ def test_accuracy_on_a_noisy_sequence(viso):
     seq = synth.make_noisy_sequence(17, 257, sigma)
     gt = seq["tr_gt"]
     ctx = libviso_amd.Context(0)
-    b = _seq_run(ctx, seq, 2, mode=2, sigma=sigma)
+    b = seq_batch(ctx, seq, window=(2, 2, sigma))
     r2 = b.window_refines()
     b.set_window_refine(4, 2, sigma)
     b.run()

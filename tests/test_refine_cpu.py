@@ -13,6 +13,7 @@ from libviso_amd.abi import MOTION_COV_DTYPE, MOTION_REFINE_DTYPE, Param
 
 import covariance_ref as CR
 import refine_ref as RR
+from estimator_util import kernel_resources
 
 
 def _scene(rng, m, zmin=5.0, zmax=50.0):
@@ -186,21 +187,7 @@ def test_argument_errors_return_codes():
 def test_kernel_keeps_occupancy_two_without_scratch():
     """The kernel's register budget is a property of the compiler's output: compile refine.hip for gfx950 and read the resource
     usage.  Occupancy 1 is the trap DESIGN 5.8 describes; scratch is not allowed."""
-    import os
-    import re
-    import subprocess
-    import tempfile
-    src = os.path.join(os.path.dirname(libviso_amd.SO_PATH), "csrc", "refine.hip")
-    with tempfile.TemporaryDirectory() as tmp:
-        r = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off",
-                            "-fno-fast-math", "-c", src, "-o", os.path.join(tmp, "refine.o"), "-Rpass-analysis=kernel-resource-usage"],
-                           capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    text = r.stderr
-    i = text.index("motion_refine_kernel")
-    block = text[i:i + 4000]
-    occ = int(re.search(r"Occupancy \[waves/SIMD\]: (\d+)", block).group(1))
-    scratch = int(re.search(r"ScratchSize \[bytes/lane\]: (\d+)", block).group(1))
+    occ, scratch = kernel_resources("refine.hip", ("motion_refine_kernel",))["motion_refine_kernel"]
     print(f"occupancy {occ}, scratch {scratch}")
     assert occ >= 2 and scratch == 0
 

@@ -14,6 +14,7 @@ from libviso_amd.abi import MOTION_COV_DTYPE, WINDOW_RECORD_DTYPE, Param
 import covariance_ref as CR
 import refine_ref as RR
 import window_ref as WR
+from estimator_util import kernel_resources
 
 
 def _param():
@@ -293,22 +294,8 @@ def test_argument_errors_return_codes():
 def test_kernel_has_no_scratch():
     """The kernels' resource usage is a property of the compiler's output: compile window.hip for gfx950 and read it.  Scratch is not
     allowed; the occupancy is reported."""
-    import os
-    import re
-    import subprocess
-    import tempfile
-    src = os.path.join(os.path.dirname(libviso_amd.SO_PATH), "csrc", "window.hip")
-    with tempfile.TemporaryDirectory() as tmp:
-        r = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off",
-                            "-fno-fast-math", "-c", src, "-o", os.path.join(tmp, "window.o"), "-Rpass-analysis=kernel-resource-usage"],
-                           capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    text = r.stderr
-    for name in ("window_links_kernel", "window_refine_kernel"):
-        i = text.index(name)
-        block = text[i:i + 4000]
-        occ = int(re.search(r"Occupancy \[waves/SIMD\]: (\d+)", block).group(1))
-        scratch = int(re.search(r"ScratchSize \[bytes/lane\]: (\d+)", block).group(1))
+    res = kernel_resources("window.hip", ("window_links_kernel", "window_refine_kernel"))
+    for name, (occ, scratch) in res.items():
         print(f"{name}: occupancy {occ}, scratch {scratch}")
         assert scratch == 0 and occ >= 1
 
