@@ -9,41 +9,11 @@ import libviso_amd
 from libviso_amd import synth
 from libviso_amd.abi import MatchParams
 
-import covariance_ref as CR
 import window_ref as WR
-from estimator_util import ambiguous, seq_batch
+from estimator_util import seq_batch
+from window_cases import check, check_k2_identity
 
 pytestmark = pytest.mark.gpu
-
-ZERO_FIELDS = ("cov", "sigma2", "cost0", "cost", "gap", "iters")
-
-
-def _check(got, want, what):
-    for k in ("status", "len", "n_points", "n_rows"):
-        assert int(got[k]) == want[k], (what, k, int(got[k]), want[k])
-    for k in ("tr", "tr_win") + ZERO_FIELDS:
-        assert np.all(np.isfinite(got[k])), (what, k)
-    if want["status"] != 1:
-        assert np.asarray(got["tr"]).tobytes() == np.asarray(want["tr"]).tobytes(), what
-        assert np.asarray(got["tr_win"]).tobytes() == np.asarray(want["tr_win"]).tobytes(), what
-        for k in ZERO_FIELDS:
-            assert not np.any(got[k]), (what, k)
-        return
-    amb = ambiguous(want)
-    assert abs(int(got["iters"]) - want["iters"]) <= (1 if amb else 0), (what, int(got["iters"]), want["iters"])
-    d = np.asarray(got["tr"]) - want["tr"]
-    white = float(np.sqrt(d @ np.linalg.solve(want["cov"], d)))
-    if want["n_points"] >= 40:
-        assert white <= (1e-4 if amb else 1e-5), (what, white, d)
-    dw = np.abs(np.asarray(got["tr_win"]) - want["tr_win"]).max()
-    assert dw <= (1e-6 if amb else 1e-7), (what, dw)
-    S = np.asarray(got["cov"])
-    assert np.array_equal(S, S.T), what
-    assert CR.whitened_error(want["cov"], S) <= 1e-7, (what, CR.whitened_error(want["cov"], S))
-    for k in ("sigma2", "cost0", "cost"):
-        assert abs(float(got[k]) - want[k]) <= 1e-9 * max(want[k], 1e-300), (what, k, float(got[k]), want[k])
-    assert float(got["gap"]) <= 1e-6 and want["gap"] <= 1e-6, (what, float(got["gap"]), want["gap"])
-
 
 @pytest.fixture(scope="module")
 def noisy40():
@@ -59,7 +29,7 @@ def test_batch_against_the_restatement(viso, noisy40, K):
     n_valid, lens = 0, []
     for t in range(b.nf):
         want = WR.window(frames, t, K, noisy40["param"], 1)
-        _check(recs[t], want, (K, t))
+        check(recs[t], want, (K, t))
         assert recs[t].tobytes() == b.window_refine(t).tobytes()
         n_valid += want["status"] == 1
         lens.append(want["len"])
@@ -70,21 +40,7 @@ def test_batch_against_the_restatement(viso, noisy40, K):
 def test_k2_records_agree_with_the_motion_refinement(viso, noisy40):
     ctx = libviso_amd.Context(0)
     b = seq_batch(ctx, noisy40, refine=(1,), window=(2,))
-    w, r = b.window_refines(), b.refines()
-    good = 0
-    for t in range(1, b.nf):
-        assert int(w[t]["status"]) == int(r[t]["status"]), t
-        if int(r[t]["status"]) != 1:
-            continue
-        good += 1
-        assert abs(int(w[t]["iters"]) - int(r[t]["iters"])) <= 1, t
-        d = w[t]["tr"] - r[t]["tr"]
-        assert float(np.sqrt(d @ np.linalg.solve(r[t]["cov"], d))) <= 1e-4, t
-        assert CR.whitened_error(r[t]["cov"], w[t]["cov"]) <= 1e-6, t
-        for k in ("sigma2", "cost0", "cost"):
-            assert abs(float(w[t][k]) - float(r[t][k])) <= 1e-8 * float(r[t][k]), (t, k)
-        assert float(w[t]["gap"]) <= 1e-6 and int(w[t]["n_points"]) == int(r[t]["n"])
-    assert good >= 35
+    assert check_k2_identity(b.window_refines(), b.refines()) >= 35
     b.close(); ctx.close()
 
 
@@ -168,7 +124,7 @@ def test_image_in_path_with_subpixel(viso):
     n_valid = 0
     for t in range(nf):
         want = WR.window(frames, t, 3, seq["param"], 1)
-        _check(recs[t], want, t)
+        check(recs[t], want, t)
         n_valid += want["status"] == 1
     assert n_valid >= 10
     b.run_images(matcher_only=True)

@@ -1,51 +1,21 @@
 """No-GPU checks of the opt-in sliding-window bundle adjustment (include/viso_hip.h, "window refinement"): the K = 2 identity with the
 two-frame refinement, the optimum against numeric derivatives of the full cost, the Schur complement against the dense Gauss-Newton
-system, hand-built links, breaks and tracks, the status cases, a Monte Carlo of accuracy and consistency, argument errors, the
-kernel's resource usage and the device entry points failing loudly without a device."""
+system, hand-built links, breaks and tracks, the status cases, the expected records of the device tests' hand-built and chunk-edge
+windows (tests/window_cases.py), a Monte Carlo of accuracy and consistency, argument errors, the kernel's resource usage and the
+device entry points failing loudly without a device."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 import libviso_amd
-from libviso_amd import synth
-from libviso_amd.abi import MOTION_COV_DTYPE, WINDOW_RECORD_DTYPE, Param
+from libviso_amd.abi import MOTION_COV_DTYPE, WINDOW_RECORD_DTYPE
 
 import covariance_ref as CR
 import refine_ref as RR
 import window_ref as WR
 from estimator_util import kernel_resources
-
-
-def _param():
-    return Param.default(base=synth.KITTI_BASE, f=synth.KITTI_F, cu=synth.KITTI_CU, cv=synth.KITTI_CV)
-
-
-def simulate(rng, nf, m=40, sigma=0.3, keep=0.8, zmin=8.0, zmax=40.0):
-    """A sequence of nf frames with persistent points (each survives a frame with probability `keep`, new ones replace the others)
-    and fresh N(0, sigma^2) pixel noise on every keypoint of every frame; a keypoint's index is its point's id.  Returns
-    ([None, Frame(1), ...], the true motions, param); every frame starts at its true motion with every row an inlier."""
-    param = _param()
-    f, cu, cv = param.f, param.cu, param.cv
-    trs = [np.zeros(6)] + [np.concatenate([rng.uniform(-0.01, 0.01, 3), rng.uniform(-0.03, 0.03, 2), [-rng.uniform(0.3, 0.6)]])
-                           for _ in range(nf - 1)]
-    X = synth._new_points(rng, m, 1241, 376, zmin, zmax, f, cu, cv).T.copy()
-    ids = np.arange(m)
-    nxt = m
-    kp_prev = CR.predict(X, np.zeros(6), param)[0] + rng.normal(0, sigma, (4, m))
-    frames = [None]
-    for j in range(1, nf):
-        Xc = CR.rot(trs[j]) @ X + trs[j][3:, None]
-        kp = CR.predict(X, trs[j], param)[0] + rng.normal(0, sigma, (4, X.shape[1]))
-        frames.append(WR.Frame(CR.triangulate(kp_prev, param), kp, np.stack([ids, ids], 1), trs[j], 1, np.arange(X.shape[1])))
-        alive = rng.random(X.shape[1]) < keep
-        k_new = int(X.shape[1] - alive.sum())
-        Xn = synth._new_points(rng, k_new, 1241, 376, zmin, zmax, f, cu, cv).T.copy()
-        X = np.concatenate([Xc[:, alive], Xn], 1)
-        kp_prev = np.concatenate([kp[:, alive], CR.predict(Xn, np.zeros(6), param)[0] + rng.normal(0, sigma, (4, k_new))], 1)
-        ids = np.concatenate([ids[alive], np.arange(nxt, nxt + k_new)])
-        nxt += k_new
-    return frames, np.array(trs), param
+from window_cases import HAND_CASES, KEY_MAX, chunk_case, chunk_sizes, direct_frames, hand, hand_case, simulate, wn_chunk
 
 
 def test_k2_is_the_two_frame_refinement():
@@ -118,26 +88,12 @@ def test_schur_block_equals_the_dense_inverse():
             assert np.allclose(np.linalg.solve(S, s), (Hi @ g)[:W.nc], rtol=1e-7, atol=1e-14)
 
 
-def _hand(lefts, oks=None):
-    """Frames whose rows have the (cur-left, prev-left) lefts[j]; points and observations from a simple scene."""
-    rng = np.random.default_rng(0)
-    param = _param()
-    frames = [None]
-    for j in range(1, len(lefts)):
-        m = len(lefts[j])
-        X = np.stack([rng.uniform(-5, 5, m), rng.uniform(-2, 2, m), rng.uniform(8, 30, m)])
-        obs = CR.predict(X, np.zeros(6), param)[0]
-        ok = 1 if oks is None else oks[j]
-        frames.append(WR.Frame(X, obs, lefts[j], np.zeros(6), ok, np.arange(m)))
-    return frames, param
-
-
 def test_links_forks_breaks_and_track_starts():
     # frame j + 1 continues frame j's keypoints through its prev-left
     f1 = [(10 + i, 0 + i) for i in range(8)]
     f2 = [(20 + i, 10 + i) for i in range(8)]
     f3 = [(30 + i, 20 + i) for i in range(8)]
-    frames, param = _hand([None, f1, f2, f3])
+    frames, param = hand([None, f1, f2, f3])
     trk = WR.tracks(frames, 0, 3)
     assert [(s, rows) for s, rows in trk] == [(0, [i, i, i]) for i in range(8)]
     # frame a's own rows are never used: anchored at 1, frame 1's rows start nothing
@@ -149,7 +105,7 @@ def test_links_forks_breaks_and_track_starts():
     f3b[1] = (31, 20)
     f1b = list(f1)
     f1b[0] = (11, 0)
-    frames, param = _hand([None, f1b, f2, f3b])
+    frames, param = hand([None, f1b, f2, f3b])
     trk = WR.tracks(frames, 0, 3)
     starts = {(s, rows[0]) for s, rows in trk}
     assert (0, 0) in starts and (0, 1) in starts          # frame 1 rows 0, 1 share cur-left 11
@@ -166,12 +122,12 @@ def test_links_forks_breaks_and_track_starts():
     assert np.allclose(g["z0"][:, k], RR.project0(frames[3].X[:, [0]], param)[:, 0])
     # breaks: ok = 0 at frame 2, or |L'| < 6 at frame 2, move the anchor to 2
     for oks, f2x in (([1, 1, 0, 1, 1], f2), ([1, 1, 1, 1, 1], f2[:5])):
-        frames, param = _hand([None, f1, f2x, f3, [(40 + i, 30 + i) for i in range(8)]], oks=oks)
+        frames, param = hand([None, f1, f2x, f3, [(40 + i, 30 + i) for i in range(8)]], oks=oks)
         assert WR.anchor(frames, 4, 5) == 2 and WR.anchor(frames, 3, 5) == 2
         assert WR.is_break(frames[2])
         rec = WR.window(frames, 4, 5, param, 1)
         assert rec["len"] == 3
-    frames, param = _hand([None, f1, f2, f3, [(40 + i, 30 + i) for i in range(8)]])
+    frames, param = hand([None, f1, f2, f3, [(40 + i, 30 + i) for i in range(8)]])
     assert WR.anchor(frames, 4, 5) == 0 and WR.anchor(frames, 4, 3) == 2 and WR.anchor(frames, 1, 5) == 0
 
 
@@ -200,6 +156,60 @@ def test_status_cases():
     frames[3] = WR.Frame(Xh, fr.obs, fr.left, fr.tr, 1, fr.inl)
     frames[2] = f2
     assert WR.window(frames, 3, 2, param, 1)["status"] == -3   # K = 2: every row of frame 3 starts a track (its Xp_c is used)
+
+
+@pytest.mark.parametrize("name", sorted(HAND_CASES))
+def test_hand_cases_give_their_records(name):
+    """Every hand-built window of the device tests (tests/test_gpu_window_edges.py) gives the record worked out for it by hand,
+    in both modes, so that none of them passes as an easy status-1 record."""
+    frames, param, (status, length, n_points) = hand_case(name)
+    for mode, sigma in ((1, None), (2, 0.3)):
+        with np.errstate(all="ignore"):
+            rec = WR.window(frames, len(frames) - 1, len(frames), param, mode, sigma)
+        assert (rec["status"], rec["len"], rec["n_points"]) == (status, length, n_points), (name, mode)
+        if status == 1:
+            trk = rec["window"].order
+            a = len(frames) - length
+            rows = sorted((s + 1 + i, r) for s, rr in trk for i, r in enumerate(rr))
+            want = sorted((j, int(r)) for j in range(a + 1, len(frames)) for r in frames[j].Lp)
+            assert rows == want, name                       # every entry of L'_{a+1..t} in exactly one track
+            assert rec["gap"] <= 1e-6 and rec["iters"] < WR.MAX_ACCEPT, name   # converged: the device check applies unchanged
+
+
+def test_hand_case_details():
+    # the table is built from L' only: the second holder of key 15 (frame 1) and of key 13 (frame 2) is not in L'
+    frames, _p, _w = hand_case("dropped_row")
+    assert len(frames[1].Lp) == len(frames[2].Lp) == 8 and frames[1].left[8, 0] == 15 and frames[2].left[8, 1] == 13
+    assert WR.tables(frames[1])[0][15] == 5 and WR.tables(frames[2])[1][13] == 3
+    # a row listed twice holds its keys twice: neither links, and each entry starts a track
+    frames, _p, _w = hand_case("row_twice")
+    cur, prev = WR.tables(frames[2])
+    assert cur[23] == -2 and prev[13] == -2
+    assert [rows for s, rows in WR.tracks(frames, 0, 3) if s == 1] == [[3], [3]]
+    # a key held by two or three rows of L' is -2, whichever row wrote first
+    for name, j, side, key in (("fork3_prev", 2, 1, 10), ("fork3_cur", 1, 0, 10), ("extreme_keys_forked", 2, 0, KEY_MAX),
+                               ("extreme_keys_forked", 3, 1, 0)):
+        frames, _p, _w = hand_case(name)
+        assert WR.tables(frames[j])[side][key] == -2, name
+    frames, _p, _w = hand_case("extreme_keys")
+    assert WR.tables(frames[1])[0][KEY_MAX] == 0 and WR.tables(frames[2])[1][KEY_MAX] == 0
+    assert WR.tables(frames[2])[0][0] == 0 and WR.tables(frames[3])[1][0] == 0
+    # breaks by |L'| < 6 move the anchor; |L'| = 6 does not
+    for name in ("break_lp5", "empty_m0", "empty_ninl0", "break_z", "break_nan"):
+        frames, _p, _w = hand_case(name)
+        assert WR.is_break(frames[2]) and WR.anchor(frames, 4, 5) == 2, name
+    frames, _p, _w = hand_case("lp6_mid")
+    assert len(frames[2].Lp) == 6 and not WR.is_break(frames[2]) and WR.anchor(frames, 4, 5) == 0
+
+
+@pytest.mark.parametrize("length", [2, 3, 4, 5])
+def test_chunk_edge_windows(length):
+    assert [wn_chunk(L) for L in (2, 3, 4, 5)] == [64, 37, 21, 13]
+    for n in chunk_sizes(length):
+        frames, param, want = chunk_case(length, n)
+        rec = WR.window(frames, length - 1, length, param, 1)
+        assert (rec["status"], rec["len"], rec["n_points"]) == want, (length, n)
+        assert rec["n_rows"] == n * (3 + 4 * (length - 1)) and rec["gap"] <= 1e-6
 
 
 def test_monte_carlo_accuracy_and_nees():
@@ -249,7 +259,7 @@ def test_window_refines_as_covariances_packs_for_the_chain():
 
 def _direct_frames(rng, n=3, m=20):
     frames, _trs, param = simulate(rng, n + 1, m=m)
-    return [(fr.X, fr.obs, fr.left, fr.tr, fr.inl) for fr in frames[1:]], param
+    return direct_frames(frames), param
 
 
 def test_argument_errors_return_codes():
