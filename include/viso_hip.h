@@ -678,6 +678,66 @@ int viso_window_refine(int len, const int* m, const double* X, const double* obs
                        const int32_t* inl, const int* n_inl, const viso_param* param, int mode, double sigma_px,
                        viso_window_record* out);
 
+/* ------------------------------------------------ dense stereo disparity (opt-in; NOT in the reference)
+ *
+ * A per-pixel disparity map of a rectified pair, in the form of OpenCV's StereoBM (XSOBEL prefilter, SAD block, texture
+ * threshold, uniqueness ratio, 1/16-px V-fit) with an order-free variant of its left-right check.  Parity with OpenCV is not
+ * pinned; this definition is the contract, and the device output is bit-identical to it (exact integers throughout).
+ * Inputs: rectified uint8 L, R [rows][cols]; parameters D = num_disp, B = block, c = prefilter_cap, T = texture_threshold,
+ * u = uniqueness, m = lr_max_diff.  Valid: D in 16, 32, ..., 256; B odd in 5..21; c in 1..63; T >= 0; u in 0..100; m = -1 or
+ * 0..D.  Any other value gives VISO_ERR_ARG.
+ *   1. Prefilter: G = SobelX(I) exactly as the extractor computes it (3x3, BORDER_REFLECT_101 on both axes, an integer in
+ *      [-1020, 1020]); P = clamp(G, -c, c) + c, in [0, 2c].
+ *   2. r = B / 2.  A pixel (x, y) is inside when r <= y < rows - r and r <= x < cols - r; every other pixel is invalid (images
+ *      smaller than the block are all invalid; not an error).  Candidates of an inside pixel: d in [0, dmax(x)],
+ *      dmax(x) = min(D - 1, x - r).
+ *   3. Cost C(x, y, d) = sum_{|i|,|j| <= r} |P_L(x+i, y+j) - P_R(x+i-d, y+j)|, exact; at most 2c B^2 <= 55 566 (fits 16 bits).
+ *   4. d* = the smallest d that minimises C over the candidates; S = C(d*).
+ *   5. Texture: invalid if sum over the window of |P_L - c| < T.
+ *   6. Uniqueness (u > 0 only): thr = S + (S u) / 100 (integer division); invalid if some candidate d with |d - d*| > 1 has
+ *      C(d) <= thr.
+ *   7. Sub-pixel: when 0 < d* < dmax(x), p = C(d*+1), n = C(d*-1), k = p + n - 2S + |p - n|, off = k ? ((n - p) 256) / k : 0
+ *      (C division, truncating toward zero; |off| <= 128); else off = 0.  disp16 = (256 d* + off + 8) >> 4, in 1/16 px.
+ *      (StereoBM writes p - n: its cost index runs the other way.)
+ *   8. Left-right check (m >= 0 only): for a right pixel xr >= r, dR(xr, y) = the smallest d in [0, D-1] that minimises
+ *      C(xr + d, y, d) over the d with xr + d < cols - r, taken over every inside left pixel, valid or not (so the check does not
+ *      depend on an order); invalid if |dR(x - d*, y) - d*| > m.
+ *   9. Output int16 [rows][cols]: disp16 for valid pixels, VISO_DISP_INVALID (-16, StereoBM's value for a minimum disparity of 0)
+ *      otherwise.
+ * Out of scope: a negative minimum disparity, the speckle filter, SGM.
+ * One HIP kernel (stereo_disparity_kernel, one launch per batch) computes every frame of a call: one workgroup per row and
+ * frame, the cost volume never written to memory.  This build handles cols <= 2048 (VISO_ERR_UNSUPPORTED beyond). */
+#define VISO_DISP_INVALID (-16)
+typedef struct viso_disparity_params {
+    int32_t num_disp;           /* D */
+    int32_t block;              /* B */
+    int32_t prefilter_cap;      /* c */
+    int32_t texture_threshold;  /* T */
+    int32_t uniqueness;         /* u, percent */
+    int32_t lr_max_diff;        /* m; -1 turns the left-right check off */
+} viso_disparity_params;
+
+/* D = 128, B = 11, c = 31, T = 10, u = 15, m = 1.  Host only. */
+void viso_disparity_params_default(viso_disparity_params* p);
+/* Host pointers, default context: the map of one pair (out rows x cols int16).  The arguments are checked before any device is
+ * touched: VISO_ERR_ARG for null pointers, sizes <= 0 or invalid parameters; VISO_ERR_UNSUPPORTED for cols > 2048. */
+int viso_stereo_disparity(const uint8_t* left, const uint8_t* right, int rows, int cols, const viso_disparity_params* params,
+                          int16_t* out);
+/* Turn dense disparity on with a copy of *params (off with NULL, the default) for the batch's next image-in runs:
+ * viso_batch_run_images (also with matcher_only) then launches the kernel on the context's stream after the rest of the run
+ * has been issued (the solver does not wait behind it; it is outside the run's time stamps), over the resident images (the rectified ones when rectification is on); poses, matches and every other output are unchanged, and with it
+ * off nothing new is launched.  viso_batch_run and viso_batch_run_matcher (descriptor-in: no images) return VISO_ERR_ARG while it
+ * is on, and the batch stays usable.  The output [n_frames][rows][cols] int16 is allocated when first needed and again whenever
+ * the image geometry changes.  VISO_ERR_ARG: invalid parameters, a dead handle. */
+int viso_batch_set_disparity(viso_batch* b, const viso_disparity_params* params);
+/* Only the disparity of every frame, over images uploaded without keypoints (viso_batch_upload_images with kp = n = NULL).
+ * VISO_ERR_ARG when disparity is off or no images are uploaded; VISO_ERR_UNSUPPORTED for images wider than 2048. */
+int viso_batch_run_disparity(viso_batch* b);
+/* The map of frame t / of all n_frames frames (rows x cols int16 each, viso_batch_get_image_geometry) from the last run that
+ * computed one.  VISO_ERR_ARG when disparity is off or no run has computed it yet.  Synchronise like the other getters. */
+int viso_batch_get_disparity(viso_batch* b, int t, int16_t* out);
+int viso_batch_get_disparities(viso_batch* b, int16_t* out /* [n_frames][rows][cols] */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,9 +16,9 @@ import weakref
 
 import numpy as np
 
-from .abi import (DESC_LEN, MOTION_COV_DTYPE, MOTION_REFINE_DTYPE, WINDOW_RECORD_DTYPE, MatchParams, Param, declare_common,
-                  declare_covariance, declare_refine, declare_rectify, declare_subpixel, declare_window, f32p, f64p, i32p, i64p, intp,
-                  ptr)
+from .abi import (DESC_LEN, MOTION_COV_DTYPE, MOTION_REFINE_DTYPE, WINDOW_RECORD_DTYPE, DisparityParams, MatchParams, Param,
+                  declare_common, declare_covariance, declare_disparity, declare_refine, declare_rectify, declare_subpixel,
+                  declare_window, f32p, f64p, i32p, i64p, intp, ptr)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("VISO_HIP_SO") or os.path.join(_HERE, "libviso_hip.so")   # VISO_HIP_SO: another build of the library (A/B runs)
@@ -124,6 +124,8 @@ def load():
         declare_refine(L)
     if hasattr(L, "viso_batch_set_window_refine"):
         declare_window(L)
+    if hasattr(L, "viso_batch_set_disparity"):
+        declare_disparity(L)
     L.viso_harris_response.argtypes = [C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_double, f32p]
     L.viso_detect_harris_binned.argtypes = [C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                             C.c_double, f32p, f32p, intp]
@@ -455,6 +457,46 @@ def rectify_images(raw, mapx, mapy, out_shape, border=0):
     return out[0].copy() if single else out[:n].copy()
 
 
+DISP_INVALID = -16   # VISO_DISP_INVALID
+
+
+def disparity_params(**params):
+    """viso_disparity_params: viso_disparity_params_default with the given fields (num_disp, block, prefilter_cap,
+    texture_threshold, uniqueness, lr_max_diff) replaced."""
+    p = DisparityParams()
+    load().viso_disparity_params_default(C.byref(p))
+    for k, v in params.items():
+        if k not in dict(DisparityParams._fields_):
+            raise TypeError(f"disparity_params: unknown parameter {k!r}")
+        setattr(p, k, int(v))
+    return p
+
+
+def stereo_disparity(imgL, imgR, **params):
+    """viso_stereo_disparity: the dense disparity map of one rectified pair (opt-in, not in the reference; the definition of
+    include/viso_hip.h), on the device.  Returns int16 [rows][cols] in 1/16 px, DISP_INVALID where invalid."""
+    L = load()
+    imgL = np.ascontiguousarray(imgL, dtype=np.uint8)
+    imgR = np.ascontiguousarray(imgR, dtype=np.uint8)
+    if imgL.shape != imgR.shape or imgL.ndim != 2:
+        raise ValueError("stereo_disparity: the two images must be 2-D and of one size")
+    p = disparity_params(**params)
+    out = np.empty(imgL.shape, np.int16)
+    r = L.viso_stereo_disparity(ptr(imgL, C.c_uint8), ptr(imgR, C.c_uint8), imgL.shape[0], imgL.shape[1], C.byref(p),
+                                ptr(out, C.c_int16))
+    if r != 1:
+        _err("viso_stereo_disparity", r)
+    return out
+
+
+def disparity_to_float(d16):
+    """float32 disparity in pixels (d16 / 16), NaN where invalid."""
+    d16 = np.asarray(d16)
+    out = d16.astype(np.float32) / np.float32(16)
+    out[d16 == DISP_INVALID] = np.nan
+    return out
+
+
 HARRIS_K = float(np.float32(0.04))   # the reference's intended default (float k = .04, src/viso.cpp:915)
 
 
@@ -742,6 +784,36 @@ class Batch:
             raise VisoError("Batch.image: no images uploaded")
         out = np.empty(shape, np.uint8)
         self._chk("viso_batch_get_image", self.L.viso_batch_get_image(self.h, int(t), int(side), ptr(out, C.c_uint8)))
+        return out
+
+    def set_disparity(self, params=None, **kw):
+        """viso_batch_set_disparity: dense disparity of every frame's resident pair in the next image-in runs (run_images, also
+        matcher_only) and in run_disparity.  params: a DisparityParams, a dict of its fields, or keyword fields (defaults for the
+        rest); set_disparity(None) turns it off (the default)."""
+        if params is None and not kw:
+            self._chk("viso_batch_set_disparity", self.L.viso_batch_set_disparity(self.h, None))
+            return
+        if isinstance(params, DisparityParams):
+            if kw:
+                raise TypeError("set_disparity: keyword fields cannot be combined with a DisparityParams")
+        else:
+            params = disparity_params(**dict(params or {}, **kw))
+        self._chk("viso_batch_set_disparity", self.L.viso_batch_set_disparity(self.h, C.byref(params)))
+
+    def run_disparity(self):
+        """viso_batch_run_disparity: only the disparity, over the resident images (upload_images_only)."""
+        self._chk("viso_batch_run_disparity", self.L.viso_batch_run_disparity(self.h))
+
+    def disparity(self, t):
+        """Frame t's int16 map [rows][cols] from the last run that computed one."""
+        out = np.empty(self.image_shape(), np.int16)
+        self._chk("viso_batch_get_disparity", self.L.viso_batch_get_disparity(self.h, int(t), ptr(out, C.c_int16)))
+        return out
+
+    def disparities(self):
+        """Every frame's int16 map, [n_frames][rows][cols]."""
+        out = np.empty((self.nf,) + tuple(self.image_shape()), np.int16)
+        self._chk("viso_batch_get_disparities", self.L.viso_batch_get_disparities(self.h, ptr(out, C.c_int16)))
         return out
 
     def _records(self, name, dtype, t=None):

@@ -146,6 +146,23 @@ def declare_rectify(lib):
     lib.viso_rectify_images.argtypes = [u8p, C.c_int, C.c_int, C.c_int, f32p, f32p, C.c_int, C.c_int, C.c_int, u8p]
 
 
+class DisparityParams(C.Structure):
+    """struct viso_disparity_params (include/viso_hip.h, "dense stereo disparity")."""
+    _fields_ = [(name, C.c_int32) for name in ("num_disp", "block", "prefilter_cap", "texture_threshold", "uniqueness", "lr_max_diff")]
+
+
+def declare_disparity(lib):
+    """Prototypes of the opt-in dense disparity (include/viso_hip.h; libviso_hip.so only)."""
+    u8p, i16p, DP = C.POINTER(C.c_uint8), C.POINTER(C.c_int16), C.POINTER(DisparityParams)
+    lib.viso_disparity_params_default.restype = None
+    lib.viso_disparity_params_default.argtypes = [DP]
+    lib.viso_stereo_disparity.argtypes = [u8p, u8p, C.c_int, C.c_int, DP, i16p]
+    lib.viso_batch_set_disparity.argtypes = [C.c_void_p, DP]
+    lib.viso_batch_run_disparity.argtypes = [C.c_void_p]
+    lib.viso_batch_get_disparity.argtypes = [C.c_void_p, C.c_int, i16p]
+    lib.viso_batch_get_disparities.argtypes = [C.c_void_p, i16p]
+
+
 class MotionCov(C.Structure):
     """struct viso_motion_cov (include/viso_hip.h, "motion covariance")."""
     _fields_ = [

@@ -11,6 +11,7 @@
 //   x_c [nf][4][cap], Xp_c [nf][3][cap]   double, SoA rows like cv::Mat(4,M): the solver's inputs, written by the circle join
 //   uv  [nf][cap] float2                 refined right-image points per stereo row (viso_batch_set_subpixel != 0 only)
 //   raw [nf][2][raw_rows][raw_cols] u8   staged raw images the remap reads into `images` (viso_batch_set_rectify only)
+//   disp [nf][img_rows][img_cols] i16    dense disparity of every frame's resident pair (viso_batch_set_disparity only)
 // `which` = 0 stereo L->R of frame t, 1 temporal left (t vs t-1), 2 temporal right.
 #include "common.h"
 
@@ -43,6 +44,9 @@ struct viso_batch {
     // opt-in rectification of raw images (rectify.hip): on while rmap != null; the quantised maps [2][img_rows * img_cols], the
     // raw staging buffer, its geometry and the border value
     RectEntry* rmap = nullptr; uint8_t* raw = nullptr; int raw_rows = 0, raw_cols = 0, rborder = 0; size_t raw_bytes = 0;
+    // opt-in dense disparity (disparity.hip): on while disp_on; the parameters, the maps (allocated when first needed, for the
+    // geometry disp_rows x disp_cols), and whether the maps hold the last image geometry's result (0: no run has computed them)
+    bool disp_on = false; viso_disparity_params disp_p = {}; int16_t* disp = nullptr; int disp_rows = 0, disp_cols = 0; int disp_last = 0;
     // opt-in motion covariance (covariance.hip): the mode and sigma asked for, the records [nf] (allocated on the first request,
     // frame 0 stays zero: status 0), and the mode the last run computed them with (0: the last run computed none)
     int cov_mode = 0; double cov_sigma = 0.0; viso_motion_cov* cov = nullptr; int cov_last = 0;
@@ -181,7 +185,7 @@ int viso_batch_free(viso_batch* b, bool keep_shell) {
     void* ptrs[] = {b->h_part, b->h_resp, b->h_tmp_kp, b->h_tmp_resp, b->h_cnt, b->images, b->skp, b->sidx, b->rank, b->bstart, b->xinfo, b->views,
                     b->kp, b->desc, b->n, b->packed, b->packed8, b->r8cnt, b->sums, b->zero, b->probs, b->res, b->sorted,
                     b->pos, b->m_cnt, b->scored, b->x_c, b->Xp_c, b->join,
-                    b->sitems, b->circ, b->pcl, b->mc, b->uv, b->cov, b->ref, b->ref_pts, b->ref_idx, b->win, b->win_lp, b->win_nlp, b->win_tab, b->win_trk, b->win_pts, b->rmap, b->raw, b->tr /* + ok, n_inl */, b->inl, b->tr_h, b->ok_h, b->cnt_h, b->hq, b->samp_h, b->rot, b->tile_flag, b->qord, b->ovf_q};
+                    b->sitems, b->circ, b->pcl, b->mc, b->uv, b->cov, b->ref, b->ref_pts, b->ref_idx, b->win, b->win_lp, b->win_nlp, b->win_tab, b->win_trk, b->win_pts, b->rmap, b->raw, b->disp, b->tr /* + ok, n_inl */, b->inl, b->tr_h, b->ok_h, b->cnt_h, b->hq, b->samp_h, b->rot, b->tile_flag, b->qord, b->ovf_q};
     for (void* p : ptrs) if (p) note(hipFree(p));
     if (keep_shell) { b->ctx = nullptr; b->events.clear(); b->desc_family.clear(); b->desc_family.shrink_to_fit(); }
     else delete b;
@@ -467,6 +471,7 @@ static int ensure_images(viso_batch* b, int rows, int cols) {
         b->images = nullptr;
         if (b->h_resp) HIP_TRY(hipFree(b->h_resp));
         b->h_resp = nullptr;
+        b->disp_last = 0;   // the maps were of the old geometry (their buffer follows at the next disparity launch)
     }
     if (!b->images) {
         HIP_TRY(hipMalloc((void**)&b->images, (size_t)rows * cols * 2 * (size_t)b->nf));
@@ -575,12 +580,43 @@ extern "C" int viso_batch_kernel_timing(viso_batch* b, int enable) {
     return VISO_OK;
 }
 
+// The disparity of every frame's resident pair on the context's stream (viso_batch_set_disparity on, images present, geometry
+// checked by the caller).  The maps' buffer follows the image geometry: (re)allocated here, after the batch's work in flight.
+static int launch_batch_disparity(viso_batch* b) {
+    const size_t per = (size_t)b->img_rows * b->img_cols;
+    if (b->disp && (b->disp_rows != b->img_rows || b->disp_cols != b->img_cols)) {
+        int r;
+        if ((r = batch_sync(b)) < 0) return r;
+        HIP_TRY(hipFree(b->disp));
+        b->disp = nullptr;
+    }
+    if (!b->disp) {
+        HIP_TRY(hipMalloc((void**)&b->disp, sizeof(int16_t) * per * (size_t)b->nf));
+        b->disp_rows = b->img_rows; b->disp_cols = b->img_cols;
+    }
+    b->disp_last = 0;
+    HIP_TRY(hipSetDevice(b->ctx->device));
+    const int r = launch_disparity(b->ctx->stream, b->images, 2 * per, per, b->img_rows, b->img_cols, b->nf, &b->disp_p, b->disp, per);
+    if (r < 0) return r;
+    b->disp_last = 1;
+    return VISO_OK;
+}
+
 static int run_matcher_impl(viso_batch* b, bool from_images) {
     if (!dead(b)) b->cov_last = b->ref_last = b->win_last = 0;   // the records of an earlier run are not this run's
     if (dead(b) || !b->params_set) { viso_set_error("viso_batch_run: parameters not set"); return VISO_ERR_ARG; }
     if (from_images && (!b->images || b->dlen != VISO_DESC_LEN)) {
         viso_set_error("viso_batch_run_images: no images uploaded (or descriptor length is not 121)");
         return VISO_ERR_ARG;
+    }
+    if (!from_images && b->disp_on) {
+        viso_set_error("viso_batch_run: dense disparity (viso_batch_set_disparity) needs the images: use viso_batch_run_images, "
+                       "or turn it off for descriptor-in runs");
+        return VISO_ERR_ARG;
+    }
+    if (from_images && b->disp_on && !disparity_geometry_ok(b->img_rows, b->img_cols)) {
+        viso_set_error("viso_batch_run_images: dense disparity of %d-column images is beyond this build (2048 at most)", b->img_cols);
+        return VISO_ERR_UNSUPPORTED;
     }
     if (!from_images && b->subpix) {
         viso_set_error("viso_batch_run: sub-pixel refinement (viso_batch_set_subpixel %d) needs the images: use viso_batch_run_images, "
@@ -698,10 +734,13 @@ extern "C" int viso_batch_run(viso_batch* b) {
     return run_rest(b);
 }
 
+// Dense disparity (when on) goes on the context's stream behind everything else of the run: the circle join and the RANSAC stream
+// are issued first, so the poses do not queue behind it, and it stays outside the run's time stamps.
 extern "C" int viso_batch_run_images(viso_batch* b, int matcher_only) {
     int r = run_matcher_impl(b, true);
-    if (r < 0 || matcher_only) return r;
-    return run_rest(b);
+    if (r < 0) return r;
+    if (!matcher_only && (r = run_rest(b)) < 0) return r;
+    return b->disp_on ? launch_batch_disparity(b) : VISO_OK;
 }
 
 extern "C" int viso_batch_upload_images(viso_batch* b, int f0, int nf, const uint8_t* images, int rows, int cols,
@@ -1016,6 +1055,46 @@ extern "C" int viso_batch_set_rectify(viso_batch* b, int raw_rows, int raw_cols,
     b->rmap = m; b->raw_rows = raw_rows; b->raw_cols = raw_cols; b->rborder = border;
     return VISO_OK;
 }
+
+// Opt-in dense disparity (not in the reference; disparity.hip).  Only the parameters are kept here: the maps' buffer is allocated
+// by the first launch that needs it.
+extern "C" int viso_batch_set_disparity(viso_batch* b, const viso_disparity_params* params) {
+    if (dead(b) || (params && !disparity_params_ok(params))) {
+        viso_set_error("viso_batch_set_disparity: bad argument (NULL, or the parameters of include/viso_hip.h)");
+        return VISO_ERR_ARG;
+    }
+    b->disp_on = params != nullptr;
+    if (params) b->disp_p = *params;
+    return VISO_OK;
+}
+
+// Only the disparity, over images uploaded without keypoints.
+extern "C" int viso_batch_run_disparity(viso_batch* b) {
+    if (dead(b) || !b->disp_on || !b->images) {
+        viso_set_error("viso_batch_run_disparity: dense disparity is off, or no images are uploaded");
+        return VISO_ERR_ARG;
+    }
+    if (!disparity_geometry_ok(b->img_rows, b->img_cols)) {
+        viso_set_error("viso_batch_run_disparity: dense disparity of %d-column images is beyond this build (2048 at most)", b->img_cols);
+        return VISO_ERR_UNSUPPORTED;
+    }
+    int r;
+    if ((r = enter(b)) < 0) return r;
+    return launch_batch_disparity(b);
+}
+
+static int get_disparity(viso_batch* b, bool all, int t, int16_t* out, const char* where) {
+    if (dead(b) || (!all && (t < 0 || t >= b->nf)) || !out) { viso_set_error("%s: bad argument", where); return VISO_ERR_ARG; }
+    if (!b->disp_on || !b->disp_last) { viso_set_error("%s: dense disparity is off, or no run has computed it", where); return VISO_ERR_ARG; }
+    { const int rs_ = batch_sync(b); if (rs_ < 0) return rs_; }
+    const size_t per = (size_t)b->disp_rows * b->disp_cols;
+    HIP_TRY(hipMemcpy(out, b->disp + (all ? 0 : (size_t)t * per), sizeof(int16_t) * per * (all ? (size_t)b->nf : 1), hipMemcpyDeviceToHost));
+    return VISO_OK;
+}
+
+extern "C" int viso_batch_get_disparity(viso_batch* b, int t, int16_t* out) { return get_disparity(b, false, t, out, "viso_batch_get_disparity"); }
+
+extern "C" int viso_batch_get_disparities(viso_batch* b, int16_t* out) { return get_disparity(b, true, 0, out, "viso_batch_get_disparities"); }
 
 // The geometry of the batch's device images (what viso_batch_get_image copies): 0 x 0 before the first image upload.
 extern "C" int viso_batch_get_image_geometry(viso_batch* b, int* rows, int* cols) {

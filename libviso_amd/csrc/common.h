@@ -449,6 +449,12 @@ bool rect_geometry_ok(int raw_rows, int raw_cols, int out_rows, int out_cols);
 // image (f, side) of raw / out at f * fs + side * ss; map [sides][out_rows * out_cols]; frames 0 .. n_frames-1 of the pointers
 int launch_rectify(hipStream_t s, const uint8_t* raw, size_t raw_fs, size_t raw_ss, int raw_cols, uint8_t* out, size_t out_fs,
                    size_t out_ss, const RectEntry* map, int out_rows, int out_cols, int n_frames, int sides, int border);
+// disparity.hip: the opt-in dense disparity (viso_batch_set_disparity); pair of frame f at img + f * fs (left), + ss (right), its map
+// at out + f * ofs; frames 0 .. n_frames-1
+bool disparity_params_ok(const viso_disparity_params* p);
+bool disparity_geometry_ok(int rows, int cols);   // cols within what the kernel handles
+int launch_disparity(hipStream_t s, const uint8_t* img, size_t fs, size_t ss, int rows, int cols, int n_frames,
+                     const viso_disparity_params* p, int16_t* out, size_t ofs);
 // covariance.hip: the opt-in motion covariance (viso_batch_set_covariance); one record per item, out[item], read from the item's
 // X, obs, m_ptr, ld, tr, ok, n_inl, inl (what ransac_refit_kernel left)
 int launch_motion_cov(hipStream_t s, const SolverItem* items_dev, int n_items, const SolverParamsDev& sp, int mode, double sigma,

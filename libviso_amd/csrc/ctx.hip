@@ -20,7 +20,7 @@ void viso_set_error(const char* fmt, ...) {
 }
 
 extern "C" const char* viso_last_error(void) { return g_err; }
-extern "C" const char* viso_version(void) { return "libviso_hip 0.4.1 (gfx950, HIP, wave64; sub-pixel stereo refinement, rectification, motion covariance, motion refinement, window refinement)"; }
+extern "C" const char* viso_version(void) { return "libviso_hip 0.4.2 (gfx950, HIP, wave64; sub-pixel stereo refinement, rectification, motion covariance, motion refinement, window refinement, dense disparity)"; }
 
 // ---- handle registry ---------------------------------------------------------------------------------------------
 // "We never abort across the ABI" has to hold for a caller that gets the teardown order wrong, too: a batch follows its

@@ -2,6 +2,7 @@
 // arithmetic happens in viso::sequence_odometry -> libviso_hip.so.
 #include "kitti_shard.hpp"
 
+#include <algorithm>
 #include <climits>
 #include <cmath>
 #include <cstdio>
@@ -53,15 +54,17 @@ int kitti_count_frames(const std::string& seq_base, int begin, int end) {
 std::vector<FrameRecord> kitti_run_range(const std::string& seq_base, const Matd& P1, const Matd& P2, int begin,
                                          int first, int last, int device, int chunk, uint64_t ransac_seed,
                                          int decode_threads, OdometryStats* stats, int subpixel, const StereoRectification* rect,
-                                         int cov_mode, double cov_sigma, std::vector<viso_motion_cov>* cov) {
+                                         int cov_mode, double cov_sigma, std::vector<viso_motion_cov>* cov, const DisparityOutput* disp) {
     std::vector<FrameRecord> rec;
     if (cov) cov->clear();
     if (last <= first) return rec;
     const std::string ext = kitti_image_ext(seq_base, begin);
     StereoImageGenerator images({seq_base + "/image_0/%06d" + ext, seq_base + "/image_1/%06d" + ext},
                                 begin + first, begin + last);
+    DisparityOutput d;
+    if (disp) { d = *disp; d.write_first = first == 0; }   // frame `first` of a later range is the previous range's last frame
     OdometryResult res = sequence_odometry(P1, P2, images, chunk, ransac_seed, (uint64_t)(begin + first), device, decode_threads,
-                                           subpixel, rect, cov ? cov_mode : 0, cov_sigma);
+                                           subpixel, rect, cov ? cov_mode : 0, cov_sigma, disp ? &d : nullptr);
     if (stats) *stats = res.stats;
     // res.ok / res.tr / res.n_inliers: one entry per frame read, entry 0 = this range's first frame (no pose)
     for (size_t t = 1; t < res.ok.size(); ++t) {
@@ -206,6 +209,9 @@ static thread_local viso::Matd g_rect_P1, g_rect_P2;
 static thread_local int g_cov_mode = 0;
 static thread_local double g_cov_sigma = 0.0;
 static thread_local std::vector<viso_motion_cov> g_last_cov;
+// viso_kitti_set_disparity (g_disp_on)
+static thread_local bool g_disp_on = false;
+static thread_local viso::DisparityOutput g_disp;
 
 extern "C" const char* viso_host_last_error(void) { return g_host_err.c_str(); }
 namespace viso { void set_host_error(const std::string& s) { g_host_err = s; } }   // for the other C entry points (drop_in.cpp)
@@ -235,7 +241,7 @@ extern "C" int viso_kitti_run_range(const char* seq_base, int begin, int first, 
         std::vector<viso::FrameRecord> rec = viso::kitti_run_range(seq_base, P1, P2, begin, first, last, device, chunk, ransac_seed,
                                                                    g_decode_threads, &g_last_stats, g_subpixel,
                                                                    g_rect_on ? &g_rect : nullptr, g_cov_mode, g_cov_sigma,
-                                                                   g_cov_mode ? &g_last_cov : nullptr);
+                                                                   g_cov_mode ? &g_last_cov : nullptr, g_disp_on ? &g_disp : nullptr);
         for (size_t i = 0; i < rec.size(); ++i) {
             for (int j = 0; j < 6; ++j) rec8[i * 8 + (size_t)j] = rec[i].tr[j];
             rec8[i * 8 + 6] = rec[i].ok;
@@ -318,6 +324,102 @@ extern "C" int viso_kitti_set_rectify(const char* cam_to_cam_file) {
         return VISO_ERR_ARG;
     }
     g_rect = r; g_rect_P1 = P1; g_rect_P2 = P2; g_rect_on = true;
+    return VISO_OK;
+}
+
+extern "C" int viso_kitti_set_disparity(const char* dir, const viso_disparity_params* params) {
+    if (!dir || !*dir) { g_disp_on = false; return VISO_OK; }
+    viso_disparity_params p;
+    viso_disparity_params_default(&p);
+    if (params) p = *params;
+    const bool ok = p.num_disp >= 16 && p.num_disp <= 256 && p.num_disp % 16 == 0 && p.block >= 5 && p.block <= 21 && p.block % 2 == 1 &&
+                    p.prefilter_cap >= 1 && p.prefilter_cap <= 63 && p.texture_threshold >= 0 && p.uniqueness >= 0 &&
+                    p.uniqueness <= 100 && p.lr_max_diff >= -1 && p.lr_max_diff <= p.num_disp;
+    if (!ok) { g_host_err = "viso_kitti_set_disparity: parameters outside the ranges of include/viso_hip.h"; return VISO_ERR_ARG; }
+    viso::mkdirs(dir);
+    struct stat st;
+    if (::stat(dir, &st) != 0 || !S_ISDIR(st.st_mode)) { g_host_err = std::string("viso_kitti_set_disparity: cannot create ") + dir; return VISO_ERR_ARG; }
+    g_disp.dir = dir; g_disp.params = p; g_disp.write_first = true; g_disp_on = true;
+    return VISO_OK;
+}
+
+// ---- KITTI stereo PNG (16-bit grayscale) without zlib: stored deflate blocks, checksums computed here ----
+namespace {
+uint32_t crc32_update(uint32_t c, const uint8_t* p, size_t n) {
+    static const std::array<uint32_t, 256> table = [] {   // the reflected polynomial 0xEDB88320 of PNG / zlib
+        std::array<uint32_t, 256> t{};
+        for (uint32_t i = 0; i < 256; ++i) {
+            uint32_t v = i;
+            for (int k = 0; k < 8; ++k) v = (v & 1u) ? 0xEDB88320u ^ (v >> 1) : v >> 1;
+            t[i] = v;
+        }
+        return t;
+    }();
+    for (size_t i = 0; i < n; ++i) c = table[(c ^ p[i]) & 0xFFu] ^ (c >> 8);
+    return c;
+}
+void put32(std::vector<uint8_t>& v, uint32_t x) {
+    v.push_back((uint8_t)(x >> 24)); v.push_back((uint8_t)(x >> 16)); v.push_back((uint8_t)(x >> 8)); v.push_back((uint8_t)x);
+}
+void put_chunk(std::vector<uint8_t>& png, const char type[4], const std::vector<uint8_t>& data) {
+    put32(png, (uint32_t)data.size());
+    const size_t at = png.size();
+    png.insert(png.end(), type, type + 4);
+    png.insert(png.end(), data.begin(), data.end());
+    put32(png, crc32_update(0xFFFFFFFFu, png.data() + at, 4 + data.size()) ^ 0xFFFFFFFFu);
+}
+}  // namespace
+
+extern "C" int viso_write_disparity_png(const char* path, const int16_t* d16, int rows, int cols) {
+    if (!path || !*path || !d16 || rows <= 0 || cols <= 0 || (long long)cols * 2 + 1 > (1ll << 30)) {
+        g_host_err = "viso_write_disparity_png: bad argument";
+        return VISO_ERR_ARG;
+    }
+    // raw scanlines: filter byte 0, then cols big-endian 16-bit values; Adler-32 over them
+    const size_t line = (size_t)cols * 2 + 1, total = line * (size_t)rows;
+    std::vector<uint8_t> raw(total);
+    uint32_t a = 1, b = 0;
+    for (int y = 0; y < rows; ++y) {
+        uint8_t* o = raw.data() + (size_t)y * line;
+        o[0] = 0;
+        for (int x = 0; x < cols; ++x) {
+            const int v = d16[(size_t)y * cols + x];
+            const uint32_t u = v < 0 ? 0u : (uint32_t)v * 16u;   // VISO_DISP_INVALID and every negative value: 0
+            o[1 + 2 * x] = (uint8_t)(u >> 8); o[2 + 2 * x] = (uint8_t)u;
+        }
+    }
+    for (size_t i = 0; i < total; ) {   // Adler-32 in runs short enough that the sums cannot overflow before the modulo
+        const size_t n = std::min<size_t>(5552, total - i);
+        for (size_t k = 0; k < n; ++k) { a += raw[i + k]; b += a; }
+        a %= 65521u; b %= 65521u;
+        i += n;
+    }
+    std::vector<uint8_t> z;
+    z.reserve(total + total / 65535 * 5 + 16);
+    z.push_back(0x78); z.push_back(0x01);   // deflate, 32 K window, no dictionary; (0x7801 % 31 == 0)
+    size_t i = 0;
+    do {   // stored blocks of at most 65 535 bytes
+        const size_t n = std::min<size_t>(65535, total - i);
+        const bool last = i + n == total;
+        z.push_back(last ? 1 : 0);
+        z.push_back((uint8_t)n); z.push_back((uint8_t)(n >> 8));
+        z.push_back((uint8_t)~n); z.push_back((uint8_t)(~n >> 8));
+        z.insert(z.end(), raw.begin() + (long)i, raw.begin() + (long)(i + n));
+        i += n;
+    } while (i < total);
+    put32(z, (b << 16) | a);
+    std::vector<uint8_t> png = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1A, '\n'};
+    std::vector<uint8_t> ihdr;
+    put32(ihdr, (uint32_t)cols); put32(ihdr, (uint32_t)rows);
+    ihdr.push_back(16); ihdr.push_back(0); ihdr.push_back(0); ihdr.push_back(0); ihdr.push_back(0);   // 16-bit gray, no interlace
+    put_chunk(png, "IHDR", ihdr);
+    put_chunk(png, "IDAT", z);
+    put_chunk(png, "IEND", {});
+    const std::string f = path, tmp = f + ".tmp";
+    FILE* fp = std::fopen(tmp.c_str(), "wb");
+    bool ok = fp && std::fwrite(png.data(), 1, png.size(), fp) == png.size();
+    if (fp) ok = std::fclose(fp) == 0 && ok;
+    if (!ok || std::rename(tmp.c_str(), f.c_str()) != 0) { g_host_err = "viso_write_disparity_png: cannot write " + f; return VISO_ERR_ARG; }
     return VISO_OK;
 }
 

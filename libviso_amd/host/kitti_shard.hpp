@@ -50,8 +50,10 @@ std::vector<FrameRecord> kitti_run_range(const std::string& seq_base, const Matd
                                          int first, int last, int device, int chunk = 64, uint64_t ransac_seed = 0,
                                          int decode_threads = 0, OdometryStats* stats = nullptr, int subpixel = 0,
                                          const StereoRectification* rect = nullptr, int cov_mode = 0, double cov_sigma = 0.0,
-                                         std::vector<viso_motion_cov>* cov = nullptr);
+                                         std::vector<viso_motion_cov>* cov = nullptr, const DisparityOutput* disp = nullptr);
 // cov_mode / cov_sigma / cov: the opt-in motion covariance of sequence_odometry; *cov gets one record per FrameRecord.
+// disp: the opt-in dense disparity maps of sequence_odometry, one PNG per frame first + 1 .. last (and frame first too when
+// first == 0): a range's halo frame is written by the range that owns it.
 
 // The covariance file of the runners' --covariance option: one line per frame pair, "status n sigma2 gap" and the 21
 // upper-triangle entries of cov (row by row), every value %.17g.  Written under a temporary name and renamed.
@@ -111,6 +113,15 @@ int viso_kitti_set_covariance(int mode, double sigma_px);
 int viso_kitti_last_covariances(viso_motion_cov* out, int cap, int* n);
 // the covariance file of --covariance (viso::write_covariance_file)
 int viso_kitti_write_covariances(const char* file_name, const viso_motion_cov* rec, int n);
+// the dense disparity maps (viso_batch_set_disparity) of the next viso_kitti_run_range calls of this thread, written to
+// dir/%06d.png (the directory is created); dir null or "" = off.  params null = viso_disparity_params_default.  VISO_ERR_ARG for
+// invalid parameters or a directory that cannot be created.
+int viso_kitti_set_disparity(const char* dir, const viso_disparity_params* params);
+// One disparity map (int16 rows x cols, 1/16 px, VISO_DISP_INVALID = -16) as KITTI's stereo PNG: 16-bit grayscale, value =
+// 16 * disp16 (disparity = value / 256), 0 = invalid.  A valid disparity of 0 px is written as 0 as well: the format cannot tell it
+// from invalid.  zlib stored blocks (no compression: about 0.93 MB at 1241 x 376), Adler-32 and CRC-32 computed here; written under
+// a temporary name and renamed.  No device needed.  VISO_ERR_ARG: null pointers, sizes <= 0, a file that cannot be written.
+int viso_write_disparity_png(const char* path, const int16_t* d16, int rows, int cols);
 // chain n records and write the KITTI pose file (directories are created); *n_poses = lines written
 int viso_kitti_write_poses(const char* file_name, const double* rec8, int n, int* n_poses);
 // the same with the pose list the reference writes ([P1..Pn, Pn], see chain_records) when reference_pose_list != 0

@@ -263,6 +263,15 @@ struct StereoRectification {
     int border = 0;
 };
 
+// Opt-in dense disparity maps of every frame (viso_batch_set_disparity; NOT in the reference): each frame's map is written to
+// dir/%06d.png, named by the image index, in KITTI's stereo format (viso_write_disparity_png).  write_first: also the map of the
+// run's first frame (false when that frame is another range's last one: the halo frame is written only by its owner).
+struct DisparityOutput {
+    std::string dir;
+    viso_disparity_params params{};
+    bool write_first = true;
+};
+
 // sequence_odometry(P1, P2, images, dbg_dir), src/viso.h:138-139 / src/viso.cpp:1167-1330, without the
 // debug dumps: detection (MAX_FEATURE_NUM 1200, radius 5, :1171-1174), description, matching and the
 // solver all run on the device, `chunk` frames per batch.
@@ -278,9 +287,11 @@ struct StereoRectification {
 // cov_mode (opt-in, viso_batch_set_covariance; NOT in the reference): 1 = sigma^2 estimated, 2 = sigma = cov_sigma pixels; fills
 // OdometryResult::cov with one viso_motion_cov per frame.  A chunk's halo frame is recomputed like any other frame, so every
 // chunking and partition gives byte-identical records.
+// disp (may be null): the opt-in dense disparity maps, written as each chunk drains; the poses are unchanged by it.
 OdometryResult sequence_odometry(const Matd& P1, const Matd& P2, StereoImageGenerator& images,
                                  int chunk = 64, uint64_t ransac_seed = 0, uint64_t first_frame_index = 0,
                                  int device = 0, int decode_threads = 0, int subpixel = 0,
-                                 const StereoRectification* rect = nullptr, int cov_mode = 0, double cov_sigma = 0.0);
+                                 const StereoRectification* rect = nullptr, int cov_mode = 0, double cov_sigma = 0.0,
+                                 const DisparityOutput* disp = nullptr);
 
 }  // namespace viso

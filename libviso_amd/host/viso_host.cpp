@@ -2,6 +2,7 @@
 // the C-ABI (include/viso_hip.h).  No arithmetic of the hot path happens here:
 // this file reshapes containers into the ABI's plain arrays and chains poses.
 #include "viso.hpp"
+#include "kitti_shard.hpp"
 #ifdef __linux__
 #include <sched.h>
 #endif
@@ -321,6 +322,8 @@ struct ChunkPipeline {
     OdometryResult& out;
     double pose[16];
     int cov_mode = 0;                       // the image-driven run's viso_batch_set_covariance mode: drain collects the records
+    const DisparityOutput* disp = nullptr;  // the image-driven run's dense disparity: drain writes every owned frame's map
+    int first_index = 0;                    // image index of the run's first frame (the maps' file names)
     ChunkPipeline(OdometryResult& o, int device) : slot{Slot(device), Slot(device)}, out(o) {
         std::memcpy(pose, out.poses[0].ptr(), sizeof(pose));
     }
@@ -350,6 +353,7 @@ struct ChunkPipeline {
         std::vector<viso_motion_cov> cov(cov_mode ? (size_t)nf : 0);
         if (cov_mode) hip_check(viso_batch_get_covariances(s.b, cov.data()), "sequence_odometry (viso_batch_get_covariances)");
         out.stats.drain_wait_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (disp) write_maps(s);
         if (s.stamped) {
             double ms[2] = {0, 0};
             hip_check(viso_batch_stamp_ms(s.b, ms), "sequence_odometry");
@@ -376,6 +380,20 @@ struct ChunkPipeline {
                 out.poses.push_back(P);
                 out.frame_of_pose.push_back(s.global0 + t);
             }
+        }
+    }
+    // the chunk's maps, frame by frame: its halo frame (t = 0) belongs to the previous chunk, or to another range (write_first)
+    void write_maps(Slot& s) {
+        int rows = 0, cols = 0;
+        hip_check(viso_batch_get_image_geometry(s.b, &rows, &cols), "sequence_odometry (viso_batch_get_image_geometry)");
+        std::vector<int16_t> d((size_t)rows * cols);
+        for (int t = (s.global0 == 0 && disp->write_first) ? 0 : 1; t < s.nf; ++t) {
+            hip_check(viso_batch_get_disparity(s.b, t, d.data()), "sequence_odometry (viso_batch_get_disparity)");
+            char name[32];
+            std::snprintf(name, sizeof(name), "/%06d.png", first_index + s.global0 + t);
+            const std::string f = disp->dir + name;
+            if (viso_write_disparity_png(f.c_str(), d.data(), rows, cols) != VISO_OK)
+                throw std::runtime_error("sequence_odometry: cannot write " + f);
         }
     }
     void finish() {   // oldest first
@@ -734,7 +752,7 @@ int cpu_budget() {
 // slot's pinned buffer.  The halo frame is copied from the previous slot's buffer, not decoded twice.
 OdometryResult sequence_odometry(const Matd& P1, const Matd& P2, StereoImageGenerator& images, int chunk,
                                  uint64_t ransac_seed, uint64_t first_frame_index, int device, int decode_threads, int subpixel,
-                                 const StereoRectification* rect, int cov_mode, double cov_sigma) {
+                                 const StereoRectification* rect, int cov_mode, double cov_sigma, const DisparityOutput* disp) {
     using clock = std::chrono::steady_clock;
     auto since = [](clock::time_point t0) { return std::chrono::duration<double>(clock::now() - t0).count(); };
     const auto t_start = clock::now();
@@ -787,6 +805,8 @@ OdometryResult sequence_odometry(const Matd& P1, const Matd& P2, StereoImageGene
     out.stats.decode_threads = pool.size();
     ChunkPipeline pipe(out, device);
     pipe.cov_mode = cov_mode;
+    pipe.disp = disp;
+    pipe.first_index = first_index;
     int global0 = 0;                 // frame (relative to first_index) of the current chunk's halo
     int frames_read = 1;
     bool eos = false;
@@ -847,6 +867,7 @@ OdometryResult sequence_odometry(const Matd& P1, const Matd& P2, StereoImageGene
         if (r >= 0) r = viso_batch_set_params(b, &st, &tm, &vp, ransac_seed, first_frame_index + (uint64_t)global0);
         if (r >= 0) r = viso_batch_set_subpixel(b, subpixel);
         if (r >= 0 && cov_mode) r = viso_batch_set_covariance(b, cov_mode, cov_sigma);
+        if (r >= 0) r = viso_batch_set_disparity(b, disp ? &disp->params : nullptr);
         if (r >= 0) r = viso_batch_stamp(b, 0);
         if (r >= 0) r = viso_batch_upload_images_async(b, 0, nf, pin, rows, cols, nullptr, nullptr);
         if (r >= 0) r = viso_batch_stamp(b, 1);

@@ -27,6 +27,13 @@
 //                       (%.17g); byte-identical for every chunk size, W and partition.  Pose files are unchanged.  Not in the
 //                       reference
 //   --covariance-sigma s  with --covariance: mode 2, sigma = s pixels
+//   --disparity dir     opt-in: also write every frame's dense disparity map (viso_batch_set_disparity) to dir/%06d.png, named by
+//                       the image index, in KITTI's stereo format (16-bit, value = 16 * disp16, i.e. disparity * 256; invalid =
+//                       0, and a valid 0 px is 0 too: the format cannot tell them apart).  Uncompressed: about 0.93 MB per frame
+//                       at 1241 x 376.  A chunk's or rank's halo frame is written by its owner only, so the directory is
+//                       byte-identical for every chunk size, W and partition.  Pose files are unchanged.  Not in the reference
+//   --disparity-params D,B,c,T,u,m  with --disparity: num_disp, block, prefilter_cap, texture_threshold, uniqueness,
+//                       lr_max_diff (default 128,11,31,10,15,1)
 // Every rank reports where its wall time went: decode (PNG inflate on the worker threads; the calling thread's wait for
 // it is the runner's critical path), upload and GPU seconds from time stamps on the device.
 // libviso_amd/kitti_shard.py is the same runner with the gather as an RCCL all-gather (torch.distributed).
@@ -58,6 +65,9 @@ struct Args {
     std::string rectify;   // calib_cam_to_cam.txt of --rectify ("" = off)
     std::string covariance;   // --covariance file ("" = off)
     double cov_sigma = 0.0;   // --covariance-sigma (0: mode 1)
+    std::string disparity;    // --disparity dir ("" = off)
+    bool disp_params_given = false;
+    viso_disparity_params disp{};   // --disparity-params (defaults otherwise)
 };
 
 bool parse(int argc, char** argv, Args& a) {
@@ -76,6 +86,15 @@ bool parse(int argc, char** argv, Args& a) {
         else if (s == "--reference-pose-list") a.reference_pose_list = true;
         else if (s == "--rectify") { if (i + 1 >= argc || !*argv[i + 1]) return false; a.rectify = argv[++i]; }
         else if (s == "--covariance") { if (i + 1 >= argc || !*argv[i + 1]) return false; a.covariance = argv[++i]; }
+        else if (s == "--disparity") { if (i + 1 >= argc || !*argv[i + 1]) return false; a.disparity = argv[++i]; }
+        else if (s == "--disparity-params") {
+            if (i + 1 >= argc) return false;
+            viso_disparity_params& p = a.disp;
+            char tail = 0;
+            if (std::sscanf(argv[++i], "%d,%d,%d,%d,%d,%d%c", &p.num_disp, &p.block, &p.prefilter_cap, &p.texture_threshold,
+                            &p.uniqueness, &p.lr_max_diff, &tail) != 6) return false;
+            a.disp_params_given = true;
+        }
         else if (s == "--covariance-sigma") {
             if (i + 1 >= argc) return false;
             char* e = nullptr;
@@ -98,6 +117,7 @@ bool parse(int argc, char** argv, Args& a) {
     if ((a.rank >= 0) != (a.world > 0)) return false;
     if (a.rank >= a.world && a.world > 0) return false;
     if (a.cov_sigma > 0.0 && a.covariance.empty()) return false;   // --covariance-sigma belongs to --covariance
+    if (a.disp_params_given && a.disparity.empty()) return false;    // --disparity-params belongs to --disparity
     return true;
 }
 
@@ -133,7 +153,7 @@ int main(int argc, char** argv) {
     if (!parse(argc, argv, a)) {
         std::printf("usage: demo result_sha seq_name begin end [--gpus W | --rank r --world W | --gather W] "
                     "[--device d] [--same-device] [--chunk n] [--seed s] [--decode-threads n] [--reference-pose-list] [--subpixel 0|1|2] [--rectify calib_cam_to_cam.txt] "
-                    "[--covariance file [--covariance-sigma s]]\n");   // :81-85
+                    "[--covariance file [--covariance-sigma s]] [--disparity dir [--disparity-params D,B,c,T,u,m]]\n");   // :81-85
         return 1;
     }
     const char* home = std::getenv("KITTI_HOME");                                              // :96
@@ -153,6 +173,18 @@ int main(int argc, char** argv) {
         rectp = &rect;
     } else if (!viso::loadCalib(seq_base + "/calib.txt", P1, P2)) { std::fprintf(stderr, "cannot read %s/calib.txt\n", seq_base.c_str()); return 2; }
     const int n_frames = viso::kitti_count_frames(seq_base, a.begin, a.end);
+    viso::DisparityOutput disp;   // --disparity: checked (and its directory made) here, before any rank is forked
+    const viso::DisparityOutput* dispp = nullptr;
+    if (!a.disparity.empty()) {
+        if (viso_kitti_set_disparity(a.disparity.c_str(), a.disp_params_given ? &a.disp : nullptr) != VISO_OK) {
+            std::fprintf(stderr, "%s\n", viso_host_last_error());
+            return 2;
+        }
+        disp.dir = a.disparity;
+        if (a.disp_params_given) disp.params = a.disp;
+        else viso_disparity_params_default(&disp.params);
+        dispp = &disp;
+    }
 
     // ---- --gpus W: fork the ranks BEFORE this process touches the GPU (the parent never does: nothing above makes a
     // HIP call), each child carries on below as `--rank r --world W`; the parent waits and gathers.  fork without exec:
@@ -234,7 +266,7 @@ int main(int argc, char** argv) {
             std::vector<viso_motion_cov> cov;
             std::vector<viso::FrameRecord> rec = viso::kitti_run_range(seq_base, P1, P2, a.begin, range.first, range.second,
                                                                        device, a.chunk, a.seed, a.decode_threads, &stats, a.subpixel, rectp,
-                                                                       cov_mode(a), a.cov_sigma, a.covariance.empty() ? nullptr : &cov);
+                                                                       cov_mode(a), a.cov_sigma, a.covariance.empty() ? nullptr : &cov, dispp);
             viso::mkdirs(result_dir + "/shards");
             const std::string f = rank_file(result_dir, a.seq_name, a.rank, a.world);
             if (!a.covariance.empty() && !viso::write_cov_records(f + ".cov", range.first, range.second, cov)) {
@@ -252,7 +284,7 @@ int main(int argc, char** argv) {
         viso::StereoImageGenerator images({seq_base + "/image_0/%06d" + ext, seq_base + "/image_1/%06d" + ext}, a.begin, a.end);
         viso::OdometryResult res = viso::sequence_odometry(P1, P2, images, a.chunk, a.seed, (uint64_t)a.begin,
                                                            a.device >= 0 ? a.device : 0, a.decode_threads, a.subpixel, rectp,
-                                                           cov_mode(a), a.cov_sigma);   // :111
+                                                           cov_mode(a), a.cov_sigma, dispp);   // :111
         if (!a.covariance.empty()) {   // one line per frame pair: the records of frames 1 .. (entry 0 is the first frame)
             const std::vector<viso_motion_cov> pairs(res.cov.size() > 1 ? res.cov.begin() + 1 : res.cov.end(), res.cov.end());
             if (!write_covariances(a.covariance, pairs)) return 3;

@@ -71,6 +71,8 @@ def load_host():
     L.viso_kitti_set_subpixel.argtypes = [C.c_int]
     L.viso_kitti_set_rectify.argtypes = [C.c_char_p]
     L.viso_kitti_set_covariance.argtypes = [C.c_int, C.c_double]
+    L.viso_kitti_set_disparity.argtypes = [C.c_char_p, C.c_void_p]
+    L.viso_write_disparity_png.argtypes = [C.c_char_p, C.POINTER(C.c_int16), C.c_int, C.c_int]
     L.viso_kitti_last_covariances.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     L.viso_kitti_write_covariances.argtypes = [C.c_char_p, C.c_void_p, C.c_int]
     L.viso_kitti_load_cam_to_cam.argtypes = [C.c_char_p] + [C.POINTER(C.c_double)] * 4 + [C.POINTER(C.c_int)]
@@ -268,9 +270,27 @@ def main(argv=None):
                          "(status n sigma2 gap + 21 upper-triangle entries); not in the reference")
     ap.add_argument("--covariance-sigma", type=float, default=None, metavar="S",
                     help="with --covariance: take sigma = S pixels instead of estimating it")
+    ap.add_argument("--disparity", default=None, metavar="DIR",
+                    help="opt-in: also write every frame's dense disparity map to DIR/%%06d.png in KITTI's stereo format "
+                         "(16-bit, disparity * 256, 0 = invalid); halo frames are written by their owner only (not in the reference)")
+    ap.add_argument("--disparity-params", default=None, metavar="D,B,c,T,u,m",
+                    help="with --disparity: num_disp, block, prefilter_cap, texture_threshold, uniqueness, lr_max_diff "
+                         "(default 128,11,31,10,15,1)")
     args = ap.parse_args(argv)
     if args.covariance_sigma is not None and args.covariance is None:
         ap.error("--covariance-sigma needs --covariance")
+    disp_params = None
+    if args.disparity_params is not None:
+        if args.disparity is None:
+            ap.error("--disparity-params needs --disparity")
+        try:
+            vals = [int(v) for v in args.disparity_params.split(",")]
+        except ValueError:
+            vals = []
+        if len(vals) != 6:
+            ap.error("--disparity-params takes six integers D,B,c,T,u,m")
+        from .abi import DisparityParams
+        disp_params = DisparityParams(*vals)
     home = os.environ.get("KITTI_HOME")
     if not home:
         print("KITTI_HOME is not set", file=sys.stderr)
@@ -324,6 +344,11 @@ def main(argv=None):
         if L.viso_kitti_set_covariance(mode, float(args.covariance_sigma or 0.0)) != 1:
             print(f"kitti_shard: {L.viso_host_last_error().decode()}", file=sys.stderr)
             return 2
+
+    if args.disparity is not None and L.viso_kitti_set_disparity(
+            os.fsencode(os.path.abspath(args.disparity)), C.addressof(disp_params) if disp_params is not None else None) != 1:
+        print(f"kitti_shard: {L.viso_host_last_error().decode()}", file=sys.stderr)
+        return 2
 
     def die(code, what):
         # a failure that the peers cannot learn about through the collective: leave WITHOUT joining one (no barrier,
