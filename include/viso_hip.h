@@ -738,6 +738,59 @@ int viso_batch_run_disparity(viso_batch* b);
 int viso_batch_get_disparity(viso_batch* b, int t, int16_t* out);
 int viso_batch_get_disparities(viso_batch* b, int16_t* out /* [n_frames][rows][cols] */);
 
+/* ------------------------------------------------ semi-global matching (opt-in; NOT in the reference)
+ *
+ * A second method for the same dense maps: census costs smoothed along 4 or 8 image paths (Hirschmueller's SGM), then the
+ * selection of the block matcher above on the summed costs.  Parity with any other SGM implementation is not pinned; this
+ * definition is the contract, and the device output is bit-identical to it (exact integers throughout).
+ * Inputs: rectified uint8 L, R [rows][cols]; parameters D = num_disp, P1 = p1, P2 = p2, paths, u = uniqueness, m = lr_max_diff.
+ * Valid: D in 16, 32, ..., 256; 1 <= P1 <= P2 <= 192; paths 4 or 8; u in 0..100; m = -1 or 0..D.  Any other value gives
+ * VISO_ERR_ARG.
+ *   1. Census: a window 9 wide x 7 tall, rows and columns outside the image replicated (coordinates clamped).  Bit (i, j) of
+ *      cen(x, y), |i| <= 4, |j| <= 3, (i, j) != (0, 0), is 1 when I(x+i, y+j) < I(x, y): 62 bits, in any order.
+ *   2. Every pixel is inside (no block margin).  Candidates of (x, y): d in [0, dmax(x)], dmax(x) = min(D - 1, x).
+ *   3. Cost C(x, y, d) = popcount(cen_L(x, y) xor cen_R(x - d, y)) <= 62.
+ *   4. Paths: the directions r are (+-1, 0) and (0, +-1), with paths = 8 also (+-1, +-1).  If the pixel p - r is outside the
+ *      image, L_r(p, d) = C(p, d).  Otherwise, with M = the minimum of L_r(p - r, k) over the candidates k of p - r,
+ *        L_r(p, d) = C(p, d) + min(L_r(p-r, d), L_r(p-r, d-1) + P1, L_r(p-r, d+1) + P1, M + P2) - M,
+ *      terms whose disparity is not a candidate of p - r left out (M + P2 is always there).  So L_r <= 62 + P2 <= 254.
+ *   5. S(p, d) = sum over r of L_r(p, d) <= 8 * 254 (fits 16 bits).
+ *   6. Selection, steps 4 and 6-9 of the block matcher with S in place of C and no texture test: d* = the smallest minimiser of
+ *      S over the candidates, S* = S(d*); uniqueness (u > 0): thr = S* + (S* u) / 100, invalid if a candidate with
+ *      |d - d*| > 1 has S(d) <= thr; V-fit when 0 < d* < dmax(x): p = S(d*+1), n = S(d*-1), k = p + n - 2 S* + |p - n|,
+ *      off = k ? ((n - p) 256) / k : 0 (C division), disp16 = (256 d* + off + 8) >> 4; left-right check (m >= 0): dR(xr, y) = the
+ *      smallest d in [0, D-1] with xr + d < cols that minimises S(xr + d, y, d), over every pixel, valid or not; invalid if
+ *      |dR(x - d*, y) - d*| > m.  Output int16 [rows][cols]: disp16, or VISO_DISP_INVALID.
+ * Out of scope: a negative minimum disparity, the speckle filter, OpenCV's SGBM cost (Birchfield-Tomasi), more than 8 paths.
+ * HIP kernels (sgm.hip): census words, one launch per path direction over S [rows][cols][D] u16 in device memory, one selection
+ * launch.  This build handles cols <= 2048 (VISO_ERR_UNSUPPORTED beyond). */
+typedef struct viso_sgm_params {
+    int32_t num_disp;      /* D */
+    int32_t p1;            /* P1 */
+    int32_t p2;            /* P2 */
+    int32_t paths;         /* 4 or 8 */
+    int32_t uniqueness;    /* u, percent */
+    int32_t lr_max_diff;   /* m; -1 turns the left-right check off */
+} viso_sgm_params;
+
+/* D = 128, P1 = 10, P2 = 120, paths = 8, u = 10, m = 1.  Host only. */
+void viso_sgm_params_default(viso_sgm_params* p);
+/* Host pointers, default context: the map of one pair (out rows x cols int16).  The arguments are checked before any device is
+ * touched: VISO_ERR_ARG for null pointers, sizes <= 0 or invalid parameters; VISO_ERR_UNSUPPORTED for cols > 2048; VISO_ERR_NOMEM
+ * when the workspace cap cannot hold one frame. */
+int viso_stereo_sgm(const uint8_t* left, const uint8_t* right, int rows, int cols, const viso_sgm_params* params, int16_t* out);
+/* Turn SGM on with a copy of *params (off with NULL, the default): the batch's dense stage (viso_batch_run_images, also with
+ * matcher_only, and viso_batch_run_disparity) then computes its maps with SGM, at the place and with the guarantees of
+ * viso_batch_set_disparity; viso_batch_run_disparity and viso_batch_get_disparity(ies) serve them.  A batch has one map buffer, so
+ * one method at a time: VISO_ERR_ARG while viso_batch_set_disparity is on (and viso_batch_set_disparity returns VISO_ERR_ARG while
+ * SGM is on); the batch stays usable.  Descriptor-in runs return VISO_ERR_ARG while it is on.  The frames are processed in groups
+ * whose census words and S volumes (rows cols (16 + 2 D) bytes a frame) fit the workspace cap; the workspace is allocated by the
+ * first launch and freed with the batch, and the maps are the same for every group size.  A run returns VISO_ERR_NOMEM when the cap
+ * cannot hold one frame.  VISO_ERR_ARG: invalid parameters, a dead handle. */
+int viso_batch_set_sgm(viso_batch* b, const viso_sgm_params* params);
+/* The workspace cap in bytes of every later SGM launch of the process (0: the default, 2 GiB). */
+void viso_sgm_set_workspace_cap(size_t bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,9 +16,9 @@ import weakref
 
 import numpy as np
 
-from .abi import (DESC_LEN, MOTION_COV_DTYPE, MOTION_REFINE_DTYPE, WINDOW_RECORD_DTYPE, DisparityParams, MatchParams, Param,
-                  declare_common, declare_covariance, declare_disparity, declare_refine, declare_rectify, declare_subpixel,
-                  declare_window, f32p, f64p, i32p, i64p, intp, ptr)
+from .abi import (DESC_LEN, MOTION_COV_DTYPE, MOTION_REFINE_DTYPE, SGM_DEFAULTS, WINDOW_RECORD_DTYPE, DisparityParams, MatchParams,
+                  Param, SgmParams, declare_common, declare_covariance, declare_disparity, declare_refine, declare_rectify,
+                  declare_sgm, declare_subpixel, declare_window, f32p, f64p, i32p, i64p, intp, ptr)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("VISO_HIP_SO") or os.path.join(_HERE, "libviso_hip.so")   # VISO_HIP_SO: another build of the library (A/B runs)
@@ -126,6 +126,8 @@ def load():
         declare_window(L)
     if hasattr(L, "viso_batch_set_disparity"):
         declare_disparity(L)
+    if hasattr(L, "viso_batch_set_sgm"):
+        declare_sgm(L)
     L.viso_harris_response.argtypes = [C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_double, f32p]
     L.viso_detect_harris_binned.argtypes = [C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                             C.c_double, f32p, f32p, intp]
@@ -489,6 +491,44 @@ def stereo_disparity(imgL, imgR, **params):
     return out
 
 
+def sgm_params(**params):
+    """viso_sgm_params: viso_sgm_params_default with the given fields (num_disp, p1, p2, paths, uniqueness, lr_max_diff) replaced.
+    Needs no library: the ranges are checked by the calls that take it (SgmParams.ok restates them)."""
+    p = SgmParams(**SGM_DEFAULTS)
+    for k, v in params.items():
+        if k not in SGM_DEFAULTS:
+            raise TypeError(f"sgm_params: unknown parameter {k!r}")
+        setattr(p, k, int(v))
+    return p
+
+
+def stereo_sgm(imgL, imgR, **params):
+    """viso_stereo_sgm: the dense disparity map of one rectified pair by semi-global matching (opt-in, not in the reference; the
+    definition of include/viso_hip.h), on the device.  Returns int16 [rows][cols] in 1/16 px, DISP_INVALID where invalid."""
+    L = load()
+    imgL = np.ascontiguousarray(imgL, dtype=np.uint8)
+    imgR = np.ascontiguousarray(imgR, dtype=np.uint8)
+    if imgL.shape != imgR.shape or imgL.ndim != 2:
+        raise ValueError("stereo_sgm: the two images must be 2-D and of one size")
+    p = sgm_params(**params)
+    out = np.empty(imgL.shape, np.int16)
+    r = L.viso_stereo_sgm(ptr(imgL, C.c_uint8), ptr(imgR, C.c_uint8), imgL.shape[0], imgL.shape[1], C.byref(p), ptr(out, C.c_int16))
+    if r != 1:
+        _err("viso_stereo_sgm", r)
+    return out
+
+
+def sgm_set_workspace_cap(nbytes):
+    """viso_sgm_set_workspace_cap: the bytes of census words and S volumes one group of frames may take (0: the default)."""
+    load().viso_sgm_set_workspace_cap(int(nbytes))
+
+
+def sgm_frame_bytes(rows, cols, num_disp=128):
+    """The workspace of one frame: the two images' census words and the S volume, each rounded up to 256 bytes."""
+    up = lambda b: (b + 255) & ~255   # noqa: E731
+    return up(rows * cols * 16) + up(rows * cols * num_disp * 2)
+
+
 def disparity_to_float(d16):
     """float32 disparity in pixels (d16 / 16), NaN where invalid."""
     d16 = np.asarray(d16)
@@ -799,6 +839,21 @@ class Batch:
         else:
             params = disparity_params(**dict(params or {}, **kw))
         self._chk("viso_batch_set_disparity", self.L.viso_batch_set_disparity(self.h, C.byref(params)))
+
+    def set_sgm(self, params=None, **kw):
+        """viso_batch_set_sgm: the batch's dense maps by semi-global matching in the next image-in runs and in run_disparity
+        (run_disparity / disparity / disparities serve them).  params: an SgmParams, a dict of its fields, or keyword fields
+        (defaults for the rest); set_sgm(None) turns it off (the default).  One method at a time: refused while set_disparity is
+        on."""
+        if params is None and not kw:
+            self._chk("viso_batch_set_sgm", self.L.viso_batch_set_sgm(self.h, None))
+            return
+        if isinstance(params, SgmParams):
+            if kw:
+                raise TypeError("set_sgm: keyword fields cannot be combined with an SgmParams")
+        else:
+            params = sgm_params(**dict(params or {}, **kw))
+        self._chk("viso_batch_set_sgm", self.L.viso_batch_set_sgm(self.h, C.byref(params)))
 
     def run_disparity(self):
         """viso_batch_run_disparity: only the disparity, over the resident images (upload_images_only)."""

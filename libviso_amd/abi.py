@@ -163,6 +163,30 @@ def declare_disparity(lib):
     lib.viso_batch_get_disparities.argtypes = [C.c_void_p, i16p]
 
 
+class SgmParams(C.Structure):
+    """struct viso_sgm_params (include/viso_hip.h, "semi-global matching")."""
+    _fields_ = [(name, C.c_int32) for name in ("num_disp", "p1", "p2", "paths", "uniqueness", "lr_max_diff")]
+
+    def ok(self):
+        """The valid ranges of include/viso_hip.h (what the library checks before it touches a device)."""
+        return (16 <= self.num_disp <= 256 and self.num_disp % 16 == 0 and 1 <= self.p1 <= self.p2 <= 192 and self.paths in (4, 8)
+                and 0 <= self.uniqueness <= 100 and -1 <= self.lr_max_diff <= self.num_disp)
+
+
+SGM_DEFAULTS = dict(num_disp=128, p1=10, p2=120, paths=8, uniqueness=10, lr_max_diff=1)   # viso_sgm_params_default
+
+
+def declare_sgm(lib):
+    """Prototypes of the opt-in semi-global matching (include/viso_hip.h; libviso_hip.so only)."""
+    u8p, i16p, SP = C.POINTER(C.c_uint8), C.POINTER(C.c_int16), C.POINTER(SgmParams)
+    lib.viso_sgm_params_default.restype = None
+    lib.viso_sgm_params_default.argtypes = [SP]
+    lib.viso_stereo_sgm.argtypes = [u8p, u8p, C.c_int, C.c_int, SP, i16p]
+    lib.viso_batch_set_sgm.argtypes = [C.c_void_p, SP]
+    lib.viso_sgm_set_workspace_cap.restype = None
+    lib.viso_sgm_set_workspace_cap.argtypes = [C.c_size_t]
+
+
 class MotionCov(C.Structure):
     """struct viso_motion_cov (include/viso_hip.h, "motion covariance")."""
     _fields_ = [

@@ -11,7 +11,8 @@
 //   x_c [nf][4][cap], Xp_c [nf][3][cap]   double, SoA rows like cv::Mat(4,M): the solver's inputs, written by the circle join
 //   uv  [nf][cap] float2                 refined right-image points per stereo row (viso_batch_set_subpixel != 0 only)
 //   raw [nf][2][raw_rows][raw_cols] u8   staged raw images the remap reads into `images` (viso_batch_set_rectify only)
-//   disp [nf][img_rows][img_cols] i16    dense disparity of every frame's resident pair (viso_batch_set_disparity only)
+//   disp [nf][img_rows][img_cols] i16    dense disparity of every frame's resident pair (viso_batch_set_disparity / _set_sgm only)
+//   sgm_ws                               census words and S volumes of one group of frames (viso_batch_set_sgm only; sgm.hip)
 // `which` = 0 stereo L->R of frame t, 1 temporal left (t vs t-1), 2 temporal right.
 #include "common.h"
 
@@ -47,6 +48,9 @@ struct viso_batch {
     // opt-in dense disparity (disparity.hip): on while disp_on; the parameters, the maps (allocated when first needed, for the
     // geometry disp_rows x disp_cols), and whether the maps hold the last image geometry's result (0: no run has computed them)
     bool disp_on = false; viso_disparity_params disp_p = {}; int16_t* disp = nullptr; int disp_rows = 0, disp_cols = 0; int disp_last = 0;
+    // opt-in semi-global matching (sgm.hip): on while sgm_on (never together with disp_on: the maps are one buffer, `disp`); the
+    // parameters and the workspace of one group of frames (allocated by the first launch, again when a launch needs another size)
+    bool sgm_on = false; viso_sgm_params sgm_p = {}; void* sgm_ws = nullptr; size_t sgm_ws_bytes = 0;
     // opt-in motion covariance (covariance.hip): the mode and sigma asked for, the records [nf] (allocated on the first request,
     // frame 0 stays zero: status 0), and the mode the last run computed them with (0: the last run computed none)
     int cov_mode = 0; double cov_sigma = 0.0; viso_motion_cov* cov = nullptr; int cov_last = 0;
@@ -185,7 +189,7 @@ int viso_batch_free(viso_batch* b, bool keep_shell) {
     void* ptrs[] = {b->h_part, b->h_resp, b->h_tmp_kp, b->h_tmp_resp, b->h_cnt, b->images, b->skp, b->sidx, b->rank, b->bstart, b->xinfo, b->views,
                     b->kp, b->desc, b->n, b->packed, b->packed8, b->r8cnt, b->sums, b->zero, b->probs, b->res, b->sorted,
                     b->pos, b->m_cnt, b->scored, b->x_c, b->Xp_c, b->join,
-                    b->sitems, b->circ, b->pcl, b->mc, b->uv, b->cov, b->ref, b->ref_pts, b->ref_idx, b->win, b->win_lp, b->win_nlp, b->win_tab, b->win_trk, b->win_pts, b->rmap, b->raw, b->disp, b->tr /* + ok, n_inl */, b->inl, b->tr_h, b->ok_h, b->cnt_h, b->hq, b->samp_h, b->rot, b->tile_flag, b->qord, b->ovf_q};
+                    b->sitems, b->circ, b->pcl, b->mc, b->uv, b->cov, b->ref, b->ref_pts, b->ref_idx, b->win, b->win_lp, b->win_nlp, b->win_tab, b->win_trk, b->win_pts, b->rmap, b->raw, b->disp, b->sgm_ws, b->tr /* + ok, n_inl */, b->inl, b->tr_h, b->ok_h, b->cnt_h, b->hq, b->samp_h, b->rot, b->tile_flag, b->qord, b->ovf_q};
     for (void* p : ptrs) if (p) note(hipFree(p));
     if (keep_shell) { b->ctx = nullptr; b->events.clear(); b->desc_family.clear(); b->desc_family.shrink_to_fit(); }
     else delete b;
@@ -596,6 +600,31 @@ static int launch_batch_disparity(viso_batch* b) {
     }
     b->disp_last = 0;
     HIP_TRY(hipSetDevice(b->ctx->device));
+    if (b->sgm_on) {   // the same maps by semi-global matching, group by group through the batch's workspace
+        const int group = sgm_group_frames(b->img_rows, b->img_cols, b->sgm_p.num_disp, b->nf);
+        if (group < 1) return sgm_nomem("viso_batch_run", b->img_rows, b->img_cols, b->sgm_p.num_disp);
+        const size_t want = sgm_frame_bytes(b->img_rows, b->img_cols, b->sgm_p.num_disp) * (size_t)group;
+        if (b->sgm_ws && b->sgm_ws_bytes != want) {
+            int r;
+            if ((r = batch_sync(b)) < 0) return r;
+            HIP_TRY(hipFree(b->sgm_ws));
+            b->sgm_ws = nullptr;
+        }
+        if (!b->sgm_ws) {
+            if (hipMalloc(&b->sgm_ws, want) != hipSuccess) {
+                (void)hipGetLastError();
+                b->sgm_ws = nullptr;
+                viso_set_error("viso_batch_run: cannot allocate the %zu-byte SGM workspace (viso_sgm_set_workspace_cap)", want);
+                return VISO_ERR_NOMEM;
+            }
+            b->sgm_ws_bytes = want;
+        }
+        const int r = launch_sgm(b->ctx->stream, b->images, 2 * per, per, b->img_rows, b->img_cols, b->nf, &b->sgm_p, b->disp, per,
+                                 b->sgm_ws, group);
+        if (r < 0) return r;
+        b->disp_last = 1;
+        return VISO_OK;
+    }
     const int r = launch_disparity(b->ctx->stream, b->images, 2 * per, per, b->img_rows, b->img_cols, b->nf, &b->disp_p, b->disp, per);
     if (r < 0) return r;
     b->disp_last = 1;
@@ -609,15 +638,17 @@ static int run_matcher_impl(viso_batch* b, bool from_images) {
         viso_set_error("viso_batch_run_images: no images uploaded (or descriptor length is not 121)");
         return VISO_ERR_ARG;
     }
-    if (!from_images && b->disp_on) {
-        viso_set_error("viso_batch_run: dense disparity (viso_batch_set_disparity) needs the images: use viso_batch_run_images, "
+    if (!from_images && (b->disp_on || b->sgm_on)) {
+        viso_set_error("viso_batch_run: dense disparity (viso_batch_set_disparity, viso_batch_set_sgm) needs the images: use viso_batch_run_images, "
                        "or turn it off for descriptor-in runs");
         return VISO_ERR_ARG;
     }
-    if (from_images && b->disp_on && !disparity_geometry_ok(b->img_rows, b->img_cols)) {
+    if (from_images && (b->disp_on || b->sgm_on) && !disparity_geometry_ok(b->img_rows, b->img_cols)) {
         viso_set_error("viso_batch_run_images: dense disparity of %d-column images is beyond this build (2048 at most)", b->img_cols);
         return VISO_ERR_UNSUPPORTED;
     }
+    if (from_images && b->sgm_on && sgm_group_frames(b->img_rows, b->img_cols, b->sgm_p.num_disp, b->nf) < 1)
+        return sgm_nomem("viso_batch_run_images", b->img_rows, b->img_cols, b->sgm_p.num_disp);
     if (!from_images && b->subpix) {
         viso_set_error("viso_batch_run: sub-pixel refinement (viso_batch_set_subpixel %d) needs the images: use viso_batch_run_images, "
                        "or set mode 0 for descriptor-in runs", b->subpix);
@@ -740,7 +771,7 @@ extern "C" int viso_batch_run_images(viso_batch* b, int matcher_only) {
     int r = run_matcher_impl(b, true);
     if (r < 0) return r;
     if (!matcher_only && (r = run_rest(b)) < 0) return r;
-    return b->disp_on ? launch_batch_disparity(b) : VISO_OK;
+    return b->disp_on || b->sgm_on ? launch_batch_disparity(b) : VISO_OK;
 }
 
 extern "C" int viso_batch_upload_images(viso_batch* b, int f0, int nf, const uint8_t* images, int rows, int cols,
@@ -1063,14 +1094,35 @@ extern "C" int viso_batch_set_disparity(viso_batch* b, const viso_disparity_para
         viso_set_error("viso_batch_set_disparity: bad argument (NULL, or the parameters of include/viso_hip.h)");
         return VISO_ERR_ARG;
     }
+    if (params && b->sgm_on) {
+        viso_set_error("viso_batch_set_disparity: semi-global matching is on (one method at a time: viso_batch_set_sgm(b, NULL) first)");
+        return VISO_ERR_ARG;
+    }
     b->disp_on = params != nullptr;
     if (params) b->disp_p = *params;
     return VISO_OK;
 }
 
+// Opt-in semi-global matching (not in the reference; sgm.hip): the other method for the same maps.  Only the parameters are kept
+// here: the workspace and the maps' buffer are allocated by the first launch that needs them.
+extern "C" int viso_batch_set_sgm(viso_batch* b, const viso_sgm_params* params) {
+    if (dead(b) || (params && !sgm_params_ok(params))) {
+        viso_set_error("viso_batch_set_sgm: bad argument (NULL, or the parameters of include/viso_hip.h)");
+        return VISO_ERR_ARG;
+    }
+    if (params && b->disp_on) {
+        viso_set_error("viso_batch_set_sgm: block matching is on (one method at a time: viso_batch_set_disparity(b, NULL) first)");
+        return VISO_ERR_ARG;
+    }
+    if (b->sgm_on != (params != nullptr)) b->disp_last = 0;   // maps of the other state are not this one's
+    b->sgm_on = params != nullptr;
+    if (params) b->sgm_p = *params;
+    return VISO_OK;
+}
+
 // Only the disparity, over images uploaded without keypoints.
 extern "C" int viso_batch_run_disparity(viso_batch* b) {
-    if (dead(b) || !b->disp_on || !b->images) {
+    if (dead(b) || !(b->disp_on || b->sgm_on) || !b->images) {
         viso_set_error("viso_batch_run_disparity: dense disparity is off, or no images are uploaded");
         return VISO_ERR_ARG;
     }
@@ -1078,6 +1130,8 @@ extern "C" int viso_batch_run_disparity(viso_batch* b) {
         viso_set_error("viso_batch_run_disparity: dense disparity of %d-column images is beyond this build (2048 at most)", b->img_cols);
         return VISO_ERR_UNSUPPORTED;
     }
+    if (b->sgm_on && sgm_group_frames(b->img_rows, b->img_cols, b->sgm_p.num_disp, b->nf) < 1)
+        return sgm_nomem("viso_batch_run_disparity", b->img_rows, b->img_cols, b->sgm_p.num_disp);
     int r;
     if ((r = enter(b)) < 0) return r;
     return launch_batch_disparity(b);
@@ -1085,7 +1139,7 @@ extern "C" int viso_batch_run_disparity(viso_batch* b) {
 
 static int get_disparity(viso_batch* b, bool all, int t, int16_t* out, const char* where) {
     if (dead(b) || (!all && (t < 0 || t >= b->nf)) || !out) { viso_set_error("%s: bad argument", where); return VISO_ERR_ARG; }
-    if (!b->disp_on || !b->disp_last) { viso_set_error("%s: dense disparity is off, or no run has computed it", where); return VISO_ERR_ARG; }
+    if (!(b->disp_on || b->sgm_on) || !b->disp_last) { viso_set_error("%s: dense disparity is off, or no run has computed it", where); return VISO_ERR_ARG; }
     { const int rs_ = batch_sync(b); if (rs_ < 0) return rs_; }
     const size_t per = (size_t)b->disp_rows * b->disp_cols;
     HIP_TRY(hipMemcpy(out, b->disp + (all ? 0 : (size_t)t * per), sizeof(int16_t) * per * (all ? (size_t)b->nf : 1), hipMemcpyDeviceToHost));

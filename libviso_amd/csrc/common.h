@@ -455,6 +455,15 @@ bool disparity_params_ok(const viso_disparity_params* p);
 bool disparity_geometry_ok(int rows, int cols);   // cols within what the kernel handles
 int launch_disparity(hipStream_t s, const uint8_t* img, size_t fs, size_t ss, int rows, int cols, int n_frames,
                      const viso_disparity_params* p, int16_t* out, size_t ofs);
+// sgm.hip: the opt-in semi-global matching (viso_batch_set_sgm); images and maps addressed as in launch_disparity.  The frames go
+// through the workspace ws in groups of `group` (>= 1) frames: ws holds group * sgm_frame_bytes.  sgm_group_frames: how many of
+// n_frames frames fit the workspace cap (0: not even one)
+bool sgm_params_ok(const viso_sgm_params* p);
+size_t sgm_frame_bytes(int rows, int cols, int D);
+int sgm_group_frames(int rows, int cols, int D, int n_frames);
+int sgm_nomem(const char* where, int rows, int cols, int D);   // sets the error text; returns VISO_ERR_NOMEM
+int launch_sgm(hipStream_t s, const uint8_t* img, size_t fs, size_t ss, int rows, int cols, int n_frames, const viso_sgm_params* p,
+               int16_t* out, size_t ofs, void* ws, int group);
 // covariance.hip: the opt-in motion covariance (viso_batch_set_covariance); one record per item, out[item], read from the item's
 // X, obs, m_ptr, ld, tr, ok, n_inl, inl (what ransac_refit_kernel left)
 int launch_motion_cov(hipStream_t s, const SolverItem* items_dev, int n_items, const SolverParamsDev& sp, int mode, double sigma,

@@ -339,7 +339,23 @@ extern "C" int viso_kitti_set_disparity(const char* dir, const viso_disparity_pa
     viso::mkdirs(dir);
     struct stat st;
     if (::stat(dir, &st) != 0 || !S_ISDIR(st.st_mode)) { g_host_err = std::string("viso_kitti_set_disparity: cannot create ") + dir; return VISO_ERR_ARG; }
-    g_disp.dir = dir; g_disp.params = p; g_disp.write_first = true; g_disp_on = true;
+    g_disp.dir = dir; g_disp.params = p; g_disp.write_first = true; g_disp.sgm = false; g_disp_on = true;
+    return VISO_OK;
+}
+
+extern "C" int viso_kitti_set_sgm(const char* dir, const viso_sgm_params* params) {
+    if (!dir || !*dir) { g_disp_on = false; return VISO_OK; }
+    viso_sgm_params p;
+    viso_sgm_params_default(&p);
+    if (params) p = *params;
+    const bool ok = p.num_disp >= 16 && p.num_disp <= 256 && p.num_disp % 16 == 0 && p.p1 >= 1 && p.p1 <= p.p2 && p.p2 <= 192 &&
+                    (p.paths == 4 || p.paths == 8) && p.uniqueness >= 0 && p.uniqueness <= 100 && p.lr_max_diff >= -1 &&
+                    p.lr_max_diff <= p.num_disp;
+    if (!ok) { g_host_err = "viso_kitti_set_sgm: parameters outside the ranges of include/viso_hip.h"; return VISO_ERR_ARG; }
+    viso::mkdirs(dir);
+    struct stat st;
+    if (::stat(dir, &st) != 0 || !S_ISDIR(st.st_mode)) { g_host_err = std::string("viso_kitti_set_sgm: cannot create ") + dir; return VISO_ERR_ARG; }
+    g_disp.dir = dir; g_disp.sgm_params = p; g_disp.write_first = true; g_disp.sgm = true; g_disp_on = true;
     return VISO_OK;
 }
 

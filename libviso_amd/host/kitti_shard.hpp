@@ -117,6 +117,9 @@ int viso_kitti_write_covariances(const char* file_name, const viso_motion_cov* r
 // dir/%06d.png (the directory is created); dir null or "" = off.  params null = viso_disparity_params_default.  VISO_ERR_ARG for
 // invalid parameters or a directory that cannot be created.
 int viso_kitti_set_disparity(const char* dir, const viso_disparity_params* params);
+// the same maps by semi-global matching (viso_batch_set_sgm): same directory, names and ownership of halo frames; the last of the
+// two calls decides the method.  params null = viso_sgm_params_default
+int viso_kitti_set_sgm(const char* dir, const viso_sgm_params* params);
 // One disparity map (int16 rows x cols, 1/16 px, VISO_DISP_INVALID = -16) as KITTI's stereo PNG: 16-bit grayscale, value =
 // 16 * disp16 (disparity = value / 256), 0 = invalid.  A valid disparity of 0 px is written as 0 as well: the format cannot tell it
 // from invalid.  zlib stored blocks (no compression: about 0.93 MB at 1241 x 376), Adler-32 and CRC-32 computed here; written under

@@ -270,6 +270,8 @@ struct DisparityOutput {
     std::string dir;
     viso_disparity_params params{};
     bool write_first = true;
+    bool sgm = false;                 // the maps by semi-global matching (viso_batch_set_sgm with sgm_params) instead
+    viso_sgm_params sgm_params{};
 };
 
 // sequence_odometry(P1, P2, images, dbg_dir), src/viso.h:138-139 / src/viso.cpp:1167-1330, without the

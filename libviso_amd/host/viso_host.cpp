@@ -867,7 +867,13 @@ OdometryResult sequence_odometry(const Matd& P1, const Matd& P2, StereoImageGene
         if (r >= 0) r = viso_batch_set_params(b, &st, &tm, &vp, ransac_seed, first_frame_index + (uint64_t)global0);
         if (r >= 0) r = viso_batch_set_subpixel(b, subpixel);
         if (r >= 0 && cov_mode) r = viso_batch_set_covariance(b, cov_mode, cov_sigma);
-        if (r >= 0) r = viso_batch_set_disparity(b, disp ? &disp->params : nullptr);
+        if (r >= 0 && disp && disp->sgm) {   // one method at a time: the other one off first
+            r = viso_batch_set_disparity(b, nullptr);
+            if (r >= 0) r = viso_batch_set_sgm(b, &disp->sgm_params);
+        } else if (r >= 0) {
+            r = viso_batch_set_sgm(b, nullptr);
+            if (r >= 0) r = viso_batch_set_disparity(b, disp ? &disp->params : nullptr);
+        }
         if (r >= 0) r = viso_batch_stamp(b, 0);
         if (r >= 0) r = viso_batch_upload_images_async(b, 0, nf, pin, rows, cols, nullptr, nullptr);
         if (r >= 0) r = viso_batch_stamp(b, 1);

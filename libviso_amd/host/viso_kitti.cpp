@@ -34,6 +34,10 @@
 //                       byte-identical for every chunk size, W and partition.  Pose files are unchanged.  Not in the reference
 //   --disparity-params D,B,c,T,u,m  with --disparity: num_disp, block, prefilter_cap, texture_threshold, uniqueness,
 //                       lr_max_diff (default 128,11,31,10,15,1)
+//   --disparity-method bm|sgm  with --disparity: bm (the default) is the block matcher; sgm computes the same files by semi-global
+//                       matching (viso_batch_set_sgm), with the same names, format and halo ownership
+//   --sgm-params D,P1,P2,paths,u,m  with --disparity-method sgm: num_disp, p1, p2, paths, uniqueness, lr_max_diff (default
+//                       128,10,120,8,10,1)
 // Every rank reports where its wall time went: decode (PNG inflate on the worker threads; the calling thread's wait for
 // it is the runner's critical path), upload and GPU seconds from time stamps on the device.
 // libviso_amd/kitti_shard.py is the same runner with the gather as an RCCL all-gather (torch.distributed).
@@ -68,6 +72,9 @@ struct Args {
     std::string disparity;    // --disparity dir ("" = off)
     bool disp_params_given = false;
     viso_disparity_params disp{};   // --disparity-params (defaults otherwise)
+    bool method_given = false, sgm = false;   // --disparity-method
+    bool sgm_params_given = false;
+    viso_sgm_params sgmp{};         // --sgm-params (defaults otherwise)
 };
 
 bool parse(int argc, char** argv, Args& a) {
@@ -95,6 +102,20 @@ bool parse(int argc, char** argv, Args& a) {
                             &p.uniqueness, &p.lr_max_diff, &tail) != 6) return false;
             a.disp_params_given = true;
         }
+        else if (s == "--disparity-method") {
+            if (i + 1 >= argc) return false;
+            const std::string m = argv[++i];
+            if (m != "bm" && m != "sgm") return false;
+            a.method_given = true; a.sgm = m == "sgm";
+        }
+        else if (s == "--sgm-params") {
+            if (i + 1 >= argc) return false;
+            viso_sgm_params& p = a.sgmp;
+            char tail = 0;
+            if (std::sscanf(argv[++i], "%d,%d,%d,%d,%d,%d%c", &p.num_disp, &p.p1, &p.p2, &p.paths, &p.uniqueness, &p.lr_max_diff,
+                            &tail) != 6) return false;
+            a.sgm_params_given = true;
+        }
         else if (s == "--covariance-sigma") {
             if (i + 1 >= argc) return false;
             char* e = nullptr;
@@ -118,6 +139,9 @@ bool parse(int argc, char** argv, Args& a) {
     if (a.rank >= a.world && a.world > 0) return false;
     if (a.cov_sigma > 0.0 && a.covariance.empty()) return false;   // --covariance-sigma belongs to --covariance
     if (a.disp_params_given && a.disparity.empty()) return false;    // --disparity-params belongs to --disparity
+    if (a.method_given && a.disparity.empty()) return false;         // and so does --disparity-method
+    if (a.sgm_params_given && !a.sgm) return false;                  // --sgm-params belongs to --disparity-method sgm
+    if (a.disp_params_given && a.sgm) return false;                  // --disparity-params to the block matcher
     return true;
 }
 
@@ -153,7 +177,8 @@ int main(int argc, char** argv) {
     if (!parse(argc, argv, a)) {
         std::printf("usage: demo result_sha seq_name begin end [--gpus W | --rank r --world W | --gather W] "
                     "[--device d] [--same-device] [--chunk n] [--seed s] [--decode-threads n] [--reference-pose-list] [--subpixel 0|1|2] [--rectify calib_cam_to_cam.txt] "
-                    "[--covariance file [--covariance-sigma s]] [--disparity dir [--disparity-params D,B,c,T,u,m]]\n");   // :81-85
+                    "[--covariance file [--covariance-sigma s]] [--disparity dir [--disparity-params D,B,c,T,u,m] "
+                    "[--disparity-method bm|sgm [--sgm-params D,P1,P2,paths,u,m]]]\n");   // :81-85
         return 1;
     }
     const char* home = std::getenv("KITTI_HOME");                                              // :96
@@ -176,11 +201,16 @@ int main(int argc, char** argv) {
     viso::DisparityOutput disp;   // --disparity: checked (and its directory made) here, before any rank is forked
     const viso::DisparityOutput* dispp = nullptr;
     if (!a.disparity.empty()) {
-        if (viso_kitti_set_disparity(a.disparity.c_str(), a.disp_params_given ? &a.disp : nullptr) != VISO_OK) {
+        const int ok = a.sgm ? viso_kitti_set_sgm(a.disparity.c_str(), a.sgm_params_given ? &a.sgmp : nullptr)
+                             : viso_kitti_set_disparity(a.disparity.c_str(), a.disp_params_given ? &a.disp : nullptr);
+        if (ok != VISO_OK) {
             std::fprintf(stderr, "%s\n", viso_host_last_error());
             return 2;
         }
         disp.dir = a.disparity;
+        disp.sgm = a.sgm;
+        if (a.sgm_params_given) disp.sgm_params = a.sgmp;
+        else viso_sgm_params_default(&disp.sgm_params);
         if (a.disp_params_given) disp.params = a.disp;
         else viso_disparity_params_default(&disp.params);
         dispp = &disp;

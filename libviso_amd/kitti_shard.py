@@ -72,6 +72,8 @@ def load_host():
     L.viso_kitti_set_rectify.argtypes = [C.c_char_p]
     L.viso_kitti_set_covariance.argtypes = [C.c_int, C.c_double]
     L.viso_kitti_set_disparity.argtypes = [C.c_char_p, C.c_void_p]
+    if hasattr(L, "viso_kitti_set_sgm"):
+        L.viso_kitti_set_sgm.argtypes = [C.c_char_p, C.c_void_p]
     L.viso_write_disparity_png.argtypes = [C.c_char_p, C.POINTER(C.c_int16), C.c_int, C.c_int]
     L.viso_kitti_last_covariances.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     L.viso_kitti_write_covariances.argtypes = [C.c_char_p, C.c_void_p, C.c_int]
@@ -276,6 +278,10 @@ def main(argv=None):
     ap.add_argument("--disparity-params", default=None, metavar="D,B,c,T,u,m",
                     help="with --disparity: num_disp, block, prefilter_cap, texture_threshold, uniqueness, lr_max_diff "
                          "(default 128,11,31,10,15,1)")
+    ap.add_argument("--disparity-method", default=None, choices=("bm", "sgm"),
+                    help="with --disparity: bm (default) = the block matcher, sgm = semi-global matching; same files, names and format")
+    ap.add_argument("--sgm-params", default=None, metavar="D,P1,P2,paths,u,m",
+                    help="with --disparity-method sgm: num_disp, p1, p2, paths, uniqueness, lr_max_diff (default 128,10,120,8,10,1)")
     args = ap.parse_args(argv)
     if args.covariance_sigma is not None and args.covariance is None:
         ap.error("--covariance-sigma needs --covariance")
@@ -291,6 +297,23 @@ def main(argv=None):
             ap.error("--disparity-params takes six integers D,B,c,T,u,m")
         from .abi import DisparityParams
         disp_params = DisparityParams(*vals)
+    if args.disparity_method is not None and args.disparity is None:
+        ap.error("--disparity-method needs --disparity")
+    use_sgm = args.disparity_method == "sgm"
+    if args.sgm_params is not None and not use_sgm:
+        ap.error("--sgm-params needs --disparity-method sgm")
+    if use_sgm and args.disparity_params is not None:
+        ap.error("--disparity-params belongs to --disparity-method bm")
+    sgm_params = None
+    if args.sgm_params is not None:
+        try:
+            vals = [int(v) for v in args.sgm_params.split(",")]
+        except ValueError:
+            vals = []
+        if len(vals) != 6:
+            ap.error("--sgm-params takes six integers D,P1,P2,paths,u,m")
+        from .abi import SgmParams
+        sgm_params = SgmParams(*vals)
     home = os.environ.get("KITTI_HOME")
     if not home:
         print("KITTI_HOME is not set", file=sys.stderr)
@@ -345,7 +368,12 @@ def main(argv=None):
             print(f"kitti_shard: {L.viso_host_last_error().decode()}", file=sys.stderr)
             return 2
 
-    if args.disparity is not None and L.viso_kitti_set_disparity(
+    if args.disparity is not None and use_sgm:
+        if L.viso_kitti_set_sgm(os.fsencode(os.path.abspath(args.disparity)),
+                                C.addressof(sgm_params) if sgm_params is not None else None) != 1:
+            print(f"kitti_shard: {L.viso_host_last_error().decode()}", file=sys.stderr)
+            return 2
+    elif args.disparity is not None and L.viso_kitti_set_disparity(
             os.fsencode(os.path.abspath(args.disparity)), C.addressof(disp_params) if disp_params is not None else None) != 1:
         print(f"kitti_shard: {L.viso_host_last_error().decode()}", file=sys.stderr)
         return 2
