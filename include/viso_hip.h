@@ -704,7 +704,7 @@ int viso_window_refine(int len, const int* m, const double* X, const double* obs
  *      depend on an order); invalid if |dR(x - d*, y) - d*| > m.
  *   9. Output int16 [rows][cols]: disp16 for valid pixels, VISO_DISP_INVALID (-16, StereoBM's value for a minimum disparity of 0)
  *      otherwise.
- * Out of scope: a negative minimum disparity, the speckle filter, SGM.
+ * Out of scope: a negative minimum disparity.  SGM and the speckle filter are stages of their own (the next two sections).
  * One HIP kernel (stereo_disparity_kernel, one launch per batch) computes every frame of a call: one workgroup per row and
  * frame, the cost volume never written to memory.  This build handles cols <= 2048 (VISO_ERR_UNSUPPORTED beyond). */
 #define VISO_DISP_INVALID (-16)
@@ -761,7 +761,8 @@ int viso_batch_get_disparities(viso_batch* b, int16_t* out /* [n_frames][rows][c
  *      off = k ? ((n - p) 256) / k : 0 (C division), disp16 = (256 d* + off + 8) >> 4; left-right check (m >= 0): dR(xr, y) = the
  *      smallest d in [0, D-1] with xr + d < cols that minimises S(xr + d, y, d), over every pixel, valid or not; invalid if
  *      |dR(x - d*, y) - d*| > m.  Output int16 [rows][cols]: disp16, or VISO_DISP_INVALID.
- * Out of scope: a negative minimum disparity, the speckle filter, OpenCV's SGBM cost (Birchfield-Tomasi), more than 8 paths.
+ * Out of scope: a negative minimum disparity, OpenCV's SGBM cost (Birchfield-Tomasi), more than 8 paths.  The speckle filter is a
+ * stage of its own (the next section).
  * HIP kernels (sgm.hip): census words, one launch per path direction over S [rows][cols][D] u16 in device memory, one selection
  * launch.  This build handles cols <= 2048 (VISO_ERR_UNSUPPORTED beyond). */
 typedef struct viso_sgm_params {
@@ -790,6 +791,66 @@ int viso_stereo_sgm(const uint8_t* left, const uint8_t* right, int rows, int col
 int viso_batch_set_sgm(viso_batch* b, const viso_sgm_params* params);
 /* The workspace cap in bytes of every later SGM launch of the process (0: the default, 2 GiB). */
 void viso_sgm_set_workspace_cap(size_t bytes);
+
+/* ------------------------------------------------ speckle filter and 3-D reprojection of the maps (opt-in; NOT in the reference)
+ *
+ * The last stage of both methods above, in the form of OpenCV's filterSpeckles with newVal = the invalid value.  Parity with OpenCV
+ * is not pinned (it is not a dependency); this definition is the contract, and the device output is bit-identical to it (it is
+ * stated through components, so it depends on no traversal order).
+ * Input: an int16 map [rows][cols] in the format above (1/16 px, VISO_DISP_INVALID for invalid).  Parameters S = max_size >= 0
+ * (pixels) and Delta = max_diff in 0..4096 (map units, 1/16 px; 4096 is 256 px).  Any other value gives VISO_ERR_ARG.
+ *   1. Pixels equal to VISO_DISP_INVALID belong to no component and stay as they are.
+ *   2. Two valid pixels that are 4-neighbours are linked when |d(p) - d(q)| <= Delta.  The relation is symmetric.
+ *   3. The components are the connected components of that graph over the whole image (not per tile, not per row).
+ *   4. Every pixel of a component with at most S pixels becomes VISO_DISP_INVALID.  Every other pixel keeps its value.
+ * S = 0 changes nothing and is valid (nothing is launched).
+ * Out of scope: 8-connectivity, a median or hole-filling filter.
+ * HIP kernels (speckle.hip): union-find over linear pixel indices: 64 x 16 tiles in LDS, the tile borders joined in device memory
+ * by atomicMin on the larger root, a flatten-and-count pass (integer atomics, one per tile and component), the removal.  Four
+ * launches for all frames of a group; no launch count or pass count depends on the shape of a component.  Workspace: 8 bytes a
+ * pixel.  This build handles cols <= 2048 and rows cols < 2^31 (VISO_ERR_UNSUPPORTED beyond). */
+typedef struct viso_speckle_params {
+    int32_t max_size;   /* S, pixels */
+    int32_t max_diff;   /* Delta, 1/16 px */
+} viso_speckle_params;
+
+/* S = 100, Delta = 16 (1 px).  Host only. */
+void viso_speckle_params_default(viso_speckle_params* p);
+/* Host pointer, default context, in place.  The arguments are checked before any device is touched: VISO_ERR_ARG for a null map,
+ * sizes <= 0 or invalid parameters; VISO_ERR_UNSUPPORTED for cols > 2048; VISO_ERR_NOMEM when the workspace cap cannot hold one
+ * frame. */
+int viso_filter_speckles(int16_t* map, int rows, int cols, const viso_speckle_params* params);
+/* Turn the filter on with a copy of *params (off with NULL, the default).  While on, the batch's dense stage
+ * (viso_batch_run_images, also with matcher_only, and viso_batch_run_disparity) filters its map buffer in place right after the
+ * method's last kernel, for block matching and for SGM alike, and viso_batch_get_disparity(ies) serve the filtered maps; every other
+ * output is unchanged, and it stays outside the run's time stamps.  It may be set while no method is on: it then does nothing until
+ * one is.  With it off nothing new is launched or allocated.  The frames are processed in groups whose label and size words fit the
+ * workspace cap; the workspace is allocated by the first launch and freed with the batch, and the maps are the same for every group
+ * size.  A run returns VISO_ERR_NOMEM when the cap cannot hold one frame, and the batch stays usable.  VISO_ERR_ARG: invalid
+ * parameters, a dead handle. */
+int viso_batch_set_speckle(viso_batch* b, const viso_speckle_params* params);
+/* The workspace cap in bytes of every later speckle launch of the process (0: the default, 2 GiB). */
+void viso_speckle_set_workspace_cap(size_t bytes);
+
+/* Reprojection of a map to an organised point image out [rows][cols][3] float32 (the form of OpenCV's reprojectImageTo3D), with
+ * the calibration f, cu, cv, base of *param and an optional pose T (4 x 4 row-major double, the first three rows are read; NULL =
+ * identity, applied as no transform at all):
+ *   - a pixel (x, y) is used when disp16 != VISO_DISP_INVALID and disp16 >= min_disp16 (min_disp16 >= 1, so a disparity of 0 never
+ *     divides); every other pixel gets three NaNs;
+ *   - in double: d = disp16 / 16, X = base (x - cu) / d, Y = base (y - cv) / d, Z = f base / d (the products first, then the
+ *     division: the operand order of the sparse triangulation);
+ *   - with a pose: P_i = ((T[i][0] X + T[i][1] Y) + T[i][2] Z) + T[i][3], i = 0..2, in double, in exactly that association, with
+ *     no fused multiply-add;
+ *   - then each coordinate is rounded once to float32.
+ * Host pointers, default context; the arguments are checked before any device is touched (VISO_ERR_ARG: a null map, calibration or
+ * output, sizes <= 0, min_disp16 < 1). */
+int viso_disparity_to_points(const int16_t* disp, int rows, int cols, const viso_param* param, const double* pose_or_null,
+                             int min_disp16, float* out);
+/* The same over frame t's resident map of the batch (the filtered one while the speckle filter is on), with the calibration of
+ * viso_batch_set_params: the kernel is launched on demand and the points copied out; the batch keeps no point buffer.
+ * (viso_batch_get_points, the older call above, returns the solver's sparse inputs; hence the longer name.)  VISO_ERR_ARG when
+ * disparity is off, no run has computed it, or the batch's parameters are not set. */
+int viso_batch_get_disparity_points(viso_batch* b, int t, const double* pose_or_null, int min_disp16, float* out);
 
 #ifdef __cplusplus
 }

@@ -16,9 +16,9 @@ import weakref
 
 import numpy as np
 
-from .abi import (DESC_LEN, MOTION_COV_DTYPE, MOTION_REFINE_DTYPE, SGM_DEFAULTS, WINDOW_RECORD_DTYPE, DisparityParams, MatchParams,
-                  Param, SgmParams, declare_common, declare_covariance, declare_disparity, declare_refine, declare_rectify,
-                  declare_sgm, declare_subpixel, declare_window, f32p, f64p, i32p, i64p, intp, ptr)
+from .abi import (DESC_LEN, MOTION_COV_DTYPE, MOTION_REFINE_DTYPE, SGM_DEFAULTS, SPECKLE_DEFAULTS, WINDOW_RECORD_DTYPE, DisparityParams, MatchParams,
+                  Param, SgmParams, SpeckleParams, declare_common, declare_covariance, declare_disparity, declare_refine, declare_rectify,
+                  declare_sgm, declare_speckle, declare_subpixel, declare_window, f32p, f64p, i32p, i64p, intp, ptr)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("VISO_HIP_SO") or os.path.join(_HERE, "libviso_hip.so")   # VISO_HIP_SO: another build of the library (A/B runs)
@@ -128,6 +128,8 @@ def load():
         declare_disparity(L)
     if hasattr(L, "viso_batch_set_sgm"):
         declare_sgm(L)
+    if hasattr(L, "viso_batch_set_speckle"):
+        declare_speckle(L)
     L.viso_harris_response.argtypes = [C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_double, f32p]
     L.viso_detect_harris_binned.argtypes = [C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                             C.c_double, f32p, f32p, intp]
@@ -529,6 +531,72 @@ def sgm_frame_bytes(rows, cols, num_disp=128):
     return up(rows * cols * 16) + up(rows * cols * num_disp * 2)
 
 
+def speckle_params(**params):
+    """viso_speckle_params: viso_speckle_params_default with the given fields (max_size in pixels, max_diff in 1/16 px) replaced.
+    Needs no library: the ranges are checked by the calls that take it (SpeckleParams.ok restates them)."""
+    p = SpeckleParams(**SPECKLE_DEFAULTS)
+    for k, v in params.items():
+        if k not in SPECKLE_DEFAULTS:
+            raise TypeError(f"speckle_params: unknown parameter {k!r}")
+        setattr(p, k, int(v))
+    return p
+
+
+def filter_speckles(d16, **params):
+    """viso_filter_speckles: a copy of the int16 map with every 4-connected component of at most max_size pixels (neighbours linked
+    when they differ by at most max_diff) set to DISP_INVALID (opt-in, not in the reference; the definition of include/viso_hip.h),
+    on the device."""
+    d16 = np.asarray(d16)
+    if d16.ndim != 2 or d16.dtype != np.int16:
+        raise ValueError("filter_speckles: the map must be a 2-D int16 array")
+    out = np.array(d16, dtype=np.int16, order="C", copy=True)
+    p = speckle_params(**params)
+    r = load().viso_filter_speckles(ptr(out, C.c_int16), out.shape[0], out.shape[1], C.byref(p))
+    if r != 1:
+        _err("viso_filter_speckles", r)
+    return out
+
+
+def speckle_set_workspace_cap(nbytes):
+    """viso_speckle_set_workspace_cap: the bytes of label and size words one group of frames may take (0: the default)."""
+    load().viso_speckle_set_workspace_cap(int(nbytes))
+
+
+def speckle_frame_bytes(rows, cols):
+    """The workspace of one frame: a label word and a size word per pixel, each plane rounded up to 256 bytes."""
+    return 2 * ((rows * cols * 4 + 255) & ~255)
+
+
+def _pose_arg(where, pose):
+    """A pose for the reprojection: None, or a 4 x 4 (or 3 x 4) matrix as contiguous float64 (the first three rows are read)."""
+    if pose is None:
+        return None, None
+    T = np.ascontiguousarray(pose, dtype=np.float64)
+    if T.shape not in ((4, 4), (3, 4)):
+        raise ValueError(f"{where}: the pose must be a 4 x 4 (or 3 x 4) matrix")
+    return T, ptr(T, C.c_double)
+
+
+def disparity_to_points(d16, param, pose=None, min_disp16=1):
+    """viso_disparity_to_points: the int16 map as an organised point image float32 [rows][cols][3] (X, Y, Z in the left camera's
+    frame, or transformed by the 4 x 4 pose), three NaNs where the pixel is invalid or its disparity is below min_disp16 (1/16 px).
+    param: a Param (f, cu, cv, base).  A point set is `P[np.isfinite(P[..., 2])]`.  With a trajectory:
+
+        poses, valid = hostmath.chain_poses(tr, ok)      # poses[k + 1] places frame valid[k] in frame 0's coordinates
+        P = disparity_to_points(batch.disparity(valid[k]), param, pose=poses[k + 1])
+    """
+    d16 = np.ascontiguousarray(d16)
+    if d16.ndim != 2 or d16.dtype != np.int16:
+        raise ValueError("disparity_to_points: the map must be a 2-D int16 array")
+    T, Tp = _pose_arg("disparity_to_points", pose)
+    out = np.empty(d16.shape + (3,), np.float32)
+    r = load().viso_disparity_to_points(ptr(d16, C.c_int16), d16.shape[0], d16.shape[1], C.byref(param), Tp, int(min_disp16),
+                                        ptr(out, C.c_float))
+    if r != 1:
+        _err("viso_disparity_to_points", r)
+    return out
+
+
 def disparity_to_float(d16):
     """float32 disparity in pixels (d16 / 16), NaN where invalid."""
     d16 = np.asarray(d16)
@@ -854,6 +922,37 @@ class Batch:
         else:
             params = sgm_params(**dict(params or {}, **kw))
         self._chk("viso_batch_set_sgm", self.L.viso_batch_set_sgm(self.h, C.byref(params)))
+
+    def set_speckle(self, params=None, **kw):
+        """viso_batch_set_speckle: the speckle filter over the batch's maps, right behind whichever method is on (set_disparity or
+        set_sgm), in the next image-in runs and in run_disparity; disparity / disparities serve the filtered maps.  params: a
+        SpeckleParams, a dict of its fields, or keyword fields (defaults for the rest); set_speckle(None) turns it off (the
+        default).  With no method on it does nothing."""
+        if params is None and not kw:
+            self._chk("viso_batch_set_speckle", self.L.viso_batch_set_speckle(self.h, None))
+            return
+        if isinstance(params, SpeckleParams):
+            if kw:
+                raise TypeError("set_speckle: keyword fields cannot be combined with a SpeckleParams")
+        else:
+            params = speckle_params(**dict(params or {}, **kw))
+        self._chk("viso_batch_set_speckle", self.L.viso_batch_set_speckle(self.h, C.byref(params)))
+
+    def disparity_points(self, t, pose=None, min_disp16=1):
+        """viso_batch_get_disparity_points: frame t's resident map as an organised point image float32 [rows][cols][3], with the
+        batch's calibration (set_params) and an optional 4 x 4 pose; NaNs where the pixel is invalid or below min_disp16.  Equal to
+        disparity_to_points(self.disparity(t), param, pose, min_disp16).  (Batch.points is the older call for the solver's sparse
+        inputs.)  With the run's trajectory:
+
+            tr, ok, _ = batch.poses()
+            poses, valid = hostmath.chain_poses(tr, ok)      # poses[k + 1] places frame valid[k] in frame 0's coordinates
+            P = batch.disparity_points(valid[k], pose=poses[k + 1])
+        """
+        T, Tp = _pose_arg("Batch.disparity_points", pose)
+        out = np.empty(tuple(self.image_shape()) + (3,), np.float32)
+        self._chk("viso_batch_get_disparity_points",
+                  self.L.viso_batch_get_disparity_points(self.h, int(t), Tp, int(min_disp16), ptr(out, C.c_float)))
+        return out
 
     def run_disparity(self):
         """viso_batch_run_disparity: only the disparity, over the resident images (upload_images_only)."""

@@ -187,6 +187,31 @@ def declare_sgm(lib):
     lib.viso_sgm_set_workspace_cap.argtypes = [C.c_size_t]
 
 
+class SpeckleParams(C.Structure):
+    """struct viso_speckle_params (include/viso_hip.h, "speckle filter and 3-D reprojection of the maps")."""
+    _fields_ = [(name, C.c_int32) for name in ("max_size", "max_diff")]
+
+    def ok(self):
+        """The valid ranges of include/viso_hip.h (what the library checks before it touches a device)."""
+        return self.max_size >= 0 and 0 <= self.max_diff <= 4096
+
+
+SPECKLE_DEFAULTS = dict(max_size=100, max_diff=16)   # viso_speckle_params_default
+
+
+def declare_speckle(lib):
+    """Prototypes of the opt-in speckle filter and reprojection (include/viso_hip.h; libviso_hip.so only)."""
+    i16p, KP = C.POINTER(C.c_int16), C.POINTER(SpeckleParams)
+    lib.viso_speckle_params_default.restype = None
+    lib.viso_speckle_params_default.argtypes = [KP]
+    lib.viso_filter_speckles.argtypes = [i16p, C.c_int, C.c_int, KP]
+    lib.viso_batch_set_speckle.argtypes = [C.c_void_p, KP]
+    lib.viso_speckle_set_workspace_cap.restype = None
+    lib.viso_speckle_set_workspace_cap.argtypes = [C.c_size_t]
+    lib.viso_disparity_to_points.argtypes = [i16p, C.c_int, C.c_int, C.POINTER(Param), f64p, C.c_int, f32p]
+    lib.viso_batch_get_disparity_points.argtypes = [C.c_void_p, C.c_int, f64p, C.c_int, f32p]
+
+
 class MotionCov(C.Structure):
     """struct viso_motion_cov (include/viso_hip.h, "motion covariance")."""
     _fields_ = [

@@ -13,6 +13,7 @@
 //   raw [nf][2][raw_rows][raw_cols] u8   staged raw images the remap reads into `images` (viso_batch_set_rectify only)
 //   disp [nf][img_rows][img_cols] i16    dense disparity of every frame's resident pair (viso_batch_set_disparity / _set_sgm only)
 //   sgm_ws                               census words and S volumes of one group of frames (viso_batch_set_sgm only; sgm.hip)
+//   spk_ws                               label and size words of one group of frames (viso_batch_set_speckle only; speckle.hip)
 // `which` = 0 stereo L->R of frame t, 1 temporal left (t vs t-1), 2 temporal right.
 #include "common.h"
 
@@ -51,6 +52,9 @@ struct viso_batch {
     // opt-in semi-global matching (sgm.hip): on while sgm_on (never together with disp_on: the maps are one buffer, `disp`); the
     // parameters and the workspace of one group of frames (allocated by the first launch, again when a launch needs another size)
     bool sgm_on = false; viso_sgm_params sgm_p = {}; void* sgm_ws = nullptr; size_t sgm_ws_bytes = 0;
+    // opt-in speckle filter of the maps (speckle.hip): on while spk_on, behind either method's selection kernel; the parameters and
+    // the workspace of one group of frames (allocated by the first launch, again when a launch needs another size)
+    bool spk_on = false; viso_speckle_params spk_p = {}; void* spk_ws = nullptr; size_t spk_ws_bytes = 0;
     // opt-in motion covariance (covariance.hip): the mode and sigma asked for, the records [nf] (allocated on the first request,
     // frame 0 stays zero: status 0), and the mode the last run computed them with (0: the last run computed none)
     int cov_mode = 0; double cov_sigma = 0.0; viso_motion_cov* cov = nullptr; int cov_last = 0;
@@ -189,7 +193,7 @@ int viso_batch_free(viso_batch* b, bool keep_shell) {
     void* ptrs[] = {b->h_part, b->h_resp, b->h_tmp_kp, b->h_tmp_resp, b->h_cnt, b->images, b->skp, b->sidx, b->rank, b->bstart, b->xinfo, b->views,
                     b->kp, b->desc, b->n, b->packed, b->packed8, b->r8cnt, b->sums, b->zero, b->probs, b->res, b->sorted,
                     b->pos, b->m_cnt, b->scored, b->x_c, b->Xp_c, b->join,
-                    b->sitems, b->circ, b->pcl, b->mc, b->uv, b->cov, b->ref, b->ref_pts, b->ref_idx, b->win, b->win_lp, b->win_nlp, b->win_tab, b->win_trk, b->win_pts, b->rmap, b->raw, b->disp, b->sgm_ws, b->tr /* + ok, n_inl */, b->inl, b->tr_h, b->ok_h, b->cnt_h, b->hq, b->samp_h, b->rot, b->tile_flag, b->qord, b->ovf_q};
+                    b->sitems, b->circ, b->pcl, b->mc, b->uv, b->cov, b->ref, b->ref_pts, b->ref_idx, b->win, b->win_lp, b->win_nlp, b->win_tab, b->win_trk, b->win_pts, b->rmap, b->raw, b->disp, b->sgm_ws, b->spk_ws, b->tr /* + ok, n_inl */, b->inl, b->tr_h, b->ok_h, b->cnt_h, b->hq, b->samp_h, b->rot, b->tile_flag, b->qord, b->ovf_q};
     for (void* p : ptrs) if (p) note(hipFree(p));
     if (keep_shell) { b->ctx = nullptr; b->events.clear(); b->desc_family.clear(); b->desc_family.shrink_to_fit(); }
     else delete b;
@@ -584,6 +588,33 @@ extern "C" int viso_batch_kernel_timing(viso_batch* b, int enable) {
     return VISO_OK;
 }
 
+// The speckle filter over the batch's maps, in place, behind the method's launches on the context's stream (viso_batch_set_speckle
+// on with max_size > 0), group by group through the batch's workspace.
+static bool speckle_active(const viso_batch* b) { return b->spk_on && b->spk_p.max_size > 0; }
+
+static int launch_batch_speckle(viso_batch* b) {
+    const int group = speckle_group_frames(b->img_rows, b->img_cols, b->nf);
+    if (group < 1) return speckle_nomem("viso_batch_run", b->img_rows, b->img_cols);
+    const size_t want = speckle_frame_bytes(b->img_rows, b->img_cols) * (size_t)group;
+    if (b->spk_ws && b->spk_ws_bytes != want) {
+        int r;
+        if ((r = batch_sync(b)) < 0) return r;
+        HIP_TRY(hipFree(b->spk_ws));
+        b->spk_ws = nullptr;
+    }
+    if (!b->spk_ws) {
+        if (hipMalloc(&b->spk_ws, want) != hipSuccess) {
+            (void)hipGetLastError();
+            b->spk_ws = nullptr;
+            viso_set_error("viso_batch_run: cannot allocate the %zu-byte speckle workspace (viso_speckle_set_workspace_cap)", want);
+            return VISO_ERR_NOMEM;
+        }
+        b->spk_ws_bytes = want;
+    }
+    return launch_speckle(b->ctx->stream, b->disp, (size_t)b->img_rows * b->img_cols, b->img_rows, b->img_cols, b->nf, &b->spk_p,
+                          b->spk_ws, group);
+}
+
 // The disparity of every frame's resident pair on the context's stream (viso_batch_set_disparity on, images present, geometry
 // checked by the caller).  The maps' buffer follows the image geometry: (re)allocated here, after the batch's work in flight.
 static int launch_batch_disparity(viso_batch* b) {
@@ -622,11 +653,14 @@ static int launch_batch_disparity(viso_batch* b) {
         const int r = launch_sgm(b->ctx->stream, b->images, 2 * per, per, b->img_rows, b->img_cols, b->nf, &b->sgm_p, b->disp, per,
                                  b->sgm_ws, group);
         if (r < 0) return r;
-        b->disp_last = 1;
-        return VISO_OK;
+    } else {
+        const int r = launch_disparity(b->ctx->stream, b->images, 2 * per, per, b->img_rows, b->img_cols, b->nf, &b->disp_p, b->disp, per);
+        if (r < 0) return r;
     }
-    const int r = launch_disparity(b->ctx->stream, b->images, 2 * per, per, b->img_rows, b->img_cols, b->nf, &b->disp_p, b->disp, per);
-    if (r < 0) return r;
+    if (speckle_active(b)) {
+        const int r = launch_batch_speckle(b);
+        if (r < 0) return r;
+    }
     b->disp_last = 1;
     return VISO_OK;
 }
@@ -649,6 +683,12 @@ static int run_matcher_impl(viso_batch* b, bool from_images) {
     }
     if (from_images && b->sgm_on && sgm_group_frames(b->img_rows, b->img_cols, b->sgm_p.num_disp, b->nf) < 1)
         return sgm_nomem("viso_batch_run_images", b->img_rows, b->img_cols, b->sgm_p.num_disp);
+    if (from_images && (b->disp_on || b->sgm_on) && speckle_active(b) && !speckle_geometry_ok(b->img_rows, b->img_cols)) {
+        viso_set_error("viso_batch_run_images: the speckle filter of %d x %d maps is beyond this build (2^31 - 1 pixels)", b->img_rows, b->img_cols);
+        return VISO_ERR_UNSUPPORTED;
+    }
+    if (from_images && (b->disp_on || b->sgm_on) && speckle_active(b) && speckle_group_frames(b->img_rows, b->img_cols, b->nf) < 1)
+        return speckle_nomem("viso_batch_run_images", b->img_rows, b->img_cols);
     if (!from_images && b->subpix) {
         viso_set_error("viso_batch_run: sub-pixel refinement (viso_batch_set_subpixel %d) needs the images: use viso_batch_run_images, "
                        "or set mode 0 for descriptor-in runs", b->subpix);
@@ -1120,6 +1160,21 @@ extern "C" int viso_batch_set_sgm(viso_batch* b, const viso_sgm_params* params) 
     return VISO_OK;
 }
 
+// Opt-in speckle filter of the maps (not in the reference; speckle.hip): a stage behind whichever method is on.  Only the parameters
+// are kept here: the workspace is allocated by the first launch that needs it.  With no method on it does nothing.
+extern "C" int viso_batch_set_speckle(viso_batch* b, const viso_speckle_params* params) {
+    if (dead(b) || (params && !speckle_params_ok(params))) {
+        viso_set_error("viso_batch_set_speckle: bad argument (NULL, or the parameters of include/viso_hip.h)");
+        return VISO_ERR_ARG;
+    }
+    const bool same = b->spk_on == (params != nullptr) &&
+                      (!params || (b->spk_p.max_size == params->max_size && b->spk_p.max_diff == params->max_diff));
+    if (!same) b->disp_last = 0;   // maps of the other state are not this one's
+    b->spk_on = params != nullptr;
+    if (params) b->spk_p = *params;
+    return VISO_OK;
+}
+
 // Only the disparity, over images uploaded without keypoints.
 extern "C" int viso_batch_run_disparity(viso_batch* b) {
     if (dead(b) || !(b->disp_on || b->sgm_on) || !b->images) {
@@ -1132,6 +1187,12 @@ extern "C" int viso_batch_run_disparity(viso_batch* b) {
     }
     if (b->sgm_on && sgm_group_frames(b->img_rows, b->img_cols, b->sgm_p.num_disp, b->nf) < 1)
         return sgm_nomem("viso_batch_run_disparity", b->img_rows, b->img_cols, b->sgm_p.num_disp);
+    if (speckle_active(b) && !speckle_geometry_ok(b->img_rows, b->img_cols)) {
+        viso_set_error("viso_batch_run_disparity: the speckle filter of %d x %d maps is beyond this build (2^31 - 1 pixels)", b->img_rows, b->img_cols);
+        return VISO_ERR_UNSUPPORTED;
+    }
+    if (speckle_active(b) && speckle_group_frames(b->img_rows, b->img_cols, b->nf) < 1)
+        return speckle_nomem("viso_batch_run_disparity", b->img_rows, b->img_cols);
     int r;
     if ((r = enter(b)) < 0) return r;
     return launch_batch_disparity(b);
@@ -1149,6 +1210,35 @@ static int get_disparity(viso_batch* b, bool all, int t, int16_t* out, const cha
 extern "C" int viso_batch_get_disparity(viso_batch* b, int t, int16_t* out) { return get_disparity(b, false, t, out, "viso_batch_get_disparity"); }
 
 extern "C" int viso_batch_get_disparities(viso_batch* b, int16_t* out) { return get_disparity(b, true, 0, out, "viso_batch_get_disparities"); }
+
+// Frame t's resident map as an organised point image [rows][cols][3] f32 (speckle.hip), computed on demand with the batch's
+// calibration; the batch keeps no point buffer.
+extern "C" int viso_batch_get_disparity_points(viso_batch* b, int t, const double* pose_or_null, int min_disp16, float* out) {
+    const char* where = "viso_batch_get_disparity_points";
+    if (dead(b) || t < 0 || t >= b->nf || !out || min_disp16 < 1) { viso_set_error("%s: bad argument", where); return VISO_ERR_ARG; }
+    if (!b->params_set) { viso_set_error("%s: parameters not set (the calibration comes from viso_batch_set_params)", where); return VISO_ERR_ARG; }
+    if (!(b->disp_on || b->sgm_on) || !b->disp_last) { viso_set_error("%s: dense disparity is off, or no run has computed it", where); return VISO_ERR_ARG; }
+    int r;
+    if ((r = enter(b)) < 0) return r;
+    const size_t per = (size_t)b->disp_rows * b->disp_cols;
+    float* dout = nullptr;
+    if (hipMalloc((void**)&dout, 3 * sizeof(float) * per) != hipSuccess) {
+        (void)hipGetLastError();
+        viso_set_error("%s: cannot allocate the %zu-byte point image", where, 3 * sizeof(float) * per);
+        return VISO_ERR_NOMEM;
+    }
+    hipStream_t s = b->ctx->stream;
+    r = launch_points(s, b->disp + (size_t)t * per, b->disp_rows, b->disp_cols, b->sp.f, b->sp.cu, b->sp.cv, b->sp.base, pose_or_null,
+                      min_disp16, dout);
+    hipError_t e = hipSuccess;
+    if (r >= 0) e = hipMemcpyAsync(out, dout, 3 * sizeof(float) * per, hipMemcpyDeviceToHost, s);
+    const hipError_t e2 = hipStreamSynchronize(s);
+    (void)hipFree(dout);
+    if (r < 0) return r;
+    HIP_TRY(e);
+    HIP_TRY(e2);
+    return VISO_OK;
+}
 
 // The geometry of the batch's device images (what viso_batch_get_image copies): 0 x 0 before the first image upload.
 extern "C" int viso_batch_get_image_geometry(viso_batch* b, int* rows, int* cols) {

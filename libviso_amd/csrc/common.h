@@ -464,6 +464,19 @@ int sgm_group_frames(int rows, int cols, int D, int n_frames);
 int sgm_nomem(const char* where, int rows, int cols, int D);   // sets the error text; returns VISO_ERR_NOMEM
 int launch_sgm(hipStream_t s, const uint8_t* img, size_t fs, size_t ss, int rows, int cols, int n_frames, const viso_sgm_params* p,
                int16_t* out, size_t ofs, void* ws, int group);
+// speckle.hip: the opt-in speckle filter of the maps (viso_batch_set_speckle), in place; frame f's map at map + f * mfs.  The frames
+// go through the workspace ws in groups of `group` (>= 1) frames: ws holds group * speckle_frame_bytes.  speckle_group_frames: how
+// many of n_frames frames fit the workspace cap (0: not even one).  launch_points: the reprojection of one device map; pose = the
+// first three rows of a 4 x 4 row-major matrix on the host, or null.
+bool speckle_params_ok(const viso_speckle_params* p);
+bool speckle_geometry_ok(int rows, int cols);   // cols as the methods, and rows * cols within the 32-bit labels
+size_t speckle_frame_bytes(int rows, int cols);
+int speckle_group_frames(int rows, int cols, int n_frames);
+int speckle_nomem(const char* where, int rows, int cols);   // sets the error text; returns VISO_ERR_NOMEM
+int launch_speckle(hipStream_t s, int16_t* map, size_t mfs, int rows, int cols, int n_frames, const viso_speckle_params* p, void* ws,
+                   int group);
+int launch_points(hipStream_t s, const int16_t* disp, int rows, int cols, double f, double cu, double cv, double base,
+                  const double* pose, int min_disp16, float* out);
 // covariance.hip: the opt-in motion covariance (viso_batch_set_covariance); one record per item, out[item], read from the item's
 // X, obs, m_ptr, ld, tr, ok, n_inl, inl (what ransac_refit_kernel left)
 int launch_motion_cov(hipStream_t s, const SolverItem* items_dev, int n_items, const SolverParamsDev& sp, int mode, double sigma,

@@ -359,6 +359,16 @@ extern "C" int viso_kitti_set_sgm(const char* dir, const viso_sgm_params* params
     return VISO_OK;
 }
 
+extern "C" int viso_kitti_set_speckle(const viso_speckle_params* params) {
+    if (!params) { g_disp.speckle = false; return VISO_OK; }
+    if (params->max_size < 0 || params->max_diff < 0 || params->max_diff > 4096) {
+        g_host_err = "viso_kitti_set_speckle: parameters outside the ranges of include/viso_hip.h";
+        return VISO_ERR_ARG;
+    }
+    g_disp.speckle = true; g_disp.speckle_params = *params;
+    return VISO_OK;
+}
+
 // ---- KITTI stereo PNG (16-bit grayscale) without zlib: stored deflate blocks, checksums computed here ----
 namespace {
 uint32_t crc32_update(uint32_t c, const uint8_t* p, size_t n) {

@@ -120,6 +120,9 @@ int viso_kitti_set_disparity(const char* dir, const viso_disparity_params* param
 // the same maps by semi-global matching (viso_batch_set_sgm): same directory, names and ownership of halo frames; the last of the
 // two calls decides the method.  params null = viso_sgm_params_default
 int viso_kitti_set_sgm(const char* dir, const viso_sgm_params* params);
+// the speckle filter (viso_batch_set_speckle) over those maps, for either method, in the next viso_kitti_run_range calls of this
+// thread; params null = off.  It does nothing while no maps are written.  VISO_ERR_ARG for invalid parameters.
+int viso_kitti_set_speckle(const viso_speckle_params* params);
 // One disparity map (int16 rows x cols, 1/16 px, VISO_DISP_INVALID = -16) as KITTI's stereo PNG: 16-bit grayscale, value =
 // 16 * disp16 (disparity = value / 256), 0 = invalid.  A valid disparity of 0 px is written as 0 as well: the format cannot tell it
 // from invalid.  zlib stored blocks (no compression: about 0.93 MB at 1241 x 376), Adler-32 and CRC-32 computed here; written under

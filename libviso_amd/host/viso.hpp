@@ -272,6 +272,8 @@ struct DisparityOutput {
     bool write_first = true;
     bool sgm = false;                 // the maps by semi-global matching (viso_batch_set_sgm with sgm_params) instead
     viso_sgm_params sgm_params{};
+    bool speckle = false;             // the speckle filter behind either method (viso_batch_set_speckle with speckle_params)
+    viso_speckle_params speckle_params{};
 };
 
 // sequence_odometry(P1, P2, images, dbg_dir), src/viso.h:138-139 / src/viso.cpp:1167-1330, without the

@@ -874,6 +874,7 @@ OdometryResult sequence_odometry(const Matd& P1, const Matd& P2, StereoImageGene
             r = viso_batch_set_sgm(b, nullptr);
             if (r >= 0) r = viso_batch_set_disparity(b, disp ? &disp->params : nullptr);
         }
+        if (r >= 0) r = viso_batch_set_speckle(b, disp && disp->speckle ? &disp->speckle_params : nullptr);
         if (r >= 0) r = viso_batch_stamp(b, 0);
         if (r >= 0) r = viso_batch_upload_images_async(b, 0, nf, pin, rows, cols, nullptr, nullptr);
         if (r >= 0) r = viso_batch_stamp(b, 1);

@@ -38,6 +38,8 @@
 //                       matching (viso_batch_set_sgm), with the same names, format and halo ownership
 //   --sgm-params D,P1,P2,paths,u,m  with --disparity-method sgm: num_disp, p1, p2, paths, uniqueness, lr_max_diff (default
 //                       128,10,120,8,10,1)
+//   --speckle SIZE,DIFF  with --disparity, for either method: the speckle filter (viso_batch_set_speckle) over every map before it is
+//                       written: max_size in pixels, max_diff in 1/16 px.  Same names, format and halo ownership
 // Every rank reports where its wall time went: decode (PNG inflate on the worker threads; the calling thread's wait for
 // it is the runner's critical path), upload and GPU seconds from time stamps on the device.
 // libviso_amd/kitti_shard.py is the same runner with the gather as an RCCL all-gather (torch.distributed).
@@ -75,6 +77,8 @@ struct Args {
     bool method_given = false, sgm = false;   // --disparity-method
     bool sgm_params_given = false;
     viso_sgm_params sgmp{};         // --sgm-params (defaults otherwise)
+    bool speckle = false;
+    viso_speckle_params spk{};      // --speckle SIZE,DIFF
 };
 
 bool parse(int argc, char** argv, Args& a) {
@@ -116,6 +120,12 @@ bool parse(int argc, char** argv, Args& a) {
                             &tail) != 6) return false;
             a.sgm_params_given = true;
         }
+        else if (s == "--speckle") {
+            if (i + 1 >= argc) return false;
+            char tail = 0;
+            if (std::sscanf(argv[++i], "%d,%d%c", &a.spk.max_size, &a.spk.max_diff, &tail) != 2) return false;
+            a.speckle = true;
+        }
         else if (s == "--covariance-sigma") {
             if (i + 1 >= argc) return false;
             char* e = nullptr;
@@ -142,6 +152,7 @@ bool parse(int argc, char** argv, Args& a) {
     if (a.method_given && a.disparity.empty()) return false;         // and so does --disparity-method
     if (a.sgm_params_given && !a.sgm) return false;                  // --sgm-params belongs to --disparity-method sgm
     if (a.disp_params_given && a.sgm) return false;                  // --disparity-params to the block matcher
+    if (a.speckle && a.disparity.empty()) return false;              // --speckle filters the maps of --disparity
     return true;
 }
 
@@ -178,7 +189,7 @@ int main(int argc, char** argv) {
         std::printf("usage: demo result_sha seq_name begin end [--gpus W | --rank r --world W | --gather W] "
                     "[--device d] [--same-device] [--chunk n] [--seed s] [--decode-threads n] [--reference-pose-list] [--subpixel 0|1|2] [--rectify calib_cam_to_cam.txt] "
                     "[--covariance file [--covariance-sigma s]] [--disparity dir [--disparity-params D,B,c,T,u,m] "
-                    "[--disparity-method bm|sgm [--sgm-params D,P1,P2,paths,u,m]]]\n");   // :81-85
+                    "[--disparity-method bm|sgm [--sgm-params D,P1,P2,paths,u,m]] [--speckle SIZE,DIFF]]\n");   // :81-85
         return 1;
     }
     const char* home = std::getenv("KITTI_HOME");                                              // :96
@@ -213,6 +224,14 @@ int main(int argc, char** argv) {
         else viso_sgm_params_default(&disp.sgm_params);
         if (a.disp_params_given) disp.params = a.disp;
         else viso_disparity_params_default(&disp.params);
+        if (a.speckle) {
+            if (viso_kitti_set_speckle(&a.spk) != VISO_OK) {
+                std::fprintf(stderr, "%s\n", viso_host_last_error());
+                return 2;
+            }
+            disp.speckle = true;
+            disp.speckle_params = a.spk;
+        }
         dispp = &disp;
     }
 

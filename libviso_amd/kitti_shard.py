@@ -74,6 +74,8 @@ def load_host():
     L.viso_kitti_set_disparity.argtypes = [C.c_char_p, C.c_void_p]
     if hasattr(L, "viso_kitti_set_sgm"):
         L.viso_kitti_set_sgm.argtypes = [C.c_char_p, C.c_void_p]
+    if hasattr(L, "viso_kitti_set_speckle"):
+        L.viso_kitti_set_speckle.argtypes = [C.c_void_p]
     L.viso_write_disparity_png.argtypes = [C.c_char_p, C.POINTER(C.c_int16), C.c_int, C.c_int]
     L.viso_kitti_last_covariances.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     L.viso_kitti_write_covariances.argtypes = [C.c_char_p, C.c_void_p, C.c_int]
@@ -282,6 +284,9 @@ def main(argv=None):
                     help="with --disparity: bm (default) = the block matcher, sgm = semi-global matching; same files, names and format")
     ap.add_argument("--sgm-params", default=None, metavar="D,P1,P2,paths,u,m",
                     help="with --disparity-method sgm: num_disp, p1, p2, paths, uniqueness, lr_max_diff (default 128,10,120,8,10,1)")
+    ap.add_argument("--speckle", default=None, metavar="SIZE,DIFF",
+                    help="with --disparity, for either method: the speckle filter over every map before it is written "
+                         "(max_size in pixels, max_diff in 1/16 px)")
     args = ap.parse_args(argv)
     if args.covariance_sigma is not None and args.covariance is None:
         ap.error("--covariance-sigma needs --covariance")
@@ -314,6 +319,18 @@ def main(argv=None):
             ap.error("--sgm-params takes six integers D,P1,P2,paths,u,m")
         from .abi import SgmParams
         sgm_params = SgmParams(*vals)
+    speckle = None
+    if args.speckle is not None:
+        if args.disparity is None:
+            ap.error("--speckle needs --disparity")
+        try:
+            vals = [int(v) for v in args.speckle.split(",")]
+        except ValueError:
+            vals = []
+        if len(vals) != 2:
+            ap.error("--speckle takes two integers SIZE,DIFF")
+        from .abi import SpeckleParams
+        speckle = SpeckleParams(*vals)
     home = os.environ.get("KITTI_HOME")
     if not home:
         print("KITTI_HOME is not set", file=sys.stderr)
@@ -375,6 +392,10 @@ def main(argv=None):
             return 2
     elif args.disparity is not None and L.viso_kitti_set_disparity(
             os.fsencode(os.path.abspath(args.disparity)), C.addressof(disp_params) if disp_params is not None else None) != 1:
+        print(f"kitti_shard: {L.viso_host_last_error().decode()}", file=sys.stderr)
+        return 2
+
+    if speckle is not None and L.viso_kitti_set_speckle(C.addressof(speckle)) != 1:
         print(f"kitti_shard: {L.viso_host_last_error().decode()}", file=sys.stderr)
         return 2
 
