@@ -852,6 +852,87 @@ int viso_disparity_to_points(const int16_t* disp, int rows, int cols, const viso
  * disparity is off, no run has computed it, or the batch's parameters are not set. */
 int viso_batch_get_disparity_points(viso_batch* b, int t, const double* pose_or_null, int min_disp16, float* out);
 
+/* ------------------------------------------------ voxel map: dense maps and poses fused on the device (opt-in; NOT in the reference)
+ *
+ * A persistent hash table of voxels on the device that takes any number of (disparity map, pose) pairs and gives back a compact,
+ * sorted list of the occupied voxels with observation counts and centroids.  Everything behind one double division is integer
+ * arithmetic, so a map depends on neither the order of the frames nor on scheduling, and maps are additive: fusing a sequence in
+ * any partition and adding the parts (viso_map_add_entries) gives the same bytes.  This definition is the contract; the device
+ * output is bit-identical to tests/map_ref.py.
+ * Parameters: voxel > 0 and finite (metres), min_disp16 >= 1 (1/16 px), capacity_log2 in 10..28 (the table has 2^capacity_log2
+ * slots).  Any other value gives VISO_ERR_ARG.  s = voxel / 1024, computed once in double on the host, is the only derived constant.
+ *   1. A pixel (x, y) of a frame contributes when disp16 != VISO_DISP_INVALID and disp16 >= min_disp16.
+ *   2. Its world point P is the reprojection above in double, BEFORE that section's rounding to float32: d = disp16 / 16,
+ *      X = base (x - cu) / d, Y = base (y - cv) / d, Z = f base / d, and with a pose P_i = ((T[i][0] X + T[i][1] Y) + T[i][2] Z) +
+ *      T[i][3] in exactly that association, with no fused multiply-add; without one P = (X, Y, Z).  The pose is a 4 x 4 row-major
+ *      matrix whose first three rows are read; all 16 entries must be finite (VISO_ERR_ARG, checked before any device is touched).
+ *   3. Cell: g_i = (int64) floor(P_i / s), i = x, y, z: one IEEE double division and one floor.  If any |g_i| >= 2^30 (or P_i / s
+ *      is not finite) the point is not inserted and n_out_of_range is incremented.
+ *   4. Otherwise the voxel is k_i = g_i >> 10 (arithmetic shift: -2^20 <= k_i < 2^20) and the offset o_i = g_i & 1023.
+ *      key = ((k_x + 2^20) << 42) | ((k_y + 2^20) << 21) | (k_z + 2^20): 63 bits; all ones marks an empty slot.
+ *   5. Per voxel: count (uint32) += 1, sum[i] (uint64) += o_i.
+ *   6. Extraction: every occupied voxel with count >= min_count (>= 1) as a viso_map_entry, sorted by key, ascending.
+ *   7. Centroid of an entry (host only): c_i = (float)(((double)(k_i * 1024) + (double)sum[i] / (double)count + 0.5) * s).
+ * Full table: insertion is open addressing (linear probing from a hash of the key) with a 64-bit compare-and-swap on the key array;
+ * the probe loop is bounded by the capacity and advances strictly, so a full table is a wrong count, never a hang.  A point that
+ * finds no slot increments n_dropped; a call that ends with n_dropped > 0 returns VISO_ERR_NOMEM and marks the map overflowed
+ * (which points were dropped depends on scheduling), and viso_map_count / viso_map_get / viso_map_add_entries / the fuse calls
+ * then refuse with VISO_ERR_NOMEM until viso_map_clear, after which the map is fully usable again.
+ * Out of scope: colour, a TSDF or surface form, eviction of far voxels, fusing inside the KITTI runners while their chunks drain.
+ * HIP kernels (voxelmap.hip): map_fuse_kernel (one thread per pixel of a group of frames; lanes that continue the key of the lane
+ * to their left form a run, the run heads come from one ballot, the runs' sums from a wave scan, and only a run's head probes the
+ * table and issues the four integer atomic adds), map_add_entries_kernel, map_compact_kernel, map_clear_kernel.  Memory: 36 bytes a
+ * slot (604 MB at the default capacity). */
+typedef struct viso_map_params {
+    double voxel;            /* edge of a voxel, metres */
+    int32_t min_disp16;      /* smallest disparity used, 1/16 px */
+    int32_t capacity_log2;   /* log2 of the table's slots */
+} viso_map_params;
+
+typedef struct viso_map_entry {   /* 40 bytes */
+    int32_t k[3];            /* voxel index: the voxel is [k voxel, (k + 1) voxel) on every axis */
+    uint32_t count;          /* points fused into it */
+    uint64_t sum[3];         /* sums of the points' offsets inside the voxel, in units of s = voxel / 1024 */
+} viso_map_entry;
+
+typedef struct viso_map_counters {
+    uint64_t n_points;       /* pixels that contributed (step 1), the counts of added entries included */
+    uint64_t n_inserts;      /* table insertions issued, after the combining inside the waves (a diagnostic: depends on the launch shape) */
+    uint64_t n_out_of_range; /* step 3 */
+    uint64_t n_dropped;      /* points that found no slot */
+    uint64_t n_occupied;     /* slots in use */
+} viso_map_counters;
+
+typedef struct viso_map viso_map;
+
+/* voxel 0.2, min_disp16 16 (1 px), capacity_log2 24.  Host only. */
+void viso_map_params_default(viso_map_params* p);
+/* A map on the context's device and stream (NULL: the default context), empty.  The arguments are checked before any device is
+ * touched (VISO_ERR_ARG); VISO_ERR_NOMEM when the table cannot be allocated. */
+int viso_map_create(viso_ctx* ctx_or_null, const viso_map_params* params, viso_map** out);
+/* Frees the map.  VISO_OK also for a map whose context was destroyed before it (its memory is freed all the same); every other
+ * call on such a map returns VISO_ERR_ARG, and so does anything on a handle that is not, or no longer, a map. */
+int viso_map_destroy(viso_map* m);
+/* Empties the table, zeroes the statistics and lifts the overflow mark. */
+int viso_map_clear(viso_map* m);
+/* Fuses one host map with the calibration f, cu, cv, base of *param (all finite) and the pose (NULL: no transform). */
+int viso_map_fuse(viso_map* m, const int16_t* disp, int rows, int cols, const viso_param* param, const double* pose_or_null);
+/* Fuses the resident maps of frames t0 .. t1-1 of the batch (the filtered ones while the speckle filter is on) with the calibration of
+ * viso_batch_set_params and poses [t1 - t0][16], frame t0 + i with pose i, with no host copy of the maps.  The map and the batch must
+ * share a context.  VISO_ERR_ARG when disparity is off, no run has computed it, or the batch's parameters are not set. */
+int viso_batch_fuse_disparities(viso_batch* b, viso_map* m, int t0, int t1, const double* poses);
+/* Adds n entries (of viso_map_get, of this or another map with the same voxel) to the table: count += count, sum += sum per voxel.
+ * VISO_ERR_ARG: a k outside -2^20 .. 2^20 - 1, a count of 0, a sum[i] > 1023 count. */
+int viso_map_add_entries(viso_map* m, const viso_map_entry* entries, size_t n);
+/* The number of voxels with count >= min_count (>= 1). */
+int viso_map_count(viso_map* m, uint32_t min_count, size_t* n);
+/* Those voxels, sorted by key; *n = their number.  VISO_ERR_ARG, with *n set and nothing written, when n_cap is smaller.  The table is
+ * compacted on the device; the sort runs on the host. */
+int viso_map_get(viso_map* m, uint32_t min_count, viso_map_entry* entries_out, size_t n_cap, size_t* n);
+int viso_map_stats(viso_map* m, viso_map_counters* out);
+/* Step 7.  Host only; VISO_ERR_ARG for a null pointer, a count of 0, a voxel that is not finite and > 0. */
+int viso_map_entry_centroid(const viso_map_entry* entry, double voxel, float out[3]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,7 +16,7 @@ import weakref
 
 import numpy as np
 
-from .abi import (DESC_LEN, MOTION_COV_DTYPE, MOTION_REFINE_DTYPE, SGM_DEFAULTS, SPECKLE_DEFAULTS, WINDOW_RECORD_DTYPE, DisparityParams, MatchParams,
+from .abi import (DESC_LEN, MAP_DEFAULTS, MAP_ENTRY_DTYPE, MapCounters, MapParams, declare_map, MOTION_COV_DTYPE, MOTION_REFINE_DTYPE, SGM_DEFAULTS, SPECKLE_DEFAULTS, WINDOW_RECORD_DTYPE, DisparityParams, MatchParams,
                   Param, SgmParams, SpeckleParams, declare_common, declare_covariance, declare_disparity, declare_refine, declare_rectify,
                   declare_sgm, declare_speckle, declare_subpixel, declare_window, f32p, f64p, i32p, i64p, intp, ptr)
 
@@ -130,6 +130,8 @@ def load():
         declare_sgm(L)
     if hasattr(L, "viso_batch_set_speckle"):
         declare_speckle(L)
+    if hasattr(L, "viso_map_create"):
+        declare_map(L)
     L.viso_harris_response.argtypes = [C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_double, f32p]
     L.viso_detect_harris_binned.argtypes = [C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                             C.c_double, f32p, f32p, intp]
@@ -597,6 +599,48 @@ def disparity_to_points(d16, param, pose=None, min_disp16=1):
     return out
 
 
+def map_params(**params):
+    """viso_map_params: viso_map_params_default with the given fields (voxel in metres, min_disp16 in 1/16 px, capacity_log2)
+    replaced.  Needs no library: the ranges are checked by viso_map_create (MapParams.ok restates them)."""
+    p = MapParams(**MAP_DEFAULTS)
+    for k, v in params.items():
+        if k not in MAP_DEFAULTS:
+            raise TypeError(f"map_params: unknown parameter {k!r}")
+        setattr(p, k, float(v) if k == "voxel" else int(v))
+    return p
+
+
+def map_entry_centroids(entries, voxel):
+    """viso_map_entry_centroid of every entry: float32 [n][3], the mean position of the points fused into each voxel.  Host only."""
+    entries = np.ascontiguousarray(entries, dtype=MAP_ENTRY_DTYPE)
+    out = np.empty((len(entries), 3), np.float32)
+    L = load()
+    for i in range(len(entries)):
+        r = L.viso_map_entry_centroid(entries[i:i + 1].ctypes.data, float(voxel), ptr(out[i], C.c_float))
+        if r != 1:
+            _err("viso_map_entry_centroid", r)
+    return out
+
+
+def map_ply_bytes(entries, voxel):
+    """The bytes of write_map_ply: a binary little-endian PLY with one vertex per entry, x, y, z the float32 centroid and count a
+    uint32, in the entries' order."""
+    entries = np.ascontiguousarray(entries, dtype=MAP_ENTRY_DTYPE)
+    c = map_entry_centroids(entries, voxel)
+    v = np.empty(len(entries), np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("count", "<u4")]))
+    v["x"], v["y"], v["z"], v["count"] = c[:, 0], c[:, 1], c[:, 2], entries["count"]
+    head = ("ply\nformat binary_little_endian 1.0\ncomment libviso_amd voxel map, voxel %r m\nelement vertex %d\n"
+            "property float x\nproperty float y\nproperty float z\nproperty uint count\nend_header\n" % (float(voxel), len(entries)))
+    return head.encode("ascii") + v.tobytes()
+
+
+def write_map_ply(path, entries, voxel):
+    """The entries of VoxelMap.entries as a point cloud file (map_ply_bytes)."""
+    data = map_ply_bytes(entries, voxel)
+    with open(path, "wb") as f:
+        f.write(data)
+
+
 def disparity_to_float(d16):
     """float32 disparity in pixels (d16 / 16), NaN where invalid."""
     d16 = np.asarray(d16)
@@ -765,6 +809,92 @@ class Context:
             r = self.L.viso_ctx_destroy(h)
             if r != 1:
                 _err("viso_ctx_destroy", r)
+
+    def __del__(self, _finalizing=sys.is_finalizing):   # bound at definition: module globals are None late in shutdown
+        if _finalizing():   # the atexit hook has closed everything that was still open
+            return
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class VoxelMap:
+    """viso_map: a persistent voxel map on the device that dense disparity maps and their poses are fused into (opt-in, not in the
+    reference; the definition of include/viso_hip.h).  ctx: a Context, or None for the default one.  With a trajectory:
+
+        poses, valid = hostmath.chain_poses(tr, ok)      # poses[k + 1] places frame valid[k] in frame 0's coordinates
+        vmap = VoxelMap(ctx, voxel=0.2)
+        for k, t in enumerate(valid):
+            batch.fuse_disparities(vmap, poses[k + 1][None], t0=t, t1=t + 1)
+        write_map_ply("scene.ply", vmap.entries(min_count=2), vmap.voxel)
+    """
+
+    def __init__(self, ctx=None, params=None, **kw):
+        self.L = load()
+        if isinstance(params, MapParams):
+            if kw:
+                raise TypeError("VoxelMap: keyword fields cannot be combined with a MapParams")
+        else:
+            params = map_params(**dict(params or {}, **kw))
+        self.ctx, self.voxel = ctx, float(params.voxel)
+        h = C.c_void_p()
+        r = self.L.viso_map_create(ctx.h if ctx is not None else None, C.byref(params), C.byref(h))
+        self.h = h.value if r == 1 else None
+        if r != 1:
+            _err("viso_map_create", r)
+        _live.add(self)
+
+    def _chk(self, where, r):
+        if r != 1:
+            _err(where, r)
+
+    def fuse(self, d16, param, pose=None):
+        """viso_map_fuse: one host int16 map with the calibration of param (f, cu, cv, base) and an optional 4 x 4 pose."""
+        d16 = np.ascontiguousarray(d16)
+        if d16.ndim != 2 or d16.dtype != np.int16:
+            raise ValueError("VoxelMap.fuse: the map must be a 2-D int16 array")
+        if pose is not None and np.shape(pose) != (4, 4):
+            raise ValueError("VoxelMap.fuse: the pose must be a 4 x 4 matrix")
+        T, Tp = _pose_arg("VoxelMap.fuse", pose)
+        self._chk("viso_map_fuse", self.L.viso_map_fuse(self.h, ptr(d16, C.c_int16), d16.shape[0], d16.shape[1], C.byref(param), Tp))
+
+    def add_entries(self, entries):
+        """viso_map_add_entries: the entries of another map with the same voxel (or of a saved one) added to this one."""
+        entries = np.ascontiguousarray(entries, dtype=MAP_ENTRY_DTYPE)
+        self._chk("viso_map_add_entries", self.L.viso_map_add_entries(self.h, entries.ctypes.data, len(entries)))
+
+    def count(self, min_count=1):
+        n = C.c_size_t()
+        self._chk("viso_map_count", self.L.viso_map_count(self.h, int(min_count), C.byref(n)))
+        return n.value
+
+    def entries(self, min_count=1):
+        """viso_map_get: the voxels with at least min_count points as a MAP_ENTRY_DTYPE array (k, count, sum), sorted by key."""
+        out = np.zeros(self.count(min_count), MAP_ENTRY_DTYPE)
+        n = C.c_size_t()
+        self._chk("viso_map_get", self.L.viso_map_get(self.h, int(min_count), out.ctypes.data, len(out), C.byref(n)))
+        return out[:n.value]
+
+    def centroids(self, min_count=1):
+        """float32 [n][3]: the centroids of entries(min_count), in their order."""
+        return map_entry_centroids(self.entries(min_count), self.voxel)
+
+    def stats(self):
+        """viso_map_stats as a dict: n_points, n_inserts, n_out_of_range, n_dropped, n_occupied."""
+        c = MapCounters()
+        self._chk("viso_map_stats", self.L.viso_map_stats(self.h, C.byref(c)))
+        return {name: int(getattr(c, name)) for name, _ in MapCounters._fields_}
+
+    def clear(self):
+        self._chk("viso_map_clear", self.L.viso_map_clear(self.h))
+
+    def close(self):
+        if self.h:
+            h, self.h = self.h, None
+            r = self.L.viso_map_destroy(h)
+            if r != 1:
+                _err("viso_map_destroy", r)
 
     def __del__(self, _finalizing=sys.is_finalizing):   # bound at definition: module globals are None late in shutdown
         if _finalizing():   # the atexit hook has closed everything that was still open
@@ -953,6 +1083,16 @@ class Batch:
         self._chk("viso_batch_get_disparity_points",
                   self.L.viso_batch_get_disparity_points(self.h, int(t), Tp, int(min_disp16), ptr(out, C.c_float)))
         return out
+
+    def fuse_disparities(self, vmap, poses, t0=0, t1=None):
+        """viso_batch_fuse_disparities: the resident maps of frames t0 .. t1-1 (t1 None: to the last frame) fused into the VoxelMap
+        on the device, frame t0 + i with the 4 x 4 pose poses[i]; no map is copied to the host.  The map must be on this batch's
+        context."""
+        t1 = self.nf if t1 is None else int(t1)
+        T = np.ascontiguousarray(poses, dtype=np.float64)
+        if T.ndim != 3 or T.shape[1:] != (4, 4) or T.shape[0] != t1 - int(t0):
+            raise ValueError("Batch.fuse_disparities: poses must be [t1 - t0][4][4]")
+        self._chk("viso_batch_fuse_disparities", self.L.viso_batch_fuse_disparities(self.h, vmap.h, int(t0), t1, ptr(T, C.c_double)))
 
     def run_disparity(self):
         """viso_batch_run_disparity: only the disparity, over the resident images (upload_images_only)."""

@@ -212,6 +212,43 @@ def declare_speckle(lib):
     lib.viso_batch_get_disparity_points.argtypes = [C.c_void_p, C.c_int, f64p, C.c_int, f32p]
 
 
+class MapParams(C.Structure):
+    """struct viso_map_params (include/viso_hip.h, "voxel map")."""
+    _fields_ = [("voxel", C.c_double), ("min_disp16", C.c_int32), ("capacity_log2", C.c_int32)]
+
+    def ok(self):
+        """The valid ranges of include/viso_hip.h (what the library checks before it touches a device)."""
+        return bool(np.isfinite(self.voxel)) and self.voxel > 0 and self.min_disp16 >= 1 and 10 <= self.capacity_log2 <= 28
+
+
+MAP_DEFAULTS = dict(voxel=0.2, min_disp16=16, capacity_log2=24)   # viso_map_params_default
+
+# struct viso_map_entry: 40 bytes
+MAP_ENTRY_DTYPE = np.dtype([("k", np.int32, (3,)), ("count", np.uint32), ("sum", np.uint64, (3,))])
+
+
+class MapCounters(C.Structure):
+    """struct viso_map_counters (include/viso_hip.h, "voxel map")."""
+    _fields_ = [(name, C.c_uint64) for name in ("n_points", "n_inserts", "n_out_of_range", "n_dropped", "n_occupied")]
+
+
+def declare_map(lib):
+    """Prototypes of the opt-in voxel map (include/viso_hip.h; libviso_hip.so only)."""
+    i16p, MPP, vp = C.POINTER(C.c_int16), C.POINTER(MapParams), C.c_void_p
+    lib.viso_map_params_default.restype = None
+    lib.viso_map_params_default.argtypes = [MPP]
+    lib.viso_map_create.argtypes = [vp, MPP, C.POINTER(vp)]
+    lib.viso_map_destroy.argtypes = [vp]
+    lib.viso_map_clear.argtypes = [vp]
+    lib.viso_map_fuse.argtypes = [vp, i16p, C.c_int, C.c_int, C.POINTER(Param), f64p]
+    lib.viso_batch_fuse_disparities.argtypes = [vp, vp, C.c_int, C.c_int, f64p]
+    lib.viso_map_add_entries.argtypes = [vp, vp, C.c_size_t]
+    lib.viso_map_count.argtypes = [vp, C.c_uint32, C.POINTER(C.c_size_t)]
+    lib.viso_map_get.argtypes = [vp, C.c_uint32, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    lib.viso_map_stats.argtypes = [vp, C.POINTER(MapCounters)]
+    lib.viso_map_entry_centroid.argtypes = [vp, C.c_double, f32p]
+
+
 class MotionCov(C.Structure):
     """struct viso_motion_cov (include/viso_hip.h, "motion covariance")."""
     _fields_ = [

@@ -1240,6 +1240,21 @@ extern "C" int viso_batch_get_disparity_points(viso_batch* b, int t, const doubl
     return VISO_OK;
 }
 
+// The resident maps of frames t0 .. t1-1 into a voxel map of the same context (voxelmap.hip), with the batch's calibration: on the
+// context's stream, behind the run that computed them, with no host copy of the maps.
+extern "C" int viso_batch_fuse_disparities(viso_batch* b, viso_map* m, int t0, int t1, const double* poses) {
+    const char* where = "viso_batch_fuse_disparities";
+    if (dead(b) || !m || t0 < 0 || t1 > b->nf || t0 >= t1 || !poses) {
+        viso_set_error("%s: bad argument (live handles, 0 <= t0 < t1 <= n_frames, poses [t1 - t0][16])", where);
+        return VISO_ERR_ARG;
+    }
+    if (!b->params_set) { viso_set_error("%s: parameters not set (the calibration comes from viso_batch_set_params)", where); return VISO_ERR_ARG; }
+    if (!(b->disp_on || b->sgm_on) || !b->disp_last) { viso_set_error("%s: dense disparity is off, or no run has computed it", where); return VISO_ERR_ARG; }
+    const size_t per = (size_t)b->disp_rows * b->disp_cols;
+    return map_fuse_resident(where, m, b->ctx, b->disp + (size_t)t0 * per, per, b->disp_rows, b->disp_cols, t1 - t0, b->sp.f, b->sp.cu,
+                             b->sp.cv, b->sp.base, poses);
+}
+
 // The geometry of the batch's device images (what viso_batch_get_image copies): 0 x 0 before the first image upload.
 extern "C" int viso_batch_get_image_geometry(viso_batch* b, int* rows, int* cols) {
     if (dead(b) || !rows || !cols) { viso_set_error("viso_batch_get_image_geometry: bad argument"); return VISO_ERR_ARG; }

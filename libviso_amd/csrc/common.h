@@ -123,6 +123,7 @@ struct viso_ctx {
     // completion signal of the plain family's calls (PlainSignal below): a word of pinned memory the call's LAST kernel writes,
     // a device counter of that kernel's finished workgroups, the sequence number of the last signal asked for
     int* sig_flag; int* sig_ctr; int sig_seq;
+    unsigned long long serial;   // unique per created context: a voxel map tells its own context from a later one at the same address
 };
 
 // handle registry (ctx.hip): the live contexts, the live batches of each, tombstones of batches their context took along
@@ -477,6 +478,10 @@ int launch_speckle(hipStream_t s, int16_t* map, size_t mfs, int rows, int cols, 
                    int group);
 int launch_points(hipStream_t s, const int16_t* disp, int rows, int cols, double f, double cu, double cv, double base,
                   const double* pose, int min_disp16, float* out);
+// voxelmap.hip: the opt-in voxel map (viso_map_*).  map_fuse_resident: the fuse of n_frames device maps (frame f at disp + f * mfs)
+// that live on context c, on its stream, with poses [n_frames][16] on the host; checks the map handle, its context and the poses
+int map_fuse_resident(const char* where, viso_map* m, viso_ctx* c, const int16_t* disp, size_t mfs, int rows, int cols, int n_frames,
+                      double f, double cu, double cv, double base, const double* poses);
 // covariance.hip: the opt-in motion covariance (viso_batch_set_covariance); one record per item, out[item], read from the item's
 // X, obs, m_ptr, ld, tr, ok, n_inl, inl (what ransac_refit_kernel left)
 int launch_motion_cov(hipStream_t s, const SolverItem* items_dev, int n_items, const SolverParamsDev& sp, int mode, double sigma,

@@ -77,6 +77,7 @@ extern "C" viso_ctx* viso_ctx_create(int device, void* stream) {
     viso_ctx* c = new viso_ctx();
     memset(c, 0, sizeof(*c));
     c->device = device;
+    { static std::mutex mu; static unsigned long long next = 0; std::lock_guard<std::mutex> lk(mu); c->serial = ++next; }
     c->matcher_variant = viso_matcher_default();
     c->row8_force = -1;
     if (const char* e = getenv("VISO_ROW8_SHIFT")) {   // test / A-B aid: a fixed shift of the 8-bit planes for every new context

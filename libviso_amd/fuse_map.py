@@ -1,0 +1,162 @@
+"""python -m libviso_amd.fuse_map DISPARITY_DIR POSES.txt CALIB.txt OUT.ply [--voxel V --min-count N --min-disp PX --frames B E]
+
+Fuses the maps a KITTI runner wrote with --disparity DIR and the poses of its pose file into one voxel map on the device
+(libviso_amd.VoxelMap; include/viso_hip.h, "voxel map") and writes the occupied voxels as a binary PLY point cloud: x, y, z the
+float32 centroid of each voxel, count the number of points fused into it.
+
+  DISPARITY_DIR  16-bit grayscale PNGs named by image index (value / 16 = disparity in 1/16 px, 0 = invalid)
+  POSES.txt      KITTI pose file: 12 numbers a line, the first three rows of the pose; line i belongs to the i-th map
+  CALIB.txt      the sequence's calib.txt (lines P0: and P1:)
+  --frames B E   only maps B .. E-1 of the directory (positions in name order), with their poses
+
+Both runners write byte-identical directories and pose files for every rank count and chunk size, so the PLY is identical too."""
+import argparse
+import os
+import struct
+import sys
+import zlib
+
+import numpy as np
+
+DISP_INVALID = -16
+
+
+def read_png16(path):
+    """A non-interlaced 16-bit grayscale PNG as uint16 [rows][cols]; all five row filters.  ValueError for anything else."""
+    with open(path, "rb") as f:
+        data = f.read()
+    if data[:8] != b"\x89PNG\r\n\x1a\n":
+        raise ValueError(f"{path}: not a PNG file")
+    pos, idat, ihdr = 8, [], None
+    while pos + 12 <= len(data):
+        n, = struct.unpack(">I", data[pos:pos + 4])
+        kind, body = data[pos + 4:pos + 8], data[pos + 8:pos + 8 + n]
+        if len(body) != n or pos + 12 + n > len(data):
+            raise ValueError(f"{path}: truncated chunk")
+        if zlib.crc32(kind + body) != struct.unpack(">I", data[pos + 8 + n:pos + 12 + n])[0]:
+            raise ValueError(f"{path}: bad CRC in chunk {kind!r}")
+        if kind == b"IHDR":
+            ihdr = struct.unpack(">IIBBBBB", body)
+        elif kind == b"IDAT":
+            idat.append(body)
+        elif kind == b"IEND":
+            break
+        pos += 12 + n
+    if ihdr is None:
+        raise ValueError(f"{path}: no IHDR chunk")
+    cols, rows, depth, color, comp, filt, inter = ihdr
+    if (depth, color, comp, filt, inter) != (16, 0, 0, 0, 0) or rows < 1 or cols < 1:
+        raise ValueError(f"{path}: only non-interlaced 16-bit grayscale PNGs are read")
+    stride = 2 * cols
+    raw = np.frombuffer(zlib.decompress(b"".join(idat)), np.uint8)
+    if raw.size != rows * (stride + 1):
+        raise ValueError(f"{path}: {raw.size} bytes of image data, expected {rows * (stride + 1)}")
+    raw = raw.reshape(rows, stride + 1)
+    out = np.zeros((rows, stride), np.uint8)
+    zero = np.zeros(stride, np.int32)
+    bpp = 2
+    for y in range(rows):
+        ft, line = int(raw[y, 0]), raw[y, 1:].astype(np.int32)
+        up = out[y - 1].astype(np.int32) if y else zero
+        if ft == 0:
+            rec = line
+        elif ft == 2:
+            rec = line + up
+        elif ft in (1, 3, 4):   # the filters that look left: byte by byte, per channel of bpp bytes
+            rec = np.zeros(stride, np.int32)
+            for i in range(stride):
+                a = int(rec[i - bpp]) if i >= bpp else 0
+                b = int(up[i])
+                if ft == 1:
+                    pred = a
+                elif ft == 3:
+                    pred = (a + b) >> 1
+                else:
+                    c = int(up[i - bpp]) if i >= bpp else 0
+                    p = a + b - c
+                    pa, pb, pc = abs(p - a), abs(p - b), abs(p - c)
+                    pred = a if pa <= pb and pa <= pc else b if pb <= pc else c
+                rec[i] = (int(line[i]) + pred) & 255
+        else:
+            raise ValueError(f"{path}: unknown row filter {ft}")
+        out[y] = (rec & 255).astype(np.uint8)
+    return out.view(">u2").astype(np.uint16)
+
+
+def read_disparity_png(path):
+    """The runners' map as int16 in 1/16 px: value / 16, DISP_INVALID where the file has 0."""
+    v = read_png16(path)
+    d = (v // 16).astype(np.int16)
+    d[v == 0] = DISP_INVALID
+    return d
+
+
+def read_poses(path):
+    """[n][4][4] float64 from a KITTI pose file (12 numbers a line)."""
+    out = []
+    with open(path) as f:
+        for ln, line in enumerate(f, 1):
+            if not line.strip():
+                continue
+            v = [float(t) for t in line.split()]
+            if len(v) != 12:
+                raise ValueError(f"{path}:{ln}: expected 12 numbers, found {len(v)}")
+            T = np.eye(4)
+            T[:3] = np.array(v).reshape(3, 4)
+            out.append(T)
+    return np.array(out).reshape(-1, 4, 4)
+
+
+def read_calib(path):
+    """(f, cu, cv, base) from calib.txt's P0 and P1, as the runners take them."""
+    P = {}
+    with open(path) as f:
+        for line in f:
+            name, _, rest = line.partition(":")
+            v = rest.split()
+            if name.strip() in ("P0", "P1") and len(v) == 12:
+                P[name.strip()] = np.array([float(t) for t in v]).reshape(3, 4)
+    if "P0" not in P or "P1" not in P:
+        raise ValueError(f"{path}: no P0: and P1: lines of 12 numbers")
+    P1, P2 = P["P0"], P["P1"]
+    return float(P1[0, 0]), float(P1[0, 2]), float(P1[1, 2]), float(abs(P2[0, 3] / P2[0, 0]))
+
+
+def list_maps(directory):
+    return sorted(n for n in os.listdir(directory) if n.lower().endswith(".png"))
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m libviso_amd.fuse_map", description=__doc__.split("\n\n")[1])
+    ap.add_argument("disparity_dir"); ap.add_argument("poses"); ap.add_argument("calib"); ap.add_argument("out")
+    ap.add_argument("--voxel", type=float, default=0.2, help="edge of a voxel in metres (0.2)")
+    ap.add_argument("--min-count", type=int, default=1, help="only voxels with at least this many points (1)")
+    ap.add_argument("--min-disp", type=float, default=1.0, help="smallest disparity used, in pixels (1.0)")
+    ap.add_argument("--frames", type=int, nargs=2, metavar=("B", "E"), help="only maps B .. E-1 of the directory")
+    ap.add_argument("--capacity-log2", type=int, default=24, help="log2 of the table's slots (24)")
+    a = ap.parse_args(argv)
+    import libviso_amd
+    from libviso_amd.abi import Param
+    names, poses = list_maps(a.disparity_dir), read_poses(a.poses)
+    if len(names) != len(poses):
+        sys.exit(f"fuse_map: {len(names)} maps in {a.disparity_dir} but {len(poses)} poses in {a.poses}")
+    b, e = a.frames if a.frames else (0, len(names))
+    if not 0 <= b <= e <= len(names):
+        sys.exit(f"fuse_map: --frames {b} {e} is outside the {len(names)} maps")
+    f, cu, cv, base = read_calib(a.calib)
+    prm = Param.default(base=base, f=f, cu=cu, cv=cv)
+    vmap = libviso_amd.VoxelMap(None, voxel=a.voxel, min_disp16=max(1, int(round(a.min_disp * 16))), capacity_log2=a.capacity_log2)
+    try:
+        for i in range(b, e):
+            vmap.fuse(read_disparity_png(os.path.join(a.disparity_dir, names[i])), prm, pose=poses[i])
+        entries, st = vmap.entries(a.min_count), vmap.stats()
+    finally:
+        vmap.close()
+    libviso_amd.write_map_ply(a.out, entries, a.voxel)
+    print(f"fuse_map: {e - b} maps, {st['n_points']} points ({st['n_out_of_range']} out of range), {st['n_occupied']} voxels, "
+          f"{len(entries)} with count >= {a.min_count} -> {a.out}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
