@@ -1,161 +1,59 @@
 // batch.hip — device-resident frame batches: the loop body of
 // sequence_odometry (reference src/viso.cpp:1205-1327) for many frames per
 // launch, every stage on one HIP stream with no host round trip in between.
-//
-// HBM layout (all allocations made once, at viso_batch_create):
-//   kp      [nf][2][cap] float2          boundary layout (x,y)
-//   desc    [nf][2][cap][dlen] float     boundary layout (reference Mat N x 121 CV_32F)
-//   packed  [nf][2][cap][128] u16        biased rows the matcher reads (256 B, 16-B aligned)
-//   res     [3][nf][cap] int2            per query (target | -1, SAD)
-//   sorted  [3][nf][cap][3] int          match lists in (dist,i1) order; pos = inverse
-//   x_c [nf][4][cap], Xp_c [nf][3][cap]   double, SoA rows like cv::Mat(4,M): the solver's inputs, written by the circle join
-//   uv  [nf][cap] float2                 refined right-image points per stereo row (viso_batch_set_subpixel != 0 only)
-//   raw [nf][2][raw_rows][raw_cols] u8   staged raw images the remap reads into `images` (viso_batch_set_rectify only)
-//   disp [nf][img_rows][img_cols] i16    dense disparity of every frame's resident pair (viso_batch_set_disparity / _set_sgm only)
-//   sgm_ws                               census words and S volumes of one group of frames (viso_batch_set_sgm only; sgm.hip)
-//   spk_ws                               label and size words of one group of frames (viso_batch_set_speckle only; speckle.hip)
-// `which` = 0 stereo L->R of frame t, 1 temporal left (t vs t-1), 2 temporal right.
-#include "common.h"
+// struct viso_batch, the HBM layout and the map of the three batch files are in batch.h.  Here: the batch's life, its uploads, the
+// run itself and the core getters; the opt-in stages that belong to the uploads and the matcher (rectify, sub-pixel) with them.
+#include "batch.h"
 
-#include <string.h>
-#include <initializer_list>
-#include <vector>
+#include <algorithm>
 
-#define VISO_NPIN_SLOTS 4
-
-struct viso_batch {
-    viso_ctx* ctx;
-    int nf, cap, dlen, iters;
-    int n_probs;               // padded problem count (multiple of 24)
-    float2* kp; float* desc; int* n; uint16_t* packed; uint8_t* packed8; uint2* sums;
-    // the 8-bit planes' shift (VISO_R8_*, csrc/common.h): device counters, their pinned landing place, the event behind the copy
-    int* r8cnt = nullptr; int* r8pin = nullptr; hipEvent_t r8ev = nullptr; bool r8pending = false; int r8shift = VISO_R8_DEFAULT; int r8last = VISO_R8_DEFAULT; unsigned r8runs = 0; int* bad_img; int* bad_any; int* zero;
-    float2* skp; int *sidx, *rank, *bstart; float* xinfo; uint8_t* qord;   // column-bucket view of every image
-    uint8_t* images; int img_rows, img_cols;                // optional: [nf][2][rows][cols] uint8 (image-in mode)
-    float* h_resp; float2* h_tmp_kp; float* h_tmp_resp; int* h_cnt; size_t h_slots;   // Harris detector scratch
-    void* h_part = nullptr; size_t h_part_bytes = 0;                                   // ... of the strip kernel (harris_strip_bytes)
-    ImageView* views;                                       // [nf*2] (+1 empty)
-    MatchProblem* probs;
-    int2* ovf_q;                 // the launch's overflow queue: up to one entry per query of the batch
-    int* tile_flag; int tiles;   // [3][nf][tiles] per-64-query-tile scratch of the stereo kernels
-    int2* res; int* sorted; int* pos; int* m_cnt; int* ovf_cnt; unsigned long long* scored; size_t zeroed_bytes;
-    double *x_c, *Xp_c;          // the solver's inputs: gathered + triangulated by the circle join
-    // opt-in sub-pixel refinement of the stereo observations (subpixel.hip): the mode asked for, the buffer (allocated on the first
-    // request), and the mode the last run refined with (0: the last run produced no refined points)
-    int subpix = 0; float2* uv = nullptr; int uv_mode = 0;
-    // opt-in rectification of raw images (rectify.hip): on while rmap != null; the quantised maps [2][img_rows * img_cols], the
-    // raw staging buffer, its geometry and the border value
-    RectEntry* rmap = nullptr; uint8_t* raw = nullptr; int raw_rows = 0, raw_cols = 0, rborder = 0; size_t raw_bytes = 0;
-    // opt-in dense disparity (disparity.hip): on while disp_on; the parameters, the maps (allocated when first needed, for the
-    // geometry disp_rows x disp_cols), and whether the maps hold the last image geometry's result (0: no run has computed them)
-    bool disp_on = false; viso_disparity_params disp_p = {}; int16_t* disp = nullptr; int disp_rows = 0, disp_cols = 0; int disp_last = 0;
-    // opt-in semi-global matching (sgm.hip): on while sgm_on (never together with disp_on: the maps are one buffer, `disp`); the
-    // parameters and the workspace of one group of frames (allocated by the first launch, again when a launch needs another size)
-    bool sgm_on = false; viso_sgm_params sgm_p = {}; void* sgm_ws = nullptr; size_t sgm_ws_bytes = 0;
-    // opt-in speckle filter of the maps (speckle.hip): on while spk_on, behind either method's selection kernel; the parameters and
-    // the workspace of one group of frames (allocated by the first launch, again when a launch needs another size)
-    bool spk_on = false; viso_speckle_params spk_p = {}; void* spk_ws = nullptr; size_t spk_ws_bytes = 0;
-    // opt-in motion covariance (covariance.hip): the mode and sigma asked for, the records [nf] (allocated on the first request,
-    // frame 0 stays zero: status 0), and the mode the last run computed them with (0: the last run computed none)
-    int cov_mode = 0; double cov_sigma = 0.0; viso_motion_cov* cov = nullptr; int cov_last = 0;
-    // opt-in motion refinement (refine.hip): the mode and sigma asked for, the records [nf] and the working buffers (points
-    // [nf][2][3][cap], L' [nf][cap]; allocated on the first request, frame 0 stays zero), and the mode the last run computed them with
-    int ref_mode = 0; double ref_sigma = 0.0; viso_motion_refine* ref = nullptr; double* ref_pts = nullptr; int* ref_idx = nullptr;
-    int ref_last = 0;
-    // opt-in window refinement (window.hip): K (0 off), mode and sigma asked for, the records [nf] and the working buffers (L' [nf][cap],
-    // |L'| [nf], tables [nf][2][cap], tracks [nf][5][(K-1) cap], points [nf][2][3][(K-1) cap]; allocated on the first request with
-    // K > 0, for the largest K asked for so far: win_kalloc), and the K the last run computed them with (0: none)
-    int win_K = 0, win_mode = 0, win_kalloc = 0, win_last = 0; double win_sigma = 0.0; viso_window_record* win = nullptr;
-    int *win_lp = nullptr, *win_nlp = nullptr, *win_tab = nullptr, *win_trk = nullptr; double* win_pts = nullptr;
-    JoinItem* join; SolverItem* sitems;
-    int *circ, *pcl, *mc;
-    double* tr_h; int *ok_h, *cnt_h, *hq; char* rot;   // hq: list of undecided hypotheses (launch_ransac)
-    int* samp_h;                            // [nf][iters][3] sample triples of the run (ransac_hyp_kernel)
-    // the *_async uploads stage the caller's (pageable, possibly temporary) n array through a small pinned ring:
-    // slot k is reusable once the copy that read it has passed (n_pin_ev[k])
-    int* n_pin; hipEvent_t n_pin_ev[VISO_NPIN_SLOTS]; bool n_pin_used[VISO_NPIN_SLOTS]; int n_pin_next;
-    double* tr; int *ok, *n_inl, *inl;   // tr, ok, n_inl: ONE device block (tr first), mirrored in pinned memory by every run's last kernel
-    unsigned char* pose_pin = nullptr;   // [n_frames] x (6 doubles) | [n_frames] ok | [n_frames] n_inl: what viso_batch_get_poses reads
-    size_t pose_bytes = 0;
-    MatchParamsDev mp[2];
-    SolverParamsDev sp;
-    unsigned long long seed, first_frame;
-    bool params_set;
-    bool timing;
-    bool desc_i16;             // the descriptor buffer holds int16 rows (viso_batch_upload_i16*), not the f32 boundary layout
-    std::vector<signed char> desc_family;   // per frame: 0 = never uploaded, 1 = f32 rows, 2 = int16 rows (the two must not mix in a run)
-    // The RANSAC stage of run k (latency bound: a few hundred waves on serial fp64 chains for ~1 ms) runs on a
-    // stream of its own (the context's second stream), so that the matcher of run k+1 — which touches none of its
-    // buffers — fills the GPU beside it: stream (matcher, triangulation, circle join) --ev_join--> solver_stream (RANSAC) --ev_ransac--> the next
-    // run's circle join (which rewrites the RANSAC inputs).
-    hipStream_t solver_stream;
-    hipEvent_t ev_join, ev_ransac;
-    bool ransac_pending;
-    // matcher-kernel timing: event pairs of the runs not yet read back (bounded: the oldest pair is folded into
-    // the running sum and reused once VISO_EVENT_POOL pairs are outstanding)
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
-    size_t ev_next;            // ring position of the oldest outstanding pair
-    double ev_ms_sum; int ev_n;
-    // viso_batch_stamp: time stamps of a run (0 = before its uploads, 1 = after them, 2 = behind its last kernel)
-    hipEvent_t ev_stamp[3];
-    bool stamps;
-};
-#define VISO_EVENT_POOL 64
-
-// A handle the library does not know -- null, destroyed, or taken along by viso_ctx_destroy of its context (ctx.hip keeps the
-// registry): every entry point answers VISO_ERR_ARG instead of following a freed pointer.
-static inline bool dead(const viso_batch* b) { return !b || !viso_batch_live(b); }
-
-static int enter(viso_batch* b) {   // every entry point that allocates, copies or launches
-    HIP_TRY(hipSetDevice(b->ctx->device));
-    return VISO_OK;
+void viso_batch::own(void** p) {
+    if (std::find(owned.begin(), owned.end(), p) == owned.end()) owned.push_back(p);
 }
 
-static int batch_sync(viso_batch* b) {   // everything the batch has in flight: matcher stream, then its RANSAC stream
-    HIP_TRY(hipStreamSynchronize(b->ctx->stream));
-    if (b->solver_stream) HIP_TRY(hipStreamSynchronize(b->solver_stream));
-    return VISO_OK;
-}
-
-static inline int prob_slot(int which, int t) { return (t / 8) * 24 + which * 8 + (t % 8); }
-
-template <class T>
-static int dalloc(T** p, size_t count) {
+int viso_batch::alloc_bytes(void** p, size_t bytes) {
     *p = nullptr;
-    HIP_TRY(hipMalloc((void**)p, sizeof(T) * (count ? count : 1)));
+    HIP_TRY(hipMalloc(p, bytes ? bytes : 1));
+    own(p);
     return VISO_OK;
 }
 
-// One buffer of dalloc_zeroed: the pointer to set and its element count.
-struct DBuf {
-    void** p; size_t bytes;
-    template <class T> DBuf(T** q, size_t count) : p(reinterpret_cast<void**>(q)), bytes(sizeof(T) * (count ? count : 1)) {}
-};
-
-// Allocates every buffer of the list and zeroes it.  When an allocation fails, the buffers already allocated are freed and every
-// pointer of the list is left null.
-static int dalloc_zeroed(std::initializer_list<DBuf> bufs) {
+int viso_batch::alloc_zeroed(std::initializer_list<DBuf> bufs) {
     int r = VISO_OK;
     for (const DBuf& d : bufs) *d.p = nullptr;
     for (const DBuf& d : bufs)
-        if ((r = dalloc(reinterpret_cast<char**>(d.p), d.bytes)) < 0) break;
+        if ((r = alloc_bytes(d.p, d.bytes)) < 0) break;
     if (r < 0) {
-        for (const DBuf& d : bufs) if (*d.p) (void)hipFree(*d.p);
-        for (const DBuf& d : bufs) *d.p = nullptr;
+        for (const DBuf& d : bufs) (void)release_bytes(d.p);
         return r;
     }
     for (const DBuf& d : bufs) HIP_TRY(hipMemset(*d.p, 0, d.bytes));
     return VISO_OK;
 }
 
-static void free_solver_bufs(viso_batch* b) {
-    if (b->tr_h) hipFree(b->tr_h);
-    if (b->ok_h) hipFree(b->ok_h);
-    if (b->cnt_h) hipFree(b->cnt_h);
-    if (b->rot) hipFree(b->rot);
-    if (b->hq) hipFree(b->hq);
-    if (b->samp_h) hipFree(b->samp_h);
-    b->tr_h = nullptr; b->ok_h = b->cnt_h = b->hq = nullptr; b->samp_h = nullptr; b->rot = nullptr;
+int viso_batch::release_bytes(void** p) {   // the pointer stays recorded: null until the next allocation fills it
+    void* q = *p;
+    *p = nullptr;
+    if (q) HIP_TRY(hipFree(q));
+    return VISO_OK;
+}
+
+int viso_batch::fit_bytes(void** p, size_t* have, size_t want, bool grow_only, const char* where, const char* what) {
+    if (*p && (grow_only ? *have >= want : *have == want)) return VISO_OK;
+    if (*p) VISO_TRY(batch_sync(this));
+    *have = 0;
+    VISO_TRY(release_bytes(p));
+    const hipError_t e = hipMalloc(p, want);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        *p = nullptr;
+        if (what) { viso_set_error("%s: cannot allocate the %zu-byte %s", where, want, what); return VISO_ERR_NOMEM; }
+        viso_set_error("hipMalloc(%zu) -> %s", want, hipGetErrorString(e));
+        return VISO_ERR_HIP;
+    }
+    own(p);
+    *have = want;
+    return VISO_OK;
 }
 
 // Frees everything it can; the first HIP error met is recorded (viso_last_error) and returned.  Like
@@ -190,12 +88,13 @@ int viso_batch_free(viso_batch* b, bool keep_shell) {
     if (b->r8pin) note(hipHostFree(b->r8pin));
     if (b->pose_pin) note(hipHostFree(b->pose_pin));
     if (b->r8ev) note(hipEventDestroy(b->r8ev));
-    void* ptrs[] = {b->h_part, b->h_resp, b->h_tmp_kp, b->h_tmp_resp, b->h_cnt, b->images, b->skp, b->sidx, b->rank, b->bstart, b->xinfo, b->views,
-                    b->kp, b->desc, b->n, b->packed, b->packed8, b->r8cnt, b->sums, b->zero, b->probs, b->res, b->sorted,
-                    b->pos, b->m_cnt, b->scored, b->x_c, b->Xp_c, b->join,
-                    b->sitems, b->circ, b->pcl, b->mc, b->uv, b->cov, b->ref, b->ref_pts, b->ref_idx, b->win, b->win_lp, b->win_nlp, b->win_tab, b->win_trk, b->win_pts, b->rmap, b->raw, b->disp, b->sgm_ws, b->spk_ws, b->tr /* + ok, n_inl */, b->inl, b->tr_h, b->ok_h, b->cnt_h, b->hq, b->samp_h, b->rot, b->tile_flag, b->qord, b->ovf_q};
-    for (void* p : ptrs) if (p) note(hipFree(p));
-    if (keep_shell) { b->ctx = nullptr; b->events.clear(); b->desc_family.clear(); b->desc_family.shrink_to_fit(); }
+    for (void** p : b->owned) if (*p) { note(hipFree(*p)); *p = nullptr; }
+    if (keep_shell) {   // the shell owns nothing, heap included
+        b->ctx = nullptr;
+        b->events.clear(); b->events.shrink_to_fit();
+        b->desc_family.clear(); b->desc_family.shrink_to_fit();
+        b->owned.clear(); b->owned.shrink_to_fit();
+    }
     else delete b;
     if (first != hipSuccess) { viso_set_error("viso_batch_destroy: %s", hipGetErrorString(first)); return VISO_ERR_HIP; }
     return VISO_OK;
@@ -285,111 +184,94 @@ static int build_solver_items(viso_batch* b) {
     return VISO_OK;
 }
 
+// Everything viso_batch_create allocates (events, pinned mirrors, device buffers) and the buffers' first contents.  On an error the
+// caller frees what exists so far.
+static int create_buffers(viso_batch* b) {
+    const size_t nf = (size_t)b->nf, c = (size_t)b->cap;
+    if (b->ctx->solver_stream) {
+        if (hipEventCreateWithFlags(&b->ev_join, hipEventDisableTiming) != hipSuccess ||
+            hipEventCreateWithFlags(&b->ev_ransac, hipEventDisableTiming) != hipSuccess) {
+            viso_set_error("viso_batch_create: event creation failed");
+            return VISO_ERR_HIP;
+        }
+        b->solver_stream = b->ctx->solver_stream;
+    }
+    VISO_TRY(b->alloc(&b->kp, nf * 2 * c)); VISO_TRY(b->alloc(&b->desc, nf * 2 * c * b->dlen)); VISO_TRY(b->alloc(&b->n, nf * 2));
+    VISO_TRY(b->alloc(&b->packed, nf * 2 * c * VISO_ROW)); VISO_TRY(b->alloc(&b->packed8, nf * 2 * c * VISO_ROW8));
+    VISO_TRY(b->alloc(&b->r8cnt, 4)); VISO_TRY(b->alloc(&b->sums, nf * 2 * c)); VISO_TRY(b->alloc(&b->zero, 8));
+    VISO_TRY(b->alloc(&b->probs, (size_t)b->n_probs));
+    VISO_TRY(b->alloc(&b->skp, nf * 2 * c)); VISO_TRY(b->alloc(&b->sidx, nf * 2 * c)); VISO_TRY(b->alloc(&b->rank, nf * 2 * c));
+    VISO_TRY(b->alloc(&b->bstart, nf * 2 * (VISO_NB + 1))); VISO_TRY(b->alloc(&b->xinfo, nf * 2 * 8)); VISO_TRY(b->alloc(&b->views, nf * 2 + 1));
+    VISO_TRY(b->alloc(&b->qord, nf * 2 * ((c + 63) & ~(size_t)63)));
+    VISO_TRY(b->alloc(&b->res, 3 * nf * c)); VISO_TRY(b->alloc(&b->sorted, 3 * nf * c * 3)); VISO_TRY(b->alloc(&b->pos, 3 * nf * c));
+    VISO_TRY(b->alloc(&b->m_cnt, 3 * nf));
+    VISO_TRY(b->alloc(&b->ovf_q, 3 * nf * c));
+    b->tiles = (b->cap + 63) / 64;
+    VISO_TRY(b->alloc(&b->tile_flag, 3 * nf * (size_t)b->tiles));
+    // per-run counters zeroed by ONE memset: scored[3nf] (u64) | ovf_cnt[3nf] (int) | bad_img[2nf] (int) | bad_any (int)
+    b->zeroed_bytes = 3 * nf * sizeof(unsigned long long) + (3 * nf + 2 * nf + 4) * sizeof(int);
+    VISO_TRY(b->alloc(&b->scored, b->zeroed_bytes / sizeof(unsigned long long) + 1));
+    b->ovf_cnt = reinterpret_cast<int*>(b->scored + 3 * nf);
+    b->bad_img = b->ovf_cnt + 3 * nf;
+    b->bad_any = b->bad_img + 2 * nf;
+    VISO_TRY(b->alloc(&b->x_c, nf * 4 * c)); VISO_TRY(b->alloc(&b->Xp_c, nf * 3 * c));
+    VISO_TRY(b->alloc(&b->join, nf)); VISO_TRY(b->alloc(&b->sitems, nf));
+    VISO_TRY(b->alloc(&b->circ, nf * c * 4)); VISO_TRY(b->alloc(&b->pcl, nf * c * 2)); VISO_TRY(b->alloc(&b->mc, nf));
+    // poses, flags and inlier counts in one block: one blit into the pinned mirror per run (three blocking copies of a
+    // few bytes were 50 us of a one-pair batch's 0.42 ms)
+    b->pose_bytes = nf * (6 * sizeof(double) + 2 * sizeof(int));
+    VISO_TRY(b->alloc_bytes(reinterpret_cast<void**>(&b->tr), b->pose_bytes));
+    b->ok = reinterpret_cast<int*>(b->tr + nf * 6);
+    b->n_inl = b->ok + nf;
+    VISO_TRY(b->alloc(&b->inl, nf * c));
+    if (hipHostMalloc((void**)&b->pose_pin, b->pose_bytes, hipHostMallocDefault) != hipSuccess) {
+        b->pose_pin = nullptr;
+        viso_set_error("viso_batch_create: hipHostMalloc of the pose mirror failed");
+        return VISO_ERR_NOMEM;
+    }
+    memset(b->pose_pin, 0, b->pose_bytes);
+    if (hipHostMalloc((void**)&b->r8pin, sizeof(int) * 4, hipHostMallocDefault) != hipSuccess ||
+        hipEventCreateWithFlags(&b->r8ev, hipEventDisableTiming) != hipSuccess) {
+        viso_set_error("viso_batch_create: pinned buffer / event for the planes' statistics failed");
+        return VISO_ERR_HIP;
+    }
+    if (hipHostMalloc((void**)&b->n_pin, sizeof(int) * VISO_NPIN_SLOTS * 2 * nf, hipHostMallocDefault) != hipSuccess) {
+        b->n_pin = nullptr;
+        viso_set_error("viso_batch_create: hipHostMalloc of the n staging ring failed");
+        return VISO_ERR_NOMEM;
+    }
+    for (int k = 0; k < VISO_NPIN_SLOTS; ++k)
+        if (hipEventCreateWithFlags(&b->n_pin_ev[k], hipEventDisableTiming) != hipSuccess) { b->n_pin_ev[k] = nullptr; return VISO_ERR_HIP; }
+    const bool ok = hipMemset(b->zero, 0, 8 * sizeof(int)) == hipSuccess &&
+                    hipMemset(b->n, 0, nf * 2 * sizeof(int)) == hipSuccess &&
+                    hipMemset(b->m_cnt, 0, 3 * nf * sizeof(int)) == hipSuccess &&
+                    hipMemset(b->mc, 0, nf * sizeof(int)) == hipSuccess &&
+                    hipMemset(b->tr, 0, b->pose_bytes) == hipSuccess &&
+                    hipMemset(b->scored, 0, b->zeroed_bytes) == hipSuccess;
+    if (!ok || build_items(b) < 0) { viso_set_error("viso_batch_create: device initialisation failed"); return VISO_ERR_HIP; }
+    return VISO_OK;
+}
+
 extern "C" viso_batch* viso_batch_create(viso_ctx* ctx, int n_frames, int cap, int dlen) {
     if (!ctx || n_frames <= 0 || cap <= 0 || dlen <= 0) { viso_set_error("viso_batch_create: bad argument"); return nullptr; }
     if (!viso_ctx_live(ctx)) { viso_set_error("viso_batch_create: not a live context handle"); return nullptr; }
     if (hipSetDevice(ctx->device) != hipSuccess) { viso_set_error("hipSetDevice failed"); return nullptr; }
     viso_batch* b = new viso_batch();
-    b->ctx = ctx; b->nf = n_frames; b->cap = cap; b->dlen = dlen; b->iters = 0;
+    b->ctx = ctx; b->nf = n_frames; b->cap = cap; b->dlen = dlen;
     b->n_probs = ((n_frames + 7) / 8) * 24;
-    b->params_set = false; b->timing = false; b->desc_i16 = false;
     b->desc_family.assign((size_t)n_frames, 0);
-    b->ev_next = 0; b->ev_ms_sum = 0; b->ev_n = 0;
-    b->solver_stream = nullptr; b->ev_join = nullptr; b->ev_ransac = nullptr; b->ransac_pending = false;
-    b->ev_stamp[0] = b->ev_stamp[1] = b->ev_stamp[2] = nullptr; b->stamps = false;
-    if (ctx->solver_stream) {
-        if (hipEventCreateWithFlags(&b->ev_join, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&b->ev_ransac, hipEventDisableTiming) != hipSuccess) {
-            viso_set_error("viso_batch_create: event creation failed");
-            if (b->ev_join) hipEventDestroy(b->ev_join);
-            if (b->ev_ransac) hipEventDestroy(b->ev_ransac);
-            delete b;
-            return nullptr;
-        }
-        b->solver_stream = ctx->solver_stream;
-    }
-    b->n_pin = nullptr; b->n_pin_next = 0;
-    for (int k = 0; k < VISO_NPIN_SLOTS; ++k) { b->n_pin_ev[k] = nullptr; b->n_pin_used[k] = false; }
-    b->images = nullptr; b->img_rows = b->img_cols = 0;
-    b->h_resp = nullptr; b->h_tmp_kp = nullptr; b->h_tmp_resp = nullptr; b->h_cnt = nullptr; b->h_slots = 0;
-    b->tr_h = nullptr; b->ok_h = b->cnt_h = b->hq = nullptr; b->samp_h = nullptr; b->rot = nullptr;
-    const size_t nf = (size_t)n_frames, c = (size_t)cap;
-    int r = VISO_OK;
-    auto A = [&](int rr) { if (r >= 0 && rr < 0) r = rr; };
-    A(dalloc(&b->kp, nf * 2 * c)); A(dalloc(&b->desc, nf * 2 * c * dlen)); A(dalloc(&b->n, nf * 2));
-    A(dalloc(&b->packed, nf * 2 * c * VISO_ROW)); A(dalloc(&b->packed8, nf * 2 * c * VISO_ROW8)); A(dalloc(&b->r8cnt, 4)); A(dalloc(&b->sums, nf * 2 * c)); A(dalloc(&b->zero, 8));
-    A(dalloc(&b->probs, (size_t)b->n_probs));
-    A(dalloc(&b->skp, nf * 2 * c)); A(dalloc(&b->sidx, nf * 2 * c)); A(dalloc(&b->rank, nf * 2 * c));
-    A(dalloc(&b->bstart, nf * 2 * (VISO_NB + 1))); A(dalloc(&b->xinfo, nf * 2 * 8)); A(dalloc(&b->views, nf * 2 + 1));
-    A(dalloc(&b->qord, nf * 2 * ((c + 63) & ~(size_t)63)));
-    A(dalloc(&b->res, 3 * nf * c)); A(dalloc(&b->sorted, 3 * nf * c * 3)); A(dalloc(&b->pos, 3 * nf * c));
-    A(dalloc(&b->m_cnt, 3 * nf));
-    A(dalloc(&b->ovf_q, 3 * nf * c));
-    b->tiles = (cap + 63) / 64;
-    A(dalloc(&b->tile_flag, 3 * nf * (size_t)b->tiles));
-    // per-run counters zeroed by ONE memset: scored[3nf] (u64) | ovf_cnt[3nf] (int) | bad_img[2nf] (int) | bad_any (int)
-    b->zeroed_bytes = 3 * nf * sizeof(unsigned long long) + (3 * nf + 2 * nf + 4) * sizeof(int);
-    A(dalloc(&b->scored, b->zeroed_bytes / sizeof(unsigned long long) + 1));
-    b->ovf_cnt = r >= 0 ? reinterpret_cast<int*>(b->scored + 3 * nf) : nullptr;
-    b->bad_img = r >= 0 ? b->ovf_cnt + 3 * nf : nullptr;
-    b->bad_any = r >= 0 ? b->bad_img + 2 * nf : nullptr;
-    A(dalloc(&b->x_c, nf * 4 * c)); A(dalloc(&b->Xp_c, nf * 3 * c));
-    A(dalloc(&b->join, nf)); A(dalloc(&b->sitems, nf));
-    A(dalloc(&b->circ, nf * c * 4)); A(dalloc(&b->pcl, nf * c * 2)); A(dalloc(&b->mc, nf));
-    // poses, flags and inlier counts in one block: one blit into the pinned mirror per run (three blocking copies of a
-    // few bytes were 50 us of a one-pair batch's 0.42 ms)
-    b->pose_bytes = nf * (6 * sizeof(double) + 2 * sizeof(int));
-    { unsigned char* blk = nullptr; A(dalloc(&blk, b->pose_bytes)); b->tr = reinterpret_cast<double*>(blk); }
-    b->ok = r >= 0 ? reinterpret_cast<int*>(b->tr + nf * 6) : nullptr;
-    b->n_inl = r >= 0 ? b->ok + nf : nullptr;
-    A(dalloc(&b->inl, nf * c));
-    if (r >= 0 && hipHostMalloc((void**)&b->pose_pin, b->pose_bytes, hipHostMallocDefault) != hipSuccess) {
-        b->pose_pin = nullptr;
-        viso_set_error("viso_batch_create: hipHostMalloc of the pose mirror failed");
-        r = VISO_ERR_NOMEM;
-    }
-    if (r >= 0) memset(b->pose_pin, 0, b->pose_bytes);
-    if (r >= 0 && (hipHostMalloc((void**)&b->r8pin, sizeof(int) * 4, hipHostMallocDefault) != hipSuccess ||
-                   hipEventCreateWithFlags(&b->r8ev, hipEventDisableTiming) != hipSuccess)) {
-        viso_set_error("viso_batch_create: pinned buffer / event for the planes' statistics failed");
-        r = VISO_ERR_HIP;
-    }
-    if (r >= 0 && hipHostMalloc((void**)&b->n_pin, sizeof(int) * VISO_NPIN_SLOTS * 2 * nf, hipHostMallocDefault) != hipSuccess) {
-        b->n_pin = nullptr;
-        viso_set_error("viso_batch_create: hipHostMalloc of the n staging ring failed");
-        r = VISO_ERR_NOMEM;
-    }
-    for (int k = 0; r >= 0 && k < VISO_NPIN_SLOTS; ++k)
-        if (hipEventCreateWithFlags(&b->n_pin_ev[k], hipEventDisableTiming) != hipSuccess) { b->n_pin_ev[k] = nullptr; r = VISO_ERR_HIP; }
-    if (r < 0) { viso_batch_free(b, false); return nullptr; }
-    bool ok = hipMemset(b->zero, 0, 8 * sizeof(int)) == hipSuccess &&
-              hipMemset(b->n, 0, nf * 2 * sizeof(int)) == hipSuccess &&
-              hipMemset(b->m_cnt, 0, 3 * nf * sizeof(int)) == hipSuccess &&
-              hipMemset(b->mc, 0, nf * sizeof(int)) == hipSuccess &&
-              hipMemset(b->tr, 0, b->pose_bytes) == hipSuccess &&
-              hipMemset(b->scored, 0, b->zeroed_bytes) == hipSuccess;
-    if (!ok || build_items(b) < 0) { viso_set_error("viso_batch_create: device initialisation failed"); viso_batch_free(b, false); return nullptr; }
+    if (create_buffers(b) < 0) { viso_batch_free(b, false); return nullptr; }
     if (!viso_batch_register(ctx, b)) { viso_set_error("viso_batch_create: the context was destroyed meanwhile"); viso_batch_free(b, false); return nullptr; }
     return b;
 }
 
-extern "C" int viso_batch_upload(viso_batch* b, int f0, int nf, const float* kp, const float* desc,
-                                 const int32_t* n) {
-    if (dead(b) || f0 < 0 || nf < 0 || f0 + nf > b->nf || (nf && (!kp || !desc || !n))) { viso_set_error("viso_batch_upload: bad argument"); return VISO_ERR_ARG; }
-    for (int i = 0; i < 2 * nf; ++i)
-        if (n[i] < 0 || n[i] > b->cap) { viso_set_error("viso_batch_upload: n[%d]=%d exceeds cap %d", i, n[i], b->cap); return VISO_ERR_ARG; }
-    if (nf == 0) return VISO_OK;
-    int r;
-    if ((r = enter(b)) < 0) return r;
-    b->desc_i16 = false;
-    for (int t = f0; t < f0 + nf; ++t) b->desc_family[(size_t)t] = 1;
-    // the batch's kernels run on a non-blocking stream: order the copies behind them, then wait (synchronous call)
-    hipStream_t s = b->ctx->stream;
-    const size_t c = (size_t)b->cap;
-    HIP_TRY(hipMemcpyAsync(b->kp + (size_t)f0 * 2 * c, kp, sizeof(float2) * (size_t)nf * 2 * c, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(b->desc + (size_t)f0 * 2 * c * b->dlen, desc, sizeof(float) * (size_t)nf * 2 * c * b->dlen, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(b->n + (size_t)f0 * 2, n, sizeof(int) * (size_t)nf * 2, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipStreamSynchronize(s));
+// The argument checks every upload shares: a live batch, frames f0 .. f0+nf-1 inside it, what else the entry point asks of its
+// arguments (rest_ok, which must not read the batch), and the keypoint counts n[2 nf], where given, within the capacity.
+static int check_upload(const char* where, viso_batch* b, int f0, int nf, const int32_t* n_or_null, bool rest_ok) {
+    if (dead(b) || f0 < 0 || nf < 0 || f0 + nf > b->nf || !rest_ok) { viso_set_error("%s: bad argument", where); return VISO_ERR_ARG; }
+    const int32_t* n = n_or_null;
+    for (int i = 0; n && i < 2 * nf; ++i)
+        if (n[i] < 0 || n[i] > b->cap) { viso_set_error("%s: n[%d]=%d exceeds cap %d", where, i, n[i], b->cap); return VISO_ERR_ARG; }
     return VISO_OK;
 }
 
@@ -418,71 +300,55 @@ static int stage_n_async(viso_batch* b, int f0, int nf, const int32_t* n, hipStr
     return VISO_OK;
 }
 
-// viso_batch_upload without the wait: the three copies are enqueued on the context's stream (behind the batch's
-// previous run, in front of the next one) and the call returns.  The host buffers must stay untouched until the
-// stream has passed the copies (viso_ctx_synchronize, or any result getter of a later run); with buffers from
-// viso_host_alloc the copies are true DMA and overlap the kernels of other contexts.  `n` is validated now and
-// copied through a small pinned slot of the batch, so the caller's n array need not be pinned.
-extern "C" int viso_batch_upload_async(viso_batch* b, int f0, int nf, const float* kp, const float* desc,
-                                       const int32_t* n) {
-    if (dead(b) || f0 < 0 || nf < 0 || f0 + nf > b->nf || (nf && (!kp || !desc || !n))) { viso_set_error("viso_batch_upload_async: bad argument"); return VISO_ERR_ARG; }
-    for (int i = 0; i < 2 * nf; ++i)
-        if (n[i] < 0 || n[i] > b->cap) { viso_set_error("viso_batch_upload_async: n[%d]=%d exceeds cap %d", i, n[i], b->cap); return VISO_ERR_ARG; }
-    if (nf == 0) return VISO_OK;
-    int r;
-    if ((r = enter(b)) < 0) return r;
-    b->desc_i16 = false;
-    for (int t = f0; t < f0 + nf; ++t) b->desc_family[(size_t)t] = 1;
-    hipStream_t s = b->ctx->stream;
-    const size_t c = (size_t)b->cap;
-    HIP_TRY(hipMemcpyAsync(b->kp + (size_t)f0 * 2 * c, kp, sizeof(float2) * (size_t)nf * 2 * c, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(b->desc + (size_t)f0 * 2 * c * b->dlen, desc, sizeof(float) * (size_t)nf * 2 * c * b->dlen, hipMemcpyHostToDevice, s));
-    return stage_n_async(b, f0, nf, n, s);
-}
-
-// The descriptors as int16 (N x dlen, tightly packed): the lossless encoding of the reference's Sobel windows (integers
+// The body of the four descriptor-in uploads.  The three copies are enqueued on the context's stream (the batch's kernels run on
+// that non-blocking stream: behind the batch's previous run, in front of the next one); `n` is validated now and copied through a
+// small pinned slot of the batch, so the caller's n array need not be pinned.  sync: wait for the copies.  Without it the host
+// buffers must stay untouched until the stream has passed the copies (viso_ctx_synchronize, or any result getter of a later
+// run); with buffers from viso_host_alloc the copies are true DMA and overlap the kernels of other contexts.
+// esz 2: the descriptors as int16 (N x dlen, tightly packed): the lossless encoding of the reference's Sobel windows (integers
 // in [-1020, 1020], src/viso.cpp:1004-1024) at half the bytes of the CV_32F boundary layout.  They live in the same
 // device buffer as the f32 rows (reinterpreted), so all frames of a batch must come through ONE of the two families;
-// the last upload decides which pack kernel the next run uses.  sync != 0: wait for the copies.
-static int upload_i16_impl(viso_batch* b, int f0, int nf, const float* kp, const int16_t* desc16, const int32_t* n, bool sync,
-                           const char* who) {
-    if (dead(b) || f0 < 0 || nf < 0 || f0 + nf > b->nf || (nf && (!kp || !desc16 || !n))) { viso_set_error("%s: bad argument", who); return VISO_ERR_ARG; }
-    if (b->dlen > VISO_ROW) { viso_set_error("%s: int16 descriptors need dlen <= %d", who, VISO_ROW); return VISO_ERR_UNSUPPORTED; }
-    for (int i = 0; i < 2 * nf; ++i)
-        if (n[i] < 0 || n[i] > b->cap) { viso_set_error("%s: n[%d]=%d exceeds cap %d", who, i, n[i], b->cap); return VISO_ERR_ARG; }
+// the last upload decides which pack kernel the next run uses.
+static int upload_impl(viso_batch* b, int f0, int nf, const float* kp, const void* desc, size_t esz, const int32_t* n, bool sync,
+                       const char* who) {
+    const bool i16 = esz == sizeof(int16_t);
+    VISO_TRY(check_upload(who, b, f0, nf, n, !nf || (kp && desc && n)));
+    if (i16 && b->dlen > VISO_ROW) { viso_set_error("%s: int16 descriptors need dlen <= %d", who, VISO_ROW); return VISO_ERR_UNSUPPORTED; }
     if (nf == 0) return VISO_OK;
-    int r;
-    if ((r = enter(b)) < 0) return r;
-    b->desc_i16 = true;
-    for (int t = f0; t < f0 + nf; ++t) b->desc_family[(size_t)t] = 2;
+    VISO_TRY(enter(b));
+    b->desc_i16 = i16;
+    for (int t = f0; t < f0 + nf; ++t) b->desc_family[(size_t)t] = i16 ? 2 : 1;
     hipStream_t s = b->ctx->stream;
-    const size_t c = (size_t)b->cap;
-    int16_t* d16 = reinterpret_cast<int16_t*>(b->desc);
+    const size_t c = (size_t)b->cap, row = (size_t)b->dlen * esz;
     HIP_TRY(hipMemcpyAsync(b->kp + (size_t)f0 * 2 * c, kp, sizeof(float2) * (size_t)nf * 2 * c, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d16 + (size_t)f0 * 2 * c * b->dlen, desc16, sizeof(int16_t) * (size_t)nf * 2 * c * b->dlen, hipMemcpyHostToDevice, s));
-    if ((r = stage_n_async(b, f0, nf, n, s)) < 0) return r;
+    HIP_TRY(hipMemcpyAsync(reinterpret_cast<char*>(b->desc) + (size_t)f0 * 2 * c * row, desc, (size_t)nf * 2 * c * row, hipMemcpyHostToDevice, s));
+    VISO_TRY(stage_n_async(b, f0, nf, n, s));
     if (sync) HIP_TRY(hipStreamSynchronize(s));
     return VISO_OK;
 }
+extern "C" int viso_batch_upload(viso_batch* b, int f0, int nf, const float* kp, const float* desc, const int32_t* n) {
+    return upload_impl(b, f0, nf, kp, desc, sizeof(float), n, true, "viso_batch_upload");
+}
+extern "C" int viso_batch_upload_async(viso_batch* b, int f0, int nf, const float* kp, const float* desc, const int32_t* n) {
+    return upload_impl(b, f0, nf, kp, desc, sizeof(float), n, false, "viso_batch_upload_async");
+}
 extern "C" int viso_batch_upload_i16(viso_batch* b, int f0, int nf, const float* kp, const int16_t* desc16, const int32_t* n) {
-    return upload_i16_impl(b, f0, nf, kp, desc16, n, true, "viso_batch_upload_i16");
+    return upload_impl(b, f0, nf, kp, desc16, sizeof(int16_t), n, true, "viso_batch_upload_i16");
 }
 extern "C" int viso_batch_upload_i16_async(viso_batch* b, int f0, int nf, const float* kp, const int16_t* desc16, const int32_t* n) {
-    return upload_i16_impl(b, f0, nf, kp, desc16, n, false, "viso_batch_upload_i16_async");
+    return upload_impl(b, f0, nf, kp, desc16, sizeof(int16_t), n, false, "viso_batch_upload_i16_async");
 }
 
 // The image buffer for rows x cols images (the caller has synchronised the batch's stream).  The Harris response image of
 // viso_batch_detect is sized by the geometry it first met: it goes with the old buffer.
 static int ensure_images(viso_batch* b, int rows, int cols) {
     if (b->images && (rows != b->img_rows || cols != b->img_cols)) {
-        HIP_TRY(hipFree(b->images));
-        b->images = nullptr;
-        if (b->h_resp) HIP_TRY(hipFree(b->h_resp));
-        b->h_resp = nullptr;
-        b->disp_last = 0;   // the maps were of the old geometry (their buffer follows at the next disparity launch)
+        VISO_TRY(b->release(&b->images));
+        VISO_TRY(b->release(&b->h_resp));
+        b->dense.last = 0;   // the maps were of the old geometry (their buffer follows at the next disparity launch)
     }
     if (!b->images) {
-        HIP_TRY(hipMalloc((void**)&b->images, (size_t)rows * cols * 2 * (size_t)b->nf));
+        VISO_TRY(b->alloc(&b->images, (size_t)rows * cols * 2 * (size_t)b->nf));
         b->img_rows = rows; b->img_cols = cols;
     }
     return VISO_OK;
@@ -491,43 +357,103 @@ static int ensure_images(viso_batch* b, int rows, int cols) {
 // Rectification on: raw images of frames f0 .. f0+nf-1 -> the staging buffer -> rectify_remap_kernel -> the image buffer, all on s.
 // One launch per upload: the maps are read once per upload, not once per frame.
 static int upload_raw(viso_batch* b, int f0, int nf, const uint8_t* images, hipStream_t s) {
-    const size_t rper = (size_t)b->raw_rows * b->raw_cols, oper = (size_t)b->img_rows * b->img_cols;
-    HIP_TRY(hipMemcpyAsync(b->raw + (size_t)f0 * 2 * rper, images, rper * 2 * (size_t)nf, hipMemcpyHostToDevice, s));
-    return launch_rectify(s, b->raw + (size_t)f0 * 2 * rper, 2 * rper, rper, b->raw_cols, b->images + (size_t)f0 * 2 * oper, 2 * oper,
-                          oper, b->rmap, b->img_rows, b->img_cols, nf, 2, b->rborder);
+    const BatchRectify& R = b->rect;
+    const size_t rper = (size_t)R.raw_rows * R.raw_cols, oper = (size_t)b->img_rows * b->img_cols;
+    HIP_TRY(hipMemcpyAsync(R.raw + (size_t)f0 * 2 * rper, images, rper * 2 * (size_t)nf, hipMemcpyHostToDevice, s));
+    return launch_rectify(s, R.raw + (size_t)f0 * 2 * rper, 2 * rper, rper, R.raw_cols, b->images + (size_t)f0 * 2 * oper, 2 * oper,
+                          oper, R.map, b->img_rows, b->img_cols, nf, 2, R.border);
+}
+
+// With rectification on, the images of an upload must be the raw ones.
+static int check_raw_geometry(const char* where, viso_batch* b, int rows, int cols) {
+    if (!b->rect.map || (rows == b->rect.raw_rows && cols == b->rect.raw_cols)) return VISO_OK;
+    viso_set_error("%s: rectification is on: the images must be raw, %d x %d (got %d x %d)", where, b->rect.raw_rows, b->rect.raw_cols, rows, cols);
+    return VISO_ERR_ARG;
 }
 
 extern "C" int viso_batch_upload_images_async(viso_batch* b, int f0, int nf, const uint8_t* images, int rows, int cols,
                                               const float* kp, const int32_t* n) {
-    if (dead(b) || f0 < 0 || nf < 0 || f0 + nf > b->nf || rows <= 0 || cols <= 0 || (nf && !images) || ((kp == nullptr) != (n == nullptr))) {
-        viso_set_error("viso_batch_upload_images_async: bad argument");
-        return VISO_ERR_ARG;
-    }
-    if (b->rmap && (rows != b->raw_rows || cols != b->raw_cols)) {
-        viso_set_error("viso_batch_upload_images_async: rectification is on: the images must be raw, %d x %d (got %d x %d)", b->raw_rows,
-                       b->raw_cols, rows, cols);
-        return VISO_ERR_ARG;
-    }
-    if (!b->rmap && (!b->images || rows != b->img_rows || cols != b->img_cols)) {
+    const char* where = "viso_batch_upload_images_async";
+    VISO_TRY(check_upload(where, b, f0, nf, n, rows > 0 && cols > 0 && (!nf || images) && (kp == nullptr) == (n == nullptr)));
+    VISO_TRY(check_raw_geometry(where, b, rows, cols));
+    if (!b->rect.map && (!b->images || rows != b->img_rows || cols != b->img_cols)) {
         viso_set_error("viso_batch_upload_images_async: image buffers not allocated for %d x %d (call viso_batch_upload_images once first)", rows, cols);
         return VISO_ERR_ARG;
     }
-    for (int i = 0; n && i < 2 * nf; ++i)
-        if (n[i] < 0 || n[i] > b->cap) { viso_set_error("viso_batch_upload_images_async: n[%d]=%d exceeds cap %d", i, n[i], b->cap); return VISO_ERR_ARG; }
     if (nf == 0) return VISO_OK;
-    int r;
-    if ((r = enter(b)) < 0) return r;
+    VISO_TRY(enter(b));
     hipStream_t s = b->ctx->stream;
     const size_t per = (size_t)rows * cols, c = (size_t)b->cap;
-    if (b->rmap) {
-        if ((r = upload_raw(b, f0, nf, images, s)) < 0) return r;
-    } else {
-        HIP_TRY(hipMemcpyAsync(b->images + (size_t)f0 * 2 * per, images, per * 2 * (size_t)nf, hipMemcpyHostToDevice, s));
-    }
+    if (b->rect.map) VISO_TRY(upload_raw(b, f0, nf, images, s));
+    else HIP_TRY(hipMemcpyAsync(b->images + (size_t)f0 * 2 * per, images, per * 2 * (size_t)nf, hipMemcpyHostToDevice, s));
     if (kp) {
         HIP_TRY(hipMemcpyAsync(b->kp + (size_t)f0 * 2 * c, kp, sizeof(float2) * (size_t)nf * 2 * c, hipMemcpyHostToDevice, s));
         return stage_n_async(b, f0, nf, n, s);
     }
+    return VISO_OK;
+}
+
+extern "C" int viso_batch_upload_images(viso_batch* b, int f0, int nf, const uint8_t* images, int rows, int cols,
+                                        const float* kp, const int32_t* n) {
+    const char* where = "viso_batch_upload_images";
+    VISO_TRY(check_upload(where, b, f0, nf, n, rows > 0 && cols > 0 && (!nf || images) && (kp == nullptr) == (n == nullptr)));
+    VISO_TRY(check_raw_geometry(where, b, rows, cols));
+    VISO_TRY(enter(b));
+    const size_t c = (size_t)b->cap;
+    if (b->rect.map) {   // raw images: staged and rectified on the batch's stream, behind the run in flight
+        if (nf == 0) return VISO_OK;
+        hipStream_t s = b->ctx->stream;
+        VISO_TRY(upload_raw(b, f0, nf, images, s));
+        if (kp) {
+            HIP_TRY(hipMemcpyAsync(b->kp + (size_t)f0 * 2 * c, kp, sizeof(float2) * (size_t)nf * 2 * c, hipMemcpyHostToDevice, s));
+            HIP_TRY(hipMemcpyAsync(b->n + (size_t)f0 * 2, n, sizeof(int) * (size_t)nf * 2, hipMemcpyHostToDevice, s));
+        }
+        HIP_TRY(hipStreamSynchronize(s));
+        return VISO_OK;
+    }
+    HIP_TRY(hipStreamSynchronize(b->ctx->stream));   // a run in flight may still read what the (null-stream) copies below rewrite
+    VISO_TRY(ensure_images(b, rows, cols));
+    const size_t per = (size_t)rows * cols;
+    if (nf == 0) return VISO_OK;
+    HIP_TRY(hipMemcpy(b->images + (size_t)f0 * 2 * per, images, per * 2 * (size_t)nf, hipMemcpyHostToDevice));
+    if (kp) {   // keypoints may instead come from viso_batch_detect
+        HIP_TRY(hipMemcpy(b->kp + (size_t)f0 * 2 * c, kp, sizeof(float2) * (size_t)nf * 2 * c, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(b->n + (size_t)f0 * 2, n, sizeof(int) * (size_t)nf * 2, hipMemcpyHostToDevice));
+    }
+    return VISO_OK;
+}
+
+// Opt-in rectification of raw images (not in the reference; rectify.hip).  Synchronous like the other setters: the batch's work
+// in flight finishes first, then the maps are quantised on the host and the buffers (re)allocated.
+extern "C" int viso_batch_set_rectify(viso_batch* b, int raw_rows, int raw_cols, int out_rows, int out_cols, const float* mapxL,
+                                      const float* mapyL, const float* mapxR, const float* mapyR, int border) {
+    const int given = (mapxL != nullptr) + (mapyL != nullptr) + (mapxR != nullptr) + (mapyR != nullptr);
+    if (dead(b) || (given != 0 && given != 4) ||
+        (given == 4 && (!rect_geometry_ok(raw_rows, raw_cols, out_rows, out_cols) || border < 0 || border > 255))) {
+        viso_set_error("viso_batch_set_rectify: bad argument (sizes > 0, border 0..255, all four maps or none)");
+        return VISO_ERR_ARG;
+    }
+    VISO_TRY(enter(b));
+    VISO_TRY(batch_sync(b));
+    BatchRectify& R = b->rect;
+    VISO_TRY(b->release(&R.map));
+    if (given == 0) {   // off: the staging buffer goes too; the image buffer stays (the next upload decides its geometry)
+        R.raw_bytes = 0; R.raw_rows = R.raw_cols = 0;
+        return b->release(&R.raw);
+    }
+    const size_t oper = (size_t)out_rows * out_cols;
+    std::vector<RectEntry> q(2 * oper);
+    rect_quantise(mapxL, mapyL, oper, raw_rows, raw_cols, q.data());
+    rect_quantise(mapxR, mapyR, oper, raw_rows, raw_cols, q.data() + oper);
+    VISO_TRY(ensure_images(b, out_rows, out_cols));
+    VISO_TRY(b->fit(&R.raw, &R.raw_bytes, (size_t)raw_rows * raw_cols * 2 * (size_t)b->nf));
+    VISO_TRY(b->alloc(&R.map, 2 * oper));
+    if (hipMemcpy(R.map, q.data(), sizeof(RectEntry) * 2 * oper, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)b->release(&R.map);
+        viso_set_error("viso_batch_set_rectify: copying the maps failed");
+        return VISO_ERR_HIP;
+    }
+    R.raw_rows = raw_rows; R.raw_cols = raw_cols; R.border = border;
     return VISO_OK;
 }
 
@@ -553,31 +479,29 @@ extern "C" int viso_batch_set_params(viso_batch* b, const viso_match_params* ste
         viso_set_error("viso_batch_set_params: bad argument");
         return VISO_ERR_ARG;
     }
-    int r0;
-    if ((r0 = enter(b)) < 0) return r0;
+    VISO_TRY(enter(b));
     // kernels of a run still in flight read the solver items rewritten below (null-stream copies do not order
     // against the context's non-blocking stream)
-    { const int rs_ = batch_sync(b); if (rs_ < 0) return rs_; }
+    VISO_TRY(batch_sync(b));
     fill_match_params(&b->mp[0], stereo);
     fill_match_params(&b->mp[1], temporal);
     fill_solver_params(&b->sp, p);
     b->seed = seed; b->first_frame = first_frame_index;
     if (p->ransac_iter != b->iters || !b->tr_h) {
-        free_solver_bufs(b);
         b->iters = p->ransac_iter;
         const size_t k = (size_t)b->nf * (size_t)(b->iters > 0 ? b->iters : 1);
-        int r;
-        if ((r = dalloc(&b->tr_h, k * 6)) < 0 || (r = dalloc(&b->ok_h, k)) < 0 || (r = dalloc(&b->cnt_h, k)) < 0 ||
-            (r = dalloc(&b->hq, k + 2)) < 0 || (r = dalloc(&b->samp_h, k * 3)) < 0 ||
-            (r = dalloc(&b->rot, (size_t)b->nf * viso_rot_bytes(b->iters))) < 0) return r;
+        (void)b->release(&b->tr_h); (void)b->release(&b->ok_h); (void)b->release(&b->cnt_h);
+        (void)b->release(&b->hq); (void)b->release(&b->samp_h); (void)b->release(&b->rot);
+        VISO_TRY(b->alloc(&b->tr_h, k * 6)); VISO_TRY(b->alloc(&b->ok_h, k)); VISO_TRY(b->alloc(&b->cnt_h, k));
+        VISO_TRY(b->alloc(&b->hq, k + 2)); VISO_TRY(b->alloc(&b->samp_h, k * 3));
+        VISO_TRY(b->alloc(&b->rot, (size_t)b->nf * viso_rot_bytes(b->iters)));
         // frame 0 has no solve: its rows are never written, and viso_batch_get_hypotheses hands them out with the rest
         HIP_TRY(hipMemset(b->tr_h, 0, sizeof(double) * 6 * k));
         HIP_TRY(hipMemset(b->ok_h, 0, sizeof(int) * k));
         HIP_TRY(hipMemset(b->cnt_h, 0, sizeof(int) * k));
         HIP_TRY(hipMemset(b->hq, 0, sizeof(int) * 2));   // the list of undecided hypotheses starts empty; every chain leaves it empty
     }
-    int r = build_solver_items(b);
-    if (r < 0) return r;
+    VISO_TRY(build_solver_items(b));
     b->params_set = true;
     return VISO_OK;
 }
@@ -588,124 +512,39 @@ extern "C" int viso_batch_kernel_timing(viso_batch* b, int enable) {
     return VISO_OK;
 }
 
-// The speckle filter over the batch's maps, in place, behind the method's launches on the context's stream (viso_batch_set_speckle
-// on with max_size > 0), group by group through the batch's workspace.
-static bool speckle_active(const viso_batch* b) { return b->spk_on && b->spk_p.max_size > 0; }
-
-static int launch_batch_speckle(viso_batch* b) {
-    const int group = speckle_group_frames(b->img_rows, b->img_cols, b->nf);
-    if (group < 1) return speckle_nomem("viso_batch_run", b->img_rows, b->img_cols);
-    const size_t want = speckle_frame_bytes(b->img_rows, b->img_cols) * (size_t)group;
-    if (b->spk_ws && b->spk_ws_bytes != want) {
-        int r;
-        if ((r = batch_sync(b)) < 0) return r;
-        HIP_TRY(hipFree(b->spk_ws));
-        b->spk_ws = nullptr;
-    }
-    if (!b->spk_ws) {
-        if (hipMalloc(&b->spk_ws, want) != hipSuccess) {
-            (void)hipGetLastError();
-            b->spk_ws = nullptr;
-            viso_set_error("viso_batch_run: cannot allocate the %zu-byte speckle workspace (viso_speckle_set_workspace_cap)", want);
-            return VISO_ERR_NOMEM;
-        }
-        b->spk_ws_bytes = want;
-    }
-    return launch_speckle(b->ctx->stream, b->disp, (size_t)b->img_rows * b->img_cols, b->img_rows, b->img_cols, b->nf, &b->spk_p,
-                          b->spk_ws, group);
-}
-
-// The disparity of every frame's resident pair on the context's stream (viso_batch_set_disparity on, images present, geometry
-// checked by the caller).  The maps' buffer follows the image geometry: (re)allocated here, after the batch's work in flight.
-static int launch_batch_disparity(viso_batch* b) {
-    const size_t per = (size_t)b->img_rows * b->img_cols;
-    if (b->disp && (b->disp_rows != b->img_rows || b->disp_cols != b->img_cols)) {
-        int r;
-        if ((r = batch_sync(b)) < 0) return r;
-        HIP_TRY(hipFree(b->disp));
-        b->disp = nullptr;
-    }
-    if (!b->disp) {
-        HIP_TRY(hipMalloc((void**)&b->disp, sizeof(int16_t) * per * (size_t)b->nf));
-        b->disp_rows = b->img_rows; b->disp_cols = b->img_cols;
-    }
-    b->disp_last = 0;
-    HIP_TRY(hipSetDevice(b->ctx->device));
-    if (b->sgm_on) {   // the same maps by semi-global matching, group by group through the batch's workspace
-        const int group = sgm_group_frames(b->img_rows, b->img_cols, b->sgm_p.num_disp, b->nf);
-        if (group < 1) return sgm_nomem("viso_batch_run", b->img_rows, b->img_cols, b->sgm_p.num_disp);
-        const size_t want = sgm_frame_bytes(b->img_rows, b->img_cols, b->sgm_p.num_disp) * (size_t)group;
-        if (b->sgm_ws && b->sgm_ws_bytes != want) {
-            int r;
-            if ((r = batch_sync(b)) < 0) return r;
-            HIP_TRY(hipFree(b->sgm_ws));
-            b->sgm_ws = nullptr;
-        }
-        if (!b->sgm_ws) {
-            if (hipMalloc(&b->sgm_ws, want) != hipSuccess) {
-                (void)hipGetLastError();
-                b->sgm_ws = nullptr;
-                viso_set_error("viso_batch_run: cannot allocate the %zu-byte SGM workspace (viso_sgm_set_workspace_cap)", want);
-                return VISO_ERR_NOMEM;
-            }
-            b->sgm_ws_bytes = want;
-        }
-        const int r = launch_sgm(b->ctx->stream, b->images, 2 * per, per, b->img_rows, b->img_cols, b->nf, &b->sgm_p, b->disp, per,
-                                 b->sgm_ws, group);
-        if (r < 0) return r;
-    } else {
-        const int r = launch_disparity(b->ctx->stream, b->images, 2 * per, per, b->img_rows, b->img_cols, b->nf, &b->disp_p, b->disp, per);
-        if (r < 0) return r;
-    }
-    if (speckle_active(b)) {
-        const int r = launch_batch_speckle(b);
-        if (r < 0) return r;
-    }
-    b->disp_last = 1;
-    return VISO_OK;
-}
-
-static int run_matcher_impl(viso_batch* b, bool from_images) {
-    if (!dead(b)) b->cov_last = b->ref_last = b->win_last = 0;   // the records of an earlier run are not this run's
+// What a run refuses before anything is launched.  Where the dense maps are on, dense_preflight follows (viso_batch_run_images).
+static int run_matcher_check(viso_batch* b, bool from_images) {
+    if (!dead(b)) b->est.cov.last = b->est.ref.last = b->est.win.last = 0;   // the records of an earlier run are not this run's
     if (dead(b) || !b->params_set) { viso_set_error("viso_batch_run: parameters not set"); return VISO_ERR_ARG; }
     if (from_images && (!b->images || b->dlen != VISO_DESC_LEN)) {
         viso_set_error("viso_batch_run_images: no images uploaded (or descriptor length is not 121)");
         return VISO_ERR_ARG;
     }
-    if (!from_images && (b->disp_on || b->sgm_on)) {
+    if (from_images) return VISO_OK;
+    if (b->dense.on()) {
         viso_set_error("viso_batch_run: dense disparity (viso_batch_set_disparity, viso_batch_set_sgm) needs the images: use viso_batch_run_images, "
                        "or turn it off for descriptor-in runs");
         return VISO_ERR_ARG;
     }
-    if (from_images && (b->disp_on || b->sgm_on) && !disparity_geometry_ok(b->img_rows, b->img_cols)) {
-        viso_set_error("viso_batch_run_images: dense disparity of %d-column images is beyond this build (2048 at most)", b->img_cols);
-        return VISO_ERR_UNSUPPORTED;
-    }
-    if (from_images && b->sgm_on && sgm_group_frames(b->img_rows, b->img_cols, b->sgm_p.num_disp, b->nf) < 1)
-        return sgm_nomem("viso_batch_run_images", b->img_rows, b->img_cols, b->sgm_p.num_disp);
-    if (from_images && (b->disp_on || b->sgm_on) && speckle_active(b) && !speckle_geometry_ok(b->img_rows, b->img_cols)) {
-        viso_set_error("viso_batch_run_images: the speckle filter of %d x %d maps is beyond this build (2^31 - 1 pixels)", b->img_rows, b->img_cols);
-        return VISO_ERR_UNSUPPORTED;
-    }
-    if (from_images && (b->disp_on || b->sgm_on) && speckle_active(b) && speckle_group_frames(b->img_rows, b->img_cols, b->nf) < 1)
-        return speckle_nomem("viso_batch_run_images", b->img_rows, b->img_cols);
-    if (!from_images && b->subpix) {
+    if (b->subpix) {
         viso_set_error("viso_batch_run: sub-pixel refinement (viso_batch_set_subpixel %d) needs the images: use viso_batch_run_images, "
                        "or set mode 0 for descriptor-in runs", b->subpix);
         return VISO_ERR_ARG;
     }
-    if (!from_images) {   // f32 rows and int16 rows share one device buffer: a run over frames of both families would
-                          // reinterpret one of them (garbage matches, no error) -- refuse it
-        bool f32 = false, i16 = false;
-        for (signed char f : b->desc_family) { f32 = f32 || f == 1; i16 = i16 || f == 2; }
-        if (f32 && i16) {
-            viso_set_error("viso_batch_run: frames of this batch were uploaded through both viso_batch_upload (f32 rows) and "
-                           "viso_batch_upload_i16 (int16 rows); upload all frames through one family");
-            return VISO_ERR_ARG;
-        }
+    // f32 rows and int16 rows share one device buffer: a run over frames of both families would reinterpret one of them (garbage
+    // matches, no error) -- refuse it
+    bool f32 = false, i16 = false;
+    for (signed char f : b->desc_family) { f32 = f32 || f == 1; i16 = i16 || f == 2; }
+    if (f32 && i16) {
+        viso_set_error("viso_batch_run: frames of this batch were uploaded through both viso_batch_upload (f32 rows) and "
+                       "viso_batch_upload_i16 (int16 rows); upload all frames through one family");
+        return VISO_ERR_ARG;
     }
-    int r;
-    if ((r = enter(b)) < 0) return r;
+    return VISO_OK;
+}
+
+static int run_matcher_launch(viso_batch* b, bool from_images) {
+    VISO_TRY(enter(b));
     hipStream_t s = b->ctx->stream;
     const int with_sums = pack_extras(b->ctx->matcher_variant, b->dlen);   // block sums / 8-bit planes: what the selected temporal kernel reads
     // the run's counters (scored, ovf_cnt, bad_img, bad_any) are zeroed by the first kernel of the run, not by a memset
@@ -725,14 +564,13 @@ static int run_matcher_impl(viso_batch* b, bool from_images) {
         b->r8last = b->ctx->row8_force >= 0 ? b->ctx->row8_force : b->r8shift;
     }
     const int r8s = b->r8last;
-    if ((r = launch_sort_kp(s, b->views, b->nf * 2, b->cap, reinterpret_cast<uint32_t*>(b->scored), (int)(b->zeroed_bytes / 4), r8cnt)) < 0) return r;
-    if (from_images) {   // Sobel windows straight into packed rows (never bad: integers in [-1020,1020])
-        if ((r = launch_extract_pack(s, b->views, b->nf * 2, b->cap, b->images, b->img_rows, b->img_cols, with_sums, r8s, r8cnt)) < 0) return r;
-    } else {
-        if (b->desc_i16) r = launch_pack_i16(s, b->views, b->nf * 2, b->cap, b->dlen, reinterpret_cast<const int16_t*>(b->desc), with_sums, r8s, r8cnt);
-        else r = launch_pack(s, b->views, b->nf * 2, b->cap, b->dlen, b->bad_img, b->bad_any, with_sums, r8s, r8cnt);
-        if (r < 0) return r;
-    }
+    VISO_TRY(launch_sort_kp(s, b->views, b->nf * 2, b->cap, reinterpret_cast<uint32_t*>(b->scored), (int)(b->zeroed_bytes / 4), r8cnt));
+    if (from_images)   // Sobel windows straight into packed rows (never bad: integers in [-1020,1020])
+        VISO_TRY(launch_extract_pack(s, b->views, b->nf * 2, b->cap, b->images, b->img_rows, b->img_cols, with_sums, r8s, r8cnt));
+    else if (b->desc_i16)
+        VISO_TRY(launch_pack_i16(s, b->views, b->nf * 2, b->cap, b->dlen, reinterpret_cast<const int16_t*>(b->desc), with_sums, r8s, r8cnt));
+    else
+        VISO_TRY(launch_pack(s, b->views, b->nf * 2, b->cap, b->dlen, b->bad_img, b->bad_any, with_sums, r8s, r8cnt));
     if (r8cnt) {   // the sample's counts on their way to the host
         HIP_TRY(hipMemcpyAsync(b->r8pin, b->r8cnt, sizeof(int) * 4, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipEventRecord(b->r8ev, s));
@@ -753,14 +591,14 @@ static int run_matcher_impl(viso_batch* b, bool from_images) {
             b->ev_next = (b->ev_next + 1) % VISO_EVENT_POOL;
         }
     }
-    if ((r = launch_match_timed(s, b->probs, b->n_probs, b->cap, b->dlen, b->mp, b->bad_any, e0, e1, 1, b->ctx->matcher_variant, b->ovf_q, b->ovf_cnt, r8s, from_images ? 0 : 1)) < 0) return r;
-    if ((r = launch_sort(s, b->probs, b->n_probs, b->cap)) < 0) return r;
+    VISO_TRY(launch_match_timed(s, b->probs, b->n_probs, b->cap, b->dlen, b->mp, b->bad_any, e0, e1, 1, b->ctx->matcher_variant, b->ovf_q, b->ovf_cnt, r8s, from_images ? 0 : 1));
+    VISO_TRY(launch_sort(s, b->probs, b->n_probs, b->cap));
     b->uv_mode = 0;
     if (from_images && b->subpix) {   // the stereo lists are final: refine their right-image points (which = 0 lists come first)
         const size_t per = (size_t)b->img_rows * b->img_cols;
-        if ((r = launch_subpixel(s, b->images, 2 * per, per, b->img_rows, b->img_cols, b->kp, 2 * (size_t)b->cap, b->cap, b->sorted,
+        VISO_TRY(launch_subpixel(s, b->images, 2 * per, per, b->img_rows, b->img_cols, b->kp, 2 * (size_t)b->cap, b->cap, b->sorted,
                                  3 * (size_t)b->cap, b->m_cnt, b->nf, b->subpix, b->uv, b->packed, 2 * (size_t)b->cap * VISO_ROW, b->rank,
-                                 2 * (size_t)b->cap)) < 0) return r;
+                                 2 * (size_t)b->cap));
         b->uv_mode = b->subpix;
     }
     if (b->stamps) HIP_TRY(hipEventRecord(b->ev_stamp[2], s));   // re-recorded behind the solver by run_rest
@@ -771,8 +609,7 @@ static int run_matcher_impl(viso_batch* b, bool from_images) {
 // the run is stamped by viso_batch_run* itself once stamping is on (i.e. after the first viso_batch_stamp call).
 extern "C" int viso_batch_stamp(viso_batch* b, int which) {
     if (dead(b) || which < 0 || which > 1) { viso_set_error("viso_batch_stamp: bad argument"); return VISO_ERR_ARG; }
-    int r;
-    if ((r = enter(b)) < 0) return r;
+    VISO_TRY(enter(b));
     for (int k = 0; k < 3; ++k)
         if (!b->ev_stamp[k]) HIP_TRY(hipEventCreate(&b->ev_stamp[k]));
     if (!b->stamps) {   // all three recorded once, so that viso_batch_stamp_ms never meets an unrecorded event
@@ -786,7 +623,7 @@ extern "C" int viso_batch_stamp(viso_batch* b, int which) {
 // Waits for the batch; ms[0] = stamp 0 -> stamp 1 (the uploads), ms[1] = stamp 1 -> behind the run's last kernel.
 extern "C" int viso_batch_stamp_ms(viso_batch* b, double ms[2]) {
     if (dead(b) || !ms || !b->stamps) { viso_set_error("viso_batch_stamp_ms: no stamps taken"); return VISO_ERR_ARG; }
-    { const int rs_ = batch_sync(b); if (rs_ < 0) return rs_; }
+    VISO_TRY(batch_sync(b));
     float a = 0, c = 0;
     HIP_TRY(hipEventElapsedTime(&a, b->ev_stamp[0], b->ev_stamp[1]));
     HIP_TRY(hipEventElapsedTime(&c, b->ev_stamp[1], b->ev_stamp[2]));
@@ -794,63 +631,55 @@ extern "C" int viso_batch_stamp_ms(viso_batch* b, double ms[2]) {
     return VISO_OK;
 }
 
-extern "C" int viso_batch_run_matcher(viso_batch* b) { return run_matcher_impl(b, false); }
+static int run_rest(viso_batch* b) {
+    VISO_TRY(enter(b));
+    hipStream_t s = b->ctx->stream;
+    hipStream_t ss = b->solver_stream ? b->solver_stream : s;
+    // the circle join rewrites what the previous run's RANSAC reads (x_c, Xp_c, mc)
+    if (ss != s && b->ransac_pending) HIP_TRY(hipStreamWaitEvent(s, b->ev_ransac, 0));
+    if (b->nf > 1) {
+        VISO_TRY(launch_circle_join(s, b->join, b->nf - 1, b->sp, b->uv_mode != 0));   // :1245-1247 (the rows it joins), :1282, 1292-1305
+        if (ss != s) {
+            HIP_TRY(hipEventRecord(b->ev_join, s));
+            HIP_TRY(hipStreamWaitEvent(ss, b->ev_join, 0));
+        }
+        // vector<double> tr(6,0), :1312: ransac_refit_kernel writes the zeros itself where no solve succeeds
+        VISO_TRY(launch_ransac(ss, b->sitems, b->nf - 1, b->iters, b->seed, b->sp, b->hq, b->ctx->gn_split, b->cap));   // :1313
+        // the run's poses, flags and inlier counts into the pinned mirror (the kernel writes over PCIe; viso_batch_get_poses
+        // waits for the streams and reads host memory)
+        VISO_TRY(plain_blit(ss, b->tr, b->pose_pin, b->pose_bytes / 4));
+        VISO_TRY(batch_launch_estimators(b, ss));
+    }
+    b->est.cov.last = b->est.cov.mode;
+    b->est.ref.last = b->est.ref.mode;
+    b->est.win.last = b->est.win_K;
+    if (ss != s) {
+        HIP_TRY(hipEventRecord(b->ev_ransac, ss));
+        b->ransac_pending = true;
+    }
+    if (b->stamps) HIP_TRY(hipEventRecord(b->ev_stamp[2], ss));
+    return VISO_OK;
+}
 
-static int run_rest(viso_batch* b);
-static bool slot_ok(viso_batch* b, int which, int t);
+extern "C" int viso_batch_run_matcher(viso_batch* b) {
+    VISO_TRY(run_matcher_check(b, false));
+    return run_matcher_launch(b, false);
+}
 
 extern "C" int viso_batch_run(viso_batch* b) {
-    int r = run_matcher_impl(b, false);
-    if (r < 0) return r;
+    VISO_TRY(viso_batch_run_matcher(b));
     return run_rest(b);
 }
 
 // Dense disparity (when on) goes on the context's stream behind everything else of the run: the circle join and the RANSAC stream
 // are issued first, so the poses do not queue behind it, and it stays outside the run's time stamps.
 extern "C" int viso_batch_run_images(viso_batch* b, int matcher_only) {
-    int r = run_matcher_impl(b, true);
-    if (r < 0) return r;
-    if (!matcher_only && (r = run_rest(b)) < 0) return r;
-    return b->disp_on || b->sgm_on ? launch_batch_disparity(b) : VISO_OK;
-}
-
-extern "C" int viso_batch_upload_images(viso_batch* b, int f0, int nf, const uint8_t* images, int rows, int cols,
-                                        const float* kp, const int32_t* n) {
-    if (dead(b) || f0 < 0 || nf < 0 || f0 + nf > b->nf || rows <= 0 || cols <= 0 || (nf && !images) || ((kp == nullptr) != (n == nullptr))) {
-        viso_set_error("viso_batch_upload_images: bad argument");
-        return VISO_ERR_ARG;
-    }
-    for (int i = 0; n && i < 2 * nf; ++i)
-        if (n[i] < 0 || n[i] > b->cap) { viso_set_error("viso_batch_upload_images: n[%d]=%d exceeds cap %d", i, n[i], b->cap); return VISO_ERR_ARG; }
-    if (b->rmap && (rows != b->raw_rows || cols != b->raw_cols)) {
-        viso_set_error("viso_batch_upload_images: rectification is on: the images must be raw, %d x %d (got %d x %d)", b->raw_rows,
-                       b->raw_cols, rows, cols);
-        return VISO_ERR_ARG;
-    }
-    int r0;
-    if ((r0 = enter(b)) < 0) return r0;
-    const size_t c = (size_t)b->cap;
-    if (b->rmap) {   // raw images: staged and rectified on the batch's stream, behind the run in flight
-        if (nf == 0) return VISO_OK;
-        hipStream_t s = b->ctx->stream;
-        if ((r0 = upload_raw(b, f0, nf, images, s)) < 0) return r0;
-        if (kp) {
-            HIP_TRY(hipMemcpyAsync(b->kp + (size_t)f0 * 2 * c, kp, sizeof(float2) * (size_t)nf * 2 * c, hipMemcpyHostToDevice, s));
-            HIP_TRY(hipMemcpyAsync(b->n + (size_t)f0 * 2, n, sizeof(int) * (size_t)nf * 2, hipMemcpyHostToDevice, s));
-        }
-        HIP_TRY(hipStreamSynchronize(s));
-        return VISO_OK;
-    }
-    HIP_TRY(hipStreamSynchronize(b->ctx->stream));   // a run in flight may still read what the (null-stream) copies below rewrite
-    if ((r0 = ensure_images(b, rows, cols)) < 0) return r0;
-    const size_t per = (size_t)rows * cols;
-    if (nf == 0) return VISO_OK;
-    HIP_TRY(hipMemcpy(b->images + (size_t)f0 * 2 * per, images, per * 2 * (size_t)nf, hipMemcpyHostToDevice));
-    if (kp) {   // keypoints may instead come from viso_batch_detect
-        HIP_TRY(hipMemcpy(b->kp + (size_t)f0 * 2 * c, kp, sizeof(float2) * (size_t)nf * 2 * c, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(b->n + (size_t)f0 * 2, n, sizeof(int) * (size_t)nf * 2, hipMemcpyHostToDevice));
-    }
-    return VISO_OK;
+    const char* where = "viso_batch_run_images";
+    VISO_TRY(run_matcher_check(b, true));
+    if (b->dense.on()) VISO_TRY(dense_preflight(b, where));
+    VISO_TRY(run_matcher_launch(b, true));
+    if (!matcher_only) VISO_TRY(run_rest(b));
+    return b->dense.on() ? launch_batch_disparity(b, where) : VISO_OK;
 }
 
 // HarrisBinnedFeatureDetector on every uploaded image (src/viso.cpp:1226-1227): fills the batch's
@@ -865,38 +694,27 @@ extern "C" int viso_batch_detect(viso_batch* b, int n_features, int nbinx, int n
     const int nbins = nbinx * nbiny, per = n_features / nbins;
     if ((long long)nbins * per > b->cap) { viso_set_error("viso_batch_detect: %d features exceed the batch capacity %d", nbins * per, b->cap); return VISO_ERR_ARG; }
     const int n_img = b->nf * 2;
-    int r0;
-    if ((r0 = enter(b)) < 0) return r0;
+    VISO_TRY(enter(b));
     hipStream_t s = b->ctx->stream;
     const bool fused = harris_fused_lds(b->img_rows, b->img_cols, nbinx, nbiny, per) != 0;   // no response image then
-    if (!fused && !b->h_resp) HIP_TRY(hipMalloc((void**)&b->h_resp, sizeof(float) * (size_t)n_img * b->img_rows * b->img_cols));
+    if (!fused && !b->h_resp) VISO_TRY(b->alloc(&b->h_resp, (size_t)n_img * b->img_rows * b->img_cols));
     const size_t slots = (size_t)nbins * (per > 0 ? per : 1);
     if (slots > b->h_slots) {
         HIP_TRY(hipStreamSynchronize(s));
-        if (b->h_tmp_kp) HIP_TRY(hipFree(b->h_tmp_kp));
-        if (b->h_tmp_resp) HIP_TRY(hipFree(b->h_tmp_resp));
-        if (b->h_cnt) HIP_TRY(hipFree(b->h_cnt));
-        b->h_tmp_kp = nullptr; b->h_tmp_resp = nullptr; b->h_cnt = nullptr;
-        HIP_TRY(hipMalloc((void**)&b->h_tmp_kp, sizeof(float2) * slots * n_img));
-        HIP_TRY(hipMalloc((void**)&b->h_tmp_resp, sizeof(float) * slots * n_img));
-        HIP_TRY(hipMalloc((void**)&b->h_cnt, sizeof(int) * (size_t)16384 * n_img));
+        VISO_TRY(b->release(&b->h_tmp_kp)); VISO_TRY(b->release(&b->h_tmp_resp)); VISO_TRY(b->release(&b->h_cnt));
+        VISO_TRY(b->alloc(&b->h_tmp_kp, slots * n_img));
+        VISO_TRY(b->alloc(&b->h_tmp_resp, slots * n_img));
+        VISO_TRY(b->alloc(&b->h_cnt, (size_t)16384 * n_img));
         b->h_slots = slots;
     }
-    int r;
     if (per == 0) { HIP_TRY(hipMemsetAsync(b->n, 0, sizeof(int) * (size_t)n_img, s)); return VISO_OK; }
     if (fused) {
         const size_t pb = harris_strip_bytes(n_img, b->img_rows, b->img_cols, nbinx, nbiny, per);   // 0: the wave-per-bin kernel
-        if (pb > b->h_part_bytes) {
-            HIP_TRY(hipStreamSynchronize(s));
-            if (b->h_part) HIP_TRY(hipFree(b->h_part));
-            b->h_part = nullptr; b->h_part_bytes = 0;
-            HIP_TRY(hipMalloc(&b->h_part, pb));
-            b->h_part_bytes = pb;
-        }
+        if (pb) VISO_TRY(b->fit(&b->h_part, &b->h_part_bytes, pb, true));   // grows only
         return launch_harris_detect(s, b->images, n_img, b->img_rows, b->img_cols, n_features, nbinx, nbiny, k, b->h_tmp_kp,
                                     b->h_tmp_resp, b->h_cnt, b->kp, nullptr, b->n, b->cap, (size_t)b->cap, pb ? b->h_part : nullptr);
     }
-    if ((r = launch_harris_response(s, b->images, n_img, b->img_rows, b->img_cols, k, b->h_resp)) < 0) return r;
+    VISO_TRY(launch_harris_response(s, b->images, n_img, b->img_rows, b->img_cols, k, b->h_resp));
     return launch_harris_bins(s, b->h_resp, n_img, b->img_rows, b->img_cols, n_features, nbinx, nbiny, b->h_tmp_kp,
                               b->h_tmp_resp, b->h_cnt, b->kp, nullptr, b->n, b->cap, (size_t)b->cap);
 }
@@ -904,7 +722,7 @@ extern "C" int viso_batch_detect(viso_batch* b, int n_features, int nbinx, int n
 // Keypoints of frame t, image side (after viso_batch_detect or an upload).
 extern "C" int viso_batch_get_keypoints(viso_batch* b, int t, int side, float* kp, int* n_out) {
     if (dead(b) || t < 0 || t >= b->nf || side < 0 || side > 1 || !n_out) { viso_set_error("viso_batch_get_keypoints: bad argument"); return VISO_ERR_ARG; }
-    { const int rs_ = batch_sync(b); if (rs_ < 0) return rs_; }
+    VISO_TRY(batch_sync(b));
     int n = 0;
     HIP_TRY(hipMemcpy(&n, b->n + (size_t)t * 2 + side, sizeof(int), hipMemcpyDeviceToHost));
     if (n > 0 && kp) HIP_TRY(hipMemcpy(kp, b->kp + ((size_t)t * 2 + side) * b->cap, sizeof(float2) * (size_t)n, hipMemcpyDeviceToHost));
@@ -916,12 +734,11 @@ extern "C" int viso_batch_get_keypoints(viso_batch* b, int t, int side, float* k
 // is allocated on the first request, and the join items are rebuilt to point at it (after the batch's work in flight).
 extern "C" int viso_batch_set_subpixel(viso_batch* b, int mode) {
     if (dead(b) || mode < 0 || mode > 2) { viso_set_error("viso_batch_set_subpixel: bad argument (mode 0, 1 or 2)"); return VISO_ERR_ARG; }
-    int r;
-    if ((r = enter(b)) < 0) return r;
+    VISO_TRY(enter(b));
     if (mode && !b->uv) {
-        if ((r = batch_sync(b)) < 0) return r;
-        if ((r = dalloc(&b->uv, (size_t)b->nf * b->cap)) < 0) return r;
-        if ((r = build_items(b)) < 0) return r;
+        VISO_TRY(batch_sync(b));
+        VISO_TRY(b->alloc(&b->uv, (size_t)b->nf * b->cap));
+        VISO_TRY(build_items(b));
     }
     b->subpix = mode;
     return VISO_OK;
@@ -930,7 +747,7 @@ extern "C" int viso_batch_set_subpixel(viso_batch* b, int mode) {
 // The refined (uR', vR') of frame t's stereo rows, in the order of viso_batch_get_matches(b, 0, t).
 extern "C" int viso_batch_get_subpixel(viso_batch* b, int t, float* uv, int* out_n) {
     if (!slot_ok(b, 0, t) || !out_n) { viso_set_error("viso_batch_get_subpixel: bad argument"); return VISO_ERR_ARG; }
-    { const int rs_ = batch_sync(b); if (rs_ < 0) return rs_; }
+    VISO_TRY(batch_sync(b));
     if (!b->uv_mode) { viso_set_error("viso_batch_get_subpixel: the last run refined nothing (mode 0, or not viso_batch_run_images)"); return VISO_ERR_ARG; }
     int m = 0;
     HIP_TRY(hipMemcpy(&m, b->m_cnt + t, sizeof(int), hipMemcpyDeviceToHost));
@@ -940,60 +757,10 @@ extern "C" int viso_batch_get_subpixel(viso_batch* b, int t, float* uv, int* out
     return VISO_OK;
 }
 
-// Opt-in motion covariance (not in the reference; covariance.hip).  The records are allocated (zeroed) on the first request.
-extern "C" int viso_batch_set_covariance(viso_batch* b, int mode, double sigma_px) {
-    if (dead(b) || (mode != 0 && !motion_args_ok(mode, sigma_px))) {
-        viso_set_error("viso_batch_set_covariance: bad argument (mode 0, 1, or 2 with a finite sigma_px > 0)");
-        return VISO_ERR_ARG;
-    }
-    int r;
-    if ((r = enter(b)) < 0) return r;
-    if (mode && !b->cov) {
-        if ((r = batch_sync(b)) < 0) return r;
-        if ((r = dalloc(&b->cov, (size_t)b->nf)) < 0) return r;
-        HIP_TRY(hipMemset(b->cov, 0, sizeof(viso_motion_cov) * (size_t)b->nf));
-    }
-    b->cov_mode = mode;
-    b->cov_sigma = mode == 2 ? sigma_px : 0.0;
-    return VISO_OK;
-}
-
-// An opt-in estimator's records of the last run (the flag `last` of viso_batch): after the batch's work in flight, an error naming
-// `where` when that run computed none.
-static int records_ready(viso_batch* b, int last, const char* where, const char* none) {
-    const int rs_ = batch_sync(b);
-    if (rs_ < 0) return rs_;
-    if (!last) { viso_set_error("%s: the last run computed no %s", where, none); return VISO_ERR_ARG; }
-    return VISO_OK;
-}
-#define COV_NONE "covariance (mode 0, or matcher_only)"
-#define REF_NONE "refinement (mode 0, or matcher_only)"
-#define WIN_NONE "window refinement (K = 0, or matcher_only)"
-
-// The body of the record getters: frame t's record, or (all) the records of every frame, of the estimator whose records and flag
-// are the members recs, last.
-template <class Rec>
-static int get_records(viso_batch* b, bool all, int t, Rec* out, Rec* viso_batch::*recs, int viso_batch::*last, const char* where,
-                       const char* none) {
-    if ((all ? dead(b) : !slot_ok(b, 0, t)) || !out) { viso_set_error("%s: bad argument", where); return VISO_ERR_ARG; }
-    int r;
-    if ((r = records_ready(b, b->*last, where, none)) < 0) return r;
-    HIP_TRY(hipMemcpy(out, b->*recs + (all ? 0 : t), sizeof(Rec) * (all ? (size_t)b->nf : 1), hipMemcpyDeviceToHost));
-    return VISO_OK;
-}
-
-extern "C" int viso_batch_get_covariance(viso_batch* b, int t, viso_motion_cov* out) {
-    return get_records(b, false, t, out, &viso_batch::cov, &viso_batch::cov_last, "viso_batch_get_covariance", COV_NONE);
-}
-
-extern "C" int viso_batch_get_covariances(viso_batch* b, viso_motion_cov* out) {
-    return get_records(b, true, 0, out, &viso_batch::cov, &viso_batch::cov_last, "viso_batch_get_covariances", COV_NONE);
-}
-
 // Frame t's solver inputs (what the circle join wrote for the last run): Xp_c and x_c rows of cap doubles.
 extern "C" int viso_batch_get_points(viso_batch* b, int t, double* X3xcap, double* obs4xcap, int* m) {
     if (!slot_ok(b, 0, t) || !m) { viso_set_error("viso_batch_get_points: bad argument"); return VISO_ERR_ARG; }
-    { const int rs_ = batch_sync(b); if (rs_ < 0) return rs_; }
+    VISO_TRY(batch_sync(b));
     int mm = 0;
     HIP_TRY(hipMemcpy(&mm, b->mc + t, sizeof(int), hipMemcpyDeviceToHost));
     mm = mm < 0 ? 0 : mm > b->cap ? b->cap : mm;
@@ -1002,257 +769,6 @@ extern "C" int viso_batch_get_points(viso_batch* b, int t, double* X3xcap, doubl
     if (obs4xcap) HIP_TRY(hipMemcpy(obs4xcap, b->x_c + (size_t)t * 4 * c, sizeof(double) * 4 * c, hipMemcpyDeviceToHost));
     *m = mm;
     return VISO_OK;
-}
-
-// Opt-in motion refinement (not in the reference; refine.hip).  The records and working buffers are allocated (zeroed) on the
-// first request.
-extern "C" int viso_batch_set_refine(viso_batch* b, int mode, double sigma_px) {
-    if (dead(b) || (mode != 0 && !motion_args_ok(mode, sigma_px))) {
-        viso_set_error("viso_batch_set_refine: bad argument (mode 0, 1, or 2 with a finite sigma_px > 0)");
-        return VISO_ERR_ARG;
-    }
-    int r;
-    if ((r = enter(b)) < 0) return r;
-    if (mode && !b->ref) {
-        if ((r = batch_sync(b)) < 0) return r;
-        const size_t nf = (size_t)b->nf, c = (size_t)b->cap;
-        if ((r = dalloc_zeroed({{&b->ref, nf}, {&b->ref_pts, nf * 6 * c}, {&b->ref_idx, nf * c}})) < 0) return r;
-    }
-    b->ref_mode = mode;
-    b->ref_sigma = mode == 2 ? sigma_px : 0.0;
-    return VISO_OK;
-}
-
-extern "C" int viso_batch_get_refine(viso_batch* b, int t, viso_motion_refine* out) {
-    return get_records(b, false, t, out, &viso_batch::ref, &viso_batch::ref_last, "viso_batch_get_refine", REF_NONE);
-}
-
-extern "C" int viso_batch_get_refines(viso_batch* b, viso_motion_refine* out) {
-    return get_records(b, true, 0, out, &viso_batch::ref, &viso_batch::ref_last, "viso_batch_get_refines", REF_NONE);
-}
-
-// Frame t's refined points (the kernel leaves the final state in half 0 of the frame's point buffer) and L'.
-extern "C" int viso_batch_get_refined_points(viso_batch* b, int t, int32_t* idx, double* X3xcap, int* n) {
-    if (!slot_ok(b, 0, t) || !n) { viso_set_error("viso_batch_get_refined_points: bad argument"); return VISO_ERR_ARG; }
-    int r;
-    if ((r = records_ready(b, b->ref_last, "viso_batch_get_refined_points", REF_NONE)) < 0) return r;
-    viso_motion_refine rec;
-    HIP_TRY(hipMemcpy(&rec, b->ref + t, sizeof(rec), hipMemcpyDeviceToHost));
-    const int nn = rec.status == 1 ? (rec.n < 0 ? 0 : rec.n > b->cap ? b->cap : rec.n) : 0;
-    const size_t c = (size_t)b->cap;
-    if (idx && nn) HIP_TRY(hipMemcpy(idx, b->ref_idx + (size_t)t * c, sizeof(int) * (size_t)nn, hipMemcpyDeviceToHost));
-    if (X3xcap && nn)
-        for (int row = 0; row < 3; ++row)
-            HIP_TRY(hipMemcpy(X3xcap + (size_t)row * c, b->ref_pts + ((size_t)t * 6 + (size_t)row) * c, sizeof(double) * (size_t)nn,
-                              hipMemcpyDeviceToHost));
-    *n = nn;
-    return VISO_OK;
-}
-
-// Opt-in window refinement (not in the reference; window.hip).  The records and working buffers are allocated (zeroed) on the first
-// request with K > 0 and again for a larger K: the track and point buffers are sized (K - 1) cap per frame.
-extern "C" int viso_batch_set_window_refine(viso_batch* b, int K, int mode, double sigma_px) {
-    if (dead(b) || (K != 0 && !window_refine_args_ok(K, mode, sigma_px))) {
-        viso_set_error("viso_batch_set_window_refine: bad argument (K 0, or K in 2..5 with mode 1, or mode 2 with a finite sigma_px > 0)");
-        return VISO_ERR_ARG;
-    }
-    int r;
-    if ((r = enter(b)) < 0) return r;
-    if (K > b->win_kalloc) {
-        if ((r = batch_sync(b)) < 0) return r;
-        void* old[] = {b->win, b->win_lp, b->win_nlp, b->win_tab, b->win_trk, b->win_pts};
-        for (void* p : old) if (p) (void)hipFree(p);
-        b->win = nullptr; b->win_lp = b->win_nlp = b->win_tab = b->win_trk = nullptr; b->win_pts = nullptr; b->win_kalloc = 0;
-        const size_t nf = (size_t)b->nf, c = (size_t)b->cap, T = (size_t)(K - 1) * c;
-        if ((r = dalloc_zeroed({{&b->win, nf}, {&b->win_lp, nf * c}, {&b->win_nlp, nf}, {&b->win_tab, nf * 2 * c},
-                                {&b->win_trk, nf * 5 * T}, {&b->win_pts, nf * 6 * T}})) < 0)
-            return r;
-        b->win_kalloc = K;
-    }
-    b->win_K = K;
-    b->win_mode = K ? mode : 0;
-    b->win_sigma = K && mode == 2 ? sigma_px : 0.0;
-    return VISO_OK;
-}
-
-extern "C" int viso_batch_get_window_refine(viso_batch* b, int t, viso_window_record* out) {
-    return get_records(b, false, t, out, &viso_batch::win, &viso_batch::win_last, "viso_batch_get_window_refine", WIN_NONE);
-}
-
-extern "C" int viso_batch_get_window_refines(viso_batch* b, viso_window_record* out) {
-    return get_records(b, true, 0, out, &viso_batch::win, &viso_batch::win_last, "viso_batch_get_window_refines", WIN_NONE);
-}
-
-// Opt-in rectification of raw images (not in the reference; rectify.hip).  Synchronous like the other setters: the batch's work
-// in flight finishes first, then the maps are quantised on the host and the buffers (re)allocated.
-extern "C" int viso_batch_set_rectify(viso_batch* b, int raw_rows, int raw_cols, int out_rows, int out_cols, const float* mapxL,
-                                      const float* mapyL, const float* mapxR, const float* mapyR, int border) {
-    const int given = (mapxL != nullptr) + (mapyL != nullptr) + (mapxR != nullptr) + (mapyR != nullptr);
-    if (dead(b) || (given != 0 && given != 4) ||
-        (given == 4 && (!rect_geometry_ok(raw_rows, raw_cols, out_rows, out_cols) || border < 0 || border > 255))) {
-        viso_set_error("viso_batch_set_rectify: bad argument (sizes > 0, border 0..255, all four maps or none)");
-        return VISO_ERR_ARG;
-    }
-    int r;
-    if ((r = enter(b)) < 0) return r;
-    if ((r = batch_sync(b)) < 0) return r;
-    if (b->rmap) HIP_TRY(hipFree(b->rmap));
-    b->rmap = nullptr;
-    if (given == 0) {   // off: the staging buffer goes too; the image buffer stays (the next upload decides its geometry)
-        if (b->raw) HIP_TRY(hipFree(b->raw));
-        b->raw = nullptr; b->raw_bytes = 0; b->raw_rows = b->raw_cols = 0;
-        return VISO_OK;
-    }
-    const size_t oper = (size_t)out_rows * out_cols, rbytes = (size_t)raw_rows * raw_cols * 2 * (size_t)b->nf;
-    std::vector<RectEntry> q(2 * oper);
-    rect_quantise(mapxL, mapyL, oper, raw_rows, raw_cols, q.data());
-    rect_quantise(mapxR, mapyR, oper, raw_rows, raw_cols, q.data() + oper);
-    if ((r = ensure_images(b, out_rows, out_cols)) < 0) return r;
-    if (b->raw && b->raw_bytes != rbytes) {
-        HIP_TRY(hipFree(b->raw));
-        b->raw = nullptr; b->raw_bytes = 0;
-    }
-    if (!b->raw) {
-        HIP_TRY(hipMalloc((void**)&b->raw, rbytes));
-        b->raw_bytes = rbytes;
-    }
-    RectEntry* m = nullptr;
-    if ((r = dalloc(&m, 2 * oper)) < 0) return r;
-    if (hipMemcpy(m, q.data(), sizeof(RectEntry) * 2 * oper, hipMemcpyHostToDevice) != hipSuccess) {
-        hipFree(m);
-        viso_set_error("viso_batch_set_rectify: copying the maps failed");
-        return VISO_ERR_HIP;
-    }
-    b->rmap = m; b->raw_rows = raw_rows; b->raw_cols = raw_cols; b->rborder = border;
-    return VISO_OK;
-}
-
-// Opt-in dense disparity (not in the reference; disparity.hip).  Only the parameters are kept here: the maps' buffer is allocated
-// by the first launch that needs it.
-extern "C" int viso_batch_set_disparity(viso_batch* b, const viso_disparity_params* params) {
-    if (dead(b) || (params && !disparity_params_ok(params))) {
-        viso_set_error("viso_batch_set_disparity: bad argument (NULL, or the parameters of include/viso_hip.h)");
-        return VISO_ERR_ARG;
-    }
-    if (params && b->sgm_on) {
-        viso_set_error("viso_batch_set_disparity: semi-global matching is on (one method at a time: viso_batch_set_sgm(b, NULL) first)");
-        return VISO_ERR_ARG;
-    }
-    b->disp_on = params != nullptr;
-    if (params) b->disp_p = *params;
-    return VISO_OK;
-}
-
-// Opt-in semi-global matching (not in the reference; sgm.hip): the other method for the same maps.  Only the parameters are kept
-// here: the workspace and the maps' buffer are allocated by the first launch that needs them.
-extern "C" int viso_batch_set_sgm(viso_batch* b, const viso_sgm_params* params) {
-    if (dead(b) || (params && !sgm_params_ok(params))) {
-        viso_set_error("viso_batch_set_sgm: bad argument (NULL, or the parameters of include/viso_hip.h)");
-        return VISO_ERR_ARG;
-    }
-    if (params && b->disp_on) {
-        viso_set_error("viso_batch_set_sgm: block matching is on (one method at a time: viso_batch_set_disparity(b, NULL) first)");
-        return VISO_ERR_ARG;
-    }
-    if (b->sgm_on != (params != nullptr)) b->disp_last = 0;   // maps of the other state are not this one's
-    b->sgm_on = params != nullptr;
-    if (params) b->sgm_p = *params;
-    return VISO_OK;
-}
-
-// Opt-in speckle filter of the maps (not in the reference; speckle.hip): a stage behind whichever method is on.  Only the parameters
-// are kept here: the workspace is allocated by the first launch that needs it.  With no method on it does nothing.
-extern "C" int viso_batch_set_speckle(viso_batch* b, const viso_speckle_params* params) {
-    if (dead(b) || (params && !speckle_params_ok(params))) {
-        viso_set_error("viso_batch_set_speckle: bad argument (NULL, or the parameters of include/viso_hip.h)");
-        return VISO_ERR_ARG;
-    }
-    const bool same = b->spk_on == (params != nullptr) &&
-                      (!params || (b->spk_p.max_size == params->max_size && b->spk_p.max_diff == params->max_diff));
-    if (!same) b->disp_last = 0;   // maps of the other state are not this one's
-    b->spk_on = params != nullptr;
-    if (params) b->spk_p = *params;
-    return VISO_OK;
-}
-
-// Only the disparity, over images uploaded without keypoints.
-extern "C" int viso_batch_run_disparity(viso_batch* b) {
-    if (dead(b) || !(b->disp_on || b->sgm_on) || !b->images) {
-        viso_set_error("viso_batch_run_disparity: dense disparity is off, or no images are uploaded");
-        return VISO_ERR_ARG;
-    }
-    if (!disparity_geometry_ok(b->img_rows, b->img_cols)) {
-        viso_set_error("viso_batch_run_disparity: dense disparity of %d-column images is beyond this build (2048 at most)", b->img_cols);
-        return VISO_ERR_UNSUPPORTED;
-    }
-    if (b->sgm_on && sgm_group_frames(b->img_rows, b->img_cols, b->sgm_p.num_disp, b->nf) < 1)
-        return sgm_nomem("viso_batch_run_disparity", b->img_rows, b->img_cols, b->sgm_p.num_disp);
-    if (speckle_active(b) && !speckle_geometry_ok(b->img_rows, b->img_cols)) {
-        viso_set_error("viso_batch_run_disparity: the speckle filter of %d x %d maps is beyond this build (2^31 - 1 pixels)", b->img_rows, b->img_cols);
-        return VISO_ERR_UNSUPPORTED;
-    }
-    if (speckle_active(b) && speckle_group_frames(b->img_rows, b->img_cols, b->nf) < 1)
-        return speckle_nomem("viso_batch_run_disparity", b->img_rows, b->img_cols);
-    int r;
-    if ((r = enter(b)) < 0) return r;
-    return launch_batch_disparity(b);
-}
-
-static int get_disparity(viso_batch* b, bool all, int t, int16_t* out, const char* where) {
-    if (dead(b) || (!all && (t < 0 || t >= b->nf)) || !out) { viso_set_error("%s: bad argument", where); return VISO_ERR_ARG; }
-    if (!(b->disp_on || b->sgm_on) || !b->disp_last) { viso_set_error("%s: dense disparity is off, or no run has computed it", where); return VISO_ERR_ARG; }
-    { const int rs_ = batch_sync(b); if (rs_ < 0) return rs_; }
-    const size_t per = (size_t)b->disp_rows * b->disp_cols;
-    HIP_TRY(hipMemcpy(out, b->disp + (all ? 0 : (size_t)t * per), sizeof(int16_t) * per * (all ? (size_t)b->nf : 1), hipMemcpyDeviceToHost));
-    return VISO_OK;
-}
-
-extern "C" int viso_batch_get_disparity(viso_batch* b, int t, int16_t* out) { return get_disparity(b, false, t, out, "viso_batch_get_disparity"); }
-
-extern "C" int viso_batch_get_disparities(viso_batch* b, int16_t* out) { return get_disparity(b, true, 0, out, "viso_batch_get_disparities"); }
-
-// Frame t's resident map as an organised point image [rows][cols][3] f32 (speckle.hip), computed on demand with the batch's
-// calibration; the batch keeps no point buffer.
-extern "C" int viso_batch_get_disparity_points(viso_batch* b, int t, const double* pose_or_null, int min_disp16, float* out) {
-    const char* where = "viso_batch_get_disparity_points";
-    if (dead(b) || t < 0 || t >= b->nf || !out || min_disp16 < 1) { viso_set_error("%s: bad argument", where); return VISO_ERR_ARG; }
-    if (!b->params_set) { viso_set_error("%s: parameters not set (the calibration comes from viso_batch_set_params)", where); return VISO_ERR_ARG; }
-    if (!(b->disp_on || b->sgm_on) || !b->disp_last) { viso_set_error("%s: dense disparity is off, or no run has computed it", where); return VISO_ERR_ARG; }
-    int r;
-    if ((r = enter(b)) < 0) return r;
-    const size_t per = (size_t)b->disp_rows * b->disp_cols;
-    float* dout = nullptr;
-    if (hipMalloc((void**)&dout, 3 * sizeof(float) * per) != hipSuccess) {
-        (void)hipGetLastError();
-        viso_set_error("%s: cannot allocate the %zu-byte point image", where, 3 * sizeof(float) * per);
-        return VISO_ERR_NOMEM;
-    }
-    hipStream_t s = b->ctx->stream;
-    r = launch_points(s, b->disp + (size_t)t * per, b->disp_rows, b->disp_cols, b->sp.f, b->sp.cu, b->sp.cv, b->sp.base, pose_or_null,
-                      min_disp16, dout);
-    hipError_t e = hipSuccess;
-    if (r >= 0) e = hipMemcpyAsync(out, dout, 3 * sizeof(float) * per, hipMemcpyDeviceToHost, s);
-    const hipError_t e2 = hipStreamSynchronize(s);
-    (void)hipFree(dout);
-    if (r < 0) return r;
-    HIP_TRY(e);
-    HIP_TRY(e2);
-    return VISO_OK;
-}
-
-// The resident maps of frames t0 .. t1-1 into a voxel map of the same context (voxelmap.hip), with the batch's calibration: on the
-// context's stream, behind the run that computed them, with no host copy of the maps.
-extern "C" int viso_batch_fuse_disparities(viso_batch* b, viso_map* m, int t0, int t1, const double* poses) {
-    const char* where = "viso_batch_fuse_disparities";
-    if (dead(b) || !m || t0 < 0 || t1 > b->nf || t0 >= t1 || !poses) {
-        viso_set_error("%s: bad argument (live handles, 0 <= t0 < t1 <= n_frames, poses [t1 - t0][16])", where);
-        return VISO_ERR_ARG;
-    }
-    if (!b->params_set) { viso_set_error("%s: parameters not set (the calibration comes from viso_batch_set_params)", where); return VISO_ERR_ARG; }
-    if (!(b->disp_on || b->sgm_on) || !b->disp_last) { viso_set_error("%s: dense disparity is off, or no run has computed it", where); return VISO_ERR_ARG; }
-    const size_t per = (size_t)b->disp_rows * b->disp_cols;
-    return map_fuse_resident(where, m, b->ctx, b->disp + (size_t)t0 * per, per, b->disp_rows, b->disp_cols, t1 - t0, b->sp.f, b->sp.cu,
-                             b->sp.cv, b->sp.base, poses);
 }
 
 // The geometry of the batch's device images (what viso_batch_get_image copies): 0 x 0 before the first image upload.
@@ -1267,64 +783,15 @@ extern "C" int viso_batch_get_image_geometry(viso_batch* b, int* rows, int* cols
 extern "C" int viso_batch_get_image(viso_batch* b, int t, int side, uint8_t* out) {
     if (dead(b) || t < 0 || t >= b->nf || side < 0 || side > 1 || !out) { viso_set_error("viso_batch_get_image: bad argument"); return VISO_ERR_ARG; }
     if (!b->images) { viso_set_error("viso_batch_get_image: no images uploaded"); return VISO_ERR_ARG; }
-    { const int rs_ = batch_sync(b); if (rs_ < 0) return rs_; }
+    VISO_TRY(batch_sync(b));
     const size_t per = (size_t)b->img_rows * b->img_cols;
     HIP_TRY(hipMemcpy(out, b->images + ((size_t)t * 2 + side) * per, per, hipMemcpyDeviceToHost));
     return VISO_OK;
 }
 
-static int run_rest(viso_batch* b) {
-    int r;
-    if ((r = enter(b)) < 0) return r;
-    hipStream_t s = b->ctx->stream;
-    hipStream_t ss = b->solver_stream ? b->solver_stream : s;
-    // the circle join rewrites what the previous run's RANSAC reads (x_c, Xp_c, mc)
-    if (ss != s && b->ransac_pending) HIP_TRY(hipStreamWaitEvent(s, b->ev_ransac, 0));
-    if (b->nf > 1) {
-        if ((r = launch_circle_join(s, b->join, b->nf - 1, b->sp, b->uv_mode != 0)) < 0) return r;   // :1245-1247 (the rows it joins), :1282, 1292-1305
-        if (ss != s) {
-            HIP_TRY(hipEventRecord(b->ev_join, s));
-            HIP_TRY(hipStreamWaitEvent(ss, b->ev_join, 0));
-        }
-    }
-    // vector<double> tr(6,0), :1312: ransac_refit_kernel writes the zeros itself where no solve succeeds
-    if (b->nf > 1) {
-        if ((r = launch_ransac(ss, b->sitems, b->nf - 1, b->iters, b->seed, b->sp, b->hq, b->ctx->gn_split, b->cap)) < 0) return r;   // :1313
-        // the run's poses, flags and inlier counts into the pinned mirror (the kernel writes over PCIe; viso_batch_get_poses
-        // waits for the streams and reads host memory)
-        if ((r = plain_blit(ss, b->tr, b->pose_pin, b->pose_bytes / 4)) < 0) return r;
-        // opt-in: the motion covariance from what the refit left (tr, ok, the final inlier list), frames 1 .. nf-1
-        if (b->cov_mode && (r = launch_motion_cov(ss, b->sitems, b->nf - 1, b->sp, b->cov_mode, b->cov_sigma, b->cov + 1)) < 0) return r;
-        // opt-in: the two-frame bundle adjustment from the same inputs (it changes none of them)
-        const size_t c = (size_t)b->cap;
-        if (b->ref_mode && (r = launch_motion_refine(ss, b->sitems, b->nf - 1, b->sp, b->ref_mode, b->ref_sigma, b->ref_pts + 6 * c,
-                                                     b->ref_idx + c, c, b->ref + 1)) < 0) return r;
-        // opt-in: the sliding-window bundle adjustment over every frame's final inliers (it changes none of the inputs)
-        if (b->win_K) {
-            WinData d;
-            d.X = b->Xp_c; d.obs = b->x_c; d.left = b->circ; d.left_fs = 4 * c; d.lstride = 4; d.lprev = 2;
-            d.tr = b->tr; d.ok = b->ok; d.n_inl = b->n_inl; d.inl = b->inl; d.m = b->mc; d.ld = b->cap; d.tab = b->cap;
-            WinWork w;
-            w.Lp = b->win_lp; w.nLp = b->win_nlp; w.tabs = b->win_tab; w.maxT = (size_t)(b->win_K - 1) * c;
-            w.trk = b->win_trk; w.pts = b->win_pts;
-            if ((r = launch_window_links(ss, d, w, 1, b->nf - 1)) < 0) return r;
-            if ((r = launch_window_refine(ss, d, w, b->sp, b->win_K, b->win_mode, b->win_sigma, 1, b->nf - 1, b->win + 1)) < 0) return r;
-        }
-    }
-    b->cov_last = b->cov_mode;
-    b->ref_last = b->ref_mode;
-    b->win_last = b->win_K;
-    if (ss != s) {
-        HIP_TRY(hipEventRecord(b->ev_ransac, ss));
-        b->ransac_pending = true;
-    }
-    if (b->stamps) HIP_TRY(hipEventRecord(b->ev_stamp[2], ss));
-    return VISO_OK;
-}
-
 extern "C" int viso_batch_kernel_ms(viso_batch* b, double* matcher_ms_avg, int* n_launches) {
     if (dead(b)) return VISO_ERR_ARG;
-    { const int rs_ = batch_sync(b); if (rs_ < 0) return rs_; }
+    VISO_TRY(batch_sync(b));
     double tot = b->ev_ms_sum;
     int n = b->ev_n;
     for (auto& e : b->events) {
@@ -1339,11 +806,9 @@ extern "C" int viso_batch_kernel_ms(viso_batch* b, double* matcher_ms_avg, int* 
     return VISO_OK;
 }
 
-static bool slot_ok(viso_batch* b, int which, int t) { return !dead(b) && which >= 0 && which < 3 && t >= 0 && t < b->nf; }
-
 extern "C" int viso_batch_get_matches(viso_batch* b, int which, int t, int32_t* out_match, int* out_n) {
     if (!slot_ok(b, which, t) || !out_n) { viso_set_error("viso_batch_get_matches: bad argument"); return VISO_ERR_ARG; }
-    { const int rs_ = batch_sync(b); if (rs_ < 0) return rs_; }
+    VISO_TRY(batch_sync(b));
     const size_t o = (size_t)which * b->nf + t;
     int m = 0;
     HIP_TRY(hipMemcpy(&m, b->m_cnt + o, sizeof(int), hipMemcpyDeviceToHost));
@@ -1354,7 +819,7 @@ extern "C" int viso_batch_get_matches(viso_batch* b, int which, int t, int32_t* 
 
 extern "C" int viso_batch_get_circle(viso_batch* b, int t, int32_t* circ, int32_t* pcl, int* out_n) {
     if (!slot_ok(b, 0, t) || !out_n) { viso_set_error("viso_batch_get_circle: bad argument"); return VISO_ERR_ARG; }
-    { const int rs_ = batch_sync(b); if (rs_ < 0) return rs_; }
+    VISO_TRY(batch_sync(b));
     int m = 0;
     HIP_TRY(hipMemcpy(&m, b->mc + t, sizeof(int), hipMemcpyDeviceToHost));
     if (m > 0 && circ) HIP_TRY(hipMemcpy(circ, b->circ + (size_t)t * b->cap * 4, sizeof(int) * 4 * (size_t)m, hipMemcpyDeviceToHost));
@@ -1365,7 +830,7 @@ extern "C" int viso_batch_get_circle(viso_batch* b, int t, int32_t* circ, int32_
 
 extern "C" int viso_batch_get_pose(viso_batch* b, int t, double tr[6], int* ok, int32_t* inliers, int* n_inl) {
     if (!slot_ok(b, 0, t)) { viso_set_error("viso_batch_get_pose: bad argument"); return VISO_ERR_ARG; }
-    { const int rs_ = batch_sync(b); if (rs_ < 0) return rs_; }
+    VISO_TRY(batch_sync(b));
     int o = 0, n = 0;
     const size_t nf = (size_t)b->nf;
     if (tr) memcpy(tr, b->pose_pin + sizeof(double) * 6 * (size_t)t, sizeof(double) * 6);
@@ -1379,7 +844,7 @@ extern "C" int viso_batch_get_pose(viso_batch* b, int t, double tr[6], int* ok, 
 
 extern "C" int viso_batch_get_poses(viso_batch* b, double* tr, int32_t* ok, int32_t* n_inl) {
     if (dead(b)) return VISO_ERR_ARG;
-    { const int rs_ = batch_sync(b); if (rs_ < 0) return rs_; }
+    VISO_TRY(batch_sync(b));
     // the pinned mirror of the device block (run_rest's last kernel; zeros before the first run, like the device's)
     const size_t nf = (size_t)b->nf;
     if (tr) memcpy(tr, b->pose_pin, sizeof(double) * 6 * nf);
@@ -1390,23 +855,24 @@ extern "C" int viso_batch_get_poses(viso_batch* b, double* tr, int32_t* ok, int3
 
 // The per-hypothesis state of the last run's RANSAC stage (test / diagnostics): tr_h [n_frames][iters][6], ok_h and
 // cnt_h [n_frames][iters] (frame 0 unused), *n_undecided = hypotheses the lane-per-hypothesis kernel handed on.
-extern "C" int viso_batch_get_hypotheses2(viso_batch* b, int iters_capacity, double* tr_h, int32_t* ok_h, int32_t* cnt_h,
+extern "C" int viso_batch_get_hypotheses2(viso_batch* b, int capacity, double* tr_h, int32_t* ok_h, int32_t* cnt_h,
                                           int32_t* n_undecided) {
-    if (dead(b) || iters_capacity < (b->iters > 0 ? b->iters : 1)) {
-        viso_set_error("viso_batch_get_hypotheses2: arrays hold %d hypotheses per frame, the batch has %d", iters_capacity, b ? b->iters : 0);
+    if (dead(b)) { viso_set_error("viso_batch_get_hypotheses2: bad argument"); return VISO_ERR_ARG; }   // b is not read: it may be freed memory
+    const int iters = b->iters > 0 ? b->iters : 1;
+    if (capacity < iters) {
+        viso_set_error("viso_batch_get_hypotheses2: arrays hold %d hypotheses per frame, the batch has %d", capacity, b->iters);
         return VISO_ERR_ARG;
     }
-    const int iters = b->iters > 0 ? b->iters : 1;
-    if (iters_capacity == iters) return viso_batch_get_hypotheses(b, tr_h, ok_h, cnt_h, n_undecided);
+    if (capacity == iters) return viso_batch_get_hypotheses(b, tr_h, ok_h, cnt_h, n_undecided);
     // the caller's rows are longer than the batch's: frame by frame, at the caller's stride
     if (!b->tr_h) { viso_set_error("viso_batch_get_hypotheses2: no run yet"); return VISO_ERR_ARG; }
-    { const int rs_ = batch_sync(b); if (rs_ < 0) return rs_; }
+    VISO_TRY(batch_sync(b));
     const size_t nf = (size_t)b->nf;
-    if (tr_h) HIP_TRY(hipMemcpy2D(tr_h, sizeof(double) * 6 * (size_t)iters_capacity, b->tr_h, sizeof(double) * 6 * (size_t)iters,
+    if (tr_h) HIP_TRY(hipMemcpy2D(tr_h, sizeof(double) * 6 * (size_t)capacity, b->tr_h, sizeof(double) * 6 * (size_t)iters,
                                   sizeof(double) * 6 * (size_t)iters, nf, hipMemcpyDeviceToHost));
-    if (ok_h) HIP_TRY(hipMemcpy2D(ok_h, sizeof(int) * (size_t)iters_capacity, b->ok_h, sizeof(int) * (size_t)iters, sizeof(int) * (size_t)iters, nf,
+    if (ok_h) HIP_TRY(hipMemcpy2D(ok_h, sizeof(int) * (size_t)capacity, b->ok_h, sizeof(int) * (size_t)iters, sizeof(int) * (size_t)iters, nf,
                                   hipMemcpyDeviceToHost));
-    if (cnt_h) HIP_TRY(hipMemcpy2D(cnt_h, sizeof(int) * (size_t)iters_capacity, b->cnt_h, sizeof(int) * (size_t)iters, sizeof(int) * (size_t)iters, nf,
+    if (cnt_h) HIP_TRY(hipMemcpy2D(cnt_h, sizeof(int) * (size_t)capacity, b->cnt_h, sizeof(int) * (size_t)iters, sizeof(int) * (size_t)iters, nf,
                                    hipMemcpyDeviceToHost));
     if (n_undecided) HIP_TRY(hipMemcpy(n_undecided, b->hq + 1, sizeof(int), hipMemcpyDeviceToHost));   // [1]: the last chain's count (solver.hip)
     return VISO_OK;
@@ -1414,7 +880,7 @@ extern "C" int viso_batch_get_hypotheses2(viso_batch* b, int iters_capacity, dou
 
 extern "C" int viso_batch_get_hypotheses(viso_batch* b, double* tr_h, int32_t* ok_h, int32_t* cnt_h, int32_t* n_undecided) {
     if (dead(b) || !b->tr_h) { viso_set_error("viso_batch_get_hypotheses: no run yet"); return VISO_ERR_ARG; }
-    { const int rs_ = batch_sync(b); if (rs_ < 0) return rs_; }
+    VISO_TRY(batch_sync(b));
     const size_t k = (size_t)b->nf * (size_t)(b->iters > 0 ? b->iters : 1);
     if (tr_h) HIP_TRY(hipMemcpy(tr_h, b->tr_h, sizeof(double) * 6 * k, hipMemcpyDeviceToHost));
     if (ok_h) HIP_TRY(hipMemcpy(ok_h, b->ok_h, sizeof(int) * k, hipMemcpyDeviceToHost));
@@ -1427,7 +893,7 @@ extern "C" int viso_batch_get_hypotheses(viso_batch* b, double* tr_h, int32_t* o
 // [-32768, 32767]): the problems reading them took the general (double) kernel, all others the u16 kernels.
 extern "C" int viso_batch_get_general_path_flags(viso_batch* b, int32_t* flags) {
     if (dead(b) || !flags) return VISO_ERR_ARG;
-    { const int rs_ = batch_sync(b); if (rs_ < 0) return rs_; }
+    VISO_TRY(batch_sync(b));
     HIP_TRY(hipMemcpy(flags, b->bad_img, sizeof(int) * 2 * (size_t)b->nf, hipMemcpyDeviceToHost));
     return VISO_OK;
 }
@@ -1436,14 +902,14 @@ extern "C" int viso_batch_get_general_path_flags(viso_batch* b, int32_t* flags) 
 // candidates, a candidate list that outgrew its LDS slot, an exact tie of the minimum): the data-dependent slow path.
 extern "C" int viso_batch_get_overflow_count(viso_batch* b, int32_t* n) {
     if (dead(b) || !n) return VISO_ERR_ARG;
-    { const int rs_ = batch_sync(b); if (rs_ < 0) return rs_; }
+    VISO_TRY(batch_sync(b));
     HIP_TRY(hipMemcpy(n, b->ovf_cnt, sizeof(int), hipMemcpyDeviceToHost));
     return VISO_OK;
 }
 
 extern "C" int viso_batch_get_counters(viso_batch* b, int64_t* scored, int64_t* m_out) {
     if (dead(b)) return VISO_ERR_ARG;
-    { const int rs_ = batch_sync(b); if (rs_ < 0) return rs_; }
+    VISO_TRY(batch_sync(b));
     const size_t k = 3 * (size_t)b->nf;
     if (scored) HIP_TRY(hipMemcpy(scored, b->scored, sizeof(int64_t) * k, hipMemcpyDeviceToHost));
     if (m_out) {

@@ -41,6 +41,13 @@ void viso_set_error(const char* fmt, ...);
         }                                                                          \
     } while (0)
 
+// a call of this library's own: its error (the text is set) is the caller's
+#define VISO_TRY(expr)                                                             \
+    do {                                                                           \
+        const int _r = (expr);                                                     \
+        if (_r < 0) return _r;                                                     \
+    } while (0)
+
 // ---- device-side views -----------------------------------------------------
 struct MatchParamsDev {          // viso_match_params, device copy (kernarg)
     int epi, second, K, _pad;
