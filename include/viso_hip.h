@@ -878,7 +878,8 @@ int viso_batch_get_disparity_points(viso_batch* b, int t, const double* pose_or_
  * finds no slot increments n_dropped; a call that ends with n_dropped > 0 returns VISO_ERR_NOMEM and marks the map overflowed
  * (which points were dropped depends on scheduling), and viso_map_count / viso_map_get / viso_map_add_entries / the fuse calls
  * then refuse with VISO_ERR_NOMEM until viso_map_clear, after which the map is fully usable again.
- * Out of scope: colour, a TSDF or surface form, eviction of far voxels, fusing inside the KITTI runners while their chunks drain.
+ * Out of scope: colour, eviction of far voxels, fusing inside the KITTI runners while their chunks drain (a surface form is the
+ * TSDF map below).
  * HIP kernels (voxelmap.hip): map_fuse_kernel (one thread per pixel of a group of frames; lanes that continue the key of the lane
  * to their left form a run, the run heads come from one ballot, the runs' sums from a wave scan, and only a run's head probes the
  * table and issues the four integer atomic adds), map_add_entries_kernel, map_compact_kernel, map_clear_kernel.  Memory: 36 bytes a
@@ -932,6 +933,105 @@ int viso_map_get(viso_map* m, uint32_t min_count, viso_map_entry* entries_out, s
 int viso_map_stats(viso_map* m, viso_map_counters* out);
 /* Step 7.  Host only; VISO_ERR_ARG for a null pointer, a count of 0, a voxel that is not finite and > 0. */
 int viso_map_entry_centroid(const viso_map_entry* entry, double voxel, float out[3]);
+
+/* ------------------------------------------------ TSDF map: signed-distance fusion and surface points (opt-in; NOT in the reference)
+ *
+ * A second persistent hash table of voxels on the device, beside the voxel map above and with its key, probe, full-table rule and
+ * lifetime rules.  Where the voxel map counts the points that fall into a voxel, this one averages, per voxel, the signed distance
+ * of the voxel's centre from the measured surface along the viewing direction, truncated to a band of T voxels (a truncated signed
+ * distance function, TSDF); the surface is where the average changes sign between two neighbouring voxels.  Sum of distances and
+ * sum of weights are integers, so a map depends on neither the order of the frames nor on scheduling, and maps are additive.  This
+ * definition is the contract; the device output is bit-identical to tests/tsdf_ref.py.
+ * Parameters: voxel > 0 and finite (metres), trunc_voxels T in 1..8, min_disp16 >= 1 (1/16 px), capacity_log2 in 10..28.  Any other
+ * value gives VISO_ERR_ARG before a device is touched.  Derived once in double on the host: s = voxel / 1024 and h = voxel * 0.5.
+ * Everything below is IEEE double in the operand order written, with no fused multiply-add.
+ *   1. A pixel (x, y) of a frame contributes when disp16 != VISO_DISP_INVALID and disp16 >= min_disp16 (the voxel map's rule 1).
+ *   2. Camera point: d = disp16 / 16, X = base (x - cu) / d, Y = base (y - cv) / d, Z = f base / d.
+ *   3. Samples: for j = -2T .. +2T in ascending order, zj = Z + (double)j h.  A sample with !(zj > 0) is not inserted and resets
+ *      the duplicate rule of step 5.  Otherwise r = zj / Z, Qc = (X r, Y r, zj), and the world point is
+ *      Q_i = ((T[i][0] Qc0 + T[i][1] Qc1) + T[i][2] Qc2) + T[i][3].  The pose is a 4 x 4 row-major matrix whose 16 entries must be
+ *      finite (VISO_ERR_ARG, checked before any device is touched); it is taken as rigid.  A null pose means Q = Qc.
+ *   4. Grid cell: g_i = floor(Q_i / s).  Any |g_i| >= 2^30, or a quotient that is not finite: the sample is not inserted, counts in
+ *      n_out_of_range and resets the duplicate rule.  Voxel k_i = g_i >> 10 (arithmetic shift); the key is the voxel map's.
+ *   5. One update per pixel and voxel: a sample whose voxel equals that of the previous inserted sample of the same pixel is
+ *      skipped (the ray is straight and voxels are convex, so equal voxels are consecutive).
+ *   6. Projective distance of the voxel centre: C_i = (double)(k_i 1024 + 512) s,
+ *      zc = (T[0][2] (C0 - T[0][3]) + T[1][2] (C1 - T[1][3])) + T[2][2] (C2 - T[2][3]), or zc = C2 without a pose, and
+ *      q = (int64) floor((Z - zc) / s).  !(q >= -T 1024) (the voxel lies behind the surface by more than the truncation, or the
+ *      quotient is not a number): no update, but the sample still is the previous sample of rule 5.  q > T 1024: q = T 1024.
+ *   7. Per voxel: weight (uint32) += 1, sum (int64) += q.
+ *   8. Voxels: viso_tsdf_get returns those with weight >= min_weight (>= 1), sorted by key, ascending.
+ *   9. Surface crossings: for every voxel a with weight >= min_weight and axis = 0, 1, 2, let b = a + e_axis.  If b is in the table
+ *      with weight >= min_weight and (sum_a < 0) != (sum_b < 0), a viso_tsdf_crossing is emitted.  Sorted by (key of a, axis).
+ *  10. Crossing point (host only): da = (double)sa / (double)wa, db likewise, t = da / (da - db), and
+ *      p_i = (float)(((double)(k_i 1024 + 512) + (i == axis ? t 1024.0 : 0.0)) s).
+ * Full table: the voxel map's rule.  An update that finds no slot counts in n_dropped; a call that ends with n_dropped > 0 returns
+ * VISO_ERR_NOMEM and marks the map overflowed, and every getter, viso_tsdf_add_entries and every fuse call then refuse with
+ * VISO_ERR_NOMEM until viso_tsdf_clear.  Every probe loop, the read-only lookups of the extraction included, visits each slot at
+ * most once and advances strictly.
+ * Out of scope: triangle meshes, colour, carving free space beyond the truncation band, weights that fall with depth, eviction,
+ * fusing inside the KITTI runners, the sort on the device.
+ * HIP kernels (tsdf.hip): tsdf_fuse_kernel (one thread per pixel of a group of frames; the loop over j is uniform across the wave,
+ * and per j the lanes that continue the voxel of the lane to their left form a run whose head lane alone probes the table and
+ * issues the two integer atomic adds), tsdf_add_entries_kernel, tsdf_compact_kernel, tsdf_crossings_kernel, tsdf_clear_kernel.
+ * Memory: 20 bytes a slot (1.34 GB at the default capacity). */
+typedef struct viso_tsdf_params {
+    double voxel;            /* edge of a voxel, metres */
+    int32_t trunc_voxels;    /* T: the truncation band, in voxels */
+    int32_t min_disp16;      /* smallest disparity used, 1/16 px */
+    int32_t capacity_log2;   /* log2 of the table's slots */
+} viso_tsdf_params;
+
+typedef struct viso_tsdf_entry {   /* 24 bytes */
+    int32_t k[3];            /* voxel index: the voxel is [k voxel, (k + 1) voxel) on every axis */
+    uint32_t weight;         /* updates fused into it */
+    int64_t sum;             /* sum of their q, in units of s = voxel / 1024; positive: the centre is in front of the surface */
+} viso_tsdf_entry;
+
+typedef struct viso_tsdf_crossing {   /* 40 bytes */
+    int32_t k[3];            /* voxel a; b = a + e_axis */
+    int32_t axis;
+    uint32_t wa, wb;         /* weights of a and b */
+    int64_t sa, sb;          /* sums of a and b */
+} viso_tsdf_crossing;
+
+typedef struct viso_tsdf_counters {
+    uint64_t n_points;       /* pixels that contributed (step 1) */
+    uint64_t n_updates;      /* updates of step 7, the weights of added entries included */
+    uint64_t n_out_of_range; /* samples of step 4 */
+    uint64_t n_dropped;      /* updates that found no slot */
+    uint64_t n_occupied;     /* slots in use */
+} viso_tsdf_counters;
+
+typedef struct viso_tsdf viso_tsdf;
+
+/* voxel 0.2, trunc_voxels 3, min_disp16 16 (1 px), capacity_log2 26.  Host only. */
+void viso_tsdf_params_default(viso_tsdf_params* p);
+/* A TSDF map on the context's device and stream (NULL: the default context), empty.  VISO_ERR_NOMEM when the table cannot be
+ * allocated.  Handles follow the rules of viso_map: viso_tsdf_destroy frees the map and returns VISO_OK also when its context was
+ * destroyed before it; every other call on such a map, or on a handle that is not a TSDF map, returns VISO_ERR_ARG. */
+int viso_tsdf_create(viso_ctx* ctx_or_null, const viso_tsdf_params* params, viso_tsdf** out);
+int viso_tsdf_destroy(viso_tsdf* t);
+/* Empties the table, zeroes the statistics and lifts the overflow mark. */
+int viso_tsdf_clear(viso_tsdf* t);
+/* Fuses one host map with the calibration f, cu, cv, base of *param (all finite) and the pose (NULL: no transform). */
+int viso_tsdf_fuse(viso_tsdf* t, const int16_t* disp, int rows, int cols, const viso_param* param, const double* pose_or_null);
+/* Fuses the resident maps of frames t0 .. t1-1 of the batch, as viso_batch_fuse_disparities does and with its refusals. */
+int viso_batch_fuse_tsdf(viso_batch* b, viso_tsdf* t, int t0, int t1, const double* poses);
+/* Adds n entries (of viso_tsdf_get, of a map with the same voxel and truncation): weight += weight, sum += sum per voxel.
+ * VISO_ERR_ARG: a k outside -2^20 .. 2^20 - 1, a weight of 0, |sum| > T 1024 weight. */
+int viso_tsdf_add_entries(viso_tsdf* t, const viso_tsdf_entry* entries, size_t n);
+/* Step 8: the number of voxels with weight >= min_weight, and those voxels (VISO_ERR_ARG, with *n set and nothing written, when
+ * n_cap is smaller).  The table is compacted on the device; the sort runs on the host. */
+int viso_tsdf_count(viso_tsdf* t, uint32_t min_weight, size_t* n);
+int viso_tsdf_get(viso_tsdf* t, uint32_t min_weight, viso_tsdf_entry* entries_out, size_t n_cap, size_t* n);
+/* Step 9, in the same two forms. */
+int viso_tsdf_surface_count(viso_tsdf* t, uint32_t min_weight, size_t* n);
+int viso_tsdf_surface(viso_tsdf* t, uint32_t min_weight, viso_tsdf_crossing* crossings_out, size_t n_cap, size_t* n);
+int viso_tsdf_stats(viso_tsdf* t, viso_tsdf_counters* out);
+/* Step 10.  Host only; VISO_ERR_ARG for a null pointer, an axis outside 0..2, a weight of 0, sums of the same sign, a voxel that
+ * is not finite and > 0. */
+int viso_tsdf_crossing_point(const viso_tsdf_crossing* crossing, double voxel, float out[3]);
 
 #ifdef __cplusplus
 }

@@ -18,7 +18,8 @@ import numpy as np
 
 from .abi import (DESC_LEN, MAP_DEFAULTS, MAP_ENTRY_DTYPE, MapCounters, MapParams, declare_map, MOTION_COV_DTYPE, MOTION_REFINE_DTYPE, SGM_DEFAULTS, SPECKLE_DEFAULTS, WINDOW_RECORD_DTYPE, DisparityParams, MatchParams,
                   Param, SgmParams, SpeckleParams, declare_common, declare_covariance, declare_disparity, declare_refine, declare_rectify,
-                  declare_sgm, declare_speckle, declare_subpixel, declare_window, f32p, f64p, i32p, i64p, intp, ptr)
+                  declare_sgm, declare_speckle, declare_subpixel, declare_window, f32p, f64p, i32p, i64p, intp, ptr,
+                  TSDF_CROSSING_DTYPE, TSDF_DEFAULTS, TSDF_ENTRY_DTYPE, TsdfCounters, TsdfParams, declare_tsdf)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("VISO_HIP_SO") or os.path.join(_HERE, "libviso_hip.so")   # VISO_HIP_SO: another build of the library (A/B runs)
@@ -132,6 +133,8 @@ def load():
         declare_speckle(L)
     if hasattr(L, "viso_map_create"):
         declare_map(L)
+    if hasattr(L, "viso_tsdf_create"):
+        declare_tsdf(L)
     L.viso_harris_response.argtypes = [C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_double, f32p]
     L.viso_detect_harris_binned.argtypes = [C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                             C.c_double, f32p, f32p, intp]
@@ -641,6 +644,49 @@ def write_map_ply(path, entries, voxel):
         f.write(data)
 
 
+def tsdf_params(**params):
+    """viso_tsdf_params: viso_tsdf_params_default with the given fields (voxel in metres, trunc_voxels, min_disp16 in 1/16 px,
+    capacity_log2) replaced.  Needs no library: the ranges are checked by viso_tsdf_create (TsdfParams.ok restates them)."""
+    p = TsdfParams(**TSDF_DEFAULTS)
+    for k, v in params.items():
+        if k not in TSDF_DEFAULTS:
+            raise TypeError(f"tsdf_params: unknown parameter {k!r}")
+        setattr(p, k, float(v) if k == "voxel" else int(v))
+    return p
+
+
+def tsdf_crossing_points(crossings, voxel):
+    """viso_tsdf_crossing_point of every crossing: float32 [n][3], where the averaged signed distance passes through zero between
+    the centres of the two voxels.  Host only."""
+    crossings = np.ascontiguousarray(crossings, dtype=TSDF_CROSSING_DTYPE)
+    out = np.empty((len(crossings), 3), np.float32)
+    L = load()
+    for i in range(len(crossings)):
+        r = L.viso_tsdf_crossing_point(crossings[i:i + 1].ctypes.data, float(voxel), ptr(out[i], C.c_float))
+        if r != 1:
+            _err("viso_tsdf_crossing_point", r)
+    return out
+
+
+def surface_ply_bytes(crossings, voxel):
+    """The bytes of write_surface_ply: a binary little-endian PLY with one vertex per crossing, x, y, z the float32 crossing point
+    and weight = min(wa, wb) a uint32, in the crossings' order."""
+    crossings = np.ascontiguousarray(crossings, dtype=TSDF_CROSSING_DTYPE)
+    c = tsdf_crossing_points(crossings, voxel)
+    v = np.empty(len(crossings), np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("weight", "<u4")]))
+    v["x"], v["y"], v["z"], v["weight"] = c[:, 0], c[:, 1], c[:, 2], np.minimum(crossings["wa"], crossings["wb"])
+    head = ("ply\nformat binary_little_endian 1.0\ncomment libviso_amd TSDF surface, voxel %r m\nelement vertex %d\n"
+            "property float x\nproperty float y\nproperty float z\nproperty uint weight\nend_header\n" % (float(voxel), len(crossings)))
+    return head.encode("ascii") + v.tobytes()
+
+
+def write_surface_ply(path, crossings, voxel):
+    """The crossings of TsdfMap.surface as a point cloud file (surface_ply_bytes)."""
+    data = surface_ply_bytes(crossings, voxel)
+    with open(path, "wb") as f:
+        f.write(data)
+
+
 def disparity_to_float(d16):
     """float32 disparity in pixels (d16 / 16), NaN where invalid."""
     d16 = np.asarray(d16)
@@ -905,6 +951,97 @@ class VoxelMap:
             pass
 
 
+class TsdfMap:
+    """viso_tsdf: a persistent map of truncated signed distances on the device that dense disparity maps and their poses are fused
+    into, read back as voxels or as the points where the averaged distance changes sign (opt-in, not in the reference; the
+    definition of include/viso_hip.h).  ctx: a Context, or None for the default one.  With a trajectory:
+
+        poses, valid = hostmath.chain_poses(tr, ok)      # poses[k + 1] places frame valid[k] in frame 0's coordinates
+        tsdf = TsdfMap(ctx, voxel=0.2)
+        for k, t in enumerate(valid):
+            batch.fuse_tsdf(tsdf, poses[k + 1][None], t0=t, t1=t + 1)
+        write_surface_ply("surface.ply", tsdf.surface(min_weight=2), tsdf.voxel)
+    """
+
+    def __init__(self, ctx=None, params=None, **kw):
+        self.L = load()
+        if isinstance(params, TsdfParams):
+            if kw:
+                raise TypeError("TsdfMap: keyword fields cannot be combined with a TsdfParams")
+        else:
+            params = tsdf_params(**dict(params or {}, **kw))
+        self.ctx, self.voxel, self.trunc_voxels = ctx, float(params.voxel), int(params.trunc_voxels)
+        h = C.c_void_p()
+        r = self.L.viso_tsdf_create(ctx.h if ctx is not None else None, C.byref(params), C.byref(h))
+        self.h = h.value if r == 1 else None
+        if r != 1:
+            _err("viso_tsdf_create", r)
+        _live.add(self)
+
+    def _chk(self, where, r):
+        if r != 1:
+            _err(where, r)
+
+    def fuse(self, d16, param, pose=None):
+        """viso_tsdf_fuse: one host int16 map with the calibration of param (f, cu, cv, base) and an optional 4 x 4 pose."""
+        d16 = np.ascontiguousarray(d16)
+        if d16.ndim != 2 or d16.dtype != np.int16:
+            raise ValueError("TsdfMap.fuse: the map must be a 2-D int16 array")
+        if pose is not None and np.shape(pose) != (4, 4):
+            raise ValueError("TsdfMap.fuse: the pose must be a 4 x 4 matrix")
+        T, Tp = _pose_arg("TsdfMap.fuse", pose)
+        self._chk("viso_tsdf_fuse", self.L.viso_tsdf_fuse(self.h, ptr(d16, C.c_int16), d16.shape[0], d16.shape[1], C.byref(param), Tp))
+
+    def add_entries(self, entries):
+        """viso_tsdf_add_entries: the entries of another map with the same voxel and truncation (or of a saved one) added to this one."""
+        entries = np.ascontiguousarray(entries, dtype=TSDF_ENTRY_DTYPE)
+        self._chk("viso_tsdf_add_entries", self.L.viso_tsdf_add_entries(self.h, entries.ctypes.data, len(entries)))
+
+    def _list(self, count_name, get_name, dtype, min_weight):
+        n = C.c_size_t()
+        self._chk(count_name, getattr(self.L, count_name)(self.h, int(min_weight), C.byref(n)))
+        out = np.zeros(n.value, dtype)
+        self._chk(get_name, getattr(self.L, get_name)(self.h, int(min_weight), out.ctypes.data, len(out), C.byref(n)))
+        return out[:n.value]
+
+    def entries(self, min_weight=1):
+        """viso_tsdf_get: the voxels with at least min_weight updates as a TSDF_ENTRY_DTYPE array (k, weight, sum), sorted by key."""
+        return self._list("viso_tsdf_count", "viso_tsdf_get", TSDF_ENTRY_DTYPE, min_weight)
+
+    def surface(self, min_weight=1):
+        """viso_tsdf_surface: the sign changes between neighbouring voxels of at least min_weight updates as a TSDF_CROSSING_DTYPE
+        array (k, axis, wa, wb, sa, sb), sorted by (key, axis)."""
+        return self._list("viso_tsdf_surface_count", "viso_tsdf_surface", TSDF_CROSSING_DTYPE, min_weight)
+
+    def surface_points(self, min_weight=1):
+        """float32 [n][3]: the crossing points of surface(min_weight), in their order."""
+        return tsdf_crossing_points(self.surface(min_weight), self.voxel)
+
+    def stats(self):
+        """viso_tsdf_stats as a dict: n_points, n_updates, n_out_of_range, n_dropped, n_occupied."""
+        c = TsdfCounters()
+        self._chk("viso_tsdf_stats", self.L.viso_tsdf_stats(self.h, C.byref(c)))
+        return {name: int(getattr(c, name)) for name, _ in TsdfCounters._fields_}
+
+    def clear(self):
+        self._chk("viso_tsdf_clear", self.L.viso_tsdf_clear(self.h))
+
+    def close(self):
+        if self.h:
+            h, self.h = self.h, None
+            r = self.L.viso_tsdf_destroy(h)
+            if r != 1:
+                _err("viso_tsdf_destroy", r)
+
+    def __del__(self, _finalizing=sys.is_finalizing):   # bound at definition: module globals are None late in shutdown
+        if _finalizing():   # the atexit hook has closed everything that was still open
+            return
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Batch:
     """viso_batch: n_frames stereo frames resident in HBM (include/viso_hip.h)."""
 
@@ -1093,6 +1230,15 @@ class Batch:
         if T.ndim != 3 or T.shape[1:] != (4, 4) or T.shape[0] != t1 - int(t0):
             raise ValueError("Batch.fuse_disparities: poses must be [t1 - t0][4][4]")
         self._chk("viso_batch_fuse_disparities", self.L.viso_batch_fuse_disparities(self.h, vmap.h, int(t0), t1, ptr(T, C.c_double)))
+
+    def fuse_tsdf(self, tsdf, poses, t0=0, t1=None):
+        """viso_batch_fuse_tsdf: the resident maps of frames t0 .. t1-1 (t1 None: to the last frame) fused into the TsdfMap on the
+        device, frame t0 + i with the 4 x 4 pose poses[i]; no map is copied to the host.  The map must be on this batch's context."""
+        t1 = self.nf if t1 is None else int(t1)
+        T = np.ascontiguousarray(poses, dtype=np.float64)
+        if T.ndim != 3 or T.shape[1:] != (4, 4) or T.shape[0] != t1 - int(t0):
+            raise ValueError("Batch.fuse_tsdf: poses must be [t1 - t0][4][4]")
+        self._chk("viso_batch_fuse_tsdf", self.L.viso_batch_fuse_tsdf(self.h, tsdf.h, int(t0), t1, ptr(T, C.c_double)))
 
     def run_disparity(self):
         """viso_batch_run_disparity: only the disparity, over the resident images (upload_images_only)."""

@@ -249,6 +249,48 @@ def declare_map(lib):
     lib.viso_map_entry_centroid.argtypes = [vp, C.c_double, f32p]
 
 
+class TsdfParams(C.Structure):
+    """struct viso_tsdf_params (include/viso_hip.h, "TSDF map")."""
+    _fields_ = [("voxel", C.c_double), ("trunc_voxels", C.c_int32), ("min_disp16", C.c_int32), ("capacity_log2", C.c_int32)]
+
+    def ok(self):
+        """The valid ranges of include/viso_hip.h (what the library checks before it touches a device)."""
+        return (bool(np.isfinite(self.voxel)) and self.voxel > 0 and 1 <= self.trunc_voxels <= 8 and self.min_disp16 >= 1
+                and 10 <= self.capacity_log2 <= 28)
+
+
+TSDF_DEFAULTS = dict(voxel=0.2, trunc_voxels=3, min_disp16=16, capacity_log2=26)   # viso_tsdf_params_default
+
+# struct viso_tsdf_entry (24 bytes) and struct viso_tsdf_crossing (40 bytes)
+TSDF_ENTRY_DTYPE = np.dtype([("k", np.int32, (3,)), ("weight", np.uint32), ("sum", np.int64)])
+TSDF_CROSSING_DTYPE = np.dtype([("k", np.int32, (3,)), ("axis", np.int32), ("wa", np.uint32), ("wb", np.uint32), ("sa", np.int64),
+                                ("sb", np.int64)])
+
+
+class TsdfCounters(C.Structure):
+    """struct viso_tsdf_counters (include/viso_hip.h, "TSDF map")."""
+    _fields_ = [(name, C.c_uint64) for name in ("n_points", "n_updates", "n_out_of_range", "n_dropped", "n_occupied")]
+
+
+def declare_tsdf(lib):
+    """Prototypes of the opt-in TSDF map (include/viso_hip.h; libviso_hip.so only)."""
+    i16p, TPP, vp, szp = C.POINTER(C.c_int16), C.POINTER(TsdfParams), C.c_void_p, C.POINTER(C.c_size_t)
+    lib.viso_tsdf_params_default.restype = None
+    lib.viso_tsdf_params_default.argtypes = [TPP]
+    lib.viso_tsdf_create.argtypes = [vp, TPP, C.POINTER(vp)]
+    lib.viso_tsdf_destroy.argtypes = [vp]
+    lib.viso_tsdf_clear.argtypes = [vp]
+    lib.viso_tsdf_fuse.argtypes = [vp, i16p, C.c_int, C.c_int, C.POINTER(Param), f64p]
+    lib.viso_batch_fuse_tsdf.argtypes = [vp, vp, C.c_int, C.c_int, f64p]
+    lib.viso_tsdf_add_entries.argtypes = [vp, vp, C.c_size_t]
+    lib.viso_tsdf_count.argtypes = [vp, C.c_uint32, szp]
+    lib.viso_tsdf_get.argtypes = [vp, C.c_uint32, vp, C.c_size_t, szp]
+    lib.viso_tsdf_surface_count.argtypes = [vp, C.c_uint32, szp]
+    lib.viso_tsdf_surface.argtypes = [vp, C.c_uint32, vp, C.c_size_t, szp]
+    lib.viso_tsdf_stats.argtypes = [vp, C.POINTER(TsdfCounters)]
+    lib.viso_tsdf_crossing_point.argtypes = [vp, C.c_double, f32p]
+
+
 class MotionCov(C.Structure):
     """struct viso_motion_cov (include/viso_hip.h, "motion covariance")."""
     _fields_ = [

@@ -17,6 +17,7 @@
 // The statistics are 256 sets of counters on cache lines of their own (a workgroup adds to set blockIdx & 255, one atomic per wave
 // and counter), summed on the host; the dropped points, which are rare, have one word.
 #include "common.h"
+#include "voxel_hash.h"
 
 #include <algorithm>
 #include <cmath>
@@ -24,9 +25,6 @@
 #include <unordered_set>
 #include <vector>
 
-#define MAP_EMPTY 0xffffffffffffffffull
-#define MAP_BIAS (1 << 20)
-#define MAP_RANGE 1073741824.0          // 2^30: |g| at and beyond it is out of range
 #define MAP_STAT_SETS 256
 #define MAP_STAT_WORDS 16               // 128 bytes a set
 #define MAP_ST_POINTS 0
@@ -45,32 +43,11 @@ struct MapTable {
     uint32_t mask;               // slots - 1
 };
 
-__device__ __forceinline__ uint32_t map_hash(unsigned long long k) {   // the finaliser of splitmix64
-    k ^= k >> 30; k *= 0xbf58476d1ce4e5b9ull;
-    k ^= k >> 27; k *= 0x94d049bb133111ebull;
-    k ^= k >> 31;
-    return (uint32_t)k;
-}
-
-// The slot of `key`, claimed if the key is new.  false: every slot holds another key.
-__device__ __forceinline__ bool map_probe(const MapTable& t, unsigned long long key, uint32_t* slot_out, bool* claimed) {
-    uint32_t slot = map_hash(key) & t.mask;
-    for (uint32_t n = 0; n <= t.mask; ++n, slot = (slot + 1) & t.mask) {   // at most one visit of every slot
-        unsigned long long cur = __hip_atomic_load(t.keys + slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (cur == MAP_EMPTY) {
-            cur = atomicCAS(t.keys + slot, MAP_EMPTY, key);
-            if (cur == MAP_EMPTY) { *claimed = true; *slot_out = slot; return true; }
-        }
-        if (cur == key) { *slot_out = slot; return true; }
-    }
-    return false;
-}
-
 // count points with offset sums sx, sy, sz into the voxel `key`
 __device__ __forceinline__ void map_insert(const MapTable& t, unsigned long long key, uint32_t count, unsigned long long sx,
                                            unsigned long long sy, unsigned long long sz, bool* claimed) {
     uint32_t slot;
-    if (map_probe(t, key, &slot, claimed)) {
+    if (voxel_probe(t.keys, t.mask, key, &slot, claimed)) {
         atomicAdd(t.cnt + slot, count);
         atomicAdd(t.sums + 3 * (size_t)slot + 0, sx);
         atomicAdd(t.sums + 3 * (size_t)slot + 1, sy);
@@ -91,11 +68,6 @@ __device__ __forceinline__ void map_count_wave(const MapTable& t, unsigned block
         if (no) atomicAdd(st + MAP_ST_OOR, no);
         if (nc) atomicAdd(st + MAP_ST_OCC, nc);
     }
-}
-
-__device__ __forceinline__ unsigned long long map_key(int kx, int ky, int kz) {
-    return ((unsigned long long)(uint32_t)(kx + MAP_BIAS) << 42) | ((unsigned long long)(uint32_t)(ky + MAP_BIAS) << 21) |
-           (unsigned long long)(uint32_t)(kz + MAP_BIAS);
 }
 
 struct FuseArgs {

@@ -1,4 +1,5 @@
 """python -m libviso_amd.fuse_map DISPARITY_DIR POSES.txt CALIB.txt OUT.ply [--voxel V --min-count N --min-disp PX --frames B E]
+                                 [--surface [--trunc T --min-weight N]]
 
 Fuses the maps a KITTI runner wrote with --disparity DIR and the poses of its pose file into one voxel map on the device
 (libviso_amd.VoxelMap; include/viso_hip.h, "voxel map") and writes the occupied voxels as a binary PLY point cloud: x, y, z the
@@ -8,6 +9,10 @@ float32 centroid of each voxel, count the number of points fused into it.
   POSES.txt      KITTI pose file: 12 numbers a line, the first three rows of the pose; line i belongs to the i-th map
   CALIB.txt      the sequence's calib.txt (lines P0: and P1:)
   --frames B E   only maps B .. E-1 of the directory (positions in name order), with their poses
+  --surface      fuse into a TSDF map instead (libviso_amd.TsdfMap; include/viso_hip.h, "TSDF map") and write the points where the
+                 averaged signed distance changes sign between neighbouring voxels: x, y, z the float32 crossing point, weight the
+                 smaller of the two voxels' weights.  --trunc T: the truncation band in voxels (3); --min-weight N: only voxels
+                 with at least this many updates (1).  --capacity-log2 then defaults to 26.
 
 Both runners write byte-identical directories and pose files for every rank count and chunk size, so the PLY is identical too."""
 import argparse
@@ -133,7 +138,10 @@ def main(argv=None):
     ap.add_argument("--min-count", type=int, default=1, help="only voxels with at least this many points (1)")
     ap.add_argument("--min-disp", type=float, default=1.0, help="smallest disparity used, in pixels (1.0)")
     ap.add_argument("--frames", type=int, nargs=2, metavar=("B", "E"), help="only maps B .. E-1 of the directory")
-    ap.add_argument("--capacity-log2", type=int, default=24, help="log2 of the table's slots (24)")
+    ap.add_argument("--capacity-log2", type=int, default=None, help="log2 of the table's slots (24; 26 with --surface)")
+    ap.add_argument("--surface", action="store_true", help="write the surface crossings of a TSDF map in place of the centroids")
+    ap.add_argument("--trunc", type=int, default=3, help="with --surface: the truncation band in voxels (3)")
+    ap.add_argument("--min-weight", type=int, default=1, help="with --surface: only voxels with at least this many updates (1)")
     a = ap.parse_args(argv)
     import libviso_amd
     from libviso_amd.abi import Param
@@ -145,7 +153,21 @@ def main(argv=None):
         sys.exit(f"fuse_map: --frames {b} {e} is outside the {len(names)} maps")
     f, cu, cv, base = read_calib(a.calib)
     prm = Param.default(base=base, f=f, cu=cu, cv=cv)
-    vmap = libviso_amd.VoxelMap(None, voxel=a.voxel, min_disp16=max(1, int(round(a.min_disp * 16))), capacity_log2=a.capacity_log2)
+    if a.surface:
+        tsdf = libviso_amd.TsdfMap(None, voxel=a.voxel, trunc_voxels=a.trunc, min_disp16=max(1, int(round(a.min_disp * 16))),
+                                   capacity_log2=26 if a.capacity_log2 is None else a.capacity_log2)
+        try:
+            for i in range(b, e):
+                tsdf.fuse(read_disparity_png(os.path.join(a.disparity_dir, names[i])), prm, pose=poses[i])
+            crossings, st = tsdf.surface(a.min_weight), tsdf.stats()
+        finally:
+            tsdf.close()
+        libviso_amd.write_surface_ply(a.out, crossings, a.voxel)
+        print(f"fuse_map: {e - b} maps, {st['n_points']} points, {st['n_updates']} updates ({st['n_out_of_range']} samples out of range), "
+              f"{st['n_occupied']} voxels, {len(crossings)} crossings at weight >= {a.min_weight} -> {a.out}")
+        return 0
+    vmap = libviso_amd.VoxelMap(None, voxel=a.voxel, min_disp16=max(1, int(round(a.min_disp * 16))),
+                                capacity_log2=24 if a.capacity_log2 is None else a.capacity_log2)
     try:
         for i in range(b, e):
             vmap.fuse(read_disparity_png(os.path.join(a.disparity_dir, names[i])), prm, pose=poses[i])

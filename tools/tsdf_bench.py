@@ -1,0 +1,118 @@
+"""Cost of the opt-in TSDF map (viso_tsdf_*, viso_batch_fuse_tsdf) at 512 block-matching maps of 1241x376, default parameters
+(voxel 0.2 m, T = 3, min_disp16 16, 2^26 slots; the next capacity that holds the scene when that one overflows).
+
+  python tools/tsdf_bench.py [--frames N] [--reps N] [--capacity-log2 N] [--kernel-only] [--out FILE]
+
+The pairs and poses are those of tools/map_bench.py: 17 seeded synthetic frames repeated, frame t seen from a camera that has moved
+0.8 t m forward and turned 0.002 t rad.  Legs (host clock around work that ends in a synchronise, medians of alternating
+repetitions):
+  fuse_tsdf    Batch.fuse_tsdf of all resident maps into a cleared map (the clear is outside the clock);
+  fuse_map     Batch.fuse_disparities of the same maps into a cleared voxel map: the comparison;
+  entries      TsdfMap.entries(): two compaction passes, the copy, the sort on the host;
+  surface      TsdfMap.surface(): two passes of three probes a voxel, the copy, the sort on the host;
+  clear        viso_tsdf_clear.
+n_updates / n_points from viso_tsdf_stats is the number of voxels a pixel's band touches.  --kernel-only runs clear + fuse_tsdf
+--reps times and both extractions once: the run to put under `rocprofv3 --kernel-trace --stats` for the kernels' own times.  The
+count the result is held against (not a measurement) is printed with it."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import libviso_amd  # noqa: E402
+from libviso_amd import hostmath, synth  # noqa: E402
+from libviso_amd.abi import MatchParams  # noqa: E402
+
+
+def count_ms(nf, rows, cols):
+    """A count, not a measurement: every map read once (2 B a pixel) over 8 TB/s.  A floor for the pass: neither the table's atomics
+    nor the five double divisions a sample are in it."""
+    b = float(rows) * cols * nf * 2
+    return b, b / 8e12 * 1e3
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=512)
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--capacity-log2", type=int, default=26)
+    ap.add_argument("--kernel-only", action="store_true")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    nf = a.frames
+    seq = synth.make_image_sequence(2000, 17, n_kp=64)
+    images = np.ascontiguousarray(np.resize(seq["images"], (nf,) + seq["images"].shape[1:]))
+    rows, cols = images.shape[2:]
+    poses = np.array([np.linalg.inv(hostmath.tr2mat([0.0, 0.002 * t, 0.0, 0.0, 0.0, -0.8 * t])) for t in range(nf)])
+    ctx = libviso_amd.Context(0)
+
+    def clock(fn):
+        ctx.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        ctx.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    b = libviso_amd.Batch(ctx, nf, 64)
+    b.upload_images_only(images)
+    b.set_params(MatchParams.stereo(seq["F"]), MatchParams.temporal(), seq["param"])
+    b.set_disparity({})
+    b.run_disparity()
+    # the default capacity, or the next one that holds the scene (the result names the one used)
+    for log2 in sorted({a.capacity_log2, 27, 28}):
+        if log2 < a.capacity_log2:
+            continue
+        tsdf = libviso_amd.TsdfMap(ctx, capacity_log2=log2)
+        try:
+            b.fuse_tsdf(tsdf, poses)
+            break
+        except libviso_amd.VisoError as e:
+            tsdf.close()
+            if "-4" not in str(e) or log2 == 28:
+                raise
+
+    if a.kernel_only:
+        ms = []
+        for _ in range(a.reps):
+            tsdf.clear()
+            ms.append(clock(lambda: b.fuse_tsdf(tsdf, poses)))
+        res = {"frames": nf, "fuse_tsdf_ms": ms, "voxels": int(len(tsdf.entries())), "crossings": int(len(tsdf.surface()))}
+        print(json.dumps(res))
+        tsdf.close(); b.close(); ctx.close()
+        return
+
+    vmap = libviso_amd.VoxelMap(ctx, capacity_log2=26)
+    for _ in range(2):   # warm-up
+        tsdf.clear(); b.fuse_tsdf(tsdf, poses); tsdf.entries(); tsdf.surface()
+        vmap.clear(); b.fuse_disparities(vmap, poses)
+    legs = {k: [] for k in ("fuse_tsdf", "fuse_map", "entries", "surface", "clear")}
+    for _ in range(a.reps):   # alternating
+        legs["clear"].append(clock(tsdf.clear))
+        legs["fuse_tsdf"].append(clock(lambda: b.fuse_tsdf(tsdf, poses)))
+        vmap.clear()
+        legs["fuse_map"].append(clock(lambda: b.fuse_disparities(vmap, poses)))
+        legs["entries"].append(clock(tsdf.entries))
+        legs["surface"].append(clock(tsdf.surface))
+    st, n_vox, n_cross = tsdf.stats(), len(tsdf.entries()), len(tsdf.surface())
+    res = {"frames": nf, "shape": [int(rows), int(cols)], "params": "voxel 0.2, T 3, min_disp16 16", "capacity_log2": log2, "reps": a.reps,
+           "ms_median": {k: float(np.median(v)) for k, v in legs.items()}, "ms_min": {k: float(np.min(v)) for k, v in legs.items()},
+           "stats": st, "voxels": int(n_vox), "crossings": int(n_cross), "updates_per_point": st["n_updates"] / max(1, st["n_points"]),
+           "map_stats": vmap.stats()}
+    res["count_bytes"], res["count_ms"] = count_ms(nf, rows, cols)
+    print(json.dumps(res))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+    tsdf.close(); vmap.close()
+    b.close(); ctx.close()
+
+
+if __name__ == "__main__":
+    main()
