@@ -969,8 +969,8 @@ int viso_map_entry_centroid(const viso_map_entry* entry, double voxel, float out
  * VISO_ERR_NOMEM and marks the map overflowed, and every getter, viso_tsdf_add_entries and every fuse call then refuse with
  * VISO_ERR_NOMEM until viso_tsdf_clear.  Every probe loop, the read-only lookups of the extraction included, visits each slot at
  * most once and advances strictly.
- * Out of scope: triangle meshes, colour, carving free space beyond the truncation band, weights that fall with depth, eviction,
- * fusing inside the KITTI runners, the sort on the device.
+ * Out of scope: colour, carving free space beyond the truncation band, weights that fall with depth, eviction, fusing inside the
+ * KITTI runners, the sort on the device.
  * HIP kernels (tsdf.hip): tsdf_fuse_kernel (one thread per pixel of a group of frames; the loop over j is uniform across the wave,
  * and per j the lanes that continue the voxel of the lane to their left form a run whose head lane alone probes the table and
  * issues the two integer atomic adds), tsdf_add_entries_kernel, tsdf_compact_kernel, tsdf_crossings_kernel, tsdf_clear_kernel.
@@ -1032,6 +1032,57 @@ int viso_tsdf_stats(viso_tsdf* t, viso_tsdf_counters* out);
 /* Step 10.  Host only; VISO_ERR_ARG for a null pointer, an axis outside 0..2, a weight of 0, sums of the same sign, a voxel that
  * is not finite and > 0. */
 int viso_tsdf_crossing_point(const viso_tsdf_crossing* crossing, double voxel, float out[3]);
+
+/* ------------------------------------------------ TSDF mesh: triangles by marching tetrahedra (opt-in; NOT in the reference)
+ *
+ * The surface of a TSDF map as a triangle mesh.  A mesh is a function of the signs and the integer sums of the voxels alone, so it
+ * depends on neither the order of the frames nor on scheduling.  This definition is the contract; the device output is
+ * bit-identical to tests/mesh_ref.py.  Marching tetrahedra rather than marching cubes: the 16 cases of one tetrahedron follow from
+ * the rule below, no face is ambiguous, and the subdivision is the same in every cube and matches across cube faces, so the mesh is
+ * a closed oriented 2-manifold wherever the data is complete.
+ *   Voxels: a voxel is usable when weight >= min_weight (min_weight >= 1).  A usable voxel is negative when sum < 0, otherwise
+ *     positive (the rule of step 9 above).
+ *   Cells: the cell of voxel k has the 8 corners k + (dx, dy, dz), dx, dy, dz in {0, 1}.  A cell with a corner that is not usable
+ *     emits nothing.  A cell with k_i = 2^20 - 1 on any axis emits nothing: no key is formed beyond a field.
+ *   Tetrahedra: the six permutations pi of (0, 1, 2) in lexicographic order are the tetrahedra 0..5 of a cell, with the corners
+ *     c0 = k, c1 = c0 + e_pi0, c2 = c1 + e_pi1, c3 = c2 + e_pi2 = k + (1, 1, 1) (the Kuhn subdivision).
+ *   Edges: the edge between ci and cj (i < j) belongs to voxel ci; its direction is d = cj - ci in {0, 1}^3 \ 0, with the code
+ *     dir = dx + 2 dy + 4 dz (1..7; the axes are 1, 2, 4).  Edge (a, dir) carries a vertex when both ends a and b = a + d are usable
+ *     and differ in sign.  With da = (double)sa / (double)wa, db likewise, t = da / (da - db):
+ *     p_i = (float)(((double)(a_i 1024 + 512) + (d_i ? t 1024.0 : 0.0)) s), s = voxel / 1024.  For dir = 1, 2, 4 this is step 10
+ *     above bit for bit.  t lies in [0, 1); t = 0 when sum_a = 0, and the triangles of zero area that follow stay in the list.
+ *   Triangles of a tetrahedron, N its negative and P its positive corners, each by ascending local index, e(i, j) the vertex on
+ *     the edge between corners i and j: N or P empty: none.  One corner i alone on its side: (e(i, j1), e(i, j2), e(i, j3)) over
+ *     the other corners ascending.  N = {a, b}, P = {c, d}: (e(a, c), e(a, d), e(b, d)) and (e(a, c), e(b, d), e(b, c)), index 0, 1.
+ *   Orientation: the normal points to the positive side, towards the camera that saw the surface.  With every vertex at its edge
+ *     midpoint (2 owner + d, in half voxels), n = (v1 - v0) x (v2 - v0) and g = |N| sum_P c - |P| sum_N c: v1 and v2 are swapped
+ *     when n . g < 0 (n . g is never 0).  The interpolated triangle has the orientation of the midpoint one.
+ *   Output: the vertices some triangle refers to, sorted by (key of owner, dir); the triangles as indices into that list, sorted
+ *     by (key of cell, tetrahedron, index).  More than 2^32 - 1 vertices: VISO_ERR_UNSUPPORTED.
+ * Full table, the overflowed state and the lifetime of the handle are the TSDF map's.
+ * HIP kernel (tsdf.hip): tsdf_mesh_kernel, one thread per slot: seven read-only probes for the other corners of its cell; the
+ * sign-changing edges it owns as vertex records, positions computed on the device in double, and, when all eight corners are
+ * usable, the cell's at most 12 triangles as references (cell, tetrahedron, index, three (corner, dir)).  Count pass and list pass
+ * as for the crossings.  An owned edge can belong to a complete cell other than its owner's, so every sign-changing edge is
+ * emitted; the host sorts both lists, drops the vertices no triangle refers to and resolves the references by binary search. */
+typedef struct viso_tsdf_mesh_vertex {   /* 32 bytes */
+    int32_t k[3];            /* the edge's owner a; its other end is a + (dir & 1, dir >> 1 & 1, dir >> 2) */
+    int32_t dir;             /* 1..7 */
+    float p[3];              /* position, metres */
+    uint32_t weight;         /* min(wa, wb) */
+} viso_tsdf_mesh_vertex;
+
+typedef struct viso_tsdf_triangle {   /* 12 bytes */
+    uint32_t v[3];           /* indices into the vertex list */
+} viso_tsdf_triangle;
+
+/* The numbers of vertices and triangles of the mesh at min_weight.  (The whole extraction runs: which vertices are referred to is
+ * only known once the references are resolved.) */
+int viso_tsdf_mesh_count(viso_tsdf* t, uint32_t min_weight, size_t* n_vertices, size_t* n_triangles);
+/* The mesh.  Arguments are checked before any device is touched, with the refusals of viso_tsdf_surface.  VISO_ERR_ARG, with both
+ * numbers set and nothing written, when either capacity is smaller. */
+int viso_tsdf_mesh(viso_tsdf* t, uint32_t min_weight, viso_tsdf_mesh_vertex* vertices_out, size_t nv_cap,
+                   viso_tsdf_triangle* triangles_out, size_t nt_cap, size_t* n_vertices, size_t* n_triangles);
 
 #ifdef __cplusplus
 }

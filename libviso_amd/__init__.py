@@ -19,7 +19,7 @@ import numpy as np
 from .abi import (DESC_LEN, MAP_DEFAULTS, MAP_ENTRY_DTYPE, MapCounters, MapParams, declare_map, MOTION_COV_DTYPE, MOTION_REFINE_DTYPE, SGM_DEFAULTS, SPECKLE_DEFAULTS, WINDOW_RECORD_DTYPE, DisparityParams, MatchParams,
                   Param, SgmParams, SpeckleParams, declare_common, declare_covariance, declare_disparity, declare_refine, declare_rectify,
                   declare_sgm, declare_speckle, declare_subpixel, declare_window, f32p, f64p, i32p, i64p, intp, ptr,
-                  TSDF_CROSSING_DTYPE, TSDF_DEFAULTS, TSDF_ENTRY_DTYPE, TsdfCounters, TsdfParams, declare_tsdf)
+                  TSDF_CROSSING_DTYPE, TSDF_DEFAULTS, TSDF_ENTRY_DTYPE, TSDF_MESH_VERTEX_DTYPE, TsdfCounters, TsdfParams, declare_tsdf)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("VISO_HIP_SO") or os.path.join(_HERE, "libviso_hip.so")   # VISO_HIP_SO: another build of the library (A/B runs)
@@ -687,6 +687,30 @@ def write_surface_ply(path, crossings, voxel):
         f.write(data)
 
 
+def mesh_ply_bytes(vertices, triangles):
+    """The bytes of write_mesh_ply: a binary little-endian PLY; per vertex x, y, z the float32 position and weight a uint32, per
+    face a uchar 3 and three int32 vertex indices, both in the order given."""
+    vertices = np.ascontiguousarray(vertices, dtype=TSDF_MESH_VERTEX_DTYPE)
+    triangles = np.ascontiguousarray(triangles, dtype=np.uint32).reshape(-1, 3)
+    if len(triangles) and (int(triangles.max()) >= len(vertices) or len(vertices) > 2 ** 31):
+        raise ValueError("mesh_ply_bytes: a triangle refers to a vertex that is not in the list (or is beyond int32)")
+    v = np.empty(len(vertices), np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("weight", "<u4")]))
+    v["x"], v["y"], v["z"], v["weight"] = vertices["p"][:, 0], vertices["p"][:, 1], vertices["p"][:, 2], vertices["weight"]
+    f = np.empty(len(triangles), np.dtype([("n", "u1"), ("v", "<i4", (3,))]))
+    f["n"], f["v"] = 3, triangles
+    head = ("ply\nformat binary_little_endian 1.0\ncomment libviso_amd TSDF mesh\nelement vertex %d\n"
+            "property float x\nproperty float y\nproperty float z\nproperty uint weight\nelement face %d\n"
+            "property list uchar int vertex_indices\nend_header\n" % (len(vertices), len(triangles)))
+    return head.encode("ascii") + v.tobytes() + f.tobytes()
+
+
+def write_mesh_ply(path, vertices, triangles):
+    """The mesh of TsdfMap.mesh as a PLY file (mesh_ply_bytes)."""
+    data = mesh_ply_bytes(vertices, triangles)
+    with open(path, "wb") as f:
+        f.write(data)
+
+
 def disparity_to_float(d16):
     """float32 disparity in pixels (d16 / 16), NaN where invalid."""
     d16 = np.asarray(d16)
@@ -961,6 +985,7 @@ class TsdfMap:
         for k, t in enumerate(valid):
             batch.fuse_tsdf(tsdf, poses[k + 1][None], t0=t, t1=t + 1)
         write_surface_ply("surface.ply", tsdf.surface(min_weight=2), tsdf.voxel)
+        write_mesh_ply("mesh.ply", *tsdf.mesh(min_weight=2))
     """
 
     def __init__(self, ctx=None, params=None, **kw):
@@ -1016,6 +1041,17 @@ class TsdfMap:
     def surface_points(self, min_weight=1):
         """float32 [n][3]: the crossing points of surface(min_weight), in their order."""
         return tsdf_crossing_points(self.surface(min_weight), self.voxel)
+
+    def mesh(self, min_weight=1):
+        """viso_tsdf_mesh: the surface as triangles by marching tetrahedra over the voxels of at least min_weight updates.  Returns
+        (vertices, triangles): a TSDF_MESH_VERTEX_DTYPE array (k, dir, p, weight) sorted by (key, dir), and uint32 [n][3] indices
+        into it sorted by (cell, tetrahedron, index), the normals towards the side the surface was seen from."""
+        nv, nt = C.c_size_t(), C.c_size_t()
+        self._chk("viso_tsdf_mesh_count", self.L.viso_tsdf_mesh_count(self.h, int(min_weight), C.byref(nv), C.byref(nt)))
+        v, tri = np.zeros(nv.value, TSDF_MESH_VERTEX_DTYPE), np.zeros((nt.value, 3), np.uint32)
+        self._chk("viso_tsdf_mesh", self.L.viso_tsdf_mesh(self.h, int(min_weight), v.ctypes.data, len(v), tri.ctypes.data, len(tri),
+                                                          C.byref(nv), C.byref(nt)))
+        return v[:nv.value], tri[:nt.value]
 
     def stats(self):
         """viso_tsdf_stats as a dict: n_points, n_updates, n_out_of_range, n_dropped, n_occupied."""

@@ -265,6 +265,8 @@ TSDF_DEFAULTS = dict(voxel=0.2, trunc_voxels=3, min_disp16=16, capacity_log2=26)
 TSDF_ENTRY_DTYPE = np.dtype([("k", np.int32, (3,)), ("weight", np.uint32), ("sum", np.int64)])
 TSDF_CROSSING_DTYPE = np.dtype([("k", np.int32, (3,)), ("axis", np.int32), ("wa", np.uint32), ("wb", np.uint32), ("sa", np.int64),
                                 ("sb", np.int64)])
+# struct viso_tsdf_mesh_vertex (32 bytes); a struct viso_tsdf_triangle is a row of a uint32 [n][3] array
+TSDF_MESH_VERTEX_DTYPE = np.dtype([("k", np.int32, (3,)), ("dir", np.int32), ("p", np.float32, (3,)), ("weight", np.uint32)])
 
 
 class TsdfCounters(C.Structure):
@@ -289,6 +291,8 @@ def declare_tsdf(lib):
     lib.viso_tsdf_surface.argtypes = [vp, C.c_uint32, vp, C.c_size_t, szp]
     lib.viso_tsdf_stats.argtypes = [vp, C.POINTER(TsdfCounters)]
     lib.viso_tsdf_crossing_point.argtypes = [vp, C.c_double, f32p]
+    lib.viso_tsdf_mesh_count.argtypes = [vp, C.c_uint32, szp, szp]
+    lib.viso_tsdf_mesh.argtypes = [vp, C.c_uint32, vp, C.c_size_t, vp, C.c_size_t, szp, szp]
 
 
 class MotionCov(C.Structure):

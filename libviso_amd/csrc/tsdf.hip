@@ -1,6 +1,6 @@
 // tsdf.hip — opt-in TSDF map: dense disparity maps and poses fused into a hash table of truncated signed distances on the device,
 // and the sign changes between neighbouring voxels read back as surface crossings (NOT in the reference: viso_tsdf_*,
-// viso_batch_fuse_tsdf, include/viso_hip.h).
+// viso_batch_fuse_tsdf, include/viso_hip.h) or as a triangle mesh by marching tetrahedra.
 //
 // The table is the voxel map's (voxel_hash.h): keys [slots] u64 (all ones = empty), weight [slots] u32, sum [slots] i64 (added as
 // u64, two's complement).  A key is claimed with one 64-bit compare-and-swap; everything added behind it is an integer atomic add,
@@ -17,6 +17,9 @@
 //   tsdf_compact_kernel      one thread per slot: the slots with weight >= min_weight to a dense list, one atomic per wave for the
 //                            list positions (out == null: only their number).
 //   tsdf_crossings_kernel    one thread per slot, three read-only probes for the neighbours at +1 on every axis; the same two passes.
+//   tsdf_mesh_kernel         one thread per slot, seven read-only probes for the other corners of the voxel's cell: the sign-changing
+//                            edges the voxel owns as vertices, and the triangles of the cell's six tetrahedra as references to
+//                            them; two lists, one atomic per wave and list; the same two passes.
 //   tsdf_clear_kernel        one thread per slot.
 // The statistics are 256 sets of counters on cache lines of their own (a wave adds its totals once, at its end), summed on the host.
 #include "common.h"
@@ -244,6 +247,139 @@ __global__ __launch_bounds__(256) void tsdf_crossings_kernel(TsdfTable t, uint32
             out[at] = c;
         }
         ++at;
+    }
+}
+
+// ---- triangle mesh by marching tetrahedra (include/viso_hip.h, "TSDF mesh") --------------------------------------
+// A cell's corners carry the code c = dx + 2 dy + 4 dz.  Tetrahedron t (the permutations of the axes in lexicographic order) has the
+// corners c0 = 0, c1 = c0 + e_pi0, c2 = c1 + e_pi1, c3 = 7: TSDF_TET_CORNERS(t) packs their codes, three bits each.  A tetrahedron's
+// case is the four signs of its corners, bit i = corner i negative.  Derived from the rule of the header for the tetrahedron of the
+// identity permutation, whose corners are (0,0,0), (1,0,0), (1,1,0), (1,1,1):
+//   the number of triangles per case: 0 for none or all negative, 2 for two against two, else 1 (TSDF_TET_COUNTS, two bits a case);
+//   the triangles per case: twelve bits a triangle, four a vertex, the vertex on the edge between the local corners i < j as i | j << 2.
+//   One corner i alone: e(i, j) over the other corners ascending; N = {a, b}, P = {c, d}: (e(a,c), e(a,d), e(b,d)) and
+//   (e(a,c), e(b,d), e(b,c)); the second and third vertex swapped where the normal of the midpoint triangle would point to N.
+// The other five tetrahedra are the images of this one under the permutation of the axes, corner i to corner i: a linear map M
+// takes (v1 - v0) x (v2 - v0) to det(M) M^-T of it and g to M g, so n . g is multiplied by det(M), the permutation's sign.  The
+// same table therefore serves all six, and the odd permutations (tetrahedra 1, 2, 5) swap the second and third vertex once more.
+#define TSDF_TET_COUNTS 0x16696994u
+#define TSDF_TET_ODD 0x26u
+#define TSDF_W_TRIS 2                   // words: the triangle list's length (TSDF_W_OUT: the vertex list's)
+__constant__ uint32_t TSDF_TET_CASES[16] = {0x000000, 0x000c84, 0x0009d4, 0x9d8dc8, 0x000e98, 0xe94ce4, 0x8e4ed4, 0x000edc,
+                                            0x000dec, 0xde4e84, 0xec49e4, 0x0009e8, 0xcd8d98, 0x000d94, 0x0008c4, 0x000000};
+__device__ __forceinline__ constexpr uint32_t TSDF_TET_CORNERS(int t) {
+    return t == 0 ? 0xec8u : t == 1 ? 0xf48u : t == 2 ? 0xed0u : t == 3 ? 0xf90u : t == 4 ? 0xf60u : 0xfa0u;
+}
+
+// a triangle as the device lists it: the host sorts by (cell, order) and turns the three (corner, dir) into indices
+struct TsdfTriRef {
+    unsigned long long cell;   // key of the cell's voxel
+    uint32_t code;             // order = 2 tetrahedron + index | v0 << 4 | v1 << 10 | v2 << 16, v = 8 corner code + dir of the edge
+    uint32_t pad;
+};
+
+// the case of tetrahedron t from the eight signs of the cell (bit c: corner c negative)
+__device__ __forceinline__ uint32_t tsdf_tet_case(int t, uint32_t neg) {
+    const uint32_t tc = TSDF_TET_CORNERS(t);
+    return (neg & 1u) | (((neg >> ((tc >> 3) & 7u)) & 1u) << 1) | (((neg >> ((tc >> 6) & 7u)) & 1u) << 2) | (((neg >> 7) & 1u) << 3);
+}
+
+// One thread per slot.  Seven read-only probes for the neighbours at d = 1..7; the voxel's up to seven sign-changing edges as vertex
+// records, and, when all eight corners are usable, the cell's up to twelve triangles as references.  verts == null: only the two
+// numbers (both lists are written, or neither).
+__global__ __launch_bounds__(256) void tsdf_mesh_kernel(TsdfTable t, uint32_t min_weight, double s, viso_tsdf_mesh_vertex* verts,
+                                                        unsigned long long v_cap, TsdfTriRef* tris, unsigned long long t_cap) {
+    const uint32_t slot = blockIdx.x * 256 + threadIdx.x;   // the grid covers the slots exactly
+    const int lane = threadIdx.x & 63;
+    const unsigned long long key = t.keys[slot];
+    const uint32_t wa = t.weight[slot];
+    const bool take = key != MAP_EMPTY && wa >= min_weight;
+    if (!__ballot(take)) return;   // the whole wave
+    int32_t k[3] = {0, 0, 0};
+    long long sa = 0, sb[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    uint32_t wb[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    uint32_t usable = 0, neg = 0, hit = 0;   // bit d: the neighbour at d is usable / negative / across a sign change from this voxel
+    if (take) {
+        tsdf_unkey(key, k);
+        sa = (long long)t.sum[slot];
+        usable = 1u; neg = sa < 0 ? 1u : 0u;
+#pragma unroll
+        for (int d = 1; d < 8; ++d) {
+            // the last voxel of an axis has no neighbour along it: no key is formed beyond a field
+            if (((d & 1) && k[0] == MAP_BIAS - 1) || ((d & 2) && k[1] == MAP_BIAS - 1) || ((d & 4) && k[2] == MAP_BIAS - 1)) continue;
+            uint32_t nb;
+            if (!voxel_find(t.keys, t.mask, key + ((unsigned long long)(d & 1) << 42) + ((unsigned long long)((d >> 1) & 1) << 21) + (unsigned long long)(d >> 2), &nb)) continue;
+            wb[d] = t.weight[nb];
+            if (wb[d] < min_weight) continue;
+            sb[d] = (long long)t.sum[nb];
+            usable |= 1u << d;
+            if (sb[d] < 0) neg |= 1u << d;
+            if ((sb[d] < 0) != (sa < 0)) hit |= 1u << d;
+        }
+    }
+    const bool cell = usable == 0xffu;
+    uint32_t n_tri = 0;
+    if (cell) {
+#pragma unroll
+        for (int tet = 0; tet < 6; ++tet) n_tri += (TSDF_TET_COUNTS >> (2u * tsdf_tet_case(tet, neg))) & 3u;
+    }
+    const uint32_t mine = (uint32_t)__popc(hit) | (n_tri << 16);          // at most 64 x 7 and 64 x 12: both fit 16 bits
+    const uint32_t incl = viso_wave_scan(mine);
+    const uint32_t total = (uint32_t)__shfl((int)incl, 63);
+    if (!total) return;   // the whole wave
+    unsigned long long vbase = 0, tbase = 0;
+    if (lane == 0) {
+        if (total & 0xffffu) vbase = atomicAdd(t.words + TSDF_W_OUT, (unsigned long long)(total & 0xffffu));
+        if (total >> 16) tbase = atomicAdd(t.words + TSDF_W_TRIS, (unsigned long long)(total >> 16));
+    }
+    vbase = __shfl(vbase, 0);
+    tbase = __shfl(tbase, 0);
+    if (!verts) return;
+    unsigned long long at = vbase + ((incl - mine) & 0xffffu);
+#pragma unroll
+    for (int d = 1; d < 8; ++d) {
+        if (!((hit >> d) & 1u)) continue;
+        if (at < v_cap) {
+            const double da = (double)sa / (double)wa, db = (double)sb[d] / (double)wb[d];
+            const double off = da / (da - db) * 1024.0;
+            viso_tsdf_mesh_vertex v;
+            v.k[0] = k[0]; v.k[1] = k[1]; v.k[2] = k[2];
+            v.dir = d;
+            v.p[0] = (float)(((double)((long long)k[0] * 1024 + 512) + ((d & 1) ? off : 0.0)) * s);
+            v.p[1] = (float)(((double)((long long)k[1] * 1024 + 512) + ((d & 2) ? off : 0.0)) * s);
+            v.p[2] = (float)(((double)((long long)k[2] * 1024 + 512) + ((d & 4) ? off : 0.0)) * s);
+            v.weight = wa < wb[d] ? wa : wb[d];
+            verts[at] = v;
+        }
+        ++at;
+    }
+    if (!cell) return;
+    at = tbase + ((incl - mine) >> 16);
+#pragma unroll
+    for (int tet = 0; tet < 6; ++tet) {
+        const uint32_t tc = TSDF_TET_CORNERS(tet);
+        const uint32_t p = tsdf_tet_case(tet, neg);
+        const uint32_t n = (TSDF_TET_COUNTS >> (2u * p)) & 3u;
+        if (!n) continue;
+        const uint32_t edges = TSDF_TET_CASES[p];
+        for (uint32_t q = 0; q < n; ++q) {
+            if (at < t_cap) {
+                uint32_t v[3];
+#pragma unroll
+                for (int m = 0; m < 3; ++m) {
+                    const uint32_t e = edges >> (12u * q + 4u * m);
+                    const uint32_t ci = (tc >> (3u * (e & 3u))) & 7u, cj = (tc >> (3u * ((e >> 2) & 3u))) & 7u;
+                    v[m] = ci * 8u + (cj ^ ci);           // the owner is the corner of the smaller local index; cj's bits include ci's
+                }
+                const bool odd = (TSDF_TET_ODD >> tet) & 1u;
+                TsdfTriRef r;
+                r.cell = key;
+                r.code = ((uint32_t)(2 * tet) + q) | (v[0] << 4) | ((odd ? v[2] : v[1]) << 10) | ((odd ? v[1] : v[2]) << 16);
+                r.pad = 0u;
+                tris[at] = r;
+            }
+            ++at;
+        }
     }
 }
 
@@ -574,6 +710,127 @@ extern "C" int viso_tsdf_surface_count(viso_tsdf* t, uint32_t min_weight, size_t
 }
 extern "C" int viso_tsdf_surface(viso_tsdf* t, uint32_t min_weight, viso_tsdf_crossing* crossings_out, size_t n_cap, size_t* n) {
     return tsdf_extract<viso_tsdf_crossing>("viso_tsdf_surface", t, min_weight, false, crossings_out, n_cap, n);
+}
+
+// One pass of the mesh extraction: the numbers of vertex records and of triangles, both lists written when `verts` is set
+static int tsdf_mesh_pass(viso_tsdf* t, uint32_t min_weight, viso_tsdf_mesh_vertex* verts, size_t v_cap, TsdfTriRef* tris, size_t t_cap,
+                          unsigned long long* nv, unsigned long long* nt) {
+    hipStream_t s = t->ctx->stream;
+    HIP_TRY(hipMemsetAsync(t->t.words + TSDF_W_OUT, 0, sizeof(unsigned long long), s));
+    HIP_TRY(hipMemsetAsync(t->t.words + TSDF_W_TRIS, 0, sizeof(unsigned long long), s));
+    hipLaunchKernelGGL(tsdf_mesh_kernel, dim3((t->t.mask + 1u) / 256u), dim3(256), 0, s, t->t, min_weight, t->s, verts,
+                       (unsigned long long)v_cap, tris, (unsigned long long)t_cap);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(nv, t->t.words + TSDF_W_OUT, sizeof(*nv), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(nt, t->t.words + TSDF_W_TRIS, sizeof(*nt), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return VISO_OK;
+}
+
+static inline bool vertex_less(const viso_tsdf_mesh_vertex& x, const viso_tsdf_mesh_vertex& y) {
+    const unsigned long long a = host_key(x.k), b = host_key(y.k);
+    return a != b ? a < b : x.dir < y.dir;
+}
+
+// The map is entered and locked.  Both lists from the device, sorted; the vertices no triangle refers to dropped; the references
+// turned into indices.
+static int tsdf_mesh_lists(const char* where, viso_tsdf* t, uint32_t min_weight, std::vector<viso_tsdf_mesh_vertex>& verts,
+                           std::vector<viso_tsdf_triangle>& tris) {
+    verts.clear(); tris.clear();
+    unsigned long long nv = 0, nt = 0;
+    int r;
+    if ((r = tsdf_mesh_pass(t, min_weight, nullptr, 0, nullptr, 0, &nv, &nt)) < 0) return r;
+    if (!nt) return VISO_OK;   // no triangle: no vertex is referred to
+    std::vector<viso_tsdf_mesh_vertex> all((size_t)nv);
+    std::vector<TsdfTriRef> refs((size_t)nt);
+    viso_tsdf_mesh_vertex* dv = nullptr;
+    TsdfTriRef* dt = nullptr;
+    const size_t bv = (size_t)nv * sizeof(viso_tsdf_mesh_vertex), bt = (size_t)nt * sizeof(TsdfTriRef);
+    if (hipMalloc((void**)&dv, bv) != hipSuccess || hipMalloc((void**)&dt, bt) != hipSuccess) {
+        (void)hipGetLastError();
+        if (dv) (void)hipFree(dv);
+        viso_set_error("%s: cannot allocate %zu bytes for the lists", where, bv + bt);
+        return VISO_ERR_NOMEM;
+    }
+    unsigned long long nv2 = 0, nt2 = 0;
+    r = tsdf_mesh_pass(t, min_weight, dv, (size_t)nv, dt, (size_t)nt, &nv2, &nt2);
+    hipError_t e = hipSuccess;
+    if (r >= 0) e = hipMemcpy(all.data(), dv, bv, hipMemcpyDeviceToHost);
+    if (r >= 0 && e == hipSuccess) e = hipMemcpy(refs.data(), dt, bt, hipMemcpyDeviceToHost);
+    (void)hipFree(dv);
+    (void)hipFree(dt);
+    if (r < 0) return r;
+    HIP_TRY(e);
+    if (nv2 != nv || nt2 != nt) { viso_set_error("%s: the table changed between the two passes", where); return VISO_ERR_HIP; }   // (the map's lock rules it out)
+    std::sort(all.begin(), all.end(), vertex_less);
+    std::sort(refs.begin(), refs.end(), [](const TsdfTriRef& x, const TsdfTriRef& y) { return x.cell != y.cell ? x.cell < y.cell : (x.code & 15u) < (y.code & 15u); });
+    // every reference to the position of its vertex in the sorted list
+    std::vector<unsigned long long> at((size_t)nt * 3);
+    std::vector<unsigned char> used((size_t)nv, 0);
+    for (size_t i = 0; i < (size_t)nt; ++i) {
+        for (int m = 0; m < 3; ++m) {
+            const uint32_t v = (refs[i].code >> (4 + 6 * m)) & 63u, c = v >> 3;
+            const unsigned long long key = refs[i].cell + ((unsigned long long)(c & 1u) << 42) + ((unsigned long long)((c >> 1) & 1u) << 21) + (unsigned long long)(c >> 2);
+            const int dir = (int)(v & 7u);
+            size_t lo = 0, hi = (size_t)nv;
+            while (lo < hi) {
+                const size_t mid = lo + (hi - lo) / 2;
+                const unsigned long long km = host_key(all[mid].k);
+                if (km < key || (km == key && all[mid].dir < dir)) lo = mid + 1; else hi = mid;
+            }
+            if (lo == (size_t)nv || host_key(all[lo].k) != key || all[lo].dir != dir) {
+                viso_set_error("%s: a triangle refers to a vertex that is not in the list", where);   // (the definition rules it out)
+                return VISO_ERR_HIP;
+            }
+            at[i * 3 + m] = lo;
+            used[lo] = 1;
+        }
+    }
+    std::vector<unsigned long long> index((size_t)nv);
+    unsigned long long kept = 0;
+    for (size_t i = 0; i < (size_t)nv; ++i) { index[i] = kept; kept += used[i]; }
+    if (kept > 0xffffffffull) { viso_set_error("%s: %llu vertices are beyond the 32-bit indices of a triangle", where, kept); return VISO_ERR_UNSUPPORTED; }
+    verts.reserve((size_t)kept);
+    for (size_t i = 0; i < (size_t)nv; ++i) if (used[i]) verts.push_back(all[i]);
+    tris.resize((size_t)nt);
+    for (size_t i = 0; i < (size_t)nt; ++i) for (int m = 0; m < 3; ++m) tris[i].v[m] = (uint32_t)index[(size_t)at[i * 3 + m]];
+    return VISO_OK;
+}
+
+static int tsdf_mesh_extract(const char* where, viso_tsdf* t, uint32_t min_weight, bool count_only, viso_tsdf_mesh_vertex* vertices_out,
+                             size_t nv_cap, viso_tsdf_triangle* triangles_out, size_t nt_cap, size_t* n_vertices, size_t* n_triangles) {
+    if (!tsdf_known(t)) { viso_set_error("%s: not a live TSDF handle", where); return VISO_ERR_ARG; }
+    if (!n_vertices || !n_triangles || min_weight < 1 || (!count_only && ((nv_cap && !vertices_out) || (nt_cap && !triangles_out)))) {
+        viso_set_error("%s: bad argument (min_weight >= 1, non-null outputs)", where);
+        return VISO_ERR_ARG;
+    }
+    int r;
+    if ((r = tsdf_enter(where, t)) < 0) return r;
+    std::vector<viso_tsdf_mesh_vertex> verts;
+    std::vector<viso_tsdf_triangle> tris;
+    {
+        std::lock_guard<std::mutex> lk(t->mu);
+        if (t->overflowed) return tsdf_refuse_overflowed(where);
+        if ((r = tsdf_mesh_lists(where, t, min_weight, verts, tris)) < 0) return r;
+    }
+    *n_vertices = verts.size();
+    *n_triangles = tris.size();
+    if (count_only) return VISO_OK;
+    if (verts.size() > nv_cap || tris.size() > nt_cap) {
+        viso_set_error("%s: %zu vertices and %zu triangles do not fit the %zu and %zu given", where, verts.size(), tris.size(), nv_cap, nt_cap);
+        return VISO_ERR_ARG;
+    }
+    std::copy(verts.begin(), verts.end(), vertices_out);
+    std::copy(tris.begin(), tris.end(), triangles_out);
+    return VISO_OK;
+}
+
+extern "C" int viso_tsdf_mesh_count(viso_tsdf* t, uint32_t min_weight, size_t* n_vertices, size_t* n_triangles) {
+    return tsdf_mesh_extract("viso_tsdf_mesh_count", t, min_weight, true, nullptr, 0, nullptr, 0, n_vertices, n_triangles);
+}
+extern "C" int viso_tsdf_mesh(viso_tsdf* t, uint32_t min_weight, viso_tsdf_mesh_vertex* vertices_out, size_t nv_cap,
+                              viso_tsdf_triangle* triangles_out, size_t nt_cap, size_t* n_vertices, size_t* n_triangles) {
+    return tsdf_mesh_extract("viso_tsdf_mesh", t, min_weight, false, vertices_out, nv_cap, triangles_out, nt_cap, n_vertices, n_triangles);
 }
 
 extern "C" int viso_tsdf_stats(viso_tsdf* t, viso_tsdf_counters* out) {

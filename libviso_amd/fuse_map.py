@@ -1,5 +1,5 @@
 """python -m libviso_amd.fuse_map DISPARITY_DIR POSES.txt CALIB.txt OUT.ply [--voxel V --min-count N --min-disp PX --frames B E]
-                                 [--surface [--trunc T --min-weight N]]
+                                 [--surface | --mesh [--trunc T --min-weight N]]
 
 Fuses the maps a KITTI runner wrote with --disparity DIR and the poses of its pose file into one voxel map on the device
 (libviso_amd.VoxelMap; include/viso_hip.h, "voxel map") and writes the occupied voxels as a binary PLY point cloud: x, y, z the
@@ -13,6 +13,9 @@ float32 centroid of each voxel, count the number of points fused into it.
                  averaged signed distance changes sign between neighbouring voxels: x, y, z the float32 crossing point, weight the
                  smaller of the two voxels' weights.  --trunc T: the truncation band in voxels (3); --min-weight N: only voxels
                  with at least this many updates (1).  --capacity-log2 then defaults to 26.
+  --mesh         fuse into a TSDF map as --surface does, with its options, and write the surface as a triangle mesh by marching
+                 tetrahedra (include/viso_hip.h, "TSDF mesh"): per vertex x, y, z and weight as above, per face three vertex
+                 indices, the normals towards the cameras.  Not together with --surface.
 
 Both runners write byte-identical directories and pose files for every rank count and chunk size, so the PLY is identical too."""
 import argparse
@@ -138,10 +141,12 @@ def main(argv=None):
     ap.add_argument("--min-count", type=int, default=1, help="only voxels with at least this many points (1)")
     ap.add_argument("--min-disp", type=float, default=1.0, help="smallest disparity used, in pixels (1.0)")
     ap.add_argument("--frames", type=int, nargs=2, metavar=("B", "E"), help="only maps B .. E-1 of the directory")
-    ap.add_argument("--capacity-log2", type=int, default=None, help="log2 of the table's slots (24; 26 with --surface)")
-    ap.add_argument("--surface", action="store_true", help="write the surface crossings of a TSDF map in place of the centroids")
-    ap.add_argument("--trunc", type=int, default=3, help="with --surface: the truncation band in voxels (3)")
-    ap.add_argument("--min-weight", type=int, default=1, help="with --surface: only voxels with at least this many updates (1)")
+    ap.add_argument("--capacity-log2", type=int, default=None, help="log2 of the table's slots (24; 26 with --surface or --mesh)")
+    mode = ap.add_mutually_exclusive_group()
+    mode.add_argument("--surface", action="store_true", help="write the surface crossings of a TSDF map in place of the centroids")
+    mode.add_argument("--mesh", action="store_true", help="write the triangle mesh of a TSDF map in place of the centroids")
+    ap.add_argument("--trunc", type=int, default=3, help="with --surface or --mesh: the truncation band in voxels (3)")
+    ap.add_argument("--min-weight", type=int, default=1, help="with --surface or --mesh: only voxels with at least this many updates (1)")
     a = ap.parse_args(argv)
     import libviso_amd
     from libviso_amd.abi import Param
@@ -153,15 +158,24 @@ def main(argv=None):
         sys.exit(f"fuse_map: --frames {b} {e} is outside the {len(names)} maps")
     f, cu, cv, base = read_calib(a.calib)
     prm = Param.default(base=base, f=f, cu=cu, cv=cv)
-    if a.surface:
+    if a.surface or a.mesh:
         tsdf = libviso_amd.TsdfMap(None, voxel=a.voxel, trunc_voxels=a.trunc, min_disp16=max(1, int(round(a.min_disp * 16))),
                                    capacity_log2=26 if a.capacity_log2 is None else a.capacity_log2)
         try:
             for i in range(b, e):
                 tsdf.fuse(read_disparity_png(os.path.join(a.disparity_dir, names[i])), prm, pose=poses[i])
-            crossings, st = tsdf.surface(a.min_weight), tsdf.stats()
+            st = tsdf.stats()
+            if a.mesh:
+                vertices, triangles = tsdf.mesh(a.min_weight)
+            else:
+                crossings = tsdf.surface(a.min_weight)
         finally:
             tsdf.close()
+        if a.mesh:
+            libviso_amd.write_mesh_ply(a.out, vertices, triangles)
+            print(f"fuse_map: {e - b} maps, {st['n_points']} points, {st['n_updates']} updates ({st['n_out_of_range']} samples out of range), "
+                  f"{st['n_occupied']} voxels, {len(vertices)} vertices and {len(triangles)} triangles at weight >= {a.min_weight} -> {a.out}")
+            return 0
         libviso_amd.write_surface_ply(a.out, crossings, a.voxel)
         print(f"fuse_map: {e - b} maps, {st['n_points']} points, {st['n_updates']} updates ({st['n_out_of_range']} samples out of range), "
               f"{st['n_occupied']} voxels, {len(crossings)} crossings at weight >= {a.min_weight} -> {a.out}")

@@ -10,9 +10,11 @@ repetitions):
   fuse_map     Batch.fuse_disparities of the same maps into a cleared voxel map: the comparison;
   entries      TsdfMap.entries(): two compaction passes, the copy, the sort on the host;
   surface      TsdfMap.surface(): two passes of three probes a voxel, the copy, the sort on the host;
+  mesh         TsdfMap.mesh() over the same table: the extraction twice (count, list), each two passes of seven probes a voxel, the
+               copies, the two sorts and the resolution of the triangles' references on the host;
   clear        viso_tsdf_clear.
 n_updates / n_points from viso_tsdf_stats is the number of voxels a pixel's band touches.  --kernel-only runs clear + fuse_tsdf
---reps times and both extractions once: the run to put under `rocprofv3 --kernel-trace --stats` for the kernels' own times.  The
+--reps times and the extractions once: the run to put under `rocprofv3 --kernel-trace --stats` for the kernels' own times.  The
 count the result is held against (not a measurement) is printed with it."""
 import argparse
 import json
@@ -82,16 +84,17 @@ def main():
         for _ in range(a.reps):
             tsdf.clear()
             ms.append(clock(lambda: b.fuse_tsdf(tsdf, poses)))
-        res = {"frames": nf, "fuse_tsdf_ms": ms, "voxels": int(len(tsdf.entries())), "crossings": int(len(tsdf.surface()))}
+        res = {"frames": nf, "fuse_tsdf_ms": ms, "voxels": int(len(tsdf.entries())), "crossings": int(len(tsdf.surface())),
+               "triangles": int(len(tsdf.mesh()[1]))}
         print(json.dumps(res))
         tsdf.close(); b.close(); ctx.close()
         return
 
     vmap = libviso_amd.VoxelMap(ctx, capacity_log2=26)
     for _ in range(2):   # warm-up
-        tsdf.clear(); b.fuse_tsdf(tsdf, poses); tsdf.entries(); tsdf.surface()
+        tsdf.clear(); b.fuse_tsdf(tsdf, poses); tsdf.entries(); tsdf.surface(); tsdf.mesh()
         vmap.clear(); b.fuse_disparities(vmap, poses)
-    legs = {k: [] for k in ("fuse_tsdf", "fuse_map", "entries", "surface", "clear")}
+    legs = {k: [] for k in ("fuse_tsdf", "fuse_map", "entries", "surface", "mesh", "clear")}
     for _ in range(a.reps):   # alternating
         legs["clear"].append(clock(tsdf.clear))
         legs["fuse_tsdf"].append(clock(lambda: b.fuse_tsdf(tsdf, poses)))
@@ -99,10 +102,12 @@ def main():
         legs["fuse_map"].append(clock(lambda: b.fuse_disparities(vmap, poses)))
         legs["entries"].append(clock(tsdf.entries))
         legs["surface"].append(clock(tsdf.surface))
+        legs["mesh"].append(clock(tsdf.mesh))
     st, n_vox, n_cross = tsdf.stats(), len(tsdf.entries()), len(tsdf.surface())
+    n_vert, n_tri = (len(x) for x in tsdf.mesh())
     res = {"frames": nf, "shape": [int(rows), int(cols)], "params": "voxel 0.2, T 3, min_disp16 16", "capacity_log2": log2, "reps": a.reps,
            "ms_median": {k: float(np.median(v)) for k, v in legs.items()}, "ms_min": {k: float(np.min(v)) for k, v in legs.items()},
-           "stats": st, "voxels": int(n_vox), "crossings": int(n_cross), "updates_per_point": st["n_updates"] / max(1, st["n_points"]),
+           "stats": st, "voxels": int(n_vox), "crossings": int(n_cross), "vertices": int(n_vert), "triangles": int(n_tri), "updates_per_point": st["n_updates"] / max(1, st["n_points"]),
            "map_stats": vmap.stats()}
     res["count_bytes"], res["count_ms"] = count_ms(nf, rows, cols)
     print(json.dumps(res))
