@@ -889,82 +889,78 @@ class Context:
             pass
 
 
-class VoxelMap:
-    """viso_map: a persistent voxel map on the device that dense disparity maps and their poses are fused into (opt-in, not in the
-    reference; the definition of include/viso_hip.h).  ctx: a Context, or None for the default one.  With a trajectory:
-
-        poses, valid = hostmath.chain_poses(tr, ok)      # poses[k + 1] places frame valid[k] in frame 0's coordinates
-        vmap = VoxelMap(ctx, voxel=0.2)
-        for k, t in enumerate(valid):
-            batch.fuse_disparities(vmap, poses[k + 1][None], t0=t, t1=t + 1)
-        write_map_ply("scene.ply", vmap.entries(min_count=2), vmap.voxel)
-    """
+class _TableMap:
+    """What VoxelMap and TsdfMap share: a handle of one of the two kinds of hash tables of voxels (csrc/voxel_host.h).  A subclass
+    sets _prefix (the C functions are _prefix + name), _Params and _params (the parameter struct and its factory), _ENTRY_DTYPE and
+    _Counters."""
 
     def __init__(self, ctx=None, params=None, **kw):
+        name = type(self).__name__
         self.L = load()
-        if isinstance(params, MapParams):
+        if isinstance(params, self._Params):
             if kw:
-                raise TypeError("VoxelMap: keyword fields cannot be combined with a MapParams")
+                raise TypeError(f"{name}: keyword fields cannot be combined with a {self._Params.__name__}")
         else:
-            params = map_params(**dict(params or {}, **kw))
-        self.ctx, self.voxel = ctx, float(params.voxel)
+            params = type(self)._params(**dict(params or {}, **kw))
+        self.ctx, self._p, self.voxel = ctx, params, float(params.voxel)
         h = C.c_void_p()
-        r = self.L.viso_map_create(ctx.h if ctx is not None else None, C.byref(params), C.byref(h))
+        r = self._c("create")(ctx.h if ctx is not None else None, C.byref(params), C.byref(h))
         self.h = h.value if r == 1 else None
         if r != 1:
-            _err("viso_map_create", r)
+            _err(self._prefix + "create", r)
         _live.add(self)
+
+    def _c(self, name):
+        return getattr(self.L, self._prefix + name)
 
     def _chk(self, where, r):
         if r != 1:
             _err(where, r)
 
     def fuse(self, d16, param, pose=None):
-        """viso_map_fuse: one host int16 map with the calibration of param (f, cu, cv, base) and an optional 4 x 4 pose."""
+        """viso_map_fuse / viso_tsdf_fuse: one host int16 map with the calibration of param (f, cu, cv, base) and an optional 4 x 4
+        pose."""
+        where = type(self).__name__ + ".fuse"
         d16 = np.ascontiguousarray(d16)
         if d16.ndim != 2 or d16.dtype != np.int16:
-            raise ValueError("VoxelMap.fuse: the map must be a 2-D int16 array")
+            raise ValueError(f"{where}: the map must be a 2-D int16 array")
         if pose is not None and np.shape(pose) != (4, 4):
-            raise ValueError("VoxelMap.fuse: the pose must be a 4 x 4 matrix")
-        T, Tp = _pose_arg("VoxelMap.fuse", pose)
-        self._chk("viso_map_fuse", self.L.viso_map_fuse(self.h, ptr(d16, C.c_int16), d16.shape[0], d16.shape[1], C.byref(param), Tp))
+            raise ValueError(f"{where}: the pose must be a 4 x 4 matrix")
+        T, Tp = _pose_arg(where, pose)
+        self._chk(self._prefix + "fuse", self._c("fuse")(self.h, ptr(d16, C.c_int16), d16.shape[0], d16.shape[1], C.byref(param), Tp))
 
     def add_entries(self, entries):
-        """viso_map_add_entries: the entries of another map with the same voxel (or of a saved one) added to this one."""
-        entries = np.ascontiguousarray(entries, dtype=MAP_ENTRY_DTYPE)
-        self._chk("viso_map_add_entries", self.L.viso_map_add_entries(self.h, entries.ctypes.data, len(entries)))
+        """viso_map_add_entries / viso_tsdf_add_entries: the entries of another map with the same voxel (a TSDF map: and truncation),
+        or of a saved one, added to this one."""
+        entries = np.ascontiguousarray(entries, dtype=self._ENTRY_DTYPE)
+        self._chk(self._prefix + "add_entries", self._c("add_entries")(self.h, entries.ctypes.data, len(entries)))
 
-    def count(self, min_count=1):
+    def _count(self, count_name, threshold):
         n = C.c_size_t()
-        self._chk("viso_map_count", self.L.viso_map_count(self.h, int(min_count), C.byref(n)))
-        return n.value
+        self._chk(self._prefix + count_name, self._c(count_name)(self.h, int(threshold), C.byref(n)))
+        return n
 
-    def entries(self, min_count=1):
-        """viso_map_get: the voxels with at least min_count points as a MAP_ENTRY_DTYPE array (k, count, sum), sorted by key."""
-        out = np.zeros(self.count(min_count), MAP_ENTRY_DTYPE)
-        n = C.c_size_t()
-        self._chk("viso_map_get", self.L.viso_map_get(self.h, int(min_count), out.ctypes.data, len(out), C.byref(n)))
+    def _list(self, count_name, get_name, dtype, threshold):
+        n = self._count(count_name, threshold)
+        out = np.zeros(n.value, dtype)
+        self._chk(self._prefix + get_name, self._c(get_name)(self.h, int(threshold), out.ctypes.data, len(out), C.byref(n)))
         return out[:n.value]
 
-    def centroids(self, min_count=1):
-        """float32 [n][3]: the centroids of entries(min_count), in their order."""
-        return map_entry_centroids(self.entries(min_count), self.voxel)
-
     def stats(self):
-        """viso_map_stats as a dict: n_points, n_inserts, n_out_of_range, n_dropped, n_occupied."""
-        c = MapCounters()
-        self._chk("viso_map_stats", self.L.viso_map_stats(self.h, C.byref(c)))
-        return {name: int(getattr(c, name)) for name, _ in MapCounters._fields_}
+        """viso_map_stats / viso_tsdf_stats as a dict of the counters' fields."""
+        c = self._Counters()
+        self._chk(self._prefix + "stats", self._c("stats")(self.h, C.byref(c)))
+        return {name: int(getattr(c, name)) for name, _ in self._Counters._fields_}
 
     def clear(self):
-        self._chk("viso_map_clear", self.L.viso_map_clear(self.h))
+        self._chk(self._prefix + "clear", self._c("clear")(self.h))
 
     def close(self):
         if self.h:
             h, self.h = self.h, None
-            r = self.L.viso_map_destroy(h)
+            r = self._c("destroy")(h)
             if r != 1:
-                _err("viso_map_destroy", r)
+                _err(self._prefix + "destroy", r)
 
     def __del__(self, _finalizing=sys.is_finalizing):   # bound at definition: module globals are None late in shutdown
         if _finalizing():   # the atexit hook has closed everything that was still open
@@ -975,7 +971,31 @@ class VoxelMap:
             pass
 
 
-class TsdfMap:
+class VoxelMap(_TableMap):
+    """viso_map: a persistent voxel map on the device that dense disparity maps and their poses are fused into (opt-in, not in the
+    reference; the definition of include/viso_hip.h).  ctx: a Context, or None for the default one.  With a trajectory:
+
+        poses, valid = hostmath.chain_poses(tr, ok)      # poses[k + 1] places frame valid[k] in frame 0's coordinates
+        vmap = VoxelMap(ctx, voxel=0.2)
+        for k, t in enumerate(valid):
+            batch.fuse_disparities(vmap, poses[k + 1][None], t0=t, t1=t + 1)
+        write_map_ply("scene.ply", vmap.entries(min_count=2), vmap.voxel)
+    """
+    _prefix, _Params, _params, _ENTRY_DTYPE, _Counters = "viso_map_", MapParams, map_params, MAP_ENTRY_DTYPE, MapCounters
+
+    def count(self, min_count=1):
+        return self._count("count", min_count).value
+
+    def entries(self, min_count=1):
+        """viso_map_get: the voxels with at least min_count points as a MAP_ENTRY_DTYPE array (k, count, sum), sorted by key."""
+        return self._list("count", "get", MAP_ENTRY_DTYPE, min_count)
+
+    def centroids(self, min_count=1):
+        """float32 [n][3]: the centroids of entries(min_count), in their order."""
+        return map_entry_centroids(self.entries(min_count), self.voxel)
+
+
+class TsdfMap(_TableMap):
     """viso_tsdf: a persistent map of truncated signed distances on the device that dense disparity maps and their poses are fused
     into, read back as voxels or as the points where the averaged distance changes sign (opt-in, not in the reference; the
     definition of include/viso_hip.h).  ctx: a Context, or None for the default one.  With a trajectory:
@@ -987,56 +1007,20 @@ class TsdfMap:
         write_surface_ply("surface.ply", tsdf.surface(min_weight=2), tsdf.voxel)
         write_mesh_ply("mesh.ply", *tsdf.mesh(min_weight=2))
     """
+    _prefix, _Params, _params, _ENTRY_DTYPE, _Counters = "viso_tsdf_", TsdfParams, tsdf_params, TSDF_ENTRY_DTYPE, TsdfCounters
 
     def __init__(self, ctx=None, params=None, **kw):
-        self.L = load()
-        if isinstance(params, TsdfParams):
-            if kw:
-                raise TypeError("TsdfMap: keyword fields cannot be combined with a TsdfParams")
-        else:
-            params = tsdf_params(**dict(params or {}, **kw))
-        self.ctx, self.voxel, self.trunc_voxels = ctx, float(params.voxel), int(params.trunc_voxels)
-        h = C.c_void_p()
-        r = self.L.viso_tsdf_create(ctx.h if ctx is not None else None, C.byref(params), C.byref(h))
-        self.h = h.value if r == 1 else None
-        if r != 1:
-            _err("viso_tsdf_create", r)
-        _live.add(self)
-
-    def _chk(self, where, r):
-        if r != 1:
-            _err(where, r)
-
-    def fuse(self, d16, param, pose=None):
-        """viso_tsdf_fuse: one host int16 map with the calibration of param (f, cu, cv, base) and an optional 4 x 4 pose."""
-        d16 = np.ascontiguousarray(d16)
-        if d16.ndim != 2 or d16.dtype != np.int16:
-            raise ValueError("TsdfMap.fuse: the map must be a 2-D int16 array")
-        if pose is not None and np.shape(pose) != (4, 4):
-            raise ValueError("TsdfMap.fuse: the pose must be a 4 x 4 matrix")
-        T, Tp = _pose_arg("TsdfMap.fuse", pose)
-        self._chk("viso_tsdf_fuse", self.L.viso_tsdf_fuse(self.h, ptr(d16, C.c_int16), d16.shape[0], d16.shape[1], C.byref(param), Tp))
-
-    def add_entries(self, entries):
-        """viso_tsdf_add_entries: the entries of another map with the same voxel and truncation (or of a saved one) added to this one."""
-        entries = np.ascontiguousarray(entries, dtype=TSDF_ENTRY_DTYPE)
-        self._chk("viso_tsdf_add_entries", self.L.viso_tsdf_add_entries(self.h, entries.ctypes.data, len(entries)))
-
-    def _list(self, count_name, get_name, dtype, min_weight):
-        n = C.c_size_t()
-        self._chk(count_name, getattr(self.L, count_name)(self.h, int(min_weight), C.byref(n)))
-        out = np.zeros(n.value, dtype)
-        self._chk(get_name, getattr(self.L, get_name)(self.h, int(min_weight), out.ctypes.data, len(out), C.byref(n)))
-        return out[:n.value]
+        super().__init__(ctx, params, **kw)
+        self.trunc_voxels = int(self._p.trunc_voxels)
 
     def entries(self, min_weight=1):
         """viso_tsdf_get: the voxels with at least min_weight updates as a TSDF_ENTRY_DTYPE array (k, weight, sum), sorted by key."""
-        return self._list("viso_tsdf_count", "viso_tsdf_get", TSDF_ENTRY_DTYPE, min_weight)
+        return self._list("count", "get", TSDF_ENTRY_DTYPE, min_weight)
 
     def surface(self, min_weight=1):
         """viso_tsdf_surface: the sign changes between neighbouring voxels of at least min_weight updates as a TSDF_CROSSING_DTYPE
         array (k, axis, wa, wb, sa, sb), sorted by (key, axis)."""
-        return self._list("viso_tsdf_surface_count", "viso_tsdf_surface", TSDF_CROSSING_DTYPE, min_weight)
+        return self._list("surface_count", "surface", TSDF_CROSSING_DTYPE, min_weight)
 
     def surface_points(self, min_weight=1):
         """float32 [n][3]: the crossing points of surface(min_weight), in their order."""
@@ -1052,30 +1036,6 @@ class TsdfMap:
         self._chk("viso_tsdf_mesh", self.L.viso_tsdf_mesh(self.h, int(min_weight), v.ctypes.data, len(v), tri.ctypes.data, len(tri),
                                                           C.byref(nv), C.byref(nt)))
         return v[:nv.value], tri[:nt.value]
-
-    def stats(self):
-        """viso_tsdf_stats as a dict: n_points, n_updates, n_out_of_range, n_dropped, n_occupied."""
-        c = TsdfCounters()
-        self._chk("viso_tsdf_stats", self.L.viso_tsdf_stats(self.h, C.byref(c)))
-        return {name: int(getattr(c, name)) for name, _ in TsdfCounters._fields_}
-
-    def clear(self):
-        self._chk("viso_tsdf_clear", self.L.viso_tsdf_clear(self.h))
-
-    def close(self):
-        if self.h:
-            h, self.h = self.h, None
-            r = self.L.viso_tsdf_destroy(h)
-            if r != 1:
-                _err("viso_tsdf_destroy", r)
-
-    def __del__(self, _finalizing=sys.is_finalizing):   # bound at definition: module globals are None late in shutdown
-        if _finalizing():   # the atexit hook has closed everything that was still open
-            return
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class Batch:

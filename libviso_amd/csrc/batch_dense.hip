@@ -163,17 +163,22 @@ extern "C" int viso_batch_get_disparity_points(viso_batch* b, int t, const doubl
     return VISO_OK;
 }
 
-// The resident maps of frames t0 .. t1-1 into a voxel map of the same context (voxelmap.hip), with the batch's calibration: on the
-// context's stream, behind the run that computed them, with no host copy of the maps.
-extern "C" int viso_batch_fuse_disparities(viso_batch* b, viso_map* m, int t0, int t1, const double* poses) {
-    const char* where = "viso_batch_fuse_disparities";
-    if (dead(b) || !m || t0 < 0 || t1 > b->nf || t0 >= t1 || !poses) {
+// What viso_batch_fuse_disparities and viso_batch_fuse_tsdf check before they hand over (`map`: the handle, only compared with null).
+static int fuse_prelude(const char* where, viso_batch* b, const void* map, int t0, int t1, const double* poses) {
+    if (dead(b) || !map || t0 < 0 || t1 > b->nf || t0 >= t1 || !poses) {
         viso_set_error("%s: bad argument (live handles, 0 <= t0 < t1 <= n_frames, poses [t1 - t0][16])", where);
         return VISO_ERR_ARG;
     }
     if (!b->params_set) { viso_set_error("%s: parameters not set (the calibration comes from viso_batch_set_params)", where); return VISO_ERR_ARG; }
     VISO_TRY(dense_ready(b, where));
-    VISO_TRY(enter(b));
+    return enter(b);
+}
+
+// The resident maps of frames t0 .. t1-1 into a voxel map of the same context (voxelmap.hip), with the batch's calibration: on the
+// context's stream, behind the run that computed them, with no host copy of the maps.
+extern "C" int viso_batch_fuse_disparities(viso_batch* b, viso_map* m, int t0, int t1, const double* poses) {
+    const char* where = "viso_batch_fuse_disparities";
+    VISO_TRY(fuse_prelude(where, b, m, t0, t1, poses));
     const BatchDense& D = b->dense;
     const size_t per = (size_t)D.rows * D.cols;
     return map_fuse_resident(where, m, b->ctx, D.disp + (size_t)t0 * per, per, D.rows, D.cols, t1 - t0, b->sp.f, b->sp.cu, b->sp.cv, b->sp.base, poses);
@@ -182,13 +187,7 @@ extern "C" int viso_batch_fuse_disparities(viso_batch* b, viso_map* m, int t0, i
 // The same into a TSDF map of the same context (tsdf.hip).
 extern "C" int viso_batch_fuse_tsdf(viso_batch* b, viso_tsdf* t, int t0, int t1, const double* poses) {
     const char* where = "viso_batch_fuse_tsdf";
-    if (dead(b) || !t || t0 < 0 || t1 > b->nf || t0 >= t1 || !poses) {
-        viso_set_error("%s: bad argument (live handles, 0 <= t0 < t1 <= n_frames, poses [t1 - t0][16])", where);
-        return VISO_ERR_ARG;
-    }
-    if (!b->params_set) { viso_set_error("%s: parameters not set (the calibration comes from viso_batch_set_params)", where); return VISO_ERR_ARG; }
-    VISO_TRY(dense_ready(b, where));
-    VISO_TRY(enter(b));
+    VISO_TRY(fuse_prelude(where, b, t, t0, t1, poses));
     const BatchDense& D = b->dense;
     const size_t per = (size_t)D.rows * D.cols;
     return tsdf_fuse_resident(where, t, b->ctx, D.disp + (size_t)t0 * per, per, D.rows, D.cols, t1 - t0, b->sp.f, b->sp.cu, b->sp.cv, b->sp.base, poses);

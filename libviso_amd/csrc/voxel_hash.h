@@ -1,7 +1,8 @@
-// voxel_hash.h — the key, the hash and the probes of the hash tables of voxels (voxelmap.hip, tsdf.hip; include/viso_hip.h,
-// "voxel map" step 4 and "Full table").  Device only.  A table's keys are [mask + 1] u64, all ones = empty; a key is claimed with
-// one 64-bit compare-and-swap.  Every probe loop visits each slot at most once and advances strictly: a full table is a wrong count,
-// never a hang.
+// voxel_hash.h — the device side of the shared table layer of the hash tables of voxels (voxelmap.hip, tsdf.hip; the host side is
+// voxel_host.h; include/viso_hip.h, "voxel map" step 4 and "Full table").  A table's keys are [mask + 1] u64, all
+// ones = empty; a key is claimed with one 64-bit compare-and-swap.  Every probe loop visits each slot at most once and advances
+// strictly: a full table is a wrong count, never a hang.  Beside the keys every table has 256 sets of counters on cache lines of
+// their own (a workgroup adds to set blockIdx & 255, one atomic per wave and counter; summed on the host) and a few single words.
 #ifndef VISO_VOXEL_HASH_H_
 #define VISO_VOXEL_HASH_H_
 #include "common.h"
@@ -10,16 +11,51 @@
 #define MAP_BIAS (1 << 20)
 #define MAP_RANGE 1073741824.0          // 2^30: |g| at and beyond it is out of range
 
+#define VOXEL_STAT_SETS 256
+#define VOXEL_STAT_WORDS 16             // 128 bytes a set
+#define VOXEL_ST_POINTS 0
+#define VOXEL_ST_UPDATES 1              // the voxel map's inserts, the TSDF map's updates
+#define VOXEL_ST_OOR 2
+#define VOXEL_ST_OCC 3
+#define VOXEL_W_OUT 0                   // words: an extraction's list length
+#define VOXEL_W_DROPPED 1               //        points / updates that found no slot
+#define VOXEL_W_TRIS 2                  //        the mesh's triangle list length (VOXEL_W_OUT: its vertex list's)
+#define VOXEL_MAX_PIXELS 0x7fffffffll
+#define VOXEL_GROUP 16384               // frames along a grid's y
+
+// the head of every table; a table embeds it as its first member, next to its payload arrays
+struct VoxelTable {
+    unsigned long long* keys;
+    unsigned long long* stats;   // [VOXEL_STAT_SETS][VOXEL_STAT_WORDS]
+    unsigned long long* words;   // VOXEL_W_*, behind the stats
+    uint32_t mask;               // slots - 1
+};
+
+// what every fuse kernel takes: the maps, the poses and the calibration
+struct VoxelFuseArgs {
+    const int16_t* disp; size_t mfs;   // frame f's map at disp + f * mfs
+    const double* poses;               // [frames][12] on the device, or null: no transform
+    int rows, cols, min_disp16, _pad;
+    double f, cu, cv, base;
+};
+
+__host__ __device__ __forceinline__ unsigned long long voxel_key(int kx, int ky, int kz) {
+    return ((unsigned long long)(uint32_t)(kx + MAP_BIAS) << 42) | ((unsigned long long)(uint32_t)(ky + MAP_BIAS) << 21) |
+           (unsigned long long)(uint32_t)(kz + MAP_BIAS);
+}
+__host__ __device__ __forceinline__ void voxel_unkey(unsigned long long key, int32_t* k) {
+    for (int i = 0; i < 3; ++i) k[i] = (int)((key >> (21 * (2 - i))) & 0x1fffffu) - MAP_BIAS;
+}
+// the key of the voxel at the corner d = dx + 2 dy + 4 dz of key's cell (no field of key is at its last value along a set bit of d)
+__host__ __device__ __forceinline__ unsigned long long voxel_neighbour(unsigned long long key, uint32_t d) {
+    return key + voxel_key((int)(d & 1u) - MAP_BIAS, (int)((d >> 1) & 1u) - MAP_BIAS, (int)(d >> 2) - MAP_BIAS);
+}
+
 __device__ __forceinline__ uint32_t map_hash(unsigned long long k) {   // the finaliser of splitmix64
     k ^= k >> 30; k *= 0xbf58476d1ce4e5b9ull;
     k ^= k >> 27; k *= 0x94d049bb133111ebull;
     k ^= k >> 31;
     return (uint32_t)k;
-}
-
-__device__ __forceinline__ unsigned long long map_key(int kx, int ky, int kz) {
-    return ((unsigned long long)(uint32_t)(kx + MAP_BIAS) << 42) | ((unsigned long long)(uint32_t)(ky + MAP_BIAS) << 21) |
-           (unsigned long long)(uint32_t)(kz + MAP_BIAS);
 }
 
 // The slot of `key`, claimed if the key is new.  false: every slot holds another key.
@@ -45,5 +81,63 @@ __device__ __forceinline__ bool voxel_find(const unsigned long long* keys, uint3
         if (cur == MAP_EMPTY) return false;
     }
     return false;
+}
+
+// Pixel i of frame `frame` to its point in the camera's coordinates.  false (X, Y, Z untouched): beyond the map, invalid or below
+// min_disp16.
+__device__ __forceinline__ bool voxel_point(const VoxelFuseArgs& a, size_t i, int frame, double* X, double* Y, double* Z) {
+    if (i >= (size_t)a.rows * a.cols) return false;
+    const int d16 = a.disp[(size_t)frame * a.mfs + i];
+    if (d16 == VISO_DISP_INVALID || d16 < a.min_disp16) return false;
+    const int y = (int)(i / (size_t)a.cols), x = (int)(i - (size_t)y * a.cols);
+    const double d = (double)d16 / 16.0;
+    *X = a.base * ((double)x - a.cu) / d;      // the operand order of points_kernel (speckle.hip)
+    *Y = a.base * ((double)y - a.cv) / d;
+    *Z = a.f * a.base / d;
+    return true;
+}
+
+// The runs of equal keys along the wave: `head` in the first lane of a run, `len` the number of lanes from this one to the end of
+// its run (in a head lane: the run's length).  Every lane of the wave calls.
+__device__ __forceinline__ void voxel_runs(unsigned long long key, int lane, bool* head, uint32_t* len) {
+    const unsigned long long kl = __shfl_up(key, 1);
+    *head = lane == 0 || key != kl;
+    const unsigned long long m = __ballot(*head);
+    const unsigned long long above = lane < 63 ? m >> (lane + 1) : 0ull;
+    *len = above ? (uint32_t)__ffsll((long long)above) : (uint32_t)(64 - lane);
+}
+
+__device__ __forceinline__ unsigned long long* voxel_stat(const VoxelTable& t, unsigned block, int which) {
+    return t.stats + (size_t)(block & (VOXEL_STAT_SETS - 1)) * VOXEL_STAT_WORDS + which;
+}
+
+// A wave's totals into the block's set: one atomic per counter that is not zero, from lane 0.
+__device__ __forceinline__ void voxel_count_wave(const VoxelTable& t, unsigned block, int lane, unsigned long long points,
+                                                 unsigned long long updates, unsigned long long oor, unsigned long long occ) {
+    if (lane == 0) {
+        if (points) atomicAdd(voxel_stat(t, block, VOXEL_ST_POINTS), points);
+        if (updates) atomicAdd(voxel_stat(t, block, VOXEL_ST_UPDATES), updates);
+        if (oor) atomicAdd(voxel_stat(t, block, VOXEL_ST_OOR), oor);
+        if (occ) atomicAdd(voxel_stat(t, block, VOXEL_ST_OCC), occ);
+    }
+}
+
+// The position in the list of VOXEL_W_OUT of a lane that takes one: one atomic per wave.  false: no lane of the wave takes one.
+// Every lane of the wave calls.
+__device__ __forceinline__ bool voxel_list_position(const VoxelTable& t, bool take, int lane, unsigned long long* at) {
+    const unsigned long long m = __ballot(take);
+    if (!m) return false;
+    unsigned long long base = 0;
+    if (lane == 0) base = atomicAdd(t.words + VOXEL_W_OUT, (unsigned long long)__popcll(m));
+    base = __shfl(base, 0);
+    *at = base + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull));
+    return true;
+}
+
+// a clear kernel's part for the head: one thread per slot
+__device__ __forceinline__ void voxel_clear_head(const VoxelTable& t, uint32_t slot) {
+    t.keys[slot] = MAP_EMPTY;
+    for (uint32_t w = slot; w < VOXEL_STAT_SETS * VOXEL_STAT_WORDS; w += t.mask + 1u) t.stats[w] = 0ull;   // (the smallest table has fewer slots)
+    if (slot < 2) t.words[slot] = 0ull;
 }
 #endif /* VISO_VOXEL_HASH_H_ */

@@ -1,0 +1,267 @@
+// voxel_host.hip — the host side of the shared table layer (voxel_host.h): the registry of live handles, the life of a table, the
+// staging and the group loop of a fuse, the scaffold of add_entries, the pass of an extraction and the read-back of the statistics.
+// No kernel is here: every kind passes its launches in.
+#include "voxel_host.h"
+
+#include <cmath>
+#include <vector>
+
+bool voxel_known(VoxelRegistry& reg, const void* handle) {
+    std::lock_guard<std::mutex> lk(reg.mu);
+    return handle && reg.live.count(handle) != 0;
+}
+
+static bool voxel_ctx_live(const VoxelHost* h) { return viso_ctx_live(h->ctx) && h->ctx->serial == h->ctx_serial; }
+
+static int voxel_not_live(const char* where, const VoxelRegistry& reg) {
+    viso_set_error("%s: not a live %s handle", where, reg.kind.handle);
+    return VISO_ERR_ARG;
+}
+
+int voxel_enter(const char* where, VoxelRegistry& reg, const void* handle, VoxelHost** h) {
+    {
+        std::lock_guard<std::mutex> lk(reg.mu);
+        const auto it = handle ? reg.live.find(handle) : reg.live.end();
+        if (it == reg.live.end()) return voxel_not_live(where, reg);
+        *h = it->second;
+    }
+    if (!voxel_ctx_live(*h)) { viso_set_error("%s: the %s's context has been destroyed", where, reg.kind.noun); return VISO_ERR_ARG; }
+    HIP_TRY(hipSetDevice((*h)->device));
+    return VISO_OK;
+}
+
+int voxel_refuse_overflowed(const char* where, const VoxelHost* h) {
+    viso_set_error("%s: the %s has overflowed (%s were dropped; which ones depends on scheduling): %s it, or use a larger capacity_log2", where,
+                   h->kind->noun, h->kind->unit, h->kind->clear_fn);
+    return VISO_ERR_NOMEM;
+}
+
+int voxel_create(const char* where, VoxelRegistry& reg, viso_ctx* ctx_or_null, int capacity_log2, int min_disp16, size_t payload_bytes,
+                 VoxelHost* h, char** payload) {
+    if (ctx_or_null && !viso_ctx_live(ctx_or_null)) { viso_set_error("%s: not a live context handle", where); return VISO_ERR_ARG; }
+    viso_ctx* c = ctx_or_null ? ctx_or_null : viso_default_ctx();
+    if (!c) return VISO_ERR_HIP;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t slots = (size_t)1 << capacity_log2;
+    const size_t b_keys = 8 * slots, b_payload = payload_bytes * slots, b_stats = 8 * VOXEL_STAT_SETS * VOXEL_STAT_WORDS;
+    const size_t bytes = b_keys + b_payload + b_stats + 256;
+    void* block = nullptr;
+    if (hipMalloc(&block, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        viso_set_error("%s: cannot allocate the %zu-byte table of 2^%d slots", where, bytes, capacity_log2);
+        return VISO_ERR_NOMEM;
+    }
+    h->kind = &reg.kind;
+    h->ctx = c; h->ctx_serial = c->serial; h->device = c->device;
+    h->capacity_log2 = capacity_log2; h->min_disp16 = min_disp16;
+    h->block = block;
+    char* at = static_cast<char*>(block);
+    h->head.keys = reinterpret_cast<unsigned long long*>(at); at += b_keys;
+    *payload = at; at += b_payload;
+    h->head.stats = reinterpret_cast<unsigned long long*>(at); at += b_stats;
+    h->head.words = reinterpret_cast<unsigned long long*>(at);
+    h->head.mask = (uint32_t)(slots - 1);
+    h->overflowed = false;
+    h->d_disp = nullptr; h->d_disp_bytes = 0; h->d_pose = nullptr; h->d_pose_bytes = 0;
+    return VISO_OK;
+}
+
+static int voxel_launch_clear(VoxelHost* h, const VoxelLaunch& clear) {
+    clear(h->ctx->stream);
+    HIP_TRY(hipGetLastError());
+    h->overflowed = false;
+    return VISO_OK;
+}
+
+int voxel_open(VoxelRegistry& reg, const void* handle, VoxelHost* h, const VoxelLaunch& clear) {
+    const int r = voxel_launch_clear(h, clear);
+    if (r < 0) { (void)hipFree(h->block); return r; }
+    std::lock_guard<std::mutex> lk(reg.mu);
+    reg.live[handle] = h;
+    return VISO_OK;
+}
+
+bool voxel_unregister(const char* where, VoxelRegistry& reg, const void* handle) {
+    std::lock_guard<std::mutex> lk(reg.mu);
+    if (reg.live.erase(handle)) return true;
+    voxel_not_live(where, reg);
+    return false;
+}
+
+int voxel_free(const char* where, VoxelHost* h) {
+    hipError_t first = hipSetDevice(h->device);
+    auto note = [&](hipError_t e) { if (e != hipSuccess && first == hipSuccess) first = e; };
+    if (voxel_ctx_live(h)) note(hipStreamSynchronize(h->ctx->stream));   // a destroyed context has waited for its streams itself
+    note(hipFree(h->block));
+    if (h->d_disp) note(hipFree(h->d_disp));
+    if (h->d_pose) note(hipFree(h->d_pose));
+    if (first != hipSuccess) { viso_set_error("%s: %s", where, hipGetErrorString(first)); return VISO_ERR_HIP; }
+    return VISO_OK;
+}
+
+int voxel_clear(const char* where, VoxelRegistry& reg, const void* handle, const VoxelLaunch& clear) {
+    int r;
+    VoxelHost* h;
+    if ((r = voxel_enter(where, reg, handle, &h)) < 0) return r;
+    std::lock_guard<std::mutex> lk(h->mu);
+    return voxel_launch_clear(h, clear);
+}
+
+// grow-only staging of `bytes` at *p
+template <class T>
+static int voxel_grow(const char* where, T** p, size_t* have, size_t bytes, hipStream_t s) {
+    if (*have >= bytes) return VISO_OK;
+    HIP_TRY(hipStreamSynchronize(s));   // nothing in flight reads the old block
+    if (*p) HIP_TRY(hipFree(*p));
+    *p = nullptr; *have = 0;
+    if (hipMalloc((void**)p, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        *p = nullptr;
+        viso_set_error("%s: cannot allocate %zu bytes of staging", where, bytes);
+        return VISO_ERR_NOMEM;
+    }
+    *have = bytes;
+    return VISO_OK;
+}
+
+// behind a call's launches: waits for them and turns dropped points / updates into the overflow mark
+static int voxel_finish(const char* where, VoxelHost* h) {
+    unsigned long long dropped = 0;
+    hipStream_t s = h->ctx->stream;
+    HIP_TRY(hipMemcpyAsync(&dropped, h->head.words + VOXEL_W_DROPPED, sizeof(dropped), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (dropped) {
+        h->overflowed = true;
+        viso_set_error("%s: the table of 2^%d slots is full: %llu %s found no slot (%s, or a larger capacity_log2)", where, h->capacity_log2,
+                       dropped, h->kind->unit, h->kind->clear_fn);
+        return VISO_ERR_NOMEM;
+    }
+    return VISO_OK;
+}
+
+static bool all_finite(const double* v, size_t n) {
+    for (size_t i = 0; i < n; ++i) if (!std::isfinite(v[i])) return false;
+    return true;
+}
+
+static int voxel_fuse_check(const char* where, int rows, int cols, int n_frames, double f, double cu, double cv, double base, const double* poses) {
+    if (poses && !all_finite(poses, (size_t)n_frames * 16)) { viso_set_error("%s: a pose has an entry that is not finite", where); return VISO_ERR_ARG; }
+    if (!std::isfinite(f) || !std::isfinite(cu) || !std::isfinite(cv) || !std::isfinite(base)) {
+        viso_set_error("%s: the calibration (f, cu, cv, base) must be finite", where);
+        return VISO_ERR_ARG;
+    }
+    if ((long long)rows * cols > VOXEL_MAX_PIXELS) { viso_set_error("%s: a %d x %d map is beyond this build (2^31 - 1 pixels)", where, rows, cols); return VISO_ERR_UNSUPPORTED; }
+    return VISO_OK;
+}
+
+// h is entered and locked; disp on its device
+static int voxel_fuse_device(const char* where, VoxelHost* h, const int16_t* disp, size_t mfs, int rows, int cols, int n_frames, double f,
+                             double cu, double cv, double base, const double* poses, const VoxelFuseLaunch& launch) {
+    if (h->overflowed) return voxel_refuse_overflowed(where, h);
+    hipStream_t s = h->ctx->stream;
+    int r;
+    std::vector<double> rows12;   // alive until voxel_finish has waited for the copy that reads it
+    if (poses) {
+        rows12.resize((size_t)n_frames * 12);
+        for (int k = 0; k < n_frames; ++k) std::copy(poses + (size_t)k * 16, poses + (size_t)k * 16 + 12, rows12.begin() + (size_t)k * 12);
+        if ((r = voxel_grow(where, &h->d_pose, &h->d_pose_bytes, rows12.size() * sizeof(double), s)) < 0) return r;
+        HIP_TRY(hipMemcpyAsync(h->d_pose, rows12.data(), rows12.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    }
+    VoxelFuseArgs a;
+    a.mfs = mfs; a.rows = rows; a.cols = cols; a.min_disp16 = h->min_disp16; a._pad = 0;
+    a.f = f; a.cu = cu; a.cv = cv; a.base = base;
+    const size_t px = (size_t)rows * cols;
+    for (int f0 = 0; f0 < n_frames; f0 += VOXEL_GROUP) {
+        const int nf = n_frames - f0 < VOXEL_GROUP ? n_frames - f0 : VOXEL_GROUP;
+        a.disp = disp + (size_t)f0 * mfs;
+        a.poses = poses ? h->d_pose + (size_t)f0 * 12 : nullptr;
+        launch(a, dim3((unsigned)((px + 255) / 256), (unsigned)nf), s);
+        HIP_TRY(hipGetLastError());
+    }
+    return voxel_finish(where, h);
+}
+
+int voxel_fuse_resident(const char* where, VoxelRegistry& reg, const void* handle, viso_ctx* c, const int16_t* disp, size_t mfs, int rows,
+                        int cols, int n_frames, double f, double cu, double cv, double base, const double* poses, const VoxelFuseLaunch& launch) {
+    if (!voxel_known(reg, handle)) return voxel_not_live(where, reg);
+    int r;
+    VoxelHost* h;
+    if ((r = voxel_fuse_check(where, rows, cols, n_frames, f, cu, cv, base, poses)) < 0) return r;
+    if ((r = voxel_enter(where, reg, handle, &h)) < 0) return r;
+    if (h->ctx != c) { viso_set_error("%s: the %s and the batch must share a context", where, reg.kind.noun); return VISO_ERR_ARG; }
+    std::lock_guard<std::mutex> lk(h->mu);
+    return voxel_fuse_device(where, h, disp, mfs, rows, cols, n_frames, f, cu, cv, base, poses, launch);
+}
+
+int voxel_fuse_host(const char* where, VoxelRegistry& reg, const void* handle, const int16_t* disp, int rows, int cols, const viso_param* param,
+                    const double* pose_or_null, const VoxelFuseLaunch& launch) {
+    if (!voxel_known(reg, handle)) return voxel_not_live(where, reg);
+    if (!disp || !param || rows <= 0 || cols <= 0) { viso_set_error("%s: bad argument (non-null map and calibration, sizes > 0)", where); return VISO_ERR_ARG; }
+    int r;
+    VoxelHost* h;
+    if ((r = voxel_fuse_check(where, rows, cols, 1, param->f, param->cu, param->cv, param->base, pose_or_null)) < 0) return r;
+    if ((r = voxel_enter(where, reg, handle, &h)) < 0) return r;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (h->overflowed) return voxel_refuse_overflowed(where, h);
+    const size_t px = (size_t)rows * cols;
+    hipStream_t s = h->ctx->stream;
+    if ((r = voxel_grow(where, &h->d_disp, &h->d_disp_bytes, px * sizeof(int16_t), s)) < 0) return r;
+    HIP_TRY(hipMemcpyAsync(h->d_disp, disp, px * sizeof(int16_t), hipMemcpyHostToDevice, s));
+    return voxel_fuse_device(where, h, h->d_disp, px, rows, cols, 1, param->f, param->cu, param->cv, param->base, pose_or_null, launch);
+}
+
+int voxel_add_entries(const char* where, VoxelRegistry& reg, const void* handle, const void* entries, size_t n, size_t entry_bytes,
+                      const VoxelEntriesLaunch& launch) {
+    int r;
+    VoxelHost* h;
+    if ((r = voxel_enter(where, reg, handle, &h)) < 0) return r;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (h->overflowed) return voxel_refuse_overflowed(where, h);
+    if (!n) return VISO_OK;
+    hipStream_t s = h->ctx->stream;
+    void* d = nullptr;
+    if (hipMalloc(&d, n * entry_bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        viso_set_error("%s: cannot allocate %zu bytes for the entries", where, n * entry_bytes);
+        return VISO_ERR_NOMEM;
+    }
+    hipError_t e = hipMemcpyAsync(d, entries, n * entry_bytes, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) {
+        launch(d, dim3((unsigned)((n + 255) / 256)), s);
+        e = hipGetLastError();
+    }
+    r = e == hipSuccess ? voxel_finish(where, h) : VISO_OK;
+    if (e != hipSuccess) (void)hipStreamSynchronize(s);   // nothing in flight reads the list that is freed next
+    (void)hipFree(d);
+    HIP_TRY(e);
+    return r;
+}
+
+int voxel_pass(VoxelHost* h, const VoxelLaunch& launch, unsigned long long* n) {
+    hipStream_t s = h->ctx->stream;
+    HIP_TRY(hipMemsetAsync(h->head.words + VOXEL_W_OUT, 0, sizeof(unsigned long long), s));
+    launch(s);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(n, h->head.words + VOXEL_W_OUT, sizeof(*n), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return VISO_OK;
+}
+
+int voxel_stats(const char* where, VoxelRegistry& reg, const void* handle, const void* out, unsigned long long sums[4], unsigned long long* dropped) {
+    if (!voxel_known(reg, handle)) return voxel_not_live(where, reg);
+    if (!out) { viso_set_error("%s: bad argument (a non-null output)", where); return VISO_ERR_ARG; }
+    int r;
+    VoxelHost* h;
+    if ((r = voxel_enter(where, reg, handle, &h)) < 0) return r;
+    std::lock_guard<std::mutex> lk(h->mu);
+    std::vector<unsigned long long> w((size_t)VOXEL_STAT_SETS * VOXEL_STAT_WORDS + 2);
+    hipStream_t s = h->ctx->stream;
+    HIP_TRY(hipMemcpyAsync(w.data(), h->head.stats, w.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));   // stats | words: adjacent
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int c = 0; c < 4; ++c) {
+        sums[c] = 0;
+        for (int k = 0; k < VOXEL_STAT_SETS; ++k) sums[c] += w[(size_t)k * VOXEL_STAT_WORDS + c];
+    }
+    *dropped = w[(size_t)VOXEL_STAT_SETS * VOXEL_STAT_WORDS + VOXEL_W_DROPPED];
+    return VISO_OK;
+}
