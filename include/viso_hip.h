@@ -1084,6 +1084,55 @@ int viso_tsdf_mesh_count(viso_tsdf* t, uint32_t min_weight, size_t* n_vertices, 
 int viso_tsdf_mesh(viso_tsdf* t, uint32_t min_weight, viso_tsdf_mesh_vertex* vertices_out, size_t nv_cap,
                    viso_tsdf_triangle* triangles_out, size_t nt_cap, size_t* n_vertices, size_t* n_triangles);
 
+/* ------------------------------------------------ TSDF render: disparity maps of the map at any pose, by ray casting (opt-in; NOT
+ * in the reference)
+ *
+ * What a camera at a pose would see of a TSDF map, as an ordinary int16 map in 1/16 px: it goes wherever a measured map goes
+ * (viso_disparity_to_points, viso_filter_speckles, viso_map_fuse, the KITTI PNGs).  A render reads the table only: the table, its
+ * statistics and the overflow mark are untouched.  This definition is the contract; the device output is bit-identical to
+ * tests/render_ref.py.  Everything is IEEE double in the operand order written, with no fused multiply-add.
+ * Inputs: the map; min_weight >= 1; a viso_param of which f, cu, cv, base are read (all finite, f > 0, base > 0); rows, cols >= 1
+ * with rows cols <= 2^31 - 1; max_depth finite and > 0; n_views >= 1; poses [n_views][16], row-major 4 x 4, camera to world, as
+ * viso_tsdf_fuse takes them, all entries finite, or NULL, which means no transform and only with n_views == 1.  s = voxel / 1024 and
+ * h = voxel * 0.5 are the map's own; N = (int) floor(max_depth / h) must lie in 1 .. 65536.  Any violation: VISO_ERR_ARG before a
+ * device is touched.
+ * Per view and pixel (x, y):
+ *   1. Ray: a = ((double)x - cu) / f, b = ((double)y - cv) / f.
+ *   2. Samples i = 1 .. N ascending: z_i = (double)i h (not accumulated), Qc = (a z_i, b z_i, z_i), and the world point Q as step 3
+ *      of the TSDF map forms it (((T[i][0] Qc0 + T[i][1] Qc1) + T[i][2] Qc2) + T[i][3]; no pose: Q = Qc).
+ *   3. Voxel: g_i = floor(Q_i / s), k_i = g_i >> 10, as step 4 of the map.  Any |g_i| >= 2^30, or a quotient that is not finite:
+ *      the sample is a gap.
+ *   4. The ray's voxel sequence: a sample whose voxel equals the voxel of the previous non-gap sample is skipped.  A gap empties
+ *      "previous".
+ *   5. A voxel is usable when it is in the table with weight >= min_weight.  One that is not still becomes "previous" for rule 4,
+ *      marked not usable.
+ *   6. Hit: the first sample whose voxel b is usable with sum_b < 0 and whose previous voxel a (the element of the sequence right
+ *      before it, with no gap between) is usable with sum_a >= 0.  Only crossings from the front to the back count: a surface seen
+ *      from behind renders as nothing.  The ray ends at the hit.
+ *   7. Depth of the hit: the centre depths za, zb of a and b in this view's camera by step 6 of the map (C_i = (double)(k_i 1024 +
+ *      512) s, zc = (T[0][2] (C0 - T[0][3]) + T[1][2] (C1 - T[1][3])) + T[2][2] (C2 - T[2][3]); no pose: C2);
+ *      da = (double)sa / (double)wa, db likewise, t = da / (da - db), zs = za + (zb - za) t.  For a fronto-parallel surface seen
+ *      from the pose it was fused from, da s = Z - za and db s = Z - zb up to the floor of step 6, so zs = Z up to 2 s: that is why
+ *      the interpolation runs over centre depths and not over sample positions.
+ *   8. v = ((f base) / zs) 16.0 + 0.5.  !(zs > 0), !(v >= 1.0) or v >= 32768.0: the pixel is invalid.  Otherwise
+ *      disp16 = (int16) floor(v) and weight = min(wa, wb).
+ *   9. No hit within the N samples, or an invalid value: VISO_DISP_INVALID, weight 0.
+ * The surface is looked up in the nearest voxel and the distances are projective (along the fusing views' axes), so a slanted
+ * surface and a view away from the fusing poses come back within a few sixteenths of a pixel, and a depth edge bleeds by up to a
+ * voxel's footprint (DESIGN.md 5.17 has the figures).
+ * An overflowed map refuses with VISO_ERR_NOMEM, as the getters do; a handle that is not a live TSDF map, or whose context is gone,
+ * VISO_ERR_ARG; no device, VISO_ERR_HIP.  The call takes the map's lock, like an extraction.
+ * Out of scope: trilinear sampling, normals and shaded images, an empty-space skipping structure (a coarse block table), rendering
+ * into a batch's resident maps, frame-to-model alignment, colour.
+ * HIP kernel (tsdf.hip): tsdf_render_kernel, one thread per pixel of a group of views, the lanes of a wave consecutive pixels of a
+ * row.  The loop over i is uniform across the wave; per i the lanes that continue the voxel of the lane to their left form a run,
+ * whose head lane alone probes the table and loads weight and sum, and the other lanes take them from it.  Reads only: no atomics,
+ * no LDS, no scratch; the probe loop is bounded by the capacity and advances strictly. */
+/* disp_out: [n_views][rows][cols]; weight_out_or_null: the same shape, or NULL.  The views go through a device buffer that is
+ * freed on every path (VISO_ERR_NOMEM when it cannot be allocated). */
+int viso_tsdf_render(viso_tsdf* t, uint32_t min_weight, const viso_param* param, int rows, int cols, double max_depth,
+                     const double* poses_or_null, int n_views, int16_t* disp_out, uint32_t* weight_out_or_null);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1037,6 +1037,30 @@ class TsdfMap(_TableMap):
                                                           C.byref(nv), C.byref(nt)))
         return v[:nv.value], tri[:nt.value]
 
+    def render(self, param, shape, poses=None, max_depth=40.0, min_weight=2, weights=False):
+        """viso_tsdf_render: what a camera with the calibration of param (f, cu, cv, base) would see of the map, by ray casting: an
+        int16 disparity map in 1/16 px of shape (rows, cols), VISO_DISP_INVALID where the ray meets no surface from its front within
+        max_depth metres.  poses: None (no transform), one 4 x 4 camera-to-world matrix, as fuse takes it (returns [rows][cols]), or
+        [n][4][4] (returns [n][rows][cols], the views of one call).  min_weight: only voxels with at least this many updates.
+        weights=True: a tuple with the uint32 array of the same shape, the smaller weight of the two voxels of a hit (0: none)."""
+        rows, cols = (int(v) for v in shape)
+        T = None
+        if poses is not None:
+            T = np.ascontiguousarray(poses, dtype=np.float64)
+            if T.shape[-2:] != (4, 4) or T.ndim not in (2, 3) or T.size == 0:
+                raise ValueError("TsdfMap.render: poses must be None, a 4 x 4 matrix or [n][4][4]")
+        n = 1 if T is None or T.ndim == 2 else len(T)
+        if rows < 1 or cols < 1:
+            raise ValueError("TsdfMap.render: shape must be (rows, cols), both >= 1")
+        d = np.empty((n, rows, cols), np.int16)
+        w = np.empty((n, rows, cols), np.uint32) if weights else None
+        self._chk("viso_tsdf_render", self.L.viso_tsdf_render(self.h, int(min_weight), C.byref(param), rows, cols, float(max_depth),
+                                                              ptr(T, C.c_double) if T is not None else None, n, ptr(d, C.c_int16),
+                                                              ptr(w, C.c_uint32) if weights else None))
+        if T is None or T.ndim == 2:
+            d, w = d[0], (w[0] if weights else None)
+        return (d, w) if weights else d
+
 
 class Batch:
     """viso_batch: n_frames stereo frames resident in HBM (include/viso_hip.h)."""

@@ -293,6 +293,8 @@ def declare_tsdf(lib):
     lib.viso_tsdf_crossing_point.argtypes = [vp, C.c_double, f32p]
     lib.viso_tsdf_mesh_count.argtypes = [vp, C.c_uint32, szp, szp]
     lib.viso_tsdf_mesh.argtypes = [vp, C.c_uint32, vp, C.c_size_t, vp, C.c_size_t, szp, szp]
+    lib.viso_tsdf_render.argtypes = [vp, C.c_uint32, C.POINTER(Param), C.c_int, C.c_int, C.c_double, f64p, C.c_int, i16p,
+                                     C.POINTER(C.c_uint32)]
 
 
 class MotionCov(C.Structure):

@@ -20,6 +20,10 @@
 //   tsdf_mesh_kernel         one thread per slot, seven read-only probes for the other corners of the voxel's cell: the sign-changing
 //                            edges the voxel owns as vertices, and the triangles of the cell's six tetrahedra as references to
 //                            them; two lists, one atomic per wave and list; the same two passes.
+//   tsdf_render_kernel       one thread per pixel of a group of views, reads only (include/viso_hip.h, "TSDF render").
+//                            The march over the samples of a pixel's ray is uniform across the wave, with the runs of the fuse
+//                            kernel: only a run's head lane probes the table (voxel_find) and loads weight and sum, the other
+//                            lanes of the run take them from it (three ds_bpermute).  Ends when no lane of the wave marches.
 //   tsdf_clear_kernel        one thread per slot.
 // What every table of voxels shares is not here (voxelmap.hip says what): the device side is voxel_hash.h, the host side
 // voxel_host.h.  This file keeps the table's payload and insert, the kernels' own bodies, the parameter and entry checks, the
@@ -329,6 +333,98 @@ __global__ __launch_bounds__(256) void tsdf_mesh_kernel(TsdfTable t, uint32_t mi
     }
 }
 
+// ---- ray casting (include/viso_hip.h, "TSDF render") ---------------------------------------------------------------
+struct TsdfRenderArgs {
+    TsdfTable t;
+    const double* poses;               // [views][12] on the device, or null: no transform
+    int16_t* disp; uint32_t* weight;   // [views][rows * cols]; weight may be null
+    int rows, cols, n_samples; uint32_t min_weight;
+    double f, cu, cv, base, s, h;
+};
+
+__global__ __launch_bounds__(256) void tsdf_render_kernel(TsdfRenderArgs a) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, px = (size_t)a.rows * a.cols;
+    const int lane = threadIdx.x & 63, view = blockIdx.y;
+    bool march = i < px;
+    if (!__ballot(march)) return;   // the whole wave
+    const int y = (int)(i / (size_t)a.cols), x = (int)(i - (size_t)y * a.cols);
+    const double ra = ((double)x - a.cu) / a.f, rb = ((double)y - a.cv) / a.f;
+    // without a pose the identity, as in tsdf_fuse_kernel
+    double T0 = 1.0, T1 = 0.0, T2 = 0.0, T3 = 0.0, T4 = 0.0, T5 = 1.0, T6 = 0.0, T7 = 0.0, T8 = 0.0, T9 = 0.0, T10 = 1.0, T11 = 0.0;
+    if (a.poses) {
+        const double* T = a.poses + (size_t)view * 12;
+        T0 = T[0]; T1 = T[1]; T2 = T[2]; T3 = T[3]; T4 = T[4]; T5 = T[5]; T6 = T[6]; T7 = T[7]; T8 = T[8]; T9 = T[9]; T10 = T[10]; T11 = T[11];
+    }
+    // the previous element of the ray's voxel sequence: its key (empty: none, or a gap since), and where it is usable its payload
+    unsigned long long prev = MAP_EMPTY;
+    int pkx = 0, pky = 0, pkz = 0;
+    uint32_t pw = 0;                   // 0: not usable
+    long long ps = 0;
+    int16_t out_d = VISO_DISP_INVALID;
+    uint32_t out_w = 0;
+    for (int n = 1; n <= a.n_samples; ++n) {   // the same n in every lane
+        if (!__ballot(march)) break;           // the whole wave
+        unsigned long long key = MAP_EMPTY;    // the voxel this lane enters with this sample
+        int kx = 0, ky = 0, kz = 0;
+        if (march) {
+            const double z = (double)n * a.h;
+            const double c0 = ra * z, c1 = rb * z;
+            const double gx = floor((((T0 * c0 + T1 * c1) + T2 * z) + T3) / a.s);
+            const double gy = floor((((T4 * c0 + T5 * c1) + T6 * z) + T7) / a.s);
+            const double gz = floor((((T8 * c0 + T9 * c1) + T10 * z) + T11) / a.s);
+            if (fabs(gx) < MAP_RANGE && fabs(gy) < MAP_RANGE && fabs(gz) < MAP_RANGE) {   // false for a NaN
+                kx = (int)gx >> 10; ky = (int)gy >> 10; kz = (int)gz >> 10;
+                const unsigned long long k = voxel_key(kx, ky, kz);
+                if (k != prev) key = k;
+            } else {
+                prev = MAP_EMPTY;              // a gap
+                pw = 0;
+            }
+        }
+        if (!__ballot(key != MAP_EMPTY)) continue;   // the whole wave
+        // the runs of equal keys along the wave (lanes that enter no voxel: runs of the empty key, which probe nothing)
+        bool head;
+        uint32_t len;
+        voxel_runs(key, lane, &head, &len);
+        const int from = voxel_run_head(head, lane);
+        uint32_t w = 0;                        // 0: not in the table
+        long long sum = 0;
+        if (head && key != MAP_EMPTY) {
+            uint32_t slot;
+            if (voxel_find(a.t.head.keys, a.t.head.mask, key, &slot)) {
+                w = a.t.weight[slot];
+                sum = (long long)a.t.sum[slot];
+            }
+        }
+        w = (uint32_t)__shfl((int)w, from);
+        sum = __shfl(sum, from);
+        if (key == MAP_EMPTY) continue;
+        if (w < a.min_weight) w = 0;           // (min_weight >= 1: a voxel that is not in the table is not usable either)
+        if (w && sum < 0 && prev != MAP_EMPTY && pw && ps >= 0) {
+            // the hit: between the centres of the previous voxel and this one
+            const double A0 = (double)(pkx * 1024 + 512) * a.s, A1 = (double)(pky * 1024 + 512) * a.s, A2 = (double)(pkz * 1024 + 512) * a.s;
+            const double B0 = (double)(kx * 1024 + 512) * a.s, B1 = (double)(ky * 1024 + 512) * a.s, B2 = (double)(kz * 1024 + 512) * a.s;
+            const double za = (T2 * (A0 - T3) + T6 * (A1 - T7)) + T10 * (A2 - T11);
+            const double zb = (T2 * (B0 - T3) + T6 * (B1 - T7)) + T10 * (B2 - T11);
+            const double da = (double)ps / (double)pw, db = (double)sum / (double)w;
+            const double t = da / (da - db);
+            const double zs = za + (zb - za) * t;
+            const double v = ((a.f * a.base) / zs) * 16.0 + 0.5;
+            if (zs > 0.0 && v >= 1.0 && !(v >= 32768.0)) {   // false for a NaN
+                out_d = (int16_t)(int)floor(v);
+                out_w = pw < w ? pw : w;
+            }
+            march = false;
+        } else {
+            prev = key; pkx = kx; pky = ky; pkz = kz; pw = w; ps = sum;
+        }
+    }
+    if (i < px) {
+        a.disp[(size_t)view * px + i] = out_d;
+        if (a.weight) a.weight[(size_t)view * px + i] = out_w;
+    }
+}
+
 __global__ __launch_bounds__(256) void tsdf_clear_kernel(TsdfTable t) {
     const uint32_t slot = blockIdx.x * 256 + threadIdx.x;
     voxel_clear_head(t.head, slot);
@@ -574,6 +670,45 @@ extern "C" int viso_tsdf_mesh_count(viso_tsdf* t, uint32_t min_weight, size_t* n
 extern "C" int viso_tsdf_mesh(viso_tsdf* t, uint32_t min_weight, viso_tsdf_mesh_vertex* vertices_out, size_t nv_cap,
                               viso_tsdf_triangle* triangles_out, size_t nt_cap, size_t* n_vertices, size_t* n_triangles) {
     return tsdf_mesh_extract("viso_tsdf_mesh", t, min_weight, false, vertices_out, nv_cap, triangles_out, nt_cap, n_vertices, n_triangles);
+}
+
+extern "C" int viso_tsdf_render(viso_tsdf* t, uint32_t min_weight, const viso_param* param, int rows, int cols, double max_depth,
+                                const double* poses_or_null, int n_views, int16_t* disp_out, uint32_t* weight_out_or_null) {
+    const char* where = "viso_tsdf_render";
+    // what does not need the map first, so that nothing of a wrong call reaches a handle
+    if (min_weight < 1 || !param || !disp_out || rows < 1 || cols < 1 || n_views < 1 || (!poses_or_null && n_views != 1) ||
+        !(std::isfinite(max_depth) && max_depth > 0.0)) {
+        viso_set_error("%s: bad argument (min_weight >= 1, non-null calibration and output, sizes >= 1, a finite max_depth > 0, n_views >= 1 "
+                       "and 1 without poses)", where);
+        return VISO_ERR_ARG;
+    }
+    if (!(std::isfinite(param->f) && std::isfinite(param->cu) && std::isfinite(param->cv) && std::isfinite(param->base) && param->f > 0.0 &&
+          param->base > 0.0)) {
+        viso_set_error("%s: bad argument (the calibration f, cu, cv, base must be finite, f > 0 and base > 0)", where);
+        return VISO_ERR_ARG;
+    }
+    if ((long long)rows * cols > VOXEL_MAX_PIXELS) { viso_set_error("%s: bad argument (a %d x %d view is beyond 2^31 - 1 pixels)", where, rows, cols); return VISO_ERR_ARG; }
+    if (poses_or_null) {
+        for (size_t i = 0; i < (size_t)n_views * 16; ++i) {
+            if (!std::isfinite(poses_or_null[i])) { viso_set_error("%s: bad argument (pose %zu has an entry that is not finite)", where, i / 16); return VISO_ERR_ARG; }
+        }
+    }
+    if (!voxel_known(g_tsdfs, t)) { viso_set_error("%s: not a live TSDF handle", where); return VISO_ERR_ARG; }
+    const double steps = floor(max_depth / t->hs);
+    if (!(steps >= 1.0 && steps <= 65536.0)) {
+        viso_set_error("%s: bad argument (max_depth %g is %g steps of half a voxel: 1 .. 65536)", where, max_depth, steps);
+        return VISO_ERR_ARG;
+    }
+    TsdfRenderArgs a;
+    a.t = t->t;
+    a.rows = rows; a.cols = cols; a.n_samples = (int)steps; a.min_weight = min_weight;
+    a.f = param->f; a.cu = param->cu; a.cv = param->cv; a.base = param->base; a.s = t->s; a.h = t->hs;
+    return voxel_render(where, g_tsdfs, t, (size_t)rows * cols, poses_or_null, n_views, disp_out, weight_out_or_null,
+                        [a](const double* d_poses, int16_t* d_disp, uint32_t* d_weight, dim3 grid, hipStream_t s) {
+        TsdfRenderArgs g = a;
+        g.poses = d_poses; g.disp = d_disp; g.weight = d_weight;
+        hipLaunchKernelGGL(tsdf_render_kernel, grid, dim3(256), 0, s, g);
+    });
 }
 
 extern "C" int viso_tsdf_stats(viso_tsdf* t, viso_tsdf_counters* out) {

@@ -107,6 +107,13 @@ __device__ __forceinline__ void voxel_runs(unsigned long long key, int lane, boo
     *len = above ? (uint32_t)__ffsll((long long)above) : (uint32_t)(64 - lane);
 }
 
+// The first lane of this lane's run, from the `head` of voxel_runs: the highest head lane at or below this one (lane 0 is a head).
+// Every lane of the wave calls.
+__device__ __forceinline__ int voxel_run_head(bool head, int lane) {
+    const unsigned long long m = __ballot(head) & (~0ull >> (63 - lane));
+    return 63 - __clzll((long long)m);
+}
+
 __device__ __forceinline__ unsigned long long* voxel_stat(const VoxelTable& t, unsigned block, int which) {
     return t.stats + (size_t)(block & (VOXEL_STAT_SETS - 1)) * VOXEL_STAT_WORDS + which;
 }

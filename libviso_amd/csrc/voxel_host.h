@@ -41,6 +41,7 @@ struct VoxelRegistry {
 
 using VoxelLaunch = std::function<void(hipStream_t)>;                                             // the clear
 using VoxelFuseLaunch = std::function<void(const VoxelFuseArgs&, dim3 grid, hipStream_t)>;        // one group of frames
+using VoxelRenderLaunch = std::function<void(const double* d_poses, int16_t* d_disp, uint32_t* d_weight, dim3 grid, hipStream_t)>;   // one group of views
 using VoxelEntriesLaunch = std::function<void(const void* d_entries, dim3 grid, hipStream_t)>;   // add_entries
 
 bool voxel_known(VoxelRegistry& reg, const void* handle);
@@ -69,6 +70,11 @@ int voxel_fuse_host(const char* where, VoxelRegistry& reg, const void* handle, c
 // viso_*_add_entries behind the handle check and the validation of the n entries of entry_bytes each
 int voxel_add_entries(const char* where, VoxelRegistry& reg, const void* handle, const void* entries, size_t n, size_t entry_bytes,
                       const VoxelEntriesLaunch& launch);
+// viso_*_render behind the handle and argument checks: the map entered, locked and not overflowed; the poses [n_views][16] (or
+// null) through d_pose; a device buffer for n_views maps of px int16 and, with weight_out, as many uint32, freed on every path; the
+// groups of views, each started by `launch` with its poses ([.][12] or null) and its part of the buffer; the copies to the host.
+int voxel_render(const char* where, VoxelRegistry& reg, const void* handle, size_t px, const double* poses, int n_views, int16_t* disp_out,
+                 uint32_t* weight_out, const VoxelRenderLaunch& launch);
 // viso_*_stats: the four counters summed over the sets (VOXEL_ST_*) and the dropped word
 int voxel_stats(const char* where, VoxelRegistry& reg, const void* handle, const void* out, unsigned long long sums[4], unsigned long long* dropped);
 

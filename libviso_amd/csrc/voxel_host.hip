@@ -1,5 +1,6 @@
 // voxel_host.hip — the host side of the shared table layer (voxel_host.h): the registry of live handles, the life of a table, the
-// staging and the group loop of a fuse, the scaffold of add_entries, the pass of an extraction and the read-back of the statistics.
+// staging and the group loop of a fuse, the scaffold of add_entries, the pass of an extraction, the staging and the output buffer of
+// a render and the read-back of the statistics.
 // No kernel is here: every kind passes its launches in.
 #include "voxel_host.h"
 
@@ -154,6 +155,18 @@ static int voxel_fuse_check(const char* where, int rows, int cols, int n_frames,
     return VISO_OK;
 }
 
+// The first three rows of n poses [n][16] into h->d_pose (grow-only) as [n][12]; rows12 is the copy's source and must live until
+// the stream has been waited for.  h is entered and locked.
+static int voxel_stage_poses(const char* where, VoxelHost* h, const double* poses, int n, std::vector<double>& rows12) {
+    hipStream_t s = h->ctx->stream;
+    int r;
+    rows12.resize((size_t)n * 12);
+    for (int k = 0; k < n; ++k) std::copy(poses + (size_t)k * 16, poses + (size_t)k * 16 + 12, rows12.begin() + (size_t)k * 12);
+    if ((r = voxel_grow(where, &h->d_pose, &h->d_pose_bytes, rows12.size() * sizeof(double), s)) < 0) return r;
+    HIP_TRY(hipMemcpyAsync(h->d_pose, rows12.data(), rows12.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    return VISO_OK;
+}
+
 // h is entered and locked; disp on its device
 static int voxel_fuse_device(const char* where, VoxelHost* h, const int16_t* disp, size_t mfs, int rows, int cols, int n_frames, double f,
                              double cu, double cv, double base, const double* poses, const VoxelFuseLaunch& launch) {
@@ -161,12 +174,7 @@ static int voxel_fuse_device(const char* where, VoxelHost* h, const int16_t* dis
     hipStream_t s = h->ctx->stream;
     int r;
     std::vector<double> rows12;   // alive until voxel_finish has waited for the copy that reads it
-    if (poses) {
-        rows12.resize((size_t)n_frames * 12);
-        for (int k = 0; k < n_frames; ++k) std::copy(poses + (size_t)k * 16, poses + (size_t)k * 16 + 12, rows12.begin() + (size_t)k * 12);
-        if ((r = voxel_grow(where, &h->d_pose, &h->d_pose_bytes, rows12.size() * sizeof(double), s)) < 0) return r;
-        HIP_TRY(hipMemcpyAsync(h->d_pose, rows12.data(), rows12.size() * sizeof(double), hipMemcpyHostToDevice, s));
-    }
+    if (poses && (r = voxel_stage_poses(where, h, poses, n_frames, rows12)) < 0) return r;
     VoxelFuseArgs a;
     a.mfs = mfs; a.rows = rows; a.cols = cols; a.min_disp16 = h->min_disp16; a._pad = 0;
     a.f = f; a.cu = cu; a.cv = cv; a.base = base;
@@ -244,6 +252,44 @@ int voxel_pass(VoxelHost* h, const VoxelLaunch& launch, unsigned long long* n) {
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(n, h->head.words + VOXEL_W_OUT, sizeof(*n), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
+    return VISO_OK;
+}
+
+int voxel_render(const char* where, VoxelRegistry& reg, const void* handle, size_t px, const double* poses, int n_views, int16_t* disp_out,
+                 uint32_t* weight_out, const VoxelRenderLaunch& launch) {
+    int r;
+    VoxelHost* h;
+    if ((r = voxel_enter(where, reg, handle, &h)) < 0) return r;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (h->overflowed) return voxel_refuse_overflowed(where, h);
+    hipStream_t s = h->ctx->stream;
+    const size_t per = weight_out ? 6 : 2;   // bytes a pixel: the weights, then the maps
+    if (px > (size_t)-1 / per / (size_t)n_views) { viso_set_error("%s: %d views of %zu pixels are beyond the address space", where, n_views, px); return VISO_ERR_NOMEM; }
+    const size_t n = (size_t)n_views * px, b_weight = weight_out ? n * sizeof(uint32_t) : 0, bytes = b_weight + n * sizeof(int16_t);
+    std::vector<double> rows12;   // alive until the stream has been waited for
+    if (poses && (r = voxel_stage_poses(where, h, poses, n_views, rows12)) < 0) return r;
+    void* d = nullptr;
+    if (hipMalloc(&d, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipStreamSynchronize(s);   // the copy of the poses reads rows12
+        viso_set_error("%s: cannot allocate %zu bytes for the views", where, bytes);
+        return VISO_ERR_NOMEM;
+    }
+    uint32_t* d_weight = weight_out ? static_cast<uint32_t*>(d) : nullptr;
+    int16_t* d_disp = reinterpret_cast<int16_t*>(static_cast<char*>(d) + b_weight);
+    hipError_t e = hipSuccess;
+    for (int v0 = 0; v0 < n_views && e == hipSuccess; v0 += VOXEL_GROUP) {
+        const int nv = n_views - v0 < VOXEL_GROUP ? n_views - v0 : VOXEL_GROUP;
+        launch(poses ? h->d_pose + (size_t)v0 * 12 : nullptr, d_disp + (size_t)v0 * px, d_weight ? d_weight + (size_t)v0 * px : nullptr,
+               dim3((unsigned)((px + 255) / 256), (unsigned)nv), s);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(disp_out, d_disp, n * sizeof(int16_t), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && d_weight) e = hipMemcpyAsync(weight_out, d_weight, b_weight, hipMemcpyDeviceToHost, s);
+    const hipError_t e_wait = hipStreamSynchronize(s);   // nothing in flight touches the buffer that is freed next
+    (void)hipFree(d);   // on every path
+    HIP_TRY(e);
+    HIP_TRY(e_wait);
     return VISO_OK;
 }
 

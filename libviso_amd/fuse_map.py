@@ -1,5 +1,5 @@
 """python -m libviso_amd.fuse_map DISPARITY_DIR POSES.txt CALIB.txt OUT.ply [--voxel V --min-count N --min-disp PX --frames B E]
-                                 [--surface | --mesh [--trunc T --min-weight N]]
+                                 [--surface | --mesh [--trunc T --min-weight N] [--render DIR [--render-depth M]]]
 
 Fuses the maps a KITTI runner wrote with --disparity DIR and the poses of its pose file into one voxel map on the device
 (libviso_amd.VoxelMap; include/viso_hip.h, "voxel map") and writes the occupied voxels as a binary PLY point cloud: x, y, z the
@@ -16,6 +16,10 @@ float32 centroid of each voxel, count the number of points fused into it.
   --mesh         fuse into a TSDF map as --surface does, with its options, and write the surface as a triangle mesh by marching
                  tetrahedra (include/viso_hip.h, "TSDF mesh"): per vertex x, y, z and weight as above, per face three vertex
                  indices, the normals towards the cameras.  Not together with --surface.
+  --render DIR   with --surface or --mesh: after fusing, also render the model at every pose that was fused, at the size of the
+                 input maps, by ray casting (include/viso_hip.h, "TSDF render"; --min-weight applies), and write DIR/<name of the
+                 input map> in the format of the input maps (a pixel rendered beyond 255.9 px, which the format cannot hold, is
+                 written as invalid).  --render-depth M: how far a ray is followed, in metres (40).
 
 Both runners write byte-identical directories and pose files for every rank count and chunk size, so the PLY is identical too."""
 import argparse
@@ -27,6 +31,8 @@ import zlib
 import numpy as np
 
 DISP_INVALID = -16
+DISP_PNG_MAX = 4095   # the largest map value a 16-bit file holds (x 16)
+RENDER_VIEWS = 16     # views of one --render call
 
 
 def read_png16(path):
@@ -99,6 +105,33 @@ def read_disparity_png(path):
     return d
 
 
+def write_png16(path, v):
+    """uint16 [rows][cols] as a non-interlaced 16-bit grayscale PNG (row filter 0), which read_png16 reads back to the same array."""
+    v = np.ascontiguousarray(v, np.uint16)
+    if v.ndim != 2 or v.size == 0:
+        raise ValueError("write_png16: a 2-D array with at least one pixel")
+    rows, cols = v.shape
+    raw = np.zeros((rows, 1 + 2 * cols), np.uint8)
+    raw[:, 1:] = v.astype(">u2").view(np.uint8).reshape(rows, 2 * cols)
+
+    def chunk(kind, body):
+        return struct.pack(">I", len(body)) + kind + body + struct.pack(">I", zlib.crc32(kind + body) & 0xffffffff)
+
+    with open(path, "wb") as f:
+        f.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", cols, rows, 16, 0, 0, 0, 0)) +
+                chunk(b"IDAT", zlib.compress(raw.tobytes(), 6)) + chunk(b"IEND", b""))
+
+
+def write_disparity_png(path, d16):
+    """An int16 map in 1/16 px in the runners' format: value = disparity x 256, 0 where the map is invalid.  A valid value is
+    1 .. 4095 (the file's 16 bits end below 256 px), so no valid pixel is written as 0 and read_disparity_png reads the file back
+    to the same array."""
+    d16 = np.asarray(d16)
+    if d16.dtype != np.int16 or ((d16 != DISP_INVALID) & ((d16 < 1) | (d16 > DISP_PNG_MAX))).any():
+        raise ValueError(f"write_disparity_png: an int16 map whose valid values are 1 .. {DISP_PNG_MAX}")
+    write_png16(path, np.where(d16 == DISP_INVALID, 0, d16.astype(np.int32) * 16).astype(np.uint16))
+
+
 def read_poses(path):
     """[n][4][4] float64 from a KITTI pose file (12 numbers a line)."""
     out = []
@@ -147,7 +180,11 @@ def main(argv=None):
     mode.add_argument("--mesh", action="store_true", help="write the triangle mesh of a TSDF map in place of the centroids")
     ap.add_argument("--trunc", type=int, default=3, help="with --surface or --mesh: the truncation band in voxels (3)")
     ap.add_argument("--min-weight", type=int, default=1, help="with --surface or --mesh: only voxels with at least this many updates (1)")
+    ap.add_argument("--render", metavar="DIR", help="with --surface or --mesh: also write the model rendered at every fused pose into DIR")
+    ap.add_argument("--render-depth", type=float, default=40.0, metavar="M", help="with --render: how far a ray is followed, metres (40)")
     a = ap.parse_args(argv)
+    if a.render and not (a.surface or a.mesh):
+        ap.error("--render needs --surface or --mesh (only a TSDF map is rendered)")
     import libviso_amd
     from libviso_amd.abi import Param
     names, poses = list_maps(a.disparity_dir), read_poses(a.poses)
@@ -162,9 +199,26 @@ def main(argv=None):
         tsdf = libviso_amd.TsdfMap(None, voxel=a.voxel, trunc_voxels=a.trunc, min_disp16=max(1, int(round(a.min_disp * 16))),
                                    capacity_log2=26 if a.capacity_log2 is None else a.capacity_log2)
         try:
+            shape = None
             for i in range(b, e):
-                tsdf.fuse(read_disparity_png(os.path.join(a.disparity_dir, names[i])), prm, pose=poses[i])
+                m = read_disparity_png(os.path.join(a.disparity_dir, names[i]))
+                shape = shape or m.shape
+                if a.render and m.shape != shape:
+                    sys.exit(f"fuse_map: --render needs maps of one size, but {names[i]} is {m.shape[1]} x {m.shape[0]}")
+                tsdf.fuse(m, prm, pose=poses[i])
             st = tsdf.stats()
+            if a.render and e > b:
+                os.makedirs(a.render, exist_ok=True)
+                n_near = 0
+                for i0 in range(b, e, RENDER_VIEWS):   # several views a call
+                    i1 = min(e, i0 + RENDER_VIEWS)
+                    views = tsdf.render(prm, shape, poses[i0:i1], max_depth=a.render_depth, min_weight=a.min_weight)
+                    near = views > DISP_PNG_MAX   # nearer than the files can say
+                    n_near += int(near.sum())
+                    views[near] = DISP_INVALID
+                    for i in range(i0, i1):
+                        write_disparity_png(os.path.join(a.render, names[i]), views[i - i0])
+                print(f"fuse_map: {e - b} views rendered to {a.render_depth} m ({n_near} pixels beyond 255.9 px left out) -> {a.render}")
             if a.mesh:
                 vertices, triangles = tsdf.mesh(a.min_weight)
             else:

@@ -1,7 +1,7 @@
 """Cost of the opt-in TSDF map (viso_tsdf_*, viso_batch_fuse_tsdf) at 512 block-matching maps of 1241x376, default parameters
 (voxel 0.2 m, T = 3, min_disp16 16, 2^26 slots; the next capacity that holds the scene when that one overflows).
 
-  python tools/tsdf_bench.py [--frames N] [--reps N] [--capacity-log2 N] [--kernel-only] [--out FILE]
+  python tools/tsdf_bench.py [--frames N] [--reps N] [--capacity-log2 N] [--render-views N] [--kernel-only] [--out FILE]
 
 The pairs and poses are those of tools/map_bench.py: 17 seeded synthetic frames repeated, frame t seen from a camera that has moved
 0.8 t m forward and turned 0.002 t rad.  Legs (host clock around work that ends in a synchronise, medians of alternating
@@ -12,9 +12,13 @@ repetitions):
   surface      TsdfMap.surface(): two passes of three probes a voxel, the copy, the sort on the host;
   mesh         TsdfMap.mesh() over the same table: the extraction twice (count, list), each two passes of seven probes a voxel, the
                copies, the two sorts and the resolution of the triangles' references on the host;
+  render       TsdfMap.render of --render-views views of the maps' size at fusing poses spread evenly over the sequence, max_depth
+               40 m, min_weight 2, one call: the launch, the copy of the views to the host and the free (time per view = / views).
+               The marching rate is counted from the result: a pixel with a hit at depth zs has marched ceil(zs / h) samples, one
+               without a hit all N = 400;
   clear        viso_tsdf_clear.
 n_updates / n_points from viso_tsdf_stats is the number of voxels a pixel's band touches.  --kernel-only runs clear + fuse_tsdf
---reps times and the extractions once: the run to put under `rocprofv3 --kernel-trace --stats` for the kernels' own times.  The
+--reps times and the extractions and the render once: the run to put under `rocprofv3 --kernel-trace --stats` for the kernels' own times.  The
 count the result is held against (not a measurement) is printed with it."""
 import argparse
 import json
@@ -44,6 +48,7 @@ def main():
     ap.add_argument("--frames", type=int, default=512)
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--capacity-log2", type=int, default=26)
+    ap.add_argument("--render-views", type=int, default=16)
     ap.add_argument("--kernel-only", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -79,22 +84,34 @@ def main():
             if "-4" not in str(e) or log2 == 28:
                 raise
 
+    views = poses[np.linspace(0, nf - 1, max(1, min(a.render_views, nf))).astype(int)]
+
+    def render():
+        return tsdf.render(seq["param"], (rows, cols), views, max_depth=40.0, min_weight=2)
+
+    def marched(d16):
+        """Samples marched for the views d16, counted from the result (see above)."""
+        h, N = tsdf.voxel * 0.5, int(np.floor(40.0 / (tsdf.voxel * 0.5)))
+        valid = d16 != -16
+        zs = seq["param"].f * seq["param"].base / (np.where(valid, d16, 16).astype(np.float64) / 16.0)
+        return int(np.where(valid, np.minimum(np.ceil(zs / h), N), N).sum()), float(valid.mean())
+
     if a.kernel_only:
         ms = []
         for _ in range(a.reps):
             tsdf.clear()
             ms.append(clock(lambda: b.fuse_tsdf(tsdf, poses)))
         res = {"frames": nf, "fuse_tsdf_ms": ms, "voxels": int(len(tsdf.entries())), "crossings": int(len(tsdf.surface())),
-               "triangles": int(len(tsdf.mesh()[1]))}
+               "triangles": int(len(tsdf.mesh()[1])), "render_views": int(len(views)), "render_valid": marched(render())[1]}
         print(json.dumps(res))
         tsdf.close(); b.close(); ctx.close()
         return
 
     vmap = libviso_amd.VoxelMap(ctx, capacity_log2=26)
     for _ in range(2):   # warm-up
-        tsdf.clear(); b.fuse_tsdf(tsdf, poses); tsdf.entries(); tsdf.surface(); tsdf.mesh()
+        tsdf.clear(); b.fuse_tsdf(tsdf, poses); tsdf.entries(); tsdf.surface(); tsdf.mesh(); render()
         vmap.clear(); b.fuse_disparities(vmap, poses)
-    legs = {k: [] for k in ("fuse_tsdf", "fuse_map", "entries", "surface", "mesh", "clear")}
+    legs = {k: [] for k in ("fuse_tsdf", "fuse_map", "entries", "surface", "mesh", "render", "clear")}
     for _ in range(a.reps):   # alternating
         legs["clear"].append(clock(tsdf.clear))
         legs["fuse_tsdf"].append(clock(lambda: b.fuse_tsdf(tsdf, poses)))
@@ -103,6 +120,7 @@ def main():
         legs["entries"].append(clock(tsdf.entries))
         legs["surface"].append(clock(tsdf.surface))
         legs["mesh"].append(clock(tsdf.mesh))
+        legs["render"].append(clock(render))
     st, n_vox, n_cross = tsdf.stats(), len(tsdf.entries()), len(tsdf.surface())
     n_vert, n_tri = (len(x) for x in tsdf.mesh())
     res = {"frames": nf, "shape": [int(rows), int(cols)], "params": "voxel 0.2, T 3, min_disp16 16", "capacity_log2": log2, "reps": a.reps,
@@ -110,6 +128,10 @@ def main():
            "stats": st, "voxels": int(n_vox), "crossings": int(n_cross), "vertices": int(n_vert), "triangles": int(n_tri), "updates_per_point": st["n_updates"] / max(1, st["n_points"]),
            "map_stats": vmap.stats()}
     res["count_bytes"], res["count_ms"] = count_ms(nf, rows, cols)
+    n_marched, valid = marched(render())
+    ms = res["ms_median"]["render"]
+    res["render"] = {"views": int(len(views)), "max_depth": 40.0, "min_weight": 2, "valid": valid, "ms_per_view": ms / len(views),
+                     "samples_marched": n_marched, "samples_per_s": n_marched / (ms * 1e-3)}
     print(json.dumps(res))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
