@@ -104,10 +104,16 @@ __global__ __launch_bounds__(256) void extract_pack_kernel(const ImageView* __re
     float2 pl = make_float2(0.f, 0.f);
     if (lane < nk) pl = I.skp[j0 + lane];
     int px[VISO_EXT_KPW], py[VISO_EXT_KPW];
+    // A keypoint more than 5 pixels outside the image has no element with an in-image centre (all zeros) and its window reads
+    // nothing, so coordinates are clamped to [-16, len + 16] before the conversion: the result is the same, and no
+    // expression below (px + ex - 5, py - 6 + wy, ...) can overflow for a huge, saturated or non-finite coordinate.
+    const float xhi = (float)cols + 16.f, yhi = (float)rows + 16.f;
 #pragma unroll
     for (int k = 0; k < VISO_EXT_KPW; ++k) {
-        px[k] = (int)rintf(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(pl.x), k)));   // Point2i p = kp.pt, src/viso.cpp:1013
-        py[k] = (int)rintf(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(pl.y), k)));
+        const float fx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pl.x), k));
+        const float fy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pl.y), k));
+        px[k] = (int)rintf(fminf(fmaxf(fx, -16.f), xhi));   // Point2i p = kp.pt, src/viso.cpp:1013
+        py[k] = (int)rintf(fminf(fmaxf(fy, -16.f), yhi));
     }
     // window pixel t of keypoint k: image pixel (py - 6 + t / 13, px - 6 + t % 13), coordinates reflected
     unsigned char w[VISO_EXT_KPW][3];
@@ -120,7 +126,7 @@ __global__ __launch_bounds__(256) void extract_pack_kernel(const ImageView* __re
             if (k < nk && t < VISO_EXT_WIN * VISO_EXT_WIN) {
                 const int wy = t / VISO_EXT_WIN, wx = t - wy * VISO_EXT_WIN;
                 const int ry = py[k] - 6 + wy, rx = px[k] - 6 + wx;
-                if (px[k] >= 6 && py[k] >= 6 && px[k] + 6 < cols && py[k] + 6 < rows) {   // wave uniform: the whole window inside the image
+                if (px[k] >= 6 && py[k] >= 6 && px[k] < cols - 6 && py[k] < rows - 6) {   // wave uniform: the whole window inside the image (no px + 6: it overflows for a saturated px)
                     w[k][u] = im[(uint32_t)(ry * cols + rx)];
                 } else if (ry >= 0 && ry <= rows && rx >= 0 && rx <= cols) {
                     // only neighbours of in-image centres (0 < y < rows, 0 < x < cols) are ever read: rows 0..rows,
