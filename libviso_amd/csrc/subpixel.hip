@@ -218,7 +218,8 @@ __global__ __launch_bounds__(SUBPIX_THREADS) void subpixel_refine_kernel(SubpixA
         for (int m = 0; m < 5; ++m) tot[m] = (m >= 3 && !vert) ? 0 : (int)subpix_row_sum(S[m]);   // <= 121 * 2040: exact in 32 bits
         if (act && l == 15) {
             const float u = (float)((double)qxf + subpix_off(tot[0], tot[1], tot[2]));
-            const float v = vert ? (float)((double)qyf + subpix_off(tot[3], tot[1], tot[4])) : qyf;
+            // q is an integer in the header: rintf gives -0 for a keypoint in [-0.5, -0], and + 0.f makes it the +0 of mode 2
+            const float v = vert ? (float)((double)qyf + subpix_off(tot[3], tot[1], tot[4])) : qyf + 0.f;
             a.uv[(size_t)t * a.cap + r] = make_float2(u, v);
         }
         subpix_wave_sync();   // the next rows' staging rewrites s_r / s_sob

@@ -52,7 +52,7 @@ def refine(oracle, imgL, imgR, kp1, kp2, match, mode=1):
     if mode == 2:
         uv[:, 1] = (q[:, 1] + parabola_offset(Sy[:, 0], Sy[:, 1], Sy[:, 2])).astype(np.float32)
     else:
-        uv[:, 1] = q[:, 1].astype(np.float32)
+        uv[:, 1] = (q[:, 1] + 0.0).astype(np.float32)    # q is an integer: a keypoint in [-0.5, -0] gives +0, never -0
     return uv
 
 
