@@ -106,8 +106,20 @@ def render(entries, voxel, param, shape, pose=None, max_depth=40.0, min_weight=2
     return out_d.reshape(rows, cols), out_w.reshape(rows, cols)
 
 
-def render_loop(entries, voxel, param, shape, pose=None, max_depth=40.0, min_weight=2):
-    """The same, one pixel and one sample at a time, in Python floats and ints over a dict."""
+EVENTS = ("gap", "first_negative", "negative_after_unusable", "negative_after_negative", "backface", "front_sum_zero",
+          "zero_after_positive", "underweight", "hit", "hit_too_big", "hit_too_small", "hit_behind")
+
+
+def render_loop(entries, voxel, param, shape, pose=None, max_depth=40.0, min_weight=2, trace=None):
+    """The same, one pixel and one sample at a time, in Python floats and ints over a dict.
+
+    trace: a collections.Counter that counts, over all pixels, what the rule met (EVENTS); the results do not depend on it.
+    Per sample: gap (step 3, also where a whole ray is gaps).  Per voxel entered (step 4): underweight (in the table, below
+    min_weight); for a usable voxel with sum < 0: first_negative (no previous voxel), negative_after_unusable (the previous voxel is
+    absent or underweight), negative_after_negative, or hit; for a usable voxel with sum >= 0 after a usable one: backface (the
+    previous sum < 0) or, with sum == 0, zero_after_positive (the previous sum >= 0: no hit, only sum < 0 is behind the surface).
+    Per hit: front_sum_zero (sum_a == 0), and of an invalid value (step 8) hit_behind (!(zs > 0)), else hit_too_big (v >= 32768),
+    else hit_too_small (!(v >= 1))."""
     e = np.asarray(entries, ENTRY)
     table = {int(key): (int(w), int(q)) for key, w, q in zip(keys_of(e["k"]), e["weight"], e["sum"])}
     rows, cols = shape
@@ -135,6 +147,8 @@ def render_loop(entries, voxel, param, shape, pose=None, max_depth=40.0, min_wei
                 quo = [v / s for v in Q]
                 if not all(math.isfinite(v) for v in quo) or any(abs(math.floor(v)) >= RANGE for v in quo):
                     prev = None
+                    if trace is not None:
+                        trace["gap"] += 1
                     continue
                 k = [math.floor(v) >> 10 for v in quo]
                 key = ((k[0] + BIAS) << 42) | ((k[1] + BIAS) << 21) | (k[2] + BIAS)
@@ -142,7 +156,11 @@ def render_loop(entries, voxel, param, shape, pose=None, max_depth=40.0, min_wei
                     continue
                 w, q = table.get(key, (0, 0))
                 if w < min_weight:
+                    if trace is not None and w:
+                        trace["underweight"] += 1
                     w = 0
+                if trace is not None and w:
+                    _trace_voxel(trace, q, prev)
                 if w and q < 0 and prev is not None and prev[2] and prev[3] >= 0:
                     za, zb = depth(prev[1]), depth(k)
                     da, db = float(prev[3]) / float(prev[2]), float(q) / float(w)
@@ -155,9 +173,31 @@ def render_loop(entries, voxel, param, shape, pose=None, max_depth=40.0, min_wei
                     if zs > 0 and v >= 1.0 and not v >= 32768.0:
                         out_d[y, x] = math.floor(v)
                         out_w[y, x] = min(prev[2], w)
+                    elif trace is not None:
+                        trace["hit_behind" if not zs > 0 else "hit_too_big" if v >= 32768.0 else "hit_too_small"] += 1
                     break
                 prev = (key, k, w, q)
     return out_d, out_w
+
+
+def _trace_voxel(trace, q, prev):
+    """The event of a usable voxel of sum q that follows prev (None, or (key, k, weight or 0, sum)) in a ray's sequence."""
+    if q < 0:
+        if prev is None:
+            trace["first_negative"] += 1
+        elif not prev[2]:
+            trace["negative_after_unusable"] += 1
+        elif prev[3] < 0:
+            trace["negative_after_negative"] += 1
+        else:
+            trace["hit"] += 1
+            if prev[3] == 0:
+                trace["front_sum_zero"] += 1
+    elif prev is not None and prev[2]:
+        if prev[3] < 0:
+            trace["backface"] += 1
+        elif q == 0:
+            trace["zero_after_positive"] += 1
 
 
 # ---- the scenes of the render tests: maps a camera at the fusing pose measures, and what a perfect renderer gives elsewhere ----------

@@ -17,6 +17,7 @@ import disparity_ref as DR
 import mesh_ref as MR
 import tsdf_ref as R
 from test_gpu_tsdf import POSE, _mixed_map
+from tsdf_tables import random_block as _random_block
 
 pytestmark = pytest.mark.gpu
 
@@ -52,23 +53,6 @@ def _check(tsdf, entries, tag, min_weights=(1,)):
         assert _same(v, wv), (tag, mw)
         n += len(t)
     return n
-
-
-def _random_block(rng, n=9, origin=-4, occupancy=0.7, trunc=3):
-    g = np.stack(np.meshgrid(*[np.arange(n)] * 3, indexing="ij"), axis=-1).reshape(-1, 3) + origin
-    g = g[rng.random(len(g)) < occupancy]
-    e = np.zeros(len(g), TSDF_ENTRY_DTYPE)
-    e["k"] = g
-    e["weight"] = rng.integers(1, 4, len(g))
-    lim = trunc * 1024
-    q = rng.integers(-lim, lim + 1, len(g))
-    special = rng.integers(0, 8, len(g))
-    q = np.where(special == 0, 0, np.where(special == 1, lim, np.where(special == 2, -lim, q)))
-    e["sum"] = q * e["weight"].astype(np.int64)
-    # sums that are no multiple of the weight: the mean is not an integer
-    odd = (e["weight"] > 1) & (np.abs(e["sum"]) < lim) & (special > 4)
-    e["sum"][odd] += 1
-    return e[np.argsort(R.keys_of(e["k"]))]
 
 
 def test_sphere_through_add_entries(viso):

@@ -12,6 +12,7 @@ from libviso_amd.abi import TSDF_ENTRY_DTYPE, Param
 
 import render_ref as RR
 import tsdf_ref as R
+import tsdf_tables as TT
 from estimator_util import kernel_resources
 
 INV = R.INVALID
@@ -48,6 +49,88 @@ def test_the_two_restatements_agree(shape):
                 assert ((a[0] == INV) == (a[1] == 0)).all()
                 n_valid += int((a[0] != INV).sum())
     assert n_valid > 0
+
+
+def _both(case, tag, untraced=False):
+    """The case by both restatements: equal bytes; (disparity, weight, trace).  untraced: also by the loop without a trace."""
+    a = RR.render(*case)
+    d, w, trace = TT.events(case)
+    assert a[0].dtype == d.dtype == np.int16 and a[1].dtype == w.dtype == np.uint32
+    assert a[0].tobytes() == d.tobytes() and a[1].tobytes() == w.tobytes(), tag
+    assert ((d == INV) == (w == 0)).all() and set(trace) <= set(RR.EVENTS)
+    if untraced:                                       # the trace changes nothing
+        plain = RR.render_loop(*case)
+        assert plain[0].tobytes() == d.tobytes() and plain[1].tobytes() == w.tobytes()
+    return d, w, trace
+
+
+def test_hand_built_tables_are_what_they_claim():
+    """The cases of tests/tsdf_tables.py that aim at one event each (tests/test_gpu_render_edges.py runs them on the device)."""
+    seen = {}
+    for name, (fn, event) in TT.SMALL_CASES.items():
+        d, w, trace = _both(fn(), name, untraced=True)
+        print(f"{name}: {(d != INV).mean():.3f} valid, {dict(trace)}")
+        assert trace[event] > 0, (name, dict(trace))
+        seen[name] = (d, w, trace)
+    d, w, t = seen["too_big"]
+    assert (d == INV).all() and t["hit_too_big"] == t["hit"] == d.size == 45
+    d, w, t = seen["too_big_alone"]
+    assert (d == 3034).all() and (w == 2).all() and t["hit"] == 45 and t["hit_too_big"] == 0
+    d, w, t = seen["too_small"]
+    assert (d == INV).all() and t["hit_too_small"] == t["hit"] == 45
+    d, w, t = seen["behind"]
+    assert 0 < t["hit_behind"] < t["hit"] and (d != INV).any() and (d == INV).any()
+    d, w, t = seen["gap_in"]
+    assert (d == 7349).all() and t["gap"] == 45 * 12 and t["hit"] == 45                 # 0.3 m of gaps, a sample every 0.025 m
+    d, w, t = seen["gap_out"]
+    assert t["hit"] == (d != INV).sum() > 0 and (d[d != INV] == 13973).all() and (d == INV).any()
+    assert t["gap"] == (d == INV).sum() * 81                                            # from 1 m to 3 m: samples 40 .. 120
+    d, w, t = seen["gap_beside"]
+    assert (d == INV).all() and t["hit"] == 0 and t["gap"] > 0 and set(t) == {"gap"}
+    d, w, t = seen["weights_and_means"]
+    assert set(np.unique(w).tolist()) == {0, 1, 2, 3, TT.BIG} and len(np.unique(d[d != INV])) >= 5
+
+
+def test_random_block_sweeps_reach_every_event():
+    """Every view of the two sweeps is between 5 % and 95 % valid, and over them every event of a ray through an irregular table
+    occurs; first_negative only where the camera is inside the block."""
+    total = {}
+    for name in TT.BLOCKS:
+        shares = []
+        for pose, mw, case in TT.block_sweep(name):
+            d, w, trace = _both(case, (name, pose, mw))
+            shares.append(round(float((d != INV).mean()), 3))
+            assert 0.05 <= shares[-1] <= 0.95, (name, pose, mw, shares[-1])
+            assert (w[d != INV] >= mw).all()
+            for k, v in trace.items():
+                total[k] = total.get(k, 0) + v
+            assert (trace["first_negative"] > 0) == (name == "inside")
+        print(f"{name}: valid shares {shares}")
+    print(total)
+    for k in TT.BLOCK_EVENTS:
+        assert total.get(k, 0) > 0, (k, total)
+    for k in ("gap", "hit_too_big", "hit_too_small", "hit_behind"):
+        assert total.get(k, 0) == 0
+    for mw in TT.BLOCK_MIN_WEIGHTS:
+        d, w, trace = _both(TT.chains_view(mw), ("chains", mw))
+        assert 0.05 <= (d != INV).mean() <= 0.95 and trace["hit"] > 0
+
+
+def test_table_builders():
+    e = TT.slab(7, half=3, weight=2)
+    assert len(e) == 2 * 36 and (np.diff(R.keys_of(e["k"])) > 0).all() and (e["weight"] == 2).all()
+    assert (e["sum"][e["k"][:, 2] == 7] == 600).all() and (e["sum"][e["k"][:, 2] == 8] == -1000).all()
+    assert e["k"][:, :2].min() == -3 and e["k"][:, :2].max() == 2
+    a = TT.random_block(np.random.default_rng(9), origin=-4)
+    b = TT.random_block(np.random.default_rng(9), origin=(-4, -4, -4))
+    c = TT.random_block(np.random.default_rng(9), origin=(-4, 0, 3))
+    assert a.tobytes() == b.tobytes() and len(a) == len(c) == 508
+    assert np.array_equal(np.sort(c["k"] - (0, 4, 7), axis=0), np.sort(a["k"], axis=0))
+    assert [len(R.crossings(a, mw)) for mw in (1, 2, 3)] == [485, 226, 47]
+    lim = 3 * 1024 * a["weight"].astype(np.int64)
+    assert (np.abs(a["sum"]) <= lim).all() and (a["sum"] == 0).any() and (a["sum"] == lim).any() and (a["sum"] == -lim).any()
+    top = TT.crossing_block("top")
+    assert ((top["k"] == R.BIAS - 1).any(axis=1)).sum() == 158
 
 
 def test_fronto_parallel_wall_comes_back():
