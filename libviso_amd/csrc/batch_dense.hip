@@ -62,13 +62,12 @@ int dense_preflight(viso_batch* b, const char* where) {
         viso_set_error("%s: dense disparity of %d-column images is beyond this build (2048 at most)", where, b->img_cols);
         return VISO_ERR_UNSUPPORTED;
     }
-    if (D.sgm_on && sgm_group_frames(b->img_rows, b->img_cols, D.sgm_p.num_disp, b->nf) < 1)
-        return sgm_nomem(where, b->img_rows, b->img_cols, D.sgm_p.num_disp);
+    if (D.sgm_on) VISO_TRY(sgm_group_frames(where, b->img_rows, b->img_cols, D.sgm_p.num_disp, b->nf, nullptr));
     if (D.speckle() && !speckle_geometry_ok(b->img_rows, b->img_cols)) {
         viso_set_error("%s: the speckle filter of %d x %d maps is beyond this build (2^31 - 1 pixels)", where, b->img_rows, b->img_cols);
         return VISO_ERR_UNSUPPORTED;
     }
-    if (D.speckle() && speckle_group_frames(b->img_rows, b->img_cols, b->nf) < 1) return speckle_nomem(where, b->img_rows, b->img_cols);
+    if (D.speckle()) VISO_TRY(speckle_group_frames(where, b->img_rows, b->img_cols, b->nf, nullptr));
     return VISO_OK;
 }
 
@@ -76,8 +75,8 @@ int dense_preflight(viso_batch* b, const char* where) {
 // on with max_size > 0), group by group through the batch's workspace.
 static int launch_batch_speckle(viso_batch* b, const char* where) {
     BatchDense& D = b->dense;
-    const int group = speckle_group_frames(b->img_rows, b->img_cols, b->nf);
-    if (group < 1) return speckle_nomem(where, b->img_rows, b->img_cols);   // the cap moved since dense_preflight
+    int group;
+    VISO_TRY(speckle_group_frames(where, b->img_rows, b->img_cols, b->nf, &group));   // fails when the cap moved since dense_preflight
     VISO_TRY(b->fit(&D.spk_ws, &D.spk_ws_bytes, speckle_frame_bytes(b->img_rows, b->img_cols) * (size_t)group, false, where,
                     "speckle workspace (viso_speckle_set_workspace_cap)"));
     return launch_speckle(b->ctx->stream, D.disp, (size_t)b->img_rows * b->img_cols, b->img_rows, b->img_cols, b->nf, &D.spk_p, D.spk_ws, group);
@@ -92,8 +91,8 @@ int launch_batch_disparity(viso_batch* b, const char* where) {
     VISO_TRY(b->fit(&D.disp, &D.disp_bytes, sizeof(int16_t) * per * (size_t)b->nf));
     D.rows = b->img_rows; D.cols = b->img_cols;
     if (D.sgm_on) {   // the same maps by semi-global matching, group by group through the batch's workspace
-        const int group = sgm_group_frames(b->img_rows, b->img_cols, D.sgm_p.num_disp, b->nf);
-        if (group < 1) return sgm_nomem(where, b->img_rows, b->img_cols, D.sgm_p.num_disp);   // the cap moved since dense_preflight
+        int group;
+        VISO_TRY(sgm_group_frames(where, b->img_rows, b->img_cols, D.sgm_p.num_disp, b->nf, &group));   // fails when the cap moved since dense_preflight
         VISO_TRY(b->fit(&D.sgm_ws, &D.sgm_ws_bytes, sgm_frame_bytes(b->img_rows, b->img_cols, D.sgm_p.num_disp) * (size_t)group, false, where,
                         "SGM workspace (viso_sgm_set_workspace_cap)"));
         VISO_TRY(launch_sgm(b->ctx->stream, b->images, 2 * per, per, b->img_rows, b->img_cols, b->nf, &D.sgm_p, D.disp, per, D.sgm_ws, group));

@@ -386,9 +386,9 @@ extern "C" int viso_match_circle(const int32_t* lr, int n_lr, const int32_t* lr_
     a.n_lr = n_lr; a.n_lrp = n_lrp; a.n11 = n11; a.n22 = n22; a.cap = cap;
     char *dout, *hout; int* dtab;
     const size_t out_bytes = 256 + sizeof(int) * 6 * (size_t)cap;
-    if ((r = ctx_scratch(c, PLAIN_SLOT_OUT, out_bytes, (void**)&dout)) < 0) return r;
+    if ((r = ctx_scratch(c, SLOT_PLAIN_OUT, out_bytes, (void**)&dout)) < 0) return r;
     if ((r = ctx_pinned(c, 1, out_bytes, &hout)) < 0) return r;
-    if ((r = ctx_scratch(c, 16, sizeof(int) * 3 * (size_t)(tabn + 1), (void**)&dtab)) < 0) return r;
+    if ((r = ctx_scratch(c, SLOT_CIRCLE_TAB, sizeof(int) * 3 * (size_t)(tabn + 1), (void**)&dtab)) < 0) return r;
     a.out_n = reinterpret_cast<int*>(dout); a.rows = reinterpret_cast<int*>(dout + 256);
     if ((r = in.flush(c->stream)) < 0) return r;
     pp.mark(1);

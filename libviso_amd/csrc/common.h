@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <atomic>
 
 #include "../../include/viso_hip.h"
 
@@ -107,6 +108,28 @@ struct SolverParamsDev {         // viso_param, device copy
     int ransac_iter, _pad;
 };
 
+// The scratch blocks of the DEFAULT context (ctx_scratch), shared by the plain family and the direct calls.  Every user holds
+// PlainLock and issues ALL its work on the context's stream, and a block is regrown only behind a synchronize of that stream: a
+// slot's users are ordered by the stream -- behind a frame's RANSAC stage that runs on after its call returned, too -- so a call may
+// use any slot for contents that need not outlive it.  zero_new promises zeros at (re)allocation and nothing more: its user hands
+// the block back zeroed and relies on finding it so, which is why SLOT_RANSAC_QUEUE must not be borrowed.
+enum ScratchSlot {
+    SLOT_GEN0 = 0, SLOT_GEN1, SLOT_GEN2,   // general: a direct call's staged inputs and outputs, any element type
+    SLOT_HARRIS_TMP_RESP,                  // viso_detect_harris_binned: the bins' candidate responses
+    SLOT_HYP_WORDS,                        // per-hypothesis ints (ok_h, cnt_h) of the RANSAC chain and viso_support_sizes; the bins' counters
+    SLOT_HYP_TR,                           // the hypotheses' transforms tr_h; viso_detect_harris_binned: the kept keypoints
+    SLOT_GEN6,                             // viso_detect_harris_binned: the kept responses; viso_support_sizes: its SolverItem
+    SLOT_HARRIS_STRIPS,                    // viso_detect_harris_binned: the strip kernel's partial lists
+    SLOT_RANSAC_QUEUE,                     // zero_new: the undecided-hypothesis queue, left zeroed by every chain (launch_ransac)
+    SLOT_RANSAC_ROT,                       // the hypotheses' rotation block (SolverItem::rot)
+    SLOT_UNUSED10, SLOT_UNUSED11, SLOT_UNUSED12, SLOT_UNUSED13,   // no user (kept: the numbering of the others stays)
+    SLOT_PLAIN_IN, SLOT_PLAIN_OUT,         // PlainStage's device mirror; a plain-family call's result block
+    SLOT_CIRCLE_TAB,                       // the circle / RANSAC-stage join table (launch_circle_table)
+    SLOT_SUBPIX_IMG, SLOT_SUBPIX_KP, SLOT_SUBPIX_LIST, SLOT_SUBPIX_UV,   // viso_refine_stereo_subpixel
+    SLOT_RECT_RAW, SLOT_RECT_OUT, SLOT_RECT_MAP,                          // viso_rectify_images
+    SLOT_COUNT
+};
+
 struct viso_ctx {
     int device;
     hipStream_t stream;
@@ -119,9 +142,9 @@ struct viso_ctx {
     // streams onto a handful of hardware queues, and two busy RANSAC streams that land on one queue serialise
     // (measured: 9 streams for 3 busy batches -> two chains on one queue, 0.43 -> 0.68 ms per step).
     hipStream_t solver_stream;
-    // grow-only scratch for the plain (host-pointer) family
-    void* scratch[24];
-    size_t scratch_bytes[24];
+    // grow-only scratch for the plain (host-pointer) family, one block per ScratchSlot
+    void* scratch[SLOT_COUNT];
+    size_t scratch_bytes[SLOT_COUNT];
     // pinned staging of the plain family (grow-only): [0] a call's inputs, packed back to back and sent with ONE
     // host-to-device copy; [1] a call's results, fetched with ONE device-to-host copy behind ONE synchronize
     char* pin[2];
@@ -152,7 +175,7 @@ struct PlainProf {
     void wait_end();
     int fn; hipStream_t s; bool on; int marks; double t0, tw, wait;
 };
-int ctx_scratch(viso_ctx* c, int slot, size_t bytes, void** out, bool zero_new = false);   // zero_new: a block that is (re)allocated starts zeroed
+int ctx_scratch(viso_ctx* c, ScratchSlot slot, size_t bytes, void** out, bool zero_new = false);   // zero_new: a block that is (re)allocated starts zeroed
 static inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }   // offsets of the pieces of a scratch block
 int ctx_pinned(viso_ctx* c, int which, size_t bytes, char** out);
 void plain_cache_free(viso_ctx* c);   // plain.hip; from viso_ctx_destroy
@@ -185,11 +208,29 @@ struct CircleArgs {
 int launch_circle_table(hipStream_t s, const CircleArgs& a, int* tab, int tabn);
 viso_ctx* viso_default_ctx();
 
+// One direct call: a batch stage's kernel on host pointers, on the default context (ctx.hip).  Declared behind the argument checks
+// and the early VISO_OK returns, which touch no device.  An error return must not leave work in flight (plain_quiesce, plain.hip):
+// copies into or out of the caller's memory may be queued on s, and the scratch blocks they use are the next caller's.  So the
+// destructor waits for s, before it gives the lock back, unless the last thing the call did was a wait() that succeeded.
+struct __attribute__((visibility("hidden"))) DirectCall {
+    viso_ctx* c = nullptr; hipStream_t s = nullptr;
+    DirectCall() = default;
+    DirectCall(const DirectCall&) = delete;
+    ~DirectCall();
+    int begin();   // PlainLock's mutex, the default context (none: VISO_ERR_HIP, viso_ctx_create's message stays), hipSetDevice
+    template <class T> int scratch(ScratchSlot slot, size_t count, T** out, bool zero_new = false) { return ctx_scratch(c, slot, sizeof(T) * count, (void**)out, zero_new); }
+    // count elements of the HOST pointer's type, on s; count 0 copies nothing
+    template <class T> int up(void* dst_dev, const T* src_host, size_t count) { return copy(dst_dev, src_host, sizeof(T) * count, hipMemcpyHostToDevice); }
+    template <class T> int down(T* dst_host, const void* src_dev, size_t count) { return copy(dst_host, src_dev, sizeof(T) * count, hipMemcpyDeviceToHost); }
+    int wait();    // hipStreamSynchronize(s): the results are in the caller's memory
+private:
+    int copy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind);
+    bool locked = false, in_flight = false;
+};
+
 // One plain-family call's inputs: appended to the context's pinned block (256-B aligned pieces), mirrored at the same
 // offsets in one device block, sent with ONE hipMemcpyAsync.  A pageable hipMemcpyAsync costs 5-10 us of host time
 // per call whatever its size; the plain family used to issue 4-7 of them per function (tools/h2d_probe.hip).
-#define PLAIN_SLOT_IN 14      // ctx_scratch slots of the staging blocks
-#define PLAIN_SLOT_OUT 15
 struct PlainStage {
     char* h = nullptr; char* d = nullptr; size_t off = 0, cap = 0;
     static size_t need(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
@@ -197,7 +238,7 @@ struct PlainStage {
         cap = bytes; off = 0;
         int r = ctx_pinned(c, 0, bytes, &h);
         if (r < 0) return r;
-        return ctx_scratch(c, PLAIN_SLOT_IN, bytes, (void**)&d);
+        return ctx_scratch(c, SLOT_PLAIN_IN, bytes, (void**)&d);
     }
     template <class T> T* put(const T* src, size_t count) {   // returns the DEVICE address
         const size_t b = sizeof(T) * count;
@@ -463,24 +504,38 @@ bool disparity_params_ok(const viso_disparity_params* p);
 bool disparity_geometry_ok(int rows, int cols);   // cols within what the kernel handles
 int launch_disparity(hipStream_t s, const uint8_t* img, size_t fs, size_t ss, int rows, int cols, int n_frames,
                      const viso_disparity_params* p, int16_t* out, size_t ofs);
+// The cap on a dense feature's workspace (sgm.hip, speckle.hip): the frames go through it in groups of as many as fit under the cap
+struct __attribute__((visibility("hidden"))) WorkspaceCap {
+    std::atomic<size_t> cap; size_t dflt; const char *what, *setter;   // what, setter: for the message
+    void set(size_t bytes) { cap.store(bytes ? bytes : dflt); }         // 0: back to the default
+    // *group (or null) = how many of n_frames frames of frame_bytes each fit, at most max_group; not even one: VISO_ERR_NOMEM
+    int frames(const char* where, int rows, int cols, size_t frame_bytes, int n_frames, size_t max_group, int* group) {
+        size_t g = cap.load() / frame_bytes;
+        if (g < 1) {
+            viso_set_error("%s: one %d x %d frame needs %zu bytes of %s workspace, more than the cap (%s)", where, rows, cols, frame_bytes, what, setter);
+            return VISO_ERR_NOMEM;
+        }
+        if (g > max_group) g = max_group;
+        if (group) *group = (int)(g < (size_t)n_frames ? g : (size_t)n_frames);
+        return VISO_OK;
+    }
+};
 // sgm.hip: the opt-in semi-global matching (viso_batch_set_sgm); images and maps addressed as in launch_disparity.  The frames go
-// through the workspace ws in groups of `group` (>= 1) frames: ws holds group * sgm_frame_bytes.  sgm_group_frames: how many of
-// n_frames frames fit the workspace cap (0: not even one)
+// through the workspace ws in groups of `group` (>= 1) frames: ws holds group * sgm_frame_bytes.  sgm_group_frames: *group (or null)
+// = how many of n_frames frames fit the workspace cap; not even one: VISO_ERR_NOMEM, the error text names `where`
 bool sgm_params_ok(const viso_sgm_params* p);
 size_t sgm_frame_bytes(int rows, int cols, int D);
-int sgm_group_frames(int rows, int cols, int D, int n_frames);
-int sgm_nomem(const char* where, int rows, int cols, int D);   // sets the error text; returns VISO_ERR_NOMEM
+int sgm_group_frames(const char* where, int rows, int cols, int D, int n_frames, int* group);
 int launch_sgm(hipStream_t s, const uint8_t* img, size_t fs, size_t ss, int rows, int cols, int n_frames, const viso_sgm_params* p,
                int16_t* out, size_t ofs, void* ws, int group);
 // speckle.hip: the opt-in speckle filter of the maps (viso_batch_set_speckle), in place; frame f's map at map + f * mfs.  The frames
-// go through the workspace ws in groups of `group` (>= 1) frames: ws holds group * speckle_frame_bytes.  speckle_group_frames: how
-// many of n_frames frames fit the workspace cap (0: not even one).  launch_points: the reprojection of one device map; pose = the
-// first three rows of a 4 x 4 row-major matrix on the host, or null.
+// go through the workspace ws in groups of `group` (>= 1) frames: ws holds group * speckle_frame_bytes.  speckle_group_frames: as
+// sgm_group_frames.  launch_points: the reprojection of one device map; pose = the first three rows of a 4 x 4 row-major matrix
+// on the host, or null.
 bool speckle_params_ok(const viso_speckle_params* p);
 bool speckle_geometry_ok(int rows, int cols);   // cols as the methods, and rows * cols within the 32-bit labels
 size_t speckle_frame_bytes(int rows, int cols);
-int speckle_group_frames(int rows, int cols, int n_frames);
-int speckle_nomem(const char* where, int rows, int cols);   // sets the error text; returns VISO_ERR_NOMEM
+int speckle_group_frames(const char* where, int rows, int cols, int n_frames, int* group);
 int launch_speckle(hipStream_t s, int16_t* map, size_t mfs, int rows, int cols, int n_frames, const viso_speckle_params* p, void* ws,
                    int group);
 int launch_points(hipStream_t s, const int16_t* disp, int rows, int cols, double f, double cu, double cv, double base,
@@ -497,11 +552,11 @@ int tsdf_fuse_resident(const char* where, viso_tsdf* t, viso_ctx* c, const int16
 int launch_motion_cov(hipStream_t s, const SolverItem* items_dev, int n_items, const SolverParamsDev& sp, int mode, double sigma,
                       viso_motion_cov* out);
 bool motion_args_ok(int mode, double sigma_px);   // the estimators' mode 1, or mode 2 with a finite sigma_px > 0
-// The direct calls viso_pose_covariance / viso_pose_refine (inside a PlainLock): checks the arguments (the error names `where`),
-// then stages one SolverItem on the default context's stream -- X, obs, inl, tr, the words ok, n_inl, m, the item, then
-// rec_bytes for the record and extra_bytes for the caller's own buffers, in scratch slot 0.
+// The direct calls viso_pose_covariance / viso_pose_refine: checks the arguments (the error names `where`), then begins the
+// direct call dc and stages one SolverItem on its stream -- X, obs, inl, tr, the words ok, n_inl, m, the item, then
+// rec_bytes for the record and extra_bytes for the caller's own buffers, in SLOT_GEN0.
 struct PoseCall {
-    hipStream_t s;
+    DirectCall dc;
     SolverParamsDev sp;
     size_t ld;                 // max(m, 1): the item's row length
     const SolverItem* item;    // device

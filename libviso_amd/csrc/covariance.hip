@@ -270,17 +270,15 @@ int pose_call_stage(const char* where, const double* X, const double* obs, int m
                        where);
         return VISO_ERR_ARG;
     }
-    viso_ctx* c = viso_default_ctx();
-    if (!c) return VISO_ERR_HIP;
-    HIP_TRY(hipSetDevice(c->device));
+    DirectCall& dc = pc->dc;
+    VISO_TRY(dc.begin());
     const size_t ld = (size_t)(m > 0 ? m : 1);
     // one block: X [3][ld] | obs [4][ld] | inl [ld] | tr [6] | ok, n_inl, m | the item | the record | the caller's extra
     const size_t oX = 0, oO = al256(oX + sizeof(double) * 3 * ld), oI = al256(oO + sizeof(double) * 4 * ld),
                  oT = al256(oI + sizeof(int) * ld), oW = al256(oT + sizeof(double) * 6), oS = al256(oW + sizeof(int) * 4),
                  oR = al256(oS + sizeof(SolverItem)), oE = al256(oR + rec_bytes), bytes = al256(oE + extra_bytes);
     char* d;
-    int r;
-    if ((r = ctx_scratch(c, 0, bytes, (void**)&d)) < 0) return r;
+    VISO_TRY(dc.scratch(SLOT_GEN0, bytes, &d));
     SolverItem it;
     memset(&it, 0, sizeof(it));
     it.X = reinterpret_cast<double*>(d + oX); it.obs = reinterpret_cast<double*>(d + oO); it.ld = (int)ld;
@@ -288,16 +286,12 @@ int pose_call_stage(const char* where, const double* X, const double* obs, int m
     int* words = reinterpret_cast<int*>(d + oW);
     it.ok = words; it.n_inl = words + 1; it.m_ptr = words + 2;
     const int hw[4] = {1, n_inl, m, 0};
-    hipStream_t s = c->stream;
-    if (m > 0) {
-        HIP_TRY(hipMemcpyAsync(d + oX, X, sizeof(double) * 3 * (size_t)m, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d + oO, obs, sizeof(double) * 4 * (size_t)m, hipMemcpyHostToDevice, s));
-    }
-    if (n_inl > 0) HIP_TRY(hipMemcpyAsync(d + oI, inl, sizeof(int) * (size_t)n_inl, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + oT, tr, sizeof(double) * 6, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(words, hw, sizeof(hw), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + oS, &it, sizeof(it), hipMemcpyHostToDevice, s));
-    pc->s = s;
+    VISO_TRY(dc.up(d + oX, X, 3 * (size_t)m));
+    VISO_TRY(dc.up(d + oO, obs, 4 * (size_t)m));
+    VISO_TRY(dc.up(d + oI, inl, (size_t)n_inl));
+    VISO_TRY(dc.up(d + oT, tr, 6));
+    VISO_TRY(dc.up(words, hw, 4));
+    VISO_TRY(dc.up(d + oS, &it, 1));
     fill_solver_params(&pc->sp, param);
     pc->ld = ld;
     pc->item = reinterpret_cast<const SolverItem*>(d + oS);
@@ -308,14 +302,9 @@ int pose_call_stage(const char* where, const double* X, const double* obs, int m
 
 extern "C" int viso_pose_covariance(const double* X, const double* obs, int m, const double tr[6], const int32_t* inl, int n_inl,
                                     const viso_param* param, int mode, double sigma_px, viso_motion_cov* out) {
-    PlainLock lk;
     PoseCall pc;
-    int r;
-    if ((r = pose_call_stage("viso_pose_covariance", X, obs, m, tr, inl, n_inl, param, mode, sigma_px, out, sizeof(viso_motion_cov), 0,
-                             &pc)) < 0)
-        return r;
-    if ((r = launch_motion_cov(pc.s, pc.item, 1, pc.sp, mode, sigma_px, reinterpret_cast<viso_motion_cov*>(pc.rec))) < 0) return r;
-    HIP_TRY(hipMemcpyAsync(out, pc.rec, sizeof(viso_motion_cov), hipMemcpyDeviceToHost, pc.s));
-    HIP_TRY(hipStreamSynchronize(pc.s));
-    return VISO_OK;
+    VISO_TRY(pose_call_stage("viso_pose_covariance", X, obs, m, tr, inl, n_inl, param, mode, sigma_px, out, sizeof(viso_motion_cov), 0, &pc));
+    VISO_TRY(launch_motion_cov(pc.dc.s, pc.item, 1, pc.sp, mode, sigma_px, reinterpret_cast<viso_motion_cov*>(pc.rec)));
+    VISO_TRY(pc.dc.down(out, pc.rec, 1));
+    return pc.dc.wait();
 }

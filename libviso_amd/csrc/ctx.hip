@@ -130,7 +130,7 @@ extern "C" int viso_ctx_destroy(viso_ctx* c) {
     note(hipStreamSynchronize(c->stream));
     if (c->solver_stream) { note(hipStreamSynchronize(c->solver_stream)); note(hipStreamDestroy(c->solver_stream)); }
     plain_cache_free(c);
-    for (int i = 0; i < 24; ++i) if (c->scratch[i]) note(hipFree(c->scratch[i]));
+    for (int i = 0; i < SLOT_COUNT; ++i) if (c->scratch[i]) note(hipFree(c->scratch[i]));
     for (int i = 0; i < 2; ++i) if (c->pin[i]) note(hipHostFree(c->pin[i]));
     if (c->sig_flag) note(hipHostFree(c->sig_flag));
     if (c->sig_ctr) note(hipFree(c->sig_ctr));
@@ -219,7 +219,7 @@ extern "C" int viso_ctx_synchronize(viso_ctx* c) {
     return VISO_OK;
 }
 
-int ctx_scratch(viso_ctx* c, int slot, size_t bytes, void** out, bool zero_new) {
+int ctx_scratch(viso_ctx* c, ScratchSlot slot, size_t bytes, void** out, bool zero_new) {
     if (bytes < 256) bytes = 256;
     HIP_TRY(hipSetDevice(c->device));
     if (c->scratch_bytes[slot] < bytes) {
@@ -269,6 +269,25 @@ viso_ctx* viso_default_ctx() {
         g_default = viso_ctx_create(dev, nullptr);
     }
     return g_default;
+}
+
+int DirectCall::begin() {
+    g_call_mu.lock();   // PlainLock's mutex, held until the destructor
+    locked = true;
+    if (!(c = viso_default_ctx())) return VISO_ERR_HIP;
+    HIP_TRY(hipSetDevice(c->device));
+    s = c->stream;
+    in_flight = true;
+    return VISO_OK;
+}
+int DirectCall::copy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
+    if (bytes) { in_flight = true; HIP_TRY(hipMemcpyAsync(dst, src, bytes, kind, s)); }
+    return VISO_OK;
+}
+int DirectCall::wait() { HIP_TRY(hipStreamSynchronize(s)); in_flight = false; return VISO_OK; }
+DirectCall::~DirectCall() {
+    if (in_flight) (void)hipStreamSynchronize(s);   // an error return: nothing of this call stays queued (the error text is the first failure's)
+    if (locked) g_call_mu.unlock();
 }
 
 // ---- viso_plain_profile: where a plain-family call's time goes ---------------------------------------------------

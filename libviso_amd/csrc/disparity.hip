@@ -238,19 +238,14 @@ extern "C" int viso_stereo_disparity(const uint8_t* left, const uint8_t* right, 
         return VISO_ERR_UNSUPPORTED;
     }
     const size_t per = (size_t)rows * cols;
-    PlainLock lk;
-    viso_ctx* c = viso_default_ctx();
-    if (!c) return VISO_ERR_HIP;
-    HIP_TRY(hipSetDevice(c->device));
+    DirectCall dc;
+    VISO_TRY(dc.begin());
     uint8_t* dimg; int16_t* dout;
-    int r;
-    if ((r = ctx_scratch(c, 0, 2 * per, (void**)&dimg)) < 0) return r;
-    if ((r = ctx_scratch(c, 1, sizeof(int16_t) * per, (void**)&dout)) < 0) return r;
-    hipStream_t s = c->stream;
-    HIP_TRY(hipMemcpyAsync(dimg, left, per, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(dimg + per, right, per, hipMemcpyHostToDevice, s));
-    if ((r = launch_disparity(s, dimg, 2 * per, per, rows, cols, 1, params, dout, per)) < 0) return r;
-    HIP_TRY(hipMemcpyAsync(out, dout, sizeof(int16_t) * per, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return VISO_OK;
+    VISO_TRY(dc.scratch(SLOT_GEN0, 2 * per, &dimg));
+    VISO_TRY(dc.scratch(SLOT_GEN1, per, &dout));
+    VISO_TRY(dc.up(dimg, left, per));
+    VISO_TRY(dc.up(dimg + per, right, per));
+    VISO_TRY(launch_disparity(dc.s, dimg, 2 * per, per, rows, cols, 1, params, dout, per));
+    VISO_TRY(dc.down(out, dout, per));
+    return dc.wait();
 }

@@ -55,21 +55,18 @@ extern "C" int viso_extract_descriptors(const uint8_t* img, int rows, int cols, 
         return VISO_ERR_ARG;
     }
     if (n == 0) return VISO_OK;
-    PlainLock lk;
-    viso_ctx* c = viso_default_ctx();
-    if (!c) return VISO_ERR_HIP;
+    DirectCall dc;
+    VISO_TRY(dc.begin());
     const int side = 2 * radius + 1;
     uint8_t* dimg; float2* dkp; float* dd;
-    int r;
-    if ((r = ctx_scratch(c, 0, (size_t)rows * cols, (void**)&dimg)) < 0) return r;
-    if ((r = ctx_scratch(c, 1, sizeof(float2) * (size_t)n, (void**)&dkp)) < 0) return r;
-    if ((r = ctx_scratch(c, 2, sizeof(float) * (size_t)n * side * side, (void**)&dd)) < 0) return r;
-    HIP_TRY(hipMemcpyAsync(dimg, img, (size_t)rows * cols, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(dkp, kp, sizeof(float2) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    if ((r = launch_extract(c->stream, dimg, rows, cols, dkp, n, radius, dd)) < 0) return r;
-    HIP_TRY(hipMemcpyAsync(desc, dd, sizeof(float) * (size_t)n * side * side, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return VISO_OK;
+    VISO_TRY(dc.scratch(SLOT_GEN0, (size_t)rows * cols, &dimg));
+    VISO_TRY(dc.scratch(SLOT_GEN1, (size_t)n, &dkp));
+    VISO_TRY(dc.scratch(SLOT_GEN2, (size_t)n * side * side, &dd));
+    VISO_TRY(dc.up(dimg, img, (size_t)rows * cols));
+    VISO_TRY(dc.up(dkp, kp, 2 * (size_t)n));
+    VISO_TRY(launch_extract(dc.s, dimg, rows, cols, dkp, n, radius, dd));
+    VISO_TRY(dc.down(desc, dd, (size_t)n * side * side));
+    return dc.wait();
 }
 
 // ---------------------------------------------------------------------------

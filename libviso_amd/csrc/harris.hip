@@ -944,19 +944,16 @@ static int check_detect_args(int rows, int cols, int n_features, int nbinx, int 
 
 extern "C" int viso_harris_response(const uint8_t* img, int rows, int cols, double k, float* resp) {
     if (!img || !resp || rows <= 0 || cols <= 0) { viso_set_error("viso_harris_response: bad argument"); return VISO_ERR_ARG; }
-    PlainLock lk;
-    viso_ctx* c = viso_default_ctx();
-    if (!c) return VISO_ERR_HIP;
+    DirectCall dc;
+    VISO_TRY(dc.begin());
     uint8_t* dimg; float* dr;
-    int r;
     const size_t px = (size_t)rows * cols;
-    if ((r = ctx_scratch(c, 0, px, (void**)&dimg)) < 0) return r;
-    if ((r = ctx_scratch(c, 1, sizeof(float) * px, (void**)&dr)) < 0) return r;
-    HIP_TRY(hipMemcpyAsync(dimg, img, px, hipMemcpyHostToDevice, c->stream));
-    if ((r = launch_harris_response(c->stream, dimg, 1, rows, cols, k, dr)) < 0) return r;
-    HIP_TRY(hipMemcpyAsync(resp, dr, sizeof(float) * px, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return VISO_OK;
+    VISO_TRY(dc.scratch(SLOT_GEN0, px, &dimg));
+    VISO_TRY(dc.scratch(SLOT_GEN1, px, &dr));
+    VISO_TRY(dc.up(dimg, img, px));
+    VISO_TRY(launch_harris_response(dc.s, dimg, 1, rows, cols, k, dr));
+    VISO_TRY(dc.down(resp, dr, px));
+    return dc.wait();
 }
 
 extern "C" int viso_detect_harris_binned(const uint8_t* img, int rows, int cols, int n_features, int nbinx, int nbiny,
@@ -967,33 +964,31 @@ extern "C" int viso_detect_harris_binned(const uint8_t* img, int rows, int cols,
     *n_out = 0;
     const int nbins = nbinx * nbiny, per = n_features / nbins;
     if (per == 0) return VISO_OK;
-    PlainLock lk;
-    viso_ctx* c = viso_default_ctx();
-    if (!c) return VISO_ERR_HIP;
+    int n = 0;   // before the call: fetched on its stream
+    DirectCall dc;
+    VISO_TRY(dc.begin());
     uint8_t* dimg; float *dr, *dtr, *dro; float2 *dtk, *dko; int* dcnt;
     const size_t px = (size_t)rows * cols, slots = (size_t)nbins * per;
-    if ((r = ctx_scratch(c, 0, px, (void**)&dimg)) < 0) return r;
-    if ((r = ctx_scratch(c, 1, sizeof(float) * px, (void**)&dr)) < 0) return r;
-    if ((r = ctx_scratch(c, 2, sizeof(float2) * slots, (void**)&dtk)) < 0) return r;
-    if ((r = ctx_scratch(c, 3, sizeof(float) * slots, (void**)&dtr)) < 0) return r;
-    if ((r = ctx_scratch(c, 4, sizeof(int) * (size_t)(nbins + 4), (void**)&dcnt)) < 0) return r;
-    if ((r = ctx_scratch(c, 5, sizeof(float2) * slots, (void**)&dko)) < 0) return r;
-    if ((r = ctx_scratch(c, 6, sizeof(float) * slots, (void**)&dro)) < 0) return r;
-    HIP_TRY(hipMemcpyAsync(dimg, img, px, hipMemcpyHostToDevice, c->stream));
+    VISO_TRY(dc.scratch(SLOT_GEN0, px, &dimg));
+    VISO_TRY(dc.scratch(SLOT_GEN1, px, &dr));
+    VISO_TRY(dc.scratch(SLOT_GEN2, slots, &dtk));
+    VISO_TRY(dc.scratch(SLOT_HARRIS_TMP_RESP, slots, &dtr));
+    VISO_TRY(dc.scratch(SLOT_HYP_WORDS, (size_t)(nbins + 4), &dcnt));
+    VISO_TRY(dc.scratch(SLOT_HYP_TR, slots, &dko));
+    VISO_TRY(dc.scratch(SLOT_GEN6, slots, &dro));
+    VISO_TRY(dc.up(dimg, img, px));
     if (harris_fused_lds(rows, cols, nbinx, nbiny, per)) {
-        void* part = nullptr;   // one image never fills the GPU with strips: only when $VISO_HARRIS_STRIPS=1 forces them (tests)
-        if (const size_t pb = harris_strip_bytes(1, rows, cols, nbinx, nbiny, per))
-            if ((r = ctx_scratch(c, 7, pb, &part)) < 0) return r;
-        if ((r = launch_harris_detect(c->stream, dimg, 1, rows, cols, n_features, nbinx, nbiny, k, dtk, dtr, dcnt, dko, dro,
-                                      dcnt + nbins, (int)slots, slots, part)) < 0) return r;
+        char* part = nullptr;   // one image never fills the GPU with strips: only when $VISO_HARRIS_STRIPS=1 forces them (tests)
+        if (const size_t pb = harris_strip_bytes(1, rows, cols, nbinx, nbiny, per)) VISO_TRY(dc.scratch(SLOT_HARRIS_STRIPS, pb, &part));
+        VISO_TRY(launch_harris_detect(dc.s, dimg, 1, rows, cols, n_features, nbinx, nbiny, k, dtk, dtr, dcnt, dko, dro, dcnt + nbins,
+                                      (int)slots, slots, part));
     } else {
-        if ((r = launch_harris_response(c->stream, dimg, 1, rows, cols, k, dr)) < 0) return r;
-        if ((r = launch_harris_bins(c->stream, dr, 1, rows, cols, n_features, nbinx, nbiny, dtk, dtr, dcnt, dko, dro,
-                                    dcnt + nbins, (int)slots, slots)) < 0) return r;
+        VISO_TRY(launch_harris_response(dc.s, dimg, 1, rows, cols, k, dr));
+        VISO_TRY(launch_harris_bins(dc.s, dr, 1, rows, cols, n_features, nbinx, nbiny, dtk, dtr, dcnt, dko, dro, dcnt + nbins, (int)slots,
+                                    slots));
     }
-    int n = 0;
-    HIP_TRY(hipMemcpyAsync(&n, dcnt + nbins, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    VISO_TRY(dc.down(&n, dcnt + nbins, 1));
+    VISO_TRY(dc.wait());
     if (n > 0) {
         HIP_TRY(hipMemcpy(kp, dko, sizeof(float2) * (size_t)n, hipMemcpyDeviceToHost));
         if (resp_out) HIP_TRY(hipMemcpy(resp_out, dro, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost));

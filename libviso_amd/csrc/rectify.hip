@@ -207,20 +207,15 @@ extern "C" int viso_rectify_images(const uint8_t* raw, int n, int raw_rows, int 
     const size_t rper = (size_t)raw_rows * raw_cols, oper = (size_t)out_rows * out_cols;
     std::vector<RectEntry> q(oper);
     rect_quantise(mapx, mapy, oper, raw_rows, raw_cols, q.data());
-    PlainLock lk;
-    viso_ctx* c = viso_default_ctx();
-    if (!c) return VISO_ERR_HIP;
-    HIP_TRY(hipSetDevice(c->device));
+    DirectCall dc;
+    VISO_TRY(dc.begin());
     uint8_t *draw, *dout; RectEntry* dmap;
-    int r;
-    if ((r = ctx_scratch(c, 21, rper * (size_t)n, (void**)&draw)) < 0) return r;
-    if ((r = ctx_scratch(c, 22, oper * (size_t)n, (void**)&dout)) < 0) return r;
-    if ((r = ctx_scratch(c, 23, sizeof(RectEntry) * oper, (void**)&dmap)) < 0) return r;
-    hipStream_t s = c->stream;
-    HIP_TRY(hipMemcpyAsync(draw, raw, rper * (size_t)n, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(dmap, q.data(), sizeof(RectEntry) * oper, hipMemcpyHostToDevice, s));
-    if ((r = launch_rectify(s, draw, rper, 0, raw_cols, dout, oper, 0, dmap, out_rows, out_cols, n, 1, border)) < 0) return r;
-    HIP_TRY(hipMemcpyAsync(out, dout, oper * (size_t)n, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return VISO_OK;
+    VISO_TRY(dc.scratch(SLOT_RECT_RAW, rper * (size_t)n, &draw));
+    VISO_TRY(dc.scratch(SLOT_RECT_OUT, oper * (size_t)n, &dout));
+    VISO_TRY(dc.scratch(SLOT_RECT_MAP, oper, &dmap));
+    VISO_TRY(dc.up(draw, raw, rper * (size_t)n));
+    VISO_TRY(dc.up(dmap, q.data(), oper));
+    VISO_TRY(launch_rectify(dc.s, draw, rper, 0, raw_cols, dout, oper, 0, dmap, out_rows, out_cols, n, 1, border));
+    VISO_TRY(dc.down(out, dout, oper * (size_t)n));
+    return dc.wait();
 }

@@ -505,19 +505,15 @@ int launch_motion_refine(hipStream_t s, const SolverItem* items_dev, int n_items
 // ---- the direct call: host pointers, default context (pose_call_stage, covariance.hip) --------------------------------------
 extern "C" int viso_pose_refine(const double* X, const double* obs, int m, const double tr[6], const int32_t* inl, int n_inl,
                                 const viso_param* param, int mode, double sigma_px, viso_motion_refine* out, double* Xout) {
-    PlainLock lk;
     PoseCall pc;
-    int r;
     // extra: points [2][3][ld] | L' [ld]
     const size_t ld = (size_t)(m > 0 ? m : 1), oL = al256(sizeof(double) * 6 * ld);
-    if ((r = pose_call_stage("viso_pose_refine", X, obs, m, tr, inl, n_inl, param, mode, sigma_px, out, sizeof(viso_motion_refine),
-                             oL + sizeof(int) * ld, &pc)) < 0)
-        return r;
-    if ((r = launch_motion_refine(pc.s, pc.item, 1, pc.sp, mode, sigma_px, reinterpret_cast<double*>(pc.extra),
-                                  reinterpret_cast<int*>(pc.extra + oL), ld, reinterpret_cast<viso_motion_refine*>(pc.rec))) < 0)
-        return r;
-    HIP_TRY(hipMemcpyAsync(out, pc.rec, sizeof(viso_motion_refine), hipMemcpyDeviceToHost, pc.s));
-    HIP_TRY(hipStreamSynchronize(pc.s));
+    VISO_TRY(pose_call_stage("viso_pose_refine", X, obs, m, tr, inl, n_inl, param, mode, sigma_px, out, sizeof(viso_motion_refine),
+                             oL + sizeof(int) * ld, &pc));
+    VISO_TRY(launch_motion_refine(pc.dc.s, pc.item, 1, pc.sp, mode, sigma_px, reinterpret_cast<double*>(pc.extra),
+                                  reinterpret_cast<int*>(pc.extra + oL), ld, reinterpret_cast<viso_motion_refine*>(pc.rec)));
+    VISO_TRY(pc.dc.down(out, pc.rec, 1));
+    VISO_TRY(pc.dc.wait());
     if (Xout) {   // the refined points, L' order: rows of n_inl doubles, the first out->n columns set when status is 1
         if (out->status == 1 && out->n > 0)
             for (int row = 0; row < 3; ++row)

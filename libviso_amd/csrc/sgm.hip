@@ -20,8 +20,6 @@
 // L_r <= 62 + P2 <= 254, S <= 8 * 254 = 2032.
 #include "common.h"
 
-#include <atomic>
-
 #define SGM_MAX_COLS 2048
 #define SGM_SEL_THREADS 256
 #define SGM_BIG 0x3fffu           // a disparity that is not a candidate (P1, P2 <= 192 can be added without overflow)
@@ -220,25 +218,17 @@ extern "C" void viso_sgm_params_default(viso_sgm_params* p) {
     p->num_disp = 128; p->p1 = 10; p->p2 = 120; p->paths = 8; p->uniqueness = 10; p->lr_max_diff = 1;
 }
 
-static std::atomic<size_t> g_sgm_cap{SGM_DEFAULT_CAP};
+static WorkspaceCap g_sgm_cap{{SGM_DEFAULT_CAP}, SGM_DEFAULT_CAP, "SGM", "viso_sgm_set_workspace_cap"};
 
-extern "C" void viso_sgm_set_workspace_cap(size_t bytes) { g_sgm_cap.store(bytes ? bytes : SGM_DEFAULT_CAP); }
+extern "C" void viso_sgm_set_workspace_cap(size_t bytes) { g_sgm_cap.set(bytes); }
 
 size_t sgm_frame_bytes(int rows, int cols, int D) {
     const size_t px = (size_t)rows * cols;
     return al256(px * 2 * sizeof(unsigned long long)) + al256(px * (size_t)D * sizeof(uint16_t));
 }
 
-int sgm_group_frames(int rows, int cols, int D, int n_frames) {
-    size_t g = g_sgm_cap.load() / sgm_frame_bytes(rows, cols, D);
-    if (g > 16384) g = 16384;   // 2 * group workgroups along the census grid's z
-    return (int)(g < (size_t)n_frames ? g : (size_t)n_frames);
-}
-
-int sgm_nomem(const char* where, int rows, int cols, int D) {
-    viso_set_error("%s: one %d x %d frame needs %zu bytes of SGM workspace, more than the cap (viso_sgm_set_workspace_cap)", where, rows,
-                   cols, sgm_frame_bytes(rows, cols, D));
-    return VISO_ERR_NOMEM;
+int sgm_group_frames(const char* where, int rows, int cols, int D, int n_frames, int* group) {
+    return g_sgm_cap.frames(where, rows, cols, sgm_frame_bytes(rows, cols, D), n_frames, 16384, group);   // 2 * group workgroups along the census grid's z
 }
 
 int launch_sgm(hipStream_t s, const uint8_t* img, size_t fs, size_t ss, int rows, int cols, int n_frames, const viso_sgm_params* p,
@@ -290,22 +280,17 @@ extern "C" int viso_stereo_sgm(const uint8_t* left, const uint8_t* right, int ro
         viso_set_error("viso_stereo_sgm: %d columns exceed the %d this build handles", cols, SGM_MAX_COLS);
         return VISO_ERR_UNSUPPORTED;
     }
-    if (sgm_group_frames(rows, cols, params->num_disp, 1) < 1) return sgm_nomem("viso_stereo_sgm", rows, cols, params->num_disp);
+    VISO_TRY(sgm_group_frames("viso_stereo_sgm", rows, cols, params->num_disp, 1, nullptr));
     const size_t per = (size_t)rows * cols;
-    PlainLock lk;
-    viso_ctx* c = viso_default_ctx();
-    if (!c) return VISO_ERR_HIP;
-    HIP_TRY(hipSetDevice(c->device));
-    uint8_t* dimg; int16_t* dout; void* ws;
-    int r;
-    if ((r = ctx_scratch(c, 0, 2 * per, (void**)&dimg)) < 0) return r;
-    if ((r = ctx_scratch(c, 1, sizeof(int16_t) * per, (void**)&dout)) < 0) return r;
-    if ((r = ctx_scratch(c, 2, sgm_frame_bytes(rows, cols, params->num_disp), &ws)) < 0) return r;
-    hipStream_t s = c->stream;
-    HIP_TRY(hipMemcpyAsync(dimg, left, per, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(dimg + per, right, per, hipMemcpyHostToDevice, s));
-    if ((r = launch_sgm(s, dimg, 2 * per, per, rows, cols, 1, params, dout, per, ws, 1)) < 0) return r;
-    HIP_TRY(hipMemcpyAsync(out, dout, sizeof(int16_t) * per, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return VISO_OK;
+    DirectCall dc;
+    VISO_TRY(dc.begin());
+    uint8_t* dimg; int16_t* dout; char* ws;
+    VISO_TRY(dc.scratch(SLOT_GEN0, 2 * per, &dimg));
+    VISO_TRY(dc.scratch(SLOT_GEN1, per, &dout));
+    VISO_TRY(dc.scratch(SLOT_GEN2, sgm_frame_bytes(rows, cols, params->num_disp), &ws));
+    VISO_TRY(dc.up(dimg, left, per));
+    VISO_TRY(dc.up(dimg + per, right, per));
+    VISO_TRY(launch_sgm(dc.s, dimg, 2 * per, per, rows, cols, 1, params, dout, per, ws, 1));
+    VISO_TRY(dc.down(out, dout, per));
+    return dc.wait();
 }

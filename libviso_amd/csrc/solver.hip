@@ -871,7 +871,7 @@ extern "C" int viso_minimize_reproj(const double* X, const double* obs, int m, d
     if ((r = in.begin(c, PlainStage::need(sizeof(double) * 3 * (size_t)m) + PlainStage::need(sizeof(double) * 4 * (size_t)m) +
                          PlainStage::need(sizeof(int) * (size_t)n_active) + PlainStage::need(64))) < 0) return r;
     char *dout, *hout;
-    if ((r = ctx_scratch(c, PLAIN_SLOT_OUT, 128, (void**)&dout)) < 0) return r;
+    if ((r = ctx_scratch(c, SLOT_PLAIN_OUT, 128, (void**)&dout)) < 0) return r;
     if ((r = ctx_pinned(c, 1, 128, &hout)) < 0) return r;
     GnArgs a{};
     a.X = in.put(X, 3 * (size_t)m); a.obs = in.put(obs, 4 * (size_t)m); a.m = m; a.ld = m;
@@ -914,7 +914,7 @@ extern "C" int viso_get_inliers(const double* X, const double* obs, int m, const
     if ((r = in.begin(c, PlainStage::need(sizeof(double) * 3 * (size_t)m) + PlainStage::need(sizeof(double) * 4 * (size_t)m) + PlainStage::need(64))) < 0) return r;
     char *dout, *hout;
     const size_t out_bytes = 64 + sizeof(int) * (size_t)m;
-    if ((r = ctx_scratch(c, PLAIN_SLOT_OUT, out_bytes, (void**)&dout)) < 0) return r;
+    if ((r = ctx_scratch(c, SLOT_PLAIN_OUT, out_bytes, (void**)&dout)) < 0) return r;
     if ((r = ctx_pinned(c, 1, out_bytes, &hout)) < 0) return r;
     GnArgs a{};
     a.X = in.put(X, 3 * (size_t)m); a.obs = in.put(obs, 4 * (size_t)m); a.m = m; a.ld = m;
@@ -947,35 +947,30 @@ extern "C" int viso_support_sizes(const double* X, const double* obs, int m, con
                                   const viso_param* p, int32_t* cnt) {
     if (!X || !obs || !tr_h || !p || !cnt || m < 0 || n_h < 0) { viso_set_error("viso_support_sizes: bad argument"); return VISO_ERR_ARG; }
     if (n_h == 0) return VISO_OK;
-    PlainLock lk;
-    viso_ctx* c = viso_default_ctx();
-    if (!c) return VISO_ERR_HIP;
-    double *dX, *dobs, *dtrh; int *dmisc; SolverItem* ditem;
-    int r;
-    if ((r = ctx_scratch(c, 0, sizeof(double) * 3 * (size_t)(m + 1), (void**)&dX)) < 0) return r;
-    if ((r = ctx_scratch(c, 1, sizeof(double) * 4 * (size_t)(m + 1), (void**)&dobs)) < 0) return r;
-    if ((r = ctx_scratch(c, 4, sizeof(int) * (4 + 2 * (size_t)n_h), (void**)&dmisc)) < 0) return r;
-    if ((r = ctx_scratch(c, 5, sizeof(double) * 6 * (size_t)n_h, (void**)&dtrh)) < 0) return r;
-    if ((r = ctx_scratch(c, 6, sizeof(SolverItem), (void**)&ditem)) < 0) return r;
     std::vector<int> hm(4 + 2 * (size_t)n_h, 1);   // m, -, -, -, ok_h = 1 ..., cnt_h
     hm[0] = m;
-    if (m > 0) {
-        HIP_TRY(hipMemcpyAsync(dX, X, sizeof(double) * 3 * m, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(dobs, obs, sizeof(double) * 4 * m, hipMemcpyHostToDevice, c->stream));
-    }
-    HIP_TRY(hipMemcpyAsync(dtrh, tr_h, sizeof(double) * 6 * n_h, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(dmisc, hm.data(), sizeof(int) * hm.size(), hipMemcpyHostToDevice, c->stream));
     SolverItem it{};
+    DirectCall dc;
+    VISO_TRY(dc.begin());
+    double *dX, *dobs, *dtrh; int *dmisc; SolverItem* ditem;
+    VISO_TRY(dc.scratch(SLOT_GEN0, 3 * (size_t)(m + 1), &dX));
+    VISO_TRY(dc.scratch(SLOT_GEN1, 4 * (size_t)(m + 1), &dobs));
+    VISO_TRY(dc.scratch(SLOT_HYP_WORDS, 4 + 2 * (size_t)n_h, &dmisc));
+    VISO_TRY(dc.scratch(SLOT_HYP_TR, 6 * (size_t)n_h, &dtrh));
+    VISO_TRY(dc.scratch(SLOT_GEN6, 1, &ditem));
+    VISO_TRY(dc.up(dX, X, 3 * (size_t)m));
+    VISO_TRY(dc.up(dobs, obs, 4 * (size_t)m));
+    VISO_TRY(dc.up(dtrh, tr_h, 6 * (size_t)n_h));
+    VISO_TRY(dc.up(dmisc, hm.data(), hm.size()));
     it.X = dX; it.obs = dobs; it.m_ptr = dmisc; it.ld = m; it.tr_h = dtrh; it.ok_h = dmisc + 4; it.cnt_h = dmisc + 4 + n_h;
-    if ((r = ctx_scratch(c, 9, viso_rot_bytes(n_h), (void**)&it.rot)) < 0) return r;
-    HIP_TRY(hipMemcpyAsync(ditem, &it, sizeof(it), hipMemcpyHostToDevice, c->stream));
+    VISO_TRY(dc.scratch(SLOT_RANSAC_ROT, viso_rot_bytes(n_h), &it.rot));
+    VISO_TRY(dc.up(ditem, &it, 1));
     SolverArgs a{};
     a.items = ditem; a.n_items = 1; a.iters = n_h;
     fill_solver_params(&a.sp, p);
-    if ((r = launch_inlier_count(c->stream, a, m)) < 0) return r;
-    HIP_TRY(hipMemcpyAsync(cnt, dmisc + 4 + n_h, sizeof(int) * n_h, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return VISO_OK;
+    VISO_TRY(launch_inlier_count(dc.s, a, m));
+    VISO_TRY(dc.down(cnt, dmisc + 4 + n_h, (size_t)n_h));
+    return dc.wait();
 }
 
 extern "C" int viso_ransac_minimize_reproj(const double* X, const double* obs, int m,
@@ -1008,13 +1003,13 @@ extern "C" int viso_ransac_minimize_reproj(const double* X, const double* obs, i
                          PlainStage::need(sizeof(int) * 3 * (size_t)(iters + 1)) + PlainStage::need(16) + PlainStage::need(sizeof(SolverItem)))) < 0) return r;
     char *dout, *hout;
     const size_t out_bytes = 128 + sizeof(int) * (size_t)m;
-    if ((r = ctx_scratch(c, PLAIN_SLOT_OUT, out_bytes, (void**)&dout)) < 0) return r;
+    if ((r = ctx_scratch(c, SLOT_PLAIN_OUT, out_bytes, (void**)&dout)) < 0) return r;
     if ((r = ctx_pinned(c, 1, out_bytes, &hout)) < 0) return r;
     double* dtrh; int *dhyp, *dqueue;
-    if ((r = ctx_scratch(c, 4, sizeof(int) * (4 + 2 * (size_t)iters), (void**)&dhyp)) < 0) return r;
-    if ((r = ctx_scratch(c, 5, sizeof(double) * 6 * (size_t)(iters + 1), (void**)&dtrh)) < 0) return r;
+    if ((r = ctx_scratch(c, SLOT_HYP_WORDS, sizeof(int) * (4 + 2 * (size_t)iters), (void**)&dhyp)) < 0) return r;
+    if ((r = ctx_scratch(c, SLOT_HYP_TR, sizeof(double) * 6 * (size_t)(iters + 1), (void**)&dtrh)) < 0) return r;
     // undecided-hypothesis list, then the triples in use
-    if ((r = ctx_scratch(c, 8, sizeof(int) * (2 + 4 * (size_t)iters + 3), (void**)&dqueue, true)) < 0) return r;
+    if ((r = ctx_scratch(c, SLOT_RANSAC_QUEUE, sizeof(int) * (2 + 4 * (size_t)iters + 3), (void**)&dqueue, true)) < 0) return r;
     SolverItem it{};
     it.X = in.put(X, 3 * (size_t)m); it.obs = in.put(obs, 4 * (size_t)m); it.ld = m; it.frame = frame;
     it.samples = samples ? in.put(samples, 3 * (size_t)iters) : nullptr;
@@ -1022,7 +1017,7 @@ extern "C" int viso_ransac_minimize_reproj(const double* X, const double* obs, i
     it.m_ptr = in.put(hm, 4);
     it.samp_h = dqueue + 2 + iters;
     it.tr_h = dtrh; it.ok_h = dhyp; it.cnt_h = dhyp + iters;
-    if ((r = ctx_scratch(c, 9, viso_rot_bytes(iters), (void**)&it.rot)) < 0) return r;
+    if ((r = ctx_scratch(c, SLOT_RANSAC_ROT, viso_rot_bytes(iters), (void**)&it.rot)) < 0) return r;
     // the refit writes kept, ok and n_inl whatever happens (refit_item): nothing of the result block needs a value in advance.
     // best_tr is an input of the reference's function only as the value that STAYS when no hypothesis finds support
     // (src/viso.cpp:1564-1568): the stage says so in `kept` and the caller's array is then left alone, below.

@@ -19,8 +19,6 @@
 //   points_kernel          the reprojection: one thread per pixel, fp64, each coordinate rounded once to f32.
 #include "common.h"
 
-#include <atomic>
-
 #define SPK_TW 64                 // tile width: one wave per tile row
 #define SPK_TH 16                 // tile height
 #define SPK_THREADS 256
@@ -202,22 +200,14 @@ extern "C" void viso_speckle_params_default(viso_speckle_params* p) {
     p->max_size = 100; p->max_diff = 16;
 }
 
-static std::atomic<size_t> g_speckle_cap{SPK_DEFAULT_CAP};
+static WorkspaceCap g_speckle_cap{{SPK_DEFAULT_CAP}, SPK_DEFAULT_CAP, "speckle", "viso_speckle_set_workspace_cap"};
 
-extern "C" void viso_speckle_set_workspace_cap(size_t bytes) { g_speckle_cap.store(bytes ? bytes : SPK_DEFAULT_CAP); }
+extern "C" void viso_speckle_set_workspace_cap(size_t bytes) { g_speckle_cap.set(bytes); }
 
 size_t speckle_frame_bytes(int rows, int cols) { return 2 * al256((size_t)rows * cols * sizeof(uint32_t)); }
 
-int speckle_group_frames(int rows, int cols, int n_frames) {
-    size_t g = g_speckle_cap.load() / speckle_frame_bytes(rows, cols);
-    if (g > 16384) g = 16384;   // the frames run along the grids' y and z
-    return (int)(g < (size_t)n_frames ? g : (size_t)n_frames);
-}
-
-int speckle_nomem(const char* where, int rows, int cols) {
-    viso_set_error("%s: one %d x %d frame needs %zu bytes of speckle workspace, more than the cap (viso_speckle_set_workspace_cap)", where,
-                   rows, cols, speckle_frame_bytes(rows, cols));
-    return VISO_ERR_NOMEM;
+int speckle_group_frames(const char* where, int rows, int cols, int n_frames, int* group) {
+    return g_speckle_cap.frames(where, rows, cols, speckle_frame_bytes(rows, cols), n_frames, 16384, group);   // the frames run along the grids' y and z
 }
 
 int launch_speckle(hipStream_t s, int16_t* map, size_t mfs, int rows, int cols, int n_frames, const viso_speckle_params* p, void* ws,
@@ -257,22 +247,17 @@ extern "C" int viso_filter_speckles(int16_t* map, int rows, int cols, const viso
         return VISO_ERR_UNSUPPORTED;
     }
     if (params->max_size == 0) return VISO_OK;
-    if (speckle_group_frames(rows, cols, 1) < 1) return speckle_nomem("viso_filter_speckles", rows, cols);
+    VISO_TRY(speckle_group_frames("viso_filter_speckles", rows, cols, 1, nullptr));
     const size_t per = (size_t)rows * cols;
-    PlainLock lk;
-    viso_ctx* c = viso_default_ctx();
-    if (!c) return VISO_ERR_HIP;
-    HIP_TRY(hipSetDevice(c->device));
-    int16_t* dmap; void* ws;
-    int r;
-    if ((r = ctx_scratch(c, 1, sizeof(int16_t) * per, (void**)&dmap)) < 0) return r;
-    if ((r = ctx_scratch(c, 2, speckle_frame_bytes(rows, cols), &ws)) < 0) return r;
-    hipStream_t s = c->stream;
-    HIP_TRY(hipMemcpyAsync(dmap, map, sizeof(int16_t) * per, hipMemcpyHostToDevice, s));
-    if ((r = launch_speckle(s, dmap, per, rows, cols, 1, params, ws, 1)) < 0) return r;
-    HIP_TRY(hipMemcpyAsync(map, dmap, sizeof(int16_t) * per, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return VISO_OK;
+    DirectCall dc;
+    VISO_TRY(dc.begin());
+    int16_t* dmap; char* ws;
+    VISO_TRY(dc.scratch(SLOT_GEN1, per, &dmap));
+    VISO_TRY(dc.scratch(SLOT_GEN2, speckle_frame_bytes(rows, cols), &ws));
+    VISO_TRY(dc.up(dmap, map, per));
+    VISO_TRY(launch_speckle(dc.s, dmap, per, rows, cols, 1, params, ws, 1));
+    VISO_TRY(dc.down(map, dmap, per));
+    return dc.wait();
 }
 
 // ---- reprojection ----------------------------------------------------------------------------------------------------------------
@@ -329,18 +314,13 @@ extern "C" int viso_disparity_to_points(const int16_t* disp, int rows, int cols,
         return VISO_ERR_UNSUPPORTED;
     }
     const size_t per = (size_t)rows * cols;
-    PlainLock lk;
-    viso_ctx* c = viso_default_ctx();
-    if (!c) return VISO_ERR_HIP;
-    HIP_TRY(hipSetDevice(c->device));
+    DirectCall dc;
+    VISO_TRY(dc.begin());
     int16_t* dmap; float* dout;
-    int r;
-    if ((r = ctx_scratch(c, 1, sizeof(int16_t) * per, (void**)&dmap)) < 0) return r;
-    if ((r = ctx_scratch(c, 2, 3 * sizeof(float) * per, (void**)&dout)) < 0) return r;
-    hipStream_t s = c->stream;
-    HIP_TRY(hipMemcpyAsync(dmap, disp, sizeof(int16_t) * per, hipMemcpyHostToDevice, s));
-    if ((r = launch_points(s, dmap, rows, cols, param->f, param->cu, param->cv, param->base, pose_or_null, min_disp16, dout)) < 0) return r;
-    HIP_TRY(hipMemcpyAsync(out, dout, 3 * sizeof(float) * per, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return VISO_OK;
+    VISO_TRY(dc.scratch(SLOT_GEN1, per, &dmap));
+    VISO_TRY(dc.scratch(SLOT_GEN2, 3 * per, &dout));
+    VISO_TRY(dc.up(dmap, disp, per));
+    VISO_TRY(launch_points(dc.s, dmap, rows, cols, param->f, param->cu, param->cv, param->base, pose_or_null, min_disp16, dout));
+    VISO_TRY(dc.down(out, dout, 3 * per));
+    return dc.wait();
 }

@@ -259,30 +259,24 @@ extern "C" int viso_refine_stereo_subpixel(const uint8_t* imgL, const uint8_t* i
             return VISO_ERR_ARG;
         }
     if (n == 0) return VISO_OK;
-    PlainLock lk;
-    viso_ctx* c = viso_default_ctx();
-    if (!c) return VISO_ERR_HIP;
-    HIP_TRY(hipSetDevice(c->device));
+    DirectCall dc;
+    VISO_TRY(dc.begin());
     const size_t per = (size_t)rows * cols;
     const int cap = n1 > n2 ? n1 : n2;
     const int capn = cap > n ? cap : n;
     uint8_t* dimg; float2* dkp; int* dlist; float2* duv;
-    int r;
-    if ((r = ctx_scratch(c, 17, 2 * per, (void**)&dimg)) < 0) return r;
-    if ((r = ctx_scratch(c, 18, sizeof(float2) * 2 * (size_t)capn, (void**)&dkp)) < 0) return r;
-    if ((r = ctx_scratch(c, 19, sizeof(int) * (3 * (size_t)n + 1), (void**)&dlist)) < 0) return r;
-    if ((r = ctx_scratch(c, 20, sizeof(float2) * (size_t)capn, (void**)&duv)) < 0) return r;
-    hipStream_t s = c->stream;
-    HIP_TRY(hipMemcpyAsync(dimg, imgL, per, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(dimg + per, imgR, per, hipMemcpyHostToDevice, s));
-    if (n1) HIP_TRY(hipMemcpyAsync(dkp, kp1, sizeof(float2) * (size_t)n1, hipMemcpyHostToDevice, s));
-    if (n2) HIP_TRY(hipMemcpyAsync(dkp + capn, kp2, sizeof(float2) * (size_t)n2, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(dlist, match, sizeof(int) * 3 * (size_t)n, hipMemcpyHostToDevice, s));
-    const int nn = n;
-    HIP_TRY(hipMemcpyAsync(dlist + 3 * (size_t)n, &nn, sizeof(int), hipMemcpyHostToDevice, s));
-    if ((r = launch_subpixel(s, dimg, 2 * per, per, rows, cols, dkp, 2 * (size_t)capn, capn, dlist, 3 * (size_t)n, dlist + 3 * (size_t)n,
-                             1, mode, duv, nullptr, 0, nullptr, 0)) < 0) return r;
-    HIP_TRY(hipMemcpyAsync(out_uv, duv, sizeof(float2) * (size_t)n, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return VISO_OK;
+    VISO_TRY(dc.scratch(SLOT_SUBPIX_IMG, 2 * per, &dimg));
+    VISO_TRY(dc.scratch(SLOT_SUBPIX_KP, 2 * (size_t)capn, &dkp));
+    VISO_TRY(dc.scratch(SLOT_SUBPIX_LIST, 3 * (size_t)n + 1, &dlist));
+    VISO_TRY(dc.scratch(SLOT_SUBPIX_UV, (size_t)capn, &duv));
+    VISO_TRY(dc.up(dimg, imgL, per));
+    VISO_TRY(dc.up(dimg + per, imgR, per));
+    VISO_TRY(dc.up(dkp, kp1, 2 * (size_t)n1));
+    VISO_TRY(dc.up(dkp + capn, kp2, 2 * (size_t)n2));
+    VISO_TRY(dc.up(dlist, match, 3 * (size_t)n));
+    VISO_TRY(dc.up(dlist + 3 * (size_t)n, &n, 1));
+    VISO_TRY(launch_subpixel(dc.s, dimg, 2 * per, per, rows, cols, dkp, 2 * (size_t)capn, capn, dlist, 3 * (size_t)n, dlist + 3 * (size_t)n,
+                             1, mode, duv, nullptr, 0, nullptr, 0));
+    VISO_TRY(dc.down(out_uv, duv, 2 * (size_t)n));
+    return dc.wait();
 }

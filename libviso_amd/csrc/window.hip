@@ -786,10 +786,6 @@ extern "C" int viso_window_refine(int len, const int* m, const double* X, const 
                        "mode 1 or mode 2 with a finite sigma_px > 0)");
         return VISO_ERR_ARG;
     }
-    PlainLock lk;
-    viso_ctx* c = viso_default_ctx();
-    if (!c) return VISO_ERR_HIP;
-    HIP_TRY(hipSetDevice(c->device));
     const size_t nf = (size_t)len, L = (size_t)ld, maxT = (size_t)(len - 1) * L;
     // one block: X [nf][3][ld] | obs [nf][4][ld] | left [nf][ld][2] | inl [nf][ld] | tr [nf][6] | ok, n_inl, m [nf] each | L' [nf][ld]
     // | nL' [nf] | tables [nf][2][tab] | tracks [5][maxT] | points [2][3][maxT] | the record
@@ -798,10 +794,7 @@ extern "C" int viso_window_refine(int len, const int* m, const double* X, const 
                  oLp = al256(oW + sizeof(int) * 3 * nf), oN = al256(oLp + sizeof(int) * nf * L), oTb = al256(oN + sizeof(int) * nf),
                  oK = al256(oTb + sizeof(int) * 2 * nf * (size_t)tab), oP = al256(oK + sizeof(int) * 5 * maxT),
                  oR = al256(oP + sizeof(double) * 6 * maxT), bytes = al256(oR + sizeof(viso_window_record));
-    char* dv;
-    int r;
-    if ((r = ctx_scratch(c, 0, bytes, (void**)&dv)) < 0) return r;
-    // the host image of the inputs: frame 0 is empty (m = 0), frames 1..len-1 the caller's
+    // the host image of the inputs: frame 0 is empty (m = 0), frames 1..len-1 the caller's (built in front of the call: it outlives it)
     std::vector<double> hX(3 * nf * L, 0.0), hO(4 * nf * L, 0.0), hT(6 * nf, 0.0);
     std::vector<int> hL(2 * nf * L, 0), hI(nf * L, 0), hW(3 * nf, 0);
     {
@@ -821,13 +814,16 @@ extern "C" int viso_window_refine(int len, const int* m, const double* X, const 
         }
         hW[0] = 1;
     }
-    hipStream_t s = c->stream;
-    HIP_TRY(hipMemcpyAsync(dv + oX, hX.data(), sizeof(double) * hX.size(), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(dv + oO, hO.data(), sizeof(double) * hO.size(), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(dv + oLe, hL.data(), sizeof(int) * hL.size(), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(dv + oI, hI.data(), sizeof(int) * hI.size(), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(dv + oT, hT.data(), sizeof(double) * hT.size(), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(dv + oW, hW.data(), sizeof(int) * hW.size(), hipMemcpyHostToDevice, s));
+    DirectCall dc;
+    VISO_TRY(dc.begin());
+    char* dv;
+    VISO_TRY(dc.scratch(SLOT_GEN0, bytes, &dv));
+    VISO_TRY(dc.up(dv + oX, hX.data(), hX.size()));
+    VISO_TRY(dc.up(dv + oO, hO.data(), hO.size()));
+    VISO_TRY(dc.up(dv + oLe, hL.data(), hL.size()));
+    VISO_TRY(dc.up(dv + oI, hI.data(), hI.size()));
+    VISO_TRY(dc.up(dv + oT, hT.data(), hT.size()));
+    VISO_TRY(dc.up(dv + oW, hW.data(), hW.size()));
     WinData d;
     d.X = reinterpret_cast<const double*>(dv + oX); d.obs = reinterpret_cast<const double*>(dv + oO);
     d.left = reinterpret_cast<const int*>(dv + oLe); d.left_fs = 2 * L; d.lstride = 2; d.lprev = 1;
@@ -841,10 +837,8 @@ extern "C" int viso_window_refine(int len, const int* m, const double* X, const 
     w.trk = reinterpret_cast<int*>(dv + oK); w.pts = reinterpret_cast<double*>(dv + oP); w.maxT = maxT;
     SolverParamsDev sp;
     fill_solver_params(&sp, param);
-    if ((r = launch_window_links(s, d, w, 1, len - 1)) < 0) return r;
-    if ((r = launch_window_refine(s, d, w, sp, len, mode, sigma_px, len - 1, 1, reinterpret_cast<viso_window_record*>(dv + oR))) < 0)
-        return r;
-    HIP_TRY(hipMemcpyAsync(out, dv + oR, sizeof(viso_window_record), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return VISO_OK;
+    VISO_TRY(launch_window_links(dc.s, d, w, 1, len - 1));
+    VISO_TRY(launch_window_refine(dc.s, d, w, sp, len, mode, sigma_px, len - 1, 1, reinterpret_cast<viso_window_record*>(dv + oR)));
+    VISO_TRY(dc.down(out, dv + oR, 1));
+    return dc.wait();
 }
