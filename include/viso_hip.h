@@ -878,7 +878,7 @@ int viso_batch_get_disparity_points(viso_batch* b, int t, const double* pose_or_
  * finds no slot increments n_dropped; a call that ends with n_dropped > 0 returns VISO_ERR_NOMEM and marks the map overflowed
  * (which points were dropped depends on scheduling), and viso_map_count / viso_map_get / viso_map_add_entries / the fuse calls
  * then refuse with VISO_ERR_NOMEM until viso_map_clear, after which the map is fully usable again.
- * Out of scope: colour, eviction of far voxels, fusing inside the KITTI runners while their chunks drain (a surface form is the
+ * Out of scope: RGB (a TSDF map can carry one 8-bit intensity: "TSDF intensity" below), eviction of far voxels, fusing inside the KITTI runners while their chunks drain (a surface form is the
  * TSDF map below).
  * HIP kernels (voxelmap.hip): map_fuse_kernel (one thread per pixel of a group of frames; lanes that continue the key of the lane
  * to their left form a run, the run heads come from one ballot, the runs' sums from a wave scan, and only a run's head probes the
@@ -969,7 +969,7 @@ int viso_map_entry_centroid(const viso_map_entry* entry, double voxel, float out
  * VISO_ERR_NOMEM and marks the map overflowed, and every getter, viso_tsdf_add_entries and every fuse call then refuse with
  * VISO_ERR_NOMEM until viso_tsdf_clear.  Every probe loop, the read-only lookups of the extraction included, visits each slot at
  * most once and advances strictly.
- * Out of scope: colour, carving free space beyond the truncation band, weights that fall with depth, eviction, fusing inside the
+ * Out of scope: RGB (one 8-bit intensity: "TSDF intensity" below), carving free space beyond the truncation band, weights that fall with depth, eviction, fusing inside the
  * KITTI runners, the sort on the device.
  * HIP kernels (tsdf.hip): tsdf_fuse_kernel (one thread per pixel of a group of frames; the loop over j is uniform across the wave,
  * and per j the lanes that continue the voxel of the lane to their left form a run whose head lane alone probes the table and
@@ -1123,7 +1123,7 @@ int viso_tsdf_mesh(viso_tsdf* t, uint32_t min_weight, viso_tsdf_mesh_vertex* ver
  * An overflowed map refuses with VISO_ERR_NOMEM, as the getters do; a handle that is not a live TSDF map, or whose context is gone,
  * VISO_ERR_ARG; no device, VISO_ERR_HIP.  The call takes the map's lock, like an extraction.
  * Out of scope: trilinear sampling, normals and shaded images, an empty-space skipping structure (a coarse block table), rendering
- * into a batch's resident maps, frame-to-model alignment, colour.
+ * into a batch's resident maps, frame-to-model alignment, RGB (one 8-bit intensity: "TSDF intensity" below).
  * HIP kernel (tsdf.hip): tsdf_render_kernel, one thread per pixel of a group of views, the lanes of a wave consecutive pixels of a
  * row.  The loop over i is uniform across the wave; per i the lanes that continue the voxel of the lane to their left form a run,
  * whose head lane alone probes the table and loads weight and sum, and the other lanes take them from it.  Reads only: no atomics,
@@ -1132,6 +1132,70 @@ int viso_tsdf_mesh(viso_tsdf* t, uint32_t min_weight, viso_tsdf_mesh_vertex* ver
  * freed on every path (VISO_ERR_NOMEM when it cannot be allocated). */
 int viso_tsdf_render(viso_tsdf* t, uint32_t min_weight, const viso_param* param, int rows, int cols, double max_depth,
                      const double* poses_or_null, int n_views, int16_t* disp_out, uint32_t* weight_out_or_null);
+
+/* ------------------------------------------------ TSDF intensity: the cameras' 8-bit intensity fused, meshed and rendered (opt-in;
+ * NOT in the reference)
+ *
+ * A gray map is a TSDF map whose table carries a third payload array, gray [slots] u64: per voxel the sum of the 8-bit intensities
+ * of the pixels that updated it.  The sums are integers, so a gray map too depends on neither the order of the frames nor on
+ * scheduling, and gray maps are additive.  The images are grayscale: "colour" is one intensity.  This definition is the contract; the
+ * device output is bit-identical to tests/gray_ref.py.  Everything is IEEE double in the operand order written, with no fused
+ * multiply-add.  A plain map (viso_tsdf_create) keeps its 20 bytes a slot, its kernels and its outputs.
+ * Gray map: viso_tsdf_create_gray is viso_tsdf_create with the same parameter checks; memory is 28 bytes a slot.  viso_tsdf_clear
+ *   zeroes gray too; viso_tsdf_is_gray tells which kind a handle is.  Handles, lifetime, lock and the full-table rule are the TSDF
+ *   map's.
+ * Fuse: viso_tsdf_fuse_gray takes with the map the left image it was computed from, uint8 [rows][cols], pixel for pixel.  Rules
+ *   1..7 of the TSDF map hold unchanged, and rule 7 gains one line: every update of pixel (x, y) also does gray += image[y][x].  A
+ *   voxel's intensity weight is therefore its weight, gray <= 255 weight always, and (k, weight, sum) of a gray map equal those of
+ *   a plain map fused from the same frames, bit for bit.
+ * Resident path: viso_batch_fuse_tsdf given a gray map also reads the batch's resident left images, frame t's at
+ *   images + (2 t) rows cols: the images the run read, rectified if rectification was on.  VISO_ERR_ARG when the images' geometry
+ *   is not the maps'.  Given a plain map it is unchanged.
+ * Kinds do not mix.  VISO_ERR_ARG before a device is touched, the table unchanged: viso_tsdf_fuse or viso_tsdf_add_entries on a
+ *   gray map; viso_tsdf_fuse_gray, viso_tsdf_add_gray_entries, viso_tsdf_get_gray, viso_tsdf_vertex_gray or viso_tsdf_render_gray
+ *   on a plain map; a null image.
+ * Entries: viso_tsdf_get_gray lists viso_tsdf_gray_entry sorted by key, with the two passes of viso_tsdf_get (viso_tsdf_count
+ *   serves both kinds); viso_tsdf_add_gray_entries applies the checks of viso_tsdf_add_entries and gray <= 255 weight.
+ * The unchanged readers work on a gray map with unchanged output: viso_tsdf_get, _surface, _mesh, _render, _stats.
+ * Intensity of a point on an edge (vertices and renders): voxels a and b with weights wa, wb >= 1, sums sa, sb of different sign
+ *   ((sa < 0) != (sb < 0)) and gray sums ga, gb.  da = (double)sa / (double)wa, db likewise, t = da / (da - db): exactly the
+ *   mesh's and the render's.  ia = (double)ga / (double)wa, ib likewise, v = ia + (ib - ia) t,
+ *   g = (uint8) min(255.0, floor(v + 0.5)).
+ * Vertices: viso_tsdf_vertex_gray, for the vertex list of viso_tsdf_mesh or any list of (k, dir) (p and weight are not read): a = k,
+ *   b = a + (dir & 1, dir >> 1 & 1, dir >> 2).  VISO_ERR_ARG before a device is touched for a dir outside 1..7, a k outside the
+ *   key range, or a k_i = 2^20 - 1 on an axis where dir has its bit set.  An end that is not in the table, or ends that do not
+ *   differ in sign: g = 0, the vertex counts in *n_missing, and the call still returns VISO_OK.  Crossings go through the same call
+ *   with dir = 1 << axis.
+ * Render: viso_tsdf_render_gray has the arguments and checks of viso_tsdf_render, and its disp_out and weight_out are bit-identical
+ *   to it on the same table.  gray_out is g of the hit, a the previous voxel of rule 6, b the hit voxel, t rule 7's; 0 wherever the
+ *   pixel is VISO_DISP_INVALID.
+ * Out of scope: RGB, intensity weights other than the TSDF weight, exposure compensation, trilinear intensity, fusing inside the
+ * KITTI runners.
+ * HIP kernels (tsdf.hip): tsdf_gray_fuse_kernel (the fuse kernel's march with the pixel's intensity carried: one byte a pixel read
+ * along the row, the run's sum of intensities from a second wave scan, three integer atomic adds from the run's head lane),
+ * tsdf_gray_add_entries_kernel, tsdf_gray_compact_kernel, tsdf_gray_sample_kernel (one thread per vertex, two read-only probes,
+ * n_missing with one atomic per wave), tsdf_gray_render_kernel (the render march, the head lane also loads gray and hands it to its
+ * run), tsdf_gray_clear_kernel.  No LDS, no scratch; every probe loop is bounded by the capacity. */
+typedef struct viso_tsdf_gray_entry {   /* 32 bytes */
+    int32_t k[3];
+    uint32_t weight;
+    int64_t sum;
+    uint64_t gray;           /* sum of the updates' intensities: gray / weight is the voxel's mean intensity */
+} viso_tsdf_gray_entry;
+
+int viso_tsdf_create_gray(viso_ctx* ctx_or_null, const viso_tsdf_params* params, viso_tsdf** out);
+/* *out = 1 for a gray map, 0 for a plain one.  Host only. */
+int viso_tsdf_is_gray(viso_tsdf* t, int* out);
+/* image: uint8 [rows][cols], the left image of the pair the map was computed from. */
+int viso_tsdf_fuse_gray(viso_tsdf* t, const int16_t* disp, const uint8_t* image, int rows, int cols, const viso_param* param,
+                        const double* pose_or_null);
+int viso_tsdf_get_gray(viso_tsdf* t, uint32_t min_weight, viso_tsdf_gray_entry* entries_out, size_t n_cap, size_t* n);
+int viso_tsdf_add_gray_entries(viso_tsdf* t, const viso_tsdf_gray_entry* entries, size_t n);
+/* gray_out: uint8 [n]; n_missing_or_null: the number of vertices without a value. */
+int viso_tsdf_vertex_gray(viso_tsdf* t, const viso_tsdf_mesh_vertex* vertices, size_t n, uint8_t* gray_out, size_t* n_missing_or_null);
+/* gray_out: uint8 [n_views][rows][cols]; it goes through the same device buffer as the other two outputs. */
+int viso_tsdf_render_gray(viso_tsdf* t, uint32_t min_weight, const viso_param* param, int rows, int cols, double max_depth,
+                          const double* poses_or_null, int n_views, int16_t* disp_out, uint32_t* weight_out_or_null, uint8_t* gray_out);
 
 #ifdef __cplusplus
 }

@@ -19,7 +19,8 @@ import numpy as np
 from .abi import (DESC_LEN, MAP_DEFAULTS, MAP_ENTRY_DTYPE, MapCounters, MapParams, declare_map, MOTION_COV_DTYPE, MOTION_REFINE_DTYPE, SGM_DEFAULTS, SPECKLE_DEFAULTS, WINDOW_RECORD_DTYPE, DisparityParams, MatchParams,
                   Param, SgmParams, SpeckleParams, declare_common, declare_covariance, declare_disparity, declare_refine, declare_rectify,
                   declare_sgm, declare_speckle, declare_subpixel, declare_window, f32p, f64p, i32p, i64p, intp, ptr,
-                  TSDF_CROSSING_DTYPE, TSDF_DEFAULTS, TSDF_ENTRY_DTYPE, TSDF_MESH_VERTEX_DTYPE, TsdfCounters, TsdfParams, declare_tsdf)
+                  TSDF_CROSSING_DTYPE, TSDF_DEFAULTS, TSDF_ENTRY_DTYPE, TSDF_GRAY_ENTRY_DTYPE, TSDF_MESH_VERTEX_DTYPE, TsdfCounters, TsdfParams,
+                  declare_tsdf)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("VISO_HIP_SO") or os.path.join(_HERE, "libviso_hip.so")   # VISO_HIP_SO: another build of the library (A/B runs)
@@ -668,45 +669,64 @@ def tsdf_crossing_points(crossings, voxel):
     return out
 
 
-def surface_ply_bytes(crossings, voxel):
+_PLY_XYZW = [("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("weight", "<u4")]
+_PLY_XYZW_HEAD = "property float x\nproperty float y\nproperty float z\nproperty uint weight\n"
+_PLY_RGB = [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+_PLY_RGB_HEAD = "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+
+
+def _ply_vertices(where, x, y, z, weight, gray):
+    """(the vertex element's property lines, its records): x, y, z, weight and, with gray (uint8, one a vertex), red = green = blue."""
+    if gray is not None:
+        gray = np.asarray(gray)
+        if gray.dtype != np.uint8 or gray.shape != (len(x),):
+            raise ValueError(f"{where}: gray must be a uint8 array with one value a vertex")
+    v = np.empty(len(x), np.dtype(_PLY_XYZW + (_PLY_RGB if gray is not None else [])))
+    v["x"], v["y"], v["z"], v["weight"] = x, y, z, weight
+    if gray is not None:
+        v["red"] = v["green"] = v["blue"] = gray
+    return _PLY_XYZW_HEAD + (_PLY_RGB_HEAD if gray is not None else ""), v
+
+
+def surface_ply_bytes(crossings, voxel, gray=None):
     """The bytes of write_surface_ply: a binary little-endian PLY with one vertex per crossing, x, y, z the float32 crossing point
-    and weight = min(wa, wb) a uint32, in the crossings' order."""
+    and weight = min(wa, wb) a uint32, in the crossings' order.  gray (uint8 [n], TsdfMap.vertex_gray of the crossings): red, green
+    and blue, all equal to it, follow weight."""
     crossings = np.ascontiguousarray(crossings, dtype=TSDF_CROSSING_DTYPE)
     c = tsdf_crossing_points(crossings, voxel)
-    v = np.empty(len(crossings), np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("weight", "<u4")]))
-    v["x"], v["y"], v["z"], v["weight"] = c[:, 0], c[:, 1], c[:, 2], np.minimum(crossings["wa"], crossings["wb"])
+    props, v = _ply_vertices("surface_ply_bytes", c[:, 0], c[:, 1], c[:, 2], np.minimum(crossings["wa"], crossings["wb"]), gray)
     head = ("ply\nformat binary_little_endian 1.0\ncomment libviso_amd TSDF surface, voxel %r m\nelement vertex %d\n"
-            "property float x\nproperty float y\nproperty float z\nproperty uint weight\nend_header\n" % (float(voxel), len(crossings)))
+            "%send_header\n" % (float(voxel), len(crossings), props))
     return head.encode("ascii") + v.tobytes()
 
 
-def write_surface_ply(path, crossings, voxel):
+def write_surface_ply(path, crossings, voxel, gray=None):
     """The crossings of TsdfMap.surface as a point cloud file (surface_ply_bytes)."""
-    data = surface_ply_bytes(crossings, voxel)
+    data = surface_ply_bytes(crossings, voxel, gray)
     with open(path, "wb") as f:
         f.write(data)
 
 
-def mesh_ply_bytes(vertices, triangles):
+def mesh_ply_bytes(vertices, triangles, gray=None):
     """The bytes of write_mesh_ply: a binary little-endian PLY; per vertex x, y, z the float32 position and weight a uint32, per
-    face a uchar 3 and three int32 vertex indices, both in the order given."""
+    face a uchar 3 and three int32 vertex indices, both in the order given.  gray (uint8 [n], the third array of
+    TsdfMap.mesh(gray=True)): red, green and blue, all equal to it, follow weight."""
     vertices = np.ascontiguousarray(vertices, dtype=TSDF_MESH_VERTEX_DTYPE)
     triangles = np.ascontiguousarray(triangles, dtype=np.uint32).reshape(-1, 3)
     if len(triangles) and (int(triangles.max()) >= len(vertices) or len(vertices) > 2 ** 31):
         raise ValueError("mesh_ply_bytes: a triangle refers to a vertex that is not in the list (or is beyond int32)")
-    v = np.empty(len(vertices), np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("weight", "<u4")]))
-    v["x"], v["y"], v["z"], v["weight"] = vertices["p"][:, 0], vertices["p"][:, 1], vertices["p"][:, 2], vertices["weight"]
+    props, v = _ply_vertices("mesh_ply_bytes", vertices["p"][:, 0], vertices["p"][:, 1], vertices["p"][:, 2], vertices["weight"], gray)
     f = np.empty(len(triangles), np.dtype([("n", "u1"), ("v", "<i4", (3,))]))
     f["n"], f["v"] = 3, triangles
     head = ("ply\nformat binary_little_endian 1.0\ncomment libviso_amd TSDF mesh\nelement vertex %d\n"
-            "property float x\nproperty float y\nproperty float z\nproperty uint weight\nelement face %d\n"
-            "property list uchar int vertex_indices\nend_header\n" % (len(vertices), len(triangles)))
+            "%selement face %d\n"
+            "property list uchar int vertex_indices\nend_header\n" % (len(vertices), props, len(triangles)))
     return head.encode("ascii") + v.tobytes() + f.tobytes()
 
 
-def write_mesh_ply(path, vertices, triangles):
+def write_mesh_ply(path, vertices, triangles, gray=None):
     """The mesh of TsdfMap.mesh as a PLY file (mesh_ply_bytes)."""
-    data = mesh_ply_bytes(vertices, triangles)
+    data = mesh_ply_bytes(vertices, triangles, gray)
     with open(path, "wb") as f:
         f.write(data)
 
@@ -1006,16 +1026,68 @@ class TsdfMap(_TableMap):
             batch.fuse_tsdf(tsdf, poses[k + 1][None], t0=t, t1=t + 1)
         write_surface_ply("surface.ply", tsdf.surface(min_weight=2), tsdf.voxel)
         write_mesh_ply("mesh.ply", *tsdf.mesh(min_weight=2))
+
+    gray=True: a gray map (include/viso_hip.h, "TSDF intensity"), which also sums the 8-bit intensity of the left images per voxel:
+    fuse then takes the image with the map (Batch.fuse_tsdf reads the resident ones), entries(gray=True), mesh(gray=True) and
+    render(gray=True) give the intensity with the geometry, and write_mesh_ply("mesh.ply", *tsdf.mesh(2, gray=True)) writes it.
     """
     _prefix, _Params, _params, _ENTRY_DTYPE, _Counters = "viso_tsdf_", TsdfParams, tsdf_params, TSDF_ENTRY_DTYPE, TsdfCounters
 
-    def __init__(self, ctx=None, params=None, **kw):
+    def __init__(self, ctx=None, params=None, gray=False, **kw):
+        self.gray = bool(gray)
         super().__init__(ctx, params, **kw)
         self.trunc_voxels = int(self._p.trunc_voxels)
 
-    def entries(self, min_weight=1):
-        """viso_tsdf_get: the voxels with at least min_weight updates as a TSDF_ENTRY_DTYPE array (k, weight, sum), sorted by key."""
+    def _c(self, name):
+        return super()._c("create_gray" if name == "create" and self.gray else name)
+
+    def fuse(self, d16, param, pose=None, image=None):
+        """viso_tsdf_fuse, or for a gray map viso_tsdf_fuse_gray: one host int16 map with the calibration of param (f, cu, cv, base)
+        and an optional 4 x 4 pose.  image: the left image the map was computed from, a 2-D uint8 array of the map's shape, for a
+        gray map, and only for one."""
+        if (image is not None) != self.gray:
+            raise ValueError("TsdfMap.fuse: a gray map is fused with an image, a plain one without")
+        if not self.gray:
+            return super().fuse(d16, param, pose)
+        d16, image = np.ascontiguousarray(d16), np.ascontiguousarray(image)
+        if d16.ndim != 2 or d16.dtype != np.int16:
+            raise ValueError("TsdfMap.fuse: the map must be a 2-D int16 array")
+        if image.dtype != np.uint8 or image.shape != d16.shape:
+            raise ValueError("TsdfMap.fuse: the image must be a 2-D uint8 array of the map's shape")
+        if pose is not None and np.shape(pose) != (4, 4):
+            raise ValueError("TsdfMap.fuse: the pose must be a 4 x 4 matrix")
+        T, Tp = _pose_arg("TsdfMap.fuse", pose)
+        self._chk("viso_tsdf_fuse_gray", self.L.viso_tsdf_fuse_gray(self.h, ptr(d16, C.c_int16), ptr(image, C.c_uint8), d16.shape[0],
+                                                                    d16.shape[1], C.byref(param), Tp))
+
+    def add_entries(self, entries):
+        """viso_tsdf_add_entries, or for a TSDF_GRAY_ENTRY_DTYPE array viso_tsdf_add_gray_entries: the entries of another map of
+        the same kind, voxel and truncation, or of a saved one, added to this one."""
+        if getattr(entries, "dtype", None) != TSDF_GRAY_ENTRY_DTYPE:
+            return super().add_entries(entries)
+        entries = np.ascontiguousarray(entries)
+        self._chk("viso_tsdf_add_gray_entries", self.L.viso_tsdf_add_gray_entries(self.h, entries.ctypes.data, len(entries)))
+
+    def entries(self, min_weight=1, gray=False):
+        """viso_tsdf_get: the voxels with at least min_weight updates as a TSDF_ENTRY_DTYPE array (k, weight, sum), sorted by key.
+        gray=True (a gray map): viso_tsdf_get_gray, a TSDF_GRAY_ENTRY_DTYPE array (k, weight, sum, gray)."""
+        if gray:
+            return self._list("count", "get_gray", TSDF_GRAY_ENTRY_DTYPE, min_weight)
         return self._list("count", "get", TSDF_ENTRY_DTYPE, min_weight)
+
+    def vertex_gray(self, vertices, missing=False):
+        """viso_tsdf_vertex_gray: uint8 [n], the intensity of every vertex of mesh() (a TSDF_MESH_VERTEX_DTYPE array, of which k and
+        dir are read) or of every crossing of surface() (a TSDF_CROSSING_DTYPE array: dir = 1 << axis).  0 where an end of the edge
+        is not in the table or the ends do not differ in sign; missing=True: a tuple with their number."""
+        if getattr(vertices, "dtype", None) == TSDF_CROSSING_DTYPE:
+            c = vertices
+            vertices = np.zeros(len(c), TSDF_MESH_VERTEX_DTYPE)
+            vertices["k"], vertices["dir"] = c["k"], np.left_shift(1, c["axis"])
+        vertices = np.ascontiguousarray(vertices, dtype=TSDF_MESH_VERTEX_DTYPE)
+        g, n_missing = np.zeros(len(vertices), np.uint8), C.c_size_t()
+        self._chk("viso_tsdf_vertex_gray", self.L.viso_tsdf_vertex_gray(self.h, vertices.ctypes.data, len(vertices), ptr(g, C.c_uint8),
+                                                                        C.byref(n_missing)))
+        return (g, n_missing.value) if missing else g
 
     def surface(self, min_weight=1):
         """viso_tsdf_surface: the sign changes between neighbouring voxels of at least min_weight updates as a TSDF_CROSSING_DTYPE
@@ -1026,23 +1098,27 @@ class TsdfMap(_TableMap):
         """float32 [n][3]: the crossing points of surface(min_weight), in their order."""
         return tsdf_crossing_points(self.surface(min_weight), self.voxel)
 
-    def mesh(self, min_weight=1):
+    def mesh(self, min_weight=1, gray=False):
         """viso_tsdf_mesh: the surface as triangles by marching tetrahedra over the voxels of at least min_weight updates.  Returns
         (vertices, triangles): a TSDF_MESH_VERTEX_DTYPE array (k, dir, p, weight) sorted by (key, dir), and uint32 [n][3] indices
-        into it sorted by (cell, tetrahedron, index), the normals towards the side the surface was seen from."""
+        into it sorted by (cell, tetrahedron, index), the normals towards the side the surface was seen from.  gray=True (a gray
+        map): (vertices, triangles, g), g = vertex_gray(vertices)."""
         nv, nt = C.c_size_t(), C.c_size_t()
         self._chk("viso_tsdf_mesh_count", self.L.viso_tsdf_mesh_count(self.h, int(min_weight), C.byref(nv), C.byref(nt)))
         v, tri = np.zeros(nv.value, TSDF_MESH_VERTEX_DTYPE), np.zeros((nt.value, 3), np.uint32)
         self._chk("viso_tsdf_mesh", self.L.viso_tsdf_mesh(self.h, int(min_weight), v.ctypes.data, len(v), tri.ctypes.data, len(tri),
                                                           C.byref(nv), C.byref(nt)))
-        return v[:nv.value], tri[:nt.value]
+        v, tri = v[:nv.value], tri[:nt.value]
+        return (v, tri, self.vertex_gray(v)) if gray else (v, tri)
 
-    def render(self, param, shape, poses=None, max_depth=40.0, min_weight=2, weights=False):
+    def render(self, param, shape, poses=None, max_depth=40.0, min_weight=2, weights=False, gray=False):
         """viso_tsdf_render: what a camera with the calibration of param (f, cu, cv, base) would see of the map, by ray casting: an
         int16 disparity map in 1/16 px of shape (rows, cols), VISO_DISP_INVALID where the ray meets no surface from its front within
         max_depth metres.  poses: None (no transform), one 4 x 4 camera-to-world matrix, as fuse takes it (returns [rows][cols]), or
         [n][4][4] (returns [n][rows][cols], the views of one call).  min_weight: only voxels with at least this many updates.
-        weights=True: a tuple with the uint32 array of the same shape, the smaller weight of the two voxels of a hit (0: none)."""
+        weights=True: a tuple with the uint32 array of the same shape, the smaller weight of the two voxels of a hit (0: none).
+        gray=True (a gray map): viso_tsdf_render_gray, the tuple ends with the uint8 array of the same shape, the intensity of the
+        hit (0: none)."""
         rows, cols = (int(v) for v in shape)
         T = None
         if poses is not None:
@@ -1054,12 +1130,17 @@ class TsdfMap(_TableMap):
             raise ValueError("TsdfMap.render: shape must be (rows, cols), both >= 1")
         d = np.empty((n, rows, cols), np.int16)
         w = np.empty((n, rows, cols), np.uint32) if weights else None
-        self._chk("viso_tsdf_render", self.L.viso_tsdf_render(self.h, int(min_weight), C.byref(param), rows, cols, float(max_depth),
-                                                              ptr(T, C.c_double) if T is not None else None, n, ptr(d, C.c_int16),
-                                                              ptr(w, C.c_uint32) if weights else None))
+        g = np.empty((n, rows, cols), np.uint8) if gray else None
+        args = (self.h, int(min_weight), C.byref(param), rows, cols, float(max_depth), ptr(T, C.c_double) if T is not None else None, n,
+                ptr(d, C.c_int16), ptr(w, C.c_uint32) if weights else None)
+        if gray:
+            self._chk("viso_tsdf_render_gray", self.L.viso_tsdf_render_gray(*args, ptr(g, C.c_uint8)))
+        else:
+            self._chk("viso_tsdf_render", self.L.viso_tsdf_render(*args))
         if T is None or T.ndim == 2:
-            d, w = d[0], (w[0] if weights else None)
-        return (d, w) if weights else d
+            d, w, g = d[0], (w[0] if weights else None), (g[0] if gray else None)
+        out = (d,) + ((w,) if weights else ()) + ((g,) if gray else ())
+        return out if len(out) > 1 else d
 
 
 class Batch:

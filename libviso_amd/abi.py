@@ -267,6 +267,8 @@ TSDF_CROSSING_DTYPE = np.dtype([("k", np.int32, (3,)), ("axis", np.int32), ("wa"
                                 ("sb", np.int64)])
 # struct viso_tsdf_mesh_vertex (32 bytes); a struct viso_tsdf_triangle is a row of a uint32 [n][3] array
 TSDF_MESH_VERTEX_DTYPE = np.dtype([("k", np.int32, (3,)), ("dir", np.int32), ("p", np.float32, (3,)), ("weight", np.uint32)])
+# struct viso_tsdf_gray_entry (32 bytes; include/viso_hip.h, "TSDF intensity")
+TSDF_GRAY_ENTRY_DTYPE = np.dtype([("k", np.int32, (3,)), ("weight", np.uint32), ("sum", np.int64), ("gray", np.uint64)])
 
 
 class TsdfCounters(C.Structure):
@@ -295,6 +297,21 @@ def declare_tsdf(lib):
     lib.viso_tsdf_mesh.argtypes = [vp, C.c_uint32, vp, C.c_size_t, vp, C.c_size_t, szp, szp]
     lib.viso_tsdf_render.argtypes = [vp, C.c_uint32, C.POINTER(Param), C.c_int, C.c_int, C.c_double, f64p, C.c_int, i16p,
                                      C.POINTER(C.c_uint32)]
+    if hasattr(lib, "viso_tsdf_create_gray"):   # (absent from older builds of the library: VISO_HIP_SO A/B runs)
+        declare_tsdf_gray(lib)
+
+
+def declare_tsdf_gray(lib):
+    """Prototypes of the gray TSDF map (include/viso_hip.h, "TSDF intensity")."""
+    i16p, u8p, vp, szp = C.POINTER(C.c_int16), C.POINTER(C.c_uint8), C.c_void_p, C.POINTER(C.c_size_t)
+    lib.viso_tsdf_create_gray.argtypes = [vp, C.POINTER(TsdfParams), C.POINTER(vp)]
+    lib.viso_tsdf_is_gray.argtypes = [vp, C.POINTER(C.c_int)]
+    lib.viso_tsdf_fuse_gray.argtypes = [vp, i16p, u8p, C.c_int, C.c_int, C.POINTER(Param), f64p]
+    lib.viso_tsdf_get_gray.argtypes = [vp, C.c_uint32, vp, C.c_size_t, szp]
+    lib.viso_tsdf_add_gray_entries.argtypes = [vp, vp, C.c_size_t]
+    lib.viso_tsdf_vertex_gray.argtypes = [vp, vp, C.c_size_t, u8p, szp]
+    lib.viso_tsdf_render_gray.argtypes = [vp, C.c_uint32, C.POINTER(Param), C.c_int, C.c_int, C.c_double, f64p, C.c_int, i16p,
+                                          C.POINTER(C.c_uint32), u8p]
 
 
 class MotionCov(C.Structure):

@@ -183,11 +183,22 @@ extern "C" int viso_batch_fuse_disparities(viso_batch* b, viso_map* m, int t0, i
     return map_fuse_resident(where, m, b->ctx, D.disp + (size_t)t0 * per, per, D.rows, D.cols, t1 - t0, b->sp.f, b->sp.cu, b->sp.cv, b->sp.base, poses);
 }
 
-// The same into a TSDF map of the same context (tsdf.hip).
+// The same into a TSDF map of the same context (tsdf.hip).  A gray map also reads the resident left images the maps were computed
+// from (frame t's at images + 2 t per): they must still be there, with the maps' geometry.
 extern "C" int viso_batch_fuse_tsdf(viso_batch* b, viso_tsdf* t, int t0, int t1, const double* poses) {
     const char* where = "viso_batch_fuse_tsdf";
     VISO_TRY(fuse_prelude(where, b, t, t0, t1, poses));
     const BatchDense& D = b->dense;
     const size_t per = (size_t)D.rows * D.cols;
-    return tsdf_fuse_resident(where, t, b->ctx, D.disp + (size_t)t0 * per, per, D.rows, D.cols, t1 - t0, b->sp.f, b->sp.cu, b->sp.cv, b->sp.base, poses);
+    const uint8_t* image = nullptr;
+    if (tsdf_is_gray(t)) {
+        if (!b->images || b->img_rows != D.rows || b->img_cols != D.cols) {
+            viso_set_error("%s: the resident images (%d x %d) are not the maps' (%d x %d): a gray TSDF map needs the images the maps were computed from",
+                           where, b->images ? b->img_cols : 0, b->images ? b->img_rows : 0, D.cols, D.rows);
+            return VISO_ERR_ARG;
+        }
+        image = b->images + 2 * (size_t)t0 * per;
+    }
+    return tsdf_fuse_resident(where, t, b->ctx, D.disp + (size_t)t0 * per, per, D.rows, D.cols, t1 - t0, b->sp.f, b->sp.cu, b->sp.cv, b->sp.base, poses,
+                              image, 2 * per);
 }

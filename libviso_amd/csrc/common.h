@@ -544,9 +544,11 @@ int launch_points(hipStream_t s, const int16_t* disp, int rows, int cols, double
 // that live on context c, on its stream, with poses [n_frames][16] on the host; checks the map handle, its context and the poses
 int map_fuse_resident(const char* where, viso_map* m, viso_ctx* c, const int16_t* disp, size_t mfs, int rows, int cols, int n_frames,
                       double f, double cu, double cv, double base, const double* poses);
-// tsdf.hip: the opt-in TSDF map (viso_tsdf_*).  tsdf_fuse_resident: map_fuse_resident for a TSDF map
+// tsdf.hip: the opt-in TSDF map (viso_tsdf_*).  tsdf_fuse_resident: map_fuse_resident for a TSDF map; for a gray one (tsdf_is_gray:
+// 1 for a live gray map, else 0) with frame f's 8-bit left image at image + f * ifs on the device, for a plain one with image null
+int tsdf_is_gray(viso_tsdf* t);
 int tsdf_fuse_resident(const char* where, viso_tsdf* t, viso_ctx* c, const int16_t* disp, size_t mfs, int rows, int cols, int n_frames,
-                       double f, double cu, double cv, double base, const double* poses);
+                       double f, double cu, double cv, double base, const double* poses, const uint8_t* image, size_t ifs);
 // covariance.hip: the opt-in motion covariance (viso_batch_set_covariance); one record per item, out[item], read from the item's
 // X, obs, m_ptr, ld, tr, ok, n_inl, inl (what ransac_refit_kernel left)
 int launch_motion_cov(hipStream_t s, const SolverItem* items_dev, int n_items, const SolverParamsDev& sp, int mode, double sigma,

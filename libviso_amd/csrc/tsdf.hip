@@ -25,6 +25,17 @@
 //                            kernel: only a run's head lane probes the table (voxel_find) and loads weight and sum, the other
 //                            lanes of the run take them from it (three ds_bpermute).  Ends when no lane of the wave marches.
 //   tsdf_clear_kernel        one thread per slot.
+// A gray map (include/viso_hip.h, "TSDF intensity") carries a third payload array, gray [slots] u64, the sum of the
+// 8-bit intensities of the pixels that updated a voxel.  Its kernels are their plain counterparts with that array carried: the
+// fuse and the render share their bodies with them (template <bool GRAY>, the plain instance reads none of the three extra
+// arguments), the others are restated for the 32-byte entry.
+//   tsdf_gray_fuse_kernel         the fuse kernel's march with the pixel's intensity (one byte a pixel, along the row); the run's
+//                                 sum of intensities from a second wave scan (64 x 255 < 2^14), a third atomic add from its head lane.
+//   tsdf_gray_add_entries_kernel, tsdf_gray_compact_kernel, tsdf_gray_clear_kernel   as the plain ones.
+//   tsdf_gray_sample_kernel       one thread per vertex (k, dir): two read-only probes for the ends of its edge, the intensity
+//                                 interpolated with the mesh's t; the vertices without a value counted with one atomic per wave.
+//   tsdf_gray_render_kernel       the render march; a run's head lane also loads gray and hands it to its run (two more
+//                                 ds_bpermute for the 64-bit value).
 // What every table of voxels shares is not here (voxelmap.hip says what): the device side is voxel_hash.h, the host side
 // voxel_host.h.  This file keeps the table's payload and insert, the kernels' own bodies, the parameter and entry checks, the
 // orders of the items and the whole mesh extraction, whose two lists do not fit the shared two passes.
@@ -39,12 +50,20 @@ struct TsdfTable {
     unsigned long long* sum; uint32_t* weight;   // [slots] i64 (added as u64, two's complement), [slots]
 };
 
-// weight updates with the sum of q `sum` into the voxel `key`
-__device__ __forceinline__ void tsdf_insert(const TsdfTable& t, unsigned long long key, uint32_t weight, long long sum, bool* claimed) {
+// a gray map's table (include/viso_hip.h, "TSDF intensity"): the same with the sums of the updates' 8-bit intensities
+struct TsdfGrayTable {
+    TsdfTable t;
+    unsigned long long* gray;                    // [slots]
+};
+
+// weight updates with the sum of q `sum` into the voxel `key`; gray_at set (a gray map): and their sum of intensities `gray`
+__device__ __forceinline__ void tsdf_insert(const TsdfTable& t, unsigned long long key, uint32_t weight, long long sum, bool* claimed,
+                                            unsigned long long* gray_at = nullptr, unsigned long long gray = 0) {
     uint32_t slot;
     if (voxel_probe(t.head.keys, t.head.mask, key, &slot, claimed)) {
         atomicAdd(t.weight + slot, weight);
         atomicAdd(t.sum + slot, (unsigned long long)sum);
+        if (gray_at) atomicAdd(gray_at + slot, gray);
     } else {
         atomicAdd(t.head.words + VOXEL_W_DROPPED, (unsigned long long)weight);
     }
@@ -57,13 +76,24 @@ struct TsdfFuseArgs {
     TsdfTable t;
 };
 
-__global__ __launch_bounds__(256) void tsdf_fuse_kernel(TsdfFuseArgs a) {
+struct TsdfGrayFuseArgs {
+    TsdfFuseArgs a;
+    const uint8_t* image; size_t ifs;   // frame f's left image at image + f * ifs, pixel for pixel the map's
+    unsigned long long* gray;
+};
+
+// The body of both fuse kernels.  GRAY: the pixel's intensity (image, ifs) is carried along, and a run's head lane adds the run's
+// sum of intensities to gray[slot] as well; without it, none of the three is read.
+template <bool GRAY>
+__device__ __forceinline__ void tsdf_fuse_body(const TsdfFuseArgs& a, const uint8_t* image, size_t ifs, unsigned long long* gray) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     const int lane = threadIdx.x & 63, fr = blockIdx.y;
     double X = 0.0, Y = 0.0, Z = 1.0;
     const bool point = voxel_point(a.v, i, fr, &X, &Y, &Z);
     const unsigned long long pm = __ballot(point);
     if (!pm) return;   // the whole wave
+    uint32_t pix = 0;                               // one byte a pixel, the lanes of a wave consecutive bytes of a row
+    if (GRAY && point) pix = image[(size_t)fr * ifs + i];
     // Without a pose the identity: ((1 a + 0 b) + 0 c) + 0 = a and (0 a + 0 b) + 1 (c - 0) = c for finite a, b, c, up to the sign
     // of a zero, which neither floor(. / s) nor Z - zc keeps.
     double T0 = 1.0, T1 = 0.0, T2 = 0.0, T3 = 0.0, T4 = 0.0, T5 = 1.0, T6 = 0.0, T7 = 0.0, T8 = 0.0, T9 = 0.0, T10 = 1.0, T11 = 0.0;
@@ -119,11 +149,22 @@ __global__ __launch_bounds__(256) void tsdf_fuse_kernel(TsdfFuseArgs a) {
         const uint32_t sq = viso_wave_scan(qb);                                   // inclusive prefix
         const uint32_t rq = (uint32_t)__shfl((int)sq, lane + (int)len - 1) - sq + qb;   // the run's sum, in its head lane
         bool claimed = false;
-        if (head && key != MAP_EMPTY) tsdf_insert(a.t, key, len, (long long)rq - (long long)len * lim, &claimed);
+        if (GRAY) {
+            // the run's sum of intensities by a second scan of the same shape (64 x 255 < 2^14)
+            const uint32_t gb = key != MAP_EMPTY ? pix : 0u;
+            const uint32_t sg = viso_wave_scan(gb);
+            const uint32_t rg = (uint32_t)__shfl((int)sg, lane + (int)len - 1) - sg + gb;
+            if (head && key != MAP_EMPTY) tsdf_insert(a.t, key, len, (long long)rq - (long long)len * lim, &claimed, gray, rg);
+        } else {
+            if (head && key != MAP_EMPTY) tsdf_insert(a.t, key, len, (long long)rq - (long long)len * lim, &claimed);
+        }
         n_occ += __popcll(__ballot(claimed));
     }
     voxel_count_wave(a.t.head, blockIdx.x + blockIdx.y, lane, __popcll(pm), n_upd, n_oor, n_occ);
 }
+
+__global__ __launch_bounds__(256) void tsdf_fuse_kernel(TsdfFuseArgs a) { tsdf_fuse_body<false>(a, nullptr, 0, nullptr); }
+__global__ __launch_bounds__(256) void tsdf_gray_fuse_kernel(TsdfGrayFuseArgs g) { tsdf_fuse_body<true>(g.a, g.image, g.ifs, g.gray); }
 
 __global__ __launch_bounds__(256) void tsdf_add_entries_kernel(TsdfTable t, const viso_tsdf_entry* e, unsigned long long n) {
     const unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
@@ -152,6 +193,70 @@ __global__ __launch_bounds__(256) void tsdf_compact_kernel(TsdfTable t, uint32_t
         v.sum = (long long)t.sum[slot];
         out[at] = v;
     }
+}
+
+// the same two for a gray map and its 32-byte entries
+__global__ __launch_bounds__(256) void tsdf_gray_add_entries_kernel(TsdfGrayTable g, const viso_tsdf_gray_entry* e, unsigned long long n) {
+    const unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+    bool claimed = false;
+    if (i < n) {
+        const viso_tsdf_gray_entry v = e[i];
+        tsdf_insert(g.t, voxel_key(v.k[0], v.k[1], v.k[2]), v.weight, v.sum, &claimed, g.gray, v.gray);
+        atomicAdd(voxel_stat(g.t.head, blockIdx.x, VOXEL_ST_UPDATES), (unsigned long long)v.weight);
+    }
+    voxel_count_wave(g.t.head, blockIdx.x, threadIdx.x & 63, 0, 0, 0, __popcll(__ballot(claimed)));
+}
+
+__global__ __launch_bounds__(256) void tsdf_gray_compact_kernel(TsdfGrayTable g, uint32_t min_weight, viso_tsdf_gray_entry* out, unsigned long long out_cap) {
+    const uint32_t slot = blockIdx.x * 256 + threadIdx.x;   // the grid covers the slots exactly
+    const unsigned long long key = g.t.head.keys[slot];
+    const uint32_t w = g.t.weight[slot];
+    const bool take = key != MAP_EMPTY && w >= min_weight;
+    unsigned long long at;
+    if (!voxel_list_position(g.t.head, take, threadIdx.x & 63, &at)) return;   // the whole wave
+    if (take && out && at < out_cap) {
+        viso_tsdf_gray_entry v;
+        voxel_unkey(key, v.k);
+        v.weight = w;
+        v.sum = (long long)g.t.sum[slot];
+        v.gray = g.gray[slot];
+        out[at] = v;
+    }
+}
+
+// The intensity of the point on the edge between the voxels a and b (include/viso_hip.h, "TSDF intensity"): t is the mesh's and the
+// render's, the means of the intensities are interpolated with it.  wa, wb >= 1 and the sums differ in sign.
+__device__ __forceinline__ uint8_t tsdf_edge_gray(uint32_t wa, long long sa, unsigned long long ga, uint32_t wb, long long sb, unsigned long long gb) {
+    const double da = (double)sa / (double)wa, db = (double)sb / (double)wb;
+    const double t = da / (da - db);
+    const double ia = (double)ga / (double)wa, ib = (double)gb / (double)wb;
+    const double v = ia + (ib - ia) * t;
+    return (uint8_t)fmin(255.0, floor(v + 0.5));
+}
+
+// One thread per vertex (k, dir), checked on the host: two read-only probes for the ends of its edge.  An end that is not in the
+// table, or ends of one sign: 0, and the vertex counts in VOXEL_W_OUT, one atomic per wave.
+__global__ __launch_bounds__(256) void tsdf_gray_sample_kernel(TsdfGrayTable g, const viso_tsdf_mesh_vertex* verts, unsigned long long n, uint8_t* out) {
+    const unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+    bool missing = false;
+    if (i < n) {
+        const viso_tsdf_mesh_vertex v = verts[i];
+        const unsigned long long ka = voxel_key(v.k[0], v.k[1], v.k[2]);
+        uint32_t a, b;
+        uint8_t val = 0;
+        missing = true;
+        if (voxel_find(g.t.head.keys, g.t.head.mask, ka, &a) && voxel_find(g.t.head.keys, g.t.head.mask, voxel_neighbour(ka, (uint32_t)v.dir), &b)) {
+            const uint32_t wa = g.t.weight[a], wb = g.t.weight[b];
+            const long long sa = (long long)g.t.sum[a], sb = (long long)g.t.sum[b];
+            if (wa && wb && (sa < 0) != (sb < 0)) {
+                val = tsdf_edge_gray(wa, sa, g.gray[a], wb, sb, g.gray[b]);
+                missing = false;
+            }
+        }
+        out[i] = val;
+    }
+    const unsigned long long m = __ballot(missing);
+    if (m && (threadIdx.x & 63) == 0) atomicAdd(g.t.head.words + VOXEL_W_OUT, (unsigned long long)__popcll(m));
 }
 
 __global__ __launch_bounds__(256) void tsdf_crossings_kernel(TsdfTable t, uint32_t min_weight, viso_tsdf_crossing* out, unsigned long long out_cap) {
@@ -342,7 +447,10 @@ struct TsdfRenderArgs {
     double f, cu, cv, base, s, h;
 };
 
-__global__ __launch_bounds__(256) void tsdf_render_kernel(TsdfRenderArgs a) {
+// The body of both render kernels.  GRAY: a run's head lane also loads gray[slot] and hands it to its run, and the hit's intensity
+// goes to gray_out; without it, neither pointer is read.
+template <bool GRAY>
+__device__ __forceinline__ void tsdf_render_body(const TsdfRenderArgs& a, const unsigned long long* gray, uint8_t* gray_out) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, px = (size_t)a.rows * a.cols;
     const int lane = threadIdx.x & 63, view = blockIdx.y;
     bool march = i < px;
@@ -360,8 +468,10 @@ __global__ __launch_bounds__(256) void tsdf_render_kernel(TsdfRenderArgs a) {
     int pkx = 0, pky = 0, pkz = 0;
     uint32_t pw = 0;                   // 0: not usable
     long long ps = 0;
+    unsigned long long pg = 0;
     int16_t out_d = VISO_DISP_INVALID;
     uint32_t out_w = 0;
+    uint8_t out_g = 0;
     for (int n = 1; n <= a.n_samples; ++n) {   // the same n in every lane
         if (!__ballot(march)) break;           // the whole wave
         unsigned long long key = MAP_EMPTY;    // the voxel this lane enters with this sample
@@ -389,15 +499,18 @@ __global__ __launch_bounds__(256) void tsdf_render_kernel(TsdfRenderArgs a) {
         const int from = voxel_run_head(head, lane);
         uint32_t w = 0;                        // 0: not in the table
         long long sum = 0;
+        unsigned long long gs = 0;
         if (head && key != MAP_EMPTY) {
             uint32_t slot;
             if (voxel_find(a.t.head.keys, a.t.head.mask, key, &slot)) {
                 w = a.t.weight[slot];
                 sum = (long long)a.t.sum[slot];
+                if (GRAY) gs = gray[slot];
             }
         }
         w = (uint32_t)__shfl((int)w, from);
         sum = __shfl(sum, from);
+        if (GRAY) gs = __shfl(gs, from);
         if (key == MAP_EMPTY) continue;
         if (w < a.min_weight) w = 0;           // (min_weight >= 1: a voxel that is not in the table is not usable either)
         if (w && sum < 0 && prev != MAP_EMPTY && pw && ps >= 0) {
@@ -413,17 +526,28 @@ __global__ __launch_bounds__(256) void tsdf_render_kernel(TsdfRenderArgs a) {
             if (zs > 0.0 && v >= 1.0 && !(v >= 32768.0)) {   // false for a NaN
                 out_d = (int16_t)(int)floor(v);
                 out_w = pw < w ? pw : w;
+                if (GRAY) out_g = tsdf_edge_gray(pw, ps, pg, w, sum, gs);
             }
             march = false;
         } else {
             prev = key; pkx = kx; pky = ky; pkz = kz; pw = w; ps = sum;
+            if (GRAY) pg = gs;
         }
     }
     if (i < px) {
         a.disp[(size_t)view * px + i] = out_d;
         if (a.weight) a.weight[(size_t)view * px + i] = out_w;
+        if (GRAY) gray_out[(size_t)view * px + i] = out_g;
     }
 }
+
+struct TsdfGrayRenderArgs {
+    TsdfRenderArgs a;
+    const unsigned long long* gray; uint8_t* out;   // the table's sums of intensities; [views][rows * cols]
+};
+
+__global__ __launch_bounds__(256) void tsdf_render_kernel(TsdfRenderArgs a) { tsdf_render_body<false>(a, nullptr, nullptr); }
+__global__ __launch_bounds__(256) void tsdf_gray_render_kernel(TsdfGrayRenderArgs g) { tsdf_render_body<true>(g.a, g.gray, g.out); }
 
 __global__ __launch_bounds__(256) void tsdf_clear_kernel(TsdfTable t) {
     const uint32_t slot = blockIdx.x * 256 + threadIdx.x;
@@ -432,11 +556,21 @@ __global__ __launch_bounds__(256) void tsdf_clear_kernel(TsdfTable t) {
     t.sum[slot] = 0ull;
 }
 
+__global__ __launch_bounds__(256) void tsdf_gray_clear_kernel(TsdfGrayTable g) {
+    const uint32_t slot = blockIdx.x * 256 + threadIdx.x;
+    voxel_clear_head(g.t.head, slot);
+    g.t.weight[slot] = 0u;
+    g.t.sum[slot] = 0ull;
+    g.gray[slot] = 0ull;
+}
+
 // ---- host: what is the TSDF map's own; the rest is the shared layer's (voxel_host.h) ----------------------------------------------
 struct viso_tsdf {
     VoxelHost h;
     viso_tsdf_params p; double s, hs;        // hs: half a voxel, the step along a ray
-    TsdfTable t;                             // the payload in h's block: sum | weight
+    TsdfTable t;                             // the payload in h's block: sum | weight; a gray map's: sum | gray | weight
+    unsigned long long* gray;                // null: a plain map
+    TsdfGrayTable g() const { return TsdfGrayTable{t, gray}; }
 };
 
 static VoxelRegistry g_tsdfs = {{"TSDF", "TSDF map", "updates", "min_weight", "viso_tsdf_clear"}};
@@ -454,34 +588,72 @@ extern "C" void viso_tsdf_params_default(viso_tsdf_params* p) {
 // the launches the shared layer asks for; t is live by then
 static dim3 tsdf_slot_grid(const viso_tsdf* t) { return dim3((t->t.head.mask + 1u) / 256u); }
 static VoxelLaunch tsdf_clear_launch(viso_tsdf* t) {
-    return [t](hipStream_t s) { hipLaunchKernelGGL(tsdf_clear_kernel, tsdf_slot_grid(t), dim3(256), 0, s, t->t); };
+    return [t](hipStream_t s) {
+        if (t->gray) hipLaunchKernelGGL(tsdf_gray_clear_kernel, tsdf_slot_grid(t), dim3(256), 0, s, t->g());
+        else hipLaunchKernelGGL(tsdf_clear_kernel, tsdf_slot_grid(t), dim3(256), 0, s, t->t);
+    };
 }
-static VoxelFuseLaunch tsdf_fuse_launch(viso_tsdf* t) {
-    return [t](const VoxelFuseArgs& v, dim3 grid, hipStream_t s) {
+// ifs: the distance of two frames' images, for a gray map's fuse (whose calls all come with an image); 0: a plain map's
+static VoxelFuseLaunch tsdf_fuse_launch(viso_tsdf* t, size_t ifs = 0) {
+    return [t, ifs](const VoxelFuseArgs& v, const uint8_t* d_image, dim3 grid, hipStream_t s) {
         TsdfFuseArgs a;
         a.v = v; a.trunc = t->p.trunc_voxels; a.s = t->s; a.h = t->hs; a.t = t->t;
-        hipLaunchKernelGGL(tsdf_fuse_kernel, grid, dim3(256), 0, s, a);
+        if (d_image) {
+            TsdfGrayFuseArgs g;
+            g.a = a; g.image = d_image; g.ifs = ifs; g.gray = t->gray;
+            hipLaunchKernelGGL(tsdf_gray_fuse_kernel, grid, dim3(256), 0, s, g);
+        } else {
+            hipLaunchKernelGGL(tsdf_fuse_kernel, grid, dim3(256), 0, s, a);
+        }
     };
 }
 
-extern "C" int viso_tsdf_create(viso_ctx* ctx_or_null, const viso_tsdf_params* params, viso_tsdf** out) {
+static int tsdf_create(const char* where, bool gray, viso_ctx* ctx_or_null, const viso_tsdf_params* params, viso_tsdf** out) {
     if (out) *out = nullptr;
     if (!out || !tsdf_params_ok(params)) {
-        viso_set_error("viso_tsdf_create: bad argument (a finite voxel > 0, trunc_voxels in 1..8, min_disp16 >= 1, capacity_log2 in 10..28, a non-null output)");
+        viso_set_error("%s: bad argument (a finite voxel > 0, trunc_voxels in 1..8, min_disp16 >= 1, capacity_log2 in 10..28, a non-null output)", where);
         return VISO_ERR_ARG;
     }
     viso_tsdf* t = new viso_tsdf();
     char* payload;
-    int r = voxel_create("viso_tsdf_create", g_tsdfs, ctx_or_null, params->capacity_log2, params->min_disp16, 12, &t->h, &payload);
+    int r = voxel_create(where, g_tsdfs, ctx_or_null, params->capacity_log2, params->min_disp16, gray ? 20 : 12, &t->h, &payload);
     if (r >= 0) {
+        const size_t slots = (size_t)1 << params->capacity_log2;
         t->p = *params; t->s = params->voxel / 1024.0; t->hs = params->voxel * 0.5;
         t->t.head = t->h.head;
-        t->t.sum = reinterpret_cast<unsigned long long*>(payload);
-        t->t.weight = reinterpret_cast<uint32_t*>(payload + 8 * ((size_t)1 << params->capacity_log2));
+        t->t.sum = reinterpret_cast<unsigned long long*>(payload); payload += 8 * slots;
+        t->gray = nullptr;
+        if (gray) { t->gray = reinterpret_cast<unsigned long long*>(payload); payload += 8 * slots; }
+        t->t.weight = reinterpret_cast<uint32_t*>(payload);
         r = voxel_open(g_tsdfs, t, &t->h, tsdf_clear_launch(t));
     }
     if (r < 0) { delete t; return r; }
     *out = t;
+    return VISO_OK;
+}
+
+extern "C" int viso_tsdf_create(viso_ctx* ctx_or_null, const viso_tsdf_params* params, viso_tsdf** out) {
+    return tsdf_create("viso_tsdf_create", false, ctx_or_null, params, out);
+}
+extern "C" int viso_tsdf_create_gray(viso_ctx* ctx_or_null, const viso_tsdf_params* params, viso_tsdf** out) {
+    return tsdf_create("viso_tsdf_create_gray", true, ctx_or_null, params, out);
+}
+
+// A live handle of the kind the call is for (gray: a gray map), checked before anything else of the call: the kinds do not mix.
+static bool tsdf_kind_ok(const char* where, viso_tsdf* t, bool gray) {
+    if (!voxel_known(g_tsdfs, t)) { viso_set_error("%s: not a live TSDF handle", where); return false; }
+    if ((t->gray != nullptr) != gray) {
+        viso_set_error(gray ? "%s: the TSDF map carries no intensity (viso_tsdf_create_gray makes one that does)"
+                            : "%s: the TSDF map carries intensity: its calls are the *_gray ones", where);
+        return false;
+    }
+    return true;
+}
+
+extern "C" int viso_tsdf_is_gray(viso_tsdf* t, int* out) {
+    if (!voxel_known(g_tsdfs, t)) { viso_set_error("viso_tsdf_is_gray: not a live TSDF handle"); return VISO_ERR_ARG; }
+    if (!out) { viso_set_error("viso_tsdf_is_gray: bad argument (a non-null output)"); return VISO_ERR_ARG; }
+    *out = t->gray ? 1 : 0;
     return VISO_OK;
 }
 
@@ -495,33 +667,69 @@ extern "C" int viso_tsdf_destroy(viso_tsdf* t) {
 
 extern "C" int viso_tsdf_clear(viso_tsdf* t) { return voxel_clear("viso_tsdf_clear", g_tsdfs, t, tsdf_clear_launch(t)); }
 
+int tsdf_is_gray(viso_tsdf* t) { return voxel_known(g_tsdfs, t) && t->gray ? 1 : 0; }
+
 int tsdf_fuse_resident(const char* where, viso_tsdf* t, viso_ctx* c, const int16_t* disp, size_t mfs, int rows, int cols, int n_frames,
-                       double f, double cu, double cv, double base, const double* poses) {
-    return voxel_fuse_resident(where, g_tsdfs, t, c, disp, mfs, rows, cols, n_frames, f, cu, cv, base, poses, tsdf_fuse_launch(t));
+                       double f, double cu, double cv, double base, const double* poses, const uint8_t* image, size_t ifs) {
+    if (!tsdf_kind_ok(where, t, image != nullptr)) return VISO_ERR_ARG;
+    return voxel_fuse_resident(where, g_tsdfs, t, c, disp, mfs, rows, cols, n_frames, f, cu, cv, base, poses, tsdf_fuse_launch(t, ifs), image, ifs);
 }
 
 extern "C" int viso_tsdf_fuse(viso_tsdf* t, const int16_t* disp, int rows, int cols, const viso_param* param, const double* pose_or_null) {
+    if (!tsdf_kind_ok("viso_tsdf_fuse", t, false)) return VISO_ERR_ARG;
     return voxel_fuse_host("viso_tsdf_fuse", g_tsdfs, t, disp, rows, cols, param, pose_or_null, tsdf_fuse_launch(t));
+}
+
+extern "C" int viso_tsdf_fuse_gray(viso_tsdf* t, const int16_t* disp, const uint8_t* image, int rows, int cols, const viso_param* param,
+                                   const double* pose_or_null) {
+    const char* where = "viso_tsdf_fuse_gray";
+    if (!tsdf_kind_ok(where, t, true)) return VISO_ERR_ARG;
+    if (!image) { viso_set_error("%s: bad argument (a non-null image)", where); return VISO_ERR_ARG; }
+    return voxel_fuse_host(where, g_tsdfs, t, disp, rows, cols, param, pose_or_null,
+                           tsdf_fuse_launch(t, rows > 0 && cols > 0 ? (size_t)rows * cols : 0), image);
+}
+
+// the checks of an entry that both kinds share
+static bool tsdf_entry_ok(const int32_t* k, uint32_t weight, long long sum, long long lim) {
+    bool ok = weight >= 1 && sum <= lim * (long long)weight && sum >= -lim * (long long)weight;
+    for (int i = 0; i < 3; ++i) ok = ok && k[i] >= -MAP_BIAS && k[i] < MAP_BIAS;
+    return ok;
 }
 
 extern "C" int viso_tsdf_add_entries(viso_tsdf* t, const viso_tsdf_entry* entries, size_t n) {
     const char* where = "viso_tsdf_add_entries";
-    if (!voxel_known(g_tsdfs, t)) { viso_set_error("%s: not a live TSDF handle", where); return VISO_ERR_ARG; }
+    if (!tsdf_kind_ok(where, t, false)) return VISO_ERR_ARG;
     if (n && !entries) { viso_set_error("%s: bad argument (null entries)", where); return VISO_ERR_ARG; }
     const long long lim = (long long)t->p.trunc_voxels * 1024;
     for (size_t i = 0; i < n; ++i) {
         const viso_tsdf_entry& e = entries[i];
-        bool ok = e.weight >= 1 && e.sum <= lim * (long long)e.weight && e.sum >= -lim * (long long)e.weight;
-        for (int k = 0; k < 3; ++k) ok = ok && e.k[k] >= -MAP_BIAS && e.k[k] < MAP_BIAS;
-        if (!ok) { viso_set_error("%s: entry %zu is not a voxel of this map (k in -2^20 .. 2^20 - 1, weight >= 1, |sum| <= %lld weight)", where, i, lim); return VISO_ERR_ARG; }
+        if (!tsdf_entry_ok(e.k, e.weight, e.sum, lim)) { viso_set_error("%s: entry %zu is not a voxel of this map (k in -2^20 .. 2^20 - 1, weight >= 1, |sum| <= %lld weight)", where, i, lim); return VISO_ERR_ARG; }
     }
     return voxel_add_entries(where, g_tsdfs, t, entries, n, sizeof(viso_tsdf_entry), [t, n](const void* d, dim3 grid, hipStream_t s) {
         hipLaunchKernelGGL(tsdf_add_entries_kernel, grid, dim3(256), 0, s, t->t, static_cast<const viso_tsdf_entry*>(d), (unsigned long long)n);
     });
 }
 
+extern "C" int viso_tsdf_add_gray_entries(viso_tsdf* t, const viso_tsdf_gray_entry* entries, size_t n) {
+    const char* where = "viso_tsdf_add_gray_entries";
+    if (!tsdf_kind_ok(where, t, true)) return VISO_ERR_ARG;
+    if (n && !entries) { viso_set_error("%s: bad argument (null entries)", where); return VISO_ERR_ARG; }
+    const long long lim = (long long)t->p.trunc_voxels * 1024;
+    for (size_t i = 0; i < n; ++i) {
+        const viso_tsdf_gray_entry& e = entries[i];
+        if (!tsdf_entry_ok(e.k, e.weight, e.sum, lim) || e.gray > 255ull * e.weight) {
+            viso_set_error("%s: entry %zu is not a voxel of this map (k in -2^20 .. 2^20 - 1, weight >= 1, |sum| <= %lld weight, gray <= 255 weight)", where, i, lim);
+            return VISO_ERR_ARG;
+        }
+    }
+    return voxel_add_entries(where, g_tsdfs, t, entries, n, sizeof(viso_tsdf_gray_entry), [t, n](const void* d, dim3 grid, hipStream_t s) {
+        hipLaunchKernelGGL(tsdf_gray_add_entries_kernel, grid, dim3(256), 0, s, t->g(), static_cast<const viso_tsdf_gray_entry*>(d), (unsigned long long)n);
+    });
+}
+
 static inline unsigned long long key_of(const int32_t* k) { return voxel_key(k[0], k[1], k[2]); }
 static inline bool voxel_item_less(const viso_tsdf_entry& x, const viso_tsdf_entry& y) { return key_of(x.k) < key_of(y.k); }
+static inline bool voxel_item_less(const viso_tsdf_gray_entry& x, const viso_tsdf_gray_entry& y) { return key_of(x.k) < key_of(y.k); }
 static inline bool voxel_item_less(const viso_tsdf_crossing& x, const viso_tsdf_crossing& y) {
     const unsigned long long a = key_of(x.k), b = key_of(y.k);
     return a != b ? a < b : x.axis < y.axis;
@@ -542,6 +750,14 @@ extern "C" int viso_tsdf_count(viso_tsdf* t, uint32_t min_weight, size_t* n) {
 }
 extern "C" int viso_tsdf_get(viso_tsdf* t, uint32_t min_weight, viso_tsdf_entry* entries_out, size_t n_cap, size_t* n) {
     return tsdf_extract<viso_tsdf_entry>("viso_tsdf_get", t, min_weight, false, entries_out, n_cap, n, tsdf_compact_kernel);
+}
+extern "C" int viso_tsdf_get_gray(viso_tsdf* t, uint32_t min_weight, viso_tsdf_gray_entry* entries_out, size_t n_cap, size_t* n) {
+    const char* where = "viso_tsdf_get_gray";
+    if (!tsdf_kind_ok(where, t, true)) return VISO_ERR_ARG;
+    return voxel_extract<viso_tsdf_gray_entry>(where, g_tsdfs, t, min_weight, false, entries_out, n_cap, n,
+                                               [=](viso_tsdf_gray_entry* out, unsigned long long out_cap, hipStream_t s) {
+        hipLaunchKernelGGL(tsdf_gray_compact_kernel, tsdf_slot_grid(t), dim3(256), 0, s, t->g(), min_weight, out, out_cap);
+    });
 }
 extern "C" int viso_tsdf_surface_count(viso_tsdf* t, uint32_t min_weight, size_t* n) {
     return tsdf_extract<viso_tsdf_crossing>("viso_tsdf_surface_count", t, min_weight, true, nullptr, 0, n, tsdf_crossings_kernel);
@@ -672,11 +888,11 @@ extern "C" int viso_tsdf_mesh(viso_tsdf* t, uint32_t min_weight, viso_tsdf_mesh_
     return tsdf_mesh_extract("viso_tsdf_mesh", t, min_weight, false, vertices_out, nv_cap, triangles_out, nt_cap, n_vertices, n_triangles);
 }
 
-extern "C" int viso_tsdf_render(viso_tsdf* t, uint32_t min_weight, const viso_param* param, int rows, int cols, double max_depth,
-                                const double* poses_or_null, int n_views, int16_t* disp_out, uint32_t* weight_out_or_null) {
-    const char* where = "viso_tsdf_render";
+// viso_tsdf_render (gray_out null) and viso_tsdf_render_gray
+static int tsdf_render(const char* where, viso_tsdf* t, uint32_t min_weight, const viso_param* param, int rows, int cols, double max_depth,
+                       const double* poses_or_null, int n_views, int16_t* disp_out, uint32_t* weight_out_or_null, bool gray, uint8_t* gray_out) {
     // what does not need the map first, so that nothing of a wrong call reaches a handle
-    if (min_weight < 1 || !param || !disp_out || rows < 1 || cols < 1 || n_views < 1 || (!poses_or_null && n_views != 1) ||
+    if (min_weight < 1 || (gray && !gray_out) || !param || !disp_out || rows < 1 || cols < 1 || n_views < 1 || (!poses_or_null && n_views != 1) ||
         !(std::isfinite(max_depth) && max_depth > 0.0)) {
         viso_set_error("%s: bad argument (min_weight >= 1, non-null calibration and output, sizes >= 1, a finite max_depth > 0, n_views >= 1 "
                        "and 1 without poses)", where);
@@ -693,7 +909,10 @@ extern "C" int viso_tsdf_render(viso_tsdf* t, uint32_t min_weight, const viso_pa
             if (!std::isfinite(poses_or_null[i])) { viso_set_error("%s: bad argument (pose %zu has an entry that is not finite)", where, i / 16); return VISO_ERR_ARG; }
         }
     }
-    if (!voxel_known(g_tsdfs, t)) { viso_set_error("%s: not a live TSDF handle", where); return VISO_ERR_ARG; }
+    if (gray ? !tsdf_kind_ok(where, t, true) : !voxel_known(g_tsdfs, t)) {
+        if (!gray) viso_set_error("%s: not a live TSDF handle", where);
+        return VISO_ERR_ARG;
+    }
     const double steps = floor(max_depth / t->hs);
     if (!(steps >= 1.0 && steps <= 65536.0)) {
         viso_set_error("%s: bad argument (max_depth %g is %g steps of half a voxel: 1 .. 65536)", where, max_depth, steps);
@@ -703,12 +922,74 @@ extern "C" int viso_tsdf_render(viso_tsdf* t, uint32_t min_weight, const viso_pa
     a.t = t->t;
     a.rows = rows; a.cols = cols; a.n_samples = (int)steps; a.min_weight = min_weight;
     a.f = param->f; a.cu = param->cu; a.cv = param->cv; a.base = param->base; a.s = t->s; a.h = t->hs;
+    const unsigned long long* table_gray = t->gray;
     return voxel_render(where, g_tsdfs, t, (size_t)rows * cols, poses_or_null, n_views, disp_out, weight_out_or_null,
-                        [a](const double* d_poses, int16_t* d_disp, uint32_t* d_weight, dim3 grid, hipStream_t s) {
+                        [a, table_gray](const double* d_poses, int16_t* d_disp, uint32_t* d_weight, uint8_t* d_gray, dim3 grid, hipStream_t s) {
         TsdfRenderArgs g = a;
         g.poses = d_poses; g.disp = d_disp; g.weight = d_weight;
-        hipLaunchKernelGGL(tsdf_render_kernel, grid, dim3(256), 0, s, g);
-    });
+        if (d_gray) {
+            TsdfGrayRenderArgs gg;
+            gg.a = g; gg.gray = table_gray; gg.out = d_gray;
+            hipLaunchKernelGGL(tsdf_gray_render_kernel, grid, dim3(256), 0, s, gg);
+        } else {
+            hipLaunchKernelGGL(tsdf_render_kernel, grid, dim3(256), 0, s, g);
+        }
+    }, gray_out);
+}
+
+extern "C" int viso_tsdf_render(viso_tsdf* t, uint32_t min_weight, const viso_param* param, int rows, int cols, double max_depth,
+                                const double* poses_or_null, int n_views, int16_t* disp_out, uint32_t* weight_out_or_null) {
+    return tsdf_render("viso_tsdf_render", t, min_weight, param, rows, cols, max_depth, poses_or_null, n_views, disp_out, weight_out_or_null,
+                       false, nullptr);
+}
+extern "C" int viso_tsdf_render_gray(viso_tsdf* t, uint32_t min_weight, const viso_param* param, int rows, int cols, double max_depth,
+                                     const double* poses_or_null, int n_views, int16_t* disp_out, uint32_t* weight_out_or_null, uint8_t* gray_out) {
+    return tsdf_render("viso_tsdf_render_gray", t, min_weight, param, rows, cols, max_depth, poses_or_null, n_views, disp_out,
+                       weight_out_or_null, true, gray_out);
+}
+
+extern "C" int viso_tsdf_vertex_gray(viso_tsdf* t, const viso_tsdf_mesh_vertex* vertices, size_t n, uint8_t* gray_out, size_t* n_missing_or_null) {
+    const char* where = "viso_tsdf_vertex_gray";
+    if (!tsdf_kind_ok(where, t, true)) return VISO_ERR_ARG;
+    if (n && (!vertices || !gray_out)) { viso_set_error("%s: bad argument (non-null vertices and output)", where); return VISO_ERR_ARG; }
+    for (size_t i = 0; i < n; ++i) {
+        const viso_tsdf_mesh_vertex& v = vertices[i];
+        bool ok = v.dir >= 1 && v.dir <= 7;
+        for (int k = 0; k < 3 && ok; ++k) ok = v.k[k] >= -MAP_BIAS && v.k[k] < MAP_BIAS - ((v.dir >> k) & 1);
+        if (!ok) {
+            viso_set_error("%s: vertex %zu is not an edge of this map (dir in 1..7, k in -2^20 .. 2^20 - 1, and below 2^20 - 1 along dir)", where, i);
+            return VISO_ERR_ARG;
+        }
+    }
+    int r;
+    VoxelHost* h;
+    if ((r = voxel_enter(where, g_tsdfs, t, &h)) < 0) return r;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (h->overflowed) return voxel_refuse_overflowed(where, h);
+    if (n_missing_or_null) *n_missing_or_null = 0;
+    if (!n) return VISO_OK;
+    const size_t b_verts = n * sizeof(viso_tsdf_mesh_vertex);
+    char* d = nullptr;
+    if (hipMalloc((void**)&d, b_verts + n) != hipSuccess) {
+        (void)hipGetLastError();
+        viso_set_error("%s: cannot allocate %zu bytes for the vertices", where, b_verts + n);
+        return VISO_ERR_NOMEM;
+    }
+    const viso_tsdf_mesh_vertex* d_verts = reinterpret_cast<const viso_tsdf_mesh_vertex*>(d);
+    uint8_t* d_out = reinterpret_cast<uint8_t*>(d + b_verts);
+    hipError_t e = hipMemcpy(d, vertices, b_verts, hipMemcpyHostToDevice);
+    unsigned long long missing = 0;
+    if (e == hipSuccess) {
+        r = voxel_pass(h, [&](hipStream_t s) {
+            hipLaunchKernelGGL(tsdf_gray_sample_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, t->g(), d_verts, (unsigned long long)n, d_out);
+        }, &missing);
+        if (r >= 0) e = hipMemcpy(gray_out, d_out, n, hipMemcpyDeviceToHost);
+    }
+    (void)hipFree(d);   // on every path
+    if (r < 0) return r;
+    HIP_TRY(e);
+    if (n_missing_or_null) *n_missing_or_null = (size_t)missing;
+    return VISO_OK;
 }
 
 extern "C" int viso_tsdf_stats(viso_tsdf* t, viso_tsdf_counters* out) {

@@ -28,6 +28,7 @@ struct VoxelHost {
     VoxelTable head; void* block;            // one allocation: keys | payload | stats | words
     bool overflowed;
     int16_t* d_disp; size_t d_disp_bytes;    // staging of a fuse's host map (grow-only)
+    uint8_t* d_image; size_t d_image_bytes;  // staging of a fuse's host image (grow-only; a kind that fuses none never has one)
     double* d_pose; size_t d_pose_bytes;     // the poses of a call (grow-only)
     std::mutex mu;
 };
@@ -40,8 +41,10 @@ struct VoxelRegistry {
 };
 
 using VoxelLaunch = std::function<void(hipStream_t)>;                                             // the clear
-using VoxelFuseLaunch = std::function<void(const VoxelFuseArgs&, dim3 grid, hipStream_t)>;        // one group of frames
-using VoxelRenderLaunch = std::function<void(const double* d_poses, int16_t* d_disp, uint32_t* d_weight, dim3 grid, hipStream_t)>;   // one group of views
+// one group of frames; d_image: the group's first image on the device, or null when the call has none
+using VoxelFuseLaunch = std::function<void(const VoxelFuseArgs&, const uint8_t* d_image, dim3 grid, hipStream_t)>;
+// one group of views; d_gray: the group's part of the third output, or null when the call has none
+using VoxelRenderLaunch = std::function<void(const double* d_poses, int16_t* d_disp, uint32_t* d_weight, uint8_t* d_gray, dim3 grid, hipStream_t)>;
 using VoxelEntriesLaunch = std::function<void(const void* d_entries, dim3 grid, hipStream_t)>;   // add_entries
 
 bool voxel_known(VoxelRegistry& reg, const void* handle);
@@ -62,19 +65,23 @@ int voxel_free(const char* where, VoxelHost* h);
 int voxel_clear(const char* where, VoxelRegistry& reg, const void* handle, const VoxelLaunch& clear);
 
 // map_fuse_resident / tsdf_fuse_resident (common.h) and viso_*_fuse, whole: the handle and argument checks, the staging of the
-// poses and of the host map, the groups of frames, each started by `launch`, and the wait that finds a full table
+// poses and of the host map, the groups of frames, each started by `launch`, and the wait that finds a full table.  image (or
+// null): frame f's 8-bit image at image + f * ifs on the device (resident), or one host image of the map's size that is staged like
+// the map (host); each group's launch is handed its first image.
 int voxel_fuse_resident(const char* where, VoxelRegistry& reg, const void* handle, viso_ctx* c, const int16_t* disp, size_t mfs, int rows,
-                        int cols, int n_frames, double f, double cu, double cv, double base, const double* poses, const VoxelFuseLaunch& launch);
+                        int cols, int n_frames, double f, double cu, double cv, double base, const double* poses, const VoxelFuseLaunch& launch,
+                        const uint8_t* image = nullptr, size_t ifs = 0);
 int voxel_fuse_host(const char* where, VoxelRegistry& reg, const void* handle, const int16_t* disp, int rows, int cols, const viso_param* param,
-                    const double* pose_or_null, const VoxelFuseLaunch& launch);
+                    const double* pose_or_null, const VoxelFuseLaunch& launch, const uint8_t* image = nullptr);
 // viso_*_add_entries behind the handle check and the validation of the n entries of entry_bytes each
 int voxel_add_entries(const char* where, VoxelRegistry& reg, const void* handle, const void* entries, size_t n, size_t entry_bytes,
                       const VoxelEntriesLaunch& launch);
 // viso_*_render behind the handle and argument checks: the map entered, locked and not overflowed; the poses [n_views][16] (or
-// null) through d_pose; a device buffer for n_views maps of px int16 and, with weight_out, as many uint32, freed on every path; the
-// groups of views, each started by `launch` with its poses ([.][12] or null) and its part of the buffer; the copies to the host.
+// null) through d_pose; a device buffer for n_views maps of px int16 and, with weight_out, as many uint32, and, with gray_out, as
+// many uint8, freed on every path; the groups of views, each started by `launch` with its poses ([.][12] or null) and its part of
+// the buffer; the copies to the host.
 int voxel_render(const char* where, VoxelRegistry& reg, const void* handle, size_t px, const double* poses, int n_views, int16_t* disp_out,
-                 uint32_t* weight_out, const VoxelRenderLaunch& launch);
+                 uint32_t* weight_out, const VoxelRenderLaunch& launch, uint8_t* gray_out = nullptr);
 // viso_*_stats: the four counters summed over the sets (VOXEL_ST_*) and the dropped word
 int voxel_stats(const char* where, VoxelRegistry& reg, const void* handle, const void* out, unsigned long long sums[4], unsigned long long* dropped);
 

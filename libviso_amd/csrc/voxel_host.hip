@@ -1,6 +1,6 @@
 // voxel_host.hip — the host side of the shared table layer (voxel_host.h): the registry of live handles, the life of a table, the
-// staging and the group loop of a fuse, the scaffold of add_entries, the pass of an extraction, the staging and the output buffer of
-// a render and the read-back of the statistics.
+// staging (the map, the poses and, where a kind fuses one, the image) and the group loop of a fuse, the scaffold of add_entries, the
+// pass of an extraction, the staging and the output buffer of a render and the read-back of the statistics.
 // No kernel is here: every kind passes its launches in.
 #include "voxel_host.h"
 
@@ -63,7 +63,7 @@ int voxel_create(const char* where, VoxelRegistry& reg, viso_ctx* ctx_or_null, i
     h->head.words = reinterpret_cast<unsigned long long*>(at);
     h->head.mask = (uint32_t)(slots - 1);
     h->overflowed = false;
-    h->d_disp = nullptr; h->d_disp_bytes = 0; h->d_pose = nullptr; h->d_pose_bytes = 0;
+    h->d_disp = nullptr; h->d_disp_bytes = 0; h->d_image = nullptr; h->d_image_bytes = 0; h->d_pose = nullptr; h->d_pose_bytes = 0;
     return VISO_OK;
 }
 
@@ -95,6 +95,7 @@ int voxel_free(const char* where, VoxelHost* h) {
     if (voxel_ctx_live(h)) note(hipStreamSynchronize(h->ctx->stream));   // a destroyed context has waited for its streams itself
     note(hipFree(h->block));
     if (h->d_disp) note(hipFree(h->d_disp));
+    if (h->d_image) note(hipFree(h->d_image));
     if (h->d_pose) note(hipFree(h->d_pose));
     if (first != hipSuccess) { viso_set_error("%s: %s", where, hipGetErrorString(first)); return VISO_ERR_HIP; }
     return VISO_OK;
@@ -167,9 +168,10 @@ static int voxel_stage_poses(const char* where, VoxelHost* h, const double* pose
     return VISO_OK;
 }
 
-// h is entered and locked; disp on its device
+// h is entered and locked; disp, and image if there is one, on its device
 static int voxel_fuse_device(const char* where, VoxelHost* h, const int16_t* disp, size_t mfs, int rows, int cols, int n_frames, double f,
-                             double cu, double cv, double base, const double* poses, const VoxelFuseLaunch& launch) {
+                             double cu, double cv, double base, const double* poses, const VoxelFuseLaunch& launch, const uint8_t* image,
+                             size_t ifs) {
     if (h->overflowed) return voxel_refuse_overflowed(where, h);
     hipStream_t s = h->ctx->stream;
     int r;
@@ -183,14 +185,15 @@ static int voxel_fuse_device(const char* where, VoxelHost* h, const int16_t* dis
         const int nf = n_frames - f0 < VOXEL_GROUP ? n_frames - f0 : VOXEL_GROUP;
         a.disp = disp + (size_t)f0 * mfs;
         a.poses = poses ? h->d_pose + (size_t)f0 * 12 : nullptr;
-        launch(a, dim3((unsigned)((px + 255) / 256), (unsigned)nf), s);
+        launch(a, image ? image + (size_t)f0 * ifs : nullptr, dim3((unsigned)((px + 255) / 256), (unsigned)nf), s);
         HIP_TRY(hipGetLastError());
     }
     return voxel_finish(where, h);
 }
 
 int voxel_fuse_resident(const char* where, VoxelRegistry& reg, const void* handle, viso_ctx* c, const int16_t* disp, size_t mfs, int rows,
-                        int cols, int n_frames, double f, double cu, double cv, double base, const double* poses, const VoxelFuseLaunch& launch) {
+                        int cols, int n_frames, double f, double cu, double cv, double base, const double* poses, const VoxelFuseLaunch& launch,
+                        const uint8_t* image, size_t ifs) {
     if (!voxel_known(reg, handle)) return voxel_not_live(where, reg);
     int r;
     VoxelHost* h;
@@ -198,11 +201,11 @@ int voxel_fuse_resident(const char* where, VoxelRegistry& reg, const void* handl
     if ((r = voxel_enter(where, reg, handle, &h)) < 0) return r;
     if (h->ctx != c) { viso_set_error("%s: the %s and the batch must share a context", where, reg.kind.noun); return VISO_ERR_ARG; }
     std::lock_guard<std::mutex> lk(h->mu);
-    return voxel_fuse_device(where, h, disp, mfs, rows, cols, n_frames, f, cu, cv, base, poses, launch);
+    return voxel_fuse_device(where, h, disp, mfs, rows, cols, n_frames, f, cu, cv, base, poses, launch, image, ifs);
 }
 
 int voxel_fuse_host(const char* where, VoxelRegistry& reg, const void* handle, const int16_t* disp, int rows, int cols, const viso_param* param,
-                    const double* pose_or_null, const VoxelFuseLaunch& launch) {
+                    const double* pose_or_null, const VoxelFuseLaunch& launch, const uint8_t* image) {
     if (!voxel_known(reg, handle)) return voxel_not_live(where, reg);
     if (!disp || !param || rows <= 0 || cols <= 0) { viso_set_error("%s: bad argument (non-null map and calibration, sizes > 0)", where); return VISO_ERR_ARG; }
     int r;
@@ -215,7 +218,12 @@ int voxel_fuse_host(const char* where, VoxelRegistry& reg, const void* handle, c
     hipStream_t s = h->ctx->stream;
     if ((r = voxel_grow(where, &h->d_disp, &h->d_disp_bytes, px * sizeof(int16_t), s)) < 0) return r;
     HIP_TRY(hipMemcpyAsync(h->d_disp, disp, px * sizeof(int16_t), hipMemcpyHostToDevice, s));
-    return voxel_fuse_device(where, h, h->d_disp, px, rows, cols, 1, param->f, param->cu, param->cv, param->base, pose_or_null, launch);
+    if (image) {
+        if ((r = voxel_grow(where, &h->d_image, &h->d_image_bytes, px, s)) < 0) return r;
+        HIP_TRY(hipMemcpyAsync(h->d_image, image, px, hipMemcpyHostToDevice, s));
+    }
+    return voxel_fuse_device(where, h, h->d_disp, px, rows, cols, 1, param->f, param->cu, param->cv, param->base, pose_or_null, launch,
+                             image ? h->d_image : nullptr, px);
 }
 
 int voxel_add_entries(const char* where, VoxelRegistry& reg, const void* handle, const void* entries, size_t n, size_t entry_bytes,
@@ -256,16 +264,17 @@ int voxel_pass(VoxelHost* h, const VoxelLaunch& launch, unsigned long long* n) {
 }
 
 int voxel_render(const char* where, VoxelRegistry& reg, const void* handle, size_t px, const double* poses, int n_views, int16_t* disp_out,
-                 uint32_t* weight_out, const VoxelRenderLaunch& launch) {
+                 uint32_t* weight_out, const VoxelRenderLaunch& launch, uint8_t* gray_out) {
     int r;
     VoxelHost* h;
     if ((r = voxel_enter(where, reg, handle, &h)) < 0) return r;
     std::lock_guard<std::mutex> lk(h->mu);
     if (h->overflowed) return voxel_refuse_overflowed(where, h);
     hipStream_t s = h->ctx->stream;
-    const size_t per = weight_out ? 6 : 2;   // bytes a pixel: the weights, then the maps
+    const size_t per = (weight_out ? 6 : 2) + (gray_out ? 1 : 0);   // bytes a pixel: the weights, then the maps, then the intensities
     if (px > (size_t)-1 / per / (size_t)n_views) { viso_set_error("%s: %d views of %zu pixels are beyond the address space", where, n_views, px); return VISO_ERR_NOMEM; }
-    const size_t n = (size_t)n_views * px, b_weight = weight_out ? n * sizeof(uint32_t) : 0, bytes = b_weight + n * sizeof(int16_t);
+    const size_t n = (size_t)n_views * px, b_weight = weight_out ? n * sizeof(uint32_t) : 0, b_disp = n * sizeof(int16_t),
+                 bytes = b_weight + b_disp + (gray_out ? n : 0);
     std::vector<double> rows12;   // alive until the stream has been waited for
     if (poses && (r = voxel_stage_poses(where, h, poses, n_views, rows12)) < 0) return r;
     void* d = nullptr;
@@ -277,15 +286,17 @@ int voxel_render(const char* where, VoxelRegistry& reg, const void* handle, size
     }
     uint32_t* d_weight = weight_out ? static_cast<uint32_t*>(d) : nullptr;
     int16_t* d_disp = reinterpret_cast<int16_t*>(static_cast<char*>(d) + b_weight);
+    uint8_t* d_gray = gray_out ? static_cast<uint8_t*>(d) + b_weight + b_disp : nullptr;
     hipError_t e = hipSuccess;
     for (int v0 = 0; v0 < n_views && e == hipSuccess; v0 += VOXEL_GROUP) {
         const int nv = n_views - v0 < VOXEL_GROUP ? n_views - v0 : VOXEL_GROUP;
         launch(poses ? h->d_pose + (size_t)v0 * 12 : nullptr, d_disp + (size_t)v0 * px, d_weight ? d_weight + (size_t)v0 * px : nullptr,
-               dim3((unsigned)((px + 255) / 256), (unsigned)nv), s);
+               d_gray ? d_gray + (size_t)v0 * px : nullptr, dim3((unsigned)((px + 255) / 256), (unsigned)nv), s);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(disp_out, d_disp, n * sizeof(int16_t), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess && d_weight) e = hipMemcpyAsync(weight_out, d_weight, b_weight, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && d_gray) e = hipMemcpyAsync(gray_out, d_gray, n, hipMemcpyDeviceToHost, s);
     const hipError_t e_wait = hipStreamSynchronize(s);   // nothing in flight touches the buffer that is freed next
     (void)hipFree(d);   // on every path
     HIP_TRY(e);

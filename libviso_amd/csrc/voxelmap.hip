@@ -152,7 +152,7 @@ static VoxelLaunch map_clear_launch(viso_map* m) {
     return [m](hipStream_t s) { hipLaunchKernelGGL(map_clear_kernel, dim3((m->t.head.mask + 1u) / 256u), dim3(256), 0, s, m->t); };
 }
 static VoxelFuseLaunch map_fuse_launch(viso_map* m) {
-    return [m](const VoxelFuseArgs& v, dim3 grid, hipStream_t s) {
+    return [m](const VoxelFuseArgs& v, const uint8_t*, dim3 grid, hipStream_t s) {   // (a voxel map fuses no image)
         FuseArgs a;
         a.v = v; a.s = m->s; a.t = m->t;
         hipLaunchKernelGGL(map_fuse_kernel, grid, dim3(256), 0, s, a);

@@ -1,5 +1,5 @@
 """python -m libviso_amd.fuse_map DISPARITY_DIR POSES.txt CALIB.txt OUT.ply [--voxel V --min-count N --min-disp PX --frames B E]
-                                 [--surface | --mesh [--trunc T --min-weight N] [--render DIR [--render-depth M]]]
+                                 [--surface | --mesh [--trunc T --min-weight N] [--render DIR [--render-depth M]] [--gray IMAGE_DIR]]
 
 Fuses the maps a KITTI runner wrote with --disparity DIR and the poses of its pose file into one voxel map on the device
 (libviso_amd.VoxelMap; include/viso_hip.h, "voxel map") and writes the occupied voxels as a binary PLY point cloud: x, y, z the
@@ -20,6 +20,10 @@ float32 centroid of each voxel, count the number of points fused into it.
                  input maps, by ray casting (include/viso_hip.h, "TSDF render"; --min-weight applies), and write DIR/<name of the
                  input map> in the format of the input maps (a pixel rendered beyond 255.9 px, which the format cannot hold, is
                  written as invalid).  --render-depth M: how far a ray is followed, in metres (40).
+  --gray IMAGE_DIR  with --surface or --mesh: fuse the left camera images with the maps (a gray TSDF map; include/viso_hip.h, "TSDF
+                 intensity").  IMAGE_DIR holds 8-bit grayscale PNGs with the maps' names and sizes (KITTI's image_0).  The PLY's
+                 vertices then carry the surface's intensity as red = green = blue after weight, and --render also writes
+                 DIR/gray/<name> as 8-bit PNGs, the intensity of every rendered pixel (0 where the map is invalid).
 
 Both runners write byte-identical directories and pose files for every rank count and chunk size, so the PLY is identical too."""
 import argparse
@@ -35,8 +39,9 @@ DISP_PNG_MAX = 4095   # the largest map value a 16-bit file holds (x 16)
 RENDER_VIEWS = 16     # views of one --render call
 
 
-def read_png16(path):
-    """A non-interlaced 16-bit grayscale PNG as uint16 [rows][cols]; all five row filters.  ValueError for anything else."""
+def _read_png_gray(path, want_depth):
+    """The bytes of a non-interlaced grayscale PNG of want_depth (8 or 16) bits as uint8 [rows][cols * want_depth / 8]; all five
+    row filters.  ValueError for anything else."""
     with open(path, "rb") as f:
         data = f.read()
     if data[:8] != b"\x89PNG\r\n\x1a\n":
@@ -59,16 +64,16 @@ def read_png16(path):
     if ihdr is None:
         raise ValueError(f"{path}: no IHDR chunk")
     cols, rows, depth, color, comp, filt, inter = ihdr
-    if (depth, color, comp, filt, inter) != (16, 0, 0, 0, 0) or rows < 1 or cols < 1:
-        raise ValueError(f"{path}: only non-interlaced 16-bit grayscale PNGs are read")
-    stride = 2 * cols
+    if (depth, color, comp, filt, inter) != (want_depth, 0, 0, 0, 0) or rows < 1 or cols < 1:
+        raise ValueError(f"{path}: only non-interlaced {want_depth}-bit grayscale PNGs are read")
+    bpp = want_depth // 8
+    stride = bpp * cols
     raw = np.frombuffer(zlib.decompress(b"".join(idat)), np.uint8)
     if raw.size != rows * (stride + 1):
         raise ValueError(f"{path}: {raw.size} bytes of image data, expected {rows * (stride + 1)}")
     raw = raw.reshape(rows, stride + 1)
     out = np.zeros((rows, stride), np.uint8)
     zero = np.zeros(stride, np.int32)
-    bpp = 2
     for y in range(rows):
         ft, line = int(raw[y, 0]), raw[y, 1:].astype(np.int32)
         up = out[y - 1].astype(np.int32) if y else zero
@@ -94,7 +99,18 @@ def read_png16(path):
         else:
             raise ValueError(f"{path}: unknown row filter {ft}")
         out[y] = (rec & 255).astype(np.uint8)
-    return out.view(">u2").astype(np.uint16)
+    return out
+
+
+def read_png16(path):
+    """A non-interlaced 16-bit grayscale PNG as uint16 [rows][cols]; all five row filters.  ValueError for anything else."""
+    return _read_png_gray(path, 16).view(">u2").astype(np.uint16)
+
+
+def read_png8(path):
+    """A non-interlaced 8-bit grayscale PNG (a camera image, KITTI's image_0) as uint8 [rows][cols]; all five row filters.
+    ValueError for anything else."""
+    return _read_png_gray(path, 8)
 
 
 def read_disparity_png(path):
@@ -105,21 +121,34 @@ def read_disparity_png(path):
     return d
 
 
+def _write_png_gray(path, rows, cols, depth, line_bytes):
+    """line_bytes: uint8 [rows][cols * depth / 8], the big-endian samples of a grayscale PNG of `depth` bits (row filter 0)."""
+    raw = np.zeros((rows, 1 + line_bytes.shape[1]), np.uint8)
+    raw[:, 1:] = line_bytes
+
+    def chunk(kind, body):
+        return struct.pack(">I", len(body)) + kind + body + struct.pack(">I", zlib.crc32(kind + body) & 0xffffffff)
+
+    with open(path, "wb") as f:
+        f.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", cols, rows, depth, 0, 0, 0, 0)) +
+                chunk(b"IDAT", zlib.compress(raw.tobytes(), 6)) + chunk(b"IEND", b""))
+
+
 def write_png16(path, v):
     """uint16 [rows][cols] as a non-interlaced 16-bit grayscale PNG (row filter 0), which read_png16 reads back to the same array."""
     v = np.ascontiguousarray(v, np.uint16)
     if v.ndim != 2 or v.size == 0:
         raise ValueError("write_png16: a 2-D array with at least one pixel")
     rows, cols = v.shape
-    raw = np.zeros((rows, 1 + 2 * cols), np.uint8)
-    raw[:, 1:] = v.astype(">u2").view(np.uint8).reshape(rows, 2 * cols)
+    _write_png_gray(path, rows, cols, 16, v.astype(">u2").view(np.uint8).reshape(rows, 2 * cols))
 
-    def chunk(kind, body):
-        return struct.pack(">I", len(body)) + kind + body + struct.pack(">I", zlib.crc32(kind + body) & 0xffffffff)
 
-    with open(path, "wb") as f:
-        f.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", cols, rows, 16, 0, 0, 0, 0)) +
-                chunk(b"IDAT", zlib.compress(raw.tobytes(), 6)) + chunk(b"IEND", b""))
+def write_png8(path, v):
+    """uint8 [rows][cols] as a non-interlaced 8-bit grayscale PNG (row filter 0), which read_png8 reads back to the same array."""
+    v = np.asarray(v)
+    if v.dtype != np.uint8 or v.ndim != 2 or v.size == 0:
+        raise ValueError("write_png8: a 2-D uint8 array with at least one pixel")
+    _write_png_gray(path, v.shape[0], v.shape[1], 8, np.ascontiguousarray(v))
 
 
 def write_disparity_png(path, d16):
@@ -182,9 +211,12 @@ def main(argv=None):
     ap.add_argument("--min-weight", type=int, default=1, help="with --surface or --mesh: only voxels with at least this many updates (1)")
     ap.add_argument("--render", metavar="DIR", help="with --surface or --mesh: also write the model rendered at every fused pose into DIR")
     ap.add_argument("--render-depth", type=float, default=40.0, metavar="M", help="with --render: how far a ray is followed, metres (40)")
+    ap.add_argument("--gray", metavar="IMAGE_DIR", help="with --surface or --mesh: fuse the 8-bit left images of the maps' names with them")
     a = ap.parse_args(argv)
     if a.render and not (a.surface or a.mesh):
         ap.error("--render needs --surface or --mesh (only a TSDF map is rendered)")
+    if a.gray and not (a.surface or a.mesh):
+        ap.error("--gray needs --surface or --mesh (only a TSDF map carries intensity)")
     import libviso_amd
     from libviso_amd.abi import Param
     names, poses = list_maps(a.disparity_dir), read_poses(a.poses)
@@ -196,7 +228,8 @@ def main(argv=None):
     f, cu, cv, base = read_calib(a.calib)
     prm = Param.default(base=base, f=f, cu=cu, cv=cv)
     if a.surface or a.mesh:
-        tsdf = libviso_amd.TsdfMap(None, voxel=a.voxel, trunc_voxels=a.trunc, min_disp16=max(1, int(round(a.min_disp * 16))),
+        gray = bool(a.gray)
+        tsdf = libviso_amd.TsdfMap(None, gray=gray, voxel=a.voxel, trunc_voxels=a.trunc, min_disp16=max(1, int(round(a.min_disp * 16))),
                                    capacity_log2=26 if a.capacity_log2 is None else a.capacity_log2)
         try:
             shape = None
@@ -205,32 +238,44 @@ def main(argv=None):
                 shape = shape or m.shape
                 if a.render and m.shape != shape:
                     sys.exit(f"fuse_map: --render needs maps of one size, but {names[i]} is {m.shape[1]} x {m.shape[0]}")
-                tsdf.fuse(m, prm, pose=poses[i])
+                if gray:
+                    image = read_png8(os.path.join(a.gray, names[i]))
+                    if image.shape != m.shape:
+                        sys.exit(f"fuse_map: {names[i]} is {image.shape[1]} x {image.shape[0]} in {a.gray} but its map is {m.shape[1]} x {m.shape[0]}")
+                    tsdf.fuse(m, prm, pose=poses[i], image=image)
+                else:
+                    tsdf.fuse(m, prm, pose=poses[i])
             st = tsdf.stats()
             if a.render and e > b:
-                os.makedirs(a.render, exist_ok=True)
+                os.makedirs(os.path.join(a.render, "gray") if gray else a.render, exist_ok=True)
                 n_near = 0
                 for i0 in range(b, e, RENDER_VIEWS):   # several views a call
                     i1 = min(e, i0 + RENDER_VIEWS)
-                    views = tsdf.render(prm, shape, poses[i0:i1], max_depth=a.render_depth, min_weight=a.min_weight)
+                    views = tsdf.render(prm, shape, poses[i0:i1], max_depth=a.render_depth, min_weight=a.min_weight, gray=gray)
+                    views, shades = views if gray else (views, None)
                     near = views > DISP_PNG_MAX   # nearer than the files can say
                     n_near += int(near.sum())
                     views[near] = DISP_INVALID
                     for i in range(i0, i1):
                         write_disparity_png(os.path.join(a.render, names[i]), views[i - i0])
+                        if gray:
+                            write_png8(os.path.join(a.render, "gray", names[i]), np.where(near[i - i0], 0, shades[i - i0]).astype(np.uint8))
                 print(f"fuse_map: {e - b} views rendered to {a.render_depth} m ({n_near} pixels beyond 255.9 px left out) -> {a.render}")
+            shade = None   # the intensity of the PLY's vertices
             if a.mesh:
                 vertices, triangles = tsdf.mesh(a.min_weight)
+                shade = tsdf.vertex_gray(vertices) if gray else None
             else:
                 crossings = tsdf.surface(a.min_weight)
+                shade = tsdf.vertex_gray(crossings) if gray else None
         finally:
             tsdf.close()
         if a.mesh:
-            libviso_amd.write_mesh_ply(a.out, vertices, triangles)
+            libviso_amd.write_mesh_ply(a.out, vertices, triangles, shade)
             print(f"fuse_map: {e - b} maps, {st['n_points']} points, {st['n_updates']} updates ({st['n_out_of_range']} samples out of range), "
                   f"{st['n_occupied']} voxels, {len(vertices)} vertices and {len(triangles)} triangles at weight >= {a.min_weight} -> {a.out}")
             return 0
-        libviso_amd.write_surface_ply(a.out, crossings, a.voxel)
+        libviso_amd.write_surface_ply(a.out, crossings, a.voxel, shade)
         print(f"fuse_map: {e - b} maps, {st['n_points']} points, {st['n_updates']} updates ({st['n_out_of_range']} samples out of range), "
               f"{st['n_occupied']} voxels, {len(crossings)} crossings at weight >= {a.min_weight} -> {a.out}")
         return 0

@@ -16,7 +16,12 @@ repetitions):
                40 m, min_weight 2, one call: the launch, the copy of the views to the host and the free (time per view = / views).
                The marching rate is counted from the result: a pixel with a hit at depth zs has marched ceil(zs / h) samples, one
                without a hit all N = 400;
-  clear        viso_tsdf_clear.
+  clear        viso_tsdf_clear;
+  fuse_gray    Batch.fuse_tsdf of the same maps into a cleared gray map (include/viso_hip.h, "TSDF intensity") of the same capacity:
+               one more byte read a pixel and three atomics where fuse_tsdf has two per run head;
+  vertex_gray  TsdfMap.vertex_gray of the gray map's mesh vertices: the copy up, two probes a vertex, the copy back;
+  render_gray  TsdfMap.render(gray=True) of the same views over the gray map: beside `render`, one more 8-byte load a probe and one
+               more byte a pixel out.
 n_updates / n_points from viso_tsdf_stats is the number of voxels a pixel's band touches.  --kernel-only runs clear + fuse_tsdf
 --reps times and the extractions and the render once: the run to put under `rocprofv3 --kernel-trace --stats` for the kernels' own times.  The
 count the result is held against (not a measurement) is printed with it."""
@@ -108,10 +113,21 @@ def main():
         return
 
     vmap = libviso_amd.VoxelMap(ctx, capacity_log2=26)
+    has_gray = hasattr(libviso_amd.load(), "viso_tsdf_create_gray")   # (absent from older builds of the library: VISO_HIP_SO A/B runs)
+    if has_gray:
+        gmap = libviso_amd.TsdfMap(ctx, gray=True, capacity_log2=log2)
+        b.fuse_tsdf(gmap, poses)
+        gverts = gmap.mesh()[0]
+
+    def render_gray():
+        return gmap.render(seq["param"], (rows, cols), views, max_depth=40.0, min_weight=2, gray=True)
+
     for _ in range(2):   # warm-up
         tsdf.clear(); b.fuse_tsdf(tsdf, poses); tsdf.entries(); tsdf.surface(); tsdf.mesh(); render()
         vmap.clear(); b.fuse_disparities(vmap, poses)
-    legs = {k: [] for k in ("fuse_tsdf", "fuse_map", "entries", "surface", "mesh", "render", "clear")}
+        if has_gray:
+            gmap.clear(); b.fuse_tsdf(gmap, poses); gmap.vertex_gray(gverts); render_gray()
+    legs = {k: [] for k in ("fuse_tsdf", "fuse_map", "entries", "surface", "mesh", "render", "clear") + (("fuse_gray", "vertex_gray", "render_gray") if has_gray else ())}
     for _ in range(a.reps):   # alternating
         legs["clear"].append(clock(tsdf.clear))
         legs["fuse_tsdf"].append(clock(lambda: b.fuse_tsdf(tsdf, poses)))
@@ -121,10 +137,16 @@ def main():
         legs["surface"].append(clock(tsdf.surface))
         legs["mesh"].append(clock(tsdf.mesh))
         legs["render"].append(clock(render))
+        if has_gray:
+            gmap.clear()
+            legs["fuse_gray"].append(clock(lambda: b.fuse_tsdf(gmap, poses)))
+            legs["vertex_gray"].append(clock(lambda: gmap.vertex_gray(gverts)))
+            legs["render_gray"].append(clock(render_gray))
     st, n_vox, n_cross = tsdf.stats(), len(tsdf.entries()), len(tsdf.surface())
     n_vert, n_tri = (len(x) for x in tsdf.mesh())
     res = {"frames": nf, "shape": [int(rows), int(cols)], "params": "voxel 0.2, T 3, min_disp16 16", "capacity_log2": log2, "reps": a.reps,
            "ms_median": {k: float(np.median(v)) for k, v in legs.items()}, "ms_min": {k: float(np.min(v)) for k, v in legs.items()},
+           "ms_max": {k: float(np.max(v)) for k, v in legs.items()},
            "stats": st, "voxels": int(n_vox), "crossings": int(n_cross), "vertices": int(n_vert), "triangles": int(n_tri), "updates_per_point": st["n_updates"] / max(1, st["n_points"]),
            "map_stats": vmap.stats()}
     res["count_bytes"], res["count_ms"] = count_ms(nf, rows, cols)
@@ -132,12 +154,17 @@ def main():
     ms = res["ms_median"]["render"]
     res["render"] = {"views": int(len(views)), "max_depth": 40.0, "min_weight": 2, "valid": valid, "ms_per_view": ms / len(views),
                      "samples_marched": n_marched, "samples_per_s": n_marched / (ms * 1e-3)}
+    if has_gray:
+        res["gray"] = {"vertices": int(len(gverts)), "same_geometry": bool(gmap.entries().tobytes() == tsdf.entries().tobytes()),
+                       "ratio_to_plain": {g: res["ms_median"][g] / res["ms_median"][p] for g, p in (("fuse_gray", "fuse_tsdf"), ("render_gray", "render"))}}
     print(json.dumps(res))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
             json.dump(res, f, indent=1)
     tsdf.close(); vmap.close()
+    if has_gray:
+        gmap.close()
     b.close(); ctx.close()
 
 
