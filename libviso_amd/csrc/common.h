@@ -152,7 +152,7 @@ struct viso_ctx {
     struct PlainCache* plain;    // the plain family's image cache (plain.hip), created on first use
     // completion signal of the plain family's calls (PlainSignal below): a word of pinned memory the call's LAST kernel writes,
     // a device counter of that kernel's finished workgroups, the sequence number of the last signal asked for
-    int* sig_flag; int* sig_ctr; int sig_seq;
+    int* sig_flag; int* sig_ctr; uint32_t sig_seq;   // the number wraps; the wait compares differences
     unsigned long long serial;   // unique per created context: a voxel map tells its own context from a later one at the same address
 };
 
@@ -188,7 +188,7 @@ void plain_note_circle(viso_ctx* c, int cnt);
 int plain_try_ransac(viso_ctx* c, const double* X, const double* obs, int m, double best_tr[6], int32_t* best_inl, int* n_inl,
                      const viso_param* p, const int32_t* samples, uint64_t seed, uint64_t frame, int* ret);
 
-struct PlainSignal { int* ctr; int* flag; int seq; };   // a call's completion signal (described below); flag == nullptr: no signal
+struct PlainSignal { int* ctr; int* flag; uint32_t seq; };   // a call's completion signal (described below); flag == nullptr: no signal
 struct OutArgs;                                          // a copy-out into the call's pinned mirror (below)
 // match_circle on lists in device memory (circle.hip): counts by value, or read from the device when the pointers are set
 struct CircleArgs {
@@ -262,7 +262,7 @@ struct PlainStage {
 // number into a pinned word, and the host spins on that word with an acquire load (plain_signal_wait: bounded, then
 // hipStreamSynchronize as the fallback, so a lost signal costs time, never a hang or a result).
 int plain_signal_next(viso_ctx* c, PlainSignal* out);   // the next sequence number of the context (allocates on first use)
-int plain_signal_wait(viso_ctx* c, hipStream_t s, int seq);
+int plain_signal_wait(viso_ctx* c, hipStream_t s, uint32_t seq);
 int plain_blit(hipStream_t s, const void* src, void* dst, size_t head_words, const int* n_rows = nullptr, int row_words = 0, int max_rows = 0,
                const PlainSignal* sig = nullptr);
 #ifdef __HIPCC__
@@ -334,7 +334,7 @@ __device__ __forceinline__ void plain_signal_done(const PlainSignal& g, unsigned
         if (atomicAdd(g.ctr, 1) == (int)nblocks - 1) {   // the last workgroup of the launch: every other one has fenced and counted
             __threadfence_system();                      // (acquire side of the counter: what the others fenced is ordered before the flag)
             *g.ctr = 0;                                  // for the next signalling kernel (streams run them one after the other)
-            __hip_atomic_store(g.flag, g.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store(g.flag, (int)g.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
         }
     }
 }

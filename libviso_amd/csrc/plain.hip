@@ -145,7 +145,24 @@ static bool big_equal(const void* shadow, const void* user, size_t bytes) {
 
 #define PLAIN_SLOTS 4
 #define PLAIN_DISTRUST_FRAMES 64
-#define PLAIN_HDR 256      // bytes of an image's header block {n, bad}
+#define PLAIN_HDR 256      // bytes of an image's header block
+
+// An image slot's header, in the shadow and on the device: sort_kp_kernel writes {n, bad} and the view, which pack_desc_kernel's launch reads
+struct SlotHeader { int n, bad, pad[14]; ImageView view; };
+static_assert(offsetof(SlotHeader, bad) == 4 && offsetof(SlotHeader, view) == 64 && sizeof(SlotHeader) <= PLAIN_HDR, "slot header");
+// Offsets of a slot's pieces.  Shadow: kp | hdr | f32 rows, up to pin_end.  Device: kp | hdr | u16 rows | the aux pieces
+// (16-B aligned: skp 8n + sidx 4n + rank 4n | bstart + xinfo | qord | sums | rows8), up to dev_end.
+struct SlotLayout { size_t hdr, rows, pin_end, skp, sidx, rank, bstart, xinfo, qord, sums, rows8, dev_end; };
+static SlotLayout slot_layout(size_t n, int dlen) {
+    SlotLayout L;
+    L.hdr = al256(sizeof(float2) * n); L.rows = L.hdr + PLAIN_HDR; L.pin_end = L.rows + al256(sizeof(float) * n * dlen);
+    size_t o = L.rows + al256(sizeof(uint16_t) * VISO_ROW * n);
+    L.skp = o; L.sidx = o + 8 * n; L.rank = o + 12 * n; o += (16 * n + 15) / 16 * 16;
+    L.bstart = o; L.xinfo = o + 4 * (VISO_NB + 1); o += (4 * (VISO_NB + 1) + 32 + 15) / 16 * 16;
+    L.qord = o; o += (n + 63) / 64 * 64; L.sums = o; o += (8 * n + 15) / 16 * 16;
+    L.rows8 = o; L.dev_end = al256(o + VISO_ROW8 * n);
+    return L;
+}
 
 struct PlainSlot {
     bool valid;
@@ -169,6 +186,29 @@ struct PlainSlot {
 // the direct path.  Nothing is predicted about the DATA, only about which call comes next; a wrong guess costs the
 // guessed work, never a result.  $VISO_PLAIN_SPECULATE=0 / viso_plain_speculate(0) switch it off (every call direct).
 #define PF_PROBS 3      // 0 = stereo (L, R), 1 = temporal (L, previous L), 2 = temporal (R, previous R)
+// The frame block's counters and flags: 256 bytes at o_misc on the device, zeroed with the head by the blit in front of every
+// launch, and the first 256 bytes of the pinned mirror.  Who copies what into the mirror: outA, behind the sort kernel, the words
+// of the chain's first part (everything in front of n_circ) and the two images' own flags into img_bad (mirror only: on the device
+// those words stay zero); outJ, behind the join kernel, the join's eight words from n_circ on.
+struct FrameMisc {
+    int pad0[6];
+    int ovf_cnt;                  // length of the overflow queue (MatchProblem::ovf_cnt)
+    int bad[2];                   // launch_match_timed's `bad`: [0] "an image of this launch may be flagged", set in the head, read by the general kernels
+                                  // (clear: they leave at once); [1] tiles match_stereo_kernel declined: it counts, match_batch_kernel<1> and the host read
+    int pad1[7];
+    struct { int m_cnt; int pad; unsigned long long scored; } prob[PF_PROBS];   // matches and scored pairs of problem p
+    int pad2[4];
+    int n_circ;                   // the join's row count
+    int pad3[7];
+    int img_bad[2];               // the flags of the stereo call's two images (ImageView::bad), as their pack kernels left them
+    int pad4[22];
+};
+static_assert(sizeof(FrameMisc) == 256 && offsetof(FrameMisc, ovf_cnt) == 4 * 6 && offsetof(FrameMisc, bad) == 4 * 7 && offsetof(FrameMisc, prob) == 4 * 16 &&
+              sizeof(FrameMisc::prob[0]) == 16 && offsetof(FrameMisc, prob[0].scored) == 4 * 18 && offsetof(FrameMisc, n_circ) == 4 * 32 &&
+              offsetof(FrameMisc, img_bad) == 4 * 40, "the misc words stay where the kernels' pointers and the copy-outs expect them");
+// The RANSAC stage's result block at o_rs (SolverItem::kept, ok, n_inl, tr, inl; RefitMirror copies it)
+struct RansacOut { int kept, ok, n_inl, pad0[13]; double tr[6]; int pad1[4]; int inl[1]; };   // inl: one per row of the frame
+static_assert(offsetof(RansacOut, ok) == 4 && offsetof(RansacOut, n_inl) == 8 && offsetof(RansacOut, tr) == 64 && offsetof(RansacOut, inl) == 128, "result block");
 struct PlainFrame {
     bool valid;
     int L, R;                              // image slots of the stereo call
@@ -177,6 +217,7 @@ struct PlainFrame {
     char* dev; size_t dev_bytes;
     char* host; size_t host_bytes;         // pinned mirror of the result part [o_misc, o_end)
     size_t o_misc, o_sorted[PF_PROBS], o_x, o_X, o_circ, o_xc, o_Xpc, o_rs, o_end;
+    size_t o_res, o_pos, o_tile, scr_stride, o_ovf;   // device scratch behind o_end: problem p's res / pos / tile_flag at o_* + p * scr_stride; the overflow queue
     bool have[PF_PROBS], used[PF_PROBS];
     int nq[PF_PROBS], m[PF_PROBS];
     int tq[PF_PROBS], tt[PF_PROBS];
@@ -189,7 +230,7 @@ struct PlainFrame {
     bool have_B, pending_B, used_circ, used_rs;
     int n_circ;                            // rows of the join (host, once B has been waited for)
     viso_param rs_p; uint64_t rs_seed, rs_frame;
-    int seqJ, seqB;                        // sequence numbers of the join's copy-out (match_circle waits for this one only; the RANSAC
+    uint32_t seqJ, seqB;                   // sequence numbers of the join's copy-out (match_circle waits for this one only; the RANSAC
                                            // stage runs on) and of the RANSAC stage's copy-out
     bool pending_J;
 };
@@ -227,17 +268,17 @@ int plain_signal_next(viso_ctx* c, PlainSignal* out) {
         HIP_TRY(hipMemsetAsync(c->sig_ctr, 0, 256, c->stream));
         c->sig_seq = 0;
     }
-    c->sig_seq += 1;
+    c->sig_seq += 1;   // unsigned: wraps after 2^32 signals, which the wait's comparison of differences allows for
     out->ctr = c->sig_ctr; out->flag = c->sig_flag; out->seq = c->sig_seq;
     return VISO_OK;
 }
 
-int plain_signal_wait(viso_ctx* c, hipStream_t s, int seq) {
+int plain_signal_wait(viso_ctx* c, hipStream_t s, uint32_t seq) {
     static const int off = [] { const char* e = getenv("VISO_PLAIN_SIGNAL"); return e && *e == '0'; }();   // 0: always hipStreamSynchronize (A/B aid)
     if (c->sig_flag && !off) {
         const auto t0 = std::chrono::steady_clock::now();
         for (unsigned spin = 1;; ++spin) {
-            if ((int)((unsigned)__atomic_load_n(c->sig_flag, __ATOMIC_ACQUIRE) - (unsigned)seq) >= 0) return VISO_OK;
+            if ((int32_t)((uint32_t)__atomic_load_n(c->sig_flag, __ATOMIC_ACQUIRE) - seq) >= 0) return VISO_OK;
             cpu_relax();
             // a signal that does not come (a failed launch, a faulting kernel): the stream knows
             if ((spin & 4095u) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(20)) break;
@@ -284,8 +325,17 @@ int PlainStage::flush(hipStream_t s) {
     return plain_blit(s, h, d, off / 4);
 }
 
-static size_t aux_bytes(size_t n) {   // skp 8n + sidx 4n + rank 4n | bstart + xinfo | qord | sums | rows8, 16-B aligned pieces
-    return ((16 * n + 15) / 16) * 16 + ((4 * (VISO_NB + 1) + 32 + 15) / 16) * 16 + ((n + 63) / 64) * 64 + ((8 * n + 15) / 16) * 16 + VISO_ROW8 * n;
+// A grow-only block of an image slot or a frame, a quarter more than asked for: device memory (host_flags < 0) or pinned host memory.
+// Replaced only behind a synchronize: a kernel of an earlier call may still use the old block.
+static int plain_grow(viso_ctx* c, char** p, size_t* have, size_t need, int host_flags) {
+    if (*have >= need) return VISO_OK;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (*p) HIP_TRY(host_flags < 0 ? hipFree(*p) : hipHostFree(*p));
+    *p = nullptr; *have = 0;
+    need += need / 4;
+    HIP_TRY(host_flags < 0 ? hipMalloc((void**)p, need) : hipHostMalloc((void**)p, need, (unsigned)host_flags));
+    *have = need;
+    return VISO_OK;
 }
 
 static PlainCache* plain_cache(viso_ctx* c) {
@@ -314,31 +364,25 @@ void plain_cache_free(viso_ctx* c) {
     c->plain = nullptr;
 }
 
-extern "C" int viso_plain_cache(int enable) {
+static void frames_forget(PlainCache* pc) {   // nothing computed ahead is handed out any more, nothing is waited for
+    for (int i = 0; i < 3; ++i) { pc->frame[i].valid = false; pc->frame[i].pending_B = false; pc->frame[i].pending_J = false; }
+}
+// the two switches: behind the stream's work, set, and forget what was kept or learned under the old setting
+static int plain_switch(const char* who, bool cache, int enable) {
     PlainLock lk;
     viso_ctx* c = viso_default_ctx();
     if (!c) return VISO_ERR_HIP;
     PlainCache* pc = plain_cache(c);
-    if (!pc) { viso_set_error("viso_plain_cache: out of memory"); return VISO_ERR_NOMEM; }
+    if (!pc) { viso_set_error("%s: out of memory", who); return VISO_ERR_NOMEM; }
     HIP_TRY(hipStreamSynchronize(c->stream));
-    pc->enabled = enable != 0;
-    for (int i = 0; i < PLAIN_SLOTS; ++i) pc->slot[i].valid = false;
-    for (int i = 0; i < 3; ++i) { pc->frame[i].valid = false; pc->frame[i].pending_B = false; pc->frame[i].pending_J = false; }
+    (cache ? pc->enabled : pc->speculate) = enable != 0;
+    frames_forget(pc);
+    if (cache) for (int i = 0; i < PLAIN_SLOTS; ++i) pc->slot[i].valid = false;
+    else pc->tm_pattern = pc->x_pattern = pc->circ_pattern = pc->rs_pattern = pc->rs_delta_stable = false;
     return VISO_OK;
 }
-
-extern "C" int viso_plain_speculate(int enable) {
-    PlainLock lk;
-    viso_ctx* c = viso_default_ctx();
-    if (!c) return VISO_ERR_HIP;
-    PlainCache* pc = plain_cache(c);
-    if (!pc) { viso_set_error("viso_plain_speculate: out of memory"); return VISO_ERR_NOMEM; }
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    pc->speculate = enable != 0;
-    for (int i = 0; i < 3; ++i) { pc->frame[i].valid = false; pc->frame[i].pending_B = false; pc->frame[i].pending_J = false; }
-    pc->tm_pattern = pc->x_pattern = pc->circ_pattern = pc->rs_pattern = pc->rs_delta_stable = false;
-    return VISO_OK;
-}
+extern "C" int viso_plain_cache(int enable) { return plain_switch("viso_plain_cache", true, enable); }
+extern "C" int viso_plain_speculate(int enable) { return plain_switch("viso_plain_speculate", false, enable); }
 
 // out[0..3] = calls answered from a frame's results (temporal match_desc, collect_matches, triangulate_rectified, -),
 // out[4..7] = results computed ahead that no call asked for
@@ -371,34 +415,29 @@ extern "C" int viso_plain_cache_stats(int64_t* hits, int64_t* misses) {
 
 // $VISO_PLAIN_TRACE=1: host microseconds of viso_match_desc by phase, summed per call kind (0 = both images resident,
 // 1 / 2 = one / two uploaded), printed to stderr by viso_plain_trace_dump() (a measurement aid, tools/dropin_probe.py)
-static double g_tr_us[3][6];
-static long g_tr_n[3];
+static struct PlainTrace {
+    double us[3][6]; long n[3];
+    double acq_us[3]; long acq_n, acq_calls;
+    double srv_us[2]; long srv_n;         // temporal calls answered from the frame: [0] the two look-ups, [1] the rest
+    double wait_us[2]; long wait_n[2];    // waits of the frame's later calls: [0] match_circle for the join, [1] ransac_minimize_reproj for the stage
+} g_tr;
 static int g_tr_on = -1;
-static double g_acq_us[3];
-static long g_acq_n, g_acq_calls;
-static double g_srv_us[2];    // temporal calls answered from the frame: [0] the two look-ups, [1] the rest
-static long g_srv_n;
-static double g_wait_us[2];   // waits of the frame's later calls: [0] match_circle for the join, [1] ransac_minimize_reproj for the stage
-static long g_wait_n[2];
 static double tr_now() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 extern "C" void viso_plain_trace_dump(void) {
     static const char* ph[6] = {"acquire_q", "acquire_t", "setup+blit_in", "launches", "wait", "copy_out"};
     for (int k = 0; k < 3; ++k) {
-        if (!g_tr_n[k]) continue;
-        fprintf(stderr, "viso_match_desc, %d image(s) uploaded, %ld calls:", k, g_tr_n[k]);
-        for (int j = 0; j < 6; ++j) fprintf(stderr, "  %s %.1f", ph[j], g_tr_us[k][j] / g_tr_n[k]);
+        if (!g_tr.n[k]) continue;
+        fprintf(stderr, "viso_match_desc, %d image(s) uploaded, %ld calls:", k, g_tr.n[k]);
+        for (int j = 0; j < 6; ++j) fprintf(stderr, "  %s %.1f", ph[j], g_tr.us[k][j] / g_tr.n[k]);
         fprintf(stderr, "  (us per call)\n");
     }
-    if (g_acq_n) fprintf(stderr, "uploads: %ld, rows into the shadow %.1f us, pack launch %.1f us; look-ups + keypoints + sort_kp launch %.1f us per call\n", g_acq_n,
-                         g_acq_us[0] / g_acq_n, g_acq_us[1] / g_acq_n, g_acq_us[2] / (g_acq_calls > 0 ? g_acq_calls : 1));
-    if (g_wait_n[0] || g_wait_n[1])
+    if (g_tr.acq_n) fprintf(stderr, "uploads: %ld, rows into the shadow %.1f us, pack launch %.1f us; look-ups + keypoints + sort_kp launch %.1f us per call\n", g_tr.acq_n,
+                         g_tr.acq_us[0] / g_tr.acq_n, g_tr.acq_us[1] / g_tr.acq_n, g_tr.acq_us[2] / (g_tr.acq_calls > 0 ? g_tr.acq_calls : 1));
+    if (g_tr.wait_n[0] || g_tr.wait_n[1])
         fprintf(stderr, "waits behind the stereo call: match_circle for the join %.1f us (%ld), ransac_minimize_reproj for the stage %.1f us (%ld)\n",
-                g_wait_n[0] ? g_wait_us[0] / g_wait_n[0] : 0.0, g_wait_n[0], g_wait_n[1] ? g_wait_us[1] / g_wait_n[1] : 0.0, g_wait_n[1]);
-    if (g_srv_n) fprintf(stderr, "temporal calls answered from the frame: %ld, look-ups (byte comparison of both images) %.1f us, the rest %.1f us\n", g_srv_n, g_srv_us[0] / g_srv_n, g_srv_us[1] / g_srv_n);
-    g_srv_us[0] = g_srv_us[1] = 0; g_srv_n = 0;
-    memset(g_wait_us, 0, sizeof(g_wait_us)); memset(g_wait_n, 0, sizeof(g_wait_n));
-    memset(g_acq_us, 0, sizeof(g_acq_us)); g_acq_n = 0; g_acq_calls = 0;
-    memset(g_tr_us, 0, sizeof(g_tr_us)); memset(g_tr_n, 0, sizeof(g_tr_n));
+                g_tr.wait_n[0] ? g_tr.wait_us[0] / g_tr.wait_n[0] : 0.0, g_tr.wait_n[0], g_tr.wait_n[1] ? g_tr.wait_us[1] / g_tr.wait_n[1] : 0.0, g_tr.wait_n[1]);
+    if (g_tr.srv_n) fprintf(stderr, "temporal calls answered from the frame: %ld, look-ups (byte comparison of both images) %.1f us, the rest %.1f us\n", g_tr.srv_n, g_tr.srv_us[0] / g_tr.srv_n, g_tr.srv_us[1] / g_tr.srv_n);
+    g_tr = PlainTrace{};
 }
 
 // The slot that holds (kp, d), found by comparing bytes; -1: not resident.
@@ -435,55 +474,26 @@ static int plain_prepare(viso_ctx* c, PlainCache* pc, const float* kp, int n, in
         if (i != keep && i != keep2 && (vi < 0 || pc->slot[i].stamp < pc->slot[vi].stamp)) vi = i;
     PlainSlot& s = pc->slot[vi];
     s.valid = false;
-    const size_t na = (size_t)(n > 0 ? n : 1);
-    const size_t o_hdr = al256(sizeof(float2) * na), o_desc = o_hdr + PLAIN_HDR;
-    const size_t pin_need = o_desc + al256(sizeof(float) * na * dlen);
-    const size_t o_rows = o_desc, o_aux = o_rows + al256(sizeof(uint16_t) * VISO_ROW * na);
-    const size_t total = o_aux + al256(aux_bytes(na));
-    if (s.pin_bytes < pin_need) {
-        HIP_TRY(hipStreamSynchronize(c->stream));   // a kernel of an earlier call may still read the old shadow
-        if (s.pin) HIP_TRY(hipHostFree(s.pin));
-        s.pin = nullptr; s.pin_bytes = 0;
-        HIP_TRY(hipHostMalloc((void**)&s.pin, pin_need + pin_need / 4, hipHostMallocDefault));
-        s.pin_bytes = pin_need + pin_need / 4;
-    }
-    if (s.dev_bytes < total) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (s.dev) HIP_TRY(hipFree(s.dev));
-        s.dev = nullptr; s.dev_bytes = 0;
-        HIP_TRY(hipMalloc((void**)&s.dev, total + total / 4));
-        s.dev_bytes = total + total / 4;
-    }
+    const SlotLayout L = slot_layout((size_t)(n > 0 ? n : 1), dlen);
+    int r;
+    if ((r = plain_grow(c, &s.pin, &s.pin_bytes, L.pin_end, hipHostMallocDefault)) < 0 || (r = plain_grow(c, &s.dev, &s.dev_bytes, L.dev_end, -1)) < 0) return r;
     if (kb) memcpy(s.pin, kp, kb);
+    SlotHeader *hdr = reinterpret_cast<SlotHeader*>(s.pin + L.hdr), *dhdr = reinterpret_cast<SlotHeader*>(s.dev + L.hdr);
     ImageView v{};
-    v.kp = reinterpret_cast<const float2*>(s.dev);
-    v.frows = reinterpret_cast<const float*>(s.pin + o_desc);
-    v.n = reinterpret_cast<const int*>(s.dev + o_hdr);
-    v.bad = reinterpret_cast<int*>(s.dev + o_hdr) + 1;
-    v.rows = reinterpret_cast<uint16_t*>(s.dev + o_rows);
-    unsigned char* base = reinterpret_cast<unsigned char*>(s.dev + o_aux);
-    v.skp = (float2*)base;
-    v.sidx = (int*)(base + 8 * na);
-    v.rank = (int*)(base + 12 * na);
-    unsigned char* tail = base + ((16 * na + 15) / 16) * 16;
-    v.bstart = (int*)tail;
-    v.xinfo = (float*)(tail + 4 * (VISO_NB + 1));
-    v.qord = (uint8_t*)(tail + ((4 * (VISO_NB + 1) + 32 + 15) / 16) * 16);
-    v.sums = (uint2*)((unsigned char*)v.qord + ((na + 63) / 64) * 64);
-    v.rows8 = (uint8_t*)v.sums + ((8 * na + 15) / 16) * 16;
-    int* hdr = reinterpret_cast<int*>(s.pin + o_hdr);
-    hdr[0] = n;
-    hdr[1] = dlen > VISO_ROW ? 1 : 0;   // rows that do not fit the packed format: the image takes the general path
-    memcpy(s.pin + o_hdr + 64, &v, sizeof(v));
+    v.kp = reinterpret_cast<const float2*>(s.dev); v.frows = reinterpret_cast<const float*>(s.pin + L.rows);
+    v.n = &dhdr->n; v.bad = &dhdr->bad; v.rows = reinterpret_cast<uint16_t*>(s.dev + L.rows);
+    v.skp = reinterpret_cast<float2*>(s.dev + L.skp); v.sidx = reinterpret_cast<int*>(s.dev + L.sidx); v.rank = reinterpret_cast<int*>(s.dev + L.rank);
+    v.bstart = reinterpret_cast<int*>(s.dev + L.bstart); v.xinfo = reinterpret_cast<float*>(s.dev + L.xinfo);
+    v.qord = reinterpret_cast<uint8_t*>(s.dev + L.qord); v.sums = reinterpret_cast<uint2*>(s.dev + L.sums); v.rows8 = reinterpret_cast<uint8_t*>(s.dev + L.rows8);
+    hdr->n = n; hdr->bad = dlen > VISO_ROW ? 1 : 0;   // rows that do not fit the packed format: the image takes the general path
+    hdr->view = v;
     // sort_kp_kernel gets the image's view in its arguments, writes the header words {n, bad} and leaves a copy of the view on
     // the device where pack_desc_kernel's launch finds it (the copy kernel that used to bring keypoints + header over first is gone)
-    *imp = KpImport{};
-    imp->src_kp = reinterpret_cast<const float2*>(s.pin); imp->n = n; imp->bad0 = hdr[1];
-    imp->view_dst = reinterpret_cast<ImageView*>(s.dev + o_hdr + 64); imp->view = v;
+    *imp = KpImport{}; imp->src_kp = reinterpret_cast<const float2*>(s.pin); imp->n = n; imp->bad0 = hdr->bad;
+    imp->view_dst = &dhdr->view; imp->view = v;
     s.n = n; s.dlen = dlen; s.extras = extras; s.r8s = r8s;
     s.bad_host = dlen > VISO_ROW ? 1 : -1;
-    s.o_desc = o_desc; s.o_hdr = o_hdr;
-    s.v = v;
+    s.o_desc = L.rows; s.o_hdr = L.hdr; s.v = v;
     return vi;
 }
 
@@ -497,9 +507,9 @@ static int plain_finish(viso_ctx* c, PlainCache* pc, int vi, const float* d, hip
     big_copy(s.pin + s.o_desc, d, sizeof(float) * (size_t)n * dlen);
     const double ta1 = g_tr_on > 0 ? tr_now() : 0;
     int r;
-    const ImageView* dview = reinterpret_cast<const ImageView*>(s.dev + s.o_hdr + 64);
+    const ImageView* dview = &reinterpret_cast<const SlotHeader*>(s.dev + s.o_hdr)->view;
     if (dlen <= VISO_ROW && (r = launch_pack(stream, dview, 1, n > 0 ? n : 1, dlen, nullptr, const_cast<int*>(s.v.bad), s.extras, s.r8s, nullptr)) < 0) return r;
-    if (g_tr_on > 0) { g_acq_us[0] += ta1 - ta0; g_acq_us[1] += tr_now() - ta1; g_acq_n += 1; }
+    if (g_tr_on > 0) { g_tr.acq_us[0] += ta1 - ta0; g_tr.acq_us[1] += tr_now() - ta1; g_tr.acq_n += 1; }
     s.stamp = ++pc->clock;
     s.valid = true;
     return VISO_OK;
@@ -519,36 +529,30 @@ static bool tri_equal(const viso_param& a, const viso_param& b) {   // the field
 
 struct FrameHead { MatchProblem p[PF_PROBS]; TriItem tri; SolverItem rs; OutArgs outA, outJ; };
 
+// A frame's block by its offset (o_X, or offsetof(FrameHead, ...)): on the device, and in the pinned mirror, which holds [o_misc, o_end)
+template <class T> static T* frame_dev(const PlainFrame& f, size_t off) { return reinterpret_cast<T*>(f.dev + off); }
+template <class T> static T* frame_host(const PlainFrame& f, size_t off) { return reinterpret_cast<T*>(f.host + (off - f.o_misc)); }
+static size_t frame_ld(const PlainFrame& f) { return (size_t)(f.cap > 0 ? f.cap : 1); }   // leading dimension of the column blocks (x, X, xc, Xpc)
+static const int* frame_rows(const PlainFrame& f, int p) { return frame_host<const int>(f, f.o_sorted[p]); }
+
 // lays a frame's blocks out for `cap` rows per problem (grow only)
 static int frame_reserve(viso_ctx* c, PlainFrame& f, int cap) {
     const size_t C = (size_t)(cap > 0 ? cap : 1);
     size_t o = al256(sizeof(FrameHead));
-    f.o_misc = o; o += 256;
+    f.o_misc = o; o += sizeof(FrameMisc);
     for (int p = 0; p < PF_PROBS; ++p) { f.o_sorted[p] = o; o += al256(sizeof(int) * 3 * C); }
-    f.o_x = o; o += al256(sizeof(double) * 4 * C);
-    f.o_X = o; o += al256(sizeof(double) * 3 * C);
+    f.o_x = o; o += al256(sizeof(double) * 4 * C); f.o_X = o; o += al256(sizeof(double) * 3 * C);
     f.o_circ = o; o += al256(sizeof(int) * 6 * C);
-    f.o_xc = o; o += al256(sizeof(double) * 4 * C);
-    f.o_Xpc = o; o += al256(sizeof(double) * 3 * C);
-    f.o_rs = o; o += 128 + al256(sizeof(int) * C);
+    f.o_xc = o; o += al256(sizeof(double) * 4 * C); f.o_Xpc = o; o += al256(sizeof(double) * 3 * C);
+    f.o_rs = o; o += offsetof(RansacOut, inl) + al256(sizeof(int) * C);
     f.o_end = o;
-    const size_t scratch = PF_PROBS * (al256(sizeof(int2) * C) + al256(sizeof(int) * C) + al256(sizeof(int) * (C / 64 + 1))) + al256(sizeof(int2) * PF_PROBS * C);
-    const size_t total = o + scratch;
-    if (f.dev_bytes < total) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (f.dev) HIP_TRY(hipFree(f.dev));
-        f.dev = nullptr; f.dev_bytes = 0;
-        HIP_TRY(hipMalloc((void**)&f.dev, total + total / 4));
-        f.dev_bytes = total + total / 4;
-    }
-    if (f.host_bytes < f.o_end - f.o_misc) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (f.host) HIP_TRY(hipHostFree(f.host));
-        f.host = nullptr; f.host_bytes = 0;
-        const size_t want = (f.o_end - f.o_misc) + (f.o_end - f.o_misc) / 4;
-        HIP_TRY(hipHostMalloc((void**)&f.host, want, hipHostMallocCoherent));   // read by the host right behind the signal, possibly before the kernel has retired
-        f.host_bytes = want;
-    }
+    // behind the mirrored part, scratch of the matchers: res | pos | tile_flag per problem, then the overflow queue they share
+    f.o_res = o; f.o_pos = f.o_res + al256(sizeof(int2) * C); f.o_tile = f.o_pos + al256(sizeof(int) * C);
+    f.scr_stride = f.o_tile + al256(sizeof(int) * (C / 64 + 1)) - f.o_res;
+    f.o_ovf = f.o_res + PF_PROBS * f.scr_stride;
+    int r = plain_grow(c, &f.dev, &f.dev_bytes, f.o_ovf + al256(sizeof(int2) * PF_PROBS * C), -1);
+    // the mirror is coherent memory: the host reads it right behind the signal, possibly before the kernel has retired
+    if (r < 0 || (r = plain_grow(c, &f.host, &f.host_bytes, f.o_end - f.o_misc, hipHostMallocCoherent)) < 0) return r;
     f.cap = cap;
     return VISO_OK;
 }
@@ -556,30 +560,21 @@ static int frame_reserve(viso_ctx* c, PlainFrame& f, int cap) {
 static void frame_reset(PlainFrame& f) {
     f.valid = false;
     for (int p = 0; p < PF_PROBS; ++p) { f.have[p] = f.used[p] = false; f.m[p] = 0; }
-    f.have_xX = f.used_x = f.used_X = false;
-    f.have_B = f.used_circ = f.used_rs = false;
+    f.have_xX = f.used_x = f.used_X = f.have_B = f.used_circ = f.used_rs = false;
     f.n_circ = 0;
 }
 
-// the second part of a frame's chain has finished: its counters are in the mirror
-static int frame_wait_J(viso_ctx* c, PlainFrame& f) {   // the join (and the gathered columns) are in the mirror
-    if (!f.pending_J) return VISO_OK;
+// Waits for the second part of a frame's chain.  stage 0: the join and the gathered columns are in the mirror (match_circle waits for this
+// one only, the RANSAC stage runs on); stage 1: the RANSAC result is too -- the chain's last kernel: everything before it on the stream is done
+static int frame_wait(viso_ctx* c, PlainFrame& f, int stage) {
+    if (!(stage ? f.pending_B : f.pending_J)) return VISO_OK;
     const double tw0 = g_tr_on > 0 ? tr_now() : 0;
-    { const int r_ = plain_signal_wait(c, c->stream, f.seqJ); if (r_ < 0) return r_; }
-    if (g_tr_on > 0) { g_wait_us[0] += tr_now() - tw0; g_wait_n[0] += 1; }
+    const int r = plain_signal_wait(c, c->stream, stage ? f.seqB : f.seqJ);
+    if (r < 0) return r;
+    if (g_tr_on > 0) { g_tr.wait_us[stage] += tr_now() - tw0; g_tr.wait_n[stage] += 1; }
+    if (stage) f.pending_B = false;
     f.pending_J = false;
-    const int* om = reinterpret_cast<const int*>(f.host);
-    f.n_circ = om[32];
-    return VISO_OK;
-}
-static int frame_wait_B(viso_ctx* c, PlainFrame& f) {
-    if (!f.pending_B) return VISO_OK;
-    const double tw0 = g_tr_on > 0 ? tr_now() : 0;
-    { const int r_ = plain_signal_wait(c, c->stream, f.seqB); if (r_ < 0) return r_; }   // the chain's last kernel: everything before it on the stream is done
-    if (g_tr_on > 0) { g_wait_us[1] += tr_now() - tw0; g_wait_n[1] += 1; }
-    f.pending_B = false; f.pending_J = false;
-    const int* om = reinterpret_cast<const int*>(f.host);
-    f.n_circ = om[32];
+    f.n_circ = frame_host<const FrameMisc>(f, f.o_misc)->n_circ;
     return VISO_OK;
 }
 
@@ -593,13 +588,6 @@ static void frame_retire(PlainCache* pc, PlainFrame& f) {
     if (f.have_B && !f.used_rs) { pc->rs_pattern = false; pc->spec_wasted[3] += 1; }
 }
 
-static const int* frame_rows(const PlainFrame& f, int p) { return reinterpret_cast<const int*>(f.host + (f.o_sorted[p] - f.o_misc)); }
-
-#define PLAIN_RERUN 2
-static int match_run(viso_ctx* c, PlainCache* pc, PlainProf& pp, int iq, int it, bool hit_q, bool hit_t, int n1, int n2, int dlen,
-                     const viso_match_params* mp, int variant, int extras, int r8s, int32_t* out_match, int* out_n,
-                     bool force_general, double* tt);
-
 // An error return must not leave work in flight: the kernels queued so far (copy, sort_kp, pack -- possibly on the side
 // stream) read the slots' pinned shadows and the context's pinned block, a slot may already be marked valid although its
 // pack kernel never ran to the end, and the next call would memcpy over a shadow a queued kernel is still pulling over
@@ -608,17 +596,362 @@ static int match_run(viso_ctx* c, PlainCache* pc, PlainProf& pp, int iq, int it,
 static void plain_quiesce(viso_ctx* c, PlainCache* pc) {
     (void)hipStreamSynchronize(c->stream);
     for (int i = 0; i < PLAIN_SLOTS; ++i) pc->slot[i].valid = false;
-    for (int i = 0; i < 3; ++i) { pc->frame[i].valid = false; pc->frame[i].pending_B = false; pc->frame[i].pending_J = false; }
-    pc->good_streak = 0;
-    pc->narrow_streak = 0;
+    frames_forget(pc);
+    pc->good_streak = pc->narrow_streak = 0;
+}
+
+// ---- one launch of a frame: match_run drives the five stages below over this plan -------------------------------------
+struct FramePlan {
+    int iq, it, n1, dlen, variant, extras, r8s;   // the call (match_desc_locked): its images' slots, its queries, what the rows were packed for
+    const viso_match_params* mp; bool stereo, force_general;   // ... its parameters; a stereo call; the repeated launch: every kernel is in it
+    PlainFrame* f;                                // frame_open: the object that takes the call,
+    int np, cap;                                  //   its problems (1, or 3: the temporal calls ride along) and rows per problem,
+    bool spec_x, spec_B;                          //   collect + triangulate ride in the sort kernel / the second part (join, RANSAC) follows,
+    int saved_cur; unsigned long long saved_no;   //   what a repeated launch puts back
+    FrameHead* H;                                 // frame_fill_head: the head in the context's pinned block,
+    bool need_general;                            //   whether the launch includes the general kernels,
+    int *rs_tab, *rs_queue, rs_tabn;              //   the second part's join table and hypothesis queue
+    uint32_t seqA;                                // frame_copy_outs: the signal of the first copy-out
+    bool skip_wide;                               // frame_queue_first: the wide-band stereo kernel was left out
+};
+
+// stage 1: which frame object takes the call, which problems ride along, where its blocks lie
+static int frame_open(viso_ctx* c, PlainCache* pc, FramePlan& P) {
+    int r;
+    const int iq = P.iq, it = P.it, dlen = P.dlen;
+    P.saved_cur = pc->cur; P.saved_no = pc->frame_no;
+    PlainFrame* f = &pc->frame[2];
+    P.np = 1; P.spec_x = P.spec_B = false;
+    if (P.stereo && pc->speculate) {
+        if ((r = frame_wait(c, pc->frame[pc->cur ^ 1], 1)) < 0) return r;
+        // The frame that leaves is the one before the last stereo call's: every call that could have used its results is over,
+        // so what it computed ahead and nobody asked for is known now, whatever becomes of THIS launch (a repeated launch finds
+        // the object reset -- not valid -- and counts nothing twice)
+        frame_retire(pc, pc->frame[pc->cur ^ 1]);
+        pc->frame_no += 1; pc->cur ^= 1;
+        f = &pc->frame[pc->cur];
+        const PlainFrame& prv = pc->frame[pc->cur ^ 1];
+        frame_reset(*f);
+        f->L = iq; f->R = it; f->sL = pc->slot[iq].stamp; f->sR = pc->slot[it].stamp;
+        if (pc->tm_known && pc->tm_pattern && prv.valid && iq != it && prv.L != prv.R &&
+            pc->slot[prv.L].valid && pc->slot[prv.L].stamp == prv.sL && pc->slot[prv.R].valid && pc->slot[prv.R].stamp == prv.sR &&
+            pc->slot[prv.L].dlen == dlen && pc->slot[prv.R].dlen == dlen && pc->slot[prv.L].extras == P.extras && pc->slot[prv.R].extras == P.extras &&
+            pc->slot[prv.L].r8s == P.r8s && pc->slot[prv.R].r8s == P.r8s && prv.L != iq && prv.L != it && prv.R != iq && prv.R != it)
+            P.np = 3;
+        P.spec_x = pc->tri_known && pc->x_pattern;
+        P.spec_B = P.np == 3 && P.spec_x && prv.have_xX && prv.have[0] && pc->circ_pattern && pc->rs_known && pc->rs_pattern && pc->rs_delta_stable &&
+                   pc->rs_p.ransac_iter >= 1 && pc->rs_p.ransac_iter <= 4096;
+    } else frame_reset(*f);
+    P.f = f;
+    const PlainSlot &sq = pc->slot[iq], &st = pc->slot[it];
+    f->have[0] = true; f->nq[0] = P.n1; f->tq[0] = iq; f->tt[0] = it; f->stq[0] = sq.stamp; f->stt[0] = st.stamp; f->mp[0] = *P.mp;
+    if (P.np == 3) {
+        const PlainFrame& prv = pc->frame[pc->cur ^ 1];
+        f->have[1] = true; f->nq[1] = sq.n; f->tq[1] = iq; f->tt[1] = prv.L; f->stq[1] = sq.stamp; f->stt[1] = prv.sL; f->mp[1] = pc->tm;
+        f->have[2] = true; f->nq[2] = st.n; f->tq[2] = it; f->tt[2] = prv.R; f->stq[2] = st.stamp; f->stt[2] = prv.sR; f->mp[2] = pc->tm;
+    }
+    P.cap = P.n1;
+    for (int p = 1; p < P.np; ++p) P.cap = f->nq[p] > P.cap ? f->nq[p] : P.cap;
+    return frame_reserve(c, *f, P.cap);
+}
+
+// stage 2: the head of the frame's block in the context's pinned block -- problems, TriItem, SolverItem, zeroed counters: ONE copy in
+static int frame_fill_head(viso_ctx* c, PlainCache* pc, FramePlan& P) {
+    int r; char* hin;
+    PlainFrame& f = *P.f;
+    const PlainSlot &sq = pc->slot[P.iq], &st = pc->slot[P.it];
+    if ((r = ctx_pinned(c, 0, f.o_misc + sizeof(FrameMisc), &hin)) < 0) return r;
+    P.H = reinterpret_cast<FrameHead*>(hin);
+    FrameMisc* hmisc = reinterpret_cast<FrameMisc*>(hin + f.o_misc);
+    FrameMisc* dmisc = frame_dev<FrameMisc>(f, f.o_misc);
+    memset(hmisc, 0, sizeof(FrameMisc));
+    // The general (float / double) kernels are for images whose descriptors do not fit the u16 rows.  Whether a NEW image
+    // does is known only after its pack kernel has run; once a few launches in a row have seen none, new images are expected
+    // to fit and the three general kernels are left out of the launch (15 us of the chain).  If the expectation fails
+    // -- the images' own flags come back with the results -- sort_matches_kernel has emitted EMPTY lists for the problems
+    // concerned (flagged_empty) and the call is repeated with the general kernels: same results, later.
+    bool any_bad = false, any_unknown = false;
+    for (int p = 0; p < P.np; ++p) {
+        const PlainSlot &a = pc->slot[f.tq[p]], &b = pc->slot[f.tt[p]];
+        if (a.bad_host == 1 || b.bad_host == 1) any_bad = true;
+        if (a.bad_host < 0 || b.bad_host < 0) any_unknown = true;
+        MatchProblem M{};
+        M.q = a.v; M.t = b.v;
+        M.res = frame_dev<int2>(f, f.o_res + p * f.scr_stride); M.pos = frame_dev<int>(f, f.o_pos + p * f.scr_stride);
+        M.tile_flag = frame_dev<int>(f, f.o_tile + p * f.scr_stride); M.sorted = frame_dev<int>(f, f.o_sorted[p]);
+        M.m_cnt = &dmisc->prob[p].m_cnt; M.scored = &dmisc->prob[p].scored;
+        M.pidx = p == 0 ? 0 : 1; M.cap = P.cap;
+        M.ovf = frame_dev<int2>(f, f.o_ovf); M.ovf_cnt = &dmisc->ovf_cnt;
+        P.H->p[p] = M;
+    }
+    // A source that has produced a flagged image lately keeps the general kernels in the launch: a stream with sporadic
+    // fractional images would otherwise pay a dropped launch + a full synchronize + a second launch on every such frame
+    const bool trust = pc->good_streak >= 2 && !P.force_general && pc->distrust == 0;
+    P.need_general = any_bad || (any_unknown && !trust) || P.dlen > VISO_ROW;
+    if (P.need_general) hmisc->bad[0] = 1;   // the general kernels' early-exit hint; they look at every image's own flag
+    if (P.spec_x) {
+        TriItem T{};
+        T.kp1 = sq.v.kp; T.kp2 = st.v.kp; T.match = frame_dev<const int>(f, f.o_sorted[0]); T.m_cnt = &dmisc->prob[0].m_cnt;
+        T.x = frame_dev<double>(f, f.o_x); T.X = frame_dev<double>(f, f.o_X); T.ld = (int)frame_ld(f);
+        P.H->tri = T;
+    }
+    if (P.spec_B) {
+        const int iters = pc->rs_p.ransac_iter;
+        double* dtrh; int* dhyp; char* drot;
+        P.rs_tabn = sq.n > st.n ? sq.n : st.n;
+        if (pc->slot[pc->frame[pc->cur ^ 1].L].n > P.rs_tabn) P.rs_tabn = pc->slot[pc->frame[pc->cur ^ 1].L].n;
+        if ((r = ctx_scratch(c, SLOT_CIRCLE_TAB, sizeof(int) * 3 * (size_t)(P.rs_tabn + 1), (void**)&P.rs_tab)) < 0) return r;
+        if ((r = ctx_scratch(c, SLOT_HYP_WORDS, sizeof(int) * (4 + 2 * (size_t)iters), (void**)&dhyp)) < 0) return r;
+        if ((r = ctx_scratch(c, SLOT_HYP_TR, sizeof(double) * 6 * (size_t)(iters + 1), (void**)&dtrh)) < 0) return r;
+        if ((r = ctx_scratch(c, SLOT_RANSAC_QUEUE, sizeof(int) * (2 + 4 * (size_t)iters + 3), (void**)&P.rs_queue, true)) < 0) return r;
+        if ((r = ctx_scratch(c, SLOT_RANSAC_ROT, viso_rot_bytes(iters), (void**)&drot)) < 0) return r;
+        f.rs_p = pc->rs_p; f.rs_seed = pc->rs_seed; f.rs_frame = pc->rs_last_frame + pc->rs_delta;
+        RansacOut* rso = frame_dev<RansacOut>(f, f.o_rs);
+        SolverItem S{};
+        S.X = frame_dev<const double>(f, f.o_Xpc); S.obs = frame_dev<const double>(f, f.o_xc);
+        S.m_ptr = &dmisc->n_circ; S.ld = (int)frame_ld(f); S.samples = nullptr; S.samp_h = P.rs_queue + 2 + iters; S.frame = f.rs_frame;
+        S.tr_h = dtrh; S.ok_h = dhyp; S.cnt_h = dhyp + iters; S.rot = drot;
+        S.kept = &rso->kept; S.ok = &rso->ok; S.n_inl = &rso->n_inl; S.tr = rso->tr; S.inl = rso->inl;
+        P.H->rs = S;
+    }
+    return VISO_OK;
+}
+
+static void out_add(OutArgs& o, const void* src, void* dst, const int* cnt, int row_words, int max_rows) {
+    OutRegion& R = o.r[o.n_regions++];
+    R.src = static_cast<const uint32_t*>(src); R.dst = static_cast<uint32_t*>(dst); R.cnt = cnt; R.row_words = row_words; R.max_rows = max_rows;
+}
+static void out_block(OutArgs& o, const PlainFrame& f, size_t off, const int* cnt, int row_words, int max_rows) {   // a block of the frame to its place in the mirror
+    out_add(o, frame_dev<char>(f, off), frame_host<char>(f, off), cnt, row_words, max_rows);
+}
+
+// stage 3: the copy-outs into the frame's pinned mirror (common.h, OutArgs): the lists (and x, X) behind the sort kernel -- riding in
+// the join kernel's launch when the frame has one, a kernel of their own otherwise; the join and the gathered columns behind
+// the join kernel, riding in ransac_coop_kernel's launch.  Each signals: match_circle returns as soon as the join is there,
+// the RANSAC stage runs on behind the caller's gather loop.  FrameMisc says which of its words each of the two owns.
+static int frame_copy_outs(viso_ctx* c, PlainCache* pc, FramePlan& P) {
+    int r;
+    PlainFrame& f = *P.f;
+    const size_t C = frame_ld(f);
+    FrameMisc* dmisc = frame_dev<FrameMisc>(f, f.o_misc);
+    FrameMisc* omisc = frame_host<FrameMisc>(f, f.o_misc);
+    const int* m0 = &dmisc->prob[0].m_cnt;
+    OutArgs& oa = P.H->outA = OutArgs{};
+    out_block(oa, f, f.o_misc, nullptr, offsetof(FrameMisc, n_circ) / 4, 1);
+    out_add(oa, pc->slot[P.iq].v.bad, &omisc->img_bad[0], nullptr, 1, 1);
+    out_add(oa, pc->slot[P.it].v.bad, &omisc->img_bad[1], nullptr, 1, 1);
+    for (int p = 0; p < P.np; ++p) out_block(oa, f, f.o_sorted[p], &dmisc->prob[p].m_cnt, 3, f.nq[p]);
+    if (P.spec_x) {
+        for (int k = 0; k < 4; ++k) out_block(oa, f, f.o_x + sizeof(double) * C * k, m0, 2, P.n1);
+        for (int k = 0; k < 3; ++k) out_block(oa, f, f.o_X + sizeof(double) * C * k, m0, 2, P.n1);
+    }
+    const size_t tpb = P.spec_B ? 1024 : 256;   // threads of the workgroups that will do it: four words each
+    oa.gx = (int)((3 * C + 4 * tpb - 1) / (4 * tpb));
+    if ((r = plain_signal_next(c, &oa.sig)) < 0) return r;
+    P.seqA = oa.sig.seq;
+    if (P.spec_B) {
+        OutArgs& oj = P.H->outJ = OutArgs{};
+        out_block(oj, f, f.o_misc + offsetof(FrameMisc, n_circ), nullptr, (offsetof(FrameMisc, img_bad) - offsetof(FrameMisc, n_circ)) / 4, 1);
+        out_block(oj, f, f.o_circ, &dmisc->n_circ, 6, P.cap);
+        for (int k = 0; k < 4; ++k) out_block(oj, f, f.o_xc + sizeof(double) * C * k, &dmisc->n_circ, 2, P.cap);
+        for (int k = 0; k < 3; ++k) out_block(oj, f, f.o_Xpc + sizeof(double) * C * k, &dmisc->n_circ, 2, P.cap);
+        oj.gx = (int)((6 * C + 1023) / 1024);
+        if ((r = plain_signal_next(c, &oj.sig)) < 0) return r;
+        f.seqJ = oj.sig.seq;
+    }
+    return VISO_OK;
+}
+
+// stage 4, first part: the matchers and the sort kernel
+static int frame_queue_first(viso_ctx* c, PlainCache* pc, FramePlan& P) {
+    int r;
+    PlainFrame& f = *P.f;
+    FrameMisc* dmisc = frame_dev<FrameMisc>(f, f.o_misc);
+    const MatchProblem* dprob = frame_dev<const MatchProblem>(f, offsetof(FrameHead, p));
+    MatchParamsDev mpd[2]; fill_match_params(&mpd[0], P.mp);
+    if (P.np == 3) fill_match_params(&mpd[1], &pc->tm); else mpd[1] = mpd[0];
+    int kinds = P.np == 3 ? VISO_KIND_ALL : P.stereo ? VISO_KIND_STEREO : VISO_KIND_TEMPORAL;
+    // match_batch_kernel<1> takes the tiles whose epipolar band match_stereo_kernel finds too wide (pairs that are not
+    // rectified): after a few stereo launches without such a tile it is left out (5 us of the chain the caller waits for);
+    // the number of declined tiles comes back with the results, and a launch that had one without the kernel is repeated
+    P.skip_wide = P.stereo && pc->narrow_streak >= 2 && !P.force_general;
+    if (P.skip_wide) kinds |= VISO_KIND_NO_WIDE;
+    if ((r = launch_match_timed(c->stream, dprob, P.np, P.cap, P.dlen, mpd, dmisc->bad, nullptr, nullptr, 0, P.variant, frame_dev<const int2>(f, f.o_ovf),
+                                &dmisc->ovf_cnt, P.r8s, P.need_general ? 1 : 0, kinds)) < 0) return r;
+    if (!P.spec_x) return launch_sort(c->stream, dprob, P.np, P.cap, P.need_general ? 0 : 1);
+    SolverParamsDev sp; fill_solver_params(&sp, &pc->tri_p);   // collect_matches / triangulate_rectified of the stereo list ride in the sort kernel
+    return launch_sort(c->stream, dprob, P.np, P.cap, P.need_general ? 0 : 1, frame_dev<const TriItem>(f, offsetof(FrameHead, tri)), &sp);
+}
+
+// stage 4, second part: the join and the RANSAC stage -- they keep running while the caller goes through its next calls
+static int frame_queue_second(viso_ctx* c, PlainCache* pc, FramePlan& P) {
+    int r;
+    PlainFrame& f = *P.f;
+    const PlainFrame& prv = pc->frame[pc->cur ^ 1];
+    FrameMisc* dmisc = frame_dev<FrameMisc>(f, f.o_misc);
+    const FrameMisc* pmisc = frame_dev<const FrameMisc>(prv, prv.o_misc);
+    CircleArgs ca{};
+    ca.lr = frame_dev<const int>(f, f.o_sorted[0]); ca.lrp = frame_dev<const int>(prv, prv.o_sorted[0]);
+    ca.m11 = frame_dev<const int>(f, f.o_sorted[1]); ca.m22 = frame_dev<const int>(f, f.o_sorted[2]);
+    ca.n_lr_p = &dmisc->prob[0].m_cnt; ca.n_lrp_p = &pmisc->prob[0].m_cnt; ca.n11_p = &dmisc->prob[1].m_cnt; ca.n22_p = &dmisc->prob[2].m_cnt;
+    ca.rows = frame_dev<int>(f, f.o_circ); ca.cap = P.cap; ca.out_n = &dmisc->n_circ;
+    // x_c / Xp_c of :1292-1305 come out of the join kernel's tail (no gather kernel of their own)
+    ca.g_x = frame_dev<const double>(f, f.o_x); ca.g_ldx = (int)frame_ld(f);
+    ca.g_Xp = frame_dev<const double>(prv, prv.o_X); ca.g_ldXp = (int)frame_ld(prv);
+    ca.g_xc = frame_dev<double>(f, f.o_xc); ca.g_Xpc = frame_dev<double>(f, f.o_Xpc); ca.g_ldc = (int)frame_ld(f);
+    ca.ride = frame_dev<const OutArgs>(f, offsetof(FrameHead, outA)); ca.ride_blocks = P.H->outA.n_regions * P.H->outA.gx;
+    if ((r = launch_circle_table(c->stream, ca, P.rs_tab, P.rs_tabn)) < 0) return r;
+    SolverParamsDev sp; fill_solver_params(&sp, &f.rs_p);
+    RefitMirror rm{};   // the pose and the inliers go into the mirror from the refit kernel itself, which signals
+    const RansacOut* rso = frame_dev<const RansacOut>(f, f.o_rs); RansacOut* rsh = frame_host<RansacOut>(f, f.o_rs);
+    rm.res_src = reinterpret_cast<const uint32_t*>(rso); rm.res_dst = reinterpret_cast<uint32_t*>(rsh); rm.res_words = offsetof(RansacOut, inl) / 4;
+    rm.n_inl = &rso->n_inl; rm.inl_src = reinterpret_cast<const uint32_t*>(rso->inl); rm.inl_dst = reinterpret_cast<uint32_t*>(rsh->inl); rm.max_inl = P.cap;
+    if ((r = plain_signal_next(c, &rm.sig)) < 0) return r;
+    f.seqB = rm.sig.seq;
+    if ((r = launch_ransac(c->stream, frame_dev<const SolverItem>(f, offsetof(FrameHead, rs)), 1, f.rs_p.ransac_iter, f.rs_seed, sp,
+                           P.rs_queue, c->gn_split ? c->gn_split : 1, P.cap, &rm,
+                           frame_dev<const OutArgs>(f, offsetof(FrameHead, outJ)), P.H->outJ.n_regions * P.H->outJ.gx)) < 0) return r;
+    f.have_B = true; f.pending_B = true; f.pending_J = true;
+    return VISO_OK;
+}
+
+// The launch lacked a kernel that turned out to have work: everything it produced is dropped, the call repeated with it
+#define PLAIN_RERUN 2
+static int frame_repeat(viso_ctx* c, PlainCache* pc, FramePlan& P) {
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    P.f->pending_B = P.f->pending_J = false; frame_reset(*P.f);
+    pc->cur = P.saved_cur; pc->frame_no = P.saved_no;
+    pc->general_reruns += 1;
+    return PLAIN_RERUN;
+}
+
+// stage 5: behind the first copy-out's signal -- the counts, what the launch learned about its images and its stereo pair, the stereo list
+static int frame_harvest(viso_ctx* c, PlainCache* pc, FramePlan& P, int32_t* out_match, int* out_n) {
+    PlainFrame& f = *P.f;
+    PlainSlot &sq = pc->slot[P.iq], &st = pc->slot[P.it];
+    const FrameMisc* omisc = frame_host<const FrameMisc>(f, f.o_misc);
+    for (int p = 0; p < P.np; ++p) {
+        const int m = omisc->prob[p].m_cnt;
+        if (m < 0 || m > f.nq[p]) { frame_reset(f); viso_set_error("viso_match_desc: device returned %d matches for %d queries", m, f.nq[p]); return VISO_ERR_HIP; }
+        f.m[p] = m;
+    }
+    if (P.stereo) {   // tiles the stereo kernel left to the wide-band kernel
+        pc->narrow_streak = omisc->bad[1] == 0 ? pc->narrow_streak + 1 : 0;
+        if (omisc->bad[1] != 0 && P.skip_wide) return frame_repeat(c, pc, P);   // ... which was not in the launch
+    }
+    sq.bad_host = omisc->img_bad[0] != 0; st.bad_host = omisc->img_bad[1] != 0;   // the images' own flags, as their pack kernels left them
+    if (sq.bad_host || st.bad_host) {
+        pc->good_streak = 0; pc->distrust = PLAIN_DISTRUST_FRAMES;
+        if (!P.need_general) return frame_repeat(c, pc, P);   // unexpected: the launch had no kernel for them
+    } else {
+        pc->good_streak += 1;
+        if (pc->distrust > 0) pc->distrust -= 1;
+    }
+    if (f.m[0] > 0) memcpy(out_match, frame_rows(f, 0), sizeof(int) * 3 * (size_t)f.m[0]);
+    f.valid = P.stereo && pc->speculate;
+    f.have_xX = P.spec_x; f.tri_p = pc->tri_p;
+    *out_n = f.m[0];
+    return VISO_OK;
+}
+
+static int match_run(viso_ctx* c, PlainCache* pc, PlainProf& pp, FramePlan& P, int32_t* out_match, int* out_n, double* tt) {
+    hipStream_t s = c->stream; int r;
+    if ((r = frame_open(c, pc, P)) < 0 || (r = frame_fill_head(c, pc, P)) < 0 || (r = frame_copy_outs(c, pc, P)) < 0) return r;
+    if ((r = plain_blit(s, P.H, P.f->dev, (P.f->o_misc + sizeof(FrameMisc)) / 4)) < 0) return r;
+    pp.mark(1);
+    if (g_tr_on) tt[3] = tr_now();
+    if ((r = frame_queue_first(c, pc, P)) < 0) return r;
+    pp.mark(2);
+    if (!P.spec_B) {   // no join kernel for the first copy-out to ride in
+        hipLaunchKernelGGL(plain_out_kernel, dim3((unsigned)(P.H->outA.n_regions * P.H->outA.gx)), dim3(256), 0, s, P.H->outA);
+        HIP_TRY(hipGetLastError());
+    }
+    pp.mark(3);
+    if (P.spec_B && (r = frame_queue_second(c, pc, P)) < 0) return r;
+    if (g_tr_on) tt[4] = tr_now();
+    pp.wait_begin();
+    if ((r = plain_signal_wait(c, s, P.seqA)) < 0) return r;   // the first copy-out: whatever was launched behind it runs on
+    pp.wait_end();
+    if (g_tr_on) tt[5] = tr_now();
+    return frame_harvest(c, pc, P, out_match, out_n);
 }
 
 static int match_desc_locked(viso_ctx* c, PlainCache* pc, const float* kp1, int n1, const float* kp2, int n2, const float* d1, const float* d2,
-                             int dlen, const viso_match_params* mp, int32_t* out_match, int* out_n);
+                             int dlen, const viso_match_params* mp, int32_t* out_match, int* out_n) {
+    hipStream_t s = c->stream;
+    PlainProf pp(VISO_PLAIN_MATCH_DESC, s);
+    int r;
+    const int variant = matcher_effective(c->matcher_variant, dlen), extras = pack_extras(c->matcher_variant, dlen);
+    // the planes' shift (matcher variant 6): one call, no previous run to learn it from: the default, or the forced one
+    const int r8s = c->row8_force >= 0 ? c->row8_force : VISO_R8_DEFAULT;
+    // ---- the two images: resident already, or uploaded now (the uploads start before anything else is prepared)
+    if (g_tr_on < 0) { const char* e = getenv("VISO_PLAIN_TRACE"); g_tr_on = e && *e == '1'; }
+    double tt[7] = {g_tr_on ? tr_now() : 0, 0, 0, 0, 0, 0, 0};
+    int iq = plain_lookup(pc, kp1, d1, n1, dlen, extras, r8s);
+    int it = plain_lookup(pc, kp2, d2, n2, dlen, extras, r8s);
+    const bool hit_q = iq >= 0, hit_t = it >= 0;
+    const bool same_image = !hit_q && !hit_t && kp1 == kp2 && d1 == d2 && n1 == n2;   // one upload serves both sides
+    {
+        KpImport imp[2];
+        int n_imp = 0, cap_imp = 1;
+        if (!hit_q) {
+            if ((iq = plain_prepare(c, pc, kp1, n1, dlen, extras, r8s, it, -1, &imp[n_imp])) < 0) return iq;
+            ++n_imp; cap_imp = n1 > cap_imp ? n1 : cap_imp;
+        }
+        if (same_image) it = iq;
+        else if (!hit_t) {
+            if ((it = plain_prepare(c, pc, kp2, n2, dlen, extras, r8s, iq, -1, &imp[n_imp])) < 0) return it;
+            ++n_imp; cap_imp = n2 > cap_imp ? n2 : cap_imp;
+        }
+        // the new images' keypoints: ONE launch, a workgroup per image, while the host copies the rows
+        if (n_imp && (r = launch_sort_kp(s, nullptr, n_imp, cap_imp, nullptr, 0, nullptr, imp, n_imp)) < 0) return r;
+    }
+    if (g_tr_on > 0) { g_tr.acq_us[2] += tr_now() - tt[0]; g_tr.acq_calls += 1; }
+    if (!hit_q && (r = plain_finish(c, pc, iq, d1, s)) < 0) return r;
+    if (g_tr_on) tt[1] = tr_now();
+    if (!hit_t && !same_image && (r = plain_finish(c, pc, it, d2, s)) < 0) return r;
+    if (g_tr_on) tt[2] = tr_now();
+    const bool stereo_call = mp->enforce_epipolar != 0;
+    // ---- a temporal call the frame's stereo call has already answered?
+    if (!stereo_call) {
+        PlainFrame& cur = pc->frame[pc->cur];
+        PlainFrame& prv = pc->frame[pc->cur ^ 1];
+        if (pc->speculate && cur.valid)
+            for (int p = 1; p < PF_PROBS; ++p)
+                if (cur.have[p] && cur.tq[p] == iq && cur.tt[p] == it && pc->slot[iq].stamp == cur.stq[p] &&
+                    pc->slot[it].stamp == cur.stt[p] && params_equal(*mp, cur.mp[p])) {
+                    const int m = cur.m[p];
+                    if (m > 0) memcpy(out_match, frame_rows(cur, p), sizeof(int) * 3 * (size_t)m);
+                    *out_n = m;
+                    cur.used[p] = true;
+                    pc->spec_served[0] += 1;
+                    if (g_tr_on > 0) { g_tr.srv_us[0] += tt[2] - tt[0]; g_tr.srv_us[1] += tr_now() - tt[2]; g_tr.srv_n += 1; }
+                    return VISO_OK;
+                }
+        // the direct path it is; remember what a temporal call looks like, and whether it is the loop's
+        pc->tm = *mp; pc->tm_known = true;
+        if (cur.valid && prv.valid && ((iq == cur.L && it == prv.L && pc->slot[it].stamp == prv.sL) ||
+                                       (iq == cur.R && it == prv.R && pc->slot[it].stamp == prv.sR))) pc->tm_pattern = true;
+    }
+    FramePlan P{};
+    P.iq = iq; P.it = it; P.n1 = n1; P.dlen = dlen; P.variant = variant; P.extras = extras; P.r8s = r8s; P.mp = mp; P.stereo = stereo_call;
+    for (int pass = 0; pass < 2; ++pass) {   // second pass: the first lacked a kernel that turned out to have work (frame_repeat)
+        P.force_general = pass == 1;
+        r = match_run(c, pc, pp, P, out_match, out_n, tt);
+        if (r != PLAIN_RERUN) break;
+    }
+    if (r < 0) return r;
+    if (g_tr_on) {
+        tt[6] = tr_now();
+        const int k = (hit_q ? 0 : 1) + (hit_t ? 0 : 1);
+        for (int j = 0; j < 6; ++j) g_tr.us[k][j] += tt[j + 1] - tt[j];
+        g_tr.n[k] += 1;
+    }
+    return VISO_OK;
+}
 
 // match_desc, reference src/viso.cpp:669-726.
-extern "C" int viso_match_desc(const float* kp1, int n1, const float* kp2, int n2,
-                               const float* d1, const float* d2, int dlen,
+extern "C" int viso_match_desc(const float* kp1, int n1, const float* kp2, int n2, const float* d1, const float* d2, int dlen,
                                const viso_match_params* mp, int32_t* out_match, int* out_n) {
     if (n1 < 0 || n2 < 0 || dlen <= 0 || !mp || !out_n || mp->max_neighbors <= 0 ||
         (n1 && (!kp1 || !d1 || !out_match)) || (n2 && (!kp2 || !d2))) {
@@ -642,342 +975,6 @@ extern "C" int viso_match_desc(const float* kp1, int n1, const float* kp2, int n
     return r;
 }
 
-static int match_desc_locked(viso_ctx* c, PlainCache* pc, const float* kp1, int n1, const float* kp2, int n2, const float* d1, const float* d2,
-                             int dlen, const viso_match_params* mp, int32_t* out_match, int* out_n) {
-    hipStream_t s = c->stream;
-    PlainProf pp(VISO_PLAIN_MATCH_DESC, s);
-    int r;
-    const int variant = matcher_effective(c->matcher_variant, dlen);
-    const int extras = pack_extras(c->matcher_variant, dlen);
-    // the planes' shift (matcher variant 6): one call, no previous run to learn it from: the default, or the forced one
-    const int r8s = c->row8_force >= 0 ? c->row8_force : VISO_R8_DEFAULT;
-    // ---- the two images: resident already, or uploaded now (the uploads start before anything else is prepared)
-    bool hit_q = false, hit_t = false;
-    if (g_tr_on < 0) { const char* e = getenv("VISO_PLAIN_TRACE"); g_tr_on = e && *e == '1'; }
-    double tt[7] = {0, 0, 0, 0, 0, 0, 0};
-    if (g_tr_on) tt[0] = tr_now();
-    int iq = plain_lookup(pc, kp1, d1, n1, dlen, extras, r8s);
-    int it = plain_lookup(pc, kp2, d2, n2, dlen, extras, r8s);
-    hit_q = iq >= 0; hit_t = it >= 0;
-    const bool same_image = !hit_q && !hit_t && kp1 == kp2 && d1 == d2 && n1 == n2;   // one upload serves both sides
-    {
-        KpImport imp[2];
-        int n_imp = 0, cap_imp = 1;
-        if (!hit_q) {
-            if ((iq = plain_prepare(c, pc, kp1, n1, dlen, extras, r8s, it, -1, &imp[n_imp])) < 0) return iq;
-            ++n_imp; cap_imp = n1 > cap_imp ? n1 : cap_imp;
-        }
-        if (same_image) it = iq;
-        else if (!hit_t) {
-            if ((it = plain_prepare(c, pc, kp2, n2, dlen, extras, r8s, iq, -1, &imp[n_imp])) < 0) return it;
-            ++n_imp; cap_imp = n2 > cap_imp ? n2 : cap_imp;
-        }
-        // the new images' keypoints: ONE launch, a workgroup per image, while the host copies the rows
-        if (n_imp && (r = launch_sort_kp(s, nullptr, n_imp, cap_imp, nullptr, 0, nullptr, imp, n_imp)) < 0) return r;
-    }
-    if (g_tr_on > 0) { g_acq_us[2] += tr_now() - tt[0]; g_acq_calls += 1; }
-    if (!hit_q && (r = plain_finish(c, pc, iq, d1, s)) < 0) return r;
-    if (g_tr_on) tt[1] = tr_now();
-    if (!hit_t && !same_image && (r = plain_finish(c, pc, it, d2, s)) < 0) return r;
-    if (g_tr_on) tt[2] = tr_now();
-    const bool stereo_call = mp->enforce_epipolar != 0;
-    // ---- a temporal call the frame's stereo call has already answered?
-    if (!stereo_call) {
-        PlainFrame& cur = pc->frame[pc->cur];
-        PlainFrame& prv = pc->frame[pc->cur ^ 1];
-        if (pc->speculate && cur.valid)
-            for (int p = 1; p < PF_PROBS; ++p)
-                if (cur.have[p] && cur.tq[p] == iq && cur.tt[p] == it && pc->slot[iq].stamp == cur.stq[p] &&
-                    pc->slot[it].stamp == cur.stt[p] && params_equal(*mp, cur.mp[p])) {
-                    const int m = cur.m[p];
-                    if (m > 0) memcpy(out_match, frame_rows(cur, p), sizeof(int) * 3 * (size_t)m);
-                    *out_n = m;
-                    cur.used[p] = true;
-                    pc->spec_served[0] += 1;
-                    if (g_tr_on > 0) { g_srv_us[0] += tt[2] - tt[0]; g_srv_us[1] += tr_now() - tt[2]; g_srv_n += 1; }
-                    return VISO_OK;
-                }
-        // the direct path it is; remember what a temporal call looks like, and whether it is the loop's
-        pc->tm = *mp; pc->tm_known = true;
-        if (cur.valid && prv.valid && ((iq == cur.L && it == prv.L && pc->slot[it].stamp == prv.sL) ||
-                                       (iq == cur.R && it == prv.R && pc->slot[it].stamp == prv.sR))) pc->tm_pattern = true;
-    }
-    for (int pass = 0; pass < 2; ++pass) {   // second pass: an image nobody expected turned out not to fit the u16 rows
-        r = match_run(c, pc, pp, iq, it, hit_q, hit_t, n1, n2, dlen, mp, variant, extras, r8s, out_match, out_n, pass == 1, tt);
-        if (r != PLAIN_RERUN) break;
-    }
-    if (r < 0) return r;
-    if (g_tr_on) {
-        tt[6] = tr_now();
-        const int k = (hit_q ? 0 : 1) + (hit_t ? 0 : 1);
-        for (int j = 0; j < 6; ++j) g_tr_us[k][j] += tt[j + 1] - tt[j];
-        g_tr_n[k] += 1;
-    }
-    return VISO_OK;
-}
-
-static int match_run(viso_ctx* c, PlainCache* pc, PlainProf& pp, int iq, int it, bool hit_q, bool hit_t, int n1, int n2, int dlen,
-                     const viso_match_params* mp, int variant, int extras, int r8s, int32_t* out_match, int* out_n,
-                     bool force_general, double* tt) {
-    hipStream_t s = c->stream;
-    int r;
-    (void)n2; (void)hit_q; (void)hit_t;
-    const bool stereo_call = mp->enforce_epipolar != 0;
-    const int saved_cur = pc->cur;
-    const unsigned long long saved_no = pc->frame_no;
-    // ---- which frame object takes the call, and which problems ride along
-    PlainFrame* f = &pc->frame[2];
-    int np = 1;
-    bool spec_x = false, spec_B = false;
-    if (stereo_call && pc->speculate) {
-        if (pc->frame[pc->cur ^ 1].pending_B && (r = frame_wait_B(c, pc->frame[pc->cur ^ 1])) < 0) return r;
-        // The frame that leaves is the one before the last stereo call's: every call that could have used its results is over,
-        // so what it computed ahead and nobody asked for is known now, whatever becomes of THIS launch (a repeated launch finds
-        // the object reset -- not valid -- and counts nothing twice)
-        frame_retire(pc, pc->frame[pc->cur ^ 1]);
-        pc->frame_no += 1;
-        pc->cur ^= 1;
-        f = &pc->frame[pc->cur];
-        PlainFrame& prv = pc->frame[pc->cur ^ 1];
-        frame_reset(*f);
-        f->L = iq; f->R = it; f->sL = pc->slot[iq].stamp; f->sR = pc->slot[it].stamp;
-        if (pc->tm_known && pc->tm_pattern && prv.valid && iq != it && prv.L != prv.R &&
-            pc->slot[prv.L].valid && pc->slot[prv.L].stamp == prv.sL && pc->slot[prv.R].valid && pc->slot[prv.R].stamp == prv.sR &&
-            pc->slot[prv.L].dlen == dlen && pc->slot[prv.R].dlen == dlen && pc->slot[prv.L].extras == extras && pc->slot[prv.R].extras == extras &&
-            pc->slot[prv.L].r8s == r8s && pc->slot[prv.R].r8s == r8s && prv.L != iq && prv.L != it && prv.R != iq && prv.R != it)
-            np = 3;
-        spec_x = pc->tri_known && pc->x_pattern;
-        spec_B = np == 3 && spec_x && prv.have_xX && prv.have[0] && pc->circ_pattern && pc->rs_known && pc->rs_pattern && pc->rs_delta_stable &&
-                 pc->rs_p.ransac_iter >= 1 && pc->rs_p.ransac_iter <= 4096;
-    } else {
-        frame_reset(*f);
-    }
-    PlainSlot &sq = pc->slot[iq], &st = pc->slot[it];
-    f->have[0] = true; f->nq[0] = n1; f->tq[0] = iq; f->tt[0] = it; f->stq[0] = sq.stamp; f->stt[0] = st.stamp; f->mp[0] = *mp;
-    if (np == 3) {
-        PlainFrame& prv = pc->frame[pc->cur ^ 1];
-        f->have[1] = true; f->nq[1] = sq.n; f->tq[1] = iq; f->tt[1] = prv.L; f->stq[1] = sq.stamp; f->stt[1] = prv.sL; f->mp[1] = pc->tm;
-        f->have[2] = true; f->nq[2] = st.n; f->tq[2] = it; f->tt[2] = prv.R; f->stq[2] = st.stamp; f->stt[2] = prv.sR; f->mp[2] = pc->tm;
-    }
-    int cap = n1;
-    for (int p = 1; p < np; ++p) cap = f->nq[p] > cap ? f->nq[p] : cap;
-    if ((r = frame_reserve(c, *f, cap)) < 0) return r;
-    const size_t C = (size_t)(cap > 0 ? cap : 1);
-    // ---- the head of the frame's block: problems, the images to sort and pack, zeroed counters -- ONE copy in
-    char* hin;
-    if ((r = ctx_pinned(c, 0, f->o_misc + 256, &hin)) < 0) return r;
-    FrameHead* H = reinterpret_cast<FrameHead*>(hin);
-    memset(hin + f->o_misc, 0, 256);
-    int* hmisc = reinterpret_cast<int*>(hin + f->o_misc);
-    int* dmisc = reinterpret_cast<int*>(f->dev + f->o_misc);
-    // misc: [6] overflow queue length  [7] "some image of this launch is flagged" (lets the general kernels leave at once)
-    // [8] tiles match_stereo_kernel declines (BatchMatchArgs::bad[1])  [16 + 4p] matches of problem p, [18 + 4p] its scored pairs (u64)
-    char* sc = f->dev + f->o_end;
-    int2* dovf = reinterpret_cast<int2*>(sc + PF_PROBS * (al256(sizeof(int2) * C) + al256(sizeof(int) * C) + al256(sizeof(int) * (C / 64 + 1))));
-    // The general (float / double) kernels are for images whose descriptors do not fit the u16 rows.  Whether a NEW image
-    // does is known only after its pack kernel has run; once a few launches in a row have seen none, new images are expected
-    // to fit and the three general kernels are left out of the launch (15 us of the chain).  If the expectation fails
-    // -- the images' own flags come back with the results -- sort_matches_kernel has emitted EMPTY lists for the problems
-    // concerned (flagged_empty) and the call is repeated with the general kernels: same results, later.
-    bool any_bad = false, any_unknown = false;
-    for (int p = 0; p < np; ++p) {
-        PlainSlot &a = pc->slot[f->tq[p]], &b = pc->slot[f->tt[p]];
-        if (a.bad_host == 1 || b.bad_host == 1) any_bad = true;
-        if (a.bad_host < 0 || b.bad_host < 0) any_unknown = true;
-    }
-    // A source that has produced a flagged image lately keeps the general kernels in the launch: a stream with sporadic
-    // fractional images would otherwise pay a dropped launch + a full synchronize + a second launch on every such frame
-    const bool trust = pc->good_streak >= 2 && !force_general && pc->distrust == 0;
-    const bool need_general = any_bad || (any_unknown && !trust) || dlen > VISO_ROW;
-    for (int p = 0; p < np; ++p) {
-        PlainSlot &a = pc->slot[f->tq[p]], &b = pc->slot[f->tt[p]];
-        MatchProblem P{};
-        P.q = a.v; P.t = b.v;
-        char* ps = sc + p * (al256(sizeof(int2) * C) + al256(sizeof(int) * C) + al256(sizeof(int) * (C / 64 + 1)));
-        P.res = reinterpret_cast<int2*>(ps);
-        P.pos = reinterpret_cast<int*>(ps + al256(sizeof(int2) * C));
-        P.tile_flag = reinterpret_cast<int*>(ps + al256(sizeof(int2) * C) + al256(sizeof(int) * C));
-        P.sorted = reinterpret_cast<int*>(f->dev + f->o_sorted[p]);
-        P.m_cnt = dmisc + 16 + 4 * p; P.scored = reinterpret_cast<unsigned long long*>(dmisc + 18 + 4 * p);
-        P.pidx = p == 0 ? 0 : 1; P.cap = cap;
-        P.ovf = dovf; P.ovf_cnt = dmisc + 6;
-        H->p[p] = P;
-    }
-    if (need_general) hmisc[7] = 1;   // the general kernels' early-exit hint; they look at every image's own flag
-    if (spec_x) {
-        TriItem T{};
-        T.kp1 = sq.v.kp; T.kp2 = st.v.kp; T.match = reinterpret_cast<const int*>(f->dev + f->o_sorted[0]); T.m_cnt = dmisc + 16;
-        T.x = reinterpret_cast<double*>(f->dev + f->o_x); T.X = reinterpret_cast<double*>(f->dev + f->o_X); T.ld = (int)C;
-        H->tri = T;
-    }
-    int *rs_tab = nullptr, *rs_queue = nullptr, rs_tabn = 0;
-    if (spec_B) {
-        PlainFrame& prv = pc->frame[pc->cur ^ 1];
-        const int iters = pc->rs_p.ransac_iter;
-        double* dtrh; int* dhyp; char* drot;
-        rs_tabn = sq.n > st.n ? sq.n : st.n;
-        if (pc->slot[prv.L].n > rs_tabn) rs_tabn = pc->slot[prv.L].n;
-        if ((r = ctx_scratch(c, SLOT_CIRCLE_TAB, sizeof(int) * 3 * (size_t)(rs_tabn + 1), (void**)&rs_tab)) < 0) return r;
-        if ((r = ctx_scratch(c, SLOT_HYP_WORDS, sizeof(int) * (4 + 2 * (size_t)iters), (void**)&dhyp)) < 0) return r;
-        if ((r = ctx_scratch(c, SLOT_HYP_TR, sizeof(double) * 6 * (size_t)(iters + 1), (void**)&dtrh)) < 0) return r;
-        if ((r = ctx_scratch(c, SLOT_RANSAC_QUEUE, sizeof(int) * (2 + 4 * (size_t)iters + 3), (void**)&rs_queue, true)) < 0) return r;
-        if ((r = ctx_scratch(c, SLOT_RANSAC_ROT, viso_rot_bytes(iters), (void**)&drot)) < 0) return r;
-        f->rs_p = pc->rs_p; f->rs_seed = pc->rs_seed; f->rs_frame = pc->rs_last_frame + pc->rs_delta;
-        SolverItem it{};
-        it.X = reinterpret_cast<const double*>(f->dev + f->o_Xpc); it.obs = reinterpret_cast<const double*>(f->dev + f->o_xc);
-        it.m_ptr = dmisc + 32; it.ld = (int)C; it.samples = nullptr; it.samp_h = rs_queue + 2 + iters; it.frame = f->rs_frame;
-        it.tr_h = dtrh; it.ok_h = dhyp; it.cnt_h = dhyp + iters; it.rot = drot;
-        int* rso = reinterpret_cast<int*>(f->dev + f->o_rs);
-        it.kept = rso; it.ok = rso + 1; it.n_inl = rso + 2; it.tr = reinterpret_cast<double*>(f->dev + f->o_rs + 64); it.inl = reinterpret_cast<int*>(f->dev + f->o_rs + 128);
-        H->rs = it;
-        (void)prv;
-    }
-    // ---- the copy-outs into the frame's pinned mirror (common.h, OutArgs): the lists (and x, X) behind the sort kernel -- riding in
-    // the join kernel's launch when the frame has one, a kernel of their own otherwise; the join and the gathered columns behind
-    // the join kernel, riding in ransac_coop_kernel's launch.  Each signals: match_circle returns as soon as the join is there,
-    // the RANSAC stage runs on behind the caller's gather loop
-    int seqA = 0;
-    {
-        auto region = [&](OutArgs& o, size_t off, const int* cnt, int row_words, int max_rows) {
-            OutRegion& R = o.r[o.n_regions++];
-            R.src = reinterpret_cast<const uint32_t*>(f->dev + off);
-            R.dst = reinterpret_cast<uint32_t*>(f->host + (off - f->o_misc));
-            R.cnt = cnt; R.row_words = row_words; R.max_rows = max_rows;
-        };
-        OutArgs& oa = H->outA;
-        oa = OutArgs{};
-        region(oa, f->o_misc, nullptr, 40, 1);
-        {   // the two images' own flags: words 40, 41 of the mirror
-            OutRegion& R0 = oa.r[oa.n_regions++];
-            R0.src = reinterpret_cast<const uint32_t*>(sq.v.bad); R0.dst = reinterpret_cast<uint32_t*>(f->host) + 40; R0.cnt = nullptr; R0.row_words = 1; R0.max_rows = 1;
-            OutRegion& R1 = oa.r[oa.n_regions++];
-            R1.src = reinterpret_cast<const uint32_t*>(st.v.bad); R1.dst = reinterpret_cast<uint32_t*>(f->host) + 41; R1.cnt = nullptr; R1.row_words = 1; R1.max_rows = 1;
-        }
-        for (int p = 0; p < np; ++p) region(oa, f->o_sorted[p], dmisc + 16 + 4 * p, 3, f->nq[p]);
-        if (spec_x) {
-            for (int k = 0; k < 4; ++k) region(oa, f->o_x + sizeof(double) * C * k, dmisc + 16, 2, n1);
-            for (int k = 0; k < 3; ++k) region(oa, f->o_X + sizeof(double) * C * k, dmisc + 16, 2, n1);
-        }
-        const size_t tpb = spec_B ? 1024 : 256;   // threads of the workgroups that will do it: four words each
-        oa.gx = (int)((3 * C + 4 * tpb - 1) / (4 * tpb));
-        if ((r = plain_signal_next(c, &oa.sig)) < 0) return r;
-        seqA = oa.sig.seq;
-        if (spec_B) {
-            OutArgs& oj = H->outJ;
-            oj = OutArgs{};
-            region(oj, f->o_misc + 128, nullptr, 8, 1);                          // misc[32..39]: the join's row count
-            region(oj, f->o_circ, dmisc + 32, 6, cap);
-            for (int k = 0; k < 4; ++k) region(oj, f->o_xc + sizeof(double) * C * k, dmisc + 32, 2, cap);
-            for (int k = 0; k < 3; ++k) region(oj, f->o_Xpc + sizeof(double) * C * k, dmisc + 32, 2, cap);
-            oj.gx = (int)((6 * C + 1023) / 1024);
-            if ((r = plain_signal_next(c, &oj.sig)) < 0) return r;
-            f->seqJ = oj.sig.seq;
-        }
-    }
-    if ((r = plain_blit(s, hin, f->dev, (f->o_misc + 256) / 4)) < 0) return r;
-    pp.mark(1);
-    if (g_tr_on) tt[3] = tr_now();
-    const MatchProblem* dprob = reinterpret_cast<const MatchProblem*>(f->dev);
-    MatchParamsDev mpd[2];
-    fill_match_params(&mpd[0], mp);
-    if (np == 3) fill_match_params(&mpd[1], &pc->tm); else mpd[1] = mpd[0];
-    const int general_possible = need_general ? 1 : 0;
-    int kinds = np == 3 ? VISO_KIND_ALL : mpd[0].epi ? VISO_KIND_STEREO : VISO_KIND_TEMPORAL;
-    // match_batch_kernel<1> takes the tiles whose epipolar band match_stereo_kernel finds too wide (pairs that are not
-    // rectified): after a few stereo launches without such a tile it is left out (5 us of the chain the caller waits for);
-    // the number of declined tiles comes back with the results, and a launch that had one without the kernel is repeated
-    const bool skip_wide = mpd[0].epi != 0 && pc->narrow_streak >= 2 && !force_general;
-    if (skip_wide) kinds |= VISO_KIND_NO_WIDE;
-    if ((r = launch_match_timed(s, dprob, np, cap, dlen, mpd, dmisc + 7, nullptr, nullptr, 0, variant, dovf, dmisc + 6, r8s,
-                                general_possible, kinds)) < 0) return r;
-    if (spec_x) {   // collect_matches / triangulate_rectified of the stereo list ride in the sort kernel (no kernel of their own)
-        SolverParamsDev sp;
-        fill_solver_params(&sp, &pc->tri_p);
-        if ((r = launch_sort(s, dprob, np, cap, need_general ? 0 : 1, reinterpret_cast<const TriItem*>(f->dev + offsetof(FrameHead, tri)), &sp)) < 0) return r;
-    } else if ((r = launch_sort(s, dprob, np, cap, need_general ? 0 : 1)) < 0) return r;
-    pp.mark(2);
-    if (!spec_B) {   // no join kernel to ride in
-        hipLaunchKernelGGL(plain_out_kernel, dim3((unsigned)(H->outA.n_regions * H->outA.gx)), dim3(256), 0, s, H->outA);
-        HIP_TRY(hipGetLastError());
-    }
-    pp.mark(3);
-    if (spec_B) {   // ---- the second part: it keeps running while the caller goes through collect / triangulate / the temporal calls
-        PlainFrame& prv = pc->frame[pc->cur ^ 1];
-        const int* pmisc = reinterpret_cast<const int*>(prv.dev + prv.o_misc);
-        CircleArgs ca{};
-        ca.lr = reinterpret_cast<const int*>(f->dev + f->o_sorted[0]); ca.lrp = reinterpret_cast<const int*>(prv.dev + prv.o_sorted[0]);
-        ca.m11 = reinterpret_cast<const int*>(f->dev + f->o_sorted[1]); ca.m22 = reinterpret_cast<const int*>(f->dev + f->o_sorted[2]);
-        ca.n_lr_p = dmisc + 16; ca.n_lrp_p = pmisc + 16; ca.n11_p = dmisc + 20; ca.n22_p = dmisc + 24;
-        ca.rows = reinterpret_cast<int*>(f->dev + f->o_circ); ca.cap = cap; ca.out_n = dmisc + 32;
-        // x_c / Xp_c of :1292-1305 come out of the join kernel's tail (no gather kernel of their own)
-        ca.g_x = reinterpret_cast<const double*>(f->dev + f->o_x); ca.g_ldx = (int)C;
-        ca.g_Xp = reinterpret_cast<const double*>(prv.dev + prv.o_X); ca.g_ldXp = prv.cap > 0 ? prv.cap : 1;
-        ca.g_xc = reinterpret_cast<double*>(f->dev + f->o_xc); ca.g_Xpc = reinterpret_cast<double*>(f->dev + f->o_Xpc); ca.g_ldc = (int)C;
-        ca.ride = reinterpret_cast<const OutArgs*>(f->dev + offsetof(FrameHead, outA)); ca.ride_blocks = H->outA.n_regions * H->outA.gx;
-        if ((r = launch_circle_table(s, ca, rs_tab, rs_tabn)) < 0) return r;
-        SolverParamsDev sp;
-        fill_solver_params(&sp, &f->rs_p);
-        RefitMirror rm{};   // the pose and the inliers go into the mirror from the refit kernel itself, which signals
-        rm.res_src = reinterpret_cast<const uint32_t*>(f->dev + f->o_rs); rm.res_dst = reinterpret_cast<uint32_t*>(f->host + (f->o_rs - f->o_misc)); rm.res_words = 32;
-        rm.n_inl = reinterpret_cast<const int*>(f->dev + f->o_rs) + 2;
-        rm.inl_src = reinterpret_cast<const uint32_t*>(f->dev + f->o_rs + 128); rm.inl_dst = reinterpret_cast<uint32_t*>(f->host + (f->o_rs - f->o_misc) + 128); rm.max_inl = cap;
-        if ((r = plain_signal_next(c, &rm.sig)) < 0) return r;
-        f->seqB = rm.sig.seq;
-        if ((r = launch_ransac(s, reinterpret_cast<const SolverItem*>(f->dev + offsetof(FrameHead, rs)), 1, f->rs_p.ransac_iter, f->rs_seed, sp,
-                               rs_queue, c->gn_split ? c->gn_split : 1, cap, &rm,
-                               reinterpret_cast<const OutArgs*>(f->dev + offsetof(FrameHead, outJ)), H->outJ.n_regions * H->outJ.gx)) < 0) return r;
-        f->have_B = true; f->pending_B = true; f->pending_J = true;
-    }
-    if (g_tr_on) tt[4] = tr_now();
-    pp.wait_begin();
-    if ((r = plain_signal_wait(c, s, seqA)) < 0) return r;   // the first copy-out: whatever was launched behind it runs on
-    pp.wait_end();
-    if (g_tr_on) tt[5] = tr_now();
-    const int* omisc = reinterpret_cast<const int*>(f->host);
-    for (int p = 0; p < np; ++p) {
-        const int m = omisc[16 + 4 * p];
-        if (m < 0 || m > f->nq[p]) { frame_reset(*f); viso_set_error("viso_match_desc: device returned %d matches for %d queries", m, f->nq[p]); return VISO_ERR_HIP; }
-        f->m[p] = m;
-    }
-    if (mpd[0].epi != 0) {   // tiles the stereo kernel left to the wide-band kernel (misc[8])
-        if (omisc[8] != 0) {
-            pc->narrow_streak = 0;
-            if (skip_wide) {   // ... which was not in the launch: everything it produced is dropped, the call repeated with it
-                HIP_TRY(hipStreamSynchronize(s));
-                f->pending_B = false; f->pending_J = false;
-                frame_reset(*f);
-                pc->cur = saved_cur; pc->frame_no = saved_no;
-                pc->general_reruns += 1;
-                return PLAIN_RERUN;
-            }
-        } else {
-            pc->narrow_streak += 1;
-        }
-    }
-    sq.bad_host = omisc[40] != 0; st.bad_host = omisc[41] != 0;   // the images' own flags, as their pack kernels left them
-    if (sq.bad_host || st.bad_host) {
-        pc->good_streak = 0;
-        pc->distrust = PLAIN_DISTRUST_FRAMES;
-        if (!need_general) {   // unexpected: the launch had no kernel for them.  Everything it produced is dropped, the call repeated
-            HIP_TRY(hipStreamSynchronize(s));
-            f->pending_B = false; f->pending_J = false;
-            frame_reset(*f);
-            pc->cur = saved_cur; pc->frame_no = saved_no;
-            pc->general_reruns += 1;
-            return PLAIN_RERUN;
-        }
-    } else {
-        pc->good_streak += 1;
-        if (pc->distrust > 0) pc->distrust -= 1;
-    }
-    const int m = f->m[0];
-    if (m > 0) memcpy(out_match, frame_rows(*f, 0), sizeof(int) * 3 * (size_t)m);
-    f->valid = stereo_call && pc->speculate;
-    f->have_xX = spec_x; f->tri_p = pc->tri_p;
-    *out_n = m;
-    return VISO_OK;
-}
-
 // ---- the frame's other calls (circle.hip asks before it goes to the device) ----------------------------------------
 // collect_matches(kp1, kp2, match) of the stereo call's own output: x is there already.  1 = served, 0 = not.
 int plain_try_collect(viso_ctx* c, const float* kp1, int n1, const float* kp2, int n2, const int32_t* match, int n, double* x) {
@@ -992,8 +989,8 @@ int plain_try_collect(viso_ctx* c, const float* kp1, int n1, const float* kp2, i
     // the call is the loop's: worth computing ahead from the next frame on
     pc->x_pattern = true;
     if (!f.have_xX) return 0;
-    const size_t C = (size_t)(f.cap > 0 ? f.cap : 1);
-    const double* hx = reinterpret_cast<const double*>(f.host + (f.o_x - f.o_misc));
+    const size_t C = frame_ld(f);
+    const double* hx = frame_host<const double>(f, f.o_x);
     for (int k = 0; k < 4; ++k) memcpy(x + (size_t)k * n, hx + C * k, sizeof(double) * (size_t)n);
     f.used_x = true;
     pc->spec_served[1] += 1;
@@ -1008,11 +1005,11 @@ int plain_try_triangulate(viso_ctx* c, const double* x, int m, const viso_param*
     if (!pc->speculate) return 0;
     PlainFrame& f = pc->frame[pc->cur];
     if (!f.valid || !f.have_xX || f.m[0] != m || m <= 0 || !tri_equal(*p, f.tri_p)) return 0;
-    const size_t C = (size_t)(f.cap > 0 ? f.cap : 1);
-    const double* hx = reinterpret_cast<const double*>(f.host + (f.o_x - f.o_misc));
+    const size_t C = frame_ld(f);
+    const double* hx = frame_host<const double>(f, f.o_x);
     for (int k = 0; k < 4; ++k)
         if (memcmp(hx + C * k, x + (size_t)k * m, sizeof(double) * (size_t)m) != 0) return 0;
-    const double* hX = reinterpret_cast<const double*>(f.host + (f.o_X - f.o_misc));
+    const double* hX = frame_host<const double>(f, f.o_X);
     for (int k = 0; k < 3; ++k) memcpy(X + (size_t)k * m, hX + C * k, sizeof(double) * (size_t)m);
     f.used_X = true;
     pc->spec_served[2] += 1;
@@ -1034,11 +1031,11 @@ int plain_try_circle(viso_ctx* c, const int32_t* lr, int n_lr, const int32_t* lr
     if (f.have[1] && f.have[2] && !full) return 0;
     pc->circ_pattern = true;   // the loop's call: the stereo lists of this frame and the last
     if (!f.have_B || !full) return 0;
-    if (frame_wait_J(c, f) < 0) return 0;
+    if (frame_wait(c, f, 0) < 0) return 0;
     const int cnt = f.n_circ;
     if (cnt < 0 || cnt > f.cap) return 0;
     const int w = cnt < cap ? cnt : cap;
-    const int* rows = reinterpret_cast<const int*>(f.host + (f.o_circ - f.o_misc));
+    const int* rows = frame_host<const int>(f, f.o_circ);
     for (int i = 0; i < w; ++i) {
         circ[4 * i + 0] = rows[6 * i + 0]; circ[4 * i + 1] = rows[6 * i + 1]; circ[4 * i + 2] = rows[6 * i + 2]; circ[4 * i + 3] = rows[6 * i + 3];
         pcl[2 * i + 0] = rows[6 * i + 4]; pcl[2 * i + 1] = rows[6 * i + 5];
@@ -1072,21 +1069,21 @@ int plain_try_ransac(viso_ctx* c, const double* X, const double* obs, int m, dou
     PlainFrame& f = pc->frame[pc->cur];
     bool served = false;
     if (pc->speculate && !samples && f.valid && f.have_B && rs_param_equal(*p, f.rs_p) && seed == f.rs_seed && frame == f.rs_frame &&
-        frame_wait_B(c, f) >= 0 && f.n_circ == m && m >= 3 && m <= f.cap) {
-        const size_t C = (size_t)(f.cap > 0 ? f.cap : 1);
-        const double* hXp = reinterpret_cast<const double*>(f.host + (f.o_Xpc - f.o_misc));
-        const double* hxc = reinterpret_cast<const double*>(f.host + (f.o_xc - f.o_misc));
+        frame_wait(c, f, 1) >= 0 && f.n_circ == m && m >= 3 && m <= f.cap) {
+        const size_t C = frame_ld(f);
+        const double* hXp = frame_host<const double>(f, f.o_Xpc);
+        const double* hxc = frame_host<const double>(f, f.o_xc);
         bool same = true;
         for (int k = 0; k < 3 && same; ++k) same = memcmp(hXp + C * k, X + (size_t)k * m, sizeof(double) * (size_t)m) == 0;
         for (int k = 0; k < 4 && same; ++k) same = memcmp(hxc + C * k, obs + (size_t)k * m, sizeof(double) * (size_t)m) == 0;
-        const int* rso = reinterpret_cast<const int*>(f.host + (f.o_rs - f.o_misc));
-        if (same && rso[2] >= 0 && rso[2] <= m) {
+        const RansacOut* rso = frame_host<const RansacOut>(f, f.o_rs);
+        if (same && rso->n_inl >= 0 && rso->n_inl <= m) {
             // computed ahead without knowing the caller's best_tr: where the reference would leave it alone (no hypothesis with
-            // support, src/viso.cpp:1564-1568) the stage wrote none and says so in rso[0]
-            if (!rso[0]) memcpy(best_tr, f.host + (f.o_rs - f.o_misc) + 64, sizeof(double) * 6);
-            *n_inl = rso[2];
-            if (rso[2] > 0) memcpy(best_inl, f.host + (f.o_rs - f.o_misc) + 128, sizeof(int) * (size_t)rso[2]);
-            *ret = rso[1] ? 1 : 0;
+            // support, src/viso.cpp:1564-1568) the stage wrote none and says so in `kept`
+            if (!rso->kept) memcpy(best_tr, rso->tr, sizeof(double) * 6);
+            *n_inl = rso->n_inl;
+            if (rso->n_inl > 0) memcpy(best_inl, rso->inl, sizeof(int) * (size_t)rso->n_inl);
+            *ret = rso->ok ? 1 : 0;
             f.used_rs = true;
             pc->spec_served[3] += 1;
             served = true;

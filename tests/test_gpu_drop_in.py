@@ -364,3 +364,25 @@ def test_shuffled_and_perturbed_call_sequences_always_get_their_own_results(viso
         prev = cur
     st_ = drop_in.plain_stats()
     assert st_["served"][0] + st_["served"][1] > 0              # the frame logic did take part
+
+
+# What the SECOND of two runs of the module's sequence adds to the plain family's counters.  Recorded from the commit before
+# the frame launch was split into stages (the same test body: alone in two fresh processes and behind the module's other tests).
+SECOND_RUN = {"served": [24, 14, 25, 10], "wasted": [1, 0, 1, 2], "hits": 52, "misses": 28, "general_reruns": 0}
+
+
+def test_the_second_run_of_the_loop_is_answered_call_for_call_as_recorded(viso, seq):
+    """The bounds above (`served[0] >= 2 * (nf - 6)` ...) would not notice one frame that silently fell to the direct path.
+    After the learned patterns are reset, the first run teaches them again and the second meets a state that only the first
+    determines: its served / wasted calls, cache hits and misses and repeated launches are constants.  Every counter repeated
+    from process to process on the recording commit, so none is left out of the equality."""
+    drop_in.plain_cache(True)
+    drop_in.plain_speculate(True)
+    stats = []
+    for _ in range(2):
+        stats.append(drop_in.plain_stats())
+        drop_in.run(seq["kp"], seq["desc"], seq["n"], seq["F"], seq["param"], seed=5, first_frame=100)
+    before, after = stats[1], drop_in.plain_stats()
+    got = {k: [a - b for a, b in zip(after[k], before[k])] if isinstance(after[k], list) else after[k] - before[k] for k in SECOND_RUN}
+    print("second run:", got)
+    assert got == SECOND_RUN
