@@ -2,6 +2,7 @@
 // triangulation (reference src/viso.cpp:207-243 match_circle, :501-514
 // collect_matches, :1137-1162 triangulate_rectified, :1292-1305 gather).
 #include "common.h"
+#include "wave.h"
 
 #include <string.h>
 

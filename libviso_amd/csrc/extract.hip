@@ -107,8 +107,8 @@ __global__ __launch_bounds__(256) void extract_pack_kernel(const ImageView* __re
     const float xhi = (float)cols + 16.f, yhi = (float)rows + 16.f;
 #pragma unroll
     for (int k = 0; k < VISO_EXT_KPW; ++k) {
-        const float fx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pl.x), k));
-        const float fy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pl.y), k));
+        const float fx = readlane_f32(pl.x, k);
+        const float fy = readlane_f32(pl.y, k);
         px[k] = (int)rintf(fminf(fmaxf(fx, -16.f), xhi));   // Point2i p = kp.pt, src/viso.cpp:1013
         py[k] = (int)rintf(fminf(fmaxf(fy, -16.f), yhi));
     }

@@ -12,6 +12,7 @@
 // - k*(a+c)*(a+c)).  OpenCV's running column sums are the one thing an algorithm-level
 // restatement cannot pin (see the oracle's header): parity with a real OpenCV is unpinned.
 #include "common.h"
+#include "wave.h"
 #include <stdlib.h>
 
 // ---- the response of a tile, one pass, registers only ---------------------------------------------------------
@@ -103,14 +104,6 @@ __device__ __forceinline__ void harris_load_tile(const uint8_t* __restrict__ im,
             }
         }
     }
-}
-
-// lane i <- lane i - 1 / lane i + 1 of the whole wave (gfx9 DPP wave_shr:1 / wave_shl:1); the end lanes get 0
-__device__ __forceinline__ float wave_shr1(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x138, 0xf, 0xf, true));
-}
-__device__ __forceinline__ float wave_shl1(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x130, 0xf, 0xf, true));
 }
 
 // Wave `band` of the workgroup walks output rows [y0, y1) of the tile (relative to ty0); sink(y, lx - 1, R, valid) is
@@ -340,31 +333,9 @@ struct BinArgs {
 // One wave per (image, bin).  key = (|response| bits, ~push position): larger is
 // better and ties go to the earlier push.  Fast path: ONE pass over the bin in
 // which every lane keeps its three largest keys, then `per` rounds of wave-max
-// over the lanes' heads.  That is exact unless some lane's third-best key is
+// (wave_max_u64, wave.h) over the lanes' heads.  That is exact unless some lane's third-best key is
 // still above the last pick (a fourth could hide behind it); such bins (a few
 // percent) are redone by the exact multi-pass loop.
-// max over the wave of a u32, to every lane as a scalar: DPP row shifts inside the 16-lane rows, two row broadcasts, the
-// total lands in lane 63 (gfx9 reduction idiom; six v_max_u32_dpp + a readlane instead of six ds_bpermute round trips)
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
-#define HMAX_DPP(ctrl, rmask) v = max(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, ctrl, rmask, 0xf, false))
-    HMAX_DPP(0x111, 0xf);   // row_shr:1
-    HMAX_DPP(0x112, 0xf);   // row_shr:2
-    HMAX_DPP(0x114, 0xf);   // row_shr:4
-    HMAX_DPP(0x118, 0xf);   // row_shr:8   -> lane 15 of every row = the row's max
-    HMAX_DPP(0x142, 0xa);   // row_bcast:15 into rows 1 and 3
-    HMAX_DPP(0x143, 0xc);   // row_bcast:31 into rows 2 and 3 -> lane 63 = the wave's max
-#undef HMAX_DPP
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
-}
-// max over the wave of a u64 key (|response| bits : ~position): the high words first, then the low words of the lanes
-// that hold the maximal high word (ties of |response| are rare, the second reduction is still cheap)
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
-    const uint32_t hi = (uint32_t)(v >> 32), lo = (uint32_t)v;
-    const uint32_t mh = wave_max_u32(hi);
-    const uint32_t ml = wave_max_u32(hi == mh ? lo : 0u);
-    return ((unsigned long long)mh << 32) | ml;
-}
-
 #define HD_MAXPER 32  // corners per bin the fused detector keeps (the reference has 10)
 #define HB_LIST 256   // keys >= the last optimistic pick collected by the one-walk exact path (per wave)
 

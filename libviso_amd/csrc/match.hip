@@ -28,12 +28,6 @@
 
 #include <math.h>
 
-// ------------------------------------------------------------------ helpers
-template <int CTRL>
-__device__ __forceinline__ uint32_t dpp_mov(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, false);
-}
-
 // ------------------------------------------------------------------ column index
 // One workgroup per image: the keypoints grouped by a 256-bucket column map of their x (counting sort: histogram,
 // scan, scatter with LDS atomics), NOT fully sorted — nothing downstream needs more: a tile is any 64 consecutive
@@ -143,7 +137,7 @@ __global__ __launch_bounds__(VISO_IMG_THREADS) void sort_kp_kernel(const ImageVi
     SK_CLK(2);
     const float x0 = s_x[0], scale = s_x[1];
     // ---- counting sort by column bucket
-    walk([&](int, float2 k) { atomicAdd(&s_cnt[bucket_of(k.x, x0, scale)], 1); });
+    walk([&](int, float2 k) { atomicAdd(&s_cnt[bucket_of<VISO_NB>(k.x, x0, scale)], 1); });
     __syncthreads();
     if (wv == 0) {   // exclusive scan of the 256 counts: 4 per lane + wave scan
         int c[4], tot = 0;
@@ -159,7 +153,7 @@ __global__ __launch_bounds__(VISO_IMG_THREADS) void sort_kp_kernel(const ImageVi
     SK_CLK(3);
     const int n64 = (n + 63) & ~63;
     walk([&](int i, float2 k) {
-        const int p = atomicAdd(&s_cnt[bucket_of(k.x, x0, scale)], 1);   // running offset of the bucket
+        const int p = atomicAdd(&s_cnt[bucket_of<VISO_NB>(k.x, x0, scale)], 1);   // running offset of the bucket
         I.skp[p] = k;
         I.sidx[p] = i;
         I.rank[i] = p;
@@ -452,15 +446,6 @@ struct TrackT {
 #define VISO_NQ (16 / VISO_LPC)                  // 16-B chunks per lane
 #define VISO_NPASS (VISO_LPC == 8 ? 2 : 1)       // passes whose loads are in flight together (16 candidates)
 
-__device__ __forceinline__ uint32_t lpc_sum(uint32_t v) {
-    v += dpp_mov<0xB1>(v);   // quad_perm [1,0,3,2]
-    v += dpp_mov<0x4E>(v);   // quad_perm [2,3,0,1]
-#if VISO_LPC == 8
-    v += dpp_mov<0x141>(v);  // row_half_mirror (quads are uniform by now)
-#endif
-    return v;
-}
-
 struct ScorerU16 {
     const uint16_t* d2;
     const int* sidx2;
@@ -487,7 +472,7 @@ struct ScorerU16 {
             s = __builtin_amdgcn_sad_u16(r[k].z, q[k].z, s);
             s = __builtin_amdgcn_sad_u16(r[k].w, q[k].w, s);
         }
-        return lpc_sum(s);
+        return group_sum<VISO_LPC>(s);
     }
     __device__ __forceinline__ void score_fast(const uint2* queue, int n, TrackT& t) const {
         for (int b = 0; b < n; b += VISO_CPP * VISO_NPASS) {
@@ -861,8 +846,8 @@ __device__ __forceinline__ void match_tile_slot(const MatchArgs& a, int vb, uint
         const float slack = (fabsf(xa) + fabsf(xb) + fabsf(r)) * 1e-6f + 1e-6f;
         const float x0 = P.t.xinfo[0], scale = P.t.xinfo[1];
         if (r >= 0.f) {
-            const int blo = bucket_of(xa - r - slack, x0, scale);
-            const int bhi = bucket_of(xb + r + slack, x0, scale);
+            const int blo = bucket_of<VISO_NB>(xa - r - slack, x0, scale);
+            const int bhi = bucket_of<VISO_NB>(xb + r + slack, x0, scale);
             win.lo = P.t.bstart[blo];
             win.W = P.t.bstart[bhi + 1] - win.lo;
         }
@@ -951,8 +936,8 @@ __global__ __launch_bounds__(VISO_WAVE) void match_overflow_kernel(MatchArgs a) 
                 if (qx == qx) {
                     const float slack = (2.f * fabsf(qx) + fabsf(r)) * 1e-6f + 1e-6f;
                     const float x0 = P.t.xinfo[0], scale = P.t.xinfo[1];
-                    win.lo = P.t.bstart[bucket_of(qx - r - slack, x0, scale)];
-                    win.W = P.t.bstart[bucket_of(qx + r + slack, x0, scale) + 1] - win.lo;
+                    win.lo = P.t.bstart[bucket_of<VISO_NB>(qx - r - slack, x0, scale)];
+                    win.W = P.t.bstart[bucket_of<VISO_NB>(qx + r + slack, x0, scale) + 1] - win.lo;
                 }   // NaN x: no target is in radius
             }
         }

@@ -27,31 +27,6 @@
 #define MB_KPCAP 512       // window keypoints staged in LDS
 
 
-__device__ __forceinline__ uint32_t mb_wave_min(uint32_t v) {
-    const int ident = -1;
-    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(ident, (int)v, 0xB1, 0xf, 0xf, false));   // quad_perm 1,0,3,2
-    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(ident, (int)v, 0x4E, 0xf, 0xf, false));   // quad_perm 2,3,0,1
-    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(ident, (int)v, 0x141, 0xf, 0xf, false));  // row_half_mirror
-    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(ident, (int)v, 0x140, 0xf, 0xf, false));  // row_mirror
-    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(ident, (int)v, 0x142, 0xa, 0xf, false));  // row_bcast:15
-    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(ident, (int)v, 0x143, 0xc, 0xf, false));  // row_bcast:31
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
-}
-
-// bits of |qx - tx| + |qy - ty| (cvflann::L1 order, see l1_kp): the absolute values ride on the add as source
-// modifiers — left to the compiler the two differences are packed and the abs becomes two v_and
-__device__ __forceinline__ uint32_t mb_l1_bits(float qx, float qy, float2 t) {
-    const float dx = qx - t.x, dy = qy - t.y;
-    float d;
-    asm("v_add_f32_e64 %0, |%1|, |%2|" : "=v"(d) : "v"(dx), "v"(dy));
-    return __float_as_uint(d);
-}
-
-template <int CTRL>
-__device__ __forceinline__ uint32_t mb_dpp(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, false);
-}
-
 template <int EPI>
 __global__ __attribute__((amdgpu_waves_per_eu(5, 8))) __launch_bounds__(MB_THREADS) void match_batch_kernel(BatchMatchArgs a) {
     __shared__ __attribute__((aligned(16))) uint32_t s_pairs[MB_WAVES][MB_G * MB_SEG + MB_PAD];   // + the passes the pipeline may run ahead
@@ -114,8 +89,8 @@ __global__ __attribute__((amdgpu_waves_per_eu(5, 8))) __launch_bounds__(MB_THREA
         if (n2 > 0 && xa == xa && r >= 0.f) {
             const float slack = (fabsf(xa) + fabsf(xb) + fabsf(r)) * 1e-6f + 1e-6f;
             const float x0 = P.t.xinfo[0], scale = P.t.xinfo[1];
-            lo = P.t.bstart[bucket_of(xa - r - slack, x0, scale)];
-            W = P.t.bstart[bucket_of(xb + r + slack, x0, scale) + 1] - lo;
+            lo = P.t.bstart[bucket_of<VISO_NB>(xa - r - slack, x0, scale)];
+            W = P.t.bstart[bucket_of<VISO_NB>(xb + r + slack, x0, scale) + 1] - lo;
         }
     }
     lo = __builtin_amdgcn_readfirstlane(lo);   // wave uniform by construction; tell the compiler
@@ -170,8 +145,8 @@ __global__ __attribute__((amdgpu_waves_per_eu(5, 8))) __launch_bounds__(MB_THREA
         uint32_t thr[MB_G];
 #pragma unroll
         for (int k = 0; k < MB_G; ++k) {
-            qk[k].x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pq.x), k));
-            qk[k].y = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pq.y), k));
+            qk[k].x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pq.x), k));   // not readlane_f32: as a call, the code of
+            qk[k].y = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pq.y), k));   // match_batch_kernel<0> (debug builds) shifts
             orig[k] = __builtin_amdgcn_readlane(po, k);
             s_qrow[wave][k][lane] = prow[k];
             cnt[k] = 0;
@@ -192,8 +167,8 @@ __global__ __attribute__((amdgpu_waves_per_eu(5, 8))) __launch_bounds__(MB_THREA
             const uint32_t ea = (uint32_t)(base + lane), eb = ea + VISO_WAVE;
 #pragma unroll
             for (int k = 0; k < MB_G; ++k) {
-                bool ina = mb_l1_bits(qk[k].x, qk[k].y, ta) < thr[k];
-                bool inb = mb_l1_bits(qk[k].x, qk[k].y, tb) < thr[k];
+                bool ina = l1_bits(qk[k].x, qk[k].y, ta) < thr[k];
+                bool inb = l1_bits(qk[k].x, qk[k].y, tb) < thr[k];
                 if (EPI) {
                     cnt[k] += __popcll(__ballot(ina)) + __popcll(__ballot(inb));
                     ina = ina && fabsf(qk[k].y - ta.y) <= band;
@@ -336,12 +311,12 @@ __global__ __attribute__((amdgpu_waves_per_eu(5, 8))) __launch_bounds__(MB_THREA
                 sb_ = __builtin_amdgcn_sad_u16(r1[SB].z, b1_.z, sb_);                                      \
                 sa_ = __builtin_amdgcn_sad_u16(r1[SA].w, a1_.w, sa_);                                      \
                 sb_ = __builtin_amdgcn_sad_u16(r1[SB].w, b1_.w, sb_);                                      \
-                sa_ += mb_dpp<0xB1>(sa_);                                                                  \
-                sb_ += mb_dpp<0xB1>(sb_);                                                                  \
-                sa_ += mb_dpp<0x4E>(sa_);                                                                  \
-                sb_ += mb_dpp<0x4E>(sb_);                                                                  \
-                sa_ += mb_dpp<0x141>(sa_);                                                                 \
-                sb_ += mb_dpp<0x141>(sb_);                                                                 \
+                sa_ += wave_dpp<0xB1>(sa_);                                                                \
+                sb_ += wave_dpp<0xB1>(sb_);                                                                \
+                sa_ += wave_dpp<0x4E>(sa_);                                                                \
+                sb_ += wave_dpp<0x4E>(sb_);                                                                \
+                sa_ += wave_dpp<0x141>(sa_);                                                               \
+                sb_ += wave_dpp<0x141>(sb_);                                                               \
                 if (sub == 0) { sads[dst[SA]] = sa_; sads[dst[SB]] = sb_; }   /* slots past ntot are scratch */ \
             } while (0)
             int t = 0;
@@ -371,20 +346,12 @@ __global__ __attribute__((amdgpu_waves_per_eu(5, 8))) __launch_bounds__(MB_THREA
             const int my_orig = row == 0 ? orig[0] : row == 1 ? orig[1] : row == 2 ? orig[2] : orig[3];
             const bool valid = i16 < n;
             const uint32_t sv = valid ? sads[st + i16] : 0xffffffffu;
-            auto row_min = [](uint32_t v) {
-                const int ident = -1;
-                v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(ident, (int)v, 0xB1, 0xf, 0xf, false));    // quad_perm 1,0,3,2
-                v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(ident, (int)v, 0x4E, 0xf, 0xf, false));    // quad_perm 2,3,0,1
-                v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(ident, (int)v, 0x141, 0xf, 0xf, false));   // row_half_mirror
-                v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(ident, (int)v, 0x140, 0xf, 0xf, false));   // row_mirror
-                return v;
-            };
-            const uint32_t m1 = row_min(sv);
+            const uint32_t m1 = row_min_u32(sv);
             const bool eq = valid && sv == m1;
             const unsigned long long em = __ballot(eq);
             const uint32_t emr = (uint32_t)(em >> (16 * row)) & 0xffffu;
             const int c = __popc(emr);
-            const uint32_t m2 = row_min(eq ? 0xffffffffu : sv);
+            const uint32_t m2 = row_min_u32(eq ? 0xffffffffu : sv);
             const uint32_t r_d2 = c > 1 ? m1 : m2;
             if (i16 == 0 && my_orig >= 0) {
                 const int j = jg + row * MB_WAVES;
@@ -419,11 +386,11 @@ __global__ __attribute__((amdgpu_waves_per_eu(5, 8))) __launch_bounds__(MB_THREA
                 for (int b = 0; b < n; b += VISO_WAVE) {
                     const bool valid = (b + lane) < n;
                     const uint32_t s = valid ? sads[st + b + lane] : 0xffffffffu;
-                    const uint32_t m1 = mb_wave_min(s);
+                    const uint32_t m1 = wave_min_u32(s);
                     const bool eq = valid && s == m1;
                     const unsigned long long em = __ballot(eq);
                     const int c = __popcll(em);
-                    const uint32_t m2 = mb_wave_min(eq ? 0xffffffffu : s);
+                    const uint32_t m2 = wave_min_u32(eq ? 0xffffffffu : s);
                     const uint32_t wfirst = (pairs[st + b + (__ffsll((long long)em) - 1)] & 0x3fffffffu) >> 8;
                     const uint32_t o2 = c > 1 ? m1 : m2;
                     if (m1 < r_d1) { r_d2 = min(r_d1, o2); r_d1 = m1; r_w = wfirst; r_tie = c > 1; }

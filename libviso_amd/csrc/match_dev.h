@@ -1,8 +1,10 @@
-// match_dev.h — device helpers shared by the matcher kernels (match.hip,
-// match_tile.hip).  Arithmetic here is parity critical: same operation order
-// and float roundings as the reference (cited per function).
+// match_dev.h — device helpers shared by the matcher kernels (match.hip, the match_*.hip tile kernels) and the pack
+// kernels (extract.hip): what is about matching -- distances, buckets, the epipolar band, the rows' planes, the LDS sort.
+// The lane moves and reductions they are written with are wave.h's.  Arithmetic here is parity critical: same operation
+// order and float roundings as the reference (cited per function).
 #pragma once
 #include "common.h"
+#include "wave.h"
 
 #include <math.h>
 
@@ -13,10 +15,10 @@ __device__ __forceinline__ int mbcnt(unsigned long long m) {
 // v = this lane's share (elements 2l, 2l+1) of a row: the four 32-element block sums (16 lanes each), clamped to int16,
 // biased, packed as 4 x u16.  Valid in every lane.
 __device__ __forceinline__ uint2 pack_block_sums(int v) {
-    v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xf, 0xf, false);    // lane ^ 1
-    v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xf, 0xf, false);    // lane ^ 2
-    v += __builtin_amdgcn_update_dpp(0, v, 0x141, 0xf, 0xf, false);   // 7 - lane within 8
-    v += __builtin_amdgcn_update_dpp(0, v, 0x140, 0xf, 0xf, false);   // 15 - lane within 16
+    v += (int)wave_dpp<0xB1>((uint32_t)v);    // lane ^ 1
+    v += (int)wave_dpp<0x4E>((uint32_t)v);    // lane ^ 2
+    v += (int)wave_dpp<0x141>((uint32_t)v);   // 7 - lane within 8
+    v += (int)wave_dpp<0x140>((uint32_t)v);   // 15 - lane within 16
     v = min(max(v, -32768), 32767) + VISO_BIAS;
     const uint32_t s0 = (uint32_t)__builtin_amdgcn_readlane(v, 0), s1 = (uint32_t)__builtin_amdgcn_readlane(v, 16);
     const uint32_t s2 = (uint32_t)__builtin_amdgcn_readlane(v, 32), s3 = (uint32_t)__builtin_amdgcn_readlane(v, 48);
@@ -37,7 +39,7 @@ __device__ __forceinline__ uint32_t row8_of(int v, int s) {
 // lane l holds elements 2l, 2l+1 of row `row` (pad elements as 0): the even lanes write the plane's dwords
 __device__ __forceinline__ void store_row8(uint8_t* rows8, size_t row, int lane, int va, int vb, int s) {
     const uint32_t h2 = row8_of(va, s) | (row8_of(vb, s) << 8);
-    const uint32_t nb = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)h2, 0x101, 0xf, 0xf, true);   // row_shl:1: lane + 1's pair
+    const uint32_t nb = wave_dpp_bc<0x101>(h2);   // row_shl:1: lane + 1's pair
     if ((lane & 1) == 0)
         ((__attribute__((address_space(1))) uint32_t*)reinterpret_cast<uint32_t*>(rows8 + row * VISO_ROW8))[lane >> 1] = h2 | (nb << 16);
 }
@@ -74,6 +76,11 @@ __device__ __forceinline__ float l1_kp(float qx, float qy, float2 t) {
     float r = fabsf(qx - t.x);
     r += fabsf(qy - t.y);
     return r;
+}
+// its bit pattern, in the same order: what the tile kernels compare with their thresholds (non-negative floats order as their
+// bits).  The absolute values are source modifiers of the add (abs_add_abs, wave.h)
+__device__ __forceinline__ uint32_t l1_bits(float qx, float qy, float2 t) {
+    return __float_as_uint(abs_add_abs(qx - t.x, qy - t.y));
 }
 
 // sampsonDistance + algebricDistance, src/viso.cpp:655-666, 390-407 — same
@@ -150,14 +157,40 @@ __device__ __forceinline__ bool key_less(uint32_t ad, uint32_t ai, uint32_t bd, 
     return ad < bd || (ad == bd && ai < bi);
 }
 
-// Column bucket of x.  NaN x shares the last bucket with the largest columns; a NaN product (x0 = +-inf with scale 0)
-// goes to bucket 0 explicitly — never (int)NaN.
+// Bucket of x among NB (the image's VISO_NB column buckets; the y buckets of a tile's staged window): monotone in x.  NaN x
+// shares the last bucket with the largest values; a NaN product (x0 = +-inf with scale 0) goes to bucket 0 explicitly — never
+// (int)NaN.  The general form; bucket_cvt is the cheaper one of the VALU-bound union kernels.
+template <int NB>
 __device__ __forceinline__ int bucket_of(float x, float x0, float scale) {
-    if (x != x) return VISO_NB - 1;
+    if (x != x) return NB - 1;
     const float f = floorf((x - x0) * scale);
     if (f != f) return 0;
-    return f <= 0.f ? 0 : (f >= (float)(VISO_NB - 1) ? VISO_NB - 1 : (int)f);
+    return f <= 0.f ? 0 : (f >= (float)(NB - 1) ? NB - 1 : (int)f);
 }
+// bucket_of without the guard of the product, as the LDS-resident experiment (tools/experiments/match_strip.hip, debug builds)
+// has always had it: sound for a finite or NaN x only -- an infinite x with scale 0 gives a NaN product and (int)NaN.  Kept
+// apart because the guard changes that kernel's code; nothing else may use it.
+template <int NB>
+__device__ __forceinline__ int bucket_of_finite(float x, float x0, float scale) {
+    if (x != x) return NB - 1;
+    const float f = floorf((x - x0) * scale);
+    return f <= 0.f ? 0 : (f >= (float)(NB - 1) ? NB - 1 : (int)f);
+}
+// The same map as one conversion and a clamp (a compare, a select and a floor less than bucket_of, in kernels that are bound by
+// vector-ALU issue): monotone in x, total (NaN -> 0, +-inf
+// saturate): v_cvt_i32_f32 truncates, saturates and turns NaN into 0 (the C conversion would be undefined there), the clamp
+// makes truncation and floor the same thing.  Differs from bucket_of for a NaN x only (bucket 0, not the last).
+template <int NB>
+__device__ __forceinline__ int bucket_cvt(float x, float x0, float scale) {
+    const float f = (x - x0) * scale;
+    int b;
+    asm("v_cvt_i32_f32_e32 %0, %1" : "=v"(b) : "v"(f));
+    return min(max(b, 0), NB - 1);
+}
+
+// the lane that carries query k of a union kernel's round (lanes 0..31: queries 0..3, lanes 32..63: queries 4..7, repeated every
+// four lanes, so that a quad broadcast hands every lane the four queries its half tests in phase 1)
+__device__ __forceinline__ constexpr int qlane(int k) { return (k & 3) + 32 * (k >> 2); }
 
 // Ascending bitonic sort of `npad` (power of two, >= 64) 64-bit keys in LDS by a workgroup of THREADS threads.
 // Every wave owns a contiguous chunk of comparators (CW per stage), hence a contiguous chunk of 2*CW keys: the

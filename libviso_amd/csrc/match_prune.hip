@@ -54,38 +54,16 @@
 #define MP_KPCAP 512       // window keypoints staged in LDS
 #define MP_NBY 64          // y buckets of the staged window
 
-template <int CTRL>
-__device__ __forceinline__ uint32_t mp_dpp(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, false);
-}
-
-// bits of |qx - tx| + |qy - ty| (cvflann::L1 order, see l1_kp); abs as source modifiers of the add
-__device__ __forceinline__ uint32_t mp_l1_bits(float qx, float qy, float2 t) {
-    const float dx = qx - t.x, dy = qy - t.y;
-    float d;
-    asm("v_add_f32_e64 %0, |%1|, |%2|" : "=v"(d) : "v"(dx), "v"(dy));
-    return __float_as_uint(d);
-}
-
 // packed-key order statistics: see match_union.hip (MuTrack)
 struct MpTrack { uint32_t m1, m2; };
 __device__ __forceinline__ void mp_update(MpTrack& t, uint32_t key) {
-    uint32_t med;
-    asm("v_med3_u32 %0, %1, %2, %3" : "=v"(med) : "v"(t.m1), "v"(t.m2), "v"(key));
-    t.m2 = med;
+    t.m2 = med3_u32(t.m1, t.m2, key);
     t.m1 = min(t.m1, key);
 }
 __device__ __forceinline__ void mp_merge(MpTrack& a, const MpTrack& b) {
     const uint32_t hi = max(a.m1, b.m1);
     a.m2 = min(hi, min(a.m2, b.m2));
     a.m1 = min(a.m1, b.m1);
-}
-
-__device__ __forceinline__ int mp_ybucket(float y, float y0, float scale) {   // monotone in y
-    if (y != y) return MP_NBY - 1;
-    const float f = floorf((y - y0) * scale);
-    if (f != f) return 0;                       // inf * 0: never (int)NaN
-    return f <= 0.f ? 0 : (f >= (float)(MP_NBY - 1) ? MP_NBY - 1 : (int)f);
 }
 
 // A VALID pruning threshold: every bound b >= the returned value satisfies b > dstar and, when the ratio test is on,
@@ -150,8 +128,8 @@ __global__ __attribute__((amdgpu_waves_per_eu(MP_WPE, 8))) __launch_bounds__(MP_
         if (n2 > 0 && xa == xa && r >= 0.f) {
             const float slack = (fabsf(xa) + fabsf(xb) + fabsf(r)) * 1e-6f + 1e-6f;
             const float x0 = P.t.xinfo[0], scale = P.t.xinfo[1];
-            lo = P.t.bstart[bucket_of(xa - r - slack, x0, scale)];
-            W = P.t.bstart[bucket_of(xb + r + slack, x0, scale) + 1] - lo;
+            lo = P.t.bstart[bucket_of<VISO_NB>(xa - r - slack, x0, scale)];
+            W = P.t.bstart[bucket_of<VISO_NB>(xb + r + slack, x0, scale) + 1] - lo;
         }
     }
     lo = __builtin_amdgcn_readfirstlane(lo);
@@ -177,7 +155,7 @@ __global__ __attribute__((amdgpu_waves_per_eu(MP_WPE, 8))) __launch_bounds__(MP_
         if (w < wcap) {
             e_kp[i] = P.t.skp[lo + w];
             s_sum[w] = P.t.sums[lo + w];
-            e_b[i] = mp_ybucket(e_kp[i].y, ty0, yscale);
+            e_b[i] = bucket_of<MP_NBY>(e_kp[i].y, ty0, yscale);
             e_r[i] = atomicAdd(&s_ys[e_b[i]], 1);
         }
     }
@@ -267,10 +245,10 @@ __global__ __attribute__((amdgpu_waves_per_eu(MP_WPE, 8))) __launch_bounds__(MP_
         float ymn = pq.y, ymx = pq.y;   // y extent of the round's queries (all lanes hold one of them)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const float xa_ = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pq.x), i));
-            const float xb_ = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pq.x), 4 + i));
-            const float ya_ = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pq.y), i));
-            const float yb_ = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pq.y), 4 + i));
+            const float xa_ = readlane_f32(pq.x, i);
+            const float xb_ = readlane_f32(pq.x, 4 + i);
+            const float ya_ = readlane_f32(pq.y, i);
+            const float yb_ = readlane_f32(pq.y, 4 + i);
             const uint32_t ta_ = (uint32_t)__builtin_amdgcn_readlane((int)tq, i);
             const uint32_t tb_ = (uint32_t)__builtin_amdgcn_readlane((int)tq, 4 + i);
             qx[i] = half ? xb_ : xa_;
@@ -299,8 +277,8 @@ __global__ __attribute__((amdgpu_waves_per_eu(MP_WPE, 8))) __launch_bounds__(MP_
         int ucnt = 0;
         {
             const float ys = (fabsf(ymn) + fabsf(ymx) + fabsf(radius)) * 1e-6f + 1e-6f;   // covers the rounding of dy in the test
-            int sc0 = s_ys[mp_ybucket(ymn - radius - ys, ty0, yscale)] & ~63;   // steps of 64 stay inside the NaN padded array
-            int sc1 = s_ys[mp_ybucket(ymx + radius + ys, ty0, yscale) + 1];
+            int sc0 = s_ys[bucket_of<MP_NBY>(ymn - radius - ys, ty0, yscale)] & ~63;   // steps of 64 stay inside the NaN padded array
+            int sc1 = s_ys[bucket_of<MP_NBY>(ymx + radius + ys, ty0, yscale) + 1];
             sc0 = __builtin_amdgcn_readfirstlane(sc0);
             sc1 = __builtin_amdgcn_readfirstlane(sc1);
             const int l31 = lane & 31;
@@ -311,8 +289,8 @@ __global__ __attribute__((amdgpu_waves_per_eu(MP_WPE, 8))) __launch_bounds__(MP_
                 uint32_t ma = 0, mb = 0;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    const bool ina = mp_l1_bits(qx[i], qy[i], ta) < thr[i];
-                    const bool inb = mp_l1_bits(qx[i], qy[i], tb) < thr[i];
+                    const bool ina = l1_bits(qx[i], qy[i], ta) < thr[i];
+                    const bool inb = l1_bits(qx[i], qy[i], tb) < thr[i];
                     ma = ma + ma + (ina ? 1u : 0u);
                     mb = mb + mb + (inb ? 1u : 0u);
                 }
@@ -331,7 +309,7 @@ __global__ __attribute__((amdgpu_waves_per_eu(MP_WPE, 8))) __launch_bounds__(MP_
                 if (w < W) t2 = P.t.skp[lo + w];
                 uint32_t m = 0;
 #pragma unroll
-                for (int i = 0; i < 4; ++i) m = m + m + ((mp_l1_bits(qx[i], qy[i], t2) < thr[i]) ? 1u : 0u);
+                for (int i = 0; i < 4; ++i) m = m + m + ((l1_bits(qx[i], qy[i], t2) < thr[i]) ? 1u : 0u);
                 const uint32_t o = (uint32_t)__shfl_xor((int)m, 32);
                 const uint32_t m8 = half ? 0u : ((m << 4) | o);
                 const uint32_t u = (uint32_t)__ballot(m8 != 0);
@@ -372,9 +350,9 @@ __global__ __attribute__((amdgpu_waves_per_eu(MP_WPE, 8))) __launch_bounds__(MP_
         uint32_t pkey;
         {
             const bool sel0 = ((lane ^ (lane >> 2)) & 1) != 0, sel1 = (((lane >> 1) ^ (lane >> 2)) & 1) != 0, sel2 = ((lane >> 2) & 1) != 0;
-#define MP_M1(A, B) ({ const uint32_t k_ = sel0 ? (B) : (A); const uint32_t g_ = sel0 ? (A) : (B); min(k_, mp_dpp<0xB1>(g_)); })    /* lane ^ 1 */
-#define MP_M2(A, B) ({ const uint32_t k_ = sel1 ? (B) : (A); const uint32_t g_ = sel1 ? (A) : (B); min(k_, mp_dpp<0x4E>(g_)); })    /* lane ^ 2 */
-#define MP_M4(A, B) ({ const uint32_t k_ = sel2 ? (B) : (A); const uint32_t g_ = sel2 ? (A) : (B); min(k_, mp_dpp<0x141>(g_)); })   /* 7 - lane */
+#define MP_M1(A, B) ({ const uint32_t k_ = sel0 ? (B) : (A); const uint32_t g_ = sel0 ? (A) : (B); min(k_, wave_dpp<0xB1>(g_)); })    /* lane ^ 1 */
+#define MP_M2(A, B) ({ const uint32_t k_ = sel1 ? (B) : (A); const uint32_t g_ = sel1 ? (A) : (B); min(k_, wave_dpp<0x4E>(g_)); })    /* lane ^ 2 */
+#define MP_M4(A, B) ({ const uint32_t k_ = sel2 ? (B) : (A); const uint32_t g_ = sel2 ? (A) : (B); min(k_, wave_dpp<0x141>(g_)); })   /* 7 - lane */
             const uint32_t a0 = MP_M1(pmin[0], pmin[1]), a1 = MP_M1(pmin[2], pmin[3]), a2 = MP_M1(pmin[4], pmin[5]), a3 = MP_M1(pmin[6], pmin[7]);
             const uint32_t c0 = MP_M2(a0, a1), c1 = MP_M2(a2, a3);
             uint32_t m = MP_M4(c0, c1);
@@ -404,9 +382,9 @@ __global__ __attribute__((amdgpu_waves_per_eu(MP_WPE, 8))) __launch_bounds__(MP_
             s_ = __builtin_amdgcn_sad_u16((R1).y, qb_.y, s_);                                              \
             s_ = __builtin_amdgcn_sad_u16((R1).z, qb_.z, s_);                                              \
             s_ = __builtin_amdgcn_sad_u16((R1).w, qb_.w, s_);                                              \
-            s_ += mp_dpp<0xB1>(s_);    /* lane ^ 1 */                                                      \
-            s_ += mp_dpp<0x4E>(s_);    /* lane ^ 2 */                                                      \
-            s_ += mp_dpp<0x141>(s_);   /* 7 - lane: every lane of the group of 8 holds the row's SAD */    \
+            s_ += wave_dpp<0xB1>(s_);    /* lane ^ 1 */                                                    \
+            s_ += wave_dpp<0x4E>(s_);    /* lane ^ 2 */                                                    \
+            s_ += wave_dpp<0x141>(s_);   /* 7 - lane: every lane of the group of 8 holds the row's SAD */  \
             s_;                                                                                            \
         })
         const uint32_t plpos = pkey & 511u;               // group k: query k's probe (pkey = bound << 9 | list position)

@@ -45,22 +45,6 @@ struct StWaveLds {
 };
 static_assert(ST_WCAP <= 512, "window positions share a word with the SAD");
 
-template <int CTRL>
-__device__ __forceinline__ uint32_t st_dpp(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, false);
-}
-
-// (wave-wide scans and extrema: viso_wave_scan / viso_wave_fext, common.h -- DPP operands, not ds_bpermute round trips: a tile is a
-// latency chain and the kernel is latency bound)
-__device__ __forceinline__ int st_scan_incl(int v, int) { return (int)viso_wave_scan((uint32_t)v); }
-
-__device__ __forceinline__ int st_bucket(float y, float y0, float scale) {
-    if (y != y) return ST_NBY - 1;
-    const float f = floorf((y - y0) * scale);
-    if (f != f) return 0;                       // inf * 0: never (int)NaN
-    return f <= 0.f ? 0 : (f >= (float)(ST_NBY - 1) ? ST_NBY - 1 : (int)f);
-}
-
 #ifndef ST_CLK
 #define ST_CLK(I) do {} while (0)   // (match_frame.hip, debug builds: time stamps of the first tile's phases)
 #endif
@@ -123,8 +107,8 @@ ST_KERNEL_SIG {
     int lo = 0, W = 0;
     if (n2 > 0 && xa == xa && radius >= 0.f) {
         const float slack = (fabsf(xa) + fabsf(xb) + fabsf(radius)) * 1e-6f + 1e-6f;
-        lo = P.t.bstart[bucket_of(xa - radius - slack, tx0, tscale)];
-        W = P.t.bstart[bucket_of(xb + radius + slack, tx0, tscale) + 1] - lo;
+        lo = P.t.bstart[bucket_of<VISO_NB>(xa - radius - slack, tx0, tscale)];
+        W = P.t.bstart[bucket_of<VISO_NB>(xb + radius + slack, tx0, tscale) + 1] - lo;
     }
     lo = __builtin_amdgcn_readfirstlane(lo);
     W = __builtin_amdgcn_readfirstlane(W);
@@ -168,14 +152,14 @@ ST_KERNEL_SIG {
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
         for (int i = 0; i < ST_WCAP / 64; ++i) {
-            e_b[i] = st_bucket(e_kp[i].y, y0, yscale);
+            e_b[i] = bucket_of<ST_NBY>(e_kp[i].y, y0, yscale);
             e_r[i] = 0;
             if (lane + 64 * i < cw) e_r[i] = atomicAdd(&L.hist[e_b[i]], 1);   // returning LDS atomic: rank inside the bucket
         }
         __builtin_amdgcn_wave_barrier();
         {
             const int h = L.hist[lane];
-            const int incl = st_scan_incl(h, lane);
+            const int incl = (int)viso_wave_scan((uint32_t)h);
             __builtin_amdgcn_wave_barrier();
             L.hist[lane] = incl - h;           // bucket start
             if (lane == 63) L.hist[ST_NBY] = incl;
@@ -196,10 +180,10 @@ ST_KERNEL_SIG {
         // ST_SLOTS of them (`skip`): sparse data makes one pass
         // the bucket map is monotone in y; `ys` covers the rounding of the float differences the tests below take
         const float ys = (fabsf(qv.y) + fabsf(radius)) * 1e-6f + 1e-6f;
-        const int s0 = L.hist[st_bucket(qv.y - band - ys, y0, yscale)];
-        const int s1 = L.hist[st_bucket(qv.y + band + ys, y0, yscale) + 1];
+        const int s0 = L.hist[bucket_of<ST_NBY>(qv.y - band - ys, y0, yscale)];
+        const int s1 = L.hist[bucket_of<ST_NBY>(qv.y + band + ys, y0, yscale) + 1];
         // upper bound of the in-radius count (K cap): entries with |dy| <= radius
-        cnt_ub += L.hist[st_bucket(qv.y + radius + ys, y0, yscale) + 1] - L.hist[st_bucket(qv.y - radius - ys, y0, yscale)];
+        cnt_ub += L.hist[bucket_of<ST_NBY>(qv.y + radius + ys, y0, yscale) + 1] - L.hist[bucket_of<ST_NBY>(qv.y - radius - ys, y0, yscale)];
         for (int skip = 0;; skip += ST_SLOTS) {
         int n = 0, seen = 0;
         for (int i = s0; __any(i < s1); ++i) {
@@ -227,7 +211,7 @@ ST_KERNEL_SIG {
         }
         ST_CLK(4);
         // ---- flat pair list of the tile
-        const int incl = st_scan_incl(n2g, lane);
+        const int incl = (int)viso_wave_scan((uint32_t)n2g);
         const int base = incl - n2g;
         const int ntot = __builtin_amdgcn_readlane(incl, 63);
         for (int s = 0; s < n2g; ++s) L.flat[base + s] = ((uint32_t)lane << 16) | (uint32_t)L.ypos[L.slot[s][lane]];
@@ -262,9 +246,9 @@ ST_KERNEL_SIG {
                 s_ = __builtin_amdgcn_sad_u16(t1[SLOT].y, u1[SLOT].y, s_);                                 \
                 s_ = __builtin_amdgcn_sad_u16(t1[SLOT].z, u1[SLOT].z, s_);                                 \
                 s_ = __builtin_amdgcn_sad_u16(t1[SLOT].w, u1[SLOT].w, s_);                                 \
-                s_ += st_dpp<0xB1>(s_);                                                                    \
-                s_ += st_dpp<0x4E>(s_);                                                                    \
-                s_ += st_dpp<0x141>(s_);                                                                   \
+                s_ += wave_dpp<0xB1>(s_);                                                                  \
+                s_ += wave_dpp<0x4E>(s_);                                                                  \
+                s_ += wave_dpp<0x141>(s_);                                                                 \
                 if (sub == 0) L.flat[dst[SLOT]] = (s_ << 9) | wpos[SLOT];   /* slots past ntot are scratch */ \
             } while (0)
             if (npass > 0) {
@@ -314,8 +298,8 @@ ST_KERNEL_SIG {
         while (need) {
             const int ql = __ffsll((long long)need) - 1;
             need &= need - 1;
-            const float qx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(qv.x), ql));
-            const float qy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(qv.y), ql));
+            const float qx = readlane_f32(qv.x, ql);
+            const float qy = readlane_f32(qv.y, ql);
             const uint32_t th = (uint32_t)__builtin_amdgcn_readlane((int)thr, ql);
             int c = 0;
             for (int base = 0; base < W; base += VISO_WAVE) {

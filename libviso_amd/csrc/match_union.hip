@@ -46,30 +46,6 @@
 #define MU_KPCAP 512       // window keypoints staged in LDS
 #define MU_NBY 64          // y buckets of the staged window
 
-template <int CTRL>
-__device__ __forceinline__ uint32_t mu_dpp(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, false);
-}
-
-// quad broadcast (every lane has a source: no old value to keep, bound_ctrl spares the compiler its initialisation)
-template <int CTRL>
-__device__ __forceinline__ uint32_t mu_bcast(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, true);
-}
-
-// fminf / fmaxf without the canonicalising v_max x, x the compiler puts in front (v_min / v_max return the other operand
-// for a NaN, like fminf / fmaxf)
-__device__ __forceinline__ float mu_fmin(float a, float b) { float r; asm("v_min_f32_e32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ float mu_fmax(float a, float b) { float r; asm("v_max_f32_e32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-
-// bits of |qx - tx| + |qy - ty| (cvflann::L1 order, see l1_kp); abs as source modifiers of the add
-__device__ __forceinline__ uint32_t mu_l1_bits(float qx, float qy, float2 t) {
-    const float dx = qx - t.x, dy = qy - t.y;
-    float d;
-    asm("v_add_f32_e64 %0, |%1|, |%2|" : "=v"(d) : "v"(dx), "v"(dy));
-    return __float_as_uint(d);
-}
-
 // Running order statistics of one query's SADs as two packed keys, key = SAD << 9 | position in the round's union
 // list (< 512; SAD < 2^23 for int16-valued descriptors: 121 * 65535): m1 = smallest key, m2 = second smallest
 // (0xffffffff = none).  A query sees every list position at most once, so keys are distinct and
@@ -77,9 +53,7 @@ __device__ __forceinline__ uint32_t mu_l1_bits(float qx, float qy, float2 t) {
 struct MuTrack { uint32_t m1, m2; };
 
 __device__ __forceinline__ void mu_update(MuTrack& t, uint32_t key) {
-    uint32_t med;   // m1 <= m2: the median of (m1, m2, key) is the new second smallest
-    asm("v_med3_u32 %0, %1, %2, %3" : "=v"(med) : "v"(t.m1), "v"(t.m2), "v"(key));
-    t.m2 = med;
+    t.m2 = med3_u32(t.m1, t.m2, key);   // m1 <= m2: the median of (m1, m2, key) is the new second smallest
     t.m1 = min(t.m1, key);
 }
 
@@ -88,19 +62,6 @@ __device__ __forceinline__ void mu_merge(MuTrack& a, const MuTrack& b) {
     a.m2 = min(hi, min(a.m2, b.m2));
     a.m1 = min(a.m1, b.m1);
 }
-
-// y bucket of the staged window: monotone in y, total (NaN -> 0, +-inf saturate): v_cvt_i32_f32 truncates, saturates and
-// turns NaN into 0 (the C conversion would be undefined there), the clamp makes truncation and floor the same thing
-__device__ __forceinline__ int mu_ybucket(float y, float y0, float scale) {
-    const float f = (y - y0) * scale;
-    int b;
-    asm("v_cvt_i32_f32_e32 %0, %1" : "=v"(b) : "v"(f));
-    return min(max(b, 0), MU_NBY - 1);
-}
-
-// the lane that carries query k of a round (lanes 0..31: queries 0..3, lanes 32..63: queries 4..7, repeated every four
-// lanes, so that a quad broadcast hands every lane the four queries its half tests in phase 1)
-__device__ __forceinline__ constexpr int mu_qlane(int k) { return (k & 3) + 32 * (k >> 2); }
 
 __global__ __attribute__((amdgpu_waves_per_eu(7, 8))) __launch_bounds__(MU_THREADS) void match_union_kernel(BatchMatchArgs a) {
     __shared__ __attribute__((aligned(16))) uint32_t s_ul[MU_WAVES][MU_UCAP + MU_PAD];
@@ -148,8 +109,8 @@ __global__ __attribute__((amdgpu_waves_per_eu(7, 8))) __launch_bounds__(MU_THREA
         if (n2 > 0 && xa == xa && r >= 0.f) {
             const float slack = (fabsf(xa) + fabsf(xb) + fabsf(r)) * 1e-6f + 1e-6f;
             const float x0 = P.t.xinfo[0], scale = P.t.xinfo[1];
-            lo = P.t.bstart[bucket_of(xa - r - slack, x0, scale)];
-            W = P.t.bstart[bucket_of(xb + r + slack, x0, scale) + 1] - lo;
+            lo = P.t.bstart[bucket_of<VISO_NB>(xa - r - slack, x0, scale)];
+            W = P.t.bstart[bucket_of<VISO_NB>(xb + r + slack, x0, scale) + 1] - lo;
         }
     }
     lo = __builtin_amdgcn_readfirstlane(lo);
@@ -174,7 +135,7 @@ __global__ __attribute__((amdgpu_waves_per_eu(7, 8))) __launch_bounds__(MU_THREA
         e_b[i] = 0; e_r[i] = 0;
         if (w < wcap) {
             e_kp[i] = P.t.skp[lo + w];
-            e_b[i] = mu_ybucket(e_kp[i].y, ty0, yscale);
+            e_b[i] = bucket_cvt<MU_NBY>(e_kp[i].y, ty0, yscale);
             e_r[i] = atomicAdd(&s_ys[e_b[i]], 1);
         }
     }
@@ -226,7 +187,7 @@ __global__ __attribute__((amdgpu_waves_per_eu(7, 8))) __launch_bounds__(MU_THREA
     const int msh = 31 - myq;   // membership bit of query myq in a list entry (bit 7 - k of the mask byte)
 
     // query data one round ahead: lane l carries local index / keypoint / original index of query (l & 3) + 4 * half
-    // of the round (mu_qlane)
+    // of the round (qlane)
     const int qslot = (lane & 3) + 4 * half;
     int pli;
     float2 pq;
@@ -245,7 +206,7 @@ __global__ __attribute__((amdgpu_waves_per_eu(7, 8))) __launch_bounds__(MU_THREA
     for (int r = 0; r < ROUNDS; ++r) {
         // ---------------- round setup.  Lane l holds query (l & 3) + 4 * half: the four queries its half tests in phase 1
         // are the four lanes of its quad (DPP quad broadcasts, no scalar traffic)
-        const int my_orig = po, my_j = q0 + pli;   // lanes mu_qlane(k): the round's queries, for phase 3
+        const int my_orig = po, my_j = q0 + pli;   // lanes qlane(k): the round's queries, for phase 3
         if (!__any(po >= 0)) { if (r + 1 < ROUNDS) MU_PREFETCH(r + 1); continue; }   // wave uniform
         // d = |dx| + |dy| is +0, positive or NaN (sign bit clear: the add sees |dx| and |dy|): its bit pattern orders like
         // the value and NaNs are above +inf, so (d <= radius && d < d0cut) is one unsigned compare against bits(d0)
@@ -261,18 +222,18 @@ __global__ __attribute__((amdgpu_waves_per_eu(7, 8))) __launch_bounds__(MU_THREA
         tq -= 1u;   // dead slots: 0xffffffff - bits(d) has its sign set
         float qx[4], qy[4];
         uint32_t thr[4];
-        qx[0] = __uint_as_float(mu_bcast<0x00>(__float_as_uint(pq.x))); qy[0] = __uint_as_float(mu_bcast<0x00>(__float_as_uint(pq.y))); thr[0] = mu_bcast<0x00>(tq);
-        qx[1] = __uint_as_float(mu_bcast<0x55>(__float_as_uint(pq.x))); qy[1] = __uint_as_float(mu_bcast<0x55>(__float_as_uint(pq.y))); thr[1] = mu_bcast<0x55>(tq);
-        qx[2] = __uint_as_float(mu_bcast<0xAA>(__float_as_uint(pq.x))); qy[2] = __uint_as_float(mu_bcast<0xAA>(__float_as_uint(pq.y))); thr[2] = mu_bcast<0xAA>(tq);
-        qx[3] = __uint_as_float(mu_bcast<0xFF>(__float_as_uint(pq.x))); qy[3] = __uint_as_float(mu_bcast<0xFF>(__float_as_uint(pq.y))); thr[3] = mu_bcast<0xFF>(tq);
+        qx[0] = __uint_as_float(wave_dpp_bc<0x00>(__float_as_uint(pq.x))); qy[0] = __uint_as_float(wave_dpp_bc<0x00>(__float_as_uint(pq.y))); thr[0] = wave_dpp_bc<0x00>(tq);
+        qx[1] = __uint_as_float(wave_dpp_bc<0x55>(__float_as_uint(pq.x))); qy[1] = __uint_as_float(wave_dpp_bc<0x55>(__float_as_uint(pq.y))); thr[1] = wave_dpp_bc<0x55>(tq);
+        qx[2] = __uint_as_float(wave_dpp_bc<0xAA>(__float_as_uint(pq.x))); qy[2] = __uint_as_float(wave_dpp_bc<0xAA>(__float_as_uint(pq.y))); thr[2] = wave_dpp_bc<0xAA>(tq);
+        qx[3] = __uint_as_float(wave_dpp_bc<0xFF>(__float_as_uint(pq.x))); qy[3] = __uint_as_float(wave_dpp_bc<0xFF>(__float_as_uint(pq.y))); thr[3] = wave_dpp_bc<0xFF>(tq);
         // y extent of the four queries of the lane's half (the two halves' scan ranges are joined as scalars below)
-        const float ymn = mu_fmin(mu_fmin(qy[0], qy[1]), mu_fmin(qy[2], qy[3]));
-        const float ymx = mu_fmax(mu_fmax(qy[0], qy[1]), mu_fmax(qy[2], qy[3]));
+        const float ymn = fmin_raw(fmin_raw(qy[0], qy[1]), fmin_raw(qy[2], qy[3]));
+        const float ymx = fmax_raw(fmax_raw(qy[0], qy[1]), fmax_raw(qy[2], qy[3]));
         // the eight query rows: one word per lane and row from global memory (the loads land during the scan), then LDS
         uint32_t qw[MU_G];
 #pragma unroll
         for (int k = 0; k < MU_G; ++k) {
-            const int jk = q0 + __builtin_amdgcn_readlane(pli, mu_qlane(k));
+            const int jk = q0 + __builtin_amdgcn_readlane(pli, qlane(k));
             qw[k] = ((const __attribute__((address_space(1))) uint32_t*)reinterpret_cast<const uint32_t*>(P.q.rows))[(size_t)min(jk, q1 - 1) * (VISO_ROW / 2) + lane];
         }
         if (r + 1 < ROUNDS) MU_PREFETCH(r + 1);
@@ -288,7 +249,7 @@ __global__ __attribute__((amdgpu_waves_per_eu(7, 8))) __launch_bounds__(MU_THREA
         ({                                                                                                \
             uint32_t m_ = 0;                                                                              \
             _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                 \
-                m_ = __builtin_amdgcn_alignbit(m_, thr[i] - mu_l1_bits(qx[i], qy[i], (T)), 31);           \
+                m_ = __builtin_amdgcn_alignbit(m_, thr[i] - l1_bits(qx[i], qy[i], (T)), 31);              \
             /* swap(A, B): A's lanes 32..63 <-> B's lanes 0..31; with A = B = m_: r_[0] = the low half's nibble everywhere, */ \
             /* r_[1] = the high half's */                                                                 \
             const auto r_ = __builtin_amdgcn_permlane32_swap(m_, m_, false, false);                       \
@@ -296,8 +257,8 @@ __global__ __attribute__((amdgpu_waves_per_eu(7, 8))) __launch_bounds__(MU_THREA
         })
         {
             const float ys = (fabsf(ymn) + fabsf(ymx) + fabsf(radius)) * 1e-6f + 1e-6f;   // covers the rounding of dy in the test
-            const int h0 = s_ys[mu_ybucket(ymn - radius - ys, ty0, yscale)];
-            const int h1 = s_ys[mu_ybucket(ymx + radius + ys, ty0, yscale) + 1];
+            const int h0 = s_ys[bucket_cvt<MU_NBY>(ymn - radius - ys, ty0, yscale)];
+            const int h1 = s_ys[bucket_cvt<MU_NBY>(ymx + radius + ys, ty0, yscale) + 1];
             const int sc0 = min(__builtin_amdgcn_readlane(h0, 0), __builtin_amdgcn_readlane(h0, 32)) & ~63;   // steps of 64 stay inside the NaN padded array
             const int sc1 = max(__builtin_amdgcn_readlane(h1, 0), __builtin_amdgcn_readlane(h1, 32));
             const int l31 = lane & 31;
@@ -372,8 +333,8 @@ __global__ __attribute__((amdgpu_waves_per_eu(7, 8))) __launch_bounds__(MU_THREA
                 s_ = __builtin_amdgcn_sad_u16(r1[SLOT].w, qb_.w, s_);                                      \
                 s_;                                                                                        \
             })
-#define MU_X1(A, B) ({ uint32_t k_ = sel0 ? (B) : (A); const uint32_t g_ = sel0 ? (A) : (B); k_ += mu_dpp<0xB1>(g_); k_; })   /* lane ^ 1 */
-#define MU_X2(A, B) ({ uint32_t k_ = sel1 ? (B) : (A); const uint32_t g_ = sel1 ? (A) : (B); k_ += mu_dpp<0x4E>(g_); k_; })   /* lane ^ 2 */
+#define MU_X1(A, B) ({ uint32_t k_ = sel0 ? (B) : (A); const uint32_t g_ = sel0 ? (A) : (B); k_ += wave_dpp<0xB1>(g_); k_; })   /* lane ^ 1 */
+#define MU_X2(A, B) ({ uint32_t k_ = sel1 ? (B) : (A); const uint32_t g_ = sel1 ? (A) : (B); k_ += wave_dpp<0x4E>(g_); k_; })   /* lane ^ 2 */
             // first exchange step, lane ^ 4, on all four pairs at once: a lane's bit 2 is its DPP BANK, so "keep A and add
             // the partner's A" / "keep B and add the partner's B" are two bank-masked v_add_u32_dpp instead of two selects
             // and an add: banks 0, 2 take A + A[lane + 4] (row_shl:4), banks 1, 3 take B + B[lane - 4] (row_shr:4), in
@@ -430,15 +391,15 @@ __global__ __attribute__((amdgpu_waves_per_eu(7, 8))) __launch_bounds__(MU_THREA
         }
         // ---------------- phase 3: merge the 8 lane groups (lanes with equal position in the group track the same
         // query); lane l (< 8) then holds query myq(l): 0 4 2 6 1 5 3 7 -> bring query k to the lane that carries its
-        // data (mu_qlane); fetch the original target index, ratio test, store
+        // data (qlane); fetch the original target index, ratio test, store
         {   // lane ^ 8: rotation by 8 within the row of 16 (DPP); lane ^ 16: ds_swizzle; lane ^ 32: v_permlane32_swap hands
             // every lane both halves' values
             MuTrack o;
-            o.m1 = mu_dpp<0x128>(tr.m1);
-            o.m2 = mu_dpp<0x128>(tr.m2);
+            o.m1 = wave_dpp<0x128>(tr.m1);
+            o.m2 = wave_dpp<0x128>(tr.m2);
             mu_merge(tr, o);
-            o.m1 = (uint32_t)__builtin_amdgcn_ds_swizzle((int)tr.m1, 0x401F);
-            o.m2 = (uint32_t)__builtin_amdgcn_ds_swizzle((int)tr.m2, 0x401F);
+            o.m1 = wave_swizzle<0x401F>(tr.m1);
+            o.m2 = wave_swizzle<0x401F>(tr.m2);
             mu_merge(tr, o);
             const auto h1 = __builtin_amdgcn_permlane32_swap(tr.m1, tr.m1, false, false);
             const auto h2 = __builtin_amdgcn_permlane32_swap(tr.m2, tr.m2, false, false);
@@ -452,13 +413,13 @@ __global__ __attribute__((amdgpu_waves_per_eu(7, 8))) __launch_bounds__(MU_THREA
             tr.m1 = (uint32_t)__shfl((int)tr.m1, src);
             tr.m2 = (uint32_t)__shfl((int)tr.m2, src);
         }
-        const bool mine = (lane & 28) == 0 && my_orig >= 0;   // lanes mu_qlane(k) of live queries
+        const bool mine = (lane & 28) == 0 && my_orig >= 0;   // lanes qlane(k) of live queries
         const bool none = tr.m1 == 0xffffffffu;
         const uint32_t d1 = tr.m1 >> 9;
         const bool tie = !none && tr.m2 != 0xffffffffu && (tr.m2 >> 9) == d1;
         // in-radius candidates per query (K cap, and what a query that leaves for the overflow kernel must not count):
         // no query can have more than the list holds, so they are only needed when the list is longer than K or a
-        // minimum is tied — bit counts over the list then; lane mu_qlane(k) keeps query k's
+        // minimum is tied — bit counts over the list then; lane qlane(k) keeps query k's
         const bool slow = nu > K || __any(mine && tie);   // wave uniform
         int my_cnt = 0;
         if (slow) {
@@ -467,7 +428,7 @@ __global__ __attribute__((amdgpu_waves_per_eu(7, 8))) __launch_bounds__(MU_THREA
 #pragma unroll
                 for (int k = 0; k < MU_G; ++k) {
                     const int c = __popcll(__ballot(((e >> (31 - k)) & 1u) == 0));
-                    if (lane == mu_qlane(k)) my_cnt += c;
+                    if (lane == qlane(k)) my_cnt += c;
                 }
             }
         } else if (!list_ovf && half == 0) {

@@ -45,44 +45,14 @@
 #define MU_KPCAP 512       // window keypoints staged in LDS
 #define MU_NBY 64          // y buckets of the staged window
 
-template <int CTRL>
-__device__ __forceinline__ uint32_t mu_dpp(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, false);
-}
-
-// quad broadcast (every lane has a source: no old value to keep, bound_ctrl spares the compiler its initialisation)
-template <int CTRL>
-__device__ __forceinline__ uint32_t mu_bcast(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, true);
-}
-
-// fminf / fmaxf without the canonicalising v_max x, x the compiler puts in front (v_min / v_max return the other operand
-// for a NaN, like fminf / fmaxf)
-__device__ __forceinline__ float mu_fmin(float a, float b) { float r; asm("v_min_f32_e32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ float mu_fmax(float a, float b) { float r; asm("v_max_f32_e32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-
-// bits of |qx - tx| + |qy - ty| (cvflann::L1 order, see l1_kp); abs as source modifiers of the add
-__device__ __forceinline__ uint32_t mu_l1_bits(float qx, float qy, float2 t) {
-    const float dx = qx - t.x, dy = qy - t.y;
-    float d;
-    asm("v_add_f32_e64 %0, |%1|, |%2|" : "=v"(d) : "v"(dx), "v"(dy));
-    return __float_as_uint(d);
-}
-
 // Running order statistics of one query's 8-bit-plane SADs as three packed keys, key = SAD8 << 9 | position in the round's
 // union list (< 512; SAD8 <= 121 * 255): m1 <= m2 <= m3 = the three smallest keys (0xffffffff = none).  A query sees every
 // list position at most once, so keys are distinct.
 struct MuTrack { uint32_t m1, m2, m3; };
 
-__device__ __forceinline__ uint32_t mu_med3(uint32_t a, uint32_t b, uint32_t c) {
-    uint32_t r;
-    asm("v_med3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
-}
-
 __device__ __forceinline__ void mu_update(MuTrack& t, uint32_t key) {
-    t.m3 = mu_med3(t.m2, t.m3, key);   // m2 <= m3: the median of (m2, m3, key) is the new third smallest
-    t.m2 = mu_med3(t.m1, t.m2, key);
+    t.m3 = med3_u32(t.m2, t.m3, key);   // m2 <= m3: the median of (m2, m3, key) is the new third smallest
+    t.m2 = med3_u32(t.m1, t.m2, key);
     t.m1 = min(t.m1, key);
 }
 
@@ -95,15 +65,6 @@ __device__ __forceinline__ void mu_merge(MuTrack& a, const MuTrack& b) {
     a.m3 = c3;
 }
 
-// y bucket of the staged window: monotone in y, total (NaN -> 0, +-inf saturate): v_cvt_i32_f32 truncates, saturates and
-// turns NaN into 0 (the C conversion would be undefined there), the clamp makes truncation and floor the same thing
-__device__ __forceinline__ int mu_ybucket(float y, float y0, float scale) {
-    const float f = (y - y0) * scale;
-    int b;
-    asm("v_cvt_i32_f32_e32 %0, %1" : "=v"(b) : "v"(f));
-    return min(max(b, 0), MU_NBY - 1);
-}
-
 // The shift of this run's planes (BatchMatchArgs::r8s), read from the kernel-argument segment WHERE it is used, through a
 // laundered pointer: as a value the compiler preloads at the kernel's entry it is one more scalar register live across
 // the whole kernel, and this kernel already spills scalar registers into vector lanes (19 of them; 26 with that one,
@@ -113,10 +74,6 @@ __device__ __forceinline__ int mu_r8s() {
     asm volatile("" : "+s"(kp));
     return kp[offsetof(BatchMatchArgs, r8s) / sizeof(int)];
 }
-
-// the lane that carries query k of a round (lanes 0..31: queries 0..3, lanes 32..63: queries 4..7, repeated every four
-// lanes, so that a quad broadcast hands every lane the four queries its half tests in phase 1)
-__device__ __forceinline__ constexpr int mu_qlane(int k) { return (k & 3) + 32 * (k >> 2); }
 
 // (match_frame.hip includes this file with MU_KERNEL_SIG / MU_BLOCK defined: the same body as a device function that takes its
 // block number as an argument -- one launch for a single frame's stereo and temporal problems.  Here: the kernel.)
@@ -170,8 +127,8 @@ MU_KERNEL_SIG {
         if (n2 > 0 && xa == xa && r >= 0.f) {
             const float slack = (fabsf(xa) + fabsf(xb) + fabsf(r)) * 1e-6f + 1e-6f;
             const float x0 = P.t.xinfo[0], scale = P.t.xinfo[1];
-            lo = P.t.bstart[bucket_of(xa - r - slack, x0, scale)];
-            W = P.t.bstart[bucket_of(xb + r + slack, x0, scale) + 1] - lo;
+            lo = P.t.bstart[bucket_of<VISO_NB>(xa - r - slack, x0, scale)];
+            W = P.t.bstart[bucket_of<VISO_NB>(xb + r + slack, x0, scale) + 1] - lo;
         }
     }
     lo = __builtin_amdgcn_readfirstlane(lo);
@@ -199,7 +156,7 @@ MU_KERNEL_SIG {
         e_b[i] = 0; e_r[i] = 0;
         if (w < wcap) {
             e_kp[i] = P.t.skp[lo + w];
-            e_b[i] = mu_ybucket(e_kp[i].y, ty0, yscale);
+            e_b[i] = bucket_cvt<MU_NBY>(e_kp[i].y, ty0, yscale);
             e_r[i] = atomicAdd(&s_ys[e_b[i]], 1);
         }
     }
@@ -255,7 +212,7 @@ MU_KERNEL_SIG {
     const int msh = 31 - myq;   // membership bit of query myq in a list entry (bit 7 - k of the mask byte)
 
     // query data one round ahead: lane l carries local index / keypoint / original index of query (l & 3) + 4 * half
-    // of the round (mu_qlane)
+    // of the round (qlane)
     const int qslot = (lane & 3) + 4 * half;
     int pli;
     float2 pq;
@@ -282,7 +239,7 @@ MU_KERNEL_SIG {
         // ---------------- round setup.  Lane l holds query (l & 3) + 4 * half: the four queries its half tests in phase 1
         // are the four lanes of its quad (DPP quad broadcasts, no scalar traffic)
         // the round's queries for the exact scoring and the store: lane group g (lanes 8g..8g+7) takes query g
-        const int gq_orig = __shfl(po, mu_qlane(lane >> 3)), gq_j = q0 + __shfl(pli, mu_qlane(lane >> 3));
+        const int gq_orig = __shfl(po, qlane(lane >> 3)), gq_j = q0 + __shfl(pli, qlane(lane >> 3));
         if (!__any(po >= 0)) { if (r + 1 < ROUNDS) MU_PREFETCH(r + 1); continue; }   // wave uniform
         // d = |dx| + |dy| is +0, positive or NaN (sign bit clear: the add sees |dx| and |dy|): its bit pattern orders like
         // the value and NaNs are above +inf, so (d <= radius && d < d0cut) is one unsigned compare against bits(d0)
@@ -298,13 +255,13 @@ MU_KERNEL_SIG {
         tq -= 1u;   // dead slots: 0xffffffff - bits(d) has its sign set
         float qx[4], qy[4];
         uint32_t thr[4];
-        qx[0] = __uint_as_float(mu_bcast<0x00>(__float_as_uint(pq.x))); qy[0] = __uint_as_float(mu_bcast<0x00>(__float_as_uint(pq.y))); thr[0] = mu_bcast<0x00>(tq);
-        qx[1] = __uint_as_float(mu_bcast<0x55>(__float_as_uint(pq.x))); qy[1] = __uint_as_float(mu_bcast<0x55>(__float_as_uint(pq.y))); thr[1] = mu_bcast<0x55>(tq);
-        qx[2] = __uint_as_float(mu_bcast<0xAA>(__float_as_uint(pq.x))); qy[2] = __uint_as_float(mu_bcast<0xAA>(__float_as_uint(pq.y))); thr[2] = mu_bcast<0xAA>(tq);
-        qx[3] = __uint_as_float(mu_bcast<0xFF>(__float_as_uint(pq.x))); qy[3] = __uint_as_float(mu_bcast<0xFF>(__float_as_uint(pq.y))); thr[3] = mu_bcast<0xFF>(tq);
+        qx[0] = __uint_as_float(wave_dpp_bc<0x00>(__float_as_uint(pq.x))); qy[0] = __uint_as_float(wave_dpp_bc<0x00>(__float_as_uint(pq.y))); thr[0] = wave_dpp_bc<0x00>(tq);
+        qx[1] = __uint_as_float(wave_dpp_bc<0x55>(__float_as_uint(pq.x))); qy[1] = __uint_as_float(wave_dpp_bc<0x55>(__float_as_uint(pq.y))); thr[1] = wave_dpp_bc<0x55>(tq);
+        qx[2] = __uint_as_float(wave_dpp_bc<0xAA>(__float_as_uint(pq.x))); qy[2] = __uint_as_float(wave_dpp_bc<0xAA>(__float_as_uint(pq.y))); thr[2] = wave_dpp_bc<0xAA>(tq);
+        qx[3] = __uint_as_float(wave_dpp_bc<0xFF>(__float_as_uint(pq.x))); qy[3] = __uint_as_float(wave_dpp_bc<0xFF>(__float_as_uint(pq.y))); thr[3] = wave_dpp_bc<0xFF>(tq);
         // y extent of the four queries of the lane's half (the two halves' scan ranges are joined as scalars below)
-        const float ymn = mu_fmin(mu_fmin(qy[0], qy[1]), mu_fmin(qy[2], qy[3]));
-        const float ymx = mu_fmax(mu_fmax(qy[0], qy[1]), mu_fmax(qy[2], qy[3]));
+        const float ymn = fmin_raw(fmin_raw(qy[0], qy[1]), fmin_raw(qy[2], qy[3]));
+        const float ymx = fmax_raw(fmax_raw(qy[0], qy[1]), fmax_raw(qy[2], qy[3]));
         // the eight query rows' 8-bit planes (32 dwords each): one word per lane and PAIR of rows from global memory (lanes
         // 0..31 query k, lanes 32..63 query k + 4: the row of quad lane k of the lane's own half, so its byte offset is ONE
         // quad broadcast of the lane's own; the loads land during the scan), then LDS
@@ -312,10 +269,10 @@ MU_KERNEL_SIG {
         {
             const uint32_t own = (uint32_t)min(q0 + pli, q1 - 1) * (uint32_t)VISO_ROW8;   // the row of the lane's own query
             const uint32_t l4 = (uint32_t)((lane & 31) << 2);
-            qw[0] = *(const __attribute__((address_space(1))) uint32_t*)(qrows8 + (mu_bcast<0x00>(own) + l4));   // scalar base + 32-bit offset
-            qw[1] = *(const __attribute__((address_space(1))) uint32_t*)(qrows8 + (mu_bcast<0x55>(own) + l4));
-            qw[2] = *(const __attribute__((address_space(1))) uint32_t*)(qrows8 + (mu_bcast<0xAA>(own) + l4));
-            qw[3] = *(const __attribute__((address_space(1))) uint32_t*)(qrows8 + (mu_bcast<0xFF>(own) + l4));
+            qw[0] = *(const __attribute__((address_space(1))) uint32_t*)(qrows8 + (wave_dpp_bc<0x00>(own) + l4));   // scalar base + 32-bit offset
+            qw[1] = *(const __attribute__((address_space(1))) uint32_t*)(qrows8 + (wave_dpp_bc<0x55>(own) + l4));
+            qw[2] = *(const __attribute__((address_space(1))) uint32_t*)(qrows8 + (wave_dpp_bc<0xAA>(own) + l4));
+            qw[3] = *(const __attribute__((address_space(1))) uint32_t*)(qrows8 + (wave_dpp_bc<0xFF>(own) + l4));
         }
         if (r + 1 < ROUNDS) MU_PREFETCH(r + 1);
         // ---------------- phase 1: one scan over the y buckets the round's diamonds touch, 32 targets per step: both
@@ -330,7 +287,7 @@ MU_KERNEL_SIG {
         ({                                                                                                \
             uint32_t m_ = 0;                                                                              \
             _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                 \
-                m_ = __builtin_amdgcn_alignbit(m_, thr[i] - mu_l1_bits(qx[i], qy[i], (T)), 31);           \
+                m_ = __builtin_amdgcn_alignbit(m_, thr[i] - l1_bits(qx[i], qy[i], (T)), 31);              \
             /* swap(A, B): A's lanes 32..63 <-> B's lanes 0..31; with A = B = m_: r_[0] = the low half's nibble everywhere, */ \
             /* r_[1] = the high half's */                                                                 \
             const auto r_ = __builtin_amdgcn_permlane32_swap(m_, m_, false, false);                       \
@@ -338,8 +295,8 @@ MU_KERNEL_SIG {
         })
         {
             const float ys = (fabsf(ymn) + fabsf(ymx) + fabsf(radius)) * 1e-6f + 1e-6f;   // covers the rounding of dy in the test
-            const int h0 = s_ys[mu_ybucket(ymn - radius - ys, ty0, yscale)];
-            const int h1 = s_ys[mu_ybucket(ymx + radius + ys, ty0, yscale) + 1];
+            const int h0 = s_ys[bucket_cvt<MU_NBY>(ymn - radius - ys, ty0, yscale)];
+            const int h1 = s_ys[bucket_cvt<MU_NBY>(ymx + radius + ys, ty0, yscale) + 1];
             const int sc0 = min(__builtin_amdgcn_readlane(h0, 0), __builtin_amdgcn_readlane(h0, 32)) & ~63;   // steps of 64 stay inside the NaN padded array
             const int sc1 = max(__builtin_amdgcn_readlane(h1, 0), __builtin_amdgcn_readlane(h1, 32));
             const int l31 = lane & 31;
@@ -418,7 +375,7 @@ MU_KERNEL_SIG {
                 s_ = __builtin_amdgcn_sad_hi_u8(r0[SLOT].w, qb_.w, s_);                                    \
                 s_;                                                                                        \
             })
-#define MU_X2(A, B) ({ uint32_t k_ = sel1 ? (B) : (A); const uint32_t g_ = sel1 ? (A) : (B); k_ += mu_dpp<0x4E>(g_); k_; })   /* lane ^ 2 */
+#define MU_X2(A, B) ({ uint32_t k_ = sel1 ? (B) : (A); const uint32_t g_ = sel1 ? (A) : (B); k_ += wave_dpp<0x4E>(g_); k_; })   /* lane ^ 2 */
             // first exchange step, lane ^ 4, on both pairs of registers at once: a lane's bit 2 is its DPP BANK, so "keep A
             // and add the partner's A" / "keep B and add the partner's B" are two bank-masked v_add_u32_dpp (banks 0, 2 take
             // A + A[lane + 4], banks 1, 3 take B + B[lane - 4]) instead of two selects and an add.  One asm block behind an
@@ -436,7 +393,7 @@ MU_KERNEL_SIG {
                 uint32_t p0_ = MU_SAD2(0, SLOT), p1_ = MU_SAD2(1, SLOT), p2_ = MU_SAD2(2, SLOT), p3_ = MU_SAD2(3, SLOT); \
                 MU_X4x2(p0_, p1_, p2_, p3_);   /* p0_: queries (0,1) or (2,3) by lane bit 2; p2_: (4,5) or (6,7) */ \
                 uint32_t c_ = MU_X2(p0_, p2_);                                                             \
-                c_ += mu_dpp<0xB1>(c_);        /* lane ^ 1: both lanes hold the pair's two totals */       \
+                c_ += wave_dpp<0xB1>(c_);        /* lane ^ 1: both lanes hold the pair's two totals */     \
                 const uint32_t m_ = __builtin_amdgcn_ubfe(c_, hoff, 16u);                                  \
                 /* members and non-members alike; lists longer than the store pile up in its last row (the rescue then leaves   */ \
                 /* them to the overflow kernel).  As asm: a C store into LDS between the pipeline's LDS reads made the       */ \
@@ -478,11 +435,11 @@ MU_KERNEL_SIG {
         // v_permlane32_swap; every lane then holds the round's three best keys of query myq(lane)
         {
             MuTrack o;
-            o.m1 = mu_dpp<0x128>(tr.m1); o.m2 = mu_dpp<0x128>(tr.m2); o.m3 = mu_dpp<0x128>(tr.m3);
+            o.m1 = wave_dpp<0x128>(tr.m1); o.m2 = wave_dpp<0x128>(tr.m2); o.m3 = wave_dpp<0x128>(tr.m3);
             mu_merge(tr, o);
-            o.m1 = (uint32_t)__builtin_amdgcn_ds_swizzle((int)tr.m1, 0x401F);
-            o.m2 = (uint32_t)__builtin_amdgcn_ds_swizzle((int)tr.m2, 0x401F);
-            o.m3 = (uint32_t)__builtin_amdgcn_ds_swizzle((int)tr.m3, 0x401F);
+            o.m1 = wave_swizzle<0x401F>(tr.m1);
+            o.m2 = wave_swizzle<0x401F>(tr.m2);
+            o.m3 = wave_swizzle<0x401F>(tr.m3);
             mu_merge(tr, o);
             const auto h1 = __builtin_amdgcn_permlane32_swap(tr.m1, tr.m1, false, false);
             const auto h2 = __builtin_amdgcn_permlane32_swap(tr.m2, tr.m2, false, false);
@@ -519,9 +476,9 @@ MU_KERNEL_SIG {
                 s_ = __builtin_amdgcn_sad_u16((R1).y, x1.y, s_);                                           \
                 s_ = __builtin_amdgcn_sad_u16((R1).z, x1.z, s_);                                           \
                 s_ = __builtin_amdgcn_sad_u16((R1).w, x1.w, s_);                                           \
-                s_ += mu_dpp<0xB1>(s_);                                          /* lane ^ 1 */            \
-                s_ += mu_dpp<0x4E>(s_);                                          /* lane ^ 2 */            \
-                s_ += (uint32_t)__builtin_amdgcn_ds_swizzle((int)s_, 0x101F);    /* lane ^ 4 */            \
+                s_ += wave_dpp<0xB1>(s_);           /* lane ^ 1 */                                         \
+                s_ += wave_dpp<0x4E>(s_);           /* lane ^ 2 */                                         \
+                s_ += wave_swizzle<0x101F>(s_);     /* lane ^ 4 */                                         \
                 s_;                                                                                        \
             })
             dA = MU_SAD16(a0, a1);
@@ -569,7 +526,7 @@ MU_KERNEL_SIG {
                 rm = 0;
                 if (rescue) { irregular = true; rescue = false; }
             }
-#define MU_UPD2(KEY) do { const uint32_t k_ = (KEY); m2 = mu_med3(m1, m2, k_); m1 = min(m1, k_); } while (0)
+#define MU_UPD2(KEY) do { const uint32_t k_ = (KEY); m2 = med3_u32(m1, m2, k_); m1 = min(m1, k_); } while (0)
             while (rm) {   // wave uniform
                 const int bit = __builtin_ctzll(rm);
                 rm &= rm - 1;
@@ -635,17 +592,17 @@ MU_KERNEL_SIG {
                             sa = __builtin_amdgcn_sad_u16(a1[p].y, x1_.y, sa);
                             sa = __builtin_amdgcn_sad_u16(a1[p].z, x1_.z, sa);
                             sa = __builtin_amdgcn_sad_u16(a1[p].w, x1_.w, sa);
-                            sa += mu_dpp<0xB1>(sa);                                          // lane ^ 1
-                            sa += mu_dpp<0x4E>(sa);                                          // lane ^ 2
-                            sa += (uint32_t)__builtin_amdgcn_ds_swizzle((int)sa, 0x101F);    // lane ^ 4
+                            sa += wave_dpp<0xB1>(sa);          // lane ^ 1
+                            sa += wave_dpp<0x4E>(sa);          // lane ^ 2
+                            sa += wave_swizzle<0x101F>(sa);    // lane ^ 4
                             // one key per survivor (the group's first lane), none past the list's end
                             MU_UPD2(((t + p) * 8 + g8 < nm && sub == 0) ? ((sa << 9) | pos[p]) : 0xffffffffu);
                         }
                     }
                     // (min, second min) over the groups' first lanes (the only ones with keys; lane 8k reads the result): keys are distinct
 #define MU_MRG2(O1, O2) do { const uint32_t o1_ = (O1), o2_ = (O2); m2 = min(max(m1, o1_), min(m2, o2_)); m1 = min(m1, o1_); } while (0)
-                    MU_MRG2(mu_dpp<0x128>(m1), mu_dpp<0x128>(m2));                                                       // lane ^ 8
-                    MU_MRG2((uint32_t)__builtin_amdgcn_ds_swizzle((int)m1, 0x401F), (uint32_t)__builtin_amdgcn_ds_swizzle((int)m2, 0x401F));   // lane ^ 16
+                    MU_MRG2(wave_dpp<0x128>(m1), wave_dpp<0x128>(m2));                                                       // lane ^ 8
+                    MU_MRG2(wave_swizzle<0x401F>(m1), wave_swizzle<0x401F>(m2));   // lane ^ 16
                     {
                         const auto h1 = __builtin_amdgcn_permlane32_swap(m1, m1, false, false);
                         const auto h2 = __builtin_amdgcn_permlane32_swap(m2, m2, false, false);

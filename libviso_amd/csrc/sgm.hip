@@ -19,6 +19,7 @@
 //                       before d* - 1 and after d* + 1), uniqueness, left-right check, V-fit                -> out i16
 // L_r <= 62 + P2 <= 254, S <= 8 * 254 = 2032.
 #include "common.h"
+#include "wave.h"
 
 #define SGM_MAX_COLS 2048
 #define SGM_SEL_THREADS 256

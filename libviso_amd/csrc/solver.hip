@@ -94,23 +94,7 @@ __global__ __launch_bounds__(256) void ransac_hyp_kernel(SolverArgs a) {
 //              convergence test and tr stay wave uniform)
 // Values are bit-identical to gn_serial's (tests/test_gpu_solver_edges.py runs every hypothesis both ways): only
 // who computes them changes.  ~60 VGPRs instead of 205, about a third of the instructions per iteration.
-__device__ __forceinline__ double rdlane(double v, int src_lane) {   // src_lane: compile-time constant
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), src_lane);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), src_lane);
-    return __hiloint2double(hi, lo);
-}
-template <int I>
-__device__ __forceinline__ double swz_bcast8(double v) {   // element I of the lane's aligned group of 8 lanes
-    constexpr int pat = (I << 5) | 0x18;                   // bitmask mode: lane' = (lane & 0x18) | I  (per 32 lanes)
-    const int lo = __builtin_amdgcn_ds_swizzle(__double2loint(v), pat);
-    const int hi = __builtin_amdgcn_ds_swizzle(__double2hiint(v), pat);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double bperm(double v, int src_lane) {
-    const int lo = __builtin_amdgcn_ds_bpermute(src_lane << 2, __double2loint(v));
-    const int hi = __builtin_amdgcn_ds_bpermute(src_lane << 2, __double2hiint(v));
-    return __hiloint2double(hi, lo);
-}
+// (the fp64 lane moves rdlane, swz_bcast8, bperm and uni: wave.h)
 
 // one pivot step of the lane-distributed LU; returns false when the system is singular (uniform)
 template <int I>
@@ -359,12 +343,6 @@ __global__ __launch_bounds__(256) void ransac_rot_kernel(SolverArgs a) {
     }
 }
 
-__device__ __forceinline__ float inl_abs_add_abs(float a, float b) { float d; asm("v_add_f32_e64 %0, |%1|, |%2|" : "=v"(d) : "v"(a), "v"(b)); return d; }
-__device__ __forceinline__ float inl_add_abs(float acc, float a, float b) {   // acc + |a| + |b|
-    float d;
-    asm("v_add_f32_e64 %0, %1, |%2|\n\tv_add_f32_e64 %0, %0, |%3|" : "=&v"(d) : "v"(acc), "v"(a), "v"(b));
-    return d;
-}
 __device__ __forceinline__ float inl_fma_abs0(float a, float b, float c) { float d; asm("v_fma_f32 %0, |%1|, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c)); return d; }
 __device__ __forceinline__ float inl_fma_abs1(float a, float b, float c) { float d; asm("v_fma_f32 %0, %1, |%2|, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c)); return d; }
 
@@ -452,8 +430,8 @@ __global__ __launch_bounds__(64) void inlier_count_kernel(SolverArgs a, int chun
         // sum|e| and the two FMAs on |1/Zc| and |g|: absolute values are source modifiers of the unpacked encodings (as C
         // the compiler builds them from twelve v_and_b32 and packed adds)
         inl_f2 es, de2;   // sum|e|; 2.125 de
-        es.x = inl_add_abs(inl_abs_add_abs(e0.x, e1.x), e2.x, e3.x);
-        es.y = inl_add_abs(inl_abs_add_abs(e0.y, e1.y), e2.y, e3.y);
+        es.x = add_abs_abs(abs_add_abs(e0.x, e1.x), e2.x, e3.x);
+        es.y = add_abs_abs(abs_add_abs(e0.y, e1.y), e2.y, e3.y);
         const inl_f2 tail = INL_FMA(ESC, es, K1);     // 2u sum|e| + u Cm, inflated
         de2.x = inl_fma_abs0(g.x, inl_fma_abs1(c2j, rz.x, c1j), tail.x);
         de2.y = inl_fma_abs0(g.y, inl_fma_abs1(c2j, rz.y, c1j), tail.y);
@@ -549,12 +527,6 @@ __device__ int block_inliers(const double* tr, const SolverParamsDev& sp, const 
         __syncthreads();
     }
     return running;
-}
-
-// A wave-uniform double into scalar registers (the compiler cannot know a value that came back from LDS or from a
-// cross-lane read is uniform): v_readfirstlane of both halves.
-__device__ __forceinline__ double uni(double v) {
-    return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
 }
 
 #ifdef VISO_DEBUG_VARIANTS   // timing aid (tools/experiments/refit_phases.py): 100 MHz time stamps of the refit's phases, item 0

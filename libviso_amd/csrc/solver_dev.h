@@ -6,6 +6,7 @@
 // last-ulp behaviour of sin/cos and the summation tree of the block reduction.
 #pragma once
 #include "common.h"
+#include "wave.h"
 
 #include <float.h>
 #include <math.h>
@@ -295,25 +296,6 @@ __device__ inline int gn_serial(const double* X, const double* obs, int ld, cons
         for (int j = 0; j < 6; ++j) tr[j] = tr[j] + B[j];
     }
     return it_end >= 100 ? 0 : 2;                 // :1622
-}
-
-// Sum of a double over the wave, valid in lane 63: row_shr 1, 2, 4, 8 inside the rows of 16 lanes (lanes without a source
-// add 0), then row_bcast:15 into rows 1 and 3 and row_bcast:31 into rows 2 and 3 (gfx9 reduction idiom; the halves of the
-// double move as two 32-bit DPP moves).
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double dpp_f64(double v) {
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, ROW_MASK, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, ROW_MASK, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double wave_sum_to_lane63(double v) {
-    v += dpp_f64<0x111, 0xf>(v);   // row_shr:1
-    v += dpp_f64<0x112, 0xf>(v);   // row_shr:2
-    v += dpp_f64<0x114, 0xf>(v);   // row_shr:4
-    v += dpp_f64<0x118, 0xf>(v);   // row_shr:8  -> lane 15 of every row = the row's sum
-    v += dpp_f64<0x142, 0xa>(v);   // row_bcast:15 into rows 1 and 3
-    v += dpp_f64<0x143, 0xc>(v);   // row_bcast:31 into rows 2 and 3 -> lane 63 = the wave's sum
-    return v;
 }
 
 // ---- shared by the fp64 motion estimators: covariance.hip, refine.hip, window.hip ---------------------------------------

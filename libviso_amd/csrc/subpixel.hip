@@ -8,6 +8,7 @@
 // windows are recomputed from the resident right image: one 15 x 15 byte region per row gives all five.  Integer SADs, double
 // only in the final division; details at subpixel_refine_kernel.
 #include "common.h"
+#include "wave.h"
 
 #define SUBPIX_THREADS 256
 #define SUBPIX_WPB (SUBPIX_THREADS / 64)

@@ -40,6 +40,7 @@
 // voxel_host.h.  This file keeps the table's payload and insert, the kernels' own bodies, the parameter and entry checks, the
 // orders of the items and the whole mesh extraction, whose two lists do not fit the shared two passes.
 #include "common.h"
+#include "wave.h"
 #include "voxel_host.h"
 
 #include <cmath>

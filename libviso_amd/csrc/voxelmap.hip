@@ -20,6 +20,7 @@
 // passes of the getters and the statistics' read-back are voxel_host.h.  This file keeps the table's payload and insert, the
 // kernels' own bodies, the parameter and entry checks and the order of the entries.
 #include "common.h"
+#include "wave.h"
 #include "voxel_host.h"
 
 #include <cmath>

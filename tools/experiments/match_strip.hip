@@ -60,25 +60,11 @@
 #define MS_LDS_BYTES (MS_OFF_QORD + 2 * MS_QPB)
 static_assert(MS_LDS_BYTES <= 163840, "LDS budget of one CU");
 
-template <int CTRL>
-__device__ __forceinline__ uint32_t ms_dpp(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, false);
-}
-
-__device__ __forceinline__ uint32_t ms_l1_bits(float qx, float qy, float2 t) {
-    const float dx = qx - t.x, dy = qy - t.y;
-    float d;
-    asm("v_add_f32_e64 %0, |%1|, |%2|" : "=v"(d) : "v"(dx), "v"(dy));
-    return __float_as_uint(d);
-}
-
 // packed-key order statistics (see match_union.hip): key = SAD << 9 | position in the round's union list
 struct MsTrack { uint32_t m1, m2; };
 
 __device__ __forceinline__ void ms_update(MsTrack& t, uint32_t key) {
-    uint32_t med;
-    asm("v_med3_u32 %0, %1, %2, %3" : "=v"(med) : "v"(t.m1), "v"(t.m2), "v"(key));
-    t.m2 = med;
+    t.m2 = med3_u32(t.m1, t.m2, key);
     t.m1 = min(t.m1, key);
 }
 
@@ -86,12 +72,6 @@ __device__ __forceinline__ void ms_merge(MsTrack& a, const MsTrack& b) {
     const uint32_t hi = max(a.m1, b.m1);
     a.m2 = min(hi, min(a.m2, b.m2));
     a.m1 = min(a.m1, b.m1);
-}
-
-__device__ __forceinline__ int ms_ybucket(float y, float y0, float scale) {   // monotone in y
-    if (y != y) return MS_NBY - 1;
-    const float f = floorf((y - y0) * scale);
-    return f <= 0.f ? 0 : (f >= (float)(MS_NBY - 1) ? MS_NBY - 1 : (int)f);
 }
 
 struct StripArgs {
@@ -143,8 +123,8 @@ __global__ __launch_bounds__(MS_THREADS) void match_strip_kernel(StripArgs sa) {
             const float xa = P.q.skp[q0].x, xb = P.q.skp[q1v - 1].x;
             const float slack = (fabsf(xa) + fabsf(xb) + fabsf(radius)) * 1e-6f + 1e-6f;
             const float x0 = P.t.xinfo[0], scale = P.t.xinfo[1];
-            lo = P.t.bstart[bucket_of(xa - radius - slack, x0, scale)];
-            hi = P.t.bstart[bucket_of(xb + radius + slack, x0, scale) + 1];
+            lo = P.t.bstart[bucket_of<VISO_NB>(xa - radius - slack, x0, scale)];
+            hi = P.t.bstart[bucket_of<VISO_NB>(xb + radius + slack, x0, scale) + 1];
         }
         s_tlo[tid] = lo; s_thi[tid] = max(hi, lo);
     }
@@ -254,7 +234,7 @@ __global__ __launch_bounds__(MS_THREADS) void match_strip_kernel(StripArgs sa) {
             int e_b = 0, e_r = 0;
             if (tid < cw && !(sa.debug & 16)) {
                 e_kp = s_kpr[(cl + tid) & (MS_RING - 1)];
-                e_b = ms_ybucket(e_kp.y, ty0, yscale);
+                e_b = bucket_of_finite<MS_NBY>(e_kp.y, ty0, yscale);
                 e_r = atomicAdd(&s_ys[e_b], 1);
             }
             __syncthreads();   // S2
@@ -299,8 +279,8 @@ __global__ __launch_bounds__(MS_THREADS) void match_strip_kernel(StripArgs sa) {
                 bool any_live = false;
 #pragma unroll
                 for (int k = 0; k < MS_G; ++k) {
-                    qk[k].x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pq.x), k));
-                    qk[k].y = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pq.y), k));
+                    qk[k].x = readlane_f32(pq.x, k);
+                    qk[k].y = readlane_f32(pq.y, k);
                     orig[k] = __builtin_amdgcn_readlane(po, k);
                     pl[k] = __builtin_amdgcn_readlane(pli, k);
                     jq[k] = q0 + pl[k];
@@ -334,16 +314,16 @@ __global__ __launch_bounds__(MS_THREADS) void match_strip_kernel(StripArgs sa) {
                     const float ymn = fminf(fminf(qk[0].y, qk[1].y), fminf(qk[2].y, qk[3].y));
                     const float ymx = fmaxf(fmaxf(qk[0].y, qk[1].y), fmaxf(qk[2].y, qk[3].y));
                     const float ys = (fabsf(ymn) + fabsf(ymx) + fabsf(radius)) * 1e-6f + 1e-6f;   // covers the rounding of dy in the test
-                    const int sc0 = s_ys[ms_ybucket(ymn - radius - ys, ty0, yscale)] & ~(2 * VISO_WAVE - 1);
-                    const int sc1 = s_ys[ms_ybucket(ymx + radius + ys, ty0, yscale) + 1];
+                    const int sc0 = s_ys[bucket_of_finite<MS_NBY>(ymn - radius - ys, ty0, yscale)] & ~(2 * VISO_WAVE - 1);
+                    const int sc1 = s_ys[bucket_of_finite<MS_NBY>(ymx + radius + ys, ty0, yscale) + 1];
                     for (int base = sc0; base < sc1; base += 2 * VISO_WAVE) {
                         const float2 ta = s_ykp[base + lane], tb = s_ykp[base + VISO_WAVE + lane];
                         const uint32_t pa = s_ypos[base + lane], pb = s_ypos[base + VISO_WAVE + lane];
                         uint32_t ma = 0, mb = 0;
 #pragma unroll
                         for (int k = 0; k < MS_G; ++k) {
-                            const bool ina = ms_l1_bits(qk[k].x, qk[k].y, ta) < thr[k];
-                            const bool inb = ms_l1_bits(qk[k].x, qk[k].y, tb) < thr[k];
+                            const bool ina = l1_bits(qk[k].x, qk[k].y, ta) < thr[k];
+                            const bool inb = l1_bits(qk[k].x, qk[k].y, tb) < thr[k];
                             cnt[k] += __popcll(__ballot(ina)) + __popcll(__ballot(inb));
                             ma = ma + ma + (ina ? 1u : 0u);
                             mb = mb + mb + (inb ? 1u : 0u);
@@ -393,12 +373,12 @@ __global__ __launch_bounds__(MS_THREADS) void match_strip_kernel(StripArgs sa) {
                         const uint32_t s0_ = MS_SAD(0, SLOT), s1_ = MS_SAD(1, SLOT), s2_ = MS_SAD(2, SLOT), s3_ = MS_SAD(3, SLOT); \
                         uint32_t a01_ = sel0 ? s1_ : s0_, a23_ = sel0 ? s3_ : s2_;                         \
                         const uint32_t b01_ = sel0 ? s0_ : s1_, b23_ = sel0 ? s2_ : s3_;                   \
-                        a01_ += ms_dpp<0xB1>(b01_);   /* quad_perm 1,0,3,2 */                              \
-                        a23_ += ms_dpp<0xB1>(b23_);                                                        \
+                        a01_ += wave_dpp<0xB1>(b01_);   /* quad_perm 1,0,3,2 */                            \
+                        a23_ += wave_dpp<0xB1>(b23_);                                                      \
                         uint32_t m_ = sel1 ? a23_ : a01_;                                                  \
                         const uint32_t o_ = sel1 ? a01_ : a23_;                                            \
-                        m_ += ms_dpp<0x4E>(o_);       /* quad_perm 2,3,0,1 */                              \
-                        m_ += ms_dpp<0x141>(m_);      /* row_half_mirror: lanes i and 7 - i track the same query */ \
+                        m_ += wave_dpp<0x4E>(o_);       /* quad_perm 2,3,0,1 */                            \
+                        m_ += wave_dpp<0x141>(m_);      /* row_half_mirror: lanes i and 7 - i track the same query */ \
                         const bool member_ = ((ent[SLOT] >> msh) & 1u) != 0;                               \
                         ms_update(tr, member_ ? ((m_ << 9) | (uint32_t)(U)) : 0xffffffffu);                \
                     } while (0)
