@@ -1122,8 +1122,9 @@ int viso_tsdf_mesh(viso_tsdf* t, uint32_t min_weight, viso_tsdf_mesh_vertex* ver
  * voxel's footprint (DESIGN.md 5.17 has the figures).
  * An overflowed map refuses with VISO_ERR_NOMEM, as the getters do; a handle that is not a live TSDF map, or whose context is gone,
  * VISO_ERR_ARG; no device, VISO_ERR_HIP.  The call takes the map's lock, like an extraction.
- * Out of scope: trilinear sampling, normals and shaded images, an empty-space skipping structure (a coarse block table), rendering
- * into a batch's resident maps, frame-to-model alignment, RGB (one 8-bit intensity: "TSDF intensity" below).
+ * Out of scope: trilinear rendering (the distance is sampled trilinearly by "TSDF align" below), normals and shaded images, an
+ * empty-space skipping structure (a coarse block table), rendering into a batch's resident maps, RGB (one 8-bit intensity: "TSDF
+ * intensity" below).  Frame-to-model alignment: "TSDF align" below.
  * HIP kernel (tsdf.hip): tsdf_render_kernel, one thread per pixel of a group of views, the lanes of a wave consecutive pixels of a
  * row.  The loop over i is uniform across the wave; per i the lanes that continue the voxel of the lane to their left form a run,
  * whose head lane alone probes the table and loads weight and sum, and the other lanes take them from it.  Reads only: no atomics,
@@ -1196,6 +1197,122 @@ int viso_tsdf_vertex_gray(viso_tsdf* t, const viso_tsdf_mesh_vertex* vertices, s
 /* gray_out: uint8 [n_views][rows][cols]; it goes through the same device buffer as the other two outputs. */
 int viso_tsdf_render_gray(viso_tsdf* t, uint32_t min_weight, const viso_param* param, int rows, int cols, double max_depth,
                           const double* poses_or_null, int n_views, int16_t* disp_out, uint32_t* weight_out_or_null, uint8_t* gray_out);
+
+/* ------------------------------------------------ TSDF align: the pose at which a measured map lies on the model (opt-in; NOT in
+ * the reference)
+ *
+ * Frame-to-model alignment by direct tracking on the signed distance (Bylow, Sturm, Kerl, Kahl, Cremers: Real-time camera tracking
+ * and 3D reconstruction using signed distance functions, RSS 2013): no ray cast and no search for correspondences.  Every valid
+ * pixel of a measured disparity map is back-projected with a pose guess, samples the map's averaged signed distance trilinearly
+ * and contributes one row to a 6 x 6 Gauss-Newton system; the solution moves the pose so that the points come to lie on the
+ * distance's zero set.  The normal equations are sums of integers: per pixel the six entries of the row and the residual are formed
+ * in double, rounded once to integers, and their 28 pairwise products are summed as int64.  The sums depend on neither the order
+ * of the pixels nor on scheduling, and the device output is bit-identical to tests/align_ref.py.  This definition is the contract.
+ * Everything is IEEE double in the operand order written, with no fused multiply-add.  A linearise and an align read the table
+ * only: the table, its statistics and the overflow mark are untouched; a gray map is accepted, of which only weight and sum are read.
+ * Parameters (viso_tsdf_align_params): min_weight >= 1; gate_voxels finite, 0 < gate_voxels <= the map's trunc_voxels; max_iters in
+ * 1..50; eps_rot (rad) and eps_trans (m) finite and >= 0; min_pixels >= 6.
+ * Inputs of a linearise: the map; disp int16 [rows][cols], rows, cols >= 1 and rows cols <= 2^22 (a product of two entries is below
+ * 2^40, so a sum stays below 2^62); a viso_param of which f, cu, cv, base are read (all finite, f > 0, base > 0); one pose, 4 x 4
+ * row-major, camera to world, as viso_tsdf_fuse takes it, its first three rows finite (the fourth is not read), taken as rigid, or
+ * NULL: the identity matrix.  voxel and s = voxel / 1024 are the map's own, G = gate_voxels 1024.0.  Any violation: VISO_ERR_ARG;
+ * the checks that do not need the map come before the handle is looked at.
+ * Per pixel (x, y):
+ *   1. It contributes by rules 1 and 2 of the TSDF map with the map's min_disp16: P = (X, Y, Z).  n_points += 1.
+ *   2. World point: Q_i = ((T[i][0] X + T[i][1] Y) + T[i][2] Z) + T[i][3].
+ *   3. u_i = Q_i / voxel - 0.5 (a voxel's centre has integer u), k0_i = floor(u_i), t_i = u_i - k0_i.  A u_i that is not finite,
+ *      or a k0_i outside -2^20 .. 2^20 - 2: n_out_of_range += 1, the pixel is skipped.
+ *   4. The eight voxels k0 + (dx, dy, dz), d in {0, 1}.  A voxel is usable when it is in the table with weight >= min_weight.  Any
+ *      of the eight not usable: n_missing += 1, the pixel is skipped.  m[dz][dy][dx] = (double)sum / (double)weight.
+ *   5. Along x, for the four (dy, dz):  X1[dz][dy] = m[dz][dy][1] - m[dz][dy][0],  X0[dz][dy] = m[dz][dy][0] + t_0 X1[dz][dy].
+ *      Along y, for the two dz:         Y1[dz] = X0[dz][1] - X0[dz][0],             Y0[dz] = X0[dz][0] + t_1 Y1[dz],
+ *                                       YX[dz] = X1[dz][0] + t_1 (X1[dz][1] - X1[dz][0]).
+ *      Along z:  psi = Y0[0] + t_2 (Y0[1] - Y0[0]),  D0 = YX[0] + t_2 (YX[1] - YX[0]),  D1 = Y1[0] + t_2 (Y1[1] - Y1[0]),
+ *                D2 = Y0[1] - Y0[0].  psi is the distance in units of s, D its derivative per voxel; g_i = D_i / 1024.0 is metres
+ *      per metre.
+ *   6. Gate: |psi| > G: n_gated += 1, the pixel is skipped.
+ *   7. w = (f base) / (Z Z): the residual is in pixels of disparity, which whitens stereo's depth noise.  e = (psi s) w.
+ *      The gradient in the camera: c_j = (T[0][j] g_0 + T[1][j] g_1) + T[2][j] g_2.  The row, for an increment on the camera's side
+ *      (T <- T D(xi), xi = (v, omega): translation first), which keeps the system conditioned far from the world's origin:
+ *      a_0..2 = c_j w;  a_3 = (Y c_2 - Z c_1) w,  a_4 = (Z c_0 - X c_2) w,  a_5 = (X c_1 - Y c_0) w   (P x c).
+ *   8. A_i = floor(a_i 256.0 + 0.5) for i < 6, A_6 = floor(e 256.0 + 0.5).  A value that is not finite or |A_i| >= 2^20:
+ *      n_clipped += 1, the pixel is skipped.
+ *   9. n_used += 1, and for 0 <= i <= j <= 6: N[i][j] += A_i A_j (int64).  n[28] holds the upper triangle row by row:
+ *      N[i][j] = n[7 i - i (i - 1) / 2 + (j - i)].
+ * Align (viso_tsdf_align): on the host around the kernel, with T the guess (NULL: the identity) and its fourth row set to 0 0 0 1.
+ *   For it = 0 .. max_iters - 1:
+ *   a. Linearise at T.  H = N[:6][:6] / 65536.0 (both triangles), b_i = N[i][6] / 65536.0, C = N[6][6] / 65536.0.
+ *   b. n_used < min_pixels: status -1.
+ *   c. Cholesky H = L L', row by row: d = H[j][j] - L[j][0]^2 - .. - L[j][j-1]^2 (subtracted in that order); !(d > 1e-12 H[j][j]):
+ *      status -2 (a single wall, for example, leaves three directions free); L[j][j] = sqrt(d),
+ *      L[i][j] = (H[i][j] - L[i][0] L[j][0] - .. - L[i][j-1] L[j][j-1]) / L[j][j].
+ *   d. xi = -(H^-1 b) by the two triangular solves.  An entry that is not finite: status -3.
+ *   e. D(xi): theta2 = (omega_0^2 + omega_1^2) + omega_2^2, theta = sqrt(theta2); A = sin(theta) / theta and
+ *      B = (1 - cos(theta)) / theta2, or for theta < 1e-8: A = 1 - theta2 / 6, B = 0.5 - theta2 / 24; with K the cross-product
+ *      matrix of omega, R = I + A K + B (omega omega' - theta2 I), and D = [R v; 0 1].
+ *      T[i][j] <- (T[i][0] D[0][j] + T[i][1] D[1][j]) + T[i][2] D[2][j], and for j = 3: that + T[i][3].  iters = it + 1.
+ *   f. ||omega|| <= eps_rot and ||v|| <= eps_trans: status 1, the loop ends.  max_iters steps without that: status 2; the pose is
+ *      returned all the same.
+ *   One more linearise at the final T, with the checks b and c, gives cost = sqrt(C / n_used), n_used and
+ *   cov = (C / max(n_used - 6, 1)) H^-1 in the (v, omega) order of the row.
+ *   On a status < 0, pose is the guess and every other number of the record is zero.
+ *   Trace: trace_out_or_null [trace_cap] receives one viso_tsdf_align_step per linearise in their order, the last one included
+ *   (at most max_iters + 1; those beyond trace_cap are not recorded, entries that are not written are not touched; a written
+ *   entry's pose ends in 0 0 0 1).
+ * Resident path: viso_batch_align_tsdf aligns the batch's resident maps t0 .. t1-1, each on its own against the same model, with the
+ * batch's calibration and with no host copy of the maps: records_out [t1 - t0], each what viso_tsdf_align gives for that map and
+ * guess, bit for bit.  All frames of an iteration share one launch; a frame that has finished leaves it at once.  It has the
+ * refusals and the context rule of viso_batch_fuse_tsdf.
+ * An overflowed map refuses with VISO_ERR_NOMEM, as the getters do; a handle that is not a live TSDF map, or whose context is gone,
+ * VISO_ERR_ARG.  The calls take the map's lock, like an extraction.
+ * Limits: the gradient comes from 8 voxels, so the basin is about the gate wide; the distances are projective and averaged along the
+ * fusing views' axes, so a surface at grazing incidence (80 degrees) pulls the pose off by tenths of a degree even from the truth;
+ * below a voxel of about 0.05 m at KITTI's noise the steps stop shrinking before eps (status 2).  DESIGN.md 5.19 has the figures.
+ * Out of scope: photometric terms from the gray sum, robust kernels beyond the gate, coarse-to-fine pyramids, alignment inside the
+ * KITTI runners, loop closure, trilinear rendering.
+ * HIP kernel (tsdf_align.hip): tsdf_linearize_kernel, the lanes of a wave consecutive pixels of a row, a thread strides over
+ * several pixels.  Lanes whose k0 equals their left neighbour's form a run; the run's head lane alone does the eight probes and
+ * loads, the others take the 8 x (weight, sum) from it.  The 28 sums stay in registers and are reduced once: across the wave by DPP,
+ * across the workgroup's waves in LDS, then one set of 64-bit integer atomic adds per workgroup.  No float atomics, no scratch, no
+ * workgroup waits for another. */
+typedef struct viso_tsdf_align_params {   /* 48 bytes */
+    uint32_t min_weight;     /* a voxel is usable from this many updates */
+    double gate_voxels;      /* |distance| beyond this many voxels: the pixel is not used */
+    int32_t max_iters;
+    double eps_rot;          /* rad */
+    double eps_trans;        /* m */
+    int32_t min_pixels;      /* fewer used pixels: status -1 */
+} viso_tsdf_align_params;
+
+typedef struct viso_tsdf_normal {   /* 272 bytes */
+    int64_t n[28];           /* step 9 */
+    uint64_t n_points, n_used, n_missing, n_gated, n_clipped, n_out_of_range;
+} viso_tsdf_normal;
+
+typedef struct viso_tsdf_alignment {   /* 440 bytes */
+    double pose[16];         /* the aligned pose, camera to world */
+    double cov[36];          /* of (v, omega), row-major */
+    double cost;             /* rms residual, pixels of disparity */
+    uint64_t n_used;
+    int32_t iters;           /* steps taken */
+    int32_t status;          /* 1 converged, 2 max_iters reached, -1 too few pixels, -2 degenerate system, -3 a step that is not finite */
+} viso_tsdf_alignment;
+
+typedef struct viso_tsdf_align_step {   /* 400 bytes */
+    double pose[16];         /* where the linearise was taken */
+    viso_tsdf_normal normal;
+} viso_tsdf_align_step;
+
+/* min_weight 2, gate_voxels 1.0, max_iters 10, eps_rot 1e-6, eps_trans 1e-5, min_pixels 200.  Host only. */
+void viso_tsdf_align_params_default(viso_tsdf_align_params* p);
+/* Steps 1..9 at one pose.  Of *params, min_weight and gate_voxels are read (all of it is checked). */
+int viso_tsdf_linearize(viso_tsdf* t, const viso_tsdf_align_params* params, const int16_t* disp, int rows, int cols, const viso_param* param,
+                        const double* pose_or_null, viso_tsdf_normal* out);
+int viso_tsdf_align(viso_tsdf* t, const viso_tsdf_align_params* params, const int16_t* disp, int rows, int cols, const viso_param* param,
+                    const double* pose_guess_or_null, viso_tsdf_alignment* record_out, viso_tsdf_align_step* trace_out_or_null, int trace_cap);
+/* poses_guess: [t1 - t0][16]; records_out: [t1 - t0]. */
+int viso_batch_align_tsdf(viso_batch* b, viso_tsdf* t, int t0, int t1, const double* poses_guess, const viso_tsdf_align_params* params,
+                          viso_tsdf_alignment* records_out);
 
 #ifdef __cplusplus
 }

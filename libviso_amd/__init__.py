@@ -20,7 +20,8 @@ from .abi import (DESC_LEN, MAP_DEFAULTS, MAP_ENTRY_DTYPE, MapCounters, MapParam
                   Param, SgmParams, SpeckleParams, declare_common, declare_covariance, declare_disparity, declare_refine, declare_rectify,
                   declare_sgm, declare_speckle, declare_subpixel, declare_window, f32p, f64p, i32p, i64p, intp, ptr,
                   TSDF_CROSSING_DTYPE, TSDF_DEFAULTS, TSDF_ENTRY_DTYPE, TSDF_GRAY_ENTRY_DTYPE, TSDF_MESH_VERTEX_DTYPE, TsdfCounters, TsdfParams,
-                  declare_tsdf)
+                  declare_tsdf, TSDF_ALIGN_DEFAULTS, TSDF_ALIGN_STEP_DTYPE, TSDF_ALIGNMENT_DTYPE, TSDF_NORMAL_COUNTERS, TSDF_NORMAL_DTYPE,
+                  TsdfAlignParams)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("VISO_HIP_SO") or os.path.join(_HERE, "libviso_hip.so")   # VISO_HIP_SO: another build of the library (A/B runs)
@@ -656,6 +657,27 @@ def tsdf_params(**params):
     return p
 
 
+def tsdf_align_params(**params):
+    """viso_tsdf_align_params: viso_tsdf_align_params_default with the given fields (min_weight, gate_voxels, max_iters, eps_rot in
+    rad, eps_trans in metres, min_pixels) replaced.  Needs no library: the ranges are checked by the calls (TsdfAlignParams.ok
+    restates them)."""
+    p = TsdfAlignParams(**TSDF_ALIGN_DEFAULTS)
+    for k, v in params.items():
+        if k not in TSDF_ALIGN_DEFAULTS:
+            raise TypeError(f"tsdf_align_params: unknown parameter {k!r}")
+        setattr(p, k, float(v) if k in ("gate_voxels", "eps_rot", "eps_trans") else int(v))
+    return p
+
+
+def tsdf_normal_matrix(normal):
+    """The 28 sums of a TSDF_NORMAL_DTYPE record as the symmetric int64 [7][7] matrix N, and its counters as a dict."""
+    N = np.zeros((7, 7), np.int64)
+    iu = np.triu_indices(7)
+    N[iu] = normal["n"]
+    N.T[iu] = normal["n"]
+    return N, {name: int(normal[name]) for name in TSDF_NORMAL_COUNTERS}
+
+
 def tsdf_crossing_points(crossings, voxel):
     """viso_tsdf_crossing_point of every crossing: float32 [n][3], where the averaged signed distance passes through zero between
     the centres of the two voxels.  Host only."""
@@ -1111,6 +1133,40 @@ class TsdfMap(_TableMap):
         v, tri = v[:nv.value], tri[:nt.value]
         return (v, tri, self.vertex_gray(v)) if gray else (v, tri)
 
+    def _align_args(self, where, d16, pose):
+        d16 = np.ascontiguousarray(d16)
+        if d16.ndim != 2 or d16.dtype != np.int16:
+            raise ValueError(f"{where}: the map must be a 2-D int16 array")
+        if pose is not None and np.shape(pose) != (4, 4):
+            raise ValueError(f"{where}: the pose must be a 4 x 4 matrix")
+        return (d16,) + _pose_arg(where, pose)
+
+    def linearize(self, d16, param, pose=None, **params):
+        """viso_tsdf_linearize: the integer normal equations of the frame-to-model alignment (include/viso_hip.h, "TSDF align") of
+        one host int16 map at the 4 x 4 camera-to-world pose (None: the identity).  Returns (N, counters): the symmetric int64
+        [7][7] matrix of the six entries of the rows and the residual, and a dict of n_points, n_used, n_missing, n_gated,
+        n_clipped, n_out_of_range.  params: the fields of tsdf_align_params.  Reads the map only."""
+        d16, T, Tp = self._align_args("TsdfMap.linearize", d16, pose)
+        p, out = tsdf_align_params(**params), np.zeros(1, TSDF_NORMAL_DTYPE)
+        self._chk("viso_tsdf_linearize", self.L.viso_tsdf_linearize(self.h, C.byref(p), ptr(d16, C.c_int16), d16.shape[0], d16.shape[1],
+                                                                    C.byref(param), Tp, out.ctypes.data))
+        return tsdf_normal_matrix(out[0])
+
+    def align(self, d16, param, pose=None, trace=False, **params):
+        """viso_tsdf_align: the pose at which the points of one host int16 map lie on the map's surface, from the guess `pose` (4 x 4,
+        camera to world; None: the identity).  Returns a TSDF_ALIGNMENT_DTYPE record (pose, cov of (v, omega), cost in pixels of
+        disparity, n_used, iters, status: 1 converged, 2 max_iters reached, < 0 failed and pose is the guess).  trace=True: a tuple
+        with the TSDF_ALIGN_STEP_DTYPE array of the linearises (pose, normal), the last one included.  params: the fields of
+        tsdf_align_params.  Reads the map only."""
+        d16, T, Tp = self._align_args("TsdfMap.align", d16, pose)
+        p, rec = tsdf_align_params(**params), np.zeros(1, TSDF_ALIGNMENT_DTYPE)
+        steps = np.zeros(p.max_iters + 1 if trace and 1 <= p.max_iters <= 50 else 0, TSDF_ALIGN_STEP_DTYPE)
+        self._chk("viso_tsdf_align", self.L.viso_tsdf_align(self.h, C.byref(p), ptr(d16, C.c_int16), d16.shape[0], d16.shape[1], C.byref(param),
+                                                            Tp, rec.ctypes.data, steps.ctypes.data if len(steps) else None, len(steps)))
+        if not trace:
+            return rec[0]
+        return rec[0], steps[steps["pose"][:, 3, 3] == 1.0]   # a written step's pose ends in 0 0 0 1
+
     def render(self, param, shape, poses=None, max_depth=40.0, min_weight=2, weights=False, gray=False):
         """viso_tsdf_render: what a camera with the calibration of param (f, cu, cv, base) would see of the map, by ray casting: an
         int16 disparity map in 1/16 px of shape (rows, cols), VISO_DISP_INVALID where the ray meets no surface from its front within
@@ -1340,6 +1396,20 @@ class Batch:
         if T.ndim != 3 or T.shape[1:] != (4, 4) or T.shape[0] != t1 - int(t0):
             raise ValueError("Batch.fuse_tsdf: poses must be [t1 - t0][4][4]")
         self._chk("viso_batch_fuse_tsdf", self.L.viso_batch_fuse_tsdf(self.h, tsdf.h, int(t0), t1, ptr(T, C.c_double)))
+
+    def align_tsdf(self, tsdf, poses, t0=0, t1=None, **params):
+        """viso_batch_align_tsdf: the resident maps of frames t0 .. t1-1 (t1 None: to the last frame) aligned against the TsdfMap, each
+        on its own from the 4 x 4 guess poses[i]; no map is copied to the host.  Returns a TSDF_ALIGNMENT_DTYPE array [t1 - t0], each
+        what TsdfMap.align gives for that map and guess.  params: the fields of tsdf_align_params.  The map must be on this batch's
+        context."""
+        t1 = self.nf if t1 is None else int(t1)
+        T = np.ascontiguousarray(poses, dtype=np.float64)
+        if T.ndim != 3 or T.shape[1:] != (4, 4) or T.shape[0] != t1 - int(t0):
+            raise ValueError("Batch.align_tsdf: poses must be [t1 - t0][4][4]")
+        p, rec = tsdf_align_params(**params), np.zeros(len(T), TSDF_ALIGNMENT_DTYPE)
+        self._chk("viso_batch_align_tsdf", self.L.viso_batch_align_tsdf(self.h, tsdf.h, int(t0), t1, ptr(T, C.c_double), C.byref(p),
+                                                                        rec.ctypes.data))
+        return rec
 
     def run_disparity(self):
         """viso_batch_run_disparity: only the disparity, over the resident images (upload_images_only)."""

@@ -299,6 +299,8 @@ def declare_tsdf(lib):
                                      C.POINTER(C.c_uint32)]
     if hasattr(lib, "viso_tsdf_create_gray"):   # (absent from older builds of the library: VISO_HIP_SO A/B runs)
         declare_tsdf_gray(lib)
+    if hasattr(lib, "viso_tsdf_linearize"):
+        declare_tsdf_align(lib)
 
 
 def declare_tsdf_gray(lib):
@@ -312,6 +314,37 @@ def declare_tsdf_gray(lib):
     lib.viso_tsdf_vertex_gray.argtypes = [vp, vp, C.c_size_t, u8p, szp]
     lib.viso_tsdf_render_gray.argtypes = [vp, C.c_uint32, C.POINTER(Param), C.c_int, C.c_int, C.c_double, f64p, C.c_int, i16p,
                                           C.POINTER(C.c_uint32), u8p]
+
+
+class TsdfAlignParams(C.Structure):
+    """struct viso_tsdf_align_params (include/viso_hip.h, "TSDF align")."""
+    _fields_ = [("min_weight", C.c_uint32), ("gate_voxels", C.c_double), ("max_iters", C.c_int32), ("eps_rot", C.c_double),
+                ("eps_trans", C.c_double), ("min_pixels", C.c_int32)]
+
+    def ok(self, trunc_voxels=8):
+        """The valid ranges of include/viso_hip.h for a map of trunc_voxels."""
+        return (self.min_weight >= 1 and bool(np.isfinite(self.gate_voxels)) and 0 < self.gate_voxels <= trunc_voxels
+                and 1 <= self.max_iters <= 50 and bool(np.isfinite(self.eps_rot)) and self.eps_rot >= 0
+                and bool(np.isfinite(self.eps_trans)) and self.eps_trans >= 0 and self.min_pixels >= 6)
+
+
+TSDF_ALIGN_DEFAULTS = dict(min_weight=2, gate_voxels=1.0, max_iters=10, eps_rot=1e-6, eps_trans=1e-5, min_pixels=200)   # viso_tsdf_align_params_default
+TSDF_NORMAL_COUNTERS = ("n_points", "n_used", "n_missing", "n_gated", "n_clipped", "n_out_of_range")
+# struct viso_tsdf_normal (272 bytes), struct viso_tsdf_alignment (440 bytes), struct viso_tsdf_align_step (400 bytes)
+TSDF_NORMAL_DTYPE = np.dtype([("n", np.int64, (28,))] + [(name, np.uint64) for name in TSDF_NORMAL_COUNTERS])
+TSDF_ALIGNMENT_DTYPE = np.dtype([("pose", np.float64, (4, 4)), ("cov", np.float64, (6, 6)), ("cost", np.float64), ("n_used", np.uint64),
+                                 ("iters", np.int32), ("status", np.int32)])
+TSDF_ALIGN_STEP_DTYPE = np.dtype([("pose", np.float64, (4, 4)), ("normal", TSDF_NORMAL_DTYPE)])
+
+
+def declare_tsdf_align(lib):
+    """Prototypes of the frame-to-model alignment (include/viso_hip.h, "TSDF align")."""
+    i16p, vp, APP = C.POINTER(C.c_int16), C.c_void_p, C.POINTER(TsdfAlignParams)
+    lib.viso_tsdf_align_params_default.restype = None
+    lib.viso_tsdf_align_params_default.argtypes = [APP]
+    lib.viso_tsdf_linearize.argtypes = [vp, APP, i16p, C.c_int, C.c_int, C.POINTER(Param), f64p, vp]
+    lib.viso_tsdf_align.argtypes = [vp, APP, i16p, C.c_int, C.c_int, C.POINTER(Param), f64p, vp, vp, C.c_int]
+    lib.viso_batch_align_tsdf.argtypes = [vp, vp, C.c_int, C.c_int, f64p, APP, vp]
 
 
 class MotionCov(C.Structure):

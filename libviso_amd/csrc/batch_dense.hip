@@ -202,3 +202,16 @@ extern "C" int viso_batch_fuse_tsdf(viso_batch* b, viso_tsdf* t, int t0, int t1,
     return tsdf_fuse_resident(where, t, b->ctx, D.disp + (size_t)t0 * per, per, D.rows, D.cols, t1 - t0, b->sp.f, b->sp.cu, b->sp.cv, b->sp.base, poses,
                               image, 2 * per);
 }
+
+// The resident maps of frames t0 .. t1-1 aligned against a TSDF map of the same context (tsdf_align.hip), each on its own from its
+// guess, with the batch's calibration and no host copy of the maps.  The refusals of viso_batch_fuse_tsdf.
+extern "C" int viso_batch_align_tsdf(viso_batch* b, viso_tsdf* t, int t0, int t1, const double* poses_guess, const viso_tsdf_align_params* params,
+                                     viso_tsdf_alignment* records_out) {
+    const char* where = "viso_batch_align_tsdf";
+    if (!params || !records_out) { viso_set_error("%s: bad argument (non-null parameters and records)", where); return VISO_ERR_ARG; }
+    VISO_TRY(fuse_prelude(where, b, t, t0, t1, poses_guess));
+    const BatchDense& D = b->dense;
+    const size_t per = (size_t)D.rows * D.cols;
+    return tsdf_align_resident(where, t, b->ctx, D.disp + (size_t)t0 * per, per, D.rows, D.cols, t1 - t0, b->sp.f, b->sp.cu, b->sp.cv, b->sp.base,
+                               poses_guess, params, records_out);
+}

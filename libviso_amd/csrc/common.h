@@ -490,6 +490,11 @@ int map_fuse_resident(const char* where, viso_map* m, viso_ctx* c, const int16_t
 int tsdf_is_gray(viso_tsdf* t);
 int tsdf_fuse_resident(const char* where, viso_tsdf* t, viso_ctx* c, const int16_t* disp, size_t mfs, int rows, int cols, int n_frames,
                        double f, double cu, double cv, double base, const double* poses, const uint8_t* image, size_t ifs);
+// tsdf_align.hip: the opt-in frame-to-model alignment (viso_tsdf_align).  tsdf_align_resident: the alignment of n_frames device maps
+// that live on context c against the map, each on its own from poses [n_frames][16]; checks the arguments, the handle and its context
+int tsdf_align_resident(const char* where, viso_tsdf* t, viso_ctx* c, const int16_t* disp, size_t mfs, int rows, int cols, int n_frames,
+                        double f, double cu, double cv, double base, const double* poses, const viso_tsdf_align_params* params,
+                        viso_tsdf_alignment* records);
 // covariance.hip: the opt-in motion covariance (viso_batch_set_covariance); one record per item, out[item], read from the item's
 // X, obs, m_ptr, ld, tr, ok, n_inl, inl (what ransac_refit_kernel left)
 int launch_motion_cov(hipStream_t s, const SolverItem* items_dev, int n_items, const SolverParamsDev& sp, int mode, double sigma,

@@ -36,20 +36,16 @@
 //                                 interpolated with the mesh's t; the vertices without a value counted with one atomic per wave.
 //   tsdf_gray_render_kernel       the render march; a run's head lane also loads gray and hands it to its run (two more
 //                                 ds_bpermute for the 64-bit value).
+// The frame-to-model alignment that reads this table is in tsdf_align.hip (the table's layout: tsdf_table.h).
 // What every table of voxels shares is not here (voxelmap.hip says what): the device side is voxel_hash.h, the host side
 // voxel_host.h.  This file keeps the table's payload and insert, the kernels' own bodies, the parameter and entry checks, the
 // orders of the items and the whole mesh extraction, whose two lists do not fit the shared two passes.
 #include "common.h"
 #include "wave.h"
-#include "voxel_host.h"
+#include "tsdf_table.h"
 
 #include <cmath>
 #include <vector>
-
-struct TsdfTable {
-    VoxelTable head;
-    unsigned long long* sum; uint32_t* weight;   // [slots] i64 (added as u64, two's complement), [slots]
-};
 
 // a gray map's table (include/viso_hip.h, "TSDF intensity"): the same with the sums of the updates' 8-bit intensities
 struct TsdfGrayTable {
@@ -575,6 +571,11 @@ struct viso_tsdf {
 };
 
 static VoxelRegistry g_tsdfs = {{"TSDF", "TSDF map", "updates", "min_weight", "viso_tsdf_clear"}};
+
+VoxelRegistry& tsdf_registry() { return g_tsdfs; }
+void tsdf_view(viso_tsdf* t, TsdfView* out) {
+    out->t = t->t; out->voxel = t->p.voxel; out->s = t->s; out->trunc_voxels = t->p.trunc_voxels;
+}
 
 static bool tsdf_params_ok(const viso_tsdf_params* p) {
     return p && std::isfinite(p->voxel) && p->voxel > 0.0 && p->trunc_voxels >= 1 && p->trunc_voxels <= 8 && p->min_disp16 >= 1 &&

@@ -45,6 +45,9 @@ using VoxelLaunch = std::function<void(hipStream_t)>;                           
 using VoxelFuseLaunch = std::function<void(const VoxelFuseArgs&, const uint8_t* d_image, dim3 grid, hipStream_t)>;
 // one group of views; d_gray: the group's part of the third output, or null when the call has none
 using VoxelRenderLaunch = std::function<void(const double* d_poses, int16_t* d_disp, uint32_t* d_weight, uint8_t* d_gray, dim3 grid, hipStream_t)>;
+// one group of frames of a linearise: the group's poses [.][12], its flags and its part of the sums, the group's first frame
+using VoxelLinearizeLaunch = std::function<void(const double* d_poses, const unsigned long long* d_active, unsigned long long* d_out, int frame0,
+                                                dim3 grid, hipStream_t)>;
 using VoxelEntriesLaunch = std::function<void(const void* d_entries, dim3 grid, hipStream_t)>;   // add_entries
 
 bool voxel_known(VoxelRegistry& reg, const void* handle);
@@ -82,6 +85,14 @@ int voxel_add_entries(const char* where, VoxelRegistry& reg, const void* handle,
 // the buffer; the copies to the host.
 int voxel_render(const char* where, VoxelRegistry& reg, const void* handle, size_t px, const double* poses, int n_views, int16_t* disp_out,
                  uint32_t* weight_out, const VoxelRenderLaunch& launch, uint8_t* gray_out = nullptr);
+// A host map of px pixels into the fuse's staging d_disp (grow-only), on the stream; *d_disp: where it is.  h is entered and locked.
+int voxel_stage_map(const char* where, VoxelHost* h, const int16_t* disp, size_t px, const int16_t** d_disp);
+// One linearise of an alignment (include/viso_hip.h, "TSDF align") for n frames: h is entered, locked and not overflowed (the
+// caller holds the lock over the whole alignment).  The poses [n][16] as [n][12], the flags active [n] (0: the frame's lanes
+// leave at once) and `words` zeroed 64-bit sums a frame go through d_pose (grow-only), the groups of frames are started by `launch`
+// with blocks_x blocks along x, and the sums come back to out [n][words].
+int voxel_linearize(const char* where, VoxelHost* h, const double* poses, const unsigned long long* active, int n, size_t words,
+                    unsigned blocks_x, unsigned long long* out, const VoxelLinearizeLaunch& launch);
 // viso_*_stats: the four counters summed over the sets (VOXEL_ST_*) and the dropped word
 int voxel_stats(const char* where, VoxelRegistry& reg, const void* handle, const void* out, unsigned long long sums[4], unsigned long long* dropped);
 

@@ -1,6 +1,6 @@
 // voxel_host.hip — the host side of the shared table layer (voxel_host.h): the registry of live handles, the life of a table, the
 // staging (the map, the poses and, where a kind fuses one, the image) and the group loop of a fuse, the scaffold of add_entries, the
-// pass of an extraction, the staging and the output buffer of a render and the read-back of the statistics.
+// pass of an extraction, the staging and the output buffer of a render, the staging and the sums of a linearise and the read-back of the statistics.
 // No kernel is here: every kind passes its launches in.
 #include "voxel_host.h"
 
@@ -299,6 +299,42 @@ int voxel_render(const char* where, VoxelRegistry& reg, const void* handle, size
     if (e == hipSuccess && d_gray) e = hipMemcpyAsync(gray_out, d_gray, n, hipMemcpyDeviceToHost, s);
     const hipError_t e_wait = hipStreamSynchronize(s);   // nothing in flight touches the buffer that is freed next
     (void)hipFree(d);   // on every path
+    HIP_TRY(e);
+    HIP_TRY(e_wait);
+    return VISO_OK;
+}
+
+int voxel_stage_map(const char* where, VoxelHost* h, const int16_t* disp, size_t px, const int16_t** d_disp) {
+    hipStream_t s = h->ctx->stream;
+    int r;
+    if ((r = voxel_grow(where, &h->d_disp, &h->d_disp_bytes, px * sizeof(int16_t), s)) < 0) return r;
+    HIP_TRY(hipMemcpyAsync(h->d_disp, disp, px * sizeof(int16_t), hipMemcpyHostToDevice, s));
+    *d_disp = h->d_disp;
+    return VISO_OK;
+}
+
+int voxel_linearize(const char* where, VoxelHost* h, const double* poses, const unsigned long long* active, int n, size_t words,
+                    unsigned blocks_x, unsigned long long* out, const VoxelLinearizeLaunch& launch) {
+    hipStream_t s = h->ctx->stream;
+    int r;
+    // one block: poses [n][12] | active [n] | sums [n][words], all 8-byte words; the first two staged with one copy
+    std::vector<double> stage((size_t)n * 13);
+    for (int k = 0; k < n; ++k) std::copy(poses + (size_t)k * 16, poses + (size_t)k * 16 + 12, stage.begin() + (size_t)k * 12);
+    std::copy(active, active + n, reinterpret_cast<unsigned long long*>(stage.data() + (size_t)n * 12));
+    const size_t b_stage = stage.size() * sizeof(double), b_out = (size_t)n * words * sizeof(unsigned long long);
+    if ((r = voxel_grow(where, &h->d_pose, &h->d_pose_bytes, b_stage + b_out, s)) < 0) return r;
+    const double* d_poses = h->d_pose;
+    const unsigned long long* d_active = reinterpret_cast<const unsigned long long*>(h->d_pose + (size_t)n * 12);
+    unsigned long long* d_out = reinterpret_cast<unsigned long long*>(h->d_pose + (size_t)n * 13);
+    hipError_t e = hipMemcpyAsync(h->d_pose, stage.data(), b_stage, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemsetAsync(d_out, 0, b_out, s);
+    for (int f0 = 0; f0 < n && e == hipSuccess; f0 += VOXEL_GROUP) {
+        const int nf = n - f0 < VOXEL_GROUP ? n - f0 : VOXEL_GROUP;
+        launch(d_poses + (size_t)f0 * 12, d_active + f0, d_out + (size_t)f0 * words, f0, dim3(blocks_x, (unsigned)nf), s);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, b_out, hipMemcpyDeviceToHost, s);
+    const hipError_t e_wait = hipStreamSynchronize(s);   // the copies read `stage` and write `out`
     HIP_TRY(e);
     HIP_TRY(e_wait);
     return VISO_OK;

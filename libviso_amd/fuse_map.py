@@ -1,5 +1,6 @@
 """python -m libviso_amd.fuse_map DISPARITY_DIR POSES.txt CALIB.txt OUT.ply [--voxel V --min-count N --min-disp PX --frames B E]
-                                 [--surface | --mesh [--trunc T --min-weight N] [--render DIR [--render-depth M]] [--gray IMAGE_DIR]]
+                                 [--surface | --mesh [--trunc T --min-weight N] [--render DIR [--render-depth M]] [--gray IMAGE_DIR]
+                                                     [--align [--aligned-poses FILE --align-voxel-gate G]]]
 
 Fuses the maps a KITTI runner wrote with --disparity DIR and the poses of its pose file into one voxel map on the device
 (libviso_amd.VoxelMap; include/viso_hip.h, "voxel map") and writes the occupied voxels as a binary PLY point cloud: x, y, z the
@@ -24,6 +25,12 @@ float32 centroid of each voxel, count the number of points fused into it.
                  intensity").  IMAGE_DIR holds 8-bit grayscale PNGs with the maps' names and sizes (KITTI's image_0).  The PLY's
                  vertices then carry the surface's intensity as red = green = blue after weight, and --render also writes
                  DIR/gray/<name> as 8-bit PNGs, the intensity of every rendered pixel (0 where the map is invalid).
+  --align        with --surface or --mesh: track, then fuse (include/viso_hip.h, "TSDF align").  The first map is fused at its pose;
+                 every later map i is first aligned against the model fused so far, from the guess aligned(i-1) pose(i-1)^-1 pose(i)
+                 (the file's motion applied to the previous map's aligned pose), and fused at the aligned pose when the alignment
+                 ends with status >= 1, otherwise at that guess.  --align-voxel-gate G: the gate in voxels (1.0, at most --trunc);
+                 --min-weight applies to the voxels the alignment reads.  --aligned-poses FILE: the poses the maps were fused at, in
+                 the format of POSES.txt.  The statuses are counted in the tool's output.
 
 Both runners write byte-identical directories and pose files for every rank count and chunk size, so the PLY is identical too."""
 import argparse
@@ -177,6 +184,14 @@ def read_poses(path):
     return np.array(out).reshape(-1, 4, 4)
 
 
+def write_poses(path, poses):
+    """A KITTI pose file: the first three rows of every pose, 12 numbers a line, each written so that it reads back to the same
+    double."""
+    with open(path, "w") as f:
+        for T in np.asarray(poses, np.float64).reshape(-1, 4, 4):
+            f.write(" ".join("%.17g" % v for v in T[:3].reshape(-1)) + "\n")
+
+
 def read_calib(path):
     """(f, cu, cv, base) from calib.txt's P0 and P1, as the runners take them."""
     P = {}
@@ -212,7 +227,14 @@ def main(argv=None):
     ap.add_argument("--render", metavar="DIR", help="with --surface or --mesh: also write the model rendered at every fused pose into DIR")
     ap.add_argument("--render-depth", type=float, default=40.0, metavar="M", help="with --render: how far a ray is followed, metres (40)")
     ap.add_argument("--gray", metavar="IMAGE_DIR", help="with --surface or --mesh: fuse the 8-bit left images of the maps' names with them")
+    ap.add_argument("--align", action="store_true", help="with --surface or --mesh: align every map against the model before it is fused")
+    ap.add_argument("--aligned-poses", metavar="FILE", help="with --align: write the poses the maps were fused at")
+    ap.add_argument("--align-voxel-gate", type=float, default=1.0, metavar="G", help="with --align: the gate in voxels (1.0)")
     a = ap.parse_args(argv)
+    if a.align and not (a.surface or a.mesh):
+        ap.error("--align needs --surface or --mesh (only a TSDF map is aligned against)")
+    if a.aligned_poses and not a.align:
+        ap.error("--aligned-poses needs --align")
     if a.render and not (a.surface or a.mesh):
         ap.error("--render needs --surface or --mesh (only a TSDF map is rendered)")
     if a.gray and not (a.surface or a.mesh):
@@ -233,6 +255,7 @@ def main(argv=None):
                                    capacity_log2=26 if a.capacity_log2 is None else a.capacity_log2)
         try:
             shape = None
+            used, statuses = [], {}   # --align: the poses the maps were fused at, and how the alignments ended
             for i in range(b, e):
                 m = read_disparity_png(os.path.join(a.disparity_dir, names[i]))
                 shape = shape or m.shape
@@ -242,10 +265,25 @@ def main(argv=None):
                     image = read_png8(os.path.join(a.gray, names[i]))
                     if image.shape != m.shape:
                         sys.exit(f"fuse_map: {names[i]} is {image.shape[1]} x {image.shape[0]} in {a.gray} but its map is {m.shape[1]} x {m.shape[0]}")
-                    tsdf.fuse(m, prm, pose=poses[i], image=image)
+                pose = poses[i]
+                if a.align and used:
+                    pose = used[-1] @ np.linalg.inv(poses[i - 1]) @ poses[i]
+                    rec = tsdf.align(m, prm, pose, min_weight=a.min_weight, gate_voxels=a.align_voxel_gate)
+                    statuses[int(rec["status"])] = statuses.get(int(rec["status"]), 0) + 1
+                    if rec["status"] >= 1:
+                        pose = rec["pose"].copy()
+                used.append(pose)
+                if gray:
+                    tsdf.fuse(m, prm, pose=pose, image=image)
                 else:
-                    tsdf.fuse(m, prm, pose=poses[i])
+                    tsdf.fuse(m, prm, pose=pose)
             st = tsdf.stats()
+            if a.align:
+                if a.aligned_poses:
+                    write_poses(a.aligned_poses, used)
+                print(f"fuse_map: {max(0, e - b - 1)} maps aligned before they were fused (status: count " +
+                      ", ".join(f"{k}: {v}" for k, v in sorted(statuses.items())) + ")" + (f" -> {a.aligned_poses}" if a.aligned_poses else ""))
+                poses = np.array(list(poses[:b]) + used + list(poses[e:])).reshape(-1, 4, 4)   # --render sees the model from where it was fused
             if a.render and e > b:
                 os.makedirs(os.path.join(a.render, "gray") if gray else a.render, exist_ok=True)
                 n_near = 0

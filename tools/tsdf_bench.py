@@ -22,8 +22,13 @@ repetitions):
   vertex_gray  TsdfMap.vertex_gray of the gray map's mesh vertices: the copy up, two probes a vertex, the copy back;
   render_gray  TsdfMap.render(gray=True) of the same views over the gray map: beside `render`, one more 8-byte load a probe and one
                more byte a pixel out.
+  align        (include/viso_hip.h, "TSDF align") Batch.align_tsdf of the first --align-frames (16) resident maps against the table, each
+               from its fusing pose moved by 0.2 degrees and 2 cm, min_weight 2, gate 1 voxel: `linearize`, the call with max_iters 1
+               (two rounds of one launch each: time per round and per frame and round), and `align`, the call with max_iters 10
+               (its rounds: the largest iteration count + 1, from the records).  The yardstick is `render` of the same views in the
+               same process (`render_same`): a linearise does eight probes a pixel where a render marches 50..120.
 n_updates / n_points from viso_tsdf_stats is the number of voxels a pixel's band touches.  --kernel-only runs clear + fuse_tsdf
---reps times and the extractions and the render once: the run to put under `rocprofv3 --kernel-trace --stats` for the kernels' own times.  The
+--reps times, the extractions and the render once and the two align calls --reps times: the run to put under `rocprofv3 --kernel-trace --stats` for the kernels' own times.  The
 count the result is held against (not a measurement) is printed with it."""
 import argparse
 import json
@@ -54,6 +59,7 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--capacity-log2", type=int, default=26)
     ap.add_argument("--render-views", type=int, default=16)
+    ap.add_argument("--align-frames", type=int, default=16)
     ap.add_argument("--kernel-only", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -101,6 +107,16 @@ def main():
         zs = seq["param"].f * seq["param"].base / (np.where(valid, d16, 16).astype(np.float64) / 16.0)
         return int(np.where(valid, np.minimum(np.ceil(zs / h), N), N).sum()), float(valid.mean())
 
+    has_align = hasattr(libviso_amd.load(), "viso_tsdf_linearize")   # (absent from older builds of the library: VISO_HIP_SO A/B runs)
+    na = max(1, min(a.align_frames, nf))
+    guesses = np.array([poses[t] @ hostmath.tr2mat([0.002, -0.002, 0.002, 0.012, -0.01, 0.012]) for t in range(na)])
+
+    def align(max_iters):
+        return b.align_tsdf(tsdf, guesses, t0=0, t1=na, max_iters=max_iters)
+
+    def render_same():
+        return tsdf.render(seq["param"], (rows, cols), poses[:na], max_depth=40.0, min_weight=2)
+
     if a.kernel_only:
         ms = []
         for _ in range(a.reps):
@@ -108,6 +124,8 @@ def main():
             ms.append(clock(lambda: b.fuse_tsdf(tsdf, poses)))
         res = {"frames": nf, "fuse_tsdf_ms": ms, "voxels": int(len(tsdf.entries())), "crossings": int(len(tsdf.surface())),
                "triangles": int(len(tsdf.mesh()[1])), "render_views": int(len(views)), "render_valid": marched(render())[1]}
+        if has_align:
+            res["align_ms"] = [[clock(lambda: align(1)), clock(lambda: align(10))] for _ in range(a.reps)]
         print(json.dumps(res))
         tsdf.close(); b.close(); ctx.close()
         return
@@ -127,7 +145,10 @@ def main():
         vmap.clear(); b.fuse_disparities(vmap, poses)
         if has_gray:
             gmap.clear(); b.fuse_tsdf(gmap, poses); gmap.vertex_gray(gverts); render_gray()
-    legs = {k: [] for k in ("fuse_tsdf", "fuse_map", "entries", "surface", "mesh", "render", "clear") + (("fuse_gray", "vertex_gray", "render_gray") if has_gray else ())}
+        if has_align:
+            align(1); align(10); render_same()
+    legs = {k: [] for k in ("fuse_tsdf", "fuse_map", "entries", "surface", "mesh", "render", "clear") + (("fuse_gray", "vertex_gray", "render_gray") if has_gray else ())
+            + (("linearize", "align", "render_same") if has_align else ())}
     for _ in range(a.reps):   # alternating
         legs["clear"].append(clock(tsdf.clear))
         legs["fuse_tsdf"].append(clock(lambda: b.fuse_tsdf(tsdf, poses)))
@@ -142,6 +163,10 @@ def main():
             legs["fuse_gray"].append(clock(lambda: b.fuse_tsdf(gmap, poses)))
             legs["vertex_gray"].append(clock(lambda: gmap.vertex_gray(gverts)))
             legs["render_gray"].append(clock(render_gray))
+        if has_align:
+            legs["linearize"].append(clock(lambda: align(1)))
+            legs["align"].append(clock(lambda: align(10)))
+            legs["render_same"].append(clock(render_same))
     st, n_vox, n_cross = tsdf.stats(), len(tsdf.entries()), len(tsdf.surface())
     n_vert, n_tri = (len(x) for x in tsdf.mesh())
     res = {"frames": nf, "shape": [int(rows), int(cols)], "params": "voxel 0.2, T 3, min_disp16 16", "capacity_log2": log2, "reps": a.reps,
@@ -154,6 +179,15 @@ def main():
     ms = res["ms_median"]["render"]
     res["render"] = {"views": int(len(views)), "max_depth": 40.0, "min_weight": 2, "valid": valid, "ms_per_view": ms / len(views),
                      "samples_marched": n_marched, "samples_per_s": n_marched / (ms * 1e-3)}
+    if has_align:
+        r1, r10, med = align(1), align(10), res["ms_median"]
+        rounds1, rounds10 = int(r1["iters"].max()) + 1, int(r10["iters"].max()) + 1
+        res["align"] = {"frames": na, "min_weight": 2, "gate_voxels": 1.0, "status_max_iters_1": [int(v) for v in r1["status"]],
+                        "status": [int(v) for v in r10["status"]], "iters": [int(v) for v in r10["iters"]],
+                        "n_used_share": float(r10["n_used"].mean() / (rows * cols)), "rounds_max_iters_1": rounds1, "rounds": rounds10,
+                        "ms_per_round_max_iters_1": med["linearize"] / rounds1, "ms_per_frame_and_round": med["linearize"] / rounds1 / na,
+                        "ms_per_align_call": med["align"], "ms_per_round": med["align"] / rounds10,
+                        "render_same_ms_per_view": med["render_same"] / na}
     if has_gray:
         res["gray"] = {"vertices": int(len(gverts)), "same_geometry": bool(gmap.entries().tobytes() == tsdf.entries().tobytes()),
                        "ratio_to_plain": {g: res["ms_median"][g] / res["ms_median"][p] for g, p in (("fuse_gray", "fuse_tsdf"), ("render_gray", "render"))}}
