@@ -878,7 +878,7 @@ int viso_batch_get_disparity_points(viso_batch* b, int t, const double* pose_or_
  * finds no slot increments n_dropped; a call that ends with n_dropped > 0 returns VISO_ERR_NOMEM and marks the map overflowed
  * (which points were dropped depends on scheduling), and viso_map_count / viso_map_get / viso_map_add_entries / the fuse calls
  * then refuse with VISO_ERR_NOMEM until viso_map_clear, after which the map is fully usable again.
- * Out of scope: RGB (a TSDF map can carry one 8-bit intensity: "TSDF intensity" below), eviction of far voxels, fusing inside the KITTI runners while their chunks drain (a surface form is the
+ * Out of scope: RGB (a TSDF map can carry one 8-bit intensity: "TSDF intensity" below), fusing inside the KITTI runners while their chunks drain (a surface form is the
  * TSDF map below).
  * HIP kernels (voxelmap.hip): map_fuse_kernel (one thread per pixel of a group of frames; lanes that continue the key of the lane
  * to their left form a run, the run heads come from one ballot, the runs' sums from a wave scan, and only a run's head probes the
@@ -969,7 +969,7 @@ int viso_map_entry_centroid(const viso_map_entry* entry, double voxel, float out
  * VISO_ERR_NOMEM and marks the map overflowed, and every getter, viso_tsdf_add_entries and every fuse call then refuse with
  * VISO_ERR_NOMEM until viso_tsdf_clear.  Every probe loop, the read-only lookups of the extraction included, visits each slot at
  * most once and advances strictly.
- * Out of scope: RGB (one 8-bit intensity: "TSDF intensity" below), carving free space beyond the truncation band, weights that fall with depth, eviction, fusing inside the
+ * Out of scope: RGB (one 8-bit intensity: "TSDF intensity" below), carving free space beyond the truncation band, weights that fall with depth, fusing inside the
  * KITTI runners, the sort on the device.
  * HIP kernels (tsdf.hip): tsdf_fuse_kernel (one thread per pixel of a group of frames; the loop over j is uniform across the wave,
  * and per j the lanes that continue the voxel of the lane to their left form a run whose head lane alone probes the table and
@@ -1313,6 +1313,51 @@ int viso_tsdf_align(viso_tsdf* t, const viso_tsdf_align_params* params, const in
 /* poses_guess: [t1 - t0][16]; records_out: [t1 - t0]. */
 int viso_batch_align_tsdf(viso_batch* b, viso_tsdf* t, int t0, int t1, const double* poses_guess, const viso_tsdf_align_params* params,
                           viso_tsdf_alignment* records_out);
+
+/* ------------------------------------------------ Map eviction: the voxels outside a box leave a map, on the device (opt-in; NOT in
+ * the reference)
+ *
+ * A voxel map or a TSDF map (plain or gray) lets go of every voxel outside an axis-aligned box of voxel indices and hands those
+ * voxels back, so that a bounded table follows a camera over any distance.  The maps are integer and additive: the voxels evicted
+ * along the way, merged by key with what is still in the table, are the map that was never evicted, bit for bit.
+ *   What leaves: viso_*_evict removes every occupied voxel (count / weight >= 1) outside `keep` and nothing else; every surviving
+ *     voxel keeps its count / weight, its sum(s) and its gray sum.
+ *   What comes back: *n = the number removed; evicted_out receives them sorted by key, ascending, in the kind's own entry type,
+ *     exactly as viso_*_get would have listed them before the call.  evicted_out == NULL discards them and ignores n_cap.  With a
+ *     non-NULL output and n_cap < *n the call returns VISO_ERR_ARG with *n set, nothing written and nothing removed (the getters'
+ *     rule).  viso_*_evict_count reads only.
+ *   The box: voxel k is inside when lo[i] <= k[i] < hi[i] on every axis.  lo[i] > hi[i]: VISO_ERR_ARG.  lo[i] == hi[i] on any axis is
+ *     an empty box: everything leaves and the table ends empty.  Values beyond +-2^20 are legal and contain everything on that side.
+ *     viso_voxel_box_around (host only), per axis in IEEE double in this operand order: lo = (int64) floor((c - r) / voxel),
+ *     hi = (int64) floor((c + r) / voxel) + 1, each clamped to int32; VISO_ERR_ARG for a centre, r or voxel that is not finite,
+ *     r < 0, voxel not > 0, a null pointer.
+ *   Kinds: viso_tsdf_evict on a gray map and viso_tsdf_evict_gray on a plain one return VISO_ERR_ARG; viso_tsdf_evict_count takes
+ *     either kind.
+ *   Counters: n_occupied falls by *n; every other counter is a history of what was fused and stays.
+ *   Capacity comes back: after the call the table is as if the removed voxels had never been inserted: every survivor is found by
+ *     the probes, no key is in the table twice, and every freed slot is an empty slot that the next insert can claim.  Nothing
+ *     like a tombstone outlives the call.
+ *   Refusals: an overflowed map refuses with VISO_ERR_NOMEM, like the getters; the handle rules of the maps apply; all argument
+ *     checks (handle, kind, box, n) happen before a device is touched.
+ *   Bounded loops: every loop on the device advances strictly and ends at the latest after one round of the slots (a bad table is
+ *     a wrong answer, never a hang).
+ * Device memory of a call: the list of the evicted voxels (none when they are discarded).  One exception: a table without a single
+ * empty slot (exactly 2^capacity_log2 voxels, none dropped) is rebuilt through a list of its survivors.
+ * Out of scope: growing or rehashing a table, un-overflowing a map, eviction by age or weight, eviction inside the batch's fuse
+ * launches or the KITTI runners.
+ * HIP kernels (voxel_hash.h, templates over the kind's payload, one thread per slot each): voxel_evict_mark_kernel counts, then lists
+ * the voxels outside the box (one atomic per wave) and turns their keys into a reserved tombstone value; voxel_evict_rebuild_kernel
+ * walks every probe cluster from its first slot and puts each live entry back at the first tombstone at or after its home slot;
+ * voxel_evict_sweep_kernel turns the tombstones into empty slots and zeroes their payload.  The sort runs on the host. */
+typedef struct viso_voxel_box { int32_t lo[3], hi[3]; } viso_voxel_box;   /* voxel k is inside when lo[i] <= k[i] < hi[i], i = 0, 1, 2 */
+
+/* The box of the voxels that a cube of half-side half_side (metres) around centre touches.  Host only. */
+int viso_voxel_box_around(const double centre[3], double half_side, double voxel, viso_voxel_box* out);
+int viso_map_evict_count(viso_map* m, const viso_voxel_box* keep, size_t* n);
+int viso_map_evict(viso_map* m, const viso_voxel_box* keep, viso_map_entry* evicted_out, size_t n_cap, size_t* n);
+int viso_tsdf_evict_count(viso_tsdf* t, const viso_voxel_box* keep, size_t* n);
+int viso_tsdf_evict(viso_tsdf* t, const viso_voxel_box* keep, viso_tsdf_entry* evicted_out, size_t n_cap, size_t* n);
+int viso_tsdf_evict_gray(viso_tsdf* t, const viso_voxel_box* keep, viso_tsdf_gray_entry* evicted_out, size_t n_cap, size_t* n);
 
 #ifdef __cplusplus
 }

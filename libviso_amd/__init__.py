@@ -21,7 +21,7 @@ from .abi import (DESC_LEN, MAP_DEFAULTS, MAP_ENTRY_DTYPE, MapCounters, MapParam
                   declare_sgm, declare_speckle, declare_subpixel, declare_window, f32p, f64p, i32p, i64p, intp, ptr,
                   TSDF_CROSSING_DTYPE, TSDF_DEFAULTS, TSDF_ENTRY_DTYPE, TSDF_GRAY_ENTRY_DTYPE, TSDF_MESH_VERTEX_DTYPE, TsdfCounters, TsdfParams,
                   declare_tsdf, TSDF_ALIGN_DEFAULTS, TSDF_ALIGN_STEP_DTYPE, TSDF_ALIGNMENT_DTYPE, TSDF_NORMAL_COUNTERS, TSDF_NORMAL_DTYPE,
-                  TsdfAlignParams)
+                  TsdfAlignParams, VoxelBox, declare_evict)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("VISO_HIP_SO") or os.path.join(_HERE, "libviso_hip.so")   # VISO_HIP_SO: another build of the library (A/B runs)
@@ -137,6 +137,8 @@ def load():
         declare_map(L)
     if hasattr(L, "viso_tsdf_create"):
         declare_tsdf(L)
+    if hasattr(L, "viso_map_evict"):
+        declare_evict(L)
     L.viso_harris_response.argtypes = [C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_double, f32p]
     L.viso_detect_harris_binned.argtypes = [C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                             C.c_double, f32p, f32p, intp]
@@ -646,6 +648,54 @@ def write_map_ply(path, entries, voxel):
         f.write(data)
 
 
+def voxel_box(centre, half_side, voxel):
+    """viso_voxel_box_around: (lo, hi), two int32 [3] arrays, the box of the voxels of edge `voxel` that a cube of half-side
+    half_side around centre touches: voxel k is inside when lo <= k < hi on every axis (include/viso_hip.h, "Map eviction")."""
+    c = np.ascontiguousarray(centre, dtype=np.float64)
+    if c.shape != (3,):
+        raise ValueError("voxel_box: the centre must have 3 entries")
+    b = VoxelBox()
+    r = load().viso_voxel_box_around(ptr(c, C.c_double), float(half_side), float(voxel), C.byref(b))
+    if r != 1:
+        _err("viso_voxel_box_around", r)
+    return np.array(b.lo, np.int32), np.array(b.hi, np.int32)
+
+
+def _box_arg(where, box):
+    lo, hi = box
+    lo, hi = np.asarray(lo), np.asarray(hi)
+    if lo.shape != (3,) or hi.shape != (3,):
+        raise ValueError(f"{where}: the box is (lo, hi) with 3 entries each")
+    i32 = np.iinfo(np.int32)
+    if any(int(v) != v or not i32.min <= int(v) <= i32.max for v in (*lo, *hi)):
+        raise ValueError(f"{where}: the box's entries must be int32 values")
+    return VoxelBox((C.c_int32 * 3)(*map(int, lo)), (C.c_int32 * 3)(*map(int, hi)))
+
+
+def merge_entries(*parts):
+    """The sum of maps given as entry arrays of one dtype (MAP_ENTRY_DTYPE, TSDF_ENTRY_DTYPE or TSDF_GRAY_ENTRY_DTYPE): every field
+    but k summed by key, sorted by key.  Host only; what add_entries does on the device, so the entries that evict handed back
+    (an archive) merged with a map's live entries are the map that was never evicted."""
+    if not parts:
+        raise ValueError("merge_entries: at least one entry array")
+    dtype = np.asarray(parts[0]).dtype
+    if dtype not in (MAP_ENTRY_DTYPE, TSDF_ENTRY_DTYPE, TSDF_GRAY_ENTRY_DTYPE):
+        raise ValueError("merge_entries: not an entry dtype of a map")
+    if any(np.asarray(p).dtype != dtype for p in parts):
+        raise ValueError("merge_entries: the parts must share one dtype")
+    e = np.concatenate([np.asarray(p).reshape(-1) for p in parts])
+    k = e["k"].astype(np.int64) + (1 << 20)
+    keys, inv = np.unique((k[:, 0] << 42) | (k[:, 1] << 21) | k[:, 2], return_inverse=True)
+    out = np.zeros(len(keys), dtype)
+    for i in range(3):
+        out["k"][:, i] = ((keys >> (21 * (2 - i))) & 0x1fffff) - (1 << 20)
+    for name in dtype.names[1:]:
+        acc = np.zeros(out[name].shape, out[name].dtype)
+        np.add.at(acc, inv.reshape(-1), e[name])
+        out[name] = acc
+    return out
+
+
 def tsdf_params(**params):
     """viso_tsdf_params: viso_tsdf_params_default with the given fields (voxel in metres, trunc_voxels, min_disp16 in 1/16 px,
     capacity_log2) replaced.  Needs no library: the ranges are checked by viso_tsdf_create (TsdfParams.ok restates them)."""
@@ -988,6 +1038,34 @@ class _TableMap:
         self._chk(self._prefix + get_name, self._c(get_name)(self.h, int(threshold), out.ctypes.data, len(out), C.byref(n)))
         return out[:n.value]
 
+    def _evict_dtype(self):
+        return self._ENTRY_DTYPE
+
+    def evict_count(self, box):
+        """viso_map_evict_count / viso_tsdf_evict_count: the number of voxels outside box = (lo, hi); reads only."""
+        where = type(self).__name__ + ".evict_count"
+        n = C.c_size_t()
+        self._chk(self._prefix + "evict_count", self._c("evict_count")(self.h, C.byref(_box_arg(where, box)), C.byref(n)))
+        return n.value
+
+    def evict(self, box, discard=False):
+        """viso_map_evict / viso_tsdf_evict / viso_tsdf_evict_gray: every voxel outside box = (lo, hi) (voxel_box makes one around
+        a point) leaves the map, on the device, and its slot is free again.  Returns the evicted voxels as an array of the map's
+        own entry dtype (a gray map's: TSDF_GRAY_ENTRY_DTYPE), sorted by key; merge_entries of them and of what the map holds
+        later is the map that was never evicted.  discard=True: they are dropped on the device, and their number comes back."""
+        where = type(self).__name__ + ".evict"
+        b = _box_arg(where, box)
+        dtype = self._evict_dtype()
+        name = "evict_gray" if dtype == TSDF_GRAY_ENTRY_DTYPE else "evict"
+        n = C.c_size_t()
+        if discard:
+            self._chk(self._prefix + name, self._c(name)(self.h, C.byref(b), None, 0, C.byref(n)))
+            return n.value
+        self._chk(self._prefix + "evict_count", self._c("evict_count")(self.h, C.byref(b), C.byref(n)))
+        out = np.zeros(n.value, dtype)
+        self._chk(self._prefix + name, self._c(name)(self.h, C.byref(b), out.ctypes.data, len(out), C.byref(n)))
+        return out[:n.value]
+
     def stats(self):
         """viso_map_stats / viso_tsdf_stats as a dict of the counters' fields."""
         c = self._Counters()
@@ -1089,6 +1167,9 @@ class TsdfMap(_TableMap):
             return super().add_entries(entries)
         entries = np.ascontiguousarray(entries)
         self._chk("viso_tsdf_add_gray_entries", self.L.viso_tsdf_add_gray_entries(self.h, entries.ctypes.data, len(entries)))
+
+    def _evict_dtype(self):
+        return TSDF_GRAY_ENTRY_DTYPE if self.gray else TSDF_ENTRY_DTYPE
 
     def entries(self, min_weight=1, gray=False):
         """viso_tsdf_get: the voxels with at least min_weight updates as a TSDF_ENTRY_DTYPE array (k, weight, sum), sorted by key.

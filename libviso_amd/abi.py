@@ -249,6 +249,21 @@ def declare_map(lib):
     lib.viso_map_entry_centroid.argtypes = [vp, C.c_double, f32p]
 
 
+class VoxelBox(C.Structure):
+    """struct viso_voxel_box (include/viso_hip.h, "Map eviction")."""
+    _fields_ = [("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3)]
+
+
+def declare_evict(lib):
+    """Prototypes of the maps' eviction (include/viso_hip.h, "Map eviction")."""
+    vp, szp, BP = C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(VoxelBox)
+    lib.viso_voxel_box_around.argtypes = [f64p, C.c_double, C.c_double, BP]
+    for kind in ("map", "tsdf"):
+        getattr(lib, f"viso_{kind}_evict_count").argtypes = [vp, BP, szp]
+        getattr(lib, f"viso_{kind}_evict").argtypes = [vp, BP, vp, C.c_size_t, szp]
+    lib.viso_tsdf_evict_gray.argtypes = [vp, BP, vp, C.c_size_t, szp]
+
+
 class TsdfParams(C.Structure):
     """struct viso_tsdf_params (include/viso_hip.h, "TSDF map")."""
     _fields_ = [("voxel", C.c_double), ("trunc_voxels", C.c_int32), ("min_disp16", C.c_int32), ("capacity_log2", C.c_int32)]

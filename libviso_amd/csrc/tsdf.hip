@@ -561,6 +561,38 @@ __global__ __launch_bounds__(256) void tsdf_gray_clear_kernel(TsdfGrayTable g) {
     g.gray[slot] = 0ull;
 }
 
+// the payloads of a slot for the eviction's kernels (voxel_hash.h): a plain map's and a gray map's
+struct TsdfPayload {
+    TsdfTable t;
+    using Entry = viso_tsdf_entry;
+    __device__ __forceinline__ void pack(uint32_t slot, unsigned long long key, Entry* v) const {
+        voxel_unkey(key, v->k);
+        v->weight = t.weight[slot];
+        v->sum = (long long)t.sum[slot];
+    }
+    __device__ __forceinline__ void zero(uint32_t a) const { t.weight[a] = 0u; t.sum[a] = 0ull; }
+    __device__ __forceinline__ void move(uint32_t a, uint32_t b) const {
+        t.weight[b] = t.weight[a]; t.sum[b] = t.sum[a];
+        zero(a);
+    }
+};
+
+struct TsdfGrayPayload {
+    TsdfGrayTable g;
+    using Entry = viso_tsdf_gray_entry;
+    __device__ __forceinline__ void pack(uint32_t slot, unsigned long long key, Entry* v) const {
+        voxel_unkey(key, v->k);
+        v->weight = g.t.weight[slot];
+        v->sum = (long long)g.t.sum[slot];
+        v->gray = g.gray[slot];
+    }
+    __device__ __forceinline__ void zero(uint32_t a) const { g.t.weight[a] = 0u; g.t.sum[a] = 0ull; g.gray[a] = 0ull; }
+    __device__ __forceinline__ void move(uint32_t a, uint32_t b) const {
+        g.t.weight[b] = g.t.weight[a]; g.t.sum[b] = g.t.sum[a]; g.gray[b] = g.gray[a];
+        zero(a);
+    }
+};
+
 // ---- host: what is the TSDF map's own; the rest is the shared layer's (voxel_host.h) ----------------------------------------------
 struct viso_tsdf {
     VoxelHost h;
@@ -761,6 +793,36 @@ extern "C" int viso_tsdf_get_gray(viso_tsdf* t, uint32_t min_weight, viso_tsdf_g
         hipLaunchKernelGGL(tsdf_gray_compact_kernel, tsdf_slot_grid(t), dim3(256), 0, s, t->g(), min_weight, out, out_cap);
     });
 }
+
+// viso_tsdf_evict*: t is live and of the payload's kind
+static int tsdf_evict_plain(const char* where, viso_tsdf* t, const viso_voxel_box* keep, bool count_only, viso_tsdf_entry* evicted_out, size_t n_cap, size_t* n) {
+    const VoxelEvictKind<TsdfPayload> kind = {TsdfPayload{t->t}, tsdf_clear_launch(t),
+        [t](const viso_tsdf_entry* d, unsigned long long k, dim3 grid, hipStream_t s) {
+            hipLaunchKernelGGL(tsdf_add_entries_kernel, grid, dim3(256), 0, s, t->t, d, k);
+        }};
+    return voxel_evict<TsdfPayload>(where, g_tsdfs, t, keep, count_only, evicted_out, n_cap, n, kind);
+}
+static int tsdf_evict_gray(const char* where, viso_tsdf* t, const viso_voxel_box* keep, bool count_only, viso_tsdf_gray_entry* evicted_out, size_t n_cap, size_t* n) {
+    const VoxelEvictKind<TsdfGrayPayload> kind = {TsdfGrayPayload{t->g()}, tsdf_clear_launch(t),
+        [t](const viso_tsdf_gray_entry* d, unsigned long long k, dim3 grid, hipStream_t s) {
+            hipLaunchKernelGGL(tsdf_gray_add_entries_kernel, grid, dim3(256), 0, s, t->g(), d, k);
+        }};
+    return voxel_evict<TsdfGrayPayload>(where, g_tsdfs, t, keep, count_only, evicted_out, n_cap, n, kind);
+}
+extern "C" int viso_tsdf_evict_count(viso_tsdf* t, const viso_voxel_box* keep, size_t* n) {   // either kind
+    const char* where = "viso_tsdf_evict_count";
+    if (!voxel_known(g_tsdfs, t)) { viso_set_error("%s: not a live TSDF handle", where); return VISO_ERR_ARG; }
+    return t->gray ? tsdf_evict_gray(where, t, keep, true, nullptr, 0, n) : tsdf_evict_plain(where, t, keep, true, nullptr, 0, n);
+}
+extern "C" int viso_tsdf_evict(viso_tsdf* t, const viso_voxel_box* keep, viso_tsdf_entry* evicted_out, size_t n_cap, size_t* n) {
+    if (!tsdf_kind_ok("viso_tsdf_evict", t, false)) return VISO_ERR_ARG;
+    return tsdf_evict_plain("viso_tsdf_evict", t, keep, false, evicted_out, n_cap, n);
+}
+extern "C" int viso_tsdf_evict_gray(viso_tsdf* t, const viso_voxel_box* keep, viso_tsdf_gray_entry* evicted_out, size_t n_cap, size_t* n) {
+    if (!tsdf_kind_ok("viso_tsdf_evict_gray", t, true)) return VISO_ERR_ARG;
+    return tsdf_evict_gray("viso_tsdf_evict_gray", t, keep, false, evicted_out, n_cap, n);
+}
+
 extern "C" int viso_tsdf_surface_count(viso_tsdf* t, uint32_t min_weight, size_t* n) {
     return tsdf_extract<viso_tsdf_crossing>("viso_tsdf_surface_count", t, min_weight, true, nullptr, 0, n, tsdf_crossings_kernel);
 }

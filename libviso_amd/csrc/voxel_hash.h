@@ -3,11 +3,14 @@
 // ones = empty; a key is claimed with one 64-bit compare-and-swap.  Every probe loop visits each slot at most once and advances
 // strictly: a full table is a wrong count, never a hang.  Beside the keys every table has 256 sets of counters on cache lines of
 // their own (a workgroup adds to set blockIdx & 255, one atomic per wave and counter; summed on the host) and a few single words.
+// Eviction (include/viso_hip.h, "Map eviction") is here too, once for every kind: three kernels over the slots,
+// templates over the kind's payload.  Only they ever write a tombstone, and none is left when they are done.
 #ifndef VISO_VOXEL_HASH_H_
 #define VISO_VOXEL_HASH_H_
 #include "common.h"
 
 #define MAP_EMPTY 0xffffffffffffffffull
+#define MAP_TOMB 0xfffffffffffffffeull   // an evicted slot between the passes of an eviction (keys are 63 bits); never outlives the call
 #define MAP_BIAS (1 << 20)
 #define MAP_RANGE 1073741824.0          // 2^30: |g| at and beyond it is out of range
 
@@ -139,6 +142,86 @@ __device__ __forceinline__ bool voxel_list_position(const VoxelTable& t, bool ta
     base = __shfl(base, 0);
     *at = base + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull));
     return true;
+}
+
+// ---- eviction: the voxels outside a box leave the table, in place ----------------------------------------------------------------
+// A kind's payload P is a small struct by value: `typename P::Entry`, pack(slot, key, Entry*) (the slot as the kind's getter lists
+// it), move(a, b) (the payload words of slot a to slot b, slot a's zeroed) and zero(a).
+struct VoxelBox { int32_t lo[3], hi[3]; };   // viso_voxel_box: voxel k is inside when lo[i] <= k[i] < hi[i]
+
+__device__ __forceinline__ bool voxel_in_box(unsigned long long key, const VoxelBox& b) {
+    int32_t k[3];
+    voxel_unkey(key, k);
+    return k[0] >= b.lo[0] && k[0] < b.hi[0] && k[1] >= b.lo[1] && k[1] < b.hi[1] && k[2] >= b.lo[2] && k[2] < b.hi[2];
+}
+
+#define VOXEL_EVICT_COUNT 0   // the number of voxels outside the box; reads only
+#define VOXEL_EVICT_LIST 1    // those voxels to `out` (null: nowhere), their keys to MAP_TOMB
+#define VOXEL_EVICT_KEEP 2    // the voxels inside the box to `out`; reads only (the full table's way out)
+#define VOXEL_EVICT_PEEK 3    // the voxels outside the box to `out`; reads only (the same)
+
+// Pass 1, one thread per slot (the grid covers the slots exactly).  Positions come from voxel_list_position, one atomic per wave.
+template <class P>
+__global__ __launch_bounds__(256) void voxel_evict_mark_kernel(VoxelTable t, P p, VoxelBox box, int mode, typename P::Entry* out,
+                                                               unsigned long long out_cap) {
+    const uint32_t slot = blockIdx.x * 256 + threadIdx.x;
+    const unsigned long long key = t.keys[slot];
+    const bool live = key < MAP_TOMB;
+    const bool take = live && voxel_in_box(key, box) == (mode == VOXEL_EVICT_KEEP);
+    unsigned long long at;
+    if (!voxel_list_position(t, take, threadIdx.x & 63, &at)) return;   // the whole wave
+    if (!take || mode == VOXEL_EVICT_COUNT) return;
+    if (out) {
+        if (at >= out_cap) return;   // (a list of the first pass's length has room for all: the slot stays as it is)
+        typename P::Entry v;
+        p.pack(slot, key, &v);
+        out[at] = v;
+    }
+    if (mode == VOXEL_EVICT_LIST) t.keys[slot] = MAP_TOMB;
+}
+
+// Pass 2, one thread per slot; only the thread of a cluster's first slot (its own not empty, the one before it, cyclically, empty)
+// goes on, and walks its cluster in slot order to the next empty slot.  Every live entry is put back at the first tombstone at or
+// after its home slot, which is never later than the slot it is in; the slot it leaves becomes a tombstone.  So behind the walk no
+// tombstone lies between an entry's home and its slot, and the sweep may empty them all.  The pass writes MAP_EMPTY nowhere and
+// reads nothing beyond its own cluster (a home before the cluster's head, which only a bad table has, counts as the head), so the
+// walkers are independent and which slots are heads does not change while they run.  Offsets count from the head; `ft`: no
+// tombstone lies at an offset below it.  Both loops advance strictly: the outer one visits every slot of the cluster once, the
+// inner one the slots from the entry's home (or ft) to its own.  A table without an empty slot has no head: the host does not come
+// here with one.
+template <class P>
+__global__ __launch_bounds__(256) void voxel_evict_rebuild_kernel(VoxelTable t, P p) {
+    const uint32_t head = blockIdx.x * 256 + threadIdx.x, mask = t.mask;
+    unsigned long long* keys = t.keys;
+    if (keys[head] == MAP_EMPTY || keys[(head - 1u) & mask] != MAP_EMPTY) return;
+    uint32_t ft = 0;
+    for (uint32_t n = 0; n <= mask; ++n) {
+        const uint32_t s = (head + n) & mask;
+        const unsigned long long k = keys[s];
+        if (k == MAP_EMPTY) break;
+        if (k == MAP_TOMB) continue;
+        const uint32_t d = (s - (map_hash(k) & mask)) & mask;   // slots from its home to here
+        uint32_t o = d <= n ? n - d : 0u;
+        const bool from_ft = o <= ft;
+        if (from_ft) o = ft;
+        while (o < n && keys[(head + o) & mask] != MAP_TOMB) ++o;
+        if (o < n) {
+            const uint32_t to = (head + o) & mask;
+            keys[to] = k;
+            p.move(s, to);
+            keys[s] = MAP_TOMB;
+        }
+        if (from_ft) ft = o + 1u;
+    }
+}
+
+// Pass 3, one thread per slot: every tombstone to MAP_EMPTY, its payload zeroed as the clear kernel does.
+template <class P>
+__global__ __launch_bounds__(256) void voxel_evict_sweep_kernel(VoxelTable t, P p) {
+    const uint32_t slot = blockIdx.x * 256 + threadIdx.x;
+    if (t.keys[slot] != MAP_TOMB) return;
+    p.zero(slot);
+    t.keys[slot] = MAP_EMPTY;
 }
 
 // a clear kernel's part for the head: one thread per slot

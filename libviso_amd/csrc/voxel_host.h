@@ -2,7 +2,8 @@
 // voxel_hash.h; DESIGN.md 5.14, "Shared table layer").  A kind of map (viso_map, viso_tsdf) holds a VoxelHost, has a VoxelRegistry
 // of its live handles, and passes its kernel launches in as callables.  The rules that every kind must keep are here and in
 // voxel_host.hip, once: no handle is dereferenced before its registry has answered for it; staging is freed only behind a
-// synchronise; dropped updates become the sticky overflow mark; a temporary list is freed on every path.
+// synchronise; dropped updates become the sticky overflow mark; a temporary list is freed on every path; an eviction leaves no
+// tombstone behind.
 #ifndef VISO_VOXEL_HOST_H_
 #define VISO_VOXEL_HOST_H_
 #include "voxel_hash.h"
@@ -11,6 +12,7 @@
 #include <functional>
 #include <mutex>
 #include <unordered_map>
+#include <vector>
 
 // the words of a kind in the error texts
 struct VoxelKind {
@@ -135,6 +137,98 @@ int voxel_extract(const char* where, VoxelRegistry& reg, const void* handle, uin
     HIP_TRY(e);
     if (c2 != c) { viso_set_error("%s: the table changed between the two passes", where); return VISO_ERR_HIP; }   // (the map's lock rules it out)
     std::sort(items_out, items_out + c, [](const Item& x, const Item& y) { return voxel_item_less(x, y); });
+    return VISO_OK;
+}
+
+// ---- eviction (include/viso_hip.h, "Map eviction"; the kernels are voxel_hash.h's) --------------------------------------------------
+// what a kind passes in: its payload for the three kernels and, for a table without an empty slot, its clear and its add_entries
+template <class P>
+struct VoxelEvictKind {
+    P payload;
+    VoxelLaunch clear;
+    std::function<void(const typename P::Entry* d_entries, unsigned long long n, dim3 grid, hipStream_t)> add;
+};
+
+// the checks of an eviction's arguments that need no device; false: the error text is set
+bool voxel_evict_args(const char* where, VoxelRegistry& reg, const void* handle, const viso_voxel_box* keep, const size_t* n);
+// The statistics of h (entered and locked) as they lie on the device, [VOXEL_STAT_SETS][VOXEL_STAT_WORDS], and the sum of their
+// occupied counters; voxel_evict_put_stats: the same block back with `less` fewer occupied slots, every other counter as it was.
+int voxel_evict_get_stats(VoxelHost* h, std::vector<unsigned long long>& stats, unsigned long long* occupied);
+int voxel_evict_put_stats(VoxelHost* h, std::vector<unsigned long long>& stats, unsigned long long less);
+
+// viso_*_evict_count (count_only) and viso_*_evict, whole.  A first pass counts the voxels outside the box; a second one lists them
+// (items_out null: lists nothing) and turns their keys into tombstones, the rebuild pass moves every survivor to where a probe
+// finds it, the sweep empties the tombstones; the occupied counter falls on the host.  Device memory: the list of the evicted.  A
+// table without an empty slot has no cluster head to start a rebuild from: it goes through a list of its survivors, the kind's
+// clear and its add_entries, and gets its statistics back.  The list's order is the kind's voxel_item_less, as in voxel_extract.
+template <class P>
+int voxel_evict(const char* where, VoxelRegistry& reg, const void* handle, const viso_voxel_box* keep, bool count_only,
+                typename P::Entry* items_out, size_t n_cap, size_t* n, const VoxelEvictKind<P>& kind) {
+    using Item = typename P::Entry;
+    if (!voxel_evict_args(where, reg, handle, keep, n)) return VISO_ERR_ARG;
+    int r;
+    VoxelHost* h;
+    if ((r = voxel_enter(where, reg, handle, &h)) < 0) return r;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (h->overflowed) return voxel_refuse_overflowed(where, h);
+    VoxelBox box;
+    for (int i = 0; i < 3; ++i) { box.lo[i] = keep->lo[i]; box.hi[i] = keep->hi[i]; }
+    const size_t slots = (size_t)h->head.mask + 1;
+    const dim3 grid((unsigned)(slots / 256));
+    const VoxelTable head = h->head;
+    auto mark = [&](int mode, Item* out, unsigned long long cap) {
+        return [&, mode, out, cap](hipStream_t s) {
+            hipLaunchKernelGGL(voxel_evict_mark_kernel<P>, grid, dim3(256), 0, s, head, kind.payload, box, mode, out, cap);
+        };
+    };
+    unsigned long long c = 0, c2 = 0, occupied = 0;
+    if ((r = voxel_pass(h, mark(VOXEL_EVICT_COUNT, nullptr, 0), &c)) < 0) return r;
+    *n = (size_t)c;
+    if (count_only || !c) return VISO_OK;
+    if (items_out && c > n_cap) { viso_set_error("%s: %llu items do not fit the %zu given", where, c, n_cap); return VISO_ERR_ARG; }
+    std::vector<unsigned long long> stats;
+    if ((r = voxel_evict_get_stats(h, stats, &occupied)) < 0) return r;
+    const bool full = occupied >= slots;
+    const unsigned long long n_keep = full ? slots - c : 0;
+    const size_t b_out = items_out ? (size_t)c * sizeof(Item) : 0, b_keep = (size_t)n_keep * sizeof(Item);
+    char* d = nullptr;   // the evicted | a full table's survivors
+    if (b_out + b_keep && hipMalloc((void**)&d, b_out + b_keep) != hipSuccess) {
+        (void)hipGetLastError();
+        viso_set_error("%s: cannot allocate %zu bytes for the list", where, b_out + b_keep);
+        return VISO_ERR_NOMEM;
+    }
+    Item* d_out = items_out ? reinterpret_cast<Item*>(d) : nullptr;
+    Item* d_keep = reinterpret_cast<Item*>(d + b_out);
+    hipStream_t s = h->ctx->stream;
+    hipError_t e = hipSuccess;
+    if (!full) {
+        r = voxel_pass(h, mark(VOXEL_EVICT_LIST, d_out, c), &c2);
+        if (r >= 0) {   // tombstones are in the table: both passes follow whatever else happens
+            hipLaunchKernelGGL(voxel_evict_rebuild_kernel<P>, grid, dim3(256), 0, s, head, kind.payload);
+            hipLaunchKernelGGL(voxel_evict_sweep_kernel<P>, grid, dim3(256), 0, s, head, kind.payload);
+            e = hipGetLastError();
+        }
+    } else {
+        if (d_out) r = voxel_pass(h, mark(VOXEL_EVICT_PEEK, d_out, c), &c2);
+        else c2 = c;
+        unsigned long long k2 = 0;
+        if (r >= 0 && n_keep) r = voxel_pass(h, mark(VOXEL_EVICT_KEEP, d_keep, n_keep), &k2);
+        if (r >= 0 && k2 != n_keep) c2 = ~0ull;
+        if (r >= 0 && c2 == c) {
+            kind.clear(s);
+            if (n_keep) kind.add(d_keep, n_keep, dim3((unsigned)((n_keep + 255) / 256)), s);
+            e = hipGetLastError();
+        }
+    }
+    if (r >= 0 && e == hipSuccess && c2 == c) r = voxel_evict_put_stats(h, stats, c);
+    if (r >= 0 && e == hipSuccess && d_out) e = hipMemcpyAsync(items_out, d_out, b_out, hipMemcpyDeviceToHost, s);
+    const hipError_t e_wait = hipStreamSynchronize(s);   // nothing in flight touches the list that is freed next
+    if (d) (void)hipFree(d);   // on every path
+    if (r < 0) return r;
+    HIP_TRY(e);
+    HIP_TRY(e_wait);
+    if (c2 != c) { viso_set_error("%s: the table changed between the two passes", where); return VISO_ERR_HIP; }   // (the map's lock rules it out)
+    if (items_out) std::sort(items_out, items_out + c, [](const Item& x, const Item& y) { return voxel_item_less(x, y); });
     return VISO_OK;
 }
 #endif /* VISO_VOXEL_HOST_H_ */

@@ -1,9 +1,11 @@
 // voxel_host.hip — the host side of the shared table layer (voxel_host.h): the registry of live handles, the life of a table, the
 // staging (the map, the poses and, where a kind fuses one, the image) and the group loop of a fuse, the scaffold of add_entries, the
-// pass of an extraction, the staging and the output buffer of a render, the staging and the sums of a linearise and the read-back of the statistics.
+// pass of an extraction, the staging and the output buffer of a render, the staging and the sums of a linearise, the read-back of the
+// statistics, and of an eviction the argument checks, the statistics' round trip and the box around a point.
 // No kernel is here: every kind passes its launches in.
 #include "voxel_host.h"
 
+#include <climits>
 #include <cmath>
 #include <vector>
 
@@ -260,6 +262,55 @@ int voxel_pass(VoxelHost* h, const VoxelLaunch& launch, unsigned long long* n) {
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(n, h->head.words + VOXEL_W_OUT, sizeof(*n), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
+    return VISO_OK;
+}
+
+bool voxel_evict_args(const char* where, VoxelRegistry& reg, const void* handle, const viso_voxel_box* keep, const size_t* n) {
+    if (!voxel_known(reg, handle)) { voxel_not_live(where, reg); return false; }
+    bool ok = keep && n;
+    for (int i = 0; ok && i < 3; ++i) ok = keep->lo[i] <= keep->hi[i];
+    if (!ok) viso_set_error("%s: bad argument (a non-null box with lo <= hi on every axis, a non-null n)", where);
+    return ok;
+}
+
+int voxel_evict_get_stats(VoxelHost* h, std::vector<unsigned long long>& stats, unsigned long long* occupied) {
+    hipStream_t s = h->ctx->stream;
+    stats.resize((size_t)VOXEL_STAT_SETS * VOXEL_STAT_WORDS);
+    HIP_TRY(hipMemcpyAsync(stats.data(), h->head.stats, stats.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    *occupied = 0;
+    for (int k = 0; k < VOXEL_STAT_SETS; ++k) *occupied += stats[(size_t)k * VOXEL_STAT_WORDS + VOXEL_ST_OCC];
+    return VISO_OK;
+}
+
+// (the caller waits for the stream before `stats` goes)
+int voxel_evict_put_stats(VoxelHost* h, std::vector<unsigned long long>& stats, unsigned long long less) {
+    for (int k = 0; k < VOXEL_STAT_SETS && less; ++k) {   // a set gives what it has: no counter wraps
+        unsigned long long& occ = stats[(size_t)k * VOXEL_STAT_WORDS + VOXEL_ST_OCC];
+        const unsigned long long take = occ < less ? occ : less;
+        occ -= take; less -= take;
+    }
+    HIP_TRY(hipMemcpyAsync(h->head.stats, stats.data(), stats.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, h->ctx->stream));
+    return VISO_OK;
+}
+
+extern "C" int viso_voxel_box_around(const double centre[3], double half_side, double voxel, viso_voxel_box* out) {
+    bool ok = centre && out && std::isfinite(half_side) && half_side >= 0.0 && std::isfinite(voxel) && voxel > 0.0;
+    for (int i = 0; ok && i < 3; ++i) ok = std::isfinite(centre[i]);
+    if (!ok) {
+        viso_set_error("viso_voxel_box_around: bad argument (a finite centre, a finite half_side >= 0, a finite voxel > 0, a non-null output)");
+        return VISO_ERR_ARG;
+    }
+    auto clamp32 = [](double g, long long add) {   // (int64) g + add clamped to int32; g is a floor, or an infinity
+        if (!(g > -4294967296.0)) return (int32_t)INT32_MIN;
+        if (!(g < 4294967296.0)) return (int32_t)INT32_MAX;
+        const long long v = (long long)g + add;
+        return (int32_t)(v < INT32_MIN ? INT32_MIN : v > INT32_MAX ? INT32_MAX : v);
+    };
+    for (int i = 0; i < 3; ++i) {
+        out->lo[i] = clamp32(std::floor((centre[i] - half_side) / voxel), 0);
+        out->hi[i] = clamp32(std::floor((centre[i] + half_side) / voxel), 1);
+    }
     return VISO_OK;
 }
 

@@ -130,6 +130,26 @@ __global__ __launch_bounds__(256) void map_clear_kernel(MapTable t) {
     t.sums[3 * (size_t)slot + 0] = 0ull; t.sums[3 * (size_t)slot + 1] = 0ull; t.sums[3 * (size_t)slot + 2] = 0ull;
 }
 
+// the payload of a slot for the eviction's kernels (voxel_hash.h)
+struct MapPayload {
+    MapTable t;
+    using Entry = viso_map_entry;
+    __device__ __forceinline__ void pack(uint32_t slot, unsigned long long key, Entry* v) const {
+        voxel_unkey(key, v->k);
+        v->count = t.cnt[slot];
+        v->sum[0] = t.sums[3 * (size_t)slot + 0]; v->sum[1] = t.sums[3 * (size_t)slot + 1]; v->sum[2] = t.sums[3 * (size_t)slot + 2];
+    }
+    __device__ __forceinline__ void zero(uint32_t a) const {
+        t.cnt[a] = 0u;
+        t.sums[3 * (size_t)a + 0] = 0ull; t.sums[3 * (size_t)a + 1] = 0ull; t.sums[3 * (size_t)a + 2] = 0ull;
+    }
+    __device__ __forceinline__ void move(uint32_t a, uint32_t b) const {
+        t.cnt[b] = t.cnt[a];
+        for (int i = 0; i < 3; ++i) t.sums[3 * (size_t)b + i] = t.sums[3 * (size_t)a + i];
+        zero(a);
+    }
+};
+
 // ---- host: what is the voxel map's own; the rest is the shared layer's (voxel_host.h) --------------------------------------------
 struct viso_map {
     VoxelHost h;
@@ -229,6 +249,21 @@ static int map_extract(const char* where, viso_map* m, uint32_t min_count, bool 
 extern "C" int viso_map_count(viso_map* m, uint32_t min_count, size_t* n) { return map_extract("viso_map_count", m, min_count, true, nullptr, 0, n); }
 extern "C" int viso_map_get(viso_map* m, uint32_t min_count, viso_map_entry* entries_out, size_t n_cap, size_t* n) {
     return map_extract("viso_map_get", m, min_count, false, entries_out, n_cap, n);
+}
+
+static int map_evict(const char* where, viso_map* m, const viso_voxel_box* keep, bool count_only, viso_map_entry* evicted_out, size_t n_cap, size_t* n) {
+    if (!voxel_known(g_maps, m)) { viso_set_error("%s: not a live map handle", where); return VISO_ERR_ARG; }
+    const VoxelEvictKind<MapPayload> kind = {MapPayload{m->t}, map_clear_launch(m),
+        [m](const viso_map_entry* d, unsigned long long k, dim3 grid, hipStream_t s) {
+            hipLaunchKernelGGL(map_add_entries_kernel, grid, dim3(256), 0, s, m->t, d, k);
+        }};
+    return voxel_evict<MapPayload>(where, g_maps, m, keep, count_only, evicted_out, n_cap, n, kind);
+}
+extern "C" int viso_map_evict_count(viso_map* m, const viso_voxel_box* keep, size_t* n) {
+    return map_evict("viso_map_evict_count", m, keep, true, nullptr, 0, n);
+}
+extern "C" int viso_map_evict(viso_map* m, const viso_voxel_box* keep, viso_map_entry* evicted_out, size_t n_cap, size_t* n) {
+    return map_evict("viso_map_evict", m, keep, false, evicted_out, n_cap, n);
 }
 
 extern "C" int viso_map_stats(viso_map* m, viso_map_counters* out) {

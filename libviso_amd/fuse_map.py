@@ -1,6 +1,7 @@
 """python -m libviso_amd.fuse_map DISPARITY_DIR POSES.txt CALIB.txt OUT.ply [--voxel V --min-count N --min-disp PX --frames B E]
                                  [--surface | --mesh [--trunc T --min-weight N] [--render DIR [--render-depth M]] [--gray IMAGE_DIR]
                                                      [--align [--aligned-poses FILE --align-voxel-gate G]]]
+                                 [--window METRES [--archive FILE.npy]]
 
 Fuses the maps a KITTI runner wrote with --disparity DIR and the poses of its pose file into one voxel map on the device
 (libviso_amd.VoxelMap; include/viso_hip.h, "voxel map") and writes the occupied voxels as a binary PLY point cloud: x, y, z the
@@ -31,6 +32,15 @@ float32 centroid of each voxel, count the number of points fused into it.
                  ends with status >= 1, otherwise at that guess.  --align-voxel-gate G: the gate in voxels (1.0, at most --trunc);
                  --min-weight applies to the voxels the alignment reads.  --aligned-poses FILE: the poses the maps were fused at, in
                  the format of POSES.txt.  The statuses are counted in the tool's output.
+  --window METRES  keep the map on the device to a cube of this half side around the camera (include/viso_hip.h, "Map eviction"):
+                 before map i is fused (and, with --align, aligned), every voxel outside the box of voxels that the cube around the
+                 translation of pose i touches leaves the table, on the device, and is appended to an archive on the host.  So a
+                 table far smaller than the scene (--capacity-log2) follows the camera over any distance.  Without --surface or
+                 --mesh, OUT.ply is written from the archive merged with the live voxels and is byte-identical to the run without
+                 --window.  With --surface or --mesh, OUT.ply and the renders are of the live window at the end, and the model that
+                 --align tracks against is the window: tracking in bounded memory.
+  --archive FILE.npy  with --window: the evicted voxels, merged by key and sorted, as a numpy array of the map's entry dtype
+                 (libviso_amd.merge_entries of it and of a map's entries is the unbounded map).
 
 Both runners write byte-identical directories and pose files for every rank count and chunk size, so the PLY is identical too."""
 import argparse
@@ -230,7 +240,14 @@ def main(argv=None):
     ap.add_argument("--align", action="store_true", help="with --surface or --mesh: align every map against the model before it is fused")
     ap.add_argument("--aligned-poses", metavar="FILE", help="with --align: write the poses the maps were fused at")
     ap.add_argument("--align-voxel-gate", type=float, default=1.0, metavar="G", help="with --align: the gate in voxels (1.0)")
+    ap.add_argument("--window", type=float, default=None, metavar="METRES", help="keep the map to a cube of this half side around the camera; "
+                    "what leaves it goes to an archive on the host (OUT.ply: the whole map without --surface or --mesh, else the live window)")
+    ap.add_argument("--archive", metavar="FILE.npy", help="with --window: write the merged evicted voxels as a numpy array of entries")
     a = ap.parse_args(argv)
+    if a.archive and a.window is None:
+        ap.error("--archive needs --window")
+    if a.window is not None and not (np.isfinite(a.window) and a.window >= 0):
+        ap.error("--window needs a half side >= 0 in metres")
     if a.align and not (a.surface or a.mesh):
         ap.error("--align needs --surface or --mesh (only a TSDF map is aligned against)")
     if a.aligned_poses and not a.align:
@@ -249,6 +266,19 @@ def main(argv=None):
         sys.exit(f"fuse_map: --frames {b} {e} is outside the {len(names)} maps")
     f, cu, cv, base = read_calib(a.calib)
     prm = Param.default(base=base, f=f, cu=cu, cv=cv)
+    archive = []   # --window: what left the map, in the order it left
+
+    def evict_to_window(vmap, i):
+        if a.window is not None:
+            archive.append(vmap.evict(libviso_amd.voxel_box(poses[i][:3, 3], a.window, a.voxel)))
+
+    def write_archive(dtype):
+        if a.window is None:
+            return ""
+        n = sum(len(x) for x in archive)
+        if a.archive:
+            np.save(a.archive, libviso_amd.merge_entries(np.zeros(0, dtype), *archive))
+        return f"; window of {a.window} m: {n} voxels evicted" + (f" -> {a.archive}" if a.archive else "")
     if a.surface or a.mesh:
         gray = bool(a.gray)
         tsdf = libviso_amd.TsdfMap(None, gray=gray, voxel=a.voxel, trunc_voxels=a.trunc, min_disp16=max(1, int(round(a.min_disp * 16))),
@@ -265,6 +295,7 @@ def main(argv=None):
                     image = read_png8(os.path.join(a.gray, names[i]))
                     if image.shape != m.shape:
                         sys.exit(f"fuse_map: {names[i]} is {image.shape[1]} x {image.shape[0]} in {a.gray} but its map is {m.shape[1]} x {m.shape[0]}")
+                evict_to_window(tsdf, i)
                 pose = poses[i]
                 if a.align and used:
                     pose = used[-1] @ np.linalg.inv(poses[i - 1]) @ poses[i]
@@ -278,6 +309,7 @@ def main(argv=None):
                 else:
                     tsdf.fuse(m, prm, pose=pose)
             st = tsdf.stats()
+            note = write_archive(tsdf._evict_dtype())
             if a.align:
                 if a.aligned_poses:
                     write_poses(a.aligned_poses, used)
@@ -311,23 +343,31 @@ def main(argv=None):
         if a.mesh:
             libviso_amd.write_mesh_ply(a.out, vertices, triangles, shade)
             print(f"fuse_map: {e - b} maps, {st['n_points']} points, {st['n_updates']} updates ({st['n_out_of_range']} samples out of range), "
-                  f"{st['n_occupied']} voxels, {len(vertices)} vertices and {len(triangles)} triangles at weight >= {a.min_weight} -> {a.out}")
+                  f"{st['n_occupied']} voxels, {len(vertices)} vertices and {len(triangles)} triangles at weight >= {a.min_weight} -> {a.out}{note}")
             return 0
         libviso_amd.write_surface_ply(a.out, crossings, a.voxel, shade)
         print(f"fuse_map: {e - b} maps, {st['n_points']} points, {st['n_updates']} updates ({st['n_out_of_range']} samples out of range), "
-              f"{st['n_occupied']} voxels, {len(crossings)} crossings at weight >= {a.min_weight} -> {a.out}")
+              f"{st['n_occupied']} voxels, {len(crossings)} crossings at weight >= {a.min_weight} -> {a.out}{note}")
         return 0
     vmap = libviso_amd.VoxelMap(None, voxel=a.voxel, min_disp16=max(1, int(round(a.min_disp * 16))),
                                 capacity_log2=24 if a.capacity_log2 is None else a.capacity_log2)
     try:
         for i in range(b, e):
+            evict_to_window(vmap, i)
             vmap.fuse(read_disparity_png(os.path.join(a.disparity_dir, names[i])), prm, pose=poses[i])
-        entries, st = vmap.entries(a.min_count), vmap.stats()
+        st = vmap.stats()
+        if a.window is None:
+            entries = vmap.entries(a.min_count)
+        else:   # the whole map: what left merged with what is live
+            entries = libviso_amd.merge_entries(*archive, vmap.entries())
+            st["n_occupied"] = len(entries)
+            entries = entries[entries["count"] >= a.min_count]
     finally:
         vmap.close()
+    note = write_archive(entries.dtype)
     libviso_amd.write_map_ply(a.out, entries, a.voxel)
     print(f"fuse_map: {e - b} maps, {st['n_points']} points ({st['n_out_of_range']} out of range), {st['n_occupied']} voxels, "
-          f"{len(entries)} with count >= {a.min_count} -> {a.out}")
+          f"{len(entries)} with count >= {a.min_count} -> {a.out}{note}")
     return 0
 
 
