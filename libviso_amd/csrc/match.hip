@@ -210,6 +210,81 @@ int launch_sort_kp(hipStream_t s, const ImageView* imgs_dev, int n_img, int cap_
 // so row boundaries fall anywhere in a lane's 16 B), then lane l converts floats 2l, 2l+1 of every row into one
 // packed dword and the wave writes each 256-B row to its bucket-order position rank[i] (two full cache lines).
 #define VISO_PACK_RPW 8   // rows per wave
+#ifndef VISO_PACK_LEAN
+#define VISO_PACK_LEAN 1  // 0: every wave converts with pack_rows_checked (A/B builds)
+#endif
+
+// Row k of a pack wave, lane l holding its elements 2l, 2l+1 as integers (pad elements 0): the u16 row's dword to bucket-order
+// position d, and what `extras` asks for beside it.  All of it wave uniform but the values.  INT16: ia and ib are known to be
+// int16 values (the plane's bytes then come from the row's dword, two at a time).
+template <bool INT16>
+__device__ __forceinline__ void pack_store_row(const ImageView& I, int d, int lane, int ia, int ib, int extras, int r8s) {
+    typedef __attribute__((address_space(1))) uint32_t* gout_t;
+    // the low halves of the biased values side by side (one v_perm_b32; pack_rows_lean has the sums for its range test anyway)
+    const uint32_t row = __builtin_amdgcn_perm((uint32_t)ib + (uint32_t)VISO_BIAS, (uint32_t)ia + (uint32_t)VISO_BIAS, 0x05040100u);
+#ifdef VISO_DEBUG_VARIANTS   // timing experiment only ($VISO_EXP_PACK_NO_U16, HISTORY.md round 6): what the kernel would cost without the u16 rows
+    if (!(extras & 0x100))
+#endif
+    ((gout_t)reinterpret_cast<uint32_t*>(I.rows + (size_t)(unsigned)d * VISO_ROW))[lane] = row;
+    // block sums (ImageView::sums; only match_prune_kernel reads them): lanes 16b..16b+15 hold block b; meaningless
+    // for flagged images (never read then)
+    if (extras & VISO_PACK_SUMS) {   // uniform
+        const uint2 bs = pack_block_sums(ia + ib);
+        if (lane == 0) I.sums[d] = bs;
+    }
+    if (extras & VISO_PACK_ROWS8) {   // uniform (as is r8s: a kernel argument)
+        if constexpr (INT16) store_row8_pair(I.rows8, (size_t)(unsigned)d, lane, row8_pair_of_biased(row, r8s));
+        else store_row8<true>(I.rows8, (size_t)(unsigned)d, lane, ia, ib, r8s);
+    }
+}
+
+// The rows of a wave whatever their values: round to nearest, then test "an integer that fits int16" element by element.
+// Returns the lane's flag.  (Every wave took this before pack_rows_lean; now the waves that hold a value failing the test.)
+__device__ __forceinline__ bool pack_rows_checked(const ImageView& I, const float* buf, int nrows, int dlen, int dst, int lane, int extras, int r8s) {
+    const int c = 2 * lane;
+    bool isbad = false;
+#pragma unroll
+    for (int k = 0; k < VISO_PACK_RPW; ++k) {
+        if (k >= nrows) break;              // wave uniform
+        const float a = c < dlen ? buf[k * dlen + c] : 0.f;
+        const float b = c + 1 < dlen ? buf[k * dlen + c + 1] : 0.f;
+        const float ar = rintf(a), br = rintf(b);
+        if (!(a == ar) || a < -32768.f || a > 32767.f || !(b == br) || b < -32768.f || b > 32767.f) isbad = true;
+        pack_store_row<false>(I, __builtin_amdgcn_readlane(dst, k), lane, (int)ar, (int)br, extras, r8s);
+    }
+    return isbad;
+}
+
+// The same rows for what the data almost always is -- integers within int16 -- in 21 vector instructions per row where
+// pack_rows_checked takes 36 (and a third of its scalar ones): alone the kernel waits for HBM either way, but with several batches in
+// flight it runs beside a matcher kernel that is bound by vector issue, and every instruction here is one taken from there.
+// ONE conversion per element (v_cvt_i32_f32: truncates, saturates, NaN -> 0)
+// gives the value to store and, converted back, the test (x is such an integer iff float(int(x)) == x and int(x) + 32768 fits
+// 16 bits; -0.0 passes, NaN / inf / 0.5 / 32768.0 do not); the range test is OR-accumulated over the rows and looked at once.
+// For a wave where every element passes, truncation IS rounding and the rows are pack_rows_checked's bit for bit; a wave with
+// a failing element says so (the lane's flag) and the caller has pack_rows_checked write its rows again.
+// The LDS reads are unconditional (a select zeroes the pads; the last lanes read into the next row or the buffer's unused
+// tail, inside s_buf[wv]): no exec masking per row.
+__device__ __forceinline__ bool pack_rows_lean(const ImageView& I, const float* buf, int nrows, int dlen, int dst, int lane, int extras, int r8s) {
+    const int c = 2 * lane;
+    const bool va = c < dlen, vb = c + 1 < dlen;
+    const float* p = buf + c;
+    uint32_t over = 0;
+    bool frac = false;
+#pragma unroll
+    for (int k = 0; k < VISO_PACK_RPW; ++k) {
+        if (k >= nrows) break;              // wave uniform
+        float a = p[k * dlen], b = p[k * dlen + 1];
+        a = va ? a : 0.f; b = vb ? b : 0.f;
+        int ia, ib;
+        asm("v_cvt_i32_f32_e32 %0, %1" : "=v"(ia) : "v"(a));
+        asm("v_cvt_i32_f32_e32 %0, %1" : "=v"(ib) : "v"(b));
+        frac |= ((float)ia != a) | ((float)ib != b);
+        over |= ((uint32_t)ia + (uint32_t)VISO_BIAS) | ((uint32_t)ib + (uint32_t)VISO_BIAS);
+        pack_store_row<true>(I, __builtin_amdgcn_readlane(dst, k), lane, ia, ib, extras, r8s);   // (not int16: the wave's rows are written again)
+    }
+    return frac | ((over >> 16) != 0u);
+}
 
 __global__ __launch_bounds__(256) void pack_desc_kernel(const ImageView* __restrict__ imgs, int n_img,
                                                         int cap, int dlen, int* __restrict__ bad_any, int extras, int r8s, int* __restrict__ r8cnt, unsigned r8m) {
@@ -218,14 +293,13 @@ __global__ __launch_bounds__(256) void pack_desc_kernel(const ImageView* __restr
     typedef const __attribute__((address_space(1))) f32x4* gvec_t;
     typedef const __attribute__((address_space(1))) float* gflt_t;
     typedef const __attribute__((address_space(1))) int* gint_t;
-    typedef __attribute__((address_space(1))) uint32_t* gout_t;
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const long long wave = (long long)blockIdx.x * 4 + wv;
     const long long row0 = wave * VISO_PACK_RPW;
     if (row0 >= (long long)n_img * cap) return;
     const int img = (int)(row0 / cap);      // cap is a multiple of VISO_PACK_RPW: a wave never straddles images
     const ImageView I = imgs[img];
-    const int n = *I.n;
+    const int n = __builtin_amdgcn_readfirstlane(*I.n);   // (uniform: said so, the row loops below branch on it in scalar code)
     const int r0 = (int)(row0 % cap);
     if (r0 >= n) return;
     const int nrows = min(VISO_PACK_RPW, n - r0);
@@ -249,28 +323,8 @@ __global__ __launch_bounds__(256) void pack_desc_kernel(const ImageView* __restr
     if (lane < nrows) dst = ((gint_t)I.rank)[r0 + lane];
     __builtin_amdgcn_wave_barrier();
     const int c = 2 * lane;
-    bool isbad = false;
-#pragma unroll
-    for (int k = 0; k < VISO_PACK_RPW; ++k) {
-        if (k >= nrows) break;              // wave uniform
-        const float a = c < dlen ? buf[k * dlen + c] : 0.f;
-        const float b = c + 1 < dlen ? buf[k * dlen + c + 1] : 0.f;
-        const float ar = rintf(a), br = rintf(b);
-        if (!(a == ar) || a < -32768.f || a > 32767.f || !(b == br) || b < -32768.f || b > 32767.f) isbad = true;
-        const uint32_t ua = (uint32_t)((int)ar + VISO_BIAS) & 0xffffu, ub = (uint32_t)((int)br + VISO_BIAS) & 0xffffu;
-        const int d = __builtin_amdgcn_readlane(dst, k);
-#ifdef VISO_DEBUG_VARIANTS   // timing experiment only ($VISO_EXP_PACK_NO_U16, HISTORY.md round 6): what the kernel would cost without the u16 rows
-        if (!(extras & 0x100))
-#endif
-        ((gout_t)reinterpret_cast<uint32_t*>(I.rows + (size_t)d * VISO_ROW))[lane] = ua | (ub << 16);
-        // block sums (ImageView::sums; only match_prune_kernel reads them): lanes 16b..16b+15 hold block b; meaningless
-        // for flagged images (never read then)
-        if (extras & VISO_PACK_SUMS) {   // uniform
-            const uint2 bs = pack_block_sums((int)ar + (int)br);
-            if (lane == 0) I.sums[d] = bs;
-        }
-        if (extras & VISO_PACK_ROWS8) store_row8(I.rows8, (size_t)d, lane, (int)ar, (int)br, r8s);   // uniform
-    }
+    bool isbad = VISO_PACK_LEAN ? pack_rows_lean(I, buf, nrows, dlen, dst, lane, extras, r8s) : true;
+    if (__any(isbad)) isbad = pack_rows_checked(I, buf, nrows, dlen, dst, lane, extras, r8s);   // uniform; rare
     if (__any(isbad) && lane == 0) { atomicOr(I.bad, 1); atomicOr(bad_any, 1); }
     if (r8cnt && ((unsigned)wave & r8m) == 0) {   // uniform, ~256 waves of the launch: the rows once more (they are still in LDS), counted
         R8Count r8c = {0, 0, 0, 0};
@@ -290,14 +344,13 @@ __global__ __launch_bounds__(256) void pack_desc_i16_kernel(const ImageView* __r
     typedef const __attribute__((address_space(1))) u32x4* gvec_t;
     typedef const __attribute__((address_space(1))) uint16_t* gu16_t;
     typedef const __attribute__((address_space(1))) int* gint_t;
-    typedef __attribute__((address_space(1))) uint32_t* gout_t;
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const long long wave = (long long)blockIdx.x * 4 + wv;
     const long long row0 = wave * VISO_PACK_RPW;
     if (row0 >= (long long)n_img * cap) return;
     const int img = (int)(row0 / cap);      // cap is a multiple of VISO_PACK_RPW: a wave never straddles images
     const ImageView I = imgs[img];
-    const int n = *I.n;
+    const int n = __builtin_amdgcn_readfirstlane(*I.n);   // (uniform: said so)
     const int r0 = (int)(row0 % cap);
     if (r0 >= n) return;
     const int nrows = min(VISO_PACK_RPW, n - r0);
@@ -317,19 +370,14 @@ __global__ __launch_bounds__(256) void pack_desc_i16_kernel(const ImageView* __r
     if (lane < nrows) dst = ((gint_t)I.rank)[r0 + lane];
     __builtin_amdgcn_wave_barrier();
     const int c = 2 * lane;
+    const bool va = c < dlen, vb = c + 1 < dlen;
+    const uint16_t* p = buf + c;
 #pragma unroll
     for (int k = 0; k < VISO_PACK_RPW; ++k) {
         if (k >= nrows) break;              // wave uniform
-        const int a = c < dlen ? (int)(int16_t)buf[k * dlen + c] : 0;
-        const int b = c + 1 < dlen ? (int)(int16_t)buf[k * dlen + c + 1] : 0;
-        const uint32_t ua = (uint32_t)(a + VISO_BIAS) & 0xffffu, ub = (uint32_t)(b + VISO_BIAS) & 0xffffu;
-        const int d = __builtin_amdgcn_readlane(dst, k);
-        ((gout_t)reinterpret_cast<uint32_t*>(I.rows + (size_t)d * VISO_ROW))[lane] = ua | (ub << 16);
-        if (extras & VISO_PACK_SUMS) {   // uniform
-            const uint2 bs = pack_block_sums(a + b);
-            if (lane == 0) I.sums[d] = bs;
-        }
-        if (extras & VISO_PACK_ROWS8) store_row8(I.rows8, (size_t)d, lane, a, b, r8s);   // uniform
+        // unconditional LDS reads, the pads zeroed by a select (pack_rows_lean)
+        const int ra = (int)(int16_t)p[k * dlen], rb = (int)(int16_t)p[k * dlen + 1];
+        pack_store_row<true>(I, __builtin_amdgcn_readlane(dst, k), lane, va ? ra : 0, vb ? rb : 0, extras, r8s);
     }
     if (r8cnt && ((unsigned)wave & r8m) == 0) {   // uniform, ~256 waves of the launch: the rows once more (still in LDS), counted
         R8Count r8c = {0, 0, 0, 0};

@@ -36,12 +36,39 @@ __device__ __forceinline__ uint32_t row8_of(int v, int s) {
     return (uint32_t)x >> s;
 }
 
-// lane l holds elements 2l, 2l+1 of row `row` (pad elements as 0): the even lanes write the plane's dwords
-__device__ __forceinline__ void store_row8(uint8_t* rows8, size_t row, int lane, int va, int vb, int s) {
-    const uint32_t h2 = row8_of(va, s) | (row8_of(vb, s) << 8);
+// row8_of for a shift that is the same in every lane (a kernel argument): the upper bound stays in a scalar register, no move
+// into a vector register in front of every v_med3
+__device__ __forceinline__ uint32_t row8_of_uniform(int v, int s) {
+    int x = v + (128 << s);
+    asm("v_med3_i32 %0, %1, 0, %2" : "=v"(x) : "v"(x), "s"((256 << s) - 1));
+    return (uint32_t)x >> s;
+}
+
+// lane l holds h2, the two plane bytes of elements 2l, 2l+1 of row `row`: the even lanes write the plane's dwords
+__device__ __forceinline__ void store_row8_pair(uint8_t* rows8, size_t row, int lane, uint32_t h2) {
     const uint32_t nb = wave_dpp_bc<0x101>(h2);   // row_shl:1: lane + 1's pair
     if ((lane & 1) == 0)
         ((__attribute__((address_space(1))) uint32_t*)reinterpret_cast<uint32_t*>(rows8 + row * VISO_ROW8))[lane >> 1] = h2 | (nb << 16);
+}
+// ... from the elements themselves (pad elements as 0).  UNIFORM_S: s is wave uniform (row8_of_uniform)
+template <bool UNIFORM_S = false>
+__device__ __forceinline__ void store_row8(uint8_t* rows8, size_t row, int lane, int va, int vb, int s) {
+    store_row8_pair(rows8, row, lane, UNIFORM_S ? row8_of_uniform(va, s) | (row8_of_uniform(vb, s) << 8) : row8_of(va, s) | (row8_of(vb, s) << 8));
+}
+
+// A lane's two plane bytes from its dword of the packed u16 row -- the BIASED pair, u = v + 32768 in each half, so every v is an
+// int16 -- in unsigned 16-bit arithmetic, both halves per instruction: v + (128 << s) clamped below at 0 is u minus
+// (32768 - (128 << s)) with unsigned saturation, then the upper clamp and the shift (v_pk_sub_u16 clamp, v_pk_min_u16,
+// v_pk_lshrrev_b16: three instructions where two row8_of take six), then bytes 0 and 2 side by side.  Same bytes as row8_of.
+typedef unsigned short viso_u16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t row8_pair_of_biased(uint32_t row, int s) {
+    const unsigned short c = (unsigned short)(VISO_BIAS - (128 << s)), top = (unsigned short)((256 << s) - 1), sh = (unsigned short)s;
+    viso_u16x2 u = __builtin_bit_cast(viso_u16x2, row);
+    u = __builtin_elementwise_sub_sat(u, (viso_u16x2){c, c});
+    u = __builtin_elementwise_min(u, (viso_u16x2){top, top});
+    u = u >> (viso_u16x2){sh, sh};
+    const uint32_t w = __builtin_bit_cast(uint32_t, u);
+    return __builtin_amdgcn_perm(w, w, 0x0c0c0200u);   // (0x0c: a zero byte)
 }
 
 // Magnitude statistics of the rows a pack wave converts (what the NEXT run's shift is chosen from): call once per row with
