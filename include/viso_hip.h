@@ -1268,8 +1268,8 @@ int viso_tsdf_render_gray(viso_tsdf* t, uint32_t min_weight, const viso_param* p
  * Limits: the gradient comes from 8 voxels, so the basin is about the gate wide; the distances are projective and averaged along the
  * fusing views' axes, so a surface at grazing incidence (80 degrees) pulls the pose off by tenths of a degree even from the truth;
  * below a voxel of about 0.05 m at KITTI's noise the steps stop shrinking before eps (status 2).  DESIGN.md 5.19 has the figures.
- * Out of scope: photometric terms from the gray sum, robust kernels beyond the gate, coarse-to-fine pyramids, alignment inside the
- * KITTI runners, loop closure, trilinear rendering.
+ * Out of scope: robust kernels beyond the gate, coarse-to-fine pyramids, alignment inside the KITTI runners, loop closure,
+ * trilinear rendering.  Photometric terms from the gray sum: "TSDF photometric align" below.
  * HIP kernel (tsdf_align.hip): tsdf_linearize_kernel, the lanes of a wave consecutive pixels of a row, a thread strides over
  * several pixels.  Lanes whose k0 equals their left neighbour's form a run; the run's head lane alone does the eight probes and
  * loads, the others take the 8 x (weight, sum) from it.  The 28 sums stay in registers and are reduced once: across the wave by DPP,
@@ -1313,6 +1313,90 @@ int viso_tsdf_align(viso_tsdf* t, const viso_tsdf_align_params* params, const in
 /* poses_guess: [t1 - t0][16]; records_out: [t1 - t0]. */
 int viso_batch_align_tsdf(viso_batch* b, viso_tsdf* t, int t0, int t1, const double* poses_guess, const viso_tsdf_align_params* params,
                           viso_tsdf_alignment* records_out);
+
+/* ------------------------------------------------ TSDF photometric align: "TSDF align" with a second row a pixel, from the gray
+ * sums (opt-in; NOT in the reference)
+ *
+ * A gray map ("TSDF intensity") keeps per voxel the sum of the intensities that updated it.  A used pixel of "TSDF align" therefore
+ * also has a model intensity, sampled trilinearly from the same eight voxels, and the difference to the pixel's own intensity is a
+ * second residual whose gradient comes from the model, not from the image: the pixel goes forward into the model.  The row holds the
+ * motions inside a plane, which the signed distance leaves free (limit (iv) of DESIGN.md 5.19).  Its seven entries are rounded
+ * to integers like the geometric ones and their products go into the same 28 sums, so the device output is bit-identical to
+ * tests/photo_align_ref.py.  This definition is the contract.  Everything is IEEE double in the operand order written, with no
+ * fused multiply-add.  The calls read the table only.  The calls of "TSDF align" are unchanged, on either kind of map.
+ * Inputs of a linearise: those of viso_tsdf_linearize, and
+ *   image        uint8 [rows][cols], the left image the map was computed from, pixel for pixel;
+ *   photo_weight lambda, finite and >= 0: pixels of disparity per gray level, which puts the row into the units of the geometric
+ *                one.  Default 1 / 32: a disparity residual is about 0.25 px, a voxel's mean intensity about 8 gray levels off on
+ *                a ramp; the quotient, not tuned;
+ *   photo_gate   finite and > 0, gray levels.  Default 255.0, which gates nothing.
+ *   The map must be a gray map.  A plain map or a null image: VISO_ERR_ARG before a device is touched; the checks that do not need the
+ *   map (those of "TSDF align", the image, lambda, the gate) come before the handle is looked at.  An overflowed map:
+ *   VISO_ERR_NOMEM.
+ * Per pixel (x, y): steps 1..8 of "TSDF align" are unchanged and decide whether the pixel is used; a used pixel's geometric row A is
+ *   exactly the plain one and is added by step 9.  Then, for a used pixel:
+ *   P1. i[dz][dy][dx] = (double)gray / (double)weight of the same eight voxels (usable by step 4: weight >= min_weight >= 1).
+ *   P2. Step 5's interpolation on i with the same t, in the same operand order: mu for psi, E_0..2 for D_0..2.  h_i = E_i / voxel,
+ *       gray levels per metre.
+ *   P3. r = mu - (double)image[y][x].  |r| > photo_gate: n_photo_gated += 1, the pixel adds no photometric row (its geometric row
+ *       stays).
+ *   P4. hc_j = (T[0][j] h_0 + T[1][j] h_1) + T[2][j] h_2.  The row: b_0..2 = hc_j lambda;  b_3 = (Y hc_2 - Z hc_1) lambda,
+ *       b_4 = (Z hc_0 - X hc_2) lambda,  b_5 = (X hc_1 - Y hc_0) lambda;  b_6 = r lambda.  There is no w: the residual is in
+ *       measurement units already.
+ *   P5. B_i = floor(b_i 256.0 + 0.5).  A value that is not finite or |B_i| >= 2^20: n_photo_clipped += 1, no photometric row.
+ *   P6. n_photo_used += 1; for 0 <= i <= j <= 6: N[i][j] += B_i B_j, into the same 28 sums; p += B_6 B_6.
+ *   Two products below 2^40 a pixel over at most 2^22 pixels: every sum stays below 2^63.  lambda = 0 gives B = 0: the 28 sums
+ *   are those of viso_tsdf_linearize.
+ * Output of a linearise: viso_tsdf_normal_gray; its `normal` holds the combined sums and the six counters of "TSDF align".
+ * Align (viso_tsdf_align_gray): steps a..f of "TSDF align" on the combined N, min_pixels against n_used.  With C = N[6][6] / 65536.0
+ *   and pp = p / 65536.0 of the final linearise:  a.cost = sqrt(C / n_used);  cost_geo = sqrt((C - pp) / n_used), pixels;
+ *   cost_photo = sqrt(pp / n_photo_used) / lambda, gray levels, and 0 when lambda = 0 or n_photo_used = 0;
+ *   a.cov = (C / max(n_used + n_photo_used - 6, 1)) H^-1.  On a status < 0, a.pose is the guess and every other number is zero.
+ *   The trace's entries are viso_tsdf_align_gray_step, under the rules of viso_tsdf_align's.
+ * Resident path: viso_batch_align_tsdf_gray is viso_batch_align_tsdf with frame t's image at images + (2 t) rows cols, the left
+ *   images the run read; each record is what viso_tsdf_align_gray gives for that map, image and guess, bit for bit.
+ *   VISO_ERR_ARG when the images' geometry is not the maps', as viso_batch_fuse_tsdf refuses on a gray map.
+ * Limits: the texture must vary over several voxels (the model's intensity is a voxel mean; finer texture is averaged away and
+ * aliases); constant exposure is assumed; the basin is still the gate's.  DESIGN.md 5.21 has the figures.
+ * Out of scope: exposure or gain compensation, robust kernels beyond the gate, image pyramids, RGB.
+ * HIP kernel (tsdf_align.hip): tsdf_gray_linearize_kernel, the body of tsdf_linearize_kernel instantiated with the intensity: a run's
+ * head lane also loads the gray sums of its eight voxels and hands them to its run, the pixel's byte is read along the row, the
+ * products of the second row add into the same 28 registers without a branch, and p and the three counters join the reduction:
+ * 38 words a frame.  No float atomics, no scratch, no workgroup waits for another. */
+typedef struct viso_tsdf_align_gray_params {   /* 64 bytes */
+    viso_tsdf_align_params geo;
+    double photo_weight;     /* lambda: pixels of disparity per gray level */
+    double photo_gate;       /* gray levels */
+} viso_tsdf_align_gray_params;
+
+typedef struct viso_tsdf_normal_gray {   /* 304 bytes */
+    viso_tsdf_normal normal; /* both rows' products; the counters of steps 1..9 */
+    int64_t p;               /* the photometric part of N[6][6] */
+    uint64_t n_photo_used, n_photo_gated, n_photo_clipped;
+} viso_tsdf_normal_gray;
+
+typedef struct viso_tsdf_alignment_gray {   /* 464 bytes */
+    viso_tsdf_alignment a;
+    double cost_geo;         /* rms geometric residual, pixels of disparity */
+    double cost_photo;       /* rms photometric residual, gray levels */
+    uint64_t n_photo_used;
+} viso_tsdf_alignment_gray;
+
+typedef struct viso_tsdf_align_gray_step {   /* 432 bytes */
+    double pose[16];
+    viso_tsdf_normal_gray normal;
+} viso_tsdf_align_gray_step;
+
+/* geo: viso_tsdf_align_params_default; photo_weight 1 / 32, photo_gate 255.0.  Host only. */
+void viso_tsdf_align_gray_params_default(viso_tsdf_align_gray_params* p);
+int viso_tsdf_linearize_gray(viso_tsdf* t, const viso_tsdf_align_gray_params* params, const int16_t* disp, const uint8_t* image, int rows,
+                             int cols, const viso_param* param, const double* pose_or_null, viso_tsdf_normal_gray* out);
+int viso_tsdf_align_gray(viso_tsdf* t, const viso_tsdf_align_gray_params* params, const int16_t* disp, const uint8_t* image, int rows, int cols,
+                         const viso_param* param, const double* pose_guess_or_null, viso_tsdf_alignment_gray* record_out,
+                         viso_tsdf_align_gray_step* trace_out_or_null, int trace_cap);
+/* poses_guess: [t1 - t0][16]; records_out: [t1 - t0]. */
+int viso_batch_align_tsdf_gray(viso_batch* b, viso_tsdf* t, int t0, int t1, const double* poses_guess,
+                               const viso_tsdf_align_gray_params* params, viso_tsdf_alignment_gray* records_out);
 
 /* ------------------------------------------------ Map eviction: the voxels outside a box leave a map, on the device (opt-in; NOT in
  * the reference)

@@ -21,7 +21,8 @@ from .abi import (DESC_LEN, MAP_DEFAULTS, MAP_ENTRY_DTYPE, MapCounters, MapParam
                   declare_sgm, declare_speckle, declare_subpixel, declare_window, f32p, f64p, i32p, i64p, intp, ptr,
                   TSDF_CROSSING_DTYPE, TSDF_DEFAULTS, TSDF_ENTRY_DTYPE, TSDF_GRAY_ENTRY_DTYPE, TSDF_MESH_VERTEX_DTYPE, TsdfCounters, TsdfParams,
                   declare_tsdf, TSDF_ALIGN_DEFAULTS, TSDF_ALIGN_STEP_DTYPE, TSDF_ALIGNMENT_DTYPE, TSDF_NORMAL_COUNTERS, TSDF_NORMAL_DTYPE,
-                  TsdfAlignParams, VoxelBox, declare_evict)
+                  TsdfAlignParams, VoxelBox, declare_evict, TSDF_ALIGN_GRAY_DEFAULTS, TSDF_ALIGN_GRAY_STEP_DTYPE, TSDF_ALIGNMENT_GRAY_DTYPE,
+                  TSDF_NORMAL_GRAY_COUNTERS, TSDF_NORMAL_GRAY_DTYPE, TsdfAlignGrayParams)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("VISO_HIP_SO") or os.path.join(_HERE, "libviso_hip.so")   # VISO_HIP_SO: another build of the library (A/B runs)
@@ -719,6 +720,16 @@ def tsdf_align_params(**params):
     return p
 
 
+def tsdf_align_gray_params(**params):
+    """viso_tsdf_align_gray_params: viso_tsdf_align_gray_params_default with the given fields replaced: those of tsdf_align_params,
+    photo_weight (pixels of disparity per gray level) and photo_gate (gray levels).  Needs no library."""
+    photo = {k: params.pop(k) for k in tuple(params) if k in TSDF_ALIGN_GRAY_DEFAULTS}
+    p = TsdfAlignGrayParams(geo=tsdf_align_params(**params), **TSDF_ALIGN_GRAY_DEFAULTS)
+    for k, v in photo.items():
+        setattr(p, k, float(v))
+    return p
+
+
 def tsdf_normal_matrix(normal):
     """The 28 sums of a TSDF_NORMAL_DTYPE record as the symmetric int64 [7][7] matrix N, and its counters as a dict."""
     N = np.zeros((7, 7), np.int64)
@@ -726,6 +737,14 @@ def tsdf_normal_matrix(normal):
     N[iu] = normal["n"]
     N.T[iu] = normal["n"]
     return N, {name: int(normal[name]) for name in TSDF_NORMAL_COUNTERS}
+
+
+def tsdf_normal_gray_matrix(normal):
+    """A TSDF_NORMAL_GRAY_DTYPE record as (N, p, counters): the matrix of tsdf_normal_matrix on the sums of both rows, the
+    photometric part p of N[6][6], and the nine counters as a dict."""
+    N, c = tsdf_normal_matrix(normal)
+    c.update({name: int(normal[name]) for name in TSDF_NORMAL_GRAY_COUNTERS})
+    return N, int(normal["p"]), c
 
 
 def tsdf_crossing_points(crossings, voxel):
@@ -1222,24 +1241,54 @@ class TsdfMap(_TableMap):
             raise ValueError(f"{where}: the pose must be a 4 x 4 matrix")
         return (d16,) + _pose_arg(where, pose)
 
-    def linearize(self, d16, param, pose=None, **params):
+    def _align_image(self, where, image, d16):
+        """The image of a photometric call: uint8, the map's shape, and only with a gray map."""
+        if not self.gray:
+            raise ValueError(f"{where}: an image goes with a gray map (TsdfMap(gray=True))")
+        image = np.ascontiguousarray(image)
+        if image.dtype != np.uint8 or image.shape != d16.shape:
+            raise ValueError(f"{where}: the image must be a uint8 array of the map's shape")
+        return image
+
+    def linearize(self, d16, param, pose=None, image=None, **params):
         """viso_tsdf_linearize: the integer normal equations of the frame-to-model alignment (include/viso_hip.h, "TSDF align") of
         one host int16 map at the 4 x 4 camera-to-world pose (None: the identity).  Returns (N, counters): the symmetric int64
         [7][7] matrix of the six entries of the rows and the residual, and a dict of n_points, n_used, n_missing, n_gated,
-        n_clipped, n_out_of_range.  params: the fields of tsdf_align_params.  Reads the map only."""
+        n_clipped, n_out_of_range.  params: the fields of tsdf_align_params.  Reads the map only.
+        image (uint8, the map's shape; a gray map): viso_tsdf_linearize_gray ("TSDF photometric align"), the left image the map was
+        computed from; params then also takes photo_weight and photo_gate, and the result is (N, p, counters): N with the products
+        of both rows, p the photometric part of N[6][6], and n_photo_used, n_photo_gated, n_photo_clipped among the counters."""
         d16, T, Tp = self._align_args("TsdfMap.linearize", d16, pose)
+        if image is not None:
+            image = self._align_image("TsdfMap.linearize", image, d16)
+            p, out = tsdf_align_gray_params(**params), np.zeros(1, TSDF_NORMAL_GRAY_DTYPE)
+            self._chk("viso_tsdf_linearize_gray", self.L.viso_tsdf_linearize_gray(self.h, C.byref(p), ptr(d16, C.c_int16), ptr(image, C.c_uint8),
+                                                                                  d16.shape[0], d16.shape[1], C.byref(param), Tp, out.ctypes.data))
+            return tsdf_normal_gray_matrix(out[0])
         p, out = tsdf_align_params(**params), np.zeros(1, TSDF_NORMAL_DTYPE)
         self._chk("viso_tsdf_linearize", self.L.viso_tsdf_linearize(self.h, C.byref(p), ptr(d16, C.c_int16), d16.shape[0], d16.shape[1],
                                                                     C.byref(param), Tp, out.ctypes.data))
         return tsdf_normal_matrix(out[0])
 
-    def align(self, d16, param, pose=None, trace=False, **params):
+    def align(self, d16, param, pose=None, trace=False, image=None, **params):
         """viso_tsdf_align: the pose at which the points of one host int16 map lie on the map's surface, from the guess `pose` (4 x 4,
         camera to world; None: the identity).  Returns a TSDF_ALIGNMENT_DTYPE record (pose, cov of (v, omega), cost in pixels of
         disparity, n_used, iters, status: 1 converged, 2 max_iters reached, < 0 failed and pose is the guess).  trace=True: a tuple
         with the TSDF_ALIGN_STEP_DTYPE array of the linearises (pose, normal), the last one included.  params: the fields of
-        tsdf_align_params.  Reads the map only."""
+        tsdf_align_params.  Reads the map only.
+        image (uint8, the map's shape; a gray map): viso_tsdf_align_gray ("TSDF photometric align"), every used pixel also pulls the
+        model's intensity to its own; params then also takes photo_weight and photo_gate, the record is a TSDF_ALIGNMENT_GRAY_DTYPE
+        one (the same fields, then cost_geo in pixels, cost_photo in gray levels and n_photo_used) and the trace a
+        TSDF_ALIGN_GRAY_STEP_DTYPE array."""
         d16, T, Tp = self._align_args("TsdfMap.align", d16, pose)
+        if image is not None:
+            image = self._align_image("TsdfMap.align", image, d16)
+            p, rec = tsdf_align_gray_params(**params), np.zeros(1, TSDF_ALIGNMENT_GRAY_DTYPE)
+            steps = np.zeros(p.geo.max_iters + 1 if trace and 1 <= p.geo.max_iters <= 50 else 0, TSDF_ALIGN_GRAY_STEP_DTYPE)
+            self._chk("viso_tsdf_align_gray", self.L.viso_tsdf_align_gray(self.h, C.byref(p), ptr(d16, C.c_int16), ptr(image, C.c_uint8), d16.shape[0],
+                                                                          d16.shape[1], C.byref(param), Tp, rec.ctypes.data,
+                                                                          steps.ctypes.data if len(steps) else None, len(steps)))
+            return (rec[0], steps[steps["pose"][:, 3, 3] == 1.0]) if trace else rec[0]
         p, rec = tsdf_align_params(**params), np.zeros(1, TSDF_ALIGNMENT_DTYPE)
         steps = np.zeros(p.max_iters + 1 if trace and 1 <= p.max_iters <= 50 else 0, TSDF_ALIGN_STEP_DTYPE)
         self._chk("viso_tsdf_align", self.L.viso_tsdf_align(self.h, C.byref(p), ptr(d16, C.c_int16), d16.shape[0], d16.shape[1], C.byref(param),
@@ -1478,15 +1527,22 @@ class Batch:
             raise ValueError("Batch.fuse_tsdf: poses must be [t1 - t0][4][4]")
         self._chk("viso_batch_fuse_tsdf", self.L.viso_batch_fuse_tsdf(self.h, tsdf.h, int(t0), t1, ptr(T, C.c_double)))
 
-    def align_tsdf(self, tsdf, poses, t0=0, t1=None, **params):
+    def align_tsdf(self, tsdf, poses, t0=0, t1=None, photo=False, **params):
         """viso_batch_align_tsdf: the resident maps of frames t0 .. t1-1 (t1 None: to the last frame) aligned against the TsdfMap, each
         on its own from the 4 x 4 guess poses[i]; no map is copied to the host.  Returns a TSDF_ALIGNMENT_DTYPE array [t1 - t0], each
         what TsdfMap.align gives for that map and guess.  params: the fields of tsdf_align_params.  The map must be on this batch's
-        context."""
+        context.
+        photo=True (a gray map): viso_batch_align_tsdf_gray, with frame t's resident left image; params also takes photo_weight and
+        photo_gate, and the records are TSDF_ALIGNMENT_GRAY_DTYPE ones: cost_geo, cost_photo and n_photo_used follow the fields."""
         t1 = self.nf if t1 is None else int(t1)
         T = np.ascontiguousarray(poses, dtype=np.float64)
         if T.ndim != 3 or T.shape[1:] != (4, 4) or T.shape[0] != t1 - int(t0):
             raise ValueError("Batch.align_tsdf: poses must be [t1 - t0][4][4]")
+        if photo:
+            p, rec = tsdf_align_gray_params(**params), np.zeros(len(T), TSDF_ALIGNMENT_GRAY_DTYPE)
+            self._chk("viso_batch_align_tsdf_gray", self.L.viso_batch_align_tsdf_gray(self.h, tsdf.h, int(t0), t1, ptr(T, C.c_double), C.byref(p),
+                                                                                      rec.ctypes.data))
+            return rec
         p, rec = tsdf_align_params(**params), np.zeros(len(T), TSDF_ALIGNMENT_DTYPE)
         self._chk("viso_batch_align_tsdf", self.L.viso_batch_align_tsdf(self.h, tsdf.h, int(t0), t1, ptr(T, C.c_double), C.byref(p),
                                                                         rec.ctypes.data))

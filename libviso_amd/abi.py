@@ -316,6 +316,8 @@ def declare_tsdf(lib):
         declare_tsdf_gray(lib)
     if hasattr(lib, "viso_tsdf_linearize"):
         declare_tsdf_align(lib)
+    if hasattr(lib, "viso_tsdf_linearize_gray"):
+        declare_tsdf_align_gray(lib)
 
 
 def declare_tsdf_gray(lib):
@@ -360,6 +362,37 @@ def declare_tsdf_align(lib):
     lib.viso_tsdf_linearize.argtypes = [vp, APP, i16p, C.c_int, C.c_int, C.POINTER(Param), f64p, vp]
     lib.viso_tsdf_align.argtypes = [vp, APP, i16p, C.c_int, C.c_int, C.POINTER(Param), f64p, vp, vp, C.c_int]
     lib.viso_batch_align_tsdf.argtypes = [vp, vp, C.c_int, C.c_int, f64p, APP, vp]
+
+
+class TsdfAlignGrayParams(C.Structure):
+    """struct viso_tsdf_align_gray_params (include/viso_hip.h, "TSDF photometric align")."""
+    _fields_ = [("geo", TsdfAlignParams), ("photo_weight", C.c_double), ("photo_gate", C.c_double)]
+
+    def ok(self, trunc_voxels=8):
+        return (self.geo.ok(trunc_voxels) and bool(np.isfinite(self.photo_weight)) and self.photo_weight >= 0
+                and bool(np.isfinite(self.photo_gate)) and self.photo_gate > 0)
+
+
+TSDF_ALIGN_GRAY_DEFAULTS = dict(photo_weight=1.0 / 32.0, photo_gate=255.0)   # viso_tsdf_align_gray_params_default, beside TSDF_ALIGN_DEFAULTS
+TSDF_NORMAL_GRAY_COUNTERS = ("n_photo_used", "n_photo_gated", "n_photo_clipped")
+# struct viso_tsdf_normal_gray (304 bytes), struct viso_tsdf_alignment_gray (464 bytes), struct viso_tsdf_align_gray_step (432 bytes)
+# (the leading struct of each is spelled out, so that a record has the plain one's fields and the new ones side by side)
+TSDF_NORMAL_GRAY_DTYPE = np.dtype([("n", np.int64, (28,))] + [(name, np.uint64) for name in TSDF_NORMAL_COUNTERS] + [("p", np.int64)]
+                                  + [(name, np.uint64) for name in TSDF_NORMAL_GRAY_COUNTERS])
+TSDF_ALIGNMENT_GRAY_DTYPE = np.dtype([("pose", np.float64, (4, 4)), ("cov", np.float64, (6, 6)), ("cost", np.float64), ("n_used", np.uint64),
+                                      ("iters", np.int32), ("status", np.int32), ("cost_geo", np.float64), ("cost_photo", np.float64),
+                                      ("n_photo_used", np.uint64)])
+TSDF_ALIGN_GRAY_STEP_DTYPE = np.dtype([("pose", np.float64, (4, 4)), ("normal", TSDF_NORMAL_GRAY_DTYPE)])
+
+
+def declare_tsdf_align_gray(lib):
+    """Prototypes of the photometric frame-to-model alignment (include/viso_hip.h, "TSDF photometric align")."""
+    i16p, u8p, vp, GPP = C.POINTER(C.c_int16), C.POINTER(C.c_uint8), C.c_void_p, C.POINTER(TsdfAlignGrayParams)
+    lib.viso_tsdf_align_gray_params_default.restype = None
+    lib.viso_tsdf_align_gray_params_default.argtypes = [GPP]
+    lib.viso_tsdf_linearize_gray.argtypes = [vp, GPP, i16p, u8p, C.c_int, C.c_int, C.POINTER(Param), f64p, vp]
+    lib.viso_tsdf_align_gray.argtypes = [vp, GPP, i16p, u8p, C.c_int, C.c_int, C.POINTER(Param), f64p, vp, vp, C.c_int]
+    lib.viso_batch_align_tsdf_gray.argtypes = [vp, vp, C.c_int, C.c_int, f64p, GPP, vp]
 
 
 class MotionCov(C.Structure):

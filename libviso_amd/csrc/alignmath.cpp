@@ -1,7 +1,7 @@
 // alignmath.cpp — the host arithmetic of the frame-to-model alignment (include/viso_hip.h, "TSDF align", steps a..f): on the 28
 // integers of a linearise, a 6 x 6 Cholesky solve, the increment of the pose and the loop's bookkeeping.  A few hundred flops an
 // iteration; the kernel is tsdf_align.hip's.  Every operand order here is the header's, so that tests/align_ref.py follows a
-// device trace step by step.
+// device trace step by step.  The photometric alignment ("TSDF photometric align") runs the same machine on the combined sums.
 #include "alignmath.h"
 
 #include <math.h>
@@ -83,20 +83,45 @@ struct AlignFrame {
     bool final_pending, done;
 };
 
-void align_fail(viso_tsdf_alignment* rec, const double guess[16], int status) {
-    memset(rec, 0, sizeof(*rec));
-    memcpy(rec->pose, guess, 16 * sizeof(double));
-    rec->status = status;
-}
-}   // namespace
+// The two kinds of alignment as the machine sees them: the linearise's sums, the record, the trace's entry; where the counters
+// of steps 1..9 and the plain record lie in them; the photometric rows of a linearise; what the final linearise adds to a record.
+struct AlignPlain {
+    using Normal = viso_tsdf_normal; using Record = viso_tsdf_alignment; using Step = viso_tsdf_align_step;
+    static const viso_tsdf_normal& geo(const Normal& nm) { return nm; }
+    static viso_tsdf_alignment& base(Record& r) { return r; }
+    static uint64_t photo_rows(const Normal&) { return 0; }
+    static void finish(Record&, const Normal&, double, double) {}
+};
+struct AlignGray {
+    using Normal = viso_tsdf_normal_gray; using Record = viso_tsdf_alignment_gray; using Step = viso_tsdf_align_gray_step;
+    static const viso_tsdf_normal& geo(const Normal& nm) { return nm.normal; }
+    static viso_tsdf_alignment& base(Record& r) { return r.a; }
+    static uint64_t photo_rows(const Normal& nm) { return nm.n_photo_used; }
+    static void finish(Record& r, const Normal& nm, double C, double lambda) {
+        const double pp = (double)nm.p / 65536.0;
+        r.cost_geo = sqrt((C - pp) / (double)nm.normal.n_used);
+        r.cost_photo = nm.n_photo_used && lambda > 0.0 ? sqrt(pp / (double)nm.n_photo_used) / lambda : 0.0;
+        r.n_photo_used = nm.n_photo_used;
+    }
+};
 
-int align_run(const viso_tsdf_align_params& p, int n, const double* guesses, const AlignLinearize& linearize, viso_tsdf_alignment* records,
-              viso_tsdf_align_step* trace, int trace_cap) {
+template <class K>
+void align_fail(typename K::Record* rec, const double guess[16], int status) {
+    memset(rec, 0, sizeof(*rec));
+    memcpy(K::base(*rec).pose, guess, 16 * sizeof(double));
+    K::base(*rec).status = status;
+}
+
+// Steps a..f and the final linearise for n frames, on the sums of whichever kind (the gray kind's N holds both rows' products).
+template <class K>
+int align_machine(const viso_tsdf_align_params& p, double lambda, int n, const double* guesses,
+                  const std::function<int(const double*, const unsigned long long*, typename K::Normal*)>& linearize,
+                  typename K::Record* records, typename K::Step* trace, int trace_cap) {
     static const double eye[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
     std::vector<AlignFrame> fr((size_t)n);
     std::vector<double> poses((size_t)n * 16), guess((size_t)n * 16);
     std::vector<unsigned long long> active((size_t)n);
-    std::vector<viso_tsdf_normal> normals((size_t)n);
+    std::vector<typename K::Normal> normals((size_t)n);
     for (int f = 0; f < n; ++f) {
         memcpy(&guess[(size_t)f * 16], guesses ? guesses + (size_t)f * 16 : eye, 16 * sizeof(double));
         memcpy(fr[f].T, &guess[(size_t)f * 16], 12 * sizeof(double));
@@ -116,20 +141,22 @@ int align_run(const viso_tsdf_align_params& p, int n, const double* guesses, con
         for (int f = 0; f < n; ++f) {
             AlignFrame& a = fr[f];
             if (a.done) continue;
+            const viso_tsdf_normal& nm = K::geo(normals[f]);
             if (f == 0 && trace && n_trace < trace_cap) {
                 memcpy(trace[n_trace].pose, a.T, 16 * sizeof(double));
                 trace[n_trace].normal = normals[f];
                 ++n_trace;
             }
             double H[36], b[6], C = 0.0, L[36];
-            const int bad = align_system(p, normals[f], H, b, &C, L);
-            if (bad) { align_fail(&records[f], &guess[(size_t)f * 16], bad); a.done = true; continue; }
+            const int bad = align_system(p, nm, H, b, &C, L);
+            if (bad) { align_fail<K>(&records[f], &guess[(size_t)f * 16], bad); a.done = true; continue; }
             if (a.final_pending) {
-                viso_tsdf_alignment& rec = records[f];
-                memset(&rec, 0, sizeof(rec));
+                memset(&records[f], 0, sizeof(records[f]));
+                viso_tsdf_alignment& rec = K::base(records[f]);
                 memcpy(rec.pose, a.T, 16 * sizeof(double));
-                const double n_used = (double)normals[f].n_used;
-                const double dof = normals[f].n_used > 7 ? (double)(normals[f].n_used - 6) : 1.0;
+                const double n_used = (double)nm.n_used;
+                const uint64_t rows = nm.n_used + K::photo_rows(normals[f]);
+                const double dof = rows > 7 ? (double)(rows - 6) : 1.0;
                 rec.cost = sqrt(C / n_used);
                 const double sigma2 = C / dof;
                 for (int j = 0; j < 6; ++j) {
@@ -138,7 +165,8 @@ int align_run(const viso_tsdf_align_params& p, int n, const double* guesses, con
                     align_solve(L, unit, col);
                     for (int i = 0; i < 6; ++i) rec.cov[6 * i + j] = sigma2 * col[i];
                 }
-                rec.n_used = normals[f].n_used; rec.iters = a.iters; rec.status = a.status;
+                rec.n_used = nm.n_used; rec.iters = a.iters; rec.status = a.status;
+                K::finish(records[f], normals[f], C, lambda);
                 a.done = true;
                 continue;
             }
@@ -146,7 +174,7 @@ int align_run(const viso_tsdf_align_params& p, int n, const double* guesses, con
             align_solve(L, b, x);
             bool finite = true;
             for (int i = 0; i < 6; ++i) { xi[i] = -x[i]; finite = finite && isfinite(xi[i]); }
-            if (!finite) { align_fail(&records[f], &guess[(size_t)f * 16], -3); a.done = true; continue; }
+            if (!finite) { align_fail<K>(&records[f], &guess[(size_t)f * 16], -3); a.done = true; continue; }
             align_increment(a.T, xi);
             a.iters += 1;
             const double nv = sqrt((xi[0] * xi[0] + xi[1] * xi[1]) + xi[2] * xi[2]), nw = sqrt((xi[3] * xi[3] + xi[4] * xi[4]) + xi[5] * xi[5]);
@@ -155,4 +183,15 @@ int align_run(const viso_tsdf_align_params& p, int n, const double* guesses, con
         }
     }
     return VISO_OK;
+}
+}   // namespace
+
+int align_run(const viso_tsdf_align_params& p, int n, const double* guesses, const AlignLinearize& linearize, viso_tsdf_alignment* records,
+              viso_tsdf_align_step* trace, int trace_cap) {
+    return align_machine<AlignPlain>(p, 0.0, n, guesses, linearize, records, trace, trace_cap);
+}
+
+int align_run_gray(const viso_tsdf_align_gray_params& p, int n, const double* guesses, const AlignLinearizeGray& linearize,
+                   viso_tsdf_alignment_gray* records, viso_tsdf_align_gray_step* trace, int trace_cap) {
+    return align_machine<AlignGray>(p.geo, p.photo_weight, n, guesses, linearize, records, trace, trace_cap);
 }

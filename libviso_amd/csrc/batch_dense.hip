@@ -215,3 +215,21 @@ extern "C" int viso_batch_align_tsdf(viso_batch* b, viso_tsdf* t, int t0, int t1
     return tsdf_align_resident(where, t, b->ctx, D.disp + (size_t)t0 * per, per, D.rows, D.cols, t1 - t0, b->sp.f, b->sp.cu, b->sp.cv, b->sp.base,
                                poses_guess, params, records_out);
 }
+
+// The same with the photometric row (tsdf_align.hip, "TSDF photometric align"): frame t's left image at images + 2 t per, which must
+// still be there with the maps' geometry, as viso_batch_fuse_tsdf asks of them for a gray map.
+extern "C" int viso_batch_align_tsdf_gray(viso_batch* b, viso_tsdf* t, int t0, int t1, const double* poses_guess,
+                                          const viso_tsdf_align_gray_params* params, viso_tsdf_alignment_gray* records_out) {
+    const char* where = "viso_batch_align_tsdf_gray";
+    if (!params || !records_out) { viso_set_error("%s: bad argument (non-null parameters and records)", where); return VISO_ERR_ARG; }
+    VISO_TRY(fuse_prelude(where, b, t, t0, t1, poses_guess));
+    const BatchDense& D = b->dense;
+    const size_t per = (size_t)D.rows * D.cols;
+    if (!b->images || b->img_rows != D.rows || b->img_cols != D.cols) {
+        viso_set_error("%s: the resident images (%d x %d) are not the maps' (%d x %d): the photometric row needs the images the maps were computed from",
+                       where, b->images ? b->img_cols : 0, b->images ? b->img_rows : 0, D.cols, D.rows);
+        return VISO_ERR_ARG;
+    }
+    return tsdf_align_gray_resident(where, t, b->ctx, D.disp + (size_t)t0 * per, per, b->images + 2 * (size_t)t0 * per, 2 * per, D.rows, D.cols,
+                                    t1 - t0, b->sp.f, b->sp.cu, b->sp.cv, b->sp.base, poses_guess, params, records_out);
+}

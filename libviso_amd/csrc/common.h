@@ -495,6 +495,10 @@ int tsdf_fuse_resident(const char* where, viso_tsdf* t, viso_ctx* c, const int16
 int tsdf_align_resident(const char* where, viso_tsdf* t, viso_ctx* c, const int16_t* disp, size_t mfs, int rows, int cols, int n_frames,
                         double f, double cu, double cv, double base, const double* poses, const viso_tsdf_align_params* params,
                         viso_tsdf_alignment* records);
+// the same with the photometric row ("TSDF photometric align"): frame f's 8-bit left image at image + f * ifs on the device
+int tsdf_align_gray_resident(const char* where, viso_tsdf* t, viso_ctx* c, const int16_t* disp, size_t mfs, const uint8_t* image, size_t ifs, int rows,
+                             int cols, int n_frames, double f, double cu, double cv, double base, const double* poses,
+                             const viso_tsdf_align_gray_params* params, viso_tsdf_alignment_gray* records);
 // covariance.hip: the opt-in motion covariance (viso_batch_set_covariance); one record per item, out[item], read from the item's
 // X, obs, m_ptr, ld, tr, ok, n_inl, inl (what ransac_refit_kernel left)
 int launch_motion_cov(hipStream_t s, const SolverItem* items_dev, int n_items, const SolverParamsDev& sp, int mode, double sigma,

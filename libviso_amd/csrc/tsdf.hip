@@ -606,7 +606,7 @@ static VoxelRegistry g_tsdfs = {{"TSDF", "TSDF map", "updates", "min_weight", "v
 
 VoxelRegistry& tsdf_registry() { return g_tsdfs; }
 void tsdf_view(viso_tsdf* t, TsdfView* out) {
-    out->t = t->t; out->voxel = t->p.voxel; out->s = t->s; out->trunc_voxels = t->p.trunc_voxels;
+    out->t = t->t; out->gray = t->gray; out->voxel = t->p.voxel; out->s = t->s; out->trunc_voxels = t->p.trunc_voxels;
 }
 
 static bool tsdf_params_ok(const viso_tsdf_params* p) {

@@ -1,5 +1,7 @@
 // tsdf_align.hip — opt-in frame-to-model alignment of a disparity map against a TSDF map (NOT in the reference: viso_tsdf_linearize,
-// viso_tsdf_align, viso_batch_align_tsdf; include/viso_hip.h, "TSDF align").  Direct tracking on the signed distance:
+// viso_tsdf_align, viso_batch_align_tsdf; include/viso_hip.h, "TSDF align"), and the same with a photometric row
+// from a gray map's sums of intensities (viso_tsdf_linearize_gray, viso_tsdf_align_gray, viso_batch_align_tsdf_gray; "TSDF
+// photometric align").  Direct tracking on the signed distance:
 // every valid pixel's back-projected point samples the distance trilinearly and contributes one row to a 6 x 6 Gauss-Newton system
 // whose entries are sums of integers, so the kernel's output is bit-identical to tests/align_ref.py however the sums are combined.
 //
@@ -13,6 +15,10 @@
 //                           and threads 0..33 add the workgroup's totals to the frame's 34 words: one 64-bit integer atomic each,
 //                           and none for a zero.  A frame whose flag is 0 (its alignment has finished) leaves at once.
 //                           No float atomics, no scratch; no workgroup waits for another; every probe loop is the table layer's.
+//   tsdf_gray_linearize_kernel   the same body (tsdf_linearize_body<true>): the head lane also loads gray[slot] of its eight voxels
+//                           (16 more ds_bpermute), the pixel's byte is read along the row as tsdf_gray_fuse_kernel reads it, the
+//                           second row's products add into the same 28 registers without a branch (a row that is not used adds
+//                           zeros), p and three counters join the reduction: 38 words a frame, 1216 bytes of LDS.
 // The table's layout is tsdf_table.h's, the probes and the runs voxel_hash.h's, the staging of a round voxel_host.h's
 // (voxel_linearize); the 6 x 6 solve and the loop are alignmath.cpp's.
 #include "common.h"
@@ -24,6 +30,7 @@
 #include <cstring>
 
 #define ALIGN_WORDS 34                  // viso_tsdf_normal: n[28], then the six counters
+#define ALIGN_GRAY_WORDS 38             // viso_tsdf_normal_gray: those, then p and the three photometric counters
 #define ALIGN_MAX_PIXELS (1ll << 22)
 #define ALIGN_BLOCKS 512u               // along x at most: a full KITTI frame is 3.6 pixels a thread
 
@@ -31,9 +38,16 @@ struct TsdfAlignArgs {
     VoxelFuseArgs v;                    // the maps, the poses [frames][12] and the calibration
     TsdfTable t;
     const unsigned long long* active;   // [frames]
-    unsigned long long* out;            // [frames][ALIGN_WORDS]
+    unsigned long long* out;            // [frames][ALIGN_WORDS]; the gray kernel's: [frames][ALIGN_GRAY_WORDS]
     double voxel, s, gate;              // gate: gate_voxels 1024
     uint32_t min_weight; int trips;     // pixels a thread
+};
+
+struct TsdfGrayAlignArgs {
+    TsdfAlignArgs a;
+    const unsigned long long* gray;     // the table's sums of intensities [slots]
+    const uint8_t* image; size_t ifs;   // frame f's image at image + f * ifs
+    double lambda, photo_gate;
 };
 
 // A_i of step 8; *clip set when the value is not finite or beyond 2^20
@@ -43,8 +57,31 @@ __device__ __forceinline__ int align_round(double a, bool* clip) {
     return (int)r;
 }
 
-__global__ __launch_bounds__(256) void tsdf_linearize_kernel(TsdfAlignArgs a) {
-    __shared__ unsigned long long part[4][ALIGN_WORDS];
+// step 5 on the eight corners m[dx + 2 dy + 4 dz]: the value and its derivative per voxel along x, y, z
+struct AlignSample { double psi, d0, d1, d2; };
+__device__ __forceinline__ AlignSample align_interpolate(double m0, double m1, double m2, double m3, double m4, double m5, double m6, double m7,
+                                                         double t0, double t1, double t2) {
+    // x?_zy is X?[dz][dy]
+    const double x1_00 = m1 - m0, x1_01 = m3 - m2, x1_10 = m5 - m4, x1_11 = m7 - m6;
+    const double x0_00 = m0 + t0 * x1_00, x0_01 = m2 + t0 * x1_01, x0_10 = m4 + t0 * x1_10, x0_11 = m6 + t0 * x1_11;
+    const double y1_0 = x0_01 - x0_00, y1_1 = x0_11 - x0_10;
+    const double y0_0 = x0_00 + t1 * y1_0, y0_1 = x0_10 + t1 * y1_1;
+    const double yx_0 = x1_00 + t1 * (x1_01 - x1_00), yx_1 = x1_10 + t1 * (x1_11 - x1_10);
+    const double d2 = y0_1 - y0_0;
+    const double psi = y0_0 + t2 * d2;
+    const double d0 = yx_0 + t2 * (yx_1 - yx_0);
+    const double d1 = y1_0 + t2 * (y1_1 - y1_0);
+    return AlignSample{psi, d0, d1, d2};
+}
+
+// The body of both linearise kernels.  GRAY: the run's head lane also loads the gray sums of its eight voxels and hands them to
+// its run (16 more ds_bpermute), the pixel's intensity is read along the row, and a used pixel's second row ("TSDF photometric
+// align", P1..P6) adds its products into the same 28 sums; p and the three photometric counters join the reduction.
+template <bool GRAY>
+__device__ __forceinline__ void tsdf_linearize_body(const TsdfAlignArgs& a, const unsigned long long* gray, const uint8_t* image, size_t ifs,
+                                                    double lambda, double photo_gate) {
+    constexpr int WORDS = GRAY ? ALIGN_GRAY_WORDS : ALIGN_WORDS;
+    __shared__ unsigned long long part[4][WORDS];
     const int fr = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (!a.active[fr]) return;   // the whole workgroup
     const double* T = a.v.poses + (size_t)fr * 12;
@@ -53,12 +90,16 @@ __global__ __launch_bounds__(256) void tsdf_linearize_kernel(TsdfAlignArgs a) {
     long long N[28];
 #pragma unroll
     for (int k = 0; k < 28; ++k) N[k] = 0;
+    long long P = 0;   // GRAY: the photometric part of N[27]
     unsigned long long n_points = 0, n_used = 0, n_missing = 0, n_gated = 0, n_clipped = 0, n_oor = 0;   // wave totals
+    unsigned long long n_photo_used = 0, n_photo_gated = 0, n_photo_clipped = 0;
     const size_t stride = (size_t)gridDim.x * 256;
     size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     for (int trip = 0; trip < a.trips; ++trip, i += stride) {   // the same trip in every lane
         double X = 0.0, Y = 0.0, Z = 1.0;
         const bool point = voxel_point(a.v, i, fr, &X, &Y, &Z);
+        double pix = 0.0;
+        if (GRAY && point) pix = (double)image[(size_t)fr * ifs + i];   // i is inside the image: voxel_point has checked it
         const unsigned long long pm = __ballot(point);
         if (!pm) continue;   // the whole wave
         n_points += __popcll(pm);
@@ -86,8 +127,9 @@ __global__ __launch_bounds__(256) void tsdf_linearize_kernel(TsdfAlignArgs a) {
         const int from = voxel_run_head(head, lane);
         uint32_t w[8];
         long long sm[8];
+        unsigned long long gr[8];
 #pragma unroll
-        for (int c = 0; c < 8; ++c) { w[c] = 0u; sm[c] = 0; }   // 0: not in the table
+        for (int c = 0; c < 8; ++c) { w[c] = 0u; sm[c] = 0; gr[c] = 0ull; }   // 0: not in the table
         if (head && have) {
 #pragma unroll
             for (int c = 0; c < 8; ++c) {
@@ -95,6 +137,7 @@ __global__ __launch_bounds__(256) void tsdf_linearize_kernel(TsdfAlignArgs a) {
                 if (voxel_find(a.t.head.keys, a.t.head.mask, voxel_neighbour(key, (uint32_t)c), &slot)) {
                     w[c] = a.t.weight[slot];
                     sm[c] = (long long)a.t.sum[slot];
+                    if (GRAY) gr[c] = gray[slot];
                 }
             }
         }
@@ -103,6 +146,7 @@ __global__ __launch_bounds__(256) void tsdf_linearize_kernel(TsdfAlignArgs a) {
         for (int c = 0; c < 8; ++c) {
             w[c] = (uint32_t)__shfl((int)w[c], from);
             sm[c] = __shfl(sm[c], from);
+            if (GRAY) gr[c] = (unsigned long long)__shfl((long long)gr[c], from);
             usable = usable && w[c] >= a.min_weight;   // (min_weight >= 1: a voxel that is not in the table is not usable either)
         }
         n_missing += __popcll(__ballot(have && !usable));
@@ -112,16 +156,8 @@ __global__ __launch_bounds__(256) void tsdf_linearize_kernel(TsdfAlignArgs a) {
             const double m0 = (double)sm[0] / (double)w[0], m1 = (double)sm[1] / (double)w[1], m2 = (double)sm[2] / (double)w[2],
                          m3 = (double)sm[3] / (double)w[3], m4 = (double)sm[4] / (double)w[4], m5 = (double)sm[5] / (double)w[5],
                          m6 = (double)sm[6] / (double)w[6], m7 = (double)sm[7] / (double)w[7];
-            // step 5; the corner dx + 2 dy + 4 dz is m[dz][dy][dx], x?_zy is X?[dz][dy]
-            const double x1_00 = m1 - m0, x1_01 = m3 - m2, x1_10 = m5 - m4, x1_11 = m7 - m6;
-            const double x0_00 = m0 + t0 * x1_00, x0_01 = m2 + t0 * x1_01, x0_10 = m4 + t0 * x1_10, x0_11 = m6 + t0 * x1_11;
-            const double y1_0 = x0_01 - x0_00, y1_1 = x0_11 - x0_10;
-            const double y0_0 = x0_00 + t1 * y1_0, y0_1 = x0_10 + t1 * y1_1;
-            const double yx_0 = x1_00 + t1 * (x1_01 - x1_00), yx_1 = x1_10 + t1 * (x1_11 - x1_10);
-            const double d2 = y0_1 - y0_0;
-            const double psi = y0_0 + t2 * d2;
-            const double d0 = yx_0 + t2 * (yx_1 - yx_0);
-            const double d1 = y1_0 + t2 * (y1_1 - y1_0);
+            const AlignSample ps = align_interpolate(m0, m1, m2, m3, m4, m5, m6, m7, t0, t1, t2);   // the corner dx + 2 dy + 4 dz is m[dz][dy][dx]
+            const double psi = ps.psi, d0 = ps.d0, d1 = ps.d1, d2 = ps.d2;
             if (fabs(psi) > a.gate) {
                 gated = true;
             } else {
@@ -151,10 +187,48 @@ __global__ __launch_bounds__(256) void tsdf_linearize_kernel(TsdfAlignArgs a) {
 #pragma unroll
             for (int q = p; q < 7; ++q, ++at) N[at] += (long long)A[p] * (long long)A[q];   // |A| < 2^20: below 2^40 each
         }
+        if (GRAY) {
+            bool pgated = false, pclip = false;
+            int B0 = 0, B1 = 0, B2 = 0, B3 = 0, B4 = 0, B5 = 0, B6 = 0;
+            if (used) {   // every w[c] >= min_weight >= 1
+                const AlignSample is = align_interpolate((double)gr[0] / (double)w[0], (double)gr[1] / (double)w[1], (double)gr[2] / (double)w[2],
+                                                         (double)gr[3] / (double)w[3], (double)gr[4] / (double)w[4], (double)gr[5] / (double)w[5],
+                                                         (double)gr[6] / (double)w[6], (double)gr[7] / (double)w[7], t0, t1, t2);
+                const double e0 = is.d0, e1 = is.d1, e2 = is.d2;
+                const double r = is.psi - pix;
+                if (fabs(r) > photo_gate) {
+                    pgated = true;
+                } else {
+                    const double h0 = e0 / a.voxel, h1 = e1 / a.voxel, h2 = e2 / a.voxel;
+                    const double c0 = (T0 * h0 + T4 * h1) + T8 * h2;
+                    const double c1 = (T1 * h0 + T5 * h1) + T9 * h2;
+                    const double c2 = (T2 * h0 + T6 * h1) + T10 * h2;
+                    B0 = align_round(c0 * lambda, &pclip);
+                    B1 = align_round(c1 * lambda, &pclip);
+                    B2 = align_round(c2 * lambda, &pclip);
+                    B3 = align_round((Y * c2 - Z * c1) * lambda, &pclip);
+                    B4 = align_round((Z * c0 - X * c2) * lambda, &pclip);
+                    B5 = align_round((X * c1 - Y * c0) * lambda, &pclip);
+                    B6 = align_round(r * lambda, &pclip);
+                }
+            }
+            n_photo_gated += __popcll(__ballot(pgated));
+            n_photo_clipped += __popcll(__ballot(pclip));
+            const bool pused = used && !pgated && !pclip;
+            n_photo_used += __popcll(__ballot(pused));
+            const int B[7] = {pused ? B0 : 0, pused ? B1 : 0, pused ? B2 : 0, pused ? B3 : 0, pused ? B4 : 0, pused ? B5 : 0, pused ? B6 : 0};
+            at = 0;
+#pragma unroll
+            for (int p = 0; p < 7; ++p) {
+#pragma unroll
+                for (int q = p; q < 7; ++q, ++at) N[at] += (long long)B[p] * (long long)B[q];   // the second product below 2^40
+            }
+            P += (long long)B[6] * (long long)B[6];
+        }
     }
     // the wave's totals to lane 63, the four waves' through LDS, the workgroup's with one atomic a word
 #ifdef VISO_ALIGN_WAVE_ATOMICS   // the variant that lost: every wave adds its own totals, no LDS
-    unsigned long long* out = a.out + (size_t)fr * ALIGN_WORDS;
+    unsigned long long* out = a.out + (size_t)fr * WORDS;
 #pragma unroll
     for (int k = 0; k < 28; ++k) {
         const unsigned long long v = viso_wave_sum63((unsigned long long)N[k]);
@@ -164,6 +238,14 @@ __global__ __launch_bounds__(256) void tsdf_linearize_kernel(TsdfAlignArgs a) {
         const unsigned long long c[6] = {n_points, n_used, n_missing, n_gated, n_clipped, n_oor};
 #pragma unroll
         for (int k = 0; k < 6; ++k) if (c[k]) atomicAdd(out + 28 + k, c[k]);
+    }
+    if (GRAY) {
+        const unsigned long long v = viso_wave_sum63((unsigned long long)P);
+        if (lane == 63) {
+            const unsigned long long c[4] = {v, n_photo_used, n_photo_gated, n_photo_clipped};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) if (c[k]) atomicAdd(out + 34 + k, c[k]);
+        }
     }
     (void)part; (void)wave;
 #else
@@ -176,12 +258,23 @@ __global__ __launch_bounds__(256) void tsdf_linearize_kernel(TsdfAlignArgs a) {
         part[wave][28] = n_points; part[wave][29] = n_used; part[wave][30] = n_missing;
         part[wave][31] = n_gated; part[wave][32] = n_clipped; part[wave][33] = n_oor;
     }
+    if (GRAY) {
+        const unsigned long long v = viso_wave_sum63((unsigned long long)P);
+        if (lane == 63) {
+            part[wave][34] = v; part[wave][35] = n_photo_used; part[wave][36] = n_photo_gated; part[wave][37] = n_photo_clipped;
+        }
+    }
     __syncthreads();
-    if (threadIdx.x < ALIGN_WORDS) {
+    if (threadIdx.x < WORDS) {
         const unsigned long long v = (part[0][threadIdx.x] + part[1][threadIdx.x]) + (part[2][threadIdx.x] + part[3][threadIdx.x]);
-        if (v) atomicAdd(a.out + (size_t)fr * ALIGN_WORDS + threadIdx.x, v);
+        if (v) atomicAdd(a.out + (size_t)fr * WORDS + threadIdx.x, v);
     }
 #endif
+}
+
+__global__ __launch_bounds__(256) void tsdf_linearize_kernel(TsdfAlignArgs a) { tsdf_linearize_body<false>(a, nullptr, nullptr, 0, 0.0, 0.0); }
+__global__ __launch_bounds__(256) void tsdf_gray_linearize_kernel(TsdfGrayAlignArgs g) {
+    tsdf_linearize_body<true>(g.a, g.gray, g.image, g.ifs, g.lambda, g.photo_gate);
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------------
@@ -223,14 +316,30 @@ static int align_check(const char* where, const viso_tsdf_align_params* p, int r
     return VISO_OK;
 }
 
+// the photometric side of a call: null for a plain alignment
+struct AlignPhoto {
+    const viso_tsdf_align_gray_params* p;
+    const uint8_t* image; size_t ifs;        // frame f's image at image + f * ifs on the map's device, or
+    const uint8_t* host_image;               // one host image, staged like the map
+    viso_tsdf_normal_gray* linearize_out;
+    viso_tsdf_alignment_gray* records;
+    viso_tsdf_align_gray_step* trace;
+};
+
 // The alignment of n device maps (frame f at disp + f * mfs, on the map's device) behind align_check: the handle entered and locked
 // like an extraction over all of its linearises.  ctx (or null): the context the maps live on, which must be the map's.
-// linearize_out set: one linearise at the guesses and nothing else.
+// linearize_out set: one linearise at the guesses and nothing else.  photo set: the photometric alignment of a gray map, whose
+// outputs are photo's; the plain ones are null then.
 static int align_device(const char* where, viso_tsdf* t, viso_ctx* ctx, const viso_tsdf_align_params* p, const int16_t* disp, size_t mfs,
                         const int16_t* host_disp, int rows, int cols, int n, double f, double cu, double cv, double base, const double* guesses,
-                        viso_tsdf_normal* linearize_out, viso_tsdf_alignment* records, viso_tsdf_align_step* trace, int trace_cap) {
+                        viso_tsdf_normal* linearize_out, viso_tsdf_alignment* records, viso_tsdf_align_step* trace, int trace_cap,
+                        const AlignPhoto* photo = nullptr) {
     VoxelRegistry& reg = tsdf_registry();
     if (!voxel_known(reg, t)) { viso_set_error("%s: not a live TSDF handle", where); return VISO_ERR_ARG; }
+    if (photo && !tsdf_is_gray(t)) {   // before a device is touched
+        viso_set_error("%s: the TSDF map carries no intensity (viso_tsdf_create_gray makes one that does)", where);
+        return VISO_ERR_ARG;
+    }
     int r;
     VoxelHost* h;
     if ((r = voxel_enter(where, reg, t, &h)) < 0) return r;
@@ -248,6 +357,12 @@ static int align_device(const char* where, viso_tsdf* t, viso_ctx* ctx, const vi
         if ((r = voxel_stage_map(where, h, host_disp, px, &disp)) < 0) return r;
         mfs = px;
     }
+    const uint8_t* image = photo ? photo->image : nullptr;
+    size_t ifs = photo ? photo->ifs : 0;
+    if (photo && photo->host_image) {
+        if ((r = voxel_stage_image(where, h, photo->host_image, px, &image)) < 0) return r;
+        ifs = px;
+    }
     TsdfAlignArgs a;
     a.v.mfs = mfs; a.v.rows = rows; a.v.cols = cols; a.v.min_disp16 = h->min_disp16; a.v._pad = 0;
     a.v.f = f; a.v.cu = cu; a.v.cv = cv; a.v.base = base;
@@ -257,6 +372,24 @@ static int align_device(const char* where, viso_tsdf* t, viso_ctx* ctx, const vi
     const unsigned blocks_x = blocks < ALIGN_BLOCKS ? (unsigned)blocks : ALIGN_BLOCKS;
     a.trips = (int)((px + (size_t)blocks_x * 256 - 1) / ((size_t)blocks_x * 256));
     static_assert(sizeof(viso_tsdf_normal) == ALIGN_WORDS * sizeof(unsigned long long), "the kernel's words are the struct");
+    static_assert(sizeof(viso_tsdf_normal_gray) == ALIGN_GRAY_WORDS * sizeof(unsigned long long), "the gray kernel's words are the struct");
+    static const double eye[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    const unsigned long long one = 1ull;
+    if (photo) {
+        const AlignLinearizeGray linearize = [&](const double* poses, const unsigned long long* active, viso_tsdf_normal_gray* out) {
+            return voxel_linearize(where, h, poses, active, n, ALIGN_GRAY_WORDS, blocks_x, reinterpret_cast<unsigned long long*>(out),
+                                   [&](const double* d_poses, const unsigned long long* d_active, unsigned long long* d_out, int frame0, dim3 grid, hipStream_t st) {
+                TsdfGrayAlignArgs g;
+                g.a = a;
+                g.a.v.disp = disp + (size_t)frame0 * mfs; g.a.v.poses = d_poses; g.a.active = d_active; g.a.out = d_out;
+                g.gray = view.gray; g.image = image + (size_t)frame0 * ifs; g.ifs = ifs;
+                g.lambda = photo->p->photo_weight; g.photo_gate = photo->p->photo_gate;
+                hipLaunchKernelGGL(tsdf_gray_linearize_kernel, grid, dim3(256), 0, st, g);
+            });
+        };
+        if (photo->linearize_out) return linearize(guesses ? guesses : eye, &one, photo->linearize_out);
+        return align_run_gray(*photo->p, n, guesses, linearize, photo->records, photo->trace, trace_cap);
+    }
     const AlignLinearize linearize = [&](const double* poses, const unsigned long long* active, viso_tsdf_normal* out) {
         return voxel_linearize(where, h, poses, active, n, ALIGN_WORDS, blocks_x, reinterpret_cast<unsigned long long*>(out),
                                [&](const double* d_poses, const unsigned long long* d_active, unsigned long long* d_out, int frame0, dim3 grid, hipStream_t st) {
@@ -265,11 +398,7 @@ static int align_device(const char* where, viso_tsdf* t, viso_ctx* ctx, const vi
             hipLaunchKernelGGL(tsdf_linearize_kernel, grid, dim3(256), 0, st, g);
         });
     };
-    if (linearize_out) {
-        static const double eye[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-        const unsigned long long one = 1ull;
-        return linearize(guesses ? guesses : eye, &one, linearize_out);
-    }
+    if (linearize_out) return linearize(guesses ? guesses : eye, &one, linearize_out);
     return align_run(*p, n, guesses, linearize, records, trace, trace_cap);
 }
 
@@ -300,4 +429,56 @@ int tsdf_align_resident(const char* where, viso_tsdf* t, viso_ctx* c, const int1
                         viso_tsdf_alignment* records) {
     VISO_TRY(align_check(where, params, rows, cols, f, cu, cv, base, poses, n_frames));
     return align_device(where, t, c, params, disp, mfs, nullptr, rows, cols, n_frames, f, cu, cv, base, poses, nullptr, records, nullptr, 0);
+}
+
+// ---- the photometric alignment (include/viso_hip.h, "TSDF photometric align") ----------------------------------------------------------
+extern "C" void viso_tsdf_align_gray_params_default(viso_tsdf_align_gray_params* p) {
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    viso_tsdf_align_params_default(&p->geo);
+    p->photo_weight = 1.0 / 32.0; p->photo_gate = 255.0;
+}
+
+// What does not need the map: the image, the photometric parameters, then align_check.
+static int align_gray_check(const char* where, const viso_tsdf_align_gray_params* p, bool image, int rows, int cols, double f, double cu, double cv,
+                            double base, const double* poses, int n) {
+    if (!p || !image) { viso_set_error("%s: bad argument (non-null parameters and image)", where); return VISO_ERR_ARG; }
+    if (!(std::isfinite(p->photo_weight) && p->photo_weight >= 0.0 && std::isfinite(p->photo_gate) && p->photo_gate > 0.0)) {
+        viso_set_error("%s: bad argument (parameters: a finite photo_weight >= 0 and a finite photo_gate > 0)", where);
+        return VISO_ERR_ARG;
+    }
+    return align_check(where, &p->geo, rows, cols, f, cu, cv, base, poses, n);
+}
+
+extern "C" int viso_tsdf_linearize_gray(viso_tsdf* t, const viso_tsdf_align_gray_params* params, const int16_t* disp, const uint8_t* image, int rows,
+                                        int cols, const viso_param* param, const double* pose_or_null, viso_tsdf_normal_gray* out) {
+    const char* where = "viso_tsdf_linearize_gray";
+    if (!disp || !param || !out) { viso_set_error("%s: bad argument (non-null map, calibration and output)", where); return VISO_ERR_ARG; }
+    VISO_TRY(align_gray_check(where, params, image != nullptr, rows, cols, param->f, param->cu, param->cv, param->base, pose_or_null, 1));
+    const AlignPhoto photo = {params, nullptr, 0, image, out, nullptr, nullptr};
+    return align_device(where, t, nullptr, &params->geo, nullptr, 0, disp, rows, cols, 1, param->f, param->cu, param->cv, param->base, pose_or_null,
+                        nullptr, nullptr, nullptr, 0, &photo);
+}
+
+extern "C" int viso_tsdf_align_gray(viso_tsdf* t, const viso_tsdf_align_gray_params* params, const int16_t* disp, const uint8_t* image, int rows,
+                                    int cols, const viso_param* param, const double* pose_guess_or_null, viso_tsdf_alignment_gray* record_out,
+                                    viso_tsdf_align_gray_step* trace_out_or_null, int trace_cap) {
+    const char* where = "viso_tsdf_align_gray";
+    if (!disp || !param || !record_out || trace_cap < 0 || (trace_cap && !trace_out_or_null)) {
+        viso_set_error("%s: bad argument (non-null map, calibration and record, trace_cap >= 0 and 0 without a trace)", where);
+        return VISO_ERR_ARG;
+    }
+    VISO_TRY(align_gray_check(where, params, image != nullptr, rows, cols, param->f, param->cu, param->cv, param->base, pose_guess_or_null, 1));
+    const AlignPhoto photo = {params, nullptr, 0, image, nullptr, record_out, trace_out_or_null};
+    return align_device(where, t, nullptr, &params->geo, nullptr, 0, disp, rows, cols, 1, param->f, param->cu, param->cv, param->base,
+                        pose_guess_or_null, nullptr, nullptr, nullptr, trace_cap, &photo);
+}
+
+int tsdf_align_gray_resident(const char* where, viso_tsdf* t, viso_ctx* c, const int16_t* disp, size_t mfs, const uint8_t* image, size_t ifs, int rows,
+                             int cols, int n_frames, double f, double cu, double cv, double base, const double* poses,
+                             const viso_tsdf_align_gray_params* params, viso_tsdf_alignment_gray* records) {
+    VISO_TRY(align_gray_check(where, params, image != nullptr, rows, cols, f, cu, cv, base, poses, n_frames));
+    const AlignPhoto photo = {params, image, ifs, nullptr, nullptr, records, nullptr};
+    return align_device(where, t, c, &params->geo, disp, mfs, nullptr, rows, cols, n_frames, f, cu, cv, base, poses, nullptr, nullptr, nullptr, 0,
+                        &photo);
 }

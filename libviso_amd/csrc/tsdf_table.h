@@ -10,9 +10,10 @@ struct TsdfTable {
     unsigned long long* sum; uint32_t* weight;   // [slots] i64 (added as u64, two's complement), [slots]
 };
 
-// a live map's table as a reader takes it (a gray map's too: only weight and sum)
+// a live map's table as a reader takes it (gray: a gray map's sums of intensities [slots], null for a plain map)
 struct TsdfView {
     TsdfTable t;
+    const unsigned long long* gray;
     double voxel, s;      // s = voxel / 1024
     int trunc_voxels;
 };

@@ -89,6 +89,8 @@ int voxel_render(const char* where, VoxelRegistry& reg, const void* handle, size
                  uint32_t* weight_out, const VoxelRenderLaunch& launch, uint8_t* gray_out = nullptr);
 // A host map of px pixels into the fuse's staging d_disp (grow-only), on the stream; *d_disp: where it is.  h is entered and locked.
 int voxel_stage_map(const char* where, VoxelHost* h, const int16_t* disp, size_t px, const int16_t** d_disp);
+// The same for a host image of px bytes into d_image (grow-only): the image of a photometric linearise.
+int voxel_stage_image(const char* where, VoxelHost* h, const uint8_t* image, size_t px, const uint8_t** d_image);
 // One linearise of an alignment (include/viso_hip.h, "TSDF align") for n frames: h is entered, locked and not overflowed (the
 // caller holds the lock over the whole alignment).  The poses [n][16] as [n][12], the flags active [n] (0: the frame's lanes
 // leave at once) and `words` zeroed 64-bit sums a frame go through d_pose (grow-only), the groups of frames are started by `launch`

@@ -364,6 +364,15 @@ int voxel_stage_map(const char* where, VoxelHost* h, const int16_t* disp, size_t
     return VISO_OK;
 }
 
+int voxel_stage_image(const char* where, VoxelHost* h, const uint8_t* image, size_t px, const uint8_t** d_image) {
+    hipStream_t s = h->ctx->stream;
+    int r;
+    if ((r = voxel_grow(where, &h->d_image, &h->d_image_bytes, px, s)) < 0) return r;
+    HIP_TRY(hipMemcpyAsync(h->d_image, image, px, hipMemcpyHostToDevice, s));
+    *d_image = h->d_image;
+    return VISO_OK;
+}
+
 int voxel_linearize(const char* where, VoxelHost* h, const double* poses, const unsigned long long* active, int n, size_t words,
                     unsigned blocks_x, unsigned long long* out, const VoxelLinearizeLaunch& launch) {
     hipStream_t s = h->ctx->stream;

@@ -1,6 +1,6 @@
 """python -m libviso_amd.fuse_map DISPARITY_DIR POSES.txt CALIB.txt OUT.ply [--voxel V --min-count N --min-disp PX --frames B E]
                                  [--surface | --mesh [--trunc T --min-weight N] [--render DIR [--render-depth M]] [--gray IMAGE_DIR]
-                                                     [--align [--aligned-poses FILE --align-voxel-gate G]]]
+                                                     [--align [--aligned-poses FILE --align-voxel-gate G --align-photo WEIGHT]]]
                                  [--window METRES [--archive FILE.npy]]
 
 Fuses the maps a KITTI runner wrote with --disparity DIR and the poses of its pose file into one voxel map on the device
@@ -32,6 +32,9 @@ float32 centroid of each voxel, count the number of points fused into it.
                  ends with status >= 1, otherwise at that guess.  --align-voxel-gate G: the gate in voxels (1.0, at most --trunc);
                  --min-weight applies to the voxels the alignment reads.  --aligned-poses FILE: the poses the maps were fused at, in
                  the format of POSES.txt.  The statuses are counted in the tool's output.
+  --align-photo WEIGHT  with --align and --gray: every used pixel also pulls the model's intensity to its own (include/viso_hip.h,
+                 "TSDF photometric align"), which holds the motions that a flat scene leaves free.  WEIGHT: pixels of disparity per
+                 gray level (the library's default is 0.03125).  Without it --align is the alignment on the distance alone.
   --window METRES  keep the map on the device to a cube of this half side around the camera (include/viso_hip.h, "Map eviction"):
                  before map i is fused (and, with --align, aligned), every voxel outside the box of voxels that the cube around the
                  translation of pose i touches leaves the table, on the device, and is appended to an archive on the host.  So a
@@ -240,6 +243,8 @@ def main(argv=None):
     ap.add_argument("--align", action="store_true", help="with --surface or --mesh: align every map against the model before it is fused")
     ap.add_argument("--aligned-poses", metavar="FILE", help="with --align: write the poses the maps were fused at")
     ap.add_argument("--align-voxel-gate", type=float, default=1.0, metavar="G", help="with --align: the gate in voxels (1.0)")
+    ap.add_argument("--align-photo", type=float, default=None, metavar="WEIGHT", help="with --align and --gray: add the photometric row, "
+                    "at this many pixels of disparity per gray level")
     ap.add_argument("--window", type=float, default=None, metavar="METRES", help="keep the map to a cube of this half side around the camera; "
                     "what leaves it goes to an archive on the host (OUT.ply: the whole map without --surface or --mesh, else the live window)")
     ap.add_argument("--archive", metavar="FILE.npy", help="with --window: write the merged evicted voxels as a numpy array of entries")
@@ -252,6 +257,8 @@ def main(argv=None):
         ap.error("--align needs --surface or --mesh (only a TSDF map is aligned against)")
     if a.aligned_poses and not a.align:
         ap.error("--aligned-poses needs --align")
+    if a.align_photo is not None and not (a.align and a.gray):
+        ap.error("--align-photo needs --align and --gray (the photometric row reads a gray TSDF map and the maps' images)")
     if a.render and not (a.surface or a.mesh):
         ap.error("--render needs --surface or --mesh (only a TSDF map is rendered)")
     if a.gray and not (a.surface or a.mesh):
@@ -299,7 +306,8 @@ def main(argv=None):
                 pose = poses[i]
                 if a.align and used:
                     pose = used[-1] @ np.linalg.inv(poses[i - 1]) @ poses[i]
-                    rec = tsdf.align(m, prm, pose, min_weight=a.min_weight, gate_voxels=a.align_voxel_gate)
+                    photo = {} if a.align_photo is None else dict(image=image, photo_weight=a.align_photo)
+                    rec = tsdf.align(m, prm, pose, min_weight=a.min_weight, gate_voxels=a.align_voxel_gate, **photo)
                     statuses[int(rec["status"])] = statuses.get(int(rec["status"]), 0) + 1
                     if rec["status"] >= 1:
                         pose = rec["pose"].copy()

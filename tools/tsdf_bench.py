@@ -27,6 +27,10 @@ repetitions):
                (two rounds of one launch each: time per round and per frame and round), and `align`, the call with max_iters 10
                (its rounds: the largest iteration count + 1, from the records).  The yardstick is `render` of the same views in the
                same process (`render_same`): a linearise does eight probes a pixel where a render marches 50..120.
+  align_gray   (include/viso_hip.h, "TSDF photometric align") Batch.align_tsdf(photo=True) of the same frames and guesses against the
+               gray map, with the resident left images, lambda 1/32: `linearize_gray` (max_iters 1) and `align_gray` (max_iters 10),
+               beside `linearize` and `align` in the same process, alternated: 16 more 8-byte loads a run head, one more byte a
+               pixel, a second set of 28 products.
 n_updates / n_points from viso_tsdf_stats is the number of voxels a pixel's band touches.  --kernel-only runs clear + fuse_tsdf
 --reps times, the extractions and the render once and the two align calls --reps times: the run to put under `rocprofv3 --kernel-trace --stats` for the kernels' own times.  The
 count the result is held against (not a measurement) is printed with it."""
@@ -114,6 +118,11 @@ def main():
     def align(max_iters):
         return b.align_tsdf(tsdf, guesses, t0=0, t1=na, max_iters=max_iters)
 
+    has_align_gray = hasattr(libviso_amd.load(), "viso_tsdf_linearize_gray")   # (likewise)
+
+    def align_gray(max_iters):
+        return b.align_tsdf(gmap, guesses, t0=0, t1=na, photo=True, max_iters=max_iters)
+
     def render_same():
         return tsdf.render(seq["param"], (rows, cols), poses[:na], max_depth=40.0, min_weight=2)
 
@@ -147,8 +156,10 @@ def main():
             gmap.clear(); b.fuse_tsdf(gmap, poses); gmap.vertex_gray(gverts); render_gray()
         if has_align:
             align(1); align(10); render_same()
+        if has_align_gray:
+            align_gray(1); align_gray(10)
     legs = {k: [] for k in ("fuse_tsdf", "fuse_map", "entries", "surface", "mesh", "render", "clear") + (("fuse_gray", "vertex_gray", "render_gray") if has_gray else ())
-            + (("linearize", "align", "render_same") if has_align else ())}
+            + (("linearize", "align", "render_same") if has_align else ()) + (("linearize_gray", "align_gray") if has_align_gray else ())}
     for _ in range(a.reps):   # alternating
         legs["clear"].append(clock(tsdf.clear))
         legs["fuse_tsdf"].append(clock(lambda: b.fuse_tsdf(tsdf, poses)))
@@ -167,6 +178,9 @@ def main():
             legs["linearize"].append(clock(lambda: align(1)))
             legs["align"].append(clock(lambda: align(10)))
             legs["render_same"].append(clock(render_same))
+        if has_align_gray:
+            legs["linearize_gray"].append(clock(lambda: align_gray(1)))
+            legs["align_gray"].append(clock(lambda: align_gray(10)))
     st, n_vox, n_cross = tsdf.stats(), len(tsdf.entries()), len(tsdf.surface())
     n_vert, n_tri = (len(x) for x in tsdf.mesh())
     res = {"frames": nf, "shape": [int(rows), int(cols)], "params": "voxel 0.2, T 3, min_disp16 16", "capacity_log2": log2, "reps": a.reps,
@@ -188,6 +202,15 @@ def main():
                         "ms_per_round_max_iters_1": med["linearize"] / rounds1, "ms_per_frame_and_round": med["linearize"] / rounds1 / na,
                         "ms_per_align_call": med["align"], "ms_per_round": med["align"] / rounds10,
                         "render_same_ms_per_view": med["render_same"] / na}
+    if has_align_gray:
+        g1, g10, med = align_gray(1), align_gray(10), res["ms_median"]
+        rounds1, rounds10 = int(g1["iters"].max()) + 1, int(g10["iters"].max()) + 1
+        res["align_gray"] = {"frames": na, "photo_weight": 1.0 / 32.0, "status": [int(v) for v in g10["status"]], "iters": [int(v) for v in g10["iters"]],
+                             "n_photo_used_share": float(g10["n_photo_used"].mean() / (rows * cols)), "rounds_max_iters_1": rounds1, "rounds": rounds10,
+                             "cost_geo_px": float(g10["cost_geo"].mean()), "cost_photo_gray": float(g10["cost_photo"].mean()),
+                             "ms_per_round_max_iters_1": med["linearize_gray"] / rounds1, "ms_per_frame_and_round": med["linearize_gray"] / rounds1 / na,
+                             "ms_per_align_call": med["align_gray"], "ms_per_round": med["align_gray"] / rounds10,
+                             "ratio_to_plain_per_round": (med["linearize_gray"] / rounds1) / (med["linearize"] / max(1, int(align(1)["iters"].max()) + 1))}
     if has_gray:
         res["gray"] = {"vertices": int(len(gverts)), "same_geometry": bool(gmap.entries().tobytes() == tsdf.entries().tobytes()),
                        "ratio_to_plain": {g: res["ms_median"][g] / res["ms_median"][p] for g, p in (("fuse_gray", "fuse_tsdf"), ("render_gray", "render"))}}
