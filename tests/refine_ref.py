@@ -125,14 +125,46 @@ def normal_equations(P, tr, z0, z1, param, lam):
     return 0.5 * (S + S.T), s, Hpp_d, Hcp, gp, True
 
 
+ZERO_SLACK = dict(tr_abs=0.0, tr_white=0.0, pts_rel=0.0, pts_white=0.0)
+
+
 def _empty(tr, status, n):
     return dict(tr=np.array(tr, np.float64), cov=np.zeros((6, 6)), sigma2=0.0, cost0=0.0, cost=0.0, gap=0.0, iters=0,
-                status=status, n=n, points=np.zeros((3, 0)), idx=np.zeros(0, np.int64), trace=[])
+                status=status, n=n, points=np.zeros((3, 0)), idx=np.zeros(0, np.int64), trace=[], slack=dict(ZERO_SLACK))
+
+
+def lm_step(P, tr, z0, z1, param, lam):
+    """The step (dtr (6), dX (3, n)) of the damped system at (P, tr), or None where the loop would leave with -2 or -3."""
+    S, s, Hpp_d, Hcp, gp, good = normal_equations(P, tr, z0, z1, param, lam)
+    if not good or not (np.all(np.isfinite(S)) and np.all(np.isfinite(s))) or not chol_ok(S):
+        return None
+    dtr = np.linalg.solve(S, s)
+    return dtr, np.linalg.solve(Hpp_d, (gp - np.einsum("nic,i->nc", Hcp, dtr))[:, :, None])[:, :, 0].T
+
+
+def step_sizes(step, Cinv, Hpp, pmax):
+    """A step's size per compared quantity: tr absolute (largest component) and whitened by cov = Cinv^-1, the points relative to
+    pmax (the largest |coordinate| of the final points) and whitened, each by its own undamped Hpp (n, 3, 3); the largest point."""
+    if step is None:
+        return dict(ZERO_SLACK)
+    dtr, dX = step
+    return dict(tr_abs=float(np.abs(dtr).max()), tr_white=float(np.sqrt(dtr @ Cinv @ dtr)),
+                pts_rel=float(np.abs(dX).max() / pmax),
+                pts_white=float(np.sqrt(np.einsum("an,nac,cn->n", dX, Hpp, dX).max())))
+
+
+def slack_of(last, further, Cinv, Hpp, pmax):
+    """`slack`: per quantity, the larger of the last accepted step and of one further step from the final state -- how far a run
+    whose last decisions fell the other way would end from this one."""
+    a, b = step_sizes(last, Cinv, Hpp, pmax), step_sizes(further, Cinv, Hpp, pmax)
+    return {k: max(a[k], b[k]) for k in a}
 
 
 def refine(X, obs, tr, inl, param, mode, sigma=None, ok=1):
     """The record of one frame as a dict (tr, cov, sigma2, cost0, cost, gap, iters, status, n), plus the refined points (3, n),
-    their indices idx (L'), and `trace`: the relative cost change (C_new - C) / C of every accept / reject decision taken."""
+    their indices idx (L'), `trace`: the relative cost change (C_new - C) / C of every accept / reject decision taken, and
+    `slack` (slack_of): the size of the last accepted step and of one further step at the damping the loop would use next, and
+    `Hpp` (n, 3, 3): every point's undamped block at the final state."""
     tr_in = np.array(tr, np.float64)
     Lp = used_points(X, inl)
     n = len(Lp)
@@ -148,7 +180,7 @@ def refine(X, obs, tr, inl, param, mode, sigma=None, ok=1):
         C = cost(P, cur_tr, z0, z1, param)
         cost0 = C
         lam, acc, rej = LAMBDA0, 0, 0
-        trace = []
+        trace, last = [], None
         if not np.isfinite(C):
             return _empty(tr_in, -3, n)
         while C != 0.0:
@@ -168,6 +200,7 @@ def refine(X, obs, tr, inl, param, mode, sigma=None, ok=1):
                 lam = max(lam / 10.0, LAMBDA_MIN)
                 stop = C - C_new <= REL_TOL * C or C_new == 0.0 or acc == MAX_ACCEPT
                 cur_tr, P, C = tr_new, P_new, C_new
+                last = (dtr, dX)
                 if stop:
                     break
             else:
@@ -175,7 +208,7 @@ def refine(X, obs, tr, inl, param, mode, sigma=None, ok=1):
                 rej += 1
                 if rej == MAX_REJECT:
                     break
-        S, s, _H, _c, _g, good = normal_equations(P, cur_tr, z0, z1, param, 0.0)
+        S, s, Hpp, _c, _g, good = normal_equations(P, cur_tr, z0, z1, param, 0.0)
         if good and not (np.all(np.isfinite(S)) and np.all(np.isfinite(s))):
             return _empty(tr_in, -3, n)
         if not good or not chol_ok(S):
@@ -186,8 +219,10 @@ def refine(X, obs, tr, inl, param, mode, sigma=None, ok=1):
         gap = float(s @ Si @ s) / s2 if s2 > 0 else 0.0
         if not (np.all(np.isfinite(cov)) and np.isfinite(gap) and np.all(np.isfinite(cur_tr)) and np.all(np.isfinite(P))):
             return _empty(tr_in, -3, n)
+        further = lm_step(P, cur_tr, z0, z1, param, lam) if C != 0.0 else None
+        slack = slack_of(last, further, S / max(s2, 1e-300), Hpp, float(np.abs(P).max()))
     return dict(tr=cur_tr, cov=cov, sigma2=s2, cost0=cost0, cost=C, gap=gap, iters=acc, status=1, n=n, points=P, idx=Lp,
-                trace=trace)
+                trace=trace, slack=slack, Hpp=Hpp)
 
 
 def dense_hessian(P, tr, z0, z1, param):

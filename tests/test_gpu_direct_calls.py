@@ -34,7 +34,7 @@ import sgm_ref as SR
 import speckle_ref as K
 import subpixel_ref as S
 import window_ref as WR
-from estimator_util import ambiguous
+from estimator_util import check_points
 from test_gpu_covariance import _check as check_covariance
 from test_gpu_disparity import _pair
 from test_gpu_drop_in import POSE_TOL, rel_fro
@@ -257,8 +257,8 @@ def expect_refine(i, got, oracle):
     X, obs, tr, inl, param = inputs(i)["pose"]
     want = RFR.refine(X, obs, tr, inl, param, 1, None)
     check_refine(got["rec"], want, i)
-    if want["status"] == 1 and not ambiguous(want):
-        assert np.abs(got["pts"] - want["points"]).max() <= 1e-7 * max(1.0, np.abs(want["points"]).max())
+    if want["status"] == 1:
+        check_points(got["pts"], want, i)
 
 
 def expect_window(i, got, oracle):

@@ -10,14 +10,14 @@ from libviso_amd.abi import MatchParams
 
 import covariance_ref as CR
 import refine_ref as RR
-from estimator_util import ambiguous, seq_batch
+from estimator_util import TR_WHITE, bound, check_gap, check_iters, check_points, note_gap, seq_batch, tr_abs_limits
 
 pytestmark = pytest.mark.gpu
 
 ZERO_FIELDS = ("cov", "sigma2", "cost0", "cost", "gap", "iters")
 
 
-def _check(got, want, what):
+def _check(got, want, what, far=False):
     assert int(got["status"]) == want["status"] and int(got["n"]) == want["n"], (what, int(got["status"]), want["status"])
     for k in ("tr",) + ZERO_FIELDS:
         assert np.all(np.isfinite(got[k])), (what, k)
@@ -26,30 +26,28 @@ def _check(got, want, what):
         for k in ZERO_FIELDS:
             assert not np.any(got[k]), (what, k)
         return
-    if ambiguous(want):
-        assert abs(int(got["iters"]) - want["iters"]) <= 1, (what, int(got["iters"]), want["iters"])
-    else:
-        assert int(got["iters"]) == want["iters"], (what, int(got["iters"]), want["iters"])
+    check_iters(got["iters"], want, what)
     d = np.asarray(got["tr"]) - want["tr"]
-    # in units of the estimate's own standard deviation: the stop test (C_old - C_new <= 1e-12 C_old) leaves the two summation
-    # orders free to end up to ~1e-4 apart when they took different branches, far less when they did not
+    # in units of the estimate's own standard deviation.  The stop test (C_old - C_new <= 1e-12 C_old) leaves the two summation
+    # orders free to end a rounding-level accepted step or two apart: the bound is the strict one plus 4 x the restatement's own
+    # last steps (estimator_util.bound), per case
     white = float(np.sqrt(d @ np.linalg.solve(want["cov"] / max(want["sigma2"], 1e-300), d) / max(want["sigma2"], 1e-300)))
+    white_max = bound(TR_WHITE, want["slack"]["tr_white"])
+    abs_max = bound(tr_abs_limits(want["n"]), want["slack"]["tr_abs"])
+    note_gap("refine tr whitened", white, white_max, what)
+    note_gap("refine tr absolute", float(np.abs(d).max()), abs_max, what)
     if want["n"] >= 40:
-        assert white <= (1e-4 if ambiguous(want) else 1e-5), (what, white, d)
-    if not ambiguous(want):
-        assert np.abs(d).max() <= (1e-8 if want["n"] >= 40 else 1e-7), (what, np.abs(d).max())
-    else:
-        assert np.abs(d).max() <= 1e-6, (what, np.abs(d).max())   # one rounding-size step apart, any n
+        assert white <= white_max, (what, white, want["slack"]["tr_white"], d)
+    assert np.abs(d).max() <= abs_max, (what, np.abs(d).max(), want["slack"]["tr_abs"])
     S = np.asarray(got["cov"])
     assert np.array_equal(S, S.T), what
     assert CR.whitened_error(want["cov"], S) <= 1e-7, (what, CR.whitened_error(want["cov"], S))
     for k in ("sigma2", "cost0", "cost"):
         assert abs(float(got[k]) - want[k]) <= 1e-9 * max(want[k], 1e-300), (what, k, float(got[k]), want[k])
-    assert float(got["gap"]) <= 1e-6 and want["gap"] <= 1e-6, (what, float(got["gap"]), want["gap"])
+    check_gap(float(got["gap"]), want, what, far)
 
 
 def test_direct_call_against_the_restatement(viso):
-    n_amb = 0
     for m in (6, 7, 40, 300, 1200, 3000):
         X, obs, tr_true, param = synth.make_solver_case(m, m=m, outlier_frac=0.0 if m < 40 else 0.2)
         if m >= 40:
@@ -62,13 +60,10 @@ def test_direct_call_against_the_restatement(viso):
             want = RR.refine(X, obs, tr, inl, param, mode, sigma)
             assert want["status"] == 1, m
             _check(got, want, (m, mode))
-            n_amb += ambiguous(want)
             assert pts.shape == (3, want["n"])
-            if not ambiguous(want):
-                assert np.abs(pts - want["points"]).max() <= 1e-7 * max(1.0, np.abs(want["points"]).max()), m
+            check_points(pts, want, (m, mode))
             again, pts2 = libviso_amd.pose_refine(X, obs, tr, inl, param, mode=mode, sigma=sigma)
             assert got.tobytes() == again.tobytes() and pts.tobytes() == pts2.tobytes()
-    print(f"\n{n_amb} of 12 cases had a decision at rounding level")
 
 
 def test_direct_call_degenerate_inputs(viso):
@@ -96,7 +91,7 @@ def test_direct_call_degenerate_inputs(viso):
             assert want["status"] == status, (i, want["status"])
             _check(got, want, (i, mode))
             if status == 1:
-                assert np.abs(pts - want["points"]).max() <= 1e-6 * np.abs(want["points"]).max() or ambiguous(want)
+                check_points(pts, want, (i, mode))
 
 
 def _check_batch_frames(b, param, mode, sigma=None):
@@ -116,6 +111,7 @@ def _check_batch_frames(b, param, mode, sigma=None):
             assert dpts.tobytes() == pts.tobytes(), t
         if int(recs[t]["status"]) == 1:
             assert np.array_equal(idx, want["idx"])
+            check_points(pts, want, t)
         else:
             assert len(idx) == 0 and pts.shape == (3, 0)
         n_valid += int(recs[t]["status"]) == 1

@@ -12,7 +12,7 @@ from libviso_amd.abi import Param
 
 import covariance_ref as CR
 import window_ref as WR
-from estimator_util import ambiguous
+from estimator_util import TR_WHITE, WIN_ABS, bound, check_gap, check_iters, note_gap
 
 ZERO_FIELDS = ("cov", "sigma2", "cost0", "cost", "gap", "iters")
 KEY_MAX = (1 << 20) - 1                 # the largest keypoint index the direct call takes (its largest table)
@@ -229,7 +229,7 @@ def chunk_case(length, n):
 
 
 # ---- the device record against the restatement's -------------------------------------------------------------------------------
-def check(got, want, what):
+def check(got, want, what, far=False):
     for k in ("status", "len", "n_points", "n_rows"):
         assert int(got[k]) == want[k], (what, k, int(got[k]), want[k])
     for k in ("tr", "tr_win") + ZERO_FIELDS:
@@ -240,20 +240,24 @@ def check(got, want, what):
         for k in ZERO_FIELDS:
             assert not np.any(got[k]), (what, k)
         return
-    amb = ambiguous(want)
-    assert abs(int(got["iters"]) - want["iters"]) <= (1 if amb else 0), (what, int(got["iters"]), want["iters"])
+    check_iters(got["iters"], want, what)
+    # the bounds are per case: the strict one plus 4 x the restatement's own last steps (estimator_util.bound)
     d = np.asarray(got["tr"]) - want["tr"]
     white = float(np.sqrt(d @ np.linalg.solve(want["cov"], d)))
+    white_max = bound(TR_WHITE, want["slack"]["tr_white"])
+    note_gap("window tr whitened", white, white_max, what)
     if want["n_points"] >= 40:
-        assert white <= (1e-4 if amb else 1e-5), (what, white, d)
+        assert white <= white_max, (what, white, want["slack"]["tr_white"], d)
     dw = np.abs(np.asarray(got["tr_win"]) - want["tr_win"]).max()
-    assert dw <= (1e-6 if amb else 1e-7), (what, dw)
+    dw_max = bound(WIN_ABS, want["slack"]["tr_abs"])
+    note_gap("window tr_win absolute", float(dw), dw_max, what)
+    assert dw <= dw_max, (what, dw, want["slack"]["tr_abs"])
     S = np.asarray(got["cov"])
     assert np.array_equal(S, S.T), what
     assert CR.whitened_error(want["cov"], S) <= 1e-7, (what, CR.whitened_error(want["cov"], S))
     for k in ("sigma2", "cost0", "cost"):
         assert abs(float(got[k]) - want[k]) <= 1e-9 * max(want[k], 1e-300), (what, k, float(got[k]), want[k])
-    assert float(got["gap"]) <= 1e-6 and want["gap"] <= 1e-6, (what, float(got["gap"]), want["gap"])
+    check_gap(float(got["gap"]), want, what, far)
 
 
 def check_k2_identity(w, r):

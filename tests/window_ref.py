@@ -254,7 +254,7 @@ def chol_ok(A):
 
 def _record(W, tr_t, tr_win, status, **kw):
     rec = dict(tr=np.array(tr_t, np.float64), cov=np.zeros((6, 6)), tr_win=np.zeros((4, 6)), sigma2=0.0, cost0=0.0, cost=0.0,
-               gap=0.0, iters=0, status=status, len=0, n_points=0, n_rows=0, trace=[])
+               gap=0.0, iters=0, status=status, len=0, n_points=0, n_rows=0, trace=[], slack=dict(RR.ZERO_SLACK))
     if tr_win is not None:
         rec["tr_win"][:len(tr_win)] = tr_win
     if W is not None:
@@ -263,10 +263,42 @@ def _record(W, tr_t, tr_win, status, **kw):
     return rec
 
 
+def point_steps(red, dtr):
+    """The points' steps (3, n) per group that go with the motions' step dtr."""
+    out = []
+    for lc, Wt, y in red:
+        v = y - np.einsum("nci,i->nc", Wt, dtr)
+        out.append(np.linalg.solve(np.transpose(lc, (0, 2, 1)), v[:, :, None])[:, :, 0].T)
+    return out
+
+
+def lm_step(W, trs, Ps, lam):
+    """The step (dtr (nc), dX (3, n) per group) of the damped system at (trs, Ps), or None where the loop would leave with -2
+    or -3."""
+    S, s, red, good = normal_equations(W, trs, Ps, lam)
+    if not good or not (np.all(np.isfinite(S)) and np.all(np.isfinite(s))) or not chol_ok(S):
+        return None
+    dtr = np.linalg.solve(S, s)
+    return dtr, point_steps(red, dtr)
+
+
+def step_sizes(step, Cinv, red0, pmax):
+    """A step's size per compared quantity, as RR.step_sizes: tr_abs over every motion of the window (tr_win), tr_white frame t's
+    motion whitened by its cov = Cinv^-1, the points relative to pmax and whitened by their undamped Hpp = l l' (red0: the
+    undamped system's per-group terms)."""
+    if step is None:
+        return dict(RR.ZERO_SLACK)
+    dtr, dXs = step
+    white = [np.sqrt((np.einsum("nca,cn->na", lc, dX) ** 2).sum(1).max()) for (lc, _w, _y), dX in zip(red0, dXs)]
+    return dict(tr_abs=float(np.abs(dtr).max()), tr_white=float(np.sqrt(dtr[-6:] @ Cinv @ dtr[-6:])),
+                pts_rel=float(max(np.abs(dX).max() for dX in dXs) / pmax), pts_white=float(max(white)))
+
+
 def window(frames, t, K, param, mode, sigma=None):
     """The record of frame t (a dict with the fields of viso_window_record, plus `trace`: the relative cost change (C_new - C) / C
-    of every accept / reject decision, and `points`: the final points per group).  frames[j] is a Frame for j >= 1; frames[0] is
-    not read."""
+    of every accept / reject decision, `points`: the final points per group, and `slack`: per quantity of step_sizes, the larger
+    of the last accepted step and of one further step at the damping the loop would use next).  frames[j] is a Frame for j >= 1;
+    frames[0] is not read."""
     if t == 0:
         return _record(None, np.zeros(6), None, 0)
     fr = frames[t]
@@ -286,7 +318,7 @@ def window(frames, t, K, param, mode, sigma=None):
         C = total_cost(W, trs, Ps)
         C0 = C
         lam, acc, rej = LAMBDA0, 0, 0
-        trace = []
+        trace, last = [], None
         if not np.isfinite(C):
             return _record(W, fr.tr, tr_in, -3)
         while C != 0.0:
@@ -296,11 +328,8 @@ def window(frames, t, K, param, mode, sigma=None):
             if not good or not chol_ok(S):
                 return _record(W, fr.tr, tr_in, -2)
             dtr = np.linalg.solve(S, s)
-            Pn = []
-            for (lc, Wt, y), P in zip(red, Ps):
-                v = y - np.einsum("nci,i->nc", Wt, dtr)
-                dX = np.linalg.solve(np.transpose(lc, (0, 2, 1)), v[:, :, None])[:, :, 0]
-                Pn.append(P + dX.T)
+            dXs = point_steps(red, dtr)
+            Pn = [P + dX for P, dX in zip(Ps, dXs)]
             trn = trs + dtr.reshape(-1, 6)
             Cn = total_cost(W, trn, Pn)
             trace.append((Cn - C) / C)
@@ -310,6 +339,7 @@ def window(frames, t, K, param, mode, sigma=None):
                 lam = max(lam / 10.0, LAMBDA_MIN)
                 stop = C - Cn <= REL_TOL * C or Cn == 0.0 or acc == MAX_ACCEPT
                 trs, Ps, C = trn, Pn, Cn
+                last = (dtr, dXs)
                 if stop:
                     break
             else:
@@ -317,7 +347,7 @@ def window(frames, t, K, param, mode, sigma=None):
                 rej += 1
                 if rej == MAX_REJECT:
                     break
-        S, s, _red, good = normal_equations(W, trs, Ps, 0.0)
+        S, s, red0, good = normal_equations(W, trs, Ps, 0.0)
         if good and not (np.all(np.isfinite(S)) and np.all(np.isfinite(s))):
             return _record(W, fr.tr, tr_in, -3)
         if not good or not chol_ok(S):
@@ -329,8 +359,13 @@ def window(frames, t, K, param, mode, sigma=None):
         gap = float(s @ Si @ s) / s2 if s2 > 0 else 0.0
         if not (np.all(np.isfinite(cov)) and np.isfinite(gap) and np.all(np.isfinite(trs))):
             return _record(W, fr.tr, tr_in, -3)
+        further = lm_step(W, trs, Ps, lam) if C != 0.0 else None
+        Cinv = np.linalg.inv(0.5 * (Stt + Stt.T)) / max(s2, 1e-300)
+        pmax = float(max(np.abs(P).max() for P in Ps))
+        a, b = step_sizes(last, Cinv, red0, pmax), step_sizes(further, Cinv, red0, pmax)
+        slack = {k: max(a[k], b[k]) for k in a}
     return _record(W, trs[-1], trs, 1, cov=cov, sigma2=s2, cost0=C0, cost=C, gap=gap, iters=acc, trace=trace, points=Ps,
-                   window=W)
+                   window=W, slack=slack)
 
 
 def records(frames, K, param, mode, sigma=None):
