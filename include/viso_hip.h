@@ -882,7 +882,8 @@ int viso_batch_get_disparity_points(viso_batch* b, int t, const double* pose_or_
  * TSDF map below).
  * HIP kernels (voxelmap.hip): map_fuse_kernel (one thread per pixel of a group of frames; lanes that continue the key of the lane
  * to their left form a run, the run heads come from one ballot, the runs' sums from a wave scan, and only a run's head probes the
- * table and issues the four integer atomic adds), map_add_entries_kernel, map_compact_kernel, map_clear_kernel.  Memory: 36 bytes a
+ * table and issues the four integer atomic adds); adding entries, listing and clearing are the kernels every table of voxels shares
+ * (voxel_hash.h: voxel_add_entries_kernel, voxel_compact_kernel, voxel_clear_kernel, over the map's payload).  Memory: 36 bytes a
  * slot (604 MB at the default capacity). */
 typedef struct viso_map_params {
     double voxel;            /* edge of a voxel, metres */
@@ -973,7 +974,8 @@ int viso_map_entry_centroid(const viso_map_entry* entry, double voxel, float out
  * KITTI runners, the sort on the device.
  * HIP kernels (tsdf.hip): tsdf_fuse_kernel (one thread per pixel of a group of frames; the loop over j is uniform across the wave,
  * and per j the lanes that continue the voxel of the lane to their left form a run whose head lane alone probes the table and
- * issues the two integer atomic adds), tsdf_add_entries_kernel, tsdf_compact_kernel, tsdf_crossings_kernel, tsdf_clear_kernel.
+ * issues the two integer atomic adds), tsdf_crossings_kernel; adding entries, listing and clearing are the kernels every table of
+ * voxels shares (voxel_hash.h: voxel_add_entries_kernel, voxel_compact_kernel, voxel_clear_kernel, over the TSDF map's payload).
  * Memory: 20 bytes a slot (1.34 GB at the default capacity). */
 typedef struct viso_tsdf_params {
     double voxel;            /* edge of a voxel, metres */
@@ -1174,9 +1176,10 @@ int viso_tsdf_render(viso_tsdf* t, uint32_t min_weight, const viso_param* param,
  * KITTI runners.
  * HIP kernels (tsdf.hip): tsdf_gray_fuse_kernel (the fuse kernel's march with the pixel's intensity carried: one byte a pixel read
  * along the row, the run's sum of intensities from a second wave scan, three integer atomic adds from the run's head lane),
- * tsdf_gray_add_entries_kernel, tsdf_gray_compact_kernel, tsdf_gray_sample_kernel (one thread per vertex, two read-only probes,
- * n_missing with one atomic per wave), tsdf_gray_render_kernel (the render march, the head lane also loads gray and hands it to its
- * run), tsdf_gray_clear_kernel.  No LDS, no scratch; every probe loop is bounded by the capacity. */
+ * tsdf_gray_sample_kernel (one thread per vertex, two read-only probes, n_missing with one atomic per wave),
+ * tsdf_gray_render_kernel (the render march, the head lane also loads gray and hands it to its run); adding entries, listing and
+ * clearing are the shared kernels of voxel_hash.h over the gray map's payload, which carries the third array.  No LDS, no scratch;
+ * every probe loop is bounded by the capacity. */
 typedef struct viso_tsdf_gray_entry {   /* 32 bytes */
     int32_t k[3];
     uint32_t weight;

@@ -13,10 +13,9 @@
 //                            run's sum of q (biased by T 1024, so unsigned: 64 x 2 x 8 x 1024 < 2^21) from one wave scan (DPP) and
 //                            one exchange with the run's last lane.  Only the head lane probes the table and issues the two atomic
 //                            adds (weight, sum).  Lanes that skip a sample take part as runs of the empty key.
-//   tsdf_add_entries_kernel  one thread per entry through the same probe.
-//   tsdf_compact_kernel      one thread per slot: the slots with weight >= min_weight to a dense list, one atomic per wave for the
-//                            list positions (out == null: only their number).
-//   tsdf_crossings_kernel    one thread per slot, three read-only probes for the neighbours at +1 on every axis; the same two passes.
+//   tsdf_crossings_kernel    one thread per slot, three read-only probes for the neighbours at +1 on every axis: the sign changes
+//                            between voxels of weight >= min_weight to a dense list, one atomic per wave for the list positions
+//                            (out == null: only their number), in the getters' two passes.
 //   tsdf_mesh_kernel         one thread per slot, seven read-only probes for the other corners of the voxel's cell: the sign-changing
 //                            edges the voxel owns as vertices, and the triangles of the cell's six tetrahedra as references to
 //                            them; two lists, one atomic per wave and list; the same two passes.
@@ -24,27 +23,28 @@
 //                            The march over the samples of a pixel's ray is uniform across the wave, with the runs of the fuse
 //                            kernel: only a run's head lane probes the table (voxel_find) and loads weight and sum, the other
 //                            lanes of the run take them from it (three ds_bpermute).  Ends when no lane of the wave marches.
-//   tsdf_clear_kernel        one thread per slot.
 // A gray map (include/viso_hip.h, "TSDF intensity") carries a third payload array, gray [slots] u64, the sum of the
 // 8-bit intensities of the pixels that updated a voxel.  Its kernels are their plain counterparts with that array carried: the
 // fuse and the render share their bodies with them (template <bool GRAY>, the plain instance reads none of the three extra
-// arguments), the others are restated for the 32-byte entry.
+// arguments).
 //   tsdf_gray_fuse_kernel         the fuse kernel's march with the pixel's intensity (one byte a pixel, along the row); the run's
 //                                 sum of intensities from a second wave scan (64 x 255 < 2^14), a third atomic add from its head lane.
-//   tsdf_gray_add_entries_kernel, tsdf_gray_compact_kernel, tsdf_gray_clear_kernel   as the plain ones.
 //   tsdf_gray_sample_kernel       one thread per vertex (k, dir): two read-only probes for the ends of its edge, the intensity
 //                                 interpolated with the mesh's t; the vertices without a value counted with one atomic per wave.
 //   tsdf_gray_render_kernel       the render march; a run's head lane also loads gray and hands it to its run (two more
 //                                 ds_bpermute for the 64-bit value).
 // The frame-to-model alignment that reads this table is in tsdf_align.hip (the table's layout: tsdf_table.h).
 // What every table of voxels shares is not here (voxelmap.hip says what): the device side is voxel_hash.h, the host side
-// voxel_host.h.  This file keeps the table's payload and insert, the kernels' own bodies, the parameter and entry checks, the
-// orders of the items and the whole mesh extraction, whose two lists do not fit the shared two passes.
+// voxel_host.h.  The kernels that list, clear, add entries to and evict slots are voxel_hash.h's templates, instantiated here over
+// TsdfPayload<false> (a plain map) and TsdfPayload<true> (a gray map).  This file keeps the table's payload, the other kernels and
+// the fuse's insert, the parameter and entry checks, the orders of the items and the whole mesh extraction, whose two lists do not
+// fit the shared two passes.
 #include "common.h"
 #include "wave.h"
 #include "tsdf_table.h"
 
 #include <cmath>
+#include <type_traits>
 #include <vector>
 
 // a gray map's table (include/viso_hip.h, "TSDF intensity"): the same with the sums of the updates' 8-bit intensities
@@ -162,64 +162,6 @@ __device__ __forceinline__ void tsdf_fuse_body(const TsdfFuseArgs& a, const uint
 
 __global__ __launch_bounds__(256) void tsdf_fuse_kernel(TsdfFuseArgs a) { tsdf_fuse_body<false>(a, nullptr, 0, nullptr); }
 __global__ __launch_bounds__(256) void tsdf_gray_fuse_kernel(TsdfGrayFuseArgs g) { tsdf_fuse_body<true>(g.a, g.image, g.ifs, g.gray); }
-
-__global__ __launch_bounds__(256) void tsdf_add_entries_kernel(TsdfTable t, const viso_tsdf_entry* e, unsigned long long n) {
-    const unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
-    bool claimed = false;
-    unsigned long long w = 0;
-    if (i < n) {
-        const viso_tsdf_entry v = e[i];
-        w = v.weight;
-        tsdf_insert(t, voxel_key(v.k[0], v.k[1], v.k[2]), v.weight, v.sum, &claimed);
-        atomicAdd(voxel_stat(t.head, blockIdx.x, VOXEL_ST_UPDATES), w);
-    }
-    voxel_count_wave(t.head, blockIdx.x, threadIdx.x & 63, 0, 0, 0, __popcll(__ballot(claimed)));
-}
-
-__global__ __launch_bounds__(256) void tsdf_compact_kernel(TsdfTable t, uint32_t min_weight, viso_tsdf_entry* out, unsigned long long out_cap) {
-    const uint32_t slot = blockIdx.x * 256 + threadIdx.x;   // the grid covers the slots exactly (at least 1024 of them)
-    const unsigned long long key = t.head.keys[slot];
-    const uint32_t w = t.weight[slot];
-    const bool take = key != MAP_EMPTY && w >= min_weight;
-    unsigned long long at;
-    if (!voxel_list_position(t.head, take, threadIdx.x & 63, &at)) return;   // the whole wave
-    if (take && out && at < out_cap) {
-        viso_tsdf_entry v;
-        voxel_unkey(key, v.k);
-        v.weight = w;
-        v.sum = (long long)t.sum[slot];
-        out[at] = v;
-    }
-}
-
-// the same two for a gray map and its 32-byte entries
-__global__ __launch_bounds__(256) void tsdf_gray_add_entries_kernel(TsdfGrayTable g, const viso_tsdf_gray_entry* e, unsigned long long n) {
-    const unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
-    bool claimed = false;
-    if (i < n) {
-        const viso_tsdf_gray_entry v = e[i];
-        tsdf_insert(g.t, voxel_key(v.k[0], v.k[1], v.k[2]), v.weight, v.sum, &claimed, g.gray, v.gray);
-        atomicAdd(voxel_stat(g.t.head, blockIdx.x, VOXEL_ST_UPDATES), (unsigned long long)v.weight);
-    }
-    voxel_count_wave(g.t.head, blockIdx.x, threadIdx.x & 63, 0, 0, 0, __popcll(__ballot(claimed)));
-}
-
-__global__ __launch_bounds__(256) void tsdf_gray_compact_kernel(TsdfGrayTable g, uint32_t min_weight, viso_tsdf_gray_entry* out, unsigned long long out_cap) {
-    const uint32_t slot = blockIdx.x * 256 + threadIdx.x;   // the grid covers the slots exactly
-    const unsigned long long key = g.t.head.keys[slot];
-    const uint32_t w = g.t.weight[slot];
-    const bool take = key != MAP_EMPTY && w >= min_weight;
-    unsigned long long at;
-    if (!voxel_list_position(g.t.head, take, threadIdx.x & 63, &at)) return;   // the whole wave
-    if (take && out && at < out_cap) {
-        viso_tsdf_gray_entry v;
-        voxel_unkey(key, v.k);
-        v.weight = w;
-        v.sum = (long long)g.t.sum[slot];
-        v.gray = g.gray[slot];
-        out[at] = v;
-    }
-}
 
 // The intensity of the point on the edge between the voxels a and b (include/viso_hip.h, "TSDF intensity"): t is the mesh's and the
 // render's, the means of the intensities are interpolated with it.  wa, wb >= 1 and the sums differ in sign.
@@ -546,49 +488,37 @@ struct TsdfGrayRenderArgs {
 __global__ __launch_bounds__(256) void tsdf_render_kernel(TsdfRenderArgs a) { tsdf_render_body<false>(a, nullptr, nullptr); }
 __global__ __launch_bounds__(256) void tsdf_gray_render_kernel(TsdfGrayRenderArgs g) { tsdf_render_body<true>(g.a, g.gray, g.out); }
 
-__global__ __launch_bounds__(256) void tsdf_clear_kernel(TsdfTable t) {
-    const uint32_t slot = blockIdx.x * 256 + threadIdx.x;
-    voxel_clear_head(t.head, slot);
-    t.weight[slot] = 0u;
-    t.sum[slot] = 0ull;
-}
-
-__global__ __launch_bounds__(256) void tsdf_gray_clear_kernel(TsdfGrayTable g) {
-    const uint32_t slot = blockIdx.x * 256 + threadIdx.x;
-    voxel_clear_head(g.t.head, slot);
-    g.t.weight[slot] = 0u;
-    g.t.sum[slot] = 0ull;
-    g.gray[slot] = 0ull;
-}
-
-// the payloads of a slot for the eviction's kernels (voxel_hash.h): a plain map's and a gray map's
+// what is in a slot, for the shared kernels that list, zero, add to and evict slots (voxel_hash.h, "a kind's payload"): a plain
+// map's, and with GRAY a gray map's, whose table and entries carry the sums of intensities
+template <bool GRAY>
 struct TsdfPayload {
-    TsdfTable t;
-    using Entry = viso_tsdf_entry;
-    __device__ __forceinline__ void pack(uint32_t slot, unsigned long long key, Entry* v) const {
+    std::conditional_t<GRAY, TsdfGrayTable, TsdfTable> tab;
+    using Entry = std::conditional_t<GRAY, viso_tsdf_gray_entry, viso_tsdf_entry>;
+    static constexpr int UNITS_STAT = VOXEL_ST_UPDATES;   // add_entries: an entry's weight to n_updates,
+    static constexpr bool ENTRY_STAT = false;             // and nothing more an entry
+    __host__ __device__ __forceinline__ const TsdfTable& t() const { if constexpr (GRAY) return tab.t; else return tab; }
+    __host__ __device__ __forceinline__ const VoxelTable& head() const { return t().head; }
+    __device__ __forceinline__ uint32_t threshold(uint32_t slot) const { return t().weight[slot]; }
+    __device__ __forceinline__ static unsigned long long key(const Entry& v) { return voxel_key(v.k[0], v.k[1], v.k[2]); }
+    __device__ __forceinline__ static unsigned long long units(const Entry& v) { return v.weight; }
+    __device__ __forceinline__ void add(uint32_t slot, const Entry& v) const {
+        atomicAdd(t().weight + slot, v.weight);
+        atomicAdd(t().sum + slot, (unsigned long long)v.sum);
+        if constexpr (GRAY) atomicAdd(tab.gray + slot, v.gray);
+    }
+    __device__ __forceinline__ void pack(uint32_t slot, unsigned long long key, uint32_t weight, Entry* v) const {
         voxel_unkey(key, v->k);
-        v->weight = t.weight[slot];
-        v->sum = (long long)t.sum[slot];
+        v->weight = weight;
+        v->sum = (long long)t().sum[slot];
+        if constexpr (GRAY) v->gray = tab.gray[slot];
     }
-    __device__ __forceinline__ void zero(uint32_t a) const { t.weight[a] = 0u; t.sum[a] = 0ull; }
+    __device__ __forceinline__ void zero(uint32_t a) const {
+        t().weight[a] = 0u; t().sum[a] = 0ull;
+        if constexpr (GRAY) tab.gray[a] = 0ull;
+    }
     __device__ __forceinline__ void move(uint32_t a, uint32_t b) const {
-        t.weight[b] = t.weight[a]; t.sum[b] = t.sum[a];
-        zero(a);
-    }
-};
-
-struct TsdfGrayPayload {
-    TsdfGrayTable g;
-    using Entry = viso_tsdf_gray_entry;
-    __device__ __forceinline__ void pack(uint32_t slot, unsigned long long key, Entry* v) const {
-        voxel_unkey(key, v->k);
-        v->weight = g.t.weight[slot];
-        v->sum = (long long)g.t.sum[slot];
-        v->gray = g.gray[slot];
-    }
-    __device__ __forceinline__ void zero(uint32_t a) const { g.t.weight[a] = 0u; g.t.sum[a] = 0ull; g.gray[a] = 0ull; }
-    __device__ __forceinline__ void move(uint32_t a, uint32_t b) const {
-        g.t.weight[b] = g.t.weight[a]; g.t.sum[b] = g.t.sum[a]; g.gray[b] = g.gray[a];
+        t().weight[b] = t().weight[a]; t().sum[b] = t().sum[a];
+        if constexpr (GRAY) tab.gray[b] = tab.gray[a];
         zero(a);
     }
 };
@@ -601,6 +531,12 @@ struct viso_tsdf {
     unsigned long long* gray;                // null: a plain map
     TsdfGrayTable g() const { return TsdfGrayTable{t, gray}; }
 };
+
+// t's payload for the shared kernels; t is live and, with GRAY, a gray map
+template <bool GRAY>
+static TsdfPayload<GRAY> tsdf_payload(const viso_tsdf* t) {
+    if constexpr (GRAY) return {t->g()}; else return {t->t};
+}
 
 static VoxelRegistry g_tsdfs = {{"TSDF", "TSDF map", "updates", "min_weight", "viso_tsdf_clear"}};
 
@@ -623,8 +559,8 @@ extern "C" void viso_tsdf_params_default(viso_tsdf_params* p) {
 static dim3 tsdf_slot_grid(const viso_tsdf* t) { return dim3((t->t.head.mask + 1u) / 256u); }
 static VoxelLaunch tsdf_clear_launch(viso_tsdf* t) {
     return [t](hipStream_t s) {
-        if (t->gray) hipLaunchKernelGGL(tsdf_gray_clear_kernel, tsdf_slot_grid(t), dim3(256), 0, s, t->g());
-        else hipLaunchKernelGGL(tsdf_clear_kernel, tsdf_slot_grid(t), dim3(256), 0, s, t->t);
+        if (t->gray) voxel_start_clear(tsdf_payload<true>(t), s);
+        else voxel_start_clear(tsdf_payload<false>(t), s);
     };
 }
 // ifs: the distance of two frames' images, for a gray map's fuse (whose calls all come with an image); 0: a plain map's
@@ -730,35 +666,29 @@ static bool tsdf_entry_ok(const int32_t* k, uint32_t weight, long long sum, long
     return ok;
 }
 
-extern "C" int viso_tsdf_add_entries(viso_tsdf* t, const viso_tsdf_entry* entries, size_t n) {
-    const char* where = "viso_tsdf_add_entries";
-    if (!tsdf_kind_ok(where, t, false)) return VISO_ERR_ARG;
+// viso_tsdf_add_entries and, with GRAY, viso_tsdf_add_gray_entries
+template <bool GRAY>
+static int tsdf_add_entries(const char* where, viso_tsdf* t, const typename TsdfPayload<GRAY>::Entry* entries, size_t n) {
+    if (!tsdf_kind_ok(where, t, GRAY)) return VISO_ERR_ARG;
     if (n && !entries) { viso_set_error("%s: bad argument (null entries)", where); return VISO_ERR_ARG; }
     const long long lim = (long long)t->p.trunc_voxels * 1024;
     for (size_t i = 0; i < n; ++i) {
-        const viso_tsdf_entry& e = entries[i];
-        if (!tsdf_entry_ok(e.k, e.weight, e.sum, lim)) { viso_set_error("%s: entry %zu is not a voxel of this map (k in -2^20 .. 2^20 - 1, weight >= 1, |sum| <= %lld weight)", where, i, lim); return VISO_ERR_ARG; }
-    }
-    return voxel_add_entries(where, g_tsdfs, t, entries, n, sizeof(viso_tsdf_entry), [t, n](const void* d, dim3 grid, hipStream_t s) {
-        hipLaunchKernelGGL(tsdf_add_entries_kernel, grid, dim3(256), 0, s, t->t, static_cast<const viso_tsdf_entry*>(d), (unsigned long long)n);
-    });
-}
-
-extern "C" int viso_tsdf_add_gray_entries(viso_tsdf* t, const viso_tsdf_gray_entry* entries, size_t n) {
-    const char* where = "viso_tsdf_add_gray_entries";
-    if (!tsdf_kind_ok(where, t, true)) return VISO_ERR_ARG;
-    if (n && !entries) { viso_set_error("%s: bad argument (null entries)", where); return VISO_ERR_ARG; }
-    const long long lim = (long long)t->p.trunc_voxels * 1024;
-    for (size_t i = 0; i < n; ++i) {
-        const viso_tsdf_gray_entry& e = entries[i];
-        if (!tsdf_entry_ok(e.k, e.weight, e.sum, lim) || e.gray > 255ull * e.weight) {
-            viso_set_error("%s: entry %zu is not a voxel of this map (k in -2^20 .. 2^20 - 1, weight >= 1, |sum| <= %lld weight, gray <= 255 weight)", where, i, lim);
+        const auto& e = entries[i];
+        bool ok = tsdf_entry_ok(e.k, e.weight, e.sum, lim);
+        if constexpr (GRAY) ok = ok && e.gray <= 255ull * e.weight;
+        if (!ok) {
+            viso_set_error("%s: entry %zu is not a voxel of this map (k in -2^20 .. 2^20 - 1, weight >= 1, |sum| <= %lld weight%s)", where, i, lim,
+                           GRAY ? ", gray <= 255 weight" : "");
             return VISO_ERR_ARG;
         }
     }
-    return voxel_add_entries(where, g_tsdfs, t, entries, n, sizeof(viso_tsdf_gray_entry), [t, n](const void* d, dim3 grid, hipStream_t s) {
-        hipLaunchKernelGGL(tsdf_gray_add_entries_kernel, grid, dim3(256), 0, s, t->g(), static_cast<const viso_tsdf_gray_entry*>(d), (unsigned long long)n);
-    });
+    return voxel_add_entries(where, g_tsdfs, t, entries, n, tsdf_payload<GRAY>(t));
+}
+extern "C" int viso_tsdf_add_entries(viso_tsdf* t, const viso_tsdf_entry* entries, size_t n) {
+    return tsdf_add_entries<false>("viso_tsdf_add_entries", t, entries, n);
+}
+extern "C" int viso_tsdf_add_gray_entries(viso_tsdf* t, const viso_tsdf_gray_entry* entries, size_t n) {
+    return tsdf_add_entries<true>("viso_tsdf_add_gray_entries", t, entries, n);
 }
 
 static inline unsigned long long key_of(const int32_t* k) { return voxel_key(k[0], k[1], k[2]); }
@@ -769,65 +699,58 @@ static inline bool voxel_item_less(const viso_tsdf_crossing& x, const viso_tsdf_
     return a != b ? a < b : x.axis < y.axis;
 }
 
-// the count or the sorted list of what `kernel` lists: the voxels / the crossings of at least min_weight updates
-template <class Item>
-static int tsdf_extract(const char* where, viso_tsdf* t, uint32_t min_weight, bool count_only, Item* items_out, size_t n_cap, size_t* n,
-                        void (*kernel)(TsdfTable, uint32_t, Item*, unsigned long long)) {
-    return voxel_extract<Item>(where, g_tsdfs, t, min_weight, count_only, items_out, n_cap, n,
-                               [=](Item* out, unsigned long long out_cap, hipStream_t s) {
-        hipLaunchKernelGGL(kernel, tsdf_slot_grid(t), dim3(256), 0, s, t->t, min_weight, out, out_cap);
-    });
+// the count or the sorted list of the voxels of at least min_weight updates, as plain entries or, with GRAY, as a gray map's
+template <bool GRAY>
+static int tsdf_entries(const char* where, viso_tsdf* t, uint32_t min_weight, bool count_only, typename TsdfPayload<GRAY>::Entry* entries_out,
+                        size_t n_cap, size_t* n) {
+    if (GRAY ? !tsdf_kind_ok(where, t, true) : !voxel_known(g_tsdfs, t)) {
+        if (!GRAY) viso_set_error("%s: not a live TSDF handle", where);
+        return VISO_ERR_ARG;
+    }
+    return voxel_entries(where, g_tsdfs, t, min_weight, count_only, entries_out, n_cap, n, tsdf_payload<GRAY>(t));
 }
-
-extern "C" int viso_tsdf_count(viso_tsdf* t, uint32_t min_weight, size_t* n) {
-    return tsdf_extract<viso_tsdf_entry>("viso_tsdf_count", t, min_weight, true, nullptr, 0, n, tsdf_compact_kernel);
+extern "C" int viso_tsdf_count(viso_tsdf* t, uint32_t min_weight, size_t* n) {   // either kind
+    return tsdf_entries<false>("viso_tsdf_count", t, min_weight, true, nullptr, 0, n);
 }
 extern "C" int viso_tsdf_get(viso_tsdf* t, uint32_t min_weight, viso_tsdf_entry* entries_out, size_t n_cap, size_t* n) {
-    return tsdf_extract<viso_tsdf_entry>("viso_tsdf_get", t, min_weight, false, entries_out, n_cap, n, tsdf_compact_kernel);
+    return tsdf_entries<false>("viso_tsdf_get", t, min_weight, false, entries_out, n_cap, n);
 }
 extern "C" int viso_tsdf_get_gray(viso_tsdf* t, uint32_t min_weight, viso_tsdf_gray_entry* entries_out, size_t n_cap, size_t* n) {
-    const char* where = "viso_tsdf_get_gray";
-    if (!tsdf_kind_ok(where, t, true)) return VISO_ERR_ARG;
-    return voxel_extract<viso_tsdf_gray_entry>(where, g_tsdfs, t, min_weight, false, entries_out, n_cap, n,
-                                               [=](viso_tsdf_gray_entry* out, unsigned long long out_cap, hipStream_t s) {
-        hipLaunchKernelGGL(tsdf_gray_compact_kernel, tsdf_slot_grid(t), dim3(256), 0, s, t->g(), min_weight, out, out_cap);
-    });
+    return tsdf_entries<true>("viso_tsdf_get_gray", t, min_weight, false, entries_out, n_cap, n);
 }
 
 // viso_tsdf_evict*: t is live and of the payload's kind
-static int tsdf_evict_plain(const char* where, viso_tsdf* t, const viso_voxel_box* keep, bool count_only, viso_tsdf_entry* evicted_out, size_t n_cap, size_t* n) {
-    const VoxelEvictKind<TsdfPayload> kind = {TsdfPayload{t->t}, tsdf_clear_launch(t),
-        [t](const viso_tsdf_entry* d, unsigned long long k, dim3 grid, hipStream_t s) {
-            hipLaunchKernelGGL(tsdf_add_entries_kernel, grid, dim3(256), 0, s, t->t, d, k);
-        }};
-    return voxel_evict<TsdfPayload>(where, g_tsdfs, t, keep, count_only, evicted_out, n_cap, n, kind);
-}
-static int tsdf_evict_gray(const char* where, viso_tsdf* t, const viso_voxel_box* keep, bool count_only, viso_tsdf_gray_entry* evicted_out, size_t n_cap, size_t* n) {
-    const VoxelEvictKind<TsdfGrayPayload> kind = {TsdfGrayPayload{t->g()}, tsdf_clear_launch(t),
-        [t](const viso_tsdf_gray_entry* d, unsigned long long k, dim3 grid, hipStream_t s) {
-            hipLaunchKernelGGL(tsdf_gray_add_entries_kernel, grid, dim3(256), 0, s, t->g(), d, k);
-        }};
-    return voxel_evict<TsdfGrayPayload>(where, g_tsdfs, t, keep, count_only, evicted_out, n_cap, n, kind);
+template <bool GRAY>
+static int tsdf_evict(const char* where, viso_tsdf* t, const viso_voxel_box* keep, bool count_only, typename TsdfPayload<GRAY>::Entry* evicted_out,
+                      size_t n_cap, size_t* n) {
+    return voxel_evict(where, g_tsdfs, t, keep, count_only, evicted_out, n_cap, n, tsdf_payload<GRAY>(t));
 }
 extern "C" int viso_tsdf_evict_count(viso_tsdf* t, const viso_voxel_box* keep, size_t* n) {   // either kind
     const char* where = "viso_tsdf_evict_count";
     if (!voxel_known(g_tsdfs, t)) { viso_set_error("%s: not a live TSDF handle", where); return VISO_ERR_ARG; }
-    return t->gray ? tsdf_evict_gray(where, t, keep, true, nullptr, 0, n) : tsdf_evict_plain(where, t, keep, true, nullptr, 0, n);
+    return t->gray ? tsdf_evict<true>(where, t, keep, true, nullptr, 0, n) : tsdf_evict<false>(where, t, keep, true, nullptr, 0, n);
 }
 extern "C" int viso_tsdf_evict(viso_tsdf* t, const viso_voxel_box* keep, viso_tsdf_entry* evicted_out, size_t n_cap, size_t* n) {
     if (!tsdf_kind_ok("viso_tsdf_evict", t, false)) return VISO_ERR_ARG;
-    return tsdf_evict_plain("viso_tsdf_evict", t, keep, false, evicted_out, n_cap, n);
+    return tsdf_evict<false>("viso_tsdf_evict", t, keep, false, evicted_out, n_cap, n);
 }
 extern "C" int viso_tsdf_evict_gray(viso_tsdf* t, const viso_voxel_box* keep, viso_tsdf_gray_entry* evicted_out, size_t n_cap, size_t* n) {
     if (!tsdf_kind_ok("viso_tsdf_evict_gray", t, true)) return VISO_ERR_ARG;
-    return tsdf_evict_gray("viso_tsdf_evict_gray", t, keep, false, evicted_out, n_cap, n);
+    return tsdf_evict<true>("viso_tsdf_evict_gray", t, keep, false, evicted_out, n_cap, n);
 }
 
+// the count or the sorted list of the crossings between voxels of at least min_weight updates
+static int tsdf_crossings(const char* where, viso_tsdf* t, uint32_t min_weight, bool count_only, viso_tsdf_crossing* out, size_t n_cap, size_t* n) {
+    return voxel_extract<viso_tsdf_crossing>(where, g_tsdfs, t, min_weight, count_only, out, n_cap, n,
+                                             [=](viso_tsdf_crossing* d_out, unsigned long long out_cap, hipStream_t s) {
+        hipLaunchKernelGGL(tsdf_crossings_kernel, tsdf_slot_grid(t), dim3(256), 0, s, t->t, min_weight, d_out, out_cap);
+    });
+}
 extern "C" int viso_tsdf_surface_count(viso_tsdf* t, uint32_t min_weight, size_t* n) {
-    return tsdf_extract<viso_tsdf_crossing>("viso_tsdf_surface_count", t, min_weight, true, nullptr, 0, n, tsdf_crossings_kernel);
+    return tsdf_crossings("viso_tsdf_surface_count", t, min_weight, true, nullptr, 0, n);
 }
 extern "C" int viso_tsdf_surface(viso_tsdf* t, uint32_t min_weight, viso_tsdf_crossing* crossings_out, size_t n_cap, size_t* n) {
-    return tsdf_extract<viso_tsdf_crossing>("viso_tsdf_surface", t, min_weight, false, crossings_out, n_cap, n, tsdf_crossings_kernel);
+    return tsdf_crossings("viso_tsdf_surface", t, min_weight, false, crossings_out, n_cap, n);
 }
 
 // One pass of the mesh extraction: the numbers of vertex records and of triangles, both lists written when `verts` is set

@@ -3,8 +3,9 @@
 // ones = empty; a key is claimed with one 64-bit compare-and-swap.  Every probe loop visits each slot at most once and advances
 // strictly: a full table is a wrong count, never a hang.  Beside the keys every table has 256 sets of counters on cache lines of
 // their own (a workgroup adds to set blockIdx & 255, one atomic per wave and counter; summed on the host) and a few single words.
-// Eviction (include/viso_hip.h, "Map eviction") is here too, once for every kind: three kernels over the slots,
-// templates over the kind's payload.  Only they ever write a tombstone, and none is left when they are done.
+// What is in a slot is the kind's payload P (below); the kernels that only list, zero or add to slots are here once for every kind,
+// templates over P: voxel_compact_kernel, voxel_clear_kernel, voxel_add_entries_kernel and the three of an eviction
+// (include/viso_hip.h, "Map eviction").  Only those three ever write a tombstone, and none is left when they are done.
 #ifndef VISO_VOXEL_HASH_H_
 #define VISO_VOXEL_HASH_H_
 #include "common.h"
@@ -23,6 +24,7 @@
 #define VOXEL_W_OUT 0                   // words: an extraction's list length
 #define VOXEL_W_DROPPED 1               //        points / updates that found no slot
 #define VOXEL_W_TRIS 2                  //        the mesh's triangle list length (VOXEL_W_OUT: its vertex list's)
+#define VOXEL_WORDS 3                   // how many of them there are; the table's allocation has room for 32 (voxel_create)
 #define VOXEL_MAX_PIXELS 0x7fffffffll
 #define VOXEL_GROUP 16384               // frames along a grid's y
 
@@ -144,9 +146,70 @@ __device__ __forceinline__ bool voxel_list_position(const VoxelTable& t, bool ta
     return true;
 }
 
+// ---- a kind's payload ------------------------------------------------------------------------------------------------------------
+// P is a small struct by value, the only place that knows the kind's arrays and the layout of its entries:
+//   typename P::Entry            a slot as the kind's getters list it
+//   head()                       the table's VoxelTable
+//   threshold(slot)              the word the getters compare with min_count / min_weight
+//   pack(slot, key, w, Entry*)   the slot as an entry; w: its threshold word, which the caller has read
+//   zero(a), move(a, b)          slot a's payload words zeroed; moved to slot b, slot a's zeroed
+//   key(entry), add(slot, entry) an entry's key; the entry's atomic adds to the slot a probe gave it
+//   units(entry)                 what the entry stands for (its count / weight): added to VOXEL_W_DROPPED when it finds no slot,
+//                                else to the counter P::UNITS_STAT; with P::ENTRY_STAT every entry also counts one in VOXEL_ST_UPDATES
+
+// One thread per slot (the grid covers the slots exactly: at least 1024 of them): the occupied slots whose threshold word is at
+// least `min` to a dense list, one atomic per wave for the positions.  out == null: only their number.
+template <class P>
+__global__ __launch_bounds__(256) void voxel_compact_kernel(P p, uint32_t min, typename P::Entry* out, unsigned long long out_cap) {
+    const uint32_t slot = blockIdx.x * 256 + threadIdx.x;
+    const unsigned long long key = p.head().keys[slot];
+    const uint32_t w = p.threshold(slot);
+    const bool take = key != MAP_EMPTY && w >= min;
+    unsigned long long at;
+    if (!voxel_list_position(p.head(), take, threadIdx.x & 63, &at)) return;   // the whole wave
+    if (take && out && at < out_cap) {
+        typename P::Entry v;
+        p.pack(slot, key, w, &v);
+        out[at] = v;
+    }
+}
+
+// One thread per slot: the key to empty, the payload, the counters and the words to zero.
+template <class P>
+__global__ __launch_bounds__(256) void voxel_clear_kernel(P p) {
+    const uint32_t slot = blockIdx.x * 256 + threadIdx.x;
+    const VoxelTable& t = p.head();
+    t.keys[slot] = MAP_EMPTY;
+    for (uint32_t w = slot; w < VOXEL_STAT_SETS * VOXEL_STAT_WORDS; w += t.mask + 1u) t.stats[w] = 0ull;   // (the smallest table has fewer slots)
+    if (slot < VOXEL_WORDS) t.words[slot] = 0ull;
+    p.zero(slot);
+}
+
+// An entry into the slot of its key, claimed if the key is new; an entry that finds no slot counts as dropped.
+template <class P>
+__device__ __forceinline__ void voxel_insert(const P& p, const typename P::Entry& v, bool* claimed) {
+    uint32_t slot;
+    if (voxel_probe(p.head().keys, p.head().mask, P::key(v), &slot, claimed)) p.add(slot, v);
+    else atomicAdd(p.head().words + VOXEL_W_DROPPED, P::units(v));
+}
+
+// One thread per entry, through the probe of the fuse kernels.
+template <class P>
+__global__ __launch_bounds__(256) void voxel_add_entries_kernel(P p, const typename P::Entry* e, unsigned long long n) {
+    const unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+    const VoxelTable& t = p.head();
+    const bool on = i < n;
+    bool claimed = false;
+    if (on) {
+        const typename P::Entry v = e[i];
+        const unsigned long long u = P::units(v);
+        voxel_insert(p, v, &claimed);
+        atomicAdd(voxel_stat(t, blockIdx.x, P::UNITS_STAT), u);
+    }
+    voxel_count_wave(t, blockIdx.x, threadIdx.x & 63, 0, P::ENTRY_STAT ? __popcll(__ballot(on)) : 0, 0, __popcll(__ballot(claimed)));
+}
+
 // ---- eviction: the voxels outside a box leave the table, in place ----------------------------------------------------------------
-// A kind's payload P is a small struct by value: `typename P::Entry`, pack(slot, key, Entry*) (the slot as the kind's getter lists
-// it), move(a, b) (the payload words of slot a to slot b, slot a's zeroed) and zero(a).
 struct VoxelBox { int32_t lo[3], hi[3]; };   // viso_voxel_box: voxel k is inside when lo[i] <= k[i] < hi[i]
 
 __device__ __forceinline__ bool voxel_in_box(unsigned long long key, const VoxelBox& b) {
@@ -174,7 +237,7 @@ __global__ __launch_bounds__(256) void voxel_evict_mark_kernel(VoxelTable t, P p
     if (out) {
         if (at >= out_cap) return;   // (a list of the first pass's length has room for all: the slot stays as it is)
         typename P::Entry v;
-        p.pack(slot, key, &v);
+        p.pack(slot, key, p.threshold(slot), &v);
         out[at] = v;
     }
     if (mode == VOXEL_EVICT_LIST) t.keys[slot] = MAP_TOMB;
@@ -215,19 +278,12 @@ __global__ __launch_bounds__(256) void voxel_evict_rebuild_kernel(VoxelTable t, 
     }
 }
 
-// Pass 3, one thread per slot: every tombstone to MAP_EMPTY, its payload zeroed as the clear kernel does.
+// Pass 3, one thread per slot: every tombstone to MAP_EMPTY, its payload zeroed as voxel_clear_kernel does.
 template <class P>
 __global__ __launch_bounds__(256) void voxel_evict_sweep_kernel(VoxelTable t, P p) {
     const uint32_t slot = blockIdx.x * 256 + threadIdx.x;
     if (t.keys[slot] != MAP_TOMB) return;
     p.zero(slot);
     t.keys[slot] = MAP_EMPTY;
-}
-
-// a clear kernel's part for the head: one thread per slot
-__device__ __forceinline__ void voxel_clear_head(const VoxelTable& t, uint32_t slot) {
-    t.keys[slot] = MAP_EMPTY;
-    for (uint32_t w = slot; w < VOXEL_STAT_SETS * VOXEL_STAT_WORDS; w += t.mask + 1u) t.stats[w] = 0ull;   // (the smallest table has fewer slots)
-    if (slot < 2) t.words[slot] = 0ull;
 }
 #endif /* VISO_VOXEL_HASH_H_ */

@@ -1,9 +1,9 @@
 // voxel_host.h — the host side of the shared table layer of the hash tables of voxels (voxelmap.hip, tsdf.hip; the device side is
 // voxel_hash.h; DESIGN.md 5.14, "Shared table layer").  A kind of map (viso_map, viso_tsdf) holds a VoxelHost, has a VoxelRegistry
-// of its live handles, and passes its kernel launches in as callables.  The rules that every kind must keep are here and in
-// voxel_host.hip, once: no handle is dereferenced before its registry has answered for it; staging is freed only behind a
-// synchronise; dropped updates become the sticky overflow mark; a temporary list is freed on every path; an eviction leaves no
-// tombstone behind.
+// of its live handles, and passes in its payload (voxel_hash.h) for the shared kernels and the launches of its own kernels as
+// callables.  The rules that every kind must keep are here and in voxel_host.hip, once: no handle is dereferenced before its
+// registry has answered for it; staging is freed only behind a synchronise; dropped updates become the sticky overflow mark; a
+// temporary list is freed on every path; an eviction leaves no tombstone behind.
 #ifndef VISO_VOXEL_HOST_H_
 #define VISO_VOXEL_HOST_H_
 #include "voxel_hash.h"
@@ -50,7 +50,16 @@ using VoxelRenderLaunch = std::function<void(const double* d_poses, int16_t* d_d
 // one group of frames of a linearise: the group's poses [.][12], its flags and its part of the sums, the group's first frame
 using VoxelLinearizeLaunch = std::function<void(const double* d_poses, const unsigned long long* d_active, unsigned long long* d_out, int frame0,
                                                 dim3 grid, hipStream_t)>;
-using VoxelEntriesLaunch = std::function<void(const void* d_entries, dim3 grid, hipStream_t)>;   // add_entries
+
+// the launches of voxel_hash.h's kernels over the payload p of a kind: one thread per slot / per entry
+template <class P>
+void voxel_start_clear(const P& p, hipStream_t s) {
+    hipLaunchKernelGGL(voxel_clear_kernel<P>, dim3((p.head().mask + 1u) / 256u), dim3(256), 0, s, p);
+}
+template <class P>
+void voxel_start_add_entries(const P& p, const typename P::Entry* d_entries, unsigned long long n, hipStream_t s) {
+    hipLaunchKernelGGL(voxel_add_entries_kernel<P>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p, d_entries, n);
+}
 
 bool voxel_known(VoxelRegistry& reg, const void* handle);
 // a live handle whose context is alive, its device current: *h set; else the error text and code
@@ -78,9 +87,36 @@ int voxel_fuse_resident(const char* where, VoxelRegistry& reg, const void* handl
                         const uint8_t* image = nullptr, size_t ifs = 0);
 int voxel_fuse_host(const char* where, VoxelRegistry& reg, const void* handle, const int16_t* disp, int rows, int cols, const viso_param* param,
                     const double* pose_or_null, const VoxelFuseLaunch& launch, const uint8_t* image = nullptr);
-// viso_*_add_entries behind the handle check and the validation of the n entries of entry_bytes each
-int voxel_add_entries(const char* where, VoxelRegistry& reg, const void* handle, const void* entries, size_t n, size_t entry_bytes,
-                      const VoxelEntriesLaunch& launch);
+// behind a call's launches: waits for them and turns dropped points / updates into the overflow mark.  h is entered and locked.
+int voxel_finish(const char* where, VoxelHost* h);
+// viso_*_add_entries behind the handle check and the validation of the n entries
+template <class P>
+int voxel_add_entries(const char* where, VoxelRegistry& reg, const void* handle, const typename P::Entry* entries, size_t n, const P& p) {
+    int r;
+    VoxelHost* h;
+    if ((r = voxel_enter(where, reg, handle, &h)) < 0) return r;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (h->overflowed) return voxel_refuse_overflowed(where, h);
+    if (!n) return VISO_OK;
+    hipStream_t s = h->ctx->stream;
+    const size_t bytes = n * sizeof(typename P::Entry);
+    typename P::Entry* d = nullptr;
+    if (hipMalloc((void**)&d, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        viso_set_error("%s: cannot allocate %zu bytes for the entries", where, bytes);
+        return VISO_ERR_NOMEM;
+    }
+    hipError_t e = hipMemcpyAsync(d, entries, bytes, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) {
+        voxel_start_add_entries(p, d, (unsigned long long)n, s);
+        e = hipGetLastError();
+    }
+    r = e == hipSuccess ? voxel_finish(where, h) : VISO_OK;
+    if (e != hipSuccess) (void)hipStreamSynchronize(s);   // nothing in flight reads the list that is freed next
+    (void)hipFree(d);
+    HIP_TRY(e);
+    return r;
+}
 // viso_*_render behind the handle and argument checks: the map entered, locked and not overflowed; the poses [n_views][16] (or
 // null) through d_pose; a device buffer for n_views maps of px int16 and, with weight_out, as many uint32, and, with gray_out, as
 // many uint8, freed on every path; the groups of views, each started by `launch` with its poses ([.][12] or null) and its part of
@@ -142,15 +178,18 @@ int voxel_extract(const char* where, VoxelRegistry& reg, const void* handle, uin
     return VISO_OK;
 }
 
-// ---- eviction (include/viso_hip.h, "Map eviction"; the kernels are voxel_hash.h's) --------------------------------------------------
-// what a kind passes in: its payload for the three kernels and, for a table without an empty slot, its clear and its add_entries
+// The count (count_only) or the sorted list of the voxels whose threshold word is at least `min`, as the payload p packs them:
+// viso_*_count / viso_*_get, whole.  (p is the caller's own copy: the handle is not touched before the registry has answered.)
 template <class P>
-struct VoxelEvictKind {
-    P payload;
-    VoxelLaunch clear;
-    std::function<void(const typename P::Entry* d_entries, unsigned long long n, dim3 grid, hipStream_t)> add;
-};
+int voxel_entries(const char* where, VoxelRegistry& reg, const void* handle, uint32_t min, bool count_only, typename P::Entry* entries_out,
+                  size_t n_cap, size_t* n, const P& p) {
+    return voxel_extract<typename P::Entry>(where, reg, handle, min, count_only, entries_out, n_cap, n,
+                                            [p, min](typename P::Entry* out, unsigned long long out_cap, hipStream_t s) {
+        hipLaunchKernelGGL(voxel_compact_kernel<P>, dim3((p.head().mask + 1u) / 256u), dim3(256), 0, s, p, min, out, out_cap);
+    });
+}
 
+// ---- eviction (include/viso_hip.h, "Map eviction"; the kernels are voxel_hash.h's) --------------------------------------------------
 // the checks of an eviction's arguments that need no device; false: the error text is set
 bool voxel_evict_args(const char* where, VoxelRegistry& reg, const void* handle, const viso_voxel_box* keep, const size_t* n);
 // The statistics of h (entered and locked) as they lie on the device, [VOXEL_STAT_SETS][VOXEL_STAT_WORDS], and the sum of their
@@ -161,11 +200,11 @@ int voxel_evict_put_stats(VoxelHost* h, std::vector<unsigned long long>& stats, 
 // viso_*_evict_count (count_only) and viso_*_evict, whole.  A first pass counts the voxels outside the box; a second one lists them
 // (items_out null: lists nothing) and turns their keys into tombstones, the rebuild pass moves every survivor to where a probe
 // finds it, the sweep empties the tombstones; the occupied counter falls on the host.  Device memory: the list of the evicted.  A
-// table without an empty slot has no cluster head to start a rebuild from: it goes through a list of its survivors, the kind's
-// clear and its add_entries, and gets its statistics back.  The list's order is the kind's voxel_item_less, as in voxel_extract.
+// table without an empty slot has no cluster head to start a rebuild from: it goes through a list of its survivors, the clear
+// and add_entries, and gets its statistics back.  The list's order is the kind's voxel_item_less, as in voxel_extract.
 template <class P>
 int voxel_evict(const char* where, VoxelRegistry& reg, const void* handle, const viso_voxel_box* keep, bool count_only,
-                typename P::Entry* items_out, size_t n_cap, size_t* n, const VoxelEvictKind<P>& kind) {
+                typename P::Entry* items_out, size_t n_cap, size_t* n, const P& p) {
     using Item = typename P::Entry;
     if (!voxel_evict_args(where, reg, handle, keep, n)) return VISO_ERR_ARG;
     int r;
@@ -180,7 +219,7 @@ int voxel_evict(const char* where, VoxelRegistry& reg, const void* handle, const
     const VoxelTable head = h->head;
     auto mark = [&](int mode, Item* out, unsigned long long cap) {
         return [&, mode, out, cap](hipStream_t s) {
-            hipLaunchKernelGGL(voxel_evict_mark_kernel<P>, grid, dim3(256), 0, s, head, kind.payload, box, mode, out, cap);
+            hipLaunchKernelGGL(voxel_evict_mark_kernel<P>, grid, dim3(256), 0, s, head, p, box, mode, out, cap);
         };
     };
     unsigned long long c = 0, c2 = 0, occupied = 0;
@@ -206,8 +245,8 @@ int voxel_evict(const char* where, VoxelRegistry& reg, const void* handle, const
     if (!full) {
         r = voxel_pass(h, mark(VOXEL_EVICT_LIST, d_out, c), &c2);
         if (r >= 0) {   // tombstones are in the table: both passes follow whatever else happens
-            hipLaunchKernelGGL(voxel_evict_rebuild_kernel<P>, grid, dim3(256), 0, s, head, kind.payload);
-            hipLaunchKernelGGL(voxel_evict_sweep_kernel<P>, grid, dim3(256), 0, s, head, kind.payload);
+            hipLaunchKernelGGL(voxel_evict_rebuild_kernel<P>, grid, dim3(256), 0, s, head, p);
+            hipLaunchKernelGGL(voxel_evict_sweep_kernel<P>, grid, dim3(256), 0, s, head, p);
             e = hipGetLastError();
         }
     } else {
@@ -217,8 +256,8 @@ int voxel_evict(const char* where, VoxelRegistry& reg, const void* handle, const
         if (r >= 0 && n_keep) r = voxel_pass(h, mark(VOXEL_EVICT_KEEP, d_keep, n_keep), &k2);
         if (r >= 0 && k2 != n_keep) c2 = ~0ull;
         if (r >= 0 && c2 == c) {
-            kind.clear(s);
-            if (n_keep) kind.add(d_keep, n_keep, dim3((unsigned)((n_keep + 255) / 256)), s);
+            voxel_start_clear(p, s);
+            if (n_keep) voxel_start_add_entries(p, d_keep, n_keep, s);
             e = hipGetLastError();
         }
     }

@@ -1,8 +1,8 @@
 // voxel_host.hip — the host side of the shared table layer (voxel_host.h): the registry of live handles, the life of a table, the
-// staging (the map, the poses and, where a kind fuses one, the image) and the group loop of a fuse, the scaffold of add_entries, the
-// pass of an extraction, the staging and the output buffer of a render, the staging and the sums of a linearise, the read-back of the
+// staging (the map, the poses and, where a kind fuses one, the image) and the group loop of a fuse, the wait behind a call's launches,
+// the pass of an extraction, the staging and the output buffer of a render, the staging and the sums of a linearise, the read-back of the
 // statistics, and of an eviction the argument checks, the statistics' round trip and the box around a point.
-// No kernel is here: every kind passes its launches in.
+// No kernel is here: a kind passes in the launches of its own kernels, and the templates of voxel_host.h start the shared ones.
 #include "voxel_host.h"
 
 #include <climits>
@@ -47,7 +47,9 @@ int voxel_create(const char* where, VoxelRegistry& reg, viso_ctx* ctx_or_null, i
     HIP_TRY(hipSetDevice(c->device));
     const size_t slots = (size_t)1 << capacity_log2;
     const size_t b_keys = 8 * slots, b_payload = payload_bytes * slots, b_stats = 8 * VOXEL_STAT_SETS * VOXEL_STAT_WORDS;
-    const size_t bytes = b_keys + b_payload + b_stats + 256;
+    const size_t b_words = 256;
+    static_assert(VOXEL_WORDS * sizeof(unsigned long long) <= b_words, "the clear kernel zeroes VOXEL_WORDS words behind the stats");
+    const size_t bytes = b_keys + b_payload + b_stats + b_words;
     void* block = nullptr;
     if (hipMalloc(&block, bytes) != hipSuccess) {
         (void)hipGetLastError();
@@ -128,8 +130,7 @@ static int voxel_grow(const char* where, T** p, size_t* have, size_t bytes, hipS
     return VISO_OK;
 }
 
-// behind a call's launches: waits for them and turns dropped points / updates into the overflow mark
-static int voxel_finish(const char* where, VoxelHost* h) {
+int voxel_finish(const char* where, VoxelHost* h) {
     unsigned long long dropped = 0;
     hipStream_t s = h->ctx->stream;
     HIP_TRY(hipMemcpyAsync(&dropped, h->head.words + VOXEL_W_DROPPED, sizeof(dropped), hipMemcpyDeviceToHost, s));
@@ -226,33 +227,6 @@ int voxel_fuse_host(const char* where, VoxelRegistry& reg, const void* handle, c
     }
     return voxel_fuse_device(where, h, h->d_disp, px, rows, cols, 1, param->f, param->cu, param->cv, param->base, pose_or_null, launch,
                              image ? h->d_image : nullptr, px);
-}
-
-int voxel_add_entries(const char* where, VoxelRegistry& reg, const void* handle, const void* entries, size_t n, size_t entry_bytes,
-                      const VoxelEntriesLaunch& launch) {
-    int r;
-    VoxelHost* h;
-    if ((r = voxel_enter(where, reg, handle, &h)) < 0) return r;
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (h->overflowed) return voxel_refuse_overflowed(where, h);
-    if (!n) return VISO_OK;
-    hipStream_t s = h->ctx->stream;
-    void* d = nullptr;
-    if (hipMalloc(&d, n * entry_bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        viso_set_error("%s: cannot allocate %zu bytes for the entries", where, n * entry_bytes);
-        return VISO_ERR_NOMEM;
-    }
-    hipError_t e = hipMemcpyAsync(d, entries, n * entry_bytes, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) {
-        launch(d, dim3((unsigned)((n + 255) / 256)), s);
-        e = hipGetLastError();
-    }
-    r = e == hipSuccess ? voxel_finish(where, h) : VISO_OK;
-    if (e != hipSuccess) (void)hipStreamSynchronize(s);   // nothing in flight reads the list that is freed next
-    (void)hipFree(d);
-    HIP_TRY(e);
-    return r;
 }
 
 int voxel_pass(VoxelHost* h, const VoxelLaunch& launch, unsigned long long* n) {

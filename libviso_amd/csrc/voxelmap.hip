@@ -10,15 +10,12 @@
 //                           that continue the key of the lane to their left form a run: the run heads from one ballot, the runs' offset
 //                           sums from two wave scans (DPP) of the packed offsets and one exchange with the run's last lane.  Only the
 //                           head lane probes the table and issues the four atomic adds (count, three sums).
-//   map_add_entries_kernel  one thread per entry through the same probe.
-//   map_compact_kernel      one thread per slot: the occupied slots with count >= min_count to a dense list, one atomic per wave for
-//                           the list positions (out == null: only their number).
-//   map_clear_kernel        one thread per slot.
 // What every table of voxels shares is not here: the key, the probes, a pixel's point, the runs of a wave, the counters (256 sets on
-// cache lines of their own, one atomic per wave and counter, summed on the host), the list positions and the head's clear are
-// voxel_hash.h; the handles, the life of a table, the staging and the group loop of a fuse, the scaffold of add_entries, the two
-// passes of the getters and the statistics' read-back are voxel_host.h.  This file keeps the table's payload and insert, the
-// kernels' own bodies, the parameter and entry checks and the order of the entries.
+// cache lines of their own, one atomic per wave and counter, summed on the host), the list positions and the kernels that list,
+// clear, add entries to and evict slots (templates over a kind's payload, instantiated here over MapPayload) are voxel_hash.h; the
+// handles, the life of a table, the staging and the group loop of a fuse, the scaffold of add_entries, the two passes of the
+// getters, the eviction and the statistics' read-back are voxel_host.h.  This file keeps the table's payload, the fuse kernel and
+// its insert, the parameter and entry checks and the order of the entries.
 #include "common.h"
 #include "wave.h"
 #include "voxel_host.h"
@@ -95,48 +92,23 @@ __global__ __launch_bounds__(256) void map_fuse_kernel(FuseArgs a) {
     map_count_wave(a.t, blockIdx.x + blockIdx.y, lane, point, ins, oor, claimed);
 }
 
-__global__ __launch_bounds__(256) void map_add_entries_kernel(MapTable t, const viso_map_entry* e, unsigned long long n) {
-    const unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
-    const bool on = i < n;
-    bool claimed = false;
-    if (on) {
-        const viso_map_entry v = e[i];
-        map_insert(t, voxel_key(v.k[0], v.k[1], v.k[2]), v.count, v.sum[0], v.sum[1], v.sum[2], &claimed);
-        atomicAdd(voxel_stat(t.head, blockIdx.x, VOXEL_ST_POINTS), (unsigned long long)v.count);
-    }
-    map_count_wave(t, blockIdx.x, threadIdx.x & 63, false, on, false, claimed);
-}
-
-__global__ __launch_bounds__(256) void map_compact_kernel(MapTable t, uint32_t min_count, viso_map_entry* out, unsigned long long out_cap) {
-    const uint32_t slot = blockIdx.x * 256 + threadIdx.x;   // the grid covers the slots exactly (at least 1024 of them)
-    const unsigned long long key = t.head.keys[slot];
-    const uint32_t c = t.cnt[slot];
-    const bool take = key != MAP_EMPTY && c >= min_count;
-    unsigned long long at;
-    if (!voxel_list_position(t.head, take, threadIdx.x & 63, &at)) return;   // the whole wave
-    if (take && out && at < out_cap) {
-        viso_map_entry v;
-        voxel_unkey(key, v.k);
-        v.count = c;
-        v.sum[0] = t.sums[3 * (size_t)slot + 0]; v.sum[1] = t.sums[3 * (size_t)slot + 1]; v.sum[2] = t.sums[3 * (size_t)slot + 2];
-        out[at] = v;
-    }
-}
-
-__global__ __launch_bounds__(256) void map_clear_kernel(MapTable t) {
-    const uint32_t slot = blockIdx.x * 256 + threadIdx.x;
-    voxel_clear_head(t.head, slot);
-    t.cnt[slot] = 0u;
-    t.sums[3 * (size_t)slot + 0] = 0ull; t.sums[3 * (size_t)slot + 1] = 0ull; t.sums[3 * (size_t)slot + 2] = 0ull;
-}
-
-// the payload of a slot for the eviction's kernels (voxel_hash.h)
+// what is in a slot, for the shared kernels that list, zero, add to and evict slots (voxel_hash.h, "a kind's payload")
 struct MapPayload {
     MapTable t;
     using Entry = viso_map_entry;
-    __device__ __forceinline__ void pack(uint32_t slot, unsigned long long key, Entry* v) const {
+    static constexpr int UNITS_STAT = VOXEL_ST_POINTS;   // add_entries: an entry's count to n_points,
+    static constexpr bool ENTRY_STAT = true;             // and one insert an entry
+    __host__ __device__ __forceinline__ const VoxelTable& head() const { return t.head; }
+    __device__ __forceinline__ uint32_t threshold(uint32_t slot) const { return t.cnt[slot]; }
+    __device__ __forceinline__ static unsigned long long key(const Entry& v) { return voxel_key(v.k[0], v.k[1], v.k[2]); }
+    __device__ __forceinline__ static unsigned long long units(const Entry& v) { return v.count; }
+    __device__ __forceinline__ void add(uint32_t slot, const Entry& v) const {
+        atomicAdd(t.cnt + slot, v.count);
+        for (int i = 0; i < 3; ++i) atomicAdd(t.sums + 3 * (size_t)slot + i, v.sum[i]);
+    }
+    __device__ __forceinline__ void pack(uint32_t slot, unsigned long long key, uint32_t count, Entry* v) const {
         voxel_unkey(key, v->k);
-        v->count = t.cnt[slot];
+        v->count = count;
         v->sum[0] = t.sums[3 * (size_t)slot + 0]; v->sum[1] = t.sums[3 * (size_t)slot + 1]; v->sum[2] = t.sums[3 * (size_t)slot + 2];
     }
     __device__ __forceinline__ void zero(uint32_t a) const {
@@ -170,7 +142,7 @@ extern "C" void viso_map_params_default(viso_map_params* p) {
 
 // the launches the shared layer asks for; m is live by then
 static VoxelLaunch map_clear_launch(viso_map* m) {
-    return [m](hipStream_t s) { hipLaunchKernelGGL(map_clear_kernel, dim3((m->t.head.mask + 1u) / 256u), dim3(256), 0, s, m->t); };
+    return [m](hipStream_t s) { voxel_start_clear(MapPayload{m->t}, s); };
 }
 static VoxelFuseLaunch map_fuse_launch(viso_map* m) {
     return [m](const VoxelFuseArgs& v, const uint8_t*, dim3 grid, hipStream_t s) {   // (a voxel map fuses no image)
@@ -230,9 +202,7 @@ extern "C" int viso_map_add_entries(viso_map* m, const viso_map_entry* entries, 
         for (int k = 0; k < 3; ++k) ok = ok && e.k[k] >= -MAP_BIAS && e.k[k] < MAP_BIAS && e.sum[k] <= 1023ull * e.count;
         if (!ok) { viso_set_error("%s: entry %zu is not a voxel of a map (k in -2^20 .. 2^20 - 1, count >= 1, sum <= 1023 count)", where, i); return VISO_ERR_ARG; }
     }
-    return voxel_add_entries(where, g_maps, m, entries, n, sizeof(viso_map_entry), [m, n](const void* d, dim3 grid, hipStream_t s) {
-        hipLaunchKernelGGL(map_add_entries_kernel, grid, dim3(256), 0, s, m->t, static_cast<const viso_map_entry*>(d), (unsigned long long)n);
-    });
+    return voxel_add_entries(where, g_maps, m, entries, n, MapPayload{m->t});
 }
 
 static inline bool voxel_item_less(const viso_map_entry& x, const viso_map_entry& y) {
@@ -241,10 +211,8 @@ static inline bool voxel_item_less(const viso_map_entry& x, const viso_map_entry
 
 // the count or the sorted list of the voxels with count >= min_count
 static int map_extract(const char* where, viso_map* m, uint32_t min_count, bool count_only, viso_map_entry* entries_out, size_t n_cap, size_t* n) {
-    return voxel_extract<viso_map_entry>(where, g_maps, m, min_count, count_only, entries_out, n_cap, n,
-                                         [m, min_count](viso_map_entry* out, unsigned long long out_cap, hipStream_t s) {
-        hipLaunchKernelGGL(map_compact_kernel, dim3((m->t.head.mask + 1u) / 256u), dim3(256), 0, s, m->t, min_count, out, out_cap);
-    });
+    if (!voxel_known(g_maps, m)) { viso_set_error("%s: not a live map handle", where); return VISO_ERR_ARG; }
+    return voxel_entries(where, g_maps, m, min_count, count_only, entries_out, n_cap, n, MapPayload{m->t});
 }
 extern "C" int viso_map_count(viso_map* m, uint32_t min_count, size_t* n) { return map_extract("viso_map_count", m, min_count, true, nullptr, 0, n); }
 extern "C" int viso_map_get(viso_map* m, uint32_t min_count, viso_map_entry* entries_out, size_t n_cap, size_t* n) {
@@ -253,11 +221,7 @@ extern "C" int viso_map_get(viso_map* m, uint32_t min_count, viso_map_entry* ent
 
 static int map_evict(const char* where, viso_map* m, const viso_voxel_box* keep, bool count_only, viso_map_entry* evicted_out, size_t n_cap, size_t* n) {
     if (!voxel_known(g_maps, m)) { viso_set_error("%s: not a live map handle", where); return VISO_ERR_ARG; }
-    const VoxelEvictKind<MapPayload> kind = {MapPayload{m->t}, map_clear_launch(m),
-        [m](const viso_map_entry* d, unsigned long long k, dim3 grid, hipStream_t s) {
-            hipLaunchKernelGGL(map_add_entries_kernel, grid, dim3(256), 0, s, m->t, d, k);
-        }};
-    return voxel_evict<MapPayload>(where, g_maps, m, keep, count_only, evicted_out, n_cap, n, kind);
+    return voxel_evict(where, g_maps, m, keep, count_only, evicted_out, n_cap, n, MapPayload{m->t});
 }
 extern "C" int viso_map_evict_count(viso_map* m, const viso_voxel_box* keep, size_t* n) {
     return map_evict("viso_map_evict_count", m, keep, true, nullptr, 0, n);

@@ -21,8 +21,9 @@ from estimator_util import kernel_resources
 from test_speckle_cpu import random_map
 
 POSE = GC.POSE
-GRAY_KERNELS = ("tsdf_gray_fuse_kernel", "tsdf_gray_add_entries_kernel", "tsdf_gray_compact_kernel", "tsdf_gray_sample_kernel",
-                "tsdf_gray_render_kernel", "tsdf_gray_clear_kernel")
+GRAY_KERNELS = ("tsdf_gray_fuse_kernel", "tsdf_gray_sample_kernel", "tsdf_gray_render_kernel")
+# the gray map's instances of voxel_hash.h's templates, by mangled name
+GRAY_SHARED = tuple(f"voxel_{k}_kernelI11TsdfPayloadILb1EE" for k in ("add_entries", "compact", "clear", "evict_mark", "evict_rebuild", "evict_sweep"))
 
 
 def _same(a, b):
@@ -356,7 +357,7 @@ def test_png8_round_trip_and_filters(tmp_path):
 
 
 def test_new_kernels_have_no_scratch():
-    res = kernel_resources("tsdf.hip", GRAY_KERNELS)
+    res = kernel_resources("tsdf.hip", GRAY_KERNELS + GRAY_SHARED)
     for name, (occ, scratch) in res.items():
         print(f"{name}: occupancy {occ}, scratch {scratch}")
         assert scratch == 0 and occ >= 1

@@ -279,7 +279,8 @@ def test_ply_header_and_size(tmp_path):
 
 
 def test_kernels_have_no_scratch():
-    names = ("map_fuse_kernel", "map_add_entries_kernel", "map_compact_kernel", "map_clear_kernel")
+    shared = ("add_entries", "compact", "clear", "evict_mark", "evict_rebuild", "evict_sweep")   # voxel_hash.h's templates, by mangled name
+    names = ("map_fuse_kernel",) + tuple(f"voxel_{k}_kernelI10MapPayload" for k in shared)
     res = kernel_resources("voxelmap.hip", names)
     for name, (occ, scratch) in res.items():
         print(f"{name}: occupancy {occ}, scratch {scratch}")

@@ -264,7 +264,8 @@ def test_ply_header_and_bytes(tmp_path):
 
 
 def test_kernels_have_no_scratch():
-    names = ("tsdf_fuse_kernel", "tsdf_add_entries_kernel", "tsdf_compact_kernel", "tsdf_crossings_kernel", "tsdf_clear_kernel")
+    shared = ("add_entries", "compact", "clear", "evict_mark", "evict_rebuild", "evict_sweep")   # voxel_hash.h's templates, by mangled name
+    names = ("tsdf_fuse_kernel", "tsdf_crossings_kernel") + tuple(f"voxel_{k}_kernelI11TsdfPayloadILb0EE" for k in shared)
     res = kernel_resources("tsdf.hip", names)
     for name, (occ, scratch) in res.items():
         print(f"{name}: occupancy {occ}, scratch {scratch}")
