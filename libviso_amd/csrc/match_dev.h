@@ -195,7 +195,8 @@ __device__ __forceinline__ int bucket_of(float x, float x0, float scale) {
     return f <= 0.f ? 0 : (f >= (float)(NB - 1) ? NB - 1 : (int)f);
 }
 // bucket_of without the guard of the product, as the LDS-resident experiment (tools/experiments/match_strip.hip, debug builds)
-// has always had it: sound for a finite or NaN x only -- an infinite x with scale 0 gives a NaN product and (int)NaN.  Kept
+// has always had it: sound for a finite or NaN x only, and a finite x0 -- an infinite x or x0 with scale 0 (or x = x0 = +-inf)
+// gives a NaN product and (int)NaN.  Kept
 // apart because the guard changes that kernel's code; nothing else may use it.
 template <int NB>
 __device__ __forceinline__ int bucket_of_finite(float x, float x0, float scale) {
@@ -219,7 +220,8 @@ __device__ __forceinline__ int bucket_cvt(float x, float x0, float scale) {
 // four lanes, so that a quad broadcast hands every lane the four queries its half tests in phase 1)
 __device__ __forceinline__ constexpr int qlane(int k) { return (k & 3) + 32 * (k >> 2); }
 
-// Ascending bitonic sort of `npad` (power of two, >= 64) 64-bit keys in LDS by a workgroup of THREADS threads.
+// Ascending bitonic sort of `npad` (power of two, >= 64) 64-bit keys in LDS by a workgroup of THREADS threads; touches
+// keys[0 .. npad) only (tests/test_dev_harness_cpu.py enumerates the indices).
 // Every wave owns a contiguous chunk of comparators (CW per stage), hence a contiguous chunk of 2*CW keys: the
 // stages whose partner distance j fits the chunk are wave local and need no workgroup barrier (LDS operations of one
 // wave complete in order) — for 2048 keys and 8 waves that is 60 of the 66 stages.  Index arithmetic by shifts.
@@ -229,7 +231,9 @@ __device__ __forceinline__ void bitonic_sort_lds(unsigned long long* keys, int n
     constexpr int NW = THREADS / 64;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int half = npad >> 1;
-    const int cw = half >= THREADS ? half / NW : 64;   // comparators per wave and stage
+    // comparators per wave and stage: never more than the network has (npad = 64: 32, all of them wave 0's -- with 64 the upper
+    // 32 compared keys[64..127], beyond the npad keys the caller owns)
+    const int cw = half >= THREADS ? half / NW : min(half, 64);
     const bool active = wave * cw < half;
     for (int k = 2, lk = 1; k <= npad; k <<= 1, ++lk) {
         for (int j = k >> 1, lj = lk - 1; j > 0; j >>= 1, --lj) {

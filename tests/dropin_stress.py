@@ -28,7 +28,9 @@ for mode in ((True, True), (False, True), (True, False)):
     # matrices of condition 1e18 -- tools/experiments/stress_diag.py, frames 76 and 196 -- where the last bit of a sum decides
     # whether the LU calls the system singular or takes a garbage step; such a hypothesis has no motion on either side and its
     # support of 0..2 points is not comparable.  tests/test_gpu_solver_edges.py::test_every_hypothesis_against_the_oracle is the
-    # per-hypothesis comparison on well-posed data.)
+    # per-hypothesis comparison on well-posed data.  The LU itself is not where the two sides part: on identical 6 x 6 systems,
+    # twin-point ones included, the device's lu_solve6 equals the oracle's bit for bit, verdict and solution --
+    # tests/test_gpu_dev_helpers.py::test_lu_solve6_is_the_oracles_lu_bit_for_bit; what differs is the matrix each side sums up.)
     assert np.array_equal(o["n_inl"][want["ok"] == 1], want["n_inl"][want["ok"] == 1]), mode
     differ = np.nonzero(o["n_inl"] != want["n_inl"])[0]
     assert len(differ) <= 4 and (np.maximum(o["n_inl"][differ], want["n_inl"][differ]) < 6).all(), (mode, differ)

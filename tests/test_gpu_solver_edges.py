@@ -362,7 +362,10 @@ def test_every_hypothesis_against_the_oracle(viso, oracle, case):
             c1 = int(cnt_h[t, h]) if ok_h[t, h] else 0
             P3 = X[:, S[h]]
             twin = bool((P3[:, 0] == P3[:, 1]).all() or (P3[:, 0] == P3[:, 2]).all() or (P3[:, 1] == P3[:, 2]).all())
-            if it0 <= 20 and not twin:   # (two circle matches can share a previous-frame point: a triple with twins is a singular system)
+            # (two circle matches can share a previous-frame point: a triple with twins is a singular system.  Its verdict differs
+            # through the last bits of the normal matrix each side sums up, not through the LU: on identical matrices lu_solve6
+            # equals oracle.lu_solve6 bit for bit, test_gpu_dev_helpers.py::test_lu_solve6_is_the_oracles_lu_bit_for_bit)
+            if it0 <= 20 and not twin:
                 decided += 1
                 assert ok_h[t, h] == ok0, (t, h, S[h], it0)
                 if ok0:
