@@ -51,21 +51,18 @@ int kitti_count_frames(const std::string& seq_base, int begin, int end) {
     return n;
 }
 
-std::vector<FrameRecord> kitti_run_range(const std::string& seq_base, const Matd& P1, const Matd& P2, int begin,
-                                         int first, int last, int device, int chunk, uint64_t ransac_seed,
-                                         int decode_threads, OdometryStats* stats, int subpixel, const StereoRectification* rect,
-                                         int cov_mode, double cov_sigma, std::vector<viso_motion_cov>* cov, const DisparityOutput* disp) {
-    std::vector<FrameRecord> rec;
-    if (cov) cov->clear();
-    if (last <= first) return rec;
+RangeResult kitti_run_range(const std::string& seq_base, const Matd& P1, const Matd& P2, int begin, int first, int last,
+                            const RunOptions& opt) {
+    RangeResult out;
+    if (last <= first) return out;
     const std::string ext = kitti_image_ext(seq_base, begin);
     StereoImageGenerator images({seq_base + "/image_0/%06d" + ext, seq_base + "/image_1/%06d" + ext},
                                 begin + first, begin + last);
-    DisparityOutput d;
-    if (disp) { d = *disp; d.write_first = first == 0; }   // frame `first` of a later range is the previous range's last frame
-    OdometryResult res = sequence_odometry(P1, P2, images, chunk, ransac_seed, (uint64_t)(begin + first), device, decode_threads,
-                                           subpixel, rect, cov ? cov_mode : 0, cov_sigma, disp ? &d : nullptr);
-    if (stats) *stats = res.stats;
+    RunOptions o = opt;
+    o.first_frame_index = (uint64_t)(begin + first);
+    o.disparity.write_first = first == 0;   // frame `first` of a later range is the previous range's last frame
+    const OdometryResult res = sequence_odometry(P1, P2, images, o);
+    out.stats = res.stats;
     // res.ok / res.tr / res.n_inliers: one entry per frame read, entry 0 = this range's first frame (no pose)
     for (size_t t = 1; t < res.ok.size(); ++t) {
         FrameRecord r;
@@ -74,64 +71,33 @@ std::vector<FrameRecord> kitti_run_range(const std::string& seq_base, const Matd
         r.n_inl = res.n_inliers[t];
         r.frame = begin + first + (int)t;
         r.reserved = 0;
-        rec.push_back(r);
-        if (cov && t < res.cov.size()) cov->push_back(res.cov[t]);
+        out.rec.push_back(r);
+        if (t < res.cov.size()) out.cov.push_back(res.cov[t]);
     }
-    return rec;
+    return out;
+}
+
+bool write_atomically(const std::string& file_name, const char* mode, const std::function<bool(FILE*)>& write) {
+    const std::string tmp = file_name + ".tmp";
+    FILE* fp = std::fopen(tmp.c_str(), mode);
+    if (!fp) return false;
+    bool ok = write(fp);
+    ok = (std::fclose(fp) == 0) && ok;
+    return ok && std::rename(tmp.c_str(), file_name.c_str()) == 0;
 }
 
 bool write_covariance_file(const std::string& file_name, const viso_motion_cov* rec, size_t n) {
-    const std::string tmp = file_name + ".tmp";
-    FILE* fp = std::fopen(tmp.c_str(), "w");
-    if (!fp) return false;
-    bool ok = true;
-    for (size_t i = 0; i < n && ok; ++i) {
-        const viso_motion_cov& c = rec[i];
-        ok = std::fprintf(fp, "%d %d %.17g %.17g", (int)c.status, (int)c.n, c.sigma2, c.gap) > 0;
-        for (int p = 0; p < 6 && ok; ++p)
-            for (int q = p; q < 6 && ok; ++q) ok = std::fprintf(fp, " %.17g", c.cov[6 * p + q]) > 0;
-        ok = ok && std::fputc('\n', fp) != EOF;
-    }
-    ok = (std::fclose(fp) == 0) && ok;
-    return ok && std::rename(tmp.c_str(), file_name.c_str()) == 0;
-}
-
-static const int32_t COV_MAGIC = 0x56534B43;   // "VSKC"
-
-bool write_cov_records(const std::string& file_name, int first, int last, const std::vector<viso_motion_cov>& rec) {
-    const std::string tmp = file_name + ".tmp";
-    FILE* fp = std::fopen(tmp.c_str(), "wb");
-    if (!fp) return false;
-    const int32_t hdr[4] = {COV_MAGIC, first, last, (int32_t)rec.size()};
-    bool ok = std::fwrite(hdr, sizeof hdr, 1, fp) == 1;
-    if (ok && !rec.empty()) ok = std::fwrite(rec.data(), sizeof(viso_motion_cov), rec.size(), fp) == rec.size();
-    ok = (std::fclose(fp) == 0) && ok;
-    return ok && std::rename(tmp.c_str(), file_name.c_str()) == 0;
-}
-
-bool read_cov_records(const std::string& file_name, int& first, int& last, std::vector<viso_motion_cov>& rec) {
-    FILE* fp = std::fopen(file_name.c_str(), "rb");
-    if (!fp) return false;
-    int32_t hdr[4];
-    bool ok = std::fread(hdr, sizeof hdr, 1, fp) == 1 && hdr[0] == COV_MAGIC && hdr[3] >= 0 && hdr[2] >= hdr[1] &&
-              hdr[3] <= hdr[2] - hdr[1];
-    if (ok) {
-        first = hdr[1]; last = hdr[2];
-        rec.resize((size_t)hdr[3]);
-        if (hdr[3]) ok = std::fread(rec.data(), sizeof(viso_motion_cov), rec.size(), fp) == rec.size();
-    }
-    std::fclose(fp);
-    return ok;
-}
-
-std::vector<viso_motion_cov> stitch_cov_records(const std::vector<std::vector<viso_motion_cov>>& parts,
-                                                const std::vector<std::pair<int, int>>& ranges) {
-    std::vector<viso_motion_cov> all;   // the same cut as stitch_records
-    for (size_t r = 0; r < parts.size() && r < ranges.size(); ++r) {
-        all.insert(all.end(), parts[r].begin(), parts[r].end());
-        if ((int)parts[r].size() < ranges[r].second - ranges[r].first) break;
-    }
-    return all;
+    return write_atomically(file_name, "w", [&](FILE* fp) {
+        bool ok = true;
+        for (size_t i = 0; i < n && ok; ++i) {
+            const viso_motion_cov& c = rec[i];
+            ok = std::fprintf(fp, "%d %d %.17g %.17g", (int)c.status, (int)c.n, c.sigma2, c.gap) > 0;
+            for (int p = 0; p < 6 && ok; ++p)
+                for (int q = p; q < 6 && ok; ++q) ok = std::fprintf(fp, " %.17g", c.cov[6 * p + q]) > 0;
+            ok = ok && std::fputc('\n', fp) != EOF;
+        }
+        return ok;
+    });
 }
 
 std::vector<Matd> chain_records(const FrameRecord* rec, int n, bool reference_pose_list) {
@@ -150,68 +116,99 @@ std::vector<Matd> chain_records(const FrameRecord* rec, int n, bool reference_po
     return poses;
 }
 
-static const int32_t REC_MAGIC = 0x56534B52;   // "VSKR"
-
-bool write_records(const std::string& file_name, int first, int last, const std::vector<FrameRecord>& rec) {
-    // written under a temporary name and renamed: a reader never sees a partial file
-    const std::string tmp = file_name + ".tmp";
-    FILE* fp = std::fopen(tmp.c_str(), "wb");
-    if (!fp) return false;
-    const int32_t hdr[4] = {REC_MAGIC, first, last, (int32_t)rec.size()};
-    bool ok = std::fwrite(hdr, sizeof hdr, 1, fp) == 1;
-    if (ok && !rec.empty()) ok = std::fwrite(rec.data(), sizeof(FrameRecord), rec.size(), fp) == rec.size();
-    ok = (std::fclose(fp) == 0) && ok;
-    return ok && std::rename(tmp.c_str(), file_name.c_str()) == 0;
-}
-
-bool read_records(const std::string& file_name, int& first, int& last, std::vector<FrameRecord>& rec) {
-    FILE* fp = std::fopen(file_name.c_str(), "rb");
-    if (!fp) return false;
-    int32_t hdr[4];
-    bool ok = std::fread(hdr, sizeof hdr, 1, fp) == 1 && hdr[0] == REC_MAGIC && hdr[3] >= 0 && hdr[2] >= hdr[1] &&
-              hdr[3] <= hdr[2] - hdr[1];
-    if (ok) {
-        first = hdr[1]; last = hdr[2];
-        rec.resize((size_t)hdr[3]);
-        if (hdr[3]) ok = std::fread(rec.data(), sizeof(FrameRecord), rec.size(), fp) == rec.size();
-    }
-    std::fclose(fp);
-    return ok;
-}
-
-std::vector<FrameRecord> stitch_records(const std::vector<std::vector<FrameRecord>>& parts,
-                                        const std::vector<std::pair<int, int>>& ranges) {
-    std::vector<FrameRecord> all;
-    for (size_t r = 0; r < parts.size() && r < ranges.size(); ++r) {
-        all.insert(all.end(), parts[r].begin(), parts[r].end());
-        if ((int)parts[r].size() < ranges[r].second - ranges[r].first) break;   // the sequence ends here for one process too
-    }
-    return all;
-}
-
 void mkdirs(const std::string& path) {
     for (size_t i = 1; i <= path.size(); ++i)
         if (i == path.size() || path[i] == '/') ::mkdir(path.substr(0, i).c_str(), 0777);
+}
+
+void mkdirs_for(const std::string& file_name) {
+    const size_t slash = file_name.rfind('/');
+    if (slash != std::string::npos && slash > 0) mkdirs(file_name.substr(0, slash));
+}
+
+std::string set_subpixel(RunOptions& opt, int mode) {
+    if (mode < 0 || mode > 2) return "viso_kitti_set_subpixel: mode must be 0, 1 or 2";
+    opt.subpixel = mode;
+    return "";
+}
+
+std::string set_covariance(RunOptions& opt, int mode, double sigma_px) {
+    if (mode != 0 && mode != 1 && !(mode == 2 && std::isfinite(sigma_px) && sigma_px > 0.0))
+        return "viso_kitti_set_covariance: mode 0, 1, or 2 with a finite sigma_px > 0";
+    opt.cov_mode = mode;
+    opt.cov_sigma = mode == 2 ? sigma_px : 0.0;
+    return "";
+}
+
+std::string set_rectify(RunOptions& opt, Matd& P1, Matd& P2, const char* cam_to_cam_file) {
+    if (!cam_to_cam_file || !*cam_to_cam_file) { opt.rect.reset(); return ""; }
+    StereoRectification r;
+    Matd p1, p2;
+    if (!loadCalibCamToCam(cam_to_cam_file, r, p1, p2))
+        return std::string("viso_kitti_set_rectify: cannot read a KITTI raw calib_cam_to_cam file from ") + cam_to_cam_file;
+    opt.rect = r; P1 = p1; P2 = p2;
+    return "";
+}
+
+// the tail that set_disparity and set_sgm share: the directory, then the switch to the method of `who`
+static std::string write_maps_to(RunOptions& opt, const char* who, const char* dir, bool params_ok, bool sgm) {
+    if (!params_ok) return std::string(who) + ": parameters outside the ranges of include/viso_hip.h";
+    mkdirs(dir);
+    struct stat st;
+    if (::stat(dir, &st) != 0 || !S_ISDIR(st.st_mode)) return std::string(who) + ": cannot create " + dir;
+    opt.disparity.dir = dir; opt.disparity.write_first = true; opt.disparity.sgm = sgm; opt.disparity_on = true;
+    return "";
+}
+
+std::string set_disparity(RunOptions& opt, const char* dir, const viso_disparity_params* params) {
+    if (!dir || !*dir) { opt.disparity_on = false; return ""; }
+    viso_disparity_params p;
+    viso_disparity_params_default(&p);
+    if (params) p = *params;
+    const bool ok = p.num_disp >= 16 && p.num_disp <= 256 && p.num_disp % 16 == 0 && p.block >= 5 && p.block <= 21 && p.block % 2 == 1 &&
+                    p.prefilter_cap >= 1 && p.prefilter_cap <= 63 && p.texture_threshold >= 0 && p.uniqueness >= 0 &&
+                    p.uniqueness <= 100 && p.lr_max_diff >= -1 && p.lr_max_diff <= p.num_disp;
+    const std::string err = write_maps_to(opt, "viso_kitti_set_disparity", dir, ok, false);
+    if (err.empty()) opt.disparity.params = p;
+    return err;
+}
+
+std::string set_sgm(RunOptions& opt, const char* dir, const viso_sgm_params* params) {
+    if (!dir || !*dir) { opt.disparity_on = false; return ""; }
+    viso_sgm_params p;
+    viso_sgm_params_default(&p);
+    if (params) p = *params;
+    const bool ok = p.num_disp >= 16 && p.num_disp <= 256 && p.num_disp % 16 == 0 && p.p1 >= 1 && p.p1 <= p.p2 && p.p2 <= 192 &&
+                    (p.paths == 4 || p.paths == 8) && p.uniqueness >= 0 && p.uniqueness <= 100 && p.lr_max_diff >= -1 &&
+                    p.lr_max_diff <= p.num_disp;
+    const std::string err = write_maps_to(opt, "viso_kitti_set_sgm", dir, ok, true);
+    if (err.empty()) opt.disparity.sgm_params = p;
+    return err;
+}
+
+std::string set_speckle(RunOptions& opt, const viso_speckle_params* params) {
+    if (!params) { opt.disparity.speckle = false; return ""; }
+    if (params->max_size < 0 || params->max_diff < 0 || params->max_diff > 4096)
+        return "viso_kitti_set_speckle: parameters outside the ranges of include/viso_hip.h";
+    opt.disparity.speckle = true; opt.disparity.speckle_params = *params;
+    return "";
 }
 
 }  // namespace viso
 
 // ---- C entry points ---------------------------------------------------------------------------------------
 static thread_local std::string g_host_err;
-static thread_local viso::OdometryStats g_last_stats;
-static thread_local int g_decode_threads = 0;
-static thread_local int g_subpixel = 0;
-// viso_kitti_set_rectify: the calibration read from its calib_cam_to_cam.txt (g_rect_on), used in place of calib.txt
-static thread_local bool g_rect_on = false;
-static thread_local viso::StereoRectification g_rect;
+// what the viso_kitti_set_* calls of this thread have asked of its next viso_kitti_run_range calls, the rectified projections
+// of viso_kitti_set_rectify (used in place of calib.txt while g_opt.rect is set), and what the last range left behind
+static thread_local viso::RunOptions g_opt;
 static thread_local viso::Matd g_rect_P1, g_rect_P2;
-// viso_kitti_set_covariance, and the records of the last viso_kitti_run_range
-static thread_local int g_cov_mode = 0;
-static thread_local double g_cov_sigma = 0.0;
-static thread_local std::vector<viso_motion_cov> g_last_cov;
-// viso_kitti_set_disparity (g_disp_on)
-static thread_local bool g_disp_on = false;
-static thread_local viso::DisparityOutput g_disp;
+static thread_local viso::RangeResult g_last;
+
+static int report(const std::string& err) {
+    if (err.empty()) return VISO_OK;
+    g_host_err = err;
+    return VISO_ERR_ARG;
+}
 
 extern "C" const char* viso_host_last_error(void) { return g_host_err.c_str(); }
 namespace viso { void set_host_error(const std::string& s) { g_host_err = s; } }   // for the other C entry points (drop_in.cpp)
@@ -229,19 +226,15 @@ extern "C" int viso_kitti_run_range(const char* seq_base, int begin, int first, 
     }
     *n_done = 0;
     try {
-        viso::Matd P1, P2;
-        if (g_rect_on) {
-            P1 = g_rect_P1; P2 = g_rect_P2;
-        } else if (!viso::loadCalib(std::string(seq_base) + "/calib.txt", P1, P2)) {
+        viso::Matd P1 = g_rect_P1, P2 = g_rect_P2;
+        if (!g_opt.rect && !viso::loadCalib(std::string(seq_base) + "/calib.txt", P1, P2)) {
             g_host_err = std::string("cannot read ") + seq_base + "/calib.txt";
             return VISO_ERR_ARG;
         }
-        g_last_stats = viso::OdometryStats();
-        g_last_cov.clear();
-        std::vector<viso::FrameRecord> rec = viso::kitti_run_range(seq_base, P1, P2, begin, first, last, device, chunk, ransac_seed,
-                                                                   g_decode_threads, &g_last_stats, g_subpixel,
-                                                                   g_rect_on ? &g_rect : nullptr, g_cov_mode, g_cov_sigma,
-                                                                   g_cov_mode ? &g_last_cov : nullptr, g_disp_on ? &g_disp : nullptr);
+        g_last = viso::RangeResult();
+        g_opt.device = device; g_opt.chunk = chunk; g_opt.ransac_seed = ransac_seed;
+        g_last = viso::kitti_run_range(seq_base, P1, P2, begin, first, last, g_opt);
+        const std::vector<viso::FrameRecord>& rec = g_last.rec;
         for (size_t i = 0; i < rec.size(); ++i) {
             for (int j = 0; j < 6; ++j) rec8[i * 8 + (size_t)j] = rec[i].tr[j];
             rec8[i * 8 + 6] = rec[i].ok;
@@ -256,44 +249,37 @@ extern "C" int viso_kitti_run_range(const char* seq_base, int begin, int first, 
 }
 
 extern "C" void viso_kitti_last_stats(double out[9]) {
-    const viso::OdometryStats& s = g_last_stats;
+    const viso::OdometryStats& s = g_last.stats;
     const double v[9] = {(double)s.frames, (double)s.decode_threads, s.wall_s, s.decode_wait_s, s.decode_cpu_s, s.issue_s,
                          s.drain_wait_s, s.upload_ms, s.gpu_ms};
     for (int i = 0; i < 9; ++i) out[i] = v[i];
 }
 
-extern "C" void viso_kitti_set_decode_threads(int n) { g_decode_threads = n > 0 ? n : 0; }
-
-extern "C" int viso_kitti_set_subpixel(int mode) {
-    if (mode < 0 || mode > 2) { g_host_err = "viso_kitti_set_subpixel: mode must be 0, 1 or 2"; return VISO_ERR_ARG; }
-    g_subpixel = mode;
-    return VISO_OK;
+extern "C" void viso_kitti_set_decode_threads(int n) { g_opt.decode_threads = n > 0 ? n : 0; }
+extern "C" int viso_kitti_set_subpixel(int mode) { return report(viso::set_subpixel(g_opt, mode)); }
+extern "C" int viso_kitti_set_covariance(int mode, double sigma_px) { return report(viso::set_covariance(g_opt, mode, sigma_px)); }
+extern "C" int viso_kitti_set_rectify(const char* cam_to_cam_file) {
+    return report(viso::set_rectify(g_opt, g_rect_P1, g_rect_P2, cam_to_cam_file));
 }
-
-extern "C" int viso_kitti_set_covariance(int mode, double sigma_px) {
-    if (mode != 0 && mode != 1 && !(mode == 2 && std::isfinite(sigma_px) && sigma_px > 0.0)) {
-        g_host_err = "viso_kitti_set_covariance: mode 0, 1, or 2 with a finite sigma_px > 0";
-        return VISO_ERR_ARG;
-    }
-    g_cov_mode = mode;
-    g_cov_sigma = mode == 2 ? sigma_px : 0.0;
-    return VISO_OK;
+extern "C" int viso_kitti_set_disparity(const char* dir, const viso_disparity_params* params) {
+    return report(viso::set_disparity(g_opt, dir, params));
 }
+extern "C" int viso_kitti_set_sgm(const char* dir, const viso_sgm_params* params) { return report(viso::set_sgm(g_opt, dir, params)); }
+extern "C" int viso_kitti_set_speckle(const viso_speckle_params* params) { return report(viso::set_speckle(g_opt, params)); }
 
 extern "C" int viso_kitti_last_covariances(viso_motion_cov* out, int cap, int* n) {
     if (!n || cap < 0 || (cap > 0 && !out)) { g_host_err = "viso_kitti_last_covariances: bad argument"; return VISO_ERR_ARG; }
-    const size_t k = g_last_cov.size() < (size_t)cap ? g_last_cov.size() : (size_t)cap;
-    if (k) std::memcpy(out, g_last_cov.data(), sizeof(viso_motion_cov) * k);
-    *n = (int)g_last_cov.size();
+    const std::vector<viso_motion_cov>& cov = g_last.cov;
+    const size_t k = cov.size() < (size_t)cap ? cov.size() : (size_t)cap;
+    if (k) std::memcpy(out, cov.data(), sizeof(viso_motion_cov) * k);
+    *n = (int)cov.size();
     return VISO_OK;
 }
 
 extern "C" int viso_kitti_write_covariances(const char* file_name, const viso_motion_cov* rec, int n) {
     if (!file_name || n < 0 || (n > 0 && !rec)) { g_host_err = "viso_kitti_write_covariances: bad argument"; return VISO_ERR_ARG; }
-    const std::string f(file_name);
-    const size_t slash = f.rfind('/');
-    if (slash != std::string::npos && slash > 0) viso::mkdirs(f.substr(0, slash));
-    if (!viso::write_covariance_file(f, rec, (size_t)n)) { g_host_err = "cannot write " + f; return VISO_ERR_ARG; }
+    viso::mkdirs_for(file_name);
+    if (!viso::write_covariance_file(file_name, rec, (size_t)n)) { g_host_err = std::string("cannot write ") + file_name; return VISO_ERR_ARG; }
     return VISO_OK;
 }
 
@@ -312,60 +298,6 @@ extern "C" int viso_kitti_load_cam_to_cam(const char* file_name, double K[18], d
         for (int i = 0; i < 12; ++i) P[12 * c + i] = r.P[c].data[(size_t)i];
     }
     geometry[0] = r.raw_rows; geometry[1] = r.raw_cols; geometry[2] = r.out_rows; geometry[3] = r.out_cols;
-    return VISO_OK;
-}
-
-extern "C" int viso_kitti_set_rectify(const char* cam_to_cam_file) {
-    if (!cam_to_cam_file || !*cam_to_cam_file) { g_rect_on = false; return VISO_OK; }
-    viso::StereoRectification r;
-    viso::Matd P1, P2;
-    if (!viso::loadCalibCamToCam(cam_to_cam_file, r, P1, P2)) {
-        g_host_err = std::string("viso_kitti_set_rectify: cannot read a KITTI raw calib_cam_to_cam file from ") + cam_to_cam_file;
-        return VISO_ERR_ARG;
-    }
-    g_rect = r; g_rect_P1 = P1; g_rect_P2 = P2; g_rect_on = true;
-    return VISO_OK;
-}
-
-extern "C" int viso_kitti_set_disparity(const char* dir, const viso_disparity_params* params) {
-    if (!dir || !*dir) { g_disp_on = false; return VISO_OK; }
-    viso_disparity_params p;
-    viso_disparity_params_default(&p);
-    if (params) p = *params;
-    const bool ok = p.num_disp >= 16 && p.num_disp <= 256 && p.num_disp % 16 == 0 && p.block >= 5 && p.block <= 21 && p.block % 2 == 1 &&
-                    p.prefilter_cap >= 1 && p.prefilter_cap <= 63 && p.texture_threshold >= 0 && p.uniqueness >= 0 &&
-                    p.uniqueness <= 100 && p.lr_max_diff >= -1 && p.lr_max_diff <= p.num_disp;
-    if (!ok) { g_host_err = "viso_kitti_set_disparity: parameters outside the ranges of include/viso_hip.h"; return VISO_ERR_ARG; }
-    viso::mkdirs(dir);
-    struct stat st;
-    if (::stat(dir, &st) != 0 || !S_ISDIR(st.st_mode)) { g_host_err = std::string("viso_kitti_set_disparity: cannot create ") + dir; return VISO_ERR_ARG; }
-    g_disp.dir = dir; g_disp.params = p; g_disp.write_first = true; g_disp.sgm = false; g_disp_on = true;
-    return VISO_OK;
-}
-
-extern "C" int viso_kitti_set_sgm(const char* dir, const viso_sgm_params* params) {
-    if (!dir || !*dir) { g_disp_on = false; return VISO_OK; }
-    viso_sgm_params p;
-    viso_sgm_params_default(&p);
-    if (params) p = *params;
-    const bool ok = p.num_disp >= 16 && p.num_disp <= 256 && p.num_disp % 16 == 0 && p.p1 >= 1 && p.p1 <= p.p2 && p.p2 <= 192 &&
-                    (p.paths == 4 || p.paths == 8) && p.uniqueness >= 0 && p.uniqueness <= 100 && p.lr_max_diff >= -1 &&
-                    p.lr_max_diff <= p.num_disp;
-    if (!ok) { g_host_err = "viso_kitti_set_sgm: parameters outside the ranges of include/viso_hip.h"; return VISO_ERR_ARG; }
-    viso::mkdirs(dir);
-    struct stat st;
-    if (::stat(dir, &st) != 0 || !S_ISDIR(st.st_mode)) { g_host_err = std::string("viso_kitti_set_sgm: cannot create ") + dir; return VISO_ERR_ARG; }
-    g_disp.dir = dir; g_disp.sgm_params = p; g_disp.write_first = true; g_disp.sgm = true; g_disp_on = true;
-    return VISO_OK;
-}
-
-extern "C" int viso_kitti_set_speckle(const viso_speckle_params* params) {
-    if (!params) { g_disp.speckle = false; return VISO_OK; }
-    if (params->max_size < 0 || params->max_diff < 0 || params->max_diff > 4096) {
-        g_host_err = "viso_kitti_set_speckle: parameters outside the ranges of include/viso_hip.h";
-        return VISO_ERR_ARG;
-    }
-    g_disp.speckle = true; g_disp.speckle_params = *params;
     return VISO_OK;
 }
 
@@ -441,11 +373,10 @@ extern "C" int viso_write_disparity_png(const char* path, const int16_t* d16, in
     put_chunk(png, "IHDR", ihdr);
     put_chunk(png, "IDAT", z);
     put_chunk(png, "IEND", {});
-    const std::string f = path, tmp = f + ".tmp";
-    FILE* fp = std::fopen(tmp.c_str(), "wb");
-    bool ok = fp && std::fwrite(png.data(), 1, png.size(), fp) == png.size();
-    if (fp) ok = std::fclose(fp) == 0 && ok;
-    if (!ok || std::rename(tmp.c_str(), f.c_str()) != 0) { g_host_err = "viso_write_disparity_png: cannot write " + f; return VISO_ERR_ARG; }
+    if (!viso::write_atomically(path, "wb", [&](FILE* fp) { return std::fwrite(png.data(), 1, png.size(), fp) == png.size(); })) {
+        g_host_err = std::string("viso_write_disparity_png: cannot write ") + path;
+        return VISO_ERR_ARG;
+    }
     return VISO_OK;
 }
 
@@ -463,10 +394,8 @@ extern "C" int viso_kitti_write_poses2(const char* file_name, const double* rec8
         rec[(size_t)i].frame = rec[(size_t)i].reserved = 0;
     }
     std::vector<viso::Matd> poses = viso::chain_records(rec.data(), n, reference_pose_list != 0);
-    const std::string f = file_name;
-    const size_t slash = f.rfind('/');
-    if (slash != std::string::npos && slash > 0) viso::mkdirs(f.substr(0, slash));
-    if (!viso::savePoses(f, poses)) { g_host_err = "cannot write " + f; return VISO_ERR_ARG; }
+    viso::mkdirs_for(file_name);
+    if (!viso::savePoses(file_name, poses)) { g_host_err = std::string("cannot write ") + file_name; return VISO_ERR_ARG; }
     if (n_poses) *n_poses = (int)poses.size();
     return VISO_OK;
 }

@@ -13,6 +13,8 @@
 // Any W gives the byte-identical pose file (tests/test_gpu_kitti_shard.py).
 #pragma once
 #include <cstdint>
+#include <cstdio>
+#include <functional>
 #include <string>
 #include <utility>
 #include <vector>
@@ -40,29 +42,35 @@ std::string kitti_image_ext(const std::string& seq_base, int begin);
 // number of consecutive frames begin, begin+1, ... <= end for which both image files can be opened
 int kitti_count_frames(const std::string& seq_base, int begin, int end);
 
-// Frames [begin + first, begin + last] of the sequence through the device pipeline (device ordinal `device`):
-// rec[i] = record of the pair ending at frame first + 1 + i.  Fewer than last - first records come back when an
-// image in the range cannot be decoded (the reference's generator stops there, src/viso.h:94-96).
-// stats (may be null): where the range's wall time went (decode / upload / GPU), see OdometryStats.
-// subpixel: the opt-in sub-pixel stereo refinement of sequence_odometry (0 = off, the reference's arithmetic).
-// rect: the opt-in rectification of raw images of sequence_odometry (null = the images are rectified already).
-std::vector<FrameRecord> kitti_run_range(const std::string& seq_base, const Matd& P1, const Matd& P2, int begin,
-                                         int first, int last, int device, int chunk = 64, uint64_t ransac_seed = 0,
-                                         int decode_threads = 0, OdometryStats* stats = nullptr, int subpixel = 0,
-                                         const StereoRectification* rect = nullptr, int cov_mode = 0, double cov_sigma = 0.0,
-                                         std::vector<viso_motion_cov>* cov = nullptr, const DisparityOutput* disp = nullptr);
-// cov_mode / cov_sigma / cov: the opt-in motion covariance of sequence_odometry; *cov gets one record per FrameRecord.
-// disp: the opt-in dense disparity maps of sequence_odometry, one PNG per frame first + 1 .. last (and frame first too when
-// first == 0): a range's halo frame is written by the range that owns it.
+// What a range leaves behind
+struct RangeResult {
+    std::vector<FrameRecord> rec;       // rec[i] = record of the pair ending at frame first + 1 + i
+    std::vector<viso_motion_cov> cov;   // one per record exactly when opt.cov_mode != 0
+    OdometryStats stats;                // where the range's wall time went (decode / upload / GPU)
+};
+// Frames [begin + first, begin + last] of the sequence through sequence_odometry with `opt`, of which this function sets
+// first_frame_index = begin + first and disparity.write_first = (first == 0) itself: maps are written for the frames first + 1 ..
+// last, and for frame `first` only by the range that owns it (a later range's first frame is the previous range's last).  Fewer
+// than last - first records come back when an image in the range cannot be decoded (the reference's generator stops there,
+// src/viso.h:94-96).
+RangeResult kitti_run_range(const std::string& seq_base, const Matd& P1, const Matd& P2, int begin, int first, int last,
+                            const RunOptions& opt);
+
+// The runners' option checks, one per option, shared by the C setters below and by viso_kitti.  Each stores a valid value in
+// `opt` and returns "", or leaves `opt` as it was and returns the error text, which names the C setter.  A null or "" file or
+// directory switches that option off; the last of set_disparity / set_sgm decides the method; set_speckle (null = off) sticks
+// across both and does nothing while no maps are written.  set_disparity / set_sgm create the directory.  set_rectify also
+// gives the rectified projections that replace the sequence's calib.txt.
+std::string set_subpixel(RunOptions& opt, int mode);
+std::string set_covariance(RunOptions& opt, int mode, double sigma_px);
+std::string set_rectify(RunOptions& opt, Matd& P1, Matd& P2, const char* cam_to_cam_file);
+std::string set_disparity(RunOptions& opt, const char* dir, const viso_disparity_params* params);
+std::string set_sgm(RunOptions& opt, const char* dir, const viso_sgm_params* params);
+std::string set_speckle(RunOptions& opt, const viso_speckle_params* params);
 
 // The covariance file of the runners' --covariance option: one line per frame pair, "status n sigma2 gap" and the 21
 // upper-triangle entries of cov (row by row), every value %.17g.  Written under a temporary name and renamed.
 bool write_covariance_file(const std::string& file_name, const viso_motion_cov* rec, size_t n);
-// rank files of the covariance records (binary, next to the FrameRecord rank files), and the stitch of their parts
-bool write_cov_records(const std::string& file_name, int first, int last, const std::vector<viso_motion_cov>& rec);
-bool read_cov_records(const std::string& file_name, int& first, int& last, std::vector<viso_motion_cov>& rec);
-std::vector<viso_motion_cov> stitch_cov_records(const std::vector<std::vector<viso_motion_cov>>& parts,
-                                                const std::vector<std::pair<int, int>>& ranges);
 
 // poses[0] = I, then pose <- pose * inv(tr2mat(tr)) per solved record (src/viso.cpp:1189-1190, 1315-1321): the list
 // [I, P1, ..., Pn] the reference's code reads as.
@@ -73,14 +81,53 @@ std::vector<viso_motion_cov> stitch_cov_records(const std::vector<std::vector<vi
 // pose twice, the same number of lines.
 std::vector<Matd> chain_records(const FrameRecord* rec, int n, bool reference_pose_list = false);
 
-// rank files of `viso_kitti --rank r --world W`: header {magic, first, last, n_done} + n_done records
-bool write_records(const std::string& file_name, int first, int last, const std::vector<FrameRecord>& rec);
-bool read_records(const std::string& file_name, int& first, int& last, std::vector<FrameRecord>& rec);
-// Records of all ranks in rank order -> one list; stops at the first rank that came back short (see above).
-std::vector<FrameRecord> stitch_records(const std::vector<std::vector<FrameRecord>>& parts,
-                                        const std::vector<std::pair<int, int>>& ranges);
-
 void mkdirs(const std::string& path);
+// mkdirs of the directory file_name lies in
+void mkdirs_for(const std::string& file_name);
+// `write` fills file_name + ".tmp" (opened with `mode`), which is then renamed: a reader never sees a partial file
+bool write_atomically(const std::string& file_name, const char* mode, const std::function<bool(FILE*)>& write);
+
+// rank files of `viso_kitti --rank r --world W`: header {magic, first, last, n_done} + n_done records, of FrameRecord and,
+// next to them, of the covariance records
+template <class R> inline constexpr int32_t RECORD_MAGIC = 0;
+template <> inline constexpr int32_t RECORD_MAGIC<FrameRecord> = 0x56534B52;       // "VSKR"
+template <> inline constexpr int32_t RECORD_MAGIC<viso_motion_cov> = 0x56534B43;   // "VSKC"
+
+template <class R>
+bool write_records(const std::string& file_name, int first, int last, const std::vector<R>& rec) {
+    return write_atomically(file_name, "wb", [&](FILE* fp) {
+        const int32_t hdr[4] = {RECORD_MAGIC<R>, first, last, (int32_t)rec.size()};
+        return std::fwrite(hdr, sizeof hdr, 1, fp) == 1 && (rec.empty() || std::fwrite(rec.data(), sizeof(R), rec.size(), fp) == rec.size());
+    });
+}
+
+template <class R>
+bool read_records(const std::string& file_name, int& first, int& last, std::vector<R>& rec) {
+    FILE* fp = std::fopen(file_name.c_str(), "rb");
+    if (!fp) return false;
+    int32_t hdr[4];
+    bool ok = std::fread(hdr, sizeof hdr, 1, fp) == 1 && hdr[0] == RECORD_MAGIC<R> && hdr[3] >= 0 && hdr[2] >= hdr[1] &&
+              hdr[3] <= hdr[2] - hdr[1];
+    if (ok) {
+        first = hdr[1]; last = hdr[2];
+        rec.resize((size_t)hdr[3]);
+        if (hdr[3]) ok = std::fread(rec.data(), sizeof(R), rec.size(), fp) == rec.size();
+    }
+    std::fclose(fp);
+    return ok;
+}
+
+// Records of all ranks in rank order -> one list; stops at the first rank that came back short (see above): the sequence
+// ends there for one process too.
+template <class R>
+std::vector<R> stitch_records(const std::vector<std::vector<R>>& parts, const std::vector<std::pair<int, int>>& ranges) {
+    std::vector<R> all;
+    for (size_t r = 0; r < parts.size() && r < ranges.size(); ++r) {
+        all.insert(all.end(), parts[r].begin(), parts[r].end());
+        if ((int)parts[r].size() < ranges[r].second - ranges[r].first) break;
+    }
+    return all;
+}
 
 }  // namespace viso
 

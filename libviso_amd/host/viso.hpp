@@ -276,26 +276,38 @@ struct DisparityOutput {
     viso_speckle_params speckle_params{};
 };
 
+// What an image-driven run can be asked for beyond the reference's flow.  Every opt-in below is NOT in the reference; a chunk's
+// halo frame goes through each of them again like any other frame, so every chunking and partition gives byte-identical records.
+struct RunOptions {
+    int chunk = 64;                   // frames per device batch (one-frame halo between batches)
+    // The RANSAC stream of frame t is keyed on (ransac_seed, first_frame_index + t), first_frame_index being the index of the
+    // generator's first frame in the whole sequence: a sub-range gives the records of the full run (kitti_shard.hpp).
+    uint64_t ransac_seed = 0;
+    uint64_t first_frame_index = 0;
+    int device = 0;                   // HIP device ordinal
+    // Worker threads that decode a chunk's images while the GPU works on the previous chunk (0 = $VISO_DECODE_THREADS, else
+    // min(64, usable host threads)).
+    int decode_threads = 0;
+    // Sub-pixel refinement of the stereo observations (viso_batch_set_subpixel): 0 = off, 1 = uR, 2 = uR and vR.  Such poses are
+    // not comparable with the reference's output.
+    int subpixel = 0;
+    // Motion covariance (viso_batch_set_covariance): 0 = off, 1 = sigma^2 estimated, 2 = sigma = cov_sigma pixels; fills
+    // OdometryResult::cov with one viso_motion_cov per frame.
+    int cov_mode = 0;
+    double cov_sigma = 0;
+    // Set: the images are RAW, raw_rows x raw_cols, and each batch rectifies them on the device to out_rows x out_cols
+    // (viso_batch_set_rectify) before detection; P1 / P2 are then the rectified projections (P_rect).
+    std::optional<StereoRectification> rect;
+    // disparity_on: the dense disparity maps of `disparity`, written as each chunk drains; the poses are unchanged by it.  A flag
+    // and not an optional: what was chosen while the maps are off (the speckle filter of the C setters) is kept for when they go on.
+    bool disparity_on = false;
+    DisparityOutput disparity;
+};
+
 // sequence_odometry(P1, P2, images, dbg_dir), src/viso.h:138-139 / src/viso.cpp:1167-1330, without the
 // debug dumps: detection (MAX_FEATURE_NUM 1200, radius 5, :1171-1174), description, matching and the
-// solver all run on the device, `chunk` frames per batch.
-// decode_threads: worker threads that decode a chunk's images while the GPU works on the previous chunk
-// (0 = $VISO_DECODE_THREADS, else min(16, hardware threads)).  The frames are consumed in order and the sequence ends
+// solver all run on the device, opt.chunk frames per batch.  The frames are consumed in order and the sequence ends
 // at the first pair that cannot be decoded, exactly like the reference's generator (src/viso.h:94-96).
-// subpixel: the opt-in sub-pixel refinement of the stereo observations (viso_batch_set_subpixel; NOT in the reference, poses
-// not comparable with its output): 0 = off, 1 = uR, 2 = uR and vR.  A chunk's halo frame is refined again like any other
-// frame, so every chunking and partition gives the same records.
-// rect (may be null): the images are RAW, rect->raw_rows x raw_cols, and each batch rectifies them on the device to
-// rect->out_rows x out_cols (viso_batch_set_rectify) before detection; P1 / P2 are the rectified projections (P_rect).  A chunk's
-// halo frame is rectified again like any other frame.
-// cov_mode (opt-in, viso_batch_set_covariance; NOT in the reference): 1 = sigma^2 estimated, 2 = sigma = cov_sigma pixels; fills
-// OdometryResult::cov with one viso_motion_cov per frame.  A chunk's halo frame is recomputed like any other frame, so every
-// chunking and partition gives byte-identical records.
-// disp (may be null): the opt-in dense disparity maps, written as each chunk drains; the poses are unchanged by it.
-OdometryResult sequence_odometry(const Matd& P1, const Matd& P2, StereoImageGenerator& images,
-                                 int chunk = 64, uint64_t ransac_seed = 0, uint64_t first_frame_index = 0,
-                                 int device = 0, int decode_threads = 0, int subpixel = 0,
-                                 const StereoRectification* rect = nullptr, int cov_mode = 0, double cov_sigma = 0.0,
-                                 const DisparityOutput* disp = nullptr);
+OdometryResult sequence_odometry(const Matd& P1, const Matd& P2, StereoImageGenerator& images, const RunOptions& opt = {});
 
 }  // namespace viso

@@ -401,21 +401,29 @@ struct ChunkPipeline {
         if (slot[next ^ 1].busy) drain(slot[next ^ 1]);
     }
 };
+
+// What both sequence_odometry overloads do before their first frame (src/viso.cpp:1176-1190)
+struct SequenceSetup {
+    viso_match_params st, tm;
+    viso_param vp;
+    OdometryResult out;
+};
+SequenceSetup sequence_setup(const Matd& P1, const Matd& P2) {
+    if (P1.rows != 3 || P1.cols != 4 || P2.rows != 3 || P2.cols != 4) throw std::invalid_argument("sequence_odometry: P1,P2 must be 3x4");
+    param prm;
+    prm.base = std::fabs(P2.at(0, 3) / P2.at(0, 0));                  // :1184
+    prm.calib.f = P1.at(0, 0); prm.calib.cu = P1.at(0, 2); prm.calib.cv = P1.at(1, 2);   // :1185-1187
+    SequenceSetup s{to_abi(MatchParams(F_from_P(P1, P2))), to_abi(MatchParams()), to_abi(prm), {}};   // F: :1176-1180
+    s.out.poses.push_back(Matd::eye(4));                              // :1189-1190
+    s.out.frame_of_pose.push_back(0);
+    return s;
+}
 }
 
 OdometryResult sequence_odometry(const Matd& P1, const Matd& P2, StereoFeatureGenerator frames, int chunk,
                                  uint64_t ransac_seed, uint64_t first_frame_index, int device) {
-    if (P1.rows != 3 || P1.cols != 4 || P2.rows != 3 || P2.cols != 4) throw std::invalid_argument("sequence_odometry: P1,P2 must be 3x4");
+    auto [st, tm, vp, out] = sequence_setup(P1, P2);
     if (chunk < 1) chunk = 1;
-    Matd F = F_from_P(P1, P2);                                        // :1176-1180
-    param prm;
-    prm.base = std::fabs(P2.at(0, 3) / P2.at(0, 0));                  // :1184
-    prm.calib.f = P1.at(0, 0); prm.calib.cu = P1.at(0, 2); prm.calib.cv = P1.at(1, 2);   // :1185-1187
-    viso_match_params st = to_abi(MatchParams(F)), tm = to_abi(MatchParams());
-    viso_param vp = to_abi(prm);
-    OdometryResult out;
-    out.poses.push_back(Matd::eye(4));                                // :1189-1190
-    out.frame_of_pose.push_back(0);
     ChunkPipeline pipe(out, device);
     std::vector<StereoFeatures> buf;                                  // frames of the current chunk (buf[0] = halo)
     int global0 = 0;                                                  // global index of buf[0]
@@ -460,7 +468,7 @@ OdometryResult sequence_odometry(const Matd& P1, const Matd& P2, StereoFeatureGe
         global0 += nf - 1;
     }
     pipe.finish();
-    return out;
+    return std::move(out);
 }
 
 // ---- the literal per-call loop (see viso.hpp) -------------------------------
@@ -750,26 +758,17 @@ int cpu_budget() {
 // Chunks of `chunk` frames (plus the one-frame halo), two in flight: while the GPU runs chunk c (its own context,
 // asynchronous uploads from the slot's pinned buffer), the worker threads decode chunk c + 1 straight into the other
 // slot's pinned buffer.  The halo frame is copied from the previous slot's buffer, not decoded twice.
-OdometryResult sequence_odometry(const Matd& P1, const Matd& P2, StereoImageGenerator& images, int chunk,
-                                 uint64_t ransac_seed, uint64_t first_frame_index, int device, int decode_threads, int subpixel,
-                                 const StereoRectification* rect, int cov_mode, double cov_sigma, const DisparityOutput* disp) {
+OdometryResult sequence_odometry(const Matd& P1, const Matd& P2, StereoImageGenerator& images, const RunOptions& opt) {
     using clock = std::chrono::steady_clock;
     auto since = [](clock::time_point t0) { return std::chrono::duration<double>(clock::now() - t0).count(); };
     const auto t_start = clock::now();
-    if (P1.rows != 3 || P1.cols != 4 || P2.rows != 3 || P2.cols != 4) throw std::invalid_argument("sequence_odometry: P1,P2 must be 3x4");
-    if (chunk < 1) chunk = 1;
+    auto [st, tm, vp, out] = sequence_setup(P1, P2);
+    const int chunk = std::max(1, opt.chunk);
+    const StereoRectification* rect = opt.rect ? &*opt.rect : nullptr;
+    const DisparityOutput* disp = opt.disparity_on ? &opt.disparity : nullptr;
     const int MAX_FEATURE_NUM = 1200;                                   // :1171
     HarrisBinnedFeatureDetector detector(5, MAX_FEATURE_NUM);           // :1172
-    Matd F = F_from_P(P1, P2);
-    param prm;
-    prm.base = std::fabs(P2.at(0, 3) / P2.at(0, 0));
-    prm.calib.f = P1.at(0, 0); prm.calib.cu = P1.at(0, 2); prm.calib.cv = P1.at(1, 2);
-    viso_match_params st = to_abi(MatchParams(F)), tm = to_abi(MatchParams());
-    viso_param vp = to_abi(prm);
-    OdometryResult out;
-    out.poses.push_back(Matd::eye(4));
-    out.frame_of_pose.push_back(0);
-    if (images.index() > images.end()) return out;
+    if (images.index() > images.end()) return std::move(out);
     // the first frame fixes the geometry of the sequence
     Image first_l, first_r;
     {
@@ -777,7 +776,7 @@ OdometryResult sequence_odometry(const Matd& P1, const Matd& P2, StereoImageGene
         const bool ok = images.read(images.index(), first_l, first_r);
         out.stats.decode_wait_s += since(t0);
         out.stats.decode_cpu_s += since(t0);
-        if (!ok) { images.seek(images.index() + 1); return out; }      // the generator stops at an unreadable pair (src/viso.h:94-96)
+        if (!ok) { images.seek(images.index() + 1); return std::move(out); }      // the generator stops at an unreadable pair (src/viso.h:94-96)
     }
     const int rows = first_l.rows, cols = first_l.cols;
     if (first_r.rows != rows || first_r.cols != cols) throw std::invalid_argument("sequence_odometry: image size changes inside a sequence");
@@ -801,10 +800,10 @@ OdometryResult sequence_odometry(const Matd& P1, const Matd& P2, StereoImageGene
     const size_t per = (size_t)rows * cols;
     const int first_index = images.index();
     images.seek(first_index + 1);
-    DecodePool pool(decode_threads > 0 ? decode_threads : default_decode_threads());
+    DecodePool pool(opt.decode_threads > 0 ? opt.decode_threads : default_decode_threads());
     out.stats.decode_threads = pool.size();
-    ChunkPipeline pipe(out, device);
-    pipe.cov_mode = cov_mode;
+    ChunkPipeline pipe(out, opt.device);
+    pipe.cov_mode = opt.cov_mode;
     pipe.disp = disp;
     pipe.first_index = first_index;
     int global0 = 0;                 // frame (relative to first_index) of the current chunk's halo
@@ -864,9 +863,9 @@ OdometryResult sequence_odometry(const Matd& P1, const Matd& P2, StereoImageGene
             s.rectify = r >= 0;
         }
         if (r >= 0) r = viso_batch_upload_images(b, 0, 0, nullptr, rows, cols, nullptr, nullptr);   // device buffers for this geometry
-        if (r >= 0) r = viso_batch_set_params(b, &st, &tm, &vp, ransac_seed, first_frame_index + (uint64_t)global0);
-        if (r >= 0) r = viso_batch_set_subpixel(b, subpixel);
-        if (r >= 0 && cov_mode) r = viso_batch_set_covariance(b, cov_mode, cov_sigma);
+        if (r >= 0) r = viso_batch_set_params(b, &st, &tm, &vp, opt.ransac_seed, opt.first_frame_index + (uint64_t)global0);
+        if (r >= 0) r = viso_batch_set_subpixel(b, opt.subpixel);
+        if (r >= 0 && opt.cov_mode) r = viso_batch_set_covariance(b, opt.cov_mode, opt.cov_sigma);
         if (r >= 0 && disp && disp->sgm) {   // one method at a time: the other one off first
             r = viso_batch_set_disparity(b, nullptr);
             if (r >= 0) r = viso_batch_set_sgm(b, &disp->sgm_params);
@@ -891,7 +890,7 @@ OdometryResult sequence_odometry(const Matd& P1, const Matd& P2, StereoImageGene
     out.stats.frames = frames_read;
     out.stats.decode_cpu_s += pool.busy_seconds();
     out.stats.wall_s = since(t_start);
-    return out;
+    return std::move(out);
 }
 
 }  // namespace viso

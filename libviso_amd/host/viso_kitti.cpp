@@ -62,105 +62,98 @@
 
 namespace {
 struct Args {
+    // --chunk, --seed, --decode-threads, --subpixel and the covariance mode are final after parse(); the lists of
+    // --disparity-params, --sgm-params and --speckle wait in opt.disparity for main's checks (viso::set_disparity and friends)
+    viso::RunOptions opt;
     const char* result_sha = nullptr;
     std::string seq_name;
     int begin = 0, end = INT_MAX;
-    int gpus = 0, rank = -1, world = 0, gather = 0, device = -1, chunk = 64, decode_threads = 0, subpixel = 0;
+    int gpus = 0, rank = -1, world = 0, gather = 0, device = -1;
     bool same_device = false, reference_pose_list = false;
-    unsigned long long seed = 0;
-    std::string rectify;   // calib_cam_to_cam.txt of --rectify ("" = off)
+    std::string rectify;      // calib_cam_to_cam.txt of --rectify ("" = off)
     std::string covariance;   // --covariance file ("" = off)
-    double cov_sigma = 0.0;   // --covariance-sigma (0: mode 1)
     std::string disparity;    // --disparity dir ("" = off)
-    bool disp_params_given = false;
-    viso_disparity_params disp{};   // --disparity-params (defaults otherwise)
-    bool method_given = false, sgm = false;   // --disparity-method
-    bool sgm_params_given = false;
-    viso_sgm_params sgmp{};         // --sgm-params (defaults otherwise)
-    bool speckle = false;
-    viso_speckle_params spk{};      // --speckle SIZE,DIFF
+    bool sigma_given = false, disp_params_given = false, method_given = false, sgm = false, sgm_params_given = false, speckle_given = false;
 };
+
+// an option's list: exactly N integers with commas between them and nothing behind; fmt ends in the %c that must not match
+template <class... Int>
+bool int_list(const char* s, const char* fmt, Int*... dst) {
+    char tail = 0;
+    return s && std::sscanf(s, fmt, dst..., &tail) == (int)sizeof...(dst);
+}
 
 bool parse(int argc, char** argv, Args& a) {
     int pos = 0;
+    viso::DisparityOutput& d = a.opt.disparity;
     for (int i = 1; i < argc; ++i) {
         const std::string s = argv[i];
-        auto val = [&](int& dst) { if (i + 1 >= argc) return false; dst = std::atoi(argv[++i]); return true; };
-        if (s == "--gpus") { if (!val(a.gpus)) return false; }
-        else if (s == "--rank") { if (!val(a.rank)) return false; }
-        else if (s == "--world") { if (!val(a.world)) return false; }
-        else if (s == "--gather") { if (!val(a.gather)) return false; }
-        else if (s == "--device") { if (!val(a.device)) return false; }
-        else if (s == "--chunk") { if (!val(a.chunk)) return false; }
-        else if (s == "--decode-threads") { if (!val(a.decode_threads)) return false; }
-        else if (s == "--subpixel") { if (!val(a.subpixel) || a.subpixel < 0 || a.subpixel > 2) return false; }
+        auto value = [&]() -> const char* { return i + 1 < argc ? argv[++i] : nullptr; };   // the option needs one
+        auto integer = [&](int& dst) { const char* v = value(); if (v) dst = std::atoi(v); return v != nullptr; };
+        auto text = [&](std::string& dst) { const char* v = value(); if (v) dst = v; return v && *v; };   // not ""
+        bool ok = true;
+        if (s == "--gpus") ok = integer(a.gpus);
+        else if (s == "--rank") ok = integer(a.rank);
+        else if (s == "--world") ok = integer(a.world);
+        else if (s == "--gather") ok = integer(a.gather);
+        else if (s == "--device") ok = integer(a.device);
+        else if (s == "--chunk") ok = integer(a.opt.chunk);
+        else if (s == "--decode-threads") ok = integer(a.opt.decode_threads);
+        else if (s == "--subpixel") { int m = 0; ok = integer(m) && viso::set_subpixel(a.opt, m).empty(); }
         else if (s == "--reference-pose-list") a.reference_pose_list = true;
-        else if (s == "--rectify") { if (i + 1 >= argc || !*argv[i + 1]) return false; a.rectify = argv[++i]; }
-        else if (s == "--covariance") { if (i + 1 >= argc || !*argv[i + 1]) return false; a.covariance = argv[++i]; }
-        else if (s == "--disparity") { if (i + 1 >= argc || !*argv[i + 1]) return false; a.disparity = argv[++i]; }
+        else if (s == "--rectify") ok = text(a.rectify);
+        else if (s == "--covariance") ok = text(a.covariance);
+        else if (s == "--disparity") ok = text(a.disparity);
         else if (s == "--disparity-params") {
-            if (i + 1 >= argc) return false;
-            viso_disparity_params& p = a.disp;
-            char tail = 0;
-            if (std::sscanf(argv[++i], "%d,%d,%d,%d,%d,%d%c", &p.num_disp, &p.block, &p.prefilter_cap, &p.texture_threshold,
-                            &p.uniqueness, &p.lr_max_diff, &tail) != 6) return false;
-            a.disp_params_given = true;
+            viso_disparity_params& p = d.params;
+            ok = a.disp_params_given = int_list(value(), "%d,%d,%d,%d,%d,%d%c", &p.num_disp, &p.block, &p.prefilter_cap,
+                                                &p.texture_threshold, &p.uniqueness, &p.lr_max_diff);
         }
         else if (s == "--disparity-method") {
-            if (i + 1 >= argc) return false;
-            const std::string m = argv[++i];
-            if (m != "bm" && m != "sgm") return false;
-            a.method_given = true; a.sgm = m == "sgm";
+            std::string m;
+            ok = a.method_given = text(m) && (m == "bm" || m == "sgm");
+            a.sgm = m == "sgm";
         }
         else if (s == "--sgm-params") {
-            if (i + 1 >= argc) return false;
-            viso_sgm_params& p = a.sgmp;
-            char tail = 0;
-            if (std::sscanf(argv[++i], "%d,%d,%d,%d,%d,%d%c", &p.num_disp, &p.p1, &p.p2, &p.paths, &p.uniqueness, &p.lr_max_diff,
-                            &tail) != 6) return false;
-            a.sgm_params_given = true;
+            viso_sgm_params& p = d.sgm_params;
+            ok = a.sgm_params_given = int_list(value(), "%d,%d,%d,%d,%d,%d%c", &p.num_disp, &p.p1, &p.p2, &p.paths, &p.uniqueness,
+                                               &p.lr_max_diff);
         }
-        else if (s == "--speckle") {
-            if (i + 1 >= argc) return false;
-            char tail = 0;
-            if (std::sscanf(argv[++i], "%d,%d%c", &a.spk.max_size, &a.spk.max_diff, &tail) != 2) return false;
-            a.speckle = true;
-        }
-        else if (s == "--covariance-sigma") {
-            if (i + 1 >= argc) return false;
+        else if (s == "--speckle") ok = a.speckle_given = int_list(value(), "%d,%d%c", &d.speckle_params.max_size, &d.speckle_params.max_diff);
+        else if (s == "--covariance-sigma") {   // its range is set_covariance's to check, below
+            const char* v = value();
             char* e = nullptr;
-            a.cov_sigma = std::strtod(argv[++i], &e);
-            if (!e || *e || !std::isfinite(a.cov_sigma) || a.cov_sigma <= 0.0) return false;
+            if (v) a.opt.cov_sigma = std::strtod(v, &e);
+            ok = a.sigma_given = v && !*e;
         }
-        else if (s == "--seed") { if (i + 1 >= argc) return false; a.seed = std::strtoull(argv[++i], nullptr, 10); }
+        else if (s == "--seed") { const char* v = value(); if (v) a.opt.ransac_seed = std::strtoull(v, nullptr, 10); ok = v != nullptr; }
         else if (s == "--same-device") a.same_device = true;
-        else if (s.rfind("--", 0) == 0) return false;
+        else if (s.rfind("--", 0) == 0) ok = false;
         else {
             if (pos == 0) a.result_sha = argv[i];
             else if (pos == 1) a.seq_name = s;
             else if (pos == 2) a.begin = std::atoi(argv[i]);                                   // src/kitti.cpp:86-94
             else if (pos == 3) a.end = std::atoi(argv[i]);
-            else return false;
+            else ok = false;
             ++pos;
         }
+        if (!ok) return false;
     }
     if (pos < 2) return false;
     if ((a.rank >= 0) != (a.world > 0)) return false;
     if (a.rank >= a.world && a.world > 0) return false;
-    if (a.cov_sigma > 0.0 && a.covariance.empty()) return false;   // --covariance-sigma belongs to --covariance
+    if (a.sigma_given && a.covariance.empty()) return false;         // --covariance-sigma belongs to --covariance
     if (a.disp_params_given && a.disparity.empty()) return false;    // --disparity-params belongs to --disparity
     if (a.method_given && a.disparity.empty()) return false;         // and so does --disparity-method
     if (a.sgm_params_given && !a.sgm) return false;                  // --sgm-params belongs to --disparity-method sgm
     if (a.disp_params_given && a.sgm) return false;                  // --disparity-params to the block matcher
-    if (a.speckle && a.disparity.empty()) return false;              // --speckle filters the maps of --disparity
-    return true;
+    if (a.speckle_given && a.disparity.empty()) return false;        // --speckle filters the maps of --disparity
+    // --covariance: mode 1 (sigma estimated), mode 2 with --covariance-sigma
+    return viso::set_covariance(a.opt, a.covariance.empty() ? 0 : a.sigma_given ? 2 : 1, a.opt.cov_sigma).empty();
 }
 
-int cov_mode(const Args& a) { return a.covariance.empty() ? 0 : a.cov_sigma > 0.0 ? 2 : 1; }
-
 bool write_covariances(const std::string& file, const std::vector<viso_motion_cov>& rec) {
-    const size_t slash = file.rfind('/');
-    if (slash != std::string::npos && slash > 0) viso::mkdirs(file.substr(0, slash));
+    viso::mkdirs_for(file);
     if (viso::write_covariance_file(file, rec.data(), rec.size())) return true;
     std::fprintf(stderr, "cannot write %s\n", file.c_str());
     return false;
@@ -198,49 +191,24 @@ int main(int argc, char** argv) {
     const std::string result_dir = std::string(home) + "/results/" + a.seq_name + "/" + a.result_sha;   // :100
     const std::string out = result_dir + "/data/" + a.seq_name + ".txt";                       // :114
     viso::Matd P1, P2;
-    viso::StereoRectification rect;
-    const viso::StereoRectification* rectp = nullptr;
-    if (!a.rectify.empty()) {
-        if (!viso::loadCalibCamToCam(a.rectify, rect, P1, P2)) {
-            std::fprintf(stderr, "cannot read a KITTI raw calib_cam_to_cam file (S, K, D, R_rect, P_rect, S_rect of cameras 00 and 01) from %s\n",
-                         a.rectify.c_str());
-            return 2;
-        }
-        rectp = &rect;
-    } else if (!viso::loadCalib(seq_base + "/calib.txt", P1, P2)) { std::fprintf(stderr, "cannot read %s/calib.txt\n", seq_base.c_str()); return 2; }
+    std::string err = viso::set_rectify(a.opt, P1, P2, a.rectify.c_str());
+    if (!err.empty()) { std::fprintf(stderr, "%s\n", err.c_str()); return 2; }
+    if (!a.opt.rect && !viso::loadCalib(seq_base + "/calib.txt", P1, P2)) { std::fprintf(stderr, "cannot read %s/calib.txt\n", seq_base.c_str()); return 2; }
     const int n_frames = viso::kitti_count_frames(seq_base, a.begin, a.end);
-    viso::DisparityOutput disp;   // --disparity: checked (and its directory made) here, before any rank is forked
-    const viso::DisparityOutput* dispp = nullptr;
-    if (!a.disparity.empty()) {
-        const int ok = a.sgm ? viso_kitti_set_sgm(a.disparity.c_str(), a.sgm_params_given ? &a.sgmp : nullptr)
-                             : viso_kitti_set_disparity(a.disparity.c_str(), a.disp_params_given ? &a.disp : nullptr);
-        if (ok != VISO_OK) {
-            std::fprintf(stderr, "%s\n", viso_host_last_error());
-            return 2;
-        }
-        disp.dir = a.disparity;
-        disp.sgm = a.sgm;
-        if (a.sgm_params_given) disp.sgm_params = a.sgmp;
-        else viso_sgm_params_default(&disp.sgm_params);
-        if (a.disp_params_given) disp.params = a.disp;
-        else viso_disparity_params_default(&disp.params);
-        if (a.speckle) {
-            if (viso_kitti_set_speckle(&a.spk) != VISO_OK) {
-                std::fprintf(stderr, "%s\n", viso_host_last_error());
-                return 2;
-            }
-            disp.speckle = true;
-            disp.speckle_params = a.spk;
-        }
-        dispp = &disp;
+    if (!a.disparity.empty()) {   // --disparity: checked (and its directory made) here, before any rank is forked
+        viso::DisparityOutput& d = a.opt.disparity;
+        err = a.sgm ? viso::set_sgm(a.opt, a.disparity.c_str(), a.sgm_params_given ? &d.sgm_params : nullptr)
+                    : viso::set_disparity(a.opt, a.disparity.c_str(), a.disp_params_given ? &d.params : nullptr);
+        if (err.empty() && a.speckle_given) err = viso::set_speckle(a.opt, &d.speckle_params);
+        if (!err.empty()) { std::fprintf(stderr, "%s\n", err.c_str()); return 2; }
     }
 
     // ---- --gpus W: fork the ranks BEFORE this process touches the GPU (the parent never does: nothing above makes a
     // HIP call), each child carries on below as `--rank r --world W`; the parent waits and gathers.  fork without exec:
     // a child initialises its own HIP runtime on its first call ----
     const auto t_start = std::chrono::steady_clock::now();
-    if (a.decode_threads <= 0 && !std::getenv("VISO_DECODE_THREADS"))
-        a.decode_threads = threads_per_rank(a.gpus > 1 ? a.gpus : 1);
+    if (a.opt.decode_threads <= 0 && !std::getenv("VISO_DECODE_THREADS"))
+        a.opt.decode_threads = threads_per_rank(a.gpus > 1 ? a.gpus : 1);
     if (a.gpus > 1) {
         std::fflush(nullptr);
         std::vector<pid_t> kids;
@@ -288,14 +256,13 @@ int main(int argc, char** argv) {
                 for (int r = 0; r < a.gather; ++r) {
                     int first = 0, last = 0;
                     const std::string f = rank_file(result_dir, a.seq_name, r, a.gather) + ".cov";
-                    if (!viso::read_cov_records(f, first, last, cparts[(size_t)r]) || first != ranges[(size_t)r].first ||
+                    if (!viso::read_records(f, first, last, cparts[(size_t)r]) || first != ranges[(size_t)r].first ||
                         last != ranges[(size_t)r].second || cparts[(size_t)r].size() != parts[(size_t)r].size()) {
                         std::fprintf(stderr, "cannot read %s (or it does not match the rank's records)\n", f.c_str());
                         return 3;
                     }
                 }
-                const std::vector<viso_motion_cov> call = viso::stitch_cov_records(cparts, ranges);
-                if (!write_covariances(a.covariance, call)) return 3;
+                if (!write_covariances(a.covariance, viso::stitch_records(cparts, ranges))) return 3;
             }
             const std::vector<viso::Matd> poses = viso::chain_records(all.data(), (int)all.size(), a.reference_pose_list);
             viso::mkdirs(result_dir + "/data");
@@ -310,30 +277,26 @@ int main(int argc, char** argv) {
         // ---- --rank r --world W: this rank's range -> its rank file ----
         if (a.world > 0) {
             const auto range = viso::partition(n_frames, a.world)[(size_t)a.rank];
-            const int device = a.device >= 0 ? a.device : a.rank;
-            viso::OdometryStats stats;
-            std::vector<viso_motion_cov> cov;
-            std::vector<viso::FrameRecord> rec = viso::kitti_run_range(seq_base, P1, P2, a.begin, range.first, range.second,
-                                                                       device, a.chunk, a.seed, a.decode_threads, &stats, a.subpixel, rectp,
-                                                                       cov_mode(a), a.cov_sigma, a.covariance.empty() ? nullptr : &cov, dispp);
+            a.opt.device = a.device >= 0 ? a.device : a.rank;
+            const viso::RangeResult res = viso::kitti_run_range(seq_base, P1, P2, a.begin, range.first, range.second, a.opt);
             viso::mkdirs(result_dir + "/shards");
             const std::string f = rank_file(result_dir, a.seq_name, a.rank, a.world);
-            if (!a.covariance.empty() && !viso::write_cov_records(f + ".cov", range.first, range.second, cov)) {
+            if (!a.covariance.empty() && !viso::write_records(f + ".cov", range.first, range.second, res.cov)) {
                 std::fprintf(stderr, "cannot write %s.cov\n", f.c_str());
                 return 3;
             }
-            if (!viso::write_records(f, range.first, range.second, rec)) { std::fprintf(stderr, "cannot write %s\n", f.c_str()); return 3; }
-            std::printf("rank %d/%d device %d frames %d..%d pairs %zu -> %s\n", a.rank, a.world, device, a.begin + range.first,
-                        a.begin + range.second, rec.size(), f.c_str());
-            print_stats(("rank " + std::to_string(a.rank)).c_str(), stats);
+            if (!viso::write_records(f, range.first, range.second, res.rec)) { std::fprintf(stderr, "cannot write %s\n", f.c_str()); return 3; }
+            std::printf("rank %d/%d device %d frames %d..%d pairs %zu -> %s\n", a.rank, a.world, a.opt.device, a.begin + range.first,
+                        a.begin + range.second, res.rec.size(), f.c_str());
+            print_stats(("rank " + std::to_string(a.rank)).c_str(), res.stats);
             return 0;
         }
         // ---- one process, one GPU: the reference's flow (:108-116) ----
         const std::string ext = viso::kitti_image_ext(seq_base, a.begin);
         viso::StereoImageGenerator images({seq_base + "/image_0/%06d" + ext, seq_base + "/image_1/%06d" + ext}, a.begin, a.end);
-        viso::OdometryResult res = viso::sequence_odometry(P1, P2, images, a.chunk, a.seed, (uint64_t)a.begin,
-                                                           a.device >= 0 ? a.device : 0, a.decode_threads, a.subpixel, rectp,
-                                                           cov_mode(a), a.cov_sigma, dispp);   // :111
+        a.opt.first_frame_index = (uint64_t)a.begin;
+        a.opt.device = a.device >= 0 ? a.device : 0;
+        viso::OdometryResult res = viso::sequence_odometry(P1, P2, images, a.opt);             // :111
         if (!a.covariance.empty()) {   // one line per frame pair: the records of frames 1 .. (entry 0 is the first frame)
             const std::vector<viso_motion_cov> pairs(res.cov.size() > 1 ? res.cov.begin() + 1 : res.cov.end(), res.cov.end());
             if (!write_covariances(a.covariance, pairs)) return 3;

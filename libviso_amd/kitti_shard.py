@@ -36,7 +36,7 @@ import time
 
 import numpy as np
 
-from .abi import MOTION_COV_DTYPE
+from .abi import MOTION_COV_DTYPE, DisparityParams, SgmParams, SpeckleParams
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 HOST_SO = os.path.join(_HERE, "libviso_host.so")
@@ -288,20 +288,24 @@ def main(argv=None):
                     help="with --disparity, for either method: the speckle filter over every map before it is written "
                          "(max_size in pixels, max_diff in 1/16 px)")
     args = ap.parse_args(argv)
-    if args.covariance_sigma is not None and args.covariance is None:
-        ap.error("--covariance-sigma needs --covariance")
-    disp_params = None
-    if args.disparity_params is not None:
-        if args.disparity is None:
-            ap.error("--disparity-params needs --disparity")
+
+    def int_list(text, struct, what):
+        """The ctypes struct of an option that takes as many comma-separated integers as it has fields (None: not given)."""
+        if text is None:
+            return None
         try:
-            vals = [int(v) for v in args.disparity_params.split(",")]
+            vals = [int(v) for v in text.split(",")]
         except ValueError:
             vals = []
-        if len(vals) != 6:
-            ap.error("--disparity-params takes six integers D,B,c,T,u,m")
-        from .abi import DisparityParams
-        disp_params = DisparityParams(*vals)
+        if len(vals) != len(struct._fields_):
+            ap.error(what)
+        return struct(*vals)
+
+    if args.covariance_sigma is not None and args.covariance is None:
+        ap.error("--covariance-sigma needs --covariance")
+    if args.disparity_params is not None and args.disparity is None:
+        ap.error("--disparity-params needs --disparity")
+    disp_params = int_list(args.disparity_params, DisparityParams, "--disparity-params takes six integers D,B,c,T,u,m")
     if args.disparity_method is not None and args.disparity is None:
         ap.error("--disparity-method needs --disparity")
     use_sgm = args.disparity_method == "sgm"
@@ -309,28 +313,10 @@ def main(argv=None):
         ap.error("--sgm-params needs --disparity-method sgm")
     if use_sgm and args.disparity_params is not None:
         ap.error("--disparity-params belongs to --disparity-method bm")
-    sgm_params = None
-    if args.sgm_params is not None:
-        try:
-            vals = [int(v) for v in args.sgm_params.split(",")]
-        except ValueError:
-            vals = []
-        if len(vals) != 6:
-            ap.error("--sgm-params takes six integers D,P1,P2,paths,u,m")
-        from .abi import SgmParams
-        sgm_params = SgmParams(*vals)
-    speckle = None
-    if args.speckle is not None:
-        if args.disparity is None:
-            ap.error("--speckle needs --disparity")
-        try:
-            vals = [int(v) for v in args.speckle.split(",")]
-        except ValueError:
-            vals = []
-        if len(vals) != 2:
-            ap.error("--speckle takes two integers SIZE,DIFF")
-        from .abi import SpeckleParams
-        speckle = SpeckleParams(*vals)
+    sgm_params = int_list(args.sgm_params, SgmParams, "--sgm-params takes six integers D,P1,P2,paths,u,m")
+    if args.speckle is not None and args.disparity is None:
+        ap.error("--speckle needs --disparity")
+    speckle = int_list(args.speckle, SpeckleParams, "--speckle takes two integers SIZE,DIFF")
     home = os.environ.get("KITTI_HOME")
     if not home:
         print("KITTI_HOME is not set", file=sys.stderr)
@@ -372,31 +358,26 @@ def main(argv=None):
     L = load_host()
     threads = args.decode_threads or int(os.environ.get("VISO_DECODE_THREADS", "0")) or max(1, min(64, cpu_budget() // world))
     L.viso_kitti_set_decode_threads(threads)
-    if L.viso_kitti_set_subpixel(args.subpixel) != 1:
-        print(f"kitti_shard: {L.viso_host_last_error().decode()}", file=sys.stderr)
-        return 2
-    if args.rectify is not None and L.viso_kitti_set_rectify(os.fsencode(os.path.abspath(args.rectify))) != 1:
-        print(f"kitti_shard: {L.viso_host_last_error().decode()}", file=sys.stderr)
-        return 2
 
-    if args.covariance is not None:
-        mode = 1 if args.covariance_sigma is None else 2
-        if L.viso_kitti_set_covariance(mode, float(args.covariance_sigma or 0.0)) != 1:
+    def refused(result):
+        """What a viso_kitti_set_* call returned: anything but 1 is reported, and main returns 2."""
+        if result != 1:
             print(f"kitti_shard: {L.viso_host_last_error().decode()}", file=sys.stderr)
-            return 2
+        return result != 1
 
-    if args.disparity is not None and use_sgm:
-        if L.viso_kitti_set_sgm(os.fsencode(os.path.abspath(args.disparity)),
-                                C.addressof(sgm_params) if sgm_params is not None else None) != 1:
-            print(f"kitti_shard: {L.viso_host_last_error().decode()}", file=sys.stderr)
-            return 2
-    elif args.disparity is not None and L.viso_kitti_set_disparity(
-            os.fsencode(os.path.abspath(args.disparity)), C.addressof(disp_params) if disp_params is not None else None) != 1:
-        print(f"kitti_shard: {L.viso_host_last_error().decode()}", file=sys.stderr)
+    path = lambda p: os.fsencode(os.path.abspath(p))                      # noqa: E731
+    ref = lambda s: C.addressof(s) if s is not None else None            # noqa: E731
+    if refused(L.viso_kitti_set_subpixel(args.subpixel)):
         return 2
-
-    if speckle is not None and L.viso_kitti_set_speckle(C.addressof(speckle)) != 1:
-        print(f"kitti_shard: {L.viso_host_last_error().decode()}", file=sys.stderr)
+    if args.rectify is not None and refused(L.viso_kitti_set_rectify(path(args.rectify))):
+        return 2
+    if args.covariance is not None and refused(L.viso_kitti_set_covariance(1 if args.covariance_sigma is None else 2,
+                                                                           float(args.covariance_sigma or 0.0))):
+        return 2
+    if args.disparity is not None and refused(L.viso_kitti_set_sgm(path(args.disparity), ref(sgm_params)) if use_sgm else
+                                              L.viso_kitti_set_disparity(path(args.disparity), ref(disp_params))):
+        return 2
+    if speckle is not None and refused(L.viso_kitti_set_speckle(ref(speckle))):
         return 2
 
     def die(code, what):

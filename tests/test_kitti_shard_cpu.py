@@ -2,6 +2,7 @@
 pose chain and the pose file.  The per-range engine is injected (records that are a fixed function of the absolute
 frame index), so what is tested here is exactly what differs between W = 1 and W > 1; the HIP engine under the same
 code runs in tests/test_gpu_kitti_shard.py."""
+import ctypes as C
 import os
 import socket
 import struct
@@ -306,3 +307,119 @@ def test_reference_pose_list(host, tmp_path):
                        env=dict(os.environ, KITTI_HOME=home), timeout=60)
     assert r.returncode == 0, r.stdout + r.stderr
     assert np.array_equal(np.loadtxt(os.path.join(home, "results", "07", "x", "data", "07.txt")), b)
+
+
+_LIST6 = "48,9,31,10,15,1"
+USAGE_ERRORS = {                                     # D = a --disparity directory that must not come into being
+    "sigma without covariance": ["--covariance-sigma", "0.5"],
+    "disparity-params without disparity": ["--disparity-params", _LIST6],
+    "disparity-method without disparity": ["--disparity-method", "sgm"],
+    "speckle without disparity": ["--speckle", "40,12"],
+    "sgm-params without sgm": ["--disparity", "D", "--sgm-params", "48,10,120,8,10,1"],
+    "disparity-params with sgm": ["--disparity", "D", "--disparity-method", "sgm", "--disparity-params", _LIST6],
+    "two of six integers": ["--disparity", "D", "--disparity-params", "48,9"],
+    "one of two integers": ["--disparity", "D", "--speckle", "40"],
+    "three of two integers": ["--disparity", "D", "--speckle", "40,12,3"],
+    "no value at the end of the line": ["--disparity", "D", "--speckle"],
+}
+
+
+@pytest.mark.parametrize("case", sorted(USAGE_ERRORS))
+def test_usage_errors_of_both_front_ends(host, tmp_path, case, capsys):
+    """One case per "belongs to" rule of the option lists, the malformed integer lists and a missing value: viso_kitti prints its
+    usage line and exits 1, kitti_shard.main leaves through argparse's error (SystemExit 2); neither gets as far as the checks
+    that make the --disparity directory, let alone to a device."""
+    from libviso_amd import kitti_shard
+    home = str(tmp_path)
+    _tree(home, "00", 3)
+    d = str(tmp_path / "maps")
+    bad = [d if v == "D" else v for v in USAGE_ERRORS[case]]
+    r = subprocess.run([EXE, "x", "00"] + bad, capture_output=True, text=True, env=dict(os.environ, KITTI_HOME=home), timeout=60)
+    assert r.returncode == 1 and r.stdout.startswith("usage:"), r.stdout + r.stderr
+    with pytest.raises(SystemExit) as e:
+        kitti_shard.main(["x", "00", "--gpus", "1"] + bad)
+    assert e.value.code == 2 and "usage:" in capsys.readouterr().err
+    assert not os.path.exists(d) and not os.path.exists(os.path.join(home, "results"))
+
+
+def _cov_record(frame):
+    """A viso_motion_cov (cov[36], delta[6], sigma2, gap, status, n: 360 bytes) that is a fixed function of the frame."""
+    rng = np.random.default_rng(2000 + frame)
+    a = rng.normal(size=(6, 6))
+    return list((a @ a.T).reshape(-1)) + list(rng.normal(size=6)) + [0.1 + frame, 1.5 * frame, 1 + frame % 2, 40 + frame]
+
+
+def _write_cov_rank_file(path, first, last, cov):
+    with open(path, "wb") as f:
+        f.write(struct.pack("<4i", 0x56534B43, first, last, len(cov)))
+        for c in cov:
+            f.write(struct.pack("<44d2i", *c))
+
+
+def test_gather_takes_the_covariance_rank_files(host, tmp_path):
+    """`viso_kitti --gather W --covariance F`: a .cov rank file beside every .rec (magic VSKC, the same header, 360-byte records)
+    is stitched into F like the records into the pose file; one of another range, or with another number of records than its
+    .rec, is refused with code 3 and nothing is written."""
+    from libviso_amd import kitti_shard
+    home, n_frames, world = str(tmp_path), 11, 3
+    _tree(home, "05", n_frames)
+    shards = os.path.join(home, "results", "05", "x", "shards")
+    ranges = kitti_shard.partition(n_frames, world)
+    for r, (a, b) in enumerate(ranges):
+        _write_rank_file(os.path.join(shards, f"05.{r}of{world}.rec"), a, b, [_fake_record(t) for t in range(a + 1, b + 1)])
+        _write_cov_rank_file(os.path.join(shards, f"05.{r}of{world}.rec.cov"), a, b, [_cov_record(t) for t in range(a + 1, b + 1)])
+    out = str(tmp_path / "out" / "cov.txt")
+    cmd = [EXE, "x", "05", "--gather", str(world), "--covariance", out]
+    env = dict(os.environ, KITTI_HOME=home)
+    r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=60)
+    assert r.returncode == 0, r.stdout + r.stderr
+    lines = open(out).read().splitlines()
+    assert len(lines) == n_frames - 1
+    iu = np.triu_indices(6)
+    for t, line in zip(range(1, n_frames), lines):
+        c, v = _cov_record(t), line.split()
+        assert [int(v[0]), int(v[1])] == c[44:] and [float(v[2]), float(v[3])] == c[42:44]      # %.17g round-trips
+        assert [float(x) for x in v[4:]] == np.array(c[:36]).reshape(6, 6)[iu].tolist()
+    a, b = ranges[1]
+    good = [_cov_record(t) for t in range(a + 1, b + 1)]
+    poses = os.path.join(home, "results", "05", "x", "data", "05.txt")
+    os.remove(out), os.remove(poses)
+    for first, last, cov in ((a + 1, b + 1, good), (a, b, good[:-1])):      # another range; fewer records than the .rec has
+        _write_cov_rank_file(os.path.join(shards, f"05.1of{world}.rec.cov"), first, last, cov)
+        r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=60)
+        assert r.returncode == 3 and "cannot read" in r.stderr and not os.path.exists(out) and not os.path.exists(poses)
+
+
+def test_setter_sequences_return_what_they_did(host, tmp_path):
+    """The viso_kitti_set_* calls in the orders the launcher and other callers use them: disparity on -> sgm on -> off, the
+    speckle filter before, between and after, covariance 2 -> 1 -> 0.  Every valid call returns 1 whatever came before it, every
+    invalid one -1 (VISO_ERR_ARG) with viso_host_last_error naming the setter, and a refused call leaves no directory behind."""
+    from libviso_amd.abi import DisparityParams, SgmParams, SpeckleParams
+    L = host
+    d = str(tmp_path / "maps").encode()
+    ref = lambda s: C.addressof(s)   # noqa: E731
+    err = lambda: L.viso_host_last_error().decode()   # noqa: E731
+    spk, bad_spk = SpeckleParams(40, 12), SpeckleParams(40, 4097)
+    assert L.viso_kitti_set_speckle(ref(spk)) == 1                       # before: no maps are written yet
+    assert L.viso_kitti_set_speckle(ref(bad_spk)) == -1 and err().startswith("viso_kitti_set_speckle:")
+    assert L.viso_kitti_set_disparity(d, ref(DisparityParams(48, 4, 31, 10, 15, 1))) == -1       # block 4
+    assert err().startswith("viso_kitti_set_disparity:") and not os.path.exists(d)
+    assert L.viso_kitti_set_sgm(d, ref(SgmParams(48, 10, 120, 5, 10, 1))) == -1                  # paths 5
+    assert err().startswith("viso_kitti_set_sgm:") and not os.path.exists(d)
+    assert L.viso_kitti_set_disparity(d, None) == 1 and os.path.isdir(d)                         # on, the defaults
+    assert L.viso_kitti_set_speckle(ref(spk)) == 1                       # between
+    assert L.viso_kitti_set_sgm(d, ref(SgmParams(48, 10, 120, 8, 10, 1))) == 1                   # the method changes
+    assert L.viso_kitti_set_disparity(d, ref(DisparityParams(48, 9, 31, 10, 15, 1))) == 1        # and back
+    assert L.viso_kitti_set_sgm(d, None) == 1
+    assert L.viso_kitti_set_speckle(None) == 1                           # after: off
+    open(str(tmp_path / "file"), "w").close()
+    under_a_file = str(tmp_path / "file" / "maps").encode()
+    assert L.viso_kitti_set_sgm(under_a_file, None) == -1 and err().startswith("viso_kitti_set_sgm: cannot create")
+    assert L.viso_kitti_set_disparity(under_a_file, None) == -1 and err().startswith("viso_kitti_set_disparity: cannot create")
+    assert L.viso_kitti_set_sgm(None, None) == 1 and L.viso_kitti_set_disparity(b"", None) == 1  # off, twice over
+    assert L.viso_kitti_set_speckle(ref(spk)) == 1 and L.viso_kitti_set_speckle(None) == 1
+    assert L.viso_kitti_set_covariance(2, 0.5) == 1 and L.viso_kitti_set_covariance(1, 0.5) == 1
+    assert L.viso_kitti_set_covariance(2, 0.0) == -1 and err().startswith("viso_kitti_set_covariance:")
+    assert L.viso_kitti_set_covariance(0, 0.0) == 1
+    assert L.viso_kitti_set_subpixel(2) == 1 and L.viso_kitti_set_subpixel(3) == -1 and err().startswith("viso_kitti_set_subpixel:")
+    assert L.viso_kitti_set_subpixel(0) == 1
