@@ -1508,23 +1508,25 @@ class Batch:
                   self.L.viso_batch_get_disparity_points(self.h, int(t), Tp, int(min_disp16), ptr(out, C.c_float)))
         return out
 
+    def _range_poses(self, where, poses, t0, t1):
+        """The end of the frames t0 .. t1-1 (t1 None: to the last frame) and their poses as a contiguous float64 [t1 - t0][4][4]."""
+        t1 = self.nf if t1 is None else int(t1)
+        T = np.ascontiguousarray(poses, dtype=np.float64)
+        if T.ndim != 3 or T.shape[1:] != (4, 4) or T.shape[0] != t1 - int(t0):
+            raise ValueError(where + ": poses must be [t1 - t0][4][4]")
+        return t1, T
+
     def fuse_disparities(self, vmap, poses, t0=0, t1=None):
         """viso_batch_fuse_disparities: the resident maps of frames t0 .. t1-1 (t1 None: to the last frame) fused into the VoxelMap
         on the device, frame t0 + i with the 4 x 4 pose poses[i]; no map is copied to the host.  The map must be on this batch's
         context."""
-        t1 = self.nf if t1 is None else int(t1)
-        T = np.ascontiguousarray(poses, dtype=np.float64)
-        if T.ndim != 3 or T.shape[1:] != (4, 4) or T.shape[0] != t1 - int(t0):
-            raise ValueError("Batch.fuse_disparities: poses must be [t1 - t0][4][4]")
+        t1, T = self._range_poses("Batch.fuse_disparities", poses, t0, t1)
         self._chk("viso_batch_fuse_disparities", self.L.viso_batch_fuse_disparities(self.h, vmap.h, int(t0), t1, ptr(T, C.c_double)))
 
     def fuse_tsdf(self, tsdf, poses, t0=0, t1=None):
         """viso_batch_fuse_tsdf: the resident maps of frames t0 .. t1-1 (t1 None: to the last frame) fused into the TsdfMap on the
         device, frame t0 + i with the 4 x 4 pose poses[i]; no map is copied to the host.  The map must be on this batch's context."""
-        t1 = self.nf if t1 is None else int(t1)
-        T = np.ascontiguousarray(poses, dtype=np.float64)
-        if T.ndim != 3 or T.shape[1:] != (4, 4) or T.shape[0] != t1 - int(t0):
-            raise ValueError("Batch.fuse_tsdf: poses must be [t1 - t0][4][4]")
+        t1, T = self._range_poses("Batch.fuse_tsdf", poses, t0, t1)
         self._chk("viso_batch_fuse_tsdf", self.L.viso_batch_fuse_tsdf(self.h, tsdf.h, int(t0), t1, ptr(T, C.c_double)))
 
     def align_tsdf(self, tsdf, poses, t0=0, t1=None, photo=False, **params):
@@ -1534,10 +1536,7 @@ class Batch:
         context.
         photo=True (a gray map): viso_batch_align_tsdf_gray, with frame t's resident left image; params also takes photo_weight and
         photo_gate, and the records are TSDF_ALIGNMENT_GRAY_DTYPE ones: cost_geo, cost_photo and n_photo_used follow the fields."""
-        t1 = self.nf if t1 is None else int(t1)
-        T = np.ascontiguousarray(poses, dtype=np.float64)
-        if T.ndim != 3 or T.shape[1:] != (4, 4) or T.shape[0] != t1 - int(t0):
-            raise ValueError("Batch.align_tsdf: poses must be [t1 - t0][4][4]")
+        t1, T = self._range_poses("Batch.align_tsdf", poses, t0, t1)
         if photo:
             p, rec = tsdf_align_gray_params(**params), np.zeros(len(T), TSDF_ALIGNMENT_GRAY_DTYPE)
             self._chk("viso_batch_align_tsdf_gray", self.L.viso_batch_align_tsdf_gray(self.h, tsdf.h, int(t0), t1, ptr(T, C.c_double), C.byref(p),

@@ -83,28 +83,6 @@ struct AlignFrame {
     bool final_pending, done;
 };
 
-// The two kinds of alignment as the machine sees them: the linearise's sums, the record, the trace's entry; where the counters
-// of steps 1..9 and the plain record lie in them; the photometric rows of a linearise; what the final linearise adds to a record.
-struct AlignPlain {
-    using Normal = viso_tsdf_normal; using Record = viso_tsdf_alignment; using Step = viso_tsdf_align_step;
-    static const viso_tsdf_normal& geo(const Normal& nm) { return nm; }
-    static viso_tsdf_alignment& base(Record& r) { return r; }
-    static uint64_t photo_rows(const Normal&) { return 0; }
-    static void finish(Record&, const Normal&, double, double) {}
-};
-struct AlignGray {
-    using Normal = viso_tsdf_normal_gray; using Record = viso_tsdf_alignment_gray; using Step = viso_tsdf_align_gray_step;
-    static const viso_tsdf_normal& geo(const Normal& nm) { return nm.normal; }
-    static viso_tsdf_alignment& base(Record& r) { return r.a; }
-    static uint64_t photo_rows(const Normal& nm) { return nm.n_photo_used; }
-    static void finish(Record& r, const Normal& nm, double C, double lambda) {
-        const double pp = (double)nm.p / 65536.0;
-        r.cost_geo = sqrt((C - pp) / (double)nm.normal.n_used);
-        r.cost_photo = nm.n_photo_used && lambda > 0.0 ? sqrt(pp / (double)nm.n_photo_used) / lambda : 0.0;
-        r.n_photo_used = nm.n_photo_used;
-    }
-};
-
 template <class K>
 void align_fail(typename K::Record* rec, const double guess[16], int status) {
     memset(rec, 0, sizeof(*rec));
@@ -112,11 +90,14 @@ void align_fail(typename K::Record* rec, const double guess[16], int status) {
     K::base(*rec).status = status;
 }
 
+}   // namespace
+
 // Steps a..f and the final linearise for n frames, on the sums of whichever kind (the gray kind's N holds both rows' products).
 template <class K>
-int align_machine(const viso_tsdf_align_params& p, double lambda, int n, const double* guesses,
-                  const std::function<int(const double*, const unsigned long long*, typename K::Normal*)>& linearize,
-                  typename K::Record* records, typename K::Step* trace, int trace_cap) {
+int align_run(const typename K::Params& params, int n, const double* guesses, const AlignLinearize<K>& linearize, typename K::Record* records,
+              typename K::Step* trace, int trace_cap) {
+    const viso_tsdf_align_params& p = K::geo(params);
+    const double lambda = K::lambda(params);
     static const double eye[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
     std::vector<AlignFrame> fr((size_t)n);
     std::vector<double> poses((size_t)n * 16), guess((size_t)n * 16);
@@ -184,14 +165,8 @@ int align_machine(const viso_tsdf_align_params& p, double lambda, int n, const d
     }
     return VISO_OK;
 }
-}   // namespace
 
-int align_run(const viso_tsdf_align_params& p, int n, const double* guesses, const AlignLinearize& linearize, viso_tsdf_alignment* records,
-              viso_tsdf_align_step* trace, int trace_cap) {
-    return align_machine<AlignPlain>(p, 0.0, n, guesses, linearize, records, trace, trace_cap);
-}
-
-int align_run_gray(const viso_tsdf_align_gray_params& p, int n, const double* guesses, const AlignLinearizeGray& linearize,
-                   viso_tsdf_alignment_gray* records, viso_tsdf_align_gray_step* trace, int trace_cap) {
-    return align_machine<AlignGray>(p.geo, p.photo_weight, n, guesses, linearize, records, trace, trace_cap);
-}
+template int align_run<AlignPlain>(const viso_tsdf_align_params&, int, const double*, const AlignLinearize<AlignPlain>&, viso_tsdf_alignment*,
+                                   viso_tsdf_align_step*, int);
+template int align_run<AlignGray>(const viso_tsdf_align_gray_params&, int, const double*, const AlignLinearize<AlignGray>&, viso_tsdf_alignment_gray*,
+                                  viso_tsdf_align_gray_step*, int);

@@ -134,6 +134,22 @@ extern "C" int viso_batch_get_disparity(viso_batch* b, int t, int16_t* out) { re
 
 extern "C" int viso_batch_get_disparities(viso_batch* b, int16_t* out) { return get_disparity(b, true, 0, out, "viso_batch_get_disparities"); }
 
+// The resident maps of frames t0 .. t1-1 as a view (common.h) with the batch's calibration, at `poses` [t1 - t0][16] (or null).
+// needs (or null): who needs the resident left images the maps were computed from (frame t's at images + 2 t per); the view then has
+// them, and they must still be there with the maps' geometry.  The one place that knows where a frame's map and image lie.
+static int dense_view(const char* where, const viso_batch* b, int t0, int t1, const double* poses, const char* needs, DispView* v) {
+    const BatchDense& D = b->dense;
+    const size_t per = (size_t)D.rows * D.cols;
+    if (needs && (!b->images || b->img_rows != D.rows || b->img_cols != D.cols)) {
+        viso_set_error("%s: the resident images (%d x %d) are not the maps' (%d x %d): %s needs the images the maps were computed from",
+                       where, b->images ? b->img_cols : 0, b->images ? b->img_rows : 0, D.cols, D.rows, needs);
+        return VISO_ERR_ARG;
+    }
+    *v = DispView{D.disp + (size_t)t0 * per, per, needs ? b->images + 2 * (size_t)t0 * per : nullptr, 2 * per, D.rows, D.cols, t1 - t0,
+                  StereoCalib{b->sp.f, b->sp.cu, b->sp.cv, b->sp.base}, poses, b->ctx};
+    return VISO_OK;
+}
+
 // Frame t's resident map as an organised point image [rows][cols][3] f32 (speckle.hip), computed on demand with the batch's
 // calibration; the batch keeps no point buffer (the call's own is freed before it returns, so it is not recorded as the batch's).
 extern "C" int viso_batch_get_disparity_points(viso_batch* b, int t, const double* pose_or_null, int min_disp16, float* out) {
@@ -142,8 +158,9 @@ extern "C" int viso_batch_get_disparity_points(viso_batch* b, int t, const doubl
     if (!b->params_set) { viso_set_error("%s: parameters not set (the calibration comes from viso_batch_set_params)", where); return VISO_ERR_ARG; }
     VISO_TRY(dense_ready(b, where));
     VISO_TRY(enter(b));
-    const BatchDense& D = b->dense;
-    const size_t per = (size_t)D.rows * D.cols;
+    DispView v;
+    VISO_TRY(dense_view(where, b, t, t + 1, pose_or_null, nullptr, &v));
+    const size_t per = v.px();
     float* dout = nullptr;
     if (hipMalloc((void**)&dout, 3 * sizeof(float) * per) != hipSuccess) {
         (void)hipGetLastError();
@@ -151,7 +168,7 @@ extern "C" int viso_batch_get_disparity_points(viso_batch* b, int t, const doubl
         return VISO_ERR_NOMEM;
     }
     hipStream_t s = b->ctx->stream;
-    const int r = launch_points(s, D.disp + (size_t)t * per, D.rows, D.cols, b->sp.f, b->sp.cu, b->sp.cv, b->sp.base, pose_or_null, min_disp16, dout);
+    const int r = launch_points(s, v, min_disp16, dout);
     hipError_t e = hipSuccess;
     if (r >= 0) e = hipMemcpyAsync(out, dout, 3 * sizeof(float) * per, hipMemcpyDeviceToHost, s);
     const hipError_t e2 = hipStreamSynchronize(s);
@@ -178,9 +195,9 @@ static int fuse_prelude(const char* where, viso_batch* b, const void* map, int t
 extern "C" int viso_batch_fuse_disparities(viso_batch* b, viso_map* m, int t0, int t1, const double* poses) {
     const char* where = "viso_batch_fuse_disparities";
     VISO_TRY(fuse_prelude(where, b, m, t0, t1, poses));
-    const BatchDense& D = b->dense;
-    const size_t per = (size_t)D.rows * D.cols;
-    return map_fuse_resident(where, m, b->ctx, D.disp + (size_t)t0 * per, per, D.rows, D.cols, t1 - t0, b->sp.f, b->sp.cu, b->sp.cv, b->sp.base, poses);
+    DispView v;
+    VISO_TRY(dense_view(where, b, t0, t1, poses, nullptr, &v));
+    return map_fuse_resident(where, m, v);
 }
 
 // The same into a TSDF map of the same context (tsdf.hip).  A gray map also reads the resident left images the maps were computed
@@ -188,19 +205,9 @@ extern "C" int viso_batch_fuse_disparities(viso_batch* b, viso_map* m, int t0, i
 extern "C" int viso_batch_fuse_tsdf(viso_batch* b, viso_tsdf* t, int t0, int t1, const double* poses) {
     const char* where = "viso_batch_fuse_tsdf";
     VISO_TRY(fuse_prelude(where, b, t, t0, t1, poses));
-    const BatchDense& D = b->dense;
-    const size_t per = (size_t)D.rows * D.cols;
-    const uint8_t* image = nullptr;
-    if (tsdf_is_gray(t)) {
-        if (!b->images || b->img_rows != D.rows || b->img_cols != D.cols) {
-            viso_set_error("%s: the resident images (%d x %d) are not the maps' (%d x %d): a gray TSDF map needs the images the maps were computed from",
-                           where, b->images ? b->img_cols : 0, b->images ? b->img_rows : 0, D.cols, D.rows);
-            return VISO_ERR_ARG;
-        }
-        image = b->images + 2 * (size_t)t0 * per;
-    }
-    return tsdf_fuse_resident(where, t, b->ctx, D.disp + (size_t)t0 * per, per, D.rows, D.cols, t1 - t0, b->sp.f, b->sp.cu, b->sp.cv, b->sp.base, poses,
-                              image, 2 * per);
+    DispView v;
+    VISO_TRY(dense_view(where, b, t0, t1, poses, tsdf_is_gray(t) ? "a gray TSDF map" : nullptr, &v));
+    return tsdf_fuse_resident(where, t, v);
 }
 
 // The resident maps of frames t0 .. t1-1 aligned against a TSDF map of the same context (tsdf_align.hip), each on its own from its
@@ -210,10 +217,9 @@ extern "C" int viso_batch_align_tsdf(viso_batch* b, viso_tsdf* t, int t0, int t1
     const char* where = "viso_batch_align_tsdf";
     if (!params || !records_out) { viso_set_error("%s: bad argument (non-null parameters and records)", where); return VISO_ERR_ARG; }
     VISO_TRY(fuse_prelude(where, b, t, t0, t1, poses_guess));
-    const BatchDense& D = b->dense;
-    const size_t per = (size_t)D.rows * D.cols;
-    return tsdf_align_resident(where, t, b->ctx, D.disp + (size_t)t0 * per, per, D.rows, D.cols, t1 - t0, b->sp.f, b->sp.cu, b->sp.cv, b->sp.base,
-                               poses_guess, params, records_out);
+    DispView v;
+    VISO_TRY(dense_view(where, b, t0, t1, poses_guess, nullptr, &v));
+    return tsdf_align_resident(where, t, v, params, records_out);
 }
 
 // The same with the photometric row (tsdf_align.hip, "TSDF photometric align"): frame t's left image at images + 2 t per, which must
@@ -223,13 +229,7 @@ extern "C" int viso_batch_align_tsdf_gray(viso_batch* b, viso_tsdf* t, int t0, i
     const char* where = "viso_batch_align_tsdf_gray";
     if (!params || !records_out) { viso_set_error("%s: bad argument (non-null parameters and records)", where); return VISO_ERR_ARG; }
     VISO_TRY(fuse_prelude(where, b, t, t0, t1, poses_guess));
-    const BatchDense& D = b->dense;
-    const size_t per = (size_t)D.rows * D.cols;
-    if (!b->images || b->img_rows != D.rows || b->img_cols != D.cols) {
-        viso_set_error("%s: the resident images (%d x %d) are not the maps' (%d x %d): the photometric row needs the images the maps were computed from",
-                       where, b->images ? b->img_cols : 0, b->images ? b->img_rows : 0, D.cols, D.rows);
-        return VISO_ERR_ARG;
-    }
-    return tsdf_align_gray_resident(where, t, b->ctx, D.disp + (size_t)t0 * per, per, b->images + 2 * (size_t)t0 * per, 2 * per, D.rows, D.cols,
-                                    t1 - t0, b->sp.f, b->sp.cu, b->sp.cv, b->sp.base, poses_guess, params, records_out);
+    DispView v;
+    VISO_TRY(dense_view(where, b, t0, t1, poses_guess, "the photometric row", &v));
+    return tsdf_align_gray_resident(where, t, v, params, records_out);
 }

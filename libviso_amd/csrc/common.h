@@ -471,34 +471,47 @@ int launch_sgm(hipStream_t s, const uint8_t* img, size_t fs, size_t ss, int rows
                int16_t* out, size_t ofs, void* ws, int group);
 // speckle.hip: the opt-in speckle filter of the maps (viso_batch_set_speckle), in place; frame f's map at map + f * mfs.  The frames
 // go through the workspace ws in groups of `group` (>= 1) frames: ws holds group * speckle_frame_bytes.  speckle_group_frames: as
-// sgm_group_frames.  launch_points: the reprojection of one device map; pose = the first three rows of a 4 x 4 row-major matrix
-// on the host, or null.
+// sgm_group_frames.
 bool speckle_params_ok(const viso_speckle_params* p);
 bool speckle_geometry_ok(int rows, int cols);   // cols as the methods, and rows * cols within the 32-bit labels
 size_t speckle_frame_bytes(int rows, int cols);
 int speckle_group_frames(const char* where, int rows, int cols, int n_frames, int* group);
 int launch_speckle(hipStream_t s, int16_t* map, size_t mfs, int rows, int cols, int n_frames, const viso_speckle_params* p, void* ws,
                    int group);
-int launch_points(hipStream_t s, const int16_t* disp, int rows, int cols, double f, double cu, double cv, double base,
-                  const double* pose, int min_disp16, float* out);
-// voxelmap.hip: the opt-in voxel map (viso_map_*).  map_fuse_resident: the fuse of n_frames device maps (frame f at disp + f * mfs)
-// that live on context c, on its stream, with poses [n_frames][16] on the host; checks the map handle, its context and the poses
-int map_fuse_resident(const char* where, viso_map* m, viso_ctx* c, const int16_t* disp, size_t mfs, int rows, int cols, int n_frames,
-                      double f, double cu, double cv, double base, const double* poses);
+// ---- "these disparity maps": what every consumer of the maps receives (the reprojection, the fuses, the alignments) ------------------
+struct StereoCalib { double f, cu, cv, base; };
+struct DispView {
+    const int16_t* disp; size_t mfs;    // frame k's map at disp + k * mfs
+    const uint8_t* image; size_t ifs;   // frame k's 8-bit left image at image + k * ifs, or null
+    int rows, cols, n;
+    StereoCalib cal;
+    const double* poses;                // [n][16] on the host, or null
+    viso_ctx* ctx;                      // the context whose device memory disp and image are (resident); null: n = 1, one host map (and
+                                        // one host image) that the callee stages
+    size_t px() const { return (size_t)rows * cols; }
+};
+// The view of a host-pointer public call, made before any check: a size that is not positive gives strides of 0.  A call without
+// a calibration gets a view without a map: the callee's one null check ("non-null map and calibration") refuses either.
+inline DispView disp_view_host(const int16_t* disp, const uint8_t* image, int rows, int cols, const viso_param* param, const double* pose) {
+    const size_t px = rows > 0 && cols > 0 ? (size_t)rows * cols : 0;
+    const StereoCalib cal = param ? StereoCalib{param->f, param->cu, param->cv, param->base} : StereoCalib{0.0, 0.0, 0.0, 0.0};
+    return DispView{param ? disp : nullptr, px, image, px, rows, cols, 1, cal, pose, nullptr};
+}
+// speckle.hip, launch_points: the reprojection of the one map of v, on the device, at v's pose (its first three rows) or at none
+int launch_points(hipStream_t s, const DispView& v, int min_disp16, float* out);
+// voxelmap.hip: the opt-in voxel map (viso_map_*).  map_fuse_resident: the fuse of a resident view's maps on its context's stream;
+// checks the map handle, its context and the poses
+int map_fuse_resident(const char* where, viso_map* m, const DispView& v);
 // tsdf.hip: the opt-in TSDF map (viso_tsdf_*).  tsdf_fuse_resident: map_fuse_resident for a TSDF map; for a gray one (tsdf_is_gray:
-// 1 for a live gray map, else 0) with frame f's 8-bit left image at image + f * ifs on the device, for a plain one with image null
+// 1 for a live gray map, else 0) the view has the images, for a plain one it has none
 int tsdf_is_gray(viso_tsdf* t);
-int tsdf_fuse_resident(const char* where, viso_tsdf* t, viso_ctx* c, const int16_t* disp, size_t mfs, int rows, int cols, int n_frames,
-                       double f, double cu, double cv, double base, const double* poses, const uint8_t* image, size_t ifs);
-// tsdf_align.hip: the opt-in frame-to-model alignment (viso_tsdf_align).  tsdf_align_resident: the alignment of n_frames device maps
-// that live on context c against the map, each on its own from poses [n_frames][16]; checks the arguments, the handle and its context
-int tsdf_align_resident(const char* where, viso_tsdf* t, viso_ctx* c, const int16_t* disp, size_t mfs, int rows, int cols, int n_frames,
-                        double f, double cu, double cv, double base, const double* poses, const viso_tsdf_align_params* params,
-                        viso_tsdf_alignment* records);
-// the same with the photometric row ("TSDF photometric align"): frame f's 8-bit left image at image + f * ifs on the device
-int tsdf_align_gray_resident(const char* where, viso_tsdf* t, viso_ctx* c, const int16_t* disp, size_t mfs, const uint8_t* image, size_t ifs, int rows,
-                             int cols, int n_frames, double f, double cu, double cv, double base, const double* poses,
-                             const viso_tsdf_align_gray_params* params, viso_tsdf_alignment_gray* records);
+int tsdf_fuse_resident(const char* where, viso_tsdf* t, const DispView& v);
+// tsdf_align.hip: the opt-in frame-to-model alignment (viso_tsdf_align).  tsdf_align_resident: the alignment of a resident view's
+// maps against the map, each on its own from its pose; checks the arguments, the handle and its context
+int tsdf_align_resident(const char* where, viso_tsdf* t, const DispView& v, const viso_tsdf_align_params* params, viso_tsdf_alignment* records);
+// the same with the photometric row ("TSDF photometric align"), from the view's images
+int tsdf_align_gray_resident(const char* where, viso_tsdf* t, const DispView& v, const viso_tsdf_align_gray_params* params,
+                             viso_tsdf_alignment_gray* records);
 // covariance.hip: the opt-in motion covariance (viso_batch_set_covariance); one record per item, out[item], read from the item's
 // X, obs, m_ptr, ld, tr, ok, n_inl, inl (what ransac_refit_kernel left)
 int launch_motion_cov(hipStream_t s, const SolverItem* items_dev, int n_items, const SolverParamsDev& sp, int mode, double sigma,

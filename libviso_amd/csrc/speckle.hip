@@ -291,14 +291,12 @@ __global__ __launch_bounds__(256) void points_kernel(PointsArgs a) {
     o[0] = o0; o[1] = o1; o[2] = o2;
 }
 
-int launch_points(hipStream_t s, const int16_t* disp, int rows, int cols, double f, double cu, double cv, double base,
-                  const double* pose, int min_disp16, float* out) {
+int launch_points(hipStream_t s, const DispView& v, int min_disp16, float* out) {
     PointsArgs a;
-    a.disp = disp; a.out = out; a.rows = rows; a.cols = cols; a.min_disp16 = min_disp16; a.has_pose = pose != nullptr;
-    a.f = f; a.cu = cu; a.cv = cv; a.base = base;
-    for (int k = 0; k < 12; ++k) a.T[k] = pose ? pose[k] : 0.0;
-    const size_t px = (size_t)rows * cols;
-    hipLaunchKernelGGL(points_kernel, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, s, a);
+    a.disp = v.disp; a.out = out; a.rows = v.rows; a.cols = v.cols; a.min_disp16 = min_disp16; a.has_pose = v.poses != nullptr;
+    a.f = v.cal.f; a.cu = v.cal.cu; a.cv = v.cal.cv; a.base = v.cal.base;
+    for (int k = 0; k < 12; ++k) a.T[k] = v.poses ? v.poses[k] : 0.0;
+    hipLaunchKernelGGL(points_kernel, dim3((unsigned)((v.px() + 255) / 256)), dim3(256), 0, s, a);
     HIP_TRY(hipGetLastError());
     return VISO_OK;
 }
@@ -320,7 +318,9 @@ extern "C" int viso_disparity_to_points(const int16_t* disp, int rows, int cols,
     VISO_TRY(dc.scratch(SLOT_GEN1, per, &dmap));
     VISO_TRY(dc.scratch(SLOT_GEN2, 3 * per, &dout));
     VISO_TRY(dc.up(dmap, disp, per));
-    VISO_TRY(launch_points(dc.s, dmap, rows, cols, param->f, param->cu, param->cv, param->base, pose_or_null, min_disp16, dout));
+    DispView v = disp_view_host(disp, nullptr, rows, cols, param, pose_or_null);
+    v.disp = dmap;   // this call stages the map itself, in its own scratch
+    VISO_TRY(launch_points(dc.s, v, min_disp16, dout));
     VISO_TRY(dc.down(out, dout, 3 * per));
     return dc.wait();
 }

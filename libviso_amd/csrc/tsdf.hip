@@ -563,8 +563,8 @@ static VoxelLaunch tsdf_clear_launch(viso_tsdf* t) {
         else voxel_start_clear(tsdf_payload<false>(t), s);
     };
 }
-// ifs: the distance of two frames' images, for a gray map's fuse (whose calls all come with an image); 0: a plain map's
-static VoxelFuseLaunch tsdf_fuse_launch(viso_tsdf* t, size_t ifs = 0) {
+// ifs: the distance of two frames' images, for a gray map's fuse (whose calls all come with an image); a plain map's fuse ignores it
+static VoxelFuseLaunch tsdf_fuse_launch(viso_tsdf* t, size_t ifs) {
     return [t, ifs](const VoxelFuseArgs& v, const uint8_t* d_image, dim3 grid, hipStream_t s) {
         TsdfFuseArgs a;
         a.v = v; a.trunc = t->p.trunc_voxels; a.s = t->s; a.h = t->hs; a.t = t->t;
@@ -639,15 +639,15 @@ extern "C" int viso_tsdf_clear(viso_tsdf* t) { return voxel_clear("viso_tsdf_cle
 
 int tsdf_is_gray(viso_tsdf* t) { return voxel_known(g_tsdfs, t) && t->gray ? 1 : 0; }
 
-int tsdf_fuse_resident(const char* where, viso_tsdf* t, viso_ctx* c, const int16_t* disp, size_t mfs, int rows, int cols, int n_frames,
-                       double f, double cu, double cv, double base, const double* poses, const uint8_t* image, size_t ifs) {
-    if (!tsdf_kind_ok(where, t, image != nullptr)) return VISO_ERR_ARG;
-    return voxel_fuse_resident(where, g_tsdfs, t, c, disp, mfs, rows, cols, n_frames, f, cu, cv, base, poses, tsdf_fuse_launch(t, ifs), image, ifs);
+int tsdf_fuse_resident(const char* where, viso_tsdf* t, const DispView& v) {
+    if (!tsdf_kind_ok(where, t, v.image != nullptr)) return VISO_ERR_ARG;
+    return voxel_fuse(where, g_tsdfs, t, v, tsdf_fuse_launch(t, v.ifs));
 }
 
 extern "C" int viso_tsdf_fuse(viso_tsdf* t, const int16_t* disp, int rows, int cols, const viso_param* param, const double* pose_or_null) {
     if (!tsdf_kind_ok("viso_tsdf_fuse", t, false)) return VISO_ERR_ARG;
-    return voxel_fuse_host("viso_tsdf_fuse", g_tsdfs, t, disp, rows, cols, param, pose_or_null, tsdf_fuse_launch(t));
+    const DispView v = disp_view_host(disp, nullptr, rows, cols, param, pose_or_null);
+    return voxel_fuse("viso_tsdf_fuse", g_tsdfs, t, v, tsdf_fuse_launch(t, v.ifs));
 }
 
 extern "C" int viso_tsdf_fuse_gray(viso_tsdf* t, const int16_t* disp, const uint8_t* image, int rows, int cols, const viso_param* param,
@@ -655,8 +655,8 @@ extern "C" int viso_tsdf_fuse_gray(viso_tsdf* t, const int16_t* disp, const uint
     const char* where = "viso_tsdf_fuse_gray";
     if (!tsdf_kind_ok(where, t, true)) return VISO_ERR_ARG;
     if (!image) { viso_set_error("%s: bad argument (a non-null image)", where); return VISO_ERR_ARG; }
-    return voxel_fuse_host(where, g_tsdfs, t, disp, rows, cols, param, pose_or_null,
-                           tsdf_fuse_launch(t, rows > 0 && cols > 0 ? (size_t)rows * cols : 0), image);
+    const DispView v = disp_view_host(disp, image, rows, cols, param, pose_or_null);
+    return voxel_fuse(where, g_tsdfs, t, v, tsdf_fuse_launch(t, v.ifs));
 }
 
 // the checks of an entry that both kinds share
@@ -701,56 +701,54 @@ static inline bool voxel_item_less(const viso_tsdf_crossing& x, const viso_tsdf_
 
 // the count or the sorted list of the voxels of at least min_weight updates, as plain entries or, with GRAY, as a gray map's
 template <bool GRAY>
-static int tsdf_entries(const char* where, viso_tsdf* t, uint32_t min_weight, bool count_only, typename TsdfPayload<GRAY>::Entry* entries_out,
-                        size_t n_cap, size_t* n) {
+static int tsdf_entries(const char* where, viso_tsdf* t, uint32_t min_weight, const VoxelList<typename TsdfPayload<GRAY>::Entry>& list) {
     if (GRAY ? !tsdf_kind_ok(where, t, true) : !voxel_known(g_tsdfs, t)) {
         if (!GRAY) viso_set_error("%s: not a live TSDF handle", where);
         return VISO_ERR_ARG;
     }
-    return voxel_entries(where, g_tsdfs, t, min_weight, count_only, entries_out, n_cap, n, tsdf_payload<GRAY>(t));
+    return voxel_entries(where, g_tsdfs, t, min_weight, list, tsdf_payload<GRAY>(t));
 }
 extern "C" int viso_tsdf_count(viso_tsdf* t, uint32_t min_weight, size_t* n) {   // either kind
-    return tsdf_entries<false>("viso_tsdf_count", t, min_weight, true, nullptr, 0, n);
+    return tsdf_entries<false>("viso_tsdf_count", t, min_weight, {true, nullptr, 0, n});
 }
 extern "C" int viso_tsdf_get(viso_tsdf* t, uint32_t min_weight, viso_tsdf_entry* entries_out, size_t n_cap, size_t* n) {
-    return tsdf_entries<false>("viso_tsdf_get", t, min_weight, false, entries_out, n_cap, n);
+    return tsdf_entries<false>("viso_tsdf_get", t, min_weight, {false, entries_out, n_cap, n});
 }
 extern "C" int viso_tsdf_get_gray(viso_tsdf* t, uint32_t min_weight, viso_tsdf_gray_entry* entries_out, size_t n_cap, size_t* n) {
-    return tsdf_entries<true>("viso_tsdf_get_gray", t, min_weight, false, entries_out, n_cap, n);
+    return tsdf_entries<true>("viso_tsdf_get_gray", t, min_weight, {false, entries_out, n_cap, n});
 }
 
 // viso_tsdf_evict*: t is live and of the payload's kind
 template <bool GRAY>
-static int tsdf_evict(const char* where, viso_tsdf* t, const viso_voxel_box* keep, bool count_only, typename TsdfPayload<GRAY>::Entry* evicted_out,
-                      size_t n_cap, size_t* n) {
-    return voxel_evict(where, g_tsdfs, t, keep, count_only, evicted_out, n_cap, n, tsdf_payload<GRAY>(t));
+static int tsdf_evict(const char* where, viso_tsdf* t, const viso_voxel_box* keep, const VoxelList<typename TsdfPayload<GRAY>::Entry>& list) {
+    return voxel_evict(where, g_tsdfs, t, keep, list, tsdf_payload<GRAY>(t));
 }
 extern "C" int viso_tsdf_evict_count(viso_tsdf* t, const viso_voxel_box* keep, size_t* n) {   // either kind
     const char* where = "viso_tsdf_evict_count";
     if (!voxel_known(g_tsdfs, t)) { viso_set_error("%s: not a live TSDF handle", where); return VISO_ERR_ARG; }
-    return t->gray ? tsdf_evict<true>(where, t, keep, true, nullptr, 0, n) : tsdf_evict<false>(where, t, keep, true, nullptr, 0, n);
+    return t->gray ? tsdf_evict<true>(where, t, keep, {true, nullptr, 0, n}) : tsdf_evict<false>(where, t, keep, {true, nullptr, 0, n});
 }
 extern "C" int viso_tsdf_evict(viso_tsdf* t, const viso_voxel_box* keep, viso_tsdf_entry* evicted_out, size_t n_cap, size_t* n) {
     if (!tsdf_kind_ok("viso_tsdf_evict", t, false)) return VISO_ERR_ARG;
-    return tsdf_evict<false>("viso_tsdf_evict", t, keep, false, evicted_out, n_cap, n);
+    return tsdf_evict<false>("viso_tsdf_evict", t, keep, {false, evicted_out, n_cap, n});
 }
 extern "C" int viso_tsdf_evict_gray(viso_tsdf* t, const viso_voxel_box* keep, viso_tsdf_gray_entry* evicted_out, size_t n_cap, size_t* n) {
     if (!tsdf_kind_ok("viso_tsdf_evict_gray", t, true)) return VISO_ERR_ARG;
-    return tsdf_evict<true>("viso_tsdf_evict_gray", t, keep, false, evicted_out, n_cap, n);
+    return tsdf_evict<true>("viso_tsdf_evict_gray", t, keep, {false, evicted_out, n_cap, n});
 }
 
 // the count or the sorted list of the crossings between voxels of at least min_weight updates
-static int tsdf_crossings(const char* where, viso_tsdf* t, uint32_t min_weight, bool count_only, viso_tsdf_crossing* out, size_t n_cap, size_t* n) {
-    return voxel_extract<viso_tsdf_crossing>(where, g_tsdfs, t, min_weight, count_only, out, n_cap, n,
+static int tsdf_crossings(const char* where, viso_tsdf* t, uint32_t min_weight, const VoxelList<viso_tsdf_crossing>& list) {
+    return voxel_extract<viso_tsdf_crossing>(where, g_tsdfs, t, min_weight, list,
                                              [=](viso_tsdf_crossing* d_out, unsigned long long out_cap, hipStream_t s) {
         hipLaunchKernelGGL(tsdf_crossings_kernel, tsdf_slot_grid(t), dim3(256), 0, s, t->t, min_weight, d_out, out_cap);
     });
 }
 extern "C" int viso_tsdf_surface_count(viso_tsdf* t, uint32_t min_weight, size_t* n) {
-    return tsdf_crossings("viso_tsdf_surface_count", t, min_weight, true, nullptr, 0, n);
+    return tsdf_crossings("viso_tsdf_surface_count", t, min_weight, {true, nullptr, 0, n});
 }
 extern "C" int viso_tsdf_surface(viso_tsdf* t, uint32_t min_weight, viso_tsdf_crossing* crossings_out, size_t n_cap, size_t* n) {
-    return tsdf_crossings("viso_tsdf_surface", t, min_weight, false, crossings_out, n_cap, n);
+    return tsdf_crossings("viso_tsdf_surface", t, min_weight, {false, crossings_out, n_cap, n});
 }
 
 // One pass of the mesh extraction: the numbers of vertex records and of triangles, both lists written when `verts` is set
@@ -838,10 +836,11 @@ static int tsdf_mesh_lists(const char* where, viso_tsdf* t, uint32_t min_weight,
     return VISO_OK;
 }
 
-static int tsdf_mesh_extract(const char* where, viso_tsdf* t, uint32_t min_weight, bool count_only, viso_tsdf_mesh_vertex* vertices_out,
-                             size_t nv_cap, viso_tsdf_triangle* triangles_out, size_t nt_cap, size_t* n_vertices, size_t* n_triangles) {
+// viso_tsdf_mesh_count (both lists count_only) and viso_tsdf_mesh
+static int tsdf_mesh_extract(const char* where, viso_tsdf* t, uint32_t min_weight, const VoxelList<viso_tsdf_mesh_vertex>& v,
+                             const VoxelList<viso_tsdf_triangle>& tr) {
     if (!voxel_known(g_tsdfs, t)) { viso_set_error("%s: not a live TSDF handle", where); return VISO_ERR_ARG; }
-    if (!n_vertices || !n_triangles || min_weight < 1 || (!count_only && ((nv_cap && !vertices_out) || (nt_cap && !triangles_out)))) {
+    if (!v.n || !tr.n || min_weight < 1 || (!v.count_only && ((v.cap && !v.out) || (tr.cap && !tr.out)))) {
         viso_set_error("%s: bad argument (min_weight >= 1, non-null outputs)", where);
         return VISO_ERR_ARG;
     }
@@ -855,62 +854,68 @@ static int tsdf_mesh_extract(const char* where, viso_tsdf* t, uint32_t min_weigh
         if (h->overflowed) return voxel_refuse_overflowed(where, h);
         if ((r = tsdf_mesh_lists(where, t, min_weight, verts, tris)) < 0) return r;
     }
-    *n_vertices = verts.size();
-    *n_triangles = tris.size();
-    if (count_only) return VISO_OK;
-    if (verts.size() > nv_cap || tris.size() > nt_cap) {
-        viso_set_error("%s: %zu vertices and %zu triangles do not fit the %zu and %zu given", where, verts.size(), tris.size(), nv_cap, nt_cap);
+    *v.n = verts.size();
+    *tr.n = tris.size();
+    if (v.count_only) return VISO_OK;
+    if (verts.size() > v.cap || tris.size() > tr.cap) {
+        viso_set_error("%s: %zu vertices and %zu triangles do not fit the %zu and %zu given", where, verts.size(), tris.size(), v.cap, tr.cap);
         return VISO_ERR_ARG;
     }
-    std::copy(verts.begin(), verts.end(), vertices_out);
-    std::copy(tris.begin(), tris.end(), triangles_out);
+    std::copy(verts.begin(), verts.end(), v.out);
+    std::copy(tris.begin(), tris.end(), tr.out);
     return VISO_OK;
 }
 
 extern "C" int viso_tsdf_mesh_count(viso_tsdf* t, uint32_t min_weight, size_t* n_vertices, size_t* n_triangles) {
-    return tsdf_mesh_extract("viso_tsdf_mesh_count", t, min_weight, true, nullptr, 0, nullptr, 0, n_vertices, n_triangles);
+    return tsdf_mesh_extract("viso_tsdf_mesh_count", t, min_weight, {true, nullptr, 0, n_vertices}, {true, nullptr, 0, n_triangles});
 }
 extern "C" int viso_tsdf_mesh(viso_tsdf* t, uint32_t min_weight, viso_tsdf_mesh_vertex* vertices_out, size_t nv_cap,
                               viso_tsdf_triangle* triangles_out, size_t nt_cap, size_t* n_vertices, size_t* n_triangles) {
-    return tsdf_mesh_extract("viso_tsdf_mesh", t, min_weight, false, vertices_out, nv_cap, triangles_out, nt_cap, n_vertices, n_triangles);
+    return tsdf_mesh_extract("viso_tsdf_mesh", t, min_weight, {false, vertices_out, nv_cap, n_vertices}, {false, triangles_out, nt_cap, n_triangles});
 }
 
-// viso_tsdf_render (gray_out null) and viso_tsdf_render_gray
-static int tsdf_render(const char* where, viso_tsdf* t, uint32_t min_weight, const viso_param* param, int rows, int cols, double max_depth,
-                       const double* poses_or_null, int n_views, int16_t* disp_out, uint32_t* weight_out_or_null, bool gray, uint8_t* gray_out) {
+// the views a render is asked for, and where they go
+struct TsdfRenderCall {
+    uint32_t min_weight; const viso_param* param; int rows, cols; double max_depth;
+    const double* poses_or_null; int n_views;
+    VoxelRenderOut out;
+};
+
+// viso_tsdf_render (out.gray null) and viso_tsdf_render_gray
+static int tsdf_render(const char* where, viso_tsdf* t, bool gray, const TsdfRenderCall& c) {
     // what does not need the map first, so that nothing of a wrong call reaches a handle
-    if (min_weight < 1 || (gray && !gray_out) || !param || !disp_out || rows < 1 || cols < 1 || n_views < 1 || (!poses_or_null && n_views != 1) ||
-        !(std::isfinite(max_depth) && max_depth > 0.0)) {
+    if (c.min_weight < 1 || (gray && !c.out.gray) || !c.param || !c.out.disp || c.rows < 1 || c.cols < 1 || c.n_views < 1 ||
+        (!c.poses_or_null && c.n_views != 1) || !(std::isfinite(c.max_depth) && c.max_depth > 0.0)) {
         viso_set_error("%s: bad argument (min_weight >= 1, non-null calibration and output, sizes >= 1, a finite max_depth > 0, n_views >= 1 "
                        "and 1 without poses)", where);
         return VISO_ERR_ARG;
     }
-    if (!(std::isfinite(param->f) && std::isfinite(param->cu) && std::isfinite(param->cv) && std::isfinite(param->base) && param->f > 0.0 &&
-          param->base > 0.0)) {
+    if (!(std::isfinite(c.param->f) && std::isfinite(c.param->cu) && std::isfinite(c.param->cv) && std::isfinite(c.param->base) && c.param->f > 0.0 &&
+          c.param->base > 0.0)) {
         viso_set_error("%s: bad argument (the calibration f, cu, cv, base must be finite, f > 0 and base > 0)", where);
         return VISO_ERR_ARG;
     }
-    if ((long long)rows * cols > VOXEL_MAX_PIXELS) { viso_set_error("%s: bad argument (a %d x %d view is beyond 2^31 - 1 pixels)", where, rows, cols); return VISO_ERR_ARG; }
-    if (poses_or_null) {
-        for (size_t i = 0; i < (size_t)n_views * 16; ++i) {
-            if (!std::isfinite(poses_or_null[i])) { viso_set_error("%s: bad argument (pose %zu has an entry that is not finite)", where, i / 16); return VISO_ERR_ARG; }
+    if ((long long)c.rows * c.cols > VOXEL_MAX_PIXELS) { viso_set_error("%s: bad argument (a %d x %d view is beyond 2^31 - 1 pixels)", where, c.rows, c.cols); return VISO_ERR_ARG; }
+    if (c.poses_or_null) {
+        for (size_t i = 0; i < (size_t)c.n_views * 16; ++i) {
+            if (!std::isfinite(c.poses_or_null[i])) { viso_set_error("%s: bad argument (pose %zu has an entry that is not finite)", where, i / 16); return VISO_ERR_ARG; }
         }
     }
     if (gray ? !tsdf_kind_ok(where, t, true) : !voxel_known(g_tsdfs, t)) {
         if (!gray) viso_set_error("%s: not a live TSDF handle", where);
         return VISO_ERR_ARG;
     }
-    const double steps = floor(max_depth / t->hs);
+    const double steps = floor(c.max_depth / t->hs);
     if (!(steps >= 1.0 && steps <= 65536.0)) {
-        viso_set_error("%s: bad argument (max_depth %g is %g steps of half a voxel: 1 .. 65536)", where, max_depth, steps);
+        viso_set_error("%s: bad argument (max_depth %g is %g steps of half a voxel: 1 .. 65536)", where, c.max_depth, steps);
         return VISO_ERR_ARG;
     }
     TsdfRenderArgs a;
     a.t = t->t;
-    a.rows = rows; a.cols = cols; a.n_samples = (int)steps; a.min_weight = min_weight;
-    a.f = param->f; a.cu = param->cu; a.cv = param->cv; a.base = param->base; a.s = t->s; a.h = t->hs;
+    a.rows = c.rows; a.cols = c.cols; a.n_samples = (int)steps; a.min_weight = c.min_weight;
+    a.f = c.param->f; a.cu = c.param->cu; a.cv = c.param->cv; a.base = c.param->base; a.s = t->s; a.h = t->hs;
     const unsigned long long* table_gray = t->gray;
-    return voxel_render(where, g_tsdfs, t, (size_t)rows * cols, poses_or_null, n_views, disp_out, weight_out_or_null,
+    return voxel_render(where, g_tsdfs, t, (size_t)c.rows * c.cols, c.poses_or_null, c.n_views, c.out,
                         [a, table_gray](const double* d_poses, int16_t* d_disp, uint32_t* d_weight, uint8_t* d_gray, dim3 grid, hipStream_t s) {
         TsdfRenderArgs g = a;
         g.poses = d_poses; g.disp = d_disp; g.weight = d_weight;
@@ -921,18 +926,18 @@ static int tsdf_render(const char* where, viso_tsdf* t, uint32_t min_weight, con
         } else {
             hipLaunchKernelGGL(tsdf_render_kernel, grid, dim3(256), 0, s, g);
         }
-    }, gray_out);
+    });
 }
 
 extern "C" int viso_tsdf_render(viso_tsdf* t, uint32_t min_weight, const viso_param* param, int rows, int cols, double max_depth,
                                 const double* poses_or_null, int n_views, int16_t* disp_out, uint32_t* weight_out_or_null) {
-    return tsdf_render("viso_tsdf_render", t, min_weight, param, rows, cols, max_depth, poses_or_null, n_views, disp_out, weight_out_or_null,
-                       false, nullptr);
+    return tsdf_render("viso_tsdf_render", t, false,
+                       {min_weight, param, rows, cols, max_depth, poses_or_null, n_views, {disp_out, weight_out_or_null, nullptr}});
 }
 extern "C" int viso_tsdf_render_gray(viso_tsdf* t, uint32_t min_weight, const viso_param* param, int rows, int cols, double max_depth,
                                      const double* poses_or_null, int n_views, int16_t* disp_out, uint32_t* weight_out_or_null, uint8_t* gray_out) {
-    return tsdf_render("viso_tsdf_render_gray", t, min_weight, param, rows, cols, max_depth, poses_or_null, n_views, disp_out,
-                       weight_out_or_null, true, gray_out);
+    return tsdf_render("viso_tsdf_render_gray", t, true,
+                       {min_weight, param, rows, cols, max_depth, poses_or_null, n_views, {disp_out, weight_out_or_null, gray_out}});
 }
 
 extern "C" int viso_tsdf_vertex_gray(viso_tsdf* t, const viso_tsdf_mesh_vertex* vertices, size_t n, uint8_t* gray_out, size_t* n_missing_or_null) {

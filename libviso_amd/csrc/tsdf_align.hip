@@ -227,28 +227,6 @@ __device__ __forceinline__ void tsdf_linearize_body(const TsdfAlignArgs& a, cons
         }
     }
     // the wave's totals to lane 63, the four waves' through LDS, the workgroup's with one atomic a word
-#ifdef VISO_ALIGN_WAVE_ATOMICS   // the variant that lost: every wave adds its own totals, no LDS
-    unsigned long long* out = a.out + (size_t)fr * WORDS;
-#pragma unroll
-    for (int k = 0; k < 28; ++k) {
-        const unsigned long long v = viso_wave_sum63((unsigned long long)N[k]);
-        if (lane == 63 && v) atomicAdd(out + k, v);
-    }
-    if (lane == 63) {
-        const unsigned long long c[6] = {n_points, n_used, n_missing, n_gated, n_clipped, n_oor};
-#pragma unroll
-        for (int k = 0; k < 6; ++k) if (c[k]) atomicAdd(out + 28 + k, c[k]);
-    }
-    if (GRAY) {
-        const unsigned long long v = viso_wave_sum63((unsigned long long)P);
-        if (lane == 63) {
-            const unsigned long long c[4] = {v, n_photo_used, n_photo_gated, n_photo_clipped};
-#pragma unroll
-            for (int k = 0; k < 4; ++k) if (c[k]) atomicAdd(out + 34 + k, c[k]);
-        }
-    }
-    (void)part; (void)wave;
-#else
 #pragma unroll
     for (int k = 0; k < 28; ++k) {
         const unsigned long long v = viso_wave_sum63((unsigned long long)N[k]);
@@ -269,7 +247,6 @@ __device__ __forceinline__ void tsdf_linearize_body(const TsdfAlignArgs& a, cons
         const unsigned long long v = (part[0][threadIdx.x] + part[1][threadIdx.x]) + (part[2][threadIdx.x] + part[3][threadIdx.x]);
         if (v) atomicAdd(a.out + (size_t)fr * WORDS + threadIdx.x, v);
     }
-#endif
 }
 
 __global__ __launch_bounds__(256) void tsdf_linearize_kernel(TsdfAlignArgs a) { tsdf_linearize_body<false>(a, nullptr, nullptr, 0, 0.0, 0.0); }
@@ -290,50 +267,69 @@ static bool align_params_ok(const viso_tsdf_align_params* p) {
            std::isfinite(p->eps_rot) && p->eps_rot >= 0.0 && std::isfinite(p->eps_trans) && p->eps_trans >= 0.0 && p->min_pixels >= 6;
 }
 
-// What does not need the map, first, so that nothing of a wrong call reaches a handle.  poses: [n][16] or null.
-static int align_check(const char* where, const viso_tsdf_align_params* p, int rows, int cols, double f, double cu, double cv, double base,
-                       const double* poses, int n) {
+// What does not need the map, first, so that nothing of a wrong call reaches a handle.  Not the fuse's check (voxel_host.hip): an
+// alignment weighs a row by f base / Z^2, so f and base must be positive as well as finite; its int64 sums of up to two products
+// below 2^40 a pixel stay below 2^63 for at most 2^22 pixels, a limit of the definition (include/viso_hip.h), so a larger map is
+// a wrong argument, not an unsupported one.
+static int align_check(const char* where, const viso_tsdf_align_params* p, const DispView& v) {
     if (!align_params_ok(p)) {
         viso_set_error("%s: bad argument (parameters: min_weight >= 1, a finite gate_voxels > 0, max_iters in 1..50, finite eps_rot and "
                        "eps_trans >= 0, min_pixels >= 6)", where);
         return VISO_ERR_ARG;
     }
-    if (rows < 1 || cols < 1 || (long long)rows * cols > ALIGN_MAX_PIXELS) {
-        viso_set_error("%s: bad argument (a %d x %d map: sizes >= 1 and at most 2^22 pixels)", where, rows, cols);
+    if (v.rows < 1 || v.cols < 1 || (long long)v.rows * v.cols > ALIGN_MAX_PIXELS) {
+        viso_set_error("%s: bad argument (a %d x %d map: sizes >= 1 and at most 2^22 pixels)", where, v.rows, v.cols);
         return VISO_ERR_ARG;
     }
-    if (!(std::isfinite(f) && std::isfinite(cu) && std::isfinite(cv) && std::isfinite(base) && f > 0.0 && base > 0.0)) {
+    const StereoCalib& c = v.cal;
+    if (!(std::isfinite(c.f) && std::isfinite(c.cu) && std::isfinite(c.cv) && std::isfinite(c.base) && c.f > 0.0 && c.base > 0.0)) {
         viso_set_error("%s: bad argument (the calibration f, cu, cv, base must be finite, f > 0 and base > 0)", where);
         return VISO_ERR_ARG;
     }
-    if (poses) {
-        for (int k = 0; k < n; ++k) {
+    if (v.poses) {
+        for (int k = 0; k < v.n; ++k) {
             for (int i = 0; i < 12; ++i) {
-                if (!std::isfinite(poses[(size_t)k * 16 + i])) { viso_set_error("%s: bad argument (pose %d has an entry that is not finite)", where, k); return VISO_ERR_ARG; }
+                if (!std::isfinite(v.poses[(size_t)k * 16 + i])) { viso_set_error("%s: bad argument (pose %d has an entry that is not finite)", where, k); return VISO_ERR_ARG; }
             }
         }
     }
     return VISO_OK;
 }
 
-// the photometric side of a call: null for a plain alignment
-struct AlignPhoto {
-    const viso_tsdf_align_gray_params* p;
-    const uint8_t* image; size_t ifs;        // frame f's image at image + f * ifs on the map's device, or
-    const uint8_t* host_image;               // one host image, staged like the map
-    viso_tsdf_normal_gray* linearize_out;
-    viso_tsdf_alignment_gray* records;
-    viso_tsdf_align_gray_step* trace;
+// What does not need the map, for the photometric alignment: the image, the photometric parameters, then align_check.
+static int align_gray_check(const char* where, const viso_tsdf_align_gray_params* p, const DispView& v) {
+    if (!p || !v.image) { viso_set_error("%s: bad argument (non-null parameters and image)", where); return VISO_ERR_ARG; }
+    if (!(std::isfinite(p->photo_weight) && p->photo_weight >= 0.0 && std::isfinite(p->photo_gate) && p->photo_gate > 0.0)) {
+        viso_set_error("%s: bad argument (parameters: a finite photo_weight >= 0 and a finite photo_gate > 0)", where);
+        return VISO_ERR_ARG;
+    }
+    return align_check(where, &p->geo, v);
+}
+
+void AlignPlain::launch(const TsdfAlignArgs& g, dim3 grid, hipStream_t s) { hipLaunchKernelGGL(tsdf_linearize_kernel, grid, dim3(256), 0, s, g); }
+void AlignGray::launch(const TsdfGrayAlignArgs& g, dim3 grid, hipStream_t s) { hipLaunchKernelGGL(tsdf_gray_linearize_kernel, grid, dim3(256), 0, s, g); }
+static TsdfAlignArgs& align_geo_args(TsdfAlignArgs& g) { return g; }
+static TsdfAlignArgs& align_geo_args(TsdfGrayAlignArgs& g) { return g.a; }
+
+// One call of kind K (alignmath.h): the maps, the parameters, and where the result goes.  linearize_out set: one linearise at the
+// view's poses and nothing else; otherwise one record a frame and, for frame 0, at most trace_cap entries of trace (or null).
+template <class K>
+struct AlignRequest {
+    DispView v;
+    const typename K::Params* p;
+    typename K::Normal* linearize_out;
+    typename K::Record* records; typename K::Step* trace; int trace_cap;
 };
 
-// The alignment of n device maps (frame f at disp + f * mfs, on the map's device) behind align_check: the handle entered and locked
-// like an extraction over all of its linearises.  ctx (or null): the context the maps live on, which must be the map's.
-// linearize_out set: one linearise at the guesses and nothing else.  photo set: the photometric alignment of a gray map, whose
-// outputs are photo's; the plain ones are null then.
-static int align_device(const char* where, viso_tsdf* t, viso_ctx* ctx, const viso_tsdf_align_params* p, const int16_t* disp, size_t mfs,
-                        const int16_t* host_disp, int rows, int cols, int n, double f, double cu, double cv, double base, const double* guesses,
-                        viso_tsdf_normal* linearize_out, viso_tsdf_alignment* records, viso_tsdf_align_step* trace, int trace_cap,
-                        const AlignPhoto* photo = nullptr) {
+// The alignment of a view's maps behind align_check: the handle entered and locked like an extraction over all of its linearises.
+// A resident view's context must be the map's; a host view's map (and image) goes through the fuse's staging.  AlignGray: the
+// photometric alignment of a gray map.
+template <class K>
+static int align_device(const char* where, viso_tsdf* t, const AlignRequest<K>& q) {
+    constexpr bool photo = K::words == ALIGN_GRAY_WORDS;
+    static_assert(AlignPlain::words == ALIGN_WORDS && AlignGray::words == ALIGN_GRAY_WORDS, "the kernels' words are the structs");
+    const DispView& v = q.v;
+    const viso_tsdf_align_params& p = K::geo(*q.p);
     VoxelRegistry& reg = tsdf_registry();
     if (!voxel_known(reg, t)) { viso_set_error("%s: not a live TSDF handle", where); return VISO_ERR_ARG; }
     if (photo && !tsdf_is_gray(t)) {   // before a device is touched
@@ -343,72 +339,57 @@ static int align_device(const char* where, viso_tsdf* t, viso_ctx* ctx, const vi
     int r;
     VoxelHost* h;
     if ((r = voxel_enter(where, reg, t, &h)) < 0) return r;
-    if (ctx && h->ctx != ctx) { viso_set_error("%s: the TSDF map and the batch must share a context", where); return VISO_ERR_ARG; }
+    if (v.ctx && h->ctx != v.ctx) { viso_set_error("%s: the TSDF map and the batch must share a context", where); return VISO_ERR_ARG; }
     TsdfView view;
     tsdf_view(t, &view);
-    if (p->gate_voxels > (double)view.trunc_voxels) {
-        viso_set_error("%s: bad argument (gate_voxels %g is beyond the map's truncation of %d voxels)", where, p->gate_voxels, view.trunc_voxels);
+    if (p.gate_voxels > (double)view.trunc_voxels) {
+        viso_set_error("%s: bad argument (gate_voxels %g is beyond the map's truncation of %d voxels)", where, p.gate_voxels, view.trunc_voxels);
         return VISO_ERR_ARG;
     }
     std::lock_guard<std::mutex> lk(h->mu);
     if (h->overflowed) return voxel_refuse_overflowed(where, h);
-    const size_t px = (size_t)rows * cols;
-    if (host_disp) {   // one host map through the fuse's staging
-        if ((r = voxel_stage_map(where, h, host_disp, px, &disp)) < 0) return r;
-        mfs = px;
-    }
-    const uint8_t* image = photo ? photo->image : nullptr;
-    size_t ifs = photo ? photo->ifs : 0;
-    if (photo && photo->host_image) {
-        if ((r = voxel_stage_image(where, h, photo->host_image, px, &image)) < 0) return r;
-        ifs = px;
+    const size_t px = v.px();
+    const int16_t* disp = v.disp;
+    const uint8_t* image = v.image;
+    if (!v.ctx) {
+        if ((r = voxel_stage_map(where, h, v.disp, px, &disp)) < 0) return r;
+        if (v.image && (r = voxel_stage_image(where, h, v.image, px, &image)) < 0) return r;
     }
     TsdfAlignArgs a;
-    a.v.mfs = mfs; a.v.rows = rows; a.v.cols = cols; a.v.min_disp16 = h->min_disp16; a.v._pad = 0;
-    a.v.f = f; a.v.cu = cu; a.v.cv = cv; a.v.base = base;
+    a.v.mfs = v.mfs; a.v.rows = v.rows; a.v.cols = v.cols; a.v.min_disp16 = h->min_disp16; a.v._pad = 0;
+    a.v.f = v.cal.f; a.v.cu = v.cal.cu; a.v.cv = v.cal.cv; a.v.base = v.cal.base;
     a.t = view.t;
-    a.voxel = view.voxel; a.s = view.s; a.gate = p->gate_voxels * 1024.0; a.min_weight = p->min_weight;
+    a.voxel = view.voxel; a.s = view.s; a.gate = p.gate_voxels * 1024.0; a.min_weight = p.min_weight;
     const size_t blocks = (px + 255) / 256;
     const unsigned blocks_x = blocks < ALIGN_BLOCKS ? (unsigned)blocks : ALIGN_BLOCKS;
     a.trips = (int)((px + (size_t)blocks_x * 256 - 1) / ((size_t)blocks_x * 256));
-    static_assert(sizeof(viso_tsdf_normal) == ALIGN_WORDS * sizeof(unsigned long long), "the kernel's words are the struct");
-    static_assert(sizeof(viso_tsdf_normal_gray) == ALIGN_GRAY_WORDS * sizeof(unsigned long long), "the gray kernel's words are the struct");
-    static const double eye[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-    const unsigned long long one = 1ull;
-    if (photo) {
-        const AlignLinearizeGray linearize = [&](const double* poses, const unsigned long long* active, viso_tsdf_normal_gray* out) {
-            return voxel_linearize(where, h, poses, active, n, ALIGN_GRAY_WORDS, blocks_x, reinterpret_cast<unsigned long long*>(out),
-                                   [&](const double* d_poses, const unsigned long long* d_active, unsigned long long* d_out, int frame0, dim3 grid, hipStream_t st) {
-                TsdfGrayAlignArgs g;
-                g.a = a;
-                g.a.v.disp = disp + (size_t)frame0 * mfs; g.a.v.poses = d_poses; g.a.active = d_active; g.a.out = d_out;
-                g.gray = view.gray; g.image = image + (size_t)frame0 * ifs; g.ifs = ifs;
-                g.lambda = photo->p->photo_weight; g.photo_gate = photo->p->photo_gate;
-                hipLaunchKernelGGL(tsdf_gray_linearize_kernel, grid, dim3(256), 0, st, g);
-            });
-        };
-        if (photo->linearize_out) return linearize(guesses ? guesses : eye, &one, photo->linearize_out);
-        return align_run_gray(*photo->p, n, guesses, linearize, photo->records, photo->trace, trace_cap);
-    }
-    const AlignLinearize linearize = [&](const double* poses, const unsigned long long* active, viso_tsdf_normal* out) {
-        return voxel_linearize(where, h, poses, active, n, ALIGN_WORDS, blocks_x, reinterpret_cast<unsigned long long*>(out),
-                               [&](const double* d_poses, const unsigned long long* d_active, unsigned long long* d_out, int frame0, dim3 grid, hipStream_t st) {
-            TsdfAlignArgs g = a;
-            g.v.disp = disp + (size_t)frame0 * mfs; g.v.poses = d_poses; g.active = d_active; g.out = d_out;
-            hipLaunchKernelGGL(tsdf_linearize_kernel, grid, dim3(256), 0, st, g);
+    const AlignLinearize<K> linearize = [&](const double* poses, const unsigned long long* active, typename K::Normal* out) {
+        return voxel_linearize(where, h, poses, active, v.n, K::words, reinterpret_cast<unsigned long long*>(out),
+                               [&](const double* d_poses, const unsigned long long* d_active, unsigned long long* d_out, int frame0, unsigned frames, hipStream_t st) {
+            typename K::Args g;
+            TsdfAlignArgs& ga = align_geo_args(g);
+            ga = a;
+            ga.v.disp = disp + (size_t)frame0 * v.mfs; ga.v.poses = d_poses; ga.active = d_active; ga.out = d_out;
+            if constexpr (photo) {
+                g.gray = view.gray; g.image = image + (size_t)frame0 * v.ifs; g.ifs = v.ifs;
+                g.lambda = q.p->photo_weight; g.photo_gate = q.p->photo_gate;
+            }
+            K::launch(g, dim3(blocks_x, frames), st);
         });
     };
-    if (linearize_out) return linearize(guesses ? guesses : eye, &one, linearize_out);
-    return align_run(*p, n, guesses, linearize, records, trace, trace_cap);
+    static const double eye[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    const unsigned long long one = 1ull;
+    if (q.linearize_out) return linearize(v.poses ? v.poses : eye, &one, q.linearize_out);
+    return align_run<K>(*q.p, v.n, v.poses, linearize, q.records, q.trace, q.trace_cap);
 }
 
 extern "C" int viso_tsdf_linearize(viso_tsdf* t, const viso_tsdf_align_params* params, const int16_t* disp, int rows, int cols,
                                    const viso_param* param, const double* pose_or_null, viso_tsdf_normal* out) {
     const char* where = "viso_tsdf_linearize";
     if (!disp || !param || !out) { viso_set_error("%s: bad argument (non-null map, calibration and output)", where); return VISO_ERR_ARG; }
-    VISO_TRY(align_check(where, params, rows, cols, param->f, param->cu, param->cv, param->base, pose_or_null, 1));
-    return align_device(where, t, nullptr, params, nullptr, 0, disp, rows, cols, 1, param->f, param->cu, param->cv, param->base, pose_or_null,
-                        out, nullptr, nullptr, 0);
+    const DispView v = disp_view_host(disp, nullptr, rows, cols, param, pose_or_null);
+    VISO_TRY(align_check(where, params, v));
+    return align_device<AlignPlain>(where, t, {v, params, out, nullptr, nullptr, 0});
 }
 
 extern "C" int viso_tsdf_align(viso_tsdf* t, const viso_tsdf_align_params* params, const int16_t* disp, int rows, int cols, const viso_param* param,
@@ -419,16 +400,14 @@ extern "C" int viso_tsdf_align(viso_tsdf* t, const viso_tsdf_align_params* param
         viso_set_error("%s: bad argument (non-null map, calibration and record, trace_cap >= 0 and 0 without a trace)", where);
         return VISO_ERR_ARG;
     }
-    VISO_TRY(align_check(where, params, rows, cols, param->f, param->cu, param->cv, param->base, pose_guess_or_null, 1));
-    return align_device(where, t, nullptr, params, nullptr, 0, disp, rows, cols, 1, param->f, param->cu, param->cv, param->base,
-                        pose_guess_or_null, nullptr, record_out, trace_out_or_null, trace_cap);
+    const DispView v = disp_view_host(disp, nullptr, rows, cols, param, pose_guess_or_null);
+    VISO_TRY(align_check(where, params, v));
+    return align_device<AlignPlain>(where, t, {v, params, nullptr, record_out, trace_out_or_null, trace_cap});
 }
 
-int tsdf_align_resident(const char* where, viso_tsdf* t, viso_ctx* c, const int16_t* disp, size_t mfs, int rows, int cols, int n_frames,
-                        double f, double cu, double cv, double base, const double* poses, const viso_tsdf_align_params* params,
-                        viso_tsdf_alignment* records) {
-    VISO_TRY(align_check(where, params, rows, cols, f, cu, cv, base, poses, n_frames));
-    return align_device(where, t, c, params, disp, mfs, nullptr, rows, cols, n_frames, f, cu, cv, base, poses, nullptr, records, nullptr, 0);
+int tsdf_align_resident(const char* where, viso_tsdf* t, const DispView& v, const viso_tsdf_align_params* params, viso_tsdf_alignment* records) {
+    VISO_TRY(align_check(where, params, v));
+    return align_device<AlignPlain>(where, t, {v, params, nullptr, records, nullptr, 0});
 }
 
 // ---- the photometric alignment (include/viso_hip.h, "TSDF photometric align") ----------------------------------------------------------
@@ -439,25 +418,13 @@ extern "C" void viso_tsdf_align_gray_params_default(viso_tsdf_align_gray_params*
     p->photo_weight = 1.0 / 32.0; p->photo_gate = 255.0;
 }
 
-// What does not need the map: the image, the photometric parameters, then align_check.
-static int align_gray_check(const char* where, const viso_tsdf_align_gray_params* p, bool image, int rows, int cols, double f, double cu, double cv,
-                            double base, const double* poses, int n) {
-    if (!p || !image) { viso_set_error("%s: bad argument (non-null parameters and image)", where); return VISO_ERR_ARG; }
-    if (!(std::isfinite(p->photo_weight) && p->photo_weight >= 0.0 && std::isfinite(p->photo_gate) && p->photo_gate > 0.0)) {
-        viso_set_error("%s: bad argument (parameters: a finite photo_weight >= 0 and a finite photo_gate > 0)", where);
-        return VISO_ERR_ARG;
-    }
-    return align_check(where, &p->geo, rows, cols, f, cu, cv, base, poses, n);
-}
-
 extern "C" int viso_tsdf_linearize_gray(viso_tsdf* t, const viso_tsdf_align_gray_params* params, const int16_t* disp, const uint8_t* image, int rows,
                                         int cols, const viso_param* param, const double* pose_or_null, viso_tsdf_normal_gray* out) {
     const char* where = "viso_tsdf_linearize_gray";
     if (!disp || !param || !out) { viso_set_error("%s: bad argument (non-null map, calibration and output)", where); return VISO_ERR_ARG; }
-    VISO_TRY(align_gray_check(where, params, image != nullptr, rows, cols, param->f, param->cu, param->cv, param->base, pose_or_null, 1));
-    const AlignPhoto photo = {params, nullptr, 0, image, out, nullptr, nullptr};
-    return align_device(where, t, nullptr, &params->geo, nullptr, 0, disp, rows, cols, 1, param->f, param->cu, param->cv, param->base, pose_or_null,
-                        nullptr, nullptr, nullptr, 0, &photo);
+    const DispView v = disp_view_host(disp, image, rows, cols, param, pose_or_null);
+    VISO_TRY(align_gray_check(where, params, v));
+    return align_device<AlignGray>(where, t, {v, params, out, nullptr, nullptr, 0});
 }
 
 extern "C" int viso_tsdf_align_gray(viso_tsdf* t, const viso_tsdf_align_gray_params* params, const int16_t* disp, const uint8_t* image, int rows,
@@ -468,17 +435,13 @@ extern "C" int viso_tsdf_align_gray(viso_tsdf* t, const viso_tsdf_align_gray_par
         viso_set_error("%s: bad argument (non-null map, calibration and record, trace_cap >= 0 and 0 without a trace)", where);
         return VISO_ERR_ARG;
     }
-    VISO_TRY(align_gray_check(where, params, image != nullptr, rows, cols, param->f, param->cu, param->cv, param->base, pose_guess_or_null, 1));
-    const AlignPhoto photo = {params, nullptr, 0, image, nullptr, record_out, trace_out_or_null};
-    return align_device(where, t, nullptr, &params->geo, nullptr, 0, disp, rows, cols, 1, param->f, param->cu, param->cv, param->base,
-                        pose_guess_or_null, nullptr, nullptr, nullptr, trace_cap, &photo);
+    const DispView v = disp_view_host(disp, image, rows, cols, param, pose_guess_or_null);
+    VISO_TRY(align_gray_check(where, params, v));
+    return align_device<AlignGray>(where, t, {v, params, nullptr, record_out, trace_out_or_null, trace_cap});
 }
 
-int tsdf_align_gray_resident(const char* where, viso_tsdf* t, viso_ctx* c, const int16_t* disp, size_t mfs, const uint8_t* image, size_t ifs, int rows,
-                             int cols, int n_frames, double f, double cu, double cv, double base, const double* poses,
-                             const viso_tsdf_align_gray_params* params, viso_tsdf_alignment_gray* records) {
-    VISO_TRY(align_gray_check(where, params, image != nullptr, rows, cols, f, cu, cv, base, poses, n_frames));
-    const AlignPhoto photo = {params, image, ifs, nullptr, nullptr, records, nullptr};
-    return align_device(where, t, c, &params->geo, disp, mfs, nullptr, rows, cols, n_frames, f, cu, cv, base, poses, nullptr, nullptr, nullptr, 0,
-                        &photo);
+int tsdf_align_gray_resident(const char* where, viso_tsdf* t, const DispView& v, const viso_tsdf_align_gray_params* params,
+                             viso_tsdf_alignment_gray* records) {
+    VISO_TRY(align_gray_check(where, params, v));
+    return align_device<AlignGray>(where, t, {v, params, nullptr, records, nullptr, 0});
 }

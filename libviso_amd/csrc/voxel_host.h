@@ -47,9 +47,15 @@ using VoxelLaunch = std::function<void(hipStream_t)>;                           
 using VoxelFuseLaunch = std::function<void(const VoxelFuseArgs&, const uint8_t* d_image, dim3 grid, hipStream_t)>;
 // one group of views; d_gray: the group's part of the third output, or null when the call has none
 using VoxelRenderLaunch = std::function<void(const double* d_poses, int16_t* d_disp, uint32_t* d_weight, uint8_t* d_gray, dim3 grid, hipStream_t)>;
-// one group of frames of a linearise: the group's poses [.][12], its flags and its part of the sums, the group's first frame
+// one group of `frames` frames of a linearise: the group's poses [.][12], its flags and its part of the sums, the group's first
+// frame; the grid is the caller's, with the group's frames along y
 using VoxelLinearizeLaunch = std::function<void(const double* d_poses, const unsigned long long* d_active, unsigned long long* d_out, int frame0,
-                                                dim3 grid, hipStream_t)>;
+                                                unsigned frames, hipStream_t)>;
+// what a render writes on the host: n_views maps, with `weight` set as many weights, with `gray` set as many intensities
+struct VoxelRenderOut { int16_t* disp; uint32_t* weight; uint8_t* gray; };
+// where a count or a list goes: *n the number of items; count_only: nothing else, otherwise the items to out[0 .. cap)
+template <class Item>
+struct VoxelList { bool count_only; Item* out; size_t cap; size_t* n; };
 
 // the launches of voxel_hash.h's kernels over the payload p of a kind: one thread per slot / per entry
 template <class P>
@@ -78,15 +84,10 @@ bool voxel_unregister(const char* where, VoxelRegistry& reg, const void* handle)
 int voxel_free(const char* where, VoxelHost* h);
 int voxel_clear(const char* where, VoxelRegistry& reg, const void* handle, const VoxelLaunch& clear);
 
-// map_fuse_resident / tsdf_fuse_resident (common.h) and viso_*_fuse, whole: the handle and argument checks, the staging of the
-// poses and of the host map, the groups of frames, each started by `launch`, and the wait that finds a full table.  image (or
-// null): frame f's 8-bit image at image + f * ifs on the device (resident), or one host image of the map's size that is staged like
-// the map (host); each group's launch is handed its first image.
-int voxel_fuse_resident(const char* where, VoxelRegistry& reg, const void* handle, viso_ctx* c, const int16_t* disp, size_t mfs, int rows,
-                        int cols, int n_frames, double f, double cu, double cv, double base, const double* poses, const VoxelFuseLaunch& launch,
-                        const uint8_t* image = nullptr, size_t ifs = 0);
-int voxel_fuse_host(const char* where, VoxelRegistry& reg, const void* handle, const int16_t* disp, int rows, int cols, const viso_param* param,
-                    const double* pose_or_null, const VoxelFuseLaunch& launch, const uint8_t* image = nullptr);
+// map_fuse_resident / tsdf_fuse_resident (common.h) and viso_*_fuse, whole, over the view v (common.h) of either kind: the handle
+// and argument checks, the staging of the poses and of a host view's map and image, the groups of frames, each started by `launch`
+// with its first image (or null), and the wait that finds a full table.
+int voxel_fuse(const char* where, VoxelRegistry& reg, const void* handle, const DispView& v, const VoxelFuseLaunch& launch);
 // behind a call's launches: waits for them and turns dropped points / updates into the overflow mark.  h is entered and locked.
 int voxel_finish(const char* where, VoxelHost* h);
 // viso_*_add_entries behind the handle check and the validation of the n entries
@@ -118,11 +119,11 @@ int voxel_add_entries(const char* where, VoxelRegistry& reg, const void* handle,
     return r;
 }
 // viso_*_render behind the handle and argument checks: the map entered, locked and not overflowed; the poses [n_views][16] (or
-// null) through d_pose; a device buffer for n_views maps of px int16 and, with weight_out, as many uint32, and, with gray_out, as
+// null) through d_pose; a device buffer for n_views maps of px int16 and, with out.weight, as many uint32, and, with out.gray, as
 // many uint8, freed on every path; the groups of views, each started by `launch` with its poses ([.][12] or null) and its part of
 // the buffer; the copies to the host.
-int voxel_render(const char* where, VoxelRegistry& reg, const void* handle, size_t px, const double* poses, int n_views, int16_t* disp_out,
-                 uint32_t* weight_out, const VoxelRenderLaunch& launch, uint8_t* gray_out = nullptr);
+int voxel_render(const char* where, VoxelRegistry& reg, const void* handle, size_t px, const double* poses, int n_views, const VoxelRenderOut& out,
+                 const VoxelRenderLaunch& launch);
 // A host map of px pixels into the fuse's staging d_disp (grow-only), on the stream; *d_disp: where it is.  h is entered and locked.
 int voxel_stage_map(const char* where, VoxelHost* h, const int16_t* disp, size_t px, const int16_t** d_disp);
 // The same for a host image of px bytes into d_image (grow-only): the image of a photometric linearise.
@@ -130,24 +131,24 @@ int voxel_stage_image(const char* where, VoxelHost* h, const uint8_t* image, siz
 // One linearise of an alignment (include/viso_hip.h, "TSDF align") for n frames: h is entered, locked and not overflowed (the
 // caller holds the lock over the whole alignment).  The poses [n][16] as [n][12], the flags active [n] (0: the frame's lanes
 // leave at once) and `words` zeroed 64-bit sums a frame go through d_pose (grow-only), the groups of frames are started by `launch`
-// with blocks_x blocks along x, and the sums come back to out [n][words].
+// and the sums come back to out [n][words].
 int voxel_linearize(const char* where, VoxelHost* h, const double* poses, const unsigned long long* active, int n, size_t words,
-                    unsigned blocks_x, unsigned long long* out, const VoxelLinearizeLaunch& launch);
+                    unsigned long long* out, const VoxelLinearizeLaunch& launch);
 // viso_*_stats: the four counters summed over the sets (VOXEL_ST_*) and the dropped word
 int voxel_stats(const char* where, VoxelRegistry& reg, const void* handle, const void* out, unsigned long long sums[4], unsigned long long* dropped);
 
 // One pass of an extraction over the slots: VOXEL_W_OUT zeroed, the launch, the list's length.  h is entered and locked.
 int voxel_pass(VoxelHost* h, const VoxelLaunch& launch, unsigned long long* n);
 
-// The count (count_only) or the sorted list of an extraction: a first pass for the number, a second one into a list of that size.
+// The count (list.count_only) or the sorted list of an extraction: a first pass for the number, a second one into a list of that size.
 // launch(out, out_cap, stream) starts the kernel over the slots that lists the items (out == null: only counts them).  The list's
 // order is the kind's `bool voxel_item_less(const Item&, const Item&)`, declared before the call (an overload, so that the sort
 // inlines it).
 template <class Item>
-int voxel_extract(const char* where, VoxelRegistry& reg, const void* handle, uint32_t min, bool count_only, Item* items_out, size_t n_cap,
-                  size_t* n, const std::function<void(Item* out, unsigned long long out_cap, hipStream_t)>& launch) {
+int voxel_extract(const char* where, VoxelRegistry& reg, const void* handle, uint32_t min, const VoxelList<Item>& list,
+                  const std::function<void(Item* out, unsigned long long out_cap, hipStream_t)>& launch) {
     if (!voxel_known(reg, handle)) { viso_set_error("%s: not a live %s handle", where, reg.kind.handle); return VISO_ERR_ARG; }
-    if (!n || min < 1 || (!count_only && n_cap && !items_out)) {
+    if (!list.n || min < 1 || (!list.count_only && list.cap && !list.out)) {
         viso_set_error("%s: bad argument (%s >= 1, non-null outputs)", where, reg.kind.threshold);
         return VISO_ERR_ARG;
     }
@@ -158,9 +159,9 @@ int voxel_extract(const char* where, VoxelRegistry& reg, const void* handle, uin
     if (h->overflowed) return voxel_refuse_overflowed(where, h);
     unsigned long long c = 0, c2 = 0;
     if ((r = voxel_pass(h, [&](hipStream_t s) { launch(nullptr, 0, s); }, &c)) < 0) return r;
-    *n = (size_t)c;
-    if (count_only || !c) return VISO_OK;
-    if (c > n_cap) { viso_set_error("%s: %llu items do not fit the %zu given", where, c, n_cap); return VISO_ERR_ARG; }
+    *list.n = (size_t)c;
+    if (list.count_only || !c) return VISO_OK;
+    if (c > list.cap) { viso_set_error("%s: %llu items do not fit the %zu given", where, c, list.cap); return VISO_ERR_ARG; }
     Item* d = nullptr;
     if (hipMalloc((void**)&d, (size_t)c * sizeof(Item)) != hipSuccess) {
         (void)hipGetLastError();
@@ -169,21 +170,20 @@ int voxel_extract(const char* where, VoxelRegistry& reg, const void* handle, uin
     }
     r = voxel_pass(h, [&](hipStream_t s) { launch(d, c, s); }, &c2);
     hipError_t e = hipSuccess;
-    if (r >= 0) e = hipMemcpy(items_out, d, (size_t)c * sizeof(Item), hipMemcpyDeviceToHost);
+    if (r >= 0) e = hipMemcpy(list.out, d, (size_t)c * sizeof(Item), hipMemcpyDeviceToHost);
     (void)hipFree(d);   // on every path
     if (r < 0) return r;
     HIP_TRY(e);
     if (c2 != c) { viso_set_error("%s: the table changed between the two passes", where); return VISO_ERR_HIP; }   // (the map's lock rules it out)
-    std::sort(items_out, items_out + c, [](const Item& x, const Item& y) { return voxel_item_less(x, y); });
+    std::sort(list.out, list.out + c, [](const Item& x, const Item& y) { return voxel_item_less(x, y); });
     return VISO_OK;
 }
 
-// The count (count_only) or the sorted list of the voxels whose threshold word is at least `min`, as the payload p packs them:
+// The count (list.count_only) or the sorted list of the voxels whose threshold word is at least `min`, as the payload p packs them:
 // viso_*_count / viso_*_get, whole.  (p is the caller's own copy: the handle is not touched before the registry has answered.)
 template <class P>
-int voxel_entries(const char* where, VoxelRegistry& reg, const void* handle, uint32_t min, bool count_only, typename P::Entry* entries_out,
-                  size_t n_cap, size_t* n, const P& p) {
-    return voxel_extract<typename P::Entry>(where, reg, handle, min, count_only, entries_out, n_cap, n,
+int voxel_entries(const char* where, VoxelRegistry& reg, const void* handle, uint32_t min, const VoxelList<typename P::Entry>& list, const P& p) {
+    return voxel_extract<typename P::Entry>(where, reg, handle, min, list,
                                             [p, min](typename P::Entry* out, unsigned long long out_cap, hipStream_t s) {
         hipLaunchKernelGGL(voxel_compact_kernel<P>, dim3((p.head().mask + 1u) / 256u), dim3(256), 0, s, p, min, out, out_cap);
     });
@@ -197,16 +197,16 @@ bool voxel_evict_args(const char* where, VoxelRegistry& reg, const void* handle,
 int voxel_evict_get_stats(VoxelHost* h, std::vector<unsigned long long>& stats, unsigned long long* occupied);
 int voxel_evict_put_stats(VoxelHost* h, std::vector<unsigned long long>& stats, unsigned long long less);
 
-// viso_*_evict_count (count_only) and viso_*_evict, whole.  A first pass counts the voxels outside the box; a second one lists them
-// (items_out null: lists nothing) and turns their keys into tombstones, the rebuild pass moves every survivor to where a probe
+// viso_*_evict_count (list.count_only) and viso_*_evict, whole.  A first pass counts the voxels outside the box; a second one lists them
+// (list.out null: lists nothing) and turns their keys into tombstones, the rebuild pass moves every survivor to where a probe
 // finds it, the sweep empties the tombstones; the occupied counter falls on the host.  Device memory: the list of the evicted.  A
 // table without an empty slot has no cluster head to start a rebuild from: it goes through a list of its survivors, the clear
 // and add_entries, and gets its statistics back.  The list's order is the kind's voxel_item_less, as in voxel_extract.
 template <class P>
-int voxel_evict(const char* where, VoxelRegistry& reg, const void* handle, const viso_voxel_box* keep, bool count_only,
-                typename P::Entry* items_out, size_t n_cap, size_t* n, const P& p) {
+int voxel_evict(const char* where, VoxelRegistry& reg, const void* handle, const viso_voxel_box* keep, const VoxelList<typename P::Entry>& list,
+                const P& p) {
     using Item = typename P::Entry;
-    if (!voxel_evict_args(where, reg, handle, keep, n)) return VISO_ERR_ARG;
+    if (!voxel_evict_args(where, reg, handle, keep, list.n)) return VISO_ERR_ARG;
     int r;
     VoxelHost* h;
     if ((r = voxel_enter(where, reg, handle, &h)) < 0) return r;
@@ -224,21 +224,21 @@ int voxel_evict(const char* where, VoxelRegistry& reg, const void* handle, const
     };
     unsigned long long c = 0, c2 = 0, occupied = 0;
     if ((r = voxel_pass(h, mark(VOXEL_EVICT_COUNT, nullptr, 0), &c)) < 0) return r;
-    *n = (size_t)c;
-    if (count_only || !c) return VISO_OK;
-    if (items_out && c > n_cap) { viso_set_error("%s: %llu items do not fit the %zu given", where, c, n_cap); return VISO_ERR_ARG; }
+    *list.n = (size_t)c;
+    if (list.count_only || !c) return VISO_OK;
+    if (list.out && c > list.cap) { viso_set_error("%s: %llu items do not fit the %zu given", where, c, list.cap); return VISO_ERR_ARG; }
     std::vector<unsigned long long> stats;
     if ((r = voxel_evict_get_stats(h, stats, &occupied)) < 0) return r;
     const bool full = occupied >= slots;
     const unsigned long long n_keep = full ? slots - c : 0;
-    const size_t b_out = items_out ? (size_t)c * sizeof(Item) : 0, b_keep = (size_t)n_keep * sizeof(Item);
+    const size_t b_out = list.out ? (size_t)c * sizeof(Item) : 0, b_keep = (size_t)n_keep * sizeof(Item);
     char* d = nullptr;   // the evicted | a full table's survivors
     if (b_out + b_keep && hipMalloc((void**)&d, b_out + b_keep) != hipSuccess) {
         (void)hipGetLastError();
         viso_set_error("%s: cannot allocate %zu bytes for the list", where, b_out + b_keep);
         return VISO_ERR_NOMEM;
     }
-    Item* d_out = items_out ? reinterpret_cast<Item*>(d) : nullptr;
+    Item* d_out = list.out ? reinterpret_cast<Item*>(d) : nullptr;
     Item* d_keep = reinterpret_cast<Item*>(d + b_out);
     hipStream_t s = h->ctx->stream;
     hipError_t e = hipSuccess;
@@ -262,14 +262,14 @@ int voxel_evict(const char* where, VoxelRegistry& reg, const void* handle, const
         }
     }
     if (r >= 0 && e == hipSuccess && c2 == c) r = voxel_evict_put_stats(h, stats, c);
-    if (r >= 0 && e == hipSuccess && d_out) e = hipMemcpyAsync(items_out, d_out, b_out, hipMemcpyDeviceToHost, s);
+    if (r >= 0 && e == hipSuccess && d_out) e = hipMemcpyAsync(list.out, d_out, b_out, hipMemcpyDeviceToHost, s);
     const hipError_t e_wait = hipStreamSynchronize(s);   // nothing in flight touches the list that is freed next
     if (d) (void)hipFree(d);   // on every path
     if (r < 0) return r;
     HIP_TRY(e);
     HIP_TRY(e_wait);
     if (c2 != c) { viso_set_error("%s: the table changed between the two passes", where); return VISO_ERR_HIP; }   // (the map's lock rules it out)
-    if (items_out) std::sort(items_out, items_out + c, [](const Item& x, const Item& y) { return voxel_item_less(x, y); });
+    if (list.out) std::sort(list.out, list.out + c, [](const Item& x, const Item& y) { return voxel_item_less(x, y); });
     return VISO_OK;
 }
 #endif /* VISO_VOXEL_HOST_H_ */

@@ -149,13 +149,15 @@ static bool all_finite(const double* v, size_t n) {
     return true;
 }
 
-static int voxel_fuse_check(const char* where, int rows, int cols, int n_frames, double f, double cu, double cv, double base, const double* poses) {
-    if (poses && !all_finite(poses, (size_t)n_frames * 16)) { viso_set_error("%s: a pose has an entry that is not finite", where); return VISO_ERR_ARG; }
-    if (!std::isfinite(f) || !std::isfinite(cu) || !std::isfinite(cv) || !std::isfinite(base)) {
+// Not the alignment's check (tsdf_align.hip, align_check): a fuse only scales and offsets by the calibration, so any finite one
+// will do, and the limit on the pixels is this build's 32-bit pixel index, not the definition's: VISO_ERR_UNSUPPORTED.
+static int voxel_fuse_check(const char* where, const DispView& v) {
+    if (v.poses && !all_finite(v.poses, (size_t)v.n * 16)) { viso_set_error("%s: a pose has an entry that is not finite", where); return VISO_ERR_ARG; }
+    if (!std::isfinite(v.cal.f) || !std::isfinite(v.cal.cu) || !std::isfinite(v.cal.cv) || !std::isfinite(v.cal.base)) {
         viso_set_error("%s: the calibration (f, cu, cv, base) must be finite", where);
         return VISO_ERR_ARG;
     }
-    if ((long long)rows * cols > VOXEL_MAX_PIXELS) { viso_set_error("%s: a %d x %d map is beyond this build (2^31 - 1 pixels)", where, rows, cols); return VISO_ERR_UNSUPPORTED; }
+    if ((long long)v.rows * v.cols > VOXEL_MAX_PIXELS) { viso_set_error("%s: a %d x %d map is beyond this build (2^31 - 1 pixels)", where, v.rows, v.cols); return VISO_ERR_UNSUPPORTED; }
     return VISO_OK;
 }
 
@@ -171,62 +173,37 @@ static int voxel_stage_poses(const char* where, VoxelHost* h, const double* pose
     return VISO_OK;
 }
 
-// h is entered and locked; disp, and image if there is one, on its device
-static int voxel_fuse_device(const char* where, VoxelHost* h, const int16_t* disp, size_t mfs, int rows, int cols, int n_frames, double f,
-                             double cu, double cv, double base, const double* poses, const VoxelFuseLaunch& launch, const uint8_t* image,
-                             size_t ifs) {
-    if (h->overflowed) return voxel_refuse_overflowed(where, h);
-    hipStream_t s = h->ctx->stream;
+int voxel_fuse(const char* where, VoxelRegistry& reg, const void* handle, const DispView& v, const VoxelFuseLaunch& launch) {
+    if (!voxel_known(reg, handle)) return voxel_not_live(where, reg);
+    if (!v.ctx && (!v.disp || v.rows <= 0 || v.cols <= 0)) { viso_set_error("%s: bad argument (non-null map and calibration, sizes > 0)", where); return VISO_ERR_ARG; }
     int r;
+    VoxelHost* h;
+    if ((r = voxel_fuse_check(where, v)) < 0) return r;
+    if ((r = voxel_enter(where, reg, handle, &h)) < 0) return r;
+    if (v.ctx && h->ctx != v.ctx) { viso_set_error("%s: the %s and the batch must share a context", where, reg.kind.noun); return VISO_ERR_ARG; }
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (h->overflowed) return voxel_refuse_overflowed(where, h);
+    const size_t px = v.px();
+    const int16_t* disp = v.disp;
+    const uint8_t* image = v.image;
+    if (!v.ctx) {   // one host map, and one host image if there is one, through the staging
+        if ((r = voxel_stage_map(where, h, v.disp, px, &disp)) < 0) return r;
+        if (v.image && (r = voxel_stage_image(where, h, v.image, px, &image)) < 0) return r;
+    }
+    hipStream_t s = h->ctx->stream;
     std::vector<double> rows12;   // alive until voxel_finish has waited for the copy that reads it
-    if (poses && (r = voxel_stage_poses(where, h, poses, n_frames, rows12)) < 0) return r;
+    if (v.poses && (r = voxel_stage_poses(where, h, v.poses, v.n, rows12)) < 0) return r;
     VoxelFuseArgs a;
-    a.mfs = mfs; a.rows = rows; a.cols = cols; a.min_disp16 = h->min_disp16; a._pad = 0;
-    a.f = f; a.cu = cu; a.cv = cv; a.base = base;
-    const size_t px = (size_t)rows * cols;
-    for (int f0 = 0; f0 < n_frames; f0 += VOXEL_GROUP) {
-        const int nf = n_frames - f0 < VOXEL_GROUP ? n_frames - f0 : VOXEL_GROUP;
-        a.disp = disp + (size_t)f0 * mfs;
-        a.poses = poses ? h->d_pose + (size_t)f0 * 12 : nullptr;
-        launch(a, image ? image + (size_t)f0 * ifs : nullptr, dim3((unsigned)((px + 255) / 256), (unsigned)nf), s);
+    a.mfs = v.mfs; a.rows = v.rows; a.cols = v.cols; a.min_disp16 = h->min_disp16; a._pad = 0;
+    a.f = v.cal.f; a.cu = v.cal.cu; a.cv = v.cal.cv; a.base = v.cal.base;
+    for (int f0 = 0; f0 < v.n; f0 += VOXEL_GROUP) {
+        const int nf = v.n - f0 < VOXEL_GROUP ? v.n - f0 : VOXEL_GROUP;
+        a.disp = disp + (size_t)f0 * v.mfs;
+        a.poses = v.poses ? h->d_pose + (size_t)f0 * 12 : nullptr;
+        launch(a, image ? image + (size_t)f0 * v.ifs : nullptr, dim3((unsigned)((px + 255) / 256), (unsigned)nf), s);
         HIP_TRY(hipGetLastError());
     }
     return voxel_finish(where, h);
-}
-
-int voxel_fuse_resident(const char* where, VoxelRegistry& reg, const void* handle, viso_ctx* c, const int16_t* disp, size_t mfs, int rows,
-                        int cols, int n_frames, double f, double cu, double cv, double base, const double* poses, const VoxelFuseLaunch& launch,
-                        const uint8_t* image, size_t ifs) {
-    if (!voxel_known(reg, handle)) return voxel_not_live(where, reg);
-    int r;
-    VoxelHost* h;
-    if ((r = voxel_fuse_check(where, rows, cols, n_frames, f, cu, cv, base, poses)) < 0) return r;
-    if ((r = voxel_enter(where, reg, handle, &h)) < 0) return r;
-    if (h->ctx != c) { viso_set_error("%s: the %s and the batch must share a context", where, reg.kind.noun); return VISO_ERR_ARG; }
-    std::lock_guard<std::mutex> lk(h->mu);
-    return voxel_fuse_device(where, h, disp, mfs, rows, cols, n_frames, f, cu, cv, base, poses, launch, image, ifs);
-}
-
-int voxel_fuse_host(const char* where, VoxelRegistry& reg, const void* handle, const int16_t* disp, int rows, int cols, const viso_param* param,
-                    const double* pose_or_null, const VoxelFuseLaunch& launch, const uint8_t* image) {
-    if (!voxel_known(reg, handle)) return voxel_not_live(where, reg);
-    if (!disp || !param || rows <= 0 || cols <= 0) { viso_set_error("%s: bad argument (non-null map and calibration, sizes > 0)", where); return VISO_ERR_ARG; }
-    int r;
-    VoxelHost* h;
-    if ((r = voxel_fuse_check(where, rows, cols, 1, param->f, param->cu, param->cv, param->base, pose_or_null)) < 0) return r;
-    if ((r = voxel_enter(where, reg, handle, &h)) < 0) return r;
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (h->overflowed) return voxel_refuse_overflowed(where, h);
-    const size_t px = (size_t)rows * cols;
-    hipStream_t s = h->ctx->stream;
-    if ((r = voxel_grow(where, &h->d_disp, &h->d_disp_bytes, px * sizeof(int16_t), s)) < 0) return r;
-    HIP_TRY(hipMemcpyAsync(h->d_disp, disp, px * sizeof(int16_t), hipMemcpyHostToDevice, s));
-    if (image) {
-        if ((r = voxel_grow(where, &h->d_image, &h->d_image_bytes, px, s)) < 0) return r;
-        HIP_TRY(hipMemcpyAsync(h->d_image, image, px, hipMemcpyHostToDevice, s));
-    }
-    return voxel_fuse_device(where, h, h->d_disp, px, rows, cols, 1, param->f, param->cu, param->cv, param->base, pose_or_null, launch,
-                             image ? h->d_image : nullptr, px);
 }
 
 int voxel_pass(VoxelHost* h, const VoxelLaunch& launch, unsigned long long* n) {
@@ -288,18 +265,18 @@ extern "C" int viso_voxel_box_around(const double centre[3], double half_side, d
     return VISO_OK;
 }
 
-int voxel_render(const char* where, VoxelRegistry& reg, const void* handle, size_t px, const double* poses, int n_views, int16_t* disp_out,
-                 uint32_t* weight_out, const VoxelRenderLaunch& launch, uint8_t* gray_out) {
+int voxel_render(const char* where, VoxelRegistry& reg, const void* handle, size_t px, const double* poses, int n_views, const VoxelRenderOut& out,
+                 const VoxelRenderLaunch& launch) {
     int r;
     VoxelHost* h;
     if ((r = voxel_enter(where, reg, handle, &h)) < 0) return r;
     std::lock_guard<std::mutex> lk(h->mu);
     if (h->overflowed) return voxel_refuse_overflowed(where, h);
     hipStream_t s = h->ctx->stream;
-    const size_t per = (weight_out ? 6 : 2) + (gray_out ? 1 : 0);   // bytes a pixel: the weights, then the maps, then the intensities
+    const size_t per = (out.weight ? 6 : 2) + (out.gray ? 1 : 0);   // bytes a pixel: the weights, then the maps, then the intensities
     if (px > (size_t)-1 / per / (size_t)n_views) { viso_set_error("%s: %d views of %zu pixels are beyond the address space", where, n_views, px); return VISO_ERR_NOMEM; }
-    const size_t n = (size_t)n_views * px, b_weight = weight_out ? n * sizeof(uint32_t) : 0, b_disp = n * sizeof(int16_t),
-                 bytes = b_weight + b_disp + (gray_out ? n : 0);
+    const size_t n = (size_t)n_views * px, b_weight = out.weight ? n * sizeof(uint32_t) : 0, b_disp = n * sizeof(int16_t),
+                 bytes = b_weight + b_disp + (out.gray ? n : 0);
     std::vector<double> rows12;   // alive until the stream has been waited for
     if (poses && (r = voxel_stage_poses(where, h, poses, n_views, rows12)) < 0) return r;
     void* d = nullptr;
@@ -309,9 +286,9 @@ int voxel_render(const char* where, VoxelRegistry& reg, const void* handle, size
         viso_set_error("%s: cannot allocate %zu bytes for the views", where, bytes);
         return VISO_ERR_NOMEM;
     }
-    uint32_t* d_weight = weight_out ? static_cast<uint32_t*>(d) : nullptr;
+    uint32_t* d_weight = out.weight ? static_cast<uint32_t*>(d) : nullptr;
     int16_t* d_disp = reinterpret_cast<int16_t*>(static_cast<char*>(d) + b_weight);
-    uint8_t* d_gray = gray_out ? static_cast<uint8_t*>(d) + b_weight + b_disp : nullptr;
+    uint8_t* d_gray = out.gray ? static_cast<uint8_t*>(d) + b_weight + b_disp : nullptr;
     hipError_t e = hipSuccess;
     for (int v0 = 0; v0 < n_views && e == hipSuccess; v0 += VOXEL_GROUP) {
         const int nv = n_views - v0 < VOXEL_GROUP ? n_views - v0 : VOXEL_GROUP;
@@ -319,9 +296,9 @@ int voxel_render(const char* where, VoxelRegistry& reg, const void* handle, size
                d_gray ? d_gray + (size_t)v0 * px : nullptr, dim3((unsigned)((px + 255) / 256), (unsigned)nv), s);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(disp_out, d_disp, n * sizeof(int16_t), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && d_weight) e = hipMemcpyAsync(weight_out, d_weight, b_weight, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && d_gray) e = hipMemcpyAsync(gray_out, d_gray, n, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(out.disp, d_disp, n * sizeof(int16_t), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && d_weight) e = hipMemcpyAsync(out.weight, d_weight, b_weight, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && d_gray) e = hipMemcpyAsync(out.gray, d_gray, n, hipMemcpyDeviceToHost, s);
     const hipError_t e_wait = hipStreamSynchronize(s);   // nothing in flight touches the buffer that is freed next
     (void)hipFree(d);   // on every path
     HIP_TRY(e);
@@ -348,7 +325,7 @@ int voxel_stage_image(const char* where, VoxelHost* h, const uint8_t* image, siz
 }
 
 int voxel_linearize(const char* where, VoxelHost* h, const double* poses, const unsigned long long* active, int n, size_t words,
-                    unsigned blocks_x, unsigned long long* out, const VoxelLinearizeLaunch& launch) {
+                    unsigned long long* out, const VoxelLinearizeLaunch& launch) {
     hipStream_t s = h->ctx->stream;
     int r;
     // one block: poses [n][12] | active [n] | sums [n][words], all 8-byte words; the first two staged with one copy
@@ -364,7 +341,7 @@ int voxel_linearize(const char* where, VoxelHost* h, const double* poses, const 
     if (e == hipSuccess) e = hipMemsetAsync(d_out, 0, b_out, s);
     for (int f0 = 0; f0 < n && e == hipSuccess; f0 += VOXEL_GROUP) {
         const int nf = n - f0 < VOXEL_GROUP ? n - f0 : VOXEL_GROUP;
-        launch(d_poses + (size_t)f0 * 12, d_active + f0, d_out + (size_t)f0 * words, f0, dim3(blocks_x, (unsigned)nf), s);
+        launch(d_poses + (size_t)f0 * 12, d_active + f0, d_out + (size_t)f0 * words, f0, (unsigned)nf, s);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, b_out, hipMemcpyDeviceToHost, s);

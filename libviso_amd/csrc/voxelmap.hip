@@ -183,13 +183,10 @@ extern "C" int viso_map_destroy(viso_map* m) {
 
 extern "C" int viso_map_clear(viso_map* m) { return voxel_clear("viso_map_clear", g_maps, m, map_clear_launch(m)); }
 
-int map_fuse_resident(const char* where, viso_map* m, viso_ctx* c, const int16_t* disp, size_t mfs, int rows, int cols, int n_frames,
-                      double f, double cu, double cv, double base, const double* poses) {
-    return voxel_fuse_resident(where, g_maps, m, c, disp, mfs, rows, cols, n_frames, f, cu, cv, base, poses, map_fuse_launch(m));
-}
+int map_fuse_resident(const char* where, viso_map* m, const DispView& v) { return voxel_fuse(where, g_maps, m, v, map_fuse_launch(m)); }
 
 extern "C" int viso_map_fuse(viso_map* m, const int16_t* disp, int rows, int cols, const viso_param* param, const double* pose_or_null) {
-    return voxel_fuse_host("viso_map_fuse", g_maps, m, disp, rows, cols, param, pose_or_null, map_fuse_launch(m));
+    return voxel_fuse("viso_map_fuse", g_maps, m, disp_view_host(disp, nullptr, rows, cols, param, pose_or_null), map_fuse_launch(m));
 }
 
 extern "C" int viso_map_add_entries(viso_map* m, const viso_map_entry* entries, size_t n) {
@@ -210,24 +207,24 @@ static inline bool voxel_item_less(const viso_map_entry& x, const viso_map_entry
 }
 
 // the count or the sorted list of the voxels with count >= min_count
-static int map_extract(const char* where, viso_map* m, uint32_t min_count, bool count_only, viso_map_entry* entries_out, size_t n_cap, size_t* n) {
+static int map_extract(const char* where, viso_map* m, uint32_t min_count, const VoxelList<viso_map_entry>& list) {
     if (!voxel_known(g_maps, m)) { viso_set_error("%s: not a live map handle", where); return VISO_ERR_ARG; }
-    return voxel_entries(where, g_maps, m, min_count, count_only, entries_out, n_cap, n, MapPayload{m->t});
+    return voxel_entries(where, g_maps, m, min_count, list, MapPayload{m->t});
 }
-extern "C" int viso_map_count(viso_map* m, uint32_t min_count, size_t* n) { return map_extract("viso_map_count", m, min_count, true, nullptr, 0, n); }
+extern "C" int viso_map_count(viso_map* m, uint32_t min_count, size_t* n) { return map_extract("viso_map_count", m, min_count, {true, nullptr, 0, n}); }
 extern "C" int viso_map_get(viso_map* m, uint32_t min_count, viso_map_entry* entries_out, size_t n_cap, size_t* n) {
-    return map_extract("viso_map_get", m, min_count, false, entries_out, n_cap, n);
+    return map_extract("viso_map_get", m, min_count, {false, entries_out, n_cap, n});
 }
 
-static int map_evict(const char* where, viso_map* m, const viso_voxel_box* keep, bool count_only, viso_map_entry* evicted_out, size_t n_cap, size_t* n) {
+static int map_evict(const char* where, viso_map* m, const viso_voxel_box* keep, const VoxelList<viso_map_entry>& list) {
     if (!voxel_known(g_maps, m)) { viso_set_error("%s: not a live map handle", where); return VISO_ERR_ARG; }
-    return voxel_evict(where, g_maps, m, keep, count_only, evicted_out, n_cap, n, MapPayload{m->t});
+    return voxel_evict(where, g_maps, m, keep, list, MapPayload{m->t});
 }
 extern "C" int viso_map_evict_count(viso_map* m, const viso_voxel_box* keep, size_t* n) {
-    return map_evict("viso_map_evict_count", m, keep, true, nullptr, 0, n);
+    return map_evict("viso_map_evict_count", m, keep, {true, nullptr, 0, n});
 }
 extern "C" int viso_map_evict(viso_map* m, const viso_voxel_box* keep, viso_map_entry* evicted_out, size_t n_cap, size_t* n) {
-    return map_evict("viso_map_evict", m, keep, false, evicted_out, n_cap, n);
+    return map_evict("viso_map_evict", m, keep, {false, evicted_out, n_cap, n});
 }
 
 extern "C" int viso_map_stats(viso_map* m, viso_map_counters* out) {

@@ -239,6 +239,11 @@ def test_resident_path_equals_single_calls_and_lifetime(viso):
     assert got2[1]["status"] == -1 and got2[1]["pose"].tobytes() == early[1].tobytes() and got2[1]["iters"] == 0
     assert got2[[0, 2]].tobytes() == single[[0, 2]].tobytes()
     assert b.align_tsdf(tsdf, guesses[2:], t0=4, t1=5, **par).tobytes() == single[2:].tobytes()
+    # frames 1 and 2 are different maps (frames 2..4 are one map three times): a range that starts at 1 reads the maps it names
+    g13 = np.stack([AC.perturbed(AC.FUSED[1], 0.002, 0.01), guesses[0]])
+    mixed = np.stack([tsdf.align(maps[1 + t], prm, g13[t], **par) for t in range(2)])
+    assert mixed[0]["status"] >= 1 and mixed[0].tobytes() != tsdf.align(maps[2], prm, g13[0], **par).tobytes()
+    assert b.align_tsdf(tsdf, g13, t0=1, t1=3, **par).tobytes() == mixed.tobytes()
     # nothing else of the batch, and nothing of the map, has changed
     after = (b.disparities(), b.image(0, 0))
     assert all(np.array_equal(x, y) for x, y in zip(before, after))
