@@ -9,6 +9,7 @@ from libviso_amd.abi import MatchParams, Param
 
 import rectify_ref as RR
 import subpixel_ref as S
+from dense_fuzz import hostile_map as _hostile_map
 
 pytestmark = pytest.mark.gpu
 
@@ -16,27 +17,6 @@ pytestmark = pytest.mark.gpu
 # original rectified images, 13.0 mm rectified from raw, 383 mm on the raw images unrectified.
 RECT_FACTOR = 1.5
 RAW_FACTOR = 5.0
-
-
-def _hostile_map(rng, raw_shape, out_shape):
-    """Positions reaching 0-2.5 px past every edge, negative ones, entries exactly at raw_cols-1 / raw_rows-1 (partial taps),
-    all 32 fractions, NaN, +-inf and +-40000."""
-    rr, rc = raw_shape
-    mx = rng.uniform(-2.5, rc + 1.5, out_shape).astype(np.float32)
-    my = rng.uniform(-2.5, rr + 1.5, out_shape).astype(np.float32)
-    fl = mx.reshape(-1); gl = my.reshape(-1)
-    n = fl.size
-    k = np.arange(n)
-    frac = (k % 32).astype(np.float32) / np.float32(32)
-    sel = k % 5 == 0                                    # exact 1/32 fractions on integer bases
-    fl[sel] = np.floor(fl[sel]) + frac[sel]
-    gl[sel] = np.floor(gl[sel]) + frac[(k[sel] * 7) % n]
-    special = [np.nan, np.inf, -np.inf, 40000.0, -40000.0, rc - 1, -1.0, -0.5, rc - 1 + 0.5, 0.0]
-    for j, v in enumerate(special):
-        if 3 * j + 2 < n:
-            fl[3 * j + 1] = v
-            gl[3 * j + 2] = {rc - 1: rr - 1, rc - 1 + 0.5: rr - 1 + 0.5}.get(v, v)
-    return mx, my
 
 
 @pytest.mark.parametrize("raw_shape,out_shape", [((37, 53), (29, 41)), ((9, 9), (9, 9)), ((20, 30), (43, 57)), ((512, 1392), (376, 1241))])
