@@ -14,8 +14,10 @@
 //   phase 1 one scan of the y buckets the round's diamonds touch, 32 targets per step with both lane halves on the same
 //           targets (lanes 0..31 test queries 0..3, lanes 32..63 queries 4..7).  Q1 cut and radius are ONE threshold on
 //           the bit pattern of |dx| + |dy|; the verdict is the SIGN of (thr - 1) - bits(d), shifted into a 4-bit mask
-//           by v_alignbit (no v_cmp, no select); one v_permlane32_swap joins the halves' nibbles; targets with a member
-//           are appended (ballot + mbcnt) to the round's union list in LDS.  Masks are kept INVERTED (set = not a member).
+//           by v_alignbit (no v_cmp, no select); one v_permlane32_swap of TWO steps' nibble registers against each other
+//           joins the halves' nibbles of both (lanes 0..31: the first step's masks, lanes 32..63: the second's); targets
+//           with a member are appended (64-bit ballot + mbcnt, every lane writes) to the round's union list in LDS.
+//           Masks are kept INVERTED (set = not a member).
 //           Per-query in-radius counts (K cap) are only taken when the list is longer than K or a minimum is tied
 //   phase 2 rolling pipeline over the union list, 8 lanes per row, 2 passes in flight: two global_load_dwordx4 per lane,
 //           8 x v_sad_u16 against each of the eight query rows (staged per wave in LDS), a transposing reduction (three
@@ -237,22 +239,29 @@ __global__ __attribute__((amdgpu_waves_per_eu(7, 8))) __launch_bounds__(MU_THREA
             qw[k] = ((const __attribute__((address_space(1))) uint32_t*)reinterpret_cast<const uint32_t*>(P.q.rows))[(size_t)min(jk, q1 - 1) * (VISO_ROW / 2) + lane];
         }
         if (r + 1 < ROUNDS) MU_PREFETCH(r + 1);
-        // ---------------- phase 1: one scan over the y buckets the round's diamonds touch, 32 targets per step: both
-        // halves read the same 32 entries, each tests its four queries (sign of bits(d) - thr shifted into a 4-bit mask:
-        // sub + alignbit, no condition code), one v_permlane32_swap joins the halves' nibbles into the 8-bit membership
-        // mask (bit 7 - k = query k) in every lane; targets with a non-zero mask go to the union list (lanes 0..31
-        // write).  entry = inverted mask << 24 | window position << 8.  ncnt accumulates the set bits = (query, target)
-        // pairs tested and NOT in radius (the same in both halves)
+        // ---------------- phase 1: one scan over the y buckets the round's diamonds touch, 64 targets per iteration as two
+        // steps of 32, a and b: both halves read the same 32 entries of a step, each tests its four queries (sign of
+        // bits(d) - thr shifted into a 4-bit mask: sub + alignbit, no condition code).  ONE v_permlane32_swap of the two
+        // steps' nibble registers against each other joins them: lanes 0..31 then hold step a's 8-bit membership mask
+        // (bit 7 - k = query k) of target base + lane, lanes 32..63 step b's, also of target base + lane; targets with a
+        // non-zero mask go to the union list, all 64 lanes write (lane order = a's entries before b's = y-bucket order).
+        // entry = inverted mask << 24 | window position << 8.  ncnt accumulates the set bits of the lane's own masks =
+        // (query, target) pairs tested and NOT in radius, ntest the pairs tested
         int ucnt = 0;
         uint32_t ncnt = 0, ntest = 0;
-#define MU_TEST4(T)                                                                                       \
+        // the half's four queries against target T: bit 3 - i set = query i of the half is NOT a member
+#define MU_NIB4(T)                                                                                        \
         ({                                                                                                \
             uint32_t m_ = 0;                                                                              \
             _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                 \
                 m_ = __builtin_amdgcn_alignbit(m_, thr[i] - l1_bits(qx[i], qy[i], (T)), 31);              \
-            /* swap(A, B): A's lanes 32..63 <-> B's lanes 0..31; with A = B = m_: r_[0] = the low half's nibble everywhere, */ \
-            /* r_[1] = the high half's */                                                                 \
-            const auto r_ = __builtin_amdgcn_permlane32_swap(m_, m_, false, false);                       \
+            m_;                                                                                           \
+        })
+        // swap(A, B): A's lanes 32..63 <-> B's lanes 0..31, so r_[0] = the low half's nibbles (queries 0..3) of A's target
+        // in lanes 0..31 and of B's in lanes 32..63, r_[1] = the high half's (queries 4..7) likewise
+#define MU_JOIN8(MA, MB)                                                                                  \
+        ({                                                                                                \
+            const auto r_ = __builtin_amdgcn_permlane32_swap((MA), (MB), false, false);                   \
             (uint32_t)((r_[0] << 4) | r_[1]);                                                             \
         })
         {
@@ -262,32 +271,32 @@ __global__ __attribute__((amdgpu_waves_per_eu(7, 8))) __launch_bounds__(MU_THREA
             const int sc0 = min(__builtin_amdgcn_readlane(h0, 0), __builtin_amdgcn_readlane(h0, 32)) & ~63;   // steps of 64 stay inside the NaN padded array
             const int sc1 = max(__builtin_amdgcn_readlane(h1, 0), __builtin_amdgcn_readlane(h1, 32));
             const int l31 = lane & 31;
-            if (sc1 > sc0) ntest = (uint32_t)((sc1 - sc0 + 63) >> 6) * 16u;   // two steps of eight tests per lane and iteration
+            if (sc1 > sc0) ntest = (uint32_t)((sc1 - sc0 + 63) >> 6) * 8u;   // eight tests of the lane's own target per iteration
             for (int base = sc0; base < sc1; base += 64) {
-                // two steps of 32 targets in flight
                 const float2 ta = s_ykp[base + l31], tb = s_ykp[base + 32 + l31];
-                const uint32_t pa = s_ypos[base + l31], pb = s_ypos[base + 32 + l31];
-                const uint32_t m8a = MU_TEST4(ta), m8b = MU_TEST4(tb);
-                ncnt += (uint32_t)__popc(m8a) + (uint32_t)__popc(m8b);
-                const uint32_t ua = (uint32_t)__ballot(m8a != 0xffu), ub = (uint32_t)__ballot(m8b != 0xffu);
-                const int ca = __popc(ua);
-                if (m8a != 0xffu && half == 0) ul[min(ucnt + (int)__builtin_amdgcn_mbcnt_lo(ua, 0u), MU_UCAP - 1)] = (m8a << 24) | (pa << 8);
-                if (m8b != 0xffu && half == 0) ul[min(ucnt + ca + (int)__builtin_amdgcn_mbcnt_lo(ub, 0u), MU_UCAP - 1)] = (m8b << 24) | (pb << 8);
-                ucnt += ca + __popc(ub);
+                const uint32_t pw = s_ypos[base + lane];
+                const uint32_t ma = MU_NIB4(ta), mb = MU_NIB4(tb);
+                const uint32_t m8 = MU_JOIN8(ma, mb);
+                ncnt += (uint32_t)__popc(m8);
+                const unsigned long long u = __ballot(m8 != 0xffu);
+                if (m8 != 0xffu) ul[min(ucnt + mbcnt(u), MU_UCAP - 1)] = (m8 << 24) | (pw << 8);
+                ucnt += __popcll(u);
             }
-            for (int base = wcap; base < W; base += 32) {   // windows wider than MU_KPCAP (dense data only)
+            for (int base = wcap; base < W; base += 32) {   // windows wider than MU_KPCAP (dense data only): 32 targets per step
                 const int w = base + l31;
                 float2 t2 = make_float2(__builtin_nanf(""), __builtin_nanf(""));
                 if (w < W) t2 = P.t.skp[lo + w];
-                const uint32_t m8 = MU_TEST4(t2);
-                ncnt += (uint32_t)__popc(m8);
-                ntest += 8u;
+                const uint32_t m4 = MU_NIB4(t2);
+                const uint32_t m8 = MU_JOIN8(m4, m4);   // both halves' nibbles of the one step, in every lane
+                ncnt += (uint32_t)__popc(m8 & (half ? 0x0fu : 0xf0u));   // each half counts its own four queries
+                ntest += 4u;
                 const uint32_t u = (uint32_t)__ballot(m8 != 0xffu);
                 if (m8 != 0xffu && half == 0) ul[min(ucnt + (int)__builtin_amdgcn_mbcnt_lo(u, 0u), MU_UCAP - 1)] = (m8 << 24) | ((uint32_t)w << 8);
                 ucnt += __popc(u);
             }
         }
-#undef MU_TEST4
+#undef MU_JOIN8
+#undef MU_NIB4
         const bool list_ovf = ucnt > MU_UCAP;
         const int nu = list_ovf ? 0 : ucnt;
         __builtin_amdgcn_wave_barrier();
@@ -431,8 +440,8 @@ __global__ __attribute__((amdgpu_waves_per_eu(7, 8))) __launch_bounds__(MU_THREA
                     if (lane == qlane(k)) my_cnt += c;
                 }
             }
-        } else if (!list_ovf && half == 0) {
-            scored += ntest - ncnt;   // every result of the round stands: all its cells count (lanes 0..31 hold partial sums)
+        } else if (!list_ovf) {
+            scored += ntest - ncnt;   // every result of the round stands: all its cells count (every lane holds its own targets' partial sum)
         }
         if (mine) {
             if (list_ovf || my_cnt > K || tie) {

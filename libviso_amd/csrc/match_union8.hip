@@ -275,22 +275,29 @@ MU_KERNEL_SIG {
             qw[3] = *(const __attribute__((address_space(1))) uint32_t*)(qrows8 + (wave_dpp_bc<0xFF>(own) + l4));
         }
         if (r + 1 < ROUNDS) MU_PREFETCH(r + 1);
-        // ---------------- phase 1: one scan over the y buckets the round's diamonds touch, 32 targets per step: both
-        // halves read the same 32 entries, each tests its four queries (sign of bits(d) - thr shifted into a 4-bit mask:
-        // sub + alignbit, no condition code), one v_permlane32_swap joins the halves' nibbles into the 8-bit membership
-        // mask (bit 7 - k = query k) in every lane; targets with a non-zero mask go to the union list (lanes 0..31
-        // write).  entry = inverted mask << 24 | window position << 7 (the row's offset in the 8-bit planes).  ncnt accumulates the set bits = (query, target)
-        // pairs tested and NOT in radius (the same in both halves)
+        // ---------------- phase 1: one scan over the y buckets the round's diamonds touch, 64 targets per iteration as two
+        // steps of 32, a and b: both halves read the same 32 entries of a step, each tests its four queries (sign of
+        // bits(d) - thr shifted into a 4-bit mask: sub + alignbit, no condition code).  ONE v_permlane32_swap of the two
+        // steps' nibble registers against each other joins them: lanes 0..31 then hold step a's 8-bit membership mask
+        // (bit 7 - k = query k) of target base + lane, lanes 32..63 step b's, also of target base + lane; targets with a
+        // non-zero mask go to the union list, all 64 lanes write (lane order = a's entries before b's = y-bucket order).
+        // entry = inverted mask << 24 | window position << 7 (the row's offset in the 8-bit planes).  ncnt accumulates
+        // the set bits of the lane's own masks = (query, target) pairs tested and NOT in radius, ntest the pairs tested
         int ucnt = 0;
         uint32_t ncnt = 0, ntest = 0;
-#define MU_TEST4(T)                                                                                       \
+        // the half's four queries against target T: bit 3 - i set = query i of the half is NOT a member
+#define MU_NIB4(T)                                                                                        \
         ({                                                                                                \
             uint32_t m_ = 0;                                                                              \
             _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                 \
                 m_ = __builtin_amdgcn_alignbit(m_, thr[i] - l1_bits(qx[i], qy[i], (T)), 31);              \
-            /* swap(A, B): A's lanes 32..63 <-> B's lanes 0..31; with A = B = m_: r_[0] = the low half's nibble everywhere, */ \
-            /* r_[1] = the high half's */                                                                 \
-            const auto r_ = __builtin_amdgcn_permlane32_swap(m_, m_, false, false);                       \
+            m_;                                                                                           \
+        })
+        // swap(A, B): A's lanes 32..63 <-> B's lanes 0..31, so r_[0] = the low half's nibbles (queries 0..3) of A's target
+        // in lanes 0..31 and of B's in lanes 32..63, r_[1] = the high half's (queries 4..7) likewise
+#define MU_JOIN8(MA, MB)                                                                                  \
+        ({                                                                                                \
+            const auto r_ = __builtin_amdgcn_permlane32_swap((MA), (MB), false, false);                   \
             (uint32_t)((r_[0] << 4) | r_[1]);                                                             \
         })
         {
@@ -300,32 +307,32 @@ MU_KERNEL_SIG {
             const int sc0 = min(__builtin_amdgcn_readlane(h0, 0), __builtin_amdgcn_readlane(h0, 32)) & ~63;   // steps of 64 stay inside the NaN padded array
             const int sc1 = max(__builtin_amdgcn_readlane(h1, 0), __builtin_amdgcn_readlane(h1, 32));
             const int l31 = lane & 31;
-            if (sc1 > sc0) ntest = (uint32_t)((sc1 - sc0 + 63) >> 6) * 16u;   // two steps of eight tests per lane and iteration
+            if (sc1 > sc0) ntest = (uint32_t)((sc1 - sc0 + 63) >> 6) * 8u;   // eight tests of the lane's own target per iteration
             for (int base = sc0; base < sc1; base += 64) {
-                // two steps of 32 targets in flight
                 const float2 ta = s_ykp[base + l31], tb = s_ykp[base + 32 + l31];
-                const uint32_t pa = s_ypos[base + l31], pb = s_ypos[base + 32 + l31];
-                const uint32_t m8a = MU_TEST4(ta), m8b = MU_TEST4(tb);
-                ncnt += (uint32_t)__popc(m8a) + (uint32_t)__popc(m8b);
-                const uint32_t ua = (uint32_t)__ballot(m8a != 0xffu), ub = (uint32_t)__ballot(m8b != 0xffu);
-                const int ca = __popc(ua);
-                if (m8a != 0xffu && half == 0) ul[min(ucnt + (int)__builtin_amdgcn_mbcnt_lo(ua, 0u), MU_UCAP - 1)] = (m8a << 24) | (pa << 7);
-                if (m8b != 0xffu && half == 0) ul[min(ucnt + ca + (int)__builtin_amdgcn_mbcnt_lo(ub, 0u), MU_UCAP - 1)] = (m8b << 24) | (pb << 7);
-                ucnt += ca + __popc(ub);
+                const uint32_t pw = s_ypos[base + lane];
+                const uint32_t ma = MU_NIB4(ta), mb = MU_NIB4(tb);
+                const uint32_t m8 = MU_JOIN8(ma, mb);
+                ncnt += (uint32_t)__popc(m8);
+                const unsigned long long u = __ballot(m8 != 0xffu);
+                if (m8 != 0xffu) ul[min(ucnt + mbcnt(u), MU_UCAP - 1)] = (m8 << 24) | (pw << 7);
+                ucnt += __popcll(u);
             }
-            for (int base = wcap; base < W; base += 32) {   // windows wider than MU_KPCAP (dense data only)
+            for (int base = wcap; base < W; base += 32) {   // windows wider than MU_KPCAP (dense data only): 32 targets per step
                 const int w = base + l31;
                 float2 t2 = make_float2(__builtin_nanf(""), __builtin_nanf(""));
                 if (w < W) t2 = P.t.skp[lo + w];
-                const uint32_t m8 = MU_TEST4(t2);
-                ncnt += (uint32_t)__popc(m8);
-                ntest += 8u;
+                const uint32_t m4 = MU_NIB4(t2);
+                const uint32_t m8 = MU_JOIN8(m4, m4);   // both halves' nibbles of the one step, in every lane
+                ncnt += (uint32_t)__popc(m8 & (half ? 0x0fu : 0xf0u));   // each half counts its own four queries
+                ntest += 4u;
                 const uint32_t u = (uint32_t)__ballot(m8 != 0xffu);
                 if (m8 != 0xffu && half == 0) ul[min(ucnt + (int)__builtin_amdgcn_mbcnt_lo(u, 0u), MU_UCAP - 1)] = (m8 << 24) | ((uint32_t)w << 7);
                 ucnt += __popc(u);
             }
         }
-#undef MU_TEST4
+#undef MU_JOIN8
+#undef MU_NIB4
         const bool list_ovf = ucnt > MU_UCAP;
         const int nu = __builtin_amdgcn_readfirstlane(list_ovf ? 0 : ucnt);   // wave uniform: the pipeline's loop control stays scalar
         __builtin_amdgcn_wave_barrier();
@@ -354,7 +361,8 @@ MU_KERNEL_SIG {
 #define MU_ISSUE(SLOT, T)                                                                                  \
             do {                                                                                           \
                 const uint32_t ent_ = ul[(T) * 8 + g8];                                                    \
-                un[SLOT] = (uint32_t)((T) * 8 + g8) | (uint32_t)__builtin_amdgcn_sbfe((int)ent_, (uint32_t)msh, 1u); \
+                /* the pass number is scalar and g8 < 8: position and membership join in one v_or3 */     \
+                un[SLOT] = (uint32_t)((T) * 8) | (uint32_t)g8 | (uint32_t)__builtin_amdgcn_sbfe((int)ent_, (uint32_t)msh, 1u); \
                 const grow_t row_ = (grow_t)(wrows8 + ((ent_ & 0x00ffffffu) | (uint32_t)(sub << 4)));      \
                 r0[SLOT] = row_[0];                                                                        \
             } while (0)
@@ -398,8 +406,11 @@ MU_KERNEL_SIG {
                 /* members and non-members alike; lists longer than the store pile up in its last row (the rescue then leaves   */ \
                 /* them to the overflow kernel).  As asm: a C store into LDS between the pipeline's LDS reads made the       */ \
                 /* register allocator spill 26 registers                                                                      */ \
-                asm volatile("ds_write_b8 %0, %1 offset:%2" : : "v"(s8a), "v"(m_ >> 7), "n"((SLOT) * 8));   /* SAD8 < 2^15 */ \
-                mu_update(tr, (m_ << 9) | un[SLOT]);                                                       \
+                /* The byte is bits 23:16 of the tracker key = bits 14:7 of the SAD8 (< 2^15), stored from there (d16_hi): no    */ \
+                /* shift; a non-member's key is all ones and its byte 255, which the rescue reads as "nothing to do"         */ \
+                const uint32_t key_ = (m_ << 9) | un[SLOT];                                                \
+                asm volatile("ds_write_b8_d16_hi %0, %1 offset:%2" : : "v"(s8a), "v"(key_), "n"((SLOT) * 8));               \
+                mu_update(tr, key_);                                                                       \
             } while (0)
             if (npass > 0) {
 #pragma unroll
@@ -645,8 +656,8 @@ MU_KERNEL_SIG {
                     if ((lane >> 3) == k) my_cnt += c;
                 }
             }
-        } else if (!list_ovf && half == 0) {
-            scored += ntest - ncnt;   // every result of the round stands: all its cells count (lanes 0..31 hold partial sums)
+        } else if (!list_ovf) {
+            scored += ntest - ncnt;   // every result of the round stands: all its cells count (every lane holds its own targets' partial sum)
         }
         if (mine) {
             if (list_ovf || my_cnt > K || irregular) {
