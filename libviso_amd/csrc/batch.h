@@ -160,6 +160,8 @@ static inline int batch_sync(viso_batch* b) {   // everything the batch has in f
 
 static inline bool slot_ok(viso_batch* b, int which, int t) { return !dead(b) && which >= 0 && which < 3 && t >= 0 && t < b->nf; }
 static inline int prob_slot(int which, int t) { return (t / 8) * 24 + which * 8 + (t % 8); }
+// the batch's resident images, frames f0 .. f0+n-1, as every launcher takes them (common.h)
+static inline StereoImages batch_images(const viso_batch* b, int f0, int n) { return image_block(b->images, b->img_rows, b->img_cols, f0, n); }
 
 // batch_dense.hip, for viso_batch_run_images (which has entered the device): the limits a dense launch over the resident images
 // must respect, then the launch itself on the context's stream; errors name `where`

@@ -358,10 +358,9 @@ static int ensure_images(viso_batch* b, int rows, int cols) {
 // One launch per upload: the maps are read once per upload, not once per frame.
 static int upload_raw(viso_batch* b, int f0, int nf, const uint8_t* images, hipStream_t s) {
     const BatchRectify& R = b->rect;
-    const size_t rper = (size_t)R.raw_rows * R.raw_cols, oper = (size_t)b->img_rows * b->img_cols;
-    HIP_TRY(hipMemcpyAsync(R.raw + (size_t)f0 * 2 * rper, images, rper * 2 * (size_t)nf, hipMemcpyHostToDevice, s));
-    return launch_rectify(s, R.raw + (size_t)f0 * 2 * rper, 2 * rper, rper, R.raw_cols, b->images + (size_t)f0 * 2 * oper, 2 * oper,
-                          oper, R.map, b->img_rows, b->img_cols, nf, 2, R.border);
+    const StereoImages raw = image_block(R.raw, R.raw_rows, R.raw_cols, f0, nf);
+    HIP_TRY(hipMemcpyAsync(raw.img, images, raw.fs * (size_t)nf, hipMemcpyHostToDevice, s));
+    return launch_rectify(s, raw, batch_images(b, f0, nf), R.map, R.border);
 }
 
 // With rectification on, the images of an upload must be the raw ones.
@@ -566,7 +565,7 @@ static int run_matcher_launch(viso_batch* b, bool from_images) {
     const int r8s = b->r8last;
     VISO_TRY(launch_sort_kp(s, b->views, b->nf * 2, b->cap, reinterpret_cast<uint32_t*>(b->scored), (int)(b->zeroed_bytes / 4), r8cnt));
     if (from_images)   // Sobel windows straight into packed rows (never bad: integers in [-1020,1020])
-        VISO_TRY(launch_extract_pack(s, b->views, b->nf * 2, b->cap, b->images, b->img_rows, b->img_cols, with_sums, r8s, r8cnt));
+        VISO_TRY(launch_extract_pack(s, b->views, b->cap, batch_images(b, 0, b->nf), with_sums, r8s, r8cnt));
     else if (b->desc_i16)
         VISO_TRY(launch_pack_i16(s, b->views, b->nf * 2, b->cap, b->dlen, reinterpret_cast<const int16_t*>(b->desc), with_sums, r8s, r8cnt));
     else
@@ -591,14 +590,13 @@ static int run_matcher_launch(viso_batch* b, bool from_images) {
             b->ev_next = (b->ev_next + 1) % VISO_EVENT_POOL;
         }
     }
-    VISO_TRY(launch_match_timed(s, b->probs, b->n_probs, b->cap, b->dlen, b->mp, b->bad_any, e0, e1, 1, b->ctx->matcher_variant, b->ovf_q, b->ovf_cnt, r8s, from_images ? 0 : 1));
+    VISO_TRY(launch_match(s, b->probs, b->n_probs, b->cap, b->dlen, b->mp, b->bad_any, e0, e1, 1, b->ctx->matcher_variant, b->ovf_q, b->ovf_cnt, r8s, from_images ? 0 : 1));
     VISO_TRY(launch_sort(s, b->probs, b->n_probs, b->cap));
     b->uv_mode = 0;
     if (from_images && b->subpix) {   // the stereo lists are final: refine their right-image points (which = 0 lists come first)
-        const size_t per = (size_t)b->img_rows * b->img_cols;
-        VISO_TRY(launch_subpixel(s, b->images, 2 * per, per, b->img_rows, b->img_cols, b->kp, 2 * (size_t)b->cap, b->cap, b->sorted,
-                                 3 * (size_t)b->cap, b->m_cnt, b->nf, b->subpix, b->uv, b->packed, 2 * (size_t)b->cap * VISO_ROW, b->rank,
-                                 2 * (size_t)b->cap));
+        const SubpixLists lists = {b->kp, 2 * (size_t)b->cap, b->cap, b->sorted, 3 * (size_t)b->cap, b->m_cnt};
+        const SubpixLeftRows left = {b->packed, 2 * (size_t)b->cap * VISO_ROW, b->rank, 2 * (size_t)b->cap};
+        VISO_TRY(launch_subpixel(s, batch_images(b, 0, b->nf), lists, b->subpix, b->uv, left));
         b->uv_mode = b->subpix;
     }
     if (b->stamps) HIP_TRY(hipEventRecord(b->ev_stamp[2], s));   // re-recorded behind the solver by run_rest
@@ -708,15 +706,16 @@ extern "C" int viso_batch_detect(viso_batch* b, int n_features, int nbinx, int n
         b->h_slots = slots;
     }
     if (per == 0) { HIP_TRY(hipMemsetAsync(b->n, 0, sizeof(int) * (size_t)n_img, s)); return VISO_OK; }
+    const StereoImages im = batch_images(b, 0, b->nf);
+    const HarrisBins bins = {n_features, nbinx, nbiny};
+    const HarrisOut out = {b->kp, nullptr, b->n, b->cap, (size_t)b->cap};
     if (fused) {
         const size_t pb = harris_strip_bytes(n_img, b->img_rows, b->img_cols, nbinx, nbiny, per);   // 0: the wave-per-bin kernel
         if (pb) VISO_TRY(b->fit(&b->h_part, &b->h_part_bytes, pb, true));   // grows only
-        return launch_harris_detect(s, b->images, n_img, b->img_rows, b->img_cols, n_features, nbinx, nbiny, k, b->h_tmp_kp,
-                                    b->h_tmp_resp, b->h_cnt, b->kp, nullptr, b->n, b->cap, (size_t)b->cap, pb ? b->h_part : nullptr);
+        return launch_harris_detect(s, im, bins, k, HarrisScratch{b->h_tmp_kp, b->h_tmp_resp, b->h_cnt, pb ? b->h_part : nullptr}, out);
     }
-    VISO_TRY(launch_harris_response(s, b->images, n_img, b->img_rows, b->img_cols, k, b->h_resp));
-    return launch_harris_bins(s, b->h_resp, n_img, b->img_rows, b->img_cols, n_features, nbinx, nbiny, b->h_tmp_kp,
-                              b->h_tmp_resp, b->h_cnt, b->kp, nullptr, b->n, b->cap, (size_t)b->cap);
+    VISO_TRY(launch_harris_response(s, im, k, b->h_resp));
+    return launch_harris_bins(s, b->h_resp, im, bins, HarrisScratch{b->h_tmp_kp, b->h_tmp_resp, b->h_cnt, nullptr}, out);
 }
 
 // Keypoints of frame t, image side (after viso_batch_detect or an upload).

@@ -95,9 +95,9 @@ int launch_batch_disparity(viso_batch* b, const char* where) {
         VISO_TRY(sgm_group_frames(where, b->img_rows, b->img_cols, D.sgm_p.num_disp, b->nf, &group));   // fails when the cap moved since dense_preflight
         VISO_TRY(b->fit(&D.sgm_ws, &D.sgm_ws_bytes, sgm_frame_bytes(b->img_rows, b->img_cols, D.sgm_p.num_disp) * (size_t)group, false, where,
                         "SGM workspace (viso_sgm_set_workspace_cap)"));
-        VISO_TRY(launch_sgm(b->ctx->stream, b->images, 2 * per, per, b->img_rows, b->img_cols, b->nf, &D.sgm_p, D.disp, per, D.sgm_ws, group));
+        VISO_TRY(launch_sgm(b->ctx->stream, batch_images(b, 0, b->nf), &D.sgm_p, D.disp, per, D.sgm_ws, group));
     } else {
-        VISO_TRY(launch_disparity(b->ctx->stream, b->images, 2 * per, per, b->img_rows, b->img_cols, b->nf, &D.disp_p, D.disp, per));
+        VISO_TRY(launch_disparity(b->ctx->stream, batch_images(b, 0, b->nf), &D.disp_p, D.disp, per));
     }
     if (D.speckle()) VISO_TRY(launch_batch_speckle(b, where));
     D.last = 1;
@@ -135,8 +135,8 @@ extern "C" int viso_batch_get_disparity(viso_batch* b, int t, int16_t* out) { re
 extern "C" int viso_batch_get_disparities(viso_batch* b, int16_t* out) { return get_disparity(b, true, 0, out, "viso_batch_get_disparities"); }
 
 // The resident maps of frames t0 .. t1-1 as a view (common.h) with the batch's calibration, at `poses` [t1 - t0][16] (or null).
-// needs (or null): who needs the resident left images the maps were computed from (frame t's at images + 2 t per); the view then has
-// them, and they must still be there with the maps' geometry.  The one place that knows where a frame's map and image lie.
+// needs (or null): who needs the resident left images the maps were computed from (batch_images); the view then has
+// them, and they must still be there with the maps' geometry.  The one place that knows where a frame's map lies.
 static int dense_view(const char* where, const viso_batch* b, int t0, int t1, const double* poses, const char* needs, DispView* v) {
     const BatchDense& D = b->dense;
     const size_t per = (size_t)D.rows * D.cols;
@@ -145,7 +145,8 @@ static int dense_view(const char* where, const viso_batch* b, int t0, int t1, co
                        where, b->images ? b->img_cols : 0, b->images ? b->img_rows : 0, D.cols, D.rows, needs);
         return VISO_ERR_ARG;
     }
-    *v = DispView{D.disp + (size_t)t0 * per, per, needs ? b->images + 2 * (size_t)t0 * per : nullptr, 2 * per, D.rows, D.cols, t1 - t0,
+    const StereoImages im = needs ? batch_images(b, t0, t1 - t0) : StereoImages{};   // each frame's left image; none: null and a stride of 0
+    *v = DispView{D.disp + (size_t)t0 * per, per, im.img, im.fs, D.rows, D.cols, t1 - t0,
                   StereoCalib{b->sp.f, b->sp.cu, b->sp.cv, b->sp.base}, poses, b->ctx};
     return VISO_OK;
 }

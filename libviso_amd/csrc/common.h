@@ -328,9 +328,6 @@ static inline int matcher_effective(int variant, int dlen) { return (variant == 
 static inline int pack_extras(int variant, int dlen) { variant = matcher_effective(variant, dlen); return variant == 5 ? VISO_PACK_SUMS : variant == 6 ? VISO_PACK_ROWS8 : 0; }
 // the same from int16 descriptors [n_img][cap][dlen] (viso_batch_upload_i16*): never flags anything
 int launch_pack_i16(hipStream_t s, const ImageView* imgs_dev, int n_img, int cap, int dlen, const int16_t* desc16, int extras, int r8s, int* r8cnt);
-// bad: int[2] zeroed before the run ([0] any image flagged by the pack kernel, [1] scratch counter of the stereo kernels)
-int launch_match(hipStream_t s, const MatchProblem* probs_dev, int n_probs, int cap_max, int dlen,
-                 const MatchParamsDev mp[2], int* bad, int variant, const int2* ovf_q, const int* ovf_cnt, int r8s);
 // kinds: which problems the launch can contain (the plain family knows: one call = one problem) -- kernels that would
 // find nothing to do are not launched.  VISO_KIND_TEMPORAL: problems without the epipolar gate, VISO_KIND_STEREO: with it.
 #define VISO_KIND_TEMPORAL 1
@@ -338,11 +335,12 @@ int launch_match(hipStream_t s, const MatchProblem* probs_dev, int n_probs, int 
 #define VISO_KIND_ALL 3
 #define VISO_KIND_NO_WIDE 4      // (plain family) leave match_batch_kernel<1> out: the launcher expects no tile with a wide epipolar band --
                                  // the count of declined tiles comes back with the results, and the call is repeated if there was one
+// bad: int[2] zeroed before the run ([0] any image flagged by the pack kernel, [1] scratch counter of the stereo kernels)
 // general_possible = 0: the rows cannot be flagged (descriptors extracted on the device from uint8 images), the
 // kernels of the general (double) path are not even launched
-int launch_match_timed(hipStream_t s, const MatchProblem* probs_dev, int n_probs, int cap_max, int dlen,
-                       const MatchParamsDev mp[2], int* bad, hipEvent_t e0, hipEvent_t e1, int layout, int variant,
-                       const int2* ovf_q, const int* ovf_cnt, int r8s, int general_possible = 1, int kinds = VISO_KIND_ALL);
+int launch_match(hipStream_t s, const MatchProblem* probs_dev, int n_probs, int cap_max, int dlen,
+                 const MatchParamsDev mp[2], int* bad, hipEvent_t e0, hipEvent_t e1, int layout, int variant,
+                 const int2* ovf_q, const int* ovf_cnt, int r8s, int general_possible = 1, int kinds = VISO_KIND_ALL);
 const char* matcher_kernel_name(int variant);
 #define VISO_MATCHER_DEFAULT 6
 struct TriItem;
@@ -427,24 +425,30 @@ int launch_match_stereo(hipStream_t s, const BatchMatchArgs& a64, int cap_max);
 // match_frame.hip: the stereo and the temporal problems of a handful of problems (one frame) in ONE launch
 int launch_match_frame(hipStream_t s, const BatchMatchArgs& at, const BatchMatchArgs& as64, long long blocks_t, int cap_max);
 #define VISO_FRAME_MAX_BLOCKS 256   // temporal grids up to this size (8 problem slots of 2000 keypoints) take the one-launch kernel
-// subpixel.hip: the opt-in sub-pixel refinement of frames' stereo lists (viso_batch_set_subpixel); uv [n_frames][cap]
-int launch_subpixel(hipStream_t s, const uint8_t* images, size_t img_stride, size_t r_off, int rows, int cols, const float2* kp,
-                    size_t kp_stride, int cap, const int* lists, size_t list_stride, const int* m_cnt, int n_frames, int mode, float2* uv,
-                    const uint16_t* lrows, size_t lrows_stride, const int* lrank, size_t lrank_stride);   // lrows == null: W_L from the image
+struct StereoImages {   // "these resident image pairs", for every launcher that reads them; only launch_rectify's `out` is written
+    uint8_t* img; size_t fs, ss; int rows, cols, n;   // image (k, side) of frames 0 .. n-1 at img + k * fs + side * ss; ss == 0: one camera
+    size_t px() const { return (size_t)rows * cols; }
+};
+// Frames f0 .. f0+n-1 of a block [..][sides][rows][cols] (sides 1: one camera's images): the one place that knows where they lie
+inline StereoImages image_block(uint8_t* block, int rows, int cols, int f0, int n, int sides = 2) {
+    const size_t px = (size_t)rows * cols;
+    return StereoImages{block + (size_t)f0 * sides * px, sides * px, sides == 2 ? px : 0, rows, cols, n};
+}
+// subpixel.hip: the opt-in sub-pixel refinement of frames' stereo lists (viso_batch_set_subpixel); uv [im.n][cap]
+struct SubpixLists { const float2* kp; size_t kp_stride; int cap; const int* lists; size_t list_stride; const int* m_cnt; };   // as SubpixArgs
+struct SubpixLeftRows { const uint16_t* lrows; size_t lrows_stride; const int* lrank; size_t lrank_stride; };   // absent: W_L from the image
+int launch_subpixel(hipStream_t s, const StereoImages& im, const SubpixLists& l, int mode, float2* uv, const SubpixLeftRows& left = {});
 // rectify.hip: the opt-in rectification of raw images (viso_batch_set_rectify).  One entry per output pixel, quantised on the host:
 // off = byte offset of tap (0,0) in the raw image; meta = fx | fy << 5 | inside bits of taps (0,0) (1,0) (0,1) (1,1) << 10..13
 struct RectEntry { int off; unsigned meta; };
 void rect_quantise(const float* mapx, const float* mapy, size_t n, int raw_rows, int raw_cols, RectEntry* out);
 bool rect_geometry_ok(int raw_rows, int raw_cols, int out_rows, int out_cols);
-// image (f, side) of raw / out at f * fs + side * ss; map [sides][out_rows * out_cols]; frames 0 .. n_frames-1 of the pointers
-int launch_rectify(hipStream_t s, const uint8_t* raw, size_t raw_fs, size_t raw_ss, int raw_cols, uint8_t* out, size_t out_fs,
-                   size_t out_ss, const RectEntry* map, int out_rows, int out_cols, int n_frames, int sides, int border);
-// disparity.hip: the opt-in dense disparity (viso_batch_set_disparity); pair of frame f at img + f * fs (left), + ss (right), its map
-// at out + f * ofs; frames 0 .. n_frames-1
+// raw -> out, the frames and sides of out; map [sides][out.px()]
+int launch_rectify(hipStream_t s, const StereoImages& raw, const StereoImages& out, const RectEntry* map, int border);
+// disparity.hip: the opt-in dense disparity (viso_batch_set_disparity); frame f's map at out + f * ofs
 bool disparity_params_ok(const viso_disparity_params* p);
 bool disparity_geometry_ok(int rows, int cols);   // cols within what the kernel handles
-int launch_disparity(hipStream_t s, const uint8_t* img, size_t fs, size_t ss, int rows, int cols, int n_frames,
-                     const viso_disparity_params* p, int16_t* out, size_t ofs);
+int launch_disparity(hipStream_t s, const StereoImages& im, const viso_disparity_params* p, int16_t* out, size_t ofs);
 // The cap on a dense feature's workspace (sgm.hip, speckle.hip): the frames go through it in groups of as many as fit under the cap
 struct __attribute__((visibility("hidden"))) WorkspaceCap {
     std::atomic<size_t> cap; size_t dflt; const char *what, *setter;   // what, setter: for the message
@@ -461,14 +465,13 @@ struct __attribute__((visibility("hidden"))) WorkspaceCap {
         return VISO_OK;
     }
 };
-// sgm.hip: the opt-in semi-global matching (viso_batch_set_sgm); images and maps addressed as in launch_disparity.  The frames go
+// sgm.hip: the opt-in semi-global matching (viso_batch_set_sgm); the maps addressed as in launch_disparity.  The frames go
 // through the workspace ws in groups of `group` (>= 1) frames: ws holds group * sgm_frame_bytes.  sgm_group_frames: *group (or null)
 // = how many of n_frames frames fit the workspace cap; not even one: VISO_ERR_NOMEM, the error text names `where`
 bool sgm_params_ok(const viso_sgm_params* p);
 size_t sgm_frame_bytes(int rows, int cols, int D);
 int sgm_group_frames(const char* where, int rows, int cols, int D, int n_frames, int* group);
-int launch_sgm(hipStream_t s, const uint8_t* img, size_t fs, size_t ss, int rows, int cols, int n_frames, const viso_sgm_params* p,
-               int16_t* out, size_t ofs, void* ws, int group);
+int launch_sgm(hipStream_t s, const StereoImages& im, const viso_sgm_params* p, int16_t* out, size_t ofs, void* ws, int group);
 // speckle.hip: the opt-in speckle filter of the maps (viso_batch_set_speckle), in place; frame f's map at map + f * mfs.  The frames
 // go through the workspace ws in groups of `group` (>= 1) frames: ws holds group * speckle_frame_bytes.  speckle_group_frames: as
 // sgm_group_frames.
@@ -554,16 +557,13 @@ int launch_window_links(hipStream_t s, const WinData& d, const WinWork& w, int j
 int launch_window_refine(hipStream_t s, const WinData& d, const WinWork& w, const SolverParamsDev& sp, int K, int mode, double sigma,
                          int t0, int n, viso_window_record* out);
 bool window_refine_args_ok(int K, int mode, double sigma_px);   // K in 2..5 and motion_args_ok
-int launch_extract_pack(hipStream_t s, const ImageView* imgs_dev, int n_img, int cap, const uint8_t* images,
-                        int rows, int cols, int extras, int r8s, int* r8cnt);
-int launch_harris_response(hipStream_t s, const uint8_t* images, int n_img, int rows, int cols, double k, float* resp);
+int packed_images(const char* who, const StereoImages& im);   // how many images lie back to back (extract_pack, Harris), or VISO_ERR_ARG
+int launch_extract_pack(hipStream_t s, const ImageView* imgs_dev, int cap, const StereoImages& im, int extras, int r8s, int* r8cnt);
+int launch_harris_response(hipStream_t s, const StereoImages& im, double k, float* resp);   // resp [images][rows][cols]
 size_t harris_fused_lds(int rows, int cols, int nbinx, int nbiny, int per);
-// part: harris_strip_bytes(...) bytes of device scratch for the strip kernel (waves over 58-column strips instead of bins), or
-// null: the wave-per-bin kernel.  harris_strip_bytes returns 0 where the strip kernel does not apply or would not pay.
 size_t harris_strip_bytes(int n_img, int rows, int cols, int nbinx, int nbiny, int per);
-int launch_harris_detect(hipStream_t s, const uint8_t* images, int n_img, int rows, int cols, int n_features, int nbinx,
-                         int nbiny, double k, float2* tmp_kp, float* tmp_resp, int* cnt, float2* kp_out, float* resp_out,
-                         int* n_out, int cap, size_t kp_stride, void* part = nullptr);
-int launch_harris_bins(hipStream_t s, const float* resp, int n_img, int rows, int cols, int n_features, int nbinx,
-                       int nbiny, float2* tmp_kp, float* tmp_resp, int* cnt, float2* kp_out, float* resp_out,
-                       int* n_out, int cap, size_t kp_stride);
+struct HarrisBins { int n_features, nbinx, nbiny; };   // n_features / (nbinx * nbiny) corners per bin
+struct HarrisScratch { float2* tmp_kp; float* tmp_resp; int* cnt; void* part; };   // as BinArgs; part (detect): harris_strip_bytes(...) bytes, or null
+struct HarrisOut { float2* kp_out; float* resp_out; int* n_out; int cap; size_t kp_stride; };   // [images][kp_stride], [images]; resp_out or null
+int launch_harris_detect(hipStream_t s, const StereoImages& im, const HarrisBins& bins, double k, const HarrisScratch& tmp, const HarrisOut& out);
+int launch_harris_bins(hipStream_t s, const float* resp, const StereoImages& im, const HarrisBins& bins, const HarrisScratch& tmp, const HarrisOut& out);

@@ -213,15 +213,14 @@ extern "C" void viso_disparity_params_default(viso_disparity_params* p) {
     p->num_disp = 128; p->block = 11; p->prefilter_cap = 31; p->texture_threshold = 10; p->uniqueness = 15; p->lr_max_diff = 1;
 }
 
-int launch_disparity(hipStream_t s, const uint8_t* img, size_t fs, size_t ss, int rows, int cols, int n_frames,
-                     const viso_disparity_params* p, int16_t* out, size_t ofs) {
-    if (n_frames <= 0) return VISO_OK;
+int launch_disparity(hipStream_t s, const StereoImages& im, const viso_disparity_params* p, int16_t* out, size_t ofs) {
+    if (im.n <= 0) return VISO_OK;
     DispArgs a;
-    a.img = img; a.fs = fs; a.ss = ss; a.out = out; a.ofs = ofs; a.rows = rows; a.cols = cols; a.p = *p;
+    a.img = im.img; a.fs = im.fs; a.ss = im.ss; a.out = out; a.ofs = ofs; a.rows = im.rows; a.cols = im.cols; a.p = *p;
     const int K = (p->block + 3) / 4;
-    const size_t lds = sizeof(uint32_t) * (size_t)(2 * K + 2) * cols;   // <= 14 * 2048 * 4 = 112 KiB
+    const size_t lds = sizeof(uint32_t) * (size_t)(2 * K + 2) * im.cols;   // <= 14 * 2048 * 4 = 112 KiB
     if (lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)stereo_disparity_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(stereo_disparity_kernel, dim3((unsigned)rows, (unsigned)n_frames), dim3(DISP_THREADS), lds, s, a);
+    hipLaunchKernelGGL(stereo_disparity_kernel, dim3((unsigned)im.rows, (unsigned)im.n), dim3(DISP_THREADS), lds, s, a);
     HIP_TRY(hipGetLastError());
     return VISO_OK;
 }
@@ -245,7 +244,7 @@ extern "C" int viso_stereo_disparity(const uint8_t* left, const uint8_t* right, 
     VISO_TRY(dc.scratch(SLOT_GEN1, per, &dout));
     VISO_TRY(dc.up(dimg, left, per));
     VISO_TRY(dc.up(dimg + per, right, per));
-    VISO_TRY(launch_disparity(dc.s, dimg, 2 * per, per, rows, cols, 1, params, dout, per));
+    VISO_TRY(launch_disparity(dc.s, image_block(dimg, rows, cols, 0, 1), params, dout, per));
     VISO_TRY(dc.down(out, dout, per));
     return dc.wait();
 }

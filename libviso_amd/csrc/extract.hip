@@ -178,13 +178,20 @@ __global__ __launch_bounds__(256) void extract_pack_kernel(const ImageView* __re
     if (r8on) r8_flush(r8c, r8cnt, lane);
 }
 
-int launch_extract_pack(hipStream_t s, const ImageView* imgs_dev, int n_img, int cap, const uint8_t* images,
-                        int rows, int cols, int extras, int r8s, int* r8cnt) {
+int packed_images(const char* who, const StereoImages& im) {
+    if (im.ss ? im.ss == im.px() && im.fs == 2 * im.px() : im.fs == im.px()) return im.ss ? 2 * im.n : im.n;
+    viso_set_error("%s: the images do not lie back to back", who);
+    return VISO_ERR_ARG;
+}
+
+int launch_extract_pack(hipStream_t s, const ImageView* imgs_dev, int cap, const StereoImages& im, int extras, int r8s, int* r8cnt) {
+    const int n_img = packed_images("extract_pack", im);   // one view per image
+    if (n_img < 0) return VISO_ERR_ARG;
     const int capp = (cap + VISO_EXT_KPW - 1) / VISO_EXT_KPW * VISO_EXT_KPW;
     const long long waves = (long long)n_img * capp / VISO_EXT_KPW;
     if (waves == 0) return VISO_OK;
     hipLaunchKernelGGL(extract_pack_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, imgs_dev, n_img, capp,
-                       images, rows, cols, extras, r8s, (extras & VISO_PACK_ROWS8) ? r8cnt : nullptr, r8_mask(waves));
+                       im.img, im.rows, im.cols, extras, r8s, (extras & VISO_PACK_ROWS8) ? r8cnt : nullptr, r8_mask(waves));
     HIP_TRY(hipGetLastError());
     return VISO_OK;
 }

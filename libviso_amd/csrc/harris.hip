@@ -799,19 +799,19 @@ __global__ __launch_bounds__(256) void harris_compact_kernel(BinArgs a, float2* 
     }
 }
 
-int launch_harris_response(hipStream_t s, const uint8_t* images, int n_img, int rows, int cols, double k, float* resp) {
-    if (n_img <= 0) return VISO_OK;
+int launch_harris_response(hipStream_t s, const StereoImages& im, double k, float* resp) {
+    const int n_img = packed_images("harris", im), rows = im.rows, cols = im.cols;
+    if (n_img <= 0) return n_img < 0 ? VISO_ERR_ARG : VISO_OK;
     // bands of 76 rows once the strips alone fill the GPU's wave slots a few times over, of 19 rows for a few images
     const int strips = (cols + HR_TW - 1) / HR_TW;
     int band = (long long)n_img * strips * ((rows + 75) / 76) >= 16384 ? 76 : 19;
     if (const char* e = getenv("VISO_HARRIS_BAND")) { const int v = atoi(e); if (v >= 1 && v <= 4096) band = v; }   // tuning / tests: results do not depend on it
     dim3 grid(strips, (rows + band * (HW_THREADS / 64) - 1) / (band * (HW_THREADS / 64)), n_img);
-    hipLaunchKernelGGL(harris_response_kernel, grid, dim3(HW_THREADS), 0, s, images, rows, cols, k, resp, band);
+    hipLaunchKernelGGL(harris_response_kernel, grid, dim3(HW_THREADS), 0, s, im.img, rows, cols, k, resp, band);
     HIP_TRY(hipGetLastError());
     return VISO_OK;
 }
 
-// kp_out: [n_img][kp_stride] float2, n_out: [n_img]; tmp_*: scratch sized n_img*nbins*per, cnt n_img*nbins.
 // bytes of dynamic LDS the fused detector needs for this bin geometry, or 0 when it does not apply (bins wider than a
 // wave's columns, or beyond 64 KB of responses + pixels)
 size_t harris_fused_lds(int rows, int cols, int nbinx, int nbiny, int per) {
@@ -842,66 +842,63 @@ size_t harris_strip_bytes(int n_img, int rows, int cols, int nbinx, int nbiny, i
 #endif
 }
 
-// images -> corners without a response image (callers check harris_fused_lds first)
-// part: harris_strip_bytes(...) bytes of scratch, or null: the wave-per-bin kernel
-int launch_harris_detect(hipStream_t s, const uint8_t* images, int n_img, int rows, int cols, int n_features, int nbinx,
-                         int nbiny, double k, float2* tmp_kp, float* tmp_resp, int* cnt, float2* kp_out, float* resp_out,
-                         int* n_out, int cap, size_t kp_stride, void* part) {
-    if (n_img <= 0) return VISO_OK;
+// resp: the response images, or null (the fused detector: images -> corners without one; callers check harris_fused_lds first)
+static BinArgs bin_args(const float* resp, const StereoImages& im, int n_img, const HarrisBins& b, const HarrisScratch& t) {
     BinArgs a;
-    a.resp = nullptr; a.rows = rows; a.cols = cols; a.n_img = n_img;
-    a.nbinx = nbinx; a.nbiny = nbiny; a.stridex = cols / nbinx; a.stridey = rows / nbiny;
-    a.per = n_features / (nbinx * nbiny);
-    a.tmp_kp = tmp_kp; a.tmp_resp = tmp_resp; a.cnt = cnt;
-    const int nbins = nbinx * nbiny;
-    const size_t lds = harris_fused_lds(rows, cols, nbinx, nbiny, a.per);
+    a.resp = resp; a.rows = im.rows; a.cols = im.cols; a.n_img = n_img;
+    a.nbinx = b.nbinx; a.nbiny = b.nbiny; a.stridex = im.cols / b.nbinx; a.stridey = im.rows / b.nbiny;
+    a.per = b.n_features / (b.nbinx * b.nbiny);
+    a.tmp_kp = t.tmp_kp; a.tmp_resp = t.tmp_resp; a.cnt = t.cnt;
+    return a;
+}
+
+int launch_harris_detect(hipStream_t s, const StereoImages& im, const HarrisBins& bins, double k, const HarrisScratch& tmp, const HarrisOut& out) {
+    const int n_img = packed_images("harris", im);
+    if (n_img <= 0) return n_img < 0 ? VISO_ERR_ARG : VISO_OK;
+    const BinArgs a = bin_args(nullptr, im, n_img, bins, tmp);
+    const int nbins = a.nbinx * a.nbiny;
+    const size_t lds = harris_fused_lds(a.rows, a.cols, a.nbinx, a.nbiny, a.per);
     if (!lds) { viso_set_error("harris: bin geometry does not fit the fused detector"); return VISO_ERR_UNSUPPORTED; }
 #ifdef VISO_DEBUG_VARIANTS
-    if (part && harris_strip_bytes(n_img, rows, cols, nbinx, nbiny, a.per)) {
+    if (tmp.part && harris_strip_bytes(n_img, a.rows, a.cols, a.nbinx, a.nbiny, a.per)) {
         StripArgs sa;
-        sa.nstrips = (nbinx * a.stridex + HW_DIRECT_MAXW - 1) / HW_DIRECT_MAXW;
-        sa.part = reinterpret_cast<unsigned long long*>(part);
+        sa.nstrips = (a.nbinx * a.stridex + HW_DIRECT_MAXW - 1) / HW_DIRECT_MAXW;
+        sa.part = reinterpret_cast<unsigned long long*>(tmp.part);
         sa.part_cnt = reinterpret_cast<int*>(sa.part + (size_t)n_img * nbins * 2 * a.per);
-        const long long units = (long long)n_img * sa.nstrips * nbiny;
-        hipLaunchKernelGGL(harris_strip_kernel, dim3((unsigned)((units + HW_THREADS / 64 - 1) / (HW_THREADS / 64))), dim3(HW_THREADS), 0, s, a, sa, images, k);
+        const long long units = (long long)n_img * sa.nstrips * a.nbiny;
+        hipLaunchKernelGGL(harris_strip_kernel, dim3((unsigned)((units + HW_THREADS / 64 - 1) / (HW_THREADS / 64))), dim3(HW_THREADS), 0, s, a, sa, im.img, k);
         HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(harris_merge_kernel, dim3((unsigned)(((long long)n_img * nbins + 255) / 256)), dim3(256), 0, s, a, sa);
         HIP_TRY(hipGetLastError());
     } else
 #endif
     {
-        (void)part;
         const dim3 grid((unsigned)(((long long)n_img * nbins + HW_THREADS / 64 - 1) / (HW_THREADS / 64)));
         if (a.stridex <= HW_DIRECT_MAXW) {
-            hipLaunchKernelGGL(harris_detect_kernel<true>, grid, dim3(HW_THREADS), lds, s, a, images, k);
+            hipLaunchKernelGGL(harris_detect_kernel<true>, grid, dim3(HW_THREADS), lds, s, a, im.img, k);
         } else {
             if (lds > 32 * 1024)
                 HIP_TRY(hipFuncSetAttribute((const void*)harris_detect_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(harris_detect_kernel<false>, grid, dim3(HW_THREADS), lds, s, a, images, k);
+            hipLaunchKernelGGL(harris_detect_kernel<false>, grid, dim3(HW_THREADS), lds, s, a, im.img, k);
         }
         HIP_TRY(hipGetLastError());
     }
-    hipLaunchKernelGGL(harris_compact_kernel, dim3(n_img), dim3(256), sizeof(int) * (size_t)(nbins + 1), s, a, kp_out,
-                       resp_out, n_out, cap, kp_stride);
+    hipLaunchKernelGGL(harris_compact_kernel, dim3(n_img), dim3(256), sizeof(int) * (size_t)(nbins + 1), s, a, out.kp_out,
+                       out.resp_out, out.n_out, out.cap, out.kp_stride);
     HIP_TRY(hipGetLastError());
     return VISO_OK;
 }
 
-int launch_harris_bins(hipStream_t s, const float* resp, int n_img, int rows, int cols, int n_features, int nbinx,
-                       int nbiny, float2* tmp_kp, float* tmp_resp, int* cnt, float2* kp_out, float* resp_out,
-                       int* n_out, int cap, size_t kp_stride) {
-    if (n_img <= 0) return VISO_OK;
-    BinArgs a;
-    a.resp = resp; a.rows = rows; a.cols = cols; a.n_img = n_img;
-    a.nbinx = nbinx; a.nbiny = nbiny; a.stridex = cols / nbinx; a.stridey = rows / nbiny;
-    a.per = n_features / (nbinx * nbiny);
-    a.tmp_kp = tmp_kp; a.tmp_resp = tmp_resp; a.cnt = cnt;
-    const int nbins = nbinx * nbiny;
+int launch_harris_bins(hipStream_t s, const float* resp, const StereoImages& im, const HarrisBins& bins, const HarrisScratch& tmp, const HarrisOut& out) {
+    const int n_img = packed_images("harris", im);
+    if (n_img <= 0) return n_img < 0 ? VISO_ERR_ARG : VISO_OK;
+    const BinArgs a = bin_args(resp, im, n_img, bins, tmp);
+    const int nbins = a.nbinx * a.nbiny;
     const long long waves = (long long)n_img * nbins;
     hipLaunchKernelGGL(harris_bins_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, a);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(harris_compact_kernel, dim3(n_img), dim3(256), sizeof(int) * (size_t)(nbins + 1), s, a, kp_out,
-                       resp_out, n_out, cap, kp_stride);
+    hipLaunchKernelGGL(harris_compact_kernel, dim3(n_img), dim3(256), sizeof(int) * (size_t)(nbins + 1), s, a, out.kp_out,
+                       out.resp_out, out.n_out, out.cap, out.kp_stride);
     HIP_TRY(hipGetLastError());
     return VISO_OK;
 }
@@ -922,7 +919,7 @@ extern "C" int viso_harris_response(const uint8_t* img, int rows, int cols, doub
     VISO_TRY(dc.scratch(SLOT_GEN0, px, &dimg));
     VISO_TRY(dc.scratch(SLOT_GEN1, px, &dr));
     VISO_TRY(dc.up(dimg, img, px));
-    VISO_TRY(launch_harris_response(dc.s, dimg, 1, rows, cols, k, dr));
+    VISO_TRY(launch_harris_response(dc.s, image_block(dimg, rows, cols, 0, 1, 1), k, dr));   // frame 0, one frame of one side: one image
     VISO_TRY(dc.down(resp, dr, px));
     return dc.wait();
 }
@@ -948,15 +945,16 @@ extern "C" int viso_detect_harris_binned(const uint8_t* img, int rows, int cols,
     VISO_TRY(dc.scratch(SLOT_HYP_TR, slots, &dko));
     VISO_TRY(dc.scratch(SLOT_GEN6, slots, &dro));
     VISO_TRY(dc.up(dimg, img, px));
+    const StereoImages im = image_block(dimg, rows, cols, 0, 1, 1);   // one image
+    const HarrisBins bins = {n_features, nbinx, nbiny};
+    const HarrisOut ko = {dko, dro, dcnt + nbins, (int)slots, slots};
     if (harris_fused_lds(rows, cols, nbinx, nbiny, per)) {
         char* part = nullptr;   // one image never fills the GPU with strips: only when $VISO_HARRIS_STRIPS=1 forces them (tests)
         if (const size_t pb = harris_strip_bytes(1, rows, cols, nbinx, nbiny, per)) VISO_TRY(dc.scratch(SLOT_HARRIS_STRIPS, pb, &part));
-        VISO_TRY(launch_harris_detect(dc.s, dimg, 1, rows, cols, n_features, nbinx, nbiny, k, dtk, dtr, dcnt, dko, dro, dcnt + nbins,
-                                      (int)slots, slots, part));
+        VISO_TRY(launch_harris_detect(dc.s, im, bins, k, HarrisScratch{dtk, dtr, dcnt, part}, ko));
     } else {
-        VISO_TRY(launch_harris_response(dc.s, dimg, 1, rows, cols, k, dr));
-        VISO_TRY(launch_harris_bins(dc.s, dr, 1, rows, cols, n_features, nbinx, nbiny, dtk, dtr, dcnt, dko, dro, dcnt + nbins, (int)slots,
-                                    slots));
+        VISO_TRY(launch_harris_response(dc.s, im, k, dr));
+        VISO_TRY(launch_harris_bins(dc.s, dr, im, bins, HarrisScratch{dtk, dtr, dcnt, nullptr}, ko));
     }
     VISO_TRY(dc.down(&n, dcnt + nbins, 1));
     VISO_TRY(dc.wait());

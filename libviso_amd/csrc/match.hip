@@ -1017,10 +1017,10 @@ const char* matcher_kernel_name(int variant) {
 // layout 0: problems in any order (both instantiations enumerate all of them);
 // layout 1: the batch order [8 stereo][8 temporal-left][8 temporal-right] per 8 frames.
 // e0/e1 (may be null) bracket the kernel that takes the temporal problems: the dominant kernel.
-int launch_match_timed(hipStream_t s, const MatchProblem* probs_dev, int n_probs, int cap_max,
-                       int dlen, const MatchParamsDev mp[2], int* bad,
-                       hipEvent_t e0, hipEvent_t e1, int layout, int variant,
-                       const int2* ovf_q, const int* ovf_cnt, int r8s, int general_possible, int kinds) {
+int launch_match(hipStream_t s, const MatchProblem* probs_dev, int n_probs, int cap_max,
+                 int dlen, const MatchParamsDev mp[2], int* bad,
+                 hipEvent_t e0, hipEvent_t e1, int layout, int variant,
+                 const int2* ovf_q, const int* ovf_cnt, int r8s, int general_possible, int kinds) {
     if (n_probs <= 0 || cap_max <= 0) return VISO_OK;
     variant = matcher_effective(variant, dlen);
     MatchArgs a;
@@ -1064,11 +1064,6 @@ int launch_match_timed(hipStream_t s, const MatchProblem* probs_dev, int n_probs
         HIP_TRY(hipGetLastError());
     }
     return VISO_OK;
-}
-
-int launch_match(hipStream_t s, const MatchProblem* probs_dev, int n_probs, int cap_max, int dlen,
-                 const MatchParamsDev mp[2], int* bad, int variant, const int2* ovf_q, const int* ovf_cnt, int r8s) {
-    return launch_match_timed(s, probs_dev, n_probs, cap_max, dlen, mp, bad, nullptr, nullptr, 0, variant, ovf_q, ovf_cnt, r8s);
 }
 
 

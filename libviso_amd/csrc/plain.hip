@@ -193,7 +193,7 @@ struct PlainSlot {
 struct FrameMisc {
     int pad0[6];
     int ovf_cnt;                  // length of the overflow queue (MatchProblem::ovf_cnt)
-    int bad[2];                   // launch_match_timed's `bad`: [0] "an image of this launch may be flagged", set in the head, read by the general kernels
+    int bad[2];                   // launch_match's `bad`: [0] "an image of this launch may be flagged", set in the head, read by the general kernels
                                   // (clear: they leave at once); [1] tiles match_stereo_kernel declined: it counts, match_batch_kernel<1> and the host read
     int pad1[7];
     struct { int m_cnt; int pad; unsigned long long scored; } prob[PF_PROBS];   // matches and scored pairs of problem p
@@ -776,7 +776,7 @@ static int frame_queue_first(viso_ctx* c, PlainCache* pc, FramePlan& P) {
     // the number of declined tiles comes back with the results, and a launch that had one without the kernel is repeated
     P.skip_wide = P.stereo && pc->narrow_streak >= 2 && !P.force_general;
     if (P.skip_wide) kinds |= VISO_KIND_NO_WIDE;
-    if ((r = launch_match_timed(c->stream, dprob, P.np, P.cap, P.dlen, mpd, dmisc->bad, nullptr, nullptr, 0, P.variant, frame_dev<const int2>(f, f.o_ovf),
+    if ((r = launch_match(c->stream, dprob, P.np, P.cap, P.dlen, mpd, dmisc->bad, nullptr, nullptr, 0, P.variant, frame_dev<const int2>(f, f.o_ovf),
                                 &dmisc->ovf_cnt, P.r8s, P.need_general ? 1 : 0, kinds)) < 0) return r;
     if (!P.spec_x) return launch_sort(c->stream, dprob, P.np, P.cap, P.need_general ? 0 : 1);
     SolverParamsDev sp; fill_solver_params(&sp, &pc->tri_p);   // collect_matches / triangulate_rectified of the stereo list ride in the sort kernel

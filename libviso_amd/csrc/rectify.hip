@@ -179,18 +179,17 @@ __global__ __launch_bounds__(RECT_THREADS) void rectify_remap_kernel(RectArgs a,
     }
 }
 
-int launch_rectify(hipStream_t s, const uint8_t* raw, size_t raw_fs, size_t raw_ss, int raw_cols, uint8_t* out, size_t out_fs,
-                   size_t out_ss, const RectEntry* map, int out_rows, int out_cols, int n_frames, int sides, int border) {
-    if (n_frames <= 0) return VISO_OK;
+int launch_rectify(hipStream_t s, const StereoImages& raw, const StereoImages& out, const RectEntry* map, int border) {
+    if (out.n <= 0) return VISO_OK;
     RectArgs a;
-    a.raw = raw; a.raw_fs = raw_fs; a.raw_ss = raw_ss;
-    a.out = out; a.out_fs = out_fs; a.out_ss = out_ss;
-    a.map = map; a.per = out_rows * out_cols;
-    a.n_frames = n_frames; a.border = border;
-    const dim3 grid((unsigned)((a.per + RECT_TILE - 1) / RECT_TILE), (unsigned)sides, (unsigned)((n_frames + RECT_FPB - 1) / RECT_FPB));
-    const bool dw = (a.per % 4 == 0) && (out_fs % 4 == 0) && (out_ss % 4 == 0) && ((uintptr_t)out % 4 == 0);
-    if (dw) hipLaunchKernelGGL(rectify_remap_kernel<true>, grid, dim3(RECT_THREADS), 0, s, a, raw_cols);
-    else hipLaunchKernelGGL(rectify_remap_kernel<false>, grid, dim3(RECT_THREADS), 0, s, a, raw_cols);
+    a.raw = raw.img; a.raw_fs = raw.fs; a.raw_ss = raw.ss;
+    a.out = out.img; a.out_fs = out.fs; a.out_ss = out.ss;
+    a.map = map; a.per = out.rows * out.cols;
+    a.n_frames = out.n; a.border = border;
+    const dim3 grid((unsigned)((a.per + RECT_TILE - 1) / RECT_TILE), out.ss ? 2u : 1u, (unsigned)((out.n + RECT_FPB - 1) / RECT_FPB));
+    const bool dw = (a.per % 4 == 0) && (out.fs % 4 == 0) && (out.ss % 4 == 0) && ((uintptr_t)out.img % 4 == 0);
+    if (dw) hipLaunchKernelGGL(rectify_remap_kernel<true>, grid, dim3(RECT_THREADS), 0, s, a, raw.cols);
+    else hipLaunchKernelGGL(rectify_remap_kernel<false>, grid, dim3(RECT_THREADS), 0, s, a, raw.cols);
     HIP_TRY(hipGetLastError());
     return VISO_OK;
 }
@@ -215,7 +214,7 @@ extern "C" int viso_rectify_images(const uint8_t* raw, int n, int raw_rows, int 
     VISO_TRY(dc.scratch(SLOT_RECT_MAP, oper, &dmap));
     VISO_TRY(dc.up(draw, raw, rper * (size_t)n));
     VISO_TRY(dc.up(dmap, q.data(), oper));
-    VISO_TRY(launch_rectify(dc.s, draw, rper, 0, raw_cols, dout, oper, 0, dmap, out_rows, out_cols, n, 1, border));
+    VISO_TRY(launch_rectify(dc.s, image_block(draw, raw_rows, raw_cols, 0, n, 1), image_block(dout, out_rows, out_cols, 0, n, 1), dmap, border));
     VISO_TRY(dc.down(out, dout, oper * (size_t)n));
     return dc.wait();
 }

@@ -232,28 +232,27 @@ int sgm_group_frames(const char* where, int rows, int cols, int D, int n_frames,
     return g_sgm_cap.frames(where, rows, cols, sgm_frame_bytes(rows, cols, D), n_frames, 16384, group);   // 2 * group workgroups along the census grid's z
 }
 
-int launch_sgm(hipStream_t s, const uint8_t* img, size_t fs, size_t ss, int rows, int cols, int n_frames, const viso_sgm_params* p,
-               int16_t* out, size_t ofs, void* ws, int group) {
-    if (n_frames <= 0) return VISO_OK;
+int launch_sgm(hipStream_t s, const StereoImages& im, const viso_sgm_params* p, int16_t* out, size_t ofs, void* ws, int group) {
+    if (im.n <= 0) return VISO_OK;
     const int D = p->num_disp;
-    const size_t px = (size_t)rows * cols;
+    const size_t px = im.px();
     const size_t cen_bytes = al256(px * 2 * sizeof(unsigned long long));
-    const size_t per = sgm_frame_bytes(rows, cols, D);
+    const size_t per = sgm_frame_bytes(im.rows, im.cols, D);
     static const int dirs[8][2] = {{1, 0}, {-1, 0}, {0, 1}, {0, -1}, {1, 1}, {-1, 1}, {1, -1}, {-1, -1}};
     const int K = (D + 63) / 64;
-    for (int f0 = 0; f0 < n_frames; f0 += group) {
-        const int nf = n_frames - f0 < group ? n_frames - f0 : group;
+    for (int f0 = 0; f0 < im.n; f0 += group) {
+        const int nf = im.n - f0 < group ? im.n - f0 : group;
         unsigned long long* cen = reinterpret_cast<unsigned long long*>(ws);
         uint16_t* S = reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(ws) + cen_bytes);
-        const uint8_t* im = img + (size_t)f0 * fs;
-        hipLaunchKernelGGL(sgm_census_kernel, dim3((unsigned)((cols + 255) / 256), (unsigned)rows, (unsigned)(2 * nf)), dim3(256), 0, s,
-                           im, fs, ss, rows, cols, cen, per / sizeof(unsigned long long));
+        const uint8_t* img = im.img + (size_t)f0 * im.fs;
+        hipLaunchKernelGGL(sgm_census_kernel, dim3((unsigned)((im.cols + 255) / 256), (unsigned)im.rows, (unsigned)(2 * nf)), dim3(256), 0, s,
+                           img, im.fs, im.ss, im.rows, im.cols, cen, per / sizeof(unsigned long long));
         SgmPathArgs a;
         a.cen = cen; a.cfs = per / sizeof(unsigned long long); a.S = S; a.sfs = per / sizeof(uint16_t);
-        a.rows = rows; a.cols = cols; a.D = D; a.P1 = p->p1; a.P2 = p->p2;
+        a.rows = im.rows; a.cols = im.cols; a.D = D; a.P1 = p->p1; a.P2 = p->p2;
         for (int r = 0; r < p->paths; ++r) {
             a.dx = dirs[r][0]; a.dy = dirs[r][1]; a.first = r == 0;
-            const dim3 grid((unsigned)(a.dy == 0 ? rows : cols), (unsigned)nf);
+            const dim3 grid((unsigned)(a.dy == 0 ? im.rows : im.cols), (unsigned)nf);
             switch (K) {
                 case 1: hipLaunchKernelGGL(sgm_path_kernel<1>, grid, dim3(64), 0, s, a); break;
                 case 2: hipLaunchKernelGGL(sgm_path_kernel<2>, grid, dim3(64), 0, s, a); break;
@@ -263,8 +262,8 @@ int launch_sgm(hipStream_t s, const uint8_t* img, size_t fs, size_t ss, int rows
         }
         SgmSelArgs e;
         e.S = S; e.sfs = per / sizeof(uint16_t); e.out = out + (size_t)f0 * ofs; e.ofs = ofs;
-        e.rows = rows; e.cols = cols; e.D = D; e.u = p->uniqueness; e.m = p->lr_max_diff;
-        hipLaunchKernelGGL(sgm_select_kernel, dim3((unsigned)rows, (unsigned)nf), dim3(SGM_SEL_THREADS), 0, s, e);
+        e.rows = im.rows; e.cols = im.cols; e.D = D; e.u = p->uniqueness; e.m = p->lr_max_diff;
+        hipLaunchKernelGGL(sgm_select_kernel, dim3((unsigned)im.rows, (unsigned)nf), dim3(SGM_SEL_THREADS), 0, s, e);
         HIP_TRY(hipGetLastError());
     }
     return VISO_OK;
@@ -291,7 +290,7 @@ extern "C" int viso_stereo_sgm(const uint8_t* left, const uint8_t* right, int ro
     VISO_TRY(dc.scratch(SLOT_GEN2, sgm_frame_bytes(rows, cols, params->num_disp), &ws));
     VISO_TRY(dc.up(dimg, left, per));
     VISO_TRY(dc.up(dimg + per, right, per));
-    VISO_TRY(launch_sgm(dc.s, dimg, 2 * per, per, rows, cols, 1, params, dout, per, ws, 1));
+    VISO_TRY(launch_sgm(dc.s, image_block(dimg, rows, cols, 0, 1), params, dout, per, ws, 1));
     VISO_TRY(dc.down(out, dout, per));
     return dc.wait();
 }

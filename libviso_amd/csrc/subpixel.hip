@@ -227,20 +227,18 @@ __global__ __launch_bounds__(SUBPIX_THREADS) void subpixel_refine_kernel(SubpixA
     }
 }
 
-int launch_subpixel(hipStream_t s, const uint8_t* images, size_t img_stride, size_t r_off, int rows, int cols, const float2* kp,
-                    size_t kp_stride, int cap, const int* lists, size_t list_stride, const int* m_cnt, int n_frames, int mode, float2* uv,
-                    const uint16_t* lrows, size_t lrows_stride, const int* lrank, size_t lrank_stride) {
-    if (n_frames <= 0 || cap <= 0) return VISO_OK;
+int launch_subpixel(hipStream_t s, const StereoImages& im, const SubpixLists& l, int mode, float2* uv, const SubpixLeftRows& left) {
+    if (im.n <= 0 || l.cap <= 0) return VISO_OK;
     SubpixArgs a;
-    a.images = images; a.img_stride = img_stride; a.r_off = r_off; a.rows = rows; a.cols = cols;
-    a.kp = kp; a.kp_stride = kp_stride; a.cap = cap;
-    a.lists = lists; a.list_stride = list_stride; a.m_cnt = m_cnt;
-    a.lrows = lrows; a.lrows_stride = lrows_stride; a.lrank = lrank; a.lrank_stride = lrank_stride;
+    a.images = im.img; a.img_stride = im.fs; a.r_off = im.ss; a.rows = im.rows; a.cols = im.cols;
+    a.kp = l.kp; a.kp_stride = l.kp_stride; a.cap = l.cap;
+    a.lists = l.lists; a.list_stride = l.list_stride; a.m_cnt = l.m_cnt;
+    a.lrows = left.lrows; a.lrows_stride = left.lrows_stride; a.lrank = left.lrank; a.lrank_stride = left.lrank_stride;
     a.uv = uv; a.mode = mode;
     const int per_block = SUBPIX_WPB * SUBPIX_GPW;
-    const int gx = min(SUBPIX_BLOCKS_PER_FRAME, (cap + per_block - 1) / per_block);
-    if (lrows) hipLaunchKernelGGL(subpixel_refine_kernel<true>, dim3(gx, n_frames), dim3(SUBPIX_THREADS), 0, s, a);
-    else hipLaunchKernelGGL(subpixel_refine_kernel<false>, dim3(gx, n_frames), dim3(SUBPIX_THREADS), 0, s, a);
+    const int gx = min(SUBPIX_BLOCKS_PER_FRAME, (l.cap + per_block - 1) / per_block);
+    if (left.lrows) hipLaunchKernelGGL(subpixel_refine_kernel<true>, dim3(gx, im.n), dim3(SUBPIX_THREADS), 0, s, a);
+    else hipLaunchKernelGGL(subpixel_refine_kernel<false>, dim3(gx, im.n), dim3(SUBPIX_THREADS), 0, s, a);
     HIP_TRY(hipGetLastError());
     return VISO_OK;
 }
@@ -276,8 +274,8 @@ extern "C" int viso_refine_stereo_subpixel(const uint8_t* imgL, const uint8_t* i
     VISO_TRY(dc.up(dkp + capn, kp2, 2 * (size_t)n2));
     VISO_TRY(dc.up(dlist, match, 3 * (size_t)n));
     VISO_TRY(dc.up(dlist + 3 * (size_t)n, &n, 1));
-    VISO_TRY(launch_subpixel(dc.s, dimg, 2 * per, per, rows, cols, dkp, 2 * (size_t)capn, capn, dlist, 3 * (size_t)n, dlist + 3 * (size_t)n,
-                             1, mode, duv, nullptr, 0, nullptr, 0));
+    const SubpixLists lists = {dkp, 2 * (size_t)capn, capn, dlist, 3 * (size_t)n, dlist + 3 * (size_t)n};
+    VISO_TRY(launch_subpixel(dc.s, image_block(dimg, rows, cols, 0, 1), lists, mode, duv));
     VISO_TRY(dc.down(out_uv, duv, 2 * (size_t)n));
     return dc.wait();
 }
