@@ -1,4 +1,5 @@
-"""ctypes view of include/viso_hip.h (POD structs + prototypes).
+"""ctypes view of include/viso_hip.h: the POD structs, the records as numpy dtypes, and PROTOTYPES, the one table of every
+function's restype and argtypes (declare() applies it to a loaded library; tests/test_cabi_cpu.py holds it to the header).
 
 Test/bench plumbing only: the product is the C-ABI library itself
 (libviso_amd/csrc -> libviso_hip.so) and the C++ host mirror in
@@ -101,66 +102,9 @@ u8p = C.POINTER(C.c_uint8)
 intp = C.POINTER(C.c_int)
 
 
-def declare_common(lib, prefix):
-    """Prototypes shared by libviso_hip.so (prefix 'viso_') and the oracle
-    (prefix 'oracle_'): same POD signatures, include/viso_hip.h."""
-    def fn(name, restype, argtypes):
-        f = getattr(lib, prefix + name)
-        f.restype = restype
-        f.argtypes = argtypes
-        return f
-
-    MP = C.POINTER(MatchParams)
-    PP = C.POINTER(Param)
-    fn("match_circle", C.c_int, [i32p, C.c_int, i32p, C.c_int, i32p, C.c_int, i32p, C.c_int,
-                                  i32p, i32p, C.c_int, intp])
-    fn("collect_matches", C.c_int, [f32p, C.c_int, f32p, C.c_int, i32p, C.c_int, f64p])
-    fn("triangulate_rectified", C.c_int, [f64p, C.c_int, PP, f64p])
-    fn("get_inliers", C.c_int, [f64p, f64p, C.c_int, f64p, PP, i32p, intp, f64p])
-    fn("ransac_minimize_reproj", C.c_int, [f64p, f64p, C.c_int, f64p, i32p, intp, PP, i32p,
-                                           C.c_uint64, C.c_uint64])
-    fn("ransac_samples", None, [C.c_uint64, C.c_uint64, C.c_int, C.c_int, i32p])
-    fn("tr2mat", None, [f64p, f64p])
-    fn("pose_update", None, [f64p, f64p, f64p])
-    fn("F_from_P", None, [f64p, f64p, f64p])
-    fn("extract_descriptors", C.c_int, [u8p, C.c_int, C.c_int, f32p, C.c_int, C.c_int, f32p])
-    return MP, PP
-
-
-def declare_subpixel(lib):
-    """Prototypes of the opt-in sub-pixel stereo refinement (include/viso_hip.h; libviso_hip.so only)."""
-    u8p = C.POINTER(C.c_uint8)
-    lib.viso_batch_set_subpixel.argtypes = [C.c_void_p, C.c_int]
-    lib.viso_batch_get_subpixel.argtypes = [C.c_void_p, C.c_int, f32p, intp]
-    lib.viso_refine_stereo_subpixel.argtypes = [u8p, u8p, C.c_int, C.c_int, f32p, C.c_int, f32p, C.c_int, i32p, C.c_int,
-                                                C.c_int, f32p]
-
-
-def declare_rectify(lib):
-    """Prototypes of the opt-in rectification of raw images (include/viso_hip.h; libviso_hip.so only)."""
-    u8p = C.POINTER(C.c_uint8)
-    lib.viso_rectify_map.argtypes = [f64p, f64p, f64p, f64p, C.c_int, C.c_int, f32p, f32p]
-    lib.viso_batch_set_rectify.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, f32p, f32p, f32p, f32p, C.c_int]
-    lib.viso_batch_get_image.argtypes = [C.c_void_p, C.c_int, C.c_int, u8p]
-    lib.viso_batch_get_image_geometry.argtypes = [C.c_void_p, intp, intp]
-    lib.viso_rectify_images.argtypes = [u8p, C.c_int, C.c_int, C.c_int, f32p, f32p, C.c_int, C.c_int, C.c_int, u8p]
-
-
 class DisparityParams(C.Structure):
     """struct viso_disparity_params (include/viso_hip.h, "dense stereo disparity")."""
     _fields_ = [(name, C.c_int32) for name in ("num_disp", "block", "prefilter_cap", "texture_threshold", "uniqueness", "lr_max_diff")]
-
-
-def declare_disparity(lib):
-    """Prototypes of the opt-in dense disparity (include/viso_hip.h; libviso_hip.so only)."""
-    u8p, i16p, DP = C.POINTER(C.c_uint8), C.POINTER(C.c_int16), C.POINTER(DisparityParams)
-    lib.viso_disparity_params_default.restype = None
-    lib.viso_disparity_params_default.argtypes = [DP]
-    lib.viso_stereo_disparity.argtypes = [u8p, u8p, C.c_int, C.c_int, DP, i16p]
-    lib.viso_batch_set_disparity.argtypes = [C.c_void_p, DP]
-    lib.viso_batch_run_disparity.argtypes = [C.c_void_p]
-    lib.viso_batch_get_disparity.argtypes = [C.c_void_p, C.c_int, i16p]
-    lib.viso_batch_get_disparities.argtypes = [C.c_void_p, i16p]
 
 
 class SgmParams(C.Structure):
@@ -176,17 +120,6 @@ class SgmParams(C.Structure):
 SGM_DEFAULTS = dict(num_disp=128, p1=10, p2=120, paths=8, uniqueness=10, lr_max_diff=1)   # viso_sgm_params_default
 
 
-def declare_sgm(lib):
-    """Prototypes of the opt-in semi-global matching (include/viso_hip.h; libviso_hip.so only)."""
-    u8p, i16p, SP = C.POINTER(C.c_uint8), C.POINTER(C.c_int16), C.POINTER(SgmParams)
-    lib.viso_sgm_params_default.restype = None
-    lib.viso_sgm_params_default.argtypes = [SP]
-    lib.viso_stereo_sgm.argtypes = [u8p, u8p, C.c_int, C.c_int, SP, i16p]
-    lib.viso_batch_set_sgm.argtypes = [C.c_void_p, SP]
-    lib.viso_sgm_set_workspace_cap.restype = None
-    lib.viso_sgm_set_workspace_cap.argtypes = [C.c_size_t]
-
-
 class SpeckleParams(C.Structure):
     """struct viso_speckle_params (include/viso_hip.h, "speckle filter and 3-D reprojection of the maps")."""
     _fields_ = [(name, C.c_int32) for name in ("max_size", "max_diff")]
@@ -197,19 +130,6 @@ class SpeckleParams(C.Structure):
 
 
 SPECKLE_DEFAULTS = dict(max_size=100, max_diff=16)   # viso_speckle_params_default
-
-
-def declare_speckle(lib):
-    """Prototypes of the opt-in speckle filter and reprojection (include/viso_hip.h; libviso_hip.so only)."""
-    i16p, KP = C.POINTER(C.c_int16), C.POINTER(SpeckleParams)
-    lib.viso_speckle_params_default.restype = None
-    lib.viso_speckle_params_default.argtypes = [KP]
-    lib.viso_filter_speckles.argtypes = [i16p, C.c_int, C.c_int, KP]
-    lib.viso_batch_set_speckle.argtypes = [C.c_void_p, KP]
-    lib.viso_speckle_set_workspace_cap.restype = None
-    lib.viso_speckle_set_workspace_cap.argtypes = [C.c_size_t]
-    lib.viso_disparity_to_points.argtypes = [i16p, C.c_int, C.c_int, C.POINTER(Param), f64p, C.c_int, f32p]
-    lib.viso_batch_get_disparity_points.argtypes = [C.c_void_p, C.c_int, f64p, C.c_int, f32p]
 
 
 class MapParams(C.Structure):
@@ -232,36 +152,9 @@ class MapCounters(C.Structure):
     _fields_ = [(name, C.c_uint64) for name in ("n_points", "n_inserts", "n_out_of_range", "n_dropped", "n_occupied")]
 
 
-def declare_map(lib):
-    """Prototypes of the opt-in voxel map (include/viso_hip.h; libviso_hip.so only)."""
-    i16p, MPP, vp = C.POINTER(C.c_int16), C.POINTER(MapParams), C.c_void_p
-    lib.viso_map_params_default.restype = None
-    lib.viso_map_params_default.argtypes = [MPP]
-    lib.viso_map_create.argtypes = [vp, MPP, C.POINTER(vp)]
-    lib.viso_map_destroy.argtypes = [vp]
-    lib.viso_map_clear.argtypes = [vp]
-    lib.viso_map_fuse.argtypes = [vp, i16p, C.c_int, C.c_int, C.POINTER(Param), f64p]
-    lib.viso_batch_fuse_disparities.argtypes = [vp, vp, C.c_int, C.c_int, f64p]
-    lib.viso_map_add_entries.argtypes = [vp, vp, C.c_size_t]
-    lib.viso_map_count.argtypes = [vp, C.c_uint32, C.POINTER(C.c_size_t)]
-    lib.viso_map_get.argtypes = [vp, C.c_uint32, vp, C.c_size_t, C.POINTER(C.c_size_t)]
-    lib.viso_map_stats.argtypes = [vp, C.POINTER(MapCounters)]
-    lib.viso_map_entry_centroid.argtypes = [vp, C.c_double, f32p]
-
-
 class VoxelBox(C.Structure):
     """struct viso_voxel_box (include/viso_hip.h, "Map eviction")."""
     _fields_ = [("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3)]
-
-
-def declare_evict(lib):
-    """Prototypes of the maps' eviction (include/viso_hip.h, "Map eviction")."""
-    vp, szp, BP = C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(VoxelBox)
-    lib.viso_voxel_box_around.argtypes = [f64p, C.c_double, C.c_double, BP]
-    for kind in ("map", "tsdf"):
-        getattr(lib, f"viso_{kind}_evict_count").argtypes = [vp, BP, szp]
-        getattr(lib, f"viso_{kind}_evict").argtypes = [vp, BP, vp, C.c_size_t, szp]
-    lib.viso_tsdf_evict_gray.argtypes = [vp, BP, vp, C.c_size_t, szp]
 
 
 class TsdfParams(C.Structure):
@@ -291,48 +184,6 @@ class TsdfCounters(C.Structure):
     _fields_ = [(name, C.c_uint64) for name in ("n_points", "n_updates", "n_out_of_range", "n_dropped", "n_occupied")]
 
 
-def declare_tsdf(lib):
-    """Prototypes of the opt-in TSDF map (include/viso_hip.h; libviso_hip.so only)."""
-    i16p, TPP, vp, szp = C.POINTER(C.c_int16), C.POINTER(TsdfParams), C.c_void_p, C.POINTER(C.c_size_t)
-    lib.viso_tsdf_params_default.restype = None
-    lib.viso_tsdf_params_default.argtypes = [TPP]
-    lib.viso_tsdf_create.argtypes = [vp, TPP, C.POINTER(vp)]
-    lib.viso_tsdf_destroy.argtypes = [vp]
-    lib.viso_tsdf_clear.argtypes = [vp]
-    lib.viso_tsdf_fuse.argtypes = [vp, i16p, C.c_int, C.c_int, C.POINTER(Param), f64p]
-    lib.viso_batch_fuse_tsdf.argtypes = [vp, vp, C.c_int, C.c_int, f64p]
-    lib.viso_tsdf_add_entries.argtypes = [vp, vp, C.c_size_t]
-    lib.viso_tsdf_count.argtypes = [vp, C.c_uint32, szp]
-    lib.viso_tsdf_get.argtypes = [vp, C.c_uint32, vp, C.c_size_t, szp]
-    lib.viso_tsdf_surface_count.argtypes = [vp, C.c_uint32, szp]
-    lib.viso_tsdf_surface.argtypes = [vp, C.c_uint32, vp, C.c_size_t, szp]
-    lib.viso_tsdf_stats.argtypes = [vp, C.POINTER(TsdfCounters)]
-    lib.viso_tsdf_crossing_point.argtypes = [vp, C.c_double, f32p]
-    lib.viso_tsdf_mesh_count.argtypes = [vp, C.c_uint32, szp, szp]
-    lib.viso_tsdf_mesh.argtypes = [vp, C.c_uint32, vp, C.c_size_t, vp, C.c_size_t, szp, szp]
-    lib.viso_tsdf_render.argtypes = [vp, C.c_uint32, C.POINTER(Param), C.c_int, C.c_int, C.c_double, f64p, C.c_int, i16p,
-                                     C.POINTER(C.c_uint32)]
-    if hasattr(lib, "viso_tsdf_create_gray"):   # (absent from older builds of the library: VISO_HIP_SO A/B runs)
-        declare_tsdf_gray(lib)
-    if hasattr(lib, "viso_tsdf_linearize"):
-        declare_tsdf_align(lib)
-    if hasattr(lib, "viso_tsdf_linearize_gray"):
-        declare_tsdf_align_gray(lib)
-
-
-def declare_tsdf_gray(lib):
-    """Prototypes of the gray TSDF map (include/viso_hip.h, "TSDF intensity")."""
-    i16p, u8p, vp, szp = C.POINTER(C.c_int16), C.POINTER(C.c_uint8), C.c_void_p, C.POINTER(C.c_size_t)
-    lib.viso_tsdf_create_gray.argtypes = [vp, C.POINTER(TsdfParams), C.POINTER(vp)]
-    lib.viso_tsdf_is_gray.argtypes = [vp, C.POINTER(C.c_int)]
-    lib.viso_tsdf_fuse_gray.argtypes = [vp, i16p, u8p, C.c_int, C.c_int, C.POINTER(Param), f64p]
-    lib.viso_tsdf_get_gray.argtypes = [vp, C.c_uint32, vp, C.c_size_t, szp]
-    lib.viso_tsdf_add_gray_entries.argtypes = [vp, vp, C.c_size_t]
-    lib.viso_tsdf_vertex_gray.argtypes = [vp, vp, C.c_size_t, u8p, szp]
-    lib.viso_tsdf_render_gray.argtypes = [vp, C.c_uint32, C.POINTER(Param), C.c_int, C.c_int, C.c_double, f64p, C.c_int, i16p,
-                                          C.POINTER(C.c_uint32), u8p]
-
-
 class TsdfAlignParams(C.Structure):
     """struct viso_tsdf_align_params (include/viso_hip.h, "TSDF align")."""
     _fields_ = [("min_weight", C.c_uint32), ("gate_voxels", C.c_double), ("max_iters", C.c_int32), ("eps_rot", C.c_double),
@@ -352,16 +203,6 @@ TSDF_NORMAL_DTYPE = np.dtype([("n", np.int64, (28,))] + [(name, np.uint64) for n
 TSDF_ALIGNMENT_DTYPE = np.dtype([("pose", np.float64, (4, 4)), ("cov", np.float64, (6, 6)), ("cost", np.float64), ("n_used", np.uint64),
                                  ("iters", np.int32), ("status", np.int32)])
 TSDF_ALIGN_STEP_DTYPE = np.dtype([("pose", np.float64, (4, 4)), ("normal", TSDF_NORMAL_DTYPE)])
-
-
-def declare_tsdf_align(lib):
-    """Prototypes of the frame-to-model alignment (include/viso_hip.h, "TSDF align")."""
-    i16p, vp, APP = C.POINTER(C.c_int16), C.c_void_p, C.POINTER(TsdfAlignParams)
-    lib.viso_tsdf_align_params_default.restype = None
-    lib.viso_tsdf_align_params_default.argtypes = [APP]
-    lib.viso_tsdf_linearize.argtypes = [vp, APP, i16p, C.c_int, C.c_int, C.POINTER(Param), f64p, vp]
-    lib.viso_tsdf_align.argtypes = [vp, APP, i16p, C.c_int, C.c_int, C.POINTER(Param), f64p, vp, vp, C.c_int]
-    lib.viso_batch_align_tsdf.argtypes = [vp, vp, C.c_int, C.c_int, f64p, APP, vp]
 
 
 class TsdfAlignGrayParams(C.Structure):
@@ -385,16 +226,6 @@ TSDF_ALIGNMENT_GRAY_DTYPE = np.dtype([("pose", np.float64, (4, 4)), ("cov", np.f
 TSDF_ALIGN_GRAY_STEP_DTYPE = np.dtype([("pose", np.float64, (4, 4)), ("normal", TSDF_NORMAL_GRAY_DTYPE)])
 
 
-def declare_tsdf_align_gray(lib):
-    """Prototypes of the photometric frame-to-model alignment (include/viso_hip.h, "TSDF photometric align")."""
-    i16p, u8p, vp, GPP = C.POINTER(C.c_int16), C.POINTER(C.c_uint8), C.c_void_p, C.POINTER(TsdfAlignGrayParams)
-    lib.viso_tsdf_align_gray_params_default.restype = None
-    lib.viso_tsdf_align_gray_params_default.argtypes = [GPP]
-    lib.viso_tsdf_linearize_gray.argtypes = [vp, GPP, i16p, u8p, C.c_int, C.c_int, C.POINTER(Param), f64p, vp]
-    lib.viso_tsdf_align_gray.argtypes = [vp, GPP, i16p, u8p, C.c_int, C.c_int, C.POINTER(Param), f64p, vp, vp, C.c_int]
-    lib.viso_batch_align_tsdf_gray.argtypes = [vp, vp, C.c_int, C.c_int, f64p, GPP, vp]
-
-
 class MotionCov(C.Structure):
     """struct viso_motion_cov (include/viso_hip.h, "motion covariance")."""
     _fields_ = [
@@ -413,32 +244,11 @@ MOTION_COV_DTYPE = np.dtype([("cov", np.float64, (6, 6)), ("delta", np.float64, 
 assert MOTION_COV_DTYPE.itemsize == C.sizeof(MotionCov) == 360
 
 
-def declare_covariance(lib):
-    """Prototypes of the opt-in motion covariance (include/viso_hip.h; libviso_hip.so only)."""
-    vp = C.c_void_p
-    lib.viso_batch_set_covariance.argtypes = [vp, C.c_int, C.c_double]
-    lib.viso_batch_get_covariance.argtypes = [vp, C.c_int, vp]
-    lib.viso_batch_get_covariances.argtypes = [vp, vp]
-    lib.viso_batch_get_points.argtypes = [vp, C.c_int, f64p, f64p, intp]
-    lib.viso_pose_covariance.argtypes = [f64p, f64p, C.c_int, f64p, i32p, C.c_int, C.POINTER(Param), C.c_int, C.c_double, vp]
-    lib.viso_chain_covariances.argtypes = [f64p, i32p, vp, C.c_int, f64p, i32p, intp]
-
-
 # struct viso_motion_refine (include/viso_hip.h, "motion refinement") as a numpy structured dtype (Batch.refines, pose_refine)
 MOTION_REFINE_DTYPE = np.dtype([("tr", np.float64, 6), ("cov", np.float64, (6, 6)), ("sigma2", np.float64), ("cost0", np.float64),
                                 ("cost", np.float64), ("gap", np.float64), ("iters", np.int32), ("status", np.int32),
                                 ("n", np.int32), ("_pad", np.int32)])
 assert MOTION_REFINE_DTYPE.itemsize == 384
-
-
-def declare_refine(lib):
-    """Prototypes of the opt-in motion refinement (include/viso_hip.h; libviso_hip.so only)."""
-    vp = C.c_void_p
-    lib.viso_batch_set_refine.argtypes = [vp, C.c_int, C.c_double]
-    lib.viso_batch_get_refine.argtypes = [vp, C.c_int, vp]
-    lib.viso_batch_get_refines.argtypes = [vp, vp]
-    lib.viso_batch_get_refined_points.argtypes = [vp, C.c_int, i32p, f64p, intp]
-    lib.viso_pose_refine.argtypes = [f64p, f64p, C.c_int, f64p, i32p, C.c_int, C.POINTER(Param), C.c_int, C.c_double, vp, f64p]
 
 
 # struct viso_window_record (include/viso_hip.h, "window refinement") as a numpy structured dtype (Batch.window_refines, window_refine)
@@ -449,10 +259,219 @@ WINDOW_RECORD_DTYPE = np.dtype([("tr", np.float64, 6), ("cov", np.float64, (6, 6
 assert WINDOW_RECORD_DTYPE.itemsize == 584
 
 
-def declare_window(lib):
-    """Prototypes of the opt-in window refinement (include/viso_hip.h; libviso_hip.so only)."""
-    vp = C.c_void_p
-    lib.viso_batch_set_window_refine.argtypes = [vp, C.c_int, C.c_int, C.c_double]
-    lib.viso_batch_get_window_refine.argtypes = [vp, C.c_int, vp]
-    lib.viso_batch_get_window_refines.argtypes = [vp, vp]
-    lib.viso_window_refine.argtypes = [C.c_int, intp, f64p, f64p, i32p, f64p, i32p, intp, C.POINTER(Param), C.c_int, C.c_double, vp]
+class PlainTimes(C.Structure):
+    """struct viso_plain_times (include/viso_hip.h, "plain (host) family"): viso_plain_profile_get."""
+    _fields_ = [("calls", C.c_int64), ("host_us", C.c_double), ("h2d_us", C.c_double), ("kernel_us", C.c_double),
+                ("d2h_us", C.c_double), ("wait_us", C.c_double)]
+
+
+# ------------------------------------------------------------ prototypes
+# Every function include/viso_hip.h declares, name without the viso_ prefix -> (restype, [argtypes]), in the header's order and
+# under its section names.  Handles (viso_ctx*, viso_batch*, viso_map*, viso_tsdf*) and pointers to the records that are numpy
+# dtypes here are vp; a pointer to a struct with a ctypes class is P(that class).  tests/test_cabi_cpu.py parses the header
+# and holds every entry to it.
+P = C.POINTER
+i, i64, u32, u64, sz, dbl, vp = C.c_int, C.c_int64, C.c_uint32, C.c_uint64, C.c_size_t, C.c_double, C.c_void_p
+i16p, u32p, szp, vpp = P(C.c_int16), P(C.c_uint32), P(C.c_size_t), P(C.c_void_p)
+MP, PP = P(MatchParams), P(Param)
+
+PROTOTYPES = {
+    # parameter constructors (ahead of the first section)
+    "match_params_stereo": (None, [MP, f64p]),
+    "match_params_temporal": (None, [MP]),
+    "param_default": (None, [PP]),
+    # context
+    "ctx_create": (vp, [i, vp]),
+    "ctx_destroy": (i, [vp]),
+    "ctx_stream": (vp, [vp]),
+    "ctx_synchronize": (i, [vp]),
+    "ctx_set_matcher": (i, [vp, i]),
+    "matcher_variants": (i, [intp, i]),
+    "matcher_default": (i, []),
+    "ctx_set_gn_split": (i, [vp, i]),
+    "ctx_set_row8_shift": (i, [vp, i]),
+    "ctx_matcher_kernel_name": (C.c_char_p, [vp]),
+    "last_error": (C.c_char_p, []),
+    "version": (C.c_char_p, []),
+    # plain (host) family
+    "match_desc": (i, [f32p, i, f32p, i, f32p, f32p, i, MP, i32p, intp]),
+    "match_circle": (i, [i32p, i, i32p, i, i32p, i, i32p, i, i32p, i32p, i, intp]),
+    "collect_matches": (i, [f32p, i, f32p, i, i32p, i, f64p]),
+    "triangulate_rectified": (i, [f64p, i, PP, f64p]),
+    "minimize_reproj": (i, [f64p, f64p, i, f64p, PP, i32p, i]),
+    "get_inliers": (i, [f64p, f64p, i, f64p, PP, i32p, intp, f64p]),
+    "ransac_minimize_reproj": (i, [f64p, f64p, i, f64p, i32p, intp, PP, i32p, u64, u64]),
+    "support_sizes": (i, [f64p, f64p, i, f64p, i, PP, i32p]),
+    "ransac_samples": (None, [u64, u64, i, i, i32p]),
+    "tr2mat": (None, [f64p, f64p]),
+    "pose_update": (None, [f64p, f64p, f64p]),
+    "F_from_P": (None, [f64p, f64p, f64p]),
+    "extract_descriptors": (i, [u8p, i, i, f32p, i, i, f32p]),
+    "harris_response": (i, [u8p, i, i, dbl, f32p]),
+    "detect_harris_binned": (i, [u8p, i, i, i, i, i, dbl, f32p, f32p, intp]),
+    "plain_cache": (i, [i]),
+    "plain_cache_stats": (i, [i64p, i64p]),
+    "plain_general_reruns": (i64, []),
+    "plain_speculate": (i, [i]),
+    "plain_speculate_stats": (i, [i64p]),
+    "plain_trace_dump": (None, []),
+    "plain_profile": (i, [i]),
+    "plain_profile_get": (i, [i, P(PlainTimes)]),
+    "plain_profile_name": (C.c_char_p, [i]),
+    # batched, device-resident family
+    "batch_create": (vp, [vp, i, i, i]),
+    "batch_destroy": (i, [vp]),
+    "batch_upload": (i, [vp, i, i, f32p, f32p, i32p]),
+    "batch_upload_async": (i, [vp, i, i, f32p, f32p, i32p]),
+    "batch_upload_i16": (i, [vp, i, i, f32p, i16p, i32p]),
+    "batch_upload_i16_async": (i, [vp, i, i, f32p, i16p, i32p]),
+    "host_alloc": (vp, [sz]),
+    "host_free": (i, [vp]),
+    "batch_device_ptrs": (i, [vp, vpp, vpp, vpp]),
+    "batch_set_params": (i, [vp, MP, MP, PP, u64, u64]),
+    "batch_run_matcher": (i, [vp]),
+    "batch_run": (i, [vp]),
+    "batch_upload_images": (i, [vp, i, i, u8p, i, i, f32p, i32p]),
+    "batch_run_images": (i, [vp, i]),
+    "batch_upload_images_async": (i, [vp, i, i, u8p, i, i, f32p, i32p]),
+    "batch_detect": (i, [vp, i, i, i, dbl]),
+    "batch_get_keypoints": (i, [vp, i, i, f32p, intp]),
+    "batch_get_matches": (i, [vp, i, i, i32p, intp]),
+    "batch_get_circle": (i, [vp, i, i32p, i32p, intp]),
+    "batch_get_pose": (i, [vp, i, f64p, intp, i32p, intp]),
+    "batch_get_poses": (i, [vp, f64p, i32p, i32p]),
+    "batch_get_hypotheses": (i, [vp, f64p, i32p, i32p, i32p]),
+    "batch_get_hypotheses2": (i, [vp, i, f64p, i32p, i32p, i32p]),
+    "batch_get_counters": (i, [vp, i64p, i64p]),
+    "batch_get_general_path_flags": (i, [vp, i32p]),
+    "batch_get_overflow_count": (i, [vp, i32p]),
+    "batch_get_row8_shift": (i, [vp, intp]),
+    "batch_kernel_timing": (i, [vp, i]),
+    "batch_kernel_ms": (i, [vp, f64p, intp]),
+    "batch_stamp": (i, [vp, i]),
+    "batch_stamp_ms": (i, [vp, f64p]),
+    # sub-pixel stereo refinement
+    "batch_set_subpixel": (i, [vp, i]),
+    "batch_get_subpixel": (i, [vp, i, f32p, intp]),
+    "refine_stereo_subpixel": (i, [u8p, u8p, i, i, f32p, i, f32p, i, i32p, i, i, f32p]),
+    # rectification of raw camera images
+    "rectify_map": (i, [f64p, f64p, f64p, f64p, i, i, f32p, f32p]),
+    "batch_set_rectify": (i, [vp, i, i, i, i, f32p, f32p, f32p, f32p, i]),
+    "batch_get_image": (i, [vp, i, i, u8p]),
+    "batch_get_image_geometry": (i, [vp, intp, intp]),
+    "rectify_images": (i, [u8p, i, i, i, f32p, f32p, i, i, i, u8p]),
+    # motion covariance
+    "batch_set_covariance": (i, [vp, i, dbl]),
+    "batch_get_covariance": (i, [vp, i, vp]),
+    "batch_get_covariances": (i, [vp, vp]),
+    "batch_get_points": (i, [vp, i, f64p, f64p, intp]),
+    "pose_covariance": (i, [f64p, f64p, i, f64p, i32p, i, PP, i, dbl, vp]),
+    "chain_covariances": (i, [f64p, i32p, vp, i, f64p, i32p, intp]),
+    # motion refinement
+    "batch_set_refine": (i, [vp, i, dbl]),
+    "batch_get_refine": (i, [vp, i, vp]),
+    "batch_get_refines": (i, [vp, vp]),
+    "batch_get_refined_points": (i, [vp, i, i32p, f64p, intp]),
+    "pose_refine": (i, [f64p, f64p, i, f64p, i32p, i, PP, i, dbl, vp, f64p]),
+    # window refinement
+    "batch_set_window_refine": (i, [vp, i, i, dbl]),
+    "batch_get_window_refine": (i, [vp, i, vp]),
+    "batch_get_window_refines": (i, [vp, vp]),
+    "window_refine": (i, [i, intp, f64p, f64p, i32p, f64p, i32p, intp, PP, i, dbl, vp]),
+    # dense stereo disparity
+    "disparity_params_default": (None, [P(DisparityParams)]),
+    "stereo_disparity": (i, [u8p, u8p, i, i, P(DisparityParams), i16p]),
+    "batch_set_disparity": (i, [vp, P(DisparityParams)]),
+    "batch_run_disparity": (i, [vp]),
+    "batch_get_disparity": (i, [vp, i, i16p]),
+    "batch_get_disparities": (i, [vp, i16p]),
+    # semi-global matching
+    "sgm_params_default": (None, [P(SgmParams)]),
+    "stereo_sgm": (i, [u8p, u8p, i, i, P(SgmParams), i16p]),
+    "batch_set_sgm": (i, [vp, P(SgmParams)]),
+    "sgm_set_workspace_cap": (None, [sz]),
+    # speckle filter and 3-D reprojection of the maps
+    "speckle_params_default": (None, [P(SpeckleParams)]),
+    "filter_speckles": (i, [i16p, i, i, P(SpeckleParams)]),
+    "batch_set_speckle": (i, [vp, P(SpeckleParams)]),
+    "speckle_set_workspace_cap": (None, [sz]),
+    "disparity_to_points": (i, [i16p, i, i, PP, f64p, i, f32p]),
+    "batch_get_disparity_points": (i, [vp, i, f64p, i, f32p]),
+    # voxel map
+    "map_params_default": (None, [P(MapParams)]),
+    "map_create": (i, [vp, P(MapParams), vpp]),
+    "map_destroy": (i, [vp]),
+    "map_clear": (i, [vp]),
+    "map_fuse": (i, [vp, i16p, i, i, PP, f64p]),
+    "batch_fuse_disparities": (i, [vp, vp, i, i, f64p]),
+    "map_add_entries": (i, [vp, vp, sz]),
+    "map_count": (i, [vp, u32, szp]),
+    "map_get": (i, [vp, u32, vp, sz, szp]),
+    "map_stats": (i, [vp, P(MapCounters)]),
+    "map_entry_centroid": (i, [vp, dbl, f32p]),
+    # TSDF map
+    "tsdf_params_default": (None, [P(TsdfParams)]),
+    "tsdf_create": (i, [vp, P(TsdfParams), vpp]),
+    "tsdf_destroy": (i, [vp]),
+    "tsdf_clear": (i, [vp]),
+    "tsdf_fuse": (i, [vp, i16p, i, i, PP, f64p]),
+    "batch_fuse_tsdf": (i, [vp, vp, i, i, f64p]),
+    "tsdf_add_entries": (i, [vp, vp, sz]),
+    "tsdf_count": (i, [vp, u32, szp]),
+    "tsdf_get": (i, [vp, u32, vp, sz, szp]),
+    "tsdf_surface_count": (i, [vp, u32, szp]),
+    "tsdf_surface": (i, [vp, u32, vp, sz, szp]),
+    "tsdf_stats": (i, [vp, P(TsdfCounters)]),
+    "tsdf_crossing_point": (i, [vp, dbl, f32p]),
+    # TSDF mesh
+    "tsdf_mesh_count": (i, [vp, u32, szp, szp]),
+    "tsdf_mesh": (i, [vp, u32, vp, sz, vp, sz, szp, szp]),
+    # TSDF render
+    "tsdf_render": (i, [vp, u32, PP, i, i, dbl, f64p, i, i16p, u32p]),
+    # TSDF intensity
+    "tsdf_create_gray": (i, [vp, P(TsdfParams), vpp]),
+    "tsdf_is_gray": (i, [vp, intp]),
+    "tsdf_fuse_gray": (i, [vp, i16p, u8p, i, i, PP, f64p]),
+    "tsdf_get_gray": (i, [vp, u32, vp, sz, szp]),
+    "tsdf_add_gray_entries": (i, [vp, vp, sz]),
+    "tsdf_vertex_gray": (i, [vp, vp, sz, u8p, szp]),
+    "tsdf_render_gray": (i, [vp, u32, PP, i, i, dbl, f64p, i, i16p, u32p, u8p]),
+    # TSDF align
+    "tsdf_align_params_default": (None, [P(TsdfAlignParams)]),
+    "tsdf_linearize": (i, [vp, P(TsdfAlignParams), i16p, i, i, PP, f64p, vp]),
+    "tsdf_align": (i, [vp, P(TsdfAlignParams), i16p, i, i, PP, f64p, vp, vp, i]),
+    "batch_align_tsdf": (i, [vp, vp, i, i, f64p, P(TsdfAlignParams), vp]),
+    # TSDF photometric align
+    "tsdf_align_gray_params_default": (None, [P(TsdfAlignGrayParams)]),
+    "tsdf_linearize_gray": (i, [vp, P(TsdfAlignGrayParams), i16p, u8p, i, i, PP, f64p, vp]),
+    "tsdf_align_gray": (i, [vp, P(TsdfAlignGrayParams), i16p, u8p, i, i, PP, f64p, vp, vp, i]),
+    "batch_align_tsdf_gray": (i, [vp, vp, i, i, f64p, P(TsdfAlignGrayParams), vp]),
+    # Map eviction
+    "voxel_box_around": (i, [f64p, dbl, dbl, P(VoxelBox)]),
+    "map_evict_count": (i, [vp, P(VoxelBox), szp]),
+    "map_evict": (i, [vp, P(VoxelBox), vp, sz, szp]),
+    "tsdf_evict_count": (i, [vp, P(VoxelBox), szp]),
+    "tsdf_evict": (i, [vp, P(VoxelBox), vp, sz, szp]),
+    "tsdf_evict_gray": (i, [vp, P(VoxelBox), vp, sz, szp]),
+}
+
+# what the oracle library exports under its own prefix with the same signatures (declare_common, oracle/pyoracle.py)
+COMMON = ("match_circle", "collect_matches", "triangulate_rectified", "get_inliers", "ransac_minimize_reproj", "ransac_samples",
+          "tr2mat", "pose_update", "F_from_P", "extract_descriptors")
+
+
+def declare(lib, prefix="viso_", names=None):
+    """Give the functions of PROTOTYPES (all, or `names`) their restype and argtypes on `lib`.  A function the library lacks is
+    skipped: an older build of it (VISO_HIP_SO, A/B runs) has fewer, and tests/test_cabi_cpu.py holds the current build to the
+    header's list."""
+    for name in PROTOTYPES if names is None else names:
+        fn = getattr(lib, prefix + name, None)
+        if fn is not None:
+            fn.restype, fn.argtypes = PROTOTYPES[name]
+
+
+def declare_common(lib, prefix):
+    """The COMMON subset of the table under `prefix`, and the two struct pointer types its callers declare their own
+    functions with: what oracle/pyoracle.py asks for its library (prefix 'oracle_')."""
+    declare(lib, prefix, COMMON)
+    return MP, PP

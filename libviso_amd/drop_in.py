@@ -9,16 +9,11 @@ import ctypes as C
 
 import numpy as np
 
-from . import load
-from .abi import Param, f32p, f64p, i32p, ptr
+from . import _call, load
+from .abi import Param, PlainTimes, f32p, f64p, i32p, ptr
 from .kitti_shard import load_host
 
 PLAIN_N = 7
-
-
-class PlainTimes(C.Structure):
-    _fields_ = [("calls", C.c_int64), ("host_us", C.c_double), ("h2d_us", C.c_double), ("kernel_us", C.c_double),
-                ("d2h_us", C.c_double), ("wait_us", C.c_double)]
 
 
 def _host():
@@ -31,17 +26,12 @@ def _host():
 
 def plain_profile(enable):
     """viso_plain_profile: bracket every plain-family call's phases with hipEvents (zeroes the sums when switched on)."""
-    L = load()
-    L.viso_plain_profile.argtypes = [C.c_int]
-    L.viso_plain_profile(1 if enable else 0)
+    load().viso_plain_profile(1 if enable else 0)
 
 
 def plain_profile_rows():
     """{function name: {calls, host_us, h2d_us, kernel_us, d2h_us, wait_us}} - sums since profiling was switched on."""
     L = load()
-    L.viso_plain_profile_get.argtypes = [C.c_int, C.POINTER(PlainTimes)]
-    L.viso_plain_profile_name.restype = C.c_char_p
-    L.viso_plain_profile_name.argtypes = [C.c_int]
     out = {}
     for fn in range(PLAIN_N):
         t = PlainTimes()
@@ -57,8 +47,6 @@ def run(kp, desc, n, F, param, seed=0, first_frame=0, want_matches=False):
     [, matches [3][nf] lists of (i1, i2, dist) arrays])."""
     H = _host()
     L = load()
-    L.viso_plain_profile_name.restype = C.c_char_p
-    L.viso_plain_profile_name.argtypes = [C.c_int]
     kp = np.ascontiguousarray(kp, np.float32)
     desc = np.ascontiguousarray(desc, np.float32)
     n = np.ascontiguousarray(n, np.int32)
@@ -86,23 +74,17 @@ def run(kp, desc, n, F, param, seed=0, first_frame=0, want_matches=False):
 
 def plain_cache(enable):
     """viso_plain_cache: the plain family's image cache on / off (off: every image uploaded, sorted and packed again)."""
-    r = load().viso_plain_cache(1 if enable else 0)
-    if r != 1:
-        raise RuntimeError(f"viso_plain_cache failed with {r}")
+    _call(load().viso_plain_cache, 1 if enable else 0)
 
 
 def plain_speculate(enable):
     """viso_plain_speculate: a frame's stereo call also runs what the loop asks for next (on), or every call direct (off)."""
-    r = load().viso_plain_speculate(1 if enable else 0)
-    if r != 1:
-        raise RuntimeError(f"viso_plain_speculate failed with {r}")
+    _call(load().viso_plain_speculate, 1 if enable else 0)
 
 
 def plain_stats():
     """dict(hits, misses, served [4], wasted [4], general_reruns) of the plain family's cache / frames."""
     L = load()
-    L.viso_plain_cache_stats.argtypes = [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-    L.viso_plain_general_reruns.restype = C.c_int64
     h, m = C.c_int64(0), C.c_int64(0)
     L.viso_plain_cache_stats(C.byref(h), C.byref(m))
     st = (C.c_int64 * 8)()

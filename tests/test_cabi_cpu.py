@@ -3,17 +3,24 @@ symbol include/viso_hip.h declares, host-only entry points compute the
 reference's values, and device entry points fail loudly (never fall back to
 CPU) when no HIP device is present."""
 import ctypes as C
+import inspect
+import json
 import os
 import re
+import shutil
+import subprocess
+import types
 
 import numpy as np
 import pytest
 
 import libviso_amd
-from libviso_amd import synth
+from libviso_amd import abi, synth
 from libviso_amd.abi import MatchParams, Param
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, "include", "viso_hip.h")
+SURFACE = os.path.join(ROOT, "tests", "golden", "python_surface.json")
 
 
 @pytest.fixture(scope="module")
@@ -46,6 +53,151 @@ def test_struct_layout_matches_header(L):
     p = Param()
     L.viso_param_default(C.byref(p))
     assert bytes(p) == bytes(Param.default())
+
+
+def _header_text():
+    hdr = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    return re.sub(r"//[^\n]*", "", hdr)
+
+
+# How a C type of include/viso_hip.h may be restated in abi.PROTOTYPES.  Scalars map one to one by width and signedness; a
+# pointer to (or array parameter of) a scalar is the typed pointer; a pointer to a struct with a ctypes class is POINTER(that
+# class) or c_void_p; handles and pointers to records (the structs that are numpy dtypes in abi.py, or a row of an array) are
+# c_void_p; a pointer to a pointer is POINTER(c_void_p).
+C_SCALARS = {"int": C.c_int, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t, "uint8_t": C.c_uint8, "int16_t": C.c_int16,
+             "int32_t": C.c_int32, "uint32_t": C.c_uint32, "int64_t": C.c_int64, "uint64_t": C.c_uint64}
+C_HANDLES = ("viso_ctx", "viso_batch", "viso_map", "viso_tsdf")
+# every struct the header defines and its twin(s) in abi.py: ctypes classes and numpy dtypes (None: no twin, a row of a uint32 [n][3] array)
+C_STRUCTS = {
+    "viso_match_params": [abi.MatchParams], "viso_param": [abi.Param], "viso_plain_times": [abi.PlainTimes],
+    "viso_motion_cov": [abi.MotionCov, abi.MOTION_COV_DTYPE], "viso_motion_refine": [abi.MOTION_REFINE_DTYPE],
+    "viso_window_record": [abi.WINDOW_RECORD_DTYPE], "viso_disparity_params": [abi.DisparityParams], "viso_sgm_params": [abi.SgmParams],
+    "viso_speckle_params": [abi.SpeckleParams], "viso_map_params": [abi.MapParams], "viso_map_entry": [abi.MAP_ENTRY_DTYPE],
+    "viso_map_counters": [abi.MapCounters], "viso_tsdf_params": [abi.TsdfParams], "viso_tsdf_entry": [abi.TSDF_ENTRY_DTYPE],
+    "viso_tsdf_crossing": [abi.TSDF_CROSSING_DTYPE], "viso_tsdf_counters": [abi.TsdfCounters],
+    "viso_tsdf_mesh_vertex": [abi.TSDF_MESH_VERTEX_DTYPE], "viso_tsdf_triangle": None, "viso_tsdf_gray_entry": [abi.TSDF_GRAY_ENTRY_DTYPE],
+    "viso_tsdf_align_params": [abi.TsdfAlignParams], "viso_tsdf_normal": [abi.TSDF_NORMAL_DTYPE],
+    "viso_tsdf_alignment": [abi.TSDF_ALIGNMENT_DTYPE], "viso_tsdf_align_step": [abi.TSDF_ALIGN_STEP_DTYPE],
+    "viso_tsdf_align_gray_params": [abi.TsdfAlignGrayParams], "viso_tsdf_normal_gray": [abi.TSDF_NORMAL_GRAY_DTYPE],
+    "viso_tsdf_alignment_gray": [abi.TSDF_ALIGNMENT_GRAY_DTYPE], "viso_tsdf_align_gray_step": [abi.TSDF_ALIGN_GRAY_STEP_DTYPE],
+    "viso_voxel_box": [abi.VoxelBox],
+}
+
+
+def _allowed(ctype, returned=False):
+    """The ctypes restatements of one C parameter declaration (or, returned=True, of a return type) that the mapping above allows."""
+    m = re.fullmatch(r"(?:const )?(\w+) ?(\*{0,2}) ?(\w*) ?(\[\d+\])?", " ".join(ctype.split()))
+    assert m, ctype
+    base, stars, _, array = m.groups()
+    depth = len(stars) + (1 if array else 0)
+    if depth == 0:
+        return [None] if base == "void" else [C_SCALARS[base]]
+    if depth == 2:
+        assert base == "void" or base in C_HANDLES, ctype
+        return [C.POINTER(C.c_void_p)]
+    if base == "char":
+        assert returned, ctype
+        return [C.c_char_p]
+    if base in C_SCALARS:
+        return [C.POINTER(C_SCALARS[base])]
+    if base == "void" or base in C_HANDLES:
+        return [C.c_void_p]
+    twins = [t for t in C_STRUCTS[base] or [] if isinstance(t, type)]
+    return [C.POINTER(t) for t in twins] + [C.c_void_p]
+
+
+def _prototype_mismatches(table):
+    """Every disagreement between include/viso_hip.h and a prototype table, one line each, the function's name first."""
+    hdr = _header_text()
+    protos = {name: (ret, [] if args.strip() == "void" else args.split(","))
+              for ret, name, args in re.findall(r"([A-Za-z_][\w \*]*?)\bviso_(\w+)\s*\(([^;{}()]*)\)\s*;", hdr)}
+    assert set(protos) == {n[5:] for n in re.findall(r"\b(viso_\w+)\s*\(", hdr)}   # no declaration escaped the parse
+    bad = [f"viso_{n}: in the header, not in the table" for n in sorted(set(protos) - set(table))]
+    bad += [f"viso_{n}: in the table, not in the header" for n in sorted(set(table) - set(protos))]
+    for name in sorted(set(protos) & set(table)):
+        (ret, args), (restype, argtypes) = protos[name], table[name]
+        if restype not in _allowed(ret, returned=True):
+            bad.append(f"viso_{name}: returns `{ret.strip()}`, the table says {restype}")
+        if len(args) != len(argtypes):
+            bad.append(f"viso_{name}: {len(args)} parameters, the table has {len(argtypes)}")
+            continue
+        bad += [f"viso_{name}: parameter {k} is `{' '.join(a.split())}`, the table says {t}"
+                for k, (a, t) in enumerate(zip(args, argtypes)) if t not in _allowed(a)]
+    return len(protos), bad
+
+
+def test_prototype_table_matches_header():
+    """abi.PROTOTYPES against every prototype of include/viso_hip.h: the same names, the same number of parameters, and every
+    parameter and return type as the mapping of _allowed permits.  Needs no built library."""
+    n, bad = _prototype_mismatches(abi.PROTOTYPES)
+    assert n >= 150
+    assert not bad, "\n".join(bad)
+    assert set(abi.COMMON) <= set(abi.PROTOTYPES)
+
+
+def test_struct_sizes_match_the_compiler(tmp_path):
+    """sizeof of every struct of include/viso_hip.h, as the host C compiler sees it, against its ctypes class / numpy dtype in abi.py."""
+    cc = shutil.which("cc") or shutil.which("gcc")
+    if cc is None:
+        pytest.skip("no C compiler")
+    defined = set(re.findall(r"\}\s*(viso_\w+)\s*;", _header_text()))
+    assert defined == set(C_STRUCTS), defined ^ set(C_STRUCTS)      # a new struct needs a line in C_STRUCTS
+    names = sorted(n for n, twins in C_STRUCTS.items() if twins)
+    src = tmp_path / "sizes.c"
+    src.write_text('#include <stdio.h>\n#include "viso_hip.h"\nint main(void) {\n'
+                   + "".join(f'    printf("{n} %zu\\n", sizeof({n}));\n' for n in names) + "    return 0;\n}\n")
+    exe = str(tmp_path / "sizes")
+    r = subprocess.run([cc, "-I", os.path.dirname(HEADER), str(src), "-o", exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    sizes = dict(line.split() for line in subprocess.run([exe], capture_output=True, text=True, timeout=60).stdout.splitlines())
+    assert sorted(sizes) == names
+    for n in names:
+        for twin in C_STRUCTS[n]:
+            have = C.sizeof(twin) if isinstance(twin, type) else twin.itemsize
+            assert have == int(sizes[n]), (n, twin, have, sizes[n])
+
+
+def _signatures(cls):
+    out = {}
+    for name, m in inspect.getmembers(cls, callable):
+        if name.startswith("_") and name != "__init__":
+            continue
+        try:
+            out[name] = str(inspect.signature(m))
+        except (TypeError, ValueError):
+            pass
+    return out
+
+
+def _surface(mod):
+    """The public names of a module (and _box_arg, which tests/test_evict_cpu.py uses): their kind, and the signature of every
+    function and of every public method of every class.  Imported modules and the declare_* functions of before the prototype
+    table are left out.  json.dump(_surface(libviso_amd), open(SURFACE, "w"), indent=1, sort_keys=True) records it."""
+    out = {}
+    for name in dir(mod):
+        v = getattr(mod, name)
+        if (name.startswith("_") and name != "_box_arg") or name.startswith("declare_") or isinstance(v, types.ModuleType):
+            continue
+        if inspect.isclass(v):
+            out[name] = {"kind": "class", "methods": _signatures(v)}
+        elif inspect.isfunction(v):
+            out[name] = {"kind": "function", "signature": str(inspect.signature(v))}
+        else:
+            out[name] = {"kind": "dtype" if isinstance(v, np.dtype) else type(v).__name__}
+    return out
+
+
+def test_python_surface_is_the_recorded_one():
+    """Every name `import libviso_amd` offered before the package was split by family is still there, of the same kind and with the
+    same signature (tests/golden/python_surface.json, recorded from the one-file package).  Needs no library."""
+    want, have = json.load(open(SURFACE)), _surface(libviso_amd)
+    assert len(want) >= 100
+    missing = sorted(set(want) - set(have))
+    assert not missing, missing
+    for name, rec in want.items():
+        assert have[name] == rec, (name, have[name], rec)
+        if rec["kind"] in ("class", "function"):
+            assert callable(getattr(libviso_amd, name))
 
 
 def test_host_entry_points_match_oracle(L, oracle):
