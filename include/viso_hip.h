@@ -970,8 +970,8 @@ int viso_map_entry_centroid(const viso_map_entry* entry, double voxel, float out
  * VISO_ERR_NOMEM and marks the map overflowed, and every getter, viso_tsdf_add_entries and every fuse call then refuse with
  * VISO_ERR_NOMEM until viso_tsdf_clear.  Every probe loop, the read-only lookups of the extraction included, visits each slot at
  * most once and advances strictly.
- * Out of scope: RGB (one 8-bit intensity: "TSDF intensity" below), carving free space beyond the truncation band, weights that fall with depth, fusing inside the
- * KITTI runners, the sort on the device.
+ * Out of scope: RGB (one 8-bit intensity: "TSDF intensity" below), fusing inside the KITTI runners, the sort on the device.  (Carving
+ * free space beyond the truncation band and weights that fall with depth: "TSDF fuse options" below.)
  * HIP kernels (tsdf.hip): tsdf_fuse_kernel (one thread per pixel of a group of frames; the loop over j is uniform across the wave,
  * and per j the lanes that continue the voxel of the lane to their left form a run whose head lane alone probes the table and
  * issues the two integer atomic adds), tsdf_crossings_kernel; adding entries, listing and clearing are the kernels every table of
@@ -1034,6 +1034,53 @@ int viso_tsdf_stats(viso_tsdf* t, viso_tsdf_counters* out);
 /* Step 10.  Host only; VISO_ERR_ARG for a null pointer, an axis outside 0..2, a weight of 0, sums of the same sign, a voxel that
  * is not finite and > 0. */
 int viso_tsdf_crossing_point(const viso_tsdf_crossing* crossing, double voxel, float out[3]);
+
+/* ------------------------------------------------ TSDF fuse options: free-space carving and disparity-based weights (opt-in; NOT in
+ * the reference)
+ *
+ * A TSDF map, plain or gray, carries fuse options that every way of fusing into it obeys (viso_tsdf_fuse, viso_tsdf_fuse_gray,
+ * viso_batch_fuse_tsdf).  At their defaults every rule and every output above is unchanged, bit for bit, and the same kernels are
+ * launched.  With them a frame also lowers the model where it looks through it, and a near measurement counts for more than a far
+ * one.  Sums stay integers, so the map still depends on neither the order of the frames nor on scheduling, maps fused with the
+ * same options are additive, and the device output is bit-identical to tests/carve_ref.py.
+ * Options (four scalars of viso_tsdf_set_fuse_options; the header defines no struct for them): carve_voxels C in 0..1024, weight_shift
+ * in -1..30, weight_max in 1..255 (read only when weight_shift >= 0), carve_near finite and >= 0 (metres).  Any other value gives VISO_ERR_ARG with the map's options unchanged, before a device is
+ * touched.  The changes to the rules of "TSDF map"; nothing else changes:
+ *   3. j runs over -(2T + 2C) .. +2T, ascending.  A sample with j < -2T is a free-space sample.  A free-space sample with
+ *      zj < carve_near is not inserted and resets the duplicate rule of step 5, like one with !(zj > 0).  Steps 4, 5 and 6 apply to
+ *      free-space samples unchanged: their q comes out clamped to T 1024 wherever the voxel's centre is more than the truncation in
+ *      front of the point, by step 6 alone.
+ *   7. The pixel's weight: w = 1 when weight_shift < 0, otherwise w = min(max((uint32)(disp16 disp16) >> weight_shift, 1), weight_max)
+ *      with the pixel's own disp16: integer, and proportional to 1 / Z^2 between the clamps (stereo depth error grows with Z^2).
+ *      Per voxel: weight += w, sum += w q; on a gray map gray += w I.  All of a pixel's samples carry its w, free-space ones
+ *      included.
+ * Counters: n_updates and n_dropped count updates, not weights.  |sum| <= T 1024 weight and gray <= 255 weight hold as before, so
+ * viso_tsdf_add_entries and viso_tsdf_add_gray_entries take such a map's entries.
+ * min_weight: with weights on, the thresholds of viso_tsdf_get, viso_tsdf_count, viso_tsdf_surface, viso_tsdf_mesh, viso_tsdf_render
+ * and the align calls compare sums of w, no longer numbers of observations.
+ * The 32-bit weight: one frame cannot wrap it (rows cols 255 < 2^32 for every accepted shape).  Many frames can, with carving, in the
+ * voxels close to a camera that stands still, because every ray passes through them; carve_near is there to leave those out.  A
+ * voxel that takes a free-space update holds a sample at depth >= carve_near, so every sample inside it lies at depth
+ * >= z0 = carve_near - sqrt(3) voxel; for z0 > 0 the pixels that update it span at most f sqrt(3) voxel (1 + t) / z0 + 1 columns and
+ * as many rows, t the largest |x - cu| / f, |y - cv| / f of the image, and a pixel updates a voxel once.  So one frame adds to such
+ * a voxel at most  weight_max (f sqrt(3) voxel (1 + t) / (carve_near - sqrt(3) voxel) + 1)^2  (weight_max = 1 without weights), and
+ * never more than rows cols weight_max.  The library does not detect a wrapped weight; tests/carve_ref.py asserts that none occurs.
+ * Out of scope: carving only voxels that exist already (cheaper, but dependent on the frames' order), a lower weight for free-space
+ * samples, eviction by weight, detecting a wrapped weight on the device.
+ * HIP kernels (tsdf.hip): tsdf_carve_fuse_kernel and tsdf_gray_carve_fuse_kernel, the fuse kernels' body with the pixel's weight
+ * carried: the loop over j stays uniform across the wave and starts at the smallest j at which a lane of the wave has a sample to
+ * insert; a run's sums of w, w q and w I come from wave scans, and only its head lane probes the table. */
+/* Sets the four options of a plain or gray map for every later fuse; they persist across viso_tsdf_clear.  A new map has
+ * carve_voxels 0, weight_shift -1, weight_max 255, carve_near 0: the map of "TSDF map".  The values are checked first, then the
+ * handle.  Changing them on a map that is not empty mixes frames fused by different rules: the map stays valid, but is no longer
+ * the restatement of one option set.
+ *   carve_voxels   C: 0 (off) .. 1024: voxels in front of the band that a pixel's ray also updates
+ *   weight_shift   -1 (off): every update weighs 1; 0 .. 30
+ *   weight_max     1 .. 255; read (and checked) only when weight_shift >= 0
+ *   carve_near     metres, finite, >= 0: free-space samples nearer than this are not inserted */
+int viso_tsdf_set_fuse_options(viso_tsdf* t, int32_t carve_voxels, int32_t weight_shift, uint32_t weight_max, double carve_near);
+/* The map's options as they were set; all four outputs non-null. */
+int viso_tsdf_get_fuse_options(viso_tsdf* t, int32_t* carve_voxels, int32_t* weight_shift, uint32_t* weight_max, double* carve_near);
 
 /* ------------------------------------------------ TSDF mesh: triangles by marching tetrahedra (opt-in; NOT in the reference)
  *

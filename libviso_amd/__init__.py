@@ -23,8 +23,8 @@ from . import abi
 # (the whole list is re-exported: what `from libviso_amd import ...` has always offered)
 from .abi import (DESC_LEN, MAP_DEFAULTS, MAP_ENTRY_DTYPE, MOTION_COV_DTYPE, MOTION_REFINE_DTYPE, SGM_DEFAULTS, SPECKLE_DEFAULTS,  # noqa: F401
                   TSDF_ALIGN_DEFAULTS, TSDF_ALIGN_GRAY_DEFAULTS, TSDF_ALIGN_GRAY_STEP_DTYPE, TSDF_ALIGN_STEP_DTYPE, TSDF_ALIGNMENT_DTYPE,
-                  TSDF_ALIGNMENT_GRAY_DTYPE, TSDF_CROSSING_DTYPE, TSDF_DEFAULTS, TSDF_ENTRY_DTYPE, TSDF_GRAY_ENTRY_DTYPE,
-                  TSDF_MESH_VERTEX_DTYPE, TSDF_NORMAL_COUNTERS, TSDF_NORMAL_DTYPE, TSDF_NORMAL_GRAY_COUNTERS, TSDF_NORMAL_GRAY_DTYPE,
+                  TSDF_ALIGNMENT_GRAY_DTYPE, TSDF_CROSSING_DTYPE, TSDF_DEFAULTS, TSDF_ENTRY_DTYPE, TSDF_FUSE_DEFAULTS,
+                  TSDF_GRAY_ENTRY_DTYPE, TSDF_MESH_VERTEX_DTYPE, TSDF_NORMAL_COUNTERS, TSDF_NORMAL_DTYPE, TSDF_NORMAL_GRAY_COUNTERS, TSDF_NORMAL_GRAY_DTYPE,
                   WINDOW_RECORD_DTYPE, DisparityParams, MapCounters, MapParams, MatchParams, Param, SgmParams, SpeckleParams,
                   TsdfAlignGrayParams, TsdfAlignParams, TsdfCounters, TsdfParams, VoxelBox, f32p, f64p, i32p, i64p, intp, ptr)
 
@@ -238,7 +238,8 @@ from .dense import (DISP_INVALID, disparity_params, disparity_to_float, disparit
                     speckle_set_workspace_cap, stereo_disparity, stereo_sgm)
 from .maps import (TsdfMap, VoxelMap, _box_arg, map_entry_centroids, map_params, map_ply_bytes, merge_entries,  # noqa: E402,F401
                    mesh_ply_bytes, surface_ply_bytes, tsdf_align_gray_params, tsdf_align_params, tsdf_crossing_points,
-                   tsdf_normal_gray_matrix, tsdf_normal_matrix, tsdf_params, voxel_box, write_map_ply, write_mesh_ply, write_surface_ply)
+                   tsdf_fuse_options, tsdf_normal_gray_matrix, tsdf_normal_matrix, tsdf_params, voxel_box, write_map_ply, write_mesh_ply,
+                   write_surface_ply)
 from .estimators import (chain_covariances, pose_covariance, pose_refine, refines_as_covariances, window_refine,  # noqa: E402,F401
                          window_refines_as_covariances)
 from .batch import Batch, Context, PinnedArray  # noqa: E402,F401

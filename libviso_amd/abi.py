@@ -184,6 +184,10 @@ class TsdfCounters(C.Structure):
     _fields_ = [(name, C.c_uint64) for name in ("n_points", "n_updates", "n_out_of_range", "n_dropped", "n_occupied")]
 
 
+# the options of a new map, in the order of viso_tsdf_set_fuse_options' parameters (include/viso_hip.h, "TSDF fuse options")
+TSDF_FUSE_DEFAULTS = dict(carve_voxels=0, weight_shift=-1, weight_max=255, carve_near=0.0)
+
+
 class TsdfAlignParams(C.Structure):
     """struct viso_tsdf_align_params (include/viso_hip.h, "TSDF align")."""
     _fields_ = [("min_weight", C.c_uint32), ("gate_voxels", C.c_double), ("max_iters", C.c_int32), ("eps_rot", C.c_double),
@@ -423,6 +427,9 @@ PROTOTYPES = {
     "tsdf_surface": (i, [vp, u32, vp, sz, szp]),
     "tsdf_stats": (i, [vp, P(TsdfCounters)]),
     "tsdf_crossing_point": (i, [vp, dbl, f32p]),
+    # TSDF fuse options
+    "tsdf_set_fuse_options": (i, [vp, C.c_int32, C.c_int32, u32, dbl]),
+    "tsdf_get_fuse_options": (i, [vp, i32p, i32p, u32p, f64p]),
     # TSDF mesh
     "tsdf_mesh_count": (i, [vp, u32, szp, szp]),
     "tsdf_mesh": (i, [vp, u32, vp, sz, vp, sz, szp, szp]),

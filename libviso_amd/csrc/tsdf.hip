@@ -33,6 +33,12 @@
 //                                 interpolated with the mesh's t; the vertices without a value counted with one atomic per wave.
 //   tsdf_gray_render_kernel       the render march; a run's head lane also loads gray and hands it to its run (two more
 //                                 ds_bpermute for the 64-bit value).
+// A map's fuse options (include/viso_hip.h, "TSDF fuse options") add two instances of the fuse body (template
+// <bool GRAY, bool EXT>; without EXT none of the options is read and the two kernels above are what they were):
+//   tsdf_carve_fuse_kernel        the fuse kernel's march from 2 C samples earlier, started per wave at the first j at which one of
+//   tsdf_gray_carve_fuse_kernel   its lanes has a sample to insert (one wave minimum, wave.h), with the pixel's weight w carried: the
+//                                 run's sums of w, w (q + T 1024) and w I from one wave scan each, the run's length only for the
+//                                 dropped counter.  Launched only for a map whose options are not the defaults.
 // The frame-to-model alignment that reads this table is in tsdf_align.hip (the table's layout: tsdf_table.h).
 // What every table of voxels shares is not here (voxelmap.hip says what): the device side is voxel_hash.h, the host side
 // voxel_host.h.  The kernels that list, clear, add entries to and evict slots are voxel_hash.h's templates, instantiated here over
@@ -53,16 +59,17 @@ struct TsdfGrayTable {
     unsigned long long* gray;                    // [slots]
 };
 
-// weight updates with the sum of q `sum` into the voxel `key`; gray_at set (a gray map): and their sum of intensities `gray`
-__device__ __forceinline__ void tsdf_insert(const TsdfTable& t, unsigned long long key, uint32_t weight, long long sum, bool* claimed,
-                                            unsigned long long* gray_at = nullptr, unsigned long long gray = 0) {
+// `updates` updates of the weights' sum `weight` and the sum of w q `sum` into the voxel `key`; gray_at set (a gray map): and
+// their sum of w I `gray`.  The dropped counter counts updates, not weights.
+__device__ __forceinline__ void tsdf_insert(const TsdfTable& t, unsigned long long key, uint32_t updates, uint32_t weight, long long sum,
+                                            bool* claimed, unsigned long long* gray_at = nullptr, unsigned long long gray = 0) {
     uint32_t slot;
     if (voxel_probe(t.head.keys, t.head.mask, key, &slot, claimed)) {
         atomicAdd(t.weight + slot, weight);
         atomicAdd(t.sum + slot, (unsigned long long)sum);
         if (gray_at) atomicAdd(gray_at + slot, gray);
     } else {
-        atomicAdd(t.head.words + VOXEL_W_DROPPED, (unsigned long long)weight);
+        atomicAdd(t.head.words + VOXEL_W_DROPPED, (unsigned long long)updates);
     }
 }
 
@@ -79,10 +86,26 @@ struct TsdfGrayFuseArgs {
     unsigned long long* gray;
 };
 
-// The body of both fuse kernels.  GRAY: the pixel's intensity (image, ifs) is carried along, and a run's head lane adds the run's
-// sum of intensities to gray[slot] as well; without it, none of the three is read.
-template <bool GRAY>
-__device__ __forceinline__ void tsdf_fuse_body(const TsdfFuseArgs& a, const uint8_t* image, size_t ifs, unsigned long long* gray) {
+// a map's fuse options as the extended kernels take them (include/viso_hip.h, "TSDF fuse options"); checked on the host
+struct TsdfFuseOpts {
+    int carve;                          // C
+    int weight_shift;                   // < 0: every update weighs 1
+    uint32_t weight_max; int _pad;
+    double carve_near;
+};
+
+// the sum of v over this lane's run, in the run's head lane (len: voxel_runs'); every lane of the wave calls
+__device__ __forceinline__ uint32_t tsdf_run_sum(uint32_t v, int lane, uint32_t len) {
+    const uint32_t s = viso_wave_scan(v);                                         // inclusive prefix
+    return (uint32_t)__shfl((int)s, lane + (int)len - 1) - s + v;
+}
+
+// The body of the fuse kernels.  GRAY: the pixel's intensity (image, ifs) is carried along, and a run's head lane adds the run's
+// sum of intensities to gray[slot] as well; without it, none of the three is read.  EXT: the rules of "TSDF fuse options": the
+// loop starts 2 o.carve samples earlier, and a pixel's updates carry its weight w; without it, o is not read.
+template <bool GRAY, bool EXT>
+__device__ __forceinline__ void tsdf_fuse_body(const TsdfFuseArgs& a, const TsdfFuseOpts& o, const uint8_t* image, size_t ifs,
+                                               unsigned long long* gray) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     const int lane = threadIdx.x & 63, fr = blockIdx.y;
     double X = 0.0, Y = 0.0, Z = 1.0;
@@ -91,6 +114,29 @@ __device__ __forceinline__ void tsdf_fuse_body(const TsdfFuseArgs& a, const uint
     if (!pm) return;   // the whole wave
     uint32_t pix = 0;                               // one byte a pixel, the lanes of a wave consecutive bytes of a row
     if (GRAY && point) pix = image[(size_t)fr * ifs + i];
+    uint32_t w = 1;                                 // what each of the pixel's updates weighs
+    int j_first = -2 * a.trunc;
+    if constexpr (EXT) {
+        if (point && o.weight_shift >= 0) {
+            const uint32_t d16 = (uint32_t)a.v.disp[(size_t)fr * a.v.mfs + i];    // 1 .. 32767: its square fits
+            w = min(max((d16 * d16) >> o.weight_shift, 1u), o.weight_max);
+        }
+        // The wave starts at the smallest j at which one of its lanes has a sample to insert (zj > 0 and zj >= carve_near): zj does
+        // not fall as j grows, so a lane's earlier samples insert nothing and only reset a `prev` that is empty already.  The
+        // lane's own first such j: an estimate one sample early from the division, then moved down while the sample before it
+        // still is one, with the very expression of the loop below, so that no rounding of the estimate can skip a sample.
+        const int j0 = -2 * (a.trunc + o.carve);
+        int jl = 2 * a.trunc + 1;
+        if (point) {
+            jl = (int)fmin(fmax(floor((o.carve_near - Z) / a.h) - 1.0, (double)j0), (double)(-2 * a.trunc));
+            while (jl > j0) {
+                const double zb = Z + (double)(jl - 1) * a.h;
+                if (!(zb > 0.0 && zb >= o.carve_near)) break;
+                --jl;
+            }
+        }
+        j_first = j0 + (int)wave_min_u32((uint32_t)(jl - j0));
+    }
     // Without a pose the identity: ((1 a + 0 b) + 0 c) + 0 = a and (0 a + 0 b) + 1 (c - 0) = c for finite a, b, c, up to the sign
     // of a zero, which neither floor(. / s) nor Z - zc keeps.
     double T0 = 1.0, T1 = 0.0, T2 = 0.0, T3 = 0.0, T4 = 0.0, T5 = 1.0, T6 = 0.0, T7 = 0.0, T8 = 0.0, T9 = 0.0, T10 = 1.0, T11 = 0.0;
@@ -102,13 +148,15 @@ __device__ __forceinline__ void tsdf_fuse_body(const TsdfFuseArgs& a, const uint
     const double dlim = (double)lim;
     unsigned long long prev = MAP_EMPTY;            // the voxel of the pixel's previous inserted sample
     unsigned long long n_upd = 0, n_oor = 0, n_occ = 0;
-    for (int j = -2 * a.trunc; j <= 2 * a.trunc; ++j) {   // the same j in every lane
+    for (int j = j_first; j <= 2 * a.trunc; ++j) {   // the same j in every lane
         unsigned long long key = MAP_EMPTY;
         uint32_t qb = 0;                            // q + T 1024
         bool oor = false;
         if (point) {
             const double zj = Z + (double)j * a.h;
-            if (zj > 0.0) {
+            bool on = zj > 0.0;
+            if constexpr (EXT) on = on && !(j < -2 * a.trunc && zj < o.carve_near);   // a free-space sample nearer than carve_near
+            if (on) {
                 const double r = zj / Z;
                 const double c0 = X * r, c1 = Y * r;
                 const double gx = floor((((T0 * c0 + T1 * c1) + T2 * zj) + T3) / a.s);
@@ -143,25 +191,42 @@ __device__ __forceinline__ void tsdf_fuse_body(const TsdfFuseArgs& a, const uint
         bool head;
         uint32_t len;
         voxel_runs(key, lane, &head, &len);
-        const uint32_t sq = viso_wave_scan(qb);                                   // inclusive prefix
-        const uint32_t rq = (uint32_t)__shfl((int)sq, lane + (int)len - 1) - sq + qb;   // the run's sum, in its head lane
         bool claimed = false;
-        if (GRAY) {
-            // the run's sum of intensities by a second scan of the same shape (64 x 255 < 2^14)
-            const uint32_t gb = key != MAP_EMPTY ? pix : 0u;
-            const uint32_t sg = viso_wave_scan(gb);
-            const uint32_t rg = (uint32_t)__shfl((int)sg, lane + (int)len - 1) - sg + gb;
-            if (head && key != MAP_EMPTY) tsdf_insert(a.t, key, len, (long long)rq - (long long)len * lim, &claimed, gray, rg);
+        if constexpr (EXT) {
+            // The run's sums of w, of w (q + T 1024) and, on a gray map, of w I, each by a scan of the plain kernel's shape: at most
+            // 64 x 255 < 2^14, 64 x 255 x 16384 < 2^28 and 64 x 255 x 255 < 2^22, so 32 bits hold them.  The lanes without an update
+            // are runs of the empty key, which insert nothing: what they add to the scans cancels in a run's difference.
+            const uint32_t rw = tsdf_run_sum(w, lane, len);
+            const uint32_t rq = tsdf_run_sum(w * qb, lane, len);
+            const uint32_t rg = GRAY ? tsdf_run_sum(w * pix, lane, len) : 0u;
+            if (head && key != MAP_EMPTY)
+                tsdf_insert(a.t, key, len, rw, (long long)rq - (long long)rw * lim, &claimed, GRAY ? gray : nullptr, rg);
         } else {
-            if (head && key != MAP_EMPTY) tsdf_insert(a.t, key, len, (long long)rq - (long long)len * lim, &claimed);
+            const uint32_t rq = tsdf_run_sum(qb, lane, len);                      // the run's sum, in its head lane
+            if (GRAY) {
+                // the run's sum of intensities by a second scan of the same shape (64 x 255 < 2^14)
+                const uint32_t rg = tsdf_run_sum(key != MAP_EMPTY ? pix : 0u, lane, len);
+                if (head && key != MAP_EMPTY) tsdf_insert(a.t, key, len, len, (long long)rq - (long long)len * lim, &claimed, gray, rg);
+            } else {
+                if (head && key != MAP_EMPTY) tsdf_insert(a.t, key, len, len, (long long)rq - (long long)len * lim, &claimed);
+            }
         }
         n_occ += __popcll(__ballot(claimed));
     }
     voxel_count_wave(a.t.head, blockIdx.x + blockIdx.y, lane, __popcll(pm), n_upd, n_oor, n_occ);
 }
 
-__global__ __launch_bounds__(256) void tsdf_fuse_kernel(TsdfFuseArgs a) { tsdf_fuse_body<false>(a, nullptr, 0, nullptr); }
-__global__ __launch_bounds__(256) void tsdf_gray_fuse_kernel(TsdfGrayFuseArgs g) { tsdf_fuse_body<true>(g.a, g.image, g.ifs, g.gray); }
+__global__ __launch_bounds__(256) void tsdf_fuse_kernel(TsdfFuseArgs a) { tsdf_fuse_body<false, false>(a, TsdfFuseOpts{}, nullptr, 0, nullptr); }
+__global__ __launch_bounds__(256) void tsdf_gray_fuse_kernel(TsdfGrayFuseArgs g) {
+    tsdf_fuse_body<true, false>(g.a, TsdfFuseOpts{}, g.image, g.ifs, g.gray);
+}
+// the same two with a map's fuse options (launched only when one of them is on)
+__global__ __launch_bounds__(256) void tsdf_carve_fuse_kernel(TsdfFuseArgs a, TsdfFuseOpts o) {
+    tsdf_fuse_body<false, true>(a, o, nullptr, 0, nullptr);
+}
+__global__ __launch_bounds__(256) void tsdf_gray_carve_fuse_kernel(TsdfGrayFuseArgs g, TsdfFuseOpts o) {
+    tsdf_fuse_body<true, true>(g.a, o, g.image, g.ifs, g.gray);
+}
 
 // The intensity of the point on the edge between the voxels a and b (include/viso_hip.h, "TSDF intensity"): t is the mesh's and the
 // render's, the means of the intensities are interpolated with it.  wa, wb >= 1 and the sums differ in sign.
@@ -529,6 +594,7 @@ struct viso_tsdf {
     viso_tsdf_params p; double s, hs;        // hs: half a voxel, the step along a ray
     TsdfTable t;                             // the payload in h's block: sum | weight; a gray map's: sum | gray | weight
     unsigned long long* gray;                // null: a plain map
+    TsdfFuseOpts o;                          // the map's fuse options, checked; read and written under h.mu
     TsdfGrayTable g() const { return TsdfGrayTable{t, gray}; }
 };
 
@@ -563,19 +629,56 @@ static VoxelLaunch tsdf_clear_launch(viso_tsdf* t) {
         else voxel_start_clear(tsdf_payload<false>(t), s);
     };
 }
-// ifs: the distance of two frames' images, for a gray map's fuse (whose calls all come with an image); a plain map's fuse ignores it
+// ifs: the distance of two frames' images, for a gray map's fuse (whose calls all come with an image); a plain map's fuse ignores it.
+// The map's fuse options are read when a group is launched, under the map's lock (voxel_fuse holds it): at their defaults the
+// kernels of before the options, otherwise the extended ones.
 static VoxelFuseLaunch tsdf_fuse_launch(viso_tsdf* t, size_t ifs) {
     return [t, ifs](const VoxelFuseArgs& v, const uint8_t* d_image, dim3 grid, hipStream_t s) {
         TsdfFuseArgs a;
         a.v = v; a.trunc = t->p.trunc_voxels; a.s = t->s; a.h = t->hs; a.t = t->t;
+        const TsdfFuseOpts o = t->o;
+        const bool ext = o.carve > 0 || o.weight_shift >= 0;
         if (d_image) {
             TsdfGrayFuseArgs g;
             g.a = a; g.image = d_image; g.ifs = ifs; g.gray = t->gray;
-            hipLaunchKernelGGL(tsdf_gray_fuse_kernel, grid, dim3(256), 0, s, g);
+            if (ext) hipLaunchKernelGGL(tsdf_gray_carve_fuse_kernel, grid, dim3(256), 0, s, g, o);
+            else hipLaunchKernelGGL(tsdf_gray_fuse_kernel, grid, dim3(256), 0, s, g);
         } else {
-            hipLaunchKernelGGL(tsdf_fuse_kernel, grid, dim3(256), 0, s, a);
+            if (ext) hipLaunchKernelGGL(tsdf_carve_fuse_kernel, grid, dim3(256), 0, s, a, o);
+            else hipLaunchKernelGGL(tsdf_fuse_kernel, grid, dim3(256), 0, s, a);
         }
     };
+}
+
+static const TsdfFuseOpts TSDF_FUSE_DEFAULTS = {0, -1, 255u, 0, 0.0};
+
+// The values are checked first, on the host alone; then the handle, under the registry's rules.  Either kind of map.
+extern "C" int viso_tsdf_set_fuse_options(viso_tsdf* t, int32_t carve_voxels, int32_t weight_shift, uint32_t weight_max, double carve_near) {
+    const char* where = "viso_tsdf_set_fuse_options";
+    if (carve_voxels < 0 || carve_voxels > 1024 || weight_shift < -1 || weight_shift > 30 || (weight_shift >= 0 && (weight_max < 1 || weight_max > 255)) ||
+        !std::isfinite(carve_near) || !(carve_near >= 0.0)) {
+        viso_set_error("%s: bad argument (carve_voxels in 0..1024, weight_shift in -1..30, weight_max in 1..255 when weight_shift >= 0, "
+                       "a finite carve_near >= 0)", where);
+        return VISO_ERR_ARG;
+    }
+    int r;
+    VoxelHost* h;
+    if ((r = voxel_enter(where, g_tsdfs, t, &h)) < 0) return r;
+    std::lock_guard<std::mutex> lk(h->mu);
+    t->o = TsdfFuseOpts{carve_voxels, weight_shift, weight_max, 0, carve_near};
+    return VISO_OK;
+}
+
+extern "C" int viso_tsdf_get_fuse_options(viso_tsdf* t, int32_t* carve_voxels, int32_t* weight_shift, uint32_t* weight_max, double* carve_near) {
+    const char* where = "viso_tsdf_get_fuse_options";
+    if (!voxel_known(g_tsdfs, t)) { viso_set_error("%s: not a live TSDF handle", where); return VISO_ERR_ARG; }
+    if (!carve_voxels || !weight_shift || !weight_max || !carve_near) { viso_set_error("%s: bad argument (non-null outputs)", where); return VISO_ERR_ARG; }
+    int r;
+    VoxelHost* h;
+    if ((r = voxel_enter(where, g_tsdfs, t, &h)) < 0) return r;
+    std::lock_guard<std::mutex> lk(h->mu);
+    *carve_voxels = t->o.carve; *weight_shift = t->o.weight_shift; *weight_max = t->o.weight_max; *carve_near = t->o.carve_near;
+    return VISO_OK;
 }
 
 static int tsdf_create(const char* where, bool gray, viso_ctx* ctx_or_null, const viso_tsdf_params* params, viso_tsdf** out) {
@@ -593,6 +696,7 @@ static int tsdf_create(const char* where, bool gray, viso_ctx* ctx_or_null, cons
         t->t.head = t->h.head;
         t->t.sum = reinterpret_cast<unsigned long long*>(payload); payload += 8 * slots;
         t->gray = nullptr;
+        t->o = TSDF_FUSE_DEFAULTS;
         if (gray) { t->gray = reinterpret_cast<unsigned long long*>(payload); payload += 8 * slots; }
         t->t.weight = reinterpret_cast<uint32_t*>(payload);
         r = voxel_open(g_tsdfs, t, &t->h, tsdf_clear_launch(t));

@@ -1,6 +1,7 @@
 """python -m libviso_amd.fuse_map DISPARITY_DIR POSES.txt CALIB.txt OUT.ply [--voxel V --min-count N --min-disp PX --frames B E]
                                  [--surface | --mesh [--trunc T --min-weight N] [--render DIR [--render-depth M]] [--gray IMAGE_DIR]
-                                                     [--align [--aligned-poses FILE --align-voxel-gate G --align-photo WEIGHT]]]
+                                                     [--align [--aligned-poses FILE --align-voxel-gate G --align-photo WEIGHT]]
+                                                     [--carve VOXELS [--carve-near METRES]] [--depth-weights SHIFT[,MAX]]]
                                  [--window METRES [--archive FILE.npy]]
 
 Fuses the maps a KITTI runner wrote with --disparity DIR and the poses of its pose file into one voxel map on the device
@@ -35,6 +36,13 @@ float32 centroid of each voxel, count the number of points fused into it.
   --align-photo WEIGHT  with --align and --gray: every used pixel also pulls the model's intensity to its own (include/viso_hip.h,
                  "TSDF photometric align"), which holds the motions that a flat scene leaves free.  WEIGHT: pixels of disparity per
                  gray level (the library's default is 0.03125).  Without it --align is the alignment on the distance alone.
+  --carve VOXELS  with --surface or --mesh: every pixel's ray also updates the VOXELS voxels in front of its truncation band
+                 (include/viso_hip.h, "TSDF fuse options"), so a surface that later maps look through (a stereo outlier, a car that
+                 has driven away) leaves the model.  --carve-near METRES: free-space samples nearer to the camera than this are left
+                 out (0).  Every carved voxel is at least one more update a pixel.
+  --depth-weights SHIFT[,MAX]  with --surface or --mesh: an update weighs min(max(disp16^2 >> SHIFT, 1), MAX) and not 1 (MAX: 255),
+                 so a near measurement pulls the average harder than a far one; --min-weight and the PLY's weight then are sums of
+                 such weights.  Without --carve and --depth-weights the output is byte for byte what it was.
   --window METRES  keep the map on the device to a cube of this half side around the camera (include/viso_hip.h, "Map eviction"):
                  before map i is fused (and, with --align, aligned), every voxel outside the box of voxels that the cube around the
                  translation of pose i touches leaves the table, on the device, and is appended to an archive on the host.  So a
@@ -245,12 +253,33 @@ def main(argv=None):
     ap.add_argument("--align-voxel-gate", type=float, default=1.0, metavar="G", help="with --align: the gate in voxels (1.0)")
     ap.add_argument("--align-photo", type=float, default=None, metavar="WEIGHT", help="with --align and --gray: add the photometric row, "
                     "at this many pixels of disparity per gray level")
+    ap.add_argument("--carve", type=int, default=None, metavar="VOXELS", help="with --surface or --mesh: also update this many voxels in front "
+                    "of the truncation band of every ray")
+    ap.add_argument("--carve-near", type=float, default=None, metavar="METRES", help="with --carve: leave out free-space samples nearer than this (0)")
+    ap.add_argument("--depth-weights", default=None, metavar="SHIFT[,MAX]", help="with --surface or --mesh: an update weighs "
+                    "min(max(disp16^2 >> SHIFT, 1), MAX), MAX 255")
     ap.add_argument("--window", type=float, default=None, metavar="METRES", help="keep the map to a cube of this half side around the camera; "
                     "what leaves it goes to an archive on the host (OUT.ply: the whole map without --surface or --mesh, else the live window)")
     ap.add_argument("--archive", metavar="FILE.npy", help="with --window: write the merged evicted voxels as a numpy array of entries")
     a = ap.parse_args(argv)
     if a.archive and a.window is None:
         ap.error("--archive needs --window")
+    fuse_options = {}
+    if a.carve is not None or a.depth_weights is not None:
+        if not (a.surface or a.mesh):
+            ap.error("--carve and --depth-weights need --surface or --mesh (they are fuse options of a TSDF map)")
+        if a.carve is not None:
+            fuse_options["carve_voxels"] = a.carve
+        if a.depth_weights is not None:
+            try:
+                shift, _, wmax = a.depth_weights.partition(",")
+                fuse_options.update(weight_shift=int(shift), weight_max=int(wmax) if wmax else 255)
+            except ValueError:
+                ap.error("--depth-weights needs SHIFT or SHIFT,MAX, both integers")
+    if a.carve_near is not None:
+        if a.carve is None:
+            ap.error("--carve-near needs --carve")
+        fuse_options["carve_near"] = a.carve_near
     if a.window is not None and not (np.isfinite(a.window) and a.window >= 0):
         ap.error("--window needs a half side >= 0 in metres")
     if a.align and not (a.surface or a.mesh):
@@ -289,7 +318,7 @@ def main(argv=None):
     if a.surface or a.mesh:
         gray = bool(a.gray)
         tsdf = libviso_amd.TsdfMap(None, gray=gray, voxel=a.voxel, trunc_voxels=a.trunc, min_disp16=max(1, int(round(a.min_disp * 16))),
-                                   capacity_log2=26 if a.capacity_log2 is None else a.capacity_log2)
+                                   capacity_log2=26 if a.capacity_log2 is None else a.capacity_log2, **fuse_options)
         try:
             shape = None
             used, statuses = [], {}   # --align: the poses the maps were fused at, and how the alignments ended

@@ -7,7 +7,7 @@ import numpy as np
 from . import _call, _Handle, _map16, _params, _pose_arg, _struct_arg, load
 from .abi import (MAP_DEFAULTS, MAP_ENTRY_DTYPE, TSDF_ALIGN_DEFAULTS, TSDF_ALIGN_GRAY_DEFAULTS, TSDF_ALIGN_GRAY_STEP_DTYPE,
                   TSDF_ALIGN_STEP_DTYPE, TSDF_ALIGNMENT_DTYPE, TSDF_ALIGNMENT_GRAY_DTYPE, TSDF_CROSSING_DTYPE, TSDF_DEFAULTS,
-                  TSDF_ENTRY_DTYPE, TSDF_GRAY_ENTRY_DTYPE, TSDF_MESH_VERTEX_DTYPE, TSDF_NORMAL_COUNTERS, TSDF_NORMAL_DTYPE,
+                  TSDF_ENTRY_DTYPE, TSDF_FUSE_DEFAULTS, TSDF_GRAY_ENTRY_DTYPE, TSDF_MESH_VERTEX_DTYPE, TSDF_NORMAL_COUNTERS, TSDF_NORMAL_DTYPE,
                   TSDF_NORMAL_GRAY_COUNTERS, TSDF_NORMAL_GRAY_DTYPE, MapCounters, MapParams, TsdfAlignGrayParams, TsdfAlignParams,
                   TsdfCounters, TsdfParams, VoxelBox, ptr)
 
@@ -100,6 +100,19 @@ def tsdf_params(**params):
     """viso_tsdf_params: viso_tsdf_params_default with the given fields (voxel in metres, trunc_voxels, min_disp16 in 1/16 px,
     capacity_log2) replaced.  Needs no library: the ranges are checked by viso_tsdf_create (TsdfParams.ok restates them)."""
     return _params(TsdfParams, TSDF_DEFAULTS, "tsdf_params", params)
+
+
+def tsdf_fuse_options(**options):
+    """The four fuse options of a TSDF map (include/viso_hip.h, "TSDF fuse options") as a dict in the order of
+    viso_tsdf_set_fuse_options' parameters: a new map's (TSDF_FUSE_DEFAULTS) with the given ones replaced: carve_voxels (0: off),
+    weight_shift (None or -1: every update weighs 1), weight_max, carve_near in metres.  Needs no library: the ranges are checked
+    by viso_tsdf_set_fuse_options."""
+    o = dict(TSDF_FUSE_DEFAULTS)
+    for k, v in options.items():
+        if k not in o:
+            raise TypeError(f"tsdf_fuse_options: unknown option {k!r}")
+        o[k] = float(v) if k == "carve_near" else -1 if v is None and k == "weight_shift" else int(v)
+    return o
 
 
 def tsdf_align_params(**params):
@@ -321,14 +334,42 @@ class TsdfMap(_TableMap):
     gray=True: a gray map (include/viso_hip.h, "TSDF intensity"), which also sums the 8-bit intensity of the left images per voxel:
     fuse then takes the image with the map (Batch.fuse_tsdf reads the resident ones), entries(gray=True), mesh(gray=True) and
     render(gray=True) give the intensity with the geometry, and write_mesh_ply("mesh.ply", *tsdf.mesh(2, gray=True)) writes it.
+
+    carve_voxels=0, weight_shift=None, weight_max=255, carve_near=0.0: the map's fuse options (include/viso_hip.h, "TSDF fuse
+    options"; the property fuse_options), which every way of fusing into it obeys, Batch.fuse_tsdf included.  carve_voxels=C: a pixel's ray
+    also updates the C voxels in front of its band, so surfaces that later frames look through go away; weight_shift=S: an update
+    weighs min(max(disp16^2 >> S, 1), weight_max) and not 1, so min_weight then compares sums of such weights.
     """
     _prefix, _destroy, _Params, _params, _ENTRY_DTYPE, _Counters = ("viso_tsdf_", "viso_tsdf_destroy", TsdfParams, tsdf_params,
                                                                     TSDF_ENTRY_DTYPE, TsdfCounters)
 
     def __init__(self, ctx=None, params=None, gray=False, **kw):
         self.gray = bool(gray)
+        options = {k: kw.pop(k) for k in tuple(kw) if k in TSDF_FUSE_DEFAULTS}
         super().__init__(ctx, params, **kw)
         self.trunc_voxels = int(self._p.trunc_voxels)
+        if options:
+            try:
+                self.fuse_options = options
+            except Exception:
+                self.close()
+                raise
+
+    @property
+    def fuse_options(self):
+        """The map's fuse options as a dict: carve_voxels, weight_shift (None: off), weight_max, carve_near
+        (viso_tsdf_get_fuse_options).  Assigning a dict of some of them (`tsdf.fuse_options = dict(carve_voxels=28)`; the ones not
+        given: a new map's, not the map's current values) sets them for every later fuse into this map
+        (viso_tsdf_set_fuse_options); they persist across clear().  Bad values raise and leave the map's as they were.  A property
+        and its setter, not two methods."""
+        c, s, m, n = C.c_int32(), C.c_int32(), C.c_uint32(), C.c_double()
+        _call(self.L.viso_tsdf_get_fuse_options, self.h, C.byref(c), C.byref(s), C.byref(m), C.byref(n))
+        return dict(carve_voxels=c.value, weight_shift=None if s.value < 0 else s.value, weight_max=m.value, carve_near=n.value)
+
+    @fuse_options.setter
+    def fuse_options(self, options):
+        o = tsdf_fuse_options(**options)
+        _call(self.L.viso_tsdf_set_fuse_options, self.h, o["carve_voxels"], o["weight_shift"], o["weight_max"], o["carve_near"])
 
     def _c(self, name):
         return super()._c("create_gray" if name == "create" and self.gray else name)

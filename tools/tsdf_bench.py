@@ -2,6 +2,7 @@
 (voxel 0.2 m, T = 3, min_disp16 16, 2^26 slots; the next capacity that holds the scene when that one overflows).
 
   python tools/tsdf_bench.py [--frames N] [--reps N] [--capacity-log2 N] [--render-views N] [--kernel-only] [--out FILE]
+                             [--carve C [--carve-near M]] [--depth-weights S] [--options-capacity-log2 N] [--fuse-only]
 
 The pairs and poses are those of tools/map_bench.py: 17 seeded synthetic frames repeated, frame t seen from a camera that has moved
 0.8 t m forward and turned 0.002 t rad.  Legs (host clock around work that ends in a synchronise, medians of alternating
@@ -31,6 +32,11 @@ repetitions):
                gray map, with the resident left images, lambda 1/32: `linearize_gray` (max_iters 1) and `align_gray` (max_iters 10),
                beside `linearize` and `align` in the same process, alternated: 16 more 8-byte loads a run head, one more byte a
                pixel, a second set of 28 products.
+  fuse_options (with --carve C, --carve-near M and / or --depth-weights S; include/viso_hip.h, "TSDF fuse options") Batch.fuse_tsdf of
+               the same maps into a cleared map of its own with those options (weight_max 255): the extended kernel, in the same
+               loop as fuse_tsdf, with its n_updates / n_points and its ratio to fuse_tsdf.  Its table is the first capacity from
+               --options-capacity-log2 (default: fuse_tsdf's) on that holds the carved scene; give one that does, since every
+               update that finds a table full probes all of its slots.  --fuse-only: only clear, fuse_tsdf and fuse_options are run.
 n_updates / n_points from viso_tsdf_stats is the number of voxels a pixel's band touches.  --kernel-only runs clear + fuse_tsdf
 --reps times, the extractions and the render once and the two align calls --reps times: the run to put under `rocprofv3 --kernel-trace --stats` for the kernels' own times.  The
 count the result is held against (not a measurement) is printed with it."""
@@ -65,6 +71,11 @@ def main():
     ap.add_argument("--render-views", type=int, default=16)
     ap.add_argument("--align-frames", type=int, default=16)
     ap.add_argument("--kernel-only", action="store_true")
+    ap.add_argument("--carve", type=int, default=0)
+    ap.add_argument("--carve-near", type=float, default=0.0)
+    ap.add_argument("--depth-weights", type=int, default=None, metavar="S")
+    ap.add_argument("--options-capacity-log2", type=int, default=None)
+    ap.add_argument("--fuse-only", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     nf = a.frames
@@ -98,6 +109,56 @@ def main():
             tsdf.close()
             if "-4" not in str(e) or log2 == 28:
                 raise
+
+    # --carve / --depth-weights: a second map with those fuse options, of the first capacity that holds what it carves
+    options = dict(carve_voxels=a.carve, carve_near=a.carve_near, weight_shift=a.depth_weights)
+    omap, olog2 = None, log2
+    if a.carve or a.depth_weights is not None:
+        for olog2 in range(log2 if a.options_capacity_log2 is None else a.options_capacity_log2, 29):
+            omap = libviso_amd.TsdfMap(ctx, capacity_log2=olog2, **options)
+            try:
+                b.fuse_tsdf(omap, poses)
+                break
+            except libviso_amd.VisoError as e:
+                omap.close()
+                if "-4" not in str(e) or olog2 == 28:
+                    raise
+
+    def fuse_legs(reps):
+        """clear, fuse_tsdf and fuse_options alone, alternated."""
+        legs = {"clear": [], "fuse_tsdf": []}
+        if omap is not None:
+            legs["fuse_options"] = []
+        for _ in range(reps):
+            legs["clear"].append(clock(tsdf.clear))
+            legs["fuse_tsdf"].append(clock(lambda: b.fuse_tsdf(tsdf, poses)))
+            if omap is not None:
+                omap.clear()
+                legs["fuse_options"].append(clock(lambda: b.fuse_tsdf(omap, poses)))
+        return legs
+
+    def options_result(ms_options, ms_plain):
+        so = omap.stats()
+        return {"options": options, "capacity_log2": olog2, "stats": so, "updates_per_point": so["n_updates"] / max(1, so["n_points"]),
+                "ratio_to_plain": ms_options / ms_plain}
+
+    if a.fuse_only:
+        fuse_legs(2)   # warm-up
+        legs = fuse_legs(a.reps)
+        st = tsdf.stats()
+        res = {"frames": nf, "shape": [int(rows), int(cols)], "capacity_log2": log2, "reps": a.reps,
+               "ms_median": {k: float(np.median(v)) for k, v in legs.items()}, "ms_min": {k: float(np.min(v)) for k, v in legs.items()},
+               "ms_max": {k: float(np.max(v)) for k, v in legs.items()}, "stats": st, "updates_per_point": st["n_updates"] / max(1, st["n_points"])}
+        if omap is not None:
+            res["fuse_options"] = options_result(res["ms_median"]["fuse_options"], res["ms_median"]["fuse_tsdf"])
+            omap.close()
+        print(json.dumps(res))
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                json.dump(res, f, indent=1)
+        tsdf.close(); b.close(); ctx.close()
+        return
 
     views = poses[np.linspace(0, nf - 1, max(1, min(a.render_views, nf))).astype(int)]
 
@@ -159,10 +220,14 @@ def main():
         if has_align_gray:
             align_gray(1); align_gray(10)
     legs = {k: [] for k in ("fuse_tsdf", "fuse_map", "entries", "surface", "mesh", "render", "clear") + (("fuse_gray", "vertex_gray", "render_gray") if has_gray else ())
-            + (("linearize", "align", "render_same") if has_align else ()) + (("linearize_gray", "align_gray") if has_align_gray else ())}
+            + (("linearize", "align", "render_same") if has_align else ()) + (("linearize_gray", "align_gray") if has_align_gray else ())
+            + (("fuse_options",) if omap is not None else ())}
     for _ in range(a.reps):   # alternating
         legs["clear"].append(clock(tsdf.clear))
         legs["fuse_tsdf"].append(clock(lambda: b.fuse_tsdf(tsdf, poses)))
+        if omap is not None:
+            omap.clear()
+            legs["fuse_options"].append(clock(lambda: b.fuse_tsdf(omap, poses)))
         vmap.clear()
         legs["fuse_map"].append(clock(lambda: b.fuse_disparities(vmap, poses)))
         legs["entries"].append(clock(tsdf.entries))
@@ -211,6 +276,9 @@ def main():
                              "ms_per_round_max_iters_1": med["linearize_gray"] / rounds1, "ms_per_frame_and_round": med["linearize_gray"] / rounds1 / na,
                              "ms_per_align_call": med["align_gray"], "ms_per_round": med["align_gray"] / rounds10,
                              "ratio_to_plain_per_round": (med["linearize_gray"] / rounds1) / (med["linearize"] / max(1, int(align(1)["iters"].max()) + 1))}
+    if omap is not None:
+        res["fuse_options"] = options_result(res["ms_median"]["fuse_options"], res["ms_median"]["fuse_tsdf"])
+        omap.close()
     if has_gray:
         res["gray"] = {"vertices": int(len(gverts)), "same_geometry": bool(gmap.entries().tobytes() == tsdf.entries().tobytes()),
                        "ratio_to_plain": {g: res["ms_median"][g] / res["ms_median"][p] for g, p in (("fuse_gray", "fuse_tsdf"), ("render_gray", "render"))}}
