@@ -1171,9 +1171,9 @@ int viso_tsdf_mesh(viso_tsdf* t, uint32_t min_weight, viso_tsdf_mesh_vertex* ver
  * voxel's footprint (DESIGN.md 5.17 has the figures).
  * An overflowed map refuses with VISO_ERR_NOMEM, as the getters do; a handle that is not a live TSDF map, or whose context is gone,
  * VISO_ERR_ARG; no device, VISO_ERR_HIP.  The call takes the map's lock, like an extraction.
- * Out of scope: trilinear rendering (the distance is sampled trilinearly by "TSDF align" below), normals and shaded images, an
+ * Out of scope: trilinear rendering (the distance is sampled trilinearly by "TSDF align" below), an
  * empty-space skipping structure (a coarse block table), rendering into a batch's resident maps, RGB (one 8-bit intensity: "TSDF
- * intensity" below).  Frame-to-model alignment: "TSDF align" below.
+ * intensity" below).  Normals of the hits: "TSDF normals" below.  Frame-to-model alignment: "TSDF align" below.
  * HIP kernel (tsdf.hip): tsdf_render_kernel, one thread per pixel of a group of views, the lanes of a wave consecutive pixels of a
  * row.  The loop over i is uniform across the wave; per i the lanes that continue the voxel of the lane to their left form a run,
  * whose head lane alone probes the table and loads weight and sum, and the other lanes take them from it.  Reads only: no atomics,
@@ -1247,6 +1247,55 @@ int viso_tsdf_vertex_gray(viso_tsdf* t, const viso_tsdf_mesh_vertex* vertices, s
 /* gray_out: uint8 [n_views][rows][cols]; it goes through the same device buffer as the other two outputs. */
 int viso_tsdf_render_gray(viso_tsdf* t, uint32_t min_weight, const viso_param* param, int rows, int cols, double max_depth,
                           const double* poses_or_null, int n_views, int16_t* disp_out, uint32_t* weight_out_or_null, uint8_t* gray_out);
+
+/* ------------------------------------------------ TSDF normals: which way the surface faces, at vertices, crossings and rendered
+ * hits (opt-in; NOT in the reference)
+ *
+ * The gradient of the averaged signed distance over a voxel's six neighbours, interpolated along the edge on which the surface
+ * point lies: the gradient of a function is perpendicular to its zero level set, and that holds for the projective distances of
+ * the map too.  The calls read the table only (weight and sum: a plain and a gray map alike); the table, its statistics and the
+ * overflow mark are untouched.  This definition is the contract; the device output is bit-identical to tests/normal_ref.py.
+ * Everything is IEEE double in the operand order written, with no fused multiply-add; the outputs are the doubles cast to float.
+ * Usable voxel: in the table with weight >= min_weight, min_weight >= 1.  For a usable voxel v, d(v) = (double)sum_v /
+ *   (double)weight_v.
+ * Gradient of a usable voxel v: per axis i, p = v + e_i and m = v - e_i; a neighbour whose index would leave the key range on that
+ *   axis (k_i = 2^20 - 1 has no p, k_i = -2^20 no m) is not usable.  Both usable: G_i = (d(p) - d(m)) * 0.5.  Only p:
+ *   G_i = d(p) - d(v).  Only m: G_i = d(v) - d(m).  Neither: v has no gradient.  v has a gradient only when all three axes have one.
+ * Normal of a point on the edge (a, dir), b = a + (dir & 1, dir >> 1 & 1, dir >> 2): a and b usable with sums of different sign,
+ *   (sa < 0) != (sb < 0), otherwise the normal is missing.  da = d(a), db = d(b), t = da / (da - db): exactly the mesh's and the
+ *   render's.  Both ends must have a gradient, otherwise the normal is missing.  g_i = Ga_i + (Gb_i - Ga_i) * t,
+ *   L = sqrt((g0 g0 + g1 g1) + g2 g2); !(L > 0) or L not finite: missing.  Otherwise n_i = g_i / L in double, and the output is
+ *   (float)n_i.  A missing normal is (0, 0, 0).  The normal points to the positive side, towards the cameras that saw the surface:
+ *   the orientation the mesh's triangles have.
+ * Vertices and crossings: viso_tsdf_vertex_normals, for the vertex list of viso_tsdf_mesh or any list of (k, dir) (p and weight are
+ *   not read), in the world frame.  VISO_ERR_ARG before a device is touched, whatever the handle: min_weight == 0, a null list or
+ *   output with n > 0, a dir outside 1..7, a k outside the key range, a k_i = 2^20 - 1 on an axis where dir has its bit set.
+ *   Missing normals are counted in *n_missing, and the call still returns VISO_OK.  Crossings go through the same call with
+ *   dir = 1 << axis.
+ * Render: viso_tsdf_render_normals has the arguments and checks of viso_tsdf_render plus a non-null normals_out, and its disp_out
+ *   and weight_out are bit-identical to it on the same table.  At a valid pixel the normal is that of the hit: a the previous voxel
+ *   of rule 6, b the hit voxel, t rule 7's (the two need not be axis neighbours; the definition does not ask for it).  It is rotated
+ *   into the view's camera frame before the cast: nc_j = (T[0][j] n0 + T[1][j] n1) + T[2][j] n2; no pose: nc = n.  (0, 0, 0)
+ *   wherever the pixel is VISO_DISP_INVALID and where the normal is missing.  normals_out is laid out like the points of
+ *   viso_disparity_to_points of the same map without a pose, so the two pair up pixel for pixel.  Intensity and normals are not
+ *   combined in one call: a gray map's viso_tsdf_render_gray gives the intensity of the same hits.
+ * An overflowed map refuses with VISO_ERR_NOMEM; a handle that is not a live TSDF map, or whose context is gone, VISO_ERR_ARG; no
+ * device, VISO_ERR_HIP.  The calls take the map's lock, like an extraction.
+ * Limits: both ends of the edge need a gradient, so normals are missing along the rim of the data.  The distances are projective
+ * (along the fusing views' axes), so the normal is exact only at the crossing and only up to the grid (DESIGN.md 5.23 has the
+ * angles).  No smoothing is applied.
+ * Out of scope: smoothed or area-weighted normals, trilinear rendering, a shading kernel on the device (shade_normals of the Python
+ * package is numpy), normals in the batch, point-to-plane alignment.
+ * HIP kernels (tsdf.hip): tsdf_normal_sample_kernel (one thread per vertex: two read-only probes for the ends, then at most ten
+ * for the two gradients, n_missing with one ballot and one atomic per wave), tsdf_normal_render_kernel (the render march unchanged;
+ * a lane keeps the two voxels of its hit and the at most twelve probes of the gradients run behind the march, where the wave is
+ * converged).  No LDS, no scratch; every probe loop is bounded by the capacity. */
+/* normals_out: float [n][3]; n_missing_or_null: the number of vertices without a normal. */
+int viso_tsdf_vertex_normals(viso_tsdf* t, uint32_t min_weight, const viso_tsdf_mesh_vertex* vertices, size_t n, float* normals_out,
+                             size_t* n_missing_or_null);
+/* normals_out: float [n_views][rows][cols][3]; it goes through the same device buffer as the other two outputs. */
+int viso_tsdf_render_normals(viso_tsdf* t, uint32_t min_weight, const viso_param* param, int rows, int cols, double max_depth,
+                             const double* poses_or_null, int n_views, int16_t* disp_out, uint32_t* weight_out_or_null, float* normals_out);
 
 /* ------------------------------------------------ TSDF align: the pose at which a measured map lies on the model (opt-in; NOT in
  * the reference)

@@ -443,6 +443,9 @@ PROTOTYPES = {
     "tsdf_add_gray_entries": (i, [vp, vp, sz]),
     "tsdf_vertex_gray": (i, [vp, vp, sz, u8p, szp]),
     "tsdf_render_gray": (i, [vp, u32, PP, i, i, dbl, f64p, i, i16p, u32p, u8p]),
+    # TSDF normals
+    "tsdf_vertex_normals": (i, [vp, u32, vp, sz, f32p, szp]),
+    "tsdf_render_normals": (i, [vp, u32, PP, i, i, dbl, f64p, i, i16p, u32p, f32p]),
     # TSDF align
     "tsdf_align_params_default": (None, [P(TsdfAlignParams)]),
     "tsdf_linearize": (i, [vp, P(TsdfAlignParams), i16p, i, i, PP, f64p, vp]),

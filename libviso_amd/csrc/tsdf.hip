@@ -33,6 +33,12 @@
 //                                 interpolated with the mesh's t; the vertices without a value counted with one atomic per wave.
 //   tsdf_gray_render_kernel       the render march; a run's head lane also loads gray and hands it to its run (two more
 //                                 ds_bpermute for the 64-bit value).
+// The surface normals (include/viso_hip.h, "TSDF normals") read weight and sum only, of a plain or a gray map:
+//   tsdf_normal_sample_kernel     one thread per vertex (k, dir): two read-only probes for the ends of its edge, then the gradients
+//                                 of the two voxels over their six neighbours (ten more probes for an axis edge, twelve otherwise),
+//                                 interpolated with the mesh's t; the vertices without a normal counted with one atomic per wave.
+//   tsdf_normal_render_kernel     the render march unchanged (a third instance of its body); a lane keeps the two voxels of its hit,
+//                                 and the twelve probes of the two gradients run behind the march, where the wave is converged.
 // A map's fuse options (include/viso_hip.h, "TSDF fuse options") add two instances of the fuse body (template
 // <bool GRAY, bool EXT>; without EXT none of the options is read and the two kernels above are what they were):
 //   tsdf_carve_fuse_kernel        the fuse kernel's march from 2 C samples earlier, started per wave at the first j at which one of
@@ -263,6 +269,90 @@ __global__ __launch_bounds__(256) void tsdf_gray_sample_kernel(TsdfGrayTable g, 
     if (m && (threadIdx.x & 63) == 0) atomicAdd(g.t.head.words + VOXEL_W_OUT, (unsigned long long)__popcll(m));
 }
 
+// ---- surface normals (include/viso_hip.h, "TSDF normals") ---------------------------------------------------------
+// d = sum / weight of the voxel `key` where it is usable (in the table with weight >= min_weight >= 1): one read-only probe
+__device__ __forceinline__ bool tsdf_usable(const TsdfTable& t, unsigned long long key, uint32_t min_weight, double* d) {
+    uint32_t slot;
+    if (!voxel_find(t.head.keys, t.head.mask, key, &slot)) return false;
+    const uint32_t w = t.weight[slot];
+    if (w < min_weight) return false;
+    *d = (double)(long long)t.sum[slot] / (double)w;
+    return true;
+}
+
+// G along AX of the usable voxel `key` of distance d: central where both neighbours are usable, one-sided where one is; false:
+// neither is.  known 1 / 2: the caller holds the upper / the lower neighbour, usable, of distance dk, and it is not probed again.
+template <int AX>
+__device__ __forceinline__ bool tsdf_axis_gradient(const TsdfTable& t, unsigned long long key, uint32_t min_weight, double d, int known, double dk,
+                                                   double* g) {
+    unsigned long long kp, km;
+    double dp = dk, dm = dk;
+    const bool up = known == 1 || (voxel_step_up(key, AX, &kp) && tsdf_usable(t, kp, min_weight, &dp));
+    const bool down = known == 2 || (voxel_step_down(key, AX, &km) && tsdf_usable(t, km, min_weight, &dm));
+    if (up && down) *g = (dp - dm) * 0.5;
+    else if (up) *g = dp - d;
+    else if (down) *g = d - dm;
+    else return false;
+    return true;
+}
+
+// The gradient of the usable voxel `key` of distance d over its six neighbours: six read-only probes, the three axes unrolled, G in
+// named scalars.  known_ax in 0..2: one neighbour on that axis is the caller's (known_up: the upper one), of distance dk; -1: none.
+// false: an axis without a usable neighbour, the voxel has no gradient.
+__device__ __forceinline__ bool tsdf_voxel_gradient(const TsdfTable& t, unsigned long long key, uint32_t min_weight, double d, int known_ax,
+                                                    bool known_up, double dk, double* G0, double* G1, double* G2) {
+    const int kn = known_up ? 1 : 2;
+    return tsdf_axis_gradient<0>(t, key, min_weight, d, known_ax == 0 ? kn : 0, dk, G0) &&
+           tsdf_axis_gradient<1>(t, key, min_weight, d, known_ax == 1 ? kn : 0, dk, G1) &&
+           tsdf_axis_gradient<2>(t, key, min_weight, d, known_ax == 2 ? kn : 0, dk, G2);
+}
+
+// The unit normal in the world frame of the point on the edge between the usable voxels a and b, whose sums differ in sign: the two
+// gradients interpolated with the mesh's and the render's t.  axis in 0..2: b is a's upper neighbour on that axis; -1: any two
+// voxels.  false: missing (an end without a gradient, or a length that is not positive and finite).
+__device__ __forceinline__ bool tsdf_edge_normal(const TsdfTable& t, uint32_t min_weight, unsigned long long ka, uint32_t wa, long long sa,
+                                                 unsigned long long kb, uint32_t wb, long long sb, int axis, double* n0, double* n1, double* n2) {
+    const double da = (double)sa / (double)wa, db = (double)sb / (double)wb;
+    const double tt = da / (da - db);
+    double a0, a1, a2, b0, b1, b2;
+    if (!tsdf_voxel_gradient(t, ka, min_weight, da, axis, true, db, &a0, &a1, &a2)) return false;
+    if (!tsdf_voxel_gradient(t, kb, min_weight, db, axis, false, da, &b0, &b1, &b2)) return false;
+    const double g0 = a0 + (b0 - a0) * tt, g1 = a1 + (b1 - a1) * tt, g2 = a2 + (b2 - a2) * tt;
+    const double L = sqrt((g0 * g0 + g1 * g1) + g2 * g2);
+    if (!(L > 0.0) || !isfinite(L)) return false;
+    *n0 = g0 / L; *n1 = g1 / L; *n2 = g2 / L;
+    return true;
+}
+
+// One thread per vertex (k, dir), checked on the host: two read-only probes for the ends of its edge, then the two gradients (an
+// axis edge: each end is the other's neighbour, ten probes; otherwise twelve).  A missing normal: (0, 0, 0), and the vertex counts
+// in VOXEL_W_OUT, one atomic per wave.
+__global__ __launch_bounds__(256) void tsdf_normal_sample_kernel(TsdfTable t, uint32_t min_weight, const viso_tsdf_mesh_vertex* verts,
+                                                                 unsigned long long n, float* out) {
+    const unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+    bool missing = false;
+    if (i < n) {
+        const viso_tsdf_mesh_vertex v = verts[i];
+        const unsigned long long ka = voxel_key(v.k[0], v.k[1], v.k[2]), kb = voxel_neighbour(ka, (uint32_t)v.dir);
+        uint32_t a, b;
+        float o0 = 0.0f, o1 = 0.0f, o2 = 0.0f;
+        missing = true;
+        if (voxel_find(t.head.keys, t.head.mask, ka, &a) && voxel_find(t.head.keys, t.head.mask, kb, &b)) {
+            const uint32_t wa = t.weight[a], wb = t.weight[b];
+            const long long sa = (long long)t.sum[a], sb = (long long)t.sum[b];
+            double n0, n1, n2;
+            if (wa >= min_weight && wb >= min_weight && (sa < 0) != (sb < 0) &&
+                tsdf_edge_normal(t, min_weight, ka, wa, sa, kb, wb, sb, v.dir == 1 ? 0 : v.dir == 2 ? 1 : v.dir == 4 ? 2 : -1, &n0, &n1, &n2)) {
+                o0 = (float)n0; o1 = (float)n1; o2 = (float)n2;
+                missing = false;
+            }
+        }
+        out[i * 3] = o0; out[i * 3 + 1] = o1; out[i * 3 + 2] = o2;
+    }
+    const unsigned long long m = __ballot(missing);
+    if (m && (threadIdx.x & 63) == 0) atomicAdd(t.head.words + VOXEL_W_OUT, (unsigned long long)__popcll(m));
+}
+
 __global__ __launch_bounds__(256) void tsdf_crossings_kernel(TsdfTable t, uint32_t min_weight, viso_tsdf_crossing* out, unsigned long long out_cap) {
     const uint32_t slot = blockIdx.x * 256 + threadIdx.x;   // the grid covers the slots exactly
     const int lane = threadIdx.x & 63;
@@ -451,10 +541,12 @@ struct TsdfRenderArgs {
     double f, cu, cv, base, s, h;
 };
 
-// The body of both render kernels.  GRAY: a run's head lane also loads gray[slot] and hands it to its run, and the hit's intensity
-// goes to gray_out; without it, neither pointer is read.
-template <bool GRAY>
-__device__ __forceinline__ void tsdf_render_body(const TsdfRenderArgs& a, const unsigned long long* gray, uint8_t* gray_out) {
+// The body of the render kernels.  GRAY: a run's head lane also loads gray[slot] and hands it to its run, and the hit's intensity
+// goes to gray_out; without it, neither pointer is read.  NORMALS: a lane keeps the two voxels of its valid hit, and behind the
+// march, where the wave is converged again, the hit's normal in the view's camera frame goes to normals_out [views][px][3]
+// (include/viso_hip.h, "TSDF normals"); without it, nothing is kept and the pointer is not read.
+template <bool GRAY, bool NORMALS>
+__device__ __forceinline__ void tsdf_render_body(const TsdfRenderArgs& a, const unsigned long long* gray, uint8_t* gray_out, float* normals_out) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, px = (size_t)a.rows * a.cols;
     const int lane = threadIdx.x & 63, view = blockIdx.y;
     bool march = i < px;
@@ -476,6 +568,9 @@ __device__ __forceinline__ void tsdf_render_body(const TsdfRenderArgs& a, const 
     int16_t out_d = VISO_DISP_INVALID;
     uint32_t out_w = 0;
     uint8_t out_g = 0;
+    unsigned long long hit_a = MAP_EMPTY, hit_b = MAP_EMPTY;   // NORMALS: the voxels of the valid hit, their weights and sums
+    uint32_t hit_wa = 0, hit_wb = 0;
+    long long hit_sa = 0, hit_sb = 0;
     for (int n = 1; n <= a.n_samples; ++n) {   // the same n in every lane
         if (!__ballot(march)) break;           // the whole wave
         unsigned long long key = MAP_EMPTY;    // the voxel this lane enters with this sample
@@ -531,6 +626,7 @@ __device__ __forceinline__ void tsdf_render_body(const TsdfRenderArgs& a, const 
                 out_d = (int16_t)(int)floor(v);
                 out_w = pw < w ? pw : w;
                 if (GRAY) out_g = tsdf_edge_gray(pw, ps, pg, w, sum, gs);
+                if (NORMALS) { hit_a = prev; hit_b = key; hit_wa = pw; hit_wb = w; hit_sa = ps; hit_sb = sum; }
             }
             march = false;
         } else {
@@ -543,6 +639,23 @@ __device__ __forceinline__ void tsdf_render_body(const TsdfRenderArgs& a, const 
         if (a.weight) a.weight[(size_t)view * px + i] = out_w;
         if (GRAY) gray_out[(size_t)view * px + i] = out_g;
     }
+    if (NORMALS) {
+        float o0 = 0.0f, o1 = 0.0f, o2 = 0.0f;
+        double n0, n1, n2;
+        if (out_d != VISO_DISP_INVALID && tsdf_edge_normal(a.t, a.min_weight, hit_a, hit_wa, hit_sa, hit_b, hit_wb, hit_sb, -1, &n0, &n1, &n2)) {
+            if (a.poses) {   // into the view's camera frame: the rotation's transpose
+                o0 = (float)((T0 * n0 + T4 * n1) + T8 * n2);
+                o1 = (float)((T1 * n0 + T5 * n1) + T9 * n2);
+                o2 = (float)((T2 * n0 + T6 * n1) + T10 * n2);
+            } else {
+                o0 = (float)n0; o1 = (float)n1; o2 = (float)n2;
+            }
+        }
+        if (i < px) {
+            float* o = normals_out + ((size_t)view * px + i) * 3;
+            o[0] = o0; o[1] = o1; o[2] = o2;
+        }
+    }
 }
 
 struct TsdfGrayRenderArgs {
@@ -550,8 +663,14 @@ struct TsdfGrayRenderArgs {
     const unsigned long long* gray; uint8_t* out;   // the table's sums of intensities; [views][rows * cols]
 };
 
-__global__ __launch_bounds__(256) void tsdf_render_kernel(TsdfRenderArgs a) { tsdf_render_body<false>(a, nullptr, nullptr); }
-__global__ __launch_bounds__(256) void tsdf_gray_render_kernel(TsdfGrayRenderArgs g) { tsdf_render_body<true>(g.a, g.gray, g.out); }
+struct TsdfNormalRenderArgs {
+    TsdfRenderArgs a;
+    float* out;                                     // [views][rows * cols][3]
+};
+
+__global__ __launch_bounds__(256) void tsdf_render_kernel(TsdfRenderArgs a) { tsdf_render_body<false, false>(a, nullptr, nullptr, nullptr); }
+__global__ __launch_bounds__(256) void tsdf_gray_render_kernel(TsdfGrayRenderArgs g) { tsdf_render_body<true, false>(g.a, g.gray, g.out, nullptr); }
+__global__ __launch_bounds__(256) void tsdf_normal_render_kernel(TsdfNormalRenderArgs g) { tsdf_render_body<false, true>(g.a, nullptr, nullptr, g.out); }
 
 // what is in a slot, for the shared kernels that list, zero, add to and evict slots (voxel_hash.h, "a kind's payload"): a plain
 // map's, and with GRAY a gray map's, whose table and entries carry the sums of intensities
@@ -985,10 +1104,10 @@ struct TsdfRenderCall {
     VoxelRenderOut out;
 };
 
-// viso_tsdf_render (out.gray null) and viso_tsdf_render_gray
-static int tsdf_render(const char* where, viso_tsdf* t, bool gray, const TsdfRenderCall& c) {
+// viso_tsdf_render (out.gray and out.normals null), viso_tsdf_render_gray and viso_tsdf_render_normals (normals: out.normals set)
+static int tsdf_render(const char* where, viso_tsdf* t, bool gray, bool normals, const TsdfRenderCall& c) {
     // what does not need the map first, so that nothing of a wrong call reaches a handle
-    if (c.min_weight < 1 || (gray && !c.out.gray) || !c.param || !c.out.disp || c.rows < 1 || c.cols < 1 || c.n_views < 1 ||
+    if (c.min_weight < 1 || (gray && !c.out.gray) || (normals && !c.out.normals) || !c.param || !c.out.disp || c.rows < 1 || c.cols < 1 || c.n_views < 1 ||
         (!c.poses_or_null && c.n_views != 1) || !(std::isfinite(c.max_depth) && c.max_depth > 0.0)) {
         viso_set_error("%s: bad argument (min_weight >= 1, non-null calibration and output, sizes >= 1, a finite max_depth > 0, n_views >= 1 "
                        "and 1 without poses)", where);
@@ -1020,10 +1139,15 @@ static int tsdf_render(const char* where, viso_tsdf* t, bool gray, const TsdfRen
     a.f = c.param->f; a.cu = c.param->cu; a.cv = c.param->cv; a.base = c.param->base; a.s = t->s; a.h = t->hs;
     const unsigned long long* table_gray = t->gray;
     return voxel_render(where, g_tsdfs, t, (size_t)c.rows * c.cols, c.poses_or_null, c.n_views, c.out,
-                        [a, table_gray](const double* d_poses, int16_t* d_disp, uint32_t* d_weight, uint8_t* d_gray, dim3 grid, hipStream_t s) {
+                        [a, table_gray](const double* d_poses, int16_t* d_disp, uint32_t* d_weight, uint8_t* d_gray, float* d_normals, dim3 grid,
+                                        hipStream_t s) {
         TsdfRenderArgs g = a;
         g.poses = d_poses; g.disp = d_disp; g.weight = d_weight;
-        if (d_gray) {
+        if (d_normals) {
+            TsdfNormalRenderArgs gn;
+            gn.a = g; gn.out = d_normals;
+            hipLaunchKernelGGL(tsdf_normal_render_kernel, grid, dim3(256), 0, s, gn);
+        } else if (d_gray) {
             TsdfGrayRenderArgs gg;
             gg.a = g; gg.gray = table_gray; gg.out = d_gray;
             hipLaunchKernelGGL(tsdf_gray_render_kernel, grid, dim3(256), 0, s, gg);
@@ -1035,28 +1159,40 @@ static int tsdf_render(const char* where, viso_tsdf* t, bool gray, const TsdfRen
 
 extern "C" int viso_tsdf_render(viso_tsdf* t, uint32_t min_weight, const viso_param* param, int rows, int cols, double max_depth,
                                 const double* poses_or_null, int n_views, int16_t* disp_out, uint32_t* weight_out_or_null) {
-    return tsdf_render("viso_tsdf_render", t, false,
-                       {min_weight, param, rows, cols, max_depth, poses_or_null, n_views, {disp_out, weight_out_or_null, nullptr}});
+    return tsdf_render("viso_tsdf_render", t, false, false,
+                       {min_weight, param, rows, cols, max_depth, poses_or_null, n_views, {disp_out, weight_out_or_null, nullptr, nullptr}});
 }
 extern "C" int viso_tsdf_render_gray(viso_tsdf* t, uint32_t min_weight, const viso_param* param, int rows, int cols, double max_depth,
                                      const double* poses_or_null, int n_views, int16_t* disp_out, uint32_t* weight_out_or_null, uint8_t* gray_out) {
-    return tsdf_render("viso_tsdf_render_gray", t, true,
-                       {min_weight, param, rows, cols, max_depth, poses_or_null, n_views, {disp_out, weight_out_or_null, gray_out}});
+    return tsdf_render("viso_tsdf_render_gray", t, true, false,
+                       {min_weight, param, rows, cols, max_depth, poses_or_null, n_views, {disp_out, weight_out_or_null, gray_out, nullptr}});
+}
+extern "C" int viso_tsdf_render_normals(viso_tsdf* t, uint32_t min_weight, const viso_param* param, int rows, int cols, double max_depth,
+                                        const double* poses_or_null, int n_views, int16_t* disp_out, uint32_t* weight_out_or_null,
+                                        float* normals_out) {
+    return tsdf_render("viso_tsdf_render_normals", t, false, true,
+                       {min_weight, param, rows, cols, max_depth, poses_or_null, n_views, {disp_out, weight_out_or_null, nullptr, normals_out}});
 }
 
-extern "C" int viso_tsdf_vertex_gray(viso_tsdf* t, const viso_tsdf_mesh_vertex* vertices, size_t n, uint8_t* gray_out, size_t* n_missing_or_null) {
-    const char* where = "viso_tsdf_vertex_gray";
-    if (!tsdf_kind_ok(where, t, true)) return VISO_ERR_ARG;
-    if (n && (!vertices || !gray_out)) { viso_set_error("%s: bad argument (non-null vertices and output)", where); return VISO_ERR_ARG; }
+// the (k, dir) of a vertex list, of which nothing else is read: every one an edge of the key range.  Host only.
+static bool tsdf_vertices_ok(const char* where, const viso_tsdf_mesh_vertex* vertices, size_t n) {
     for (size_t i = 0; i < n; ++i) {
         const viso_tsdf_mesh_vertex& v = vertices[i];
         bool ok = v.dir >= 1 && v.dir <= 7;
         for (int k = 0; k < 3 && ok; ++k) ok = v.k[k] >= -MAP_BIAS && v.k[k] < MAP_BIAS - ((v.dir >> k) & 1);
         if (!ok) {
             viso_set_error("%s: vertex %zu is not an edge of this map (dir in 1..7, k in -2^20 .. 2^20 - 1, and below 2^20 - 1 along dir)", where, i);
-            return VISO_ERR_ARG;
+            return false;
         }
     }
+    return true;
+}
+
+extern "C" int viso_tsdf_vertex_gray(viso_tsdf* t, const viso_tsdf_mesh_vertex* vertices, size_t n, uint8_t* gray_out, size_t* n_missing_or_null) {
+    const char* where = "viso_tsdf_vertex_gray";
+    if (!tsdf_kind_ok(where, t, true)) return VISO_ERR_ARG;
+    if (n && (!vertices || !gray_out)) { viso_set_error("%s: bad argument (non-null vertices and output)", where); return VISO_ERR_ARG; }
+    if (!tsdf_vertices_ok(where, vertices, n)) return VISO_ERR_ARG;
     int r;
     VoxelHost* h;
     if ((r = voxel_enter(where, g_tsdfs, t, &h)) < 0) return r;
@@ -1080,6 +1216,53 @@ extern "C" int viso_tsdf_vertex_gray(viso_tsdf* t, const viso_tsdf_mesh_vertex* 
             hipLaunchKernelGGL(tsdf_gray_sample_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, t->g(), d_verts, (unsigned long long)n, d_out);
         }, &missing);
         if (r >= 0) e = hipMemcpy(gray_out, d_out, n, hipMemcpyDeviceToHost);
+    }
+    (void)hipFree(d);   // on every path
+    if (r < 0) return r;
+    HIP_TRY(e);
+    if (n_missing_or_null) *n_missing_or_null = (size_t)missing;
+    return VISO_OK;
+}
+
+extern "C" int viso_tsdf_vertex_normals(viso_tsdf* t, uint32_t min_weight, const viso_tsdf_mesh_vertex* vertices, size_t n, float* normals_out,
+                                        size_t* n_missing_or_null) {
+    const char* where = "viso_tsdf_vertex_normals";
+    // what does not need the map first, so that nothing of a wrong call reaches a handle
+    if (min_weight < 1 || (n && (!vertices || !normals_out))) {
+        viso_set_error("%s: bad argument (min_weight >= 1, non-null vertices and output)", where);
+        return VISO_ERR_ARG;
+    }
+    if (n > (size_t)-1 / (sizeof(viso_tsdf_mesh_vertex) + 3 * sizeof(float))) {
+        viso_set_error("%s: bad argument (%zu vertices are beyond the address space)", where, n);
+        return VISO_ERR_ARG;
+    }
+    if (!tsdf_vertices_ok(where, vertices, n)) return VISO_ERR_ARG;
+    if (!voxel_known(g_tsdfs, t)) { viso_set_error("%s: not a live TSDF handle", where); return VISO_ERR_ARG; }
+    int r;
+    VoxelHost* h;
+    if ((r = voxel_enter(where, g_tsdfs, t, &h)) < 0) return r;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (h->overflowed) return voxel_refuse_overflowed(where, h);
+    if (n_missing_or_null) *n_missing_or_null = 0;
+    if (!n) return VISO_OK;
+    const size_t b_verts = n * sizeof(viso_tsdf_mesh_vertex), b_out = n * 3 * sizeof(float);   // 28 bytes a vertex: the floats stay aligned
+    char* d = nullptr;
+    if (hipMalloc((void**)&d, b_verts + b_out) != hipSuccess) {
+        (void)hipGetLastError();
+        viso_set_error("%s: cannot allocate %zu bytes for the vertices", where, b_verts + b_out);
+        return VISO_ERR_NOMEM;
+    }
+    const viso_tsdf_mesh_vertex* d_verts = reinterpret_cast<const viso_tsdf_mesh_vertex*>(d);
+    float* d_out = reinterpret_cast<float*>(d + b_verts);
+    hipError_t e = hipMemcpy(d, vertices, b_verts, hipMemcpyHostToDevice);
+    unsigned long long missing = 0;
+    if (e == hipSuccess) {
+        const TsdfTable table = t->t;
+        r = voxel_pass(h, [&](hipStream_t s) {
+            hipLaunchKernelGGL(tsdf_normal_sample_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, table, min_weight, d_verts,
+                               (unsigned long long)n, d_out);
+        }, &missing);
+        if (r >= 0) e = hipMemcpy(normals_out, d_out, b_out, hipMemcpyDeviceToHost);
     }
     (void)hipFree(d);   // on every path
     if (r < 0) return r;

@@ -55,6 +55,20 @@ __host__ __device__ __forceinline__ void voxel_unkey(unsigned long long key, int
 __host__ __device__ __forceinline__ unsigned long long voxel_neighbour(unsigned long long key, uint32_t d) {
     return key + voxel_key((int)(d & 1u) - MAP_BIAS, (int)((d >> 1) & 1u) - MAP_BIAS, (int)(d >> 2) - MAP_BIAS);
 }
+// the key one voxel up / down along axis ax (0: x, 1: y, 2: z); false: key is at the last / the first index of that axis, which has
+// no neighbour there (the upper end is the rule of tsdf_crossings_kernel, the lower end its twin)
+__host__ __device__ __forceinline__ bool voxel_step_up(unsigned long long key, int ax, unsigned long long* out) {
+    const int sh = 21 * (2 - ax);
+    if (((key >> sh) & 0x1fffffull) == 0x1fffffull) return false;
+    *out = key + (1ull << sh);
+    return true;
+}
+__host__ __device__ __forceinline__ bool voxel_step_down(unsigned long long key, int ax, unsigned long long* out) {
+    const int sh = 21 * (2 - ax);
+    if (((key >> sh) & 0x1fffffull) == 0ull) return false;
+    *out = key - (1ull << sh);
+    return true;
+}
 
 __device__ __forceinline__ uint32_t map_hash(unsigned long long k) {   // the finaliser of splitmix64
     k ^= k >> 30; k *= 0xbf58476d1ce4e5b9ull;

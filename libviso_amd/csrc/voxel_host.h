@@ -45,14 +45,16 @@ struct VoxelRegistry {
 using VoxelLaunch = std::function<void(hipStream_t)>;                                             // the clear
 // one group of frames; d_image: the group's first image on the device, or null when the call has none
 using VoxelFuseLaunch = std::function<void(const VoxelFuseArgs&, const uint8_t* d_image, dim3 grid, hipStream_t)>;
-// one group of views; d_gray: the group's part of the third output, or null when the call has none
-using VoxelRenderLaunch = std::function<void(const double* d_poses, int16_t* d_disp, uint32_t* d_weight, uint8_t* d_gray, dim3 grid, hipStream_t)>;
+// one group of views; d_gray, d_normals: the group's part of the third output, or null when the call has none of that kind
+using VoxelRenderLaunch = std::function<void(const double* d_poses, int16_t* d_disp, uint32_t* d_weight, uint8_t* d_gray, float* d_normals, dim3 grid,
+                                             hipStream_t)>;
 // one group of `frames` frames of a linearise: the group's poses [.][12], its flags and its part of the sums, the group's first
 // frame; the grid is the caller's, with the group's frames along y
 using VoxelLinearizeLaunch = std::function<void(const double* d_poses, const unsigned long long* d_active, unsigned long long* d_out, int frame0,
                                                 unsigned frames, hipStream_t)>;
-// what a render writes on the host: n_views maps, with `weight` set as many weights, with `gray` set as many intensities
-struct VoxelRenderOut { int16_t* disp; uint32_t* weight; uint8_t* gray; };
+// what a render writes on the host: n_views maps, with `weight` set as many weights, with `gray` set as many intensities, with
+// `normals` set as many times three floats
+struct VoxelRenderOut { int16_t* disp; uint32_t* weight; uint8_t* gray; float* normals; };
 // where a count or a list goes: *n the number of items; count_only: nothing else, otherwise the items to out[0 .. cap)
 template <class Item>
 struct VoxelList { bool count_only; Item* out; size_t cap; size_t* n; };
@@ -119,8 +121,8 @@ int voxel_add_entries(const char* where, VoxelRegistry& reg, const void* handle,
     return r;
 }
 // viso_*_render behind the handle and argument checks: the map entered, locked and not overflowed; the poses [n_views][16] (or
-// null) through d_pose; a device buffer for n_views maps of px int16 and, with out.weight, as many uint32, and, with out.gray, as
-// many uint8, freed on every path; the groups of views, each started by `launch` with its poses ([.][12] or null) and its part of
+// null) through d_pose; a device buffer for n_views maps of px int16 and, with out.weight, as many uint32, with out.gray, as
+// many uint8, and with out.normals, three floats a pixel, freed on every path; the groups of views, each started by `launch` with its poses ([.][12] or null) and its part of
 // the buffer; the copies to the host.
 int voxel_render(const char* where, VoxelRegistry& reg, const void* handle, size_t px, const double* poses, int n_views, const VoxelRenderOut& out,
                  const VoxelRenderLaunch& launch);

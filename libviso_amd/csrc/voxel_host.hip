@@ -273,10 +273,11 @@ int voxel_render(const char* where, VoxelRegistry& reg, const void* handle, size
     std::lock_guard<std::mutex> lk(h->mu);
     if (h->overflowed) return voxel_refuse_overflowed(where, h);
     hipStream_t s = h->ctx->stream;
-    const size_t per = (out.weight ? 6 : 2) + (out.gray ? 1 : 0);   // bytes a pixel: the weights, then the maps, then the intensities
+    // bytes a pixel: the normals, then the weights, then the maps, then the intensities
+    const size_t per = (out.normals ? 12 : 0) + (out.weight ? 6 : 2) + (out.gray ? 1 : 0);
     if (px > (size_t)-1 / per / (size_t)n_views) { viso_set_error("%s: %d views of %zu pixels are beyond the address space", where, n_views, px); return VISO_ERR_NOMEM; }
-    const size_t n = (size_t)n_views * px, b_weight = out.weight ? n * sizeof(uint32_t) : 0, b_disp = n * sizeof(int16_t),
-                 bytes = b_weight + b_disp + (out.gray ? n : 0);
+    const size_t n = (size_t)n_views * px, b_normals = out.normals ? n * 3 * sizeof(float) : 0, b_weight = out.weight ? n * sizeof(uint32_t) : 0,
+                 b_disp = n * sizeof(int16_t), bytes = b_normals + b_weight + b_disp + (out.gray ? n : 0);
     std::vector<double> rows12;   // alive until the stream has been waited for
     if (poses && (r = voxel_stage_poses(where, h, poses, n_views, rows12)) < 0) return r;
     void* d = nullptr;
@@ -286,19 +287,21 @@ int voxel_render(const char* where, VoxelRegistry& reg, const void* handle, size
         viso_set_error("%s: cannot allocate %zu bytes for the views", where, bytes);
         return VISO_ERR_NOMEM;
     }
-    uint32_t* d_weight = out.weight ? static_cast<uint32_t*>(d) : nullptr;
-    int16_t* d_disp = reinterpret_cast<int16_t*>(static_cast<char*>(d) + b_weight);
-    uint8_t* d_gray = out.gray ? static_cast<uint8_t*>(d) + b_weight + b_disp : nullptr;
+    float* d_normals = out.normals ? static_cast<float*>(d) : nullptr;
+    uint32_t* d_weight = out.weight ? reinterpret_cast<uint32_t*>(static_cast<char*>(d) + b_normals) : nullptr;
+    int16_t* d_disp = reinterpret_cast<int16_t*>(static_cast<char*>(d) + b_normals + b_weight);
+    uint8_t* d_gray = out.gray ? static_cast<uint8_t*>(d) + b_normals + b_weight + b_disp : nullptr;
     hipError_t e = hipSuccess;
     for (int v0 = 0; v0 < n_views && e == hipSuccess; v0 += VOXEL_GROUP) {
         const int nv = n_views - v0 < VOXEL_GROUP ? n_views - v0 : VOXEL_GROUP;
         launch(poses ? h->d_pose + (size_t)v0 * 12 : nullptr, d_disp + (size_t)v0 * px, d_weight ? d_weight + (size_t)v0 * px : nullptr,
-               d_gray ? d_gray + (size_t)v0 * px : nullptr, dim3((unsigned)((px + 255) / 256), (unsigned)nv), s);
+               d_gray ? d_gray + (size_t)v0 * px : nullptr, d_normals ? d_normals + (size_t)v0 * px * 3 : nullptr, dim3((unsigned)((px + 255) / 256), (unsigned)nv), s);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(out.disp, d_disp, n * sizeof(int16_t), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess && d_weight) e = hipMemcpyAsync(out.weight, d_weight, b_weight, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess && d_gray) e = hipMemcpyAsync(out.gray, d_gray, n, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && d_normals) e = hipMemcpyAsync(out.normals, d_normals, b_normals, hipMemcpyDeviceToHost, s);
     const hipError_t e_wait = hipStreamSynchronize(s);   // nothing in flight touches the buffer that is freed next
     (void)hipFree(d);   // on every path
     HIP_TRY(e);

@@ -1,5 +1,6 @@
 """python -m libviso_amd.fuse_map DISPARITY_DIR POSES.txt CALIB.txt OUT.ply [--voxel V --min-count N --min-disp PX --frames B E]
                                  [--surface | --mesh [--trunc T --min-weight N] [--render DIR [--render-depth M]] [--gray IMAGE_DIR]
+                                                     [--normals] [--shaded DIR]
                                                      [--align [--aligned-poses FILE --align-voxel-gate G --align-photo WEIGHT]]
                                                      [--carve VOXELS [--carve-near METRES]] [--depth-weights SHIFT[,MAX]]]
                                  [--window METRES [--archive FILE.npy]]
@@ -27,6 +28,11 @@ float32 centroid of each voxel, count the number of points fused into it.
                  intensity").  IMAGE_DIR holds 8-bit grayscale PNGs with the maps' names and sizes (KITTI's image_0).  The PLY's
                  vertices then carry the surface's intensity as red = green = blue after weight, and --render also writes
                  DIR/gray/<name> as 8-bit PNGs, the intensity of every rendered pixel (0 where the map is invalid).
+  --normals      with --surface or --mesh: the PLY's vertices also carry the surface's unit normal, towards the cameras, as float nx,
+                 ny, nz after x, y, z (include/viso_hip.h, "TSDF normals"; --min-weight applies); (0, 0, 0) where there is none, as
+                 along the rim of the data.
+  --shaded DIR   with --render: also write DIR/<name> as 8-bit PNGs, every rendered view shaded by the normals of its pixels under
+                 a light at the camera (libviso_amd.shade_normals; 0 where the map is invalid or the pixel has no normal).
   --align        with --surface or --mesh: track, then fuse (include/viso_hip.h, "TSDF align").  The first map is fused at its pose;
                  every later map i is first aligned against the model fused so far, from the guess aligned(i-1) pose(i-1)^-1 pose(i)
                  (the file's motion applied to the previous map's aligned pose), and fused at the aligned pose when the alignment
@@ -248,6 +254,8 @@ def main(argv=None):
     ap.add_argument("--render", metavar="DIR", help="with --surface or --mesh: also write the model rendered at every fused pose into DIR")
     ap.add_argument("--render-depth", type=float, default=40.0, metavar="M", help="with --render: how far a ray is followed, metres (40)")
     ap.add_argument("--gray", metavar="IMAGE_DIR", help="with --surface or --mesh: fuse the 8-bit left images of the maps' names with them")
+    ap.add_argument("--normals", action="store_true", help="with --surface or --mesh: write the vertices' normals into the PLY")
+    ap.add_argument("--shaded", metavar="DIR", help="with --render: also write every rendered view shaded by its normals into DIR")
     ap.add_argument("--align", action="store_true", help="with --surface or --mesh: align every map against the model before it is fused")
     ap.add_argument("--aligned-poses", metavar="FILE", help="with --align: write the poses the maps were fused at")
     ap.add_argument("--align-voxel-gate", type=float, default=1.0, metavar="G", help="with --align: the gate in voxels (1.0)")
@@ -290,6 +298,10 @@ def main(argv=None):
         ap.error("--align-photo needs --align and --gray (the photometric row reads a gray TSDF map and the maps' images)")
     if a.render and not (a.surface or a.mesh):
         ap.error("--render needs --surface or --mesh (only a TSDF map is rendered)")
+    if a.normals and not (a.surface or a.mesh):
+        ap.error("--normals needs --surface or --mesh (only a TSDF map has normals)")
+    if a.shaded and not a.render:
+        ap.error("--shaded needs --render DIR (the shaded images are of the rendered views)")
     if a.gray and not (a.surface or a.mesh):
         ap.error("--gray needs --surface or --mesh (only a TSDF map carries intensity)")
     import libviso_amd
@@ -355,10 +367,15 @@ def main(argv=None):
                 poses = np.array(list(poses[:b]) + used + list(poses[e:])).reshape(-1, 4, 4)   # --render sees the model from where it was fused
             if a.render and e > b:
                 os.makedirs(os.path.join(a.render, "gray") if gray else a.render, exist_ok=True)
+                if a.shaded:
+                    os.makedirs(a.shaded, exist_ok=True)
                 n_near = 0
                 for i0 in range(b, e, RENDER_VIEWS):   # several views a call
                     i1 = min(e, i0 + RENDER_VIEWS)
-                    views = tsdf.render(prm, shape, poses[i0:i1], max_depth=a.render_depth, min_weight=a.min_weight, gray=gray)
+                    views = (tsdf.normals if a.shaded else tsdf).render(prm, shape, poses[i0:i1], max_depth=a.render_depth,
+                                                                        min_weight=a.min_weight, gray=gray)
+                    if a.shaded:
+                        views, lit = views[:-1] if gray else views[0], libviso_amd.shade_normals(views[-1])
                     views, shades = views if gray else (views, None)
                     near = views > DISP_PNG_MAX   # nearer than the files can say
                     n_near += int(near.sum())
@@ -367,22 +384,32 @@ def main(argv=None):
                         write_disparity_png(os.path.join(a.render, names[i]), views[i - i0])
                         if gray:
                             write_png8(os.path.join(a.render, "gray", names[i]), np.where(near[i - i0], 0, shades[i - i0]).astype(np.uint8))
+                        if a.shaded:
+                            write_png8(os.path.join(a.shaded, names[i]), np.where(near[i - i0], 0, lit[i - i0]).astype(np.uint8))
                 print(f"fuse_map: {e - b} views rendered to {a.render_depth} m ({n_near} pixels beyond 255.9 px left out) -> {a.render}")
             shade = None   # the intensity of the PLY's vertices
             if a.mesh:
                 vertices, triangles = tsdf.mesh(a.min_weight)
                 shade = tsdf.vertex_gray(vertices) if gray else None
+                normals = tsdf.normals.vertices(vertices, a.min_weight) if a.normals else None
             else:
                 crossings = tsdf.surface(a.min_weight)
                 shade = tsdf.vertex_gray(crossings) if gray else None
+                normals = tsdf.normals.vertices(crossings, a.min_weight) if a.normals else None
         finally:
             tsdf.close()
         if a.mesh:
-            libviso_amd.write_mesh_ply(a.out, vertices, triangles, shade)
+            if normals is not None:
+                libviso_amd.write_mesh_normals_ply(a.out, vertices, triangles, normals, shade)
+            else:
+                libviso_amd.write_mesh_ply(a.out, vertices, triangles, shade)
             print(f"fuse_map: {e - b} maps, {st['n_points']} points, {st['n_updates']} updates ({st['n_out_of_range']} samples out of range), "
                   f"{st['n_occupied']} voxels, {len(vertices)} vertices and {len(triangles)} triangles at weight >= {a.min_weight} -> {a.out}{note}")
             return 0
-        libviso_amd.write_surface_ply(a.out, crossings, a.voxel, shade)
+        if normals is not None:
+            libviso_amd.write_surface_normals_ply(a.out, crossings, a.voxel, normals, shade)
+        else:
+            libviso_amd.write_surface_ply(a.out, crossings, a.voxel, shade)
         print(f"fuse_map: {e - b} maps, {st['n_points']} points, {st['n_updates']} updates ({st['n_out_of_range']} samples out of range), "
               f"{st['n_occupied']} voxels, {len(crossings)} crossings at weight >= {a.min_weight} -> {a.out}{note}")
         return 0

@@ -163,31 +163,65 @@ _PLY_XYZW = [("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("weight", "<u4")]
 _PLY_XYZW_HEAD = "property float x\nproperty float y\nproperty float z\nproperty uint weight\n"
 _PLY_RGB = [("red", "u1"), ("green", "u1"), ("blue", "u1")]
 _PLY_RGB_HEAD = "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+_PLY_XYZ, _PLY_W = _PLY_XYZW[:3], _PLY_XYZW[3:]
+_PLY_XYZ_HEAD, _PLY_W_HEAD = "property float x\nproperty float y\nproperty float z\n", "property uint weight\n"
+_PLY_N = [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+_PLY_N_HEAD = "property float nx\nproperty float ny\nproperty float nz\n"
 
 
-def _ply_vertices(where, x, y, z, weight, gray):
-    """(the vertex element's property lines, its records): x, y, z, weight and, with gray (uint8, one a vertex), red = green = blue."""
+def _ply_vertices(where, x, y, z, weight, gray, normals=None):
+    """(the vertex element's property lines, its records): x, y, z, with normals (float32 [n][3]) nx, ny, nz, then weight and, with
+    gray (uint8, one a vertex), red = green = blue."""
     if gray is not None:
         gray = np.asarray(gray)
         if gray.dtype != np.uint8 or gray.shape != (len(x),):
             raise ValueError(f"{where}: gray must be a uint8 array with one value a vertex")
-    v = np.empty(len(x), np.dtype(_PLY_XYZW + (_PLY_RGB if gray is not None else [])))
+    if normals is not None:
+        normals = np.asarray(normals)
+        if normals.dtype != np.float32 or normals.shape != (len(x), 3):
+            raise ValueError(f"{where}: normals must be a float32 array with three values a vertex")
+    v = np.empty(len(x), np.dtype(_PLY_XYZ + (_PLY_N if normals is not None else []) + _PLY_W + (_PLY_RGB if gray is not None else [])))
     v["x"], v["y"], v["z"], v["weight"] = x, y, z, weight
+    if normals is not None:
+        v["nx"], v["ny"], v["nz"] = normals[:, 0], normals[:, 1], normals[:, 2]
     if gray is not None:
         v["red"] = v["green"] = v["blue"] = gray
-    return _PLY_XYZW_HEAD + (_PLY_RGB_HEAD if gray is not None else ""), v
+    return _PLY_XYZ_HEAD + (_PLY_N_HEAD if normals is not None else "") + _PLY_W_HEAD + (_PLY_RGB_HEAD if gray is not None else ""), v
+
+
+def _ply_normals(where, normals):
+    if normals is None:
+        raise ValueError(f"{where}: normals must be a float32 array with three values a vertex")
+    return normals
+
+
+def shade_normals(normals, light=(0.0, 0.0, -1.0)):
+    """uint8 [...]: the Lambert shade floor(255 max(0, n . l) + 0.5) of float [...][3] normals (TsdfMap.normals.render, in
+    the camera frame, where (0, 0, -1) is a light at the camera) under the direction `light`, which is normalised here.  0 where
+    the normal is (0, 0, 0).  Numpy only."""
+    n = np.asarray(normals, np.float64)
+    l = np.asarray(light, np.float64)
+    if n.shape[-1:] != (3,) or l.shape != (3,) or not np.isfinite(l).all() or not l.any():
+        raise ValueError("shade_normals: normals must be [...][3] and light three finite numbers, not all zero")
+    l = l / np.sqrt((l * l).sum())
+    dot = (n[..., 0] * l[0] + n[..., 1] * l[1]) + n[..., 2] * l[2]
+    return np.floor(255.0 * np.maximum(0.0, dot) + 0.5).astype(np.uint8)
+
+
+def _surface_ply(where, crossings, voxel, gray, normals):
+    crossings = np.ascontiguousarray(crossings, dtype=TSDF_CROSSING_DTYPE)
+    c = tsdf_crossing_points(crossings, voxel)
+    props, v = _ply_vertices(where, c[:, 0], c[:, 1], c[:, 2], np.minimum(crossings["wa"], crossings["wb"]), gray, normals)
+    head = ("ply\nformat binary_little_endian 1.0\ncomment libviso_amd TSDF surface, voxel %r m\nelement vertex %d\n"
+            "%send_header\n" % (float(voxel), len(crossings), props))
+    return head.encode("ascii") + v.tobytes()
 
 
 def surface_ply_bytes(crossings, voxel, gray=None):
     """The bytes of write_surface_ply: a binary little-endian PLY with one vertex per crossing, x, y, z the float32 crossing point
     and weight = min(wa, wb) a uint32, in the crossings' order.  gray (uint8 [n], TsdfMap.vertex_gray of the crossings): red, green
     and blue, all equal to it, follow weight."""
-    crossings = np.ascontiguousarray(crossings, dtype=TSDF_CROSSING_DTYPE)
-    c = tsdf_crossing_points(crossings, voxel)
-    props, v = _ply_vertices("surface_ply_bytes", c[:, 0], c[:, 1], c[:, 2], np.minimum(crossings["wa"], crossings["wb"]), gray)
-    head = ("ply\nformat binary_little_endian 1.0\ncomment libviso_amd TSDF surface, voxel %r m\nelement vertex %d\n"
-            "%send_header\n" % (float(voxel), len(crossings), props))
-    return head.encode("ascii") + v.tobytes()
+    return _surface_ply("surface_ply_bytes", crossings, voxel, gray, None)
 
 
 def write_surface_ply(path, crossings, voxel, gray=None):
@@ -195,15 +229,22 @@ def write_surface_ply(path, crossings, voxel, gray=None):
     _write(path, surface_ply_bytes(crossings, voxel, gray))
 
 
-def mesh_ply_bytes(vertices, triangles, gray=None):
-    """The bytes of write_mesh_ply: a binary little-endian PLY; per vertex x, y, z the float32 position and weight a uint32, per
-    face a uchar 3 and three int32 vertex indices, both in the order given.  gray (uint8 [n], the third array of
-    TsdfMap.mesh(gray=True)): red, green and blue, all equal to it, follow weight."""
+def surface_normals_ply_bytes(crossings, voxel, normals, gray=None):
+    """surface_ply_bytes with the crossings' normals (float32 [n][3], TsdfMap.normals.surface): float nx, ny, nz follow x, y, z."""
+    return _surface_ply("surface_normals_ply_bytes", crossings, voxel, gray, _ply_normals("surface_normals_ply_bytes", normals))
+
+
+def write_surface_normals_ply(path, crossings, voxel, normals, gray=None):
+    """The crossings of TsdfMap.surface with their normals as a point cloud file (surface_normals_ply_bytes)."""
+    _write(path, surface_normals_ply_bytes(crossings, voxel, normals, gray))
+
+
+def _mesh_ply(where, vertices, triangles, gray, normals):
     vertices = np.ascontiguousarray(vertices, dtype=TSDF_MESH_VERTEX_DTYPE)
     triangles = np.ascontiguousarray(triangles, dtype=np.uint32).reshape(-1, 3)
     if len(triangles) and (int(triangles.max()) >= len(vertices) or len(vertices) > 2 ** 31):
-        raise ValueError("mesh_ply_bytes: a triangle refers to a vertex that is not in the list (or is beyond int32)")
-    props, v = _ply_vertices("mesh_ply_bytes", vertices["p"][:, 0], vertices["p"][:, 1], vertices["p"][:, 2], vertices["weight"], gray)
+        raise ValueError(f"{where}: a triangle refers to a vertex that is not in the list (or is beyond int32)")
+    props, v = _ply_vertices(where, vertices["p"][:, 0], vertices["p"][:, 1], vertices["p"][:, 2], vertices["weight"], gray, normals)
     f = np.empty(len(triangles), np.dtype([("n", "u1"), ("v", "<i4", (3,))]))
     f["n"], f["v"] = 3, triangles
     head = ("ply\nformat binary_little_endian 1.0\ncomment libviso_amd TSDF mesh\nelement vertex %d\n"
@@ -212,9 +253,36 @@ def mesh_ply_bytes(vertices, triangles, gray=None):
     return head.encode("ascii") + v.tobytes() + f.tobytes()
 
 
+def mesh_ply_bytes(vertices, triangles, gray=None):
+    """The bytes of write_mesh_ply: a binary little-endian PLY; per vertex x, y, z the float32 position and weight a uint32, per
+    face a uchar 3 and three int32 vertex indices, both in the order given.  gray (uint8 [n], the third array of
+    TsdfMap.mesh(gray=True)): red, green and blue, all equal to it, follow weight."""
+    return _mesh_ply("mesh_ply_bytes", vertices, triangles, gray, None)
+
+
 def write_mesh_ply(path, vertices, triangles, gray=None):
     """The mesh of TsdfMap.mesh as a PLY file (mesh_ply_bytes)."""
     _write(path, mesh_ply_bytes(vertices, triangles, gray))
+
+
+def mesh_normals_ply_bytes(vertices, triangles, normals, gray=None):
+    """mesh_ply_bytes with the vertices' normals (float32 [n][3], the last array of TsdfMap.normals.mesh): float nx, ny, nz follow
+    x, y, z, so that a viewer shades the mesh smoothly."""
+    return _mesh_ply("mesh_normals_ply_bytes", vertices, triangles, gray, _ply_normals("mesh_normals_ply_bytes", normals))
+
+
+def write_mesh_normals_ply(path, vertices, triangles, normals, gray=None):
+    """The mesh of TsdfMap.normals.mesh as a PLY file (mesh_normals_ply_bytes)."""
+    _write(path, mesh_normals_ply_bytes(vertices, triangles, normals, gray))
+
+
+def _vertex_list(vertices):
+    """The (k, dir) list of a per-vertex call: mesh vertices as they are, crossings as dir = 1 << axis."""
+    if getattr(vertices, "dtype", None) == TSDF_CROSSING_DTYPE:
+        c = vertices
+        vertices = np.zeros(len(c), TSDF_MESH_VERTEX_DTYPE)
+        vertices["k"], vertices["dir"] = c["k"], np.left_shift(1, c["axis"])
+    return np.ascontiguousarray(vertices, dtype=TSDF_MESH_VERTEX_DTYPE)
 
 
 class _TableMap(_Handle):
@@ -411,14 +479,16 @@ class TsdfMap(_TableMap):
         """viso_tsdf_vertex_gray: uint8 [n], the intensity of every vertex of mesh() (a TSDF_MESH_VERTEX_DTYPE array, of which k and
         dir are read) or of every crossing of surface() (a TSDF_CROSSING_DTYPE array: dir = 1 << axis).  0 where an end of the edge
         is not in the table or the ends do not differ in sign; missing=True: a tuple with their number."""
-        if getattr(vertices, "dtype", None) == TSDF_CROSSING_DTYPE:
-            c = vertices
-            vertices = np.zeros(len(c), TSDF_MESH_VERTEX_DTYPE)
-            vertices["k"], vertices["dir"] = c["k"], np.left_shift(1, c["axis"])
-        vertices = np.ascontiguousarray(vertices, dtype=TSDF_MESH_VERTEX_DTYPE)
+        vertices = _vertex_list(vertices)
         g, n_missing = np.zeros(len(vertices), np.uint8), C.c_size_t()
         _call(self.L.viso_tsdf_vertex_gray, self.h, vertices.ctypes.data, len(vertices), ptr(g, C.c_uint8), C.byref(n_missing))
         return (g, n_missing.value) if missing else g
+
+    @property
+    def normals(self):
+        """The surface normals of this map (include/viso_hip.h, "TSDF normals"): a TsdfNormals, whose vertices, surface, mesh and
+        render give a unit normal for every vertex, crossing and rendered hit.  A plain or a gray map."""
+        return TsdfNormals(self)
 
     def surface(self, min_weight=1):
         """viso_tsdf_surface: the sign changes between neighbouring voxels of at least min_weight updates as a TSDF_CROSSING_DTYPE
@@ -505,6 +575,10 @@ class TsdfMap(_TableMap):
         weights=True: a tuple with the uint32 array of the same shape, the smaller weight of the two voxels of a hit (0: none).
         gray=True (a gray map): viso_tsdf_render_gray, the tuple ends with the uint8 array of the same shape, the intensity of the
         hit (0: none)."""
+        return self._render(param, shape, poses, max_depth, min_weight, weights, gray, False)
+
+    def _render(self, param, shape, poses, max_depth, min_weight, weights, gray, normals):
+        """render, and with normals (TsdfNormals.render) viso_tsdf_render_normals: the tuple ends with float32 [..][rows][cols][3]."""
         rows, cols = (int(v) for v in shape)
         T = None
         if poses is not None:
@@ -519,11 +593,53 @@ class TsdfMap(_TableMap):
         g = np.empty((n, rows, cols), np.uint8) if gray else None
         args = (self.h, int(min_weight), C.byref(param), rows, cols, float(max_depth), ptr(T, C.c_double) if T is not None else None, n,
                 ptr(d, C.c_int16), ptr(w, C.c_uint32) if weights else None)
+        nrm = np.empty((n, rows, cols, 3), np.float32) if normals else None
         if gray:
             _call(self.L.viso_tsdf_render_gray, *args, ptr(g, C.c_uint8))
-        else:
+        if normals:
+            _call(self.L.viso_tsdf_render_normals, *args, ptr(nrm, C.c_float))
+        if not gray and not normals:
             _call(self.L.viso_tsdf_render, *args)
         if T is None or T.ndim == 2:
-            d, w, g = d[0], (w[0] if weights else None), (g[0] if gray else None)
-        out = (d,) + ((w,) if weights else ()) + ((g,) if gray else ())
+            d, w, g, nrm = d[0], (w[0] if weights else None), (g[0] if gray else None), (nrm[0] if normals else None)
+        out = (d,) + ((w,) if weights else ()) + ((g,) if gray else ()) + ((nrm,) if normals else ())
         return out if len(out) > 1 else d
+
+
+class TsdfNormals:
+    """TsdfMap.normals: which way the surface of a TSDF map faces (include/viso_hip.h, "TSDF normals").  A normal is the gradient of
+    the averaged signed distance over a voxel's six neighbours, interpolated between the two voxels of the edge on which the surface
+    point lies: a unit float32 vector towards the cameras that saw the surface, (0, 0, 0) where there is none (an end of the edge
+    that is not usable, ends of one sign, or an end without a neighbour on some axis, as along the rim of the data).  The calls read
+    weight and sum only, of a plain or a gray map, and change nothing in it."""
+
+    def __init__(self, tsdf):
+        self.tsdf = tsdf
+
+    def vertices(self, vertices, min_weight=1, missing=False):
+        """viso_tsdf_vertex_normals: float32 [n][3], the normal in the world frame of every vertex of TsdfMap.mesh (a
+        TSDF_MESH_VERTEX_DTYPE array, of which k and dir are read) or of every crossing of TsdfMap.surface (a TSDF_CROSSING_DTYPE
+        array: dir = 1 << axis), over the voxels of at least min_weight updates.  missing=True: a tuple with the number of
+        vertices without a normal."""
+        t = self.tsdf
+        vertices = _vertex_list(vertices)
+        nrm, n_missing = np.zeros((len(vertices), 3), np.float32), C.c_size_t()
+        _call(t.L.viso_tsdf_vertex_normals, t.h, int(min_weight), vertices.ctypes.data, len(vertices), ptr(nrm, C.c_float), C.byref(n_missing))
+        return (nrm, n_missing.value) if missing else nrm
+
+    def surface(self, min_weight=1):
+        """float32 [n][3]: the normals of the crossings of TsdfMap.surface(min_weight), at the same min_weight, in their order."""
+        return self.vertices(self.tsdf.surface(min_weight), min_weight)
+
+    def mesh(self, min_weight=1, gray=False):
+        """TsdfMap.mesh(min_weight, gray) with the tuple ending in the float32 [n][3] normals of its vertices, at the same
+        min_weight: (vertices, triangles, n), or (vertices, triangles, g, n) of a gray map."""
+        out = self.tsdf.mesh(min_weight, gray)
+        return out + (self.vertices(out[0], min_weight),)
+
+    def render(self, param, shape, poses=None, max_depth=40.0, min_weight=2, weights=False, gray=False):
+        """viso_tsdf_render_normals: TsdfMap.render with the same arguments, its tuple ending in the float32 array of the maps' shape
+        with a last axis of 3: the normal of every hit in the view's camera frame ((0, 0, 0): none), pixel for pixel the points of
+        disparity_to_points of the rendered map.  The map and the weights are TsdfMap.render's, bit for bit.  gray=True (a gray
+        map): the intensity comes from a second call on the same table."""
+        return self.tsdf._render(param, shape, poses, max_depth, min_weight, weights, gray, True)

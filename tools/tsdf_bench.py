@@ -23,6 +23,10 @@ repetitions):
   vertex_gray  TsdfMap.vertex_gray of the gray map's mesh vertices: the copy up, two probes a vertex, the copy back;
   render_gray  TsdfMap.render(gray=True) of the same views over the gray map: beside `render`, one more 8-byte load a probe and one
                more byte a pixel out.
+  render_normals  (include/viso_hip.h, "TSDF normals") TsdfMap.normals.render of the same views over the same map, beside `render`
+               in the same loop: the march unchanged, then at most twelve more probes a hit pixel and twelve more bytes a pixel out;
+  mesh_normals TsdfMap.normals.mesh() beside `mesh`: the extraction, then the vertices up, at most twelve probes a vertex and
+               twelve bytes a vertex back.
   align        (include/viso_hip.h, "TSDF align") Batch.align_tsdf of the first --align-frames (16) resident maps against the table, each
                from its fusing pose moved by 0.2 degrees and 2 cm, min_weight 2, gate 1 voxel: `linearize`, the call with max_iters 1
                (two rounds of one launch each: time per round and per frame and round), and `align`, the call with max_iters 10
@@ -210,8 +214,15 @@ def main():
     def render_gray():
         return gmap.render(seq["param"], (rows, cols), views, max_depth=40.0, min_weight=2, gray=True)
 
+    has_normals = hasattr(libviso_amd.load(), "viso_tsdf_render_normals")   # (likewise)
+
+    def render_normals():
+        return tsdf.normals.render(seq["param"], (rows, cols), views, max_depth=40.0, min_weight=2)
+
     for _ in range(2):   # warm-up
         tsdf.clear(); b.fuse_tsdf(tsdf, poses); tsdf.entries(); tsdf.surface(); tsdf.mesh(); render()
+        if has_normals:
+            render_normals(); tsdf.normals.mesh()
         vmap.clear(); b.fuse_disparities(vmap, poses)
         if has_gray:
             gmap.clear(); b.fuse_tsdf(gmap, poses); gmap.vertex_gray(gverts); render_gray()
@@ -221,7 +232,7 @@ def main():
             align_gray(1); align_gray(10)
     legs = {k: [] for k in ("fuse_tsdf", "fuse_map", "entries", "surface", "mesh", "render", "clear") + (("fuse_gray", "vertex_gray", "render_gray") if has_gray else ())
             + (("linearize", "align", "render_same") if has_align else ()) + (("linearize_gray", "align_gray") if has_align_gray else ())
-            + (("fuse_options",) if omap is not None else ())}
+            + (("fuse_options",) if omap is not None else ()) + (("render_normals", "mesh_normals") if has_normals else ())}
     for _ in range(a.reps):   # alternating
         legs["clear"].append(clock(tsdf.clear))
         legs["fuse_tsdf"].append(clock(lambda: b.fuse_tsdf(tsdf, poses)))
@@ -234,6 +245,9 @@ def main():
         legs["surface"].append(clock(tsdf.surface))
         legs["mesh"].append(clock(tsdf.mesh))
         legs["render"].append(clock(render))
+        if has_normals:
+            legs["mesh_normals"].append(clock(tsdf.normals.mesh))
+            legs["render_normals"].append(clock(render_normals))
         if has_gray:
             gmap.clear()
             legs["fuse_gray"].append(clock(lambda: b.fuse_tsdf(gmap, poses)))
@@ -258,6 +272,14 @@ def main():
     ms = res["ms_median"]["render"]
     res["render"] = {"views": int(len(views)), "max_depth": 40.0, "min_weight": 2, "valid": valid, "ms_per_view": ms / len(views),
                      "samples_marched": n_marched, "samples_per_s": n_marched / (ms * 1e-3)}
+    if has_normals:
+        d16, nrm = render_normals()
+        nv = tsdf.normals.mesh()[2]
+        med = res["ms_median"]
+        res["normals"] = {"ms_per_view": med["render_normals"] / len(views), "render_ratio_to_plain": med["render_normals"] / med["render"],
+                          "pixels_with_normal_of_valid": float(nrm.any(axis=-1).sum() / max(1, int((d16 != -16).sum()))),
+                          "mesh_ratio_to_plain": med["mesh_normals"] / med["mesh"], "vertex_normals_ms": med["mesh_normals"] - med["mesh"],
+                          "vertices_with_normal": float(nv.any(axis=1).mean()) if len(nv) else 0.0}
     if has_align:
         r1, r10, med = align(1), align(10), res["ms_median"]
         rounds1, rounds10 = int(r1["iters"].max()) + 1, int(r10["iters"].max()) + 1
