@@ -1542,6 +1542,50 @@ int viso_tsdf_evict_count(viso_tsdf* t, const viso_voxel_box* keep, size_t* n);
 int viso_tsdf_evict(viso_tsdf* t, const viso_voxel_box* keep, viso_tsdf_entry* evicted_out, size_t n_cap, size_t* n);
 int viso_tsdf_evict_gray(viso_tsdf* t, const viso_voxel_box* keep, viso_tsdf_gray_entry* evicted_out, size_t n_cap, size_t* n);
 
+/* ------------------------------------------------ TSDF distance field: how far every voxel of a box is from the surface, on the
+ * device (opt-in; NOT in the reference)
+ *
+ * For every voxel of an axis-aligned box of voxel indices, the squared distance in voxel units, an exact integer, to the nearest
+ * surface voxel of the box: what a planner, a collision check or a clearance costmap asks of a map, without pulling the surface to
+ * the host.  The call reads the table only (weight and sum: a plain and a gray map alike); the table, its statistics and the
+ * overflow mark are untouched.  This definition is the contract; the device output is bit-identical to tests/field_ref.py.
+ *   1. Box: n_i = hi[i] - lo[i], computed in int64, must be in 1..512 on every axis.  Cell (i0, i1, i2) is the voxel k = lo + i and
+ *      is stored at index (i0 n1 + i1) n2 + i2 of sq_out and state_out.  n_cap counts cells: n_cap < n0 n1 n2 gives VISO_ERR_ARG
+ *      and nothing is written.  The box may lie anywhere in int32.
+ *   2. Usable voxel: every k_i in -2^20 .. 2^20 - 1, the voxel in the table, and its weight >= min_weight (min_weight >= 1, as for
+ *      the getters).
+ *   3. State, the low two bits: 0 unknown (not usable), 1 front (sum >= 0), 2 behind (sum < 0).
+ *   4. Surface voxel: usable and, on some axis, with a usable neighbour k + e or k - e whose (sum < 0) differs: end a or end b of
+ *      a crossing of rule 9 of "TSDF map" at the same min_weight.  The neighbour may lie outside the box.  A voxel at the first or
+ *      the last index of an axis (k_i = -2^20, k_i = 2^20 - 1) has no neighbour on that side; nothing wraps.  A surface voxel's
+ *      state also has VISO_FIELD_STATE_SURFACE set.
+ *   5. Sites: the surface voxels inside the box; with VISO_FIELD_UNKNOWN_IS_SITE the unknown cells of the box too (the
+ *      conservative field for planning: what was never seen counts as an obstacle).  Any other flag bit: VISO_ERR_ARG.  *n_sites
+ *      is their number.
+ *   6. Result: sq[c] = the minimum over the sites s of (c0 - s0)^2 + (c1 - s1)^2 + (c2 - s2)^2, at most 3 * 511^2;
+ *      VISO_FIELD_NONE in every cell when the box holds no site.
+ * Sites outside the box do not exist for the call: a value is exact only up to the cell's distance from the nearest face of the
+ * box, so the caller pads the box by the clearance they care about.
+ * An overflowed map refuses with VISO_ERR_NOMEM; a handle that is not a live TSDF map, or whose context is gone, VISO_ERR_ARG; no
+ * device, VISO_ERR_HIP.  Every argument check (min_weight, box, flags, a null sq_out, n_cap, then the handle) happens before a
+ * device is touched.  The call takes the map's lock, like an extraction.
+ * Device memory of a call: two uint32 and one uint8 a cell (1.2 GB for the largest box); VISO_ERR_NOMEM when it cannot be
+ * allocated.  Every loop on the device is bounded by an axis length (<= 512), by the at most 256 rounds of cells a block of the
+ * first kernel takes, or is the probe's one round of the slots.
+ * Out of scope: sites beyond the box and boxes longer than 512 voxels, sub-voxel distances, a field that stays on the device or is
+ * updated as the map grows, fields of the voxel map, gradients of the field, anything in the batch runners.
+ * HIP kernels (tsdf_field.hip), one thread per cell, the lanes of a wave adjacent along axis 2: tsdf_field_sites_kernel (the
+ * cell's own read-only probe and at most six for its neighbours; the state, 0 at a site and VISO_FIELD_NONE elsewhere, the sites
+ * counted with one ballot a round of 256 cells and one atomic per wave), then tsdf_field_pass_kernel three times, along axis 2, 1 and 0: the exact
+ * Euclidean transform axis by axis, g'(i) = min_j g(j) + (i - j)^2 along a line, from one buffer into the other; the minimum is
+ * searched outward from i and the search ends once d^2 >= the best value so far. */
+#define VISO_FIELD_UNKNOWN_IS_SITE 1u
+#define VISO_FIELD_STATE_SURFACE 4u
+#define VISO_FIELD_NONE 0xffffffffu
+/* sq_out: uint32 [n0][n1][n2]; state_out_or_null: uint8 of the same shape; n_sites_or_null: the number of sites. */
+int viso_tsdf_distance_field(viso_tsdf* t, uint32_t min_weight, const viso_voxel_box* box, uint32_t flags,
+                             uint32_t* sq_out, uint8_t* state_out_or_null, size_t n_cap, size_t* n_sites_or_null);
+
 #ifdef __cplusplus
 }
 #endif

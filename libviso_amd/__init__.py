@@ -236,7 +236,7 @@ from .plain import (HARRIS_K, F_from_P, collect_matches, detect_harris_binned, e
 from .dense import (DISP_INVALID, disparity_params, disparity_to_float, disparity_to_points, filter_speckles,  # noqa: E402,F401
                     rectify_images, rectify_map, sgm_frame_bytes, sgm_params, sgm_set_workspace_cap, speckle_frame_bytes, speckle_params,
                     speckle_set_workspace_cap, stereo_disparity, stereo_sgm)
-from .maps import (TsdfMap, TsdfNormals, VoxelMap, _box_arg, map_entry_centroids, map_params, map_ply_bytes, merge_entries,  # noqa: E402,F401
+from .maps import (DistanceField, TsdfMap, TsdfNormals, VoxelMap, _box_arg, map_entry_centroids, map_params, map_ply_bytes, merge_entries,  # noqa: E402,F401
                    mesh_normals_ply_bytes, mesh_ply_bytes, shade_normals, surface_normals_ply_bytes, surface_ply_bytes,
                    write_mesh_normals_ply, write_surface_normals_ply, tsdf_align_gray_params, tsdf_align_params, tsdf_crossing_points,
                    tsdf_fuse_options, tsdf_normal_gray_matrix, tsdf_normal_matrix, tsdf_params, voxel_box, write_map_ply, write_mesh_ply,

@@ -157,6 +157,12 @@ class VoxelBox(C.Structure):
     _fields_ = [("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3)]
 
 
+# include/viso_hip.h, "TSDF distance field": the flag, the state bit of a surface voxel, and sq where the box holds no site
+FIELD_UNKNOWN_IS_SITE = 1
+FIELD_STATE_SURFACE = 4
+FIELD_NONE = 0xffffffff
+
+
 class TsdfParams(C.Structure):
     """struct viso_tsdf_params (include/viso_hip.h, "TSDF map")."""
     _fields_ = [("voxel", C.c_double), ("trunc_voxels", C.c_int32), ("min_disp16", C.c_int32), ("capacity_log2", C.c_int32)]
@@ -463,6 +469,8 @@ PROTOTYPES = {
     "tsdf_evict_count": (i, [vp, P(VoxelBox), szp]),
     "tsdf_evict": (i, [vp, P(VoxelBox), vp, sz, szp]),
     "tsdf_evict_gray": (i, [vp, P(VoxelBox), vp, sz, szp]),
+    # TSDF distance field
+    "tsdf_distance_field": (i, [vp, u32, P(VoxelBox), u32, u32p, u8p, sz, szp]),
 }
 
 # what the oracle library exports under its own prefix with the same signatures (declare_common, oracle/pyoracle.py)

@@ -2,7 +2,8 @@
                                  [--surface | --mesh [--trunc T --min-weight N] [--render DIR [--render-depth M]] [--gray IMAGE_DIR]
                                                      [--normals] [--shaded DIR]
                                                      [--align [--aligned-poses FILE --align-voxel-gate G --align-photo WEIGHT]]
-                                                     [--carve VOXELS [--carve-near METRES]] [--depth-weights SHIFT[,MAX]]]
+                                                     [--carve VOXELS [--carve-near METRES]] [--depth-weights SHIFT[,MAX]]
+                                                     [--distance-field FILE.npz [--field-half-side METRES]]]
                                  [--window METRES [--archive FILE.npy]]
 
 Fuses the maps a KITTI runner wrote with --disparity DIR and the poses of its pose file into one voxel map on the device
@@ -49,6 +50,11 @@ float32 centroid of each voxel, count the number of points fused into it.
   --depth-weights SHIFT[,MAX]  with --surface or --mesh: an update weighs min(max(disp16^2 >> SHIFT, 1), MAX) and not 1 (MAX: 255),
                  so a near measurement pulls the average harder than a far one; --min-weight and the PLY's weight then are sums of
                  such weights.  Without --carve and --depth-weights the output is byte for byte what it was.
+  --distance-field FILE.npz  with --surface or --mesh: after fusing, also write the distance field of the surface (include/viso_hip.h,
+                 "TSDF distance field"; --min-weight applies) over the box of voxels that a cube of half side --field-half-side METRES
+                 (20) around the last fused camera position touches, clipped to 512 voxels an axis around that position: sq (uint32
+                 [n0][n1][n2], the squared distance to the nearest surface voxel of the box in voxels; 4294967295: none), state
+                 (uint8: 0 unknown, 1 in front, 2 behind, +4 on the surface), lo (the box's first voxel) and voxel, as a numpy .npz.
   --window METRES  keep the map on the device to a cube of this half side around the camera (include/viso_hip.h, "Map eviction"):
                  before map i is fused (and, with --align, aligned), every voxel outside the box of voxels that the cube around the
                  translation of pose i touches leaves the table, on the device, and is appended to an archive on the host.  So a
@@ -69,6 +75,7 @@ import zlib
 import numpy as np
 
 DISP_INVALID = -16
+FIELD_MAX_AXIS = 512  # the longest box of a distance field, in voxels
 DISP_PNG_MAX = 4095   # the largest map value a 16-bit file holds (x 16)
 RENDER_VIEWS = 16     # views of one --render call
 
@@ -238,6 +245,18 @@ def list_maps(directory):
     return sorted(n for n in os.listdir(directory) if n.lower().endswith(".png"))
 
 
+def field_box(centre, half_side, voxel):
+    """((lo, hi), clipped): libviso_amd.voxel_box of the cube around centre, every axis longer than FIELD_MAX_AXIS voxels cut to
+    that many around the voxel that holds the centre."""
+    import libviso_amd
+    lo, hi = (v.astype(np.int64) for v in libviso_amd.voxel_box(centre, half_side, voxel))
+    long = hi - lo > FIELD_MAX_AXIS
+    mid = np.floor(np.asarray(centre, np.float64) / voxel).astype(np.int64)
+    lo = np.where(long, np.maximum(mid - FIELD_MAX_AXIS // 2, -(1 << 31)), lo)
+    hi = np.where(long, np.minimum(lo + FIELD_MAX_AXIS, (1 << 31) - 1), hi)
+    return (lo, hi), bool(long.any())
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m libviso_amd.fuse_map", description=__doc__.split("\n\n")[1])
     ap.add_argument("disparity_dir"); ap.add_argument("poses"); ap.add_argument("calib"); ap.add_argument("out")
@@ -266,6 +285,9 @@ def main(argv=None):
     ap.add_argument("--carve-near", type=float, default=None, metavar="METRES", help="with --carve: leave out free-space samples nearer than this (0)")
     ap.add_argument("--depth-weights", default=None, metavar="SHIFT[,MAX]", help="with --surface or --mesh: an update weighs "
                     "min(max(disp16^2 >> SHIFT, 1), MAX), MAX 255")
+    ap.add_argument("--distance-field", metavar="FILE.npz", help="with --surface or --mesh: also write the distance field of the surface "
+                    "around the last fused camera position")
+    ap.add_argument("--field-half-side", type=float, default=None, metavar="METRES", help="with --distance-field: the half side of its box (20)")
     ap.add_argument("--window", type=float, default=None, metavar="METRES", help="keep the map to a cube of this half side around the camera; "
                     "what leaves it goes to an archive on the host (OUT.ply: the whole map without --surface or --mesh, else the live window)")
     ap.add_argument("--archive", metavar="FILE.npy", help="with --window: write the merged evicted voxels as a numpy array of entries")
@@ -302,6 +324,12 @@ def main(argv=None):
         ap.error("--normals needs --surface or --mesh (only a TSDF map has normals)")
     if a.shaded and not a.render:
         ap.error("--shaded needs --render DIR (the shaded images are of the rendered views)")
+    if a.distance_field and not (a.surface or a.mesh):
+        ap.error("--distance-field needs --surface or --mesh (only a TSDF map has a surface to be far from)")
+    if a.field_half_side is not None and not a.distance_field:
+        ap.error("--field-half-side needs --distance-field")
+    if a.field_half_side is not None and not (np.isfinite(a.field_half_side) and a.field_half_side >= 0):
+        ap.error("--field-half-side needs a half side >= 0 in metres")
     if a.gray and not (a.surface or a.mesh):
         ap.error("--gray needs --surface or --mesh (only a TSDF map carries intensity)")
     import libviso_amd
@@ -387,6 +415,13 @@ def main(argv=None):
                         if a.shaded:
                             write_png8(os.path.join(a.shaded, names[i]), np.where(near[i - i0], 0, lit[i - i0]).astype(np.uint8))
                 print(f"fuse_map: {e - b} views rendered to {a.render_depth} m ({n_near} pixels beyond 255.9 px left out) -> {a.render}")
+            if a.distance_field and e > b:
+                half = 20.0 if a.field_half_side is None else a.field_half_side
+                box, clipped = field_box(poses[e - 1][:3, 3], half, a.voxel)
+                field = tsdf.distance_field(box, min_weight=a.min_weight)
+                np.savez(a.distance_field, sq=field.sq, state=field.state, lo=field.box[0], voxel=np.float64(a.voxel))
+                print(f"fuse_map: distance field of {' x '.join(str(v) for v in field.sq.shape)} voxels, {field.n_sites} surface voxels" +
+                      (f" (the box of {half} m clipped to {FIELD_MAX_AXIS} voxels an axis)" if clipped else "") + f" -> {a.distance_field}")
             shade = None   # the intensity of the PLY's vertices
             if a.mesh:
                 vertices, triangles = tsdf.mesh(a.min_weight)

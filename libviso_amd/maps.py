@@ -5,7 +5,7 @@ import ctypes as C
 import numpy as np
 
 from . import _call, _Handle, _map16, _params, _pose_arg, _struct_arg, load
-from .abi import (MAP_DEFAULTS, MAP_ENTRY_DTYPE, TSDF_ALIGN_DEFAULTS, TSDF_ALIGN_GRAY_DEFAULTS, TSDF_ALIGN_GRAY_STEP_DTYPE,
+from .abi import (FIELD_NONE, FIELD_UNKNOWN_IS_SITE, MAP_DEFAULTS, MAP_ENTRY_DTYPE, TSDF_ALIGN_DEFAULTS, TSDF_ALIGN_GRAY_DEFAULTS, TSDF_ALIGN_GRAY_STEP_DTYPE,
                   TSDF_ALIGN_STEP_DTYPE, TSDF_ALIGNMENT_DTYPE, TSDF_ALIGNMENT_GRAY_DTYPE, TSDF_CROSSING_DTYPE, TSDF_DEFAULTS,
                   TSDF_ENTRY_DTYPE, TSDF_FUSE_DEFAULTS, TSDF_GRAY_ENTRY_DTYPE, TSDF_MESH_VERTEX_DTYPE, TSDF_NORMAL_COUNTERS, TSDF_NORMAL_DTYPE,
                   TSDF_NORMAL_GRAY_COUNTERS, TSDF_NORMAL_GRAY_DTYPE, MapCounters, MapParams, TsdfAlignGrayParams, TsdfAlignParams,
@@ -490,6 +490,16 @@ class TsdfMap(_TableMap):
         render give a unit normal for every vertex, crossing and rendered hit.  A plain or a gray map."""
         return TsdfNormals(self)
 
+    @property
+    def distance_field(self):
+        """viso_tsdf_distance_field (include/viso_hip.h, "TSDF distance field"), called as
+        `tsdf.distance_field(box, min_weight=2, unknown_is_site=False)`: a DistanceField over box = (lo, hi) (voxel_box makes one
+        around a point; 1 .. 512 voxels an axis), for every voxel of it the exact squared distance in voxels to the nearest
+        surface voxel of the box at min_weight; unknown_is_site=True: to the nearest surface or unknown voxel, the conservative field
+        for planning.  Surface beyond the box does not exist for the call: pad the box by the clearance that matters.  Reads the
+        map only; a plain or a gray map.  A property that hands out the call, not a method."""
+        return _DistanceFieldCall(self)
+
     def surface(self, min_weight=1):
         """viso_tsdf_surface: the sign changes between neighbouring voxels of at least min_weight updates as a TSDF_CROSSING_DTYPE
         array (k, axis, wa, wb, sa, sb), sorted by (key, axis)."""
@@ -604,6 +614,58 @@ class TsdfMap(_TableMap):
             d, w, g, nrm = d[0], (w[0] if weights else None), (g[0] if gray else None), (nrm[0] if normals else None)
         out = (d,) + ((w,) if weights else ()) + ((g,) if gray else ()) + ((nrm,) if normals else ())
         return out if len(out) > 1 else d
+
+
+class DistanceField:
+    """TsdfMap.distance_field: the distance field of a TSDF map's surface over a box of voxels (include/viso_hip.h, "TSDF distance
+    field").  sq: uint32 (n0, n1, n2), the squared distance of cell i (the voxel box[0] + i) to the nearest site in voxels, FIELD_NONE
+    everywhere when the box has no site; state: uint8 of the same shape, 0 unknown, 1 in front of the surface, 2 behind it, plus
+    FIELD_STATE_SURFACE on surface voxels; box = (lo, hi) as int32 [3] arrays; voxel in metres; n_sites."""
+
+    def __init__(self, sq, state, box, voxel, n_sites):
+        self.sq, self.state, self.voxel, self.n_sites = sq, state, float(voxel), int(n_sites)
+        self.box = (np.array(box[0], np.int32), np.array(box[1], np.int32))
+
+    def metres(self):
+        """float32 (n0, n1, n2): sqrt(sq) * voxel computed in double, inf where there is no site."""
+        d = np.sqrt(self.sq.astype(np.float64)) * self.voxel
+        return np.where(self.sq == FIELD_NONE, np.inf, d).astype(np.float32)
+
+    def signed_metres(self):
+        """metres(), negated where the state is behind the surface."""
+        d = self.metres()
+        return np.where((self.state & 3) == 2, -d, d)
+
+    def at(self, points):
+        """(sq, outside) of float [n][3] points in metres: sq of the cell floor(p / voxel) - lo that holds each point (uint32 [n],
+        FIELD_NONE for a point outside the box), and the bool [n] mask of the points outside the box (not finite ones included)."""
+        p = np.asarray(points, np.float64)
+        if p.ndim != 2 or p.shape[1] != 3:
+            raise ValueError("DistanceField.at: points must be [n][3]")
+        with np.errstate(invalid="ignore"):
+            cell = np.floor(p / self.voxel) - self.box[0].astype(np.float64)
+            outside = ~((cell >= 0) & (cell < np.asarray(self.sq.shape, np.float64))).all(axis=1)   # a NaN is outside
+        i = np.where(outside[:, None], 0, cell).astype(np.int64)
+        return np.where(outside, np.uint32(FIELD_NONE), self.sq[i[:, 0], i[:, 1], i[:, 2]]).astype(np.uint32), outside
+
+
+class _DistanceFieldCall:
+    """What TsdfMap.distance_field hands out: the call on that map."""
+
+    def __init__(self, tsdf):
+        self.tsdf = tsdf
+
+    def __call__(self, box, min_weight=2, unknown_is_site=False):
+        t = self.tsdf
+        b = _box_arg("TsdfMap.distance_field", box)
+        lo, hi = np.array(b.lo, np.int64), np.array(b.hi, np.int64)
+        n = hi - lo
+        if (n < 1).any() or (n > 512).any():
+            raise ValueError("TsdfMap.distance_field: the box must have 1 .. 512 voxels on every axis")
+        sq, state, n_sites = np.empty(tuple(n), np.uint32), np.empty(tuple(n), np.uint8), C.c_size_t()
+        _call(t.L.viso_tsdf_distance_field, t.h, int(min_weight), C.byref(b), FIELD_UNKNOWN_IS_SITE if unknown_is_site else 0,
+              ptr(sq, C.c_uint32), ptr(state, C.c_uint8), sq.size, C.byref(n_sites))
+        return DistanceField(sq, state, (lo, hi), t.voxel, n_sites.value)
 
 
 class TsdfNormals:

@@ -3,6 +3,7 @@
 
   python tools/tsdf_bench.py [--frames N] [--reps N] [--capacity-log2 N] [--render-views N] [--kernel-only] [--out FILE]
                              [--carve C [--carve-near M]] [--depth-weights S] [--options-capacity-log2 N] [--fuse-only]
+                             [--distance-field]
 
 The pairs and poses are those of tools/map_bench.py: 17 seeded synthetic frames repeated, frame t seen from a camera that has moved
 0.8 t m forward and turned 0.002 t rad.  Legs (host clock around work that ends in a synchronise, medians of alternating
@@ -41,6 +42,11 @@ repetitions):
                loop as fuse_tsdf, with its n_updates / n_points and its ratio to fuse_tsdf.  Its table is the first capacity from
                --options-capacity-log2 (default: fuse_tsdf's) on that holds the carved scene; give one that does, since every
                update that finds a table full probes all of its slots.  --fuse-only: only clear, fuse_tsdf and fuse_options are run.
+  distance_field  (with --distance-field, which runs only this section; include/viso_hip.h, "TSDF distance field")
+               TsdfMap.distance_field over boxes of 256 x 256 x 64 and 512 x 512 x 64 voxels around the camera position of the middle
+               frame, min_weight 2, with and without unknown_is_site: the four launches, the copy of sq and state to the host (5
+               bytes a cell) and the free.  Where scipy imports, scipy.ndimage.distance_transform_edt of the same site grid on the
+               host beside it, as context.
 n_updates / n_points from viso_tsdf_stats is the number of voxels a pixel's band touches.  --kernel-only runs clear + fuse_tsdf
 --reps times, the extractions and the render once and the two align calls --reps times: the run to put under `rocprofv3 --kernel-trace --stats` for the kernels' own times.  The
 count the result is held against (not a measurement) is printed with it."""
@@ -80,6 +86,7 @@ def main():
     ap.add_argument("--depth-weights", type=int, default=None, metavar="S")
     ap.add_argument("--options-capacity-log2", type=int, default=None)
     ap.add_argument("--fuse-only", action="store_true")
+    ap.add_argument("--distance-field", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     nf = a.frames
@@ -161,6 +168,48 @@ def main():
             os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
             with open(a.out, "w") as f:
                 json.dump(res, f, indent=1)
+        tsdf.close(); b.close(); ctx.close()
+        return
+
+    if a.distance_field:
+        try:
+            from scipy import ndimage
+        except ImportError:
+            ndimage = None
+        mid = np.floor(poses[nf // 2][:3, 3] / tsdf.voxel).astype(np.int64)
+        res = {"frames": nf, "capacity_log2": log2, "reps": a.reps, "min_weight": 2, "voxels": int(len(tsdf.entries(2))), "boxes": {}}
+        for shape in ((256, 256, 64), (512, 512, 64)):
+            half = np.array(shape) // 2
+            box = (mid - half, mid - half + np.array(shape))
+            legs = {"surface": [], "unknown_is_site": []}
+            for rep_ in range(a.reps + 1):   # alternating; the first round is the warm-up
+                for name in legs:
+                    ms = clock(lambda: tsdf.distance_field(box, min_weight=2, unknown_is_site=name == "unknown_is_site"))
+                    if rep_:
+                        legs[name].append(ms)
+            f = tsdf.distance_field(box, min_weight=2)
+            fu = tsdf.distance_field(box, min_weight=2, unknown_is_site=True)
+            r = {"box": [[int(v) for v in box[0]], [int(v) for v in box[1]]], "n_sites": f.n_sites, "n_sites_unknown_is_site": fu.n_sites,
+                 "unknown_share": float((f.state == 0).mean()), "sq_max": int(f.sq[f.sq != 0xffffffff].max()) if f.n_sites else None,
+                 "ms_median": {k: float(np.median(v)) for k, v in legs.items()}, "ms_min": {k: float(np.min(v)) for k, v in legs.items()},
+                 "ms_max": {k: float(np.max(v)) for k, v in legs.items()}}
+            if ndimage is not None:
+                site = (f.state & 4) != 0
+                host = []
+                for _ in range(a.reps):
+                    t0 = time.perf_counter()
+                    edt = ndimage.distance_transform_edt(~site)
+                    host.append((time.perf_counter() - t0) * 1e3)
+                r["scipy_edt_ms_median"] = float(np.median(host))
+                r["scipy_agrees"] = bool(f.n_sites == 0 or np.array_equal(np.rint(edt * edt).astype(np.uint32), f.sq))
+            res["boxes"]["x".join(str(v) for v in shape)] = r
+        print(json.dumps(res))
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                json.dump(res, f, indent=1)
+        if omap is not None:
+            omap.close()
         tsdf.close(); b.close(); ctx.close()
         return
 
