@@ -1586,6 +1586,57 @@ int viso_tsdf_evict_gray(viso_tsdf* t, const viso_voxel_box* keep, viso_tsdf_gra
 int viso_tsdf_distance_field(viso_tsdf* t, uint32_t min_weight, const viso_voxel_box* box, uint32_t flags,
                              uint32_t* sq_out, uint8_t* state_out_or_null, size_t n_cap, size_t* n_sites_or_null);
 
+/* ------------------------------------------------ TSDF travel field: how far every voxel of a box is from a goal for a body that
+ * keeps a clearance from the surface, on the device (opt-in; NOT in the reference)
+ *
+ * For every voxel of an axis-aligned box of voxel indices, the cost of the cheapest way to a goal through the cells that a sphere
+ * of a given radius may occupy: whether a body gets from here to there, how far it is, and (following the costs downhill) which
+ * way.  It is the geodesic question behind the distance field, and the first output of the map that depends on connectivity.  The
+ * call reads the table only.  This definition is the contract; the device output is bit-identical to tests/travel_ref.py.
+ *   1. Box, usable voxels, states, surface voxels, sites and sq: rules 1 to 6 of "TSDF distance field" with the same min_weight and
+ *      flags; VISO_FIELD_UNKNOWN_IS_SITE is the only flag, any other bit VISO_ERR_ARG.  cost_out is stored like sq_out, and n_cap
+ *      counts cells.  sq_out and state_out, where given, receive exactly what viso_tsdf_distance_field returns.
+ *   2. Free cell: a cell of the box that is not behind the surface ((state & 3) != 2), is not a site, and has sq >= clearance_sq,
+ *      VISO_FIELD_NONE counting as at least anything.  clearance_sq is any value below VISO_FIELD_NONE (0: no clearance);
+ *      VISO_FIELD_NONE itself gives VISO_ERR_ARG.  Without the flag the unknown cells are free, the optimistic field; with it they
+ *      are sites and never free, the conservative field.
+ *   3. Goals: 1 <= n_goals <= 65536 absolute voxel indices [n_goals][3].  A goal outside the box, or whose cell is not free, is
+ *      skipped; *n_goals_used is the number of entries of the list that were used (a cell named twice counts twice, and does no
+ *      harm).  With no used goal every cell is VISO_FIELD_NONE and the call returns VISO_OK.
+ *   4. Moves: from a free cell to any of its 26 neighbours inside the box that is free, at a cost of 3, 4 or 5 when 1, 2 or 3
+ *      indices change: the <3,4,5> chamfer, in units of a third of a voxel.  There is no corner rule: a diagonal move is allowed
+ *      whatever lies in the cells beside it.  Inflating the obstacles by the clearance is what keeps a path off the surface.
+ *   5. Result: cost[c] = the smallest summed cost of a sequence of moves from c to a used goal: 0 at a used goal;
+ *      VISO_FIELD_NONE where c is not free or no sequence exists; a finite value is at most 5 * 2^27.  *n_reached is the number
+ *      of finite cells.  *n_rounds is the number of relaxation launches that found work: a diagnostic, not part of the bit-exact
+ *      contract.
+ *   6. Errors and locking follow the distance field.  Every argument check (min_weight, box, flags, clearance_sq, a null goals or
+ *      cost_out, n_goals, n_cap, then the handle) happens before a device is touched, and a refused call writes nothing.  An
+ *      overflowed map refuses with VISO_ERR_NOMEM; a handle that is not a live TSDF map, or whose context is gone, VISO_ERR_ARG.
+ *      The call takes the map's lock and is a pure reader: the table, its statistics and the overflow mark are untouched.
+ *   7. Bounds.  Device memory of a call: two uint32 and one uint8 a cell (the distance field's; the buffer its passes leave free
+ *      holds the costs), three uint32 a tile of 8 x 8 x 8 cells, 12 bytes a goal and 8 words; VISO_ERR_NOMEM when it cannot be
+ *      allocated.  Every loop on the device is bounded: the distance field's as stated there; a block of the cell kernels takes
+ *      at most 256 rounds of cells; a tile is swept at most 513 times a visit (512 cells, and a chain of lowerings visits a cell
+ *      once); a workgroup visits at most tiles / 2048 + 1 tiles a launch.  The host launches at most cells + 1 rounds: a cheapest
+ *      sequence leaves a tile at a different cell every time, so it is settled after as many rounds as it has cells.  More
+ *      returns VISO_ERR_HIP with a message; it is never a reason to go on.
+ * In a box without obstacles the cost between two cells whose indices differ by (a >= b >= c >= 0), absolute values sorted, is
+ * 3a + b + c.  So cost / 3 lies between 4 / (3 sqrt 2) = 0.943 and sqrt(11) / 3 = 1.106 times the Euclidean distance in voxels; the
+ * extremes are along (1, 1, 0) and (3, 1, 1).
+ * Out of scope: any-angle or smoothed paths; a field that stays on the device or is updated incrementally; bodies other than a
+ * sphere; boxes over 512 voxels an axis; the voxel map; the batch runners.
+ * HIP kernels (tsdf_travel.hip), behind the distance field's: tsdf_travel_init_kernel and tsdf_travel_goals_kernel (the starting
+ * costs; a cell that is not free keeps a value of its own until the end), tsdf_travel_relax_kernel once a round (a workgroup per
+ * listed tile: the tile and a halo of one cell in LDS, sweeps over the 26 neighbours until nothing falls, its own cells written
+ * back, the neighbour tiles that see a lowered cell listed for the next round, each once), tsdf_travel_finish_kernel.  The launch
+ * boundary is the only ordering between workgroups; the result is the unique fixed point whatever the schedule. */
+/* goals: int32 [n_goals][3]; cost_out, sq_out_or_null: uint32 [n0][n1][n2]; state_out_or_null: uint8 of the same shape. */
+int viso_tsdf_travel_field(viso_tsdf* t, uint32_t min_weight, const viso_voxel_box* box, uint32_t flags, uint32_t clearance_sq,
+                           const int32_t* goals, size_t n_goals, uint32_t* cost_out, uint32_t* sq_out_or_null,
+                           uint8_t* state_out_or_null, size_t n_cap, size_t* n_goals_used_or_null, size_t* n_reached_or_null,
+                           size_t* n_rounds_or_null);
+
 #ifdef __cplusplus
 }
 #endif

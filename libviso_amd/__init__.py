@@ -236,11 +236,11 @@ from .plain import (HARRIS_K, F_from_P, collect_matches, detect_harris_binned, e
 from .dense import (DISP_INVALID, disparity_params, disparity_to_float, disparity_to_points, filter_speckles,  # noqa: E402,F401
                     rectify_images, rectify_map, sgm_frame_bytes, sgm_params, sgm_set_workspace_cap, speckle_frame_bytes, speckle_params,
                     speckle_set_workspace_cap, stereo_disparity, stereo_sgm)
-from .maps import (DistanceField, TsdfMap, TsdfNormals, VoxelMap, _box_arg, map_entry_centroids, map_params, map_ply_bytes, merge_entries,  # noqa: E402,F401
+from .maps import (DistanceField, TravelField, TsdfMap, TsdfNormals, VoxelMap, _box_arg, map_entry_centroids, map_params, map_ply_bytes, merge_entries,  # noqa: E402,F401
                    mesh_normals_ply_bytes, mesh_ply_bytes, shade_normals, surface_normals_ply_bytes, surface_ply_bytes,
                    write_mesh_normals_ply, write_surface_normals_ply, tsdf_align_gray_params, tsdf_align_params, tsdf_crossing_points,
                    tsdf_fuse_options, tsdf_normal_gray_matrix, tsdf_normal_matrix, tsdf_params, voxel_box, write_map_ply, write_mesh_ply,
-                   write_surface_ply)
+                   write_surface_ply, travel_clearance_sq)
 from .estimators import (chain_covariances, pose_covariance, pose_refine, refines_as_covariances, window_refine,  # noqa: E402,F401
                          window_refines_as_covariances)
 from .batch import Batch, Context, PinnedArray  # noqa: E402,F401

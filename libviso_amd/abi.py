@@ -471,6 +471,8 @@ PROTOTYPES = {
     "tsdf_evict_gray": (i, [vp, P(VoxelBox), vp, sz, szp]),
     # TSDF distance field
     "tsdf_distance_field": (i, [vp, u32, P(VoxelBox), u32, u32p, u8p, sz, szp]),
+    # TSDF travel field
+    "tsdf_travel_field": (i, [vp, u32, P(VoxelBox), u32, u32, i32p, sz, u32p, u32p, u8p, sz, szp, szp, szp]),
 }
 
 # what the oracle library exports under its own prefix with the same signatures (declare_common, oracle/pyoracle.py)

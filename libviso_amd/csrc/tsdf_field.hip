@@ -18,18 +18,11 @@
 // Every loop is bounded by an axis length (<= 512), by the 256 rounds of the sites kernel, or is the probe's one round of the
 // slots.  Device memory of a call: two uint32 and one uint8 a cell.  No LDS, no scratch.
 #include "common.h"
-#include "tsdf_table.h"
+#include "tsdf_field.h"
 
-#define FIELD_MAX_AXIS 512
 #define FIELD_SITE_BLOCKS 2048   // the grid of the sites kernel: with the 2^27 cells of the largest box, 256 rounds a block
 #define FIELD_STATE_FRONT 1u
 #define FIELD_STATE_BEHIND 2u
-
-struct FieldBox {
-    int32_t lo[3];
-    uint32_t n[3];
-    uint32_t cells;   // n0 n1 n2 <= 2^27
-};
 
 // weight >= min_weight of the voxel `key` in the table: *neg = (sum < 0).  One read-only probe.
 __device__ __forceinline__ bool field_usable(const TsdfTable& t, unsigned long long key, uint32_t min_weight, bool* neg) {
@@ -104,6 +97,34 @@ __global__ __launch_bounds__(256) void tsdf_field_pass_kernel(const uint32_t* __
     out[c] = best;
 }
 
+bool field_box_arg(const char* where, const viso_voxel_box* box, FieldBox* b) {
+    size_t cells = 1;
+    for (int i = 0; i < 3; ++i) {
+        const long long n = (long long)box->hi[i] - (long long)box->lo[i];
+        if (n < 1 || n > FIELD_MAX_AXIS) {
+            viso_set_error("%s: bad argument (the box has %lld voxels on axis %d: 1 .. %d)", where, n, i, FIELD_MAX_AXIS);
+            return false;
+        }
+        b->lo[i] = box->lo[i];
+        b->n[i] = (uint32_t)n;
+        cells *= (size_t)n;
+    }
+    b->cells = (uint32_t)cells;
+    return true;
+}
+
+int field_passes(VoxelHost* h, const TsdfTable& t, uint32_t min_weight, const FieldBox& b, uint32_t unknown_is_site, uint32_t* result,
+                 uint32_t* other, uint8_t* d_state, unsigned long long* n_sites) {
+    const dim3 grid((b.cells + 255u) / 256u);
+    const dim3 site_grid(grid.x < FIELD_SITE_BLOCKS ? grid.x : FIELD_SITE_BLOCKS);
+    return voxel_pass(h, [&](hipStream_t s) {
+        hipLaunchKernelGGL(tsdf_field_sites_kernel, site_grid, dim3(256), 0, s, t, min_weight, b, unknown_is_site, other, d_state);
+        hipLaunchKernelGGL(tsdf_field_pass_kernel, grid, dim3(256), 0, s, other, result, b.cells, 1u, b.n[2]);
+        hipLaunchKernelGGL(tsdf_field_pass_kernel, grid, dim3(256), 0, s, result, other, b.cells, b.n[2], b.n[1]);
+        hipLaunchKernelGGL(tsdf_field_pass_kernel, grid, dim3(256), 0, s, other, result, b.cells, b.n[1] * b.n[2], b.n[0]);
+    }, n_sites);
+}
+
 extern "C" int viso_tsdf_distance_field(viso_tsdf* t, uint32_t min_weight, const viso_voxel_box* box, uint32_t flags, uint32_t* sq_out,
                                         uint8_t* state_out_or_null, size_t n_cap, size_t* n_sites_or_null) {
     const char* where = "viso_tsdf_distance_field";
@@ -113,18 +134,8 @@ extern "C" int viso_tsdf_distance_field(viso_tsdf* t, uint32_t min_weight, const
         return VISO_ERR_ARG;
     }
     FieldBox b;
-    size_t cells = 1;
-    for (int i = 0; i < 3; ++i) {
-        const long long n = (long long)box->hi[i] - (long long)box->lo[i];
-        if (n < 1 || n > FIELD_MAX_AXIS) {
-            viso_set_error("%s: bad argument (the box has %lld voxels on axis %d: 1 .. %d)", where, n, i, FIELD_MAX_AXIS);
-            return VISO_ERR_ARG;
-        }
-        b.lo[i] = box->lo[i];
-        b.n[i] = (uint32_t)n;
-        cells *= (size_t)n;
-    }
-    b.cells = (uint32_t)cells;
+    if (!field_box_arg(where, box, &b)) return VISO_ERR_ARG;
+    const size_t cells = b.cells;
     if (n_cap < cells) {
         viso_set_error("%s: the %zu cells of the box do not fit the %zu given", where, cells, n_cap);
         return VISO_ERR_ARG;
@@ -148,16 +159,8 @@ extern "C" int viso_tsdf_distance_field(viso_tsdf* t, uint32_t min_weight, const
     uint32_t* ga = reinterpret_cast<uint32_t*>(d);
     uint32_t* gb = ga + cells;
     uint8_t* d_state = reinterpret_cast<uint8_t*>(gb + cells);
-    const dim3 grid((unsigned)((cells + 255) / 256));
-    const dim3 site_grid(grid.x < FIELD_SITE_BLOCKS ? grid.x : FIELD_SITE_BLOCKS);
-    const uint32_t unknown = flags & VISO_FIELD_UNKNOWN_IS_SITE;
     unsigned long long n_sites = 0;
-    r = voxel_pass(h, [&](hipStream_t s) {
-        hipLaunchKernelGGL(tsdf_field_sites_kernel, site_grid, dim3(256), 0, s, v.t, min_weight, b, unknown, ga, d_state);
-        hipLaunchKernelGGL(tsdf_field_pass_kernel, grid, dim3(256), 0, s, ga, gb, b.cells, 1u, b.n[2]);
-        hipLaunchKernelGGL(tsdf_field_pass_kernel, grid, dim3(256), 0, s, gb, ga, b.cells, b.n[2], b.n[1]);
-        hipLaunchKernelGGL(tsdf_field_pass_kernel, grid, dim3(256), 0, s, ga, gb, b.cells, b.n[1] * b.n[2], b.n[0]);
-    }, &n_sites);
+    r = field_passes(h, v.t, min_weight, b, flags & VISO_FIELD_UNKNOWN_IS_SITE, gb, ga, d_state, &n_sites);
     hipError_t e = hipSuccess;
     if (r >= 0) {
         hipStream_t s = h->ctx->stream;

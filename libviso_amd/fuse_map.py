@@ -3,7 +3,8 @@
                                                      [--normals] [--shaded DIR]
                                                      [--align [--aligned-poses FILE --align-voxel-gate G --align-photo WEIGHT]]
                                                      [--carve VOXELS [--carve-near METRES]] [--depth-weights SHIFT[,MAX]]
-                                                     [--distance-field FILE.npz [--field-half-side METRES]]]
+                                                     [--distance-field FILE.npz [--field-half-side METRES]]
+                                                     [--travel-field FILE.npz [--travel-clearance METRES] [--field-half-side METRES]]]
                                  [--window METRES [--archive FILE.npy]]
 
 Fuses the maps a KITTI runner wrote with --disparity DIR and the poses of its pose file into one voxel map on the device
@@ -55,6 +56,13 @@ float32 centroid of each voxel, count the number of points fused into it.
                  (20) around the last fused camera position touches, clipped to 512 voxels an axis around that position: sq (uint32
                  [n0][n1][n2], the squared distance to the nearest surface voxel of the box in voxels; 4294967295: none), state
                  (uint8: 0 unknown, 1 in front, 2 behind, +4 on the surface), lo (the box's first voxel) and voxel, as a numpy .npz.
+  --travel-field FILE.npz  with --surface or --mesh: after fusing, also write the travel field (include/viso_hip.h, "TSDF travel
+                 field"; --min-weight applies) over the box of --distance-field (--field-half-side METRES, 20) around the last fused
+                 camera position, towards the first fused camera position as the goal, for a body that keeps --travel-clearance
+                 METRES (0) from the surface.  Unknown voxels count as free, the optimistic field: the cameras themselves stand in
+                 space that no map updated.  cost (uint32 [n0][n1][n2], thirds of a voxel along the cheapest <3,4,5> chamfer way;
+                 4294967295: not free or no way), box (int32 [2][3]: lo, hi), voxel and, when the last camera position is reached,
+                 path (int32 [m][3], the voxels of the way back from it to the goal), as a numpy .npz.
   --window METRES  keep the map on the device to a cube of this half side around the camera (include/viso_hip.h, "Map eviction"):
                  before map i is fused (and, with --align, aligned), every voxel outside the box of voxels that the cube around the
                  translation of pose i touches leaves the table, on the device, and is appended to an archive on the host.  So a
@@ -287,7 +295,11 @@ def main(argv=None):
                     "min(max(disp16^2 >> SHIFT, 1), MAX), MAX 255")
     ap.add_argument("--distance-field", metavar="FILE.npz", help="with --surface or --mesh: also write the distance field of the surface "
                     "around the last fused camera position")
-    ap.add_argument("--field-half-side", type=float, default=None, metavar="METRES", help="with --distance-field: the half side of its box (20)")
+    ap.add_argument("--field-half-side", type=float, default=None, metavar="METRES", help="with --distance-field or --travel-field: the half side "
+                    "of the box (20)")
+    ap.add_argument("--travel-field", metavar="FILE.npz", help="with --surface or --mesh: also write the travel field around the last fused "
+                    "camera position, the first fused camera position the goal")
+    ap.add_argument("--travel-clearance", type=float, default=None, metavar="METRES", help="with --travel-field: how far the body keeps from the surface (0)")
     ap.add_argument("--window", type=float, default=None, metavar="METRES", help="keep the map to a cube of this half side around the camera; "
                     "what leaves it goes to an archive on the host (OUT.ply: the whole map without --surface or --mesh, else the live window)")
     ap.add_argument("--archive", metavar="FILE.npy", help="with --window: write the merged evicted voxels as a numpy array of entries")
@@ -326,8 +338,14 @@ def main(argv=None):
         ap.error("--shaded needs --render DIR (the shaded images are of the rendered views)")
     if a.distance_field and not (a.surface or a.mesh):
         ap.error("--distance-field needs --surface or --mesh (only a TSDF map has a surface to be far from)")
-    if a.field_half_side is not None and not a.distance_field:
-        ap.error("--field-half-side needs --distance-field")
+    if a.travel_field and not (a.surface or a.mesh):
+        ap.error("--travel-field needs --surface or --mesh (only a TSDF map has a surface to keep clear of)")
+    if a.travel_clearance is not None and not a.travel_field:
+        ap.error("--travel-clearance needs --travel-field")
+    if a.travel_clearance is not None and not (np.isfinite(a.travel_clearance) and a.travel_clearance >= 0):
+        ap.error("--travel-clearance needs a clearance >= 0 in metres")
+    if a.field_half_side is not None and not (a.distance_field or a.travel_field):
+        ap.error("--field-half-side needs --distance-field or --travel-field")
     if a.field_half_side is not None and not (np.isfinite(a.field_half_side) and a.field_half_side >= 0):
         ap.error("--field-half-side needs a half side >= 0 in metres")
     if a.gray and not (a.surface or a.mesh):
@@ -422,6 +440,20 @@ def main(argv=None):
                 np.savez(a.distance_field, sq=field.sq, state=field.state, lo=field.box[0], voxel=np.float64(a.voxel))
                 print(f"fuse_map: distance field of {' x '.join(str(v) for v in field.sq.shape)} voxels, {field.n_sites} surface voxels" +
                       (f" (the box of {half} m clipped to {FIELD_MAX_AXIS} voxels an axis)" if clipped else "") + f" -> {a.distance_field}")
+            if a.travel_field and e > b:
+                half = 20.0 if a.field_half_side is None else a.field_half_side
+                box, clipped = field_box(poses[e - 1][:3, 3], half, a.voxel)
+                here, goal = (np.floor(poses[i][:3, 3] / a.voxel).astype(np.int64) for i in (e - 1, b))
+                travel = tsdf.travel_field(box, [goal], clearance=a.travel_clearance or 0.0, min_weight=a.min_weight, unknown_is_site=False)
+                way = travel.path(here)
+                arrays = dict(cost=travel.cost, box=np.stack(travel.box), voxel=np.float64(a.voxel))
+                if way is not None:
+                    arrays["path"] = way
+                np.savez(a.travel_field, **arrays)
+                print(f"fuse_map: travel field of {' x '.join(str(v) for v in travel.cost.shape)} voxels, {travel.n_reached} reached in "
+                      f"{travel.rounds} rounds, " + ("the goal is not free" if not travel.n_goals_used else "no way back" if way is None else
+                                                    f"the way back has {len(way)} voxels, {float(travel.cost[tuple(here - box[0])]) / 3 * a.voxel:.2f} m") +
+                      (f" (the box of {half} m clipped to {FIELD_MAX_AXIS} voxels an axis)" if clipped else "") + f" -> {a.travel_field}")
             shade = None   # the intensity of the PLY's vertices
             if a.mesh:
                 vertices, triangles = tsdf.mesh(a.min_weight)

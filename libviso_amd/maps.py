@@ -1,11 +1,12 @@
 """The two maps of include/viso_hip.h, VoxelMap and TsdfMap (csrc/voxelmap.hip, tsdf.hip, tsdf_align.hip over the table layer of
 csrc/voxel_host.hip): their parameters, eviction boxes, entry arithmetic on the host, and the PLY writers."""
 import ctypes as C
+import itertools
 
 import numpy as np
 
 from . import _call, _Handle, _map16, _params, _pose_arg, _struct_arg, load
-from .abi import (FIELD_NONE, FIELD_UNKNOWN_IS_SITE, MAP_DEFAULTS, MAP_ENTRY_DTYPE, TSDF_ALIGN_DEFAULTS, TSDF_ALIGN_GRAY_DEFAULTS, TSDF_ALIGN_GRAY_STEP_DTYPE,
+from .abi import (FIELD_NONE, FIELD_STATE_SURFACE, FIELD_UNKNOWN_IS_SITE, MAP_DEFAULTS, MAP_ENTRY_DTYPE, TSDF_ALIGN_DEFAULTS, TSDF_ALIGN_GRAY_DEFAULTS, TSDF_ALIGN_GRAY_STEP_DTYPE,
                   TSDF_ALIGN_STEP_DTYPE, TSDF_ALIGNMENT_DTYPE, TSDF_ALIGNMENT_GRAY_DTYPE, TSDF_CROSSING_DTYPE, TSDF_DEFAULTS,
                   TSDF_ENTRY_DTYPE, TSDF_FUSE_DEFAULTS, TSDF_GRAY_ENTRY_DTYPE, TSDF_MESH_VERTEX_DTYPE, TSDF_NORMAL_COUNTERS, TSDF_NORMAL_DTYPE,
                   TSDF_NORMAL_GRAY_COUNTERS, TSDF_NORMAL_GRAY_DTYPE, MapCounters, MapParams, TsdfAlignGrayParams, TsdfAlignParams,
@@ -500,6 +501,15 @@ class TsdfMap(_TableMap):
         map only; a plain or a gray map.  A property that hands out the call, not a method."""
         return _DistanceFieldCall(self)
 
+    @property
+    def travel_field(self):
+        """viso_tsdf_travel_field (include/viso_hip.h, "TSDF travel field"), called as
+        `tsdf.travel_field(box, goals, clearance=0.0, min_weight=2, unknown_is_site=True)`: a TravelField over box = (lo, hi), for
+        every voxel of it the cost of the cheapest way to a goal for a body that keeps `clearance` metres from the surface, and the
+        paths that follow from it (_TravelFieldCall has the arguments).  Reads the map only; a plain or a gray map.  A property
+        that hands out the call, like distance_field."""
+        return _TravelFieldCall(self)
+
     def surface(self, min_weight=1):
         """viso_tsdf_surface: the sign changes between neighbouring voxels of at least min_weight updates as a TSDF_CROSSING_DTYPE
         array (k, axis, wa, wb, sa, sb), sorted by (key, axis)."""
@@ -666,6 +676,137 @@ class _DistanceFieldCall:
         _call(t.L.viso_tsdf_distance_field, t.h, int(min_weight), C.byref(b), FIELD_UNKNOWN_IS_SITE if unknown_is_site else 0,
               ptr(sq, C.c_uint32), ptr(state, C.c_uint8), sq.size, C.byref(n_sites))
         return DistanceField(sq, state, (lo, hi), t.voxel, n_sites.value)
+
+
+class _TravelFieldCall:
+    """What TsdfMap.travel_field hands out: the call on that map."""
+
+    def __init__(self, tsdf):
+        self.tsdf = tsdf
+
+    def __call__(self, box, goals=None, clearance=0.0, min_weight=2, unknown_is_site=True, clearance_sq=None, goals_m=None):
+        """viso_tsdf_travel_field (include/viso_hip.h, "TSDF travel field"): a TravelField over box = (lo, hi), for every voxel of it
+        the cost in thirds of a voxel of the cheapest way, by <3,4,5> chamfer moves through free cells, to one of the goals.  A
+        cell is free when it is not behind the surface, is no site of the distance field at min_weight, and its nearest site is at
+        least `clearance` metres away (travel_clearance_sq has the rounding; clearance_sq= gives the squared clearance in voxels
+        directly).  unknown_is_site=True, the default here: what was never seen is an obstacle, the conservative field; False: the
+        optimistic one.  goals: voxel indices [n][3] (or one [3]); goals_m= instead: points in metres, each the voxel
+        floor(p / voxel) that holds it.  Goals outside the box or in cells that are not free are skipped.  Reads the map only."""
+        where, t = "TsdfMap.travel_field", self.tsdf
+        b = _box_arg(where, box)
+        lo, hi = np.array(b.lo, np.int64), np.array(b.hi, np.int64)
+        n = hi - lo
+        if (n < 1).any() or (n > 512).any():
+            raise ValueError(f"{where}: the box must have 1 .. 512 voxels on every axis")
+        if (goals is None) == (goals_m is None):
+            raise ValueError(f"{where}: either goals (voxel indices) or goals_m (points in metres)")
+        if goals_m is not None:
+            p = np.atleast_2d(np.asarray(goals_m, np.float64))
+            if p.ndim != 2 or p.shape[1] != 3 or not np.isfinite(p).all():
+                raise ValueError(f"{where}: goals_m must be finite points [n][3]")
+            g = np.floor(p / t.voxel)
+        else:
+            g = np.atleast_2d(np.asarray(goals))
+            if g.ndim != 2 or g.shape[1] != 3 or not np.issubdtype(g.dtype, np.integer):
+                raise ValueError(f"{where}: goals must be voxel indices [n][3]")
+        i32 = np.iinfo(np.int32)
+        if len(g) and (g.min() < i32.min or g.max() > i32.max):
+            raise ValueError(f"{where}: the goals must be int32 voxel indices")
+        g = np.ascontiguousarray(g, dtype=np.int32)
+        if clearance_sq is None:
+            clearance_sq = travel_clearance_sq(clearance, t.voxel)
+        elif clearance != 0.0:
+            raise ValueError(f"{where}: either clearance or clearance_sq")
+        if not 0 <= int(clearance_sq) <= FIELD_NONE:
+            raise ValueError(f"{where}: clearance_sq must be a uint32 value")
+        shape = tuple(int(v) for v in n)
+        cost, sq, state = np.empty(shape, np.uint32), np.empty(shape, np.uint32), np.empty(shape, np.uint8)
+        n_used, n_reached, n_rounds = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        flags = FIELD_UNKNOWN_IS_SITE if unknown_is_site else 0
+        _call(t.L.viso_tsdf_travel_field, t.h, int(min_weight), C.byref(b), flags, int(clearance_sq), ptr(g, C.c_int32), len(g),
+              ptr(cost, C.c_uint32), ptr(sq, C.c_uint32), ptr(state, C.c_uint8), cost.size, C.byref(n_used), C.byref(n_reached),
+              C.byref(n_rounds))
+        site = (state & FIELD_STATE_SURFACE) != 0
+        if unknown_is_site:
+            site |= (state & 3) == 0
+        n_sites = int(site.sum())        # (the sites are the cells the states say: rule 5 of the distance field)
+        return TravelField(cost, DistanceField(sq, state, (lo, hi), t.voxel, n_sites), (lo, hi), t.voxel, clearance_sq,
+                           n_used.value, n_reached.value, n_rounds.value)
+
+
+# the 26 moves of a travel field in the order in which TravelField.path tries them, and what each costs
+TRAVEL_MOVES = np.array([e for e in itertools.product((-1, 0, 1), repeat=3) if e != (0, 0, 0)], np.int64)
+TRAVEL_MOVE_COSTS = 2 + (TRAVEL_MOVES != 0).sum(axis=1)
+
+
+def travel_clearance_sq(clearance, voxel):
+    """clearance_sq of a clearance in metres: the smallest integer n with n voxel^2 >= clearance^2, so that sq >= n says exactly
+    that the nearest site is at least the clearance away.  Both doubles are taken at their exact values and the rest is integer
+    arithmetic: with clearance = p / q and voxel = r / s, n = ceil(p^2 s^2 / (q^2 r^2)).  No rounding of a quotient or a square
+    can let a body through a gap that the two numbers say it does not fit; a clearance a hair above k voxels gives k^2 + 1."""
+    clearance, voxel = float(clearance), float(voxel)
+    if not (np.isfinite(clearance) and clearance >= 0 and np.isfinite(voxel) and voxel > 0):
+        raise ValueError("travel_clearance_sq: the clearance must be finite and >= 0, the voxel finite and > 0")
+    (p, q), (r, s) = clearance.as_integer_ratio(), voxel.as_integer_ratio()
+    num, den = p * p * s * s, q * q * r * r
+    n = -(-num // den)        # the ceiling of num / den
+    if n >= FIELD_NONE:
+        raise ValueError("travel_clearance_sq: the clearance is beyond every box (clearance_sq must stay below FIELD_NONE)")
+    return n
+
+
+class TravelField:
+    """TsdfMap.travel_field: the travel field of a TSDF map over a box of voxels (include/viso_hip.h, "TSDF travel field").  cost:
+    uint32 (n0, n1, n2), the cost of the cheapest sequence of moves from cell i (the voxel box[0] + i) to a used goal in thirds of
+    a voxel, FIELD_NONE where the cell is not free or no goal is reached; field: the DistanceField of the same call; box = (lo, hi)
+    as int32 [3] arrays; voxel in metres; clearance_sq; n_goals_used, n_reached, rounds."""
+
+    def __init__(self, cost, field, box, voxel, clearance_sq, n_goals_used, n_reached, rounds):
+        self.cost, self.field, self.voxel, self.clearance_sq = cost, field, float(voxel), int(clearance_sq)
+        self.n_goals_used, self.n_reached, self.rounds = int(n_goals_used), int(n_reached), int(rounds)
+        self.box = (np.array(box[0], np.int32), np.array(box[1], np.int32))
+
+    def metres(self):
+        """float32 (n0, n1, n2): cost / 3 * voxel computed in double, inf where the cost is FIELD_NONE.  Between 0.943 and 1.106
+        times the Euclidean length where nothing is in the way."""
+        d = self.cost.astype(np.float64) / 3.0 * self.voxel
+        return np.where(self.cost == FIELD_NONE, np.inf, d).astype(np.float32)
+
+    def at(self, points):
+        """(cost, outside) of float [n][3] points in metres: the cost of the cell floor(p / voxel) - lo that holds each point
+        (uint32 [n], FIELD_NONE for a point outside the box), and the bool [n] mask of the points outside the box (not finite
+        ones included): DistanceField.at for the costs."""
+        return DistanceField(self.cost, None, self.box, self.voxel, 0).at(points)
+
+    def path(self, start):
+        """The way from the voxel `start` (absolute indices [3]) to a goal, as the int32 [m][3] array of the voxels it visits, start
+        and goal included; None when start is outside the box or has no finite cost.  From a cell c the path steps to the first
+        neighbour n inside the box with cost[n] + w == cost[c], w the move's 3, 4 or 5, first in the order of
+        itertools.product((-1, 0, 1), repeat=3) without (0, 0, 0), until the cost is 0.  Runs on the host."""
+        k = np.asarray(start)
+        if k.shape != (3,) or not np.issubdtype(k.dtype, np.integer):
+            raise ValueError("TravelField.path: start must be three voxel indices")
+        lo, shape = self.box[0].astype(np.int64), np.asarray(self.cost.shape, np.int64)
+        c = k.astype(np.int64) - lo
+        if ((c < 0) | (c >= shape)).any() or self.cost[tuple(c)] == FIELD_NONE:
+            return None
+        cells = [c]
+        while self.cost[tuple(c)] != 0:
+            here = int(self.cost[tuple(c)])
+            n = c + TRAVEL_MOVES
+            inside = ((n >= 0) & (n < shape)).all(axis=1)
+            there = np.where(inside, self.cost[tuple(np.where(inside[:, None], n, 0).T)].astype(np.int64), -1)
+            down = np.flatnonzero(inside & (there != FIELD_NONE) & (there + TRAVEL_MOVE_COSTS == here))
+            if not len(down):
+                raise ValueError("TravelField.path: the costs are not those of a travel field (no neighbour leads on)")
+            c = n[down[0]]
+            cells.append(c)
+        return (np.array(cells, np.int64) + lo).astype(np.int32)
+
+    def path_metres(self, start):
+        """path(start) as float64 [m][3] points in metres, the centres (k + 0.5) voxel of its voxels; None where path gives None."""
+        p = self.path(start)
+        return None if p is None else (p.astype(np.float64) + 0.5) * self.voxel
 
 
 class TsdfNormals:

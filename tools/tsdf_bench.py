@@ -3,7 +3,7 @@
 
   python tools/tsdf_bench.py [--frames N] [--reps N] [--capacity-log2 N] [--render-views N] [--kernel-only] [--out FILE]
                              [--carve C [--carve-near M]] [--depth-weights S] [--options-capacity-log2 N] [--fuse-only]
-                             [--distance-field]
+                             [--distance-field] [--travel-field]
 
 The pairs and poses are those of tools/map_bench.py: 17 seeded synthetic frames repeated, frame t seen from a camera that has moved
 0.8 t m forward and turned 0.002 t rad.  Legs (host clock around work that ends in a synchronise, medians of alternating
@@ -47,6 +47,14 @@ repetitions):
                frame, min_weight 2, with and without unknown_is_site: the four launches, the copy of sq and state to the host (5
                bytes a cell) and the free.  Where scipy imports, scipy.ndimage.distance_transform_edt of the same site grid on the
                host beside it, as context.
+  travel_field  (with --travel-field, which runs only this section; include/viso_hip.h, "TSDF travel field")
+               TsdfMap.travel_field over the same two boxes, the goal the middle frame's camera voxel, min_weight 2, at a clearance
+               of 0 and of 3 voxels (clearance_sq 0 and 9), with and without unknown_is_site: the distance field's launches, the
+               starting costs, the rounds of the relaxation, the copy of cost, sq and state to the host (9 bytes a cell) and the
+               free; with each the rounds, n_goals_used and n_reached, and TsdfMap.distance_field of the same box and flag beside
+               it in the same loop: the part of the time that the travel field did not add.  Where the camera's own voxel is not
+               free in a case (a site, behind the surface, nearer to a site than the clearance), the goal is the free cell nearest
+               to it; the result names the goal used.
 n_updates / n_points from viso_tsdf_stats is the number of voxels a pixel's band touches.  --kernel-only runs clear + fuse_tsdf
 --reps times, the extractions and the render once and the two align calls --reps times: the run to put under `rocprofv3 --kernel-trace --stats` for the kernels' own times.  The
 count the result is held against (not a measurement) is printed with it."""
@@ -87,6 +95,7 @@ def main():
     ap.add_argument("--options-capacity-log2", type=int, default=None)
     ap.add_argument("--fuse-only", action="store_true")
     ap.add_argument("--distance-field", action="store_true")
+    ap.add_argument("--travel-field", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     nf = a.frames
@@ -168,6 +177,47 @@ def main():
             os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
             with open(a.out, "w") as f:
                 json.dump(res, f, indent=1)
+        tsdf.close(); b.close(); ctx.close()
+        return
+
+    if a.travel_field:
+        mid = np.floor(poses[nf // 2][:3, 3] / tsdf.voxel).astype(np.int64)
+        res = {"frames": nf, "capacity_log2": log2, "reps": a.reps, "min_weight": 2, "goal": [int(v) for v in mid], "boxes": {}}
+        for shape in ((256, 256, 64), (512, 512, 64)):
+            half = np.array(shape) // 2
+            box = (mid - half, mid - half + np.array(shape))
+            r = {"box": [[int(v) for v in box[0]], [int(v) for v in box[1]]], "cases": {}}
+            for unknown in (False, True):
+                for clearance_sq in (0, 9):
+                    goal = mid
+                    call = lambda: tsdf.travel_field(box, [goal], clearance_sq=clearance_sq, min_weight=2, unknown_is_site=unknown)  # noqa: E731
+                    first = call()
+                    if not first.n_goals_used:   # the camera's own voxel is not free (a site, behind the surface, too near): the free cell nearest to it
+                        sq, st = first.field.sq, first.field.state
+                        site = ((st & 4) != 0) | ((st & 3) == 0 if unknown else False)
+                        cells = np.argwhere(((st & 3) != 2) & ~site & (sq >= clearance_sq))
+                        if len(cells):
+                            goal = cells[((cells - (mid - box[0])) ** 2).sum(axis=1).argmin()] + box[0]
+                    legs = {"travel_field": [], "distance_field": []}
+                    for rep_ in range(a.reps + 1):   # alternating; the first round is the warm-up
+                        ms = clock(call), clock(lambda: tsdf.distance_field(box, min_weight=2, unknown_is_site=unknown))
+                        if rep_:
+                            legs["travel_field"].append(ms[0])
+                            legs["distance_field"].append(ms[1])
+                    f = call()
+                    r["cases"][f"{'unknown_is_site' if unknown else 'surface'}, clearance_sq {clearance_sq}"] = {
+                        "goal": [int(v) for v in goal], "rounds": f.rounds, "n_goals_used": f.n_goals_used, "n_reached": f.n_reached,
+                        "cost_max": int(f.cost[f.cost != 0xffffffff].max()) if f.n_reached else None,
+                        "ms_median": {k: float(np.median(v)) for k, v in legs.items()}, "ms_min": {k: float(np.min(v)) for k, v in legs.items()},
+                        "ms_max": {k: float(np.max(v)) for k, v in legs.items()}}
+            res["boxes"]["x".join(str(v) for v in shape)] = r
+        print(json.dumps(res))
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                json.dump(res, f, indent=1)
+        if omap is not None:
+            omap.close()
         tsdf.close(); b.close(); ctx.close()
         return
 
