@@ -780,10 +780,8 @@ extern "C" int viso_tsdf_set_fuse_options(viso_tsdf* t, int32_t carve_voxels, in
                        "a finite carve_near >= 0)", where);
         return VISO_ERR_ARG;
     }
-    int r;
-    VoxelHost* h;
-    if ((r = voxel_enter(where, g_tsdfs, t, &h)) < 0) return r;
-    std::lock_guard<std::mutex> lk(h->mu);
+    VoxelSession ses(where, g_tsdfs, t, VoxelSession::ANY_STATE);
+    VISO_TRY(ses.status());
     t->o = TsdfFuseOpts{carve_voxels, weight_shift, weight_max, 0, carve_near};
     return VISO_OK;
 }
@@ -792,10 +790,8 @@ extern "C" int viso_tsdf_get_fuse_options(viso_tsdf* t, int32_t* carve_voxels, i
     const char* where = "viso_tsdf_get_fuse_options";
     if (!voxel_known(g_tsdfs, t)) { viso_set_error("%s: not a live TSDF handle", where); return VISO_ERR_ARG; }
     if (!carve_voxels || !weight_shift || !weight_max || !carve_near) { viso_set_error("%s: bad argument (non-null outputs)", where); return VISO_ERR_ARG; }
-    int r;
-    VoxelHost* h;
-    if ((r = voxel_enter(where, g_tsdfs, t, &h)) < 0) return r;
-    std::lock_guard<std::mutex> lk(h->mu);
+    VoxelSession ses(where, g_tsdfs, t, VoxelSession::ANY_STATE);
+    VISO_TRY(ses.status());
     *carve_voxels = t->o.carve; *weight_shift = t->o.weight_shift; *weight_max = t->o.weight_max; *carve_near = t->o.carve_near;
     return VISO_OK;
 }
@@ -977,16 +973,10 @@ extern "C" int viso_tsdf_surface(viso_tsdf* t, uint32_t min_weight, viso_tsdf_cr
 // One pass of the mesh extraction: the numbers of vertex records and of triangles, both lists written when `verts` is set
 static int tsdf_mesh_pass(viso_tsdf* t, uint32_t min_weight, viso_tsdf_mesh_vertex* verts, size_t v_cap, TsdfTriRef* tris, size_t t_cap,
                           unsigned long long* nv, unsigned long long* nt) {
-    hipStream_t s = t->h.ctx->stream;
-    HIP_TRY(hipMemsetAsync(t->t.head.words + VOXEL_W_OUT, 0, sizeof(unsigned long long), s));
-    HIP_TRY(hipMemsetAsync(t->t.head.words + VOXEL_W_TRIS, 0, sizeof(unsigned long long), s));
-    hipLaunchKernelGGL(tsdf_mesh_kernel, tsdf_slot_grid(t), dim3(256), 0, s, t->t, min_weight, t->s, verts,
-                       (unsigned long long)v_cap, tris, (unsigned long long)t_cap);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(nv, t->t.head.words + VOXEL_W_OUT, sizeof(*nv), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(nt, t->t.head.words + VOXEL_W_TRIS, sizeof(*nt), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return VISO_OK;
+    return voxel_pass(&t->h, [&](hipStream_t s) {
+        hipLaunchKernelGGL(tsdf_mesh_kernel, tsdf_slot_grid(t), dim3(256), 0, s, t->t, min_weight, t->s, verts,
+                           (unsigned long long)v_cap, tris, (unsigned long long)t_cap);
+    }, nv, nt);
 }
 
 static inline bool vertex_less(const viso_tsdf_mesh_vertex& x, const viso_tsdf_mesh_vertex& y) {
@@ -994,35 +984,27 @@ static inline bool vertex_less(const viso_tsdf_mesh_vertex& x, const viso_tsdf_m
     return a != b ? a < b : x.dir < y.dir;
 }
 
-// The map is entered and locked.  Both lists from the device, sorted; the vertices no triangle refers to dropped; the references
-// turned into indices.
-static int tsdf_mesh_lists(const char* where, viso_tsdf* t, uint32_t min_weight, std::vector<viso_tsdf_mesh_vertex>& verts,
+// Under the session of t.  Both lists from the device, sorted; the vertices no triangle refers to dropped; the references turned
+// into indices.
+static int tsdf_mesh_lists(const VoxelSession& ses, viso_tsdf* t, uint32_t min_weight, std::vector<viso_tsdf_mesh_vertex>& verts,
                            std::vector<viso_tsdf_triangle>& tris) {
+    const char* where = ses.where();
     verts.clear(); tris.clear();
     unsigned long long nv = 0, nt = 0;
-    int r;
-    if ((r = tsdf_mesh_pass(t, min_weight, nullptr, 0, nullptr, 0, &nv, &nt)) < 0) return r;
+    VISO_TRY(tsdf_mesh_pass(t, min_weight, nullptr, 0, nullptr, 0, &nv, &nt));
     if (!nt) return VISO_OK;   // no triangle: no vertex is referred to
     std::vector<viso_tsdf_mesh_vertex> all((size_t)nv);
     std::vector<TsdfTriRef> refs((size_t)nt);
-    viso_tsdf_mesh_vertex* dv = nullptr;
-    TsdfTriRef* dt = nullptr;
     const size_t bv = (size_t)nv * sizeof(viso_tsdf_mesh_vertex), bt = (size_t)nt * sizeof(TsdfTriRef);
-    if (hipMalloc((void**)&dv, bv) != hipSuccess || hipMalloc((void**)&dt, bt) != hipSuccess) {
-        (void)hipGetLastError();
-        if (dv) (void)hipFree(dv);
-        viso_set_error("%s: cannot allocate %zu bytes for the lists", where, bv + bt);
-        return VISO_ERR_NOMEM;
-    }
+    VoxelScratch d(ses, bt + bv, "the lists");   // the references | the vertices: the 64-bit word of a reference comes first
+    VISO_TRY(d.status());
+    TsdfTriRef* dt = d.as<TsdfTriRef>();
+    viso_tsdf_mesh_vertex* dv = d.as<viso_tsdf_mesh_vertex>(bt);
     unsigned long long nv2 = 0, nt2 = 0;
-    r = tsdf_mesh_pass(t, min_weight, dv, (size_t)nv, dt, (size_t)nt, &nv2, &nt2);
-    hipError_t e = hipSuccess;
-    if (r >= 0) e = hipMemcpy(all.data(), dv, bv, hipMemcpyDeviceToHost);
-    if (r >= 0 && e == hipSuccess) e = hipMemcpy(refs.data(), dt, bt, hipMemcpyDeviceToHost);
-    (void)hipFree(dv);
-    (void)hipFree(dt);
-    if (r < 0) return r;
-    HIP_TRY(e);
+    VISO_TRY(tsdf_mesh_pass(t, min_weight, dv, (size_t)nv, dt, (size_t)nt, &nv2, &nt2));
+    HIP_TRY(hipMemcpy(all.data(), dv, bv, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(refs.data(), dt, bt, hipMemcpyDeviceToHost));
+    VISO_TRY(d.release());   // (the host's part below is the long one)
     if (nv2 != nv || nt2 != nt) { viso_set_error("%s: the table changed between the two passes", where); return VISO_ERR_HIP; }   // (the map's lock rules it out)
     std::sort(all.begin(), all.end(), vertex_less);
     std::sort(refs.begin(), refs.end(), [](const TsdfTriRef& x, const TsdfTriRef& y) { return x.cell != y.cell ? x.cell < y.cell : (x.code & 15u) < (y.code & 15u); });
@@ -1067,15 +1049,12 @@ static int tsdf_mesh_extract(const char* where, viso_tsdf* t, uint32_t min_weigh
         viso_set_error("%s: bad argument (min_weight >= 1, non-null outputs)", where);
         return VISO_ERR_ARG;
     }
-    int r;
-    VoxelHost* h;
-    if ((r = voxel_enter(where, g_tsdfs, t, &h)) < 0) return r;
     std::vector<viso_tsdf_mesh_vertex> verts;
     std::vector<viso_tsdf_triangle> tris;
-    {
-        std::lock_guard<std::mutex> lk(h->mu);
-        if (h->overflowed) return voxel_refuse_overflowed(where, h);
-        if ((r = tsdf_mesh_lists(where, t, min_weight, verts, tris)) < 0) return r;
+    {   // the map's lock is not held over the copies to the caller's arrays
+        VoxelSession ses(where, g_tsdfs, t);
+        VISO_TRY(ses.status());
+        VISO_TRY(tsdf_mesh_lists(ses, t, min_weight, verts, tris));
     }
     *v.n = verts.size();
     *tr.n = tris.size();
@@ -1188,40 +1167,38 @@ static bool tsdf_vertices_ok(const char* where, const viso_tsdf_mesh_vertex* ver
     return true;
 }
 
+// viso_tsdf_vertex_gray and viso_tsdf_vertex_normals behind their own checks: the n vertices to the device, one pass of `launch`
+// (a thread a vertex) with out_bytes a vertex of output behind them, the output and the number of vertices without one back.
+// (A vertex is a multiple of four bytes, so an output of floats behind the vertices stays aligned.)
+using TsdfSampleLaunch = std::function<void(const viso_tsdf_mesh_vertex* d_verts, void* d_out, dim3 grid, hipStream_t)>;
+static int tsdf_sample_vertices(const char* where, viso_tsdf* t, const viso_tsdf_mesh_vertex* vertices, size_t n, size_t out_bytes, void* out,
+                                size_t* n_missing_or_null, const TsdfSampleLaunch& launch) {
+    VoxelSession ses(where, g_tsdfs, t);
+    VISO_TRY(ses.status());
+    if (n_missing_or_null) *n_missing_or_null = 0;
+    if (!n) return VISO_OK;
+    const size_t b_verts = n * sizeof(viso_tsdf_mesh_vertex), b_out = n * out_bytes;
+    VoxelScratch d(ses, b_verts + b_out, "the vertices");
+    VISO_TRY(d.status());
+    HIP_TRY(hipMemcpy(d.as<char>(), vertices, b_verts, hipMemcpyHostToDevice));
+    unsigned long long missing = 0;
+    VISO_TRY(voxel_pass(ses.host(), [&](hipStream_t s) {
+        launch(d.as<viso_tsdf_mesh_vertex>(), d.as<char>(b_verts), dim3((unsigned)((n + 255) / 256)), s);
+    }, &missing));
+    HIP_TRY(hipMemcpy(out, d.as<char>(b_verts), b_out, hipMemcpyDeviceToHost));
+    if (n_missing_or_null) *n_missing_or_null = (size_t)missing;
+    return VISO_OK;
+}
+
 extern "C" int viso_tsdf_vertex_gray(viso_tsdf* t, const viso_tsdf_mesh_vertex* vertices, size_t n, uint8_t* gray_out, size_t* n_missing_or_null) {
     const char* where = "viso_tsdf_vertex_gray";
     if (!tsdf_kind_ok(where, t, true)) return VISO_ERR_ARG;
     if (n && (!vertices || !gray_out)) { viso_set_error("%s: bad argument (non-null vertices and output)", where); return VISO_ERR_ARG; }
     if (!tsdf_vertices_ok(where, vertices, n)) return VISO_ERR_ARG;
-    int r;
-    VoxelHost* h;
-    if ((r = voxel_enter(where, g_tsdfs, t, &h)) < 0) return r;
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (h->overflowed) return voxel_refuse_overflowed(where, h);
-    if (n_missing_or_null) *n_missing_or_null = 0;
-    if (!n) return VISO_OK;
-    const size_t b_verts = n * sizeof(viso_tsdf_mesh_vertex);
-    char* d = nullptr;
-    if (hipMalloc((void**)&d, b_verts + n) != hipSuccess) {
-        (void)hipGetLastError();
-        viso_set_error("%s: cannot allocate %zu bytes for the vertices", where, b_verts + n);
-        return VISO_ERR_NOMEM;
-    }
-    const viso_tsdf_mesh_vertex* d_verts = reinterpret_cast<const viso_tsdf_mesh_vertex*>(d);
-    uint8_t* d_out = reinterpret_cast<uint8_t*>(d + b_verts);
-    hipError_t e = hipMemcpy(d, vertices, b_verts, hipMemcpyHostToDevice);
-    unsigned long long missing = 0;
-    if (e == hipSuccess) {
-        r = voxel_pass(h, [&](hipStream_t s) {
-            hipLaunchKernelGGL(tsdf_gray_sample_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, t->g(), d_verts, (unsigned long long)n, d_out);
-        }, &missing);
-        if (r >= 0) e = hipMemcpy(gray_out, d_out, n, hipMemcpyDeviceToHost);
-    }
-    (void)hipFree(d);   // on every path
-    if (r < 0) return r;
-    HIP_TRY(e);
-    if (n_missing_or_null) *n_missing_or_null = (size_t)missing;
-    return VISO_OK;
+    return tsdf_sample_vertices(where, t, vertices, n, 1, gray_out, n_missing_or_null,
+                                [=](const viso_tsdf_mesh_vertex* d_verts, void* d_out, dim3 grid, hipStream_t s) {
+        hipLaunchKernelGGL(tsdf_gray_sample_kernel, grid, dim3(256), 0, s, t->g(), d_verts, (unsigned long long)n, static_cast<uint8_t*>(d_out));
+    });
 }
 
 extern "C" int viso_tsdf_vertex_normals(viso_tsdf* t, uint32_t min_weight, const viso_tsdf_mesh_vertex* vertices, size_t n, float* normals_out,
@@ -1238,37 +1215,10 @@ extern "C" int viso_tsdf_vertex_normals(viso_tsdf* t, uint32_t min_weight, const
     }
     if (!tsdf_vertices_ok(where, vertices, n)) return VISO_ERR_ARG;
     if (!voxel_known(g_tsdfs, t)) { viso_set_error("%s: not a live TSDF handle", where); return VISO_ERR_ARG; }
-    int r;
-    VoxelHost* h;
-    if ((r = voxel_enter(where, g_tsdfs, t, &h)) < 0) return r;
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (h->overflowed) return voxel_refuse_overflowed(where, h);
-    if (n_missing_or_null) *n_missing_or_null = 0;
-    if (!n) return VISO_OK;
-    const size_t b_verts = n * sizeof(viso_tsdf_mesh_vertex), b_out = n * 3 * sizeof(float);   // 28 bytes a vertex: the floats stay aligned
-    char* d = nullptr;
-    if (hipMalloc((void**)&d, b_verts + b_out) != hipSuccess) {
-        (void)hipGetLastError();
-        viso_set_error("%s: cannot allocate %zu bytes for the vertices", where, b_verts + b_out);
-        return VISO_ERR_NOMEM;
-    }
-    const viso_tsdf_mesh_vertex* d_verts = reinterpret_cast<const viso_tsdf_mesh_vertex*>(d);
-    float* d_out = reinterpret_cast<float*>(d + b_verts);
-    hipError_t e = hipMemcpy(d, vertices, b_verts, hipMemcpyHostToDevice);
-    unsigned long long missing = 0;
-    if (e == hipSuccess) {
-        const TsdfTable table = t->t;
-        r = voxel_pass(h, [&](hipStream_t s) {
-            hipLaunchKernelGGL(tsdf_normal_sample_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, table, min_weight, d_verts,
-                               (unsigned long long)n, d_out);
-        }, &missing);
-        if (r >= 0) e = hipMemcpy(normals_out, d_out, b_out, hipMemcpyDeviceToHost);
-    }
-    (void)hipFree(d);   // on every path
-    if (r < 0) return r;
-    HIP_TRY(e);
-    if (n_missing_or_null) *n_missing_or_null = (size_t)missing;
-    return VISO_OK;
+    return tsdf_sample_vertices(where, t, vertices, n, 3 * sizeof(float), normals_out, n_missing_or_null,
+                                [=](const viso_tsdf_mesh_vertex* d_verts, void* d_out, dim3 grid, hipStream_t s) {
+        hipLaunchKernelGGL(tsdf_normal_sample_kernel, grid, dim3(256), 0, s, t->t, min_weight, d_verts, (unsigned long long)n, static_cast<float*>(d_out));
+    });
 }
 
 extern "C" int viso_tsdf_stats(viso_tsdf* t, viso_tsdf_counters* out) {

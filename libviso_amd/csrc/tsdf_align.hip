@@ -336,9 +336,9 @@ static int align_device(const char* where, viso_tsdf* t, const AlignRequest<K>& 
         viso_set_error("%s: the TSDF map carries no intensity (viso_tsdf_create_gray makes one that does)", where);
         return VISO_ERR_ARG;
     }
-    int r;
-    VoxelHost* h;
-    if ((r = voxel_enter(where, reg, t, &h)) < 0) return r;
+    VoxelSession ses(where, reg, t, VoxelSession::ANY_STATE);   // the overflow refusal comes behind the two checks that need the map
+    VISO_TRY(ses.status());
+    VoxelHost* h = ses.host();
     if (v.ctx && h->ctx != v.ctx) { viso_set_error("%s: the TSDF map and the batch must share a context", where); return VISO_ERR_ARG; }
     TsdfView view;
     tsdf_view(t, &view);
@@ -346,14 +346,13 @@ static int align_device(const char* where, viso_tsdf* t, const AlignRequest<K>& 
         viso_set_error("%s: bad argument (gate_voxels %g is beyond the map's truncation of %d voxels)", where, p.gate_voxels, view.trunc_voxels);
         return VISO_ERR_ARG;
     }
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (h->overflowed) return voxel_refuse_overflowed(where, h);
+    VISO_TRY(ses.refuse_overflowed());
     const size_t px = v.px();
     const int16_t* disp = v.disp;
     const uint8_t* image = v.image;
     if (!v.ctx) {
-        if ((r = voxel_stage_map(where, h, v.disp, px, &disp)) < 0) return r;
-        if (v.image && (r = voxel_stage_image(where, h, v.image, px, &image)) < 0) return r;
+        VISO_TRY(voxel_stage_map(where, h, v.disp, px, &disp));
+        if (v.image) VISO_TRY(voxel_stage_image(where, h, v.image, px, &image));
     }
     TsdfAlignArgs a;
     a.v.mfs = v.mfs; a.v.rows = v.rows; a.v.cols = v.cols; a.v.min_disp16 = h->min_disp16; a.v._pad = 0;

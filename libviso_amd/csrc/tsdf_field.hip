@@ -142,36 +142,20 @@ extern "C" int viso_tsdf_distance_field(viso_tsdf* t, uint32_t min_weight, const
     }
     VoxelRegistry& reg = tsdf_registry();
     if (!voxel_known(reg, t)) { viso_set_error("%s: not a live TSDF handle", where); return VISO_ERR_ARG; }
-    int r;
-    VoxelHost* h;
-    if ((r = voxel_enter(where, reg, t, &h)) < 0) return r;
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (h->overflowed) return voxel_refuse_overflowed(where, h);
+    VoxelSession ses(where, reg, t);
+    VISO_TRY(ses.status());
     TsdfView v;
     tsdf_view(t, &v);
-    const size_t bytes = cells * (2 * sizeof(uint32_t) + 1);
-    char* d = nullptr;   // g | g' | state
-    if (hipMalloc((void**)&d, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        viso_set_error("%s: cannot allocate %zu bytes for the field", where, bytes);
-        return VISO_ERR_NOMEM;
-    }
-    uint32_t* ga = reinterpret_cast<uint32_t*>(d);
+    VoxelScratch d(ses, cells * (2 * sizeof(uint32_t) + 1), "the field");   // g | g' | state
+    VISO_TRY(d.status());
+    uint32_t* ga = d.as<uint32_t>();
     uint32_t* gb = ga + cells;
     uint8_t* d_state = reinterpret_cast<uint8_t*>(gb + cells);
     unsigned long long n_sites = 0;
-    r = field_passes(h, v.t, min_weight, b, flags & VISO_FIELD_UNKNOWN_IS_SITE, gb, ga, d_state, &n_sites);
-    hipError_t e = hipSuccess;
-    if (r >= 0) {
-        hipStream_t s = h->ctx->stream;
-        e = hipMemcpyAsync(sq_out, gb, cells * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess && state_out_or_null) e = hipMemcpyAsync(state_out_or_null, d_state, cells, hipMemcpyDeviceToHost, s);
-    }
-    const hipError_t e_wait = hipStreamSynchronize(h->ctx->stream);   // nothing in flight touches the block that is freed next
-    (void)hipFree(d);   // on every path
-    if (r < 0) return r;
-    HIP_TRY(e);
-    HIP_TRY(e_wait);
+    VISO_TRY(field_passes(ses.host(), v.t, min_weight, b, flags & VISO_FIELD_UNKNOWN_IS_SITE, gb, ga, d_state, &n_sites));
+    HIP_TRY(hipMemcpyAsync(sq_out, gb, cells * sizeof(uint32_t), hipMemcpyDeviceToHost, ses.stream()));
+    if (state_out_or_null) HIP_TRY(hipMemcpyAsync(state_out_or_null, d_state, cells, hipMemcpyDeviceToHost, ses.stream()));
+    VISO_TRY(d.release());
     if (n_sites_or_null) *n_sites_or_null = (size_t)n_sites;
     return VISO_OK;
 }

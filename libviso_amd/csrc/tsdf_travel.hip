@@ -219,11 +219,8 @@ extern "C" int viso_tsdf_travel_field(viso_tsdf* t, uint32_t min_weight, const v
     }
     VoxelRegistry& reg = tsdf_registry();
     if (!voxel_known(reg, t)) { viso_set_error("%s: not a live TSDF handle", where); return VISO_ERR_ARG; }
-    int r;
-    VoxelHost* h;
-    if ((r = voxel_enter(where, reg, t, &h)) < 0) return r;
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (h->overflowed) return voxel_refuse_overflowed(where, h);
+    VoxelSession ses(where, reg, t);
+    VISO_TRY(ses.status());
     TsdfView v;
     tsdf_view(t, &v);
     TravelTiles tt;
@@ -231,13 +228,10 @@ extern "C" int viso_tsdf_travel_field(viso_tsdf* t, uint32_t min_weight, const v
     tt.tiles = tt.nt[0] * tt.nt[1] * tt.nt[2];
     const size_t state_words = (cells + 3) / 4;
     const size_t words = 2 * cells + state_words + 3 * (size_t)tt.tiles + TRAVEL_WORDS + 3 * n_goals;
-    uint32_t* d = nullptr;   // sq | cost | state | queued | the call's words | two lists | goals
-    if (hipMalloc((void**)&d, words * sizeof(uint32_t)) != hipSuccess) {
-        (void)hipGetLastError();
-        viso_set_error("%s: cannot allocate %zu bytes for the field", where, words * sizeof(uint32_t));
-        return VISO_ERR_NOMEM;
-    }
-    uint32_t* d_sq = d;
+    uint32_t ctl[TRAVEL_WORDS] = {0};   // (before the block: copies on the stream write it)
+    VoxelScratch d(ses, words * sizeof(uint32_t), "the field");   // sq | cost | state | queued | the call's words | two lists | goals
+    VISO_TRY(d.status());
+    uint32_t* d_sq = d.as<uint32_t>();
     uint32_t* d_cost = d_sq + cells;
     uint8_t* d_state = reinterpret_cast<uint8_t*>(d_cost + cells);
     uint32_t* d_queued = d_cost + cells + state_words;
@@ -245,55 +239,43 @@ extern "C" int viso_tsdf_travel_field(viso_tsdf* t, uint32_t min_weight, const v
     uint32_t* d_list[2] = {d_ctl + TRAVEL_WORDS, d_ctl + TRAVEL_WORDS + tt.tiles};
     int32_t* d_goals = reinterpret_cast<int32_t*>(d_list[1] + tt.tiles);
     const uint32_t unknown = flags & VISO_FIELD_UNKNOWN_IS_SITE;
-    hipStream_t s = h->ctx->stream;
+    hipStream_t s = ses.stream();
     unsigned long long n_sites = 0;
-    uint32_t ctl[TRAVEL_WORDS] = {0};
-    bool endless = false;
     // the distance field; the passes' second buffer then becomes the costs
-    r = field_passes(h, v.t, min_weight, b, unknown, d_sq, d_cost, d_state, &n_sites);
-    hipError_t e = hipSuccess;
-    if (r >= 0) e = hipMemcpyAsync(d_goals, goals, 3 * n_goals * sizeof(int32_t), hipMemcpyHostToDevice, s);
-    if (r >= 0 && e == hipSuccess) e = hipMemsetAsync(d_queued, 0, ((size_t)tt.tiles + TRAVEL_WORDS) * sizeof(uint32_t), s);
-    if (r >= 0 && e == hipSuccess) {
-        const unsigned cell_blocks = (unsigned)((cells + 255) / 256);
-        const dim3 cell_grid(cell_blocks < TRAVEL_BLOCKS ? cell_blocks : TRAVEL_BLOCKS);
-        const dim3 tile_grid(tt.tiles < TRAVEL_BLOCKS ? tt.tiles : TRAVEL_BLOCKS);
-        hipLaunchKernelGGL(tsdf_travel_init_kernel, cell_grid, dim3(256), 0, s, d_sq, d_state, b.cells, unknown, clearance_sq, d_cost);
-        hipLaunchKernelGGL(tsdf_travel_goals_kernel, dim3((unsigned)((n_goals + 255) / 256)), dim3(256), 0, s, d_goals, (uint32_t)n_goals, b, tt,
-                           d_cost, d_queued, d_list[1], d_ctl);
-        e = hipGetLastError();
-        // One launch a round, the list of round r in d_list[r & 1]; the host looks at the next list's length every TRAVEL_CHECK_EVERY
-        // rounds.  At most cells + 1 rounds: more is an error, never a reason to go on.
-        const size_t max_rounds = cells + 1;
-        size_t round = 1;
-        while (e == hipSuccess) {
-            for (int k = 0; k < TRAVEL_CHECK_EVERY && round <= max_rounds; ++k, ++round)
-                hipLaunchKernelGGL(tsdf_travel_relax_kernel, tile_grid, dim3(512), 0, s, b, tt, d_cost, d_queued, d_list[round & 1],
-                                   d_list[(round + 1) & 1], d_ctl, (uint32_t)round);
-            if ((e = hipGetLastError()) != hipSuccess) break;
-            if ((e = hipMemcpyAsync(ctl, d_ctl, sizeof(ctl), hipMemcpyDeviceToHost, s)) != hipSuccess) break;
-            if ((e = hipStreamSynchronize(s)) != hipSuccess) break;
-            if (!ctl[TRAVEL_W_COUNT + round % 3]) break;   // nothing is listed for the next round
-            if (round > max_rounds) { endless = true; break; }
+    VISO_TRY(field_passes(ses.host(), v.t, min_weight, b, unknown, d_sq, d_cost, d_state, &n_sites));
+    HIP_TRY(hipMemcpyAsync(d_goals, goals, 3 * n_goals * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(d_queued, 0, ((size_t)tt.tiles + TRAVEL_WORDS) * sizeof(uint32_t), s));
+    const unsigned cell_blocks = (unsigned)((cells + 255) / 256);
+    const dim3 cell_grid(cell_blocks < TRAVEL_BLOCKS ? cell_blocks : TRAVEL_BLOCKS);
+    const dim3 tile_grid(tt.tiles < TRAVEL_BLOCKS ? tt.tiles : TRAVEL_BLOCKS);
+    hipLaunchKernelGGL(tsdf_travel_init_kernel, cell_grid, dim3(256), 0, s, d_sq, d_state, b.cells, unknown, clearance_sq, d_cost);
+    hipLaunchKernelGGL(tsdf_travel_goals_kernel, dim3((unsigned)((n_goals + 255) / 256)), dim3(256), 0, s, d_goals, (uint32_t)n_goals, b, tt,
+                       d_cost, d_queued, d_list[1], d_ctl);
+    HIP_TRY(hipGetLastError());
+    // One launch a round, the list of round r in d_list[r & 1]; the host looks at the next list's length every TRAVEL_CHECK_EVERY
+    // rounds.  At most cells + 1 rounds: more is an error, never a reason to go on.
+    const size_t max_rounds = cells + 1;
+    for (size_t round = 1;;) {
+        for (int k = 0; k < TRAVEL_CHECK_EVERY && round <= max_rounds; ++k, ++round)
+            hipLaunchKernelGGL(tsdf_travel_relax_kernel, tile_grid, dim3(512), 0, s, b, tt, d_cost, d_queued, d_list[round & 1],
+                               d_list[(round + 1) & 1], d_ctl, (uint32_t)round);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(ctl, d_ctl, sizeof(ctl), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (!ctl[TRAVEL_W_COUNT + round % 3]) break;   // nothing is listed for the next round
+        if (round > max_rounds) {
+            VISO_TRY(d.release());
+            viso_set_error("%s: the relaxation has not come to rest after %zu rounds, more than the box has cells", where, max_rounds);
+            return VISO_ERR_HIP;
         }
-        if (e == hipSuccess && !endless) {
-            hipLaunchKernelGGL(tsdf_travel_finish_kernel, cell_grid, dim3(256), 0, s, d_cost, b.cells, d_ctl);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess && !endless) e = hipMemcpyAsync(ctl, d_ctl, sizeof(ctl), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess && !endless) e = hipMemcpyAsync(cost_out, d_cost, cells * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess && !endless && sq_out_or_null) e = hipMemcpyAsync(sq_out_or_null, d_sq, cells * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess && !endless && state_out_or_null) e = hipMemcpyAsync(state_out_or_null, d_state, cells, hipMemcpyDeviceToHost, s);
     }
-    const hipError_t e_wait = hipStreamSynchronize(s);   // nothing in flight touches the block that is freed next
-    (void)hipFree(d);   // on every path
-    if (r < 0) return r;
-    HIP_TRY(e);
-    HIP_TRY(e_wait);
-    if (endless) {
-        viso_set_error("%s: the relaxation has not come to rest after %zu rounds, more than the box has cells", where, cells + 1);
-        return VISO_ERR_HIP;
-    }
+    hipLaunchKernelGGL(tsdf_travel_finish_kernel, cell_grid, dim3(256), 0, s, d_cost, b.cells, d_ctl);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(ctl, d_ctl, sizeof(ctl), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(cost_out, d_cost, cells * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if (sq_out_or_null) HIP_TRY(hipMemcpyAsync(sq_out_or_null, d_sq, cells * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if (state_out_or_null) HIP_TRY(hipMemcpyAsync(state_out_or_null, d_state, cells, hipMemcpyDeviceToHost, s));
+    VISO_TRY(d.release());
     if (n_goals_used_or_null) *n_goals_used_or_null = ctl[TRAVEL_W_GOALS];
     if (n_reached_or_null) *n_reached_or_null = ctl[TRAVEL_W_REACHED];
     if (n_rounds_or_null) *n_rounds_or_null = ctl[TRAVEL_W_ROUNDS];

@@ -2,8 +2,14 @@
 // voxel_hash.h; DESIGN.md 5.14, "Shared table layer").  A kind of map (viso_map, viso_tsdf) holds a VoxelHost, has a VoxelRegistry
 // of its live handles, and passes in its payload (voxel_hash.h) for the shared kernels and the launches of its own kernels as
 // callables.  The rules that every kind must keep are here and in voxel_host.hip, once: no handle is dereferenced before its
-// registry has answered for it; staging is freed only behind a synchronise; dropped updates become the sticky overflow mark; a
-// temporary list is freed on every path; an eviction leaves no tombstone behind.
+// registry has answered for it; staging is freed only behind a synchronise; dropped updates become the sticky overflow mark; an
+// eviction leaves no tombstone behind.  Two of them are types, and every call on a map goes through them:
+//   VoxelSession  how a call gets at a map: the registry's answer, the live context, the map's device current (voxel_enter, which
+//                 nothing else calls), then the map's mutex for as long as the session lives, then, unless the call asks for a map in
+//                 any state (clear, stats, the option calls), the refusal of an overflowed map.  Nothing else locks VoxelHost::mu.
+//   VoxelScratch  a call's temporary device block, the only hipMalloc / hipFree outside the life of a table and its staging: the
+//                 "cannot allocate" text, and a release (or the destructor, on any return) that waits for the map's stream before
+//                 it frees, so nothing in flight touches the block or the host memory a call's copies read and write.
 #ifndef VISO_VOXEL_HOST_H_
 #define VISO_VOXEL_HOST_H_
 #include "voxel_hash.h"
@@ -70,9 +76,56 @@ void voxel_start_add_entries(const P& p, const typename P::Entry* d_entries, uns
 }
 
 bool voxel_known(VoxelRegistry& reg, const void* handle);
-// a live handle whose context is alive, its device current: *h set; else the error text and code
+// a live handle whose context is alive, its device current: *h set; else the error text and code.  Only a VoxelSession calls it.
 int voxel_enter(const char* where, VoxelRegistry& reg, const void* handle, VoxelHost** h);
 int voxel_refuse_overflowed(const char* where, const VoxelHost* h);
+
+// A call's hold on a map, from voxel_enter to the call's return; the map's mutex is held while the session lives.  status() < 0: the
+// call's return value (the error text is set), and nothing else of the session may be used.
+class VoxelSession {
+public:
+    enum State { NOT_OVERFLOWED, ANY_STATE };
+    // ANY_STATE: an overflowed map is not refused (a call with checks of its own before that refusal makes it with refuse_overflowed)
+    VoxelSession(const char* where, VoxelRegistry& reg, const void* handle, State state = NOT_OVERFLOWED) : where_(where) {
+        if ((status_ = voxel_enter(where, reg, handle, &h_)) < 0) return;
+        lock_ = std::unique_lock<std::mutex>(h_->mu);
+        if (state == NOT_OVERFLOWED) status_ = refuse_overflowed();
+    }
+    int status() const { return status_; }
+    int refuse_overflowed() const { return h_->overflowed ? voxel_refuse_overflowed(where_, h_) : VISO_OK; }
+    const char* where() const { return where_; }
+    VoxelHost* host() const { return h_; }
+    hipStream_t stream() const { return h_->ctx->stream; }
+
+private:
+    const char* where_;
+    VoxelHost* h_ = nullptr;
+    int status_;
+    std::unique_lock<std::mutex> lock_;
+};
+
+// At most one temporary device block of a session, on its device: `bytes` for `what` ("the list", "the views": the noun of the
+// error text); 0 bytes allocate nothing.  release() waits for the map's stream (with a block or without one: an eviction that
+// lists nothing still has the copy of its statistics in flight), frees the block and reports a failed wait; the destructor does
+// the same where release() was not called, so a call may return wherever it likes.  Host memory that the call's copies read or
+// write on the stream is declared before the block: it then outlives the wait.
+class VoxelScratch {
+public:
+    VoxelScratch(const VoxelSession& ses, size_t bytes, const char* what);
+    ~VoxelScratch() { (void)release(); }
+    VoxelScratch(const VoxelScratch&) = delete;
+    VoxelScratch& operator=(const VoxelScratch&) = delete;
+    int status() const { return status_; }   // < 0: the call's return value, the error text is set
+    template <class T>
+    T* as(size_t byte_offset = 0) const { return reinterpret_cast<T*>(d_ + byte_offset); }
+    int release();
+
+private:
+    hipStream_t stream_;
+    char* d_ = nullptr;
+    int status_ = VISO_OK;
+    bool released_ = false;
+};
 
 // viso_*_create behind the check of the parameters.  voxel_create: the context's choice and the table's one allocation of
 // 2^capacity_log2 slots with payload_bytes a slot (a multiple of 4, its 8-byte arrays first); h filled, *payload the payload's
@@ -95,35 +148,22 @@ int voxel_finish(const char* where, VoxelHost* h);
 // viso_*_add_entries behind the handle check and the validation of the n entries
 template <class P>
 int voxel_add_entries(const char* where, VoxelRegistry& reg, const void* handle, const typename P::Entry* entries, size_t n, const P& p) {
-    int r;
-    VoxelHost* h;
-    if ((r = voxel_enter(where, reg, handle, &h)) < 0) return r;
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (h->overflowed) return voxel_refuse_overflowed(where, h);
+    VoxelSession ses(where, reg, handle);
+    VISO_TRY(ses.status());
     if (!n) return VISO_OK;
-    hipStream_t s = h->ctx->stream;
+    hipStream_t s = ses.stream();
     const size_t bytes = n * sizeof(typename P::Entry);
-    typename P::Entry* d = nullptr;
-    if (hipMalloc((void**)&d, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        viso_set_error("%s: cannot allocate %zu bytes for the entries", where, bytes);
-        return VISO_ERR_NOMEM;
-    }
-    hipError_t e = hipMemcpyAsync(d, entries, bytes, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) {
-        voxel_start_add_entries(p, d, (unsigned long long)n, s);
-        e = hipGetLastError();
-    }
-    r = e == hipSuccess ? voxel_finish(where, h) : VISO_OK;
-    if (e != hipSuccess) (void)hipStreamSynchronize(s);   // nothing in flight reads the list that is freed next
-    (void)hipFree(d);
-    HIP_TRY(e);
-    return r;
+    VoxelScratch d(ses, bytes, "the entries");   // (its wait is also the one behind which the caller's entries are read no more)
+    VISO_TRY(d.status());
+    HIP_TRY(hipMemcpyAsync(d.as<typename P::Entry>(), entries, bytes, hipMemcpyHostToDevice, s));
+    voxel_start_add_entries(p, d.as<typename P::Entry>(), (unsigned long long)n, s);
+    HIP_TRY(hipGetLastError());
+    return voxel_finish(where, ses.host());
 }
-// viso_*_render behind the handle and argument checks: the map entered, locked and not overflowed; the poses [n_views][16] (or
-// null) through d_pose; a device buffer for n_views maps of px int16 and, with out.weight, as many uint32, with out.gray, as
-// many uint8, and with out.normals, three floats a pixel, freed on every path; the groups of views, each started by `launch` with its poses ([.][12] or null) and its part of
-// the buffer; the copies to the host.
+// viso_*_render behind the handle and argument checks: a session on the map; the poses [n_views][16] (or null) through d_pose; a
+// scratch block for n_views maps of px int16 and, with out.weight, as many uint32, with out.gray, as many uint8, and with
+// out.normals, three floats a pixel; the groups of views, each started by `launch` with its poses ([.][12] or null) and its part
+// of the block; the copies to the host.
 int voxel_render(const char* where, VoxelRegistry& reg, const void* handle, size_t px, const double* poses, int n_views, const VoxelRenderOut& out,
                  const VoxelRenderLaunch& launch);
 // A host map of px pixels into the fuse's staging d_disp (grow-only), on the stream; *d_disp: where it is.  h is entered and locked.
@@ -139,8 +179,9 @@ int voxel_linearize(const char* where, VoxelHost* h, const double* poses, const 
 // viso_*_stats: the four counters summed over the sets (VOXEL_ST_*) and the dropped word
 int voxel_stats(const char* where, VoxelRegistry& reg, const void* handle, const void* out, unsigned long long sums[4], unsigned long long* dropped);
 
-// One pass of an extraction over the slots: VOXEL_W_OUT zeroed, the launch, the list's length.  h is entered and locked.
-int voxel_pass(VoxelHost* h, const VoxelLaunch& launch, unsigned long long* n);
+// One pass of an extraction over the slots: VOXEL_W_OUT zeroed, the launch, the list's length; with n_tris, the same for the second
+// list's word, VOXEL_W_TRIS.  h is entered and locked.
+int voxel_pass(VoxelHost* h, const VoxelLaunch& launch, unsigned long long* n, unsigned long long* n_tris = nullptr);
 
 // The count (list.count_only) or the sorted list of an extraction: a first pass for the number, a second one into a list of that size.
 // launch(out, out_cap, stream) starts the kernel over the slots that lists the items (out == null: only counts them).  The list's
@@ -154,28 +195,18 @@ int voxel_extract(const char* where, VoxelRegistry& reg, const void* handle, uin
         viso_set_error("%s: bad argument (%s >= 1, non-null outputs)", where, reg.kind.threshold);
         return VISO_ERR_ARG;
     }
-    int r;
-    VoxelHost* h;
-    if ((r = voxel_enter(where, reg, handle, &h)) < 0) return r;
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (h->overflowed) return voxel_refuse_overflowed(where, h);
+    VoxelSession ses(where, reg, handle);
+    VISO_TRY(ses.status());
     unsigned long long c = 0, c2 = 0;
-    if ((r = voxel_pass(h, [&](hipStream_t s) { launch(nullptr, 0, s); }, &c)) < 0) return r;
+    VISO_TRY(voxel_pass(ses.host(), [&](hipStream_t s) { launch(nullptr, 0, s); }, &c));
     *list.n = (size_t)c;
     if (list.count_only || !c) return VISO_OK;
     if (c > list.cap) { viso_set_error("%s: %llu items do not fit the %zu given", where, c, list.cap); return VISO_ERR_ARG; }
-    Item* d = nullptr;
-    if (hipMalloc((void**)&d, (size_t)c * sizeof(Item)) != hipSuccess) {
-        (void)hipGetLastError();
-        viso_set_error("%s: cannot allocate %zu bytes for the list", where, (size_t)c * sizeof(Item));
-        return VISO_ERR_NOMEM;
-    }
-    r = voxel_pass(h, [&](hipStream_t s) { launch(d, c, s); }, &c2);
-    hipError_t e = hipSuccess;
-    if (r >= 0) e = hipMemcpy(list.out, d, (size_t)c * sizeof(Item), hipMemcpyDeviceToHost);
-    (void)hipFree(d);   // on every path
-    if (r < 0) return r;
-    HIP_TRY(e);
+    VoxelScratch d(ses, (size_t)c * sizeof(Item), "the list");
+    VISO_TRY(d.status());
+    VISO_TRY(voxel_pass(ses.host(), [&](hipStream_t s) { launch(d.as<Item>(), c, s); }, &c2));
+    HIP_TRY(hipMemcpy(list.out, d.as<Item>(), (size_t)c * sizeof(Item), hipMemcpyDeviceToHost));
+    VISO_TRY(d.release());   // (before the sort, not behind it)
     if (c2 != c) { viso_set_error("%s: the table changed between the two passes", where); return VISO_ERR_HIP; }   // (the map's lock rules it out)
     std::sort(list.out, list.out + c, [](const Item& x, const Item& y) { return voxel_item_less(x, y); });
     return VISO_OK;
@@ -209,11 +240,9 @@ int voxel_evict(const char* where, VoxelRegistry& reg, const void* handle, const
                 const P& p) {
     using Item = typename P::Entry;
     if (!voxel_evict_args(where, reg, handle, keep, list.n)) return VISO_ERR_ARG;
-    int r;
-    VoxelHost* h;
-    if ((r = voxel_enter(where, reg, handle, &h)) < 0) return r;
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (h->overflowed) return voxel_refuse_overflowed(where, h);
+    VoxelSession ses(where, reg, handle);
+    VISO_TRY(ses.status());
+    VoxelHost* h = ses.host();
     VoxelBox box;
     for (int i = 0; i < 3; ++i) { box.lo[i] = keep->lo[i]; box.hi[i] = keep->hi[i]; }
     const size_t slots = (size_t)h->head.mask + 1;
@@ -225,51 +254,41 @@ int voxel_evict(const char* where, VoxelRegistry& reg, const void* handle, const
         };
     };
     unsigned long long c = 0, c2 = 0, occupied = 0;
-    if ((r = voxel_pass(h, mark(VOXEL_EVICT_COUNT, nullptr, 0), &c)) < 0) return r;
+    VISO_TRY(voxel_pass(h, mark(VOXEL_EVICT_COUNT, nullptr, 0), &c));
     *list.n = (size_t)c;
     if (list.count_only || !c) return VISO_OK;
     if (list.out && c > list.cap) { viso_set_error("%s: %llu items do not fit the %zu given", where, c, list.cap); return VISO_ERR_ARG; }
-    std::vector<unsigned long long> stats;
-    if ((r = voxel_evict_get_stats(h, stats, &occupied)) < 0) return r;
+    std::vector<unsigned long long> stats;   // (before the block: the copy that puts them back reads them until its wait)
+    VISO_TRY(voxel_evict_get_stats(h, stats, &occupied));
     const bool full = occupied >= slots;
     const unsigned long long n_keep = full ? slots - c : 0;
     const size_t b_out = list.out ? (size_t)c * sizeof(Item) : 0, b_keep = (size_t)n_keep * sizeof(Item);
-    char* d = nullptr;   // the evicted | a full table's survivors
-    if (b_out + b_keep && hipMalloc((void**)&d, b_out + b_keep) != hipSuccess) {
-        (void)hipGetLastError();
-        viso_set_error("%s: cannot allocate %zu bytes for the list", where, b_out + b_keep);
-        return VISO_ERR_NOMEM;
-    }
-    Item* d_out = list.out ? reinterpret_cast<Item*>(d) : nullptr;
-    Item* d_keep = reinterpret_cast<Item*>(d + b_out);
-    hipStream_t s = h->ctx->stream;
-    hipError_t e = hipSuccess;
+    VoxelScratch d(ses, b_out + b_keep, "the list");   // the evicted | a full table's survivors
+    VISO_TRY(d.status());
+    Item* d_out = list.out ? d.as<Item>() : nullptr;
+    Item* d_keep = d.as<Item>(b_out);
+    hipStream_t s = ses.stream();
     if (!full) {
-        r = voxel_pass(h, mark(VOXEL_EVICT_LIST, d_out, c), &c2);
-        if (r >= 0) {   // tombstones are in the table: both passes follow whatever else happens
-            hipLaunchKernelGGL(voxel_evict_rebuild_kernel<P>, grid, dim3(256), 0, s, head, p);
-            hipLaunchKernelGGL(voxel_evict_sweep_kernel<P>, grid, dim3(256), 0, s, head, p);
-            e = hipGetLastError();
-        }
+        VISO_TRY(voxel_pass(h, mark(VOXEL_EVICT_LIST, d_out, c), &c2));
+        // tombstones are in the table: both passes follow before anything else can return
+        hipLaunchKernelGGL(voxel_evict_rebuild_kernel<P>, grid, dim3(256), 0, s, head, p);
+        hipLaunchKernelGGL(voxel_evict_sweep_kernel<P>, grid, dim3(256), 0, s, head, p);
+        HIP_TRY(hipGetLastError());
     } else {
-        if (d_out) r = voxel_pass(h, mark(VOXEL_EVICT_PEEK, d_out, c), &c2);
+        if (d_out) VISO_TRY(voxel_pass(h, mark(VOXEL_EVICT_PEEK, d_out, c), &c2));
         else c2 = c;
         unsigned long long k2 = 0;
-        if (r >= 0 && n_keep) r = voxel_pass(h, mark(VOXEL_EVICT_KEEP, d_keep, n_keep), &k2);
-        if (r >= 0 && k2 != n_keep) c2 = ~0ull;
-        if (r >= 0 && c2 == c) {
+        if (n_keep) VISO_TRY(voxel_pass(h, mark(VOXEL_EVICT_KEEP, d_keep, n_keep), &k2));
+        if (k2 != n_keep) c2 = ~0ull;
+        if (c2 == c) {
             voxel_start_clear(p, s);
             if (n_keep) voxel_start_add_entries(p, d_keep, n_keep, s);
-            e = hipGetLastError();
+            HIP_TRY(hipGetLastError());
         }
     }
-    if (r >= 0 && e == hipSuccess && c2 == c) r = voxel_evict_put_stats(h, stats, c);
-    if (r >= 0 && e == hipSuccess && d_out) e = hipMemcpyAsync(list.out, d_out, b_out, hipMemcpyDeviceToHost, s);
-    const hipError_t e_wait = hipStreamSynchronize(s);   // nothing in flight touches the list that is freed next
-    if (d) (void)hipFree(d);   // on every path
-    if (r < 0) return r;
-    HIP_TRY(e);
-    HIP_TRY(e_wait);
+    if (c2 == c) VISO_TRY(voxel_evict_put_stats(h, stats, c));
+    if (d_out) HIP_TRY(hipMemcpyAsync(list.out, d_out, b_out, hipMemcpyDeviceToHost, s));
+    VISO_TRY(d.release());
     if (c2 != c) { viso_set_error("%s: the table changed between the two passes", where); return VISO_ERR_HIP; }   // (the map's lock rules it out)
     if (list.out) std::sort(list.out, list.out + c, [](const Item& x, const Item& y) { return voxel_item_less(x, y); });
     return VISO_OK;

@@ -1,6 +1,6 @@
-// voxel_host.hip — the host side of the shared table layer (voxel_host.h): the registry of live handles, the life of a table, the
-// staging (the map, the poses and, where a kind fuses one, the image) and the group loop of a fuse, the wait behind a call's launches,
-// the pass of an extraction, the staging and the output buffer of a render, the staging and the sums of a linearise, the read-back of the
+// voxel_host.hip — the host side of the shared table layer (voxel_host.h): the registry of live handles, the life of a table, a
+// call's scratch block, the staging (the map, the poses and, where a kind fuses one, the image) and the group loop of a fuse,
+// the wait behind a call's launches, the pass of an extraction, the staging and the output buffer of a render, the staging and the sums of a linearise, the read-back of the
 // statistics, and of an eviction the argument checks, the statistics' round trip and the box around a point.
 // No kernel is here: a kind passes in the launches of its own kernels, and the templates of voxel_host.h start the shared ones.
 #include "voxel_host.h"
@@ -106,11 +106,27 @@ int voxel_free(const char* where, VoxelHost* h) {
 }
 
 int voxel_clear(const char* where, VoxelRegistry& reg, const void* handle, const VoxelLaunch& clear) {
-    int r;
-    VoxelHost* h;
-    if ((r = voxel_enter(where, reg, handle, &h)) < 0) return r;
-    std::lock_guard<std::mutex> lk(h->mu);
-    return voxel_launch_clear(h, clear);
+    VoxelSession ses(where, reg, handle, VoxelSession::ANY_STATE);
+    VISO_TRY(ses.status());
+    return voxel_launch_clear(ses.host(), clear);
+}
+
+VoxelScratch::VoxelScratch(const VoxelSession& ses, size_t bytes, const char* what) : stream_(ses.stream()) {
+    if (!bytes || hipMalloc((void**)&d_, bytes) == hipSuccess) return;
+    (void)hipGetLastError();
+    d_ = nullptr;
+    viso_set_error("%s: cannot allocate %zu bytes for %s", ses.where(), bytes, what);
+    status_ = VISO_ERR_NOMEM;
+}
+
+int VoxelScratch::release() {
+    if (released_) return VISO_OK;
+    released_ = true;
+    const hipError_t e_wait = hipStreamSynchronize(stream_);   // nothing in flight touches the block that is freed next
+    if (d_) (void)hipFree(d_);
+    d_ = nullptr;
+    HIP_TRY(e_wait);
+    return VISO_OK;
 }
 
 // grow-only staging of `bytes` at *p
@@ -177,12 +193,12 @@ int voxel_fuse(const char* where, VoxelRegistry& reg, const void* handle, const 
     if (!voxel_known(reg, handle)) return voxel_not_live(where, reg);
     if (!v.ctx && (!v.disp || v.rows <= 0 || v.cols <= 0)) { viso_set_error("%s: bad argument (non-null map and calibration, sizes > 0)", where); return VISO_ERR_ARG; }
     int r;
-    VoxelHost* h;
     if ((r = voxel_fuse_check(where, v)) < 0) return r;
-    if ((r = voxel_enter(where, reg, handle, &h)) < 0) return r;
+    VoxelSession ses(where, reg, handle, VoxelSession::ANY_STATE);   // the overflow refusal comes behind the context's
+    VISO_TRY(ses.status());
+    VoxelHost* h = ses.host();
     if (v.ctx && h->ctx != v.ctx) { viso_set_error("%s: the %s and the batch must share a context", where, reg.kind.noun); return VISO_ERR_ARG; }
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (h->overflowed) return voxel_refuse_overflowed(where, h);
+    VISO_TRY(ses.refuse_overflowed());
     const size_t px = v.px();
     const int16_t* disp = v.disp;
     const uint8_t* image = v.image;
@@ -206,12 +222,14 @@ int voxel_fuse(const char* where, VoxelRegistry& reg, const void* handle, const 
     return voxel_finish(where, h);
 }
 
-int voxel_pass(VoxelHost* h, const VoxelLaunch& launch, unsigned long long* n) {
+int voxel_pass(VoxelHost* h, const VoxelLaunch& launch, unsigned long long* n, unsigned long long* n_tris) {
     hipStream_t s = h->ctx->stream;
     HIP_TRY(hipMemsetAsync(h->head.words + VOXEL_W_OUT, 0, sizeof(unsigned long long), s));
+    if (n_tris) HIP_TRY(hipMemsetAsync(h->head.words + VOXEL_W_TRIS, 0, sizeof(unsigned long long), s));
     launch(s);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(n, h->head.words + VOXEL_W_OUT, sizeof(*n), hipMemcpyDeviceToHost, s));
+    if (n_tris) HIP_TRY(hipMemcpyAsync(n_tris, h->head.words + VOXEL_W_TRIS, sizeof(*n_tris), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return VISO_OK;
 }
@@ -267,46 +285,34 @@ extern "C" int viso_voxel_box_around(const double centre[3], double half_side, d
 
 int voxel_render(const char* where, VoxelRegistry& reg, const void* handle, size_t px, const double* poses, int n_views, const VoxelRenderOut& out,
                  const VoxelRenderLaunch& launch) {
-    int r;
-    VoxelHost* h;
-    if ((r = voxel_enter(where, reg, handle, &h)) < 0) return r;
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (h->overflowed) return voxel_refuse_overflowed(where, h);
-    hipStream_t s = h->ctx->stream;
+    VoxelSession ses(where, reg, handle);
+    VISO_TRY(ses.status());
+    VoxelHost* h = ses.host();
+    hipStream_t s = ses.stream();
     // bytes a pixel: the normals, then the weights, then the maps, then the intensities
     const size_t per = (out.normals ? 12 : 0) + (out.weight ? 6 : 2) + (out.gray ? 1 : 0);
     if (px > (size_t)-1 / per / (size_t)n_views) { viso_set_error("%s: %d views of %zu pixels are beyond the address space", where, n_views, px); return VISO_ERR_NOMEM; }
     const size_t n = (size_t)n_views * px, b_normals = out.normals ? n * 3 * sizeof(float) : 0, b_weight = out.weight ? n * sizeof(uint32_t) : 0,
                  b_disp = n * sizeof(int16_t), bytes = b_normals + b_weight + b_disp + (out.gray ? n : 0);
-    std::vector<double> rows12;   // alive until the stream has been waited for
-    if (poses && (r = voxel_stage_poses(where, h, poses, n_views, rows12)) < 0) return r;
-    void* d = nullptr;
-    if (hipMalloc(&d, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipStreamSynchronize(s);   // the copy of the poses reads rows12
-        viso_set_error("%s: cannot allocate %zu bytes for the views", where, bytes);
-        return VISO_ERR_NOMEM;
-    }
-    float* d_normals = out.normals ? static_cast<float*>(d) : nullptr;
-    uint32_t* d_weight = out.weight ? reinterpret_cast<uint32_t*>(static_cast<char*>(d) + b_normals) : nullptr;
-    int16_t* d_disp = reinterpret_cast<int16_t*>(static_cast<char*>(d) + b_normals + b_weight);
-    uint8_t* d_gray = out.gray ? static_cast<uint8_t*>(d) + b_normals + b_weight + b_disp : nullptr;
-    hipError_t e = hipSuccess;
-    for (int v0 = 0; v0 < n_views && e == hipSuccess; v0 += VOXEL_GROUP) {
+    std::vector<double> rows12;   // (before the block: the copy of the poses reads it until the block's wait, a failed allocation's too)
+    if (poses) VISO_TRY(voxel_stage_poses(where, h, poses, n_views, rows12));
+    VoxelScratch d(ses, bytes, "the views");
+    VISO_TRY(d.status());
+    float* d_normals = out.normals ? d.as<float>() : nullptr;
+    uint32_t* d_weight = out.weight ? d.as<uint32_t>(b_normals) : nullptr;
+    int16_t* d_disp = d.as<int16_t>(b_normals + b_weight);
+    uint8_t* d_gray = out.gray ? d.as<uint8_t>(b_normals + b_weight + b_disp) : nullptr;
+    for (int v0 = 0; v0 < n_views; v0 += VOXEL_GROUP) {
         const int nv = n_views - v0 < VOXEL_GROUP ? n_views - v0 : VOXEL_GROUP;
         launch(poses ? h->d_pose + (size_t)v0 * 12 : nullptr, d_disp + (size_t)v0 * px, d_weight ? d_weight + (size_t)v0 * px : nullptr,
                d_gray ? d_gray + (size_t)v0 * px : nullptr, d_normals ? d_normals + (size_t)v0 * px * 3 : nullptr, dim3((unsigned)((px + 255) / 256), (unsigned)nv), s);
-        e = hipGetLastError();
+        HIP_TRY(hipGetLastError());
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(out.disp, d_disp, n * sizeof(int16_t), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && d_weight) e = hipMemcpyAsync(out.weight, d_weight, b_weight, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && d_gray) e = hipMemcpyAsync(out.gray, d_gray, n, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && d_normals) e = hipMemcpyAsync(out.normals, d_normals, b_normals, hipMemcpyDeviceToHost, s);
-    const hipError_t e_wait = hipStreamSynchronize(s);   // nothing in flight touches the buffer that is freed next
-    (void)hipFree(d);   // on every path
-    HIP_TRY(e);
-    HIP_TRY(e_wait);
-    return VISO_OK;
+    HIP_TRY(hipMemcpyAsync(out.disp, d_disp, n * sizeof(int16_t), hipMemcpyDeviceToHost, s));
+    if (d_weight) HIP_TRY(hipMemcpyAsync(out.weight, d_weight, b_weight, hipMemcpyDeviceToHost, s));
+    if (d_gray) HIP_TRY(hipMemcpyAsync(out.gray, d_gray, n, hipMemcpyDeviceToHost, s));
+    if (d_normals) HIP_TRY(hipMemcpyAsync(out.normals, d_normals, b_normals, hipMemcpyDeviceToHost, s));
+    return d.release();
 }
 
 int voxel_stage_map(const char* where, VoxelHost* h, const int16_t* disp, size_t px, const int16_t** d_disp) {
@@ -357,10 +363,9 @@ int voxel_linearize(const char* where, VoxelHost* h, const double* poses, const 
 int voxel_stats(const char* where, VoxelRegistry& reg, const void* handle, const void* out, unsigned long long sums[4], unsigned long long* dropped) {
     if (!voxel_known(reg, handle)) return voxel_not_live(where, reg);
     if (!out) { viso_set_error("%s: bad argument (a non-null output)", where); return VISO_ERR_ARG; }
-    int r;
-    VoxelHost* h;
-    if ((r = voxel_enter(where, reg, handle, &h)) < 0) return r;
-    std::lock_guard<std::mutex> lk(h->mu);
+    VoxelSession ses(where, reg, handle, VoxelSession::ANY_STATE);
+    VISO_TRY(ses.status());
+    VoxelHost* h = ses.host();
     std::vector<unsigned long long> w((size_t)VOXEL_STAT_SETS * VOXEL_STAT_WORDS + 2);
     hipStream_t s = h->ctx->stream;
     HIP_TRY(hipMemcpyAsync(w.data(), h->head.stats, w.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));   // stats | words: adjacent
