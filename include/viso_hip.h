@@ -1637,6 +1637,86 @@ int viso_tsdf_travel_field(viso_tsdf* t, uint32_t min_weight, const viso_voxel_b
                            uint8_t* state_out_or_null, size_t n_cap, size_t* n_goals_used_or_null, size_t* n_reached_or_null,
                            size_t* n_rounds_or_null);
 
+/* ------------------------------------------------ TSDF retract: fused frames taken out of the map again, so that poses can be
+ * corrected (opt-in; NOT in the reference)
+ *
+ * A frame's pose is often known better after the frame has been fused: a window refinement, an alignment against the model, a loop
+ * closure.  The weights, the sums and the gray sums of the table are integers, so fusing is adding, and an addition has an inverse:
+ * subtracting the updates of a frame, computed from the same map, calibration, pose and fuse options, gives the table that never
+ * saw the frame, bit for bit.  A move is that, followed by the fuse at the better pose.  This definition is the contract; the
+ * device result is bit-identical to tests/retract_ref.py.
+ *   1. Updates.  A retract of a frame (disp, rows, cols, param, pose, and image on a gray map) applies rules 1 to 6 of "TSDF map" to
+ *      it, with the map's min_disp16 and its current fuse options (rules 3 and 7 of "TSDF fuse options"): exactly the updates
+ *      (voxel, w, q, I) a fuse of the frame would make now.
+ *   2. Take.  Rule 7 runs with the opposite sign, in the table's own arithmetic (weight modulo 2^32, sum and gray modulo 2^64):
+ *      weight -= w, sum -= w q, gray -= w I.  Every update looks its voxel up read-only: no slot is claimed and no key written.
+ *        An update whose voxel is not in the table changes nothing and counts in n_missing (updates, like n_dropped).
+ *        A voxel whose weight the call takes below zero makes n_underflow non-zero: n_underflow != 0 exactly when at least one
+ *        voxel underflows; its value is not part of the contract (which atomic sees the crossing depends on scheduling).
+ *        The map's counters n_points, n_updates and n_out_of_range fall by what the same fuse would have added.
+ *   3. Check, one read-only pass over the slots behind the take.
+ *        n_freed: the voxels in the table with weight 0 whose sum, and gray on a gray map, are 0.
+ *        n_inconsistent: the voxels with weight 0 and a sum or a gray that is not 0, and the voxels with weight > 0 and
+ *        |sum| > T 1024 weight or gray > 255 weight: the bounds viso_tsdf_add_entries asks of an entry.
+ *   4. Commit.  With n_missing, n_underflow and n_inconsistent all 0 the freed voxels leave the table as an eviction's do ("Map
+ *      eviction", "Capacity comes back"): every survivor is found by the probes, every freed slot is an empty slot again, nothing
+ *      like a tombstone outlives the call, and n_occupied falls by n_freed.  The call returns VISO_OK.  This is the eviction by
+ *      weight that "Map eviction" leaves out, in its exact form: a voxel goes when its weight has returned to zero.
+ *   5. Undo.  Otherwise the take runs again with the sign flipped.  It is find-only as well, so it touches exactly the same slots,
+ *      and the modular additions restore every word, the three counters included: the map is bit for bit what it was.  The call
+ *      returns VISO_ERR_ARG with an error text that names the three numbers.
+ *   6. Report.  report (or NULL) receives six uint64 either way, in this order (VISO_RETRACT_*): n_points and n_updates of the
+ *      retracted frames (what rule 2 took from the counters), n_missing, n_underflow, n_inconsistent, n_freed; the last two are the
+ *      check's, taken behind the take and before any undo.  A call refused before the take writes nothing to it.
+ *   7. Move: the retract at the old poses and, if it commits, the fuse at the new ones, under one hold on the map.  A refused
+ *      retract fuses nothing and leaves the map unchanged.  A fuse that then fills the table returns VISO_ERR_NOMEM with the
+ *      overflow mark, as any fuse does; the retract before it stays.
+ *   8. Frames: the batch calls retract (move) the resident maps of frames t0 .. t1-1, a gray map's with the resident left images,
+ *      in one call: one take, one check and one commit or undo for all of them, so the call stands or falls as a whole.
+ * What the checks are: necessary conditions, not a proof that the frames were fused.  A frame that was never fused, but whose
+ * updates all land on voxels of the table and leave every one of them within its bounds, passes, and leaves a valid table that
+ * is the sum of no set of frames.  Retracting what was fused with other fuse options, another min_disp16, another calibration or
+ * another pose is the caller's error; it is usually, but not always, refused.  The caller keeps its maps and poses (the batch
+ * does); the map keeps no log of frames.
+ * Eviction: voxels that were evicted since the fuse are missing, so the call is refused: retract before evicting, or retract from
+ * a map rebuilt from the archive with viso_tsdf_add_entries (merge_entries in Python).
+ * Refusals: the argument checks are those of the fuse calls, in the same order and with the same codes, before a device is
+ * touched: the handle and its kind (viso_tsdf_retract on a gray map and the *_gray calls on a plain one: VISO_ERR_ARG), a non-null
+ * map, calibration and (gray) image, sizes > 0, finite poses (a move: both) and calibration, then the context the batch and the map
+ * must share.  An overflowed map refuses with VISO_ERR_NOMEM, like every other call (a map whose n_dropped is not 0 always carries
+ * that mark).  A weight that wrapped beyond 2^32 while fusing is not detected.
+ * Device memory of a call: none beyond the fuse's staging; a table without a single empty slot is rebuilt through a list of its
+ * survivors, as in an eviction.  Every loop on the device is the fuse's march or a probe's one round of the slots.
+ * Cost: the take is the fuse's march with read-only probes and the same atomics; a call adds the slot passes of a discarding
+ * eviction (check, mark, rebuild, sweep) whatever the number of frames (DESIGN.md 5.26 has the measurements).
+ * Out of scope: a retract for the voxel map; a list of the slots that reached zero, so that a small call skips the slot passes;
+ * freeing deferred across calls; a log of fused frames inside the map; loop-closure detection and pose-graph optimisation.
+ * HIP kernels: tsdf_take_kernel, tsdf_gray_take_kernel, tsdf_carve_take_kernel, tsdf_gray_carve_take_kernel (tsdf.hip): the four
+ * fuse kernels' body with one more template flag, so the updates are the fuse's by construction: the loop over j uniform across
+ * the wave, the runs of equal keys, the runs' sums by wave scans, and only a run's head lane at the table, where it finds (not
+ * claims) the slot, adds the negated sums (the sums themselves in the undo: a runtime sign) and compares the weight its own atomic
+ * returns with what it took; n_missing and the underflow flag by one atomic per wave and word, only when not zero.
+ * voxel_retract_check_kernel and voxel_retract_mark_kernel (voxel_hash.h, templates over the kind's payload, one thread per
+ * slot); the rebuild and the sweep are the eviction's kernels. */
+#define VISO_RETRACT_N_POINTS 0
+#define VISO_RETRACT_N_UPDATES 1
+#define VISO_RETRACT_N_MISSING 2
+#define VISO_RETRACT_N_UNDERFLOW 3
+#define VISO_RETRACT_N_INCONSISTENT 4
+#define VISO_RETRACT_N_FREED 5
+int viso_tsdf_retract(viso_tsdf* t, const int16_t* disp, int rows, int cols, const viso_param* param, const double* pose_or_null,
+                      uint64_t report_or_null[6]);
+int viso_tsdf_retract_gray(viso_tsdf* t, const int16_t* disp, const uint8_t* image, int rows, int cols, const viso_param* param,
+                           const double* pose_or_null, uint64_t report_or_null[6]);
+/* poses [t1 - t0][16], as viso_batch_fuse_tsdf takes them and with its refusals */
+int viso_batch_retract_tsdf(viso_batch* b, viso_tsdf* t, int t0, int t1, const double* poses, uint64_t report_or_null[6]);
+int viso_tsdf_move(viso_tsdf* t, const int16_t* disp, int rows, int cols, const viso_param* param, const double* pose_old_or_null,
+                   const double* pose_new_or_null, uint64_t report_or_null[6]);
+int viso_tsdf_move_gray(viso_tsdf* t, const int16_t* disp, const uint8_t* image, int rows, int cols, const viso_param* param,
+                        const double* pose_old_or_null, const double* pose_new_or_null, uint64_t report_or_null[6]);
+int viso_batch_move_tsdf(viso_batch* b, viso_tsdf* t, int t0, int t1, const double* poses_old, const double* poses_new,
+                         uint64_t report_or_null[6]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -194,6 +194,18 @@ class TsdfCounters(C.Structure):
 TSDF_FUSE_DEFAULTS = dict(carve_voxels=0, weight_shift=-1, weight_max=255, carve_near=0.0)
 
 
+class TsdfRetractReport(C.Structure):
+    """The six uint64 a retract or a move reports, in the order of VISO_RETRACT_* (include/viso_hip.h, "TSDF retract", rule 6)."""
+    _fields_ = [(name, C.c_uint64) for name in ("n_points", "n_updates", "n_missing", "n_underflow", "n_inconsistent", "n_freed")]
+
+    def words(self):
+        """The report as the calls take it: a pointer to its six words."""
+        return C.cast(C.pointer(self), C.POINTER(C.c_uint64))
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
 class TsdfAlignParams(C.Structure):
     """struct viso_tsdf_align_params (include/viso_hip.h, "TSDF align")."""
     _fields_ = [("min_weight", C.c_uint32), ("gate_voxels", C.c_double), ("max_iters", C.c_int32), ("eps_rot", C.c_double),
@@ -282,7 +294,7 @@ class PlainTimes(C.Structure):
 # and holds every entry to it.
 P = C.POINTER
 i, i64, u32, u64, sz, dbl, vp = C.c_int, C.c_int64, C.c_uint32, C.c_uint64, C.c_size_t, C.c_double, C.c_void_p
-i16p, u32p, szp, vpp = P(C.c_int16), P(C.c_uint32), P(C.c_size_t), P(C.c_void_p)
+i16p, u32p, u64p, szp, vpp = P(C.c_int16), P(C.c_uint32), P(C.c_uint64), P(C.c_size_t), P(C.c_void_p)
 MP, PP = P(MatchParams), P(Param)
 
 PROTOTYPES = {
@@ -473,6 +485,13 @@ PROTOTYPES = {
     "tsdf_distance_field": (i, [vp, u32, P(VoxelBox), u32, u32p, u8p, sz, szp]),
     # TSDF travel field
     "tsdf_travel_field": (i, [vp, u32, P(VoxelBox), u32, u32, i32p, sz, u32p, u32p, u8p, sz, szp, szp, szp]),
+    # TSDF retract
+    "tsdf_retract": (i, [vp, i16p, i, i, PP, f64p, u64p]),
+    "tsdf_retract_gray": (i, [vp, i16p, u8p, i, i, PP, f64p, u64p]),
+    "batch_retract_tsdf": (i, [vp, vp, i, i, f64p, u64p]),
+    "tsdf_move": (i, [vp, i16p, i, i, PP, f64p, f64p, u64p]),
+    "tsdf_move_gray": (i, [vp, i16p, u8p, i, i, PP, f64p, f64p, u64p]),
+    "batch_move_tsdf": (i, [vp, vp, i, i, f64p, f64p, u64p]),
 }
 
 # what the oracle library exports under its own prefix with the same signatures (declare_common, oracle/pyoracle.py)

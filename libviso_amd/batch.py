@@ -9,7 +9,7 @@ from . import VisoError, _call, _f32, _Handle, _i32, _pose_arg, _sigma, _struct_
 from .abi import (DESC_LEN, MOTION_COV_DTYPE, MOTION_REFINE_DTYPE, TSDF_ALIGNMENT_DTYPE, TSDF_ALIGNMENT_GRAY_DTYPE, WINDOW_RECORD_DTYPE,
                   DisparityParams, SgmParams, SpeckleParams, ptr)
 from .dense import _map_pair, disparity_params, sgm_params, speckle_params
-from .maps import tsdf_align_gray_params, tsdf_align_params
+from .maps import _reported, tsdf_align_gray_params, tsdf_align_params
 from .plain import HARRIS_K
 
 
@@ -230,6 +230,26 @@ class Batch(_Handle):
         device, frame t0 + i with the 4 x 4 pose poses[i]; no map is copied to the host.  The map must be on this batch's context."""
         t1, T = self._range_poses("Batch.fuse_tsdf", poses, t0, t1)
         _call(self.L.viso_batch_fuse_tsdf, self.h, tsdf.h, int(t0), t1, ptr(T, C.c_double))
+
+    @property
+    def retract_tsdf(self):
+        """viso_batch_retract_tsdf (include/viso_hip.h, "TSDF retract"), called as `batch.retract_tsdf(tsdf, poses, t0=0, t1=None)`:
+        the resident maps of frames t0 .. t1-1 (a gray map's with the resident left images) taken out of the TsdfMap again, frame
+        t0 + i at the 4 x 4 pose poses[i] it was fused at, all in one call that stands or falls as a whole.  Returns the report as
+        a dict (TsdfMap.retract); a refusal raises the library's error with it as .report and leaves the map unchanged.  A
+        property that hands out the call, like TsdfMap.distance_field."""
+        return lambda tsdf, poses, t0=0, t1=None: self._retract_tsdf("retract", tsdf, (poses,), t0, t1)
+
+    @property
+    def move_tsdf(self):
+        """viso_batch_move_tsdf, called as `batch.move_tsdf(tsdf, old_poses, new_poses, t0=0, t1=None)`: retract_tsdf at old_poses
+        and, if that is not refused, fuse_tsdf at new_poses, under one hold on the map.  Returns the retract's report."""
+        return lambda tsdf, old_poses, new_poses, t0=0, t1=None: self._retract_tsdf("move", tsdf, (old_poses, new_poses), t0, t1)
+
+    def _retract_tsdf(self, name, tsdf, poses, t0, t1):
+        where = f"Batch.{name}_tsdf"
+        T = [self._range_poses(where, p, t0, t1) for p in poses]
+        return _reported(getattr(self.L, f"viso_batch_{name}_tsdf"), self.h, tsdf.h, int(t0), T[0][0], *(ptr(p, C.c_double) for _, p in T))
 
     def align_tsdf(self, tsdf, poses, t0=0, t1=None, photo=False, **params):
         """viso_batch_align_tsdf: the resident maps of frames t0 .. t1-1 (t1 None: to the last frame) aligned against the TsdfMap, each

@@ -211,6 +211,27 @@ extern "C" int viso_batch_fuse_tsdf(viso_batch* b, viso_tsdf* t, int t0, int t1,
     return tsdf_fuse_resident(where, t, v);
 }
 
+// The resident maps of frames t0 .. t1-1 taken out of a TSDF map again (tsdf.hip; include/viso_hip.h, "TSDF retract"), at the poses
+// they were fused at; a gray map's with the resident left images, as the fuse.  One take, one check and one commit or undo for all.
+extern "C" int viso_batch_retract_tsdf(viso_batch* b, viso_tsdf* t, int t0, int t1, const double* poses, uint64_t report_or_null[6]) {
+    const char* where = "viso_batch_retract_tsdf";
+    VISO_TRY(fuse_prelude(where, b, t, t0, t1, poses));
+    DispView v;
+    VISO_TRY(dense_view(where, b, t0, t1, poses, tsdf_is_gray(t) ? "a gray TSDF map" : nullptr, &v));
+    return tsdf_retract_resident(where, t, v, false, nullptr, report_or_null);
+}
+
+// The same, and the frames fused again at poses_new behind it, under one hold on the map: a refused retract fuses nothing.
+extern "C" int viso_batch_move_tsdf(viso_batch* b, viso_tsdf* t, int t0, int t1, const double* poses_old, const double* poses_new,
+                                    uint64_t report_or_null[6]) {
+    const char* where = "viso_batch_move_tsdf";
+    if (!poses_new) { viso_set_error("%s: bad argument (poses_new [t1 - t0][16])", where); return VISO_ERR_ARG; }
+    VISO_TRY(fuse_prelude(where, b, t, t0, t1, poses_old));
+    DispView v;
+    VISO_TRY(dense_view(where, b, t0, t1, poses_old, tsdf_is_gray(t) ? "a gray TSDF map" : nullptr, &v));
+    return tsdf_retract_resident(where, t, v, true, poses_new, report_or_null);
+}
+
 // The resident maps of frames t0 .. t1-1 aligned against a TSDF map of the same context (tsdf_align.hip), each on its own from its
 // guess, with the batch's calibration and no host copy of the maps.  The refusals of viso_batch_fuse_tsdf.
 extern "C" int viso_batch_align_tsdf(viso_batch* b, viso_tsdf* t, int t0, int t1, const double* poses_guess, const viso_tsdf_align_params* params,

@@ -509,6 +509,9 @@ int map_fuse_resident(const char* where, viso_map* m, const DispView& v);
 // 1 for a live gray map, else 0) the view has the images, for a plain one it has none
 int tsdf_is_gray(viso_tsdf* t);
 int tsdf_fuse_resident(const char* where, viso_tsdf* t, const DispView& v);
+// the retract of a view's maps from the map ("TSDF retract"), with fuse_resident's checks; move: and their fuse at poses_new
+// ([v.n][16]) behind it.  report: six words, or null
+int tsdf_retract_resident(const char* where, viso_tsdf* t, const DispView& v, bool move, const double* poses_new, uint64_t* report);
 // tsdf_align.hip: the opt-in frame-to-model alignment (viso_tsdf_align).  tsdf_align_resident: the alignment of a resident view's
 // maps against the map, each on its own from its pose; checks the arguments, the handle and its context
 int tsdf_align_resident(const char* where, viso_tsdf* t, const DispView& v, const viso_tsdf_align_params* params, viso_tsdf_alignment* records);

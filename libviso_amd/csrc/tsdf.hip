@@ -45,6 +45,13 @@
 //   tsdf_gray_carve_fuse_kernel   its lanes has a sample to insert (one wave minimum, wave.h), with the pixel's weight w carried: the
 //                                 run's sums of w, w (q + T 1024) and w I from one wave scan each, the run's length only for the
 //                                 dropped counter.  Launched only for a map whose options are not the defaults.
+// A retract (include/viso_hip.h, "TSDF retract") takes the updates of fused frames out of the table again, four
+// more instances of the fuse body (template <.., bool TAKE>; without TAKE the four kernels above are what they were):
+//   tsdf_take_kernel              the fuse kernels' march, run for run; a run's head lane finds its slot (voxel_find: no slot is
+//   tsdf_gray_take_kernel         claimed, no key written), adds the negated sums -- or, with the runtime flag undo, the sums
+//   tsdf_carve_take_kernel        themselves -- and compares the weight its own atomic returns with what it took.  The updates that
+//   tsdf_gray_carve_take_kernel   found no voxel and the underflow flag: one atomic per wave and word, only when not zero.
+// The check and the mark that follow are voxel_hash.h's, over TsdfPayload; the rebuild and the sweep are the eviction's.
 // The frame-to-model alignment that reads this table is in tsdf_align.hip (the table's layout: tsdf_table.h).
 // What every table of voxels shares is not here (voxelmap.hip says what): the device side is voxel_hash.h, the host side
 // voxel_host.h.  The kernels that list, clear, add entries to and evict slots are voxel_hash.h's templates, instantiated here over
@@ -79,6 +86,23 @@ __device__ __forceinline__ void tsdf_insert(const TsdfTable& t, unsigned long lo
     }
 }
 
+// The take's twin of tsdf_insert (include/viso_hip.h, "TSDF retract"): the same sums out of the voxel `key`, in the table's own
+// modular arithmetic, through a read-only probe: no slot is claimed and no key written.  A voxel that is not in the table: its
+// updates to *missing; a weight that the take brings below zero (the value its own atomic returns is smaller than what it takes):
+// *under set.  undo: the sums go back in, and neither is noted.
+__device__ __forceinline__ void tsdf_take(const TsdfTable& t, unsigned long long key, uint32_t updates, uint32_t weight, long long sum, bool undo,
+                                          uint32_t* missing, bool* under, unsigned long long* gray_at = nullptr, unsigned long long gray = 0) {
+    uint32_t slot;
+    if (voxel_find(t.head.keys, t.head.mask, key, &slot)) {
+        const uint32_t old = atomicAdd(t.weight + slot, undo ? weight : 0u - weight);
+        atomicAdd(t.sum + slot, undo ? (unsigned long long)sum : 0ull - (unsigned long long)sum);
+        if (gray_at) atomicAdd(gray_at + slot, undo ? gray : 0ull - gray);
+        if (!undo && old < weight) *under = true;
+    } else if (!undo) {
+        *missing += updates;
+    }
+}
+
 struct TsdfFuseArgs {
     VoxelFuseArgs v;
     int trunc;
@@ -108,10 +132,13 @@ __device__ __forceinline__ uint32_t tsdf_run_sum(uint32_t v, int lane, uint32_t 
 
 // The body of the fuse kernels.  GRAY: the pixel's intensity (image, ifs) is carried along, and a run's head lane adds the run's
 // sum of intensities to gray[slot] as well; without it, none of the three is read.  EXT: the rules of "TSDF fuse options": the
-// loop starts 2 o.carve samples earlier, and a pixel's updates carry its weight w; without it, o is not read.
-template <bool GRAY, bool EXT>
+// loop starts 2 o.carve samples earlier, and a pixel's updates carry its weight w; without it, o is not read.  TAKE: the march of a
+// retract ("TSDF retract"): a run's head lane hands the run's sums to tsdf_take and not to tsdf_insert, the wave's counters fall by
+// what the fuse adds, and what the wave could not place or took below zero goes to VOXEL_W_MISSING and VOXEL_W_UNDERFLOW, one
+// atomic per wave and word that is not zero; undo: the same march puts everything back.  Without TAKE, undo is not read.
+template <bool GRAY, bool EXT, bool TAKE = false>
 __device__ __forceinline__ void tsdf_fuse_body(const TsdfFuseArgs& a, const TsdfFuseOpts& o, const uint8_t* image, size_t ifs,
-                                               unsigned long long* gray) {
+                                               unsigned long long* gray, bool undo = false) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     const int lane = threadIdx.x & 63, fr = blockIdx.y;
     double X = 0.0, Y = 0.0, Z = 1.0;
@@ -154,6 +181,14 @@ __device__ __forceinline__ void tsdf_fuse_body(const TsdfFuseArgs& a, const Tsdf
     const double dlim = (double)lim;
     unsigned long long prev = MAP_EMPTY;            // the voxel of the pixel's previous inserted sample
     unsigned long long n_upd = 0, n_oor = 0, n_occ = 0;
+    uint32_t n_miss = 0;                            // TAKE: the updates of this lane's runs that found no voxel (at most 64 a sample)
+    bool under = false;                             //       one of this lane's runs took a weight below zero
+    // a run's sums from its head lane into the table, or with TAKE out of it
+    auto put = [&](unsigned long long key, uint32_t updates, uint32_t weight, long long sum, bool* claimed, unsigned long long* gray_at,
+                   unsigned long long run_gray) {
+        if constexpr (TAKE) tsdf_take(a.t, key, updates, weight, sum, undo, &n_miss, &under, gray_at, run_gray);
+        else tsdf_insert(a.t, key, updates, weight, sum, claimed, gray_at, run_gray);
+    };
     for (int j = j_first; j <= 2 * a.trunc; ++j) {   // the same j in every lane
         unsigned long long key = MAP_EMPTY;
         uint32_t qb = 0;                            // q + T 1024
@@ -206,20 +241,30 @@ __device__ __forceinline__ void tsdf_fuse_body(const TsdfFuseArgs& a, const Tsdf
             const uint32_t rq = tsdf_run_sum(w * qb, lane, len);
             const uint32_t rg = GRAY ? tsdf_run_sum(w * pix, lane, len) : 0u;
             if (head && key != MAP_EMPTY)
-                tsdf_insert(a.t, key, len, rw, (long long)rq - (long long)rw * lim, &claimed, GRAY ? gray : nullptr, rg);
+                put(key, len, rw, (long long)rq - (long long)rw * lim, &claimed, GRAY ? gray : nullptr, rg);
         } else {
             const uint32_t rq = tsdf_run_sum(qb, lane, len);                      // the run's sum, in its head lane
             if (GRAY) {
                 // the run's sum of intensities by a second scan of the same shape (64 x 255 < 2^14)
                 const uint32_t rg = tsdf_run_sum(key != MAP_EMPTY ? pix : 0u, lane, len);
-                if (head && key != MAP_EMPTY) tsdf_insert(a.t, key, len, len, (long long)rq - (long long)len * lim, &claimed, gray, rg);
+                if (head && key != MAP_EMPTY) put(key, len, len, (long long)rq - (long long)len * lim, &claimed, gray, rg);
             } else {
-                if (head && key != MAP_EMPTY) tsdf_insert(a.t, key, len, len, (long long)rq - (long long)len * lim, &claimed);
+                if (head && key != MAP_EMPTY) put(key, len, len, (long long)rq - (long long)len * lim, &claimed, nullptr, 0);
             }
         }
         n_occ += __popcll(__ballot(claimed));
     }
-    voxel_count_wave(a.t.head, blockIdx.x + blockIdx.y, lane, __popcll(pm), n_upd, n_oor, n_occ);
+    if constexpr (TAKE) {
+        // the counters fall (undo: rise again) by what the fuse adds to them, modulo 2^64 in a set: their sum over the sets is exact
+        const unsigned long long sg = undo ? 1ull : ~0ull;
+        voxel_count_wave(a.t.head, blockIdx.x + blockIdx.y, lane, sg * (unsigned long long)__popcll(pm), sg * n_upd, sg * n_oor, 0);
+        const uint32_t missing = viso_wave_scan(n_miss);   // lane 63: the wave's (at most 64 a sample of at most 2 (8 + 1024) + 1: 32 bits hold it)
+        const unsigned long long um = __ballot(under);
+        if (lane == 63 && missing) atomicAdd(a.t.head.words + VOXEL_W_MISSING, (unsigned long long)missing);
+        if (lane == 0 && um) atomicAdd(a.t.head.words + VOXEL_W_UNDERFLOW, (unsigned long long)__popcll(um));
+    } else {
+        voxel_count_wave(a.t.head, blockIdx.x + blockIdx.y, lane, __popcll(pm), n_upd, n_oor, n_occ);
+    }
 }
 
 __global__ __launch_bounds__(256) void tsdf_fuse_kernel(TsdfFuseArgs a) { tsdf_fuse_body<false, false>(a, TsdfFuseOpts{}, nullptr, 0, nullptr); }
@@ -232,6 +277,19 @@ __global__ __launch_bounds__(256) void tsdf_carve_fuse_kernel(TsdfFuseArgs a, Ts
 }
 __global__ __launch_bounds__(256) void tsdf_gray_carve_fuse_kernel(TsdfGrayFuseArgs g, TsdfFuseOpts o) {
     tsdf_fuse_body<true, true>(g.a, o, g.image, g.ifs, g.gray);
+}
+// The four take kernels of a retract: the same four marches with TAKE; undo: a runtime sign, one kernel for both directions.
+__global__ __launch_bounds__(256) void tsdf_take_kernel(TsdfFuseArgs a, bool undo) {
+    tsdf_fuse_body<false, false, true>(a, TsdfFuseOpts{}, nullptr, 0, nullptr, undo);
+}
+__global__ __launch_bounds__(256) void tsdf_gray_take_kernel(TsdfGrayFuseArgs g, bool undo) {
+    tsdf_fuse_body<true, false, true>(g.a, TsdfFuseOpts{}, g.image, g.ifs, g.gray, undo);
+}
+__global__ __launch_bounds__(256) void tsdf_carve_take_kernel(TsdfFuseArgs a, TsdfFuseOpts o, bool undo) {
+    tsdf_fuse_body<false, true, true>(a, o, nullptr, 0, nullptr, undo);
+}
+__global__ __launch_bounds__(256) void tsdf_gray_carve_take_kernel(TsdfGrayFuseArgs g, TsdfFuseOpts o, bool undo) {
+    tsdf_fuse_body<true, true, true>(g.a, o, g.image, g.ifs, g.gray, undo);
 }
 
 // The intensity of the point on the edge between the voxels a and b (include/viso_hip.h, "TSDF intensity"): t is the mesh's and the
@@ -700,6 +758,15 @@ struct TsdfPayload {
         t().weight[a] = 0u; t().sum[a] = 0ull;
         if constexpr (GRAY) tab.gray[a] = 0ull;
     }
+    // a retract's check: nothing but the weight in the slot; and, of a slot of weight w >= 1, what tsdf_add_entries asks of an entry
+    // (lim = T 1024 <= 2^13 and w < 2^32: the products fit 64 bits)
+    __device__ __forceinline__ bool is_zero(uint32_t a) const {
+        if constexpr (GRAY) return t().sum[a] == 0ull && tab.gray[a] == 0ull; else return t().sum[a] == 0ull;
+    }
+    __device__ __forceinline__ bool within(uint32_t a, uint32_t w, long long lim) const {
+        const long long s = (long long)t().sum[a], m = lim * (long long)w;
+        if constexpr (GRAY) return s <= m && s >= -m && tab.gray[a] <= 255ull * w; else return s <= m && s >= -m;
+    }
     __device__ __forceinline__ void move(uint32_t a, uint32_t b) const {
         t().weight[b] = t().weight[a]; t().sum[b] = t().sum[a];
         if constexpr (GRAY) tab.gray[b] = tab.gray[a];
@@ -765,6 +832,26 @@ static VoxelFuseLaunch tsdf_fuse_launch(viso_tsdf* t, size_t ifs) {
         } else {
             if (ext) hipLaunchKernelGGL(tsdf_carve_fuse_kernel, grid, dim3(256), 0, s, a, o);
             else hipLaunchKernelGGL(tsdf_fuse_kernel, grid, dim3(256), 0, s, a);
+        }
+    };
+}
+
+// The same for a retract's take (undo: with the sums going back in): the take kernel of the fuse kernel that tsdf_fuse_launch would
+// pick, with the map's options as they are when the group is launched.
+static VoxelFuseLaunch tsdf_take_launch(viso_tsdf* t, size_t ifs, bool undo) {
+    return [t, ifs, undo](const VoxelFuseArgs& v, const uint8_t* d_image, dim3 grid, hipStream_t s) {
+        TsdfFuseArgs a;
+        a.v = v; a.trunc = t->p.trunc_voxels; a.s = t->s; a.h = t->hs; a.t = t->t;
+        const TsdfFuseOpts o = t->o;
+        const bool ext = o.carve > 0 || o.weight_shift >= 0;
+        if (d_image) {
+            TsdfGrayFuseArgs g;
+            g.a = a; g.image = d_image; g.ifs = ifs; g.gray = t->gray;
+            if (ext) hipLaunchKernelGGL(tsdf_gray_carve_take_kernel, grid, dim3(256), 0, s, g, o, undo);
+            else hipLaunchKernelGGL(tsdf_gray_take_kernel, grid, dim3(256), 0, s, g, undo);
+        } else {
+            if (ext) hipLaunchKernelGGL(tsdf_carve_take_kernel, grid, dim3(256), 0, s, a, o, undo);
+            else hipLaunchKernelGGL(tsdf_take_kernel, grid, dim3(256), 0, s, a, undo);
         }
     };
 }
@@ -876,6 +963,44 @@ extern "C" int viso_tsdf_fuse_gray(viso_tsdf* t, const int16_t* disp, const uint
     if (!image) { viso_set_error("%s: bad argument (a non-null image)", where); return VISO_ERR_ARG; }
     const DispView v = disp_view_host(disp, image, rows, cols, param, pose_or_null);
     return voxel_fuse(where, g_tsdfs, t, v, tsdf_fuse_launch(t, v.ifs));
+}
+
+// ---- retract and move (include/viso_hip.h, "TSDF retract") --------------------------------------------------------
+// viso_tsdf_retract*, viso_tsdf_move* and the batch's two over the view v of the frames as they were fused (a gray map's with their
+// images); move: fused again at poses_new ([v.n][16] or null) behind the retract.  The kind is checked as the fuse calls check it.
+int tsdf_retract_resident(const char* where, viso_tsdf* t, const DispView& v, bool move, const double* poses_new, uint64_t* report) {
+    if (!tsdf_kind_ok(where, t, v.image != nullptr)) return VISO_ERR_ARG;
+    static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "the report's words");
+    unsigned long long* rep = reinterpret_cast<unsigned long long*>(report);
+    const VoxelRetractLaunches L = {tsdf_take_launch(t, v.ifs, false), tsdf_take_launch(t, v.ifs, true), tsdf_fuse_launch(t, v.ifs),
+                                    (long long)t->p.trunc_voxels * 1024};
+    if (v.image) return voxel_retract(where, g_tsdfs, t, v, move, poses_new, L, tsdf_payload<true>(t), rep);
+    return voxel_retract(where, g_tsdfs, t, v, move, poses_new, L, tsdf_payload<false>(t), rep);
+}
+
+extern "C" int viso_tsdf_retract(viso_tsdf* t, const int16_t* disp, int rows, int cols, const viso_param* param, const double* pose_or_null,
+                                 uint64_t report_or_null[6]) {
+    return tsdf_retract_resident("viso_tsdf_retract", t, disp_view_host(disp, nullptr, rows, cols, param, pose_or_null), false, nullptr, report_or_null);
+}
+extern "C" int viso_tsdf_move(viso_tsdf* t, const int16_t* disp, int rows, int cols, const viso_param* param, const double* pose_old_or_null,
+                              const double* pose_new_or_null, uint64_t report_or_null[6]) {
+    return tsdf_retract_resident("viso_tsdf_move", t, disp_view_host(disp, nullptr, rows, cols, param, pose_old_or_null), true, pose_new_or_null,
+                                 report_or_null);
+}
+// the gray twins: the image the frame was fused with
+static int tsdf_retract_gray(const char* where, viso_tsdf* t, const int16_t* disp, const uint8_t* image, int rows, int cols, const viso_param* param,
+                             const double* pose, bool move, const double* pose_new, uint64_t* report) {
+    if (!tsdf_kind_ok(where, t, true)) return VISO_ERR_ARG;
+    if (!image) { viso_set_error("%s: bad argument (a non-null image)", where); return VISO_ERR_ARG; }
+    return tsdf_retract_resident(where, t, disp_view_host(disp, image, rows, cols, param, pose), move, pose_new, report);
+}
+extern "C" int viso_tsdf_retract_gray(viso_tsdf* t, const int16_t* disp, const uint8_t* image, int rows, int cols, const viso_param* param,
+                                      const double* pose_or_null, uint64_t report_or_null[6]) {
+    return tsdf_retract_gray("viso_tsdf_retract_gray", t, disp, image, rows, cols, param, pose_or_null, false, nullptr, report_or_null);
+}
+extern "C" int viso_tsdf_move_gray(viso_tsdf* t, const int16_t* disp, const uint8_t* image, int rows, int cols, const viso_param* param,
+                                   const double* pose_old_or_null, const double* pose_new_or_null, uint64_t report_or_null[6]) {
+    return tsdf_retract_gray("viso_tsdf_move_gray", t, disp, image, rows, cols, param, pose_old_or_null, true, pose_new_or_null, report_or_null);
 }
 
 // the checks of an entry that both kinds share

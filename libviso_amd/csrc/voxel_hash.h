@@ -5,7 +5,9 @@
 // their own (a workgroup adds to set blockIdx & 255, one atomic per wave and counter; summed on the host) and a few single words.
 // What is in a slot is the kind's payload P (below); the kernels that only list, zero or add to slots are here once for every kind,
 // templates over P: voxel_compact_kernel, voxel_clear_kernel, voxel_add_entries_kernel and the three of an eviction
-// (include/viso_hip.h, "Map eviction").  Only those three ever write a tombstone, and none is left when they are done.
+// (include/viso_hip.h, "Map eviction"), and the check and the mark of a retract ("TSDF retract"), whose
+// tombstones the eviction's rebuild and sweep take away.  Only the two marks and the rebuild ever write a tombstone, and none is left
+// when a call is done.
 #ifndef VISO_VOXEL_HASH_H_
 #define VISO_VOXEL_HASH_H_
 #include "common.h"
@@ -21,10 +23,14 @@
 #define VOXEL_ST_UPDATES 1              // the voxel map's inserts, the TSDF map's updates
 #define VOXEL_ST_OOR 2
 #define VOXEL_ST_OCC 3
+#define VOXEL_ST_FREED 4                // the slots that the checks of the retracts since the last clear found freed / bad: running counts,
+#define VOXEL_ST_BAD 5                  // of which a call takes the difference; no getter reads them, and they are no part of the map
 #define VOXEL_W_OUT 0                   // words: an extraction's list length
 #define VOXEL_W_DROPPED 1               //        points / updates that found no slot
 #define VOXEL_W_TRIS 2                  //        the mesh's triangle list length (VOXEL_W_OUT: its vertex list's)
-#define VOXEL_WORDS 3                   // how many of them there are; the table's allocation has room for 32 (voxel_create)
+#define VOXEL_W_MISSING 3               //        a retract's updates whose voxel is not in the table
+#define VOXEL_W_UNDERFLOW 4             //        not zero: a retract took a voxel's weight below zero (how many atomics saw it: scheduling)
+#define VOXEL_WORDS 5                   // how many of them there are; the table's allocation has room for 32 (voxel_create)
 #define VOXEL_MAX_PIXELS 0x7fffffffll
 #define VOXEL_GROUP 16384               // frames along a grid's y
 
@@ -170,6 +176,9 @@ __device__ __forceinline__ bool voxel_list_position(const VoxelTable& t, bool ta
 //   key(entry), add(slot, entry) an entry's key; the entry's atomic adds to the slot a probe gave it
 //   units(entry)                 what the entry stands for (its count / weight): added to VOXEL_W_DROPPED when it finds no slot,
 //                                else to the counter P::UNITS_STAT; with P::ENTRY_STAT every entry also counts one in VOXEL_ST_UPDATES
+// and, only of a kind that can be retracted from (the TSDF map's two; the voxel map has neither):
+//   is_zero(slot)                every payload word of the slot but its threshold word is 0
+//   within(slot, w, bound)       the slot, of threshold word w >= 1, is one that valid entries of the kind add up to
 
 // One thread per slot (the grid covers the slots exactly: at least 1024 of them): the occupied slots whose threshold word is at
 // least `min` to a dense list, one atomic per wave for the positions.  out == null: only their number.
@@ -299,5 +308,40 @@ __global__ __launch_bounds__(256) void voxel_evict_sweep_kernel(VoxelTable t, P 
     if (t.keys[slot] != MAP_TOMB) return;
     p.zero(slot);
     t.keys[slot] = MAP_EMPTY;
+}
+
+// ---- retract: the slots whose payload a take brought back to zero leave the table (include/viso_hip.h, "TSDF retract") -----------
+#define VOXEL_SLOT_KEEP 0    // empty, or live and within the kind's bounds
+#define VOXEL_SLOT_FREED 1   // live, its threshold word 0 and every other payload word 0: what is left of a voxel all of whose updates were taken
+#define VOXEL_SLOT_BAD 2     // live and not a slot that entries of the kind add up to: the threshold word 0 beside another word that is not,
+                             // or a payload beyond the kind's bounds
+
+// what a retract's check makes of a slot; bound: what P::within compares with
+template <class P>
+__device__ __forceinline__ int voxel_slot_state(const VoxelTable& t, const P& p, uint32_t slot, long long bound) {
+    if (t.keys[slot] >= MAP_TOMB) return VOXEL_SLOT_KEEP;
+    const uint32_t w = p.threshold(slot);
+    if (!w) return p.is_zero(slot) ? VOXEL_SLOT_FREED : VOXEL_SLOT_BAD;
+    return p.within(slot, w, bound) ? VOXEL_SLOT_KEEP : VOXEL_SLOT_BAD;
+}
+
+// The check, one thread per slot (the grid covers the slots exactly), reads the table only: the freed and the bad slots counted in
+// VOXEL_ST_FREED and VOXEL_ST_BAD of the block's set, one atomic per wave and counter that is not zero.  (Not in one word, as the
+// extractions count: a retract of many frames frees a slot in most waves, and their atomics on one address would be the call.)
+template <class P>
+__global__ __launch_bounds__(256) void voxel_retract_check_kernel(VoxelTable t, P p, long long bound) {
+    const int state = voxel_slot_state(t, p, blockIdx.x * 256 + threadIdx.x, bound);
+    const unsigned long long freed = __ballot(state == VOXEL_SLOT_FREED), bad = __ballot(state == VOXEL_SLOT_BAD);
+    if ((threadIdx.x & 63) != 0) return;
+    if (freed) atomicAdd(voxel_stat(t, blockIdx.x, VOXEL_ST_FREED), (unsigned long long)__popcll(freed));
+    if (bad) atomicAdd(voxel_stat(t, blockIdx.x, VOXEL_ST_BAD), (unsigned long long)__popcll(bad));
+}
+
+// The mark, one thread per slot, behind a check that found no bad slot: the key of every freed slot to MAP_TOMB.
+// voxel_evict_rebuild_kernel and voxel_evict_sweep_kernel follow before anything else can return.
+template <class P>
+__global__ __launch_bounds__(256) void voxel_retract_mark_kernel(VoxelTable t, P p, long long bound) {
+    const uint32_t slot = blockIdx.x * 256 + threadIdx.x;
+    if (voxel_slot_state(t, p, slot, bound) == VOXEL_SLOT_FREED) t.keys[slot] = MAP_TOMB;
 }
 #endif /* VISO_VOXEL_HASH_H_ */

@@ -3,7 +3,7 @@
 // of its live handles, and passes in its payload (voxel_hash.h) for the shared kernels and the launches of its own kernels as
 // callables.  The rules that every kind must keep are here and in voxel_host.hip, once: no handle is dereferenced before its
 // registry has answered for it; staging is freed only behind a synchronise; dropped updates become the sticky overflow mark; an
-// eviction leaves no tombstone behind.  Two of them are types, and every call on a map goes through them:
+// eviction and a retract leave no tombstone behind (voxel_finish_removal), and a refused retract leaves every word as it was.  Two of them are types, and every call on a map goes through them:
 //   VoxelSession  how a call gets at a map: the registry's answer, the live context, the map's device current (voxel_enter, which
 //                 nothing else calls), then the map's mutex for as long as the session lives, then, unless the call asks for a map in
 //                 any state (clear, stats, the option calls), the refusal of an overflowed map.  Nothing else locks VoxelHost::mu.
@@ -143,6 +143,23 @@ int voxel_clear(const char* where, VoxelRegistry& reg, const void* handle, const
 // and argument checks, the staging of the poses and of a host view's map and image, the groups of frames, each started by `launch`
 // with its first image (or null), and the wait that finds a full table.
 int voxel_fuse(const char* where, VoxelRegistry& reg, const void* handle, const DispView& v, const VoxelFuseLaunch& launch);
+// The steps voxel_fuse is made of, for the calls that march the same frames with other launches (voxel_retract):
+//   voxel_fuse_args     what is checked before a device is touched: the handle, the view's map and sizes, finite poses and calibration
+//   voxel_fuse_stage    under the call's session (opened in ANY_STATE): the batch's context, the overflow refusal, then the staging of
+//                       the poses and of a host view's map and image; *f: where the frames lie on the device
+//   voxel_fuse_restage  other poses [n][16] (null: none) for the same frames, behind the launches that read the first ones
+//   voxel_fuse_groups   the groups of VOXEL_GROUP frames, each started by `launch`; v.poses says whether the groups have poses
+struct VoxelFrames {
+    VoxelFuseArgs a;                               // all but disp and poses, which a group sets
+    const int16_t* disp; const uint8_t* image;     // the first frame's map and image (or null) on the device
+    std::vector<double> rows12;                    // what the copy of the poses reads: alive until the stream has been waited for
+};
+int voxel_fuse_args(const char* where, VoxelRegistry& reg, const void* handle, const DispView& v);
+int voxel_fuse_stage(const VoxelSession& ses, VoxelRegistry& reg, const DispView& v, VoxelFrames* f);
+int voxel_fuse_restage(const VoxelSession& ses, const double* poses, int n, VoxelFrames* f);
+int voxel_fuse_groups(VoxelHost* h, const DispView& v, const VoxelFrames& f, const VoxelFuseLaunch& launch);
+// n of the table's words from VOXEL_W_`first` on, behind everything on the map's stream.  h is entered and locked.
+int voxel_read_words(VoxelHost* h, int first, int n, unsigned long long* out);
 // behind a call's launches: waits for them and turns dropped points / updates into the overflow mark.  h is entered and locked.
 int voxel_finish(const char* where, VoxelHost* h);
 // viso_*_add_entries behind the handle check and the validation of the n entries
@@ -229,6 +246,29 @@ bool voxel_evict_args(const char* where, VoxelRegistry& reg, const void* handle,
 // occupied counters; voxel_evict_put_stats: the same block back with `less` fewer occupied slots, every other counter as it was.
 int voxel_evict_get_stats(VoxelHost* h, std::vector<unsigned long long>& stats, unsigned long long* occupied);
 int voxel_evict_put_stats(VoxelHost* h, std::vector<unsigned long long>& stats, unsigned long long less);
+unsigned long long voxel_stat_sum(const std::vector<unsigned long long>& stats, int which);   // counter VOXEL_ST_`which` over the sets
+
+// The second half of every call that takes voxels out of a table (an eviction, a retract): behind it no tombstone is left and every
+// survivor is where a probe finds it.  A table with an empty slot: the leaving voxels' keys are tombstones by now; the rebuild pass
+// moves every survivor up, the sweep empties the tombstones.  A table without one (`full`) has no cluster head to start a rebuild
+// from: d_keep[n_keep] lists its survivors, and it goes through the clear and add_entries.  Either way the statistics `stats`, as
+// voxel_evict_get_stats read them, go back with `less` fewer occupied slots.  h is entered and locked; the caller waits for the
+// stream before `stats` and d_keep go.
+template <class P>
+int voxel_finish_removal(VoxelHost* h, const P& p, bool full, const typename P::Entry* d_keep, unsigned long long n_keep,
+                         std::vector<unsigned long long>& stats, unsigned long long less) {
+    hipStream_t s = h->ctx->stream;
+    if (!full) {
+        const dim3 grid((h->head.mask + 1u) / 256u);
+        hipLaunchKernelGGL(voxel_evict_rebuild_kernel<P>, grid, dim3(256), 0, s, h->head, p);
+        hipLaunchKernelGGL(voxel_evict_sweep_kernel<P>, grid, dim3(256), 0, s, h->head, p);
+    } else {
+        voxel_start_clear(p, s);
+        if (n_keep) voxel_start_add_entries(p, d_keep, n_keep, s);
+    }
+    HIP_TRY(hipGetLastError());
+    return voxel_evict_put_stats(h, stats, less);
+}
 
 // viso_*_evict_count (list.count_only) and viso_*_evict, whole.  A first pass counts the voxels outside the box; a second one lists them
 // (list.out null: lists nothing) and turns their keys into tombstones, the rebuild pass moves every survivor to where a probe
@@ -269,28 +309,104 @@ int voxel_evict(const char* where, VoxelRegistry& reg, const void* handle, const
     Item* d_keep = d.as<Item>(b_out);
     hipStream_t s = ses.stream();
     if (!full) {
-        VISO_TRY(voxel_pass(h, mark(VOXEL_EVICT_LIST, d_out, c), &c2));
-        // tombstones are in the table: both passes follow before anything else can return
-        hipLaunchKernelGGL(voxel_evict_rebuild_kernel<P>, grid, dim3(256), 0, s, head, p);
-        hipLaunchKernelGGL(voxel_evict_sweep_kernel<P>, grid, dim3(256), 0, s, head, p);
-        HIP_TRY(hipGetLastError());
+        VISO_TRY(voxel_pass(h, mark(VOXEL_EVICT_LIST, d_out, c), &c2));   // tombstones are in the table: voxel_finish_removal follows
     } else {
         if (d_out) VISO_TRY(voxel_pass(h, mark(VOXEL_EVICT_PEEK, d_out, c), &c2));
         else c2 = c;
         unsigned long long k2 = 0;
         if (n_keep) VISO_TRY(voxel_pass(h, mark(VOXEL_EVICT_KEEP, d_keep, n_keep), &k2));
         if (k2 != n_keep) c2 = ~0ull;
-        if (c2 == c) {
-            voxel_start_clear(p, s);
-            if (n_keep) voxel_start_add_entries(p, d_keep, n_keep, s);
-            HIP_TRY(hipGetLastError());
-        }
     }
-    if (c2 == c) VISO_TRY(voxel_evict_put_stats(h, stats, c));
+    if (!full || c2 == c) VISO_TRY(voxel_finish_removal(h, p, full, d_keep, n_keep, stats, c2));
     if (d_out) HIP_TRY(hipMemcpyAsync(list.out, d_out, b_out, hipMemcpyDeviceToHost, s));
     VISO_TRY(d.release());
     if (c2 != c) { viso_set_error("%s: the table changed between the two passes", where); return VISO_ERR_HIP; }   // (the map's lock rules it out)
     if (list.out) std::sort(list.out, list.out + c, [](const Item& x, const Item& y) { return voxel_item_less(x, y); });
     return VISO_OK;
+}
+
+// ---- retract (include/viso_hip.h, "TSDF retract"; the check and the mark are voxel_hash.h's, the take is the kind's) --------------------
+// the six words of the public report, in its order
+struct VoxelRetractReport { unsigned long long n_points, n_updates, n_missing, n_underflow, n_inconsistent, n_freed; };
+// The kind's launches over a group of frames: the take (the fuse's updates subtracted, through read-only probes; what it cannot
+// place and what it takes below zero to VOXEL_W_MISSING and VOXEL_W_UNDERFLOW), the same with the sign flipped, and the fuse itself
+// for a move.  bound: what the kind's payload compares with in P::within.
+struct VoxelRetractLaunches { VoxelFuseLaunch take, undo, fuse; long long bound; };
+
+// viso_*_retract and viso_*_move, whole, over the view v of the frames as they were fused; move: they are then fused again at
+// poses_new ([v.n][16], or null for none), under the same session.  What voxel_fuse checks, in its order; then the take, the
+// check over the slots, and either the commit (the freed slots leave the table as an eviction's do: voxel_finish_removal) or the
+// undo, which leaves every word of the table as it was and returns VISO_ERR_ARG.  *report (or null) is filled either way.
+template <class P>
+int voxel_retract(const char* where, VoxelRegistry& reg, const void* handle, const DispView& v, bool move, const double* poses_new,
+                  const VoxelRetractLaunches& L, const P& p, unsigned long long* report) {
+    using Item = typename P::Entry;
+    DispView v2 = v;
+    v2.poses = poses_new;
+    VISO_TRY(voxel_fuse_args(where, reg, handle, v));
+    if (move) VISO_TRY(voxel_fuse_args(where, reg, handle, v2));
+    VoxelSession ses(where, reg, handle, VoxelSession::ANY_STATE);   // the overflow refusal comes behind the context's
+    VISO_TRY(ses.status());
+    VoxelHost* h = ses.host();
+    hipStream_t s = ses.stream();
+    VoxelFrames f;
+    VISO_TRY(voxel_fuse_stage(ses, reg, v, &f));
+    const size_t slots = (size_t)h->head.mask + 1;
+    const dim3 grid((unsigned)(slots / 256));
+    const VoxelTable head = h->head;
+    const long long bound = L.bound;
+    // the take: the three counters fall on the device, what they fell by is the report's
+    std::vector<unsigned long long> before, stats;   // (before the block: the copy that puts them back reads them until its wait)
+    unsigned long long occupied = 0, words[2] = {0, 0};
+    static_assert(VOXEL_W_UNDERFLOW == VOXEL_W_MISSING + 1, "the two words of a retract are read as one");
+    HIP_TRY(hipMemsetAsync(h->head.words + VOXEL_W_MISSING, 0, sizeof(words), s));
+    VISO_TRY(voxel_evict_get_stats(h, before, &occupied));
+    VISO_TRY(voxel_fuse_groups(h, v, f, L.take));
+    // the check, behind the take on the stream: its two counts run on in the sets, like the counters
+    hipLaunchKernelGGL(voxel_retract_check_kernel<P>, grid, dim3(256), 0, s, head, p, bound);
+    HIP_TRY(hipGetLastError());
+    VISO_TRY(voxel_evict_get_stats(h, stats, &occupied));
+    VISO_TRY(voxel_read_words(h, VOXEL_W_MISSING, 2, words));
+    VoxelRetractReport rep{};
+    rep.n_points = voxel_stat_sum(before, VOXEL_ST_POINTS) - voxel_stat_sum(stats, VOXEL_ST_POINTS);
+    rep.n_updates = voxel_stat_sum(before, VOXEL_ST_UPDATES) - voxel_stat_sum(stats, VOXEL_ST_UPDATES);
+    rep.n_freed = voxel_stat_sum(stats, VOXEL_ST_FREED) - voxel_stat_sum(before, VOXEL_ST_FREED);
+    rep.n_inconsistent = voxel_stat_sum(stats, VOXEL_ST_BAD) - voxel_stat_sum(before, VOXEL_ST_BAD);
+    rep.n_missing = words[0]; rep.n_underflow = words[1];
+    static_assert(sizeof(rep) == 6 * sizeof(unsigned long long), "the report is six words");
+    if (report) std::copy(&rep.n_points, &rep.n_points + 6, report);
+    if (rep.n_missing || rep.n_underflow || rep.n_inconsistent) {
+        // the undo: the same launches find the same slots (no key was written), and the modular adds restore every word
+        VISO_TRY(voxel_fuse_groups(h, v, f, L.undo));
+        HIP_TRY(hipStreamSynchronize(s));
+        viso_set_error("%s: these are not frames of this %s as they were fused: n_missing %llu (updates whose voxel is not in the table), "
+                       "n_underflow %llu (not zero: a weight fell below zero), n_inconsistent %llu (voxels left beyond their bounds); the %s is unchanged",
+                       where, reg.kind.noun, rep.n_missing, rep.n_underflow, rep.n_inconsistent, reg.kind.noun);
+        return VISO_ERR_ARG;
+    }
+    if (rep.n_freed) {
+        const bool full = occupied >= slots;
+        const unsigned long long n_keep = full ? slots - rep.n_freed : 0;
+        VoxelScratch d(ses, (size_t)n_keep * sizeof(Item), "the list");   // a full table's survivors
+        VISO_TRY(d.status());
+        unsigned long long c2 = rep.n_freed;
+        if (!full) {
+            hipLaunchKernelGGL(voxel_retract_mark_kernel<P>, grid, dim3(256), 0, s, head, p, bound);   // tombstones are in the table:
+            HIP_TRY(hipGetLastError());                                                                // voxel_finish_removal follows
+        } else if (n_keep) {
+            unsigned long long k2 = 0;   // the survivors are the slots of threshold word >= 1: the getters' list
+            VISO_TRY(voxel_pass(h, [&](hipStream_t st) {
+                hipLaunchKernelGGL(voxel_compact_kernel<P>, grid, dim3(256), 0, st, p, 1u, d.as<Item>(), n_keep);
+            }, &k2));
+            if (k2 != n_keep) c2 = ~0ull;
+        }
+        if (!full || c2 == rep.n_freed) VISO_TRY(voxel_finish_removal(h, p, full, d.as<Item>(), n_keep, stats, c2));
+        VISO_TRY(d.release());
+        if (c2 != rep.n_freed) { viso_set_error("%s: the table changed between the two passes", where); return VISO_ERR_HIP; }   // (the map's lock rules it out)
+    }
+    if (!move) return VISO_OK;
+    VISO_TRY(voxel_fuse_restage(ses, poses_new, v.n, &f));
+    VISO_TRY(voxel_fuse_groups(h, v2, f, L.fuse));
+    return voxel_finish(where, h);
 }
 #endif /* VISO_VOXEL_HOST_H_ */

@@ -1,5 +1,6 @@
 // voxel_host.hip — the host side of the shared table layer (voxel_host.h): the registry of live handles, the life of a table, a
-// call's scratch block, the staging (the map, the poses and, where a kind fuses one, the image) and the group loop of a fuse,
+// call's scratch block, the staging (the map, the poses and, where a kind fuses one, the image) and the group loop of a fuse
+// (as the steps that a retract takes as well),
 // the wait behind a call's launches, the pass of an extraction, the staging and the output buffer of a render, the staging and the sums of a linearise, the read-back of the
 // statistics, and of an eviction the argument checks, the statistics' round trip and the box around a point.
 // No kernel is here: a kind passes in the launches of its own kernels, and the templates of voxel_host.h start the shared ones.
@@ -189,37 +190,67 @@ static int voxel_stage_poses(const char* where, VoxelHost* h, const double* pose
     return VISO_OK;
 }
 
-int voxel_fuse(const char* where, VoxelRegistry& reg, const void* handle, const DispView& v, const VoxelFuseLaunch& launch) {
+int voxel_fuse_args(const char* where, VoxelRegistry& reg, const void* handle, const DispView& v) {
     if (!voxel_known(reg, handle)) return voxel_not_live(where, reg);
     if (!v.ctx && (!v.disp || v.rows <= 0 || v.cols <= 0)) { viso_set_error("%s: bad argument (non-null map and calibration, sizes > 0)", where); return VISO_ERR_ARG; }
-    int r;
-    if ((r = voxel_fuse_check(where, v)) < 0) return r;
-    VoxelSession ses(where, reg, handle, VoxelSession::ANY_STATE);   // the overflow refusal comes behind the context's
-    VISO_TRY(ses.status());
+    return voxel_fuse_check(where, v);
+}
+
+int voxel_fuse_stage(const VoxelSession& ses, VoxelRegistry& reg, const DispView& v, VoxelFrames* f) {
+    const char* where = ses.where();
     VoxelHost* h = ses.host();
     if (v.ctx && h->ctx != v.ctx) { viso_set_error("%s: the %s and the batch must share a context", where, reg.kind.noun); return VISO_ERR_ARG; }
     VISO_TRY(ses.refuse_overflowed());
+    int r;
     const size_t px = v.px();
-    const int16_t* disp = v.disp;
-    const uint8_t* image = v.image;
+    f->disp = v.disp;
+    f->image = v.image;
     if (!v.ctx) {   // one host map, and one host image if there is one, through the staging
-        if ((r = voxel_stage_map(where, h, v.disp, px, &disp)) < 0) return r;
-        if (v.image && (r = voxel_stage_image(where, h, v.image, px, &image)) < 0) return r;
+        if ((r = voxel_stage_map(where, h, v.disp, px, &f->disp)) < 0) return r;
+        if (v.image && (r = voxel_stage_image(where, h, v.image, px, &f->image)) < 0) return r;
     }
-    hipStream_t s = h->ctx->stream;
-    std::vector<double> rows12;   // alive until voxel_finish has waited for the copy that reads it
-    if (v.poses && (r = voxel_stage_poses(where, h, v.poses, v.n, rows12)) < 0) return r;
-    VoxelFuseArgs a;
+    if (v.poses && (r = voxel_stage_poses(where, h, v.poses, v.n, f->rows12)) < 0) return r;
+    VoxelFuseArgs& a = f->a;
+    a.disp = nullptr; a.poses = nullptr;
     a.mfs = v.mfs; a.rows = v.rows; a.cols = v.cols; a.min_disp16 = h->min_disp16; a._pad = 0;
     a.f = v.cal.f; a.cu = v.cal.cu; a.cv = v.cal.cv; a.base = v.cal.base;
+    return VISO_OK;
+}
+
+int voxel_fuse_restage(const VoxelSession& ses, const double* poses, int n, VoxelFrames* f) {
+    return poses ? voxel_stage_poses(ses.where(), ses.host(), poses, n, f->rows12) : VISO_OK;
+}
+
+int voxel_fuse_groups(VoxelHost* h, const DispView& v, const VoxelFrames& f, const VoxelFuseLaunch& launch) {
+    hipStream_t s = h->ctx->stream;
+    const size_t px = v.px();
+    VoxelFuseArgs a = f.a;
     for (int f0 = 0; f0 < v.n; f0 += VOXEL_GROUP) {
         const int nf = v.n - f0 < VOXEL_GROUP ? v.n - f0 : VOXEL_GROUP;
-        a.disp = disp + (size_t)f0 * v.mfs;
+        a.disp = f.disp + (size_t)f0 * v.mfs;
         a.poses = v.poses ? h->d_pose + (size_t)f0 * 12 : nullptr;
-        launch(a, image ? image + (size_t)f0 * v.ifs : nullptr, dim3((unsigned)((px + 255) / 256), (unsigned)nf), s);
+        launch(a, f.image ? f.image + (size_t)f0 * v.ifs : nullptr, dim3((unsigned)((px + 255) / 256), (unsigned)nf), s);
         HIP_TRY(hipGetLastError());
     }
-    return voxel_finish(where, h);
+    return VISO_OK;
+}
+
+int voxel_fuse(const char* where, VoxelRegistry& reg, const void* handle, const DispView& v, const VoxelFuseLaunch& launch) {
+    int r;
+    if ((r = voxel_fuse_args(where, reg, handle, v)) < 0) return r;
+    VoxelSession ses(where, reg, handle, VoxelSession::ANY_STATE);   // the overflow refusal comes behind the context's
+    VISO_TRY(ses.status());
+    VoxelFrames f;   // its poses are alive until voxel_finish has waited for the copy that reads them
+    if ((r = voxel_fuse_stage(ses, reg, v, &f)) < 0) return r;
+    if ((r = voxel_fuse_groups(ses.host(), v, f, launch)) < 0) return r;
+    return voxel_finish(where, ses.host());
+}
+
+int voxel_read_words(VoxelHost* h, int first, int n, unsigned long long* out) {
+    hipStream_t s = h->ctx->stream;
+    HIP_TRY(hipMemcpyAsync(out, h->head.words + first, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return VISO_OK;
 }
 
 int voxel_pass(VoxelHost* h, const VoxelLaunch& launch, unsigned long long* n, unsigned long long* n_tris) {
@@ -242,13 +273,18 @@ bool voxel_evict_args(const char* where, VoxelRegistry& reg, const void* handle,
     return ok;
 }
 
+unsigned long long voxel_stat_sum(const std::vector<unsigned long long>& stats, int which) {
+    unsigned long long sum = 0;
+    for (int k = 0; k < VOXEL_STAT_SETS; ++k) sum += stats[(size_t)k * VOXEL_STAT_WORDS + which];
+    return sum;
+}
+
 int voxel_evict_get_stats(VoxelHost* h, std::vector<unsigned long long>& stats, unsigned long long* occupied) {
     hipStream_t s = h->ctx->stream;
     stats.resize((size_t)VOXEL_STAT_SETS * VOXEL_STAT_WORDS);
     HIP_TRY(hipMemcpyAsync(stats.data(), h->head.stats, stats.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    *occupied = 0;
-    for (int k = 0; k < VOXEL_STAT_SETS; ++k) *occupied += stats[(size_t)k * VOXEL_STAT_WORDS + VOXEL_ST_OCC];
+    *occupied = voxel_stat_sum(stats, VOXEL_ST_OCC);
     return VISO_OK;
 }
 

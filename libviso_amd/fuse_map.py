@@ -4,7 +4,8 @@
                                                      [--align [--aligned-poses FILE --align-voxel-gate G --align-photo WEIGHT]]
                                                      [--carve VOXELS [--carve-near METRES]] [--depth-weights SHIFT[,MAX]]
                                                      [--distance-field FILE.npz [--field-half-side METRES]]
-                                                     [--travel-field FILE.npz [--travel-clearance METRES] [--field-half-side METRES]]]
+                                                     [--travel-field FILE.npz [--travel-clearance METRES] [--field-half-side METRES]]
+                                                     [--repose NEW_POSES.txt]]
                                  [--window METRES [--archive FILE.npy]]
 
 Fuses the maps a KITTI runner wrote with --disparity DIR and the poses of its pose file into one voxel map on the device
@@ -63,6 +64,11 @@ float32 centroid of each voxel, count the number of points fused into it.
                  space that no map updated.  cost (uint32 [n0][n1][n2], thirds of a voxel along the cheapest <3,4,5> chamfer way;
                  4294967295: not free or no way), box (int32 [2][3]: lo, hi), voxel and, when the last camera position is reached,
                  path (int32 [m][3], the voxels of the way back from it to the goal), as a numpy .npz.
+  --repose NEW_POSES.txt  with --surface or --mesh: the poses were corrected after the maps were fused (include/viso_hip.h, "TSDF
+                 retract").  Every map is first fused at its pose in POSES.txt; then every map whose pose differs in NEW_POSES.txt
+                 (as many lines) is retracted at the old pose and fused at the new one (TsdfMap.move), and OUT.ply, the renders
+                 and the fields are written from the result: byte-identical to a run with NEW_POSES.txt as POSES.txt.  The number of
+                 moved maps is printed.  Not together with --window (evicted voxels cannot be retracted) or --align.
   --window METRES  keep the map on the device to a cube of this half side around the camera (include/viso_hip.h, "Map eviction"):
                  before map i is fused (and, with --align, aligned), every voxel outside the box of voxels that the cube around the
                  translation of pose i touches leaves the table, on the device, and is appended to an archive on the host.  So a
@@ -303,7 +309,15 @@ def main(argv=None):
     ap.add_argument("--window", type=float, default=None, metavar="METRES", help="keep the map to a cube of this half side around the camera; "
                     "what leaves it goes to an archive on the host (OUT.ply: the whole map without --surface or --mesh, else the live window)")
     ap.add_argument("--archive", metavar="FILE.npy", help="with --window: write the merged evicted voxels as a numpy array of entries")
+    ap.add_argument("--repose", metavar="NEW_POSES.txt", help="with --surface or --mesh: once every map is fused at POSES, move every frame "
+                    "whose pose differs in this file to its pose there (retract and fuse again), then write the output")
     a = ap.parse_args(argv)
+    if a.repose and not (a.surface or a.mesh):
+        ap.error("--repose needs --surface or --mesh (only a TSDF map lets go of a fused frame)")
+    if a.repose and a.window is not None:
+        ap.error("--repose does not go with --window (voxels that were evicted cannot be retracted)")
+    if a.repose and a.align:
+        ap.error("--repose does not go with --align (the frames are not fused at POSES then)")
     if a.archive and a.window is None:
         ap.error("--archive needs --window")
     fuse_options = {}
@@ -358,6 +372,9 @@ def main(argv=None):
     b, e = a.frames if a.frames else (0, len(names))
     if not 0 <= b <= e <= len(names):
         sys.exit(f"fuse_map: --frames {b} {e} is outside the {len(names)} maps")
+    new_poses = read_poses(a.repose) if a.repose else None
+    if new_poses is not None and len(new_poses) != len(poses):
+        sys.exit(f"fuse_map: {len(poses)} poses in {a.poses} but {len(new_poses)} in {a.repose}")
     f, cu, cv, base = read_calib(a.calib)
     prm = Param.default(base=base, f=f, cu=cu, cv=cv)
     archive = []   # --window: what left the map, in the order it left
@@ -403,6 +420,13 @@ def main(argv=None):
                     tsdf.fuse(m, prm, pose=pose, image=image)
                 else:
                     tsdf.fuse(m, prm, pose=pose)
+            if new_poses is not None:
+                moved = [i for i in range(b, e) if not np.array_equal(poses[i], new_poses[i])]
+                for i in moved:   # the frame as it was fused, from its files again
+                    m = read_disparity_png(os.path.join(a.disparity_dir, names[i]))
+                    tsdf.move(m, prm, poses[i], new_poses[i], image=read_png8(os.path.join(a.gray, names[i])) if gray else None)
+                print(f"fuse_map: {len(moved)} of {e - b} maps moved to their poses in {a.repose}")
+                poses = new_poses   # --render and the fields see the model from where the frames are now
             st = tsdf.stats()
             note = write_archive(tsdf._evict_dtype())
             if a.align:

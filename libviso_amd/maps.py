@@ -5,12 +5,12 @@ import itertools
 
 import numpy as np
 
-from . import _call, _Handle, _map16, _params, _pose_arg, _struct_arg, load
+from . import VisoError, _call, _Handle, _map16, _params, _pose_arg, _struct_arg, load
 from .abi import (FIELD_NONE, FIELD_STATE_SURFACE, FIELD_UNKNOWN_IS_SITE, MAP_DEFAULTS, MAP_ENTRY_DTYPE, TSDF_ALIGN_DEFAULTS, TSDF_ALIGN_GRAY_DEFAULTS, TSDF_ALIGN_GRAY_STEP_DTYPE,
                   TSDF_ALIGN_STEP_DTYPE, TSDF_ALIGNMENT_DTYPE, TSDF_ALIGNMENT_GRAY_DTYPE, TSDF_CROSSING_DTYPE, TSDF_DEFAULTS,
                   TSDF_ENTRY_DTYPE, TSDF_FUSE_DEFAULTS, TSDF_GRAY_ENTRY_DTYPE, TSDF_MESH_VERTEX_DTYPE, TSDF_NORMAL_COUNTERS, TSDF_NORMAL_DTYPE,
                   TSDF_NORMAL_GRAY_COUNTERS, TSDF_NORMAL_GRAY_DTYPE, MapCounters, MapParams, TsdfAlignGrayParams, TsdfAlignParams,
-                  TsdfCounters, TsdfParams, VoxelBox, ptr)
+                  TsdfCounters, TsdfParams, TsdfRetractReport, VoxelBox, ptr)
 
 
 def map_params(**params):
@@ -286,6 +286,18 @@ def _vertex_list(vertices):
     return np.ascontiguousarray(vertices, dtype=TSDF_MESH_VERTEX_DTYPE)
 
 
+def _reported(fn, *args):
+    """fn(*args, report) of a retract or a move (include/viso_hip.h, "TSDF retract"): the report as a dict of n_points, n_updates,
+    n_missing, n_underflow, n_inconsistent, n_freed.  A refusal raises the library's error with the dict as its .report."""
+    rep = TsdfRetractReport()
+    try:
+        _call(fn, *args, rep.words())
+    except VisoError as e:
+        e.report = rep.as_dict()
+        raise
+    return rep.as_dict()
+
+
 class _TableMap(_Handle):
     """What VoxelMap and TsdfMap share: a handle of one of the two kinds of hash tables of voxels (csrc/voxel_host.h).  A subclass
     sets _prefix (the C functions are _prefix + name), _Params and _params (the parameter struct and its factory), _ENTRY_DTYPE and
@@ -486,6 +498,22 @@ class TsdfMap(_TableMap):
         return (g, n_missing.value) if missing else g
 
     @property
+    def retract(self):
+        """viso_tsdf_retract / viso_tsdf_retract_gray (include/viso_hip.h, "TSDF retract"), called as
+        `tsdf.retract(d16, param, pose=None, image=None)` with the arguments the frame was fused with: its updates are taken out of
+        the map again, bit for bit, and the voxels whose weight returns to zero leave the table.  Returns the report as a dict
+        (n_points, n_updates, n_missing, n_underflow, n_inconsistent, n_freed).  A frame that is not in the map as given is refused:
+        the library's error is raised with the report as its .report, and the map is unchanged.  A property that hands out the
+        call, like distance_field."""
+        return _RetractCall(self)
+
+    @property
+    def move(self):
+        """viso_tsdf_move / viso_tsdf_move_gray, called as `tsdf.move(d16, param, old_pose, new_pose, image=None)`: retract at
+        old_pose and, if that is not refused, fuse at new_pose, under one hold on the map.  Returns the retract's report."""
+        return _MoveCall(self)
+
+    @property
     def normals(self):
         """The surface normals of this map (include/viso_hip.h, "TSDF normals"): a TsdfNormals, whose vertices, surface, mesh and
         render give a unit normal for every vertex, crossing and rendered hit.  A plain or a gray map."""
@@ -624,6 +652,42 @@ class TsdfMap(_TableMap):
             d, w, g, nrm = d[0], (w[0] if weights else None), (g[0] if gray else None), (nrm[0] if normals else None)
         out = (d,) + ((w,) if weights else ()) + ((g,) if gray else ()) + ((nrm,) if normals else ())
         return out if len(out) > 1 else d
+
+
+def _retract(t, where, name, d16, param, poses, image):
+    """viso_tsdf_<name>, or on a gray map viso_tsdf_<name>_gray, of one host map at `poses` (one for a retract, old and new for a move)."""
+    if (image is not None) != t.gray:
+        raise ValueError(f"{where}: a gray map's frame comes with its image, a plain one's without")
+    d16 = _map16(where, d16)
+    T = [_pose_arg(where, p, square=True) for p in poses]   # (the list keeps the arrays alive over the call)
+    args = (ptr(d16, C.c_int16),)
+    if t.gray:
+        image = np.ascontiguousarray(image)
+        if image.dtype != np.uint8 or image.shape != d16.shape:
+            raise ValueError(f"{where}: the image must be a 2-D uint8 array of the map's shape")
+        args += (ptr(image, C.c_uint8),)
+    fn = getattr(t.L, "viso_tsdf_" + name + ("_gray" if t.gray else ""))
+    return _reported(fn, t.h, *args, d16.shape[0], d16.shape[1], C.byref(param), *(Tp for _, Tp in T))
+
+
+class _RetractCall:
+    """What TsdfMap.retract hands out: the call on that map."""
+
+    def __init__(self, tsdf):
+        self.tsdf = tsdf
+
+    def __call__(self, d16, param, pose=None, image=None):
+        return _retract(self.tsdf, "TsdfMap.retract", "retract", d16, param, (pose,), image)
+
+
+class _MoveCall:
+    """What TsdfMap.move hands out: the call on that map."""
+
+    def __init__(self, tsdf):
+        self.tsdf = tsdf
+
+    def __call__(self, d16, param, old_pose, new_pose, image=None):
+        return _retract(self.tsdf, "TsdfMap.move", "move", d16, param, (old_pose, new_pose), image)
 
 
 class DistanceField:

@@ -3,7 +3,7 @@
 
   python tools/tsdf_bench.py [--frames N] [--reps N] [--capacity-log2 N] [--render-views N] [--kernel-only] [--out FILE]
                              [--carve C [--carve-near M]] [--depth-weights S] [--options-capacity-log2 N] [--fuse-only]
-                             [--distance-field] [--travel-field]
+                             [--distance-field] [--travel-field] [--retract]
 
 The pairs and poses are those of tools/map_bench.py: 17 seeded synthetic frames repeated, frame t seen from a camera that has moved
 0.8 t m forward and turned 0.002 t rad.  Legs (host clock around work that ends in a synchronise, medians of alternating
@@ -55,6 +55,12 @@ repetitions):
                it in the same loop: the part of the time that the travel field did not add.  Where the camera's own voxel is not
                free in a case (a site, behind the surface, nearer to a site than the clearance), the goal is the free cell nearest
                to it; the result names the goal used.
+  retract      (with --retract, which runs only this section; include/viso_hip.h, "TSDF retract") on the map of all resident frames,
+               alternated, each call followed outside the clock by what restores the map: Batch.retract_tsdf of one frame (the
+               middle one), of 16 frames (from the middle one on) and of all frames, which leaves the map empty; Batch.move_tsdf of
+               the 16 frames to poses 2 cm and 0.2 degrees off, and back; Batch.fuse_tsdf of the 16 frames and of all frames into the
+               map without them (the yardsticks: a take is the fuse's march); and viso_tsdf_clear followed by Batch.fuse_tsdf of
+               all frames, what a 16-frame move replaces.  The result says whether the map at the end is the map at the start.
 n_updates / n_points from viso_tsdf_stats is the number of voxels a pixel's band touches.  --kernel-only runs clear + fuse_tsdf
 --reps times, the extractions and the render once and the two align calls --reps times: the run to put under `rocprofv3 --kernel-trace --stats` for the kernels' own times.  The
 count the result is held against (not a measurement) is printed with it."""
@@ -96,6 +102,7 @@ def main():
     ap.add_argument("--fuse-only", action="store_true")
     ap.add_argument("--distance-field", action="store_true")
     ap.add_argument("--travel-field", action="store_true")
+    ap.add_argument("--retract", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     nf = a.frames
@@ -177,6 +184,45 @@ def main():
             os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
             with open(a.out, "w") as f:
                 json.dump(res, f, indent=1)
+        tsdf.close(); b.close(); ctx.close()
+        return
+
+    if a.retract:
+        n16 = min(16, nf)
+        t0 = min(nf // 2, nf - n16)
+        off = hostmath.tr2mat([0.002, -0.002, 0.002, 0.012, -0.01, 0.012])
+        there = np.array([poses[t] @ off for t in range(t0, t0 + n16)])
+        start = tsdf.entries().tobytes()
+        legs = {k: [] for k in ("retract_1", "fuse_1", "retract_16", "fuse_16", "retract_all", "fuse_tsdf", "move_16", "move_16_back", "clear_and_fuse_all")}
+        reports = {}
+        for rep_ in range(a.reps + 1):   # alternating; the first round is the warm-up
+            ms = {}
+            ms["retract_1"] = clock(lambda: reports.__setitem__("retract_1", b.retract_tsdf(tsdf, poses[t0:t0 + 1], t0=t0, t1=t0 + 1)))
+            ms["fuse_1"] = clock(lambda: b.fuse_tsdf(tsdf, poses[t0:t0 + 1], t0=t0, t1=t0 + 1))
+            ms["retract_16"] = clock(lambda: reports.__setitem__("retract_16", b.retract_tsdf(tsdf, poses[t0:t0 + n16], t0=t0, t1=t0 + n16)))
+            ms["fuse_16"] = clock(lambda: b.fuse_tsdf(tsdf, poses[t0:t0 + n16], t0=t0, t1=t0 + n16))
+            ms["retract_all"] = clock(lambda: reports.__setitem__("retract_all", b.retract_tsdf(tsdf, poses)))
+            ms["fuse_tsdf"] = clock(lambda: b.fuse_tsdf(tsdf, poses))
+            ms["move_16"] = clock(lambda: reports.__setitem__("move_16", b.move_tsdf(tsdf, poses[t0:t0 + n16], there, t0=t0, t1=t0 + n16)))
+            ms["move_16_back"] = clock(lambda: b.move_tsdf(tsdf, there, poses[t0:t0 + n16], t0=t0, t1=t0 + n16))
+            ms["clear_and_fuse_all"] = clock(lambda: (tsdf.clear(), b.fuse_tsdf(tsdf, poses)))
+            if rep_:
+                for k, v in ms.items():
+                    legs[k].append(v)
+        st = tsdf.stats()
+        med = {k: float(np.median(v)) for k, v in legs.items()}
+        res = {"frames": nf, "shape": [int(rows), int(cols)], "capacity_log2": log2, "reps": a.reps, "frames_16": [int(t0), int(t0 + n16)],
+               "ms_median": med, "ms_min": {k: float(np.min(v)) for k, v in legs.items()}, "ms_max": {k: float(np.max(v)) for k, v in legs.items()},
+               "reports": reports, "stats": st, "same_map_at_the_end": bool(tsdf.entries().tobytes() == start),
+               "ratio": {"retract_all_to_fuse_tsdf": med["retract_all"] / med["fuse_tsdf"], "retract_16_to_fuse_16": med["retract_16"] / med["fuse_16"],
+                         "move_16_to_clear_and_fuse_all": med["move_16"] / med["clear_and_fuse_all"]}}
+        print(json.dumps(res))
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                json.dump(res, f, indent=1)
+        if omap is not None:
+            omap.close()
         tsdf.close(); b.close(); ctx.close()
         return
 
