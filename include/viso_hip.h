@@ -1717,6 +1717,88 @@ int viso_tsdf_move_gray(viso_tsdf* t, const int16_t* disp, const uint8_t* image,
 int viso_batch_move_tsdf(viso_batch* b, viso_tsdf* t, int t0, int t1, const double* poses_old, const double* poses_new,
                          uint64_t report_or_null[6]);
 
+/* ------------------------------------------------ pose graph: many relative poses and priors reconciled into one trajectory, on the
+ * device (opt-in; NOT in the reference)
+ *
+ * The frame-to-frame motions with their covariances ("motion covariance"), the absolute poses of "TSDF align" and, later, loop
+ * closures each say something about the trajectory; this is the step that makes one trajectory of them, which "TSDF retract"'s
+ * move then applies to the map.  This definition is the contract; tests/posegraph_ref.py restates it in numpy.
+ *   Nodes.  n_poses poses P_k, 4 x 4 row-major, camera to world: the matrices of chain_poses, viso_tsdf_fuse and viso_tsdf_align.
+ *     The first three rows are read and taken as rigid.  fixed[k] != 0 (fixed_or_null NULL: none) keeps P_k as given, byte for byte.
+ *   Edges.  n_edges edges (i, j, Z, Omega), edge_ij [n_edges][2], edge_Z [n_edges][16], edge_info [n_edges][36].  Z (first three
+ *     rows read) measures P_i^-1 P_j.  i == -1 is a prior: P_-1 is the identity and never moves, so Z measures P_j itself.  j in
+ *     0 .. n_poses-1, i in -1 .. n_poses-1, i != j; i > j is allowed, and several edges may join one pair.  Omega, 6 x 6 row-major
+ *     (its lower triangle is read), is the symmetric positive definite information of the error in the tangent order (phi, rho),
+ *     rotation first, of the right perturbation P = P^ Exp(xi) that viso_chain_covariances uses.  Its Cholesky factor C
+ *     (Omega = C C') must pass the usual pivot test (> 1e-12 x the diagonal entry), else VISO_ERR_ARG.
+ *   Cost.  r_e = Log(Z_e^-1 P_i^-1 P_j), F = 1/2 sum_e r_e' Omega_e r_e.
+ *   Exp and Log.  xi = (phi, rho), theta = |phi|, K = [phi]x:  Exp(xi) = [R | V rho], R = I + a K + b K^2, V = I + b K + c1 K^2.
+ *     Log(R, t): v = vee(R - R') / 2, theta = atan2(|v|, (trace R - 1) / 2), phi = v / a, rho = (I - K / 2 + cp K^2) t.
+ *     a = sin(theta) / theta, b = (1 - cos(theta)) / theta^2, c1 = (theta - sin(theta)) / theta^3, cp = (1 - a / (2 b)) / theta^2, and for
+ *     the Jacobians c2 = (theta^2 + 2 cos(theta) - 2) / (2 theta^4), c3 = (2 theta - 3 sin(theta) + theta cos(theta)) / (2 theta^5).
+ *     For theta^2 < 1e-2 each is its series in x = theta^2, five terms: a = sum (-x)^k / (2k+1)!, b = sum (-x)^k / (2k+2)!,
+ *     c1 = sum (-x)^k / (2k+3)!, c2 = sum (-x)^k / (2k+4)!, c3 = sum (k+1) (-x)^k / (2k+5)!,
+ *     cp = 1/12 + x/720 + x^2/30240 + x^3/1209600 + x^4/47900160.  (The closed forms of c2, c3 and cp lose 1e-16 / theta^4 to
+ *     cancellation, which is why the series start this early.)  A residual rotation near pi is outside the contract.
+ *   Jacobians, exact (with J = I the iteration would stop where an approximate gradient vanishes, which is not the optimum):
+ *     M = P_i^-1 P_j, J_j = J_r^-1(r), J_i = -J_r^-1(r) Ad(M^-1), Ad(T) = [[R, 0], [[t]x R, R]], and
+ *     J_r^-1(xi) = [[A, 0], [-A Q A, A]], A = I - K/2 + cp K^2 at K = [-phi]x (the inverse of SO(3)'s left Jacobian at -phi), and
+ *     Q = Q(-rho, -phi), Q(rho, phi) = G/2 + c1 (K G + G K + K G K) + c2 (K K G + G K K - 3 K G K) + c3 (K G K K + K K G K), G = [rho]x.
+ *   Normal equations.  g_a = sum J_a' Omega r, H_ab = sum J_a' Omega J_b; fixed nodes and the world node have no columns.
+ *   Step (Levenberg-Marquardt).  (H + lambda diag H) delta = -g.  lambda starts at 1e-4; an accepted trial multiplies it by 0.1, not
+ *     below 1e-12; a rejected one by 10.
+ *   One iteration.  Solve for delta.  max |delta| <= eps_step: status 1, the step is not applied.  Otherwise the trial is
+ *     P_k <- P_k Exp(delta_k) for every k that is not fixed, with cost F'; it is accepted when F' <= F (1 + 2^-40) (the slack keeps
+ *     rounding from rejecting the last steps).  Every solve counts as an iteration; max_iters solves without convergence give
+ *     status 2, and the best poses are returned (fourth row 0 0 0 1; a fixed pose as given).
+ *   Failures.  A pivot of the factorisations that is not > 1e-12 x its original diagonal entry: status -2.  A number that is not
+ *     finite: status -3.  On a negative status poses_out equals poses, and the call still returns VISO_OK: the status is the report's.
+ *   The solver is direct and uses the graph's shape.  An edge is a chain edge when i == -1 or |i - j| == 1, and long otherwise.
+ *     The chain edges and the damping form a block-tridiagonal T; the L long edges are H_lambda = T + U U', where the 6 x 6 block of
+ *     U for edge e at node a is J_a' C_e.  delta = y - W (I + U' W)^-1 U' y, y = T^-1 (-g), W = T^-1 U: one block-tridiagonal
+ *     Cholesky, sweeps with 6 L + 1 right-hand sides and one dense Cholesky of order 6 L.
+ *   Refusals (VISO_ERR_ARG, text in viso_last_error).  T must be definite on its own: the free nodes fall into runs joined by chain
+ *     edges (a fixed node cuts a run), and every run needs a prior on one of its nodes or a chain edge to a fixed node; otherwise the
+ *     call is refused and the text names the run's first node.  A free node with no edge at all is refused.  A caller whose
+ *     odometry failed at a frame bridges the gap with a weak edge (a large covariance), or fixes a node on either side.  Poses, Z or
+ *     Omega that are not finite are refused too.
+ *   Limits.  n_poses 1 .. 65536, n_edges 1 .. 2^20, L <= 256, and the workspace -- 6 n_poses (6 L + 1) doubles, 158 a edge and the
+ *     small blocks -- at most 2^28 doubles; beyond any of these VISO_ERR_UNSUPPORTED, before anything is allocated.
+ *   Determinism.  Every sum has a fixed order: the edges of a node are added in edge-index order, reductions are fixed trees, and
+ *     there is no float atomic.  Two calls with the same arrays give the same bytes.
+ * viso_pose_graph_linearize: cost, gradient [n_poses][6] and, with step_out, the step [n_poses][6] of one solve at `lambda` (>= 0) at
+ * the given poses; rows of fixed nodes are zeros.  A step whose factorisation fails is VISO_ERR_ARG.
+ * viso_pose_graph_optimize: the loop.  max_iters 1 .. 200, eps_step >= 0.  report: VISO_PG_* below.  trace (or NULL with
+ * trace_cap 0): one entry of five doubles a solve -- F, F' (F on the converged solve), lambda, max |delta|, accepted -- the first
+ * trace_cap of them.
+ * viso_motion_edge (host only): the edge of one solved frame, Z = inv(tr2mat(tr)) and info = (G cov G')^-1 with the G of
+ * viso_chain_covariances, between the frame before (i) and the frame (j) of chain_poses' list; a cov whose G cov G' fails the pivot
+ * test: VISO_ERR_ARG.
+ * ctx_or_null: the context whose device and stream the call uses (NULL: the default context).  The checks that need no device come
+ * first.  Device memory of a call: the one workspace block, allocated and freed by the call.
+ * Out of scope: loop-closure detection; robust kernels on edges; marginal covariances of the optimised poses; graphs that are not a
+ * chain plus at most 256 long edges; a factor of less serial depth (cyclic reduction, chain segments in parallel); the C++ host
+ * mirror and the KITTI runners; the map's move inside the optimise call.
+ * HIP kernels (posegraph.hip): pg_linearize_kernel (a thread an edge: r, the Jacobians, the edge's pieces J' C and C' r),
+ * pg_assemble_kernel (a thread per node and entry, over the node's edge list), pg_cost_kernel, pg_chain_factor_kernel (a wave a run,
+ * serial along it), pg_chain_solve_kernel (a lane a right-hand side), pg_capacitance_kernel, pg_dense_kernel (one workgroup),
+ * pg_delta_kernel, pg_stepmax_kernel, pg_update_kernel. */
+#define VISO_PG_STATUS 0
+#define VISO_PG_ITERS 1
+#define VISO_PG_COST_INITIAL 2
+#define VISO_PG_COST_FINAL 3
+#define VISO_PG_LAMBDA 4
+#define VISO_PG_LAST_STEP 5
+#define VISO_PG_N_LONG 6
+#define VISO_PG_N_REJECTED 7
+int viso_pose_graph_linearize(viso_ctx* ctx_or_null, int n_poses, const double* poses, const int32_t* fixed_or_null, int n_edges,
+                              const int32_t* edge_ij, const double* edge_Z, const double* edge_info, double lambda, double* cost_out,
+                              double* grad_out, double* step_out);
+int viso_pose_graph_optimize(viso_ctx* ctx_or_null, int n_poses, const double* poses, const int32_t* fixed_or_null, int n_edges,
+                             const int32_t* edge_ij, const double* edge_Z, const double* edge_info, int max_iters, double eps_step,
+                             double* poses_out, double report[8], double* trace_or_null, int trace_cap);
+int viso_motion_edge(const double tr[6], const double cov36[36], double Z[16], double info[36]);
+
 #ifdef __cplusplus
 }
 #endif

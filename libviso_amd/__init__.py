@@ -8,7 +8,7 @@ the reference's function names.  There is NO CPU fallback: if the library is
 missing, or no HIP device is present, calls raise.
 
 This file holds the loader and what every wrapper shares; the wrappers live in sibling modules named after the csrc files
-they reach (plain, dense, maps, estimators, batch) and are re-exported at the end.  The prototypes are abi.PROTOTYPES.
+they reach (plain, dense, maps, estimators, batch, posegraph) and are re-exported at the end.  The prototypes are abi.PROTOTYPES.
 """
 import atexit
 import ctypes as C
@@ -244,3 +244,4 @@ from .maps import (DistanceField, TravelField, TsdfMap, TsdfNormals, VoxelMap, _
 from .estimators import (chain_covariances, pose_covariance, pose_refine, refines_as_covariances, window_refine,  # noqa: E402,F401
                          window_refines_as_covariances)
 from .batch import Batch, Context, PinnedArray  # noqa: E402,F401
+from .posegraph import PoseGraph, alignment_prior, motion_edge, motion_edges, read_edges, write_edges  # noqa: E402,F401

@@ -492,7 +492,14 @@ PROTOTYPES = {
     "tsdf_move": (i, [vp, i16p, i, i, PP, f64p, f64p, u64p]),
     "tsdf_move_gray": (i, [vp, i16p, u8p, i, i, PP, f64p, f64p, u64p]),
     "batch_move_tsdf": (i, [vp, vp, i, i, f64p, f64p, u64p]),
+    # pose graph
+    "pose_graph_linearize": (i, [vp, i, f64p, i32p, i, i32p, f64p, f64p, dbl, f64p, f64p, f64p]),
+    "pose_graph_optimize": (i, [vp, i, f64p, i32p, i, i32p, f64p, f64p, i, dbl, f64p, f64p, f64p, i]),
+    "motion_edge": (i, [f64p, f64p, f64p, f64p]),
 }
+
+# the words of viso_pose_graph_optimize's report, in the order of VISO_PG_* (include/viso_hip.h, "pose graph")
+POSE_GRAPH_REPORT = ("status", "iters", "cost_initial", "cost_final", "lambda", "last_step", "n_long", "n_rejected")
 
 # what the oracle library exports under its own prefix with the same signatures (declare_common, oracle/pyoracle.py)
 COMMON = ("match_circle", "collect_matches", "triangulate_rectified", "get_inliers", "ransac_minimize_reproj", "ransac_samples",

@@ -2,6 +2,7 @@
 // constructors, tr2mat, the pose chain step, F_from_P and the RANSAC sample
 // stream.  A handful of flops each; nothing here is worth a kernel launch.
 #include "solver_dev.h"
+#include "alignmath.h"
 
 #include <float.h>
 #include <math.h>
@@ -122,6 +123,31 @@ static void mat6_mul(const double* a, const double* b, double* out, bool bt) {  
         }
 }
 
+// Ad(T) and G of one motion tr (the comment above): shared by the chain and by viso_motion_edge.  T (or null): tr2mat(tr).
+static void motion_ad_g(const double* tr, double* Ad, double* G, double* T_out = nullptr) {
+    double T[16];
+    viso_tr2mat(tr, T);
+    if (T_out) memcpy(T_out, T, sizeof(T));
+    const double R[3][3] = {{T[0], T[1], T[2]}, {T[4], T[5], T[6]}, {T[8], T[9], T[10]}};
+    const double tv[3] = {T[3], T[7], T[11]};
+    const double tx[3][3] = {{0, -tv[2], tv[1]}, {tv[2], 0, -tv[0]}, {-tv[1], tv[0], 0}};
+    const double sx = sin(tr[0]), cx = cos(tr[0]), sy = sin(tr[1]), cy = cos(tr[1]);
+    const double W[3][3] = {{1, 0, sy}, {0, cx, -sx * cy}, {0, sx, cx * cy}};   // columns w_rx, w_ry, w_rz
+    memset(Ad, 0, 36 * sizeof(double));
+    memset(G, 0, 36 * sizeof(double));
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            double tR = 0, tW = 0;
+            for (int l = 0; l < 3; ++l) { tR += tx[i][l] * R[l][j]; tW += tx[i][l] * W[l][j]; }
+            Ad[6 * i + j] = R[i][j];
+            Ad[6 * (i + 3) + j + 3] = R[i][j];
+            Ad[6 * (i + 3) + j] = tR;
+            G[6 * i + j] = -W[i][j];
+            G[6 * (i + 3) + j] = -tW;
+            G[6 * (i + 3) + j + 3] = i == j ? -1.0 : 0.0;
+        }
+}
+
 extern "C" int viso_chain_covariances(const double* tr, const int32_t* ok, const viso_motion_cov* cov, int n, double* pose_cov36,
                                       int32_t* valid, int* n_out) {
     if (n < 0 || !pose_cov36 || !valid || !n_out || (n > 0 && (!tr || !ok || !cov))) {
@@ -140,26 +166,7 @@ extern "C" int viso_chain_covariances(const double* tr, const int32_t* ok, const
         double* out = pose_cov36 + 36 * (size_t)k;
         valid[k] = live ? 1 : 0;
         if (!live) { memset(out, 0, sizeof(double) * 36); continue; }
-        double T[16];
-        viso_tr2mat(tr + 6 * (size_t)t, T);
-        const double R[3][3] = {{T[0], T[1], T[2]}, {T[4], T[5], T[6]}, {T[8], T[9], T[10]}};
-        const double tv[3] = {T[3], T[7], T[11]};
-        const double tx[3][3] = {{0, -tv[2], tv[1]}, {tv[2], 0, -tv[0]}, {-tv[1], tv[0], 0}};
-        const double sx = sin(tr[6 * t]), cx = cos(tr[6 * t]), sy = sin(tr[6 * t + 1]), cy = cos(tr[6 * t + 1]);
-        const double W[3][3] = {{1, 0, sy}, {0, cx, -sx * cy}, {0, sx, cx * cy}};   // columns w_rx, w_ry, w_rz
-        memset(Ad, 0, sizeof(Ad));
-        memset(G, 0, sizeof(G));
-        for (int i = 0; i < 3; ++i)
-            for (int j = 0; j < 3; ++j) {
-                double tR = 0, tW = 0;
-                for (int l = 0; l < 3; ++l) { tR += tx[i][l] * R[l][j]; tW += tx[i][l] * W[l][j]; }
-                Ad[6 * i + j] = R[i][j];
-                Ad[6 * (i + 3) + j + 3] = R[i][j];
-                Ad[6 * (i + 3) + j] = tR;
-                G[6 * i + j] = -W[i][j];
-                G[6 * (i + 3) + j] = -tW;
-                G[6 * (i + 3) + j + 3] = i == j ? -1.0 : 0.0;
-            }
+        motion_ad_g(tr + 6 * (size_t)t, Ad, G);
         mat6_mul(Ad, S, tmp, false);
         mat6_mul(tmp, Ad, a, true);
         mat6_mul(G, cov[t].cov, tmp, false);
@@ -170,5 +177,43 @@ extern "C" int viso_chain_covariances(const double* tr, const int32_t* ok, const
         memcpy(out, S, sizeof(S));
     }
     *n_out = k + 1;
+    return VISO_OK;
+}
+
+// The pose-graph edge of one solved frame (include/viso_hip.h, "pose graph"): chain_poses steps P_k = P_{k-1} inv(T), so the edge
+// between the two measures Z = inv(T), and its error in the tangent of the right perturbation has the covariance G cov G'.
+extern "C" int viso_motion_edge(const double tr[6], const double cov36[36], double Z[16], double info[36]) {
+    bool ok = tr && cov36 && Z && info;
+    for (int i = 0; ok && i < 6; ++i) ok = isfinite(tr[i]);
+    for (int i = 0; ok && i < 36; ++i) ok = isfinite(cov36[i]);
+    if (!ok) { viso_set_error("viso_motion_edge: bad argument (non-null pointers, finite tr and cov)"); return VISO_ERR_ARG; }
+    double T[16], Ad[36], G[36], tmp[36], S[36], L[36], Li[36];
+    motion_ad_g(tr, Ad, G, T);
+    mat6_mul(G, cov36, tmp, false);
+    mat6_mul(tmp, G, S, true);
+    for (int i = 0; i < 6; ++i)
+        for (int j = 0; j < i; ++j) S[6 * i + j] = S[6 * j + i] = 0.5 * (S[6 * i + j] + S[6 * j + i]);
+    if (!align_cholesky(S, L)) {
+        viso_set_error("viso_motion_edge: G cov G' is not positive definite (a pivot of its Cholesky factor is not > 1e-12 x its diagonal entry)");
+        return VISO_ERR_ARG;
+    }
+    memset(Li, 0, sizeof(Li));   // L^-1, column by column; info = L^-T L^-1
+    for (int c = 0; c < 6; ++c)
+        for (int r = c; r < 6; ++r) {
+            double x = r == c ? 1.0 : 0.0;
+            for (int m = c; m < r; ++m) x -= L[6 * r + m] * Li[6 * m + c];
+            Li[6 * r + c] = x / L[6 * r + r];
+        }
+    for (int i = 0; i < 6; ++i)
+        for (int j = 0; j < 6; ++j) {
+            double v = 0;
+            for (int k = (i > j ? i : j); k < 6; ++k) v += Li[6 * k + i] * Li[6 * k + j];
+            info[6 * i + j] = v;
+        }
+    for (int i = 0; i < 3; ++i) {   // inv(T) = [R' | -R' t]
+        for (int j = 0; j < 3; ++j) Z[4 * i + j] = T[4 * j + i];
+        Z[4 * i + 3] = -(T[0 * 4 + i] * T[3] + T[1 * 4 + i] * T[7] + T[2 * 4 + i] * T[11]);
+    }
+    Z[12] = Z[13] = Z[14] = 0; Z[15] = 1;
     return VISO_OK;
 }
