@@ -1799,6 +1799,60 @@ int viso_pose_graph_optimize(viso_ctx* ctx_or_null, int n_poses, const double* p
                              double* poses_out, double report[8], double* trace_or_null, int trace_cap);
 int viso_motion_edge(const double tr[6], const double cov36[36], double Z[16], double info[36]);
 
+/* ------------------------------------------------ loop closure: which earlier frames a frame looks like, and which of their features
+ * are which of its own, on the device (opt-in; NOT in the reference)
+ *
+ * The producer of "pose graph"'s long edges.  A place signature per frame and an all-pairs search over the signatures of a sequence
+ * name the candidate revisits; an ungated, mutual matcher over two frames' left-image descriptors gives the correspondences that the
+ * existing solver (viso_ransac_minimize_reproj, viso_pose_covariance, viso_motion_edge) turns into an edge -- that glue is Python
+ * (libviso_amd/loops.py).  No vocabulary, no training data, no images: the 121-element descriptors a batch already holds.  This
+ * definition is the contract; tests/loop_ref.py restates it in numpy.
+ *   Rows.  A descriptor row d[0..120] is taken as the integers of the matcher's packed rows: int16 values (direct calls), or the
+ *     left-image rows of a batch's last run, whichever upload family filled them (the f32 and the int16 upload of the same integers
+ *     give the same results).  Only the first n[f] rows of frame f are read.
+ *   Word of a row.  For b = 0 .. bits-1: p_b = sum_k c[b][k] d[k], c[b][k] = +1 when bit (k mod 64) of draw (k div 64) is set and -1
+ *     otherwise, the draws those of the viso_splitmix64 stream started at state seed * 0x9E3779B97F4A7C15 + b (mod 2^64).  Bit b of
+ *     the word is p_b > 0.  Exact in int32 for |d| <= 1020 (any int16 row, in fact: 121 * 32768 < 2^31).
+ *   Signature.  h[w] = min(number of the frame's rows with word w, 255), uint8 [1 << bits], bits in 6 .. 12; n = 0 gives zeros.
+ *   Score.  s(j, i) = sum_w min(h_j[w], h_i[w]) (uint32), computed as (sum h_j + sum h_i - SAD(h_j, h_i)) / 2.
+ *   Sequence sum.  S(j, i) = sum_{k = 0 .. seq_len-1, i - k >= 0} s(j - k, i - k), seq_len in 1 .. 16.
+ *   Candidates of frame j.  The admissible i are 0 <= i <= j - min_gap (min_gap >= 1) with S(j, i) >= min_score.  They are picked
+ *     greedily in the order (S descending, i ascending); a pick removes every i' with |i' - i| <= nms (nms >= 0); at most k (1 .. 16)
+ *     are kept.  cand_out [n - j0][k] int32 (filled with -1) and score_out [n - j0][k] uint32 (filled with 0) hold rows j0 .. n-1.
+ *   Wide match of a pair (query frame, target frame).  sad(q, t) = min(sum_k |Q_q[k] - T_t[k]|, 262142) (the bound is never met by
+ *     rows within +-1020: 121 * 2040 = 246840).  For query q, t1 is the argmin over all targets by (sad, t) -- the LOWER index wins a
+ *     tie, unlike viso_match_desc -- d1 its sad, d2 the least sad over t != t1 (+infinity with one target).  The row (q, t1, d1) is
+ *     accepted when (double)d1 < (double)d2 * ratio and q is the argmin by (sad, q) over ALL queries for target t1.  match_out
+ *     [np][cap][3] holds each pair's accepted rows in ascending q (zeros behind them), m_out [np] their counts.  Pairs may repeat,
+ *     both frames of a pair may be the same, a frame without rows gives no match.
+ * viso_place_signatures: desc [nf][cap][121] int16 (left images), n [nf] -> sig_out [nf][1 << bits].
+ * viso_batch_place_signatures: the same for frames t0 .. t1-1 of the batch, from the resident rows; no descriptor leaves the device.
+ * viso_place_scores: s_out [n - j0][n], row j - j0 holds s(j, i) for i <= j and 0 for i > j; a block above 2^31 bytes is refused with
+ *   VISO_ERR_NOMEM.  viso_place_candidates: n <= 32768; the raw scores are held 16 MiB of rows at a time, so every n fits.
+ * viso_wide_match: desc / n as above, pairs [np][2] of frame indices.  viso_batch_wide_match: frames of the batch.
+ * Refusals (VISO_ERR_ARG with a text, before a device is touched): bits outside 6 .. 12, k or seq_len outside 1 .. 16, min_gap < 1,
+ *   nms < 0, ratio outside (0, 1], n outside 1 .. 32768, cap outside 1 .. 16384, a count outside 0 .. cap, a null pointer, a pair that
+ *   names a frame outside the range, a handle that is not live.  The batch calls need a batch of 121-element descriptors with a
+ *   completed run (viso_batch_run*, matcher_only included) and say so otherwise; a frame whose f32 descriptors did not fit the packed
+ *   rows (viso_batch_get_general_path_flags) is VISO_ERR_UNSUPPORTED.  A working block that does not fit the device: VISO_ERR_NOMEM.
+ * ctx_or_null: the context whose device and stream a direct call uses (NULL: the default context); the calls are serialised with the
+ *   other direct calls and use that context's scratch blocks (a named context needs no default one).  The batch calls read the rows AND
+ *   the counts of the batch's last run: an upload or a detect since then changes nothing they see until the next run (the keypoints
+ *   and counts the getters return are the upload's, so ask before uploading again).  They run on the batch's stream behind that run and use a
+ *   workspace of the batch's own.
+ * Determinism.  Counts, minima and maxima of integers only: no result depends on an order, two calls give the same bytes.
+ * HIP kernels (loops.hip): loop_pack_kernel, place_sig_kernel, place_sums_kernel, place_score_kernel, place_cand_kernel,
+ * wide_scan_kernel, wide_accept_kernel. */
+int viso_place_signatures(viso_ctx* ctx_or_null, const int16_t* desc, const int32_t* n, int nf, int cap, uint64_t seed, int bits,
+                          uint8_t* sig_out);
+int viso_batch_place_signatures(viso_batch* b, int t0, int t1, uint64_t seed, int bits, uint8_t* sig_out);
+int viso_place_scores(viso_ctx* ctx_or_null, const uint8_t* sig, int n, int bits, int j0, uint32_t* s_out);
+int viso_place_candidates(viso_ctx* ctx_or_null, const uint8_t* sig, int n, int bits, int j0, int min_gap, int seq_len, int nms,
+                          uint32_t min_score, int k, int32_t* cand_out, uint32_t* score_out);
+int viso_wide_match(viso_ctx* ctx_or_null, const int16_t* desc, const int32_t* n, int nf, int cap, const int32_t* pairs, int np,
+                    double ratio, int32_t* match_out, int32_t* m_out);
+int viso_batch_wide_match(viso_batch* b, const int32_t* pairs, int np, double ratio, int32_t* match_out, int32_t* m_out);
+
 #ifdef __cplusplus
 }
 #endif

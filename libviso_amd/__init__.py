@@ -8,7 +8,7 @@ the reference's function names.  There is NO CPU fallback: if the library is
 missing, or no HIP device is present, calls raise.
 
 This file holds the loader and what every wrapper shares; the wrappers live in sibling modules named after the csrc files
-they reach (plain, dense, maps, estimators, batch, posegraph) and are re-exported at the end.  The prototypes are abi.PROTOTYPES.
+they reach (plain, dense, maps, estimators, batch, posegraph, loops) and are re-exported at the end.  The prototypes are abi.PROTOTYPES.
 """
 import atexit
 import ctypes as C
@@ -245,3 +245,5 @@ from .estimators import (chain_covariances, pose_covariance, pose_refine, refine
                          window_refines_as_covariances)
 from .batch import Batch, Context, PinnedArray  # noqa: E402,F401
 from .posegraph import PoseGraph, alignment_prior, motion_edge, motion_edges, read_edges, write_edges  # noqa: E402,F401
+from .loops import (batch_place_signatures, batch_wide_match, detect_loops, frame_nodes, loop_edge, loop_observations,  # noqa: E402,F401
+                    place_candidates, place_scores, place_signatures, wide_match)

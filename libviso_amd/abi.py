@@ -14,6 +14,7 @@ VISO_OK = 1
 VISO_ERR_ARG = -1
 VISO_ERR_HIP = -2
 VISO_ERR_UNSUPPORTED = -3
+VISO_ERR_NOMEM = -4
 DESC_LEN = 121
 
 
@@ -496,6 +497,13 @@ PROTOTYPES = {
     "pose_graph_linearize": (i, [vp, i, f64p, i32p, i, i32p, f64p, f64p, dbl, f64p, f64p, f64p]),
     "pose_graph_optimize": (i, [vp, i, f64p, i32p, i, i32p, f64p, f64p, i, dbl, f64p, f64p, f64p, i]),
     "motion_edge": (i, [f64p, f64p, f64p, f64p]),
+    # loop closure
+    "place_signatures": (i, [vp, i16p, i32p, i, i, u64, i, u8p]),
+    "batch_place_signatures": (i, [vp, i, i, u64, i, u8p]),
+    "place_scores": (i, [vp, u8p, i, i, i, u32p]),
+    "place_candidates": (i, [vp, u8p, i, i, i, i, i, i, u32, i, i32p, u32p]),
+    "wide_match": (i, [vp, i16p, i32p, i, i, i32p, i, dbl, i32p, i32p]),
+    "batch_wide_match": (i, [vp, i32p, i, dbl, i32p, i32p]),
 }
 
 # the words of viso_pose_graph_optimize's report, in the order of VISO_PG_* (include/viso_hip.h, "pose graph")

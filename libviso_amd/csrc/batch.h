@@ -141,6 +141,8 @@ struct viso_batch {
     // viso_batch_stamp: time stamps of a run (0 = before its uploads, 1 = after them, 2 = behind its last kernel)
     hipEvent_t ev_stamp[3] = {};
     bool stamps = false;
+    // loop closure (loops.hip): a matcher launch has filled the packed rows, and the workspace of its batch calls (grow only)
+    bool has_run = false; char* loop_ws = nullptr; size_t loop_ws_bytes = 0;
 };
 
 // A handle the library does not know -- null, destroyed, or taken along by viso_ctx_destroy of its context (ctx.hip keeps the

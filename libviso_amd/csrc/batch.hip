@@ -600,6 +600,7 @@ static int run_matcher_launch(viso_batch* b, bool from_images) {
         b->uv_mode = b->subpix;
     }
     if (b->stamps) HIP_TRY(hipEventRecord(b->ev_stamp[2], s));   // re-recorded behind the solver by run_rest
+    b->has_run = true;
     return VISO_OK;
 }
 

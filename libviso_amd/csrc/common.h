@@ -108,7 +108,8 @@ struct SolverParamsDev {         // viso_param, device copy
     int ransac_iter, _pad;
 };
 
-// The scratch blocks of the DEFAULT context (ctx_scratch), shared by the plain family and the direct calls.  Every user holds
+// The scratch blocks of a context (ctx_scratch).  The DEFAULT context's are shared by the plain family and the direct calls; a direct
+// call that names a context (the loop-closure calls, DirectCall::begin(ctx)) uses that context's own blocks.  Every user holds
 // PlainLock and issues ALL its work on the context's stream, and a block is regrown only behind a synchronize of that stream: a
 // slot's users are ordered by the stream -- behind a frame's RANSAC stage that runs on after its call returned, too -- so a call may
 // use any slot for contents that need not outlive it.  zero_new promises zeros at (re)allocation and nothing more: its user hands
@@ -208,7 +209,7 @@ struct CircleArgs {
 int launch_circle_table(hipStream_t s, const CircleArgs& a, int* tab, int tabn);
 viso_ctx* viso_default_ctx();
 
-// One direct call: a batch stage's kernel on host pointers, on the default context (ctx.hip).  Declared behind the argument checks
+// One direct call: a batch stage's kernel on host pointers, on the default context or on one the caller names (ctx.hip).  Declared behind the argument checks
 // and the early VISO_OK returns, which touch no device.  An error return must not leave work in flight (plain_quiesce, plain.hip):
 // copies into or out of the caller's memory may be queued on s, and the scratch blocks they use are the next caller's.  So the
 // destructor waits for s, before it gives the lock back, unless the last thing the call did was a wait() that succeeded.
@@ -217,7 +218,9 @@ struct __attribute__((visibility("hidden"))) DirectCall {
     DirectCall() = default;
     DirectCall(const DirectCall&) = delete;
     ~DirectCall();
-    int begin();   // PlainLock's mutex, the default context (none: VISO_ERR_HIP, viso_ctx_create's message stays), hipSetDevice
+    // PlainLock's mutex, then the context -- ctx (live: the caller has checked), its device, stream and scratch blocks, or with null the
+    // default context (none: VISO_ERR_HIP, viso_ctx_create's message stays) -- and hipSetDevice
+    int begin(viso_ctx* ctx = nullptr);
     template <class T> int scratch(ScratchSlot slot, size_t count, T** out, bool zero_new = false) { return ctx_scratch(c, slot, sizeof(T) * count, (void**)out, zero_new); }
     // count elements of the HOST pointer's type, on s; count 0 copies nothing
     template <class T> int up(void* dst_dev, const T* src_host, size_t count) { return copy(dst_dev, src_host, sizeof(T) * count, hipMemcpyHostToDevice); }

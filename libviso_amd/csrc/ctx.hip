@@ -271,10 +271,10 @@ viso_ctx* viso_default_ctx() {
     return g_default;
 }
 
-int DirectCall::begin() {
+int DirectCall::begin(viso_ctx* ctx) {
     g_call_mu.lock();   // PlainLock's mutex, held until the destructor
     locked = true;
-    if (!(c = viso_default_ctx())) return VISO_ERR_HIP;
+    if (!(c = ctx ? ctx : viso_default_ctx())) return VISO_ERR_HIP;
     HIP_TRY(hipSetDevice(c->device));
     s = c->stream;
     in_flight = true;
