@@ -346,8 +346,8 @@ __global__ __launch_bounds__(256) void triangulate_direct_kernel(const double* x
 }
 
 // ------------------------------------------------------------ plain family
-// Every call: inputs packed into the context's pinned block and sent with ONE copy (PlainStage), results fetched with
-// ONE copy behind ONE synchronize.
+// Every call goes through one PlainCall (common.h), which owns the protocol and its error-return rule; what stands here is each
+// call's own: its checks, its plain_try_* question, the layout of its blocks, its launch and how it reads the mirror.
 #define CIRC_TAB_MAX (1 << 20)   // keys below this take the tables (3 ints each); larger or negative ones the literal loops
 
 extern "C" int viso_match_circle(const int32_t* lr, int n_lr, const int32_t* lr_prev, int n_lrp,
@@ -360,14 +360,11 @@ extern "C" int viso_match_circle(const int32_t* lr, int n_lr, const int32_t* lr_
     }
     *out_n = 0;
     if (n_lr == 0) return VISO_OK;
-    PlainLock lk;
-    viso_ctx* c = viso_default_ctx();
-    if (!c) return VISO_ERR_HIP;
-    HIP_TRY(hipSetDevice(c->device));
-    PlainProf pp(VISO_PLAIN_MATCH_CIRCLE, c->stream);
+    PlainCall pc;
+    VISO_TRY(pc.begin(VISO_PLAIN_MATCH_CIRCLE));
     {   // the frame's stereo call may have joined exactly these lists already (plain.hip)
         int ret = VISO_OK;
-        if (plain_try_circle(c, lr, n_lr, lr_prev, n_lrp, m11, n11, m22, n22, circ, pcl, cap, out_n, &ret)) return ret;
+        if (plain_try_circle(pc.c, lr, n_lr, lr_prev, n_lrp, m11, n11, m22, n22, circ, pcl, cap, out_n, &ret)) return ret;
     }
     // size of the tables: the largest key of the three keyed lists (a look at ~4 500 ints; argument inspection, no arithmetic of the path)
     long long kmax = -1;
@@ -376,42 +373,31 @@ extern "C" int viso_match_circle(const int32_t* lr, int n_lr, const int32_t* lr_
     for (int j = 0; j < n_lrp && tables; ++j) { const int k = lr_prev[3 * j]; if (k < 0 || k >= CIRC_TAB_MAX) tables = false; else if (k > kmax) kmax = k; }
     for (int j = 0; j < n22 && tables; ++j) { const int k = m22[3 * j]; if (k < 0 || k >= CIRC_TAB_MAX) tables = false; else if (k > kmax) kmax = k; }
     const int tabn = tables ? (int)(kmax + 1) : 0;   // 0: every key is "out of range" -> the kernel takes the literal loops
-    int r;
-    PlainStage in;
-    const size_t in_bytes = PlainStage::need(sizeof(int) * 3 * (size_t)n_lr) + PlainStage::need(sizeof(int) * 3 * (size_t)n_lrp) +
-                            PlainStage::need(sizeof(int) * 3 * (size_t)n11) + PlainStage::need(sizeof(int) * 3 * (size_t)n22);
-    if ((r = in.begin(c, in_bytes)) < 0) return r;
+    VISO_TRY(pc.inputs(PlainStage::need(sizeof(int) * 3 * (size_t)n_lr) + PlainStage::need(sizeof(int) * 3 * (size_t)n_lrp) +
+                       PlainStage::need(sizeof(int) * 3 * (size_t)n11) + PlainStage::need(sizeof(int) * 3 * (size_t)n22)));
     CircleArgs a{};
-    a.lr = in.put(lr, 3 * (size_t)n_lr); a.lrp = in.put(lr_prev, 3 * (size_t)n_lrp);
-    a.m11 = in.put(m11, 3 * (size_t)n11); a.m22 = in.put(m22, 3 * (size_t)n22);
+    a.lr = pc.in.put(lr, 3 * (size_t)n_lr); a.lrp = pc.in.put(lr_prev, 3 * (size_t)n_lrp);
+    a.m11 = pc.in.put(m11, 3 * (size_t)n11); a.m22 = pc.in.put(m22, 3 * (size_t)n22);
     a.n_lr = n_lr; a.n_lrp = n_lrp; a.n11 = n11; a.n22 = n22; a.cap = cap;
-    char *dout, *hout; int* dtab;
-    const size_t out_bytes = 256 + sizeof(int) * 6 * (size_t)cap;
-    if ((r = ctx_scratch(c, SLOT_PLAIN_OUT, out_bytes, (void**)&dout)) < 0) return r;
-    if ((r = ctx_pinned(c, 1, out_bytes, &hout)) < 0) return r;
-    if ((r = ctx_scratch(c, SLOT_CIRCLE_TAB, sizeof(int) * 3 * (size_t)(tabn + 1), (void**)&dtab)) < 0) return r;
-    a.out_n = reinterpret_cast<int*>(dout); a.rows = reinterpret_cast<int*>(dout + 256);
-    if ((r = in.flush(c->stream)) < 0) return r;
-    pp.mark(1);
-    if ((r = launch_circle_table(c->stream, a, dtab, tabn)) < 0) return r;
-    pp.mark(2);
-    // the rows that exist (the count is on the device), by a copy kernel into pinned memory
-    PlainSignal sig_;
-    if ((r = plain_signal_next(c, &sig_)) < 0) return r;
-    if ((r = plain_blit(c->stream, dout, hout, 64, a.out_n, 6, cap, &sig_)) < 0) return r;
-    pp.wait_begin();
-    if ((r = plain_signal_wait(c, c->stream, sig_.seq)) < 0) return r;
-    const int cnt = *reinterpret_cast<const int*>(hout);
+    int* dtab;
+    VISO_TRY(pc.result(256 + sizeof(int) * 6 * (size_t)cap, true));   // the count | the rows
+    VISO_TRY(ctx_scratch(pc.c, SLOT_CIRCLE_TAB, sizeof(int) * 3 * (size_t)(tabn + 1), (void**)&dtab));
+    a.out_n = reinterpret_cast<int*>(pc.dout); a.rows = reinterpret_cast<int*>(pc.dout + 256);
+    VISO_TRY(pc.sent());
+    VISO_TRY(launch_circle_table(pc.s, a, dtab, tabn));
+    pc.launched();
+    VISO_TRY(pc.fetch(64, a.out_n, 6, cap));   // the rows that exist (the count is on the device)
+    VISO_TRY(pc.wait());
+    const int cnt = *reinterpret_cast<const int*>(pc.hout);
     const int w = cnt < cap ? cnt : cap;
-    pp.wait_end();
     *out_n = cnt;
-    plain_note_circle(c, cnt);
-    const int* rows = reinterpret_cast<const int*>(hout + 256);
+    plain_note_circle(pc.c, cnt);
+    const int* rows = reinterpret_cast<const int*>(pc.hout + 256);
     for (int i = 0; i < w; ++i) {
         circ[4 * i + 0] = rows[6 * i + 0]; circ[4 * i + 1] = rows[6 * i + 1]; circ[4 * i + 2] = rows[6 * i + 2]; circ[4 * i + 3] = rows[6 * i + 3];
         pcl[2 * i + 0] = rows[6 * i + 4]; pcl[2 * i + 1] = rows[6 * i + 5];
     }
-    pp.mark(3);
+    pc.done();
     if (cnt > cap) { viso_set_error("viso_match_circle: %d rows needed, cap %d", cnt, cap); return VISO_ERR_ARG; }
     return VISO_OK;
 }
@@ -428,65 +414,48 @@ extern "C" int viso_collect_matches(const float* kp1, int n1, const float* kp2, 
             return VISO_ERR_ARG;
         }
     if (n == 0) return VISO_OK;
-    PlainLock lk;
-    viso_ctx* c = viso_default_ctx();
-    if (!c) return VISO_ERR_HIP;
-    HIP_TRY(hipSetDevice(c->device));
-    PlainProf pp(VISO_PLAIN_COLLECT_MATCHES, c->stream);
-    if (plain_try_collect(c, kp1, n1, kp2, n2, match, n, x)) return VISO_OK;   // the frame's stereo call computed it (plain.hip)
-    int r;
-    PlainStage in;
-    const size_t in_bytes = PlainStage::need(sizeof(float2) * (size_t)n1) + PlainStage::need(sizeof(float2) * (size_t)n2) +
-                            PlainStage::need(sizeof(int) * 3 * (size_t)n);
-    if ((r = in.begin(c, in_bytes)) < 0) return r;
-    char* hout;
+    PlainCall pc;
+    VISO_TRY(pc.begin(VISO_PLAIN_COLLECT_MATCHES));
+    if (plain_try_collect(pc.c, kp1, n1, kp2, n2, match, n, x)) return VISO_OK;   // the frame's stereo call computed it (plain.hip)
+    VISO_TRY(pc.inputs(PlainStage::need(sizeof(float2) * (size_t)n1) + PlainStage::need(sizeof(float2) * (size_t)n2) +
+                       PlainStage::need(sizeof(int) * 3 * (size_t)n)));
     const size_t out_bytes = sizeof(double) * 4 * (size_t)n;
-    if ((r = ctx_pinned(c, 1, out_bytes, &hout)) < 0) return r;
-    const float2* hkp1 = in.host_of(in.put(reinterpret_cast<const float2*>(kp1), (size_t)n1));   // the kernel reads the pinned block itself
-    const float2* hkp2 = in.host_of(in.put(reinterpret_cast<const float2*>(kp2), (size_t)n2));
-    const int* hmatch = in.host_of(in.put(match, 3 * (size_t)n));
-    pp.mark(1);
-    PlainSignal sig_;
-    if ((r = plain_signal_next(c, &sig_)) < 0) return r;
-    hipLaunchKernelGGL(collect_direct_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, hkp1, hkp2, hmatch, n, reinterpret_cast<double*>(hout), sig_);
+    VISO_TRY(pc.result(out_bytes, false));
+    const float2* hkp1 = pc.in.host_of(pc.in.put(reinterpret_cast<const float2*>(kp1), (size_t)n1));   // the kernel reads the pinned block itself
+    const float2* hkp2 = pc.in.host_of(pc.in.put(reinterpret_cast<const float2*>(kp2), (size_t)n2));
+    const int* hmatch = pc.in.host_of(pc.in.put(match, 3 * (size_t)n));
+    VISO_TRY(pc.sent(false));
+    PlainSignal sig;
+    VISO_TRY(pc.signal(&sig));
+    hipLaunchKernelGGL(collect_direct_kernel, dim3((n + 255) / 256), dim3(256), 0, pc.s, hkp1, hkp2, hmatch, n, reinterpret_cast<double*>(pc.hout), sig);
     HIP_TRY(hipGetLastError());
-    pp.mark(2);
-    pp.wait_begin();
-    if ((r = plain_signal_wait(c, c->stream, sig_.seq)) < 0) return r;
-    pp.wait_end();
-    memcpy(x, hout, out_bytes);
-    pp.mark(3);
+    pc.launched();
+    VISO_TRY(pc.wait());
+    memcpy(x, pc.hout, out_bytes);
+    pc.done();
     return VISO_OK;
 }
 
 extern "C" int viso_triangulate_rectified(const double* x, int m, const viso_param* p, double* X) {
     if (m < 0 || !p || (m && (!x || !X))) { viso_set_error("viso_triangulate_rectified: bad argument"); return VISO_ERR_ARG; }
     if (m == 0) return VISO_OK;
-    PlainLock lk;
-    viso_ctx* c = viso_default_ctx();
-    if (!c) return VISO_ERR_HIP;
-    HIP_TRY(hipSetDevice(c->device));
-    PlainProf pp(VISO_PLAIN_TRIANGULATE, c->stream);
-    if (plain_try_triangulate(c, x, m, p, X)) return VISO_OK;   // the frame's stereo call computed it (plain.hip)
-    int r;
-    PlainStage in;
-    if ((r = in.begin(c, PlainStage::need(sizeof(double) * 4 * (size_t)m))) < 0) return r;
-    char* hout;
+    PlainCall pc;
+    VISO_TRY(pc.begin(VISO_PLAIN_TRIANGULATE));
+    if (plain_try_triangulate(pc.c, x, m, p, X)) return VISO_OK;   // the frame's stereo call computed it (plain.hip)
+    VISO_TRY(pc.inputs(PlainStage::need(sizeof(double) * 4 * (size_t)m)));
     const size_t out_bytes = sizeof(double) * 3 * (size_t)m;
-    if ((r = ctx_pinned(c, 1, out_bytes, &hout)) < 0) return r;
-    const double* hx = in.host_of(in.put(x, 4 * (size_t)m));   // the kernel reads the pinned block itself
-    pp.mark(1);
+    VISO_TRY(pc.result(out_bytes, false));
+    const double* hx = pc.in.host_of(pc.in.put(x, 4 * (size_t)m));   // the kernel reads the pinned block itself
+    VISO_TRY(pc.sent(false));
     SolverParamsDev sp;
     fill_solver_params(&sp, p);
-    PlainSignal sig_;
-    if ((r = plain_signal_next(c, &sig_)) < 0) return r;
-    hipLaunchKernelGGL(triangulate_direct_kernel, dim3((m + 255) / 256), dim3(256), 0, c->stream, hx, m, sp, reinterpret_cast<double*>(hout), sig_);
+    PlainSignal sig;
+    VISO_TRY(pc.signal(&sig));
+    hipLaunchKernelGGL(triangulate_direct_kernel, dim3((m + 255) / 256), dim3(256), 0, pc.s, hx, m, sp, reinterpret_cast<double*>(pc.hout), sig);
     HIP_TRY(hipGetLastError());
-    pp.mark(2);
-    pp.wait_begin();
-    if ((r = plain_signal_wait(c, c->stream, sig_.seq)) < 0) return r;
-    pp.wait_end();
-    memcpy(X, hout, out_bytes);
-    pp.mark(3);
+    pc.launched();
+    VISO_TRY(pc.wait());
+    memcpy(X, pc.hout, out_bytes);
+    pc.done();
     return VISO_OK;
 }

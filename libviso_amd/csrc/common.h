@@ -169,12 +169,13 @@ struct PlainLock { PlainLock(); ~PlainLock(); };   // serialises the plain famil
 // viso_plain_profile: phases of one plain-family call, bracketed by four events on the call's stream (ctx.hip).  Used
 // inside a PlainLock.  mark(1) = inputs enqueued, mark(2) = kernels enqueued, mark(3) = results on the host.
 struct PlainProf {
-    PlainProf(int fn, hipStream_t s);
-    ~PlainProf();
+    void start(int fn, hipStream_t s);   // records event 0
+    void close();                        // adds the call to its function's times; once
+    ~PlainProf() { close(); }
     void mark(int k);
     void wait_begin();
     void wait_end();
-    int fn; hipStream_t s; bool on; int marks; double t0, tw, wait;
+    int fn = 0; hipStream_t s = nullptr; bool on = false; int marks = 0; double t0 = 0, tw = 0, wait = 0;
 };
 int ctx_scratch(viso_ctx* c, ScratchSlot slot, size_t bytes, void** out, bool zero_new = false);   // zero_new: a block that is (re)allocated starts zeroed
 static inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }   // offsets of the pieces of a scratch block
@@ -208,11 +209,16 @@ struct CircleArgs {
 // tab: 3 * tabn ints of device scratch; keys outside [0, tabn) or duplicate keys take the literal nested loops
 int launch_circle_table(hipStream_t s, const CircleArgs& a, int* tab, int tabn);
 viso_ctx* viso_default_ctx();
+// "The caller passed ctx_or_null": a handle that is not live is VISO_ERR_ARG, "<where>: not a live context handle" (where == null: the
+// text without the prefix); null is the default context (none: VISO_ERR_HIP, viso_ctx_create's message stays).  out == null: the
+// check alone, which touches no device.
+int ctx_resolve(const char* where, viso_ctx* ctx_or_null, viso_ctx** out);
 
 // One direct call: a batch stage's kernel on host pointers, on the default context or on one the caller names (ctx.hip).  Declared behind the argument checks
 // and the early VISO_OK returns, which touch no device.  An error return must not leave work in flight (plain_quiesce, plain.hip):
 // copies into or out of the caller's memory may be queued on s, and the scratch blocks they use are the next caller's.  So the
 // destructor waits for s, before it gives the lock back, unless the last thing the call did was a wait() that succeeded.
+// PlainCall (below) is its sibling for the plain family's small signalled calls, under the same rule.
 struct __attribute__((visibility("hidden"))) DirectCall {
     viso_ctx* c = nullptr; hipStream_t s = nullptr;
     DirectCall() = default;
@@ -268,6 +274,35 @@ int plain_signal_next(viso_ctx* c, PlainSignal* out);   // the next sequence num
 int plain_signal_wait(viso_ctx* c, hipStream_t s, uint32_t seq);
 int plain_blit(hipStream_t s, const void* src, void* dst, size_t head_words, const int* n_rows = nullptr, int row_words = 0, int max_rows = 0,
                const PlainSignal* sig = nullptr);
+// One small signalled call of the plain family on the default context (ctx.hip), DirectCall's sibling: declared behind the argument
+// checks and the early returns that touch no device.  The steps of every such call, in this order:
+//   begin(fn); inputs() / in.put; result(); sent(); the launch; launched(); signal() or fetch(); wait(); read the mirror; done().
+// The same rule holds: an error return must not leave work in flight -- the copy kernel of sent() reads the context's pinned block
+// over PCIe, and the next call overwrites that block.  So the destructor waits for s, before the lock goes back, when something of
+// this call may be queued (a flush, a launch, a signal asked for) and the last thing the call did was not a wait() that succeeded.
+// The returns with nothing queued (a plain_try_* answer, an allocation that failed before sent()) and the success path wait for nothing.
+struct __attribute__((visibility("hidden"))) PlainCall {
+    viso_ctx* c = nullptr; hipStream_t s = nullptr;
+    PlainProf pp;                         // viso_plain_profile's times of this call
+    PlainStage in;                        // the inputs: inputs(bytes), then in.put, in.host_of
+    char *dout = nullptr, *hout = nullptr;   // result(): the device block (on_device) and its pinned mirror
+    PlainCall() = default;
+    PlainCall(const PlainCall&) = delete;
+    ~PlainCall();
+    // PlainLock's mutex, the default context (none: VISO_ERR_HIP, viso_ctx_create's message stays), hipSetDevice, the profile's start
+    int begin(int fn);
+    int inputs(size_t bytes) { return in.begin(c, bytes); }
+    int result(size_t bytes, bool on_device);   // hout = the pinned mirror, dout = SLOT_PLAIN_OUT when asked for
+    int sent(bool flush = true);          // the inputs are on their way (flush = false: the kernel reads the pinned block itself); mark(1)
+    void launched() { queued = true; pp.mark(2); }
+    int signal(PlainSignal* out);         // the call's signal, for a last kernel that signals itself
+    // ... or a copy kernel of dout's first head_words words and the n_rows rows that exist into hout (plain_blit), which signals
+    int fetch(size_t head_words, const int* n_rows = nullptr, int row_words = 0, int max_rows = 0);
+    int wait();                           // the signal has come: the results are in hout
+    void done() { pp.mark(3); }
+private:
+    uint32_t seq = 0; bool locked = false, queued = false;
+};
 #ifdef __HIPCC__
 // Called by EVERY thread of the kernel's every workgroup, behind its last store.
 __device__ __forceinline__ void plain_signal_done(const PlainSignal& g, unsigned nblocks) {

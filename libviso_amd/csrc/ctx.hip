@@ -141,10 +141,14 @@ extern "C" int viso_ctx_destroy(viso_ctx* c) {
     return VISO_OK;
 }
 
-static viso_ctx* ctx_or_default(viso_ctx* c) {
-    if (!c) return viso_default_ctx();
-    if (!viso_ctx_live(c)) { viso_set_error("not a live context handle"); return nullptr; }
-    return c;
+int ctx_resolve(const char* where, viso_ctx* ctx_or_null, viso_ctx** out) {
+    if (ctx_or_null && !viso_ctx_live(ctx_or_null)) {
+        if (where) viso_set_error("%s: not a live context handle", where);
+        else viso_set_error("not a live context handle");
+        return VISO_ERR_ARG;
+    }
+    if (out && !(*out = ctx_or_null ? ctx_or_null : viso_default_ctx())) return VISO_ERR_HIP;
+    return VISO_OK;
 }
 
 static bool matcher_known(int variant) {
@@ -167,27 +171,21 @@ extern "C" int viso_matcher_default(void) {
 }
 
 extern "C" int viso_ctx_set_matcher(viso_ctx* c, int variant) {
-    if (c && !viso_ctx_live(c)) { viso_set_error("not a live context handle"); return VISO_ERR_ARG; }
-    c = ctx_or_default(c);
-    if (!c) return VISO_ERR_HIP;
+    VISO_TRY(ctx_resolve(nullptr, c, &c));
     if (!matcher_known(variant)) { viso_set_error("viso_ctx_set_matcher: unknown variant %d", variant); return VISO_ERR_ARG; }
     c->matcher_variant = variant;
     return VISO_OK;
 }
 
 extern "C" int viso_ctx_set_row8_shift(viso_ctx* c, int shift) {
-    if (c && !viso_ctx_live(c)) { viso_set_error("not a live context handle"); return VISO_ERR_ARG; }
-    c = ctx_or_default(c);
-    if (!c) return VISO_ERR_HIP;
+    VISO_TRY(ctx_resolve(nullptr, c, &c));
     if (shift < -1 || shift > 3) { viso_set_error("viso_ctx_set_row8_shift: -1 (from the data) or 0..3"); return VISO_ERR_ARG; }
     c->row8_force = shift;
     return VISO_OK;
 }
 
 extern "C" int viso_ctx_set_gn_split(viso_ctx* c, int split) {
-    if (c && !viso_ctx_live(c)) { viso_set_error("not a live context handle"); return VISO_ERR_ARG; }
-    c = ctx_or_default(c);
-    if (!c) return VISO_ERR_HIP;
+    VISO_TRY(ctx_resolve(nullptr, c, &c));
     if (split < 0 || split > 100) { viso_set_error("viso_ctx_set_gn_split: 0 (default) or 1..100"); return VISO_ERR_ARG; }
     c->gn_split = split;
     return VISO_OK;
@@ -206,8 +204,9 @@ extern "C" int viso_matcher_variants(int* out, int cap) {
 }
 
 extern "C" const char* viso_ctx_matcher_kernel_name(viso_ctx* c) {
-    c = ctx_or_default(c);
-    return matcher_kernel_name(c ? c->matcher_variant : VISO_MATCHER_DEFAULT);
+    viso_ctx* r = nullptr;   // a handle that is not live, or no device: the build's default
+    (void)ctx_resolve(nullptr, c, &r);
+    return matcher_kernel_name(r ? r->matcher_variant : VISO_MATCHER_DEFAULT);
 }
 
 extern "C" void* viso_ctx_stream(viso_ctx* c) { return c && viso_ctx_live(c) ? (void*)c->stream : nullptr; }
@@ -290,6 +289,48 @@ DirectCall::~DirectCall() {
     if (locked) g_call_mu.unlock();
 }
 
+int PlainCall::begin(int fn) {
+    g_call_mu.lock();   // PlainLock's mutex, held until the destructor
+    locked = true;
+    if (!(c = viso_default_ctx())) return VISO_ERR_HIP;
+    HIP_TRY(hipSetDevice(c->device));
+    s = c->stream;
+    pp.start(fn, s);
+    return VISO_OK;
+}
+int PlainCall::result(size_t bytes, bool on_device) {
+    if (on_device) VISO_TRY(ctx_scratch(c, SLOT_PLAIN_OUT, bytes, (void**)&dout));
+    return ctx_pinned(c, 1, bytes, &hout);
+}
+int PlainCall::sent(bool flush) {
+    if (flush) { queued = true; VISO_TRY(in.flush(s)); }
+    pp.mark(1);
+    return VISO_OK;
+}
+int PlainCall::signal(PlainSignal* out) {
+    queued = true;
+    VISO_TRY(plain_signal_next(c, out));
+    seq = out->seq;
+    return VISO_OK;
+}
+int PlainCall::fetch(size_t head_words, const int* n_rows, int row_words, int max_rows) {
+    PlainSignal sig;
+    VISO_TRY(signal(&sig));
+    return plain_blit(s, dout, hout, head_words, n_rows, row_words, max_rows, &sig);
+}
+int PlainCall::wait() {
+    pp.wait_begin();
+    VISO_TRY(plain_signal_wait(c, s, seq));
+    pp.wait_end();
+    queued = false;
+    return VISO_OK;
+}
+PlainCall::~PlainCall() {
+    if (queued) (void)hipStreamSynchronize(s);   // an error return, as DirectCall's
+    pp.close();
+    if (locked) g_call_mu.unlock();
+}
+
 // ---- viso_plain_profile: where a plain-family call's time goes ---------------------------------------------------
 #include <chrono>
 static bool g_prof_on = false;
@@ -300,8 +341,9 @@ static double now_us() {
     return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
-PlainProf::PlainProf(int fn_, hipStream_t s_) : fn(fn_), s(s_), on(g_prof_on), marks(0), t0(0), tw(0), wait(0) {
-    if (!on) return;
+void PlainProf::start(int fn_, hipStream_t s_) {
+    fn = fn_; s = s_;
+    if (!(on = g_prof_on)) return;
     if (!g_prof_ev_ok) {
         for (int i = 0; i < 4; ++i) if (hipEventCreate(&g_prof_ev[i]) != hipSuccess) { on = false; return; }
         g_prof_ev_ok = true;
@@ -312,8 +354,9 @@ PlainProf::PlainProf(int fn_, hipStream_t s_) : fn(fn_), s(s_), on(g_prof_on), m
 void PlainProf::mark(int k) { if (on && hipEventRecord(g_prof_ev[k], s) == hipSuccess) marks |= 1 << k; }
 void PlainProf::wait_begin() { if (on) tw = now_us(); }
 void PlainProf::wait_end() { if (on) wait += now_us() - tw; }
-PlainProf::~PlainProf() {
+void PlainProf::close() {
     if (!on) return;
+    on = false;
     viso_plain_times& p = g_prof[fn];
     p.calls += 1;
     p.host_us += now_us() - t0;

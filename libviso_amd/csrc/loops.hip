@@ -336,14 +336,6 @@ static int check_pairs(const char* where, const int32_t* pairs, int np, int nf, 
     return VISO_OK;
 }
 
-static int loops_ctx(const char* where, viso_ctx* ctx_or_null) {
-    if (ctx_or_null && !viso_ctx_live(ctx_or_null)) { viso_set_error("%s: not a live context handle", where); return VISO_ERR_ARG; }
-    return VISO_OK;
-}
-
-// the direct call on ctx_or_null's device and stream (null: the default context's)
-static int loops_begin(DirectCall& dc, viso_ctx* ctx_or_null) { return dc.begin(ctx_or_null); }
-
 // a scratch block of the call; a block that has to grow beyond the device's free memory is refused, not tried
 template <class T> static int loops_scratch(const char* where, DirectCall& dc, ScratchSlot slot, size_t count, T** out) {
     const size_t bytes = sizeof(T) * count;
@@ -383,12 +375,12 @@ extern "C" int viso_place_signatures(viso_ctx* ctx_or_null, const int16_t* desc,
     const char* where = "viso_place_signatures";
     VISO_TRY(check_rows(where, desc, n, nf, cap));
     if (bits < 6 || bits > LOOP_MAX_BITS || (nf > 0 && !sig_out)) return bad_arg(where, "bits in 6..12, a non-null output");
-    VISO_TRY(loops_ctx(where, ctx_or_null));
+    VISO_TRY(ctx_resolve(where, ctx_or_null, nullptr));
     if (nf == 0) return VISO_OK;
     uint32_t mask[VISO_ROW];
     sign_masks(seed, mask);
     DirectCall dc;
-    VISO_TRY(loops_begin(dc, ctx_or_null));
+    VISO_TRY(dc.begin(ctx_or_null));
     // SLOT_GEN2: counts [group] | masks [128] | signatures [group][1 << bits]; the frames in groups whose rows fit 256 MiB
     const size_t group = std::min<size_t>((size_t)nf, std::max<size_t>(1, ((size_t)256 << 20) / ((size_t)cap * VISO_ROW * 2)));
     const size_t oM = al256(sizeof(int) * group), oS = al256(oM + sizeof(mask)), bytes = oS + (group << bits);
@@ -490,7 +482,7 @@ extern "C" int viso_place_scores(viso_ctx* ctx_or_null, const uint8_t* sig, int 
     const char* where = "viso_place_scores";
     VISO_TRY(check_sig(where, sig, n, bits, j0));
     if (j0 < n && !s_out) return bad_arg(where, "a null output");
-    VISO_TRY(loops_ctx(where, ctx_or_null));
+    VISO_TRY(ctx_resolve(where, ctx_or_null, nullptr));
     if (j0 == n) return VISO_OK;
     const size_t cells = (size_t)(n - j0) * n;
     if (cells * sizeof(uint32_t) > PLACE_SCORES_MAX) {
@@ -498,7 +490,7 @@ extern "C" int viso_place_scores(viso_ctx* ctx_or_null, const uint8_t* sig, int 
         return VISO_ERR_NOMEM;
     }
     DirectCall dc;
-    VISO_TRY(loops_begin(dc, ctx_or_null));
+    VISO_TRY(dc.begin(ctx_or_null));
     const uint32_t *sig_d, *sums_d;
     VISO_TRY(stage_sig(where, dc, sig, n, bits, &sig_d, &sums_d));
     uint32_t* out;
@@ -515,10 +507,10 @@ extern "C" int viso_place_candidates(viso_ctx* ctx_or_null, const uint8_t* sig, 
     if (min_gap < 1 || seq_len < 1 || seq_len > 16 || nms < 0 || k < 1 || k > 16)
         return bad_arg(where, "min_gap >= 1, seq_len in 1..16, nms >= 0, k in 1..16");
     if (j0 < n && (!cand_out || !score_out)) return bad_arg(where, "a null output");
-    VISO_TRY(loops_ctx(where, ctx_or_null));
+    VISO_TRY(ctx_resolve(where, ctx_or_null, nullptr));
     if (j0 == n) return VISO_OK;
     DirectCall dc;
-    VISO_TRY(loops_begin(dc, ctx_or_null));
+    VISO_TRY(dc.begin(ctx_or_null));
     const uint32_t *sig_d, *sums_d;
     VISO_TRY(stage_sig(where, dc, sig, n, bits, &sig_d, &sums_d));
     // the raw scores of `rows` output rows and the seq_len - 1 rows before them at a time (SLOT_GEN2); the outputs in SLOT_GEN1
@@ -579,10 +571,10 @@ extern "C" int viso_wide_match(viso_ctx* ctx_or_null, const int16_t* desc, const
     const char* where = "viso_wide_match";
     VISO_TRY(check_rows(where, desc, n, nf, cap));
     VISO_TRY(check_pairs(where, pairs, np, nf, ratio, match_out, m_out));
-    VISO_TRY(loops_ctx(where, ctx_or_null));
+    VISO_TRY(ctx_resolve(where, ctx_or_null, nullptr));
     if (np == 0) return VISO_OK;
     DirectCall dc;
-    VISO_TRY(loops_begin(dc, ctx_or_null));
+    VISO_TRY(dc.begin(ctx_or_null));
     uint16_t* rows;
     VISO_TRY(stage_rows(where, dc, desc, 0, nf, cap, &rows));
     const WideBlock w = wide_block(np, cap);

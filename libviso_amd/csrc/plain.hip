@@ -876,10 +876,9 @@ static int match_run(viso_ctx* c, PlainCache* pc, PlainProf& pp, FramePlan& P, i
     return frame_harvest(c, pc, P, out_match, out_n);
 }
 
-static int match_desc_locked(viso_ctx* c, PlainCache* pc, const float* kp1, int n1, const float* kp2, int n2, const float* d1, const float* d2,
-                             int dlen, const viso_match_params* mp, int32_t* out_match, int* out_n) {
+static int match_desc_locked(viso_ctx* c, PlainCache* pc, PlainProf& pp, const float* kp1, int n1, const float* kp2, int n2, const float* d1,
+                             const float* d2, int dlen, const viso_match_params* mp, int32_t* out_match, int* out_n) {
     hipStream_t s = c->stream;
-    PlainProf pp(VISO_PLAIN_MATCH_DESC, s);
     int r;
     const int variant = matcher_effective(c->matcher_variant, dlen), extras = pack_extras(c->matcher_variant, dlen);
     // the planes' shift (matcher variant 6): one call, no previous run to learn it from: the default, or the forced one
@@ -964,14 +963,12 @@ extern "C" int viso_match_desc(const float* kp1, int n1, const float* kp2, int n
         viso_set_error("viso_match_desc: more than %d keypoints per image is not supported by this build", VISO_SORT_MAX);
         return VISO_ERR_UNSUPPORTED;
     }
-    PlainLock lk;
-    viso_ctx* c = viso_default_ctx();
-    if (!c) return VISO_ERR_HIP;
-    HIP_TRY(hipSetDevice(c->device));
-    PlainCache* pc = plain_cache(c);
+    PlainCall call;   // the lock, the context and the profile; the frame machinery below queues and waits by itself
+    VISO_TRY(call.begin(VISO_PLAIN_MATCH_DESC));
+    PlainCache* pc = plain_cache(call.c);
     if (!pc) { viso_set_error("viso_match_desc: out of memory"); return VISO_ERR_NOMEM; }
-    const int r = match_desc_locked(c, pc, kp1, n1, kp2, n2, d1, d2, dlen, mp, out_match, out_n);
-    if (r < 0) plain_quiesce(c, pc);
+    const int r = match_desc_locked(call.c, pc, call.pp, kp1, n1, kp2, n2, d1, d2, dlen, mp, out_match, out_n);
+    if (r < 0) plain_quiesce(call.c, pc);
     return r;
 }
 

@@ -830,12 +830,6 @@ void pg_launch_step(const PgDev& dv, int which, double lambda, hipStream_t s) { 
     hipLaunchKernelGGL(pg_stepmax_kernel, dim3(1), dim3(256), 0, s, dv.delta, 6 * G.n, dv.scal);
 }
 
-int pg_ctx(const char* where, viso_ctx* ctx_or_null, viso_ctx** c) {
-    if (ctx_or_null && !viso_ctx_live(ctx_or_null)) { viso_set_error("%s: not a live context handle", where); return VISO_ERR_ARG; }
-    *c = ctx_or_null ? ctx_or_null : viso_default_ctx();
-    return *c ? VISO_OK : VISO_ERR_HIP;
-}
-
 }   // namespace
 
 extern "C" int viso_pose_graph_linearize(viso_ctx* ctx_or_null, int n_poses, const double* poses, const int32_t* fixed_or_null, int n_edges,
@@ -849,7 +843,7 @@ extern "C" int viso_pose_graph_linearize(viso_ctx* ctx_or_null, int n_poses, con
     PgHost h;
     VISO_TRY(pg_check(where, n_poses, poses, fixed_or_null, n_edges, edge_ij, edge_Z, edge_info, &h));
     viso_ctx* c;
-    VISO_TRY(pg_ctx(where, ctx_or_null, &c));
+    VISO_TRY(ctx_resolve(where, ctx_or_null, &c));
     std::vector<char> stage;   // (before the block: the copy reads it until the block's wait)
     PgBlock blk(c->stream);
     PgDev dv;
@@ -885,7 +879,7 @@ extern "C" int viso_pose_graph_optimize(viso_ctx* ctx_or_null, int n_poses, cons
     PgHost h;
     VISO_TRY(pg_check(where, n_poses, poses, fixed_or_null, n_edges, edge_ij, edge_Z, edge_info, &h));
     viso_ctx* c;
-    VISO_TRY(pg_ctx(where, ctx_or_null, &c));
+    VISO_TRY(ctx_resolve(where, ctx_or_null, &c));
     std::vector<char> stage;
     PgBlock blk(c->stream);
     PgDev dv;

@@ -833,38 +833,26 @@ extern "C" int viso_minimize_reproj(const double* X, const double* obs, int m, d
     for (int i = 0; i < n_active; ++i)
         if (active[i] < 0 || active[i] >= m || i >= m) { viso_set_error("viso_minimize_reproj: active index out of range"); return VISO_ERR_ARG; }
     if (n_active == 0) return 0;
-    PlainLock lk;
-    viso_ctx* c = viso_default_ctx();
-    if (!c) return VISO_ERR_HIP;
-    HIP_TRY(hipSetDevice(c->device));
-    PlainProf pp(VISO_PLAIN_MINIMIZE, c->stream);
-    int r;
-    PlainStage in;   // ONE upload: X | obs | active; ONE read-back: tr[6], ok
-    if ((r = in.begin(c, PlainStage::need(sizeof(double) * 3 * (size_t)m) + PlainStage::need(sizeof(double) * 4 * (size_t)m) +
-                         PlainStage::need(sizeof(int) * (size_t)n_active) + PlainStage::need(64))) < 0) return r;
-    char *dout, *hout;
-    if ((r = ctx_scratch(c, SLOT_PLAIN_OUT, 128, (void**)&dout)) < 0) return r;
-    if ((r = ctx_pinned(c, 1, 128, &hout)) < 0) return r;
+    PlainCall pc;   // inputs: X | obs | active | tr; result: tr[6], ok
+    VISO_TRY(pc.begin(VISO_PLAIN_MINIMIZE));
+    VISO_TRY(pc.inputs(PlainStage::need(sizeof(double) * 3 * (size_t)m) + PlainStage::need(sizeof(double) * 4 * (size_t)m) +
+                       PlainStage::need(sizeof(int) * (size_t)n_active) + PlainStage::need(64)));
+    VISO_TRY(pc.result(128, true));
     GnArgs a{};
-    a.X = in.put(X, 3 * (size_t)m); a.obs = in.put(obs, 4 * (size_t)m); a.m = m; a.ld = m;
-    a.active = in.put(active, (size_t)n_active); a.n = n_active;
-    a.tr_in = in.put(tr, 6);
-    a.tr = reinterpret_cast<double*>(dout); a.ok = reinterpret_cast<int*>(dout + 64);
+    a.X = pc.in.put(X, 3 * (size_t)m); a.obs = pc.in.put(obs, 4 * (size_t)m); a.m = m; a.ld = m;
+    a.active = pc.in.put(active, (size_t)n_active); a.n = n_active;
+    a.tr_in = pc.in.put(tr, 6);
+    a.tr = reinterpret_cast<double*>(pc.dout); a.ok = reinterpret_cast<int*>(pc.dout + 64);
     fill_solver_params(&a.sp, p);
-    if ((r = in.flush(c->stream)) < 0) return r;
-    pp.mark(1);
-    hipLaunchKernelGGL(minimize_reproj_kernel, dim3(1), dim3(REFIT_THREADS), 0, c->stream, a);
+    VISO_TRY(pc.sent());
+    hipLaunchKernelGGL(minimize_reproj_kernel, dim3(1), dim3(REFIT_THREADS), 0, pc.s, a);
     HIP_TRY(hipGetLastError());
-    pp.mark(2);
-    PlainSignal sig_;
-    if ((r = plain_signal_next(c, &sig_)) < 0) return r;
-    if ((r = plain_blit(c->stream, dout, hout, 32, nullptr, 0, 0, &sig_)) < 0) return r;
-    pp.wait_begin();
-    if ((r = plain_signal_wait(c, c->stream, sig_.seq)) < 0) return r;
-    pp.wait_end();
-    memcpy(tr, hout, sizeof(double) * 6);
-    const int ok = *reinterpret_cast<const int*>(hout + 64);
-    pp.mark(3);
+    pc.launched();
+    VISO_TRY(pc.fetch(32));
+    VISO_TRY(pc.wait());
+    memcpy(tr, pc.hout, sizeof(double) * 6);
+    const int ok = *reinterpret_cast<const int*>(pc.hout + 64);
+    pc.done();
     return ok ? 1 : 0;
 }
 
@@ -876,40 +864,27 @@ extern "C" int viso_get_inliers(const double* X, const double* obs, int m, const
     }
     *n_inliers = 0;
     if (m == 0) { if (rms) *rms = NAN; return VISO_OK; }
-    PlainLock lk;
-    viso_ctx* c = viso_default_ctx();
-    if (!c) return VISO_ERR_HIP;
-    HIP_TRY(hipSetDevice(c->device));
-    PlainProf pp(VISO_PLAIN_GET_INLIERS, c->stream);
-    int r;
-    PlainStage in;   // ONE upload: X | obs | tr; ONE read-back: {n, rms} | inliers[m]
-    if ((r = in.begin(c, PlainStage::need(sizeof(double) * 3 * (size_t)m) + PlainStage::need(sizeof(double) * 4 * (size_t)m) + PlainStage::need(64))) < 0) return r;
-    char *dout, *hout;
-    const size_t out_bytes = 64 + sizeof(int) * (size_t)m;
-    if ((r = ctx_scratch(c, SLOT_PLAIN_OUT, out_bytes, (void**)&dout)) < 0) return r;
-    if ((r = ctx_pinned(c, 1, out_bytes, &hout)) < 0) return r;
+    PlainCall pc;   // inputs: X | obs | tr; result: {n, rms} | inliers[m]
+    VISO_TRY(pc.begin(VISO_PLAIN_GET_INLIERS));
+    VISO_TRY(pc.inputs(PlainStage::need(sizeof(double) * 3 * (size_t)m) + PlainStage::need(sizeof(double) * 4 * (size_t)m) + PlainStage::need(64)));
+    VISO_TRY(pc.result(64 + sizeof(int) * (size_t)m, true));
     GnArgs a{};
-    a.X = in.put(X, 3 * (size_t)m); a.obs = in.put(obs, 4 * (size_t)m); a.m = m; a.ld = m;
-    a.tr_in = in.put(tr, 6);
-    a.n_inl = reinterpret_cast<int*>(dout); a.rms = reinterpret_cast<double*>(dout + 8); a.inl = reinterpret_cast<int*>(dout + 64);
+    a.X = pc.in.put(X, 3 * (size_t)m); a.obs = pc.in.put(obs, 4 * (size_t)m); a.m = m; a.ld = m;
+    a.tr_in = pc.in.put(tr, 6);
+    a.n_inl = reinterpret_cast<int*>(pc.dout); a.rms = reinterpret_cast<double*>(pc.dout + 8); a.inl = reinterpret_cast<int*>(pc.dout + 64);
     fill_solver_params(&a.sp, p);
-    if ((r = in.flush(c->stream)) < 0) return r;
-    pp.mark(1);
-    hipLaunchKernelGGL(get_inliers_kernel, dim3(1), dim3(REFIT_THREADS), 0, c->stream, a);
+    VISO_TRY(pc.sent());
+    hipLaunchKernelGGL(get_inliers_kernel, dim3(1), dim3(REFIT_THREADS), 0, pc.s, a);
     HIP_TRY(hipGetLastError());
-    pp.mark(2);
-    PlainSignal sig_;
-    if ((r = plain_signal_next(c, &sig_)) < 0) return r;
-    if ((r = plain_blit(c->stream, dout, hout, 16, a.n_inl, 1, m, &sig_)) < 0) return r;
-    pp.wait_begin();
-    if ((r = plain_signal_wait(c, c->stream, sig_.seq)) < 0) return r;
-    pp.wait_end();
-    const int n = *reinterpret_cast<const int*>(hout);
+    pc.launched();
+    VISO_TRY(pc.fetch(16, a.n_inl, 1, m));
+    VISO_TRY(pc.wait());
+    const int n = *reinterpret_cast<const int*>(pc.hout);
     if (n < 0 || n > m) { viso_set_error("viso_get_inliers: device returned %d inliers of %d points", n, m); return VISO_ERR_HIP; }
-    if (n > 0) memcpy(inliers, hout + 64, sizeof(int) * (size_t)n);
+    if (n > 0) memcpy(inliers, pc.hout + 64, sizeof(int) * (size_t)n);
     *n_inliers = n;
-    if (rms) memcpy(rms, hout + 8, sizeof(double));
-    pp.mark(3);
+    if (rms) memcpy(rms, pc.hout + 8, sizeof(double));
+    pc.done();
     return VISO_OK;
 }
 
@@ -959,67 +934,55 @@ extern "C" int viso_ransac_minimize_reproj(const double* X, const double* obs, i
     if (samples)
         for (int i = 0; i < 3 * iters; ++i)
             if (samples[i] < 0 || samples[i] >= m) { viso_set_error("viso_ransac_minimize_reproj: sample index out of range"); return VISO_ERR_ARG; }
-    PlainLock lk;
-    viso_ctx* c = viso_default_ctx();
-    if (!c) return VISO_ERR_HIP;
-    HIP_TRY(hipSetDevice(c->device));
-    PlainProf pp(VISO_PLAIN_RANSAC, c->stream);
+    PlainCall pc;   // inputs: X | obs | samples | {m} | the item; result: {kept, ok, n_inl} | tr[6] | inliers[m]
+    VISO_TRY(pc.begin(VISO_PLAIN_RANSAC));
+    viso_ctx* c = pc.c;
     {   // the frame's stereo call may have solved exactly this problem already (plain.hip)
         int ret = 0;
         if (plain_try_ransac(c, X, obs, m, best_tr, best_inl, n_inl, p, samples, seed, frame, &ret)) return ret;
     }
-    int r;
-    // ONE upload: X | obs | samples | {m} | the item; ONE read-back: {kept, ok, n_inl} | tr[6] | inliers[m]
-    PlainStage in;
-    if ((r = in.begin(c, PlainStage::need(sizeof(double) * 3 * (size_t)m) + PlainStage::need(sizeof(double) * 4 * (size_t)m) +
-                         PlainStage::need(sizeof(int) * 3 * (size_t)(iters + 1)) + PlainStage::need(16) + PlainStage::need(sizeof(SolverItem)))) < 0) return r;
-    char *dout, *hout;
-    const size_t out_bytes = 128 + sizeof(int) * (size_t)m;
-    if ((r = ctx_scratch(c, SLOT_PLAIN_OUT, out_bytes, (void**)&dout)) < 0) return r;
-    if ((r = ctx_pinned(c, 1, out_bytes, &hout)) < 0) return r;
+    VISO_TRY(pc.inputs(PlainStage::need(sizeof(double) * 3 * (size_t)m) + PlainStage::need(sizeof(double) * 4 * (size_t)m) +
+                       PlainStage::need(sizeof(int) * 3 * (size_t)(iters + 1)) + PlainStage::need(16) + PlainStage::need(sizeof(SolverItem))));
+    VISO_TRY(pc.result(128 + sizeof(int) * (size_t)m, true));
+    char *dout = pc.dout, *hout = pc.hout;
     double* dtrh; int *dhyp, *dqueue;
-    if ((r = ctx_scratch(c, SLOT_HYP_WORDS, sizeof(int) * (4 + 2 * (size_t)iters), (void**)&dhyp)) < 0) return r;
-    if ((r = ctx_scratch(c, SLOT_HYP_TR, sizeof(double) * 6 * (size_t)(iters + 1), (void**)&dtrh)) < 0) return r;
+    VISO_TRY(ctx_scratch(c, SLOT_HYP_WORDS, sizeof(int) * (4 + 2 * (size_t)iters), (void**)&dhyp));
+    VISO_TRY(ctx_scratch(c, SLOT_HYP_TR, sizeof(double) * 6 * (size_t)(iters + 1), (void**)&dtrh));
     // undecided-hypothesis list, then the triples in use
-    if ((r = ctx_scratch(c, SLOT_RANSAC_QUEUE, sizeof(int) * (2 + 4 * (size_t)iters + 3), (void**)&dqueue, true)) < 0) return r;
+    VISO_TRY(ctx_scratch(c, SLOT_RANSAC_QUEUE, sizeof(int) * (2 + 4 * (size_t)iters + 3), (void**)&dqueue, true));
     SolverItem it{};
-    it.X = in.put(X, 3 * (size_t)m); it.obs = in.put(obs, 4 * (size_t)m); it.ld = m; it.frame = frame;
-    it.samples = samples ? in.put(samples, 3 * (size_t)iters) : nullptr;
+    it.X = pc.in.put(X, 3 * (size_t)m); it.obs = pc.in.put(obs, 4 * (size_t)m); it.ld = m; it.frame = frame;
+    it.samples = samples ? pc.in.put(samples, 3 * (size_t)iters) : nullptr;
     const int hm[4] = {m, 0, 0, 0};
-    it.m_ptr = in.put(hm, 4);
+    it.m_ptr = pc.in.put(hm, 4);
     it.samp_h = dqueue + 2 + iters;
     it.tr_h = dtrh; it.ok_h = dhyp; it.cnt_h = dhyp + iters;
-    if ((r = ctx_scratch(c, SLOT_RANSAC_ROT, viso_rot_bytes(iters), (void**)&it.rot)) < 0) return r;
+    VISO_TRY(ctx_scratch(c, SLOT_RANSAC_ROT, viso_rot_bytes(iters), (void**)&it.rot));
     // the refit writes kept, ok and n_inl whatever happens (refit_item): nothing of the result block needs a value in advance.
     // best_tr is an input of the reference's function only as the value that STAYS when no hypothesis finds support
     // (src/viso.cpp:1564-1568): the stage says so in `kept` and the caller's array is then left alone, below.
     it.kept = reinterpret_cast<int*>(dout);
     it.ok = reinterpret_cast<int*>(dout) + 1; it.n_inl = reinterpret_cast<int*>(dout) + 2;
     it.tr = reinterpret_cast<double*>(dout + 64); it.inl = reinterpret_cast<int*>(dout + 128);
-    const SolverItem* ditem = in.put(&it, 1);
-    if ((r = in.flush(c->stream)) < 0) return r;
-    pp.mark(1);
+    const SolverItem* ditem = pc.in.put(&it, 1);
+    VISO_TRY(pc.sent());
     SolverParamsDev sp;
     fill_solver_params(&sp, p);
     // one frame's 50 hypotheses are ONE wave of the lane-per-hypothesis kernel (5 us per iteration): hand over to the
     // wave-per-hypothesis kernel after the first iteration (2.7 us each, all hypotheses side by side) unless a split was asked
     // for (viso_ctx_set_gn_split): 203 -> 183 us per call (tools/dropin_probe.py, GN_SPLIT sweep); same hypotheses bit for bit
-    PlainSignal sig_;
-    if ((r = plain_signal_next(c, &sig_)) < 0) return r;
     RefitMirror mir{};   // the result block and the inliers go into pinned memory from the refit kernel itself, which signals
     mir.res_src = reinterpret_cast<const uint32_t*>(dout); mir.res_dst = reinterpret_cast<uint32_t*>(hout); mir.res_words = 32;
     mir.n_inl = it.n_inl; mir.inl_src = reinterpret_cast<const uint32_t*>(dout + 128); mir.inl_dst = reinterpret_cast<uint32_t*>(hout + 128); mir.max_inl = m;
-    mir.sig = sig_;
-    if ((r = launch_ransac(c->stream, ditem, 1, iters, seed, sp, dqueue, c->gn_split ? c->gn_split : 1, m, &mir)) < 0) return r;
-    pp.mark(2);
-    pp.wait_begin();
-    if ((r = plain_signal_wait(c, c->stream, sig_.seq)) < 0) return r;
-    pp.wait_end();
+    VISO_TRY(pc.signal(&mir.sig));
+    VISO_TRY(launch_ransac(pc.s, ditem, 1, iters, seed, sp, dqueue, c->gn_split ? c->gn_split : 1, m, &mir));
+    pc.launched();
+    VISO_TRY(pc.wait());
     const int* res = reinterpret_cast<const int*>(hout);
     if (res[2] < 0 || res[2] > m) { viso_set_error("viso_ransac_minimize_reproj: device returned %d inliers of %d points", res[2], m); return VISO_ERR_HIP; }
     if (!res[0]) memcpy(best_tr, hout + 64, sizeof(double) * 6);   // kept: in/out like the reference's (:1564-1568)
     *n_inl = res[2];
     if (res[2] > 0) memcpy(best_inl, hout + 128, sizeof(int) * (size_t)res[2]);
-    pp.mark(3);
+    pc.done();
     return res[1] ? 1 : 0;
 }

@@ -42,9 +42,8 @@ int voxel_refuse_overflowed(const char* where, const VoxelHost* h) {
 
 int voxel_create(const char* where, VoxelRegistry& reg, viso_ctx* ctx_or_null, int capacity_log2, int min_disp16, size_t payload_bytes,
                  VoxelHost* h, char** payload) {
-    if (ctx_or_null && !viso_ctx_live(ctx_or_null)) { viso_set_error("%s: not a live context handle", where); return VISO_ERR_ARG; }
-    viso_ctx* c = ctx_or_null ? ctx_or_null : viso_default_ctx();
-    if (!c) return VISO_ERR_HIP;
+    viso_ctx* c;
+    VISO_TRY(ctx_resolve(where, ctx_or_null, &c));
     HIP_TRY(hipSetDevice(c->device));
     const size_t slots = (size_t)1 << capacity_log2;
     const size_t b_keys = 8 * slots, b_payload = payload_bytes * slots, b_stats = 8 * VOXEL_STAT_SETS * VOXEL_STAT_WORDS;

@@ -7,7 +7,9 @@ reused).  The child only saves what the calls returned; this process compares th
 use (the oracle, tests/*_ref.py), with those tests' own comparisons.  A short per-call frame loop of the plain family runs next
 to viso_detect_harris_binned and viso_support_sizes, which also run BETWEEN its calls -- they take the hypothesis slots of the
 RANSAC stage the frame's stereo call has left running -- and must give the matches, inliers and motions of the oracle and of the
-same loop run alone."""
+same loop run alone.  The plain family's six small signalled calls (PlainCall, common.h) run in the same rounds on their direct
+path -- speculation off, so that none is answered from a frame -- at sizes under the floors of the context's blocks (256 bytes of
+scratch, 4096 of pinned memory), then well past 1.5 times the floors, then small again."""
 import functools
 import os
 import subprocess
@@ -53,6 +55,25 @@ BINS = ((16, 2, 2), (40, 4, 2))                 # n_features, nbinx, nbiny: bins
 DISP = dict(num_disp=16, block=5)               # the smallest the parameter checks accept
 SPECKLE = dict(max_size=10, max_diff=16)
 PLAIN_FRAMES, PLAIN_KP, PLAIN_SEED = 10, 64, 5
+SIX_PTS, SIX_MATCH = (6, 3000), (5, 3000)       # the six small plain calls: points of the solver calls, rows of the lists
+
+
+def _six_inputs(i):
+    """The six small plain calls' inputs: keypoints and a match list for collect / triangulate; four lists for match_circle whose
+    every second stereo row closes its circle (lr (i, pr[i]), m11 (i, a[i]), lr_prev (j, pp[j]), m22 (k, b[k]): closed when
+    pp[a[i]] == b[pr[i]]); a solver case."""
+    rng = np.random.default_rng(2000 + i)
+    n, nk = SIX_MATCH[i], SIX_MATCH[i] + 3
+    kp = [rng.uniform(0, 1000, (nk, 2)).astype(np.float32) for _ in range(2)]
+    match = np.stack([rng.integers(0, nk, n), rng.integers(0, nk, n), rng.integers(0, 9999, n)], 1).astype(np.int32)
+    pr, a, pp = rng.permutation(n), rng.permutation(n), rng.permutation(n)
+    b = np.zeros(n, np.int64)
+    b[pr] = (pp[a] + (np.arange(n) % 2)) % n
+    rows = lambda q, t: np.stack([q, t, rng.integers(0, 9999, n)], 1).astype(np.int32)   # noqa: E731
+    idx = np.arange(n)
+    lists = (rows(idx, pr), rows(idx, pp), rows(idx, a), rows(idx, b))   # lr, lr_prev, m11, m22
+    X, obs, tr, param = synth.make_solver_case(90 + i, m=SIX_PTS[i], outlier_frac=0.25 * i, noise=0.2)
+    return {"kp": kp, "match": match, "lists": lists, "solver": (X, obs, tr, param)}
 
 
 @functools.lru_cache(maxsize=None)
@@ -74,6 +95,7 @@ def inputs(i):
     X, obs, tr, param = synth.make_solver_case(70 + i, m=N_PTS[i], outlier_frac=0.0)
     d["pose"] = (X, obs, tr, np.arange(N_PTS[i], dtype=np.int32), param)
     d["window"] = hand([None] + [[(100 * j + r, 100 * (j - 1) + r) for r in range(N_PTS[i])] for j in (1, 2)])
+    d["six"] = _six_inputs(i)
     d["motions"] = np.array([tr] + [tr + rng.normal(0, sd, 6) * np.array([0.05, 0.05, 0.05, 1, 1, 1]) for sd in (1e-4, 1e-2, 0.3) for _ in range(1 + 3 * i)])
     return d
 
@@ -143,6 +165,23 @@ def call_support(i):
     return {"cnt": libviso_amd.support_sizes(X, obs, inputs(i)["motions"], param)}
 
 
+def call_six(i):
+    from libviso_amd import drop_in
+    d = inputs(i)["six"]
+    X, obs, tr, param = d["solver"]
+    drop_in.plain_speculate(False)   # every call goes to the device
+    try:
+        x = libviso_amd.collect_matches(d["kp"][0], d["kp"][1], d["match"])
+        _, circ, pcl, n = libviso_amd.match_circle(*d["lists"])
+        ok, tr_min = libviso_amd.minimize_reproj(X, obs, np.zeros(6), param, np.arange(SIX_PTS[i]))
+        inl, rms = libviso_amd.get_inliers(X, obs, tr, param)
+        rs_ok, rs_tr, rs_inl = libviso_amd.ransac_minimize_reproj(X, obs, param, seed=4, frame=7 + i)
+        return {"x": x, "X": libviso_amd.triangulate_rectified(x, param), "circ": circ, "pcl": pcl, "n": np.int32(n), "ok": np.int32(ok),
+                "tr": tr_min, "inl": inl, "rms": np.float64(rms), "rs_ok": np.int32(rs_ok), "rs_tr": rs_tr, "rs_inl": rs_inl}
+    finally:
+        drop_in.plain_speculate(True)
+
+
 def call_plain(i, alone=False):
     """The reference's loop body over plain_seq() through the plain family, one call per reference function.  Unless `alone`, the two
     direct calls that share the RANSAC stage's hypothesis slots run between the loop's calls, at size i."""
@@ -181,7 +220,7 @@ def call_plain(i, alone=False):
 
 
 ROUND_ROBIN = ("extract", "harris_response", "detect", "subpixel", "rectify", "disparity", "sgm", "speckle", "points", "covariance",
-               "refine", "window", "detect", "support", "detect", "plain")
+               "refine", "window", "detect", "support", "detect", "plain", "six")
 ORDERS = {"round_robin": ROUND_ROBIN, "reverse": ROUND_ROBIN[::-1]}
 CALLS = {name[5:]: fn for name, fn in list(globals().items()) if name.startswith("call_")}
 
@@ -273,6 +312,27 @@ def expect_support(i, got, oracle):
     with np.errstate(all="ignore"):
         want = np.array([len(oracle.get_inliers(X, obs, t, param)[0]) for t in inputs(i)["motions"]])
     assert np.array_equal(got["cnt"], want), got["cnt"] - want
+
+
+def expect_six(i, got, oracle):
+    d = inputs(i)["six"]
+    X, obs, tr, param = d["solver"]
+    x = oracle.collect_matches(d["kp"][0], d["kp"][1], d["match"])
+    assert np.array_equal(got["x"], x) and np.array_equal(got["X"], oracle.triangulate_rectified(x, param))
+    _, circ, pcl, n = oracle.match_circle(*d["lists"])
+    assert n == (SIX_MATCH[i] + 1) // 2 and int(got["n"]) == n and np.array_equal(got["circ"], circ) and np.array_equal(got["pcl"], pcl)
+    ok, tr_min, _ = oracle.minimize_reproj(X, obs, np.zeros(6), param, np.arange(SIX_PTS[i]))
+    assert int(got["ok"]) == ok
+    if ok:
+        assert rel_fro(libviso_amd.tr2mat(got["tr"]), oracle.tr2mat(tr_min)) < POSE_TOL
+    inl, rms = oracle.get_inliers(X, obs, tr, param)
+    assert len(inl) > 0 and np.array_equal(got["inl"], inl) and abs(float(got["rms"]) - rms) <= 1e-12 * max(1, rms)
+    rs_ok, rs_tr, rs_inl = oracle.ransac_minimize_reproj(X, obs, param, seed=4, frame=7 + i)
+    assert int(got["rs_ok"]) == rs_ok and np.array_equal(got["rs_inl"], rs_inl)
+    if rs_ok:
+        assert rel_fro(libviso_amd.tr2mat(got["rs_tr"]), oracle.tr2mat(rs_tr)) < POSE_TOL
+    if i == 1:
+        assert ok and rs_ok and len(rs_inl) > SIX_PTS[i] // 2   # the large case is a real problem, solved
 
 
 @functools.lru_cache(maxsize=None)
