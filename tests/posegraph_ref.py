@@ -319,3 +319,21 @@ def make_graph(rng, n, n_long, noise=0.0, n_priors=1, fixed=(0,), reversed_every
     for k in fixed:
         poses0[k] = truth[k]
     return poses0, fx, np.array(ij, np.int32).reshape(-1, 2), np.array(Z), np.array(info), truth
+
+
+def make_structured(rng, n, edges, fixed=(), noise=0.01, start=0.05):
+    """A graph over loop_truth(n) with exactly the edges listed, in that order ((i, j); i = -1 is a prior on j), measured with
+    `noise`, the fixed nodes at their truth and every other node started `start` (tangent sigma) off its own truth.  The structure
+    -- gaps in the chain, reversed and double edges, which nodes are fixed -- is the caller's list, nothing is drawn.  Returns what
+    make_graph returns."""
+    truth = loop_truth(n)
+    Z, info = [], []
+    for i, j in edges:
+        M = truth[j] if i < 0 else inv_se3(truth[i]) @ truth[j]
+        Z.append(M @ exp_se3(rng.normal(0, noise, 6)) if noise else M)
+        info.append(random_info(rng, 100.0))
+    fx = np.zeros(n, np.int32)
+    fx[list(fixed)] = 1
+    poses0 = np.array([truth[k] if fx[k] else truth[k] @ exp_se3(rng.normal(0, start, 6)) for k in range(n)])
+    return poses0, fx, np.array(edges, np.int32).reshape(-1, 2), np.array(Z), np.array(info), truth
+
